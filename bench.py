@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- range-gates/s of the cosmo_pol hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the result line: `value` and
+`ms_per_step` of that region.  `--dump-outputs DIR` then also writes what the last step left to its caller
+(dump_c2_outputs: finite values, gates without a value flagged in <field>_valid.npy).  Everything else described
+below -- the CPU baselines, the c3 / c4 / c5 extras, the five repeats of the timed region, the host-output, latency
+and roofline figures, the result and gather checks, bench_detail.json and the '#detail ' lines -- runs with `--full`.
 
 Workloads (BASELINE.json `configs`):
 
@@ -44,14 +50,14 @@ Workloads (BASELINE.json `configs`):
   c5 (configs[4])   GPM-DPR Ku (200 x 49 rays) and Ka (200 x 25) swaths over the 2-moment cube
       through RadarOperator.get_GPM_swath.  A step = both swaths; gates = the gates kept (h < 35 km).
 
-At N = 1 with the default workload the line also carries `c3`, `c4_volume_one_gpu` and `c5`:
+With --full, at N = 1 with the default workload the line also carries `c3`, `c4_volume_one_gpu` and `c5`:
 the same script run with --workload c3 / c4 / c5 in child processes after the c2 operator is
 closed (driver-timed like the rest of the run).  At N > 1 with the default workload it carries
 `c4_strong_scaling`: `--workload c4 --gpus N` run by one child process per rank on the same GPUs
 after the c2 part has closed its operator and process group (its `speedup_vs_single_gpu` is the
 strong-scaling figure of north_star's "azimuths sharded, one gather at the end").
 
-OUTPUT (rank 0).  The LAST stdout line is ONE compact JSON object (< 4 KB: `compact_line`, guarded by
+OUTPUT (rank 0; a plain run prints the compact line alone).  With --full, the LAST stdout line is ONE compact JSON object (< 4 KB: `compact_line`, guarded by
 tests/test_bench_cpu.py): metric, value, unit, n_gpus, steps, warmup, ms_per_step, dtype, data,
 config{workload, ...}, roofline{...}, cpu_baseline{...}, value_host_outputs (+ its five repeats),
 c4_speedup_vs_single_gpu, n_ranks_seen_by_rccl.  Everything else -- per-stage tables, notes, the c3 / c4 /
@@ -313,7 +319,8 @@ def compact_line(d):
     if a8:
         r['alg_8d'] = {'bytes_per_launch': a8.get('bytes_per_launch'), 'frac': a8.get('frac'),
                        'void': bool((a8.get('frac') or 0) > 1.0)}
-    out['roofline'] = r
+    if roof:                                          # (a plain run measures no roofline)
+        out['roofline'] = r
     if cpu:
         out['cpu_baseline'] = {k: cpu.get(k) for k in ('value', 'unit', 'cores', 'kind', 'host_cpus')}
         out['cpu_baseline']['sample'] = str(cpu.get('sample', ''))[:200]
@@ -345,7 +352,8 @@ def compact_line(d):
                          if 'error' not in c else {'error': str(c['error'])[:80]})
     if others:
         out['other_configs'] = others
-    out['detail'] = d.get('detail_file', 'bench_detail.json')
+    if d.get('detail_file'):                          # (emit(): a --full run)
+        out['detail'] = d['detail_file']
     out = _r(out)
     # whatever a caller put into `d`: the line stays below the limit (drop the optional parts first)
     for victim in ('other_configs', 'host_outputs_ms_per_sweep_repeats'):
@@ -354,7 +362,8 @@ def compact_line(d):
         out.pop(victim, None)
     if len(json.dumps(out)) >= COMPACT_LIMIT:
         out['config'] = {'workload': out['config']['workload'][:120]}
-        out['roofline'] = {k: out['roofline'].get(k) for k in ('kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')}
+        if 'roofline' in out:
+            out['roofline'] = {k: out['roofline'].get(k) for k in ('kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic')}
     return out
 
 
@@ -386,14 +395,25 @@ def main():
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=None)
     ap.add_argument('--workload', choices=['auto', 'c2', 'c3', 'c4', 'c5'], default='auto',
-                    help="auto: c2 (the metric's configuration; weak scaling at N > 1) followed, at N > 1, by "
-                         "the c4 strong-scaling run as an extra; c4 at N > 1: strong scaling as the main line")
-    ap.add_argument('--repeats', type=int, default=5, help='repeats of the timed region (c2)')
+                    help="auto: c2 (the metric's configuration; weak scaling at N > 1) followed, with --full, by "
+                         "the c3 / c4 / c5 extras (N > 1: the c4 strong-scaling run); c4 at N > 1: strong scaling as the main line")
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='repeats of the timed region (c2; default 1, with --full 5: the median is reported)')
     ap.add_argument('--small', action='store_true', help='small cube / tables (debugging, tests)')
-    ap.add_argument('--cpu-seconds', type=float, default=15.0,
-                    help='budget of the one-core CPU-oracle baseline (0 = skip all CPU legs)')
+    ap.add_argument('--cpu-seconds', type=float, default=None,
+                    help='budget of the one-core CPU-oracle baseline (0 = skip all CPU legs; default 0, with --full 15)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: CPU baselines, the c3 / c4 / c5 workloads (N > 1: the c4 '
+                         'strong-scaling run), host-output and latency figures, rooflines, result checks, and the full '
+                         'result in bench_detail.json and on "#detail " lines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last step to DIR/<name>.npy (c2)')
     ap.add_argument('--cpu-pool-child', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 15.0 if args.full else 0.0
     if args.cpu_pool_child:
         return cpu_pool_child(args)
 
@@ -413,6 +433,8 @@ def main():
         args.warmup = {'c2': 5, 'c3': 3, 'c4': 2, 'c5': 1}[workload]
     if workload in ('c3', 'c5') and world > 1:
         raise SystemExit('--workload %s is a single-GPU extra; the multi-GPU workloads are c4 (strong) and c2 (weak)' % workload)
+    if args.dump_outputs and workload != 'c2':
+        raise SystemExit('--dump-outputs writes the outputs of the c2 step (the default workload)')
     # debugging aids for a one-GPU box: CPOL_BENCH_BACKEND=gloo CPOL_BENCH_ONE_DEVICE=1 runs the
     # N-rank code path with every rank on GPU 0 (never used by the driver)
     backend = os.environ.get('CPOL_BENCH_BACKEND', 'nccl')
@@ -450,10 +472,12 @@ def main():
         op.load_model_arrays(cube['data'], cube['zlevels'], cube['proj_info'], cube['resolution'])
     op._ctx.synchronize()
     t_stage = time.time() - t0
-    t0 = time.time()
-    op._ctx.prepare()
-    op._ctx.synchronize()
-    t_rebuild = time.time() - t0                      # ~0: the tables exist (built inside set_lut)
+    t_rebuild = None
+    if args.full:
+        t0 = time.time()
+        op._ctx.prepare()
+        op._ctx.synchronize()
+        t_rebuild = time.time() - t0                  # ~0: the tables exist (built inside set_lut)
     # lanes: contexts forked from the operator's (shared cube / tables, own stream and work
     # buffers).  They keep the library's own non-blocking streams, created back to back before
     # any other stream of the process so that each gets its own hardware queue (measured:
@@ -494,7 +518,7 @@ def main():
         if cpu_res is not None:
             out['cpu_baseline'] = cpu_res
             out['gpu_over_cpu_core'] = out['value'] / cpu_res['value']
-    extras = args.workload == 'auto' and not os.environ.get('CPOL_BENCH_NO_EXTRAS')
+    extras = args.full and args.workload == 'auto' and not os.environ.get('CPOL_BENCH_NO_EXTRAS')
     port = [None]
     if world > 1:
         if extras:                                    # a rendezvous port for the c4 run that follows
@@ -541,7 +565,10 @@ def main():
             if args.cpu_seconds > 0 and cpu_res is not None and workload == 'c2':
                 # the fork-pool legs, last of all (time-boxed; the line never waits longer than the limit)
                 out['cpu_baseline']['all_cores'] = cpu_baseline_pool(workload, args.small)
-        emit(out)
+        if args.full:
+            emit(out)
+        else:                                         # a plain run: the result line alone
+            print(json.dumps(compact_line(out)), flush=True)
 
 
 def child_run(workload, flags, env=None, quiet=False, timeout=600):
@@ -551,7 +578,7 @@ def child_run(workload, flags, env=None, quiet=False, timeout=600):
     strong-scaling run, every rank starting its own child (`quiet`: a rank whose child prints nothing)."""
     import subprocess
     import tempfile
-    cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload] + (flags if '--cpu-seconds' in flags else flags + ['--cpu-seconds', '0'])
+    cmd = [sys.executable, os.path.abspath(__file__), '--workload', workload, '--full'] + (flags if '--cpu-seconds' in flags else flags + ['--cpu-seconds', '0'])
     t0 = time.time()
     fd, detail = tempfile.mkstemp(prefix='cpol_bench_%s_' % workload, suffix='.json')
     os.close(fd)
@@ -782,6 +809,43 @@ def run_c2(env):
     gates_per_sweep = world * n_rays * n_gates
     gates_per_step = sweeps_per_step * gates_per_sweep
     value = gates_per_step * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_c2_outputs(args.dump_outputs, slabs, rvel_slabs, els, counter[0], n_buf, n_cycle, rank, sweeps_per_step)
+    out = {
+        'metric': 'range-gates/sec', 'value': value, 'unit': 'gates/s',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': 1e3 * elapsed / args.steps, 'ms_per_sweep': 1e3 * elapsed / args.steps / sweeps_per_step,
+        'sweeps_per_step': sweeps_per_step, 'ms_per_cycle_of_8_sweeps': 1e3 * elapsed / args.steps / cycles_per_step,
+        'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+        'value_definition': 'v2 (round 4 on): sweeps at 8 elevations in turn (round 6: 80 per step), inputs and outputs resident in HBM; '
+                            'value_host_outputs = the SURVEY 8(d) step on a repeated scan geometry (round 6: all 15 arrays '
+                            'delivered complete, 11 copied per sweep: 52 B per gate); value_host_outputs_new_geometry = a new geometry every step '
+                            '(v1: `value` in rounds 1-3, `value_host_outputs` in rounds 4-5)',
+        'config': {'workload': 'c2: step = %d sweeps per GPU (%d cycles of 8 elevations) of the 360-az x 500-gate C-band PPI (R+S+G 1-mom, 1 sub-beam), '
+                               'inputs and outputs resident in HBM; synthetic %s cube; each sweep = one cpol_run_sweep at one of '
+                               '8 elevations (1.0 + 0.05 k deg, k = (sweep + rank) mod 8; per-ray constants on the host and '
+                               'table sets on the device before the timed region), every kernel of the launch sequence, the '
+                               '10 radar fields (9 float32 observables + the float64 radial velocity) left in HBM; the SURVEY 8(d) '
+                               'step with host outputs: value_host_outputs%s'
+                               % (sweeps_per_step, cycles_per_step, 'x'.join(map(str, cube['zlevels'].shape)),
+                                  '' if not weak else '; the timed region ends with one all-gather of every rank\'s '
+                                                      'last sweep (its 9 float32 observables, device to device)'),
+                   'rays_per_gpu': n_rays, 'gates_per_ray': n_gates, 'lanes': n_lanes, 'sweeps_per_step': sweeps_per_step,
+                   'parallelism': ('weak scaling: the sweeps of a scan are independent, rank r simulates elevation '
+                                   '(sweep + r) mod 8 with the N = 1 step unchanged, no collective inside a step, ONE '
+                                   'all-gather (RCCL) at the end of the timed region') if weak else 'single GPU',
+                   'small': bool(args.small)},
+        'timed_region_repeats': {'n': len(runs), 'ms_per_step_min': per_step[0],
+                                 'ms_per_step_median': statistics.median(per_step),
+                                 'ms_per_step_max': per_step[-1],
+                                 'note': 'each repeat = exactly `steps` steps between two fences; '
+                                         '`value` and `ms_per_step` are the median repeat'},
+        'host_submit_ms_per_step': 1e3 * t_submit / args.steps,
+        'host_submit_ms_per_sweep': 1e3 * t_submit / args.steps / sweeps_per_step,
+    }
+    if not args.full:                               # a plain run: the headline figure alone
+        return out if rank == 0 else None
     result_check = check_last_sweep(env, slabs, rvel_slabs, els, az, counter[0] - 1, n_buf, n_lanes, n_cycle) if rank == 0 else None
 
     # rank 0 recomputes the last sweep of every rank and compares it with the gathered block, bit for bit
@@ -990,36 +1054,7 @@ def run_c2(env):
             'CPOL_ITAB=0: every item integrated over its 1024 diameter bins by k_psd_uniform (one lane, '
             'isolated) -- the kernel that evaluates the table nodes at staging time and finishes the items '
             'outside the tables; f64-VALU bound: ' + roof['integrating_kernel']['note'])
-    out = {
-        'metric': 'range-gates/sec', 'value': value, 'unit': 'gates/s',
-        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': 1e3 * elapsed / args.steps, 'ms_per_sweep': 1e3 * elapsed / args.steps / sweeps_per_step,
-        'sweeps_per_step': sweeps_per_step, 'ms_per_cycle_of_8_sweeps': 1e3 * elapsed / args.steps / cycles_per_step,
-        'higher_is_better': True,
-        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-        'value_definition': 'v2 (round 4 on): sweeps at 8 elevations in turn (round 6: 80 per step), inputs and outputs resident in HBM; '
-                            'value_host_outputs = the SURVEY 8(d) step on a repeated scan geometry (round 6: all 15 arrays '
-                            'delivered complete, 11 copied per sweep: 52 B per gate); value_host_outputs_new_geometry = a new geometry every step '
-                            '(v1: `value` in rounds 1-3, `value_host_outputs` in rounds 4-5)',
-        'config': {'workload': 'c2: step = %d sweeps per GPU (%d cycles of 8 elevations) of the 360-az x 500-gate C-band PPI (R+S+G 1-mom, 1 sub-beam), '
-                               'inputs and outputs resident in HBM; synthetic %s cube; each sweep = one cpol_run_sweep at one of '
-                               '8 elevations (1.0 + 0.05 k deg, k = (sweep + rank) mod 8; per-ray constants on the host and '
-                               'table sets on the device before the timed region), every kernel of the launch sequence, the '
-                               '10 radar fields (9 float32 observables + the float64 radial velocity) left in HBM; the SURVEY 8(d) '
-                               'step with host outputs: value_host_outputs%s'
-                               % (sweeps_per_step, cycles_per_step, 'x'.join(map(str, cube['zlevels'].shape)),
-                                  '' if not weak else '; the timed region ends with one all-gather of every rank\'s '
-                                                      'last sweep (its 9 float32 observables, device to device)'),
-                   'rays_per_gpu': n_rays, 'gates_per_ray': n_gates, 'lanes': n_lanes, 'sweeps_per_step': sweeps_per_step,
-                   'parallelism': ('weak scaling: the sweeps of a scan are independent, rank r simulates elevation '
-                                   '(sweep + r) mod 8 with the N = 1 step unchanged, no collective inside a step, ONE '
-                                   'all-gather (RCCL) at the end of the timed region') if weak else 'single GPU',
-                   'small': bool(args.small)},
-        'timed_region_repeats': {'n': len(runs), 'ms_per_step_min': per_step[0],
-                                 'ms_per_step_median': statistics.median(per_step),
-                                 'ms_per_step_max': per_step[-1],
-                                 'note': 'each repeat = exactly `steps` steps between two fences; '
-                                         '`value` and `ms_per_step` are the median repeat'},
+    out.update({
         'roofline': roof,
         'stages_ms': {'interp': iso.ms_interp, 'classify': iso.ms_classify,
                       'bucket': iso.ms_bucket, 'psd': iso.ms_psd, 'final': iso.ms_final,
@@ -1030,14 +1065,39 @@ def run_c2(env):
                               'k_scan_rays (`final`: range scans); `bucket` and `psd` hold no kernel'},
         'counters': {'n_subbeam_gates': n_sbg, 'n_valid_items': n_valid,
                      'n_work_units': int(iso.n_work_units), 'n_table_items': int(iso.n_table_items)},
-        'host_submit_ms_per_step': 1e3 * t_submit / args.steps,
-        'host_submit_ms_per_sweep': 1e3 * t_submit / args.steps / sweeps_per_step,
         'gather_check': gather_ok,
         'result_check': None if result_check is None else bool(result_check['ok']),
         'result_check_detail': result_check,
-    }
+    })
     out.update(extra)
     return out
+
+
+def dump_c2_outputs(path, slabs, rvel_slabs, els, n_done, n_buf, n_cycle, rank, sweeps_per_step):
+    """--dump-outputs: the arrays a caller of the c2 step holds after its last step -- the device buffers of the last n_buf
+    sweeps (the step cycles through n_buf of them), read back in the order the sweeps ran: DIR/<field>.npy of shape
+    (sweeps, rays, gates), the nine observables in float32 and RVEL in float64, plus DIR/elevation_deg.npy (one per sweep).
+    A gate without a value (NaN in the product: no signal, below the sensitivity, outside the model domain) is written as 0
+    and flagged in DIR/<field>_valid.npy (float32, 1 where the product holds a finite value), so every dumped array is
+    finite and nothing of the result is lost.  The sweeps and their elevations follow from --steps / --warmup alone, so
+    runs with the same arguments compare."""
+    n_rays, n_gates = rvel_slabs[0].shape
+    per_sweep = n_rays * n_gates * (4 * len(RADAR_FIELDS) + 8 + 4 * (len(RADAR_FIELDS) + 1))      # (values + validity masks)
+    n_keep = max(1, min(n_buf, sweeps_per_step, (64 << 20) // per_sweep))         # (at most 64 MB in all)
+    kept = list(range(n_done - n_keep, n_done))
+    obs = [slabs[k % n_buf].cpu().numpy() for k in kept]
+    fields = {f: np.stack([o[i] for o in obs]) for i, f in enumerate(RADAR_FIELDS)}
+    fields['RVEL'] = np.stack([rvel_slabs[k % n_buf].cpu().numpy() for k in kept])
+    arrays = {}
+    for f, a in fields.items():
+        ok = np.isfinite(a)
+        arrays[f] = np.where(ok, a, 0).astype(a.dtype)
+        arrays[f + '_valid'] = ok.astype(np.float32)
+    arrays['elevation_deg'] = np.array([els[(k + rank) % n_cycle][0] for k in kept], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    print('[bench] wrote %d arrays of the last %d sweeps to %s' % (len(arrays), n_keep, path), file=sys.stderr, flush=True)
 
 
 def roofline(workload, kernel, ms_stage, n_valid, psd_bytes, ms_isolated=None, valu_scale=1.0):

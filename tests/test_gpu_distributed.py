@@ -54,7 +54,7 @@ def _bench_two_ranks(port, *flags):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(port),
            os.path.join(root, 'bench.py'), '--gpus', '2', '--small', '--steps', '2', '--warmup', '1',
-           '--cpu-seconds', '0'] + list(flags)
+           '--cpu-seconds', '0', '--full'] + list(flags)
     return _run_and_read(cmd, env)
 
 
@@ -131,7 +131,7 @@ def _bench_one_rank(*flags, **env_extra):
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', OMP_NUM_THREADS='1', CPOL_BENCH_NO_EXTRAS='1', **env_extra)
     env.pop('CPOL_BENCH_BACKEND', None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--small', '--steps', '3', '--warmup', '1',
-           '--cpu-seconds', '0'] + list(flags)
+           '--cpu-seconds', '0', '--full'] + list(flags)
     return _run_and_read(cmd, env)
 
 

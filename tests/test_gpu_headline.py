@@ -181,3 +181,66 @@ def test_c3_step_vs_oracle_and_blocking_path():
         for f in bench.RADAR_FIELDS + ['RVEL', 'mask', 'lats', 'lons', 'dist', 'heights']:
             assert np.array_equal(one[f], vol[e][f], equal_nan=True), (f, e)
     op.close()
+
+
+def test_plain_bench_run_prints_the_line_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: ONE region of exactly K steps, the result
+    line alone on stdout (the contract's keys, no '#detail ' lines, no side file), and DIR holding the arrays the last step
+    left to its caller: every array finite, a gate without a value written as 0 and flagged in <field>_valid.npy.  Two runs
+    with the same arguments write the same bits, and the last sweep equals the host-output path of its elevation."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from cosmo_pol_amd import RadarOperator
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag in ('a', 'b'):
+        out_dir = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--small', '--steps', '3',
+                            '--warmup', '1', '--dump-outputs', str(out_dir)],
+                           capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, CPOL_BENCH_DETAIL=str(tmp_path / ('detail_%s.json' % tag))))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        rows = r.stdout.splitlines()
+        assert len(rows) == 1, rows[:3]
+        line = json.loads(rows[0])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert line[k] is not None, k
+        assert line['metric'] == 'range-gates/sec' and line['unit'] == 'gates/s' and line['higher_is_better'] is True
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+        sweeps, gates = line['config']['sweeps_per_step'], line['config']['gates_per_ray']
+        assert abs(line['value'] - sweeps * 360 * gates / (line['ms_per_step'] * 1e-3)) <= 1e-4 * line['value']
+        assert not {'detail', 'result_check', 'cpu_baseline', 'roofline', 'other_configs'} & set(line)
+        assert not (tmp_path / ('detail_%s.json' % tag)).exists()
+        arrays = {p[:-4]: np.load(str(out_dir / p)) for p in os.listdir(str(out_dir))}
+        fields = bench.RADAR_FIELDS + ['RVEL']
+        assert set(arrays) == set(fields) | {f + '_valid' for f in fields} | {'elevation_deg'}
+        n_kept = arrays['elevation_deg'].shape[0]
+        assert 1 <= n_kept <= sweeps
+        for f in fields:
+            assert arrays[f].dtype == (np.float64 if f == 'RVEL' else np.float32) and arrays[f].shape == (n_kept, 360, gates), f
+            valid = arrays[f + '_valid']
+            assert valid.dtype == np.float32 and valid.shape == arrays[f].shape and set(np.unique(valid)) <= {0.0, 1.0}, f
+            assert np.all(arrays[f][valid == 0] == 0), f
+        for name, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays['ZH_valid'].any()
+        runs.append(arrays)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k], equal_nan=True), k
+    conf, hyds, cube, luts = bench.make_inputs('c2', True)
+    op = RadarOperator(config=conf, luts=luts, output_variables='only_radar')
+    op.load_model_arrays(cube['data'], cube['zlevels'], cube['proj_info'], cube['resolution'])
+    az = np.arange(0, 360, 1.0)
+    got = runs[0]
+    els = [float(e) for e in got['elevation_deg']]
+    assert all(e in bench.C2_ELEVATIONS[:8] for e in els) and len(set(els)) == len(els)     # (consecutive sweeps of a cycle)
+    for s, el in enumerate(els):                     # every dumped sweep against the host-output path of its elevation
+        host = op.simulate_rays(az, np.full(len(az), el))
+        for f in bench.RADAR_FIELDS + ['RVEL']:
+            ok = np.isfinite(host[f])
+            assert np.array_equal(got[f + '_valid'][s], ok.astype(np.float32)), (f, s)
+            assert np.array_equal(got[f][s], np.where(ok, host[f], 0)), (f, s)
+    op.close()

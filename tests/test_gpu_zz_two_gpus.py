@@ -47,7 +47,7 @@ def _bench_over_rccl(n, port, *flags, **env_extra):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n),
            '--master-addr', '127.0.0.1', '--master-port', str(port),
            os.path.join(root, 'bench.py'), '--gpus', str(n), '--small', '--steps', '3', '--warmup', '1',
-           '--cpu-seconds', '0'] + list(flags)
+           '--cpu-seconds', '0', '--full'] + list(flags)
     return _run_and_read(cmd, env)
 
 

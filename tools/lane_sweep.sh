@@ -6,7 +6,6 @@ for v in "$@"; do
   python - "$var=$v" <<'PY'
 import json, sys
 d = json.loads(open('/tmp/ls.json').read().strip().splitlines()[-1])
-iso = d['roofline'].get('isolated') or {}
-print(sys.argv[1], round(d['value'] / 1e6, 1), 'Mgates/s', round(d['ms_per_step'], 4), 'ms/step; isolated psd', iso.get('avg_stage_ms'), 'total', iso.get('device_total_ms'))
+print(sys.argv[1], round(d['value'] / 1e6, 1), 'Mgates/s', round(d['ms_per_step'], 4), 'ms/step')
 PY
 done

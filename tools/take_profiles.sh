@@ -10,4 +10,4 @@ wl=${2:-c2}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 if [ "$wl" = "c2" ]; then args="--steps 20 --warmup 2 --repeats 1"; else args="--steps 2 --warmup 1"; fi
 # shellcheck disable=SC2086
-CPOL_BENCH_NO_EXTRAS=1 exec "$root/tools/profile_cmd.sh" "${tag}_${wl}" bench.py --workload "$wl" $args --cpu-seconds 0
+CPOL_BENCH_NO_EXTRAS=1 exec "$root/tools/profile_cmd.sh" "${tag}_${wl}" bench.py --workload "$wl" $args --cpu-seconds 0 --full
