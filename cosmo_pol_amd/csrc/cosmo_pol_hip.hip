@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "cpol_device.h"
+#include "cpol_tile.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -2002,6 +2003,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
             rr.radial_res = (float)p->radial_res;
             const size_t lds_terms = (size_t)n_hyd * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES), lds_scan = (size_t)3 * ng * sizeof(float);
             const dim3 rgrid((unsigned)cdiv(ng, 64), (unsigned)n_rays);
+            const dim3 tgrid((unsigned)gate1_tiles(n_rays, ng).n_blocks);      // k_gate1_ray: ray x gate tiles (cpol_tile.h)
             if (g1r == 3) {
                 hipLaunchKernelGGL(k_gate1_ray_scan, rgrid, dim3(64 * n_hyd), lds_terms > lds_scan ? lds_terms : lds_scan, st,
                                    ctx->hs, ctx->its, ca, fa, ga, rr);
@@ -2009,7 +2011,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
                 // (CPOL_EXP_SKIP, timing experiments only -- wrong results: bit 0 the gate interpolation, bit 1 this kernel, bit 2 the scans)
                 static const int exp_skip = getenv("CPOL_EXP_SKIP") ? atoi(getenv("CPOL_EXP_SKIP")) : 0;
                 if (!(exp_skip & 2))
-                hipLaunchKernelGGL(k_gate1_ray, rgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr);
+                hipLaunchKernelGGL(k_gate1_ray, tgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr);
                 if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
                 if (tm_psd) { HIPCHK(hipEventRecord(ctx->ev[EV_BUCKET], st)); HIPCHK(hipEventRecord(ctx->ev[EV_PSD], st)); }
                 if (!(exp_skip & 4))

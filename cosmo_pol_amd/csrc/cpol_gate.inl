@@ -444,16 +444,21 @@ __device__ __forceinline__ void integrate_gamma_item_wave(const double *table, c
 }
 
 // RAY = false: k_gate1_species as described above (grid = ceil(n_rg / 64)).
-// RAY = true (k_gate1_ray): the workgroup's 64 gates are gates [64 bx, 64 bx + 64) of ray `by` (grid = (ceil(n_gates / 64),
-// n_rays)), an item outside its table is integrated on the spot (integrate_gamma_item_wave: no deferred gates, no
-// integrating launch behind this kernel), and the workgroup that finishes LAST of its ray -- a ticket per ray, taken behind
-// a device-scope fence -- runs the ray's three sequential float32 range scans, PHIDP, the attenuated ZDR and the
-// sensitivity cut (the second half of k_final): the whole sweep is k_interp_sweep + this kernel.
+// RAY = true: an item outside its table is integrated on the spot (integrate_gamma_item_wave: no deferred gates, no
+// integrating launch behind this kernel).
+//   k_gate1_ray (TICKET = false): the workgroup's 64 gates are a tile of R neighbouring rays x G gates (cpol_tile.h: 1-D
+//   grid of gate1_tiles().n_blocks; R x G = 64).  Round 7: along 64 gates of ONE ray a wavefront's lanes sat on 4.7-5.3
+//   distinct (slice, panel) blocks on the c2 sweep; neighbouring rays at the same range share T, PSD slope and so the block:
+//   2.3-2.6 on 4 x 16 tiles (profiles/r7_c2_locality.json).  Isolated kernel 27.7 -> 24.0 us, most of it from how the
+//   tiles are dealt over the XCDs (profiles/r7_variants.txt).
+//   k_gate1_ray_scan (TICKET = true): gates [64 bx, 64 bx + 64) of ray `by` (grid = (ceil(n_gates / 64), n_rays)), and the
+//   workgroup that finishes LAST of its ray -- a ticket per ray, taken behind a device-scope fence -- runs the ray's three
+//   sequential float32 range scans, PHIDP, the attenuated ZDR and the sensitivity cut (the second half of k_final).
 #ifndef CPOL_EXP_ONE_BLOCK
 #define CPOL_EXP_ONE_BLOCK 0
 #endif
 #ifndef CPOL_GATE1_TILE_SWIZZLE
-#define CPOL_GATE1_TILE_SWIZZLE 1  // k_gate1_ray: workgroup (x, y) takes gate tile (x + y) mod n_tiles of ray y (0: tile x).  Workgroups go to the 8 XCDs
+#define CPOL_GATE1_TILE_SWIZZLE 1  // k_gate1_ray_scan (k_gate1_ray until round 6; its tiles are dealt by cpol_tile.h now): workgroup (x, y) takes gate tile (x + y) mod n_tiles of ray y (0: tile x).  Workgroups go to the 8 XCDs
                                    // round robin by their linear index, x fastest: with 8 tiles per 500-gate ray tile x of EVERY ray landed on XCD x -- and
                                    // the tiles differ threefold in work (the first two hold no hydrometeor at 1 deg, tile 4 the melting region): the XCDs of the
                                    // empty tiles were idle after 14.6 us of a 31.7-us launch (tools/gate1_trace.py).  Rotated, every XCD ends within 2 us of 27.4
@@ -491,20 +496,32 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     // finishes the 64 gates (the sum over the species in order, get_pol_from_sz, RVEL, mask: the same statements on the same
     // LDS values, whoever runs them).  The only barrier left stands at the start, where every wavefront arrives at once.
     constexpr bool LAST_WAVE = RAY && !TICKET && CPOL_GATE1_LAST_WAVE;
+    // TILED (k_gate1_ray, round 7): the workgroup's 64 gates are a tile of R rays x G gates (cpol_tile.h), 1-D grid; the ticket
+    // form keeps 64 gates of one ray (its scan needs whole rays)
+    constexpr bool TILED = RAY && !TICKET;
+    const int lane = lane_id();
+    int ray_b = 0, gate_b = 0;
+    if (TILED) {
+        int ray0 = 0, gate0 = 0, dray, dgate;
+        if (!gate1_tile_of_block(gate1_tiles(f.n_rays, f.n_gates), blockIdx.x, ray0, gate0)) return;   // (padding: the whole workgroup)
+        gate1_lane_in_tile(lane, dray, dgate);
+        ray_b = ray0 + dray;
+        gate_b = gate0 + dgate;
+    } else if (RAY) {
+        ray_b = (int)blockIdx.y;
+#if CPOL_GATE1_TILE_SWIZZLE
+        // (workgroup (x, y) takes gate tile (x + y) mod n_tiles of ray y, so that every XCD -- workgroups go to the XCDs round robin
+        // by their linear index, x fastest -- sees every range of the ray instead of ONE gate tile of all rays: see the knob)
+        gate_b = (int)((blockIdx.x + blockIdx.y) % gridDim.x) * 64 + lane;
+#else
+        gate_b = (int)blockIdx.x * 64 + lane;
+#endif
+    }
     if (threadIdx.x == 0) { s_lookup = 0; s_done = 0; }
     if (LAST_WAVE) __syncthreads();
-    const int lane = lane_id();
     const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                    // the wavefront's hydrometeor
-    const int ray_b = RAY ? (int)blockIdx.y : 0;
-#if CPOL_GATE1_TILE_SWIZZLE
-    // (workgroup (x, y) takes gate tile (x + y) mod n_tiles of ray y, so that every XCD -- workgroups go to the XCDs round robin
-    // by their linear index, x fastest -- sees every range of the ray instead of ONE gate tile of all rays: see the knob)
-    const int gate_b = (RAY ? (int)((blockIdx.x + blockIdx.y) % gridDim.x) : (int)blockIdx.x) * 64 + lane;
-#else
-    const int gate_b = (int)blockIdx.x * 64 + lane;
-#endif
     const long i0 = RAY ? (long)ray_b * f.n_gates + gate_b : (long)blockIdx.x * 64 + lane;
-    const bool in = RAY ? gate_b < f.n_gates : i0 < a.n_sbg;
+    const bool in = TILED ? ray_b < f.n_rays && gate_b < f.n_gates : RAY ? gate_b < f.n_gates : i0 < a.n_sbg;
     const long n = a.n_sbg;
     const long i = in ? i0 : 0;
     const HydroDev &h = hs.h[j];
@@ -520,8 +537,13 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     // finishing wavefront reads the same word and leaves the slot's LDS columns alone (x + 0.0f = x: the same bits).
     unsigned pmask = ~0u;
 #if CPOL_GATE1_PRESENT
-    if (LAST_WAVE && a.present)
-        pmask = a.present[(long)ray_b * gridDim.x + (gate_b >> 6)];                    // (wave-uniform: one scalar load)
+    if (LAST_WAVE && a.present) {
+        // (the words are per (ray, 64-gate tile): the OR of those the tile's gates lie in, the same in every wavefront)
+        unsigned acc = in ? a.present[(long)ray_b * ((f.n_gates + 63) >> 6) + (gate_b >> 6)] : 0u;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc |= (unsigned)__shfl_xor((int)acc, off);
+        pmask = __builtin_amdgcn_readfirstlane(acc);
+    }
 #endif
     const bool here = (pmask >> j) & 1u;                                               // (wave-uniform)
     const bool inl = in && here;
@@ -894,14 +916,15 @@ __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_
     gate1_species_body<false, false>(hs, its, a, f, g, ScanRayArgs{});
 }
 
-// grid = (ceil(n_gates / 64), n_rays), block = 64 * n_hydro, dynamic LDS = max(n_hydro * 64 * GATE1S_BYTES, 3 * n_gates * 4)
+// grid = gate1_tiles(n_rays, n_gates).n_blocks, block = 64 * n_hydro, dynamic LDS = n_hydro * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES)
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
                                                                                   ScanRayArgs r)
 {
     gate1_species_body<true, false>(hs, its, a, f, g, r);
 }
 
-// the same with the ray's scans inside (the ticket: see gate1_species_body); CPOL_GATE1_RAY=3.  Measured: the agent-scope
+// the same with the ray's scans inside (the ticket: see gate1_species_body); CPOL_GATE1_RAY=3.  grid = (ceil(n_gates / 64), n_rays),
+// dynamic LDS = max(n_hydro * 64 * GATE1S_BYTES, 3 * n_gates * 4).  Measured: the agent-scope
 // release every workgroup needs in front of its ticket costs more than the launch of k_scan_rays saves (profiles/r5_variants.txt)
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray_scan(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
                                                                                        ScanRayArgs r)
