@@ -88,6 +88,22 @@ class Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS]
 
 
+class SubbeamOutputs(C.Structure):
+    """cpol_subbeam_outputs: the sub-beam columns of cpol_interp_subbeams."""
+    _fields_ = [('vals', C.c_void_p), ('mask', C.c_void_p), ('elev', C.c_void_p), ('lats', C.c_void_p),
+                ('lons', C.c_void_p), ('dist', C.c_void_p), ('heights', C.c_void_p), ('q_melt', C.c_void_p),
+                ('fw_melt', C.c_void_p), ('mask_ml', C.c_void_p), ('wgate', C.c_void_p),
+                ('skip_melting', C.c_int32), ('outputs_on_device', C.c_int32)]
+
+
+class Columns(C.Structure):
+    """cpol_columns_t: caller-supplied sub-beam columns of cpol_run_columns."""
+    _fields_ = [('n_vars', C.c_int32), ('inputs_on_device', C.c_int32), ('vals', C.c_void_p),
+                ('mask', C.c_void_p), ('elev', C.c_void_p), ('wgate', C.c_void_p), ('q_melt', C.c_void_p),
+                ('fw_melt', C.c_void_p), ('has_melting', C.c_void_p), ('az_sincos', C.c_void_p),
+                ('sub_w', C.c_void_p), ('nyquist', C.c_void_p), ('sens_thr', C.c_void_p), ('varray', C.c_void_p)]
+
+
 class Counters(C.Structure):
     _fields_ = [('n_subbeam_gates', C.c_int64), ('n_valid_items', C.c_int64),
                 ('n_gates', C.c_int64), ('n_work_units', C.c_int64),
@@ -100,7 +116,7 @@ EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_
            'cpol_get_stream',
            'cpol_synchronize', 'cpol_stage_model', 'cpol_stage_hydro', 'cpol_set_num_hydro',
            'cpol_stage_doppler_weights', 'cpol_stage_spectrum_tables', 'cpol_stage_t_function', 'cpol_prepare',
-           'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_counters',
+           'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_interp_subbeams', 'cpol_run_columns', 'cpol_counters',
            'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free', 'cpol_host_alloc_near',
            'cpol_device_pci_bus_id', 'cpol_mem_info',
            'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math']
@@ -213,6 +229,10 @@ def load_library():
     lib.cpol_run_sweep.restype = C.c_int
     lib.cpol_run_sweep.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(RayTables),
                                    C.POINTER(Outputs)]
+    lib.cpol_interp_subbeams.restype = C.c_int
+    lib.cpol_interp_subbeams.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(RayTables), C.POINTER(SubbeamOutputs)]
+    lib.cpol_run_columns.restype = C.c_int
+    lib.cpol_run_columns.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(Columns), C.POINTER(Outputs)]
     lib.cpol_counters.restype = C.c_int
     lib.cpol_counters.argtypes = [vp, C.POINTER(Counters)]
     lib.cpol_spaceborne_first_gate.restype = C.c_int
@@ -560,6 +580,16 @@ class Context(object):
         self.submitted += 1
         rc = self.lib.cpol_run_sweep(self.h, C.byref(params), C.byref(tables), C.byref(outputs))
         self._check(rc, 'cpol_run_sweep')
+
+    def interp_subbeams(self, params, tables, outputs):
+        self.submitted += 1
+        rc = self.lib.cpol_interp_subbeams(self.h, C.byref(params), C.byref(tables), C.byref(outputs))
+        self._check(rc, 'cpol_interp_subbeams')
+
+    def run_columns(self, params, columns, outputs):
+        self.submitted += 1
+        rc = self.lib.cpol_run_columns(self.h, C.byref(params), C.byref(columns), C.byref(outputs))
+        self._check(rc, 'cpol_run_columns')
 
     def spaceborne_first_gate(self, params, traj, site, n_cand, ceiling_m):
         n = params.n_rays * params.n_vnodes

@@ -140,6 +140,8 @@ struct cpol_ctx {
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
     DevBuf b_out[16], b_szinteg, b_sztotal, b_model, b_ticket, b_mask8;
     DevBuf b_present;                  // k_gate1_ray's sweeps: one word per (ray, 64-gate tile), which hydrometeor slots may have an item there (k_interp_sweep writes, k_gate1_ray reads)
+    DevBuf b_colin;                    // cpol_run_columns with host inputs: the caller's columns on the device, read by k_columns_ingest
+    DevBuf b_xscr, b_xgeo;             // cpol_interp_subbeams: the long-form gate kernel's scratch values, the geometry of every sub-beam
     // last sweep shapes (debug reads)
     long last_n_sbg = 0, last_n_rg = 0;
     int last_n_rays = 0, last_n_gates = 0, last_n_sub = 0, last_n_v = 0, last_n_keys = 0;
@@ -697,7 +699,8 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
                      &ctx->b_vn, &ctx->b_icefirst, &ctx->b_rvel, &ctx->b_proj, &ctx->b_blkranked, &ctx->b_rec, &ctx->b_vmask, &ctx->b_gscan, &ctx->b_defer,
-                     &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8};
+                     &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8,
+                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo};
     for (DevBuf *b : all) free_buf(*b);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
@@ -1310,12 +1313,18 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
     return CPOL_OK;
 }
 
-int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
-                   cpol_outputs *out)
+// The launch sequence of cpol_run_sweep, and its two halves:
+// - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
+//   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
+//   and one vertical node per sub-beam and no ray paths;
+// - cpol_interp_subbeams (sub_out != NULL): the sequence up to and including k_interp_sweep, then the geometry of every
+//   sub-beam (k_interp_export), the 'ml' weights, the melting scheme and the copies to sub_out -- no scattering.
+static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
+                        const cpol_columns_t *cols, cpol_subbeam_outputs *sub_out, cpol_outputs *out)
 {
     if (!ctx) return CPOL_ERR_ARG;
-    if (!p || !t || !out || !ctx->model_staged || ctx->hs.n_hydro < 1 || p->n_rays < 1 ||
-        p->n_gates < 1 || p->n_sub < 1 || p->n_hnodes < 1 || p->n_vnodes < 1 || !t->traj ||
+    if (!p || !t || !out || !(ctx->model_staged || cols) || ctx->hs.n_hydro < 1 || p->n_rays < 1 ||
+        p->n_gates < 1 || p->n_sub < 1 || p->n_hnodes < 1 || p->n_vnodes < 1 || (!t->traj && !cols) ||
         !t->geo || !t->sub_h || !t->sub_v || !t->sub_w) {
         ctx->err = "cpol_run_sweep: model / hydrometeors not staged or bad arguments";
         return CPOL_ERR_ARG;
@@ -1332,7 +1341,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     hipStream_t st = ctx->stream;
     const int n_rays = p->n_rays, ng = p->n_gates, n_sub = p->n_sub;
     const int n_h = p->n_hnodes, n_v = p->n_vnodes;
-    const int n_vars = ctx->model.n_vars, n_hyd = ctx->hs.n_hydro, n_keys = ctx->hs.n_keys;
+    const int n_vars = cols ? cols->n_vars : ctx->model.n_vars, n_hyd = ctx->hs.n_hydro, n_keys = ctx->hs.n_keys;
     const long n_rg = (long)n_rays * ng;
     const long n_sbg = n_rg * n_sub;
     if (n_sbg >= (1L << 31)) { ctx->err = "cpol_run_sweep: too many sub-beam gates in one call"; return CPOL_ERR_ARG; }
@@ -1360,12 +1369,15 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         return CPOL_ERR_ARG;
     }
     const bool cut = p->apply_sensitivity && t->sens_thr;
-    const bool ml = t->sub_smooth != nullptr;
-    if (ml && (!t->ml_filter || t->ml_radius < 0 || t->ml_radius > 64)) {
+    // integration scheme 'ml': per-gate weights, made by k_ml_weights (sweeps) or supplied with the columns
+    const bool ml = cols ? cols->wgate != nullptr : t->sub_smooth != nullptr;
+    const bool ml_tab = ml && !cols;
+    const bool melt_given = cols && cols->q_melt;       // columns with the caller's melting fields
+    if (ml_tab && (!t->ml_filter || t->ml_radius < 0 || t->ml_radius > 64)) {
         ctx->err = "cpol_run_sweep: sub_smooth needs ml_filter / ml_radius";
         return CPOL_ERR_ARG;
     }
-    const long shape[6] = {n_rays, ng, n_sub, n_h, n_v, (ml ? 64 + t->ml_radius * 128L : 0) + (long)mode * 8 + (t->nyquist ? 4 : 0) + (t->site ? 2 : 0) + (cut ? 1 : 0)
+    const long shape[6] = {n_rays, ng, n_sub, n_h, n_v, (ml_tab ? 64 + t->ml_radius * 128L : 0) + (long)mode * 8 + (t->nyquist ? 4 : 0) + (t->site ? 2 : 0) + (cut ? 1 : 0)
                            + (t->varray ? 16 + p->n_vbins * 65536L : 0)};
     void **const views[11] = {&ctx->v_traj_in, &ctx->v_site, &ctx->v_geo, &ctx->v_subh, &ctx->v_subv, &ctx->v_subw,
                               &ctx->v_sens, &ctx->v_nyq, &ctx->v_subsmooth, &ctx->v_mlfilter, &ctx->v_varray};
@@ -1383,7 +1395,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         // pack every table of this sweep into one pinned staging slot, one H2D copy
         struct Item { const void *src; size_t bytes; };
         const Item items[11] = {
-            {t->traj, (size_t)n_rays * n_v * CPOL_TRAJ_STRIDE * sizeof(double)},
+            {t->traj, t->traj ? (size_t)n_rays * n_v * CPOL_TRAJ_STRIDE * sizeof(double) : 0},
             {t->site, t->site ? (size_t)n_rays * CPOL_SITE_STRIDE * sizeof(double) : 0},
             {t->geo, (size_t)n_rays * n_h * CPOL_GEO_STRIDE * sizeof(double)},
             {t->sub_h, (size_t)n_sub * sizeof(int)},
@@ -1391,8 +1403,8 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
             {t->sub_w, (size_t)n_sub * sizeof(double)},
             {cut ? t->sens_thr : nullptr, cut ? (size_t)ng * sizeof(double) : 0},
             {t->nyquist, t->nyquist ? (size_t)n_rays * sizeof(double) : 0},
-            {ml ? t->sub_smooth : nullptr, ml ? (size_t)n_sub * sizeof(int) : 0},
-            {ml ? t->ml_filter : nullptr, ml ? (size_t)(2 * t->ml_radius + 1) * sizeof(double) : 0},
+            {ml_tab ? t->sub_smooth : nullptr, ml_tab ? (size_t)n_sub * sizeof(int) : 0},
+            {ml_tab ? t->ml_filter : nullptr, ml_tab ? (size_t)(2 * t->ml_radius + 1) * sizeof(double) : 0},
             {t->varray, t->varray ? (size_t)p->n_vbins * sizeof(double) : 0},
         };
         size_t total = 0;
@@ -1440,7 +1452,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     // ---- work buffers ----
     // several sub-beams: the ray paths (shared by the horizontal nodes of a vertical node) and the per-ray
     // constants of the geodesic come from k_trajectory instead of once per sub-beam gate
-    const bool ray_prep = n_sub >= CPOL_RAY_PREP_MIN_SUB;
+    const bool ray_prep = n_sub >= CPOL_RAY_PREP_MIN_SUB && !cols;
     const bool prep_paths = ray_prep && n_h > 1 && mode != CPOL_GEOM_HOST_PATHS;
     if (mode == CPOL_GEOM_HOST_PATHS || ctx->keep_debug || prep_paths)
         ENSURE(ctx->b_traj, (size_t)n_rays * n_v * 3 * ng * sizeof(float));
@@ -1450,7 +1462,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     const bool geo_poly = ray_prep && ctx->geo_poly && mode == CPOL_GEOM_GROUND_43 && !t->site;
     // single-beam sweeps (round 5): the one sub-beam takes the polynomials too when its float64 latitude / longitude are not
     // outputs; they belong to the resident table set of the rays and are made once per (version, range grid)
-    const bool poly_single = !ray_prep && ctx->geo_poly && ctx->geo_poly_central && mode == CPOL_GEOM_GROUND_43 && !t->site &&
+    const bool poly_single = !ray_prep && !cols && ctx->geo_poly && ctx->geo_poly_central && mode == CPOL_GEOM_GROUND_43 && !t->site &&
                              (!ctx->keep_debug || ctx->geo_poly_central == 2) && t->version != 0 && !(p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS);
     // (round 6: also when the float64 latitude / longitude are outputs -- the long form then runs for those two arrays alone and
     // the float32 grid coordinates still come from the guarded polynomials: identical calls give identical bits whether or not the
@@ -1570,6 +1582,45 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     // further down would leave the sweep's counter set half used; see counters_dirty)
     if ((size_t)3 * ng * sizeof(float) > 64 * 1024) { ctx->err = "cpol_run_sweep: n_gates too large for the range scans (3 * n_gates floats of LDS)"; return CPOL_ERR_ARG; }
     if (out->mask_sum8 && 2 * n_sub > 127) { ctx->err = "cpol_run_sweep: outputs->mask_sum8 needs 2 * n_sub <= 127 (one byte per gate)"; return CPOL_ERR_ARG; }
+    // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
+    const void *col_src[CPOL_MAX_VARS + 6] = {};
+    size_t col_bytes[CPOL_MAX_VARS + 6] = {};
+    int n_col = 0;
+    if (cols) {
+        const size_t gb = (size_t)n_sbg;
+        for (int v = 0; v < n_vars; ++v) { col_src[n_col] = cols->vals[v]; col_bytes[n_col++] = gb * sizeof(float); }
+        const void *const rest[6] = {cols->mask, cols->elev, ml ? cols->wgate : nullptr, melt_given ? cols->q_melt : nullptr,
+                                     melt_given ? cols->fw_melt : nullptr, melt_given ? cols->has_melting : nullptr};
+        const size_t rest_bytes[6] = {gb, gb * sizeof(float), gb * sizeof(double), 2 * gb * sizeof(float), 2 * gb * sizeof(double),
+                                      (size_t)n_rays * n_sub};
+        for (int k = 0; k < 6; ++k) { col_src[n_col] = rest[k]; col_bytes[n_col++] = rest[k] ? rest_bytes[k] : 0; }
+        if (!cols->inputs_on_device) {
+            size_t total = 0;
+            for (int k = 0; k < n_col; ++k) total += (col_bytes[k] + 255) & ~(size_t)255;
+            ENSURE(ctx->b_colin, total);
+        }
+    }
+    // sub-beam export: the long-form gate kernel's own values / mask / elevation (scratch), the geometry of every sub-beam
+    // (lats, lons, dist, heights, elev) and mask_ml
+    const size_t xa8 = ((size_t)n_sbg * sizeof(double) + 255) & ~(size_t)255, xa4 = ((size_t)n_sbg * sizeof(float) + 255) & ~(size_t)255;
+    const size_t xa1 = ((size_t)n_sbg + 255) & ~(size_t)255;
+    int melt_qr = -1, melt_qs = -1, melt_qg = -1;
+    for (int j = 0; j < n_hyd; ++j) {
+        const cpol_hydro_desc &d = ctx->hs.h[j].d;
+        if (d.q_source != CPOL_Q_MODEL) continue;
+        if (d.rule == CPOL_RULE_RAIN_1MOM) melt_qr = d.var_q;
+        if (d.rule == CPOL_RULE_SNOW_1MOM) melt_qs = d.var_q;
+        if (d.rule == CPOL_RULE_GRAUPEL_1MOM) melt_qg = d.var_q;
+    }
+    const bool sub_melt = sub_out && p->with_melting && !sub_out->skip_melting;
+    if (sub_out) {
+        if (p->with_melting && (melt_qr < 0 || melt_qs < 0 || melt_qg < 0)) {
+            ctx->err = "cpol_interp_subbeams: melting needs 1-moment rain, snow and graupel slots";
+            return CPOL_ERR_ARG;
+        }
+        ENSURE(ctx->b_xscr, (size_t)n_vars * xa4 + xa1 + xa4);
+        ENSURE(ctx->b_xgeo, 2 * xa8 + 3 * xa4 + xa1);
+    }
     if (dop3) {
         ENSURE(ctx->b_beam, (size_t)n_sbg * n_vb * sizeof(float));
     }
@@ -1611,7 +1662,8 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     // launches of the integrating flavours cost more than the two bucket launches they replace (C3 sweep at
     // 3 deg: 203 us this way against 188; the kernel handles them -- CPOL_GATE1=2 forces it, tests do).
     const int gate1_env = ctx->gate1;
-    bool gate1 = gate1_env != 0 && subsum_enabled && n_sub == 1 && !ctx->keep_debug && !dop3 && !ml;
+    // (columns with given melting fields: k_classify's GIVEN form; the single-beam kernels diagnose melting themselves)
+    bool gate1 = gate1_env != 0 && subsum_enabled && n_sub == 1 && !ctx->keep_debug && !dop3 && !ml && !melt_given && !sub_out;
     for (int j = 0; j < n_hyd && gate1; ++j)
         gate1 = ctx->its.t[j].tab != nullptr && (gate1_env == 2 || !ctx->its.t[j].two_d);
     if (gate1) final_inplace = true;       // (k_final's recomputed gates take the table items from their records)
@@ -1666,12 +1718,13 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     const bool want_model = p->integrate_model && out->model_vars;
     // every slot on a table, no debug reads: the gate kernel classifies its gates itself (k_interp_classify,
     // cpol_fused.inl)
-    const bool fused = ctx->fuse_classify != 0 && rare_direct && !gate1 && !ml && !dop3 && !ctx->keep_debug;
+    // (never for columns: the forms that interpolate, k_interp_classify and k_interp_gate1, are replaced by k_columns_ingest)
+    const bool fused = ctx->fuse_classify != 0 && rare_direct && !gate1 && !ml && !dop3 && !ctx->keep_debug && !cols && !sub_out;
     // k_interp_gate1 (CPOL_FUSE_GATE1=1, not the default): the single-beam kernel interpolates its gates too.  Measured: the
     // isolated C2 sweep 95.4 -> 88.6 us (one lane back to back: 70 -> 62 us per sweep), but with three lanes in flight 42.2 ->
     // 44.8 us per sweep, and the Ku swath of config 5 (9 800 rays) 0.93 -> 1.18 ms: at the 3 wavefronts per SIMD k_gate1 needs,
     // the interpolation -- VALU-bound at 5 -- loses more than the saved launch and the 14 MB of vals[] give back.
-    const bool fused_gate1 = ctx->fuse_gate1 != 0 && gate1;
+    const bool fused_gate1 = ctx->fuse_gate1 != 0 && gate1 && !cols;
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
@@ -1681,7 +1734,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     DevBuf *own[O_N];
     for (int k = 0; k < 14; ++k) {
         obytes[k] = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
-        produced[k] = true;
+        produced[k] = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
         own[k] = &ctx->b_out[k];
     }
     obytes[O_RVEL] = (size_t)n_rg * sizeof(double);            produced[O_RVEL] = doppler;    own[O_RVEL] = &ctx->b_rvel;
@@ -1746,7 +1799,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         HIPCHK(hipMemcpyAsync(ctx->b_traj.p, t->paths, (size_t)n_rays * n_v * 3 * ng * sizeof(float),
                               hipMemcpyHostToDevice, st));
     }
-    if (ray_prep || (ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS)) {
+    if (ray_prep || (ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols)) {
         // ray paths + per-ray constants ahead of the sweep kernel (and the parity access to the paths,
         // cpol_debug_read "traj"): same device functions as the in-place evaluation
         const bool paths = mode != CPOL_GEOM_HOST_PATHS && (prep_paths || ctx->keep_debug);
@@ -1807,17 +1860,103 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     ia.poly_scale = (geo_poly || poly_central) ? geo_poly_scale : 0.0;
     ia.poly_central = poly_central ? 1 : 0;
     static const int use_present = getenv("CPOL_GATE1_PRESENT") ? atoi(getenv("CPOL_GATE1_PRESENT")) : 1;
-    if (gate1_ray && use_present && CPOL_GATE1_PRESENT) {
+    if (gate1_ray && use_present && CPOL_GATE1_PRESENT && !cols) {      // (columns: no presence words are written)
         ia.present = (unsigned *)ctx->b_present.p;
         ia.n_pres = n_hyd;
         for (int j = 0; j < n_hyd; ++j) ia.pres_var[j] = ctx->hs.h[j].d.var_q;
     }
     ctx->last_poly_central = ia.poly_central;
     static const int exp_skip_interp = getenv("CPOL_EXP_SKIP") ? (atoi(getenv("CPOL_EXP_SKIP")) & 1) : 0;
-    if (!fused && !fused_gate1 && !exp_skip_interp)
+    if (cols) {
+        // ---- 2'. the caller's columns instead of the interpolation ----
+        const void *src[CPOL_MAX_VARS + 6];
+        size_t off = 0;
+        for (int k = 0; k < n_col; ++k) {
+            src[k] = col_src[k];
+            if (!col_src[k] || cols->inputs_on_device) continue;
+            void *d = (char *)ctx->b_colin.p + off;
+            HIPCHK(hipMemcpyAsync(d, col_src[k], col_bytes[k], hipMemcpyHostToDevice, st));
+            src[k] = d;
+            off += (col_bytes[k] + 255) & ~(size_t)255;
+        }
+        IngestArgs ig{};
+        for (int v = 0; v < n_vars; ++v) ig.src_vals[v] = (const float *)src[v];
+        ig.src_mask = (const signed char *)src[n_vars];
+        ig.src_elev = (const float *)src[n_vars + 1];
+        ig.src_wgate = (const double *)src[n_vars + 2];
+        ig.src_q = (const float *)src[n_vars + 3];
+        ig.src_fw = (const double *)src[n_vars + 4];
+        ig.has_melting = (const signed char *)src[n_vars + 5];
+        ig.vals = (float *)ctx->b_vals.p;
+        ig.mask = (signed char *)ctx->b_mask.p;
+        ig.elev = (float *)ctx->b_elev.p;
+        ig.wgate = ml ? (double *)ctx->b_wgate.p : nullptr;
+        ig.q_melt = (float *)ctx->b_qmelt.p;
+        ig.fw_melt = (double *)ctx->b_fwmelt.p;
+        ig.zero_buf = ia.zero_buf; ig.zero_n = ia.zero_n;
+        ig.zero_buf2 = ia.zero_buf2; ig.zero_n2 = ia.zero_n2;
+        ig.n_sbg = n_sbg; ig.n_vars = n_vars; ig.n_gates = ng;
+        // (a grid-stride pass; at least enough workgroups to clear the counter set)
+        const long blocks = std::max<long>(std::min<long>(cdiv(n_sbg, 256 * 4), 2048), cdiv(cnt_stride, 256));
+        hipLaunchKernelGGL(k_columns_ingest, dim3((unsigned)blocks), dim3(256), 0, st, ig);
+    } else if (!fused && !fused_gate1 && !exp_skip_interp)
     hipLaunchKernelGGL(k_interp_sweep, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st,
                        ctx->model, ia);
     if (tm && !fused && !fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
+    if (sub_out) {
+        // ---- 2''. cpol_interp_subbeams: geometry of every sub-beam, 'ml' weights, melting, copies; no scattering ----
+        InterpArgs ix = ia;
+        char *const xs = (char *)ctx->b_xscr.p, *const xg = (char *)ctx->b_xgeo.p;
+        ix.vals = (float *)xs;
+        ix.mask = (signed char *)(xs + (size_t)n_vars * xa4);
+        ix.elev = (float *)(xs + (size_t)n_vars * xa4 + xa1);
+        ix.zero_buf = nullptr; ix.zero_buf2 = nullptr;
+        ix.coords = nullptr; ix.lats = ix.lons = nullptr; ix.dist = ix.heights = nullptr;
+        ix.present = nullptr;
+        ix.exact_sub = 1;                         // (the long form: float64 latitude / longitude of every sub-beam)
+        ExportArgs xa{};
+        xa.lats = (double *)xg;
+        xa.lons = (double *)(xg + xa8);
+        xa.dist = (float *)(xg + 2 * xa8);
+        xa.heights = (float *)(xg + 2 * xa8 + xa4);
+        xa.elev = (float *)(xg + 2 * xa8 + 2 * xa4);
+        signed char *const mlmask = (signed char *)(xg + 2 * xa8 + 3 * xa4);
+        hipLaunchKernelGGL(k_interp_export, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ix, xa);
+        if (ml) {                                 // (on the values before melting, as in the sweep)
+            MlArgs ma{};
+            ma.vals = (const float *)ctx->b_vals.p;
+            ma.sub_w = (const double *)ctx->v_subw;
+            ma.sub_smooth = (const int *)ctx->v_subsmooth;
+            ma.taps = (const double *)ctx->v_mlfilter;
+            ma.wgate = (double *)ctx->b_wgate.p;
+            ma.n_sbg = n_sbg; ma.n_sub = n_sub; ma.n_gates = ng; ma.radius = t->ml_radius;
+            ma.with_melting = p->with_melting;
+            ma.var_qr = melt_qr; ma.var_qs = melt_qs; ma.var_qg = melt_qg;
+            hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ma);
+        }
+        if (sub_melt)
+            hipLaunchKernelGGL(k_melt_subbeams, dim3((unsigned)cdiv(n_sbg, 256)), dim3(256), 0, st, (float *)ctx->b_vals.p, n_sbg,
+                               melt_qr, melt_qs, melt_qg, (float *)ctx->b_qmelt.p, (double *)ctx->b_fwmelt.p, mlmask);
+        const hipMemcpyKind kind = sub_out->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        struct Cp { void *dst; const void *src; size_t bytes; };
+        const Cp cps[11] = {
+            {sub_out->vals, ctx->b_vals.p, (size_t)n_vars * n_sbg * sizeof(float)},
+            {sub_out->mask, ctx->b_mask.p, (size_t)n_sbg},
+            {sub_out->elev, xa.elev, (size_t)n_sbg * sizeof(float)},
+            {sub_out->lats, xa.lats, (size_t)n_sbg * sizeof(double)},
+            {sub_out->lons, xa.lons, (size_t)n_sbg * sizeof(double)},
+            {sub_out->dist, xa.dist, (size_t)n_sbg * sizeof(float)},
+            {sub_out->heights, xa.heights, (size_t)n_sbg * sizeof(float)},
+            {sub_melt ? sub_out->q_melt : nullptr, ctx->b_qmelt.p, (size_t)2 * n_sbg * sizeof(float)},
+            {sub_melt ? sub_out->fw_melt : nullptr, ctx->b_fwmelt.p, (size_t)2 * n_sbg * sizeof(double)},
+            {sub_melt ? sub_out->mask_ml : nullptr, mlmask, (size_t)n_sbg},
+            {ml ? sub_out->wgate : nullptr, ctx->b_wgate.p, (size_t)n_sbg * sizeof(double)},
+        };
+        for (const Cp &c : cps)
+            if (c.dst) HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, kind, st));
+        HIPCHK(hipGetLastError());
+        return CPOL_OK;
+    }
 
     // ---- 2b. the arguments of the final stage (k_gate1, the single-beam fast path, needs them already) ----
     FinalArgs fa{};
@@ -1958,7 +2097,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         ma.n_sbg = n_sbg; ma.n_sub = n_sub; ma.n_gates = ng; ma.radius = t->ml_radius;
         ma.with_melting = p->with_melting;
         ma.var_qr = ca.var_qr; ma.var_qs = ca.var_qs; ma.var_qg = ca.var_qg;
-        hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ma);
+        if (!cols) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ma);     // (columns: ingested)
         ca.wgate = (const double *)ctx->b_wgate.p;
     }
     // the variables later kernels read: U, V, W (the Doppler terms); all of them for the integrated model variables
@@ -2037,8 +2176,13 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         else hipLaunchKernelGGL((k_gate1<false>), dim3(cdiv(n_rg, CPOL_GATE1_THREADS)), dim3(CPOL_GATE1_THREADS), 0, st,
                                 ctx->hs, ctx->its, ca, fa, ga);
         if (tm && fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
+    } else if (melt_given) {
+        ca.q_melt = (float *)ctx->b_qmelt.p;      // (inputs here: the caller's fields as k_columns_ingest left them)
+        ca.fw_melt = (double *)ctx->b_fwmelt.p;
+        hipLaunchKernelGGL(k_classify<true>, dim3(cdiv(n_sbg, CPOL_CLASSIFY_THREADS)),
+                           dim3(CPOL_CLASSIFY_THREADS), 0, st, ctx->hs, ctx->its, ca);
     } else
-    hipLaunchKernelGGL(k_classify, dim3(cdiv(n_sbg, CPOL_CLASSIFY_THREADS)),
+    hipLaunchKernelGGL(k_classify<false>, dim3(cdiv(n_sbg, CPOL_CLASSIFY_THREADS)),
                        dim3(CPOL_CLASSIFY_THREADS), 0, st, ctx->hs, ctx->its, ca);
     if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
 
@@ -2428,7 +2572,7 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
     const double t_buffers = now_ns();
     ctx->counters_dirty = true;         // until the sequence is queued completely (cleared where sweep_serial advances)
     // graph key: every value that ends up in a kernel argument
-    const bool graphable = ctx->use_graph && dev && !tm_psd && !ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS &&
+    const bool graphable = ctx->use_graph && dev && !tm_psd && !ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out &&
                            !dop3 && reuse && !want_szt && !want_model;
     if (graphable) {
         uint64_t key = 1469598103934665603ull;
@@ -2517,6 +2661,86 @@ int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tab
         return report_domain_error(ctx);
     }
     return CPOL_OK;
+}
+
+int cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
+                   cpol_outputs *out)
+{
+    return run_sequence(ctx, p, t, nullptr, nullptr, out);
+}
+
+int cpol_interp_subbeams(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t, cpol_subbeam_outputs *so)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    if (!p || !t || !so || so->outputs_on_device < 0 || so->outputs_on_device > 1) {
+        ctx->err = "cpol_interp_subbeams: bad arguments (outputs_on_device is 0 or 1)";
+        return CPOL_ERR_ARG;
+    }
+    cpol_sweep_params q = *p;
+    q.outputs_on_device = so->outputs_on_device;
+    q.apply_sensitivity = 0;
+    q.integrate_model = 0;
+    cpol_outputs none{};
+    return run_sequence(ctx, &q, t, nullptr, so, &none);
+}
+
+int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *c, cpol_outputs *out)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
+        !c->vals || !c->elev || !c->sub_w) {
+        ctx->err = "cpol_run_columns: bad shapes, or vals / elev / sub_w missing";
+        return CPOL_ERR_ARG;
+    }
+    if ((long)p->n_rays * p->n_sub * p->n_gates >= (1L << 31)) {
+        ctx->err = "cpol_run_columns: too many sub-beam gates in one call";
+        return CPOL_ERR_ARG;
+    }
+    for (int v = 0; v < c->n_vars; ++v)
+        if (!c->vals[v]) { ctx->err = "cpol_run_columns: a variable pointer of cols->vals is NULL"; return CPOL_ERR_ARG; }
+    // every variable index of the staged descriptors must lie inside the caller's columns
+    for (int j = 0; j < ctx->hs.n_hydro; ++j) {
+        const cpol_hydro_desc &d = ctx->hs.h[j].d;
+        if (d.var_t < 0 || d.var_t >= c->n_vars || (d.q_source == CPOL_Q_MODEL && (d.var_q < 0 || d.var_q >= c->n_vars)) ||
+            (d.rule == CPOL_RULE_TWO_MOMENT && (d.var_qn < 0 || d.var_qn >= c->n_vars))) {
+            ctx->err = "cpol_run_columns: a staged hydrometeor reads a variable beyond cols->n_vars";
+            return CPOL_ERR_ARG;
+        }
+    }
+    if (p->simulate_doppler && !c->az_sincos) { ctx->err = "cpol_run_columns: simulate_doppler needs cols->az_sincos"; return CPOL_ERR_ARG; }
+    if (c->q_melt && (!c->fw_melt || !p->with_melting)) {
+        ctx->err = "cpol_run_columns: cols->q_melt needs cols->fw_melt and with_melting";
+        return CPOL_ERR_ARG;
+    }
+    // the per-ray tables of cpol_run_sweep for these columns: one horizontal and one vertical node per sub-beam, the
+    // azimuth's sin / cos where the geo table has them (RVEL), no ray paths
+    cpol_sweep_params q = *p;
+    q.n_hnodes = q.n_vnodes = p->n_sub;
+    q.geometry_mode = CPOL_GEOM_GROUND_43;
+    std::vector<double> geo;
+    std::vector<int32_t> ident;
+    try {
+        geo.assign((size_t)p->n_rays * p->n_sub * CPOL_GEO_STRIDE, 0.0);
+        ident.resize((size_t)p->n_sub);
+    } catch (...) {
+        ctx->err = "cpol_run_columns: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    if (c->az_sincos)
+        for (size_t i = 0; i < (size_t)p->n_rays * p->n_sub; ++i) {
+            geo[i * CPOL_GEO_STRIDE] = c->az_sincos[2 * i];
+            geo[i * CPOL_GEO_STRIDE + 1] = c->az_sincos[2 * i + 1];
+        }
+    for (int s = 0; s < p->n_sub; ++s) ident[s] = s;
+    cpol_ray_tables_t t{};
+    t.geo = geo.data();
+    t.sub_h = ident.data();
+    t.sub_v = ident.data();
+    t.sub_w = c->sub_w;
+    t.sens_thr = c->sens_thr;
+    t.nyquist = c->nyquist;
+    t.varray = c->varray;
+    return run_sequence(ctx, &q, &t, c, nullptr, out);
 }
 
 int cpol_spaceborne_first_gate(cpol_ctx *ctx, const cpol_sweep_params *p, const double *traj,

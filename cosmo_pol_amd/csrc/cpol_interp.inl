@@ -681,8 +681,16 @@ __device__ __forceinline__ double asin_small(double x)
 // KEEP = true (k_interp_classify): the values of a status-0 gate stay with the thread -- sv[v * blockDim.x],
 // its column of the workgroup's LDS array -- and the caller stores what later kernels read; of the NaN of the
 // other gates only the variables in a.store_mask are written.
-template <bool KEEP>
-__device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &a, float *sv, long &sbg_out, float &elev_out)
+// EXPORT (k_interp_export, cpol_interp_subbeams): the geometry of EVERY sub-beam gate to x -- float64 latitude /
+// longitude (the long form: run with a.exact_sub), distance, height, the elevation before folding.
+struct ExportArgs {
+    double *lats, *lons;        // [n_sbg]
+    float *dist, *heights, *elev;
+};
+
+template <bool KEEP, bool EXPORT = false>
+__device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &a, float *sv, long &sbg_out, float &elev_out,
+                                           const ExportArgs *x = nullptr)
 {
     // ---- which (ray, sub-beam, block of gates) this workgroup takes ----
     // The hardware deals workgroups to the 8 XCDs round robin by their linear index, and every XCD has its own L2.  With
@@ -737,6 +745,10 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
             if (!KEEP || ((a.store_mask >> v) & 1u)) a.vals[(long)v * n_sbg + sbg] = qnan;
         a.elev[sbg] = 0.0f;
         if (a.coords) { a.coords[2 * sbg] = qnan; a.coords[2 * sbg + 1] = qnan; }
+        if (EXPORT) {
+            x->lats[sbg] = __builtin_nan(""); x->lons[sbg] = __builtin_nan("");
+            x->dist[sbg] = qnan; x->heights[sbg] = qnan; x->elev[sbg] = e32;
+        }
         if (sub == a.central_sub) {
             const long rg = (long)ray * a.n_gates + gate;
             if (a.lats) a.lats[rg] = __builtin_nan("");
@@ -928,6 +940,10 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
         a.elev[sbg] = e32;
         elev_out = e32;
         if (a.coords) { a.coords[2 * sbg] = rlat; a.coords[2 * sbg + 1] = rlon; }
+        if (EXPORT) {
+            x->lats[sbg] = __builtin_nan(""); x->lons[sbg] = __builtin_nan("");
+            x->dist[sbg] = s32; x->heights[sbg] = h32; x->elev[sbg] = e32;
+        }
         if (sub == a.central_sub) {         // no stale data in the caller's buffers
             const long rg = (long)ray * a.n_gates + gate;
             if (a.lats) a.lats[rg] = __builtin_nan("");
@@ -975,6 +991,10 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     ITRACE(itr, 5);                                        // the variables gathered and interpolated (KEEP: in LDS)
     a.mask[sbg] = (signed char)g.status;
 
+    if (EXPORT) {
+        x->lats[sbg] = lat_deg; x->lons[sbg] = lon_deg;
+        x->dist[sbg] = s32; x->heights[sbg] = h32; x->elev[sbg] = e32;
+    }
     // elevation folded into [0, 90] for the LUT (doppler_scatter.py:173-176, in place)
     if (e32 > 90.0f) e32 = 180.0f - e32;
     if (e32 < 0.0f) e32 = -e32;
@@ -1022,4 +1042,83 @@ __global__ __launch_bounds__(256) CPOL_INTERP_ATTR void k_interp_sweep(ModelDev 
     long sbg;
     float e;
     interp_gate<false>(m, a, nullptr, sbg, e);
+}
+
+// The geometry of every sub-beam gate (cpol_interp_subbeams): the gate kernel in its long form (a.exact_sub), values into a
+// scratch array -- the exported values are k_interp_sweep's, whose forms the sweep takes
+__global__ __launch_bounds__(256) void k_interp_export(ModelDev m, InterpArgs a, ExportArgs x)
+{
+    long sbg;
+    float e;
+    interp_gate<false, true>(m, a, nullptr, sbg, e, &x);
+}
+
+// ---- caller-supplied sub-beam columns (cpol_run_columns) ----
+struct IngestArgs {
+    const float *src_vals[CPOL_MAX_VARS];   // [n_vars] per-gate columns of the caller (never written)
+    const signed char *src_mask;            // or NULL: 0
+    const float *src_elev;
+    const double *src_wgate;                // scheme 'ml' or NULL
+    const float *src_q;                     // [2][n_sbg] given QmS_v, QmG_v or NULL
+    const double *src_fw;                   // [2][n_sbg] given fwet_mS, fwet_mG
+    const signed char *has_melting;         // [n_rays * n_sub] or NULL (all 1)
+    float *vals;                            // the context's work buffers
+    signed char *mask;
+    float *elev;
+    double *wgate;
+    float *q_melt;
+    double *fw_melt;
+    int *zero_buf, *zero_buf2;              // as InterpArgs: the NEXT sequence's counters
+    int zero_n, zero_n2;
+    long n_sbg;
+    int n_vars, n_gates;
+};
+
+// one pass of 16-byte loads / stores over a byte range (4- or 1-byte words when the two ends are not aligned alike)
+__device__ __forceinline__ void stream_copy(void *dst, const void *src, long nbytes, long tid, long nthr)
+{
+    char *d = (char *)dst;
+    const char *s = (const char *)src;
+    const uintptr_t al = (uintptr_t)d | (uintptr_t)s;
+    long done = 0;
+    if ((al & 15) == 0) {
+        const long n16 = nbytes >> 4;
+        for (long i = tid; i < n16; i += nthr) ((uint4 *)d)[i] = ((const uint4 *)s)[i];
+        done = n16 << 4;
+    } else if ((al & 3) == 0) {
+        const long n4 = nbytes >> 2;
+        for (long i = tid; i < n4; i += nthr) ((unsigned *)d)[i] = ((const unsigned *)s)[i];
+        done = n4 << 2;
+    }
+    for (long i = done + tid; i < nbytes; i += nthr) d[i] = s[i];
+}
+
+// Copies the columns into the work buffers (k_classify melts vals[] in place: never the caller's memory) and takes over
+// the per-sequence duties of k_interp_sweep, which it replaces: the next sequence's counters are cleared here.  While
+// copying: the elevation folded into [0, 90] (doppler_scatter.py:173-176, quirk Q8), the given melting fields of a
+// sub-beam without melting zeroed (:160-165).
+__global__ __launch_bounds__(256) void k_columns_ingest(IngestArgs a)
+{
+    clear_counters(a.zero_buf, a.zero_n, a.zero_buf2, a.zero_n2);
+    const long nthr = (long)gridDim.x * blockDim.x;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long n = a.n_sbg;
+    for (int v = 0; v < a.n_vars; ++v)
+        stream_copy(a.vals + (long)v * n, a.src_vals[v], n * (long)sizeof(float), tid, nthr);
+    if (a.src_wgate) stream_copy(a.wgate, a.src_wgate, n * (long)sizeof(double), tid, nthr);
+    if (a.src_mask) stream_copy(a.mask, a.src_mask, n, tid, nthr);
+    for (long i = tid; i < n; i += nthr) {
+        if (!a.src_mask) a.mask[i] = 0;
+        float e = a.src_elev[i];
+        if (e > 90.0f) e = 180.0f - e;
+        if (e < 0.0f) e = -e;
+        a.elev[i] = e;
+        if (a.src_q) {
+            const bool melt = !a.has_melting || a.has_melting[i / a.n_gates] != 0;
+            a.q_melt[i] = melt ? a.src_q[i] : 0.0f;
+            a.q_melt[n + i] = melt ? a.src_q[n + i] : 0.0f;
+            a.fw_melt[i] = melt ? a.src_fw[i] : 0.0;
+            a.fw_melt[n + i] = melt ? a.src_fw[n + i] : 0.0;
+        }
+    }
 }

@@ -506,6 +506,43 @@ __device__ __forceinline__ void classify_item(const HydroDev &h, const ItabDev &
 #else
 #define CPOL_CLASSIFY_ATTR
 #endif
+// The melting scheme of one sub-beam gate (melting.py:34-83), float32 arithmetic as NumPy evaluates it: QmS_v, QmG_v,
+// fwet_mS, fwet_mG, and QR / QS / QG zeroed in vals[] where it melted
+__device__ __forceinline__ void melt_diagnose(float *vals, long n, long i, int var_qr, int var_qs, int var_qg,
+                                              float &qms, float &qmg, double &fws, double &fwg)
+{
+    float qr = vals[var_qr * n + i], qs = vals[var_qs * n + i], qg = vals[var_qg * n + i];
+    float qsg = qs + qg;
+    if (qr > 0.f && qsg > 0.f) {
+        qms = qs + qr * (qs / qsg);
+        qmg = qg + qr * (qg / qsg);
+        if (qms > 0.f || qmg > 0.f) {
+            vals[var_qr * n + i] = 0.f;
+            vals[var_qs * n + i] = 0.f;
+            vals[var_qg * n + i] = 0.f;
+        }
+        fws = (double)(qr * qs / qsg) / (double)qms;
+        fwg = (double)(qr * qg / qsg) / (double)qmg;
+    }
+}
+
+// The melting scheme alone (cpol_interp_subbeams): the function k_classify applies, so the fields carry the sweep's bits
+__global__ __launch_bounds__(256) void k_melt_subbeams(float *vals, long n, int var_qr, int var_qs, int var_qg,
+                                                       float *q_melt, double *fw_melt, signed char *mask_ml)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float qr = vals[var_qr * n + i], qsg = vals[var_qs * n + i] + vals[var_qg * n + i];
+    mask_ml[i] = (qr > 0.f && qsg > 0.f) ? 1 : 0;       // melting.py: QR > 0 and QS + QG > 0
+    float qms = 0.f, qmg = 0.f;
+    double fws = 0.0, fwg = 0.0;
+    melt_diagnose(vals, n, i, var_qr, var_qs, var_qg, qms, qmg, fws, fwg);
+    q_melt[i] = qms; q_melt[n + i] = qmg;
+    fw_melt[i] = fws; fw_melt[n + i] = fwg;
+}
+
+// GIVEN (cpol_run_columns with the caller's melting fields): q_melt / fw_melt are inputs, vals[] is already melted
+template <bool GIVEN>
 __global__ __launch_bounds__(CPOL_CLASSIFY_THREADS) CPOL_CLASSIFY_ATTR void k_classify(HydroSet hs, ItabSet its, ClassifyArgs a)
 {
     // one LDS ranking table per hydrometeor: all global atomics of the workgroup are
@@ -526,22 +563,13 @@ __global__ __launch_bounds__(CPOL_CLASSIFY_THREADS) CPOL_CLASSIFY_ATTR void k_cl
     const long i = in ? sbg : 0;
     float qms = 0.f, qmg = 0.f;
     double fws = 0.0, fwg = 0.0;
-    if (a.with_melting && in) {
-        // melting.py:34-83, float32 arithmetic as NumPy evaluates it
-        float qr = a.vals[a.var_qr * n + i], qs = a.vals[a.var_qs * n + i],
-              qg = a.vals[a.var_qg * n + i];
-        float qsg = qs + qg;
-        if (qr > 0.f && qsg > 0.f) {
-            qms = qs + qr * (qs / qsg);
-            qmg = qg + qr * (qg / qsg);
-            if (qms > 0.f || qmg > 0.f) {
-                a.vals[a.var_qr * n + i] = 0.f;
-                a.vals[a.var_qs * n + i] = 0.f;
-                a.vals[a.var_qg * n + i] = 0.f;
-            }
-            fws = (double)(qr * qs / qsg) / (double)qms;
-            fwg = (double)(qr * qg / qsg) / (double)qmg;
+    if (GIVEN) {
+        if (in) {
+            qms = a.q_melt[i]; qmg = a.q_melt[n + i];
+            fws = a.fw_melt[i]; fwg = a.fw_melt[n + i];
         }
+    } else if (a.with_melting && in) {
+        melt_diagnose(a.vals, n, i, a.var_qr, a.var_qs, a.var_qg, qms, qmg, fws, fwg);
         if (a.q_melt) {                               // parity access for the tests (debug mode only)
             a.q_melt[i] = qms;
             a.q_melt[n + i] = qmg;

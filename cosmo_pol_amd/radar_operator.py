@@ -192,6 +192,14 @@ class RadarScan(object):
         return self.fields[variable]['data'][i0:i1]
 
 
+def _is_torch(a):
+    return type(a).__module__.startswith('torch')
+
+
+def _host(a):
+    return a.cpu().numpy() if _is_torch(a) else np.asarray(a)
+
+
 def _mask_from_sum(sum8, n_sub):
     """Builder of the radial mask from cpol_outputs.mask_sum8: the two statements of doppler_scatter.py:472-477 on the
     sum of the sub-beams' mask codes (the sum itself comes from the device)."""
@@ -573,9 +581,310 @@ class RadarOperator(object):
         if one of them left the model domain."""
         self._lane(lane).synchronize()
 
+    # ------------------------------------------------------------------ per-radial seam
+    def _column_names(self):
+        """Variable order of the columns: the staged model's, or the configuration's when no model is loaded."""
+        return list(self._staged_vars) if self._model_staged else hyd.variable_list(self.__config)
+
+    def interpolate_rays(self, azimuths, elevations, melting=True, on_device=False, lane=0):
+        """The first half of simulate_rays (cpol_interp_subbeams): the sub-beam columns of the rays (az[i], el[i]) as the
+        reference's get_interpolated_radial leaves them (interpolation/interpolation.py:91, melting.py:19-90), for all
+        rays at once.  Returns the dict simulate_columns takes: [n_rays, n_sub, n_gates] arrays -- one per model variable,
+        'mask' (int8 codes), 'elev' (not folded), 'lats', 'lons', 'dist', 'heights' of every sub-beam and, with the
+        melting scheme, 'QmS_v', 'QmG_v', 'fwet_mS', 'fwet_mG', 'mask_ml' and 'has_melting' [n_rays, n_sub] -- plus
+        'quad_pts' [n_rays, n_sub, 2] (azimuth, elevation) and 'quad_weights' ([n_sub]; per gate under integration scheme
+        'ml').  The values carry the bits simulate_rays scatters.  `melting`: apply the melting scheme when the
+        configuration melts (False: raw values; simulate_columns then melts on the device).  `on_device`: torch tensors
+        on the operator's GPU, ordered before torch's current stream."""
+        if not self._check_ready():
+            raise ValueError('interpolate_rays: no model loaded')
+        conf = self.__config
+        coords = conf['radar']['coords']
+        if coords[2] > K.MAX_MODEL_HEIGHT:
+            raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
+        rr = self.constants.RANGE_RADAR
+        paths = None
+        if conf['refraction']['scheme'] == 2 and not (self.N is None or isinstance(self.N, int)):
+            from . import refraction
+            sub = self._cached('sub', lambda: quadrature.subbeams(conf))
+            h_col, n_col = refraction.refractivity_column(self.N.data, self._zlevels, self._proj, self._res, coords,
+                                                          conf['radar'].get('type', 'ground'))
+            paths = refraction.ode_paths(rr, elevations, sub.pts_ver, coords, h_col, n_col)
+        mode = N.GEOM_GROUND_43 if paths is None else N.GEOM_HOST_PATHS
+        return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode, apply_sensitivity=False,
+                              paths=paths, lane=lane, subbeams={'melting': bool(melting), 'on_device': bool(on_device)})
+
+    def _export_subbeams(self, p, t, keep, sub, az, el, n_gates, lane, melting, on_device):
+        conf = self.__config
+        names = list(self._staged_vars)
+        n_rays, n_sub = len(az), sub.n_sub
+        shape = (n_rays, n_sub, n_gates)
+        melt = melting and bool(conf['microphysics']['with_melting'])
+        ml = sub.sub_smooth is not None
+        spec = [('vals', np.float32, (len(names),) + shape), ('mask', np.int8, shape), ('elev', np.float32, shape),
+                ('lats', np.float64, shape), ('lons', np.float64, shape), ('dist', np.float32, shape),
+                ('heights', np.float32, shape)]
+        if melt:
+            spec += [('q_melt', np.float32, (2,) + shape), ('fw_melt', np.float64, (2,) + shape), ('mask_ml', np.int8, shape)]
+        if ml:
+            spec.append(('wgate', np.float64, shape))
+        ctx = self._lane(lane)
+        so = N.SubbeamOutputs()
+        so.skip_melting = int(not melt)
+        so.outputs_on_device = int(bool(on_device))
+        if on_device:
+            import torch
+            dev = torch.device('cuda', self.device)
+            arrs = {k: torch.empty(sh, dtype=getattr(torch, np.dtype(dt).name), device=dev) for k, dt, sh in spec}
+            for k, a in arrs.items():
+                setattr(so, k, a.data_ptr())
+            ext = torch.cuda.ExternalStream(ctx.stream_ptr(), device=dev)
+            ext.wait_stream(torch.cuda.current_stream(dev))
+            ctx.interp_subbeams(p, t, so)
+            torch.cuda.current_stream(dev).wait_stream(ext)
+        else:
+            arrs = {k: np.empty(sh, dtype=dt) for k, dt, sh in spec}
+            for k, a in arrs.items():
+                setattr(so, k, a.ctypes.data)
+            ctx.interp_subbeams(p, t, so)
+        del keep
+        out = {nm: arrs['vals'][i] for i, nm in enumerate(names)}
+        for k in ('mask', 'elev', 'lats', 'lons', 'dist', 'heights'):
+            out[k] = arrs[k]
+        if melt:
+            out['QmS_v'], out['QmG_v'] = arrs['q_melt'][0], arrs['q_melt'][1]
+            out['fwet_mS'], out['fwet_mG'] = arrs['fw_melt'][0], arrs['fw_melt'][1]
+            out['mask_ml'] = arrs['mask_ml']
+            out['has_melting'] = arrs['mask_ml'].any(-1) if not on_device else arrs['mask_ml'].bool().any(-1)
+        # (the angles of geometry.ray_tables: node + ray, the same float64 sums)
+        pts = np.stack([sub.pts_hor[sub.sub_h][None, :] + az[:, None], sub.pts_ver[sub.sub_v][None, :] + el[:, None]],
+                       axis=-1)
+        out['quad_pts'] = np.ascontiguousarray(pts)
+        out['quad_weights'] = arrs['wgate'] if ml else np.array(sub.sub_w, dtype=np.float64)
+        return out
+
+    def get_interpolated_radial(self, azimuth, elevation):
+        """The reference's get_interpolated_radial (interpolation/interpolation.py:91) on the GPU: one Radial per kept
+        sub-beam of the ray (azimuth, elevation), with `values` (the model variables and, when the configuration melts,
+        QmS_v, QmG_v, fwet_mS, fwet_mG), `mask`, the lats / lons / dist / heights / elev profiles, `quad_pt`,
+        `quad_weight`, `has_melting` and `mask_ml`."""
+        from .radial import Radial
+        c = self.interpolate_rays([azimuth], [elevation], melting=True)
+        names = list(self._staged_vars) + [k for k in ('QmS_v', 'QmG_v', 'fwet_mS', 'fwet_mG') if k in c]
+        w = c['quad_weights']
+        out = []
+        for s in range(c['elev'].shape[1]):
+            values = {k: (c[k][0, s].astype(np.float64) if k in ('QmS_v', 'QmG_v') else c[k][0, s]) for k in names}
+            r = Radial(values, c['mask'][0, s].astype(np.float64), c['lats'][0, s], c['lons'][0, s], c['dist'][0, s],
+                       c['heights'][0, s], elev_profile=c['elev'][0, s], quad_pt=[float(x) for x in c['quad_pts'][0, s]],
+                       quad_weight=(w[0, s] if np.ndim(w) == 3 else float(w[s])))
+            if 'mask_ml' in c:
+                r.mask_ml = c['mask_ml'][0, s].astype(bool)
+                r.has_melting = bool(c['has_melting'][0, s])
+            out.append(r)
+        return out
+
+    def simulate_columns(self, columns, apply_sensitivity=False, device_outputs=None, lane=0, pinned=False):
+        """The second half of simulate_rays on caller-supplied sub-beam columns (cpol_run_columns): what the
+        reference's get_radar_observables + integrate_radials do for every radial (doppler_scatter.py:49-489).
+        `columns`: dict of [n_rays, n_sub, n_gates] arrays -- one per model variable of the configuration (the names
+        of simulate_rays' model_vars), 'elev' (degrees, unfolded or folded), optionally 'mask' (codes), the given melting
+        fields 'QmS_v', 'QmG_v', 'fwet_mS', 'fwet_mG' (then the variables are the melted ones, as the reference's
+        sub-radials carry them) with 'has_melting' [n_rays, n_sub], and 'lats', 'lons', 'dist', 'heights' (the central
+        sub-beam's become the result's geometry) -- plus 'quad_pts' [n_rays, n_sub, 2] (azimuth, elevation in degrees)
+        and 'quad_weights' [n_sub] (per-gate [n_rays, n_sub, n_gates] for integration scheme 'ml').  NumPy arrays or
+        torch tensors on the operator's GPU (read in place after torch's current stream; never written).
+        Works without a loaded model.  Returns the dict of simulate_rays."""
+        conf = self.__config
+        names = self._column_names()
+        missing = [k for k in names + ['elev', 'quad_pts', 'quad_weights'] if k not in columns]
+        if missing:
+            raise ValueError('simulate_columns: missing %s' % missing)
+        elev = columns['elev']
+        if len(tuple(elev.shape)) != 3:
+            raise ValueError('simulate_columns: columns must be [n_rays, n_sub, n_gates] arrays')
+        n_rays, n_sub, n_gates = (int(x) for x in elev.shape)
+        torch_in = _is_torch(elev)
+        keep = []
+
+        def per_gate(name, dtype, shape=(n_rays, n_sub, n_gates), required=True):
+            a = columns.get(name)
+            if a is None:
+                if required:
+                    raise ValueError('simulate_columns: missing %s' % name)
+                return None
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError('simulate_columns: %s has shape %s, expected %s' % (name, tuple(a.shape), tuple(shape)))
+            if _is_torch(a) != torch_in:
+                raise ValueError('simulate_columns: mixed torch / NumPy columns (%s)' % name)
+            if torch_in:
+                import torch
+                if a.device.type != 'cuda' or a.device.index != self.device:
+                    raise ValueError('simulate_columns: %s is not on the operator\'s GPU' % name)
+                a = a.to(getattr(torch, np.dtype(dtype).name)).contiguous()
+                keep.append(a)
+                return a.data_ptr()
+            a = np.ascontiguousarray(np.asarray(a).astype(dtype, copy=False))
+            keep.append(a)
+            return a.ctypes.data
+
+        cols = N.Columns()
+        cols.n_vars = len(names)
+        cols.inputs_on_device = int(torch_in)
+        vals = (C.c_void_p * len(names))(*[per_gate(k, np.float32) for k in names])
+        cols.vals = C.cast(vals, C.c_void_p)
+        cols.elev = per_gate('elev', np.float32)
+        cols.mask = per_gate('mask', np.int8, required=False)
+        melt_keys = ('QmS_v', 'QmG_v', 'fwet_mS', 'fwet_mG')
+        given = any(k in columns for k in melt_keys)
+        if given and not all(k in columns for k in melt_keys):
+            raise ValueError('simulate_columns: the given melting fields need all of %s' % (melt_keys,))
+        if given and not conf['microphysics']['with_melting']:
+            raise ValueError('simulate_columns: melting fields given, but the configuration does not melt')
+        if given:
+            q = np.stack([_host(columns['QmS_v']), _host(columns['QmG_v'])]) if not torch_in else None
+            if torch_in:
+                import torch
+                columns = dict(columns, _q=torch.stack([columns['QmS_v'], columns['QmG_v']]),
+                               _fw=torch.stack([columns['fwet_mS'], columns['fwet_mG']]))
+            else:
+                columns = dict(columns, _q=q, _fw=np.stack([_host(columns['fwet_mS']), _host(columns['fwet_mG'])]))
+            cols.q_melt = per_gate('_q', np.float32, (2, n_rays, n_sub, n_gates))
+            cols.fw_melt = per_gate('_fw', np.float64, (2, n_rays, n_sub, n_gates))
+            cols.has_melting = per_gate('has_melting', np.int8, (n_rays, n_sub), required=False)
+        w = columns['quad_weights']
+        w = w if _is_torch(w) else np.asarray(w, dtype=np.float64)
+        ml = len(tuple(w.shape)) == 3
+        if ml:
+            cols.wgate = per_gate('quad_weights', np.float64)
+            sub_w = np.ones(n_sub)
+        else:
+            sub_w = np.ascontiguousarray(_host(w), dtype=np.float64)
+            if sub_w.shape != (n_sub,):
+                if sub_w.shape == (n_rays, n_sub) and (sub_w == sub_w[:1]).all():
+                    sub_w = np.ascontiguousarray(sub_w[0])
+                else:
+                    raise ValueError('simulate_columns: quad_weights must be [n_sub], the same for every radial, '
+                                     'or per gate [n_rays, n_sub, n_gates]')
+        qp = np.asarray(_host(columns['quad_pts']), dtype=np.float64)
+        if not np.isfinite(qp).all():
+            raise ValueError('simulate_columns: quad_pts must be finite')
+        if qp.shape != (n_rays, n_sub, 2):
+            raise ValueError('simulate_columns: quad_pts must be [n_rays, n_sub, 2]')
+        az_rad = qp[..., 0] * geo.DEG                  # (the angle of geometry.ray_tables: same sin / cos bits)
+        az_sincos = np.ascontiguousarray(np.stack([np.sin(az_rad), np.cos(az_rad)], axis=-1))
+        keep += [sub_w, az_sincos]
+        cols.az_sincos = az_sincos.ctypes.data
+        cols.sub_w = sub_w.ctypes.data
+
+        p = N.SweepParams()
+        p.n_rays, p.n_gates, p.n_sub = n_rays, n_gates, n_sub
+        p.n_hnodes = p.n_vnodes = n_sub
+        p.with_melting = int(conf['microphysics']['with_melting'])
+        p.with_attenuation = int(conf['microphysics']['with_attenuation'])
+        want_model = self.output_variables in ('all', 'only_model')
+        p.integrate_model = int(want_model)
+        p.outputs_on_device = 1 if device_outputs is not None else (2 if pinned else 0)
+        doppler = conf['doppler']['scheme'] in (1, 2, 3) and conf['radar'].get('type') != 'GPM'
+        spectrum = doppler and conf['doppler']['scheme'] == 3
+        p.simulate_doppler = int(conf['doppler']['scheme']) if doppler else 0
+        vi = {v: i for i, v in enumerate(names)}
+        p.var_u, p.var_v, p.var_w = vi['U'], vi['V'], vi['W']
+        p.var_rho = vi.get('RHO', -1)
+        if spectrum:
+            varray = np.ascontiguousarray(self.constants.VARRAY, dtype=np.float64)
+            keep.append(varray)
+            cols.varray = varray.ctypes.data
+            p.n_vbins = len(varray)
+            p.c_spectrum = float(self.constants.WAVELENGTH ** 4 / (np.pi ** 5 * conf['radar']['K_squared'] ** 2))
+        p.geometry_mode = N.GEOM_GROUND_43
+        p.range_step = float(conf['radar']['radial_resolution'])
+        p.wavelength = float(self.constants.WAVELENGTH)
+        p.k_squared = float(conf['radar']['K_squared'])
+        p.radial_res = float(conf['radar']['radial_resolution'])
+        p.c_zh = float(self.constants.WAVELENGTH ** 4 / (np.pi ** 5 * conf['radar']['K_squared']))
+        thr = geo.sensitivity_threshold(conf, self.constants, n_gates) if apply_sensitivity else None
+        p.apply_sensitivity = int(thr is not None)
+        if thr is not None:
+            keep.append(thr)
+            cols.sens_thr = thr.ctypes.data
+        if doppler and conf['radar']['nyquist_velocity'] is not None:
+            # the central sub-radial's angles (doppler_scatter.py:94-96, 436-437)
+            c = int(n_sub / 2)
+            nyq = np.ascontiguousarray(conf['radar']['nyquist_velocity'](qp[:, c, 1], qp[:, c, 0]), dtype=np.float64)
+            keep.append(nyq)
+            cols.nyquist = nyq.ctypes.data
+
+        o = N.Outputs()
+        res = {}
+        if device_outputs is not None:
+            for k, ptr in device_outputs.items():
+                setattr(o, k, ptr)
+        else:
+            shape = (n_rays, n_gates)
+            spec = [(k, np.float32, shape) for k in RADAR_FIELDS]
+            if doppler:
+                spec.append(('RVEL', np.float64, shape))
+            if spectrum:
+                spec.append(('DSPECTRUM', np.float64, shape + (p.n_vbins,)))
+            spec.append(('mask', np.float64, shape))
+            if want_model:
+                spec.append(('model_vars', np.float64, (len(names),) + shape))
+            if pinned:
+                counts = [math.prod(sh) for _, _, sh in spec]
+                sizes = [-(-n_el * _ITEMSIZE[dt] // 64) * 64 for n_el, (_, dt, _) in zip(counts, spec)]
+                slab, holder = self._pool.take(sum(sizes), writer=self._lane(lane))
+                off = 0
+                for (k, dt, sh), n_el, nb in zip(spec, counts, sizes):
+                    res[k] = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
+                    off += nb
+                del slab
+            else:
+                res = {k: np.empty(sh, dtype=dt) for k, dt, sh in spec}
+            for k, v in res.items():
+                setattr(o, k, v.ctypes.data)
+        ctx = self._lane(lane)
+        if torch_in:
+            # the columns are read in place: behind the work queued on torch's current stream, and torch's stream waits
+            # for the ingest before it may reuse their memory
+            import torch
+            ext = torch.cuda.ExternalStream(ctx.stream_ptr(), device=torch.device('cuda', self.device))
+            ext.wait_stream(torch.cuda.current_stream(self.device))
+        ctx.run_columns(p, cols, o)
+        if torch_in:
+            torch.cuda.current_stream(self.device).wait_stream(ext)
+        if device_outputs is None:
+            if pinned:
+                holder['ctx'], holder['serial'] = ctx, ctx.submitted
+            del keep
+            c = int(n_sub / 2)
+            for k in ('lats', 'lons', 'dist', 'heights'):
+                if k in columns:
+                    a = columns[k]
+                    res[k] = (a[:, c].cpu().numpy() if _is_torch(a) else np.asarray(a)[:, c]).copy()
+        res['n_sub'] = n_sub
+        return res
+
+    def get_radar_observables(self, list_subradials):
+        """The reference's get_radar_observables (scatter/doppler_scatter.py:49-489) for one radial on the GPU: a list
+        of sub-radials -- objects with the attributes of the reference's Radial (values, mask, elev_profile, quad_pt,
+        quad_weight, has_melting, lats / lons / dist / heights_profile): this package's, the oracle's or the
+        reference's own -- -> one Radial of the observables ZH ... RVEL (no sensitivity cut).  Records that carry
+        QmS_v use the given melting fields, the others are melted on the device when the configuration melts.
+        Unlike the reference, which folds elev_profile in place, the records are never modified.
+        Ragged lists (different gate counts) and weights of different kinds raise ValueError."""
+        from .radial import Radial, subradials_to_columns
+        subs = list(list_subradials)
+        cols = subradials_to_columns(subs, self._column_names(), self.__config['microphysics']['with_melting'])
+        n_sub = len(subs)
+        res = self.simulate_columns(cols, apply_sensitivity=False)
+        c = subs[int(n_sub / 2)]
+        values = {k: v[0] for k, v in res.items() if k not in ('mask', 'n_sub', 'lats', 'lons', 'dist', 'heights', 'model_vars')}
+        return Radial(values, res['mask'][0], c.lats_profile, c.lons_profile, c.dist_profile, c.heights_profile)
+
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False):
+                  pinned=False, subbeams=None):
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -693,6 +1002,8 @@ class RadarOperator(object):
         else:
             p, t, keep, doppler, spectrum, varray = prepare()
 
+        if subbeams is not None:
+            return self._export_subbeams(p, t, keep, sub, az, el, n_gates, lane, **subbeams)
         o = N.Outputs()
         res = {}
         geom = None

@@ -412,6 +412,67 @@ CPOL_API int  cpol_ray_tables(const cpol_sweep_params *p, const double *az_deg, 
 CPOL_API int  cpol_run_sweep(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *tables,
                     cpol_outputs *out);
 
+/* Sub-beam columns of cpol_interp_subbeams: every array [n_rays][n_sub][n_gates] (the library's own sub-beam order),
+ * NULL = not wanted.  Host buffers, or device buffers with outputs_on_device = 1. */
+typedef struct {
+    float   *vals;              /* [n_vars][...] float32 model values (after the melting scheme unless skipped)      */
+    int8_t  *mask;              /* mask codes (-1 below the topography, 0, 1 above the model top, 2 outside the domain) */
+    float   *elev;              /* elevation [deg] as get_interpolated_radial leaves it (not folded)                 */
+    double  *lats, *lons;       /* gate coordinates of every sub-beam (the long form of the geodesy)                */
+    float   *dist, *heights;    /* distance at the ground and height [m]                                             */
+    float   *q_melt;            /* [2][...] QmS_v, QmG_v (melting.py:19-90; zero where nothing melts)                */
+    double  *fw_melt;           /* [2][...] fwet_mS, fwet_mG                                                        */
+    int8_t  *mask_ml;           /* the reference's mask_ml: QR > 0 and QS + QG > 0 before melting; has_melting = any
+                                   over a sub-beam                                                                    */
+    double  *wgate;             /* integration scheme 'ml' (tables->sub_smooth): the per-gate sub-beam weights        */
+    int32_t skip_melting;       /* 1: no melting scheme (raw interpolated values; q_melt / fw_melt / mask_ml unwritten) */
+    int32_t outputs_on_device;  /* 1: the pointers above are device memory and the call returns at once             */
+} cpol_subbeam_outputs;
+
+/* The first half of cpol_run_sweep for the same rays: ray paths, gate geodesy, gate interpolation (the sweep's own
+ * forms: the values carry cpol_run_sweep's bits) and, unless out->skip_melting, the melting scheme -- the reference's
+ * get_interpolated_radial (interpolation/interpolation.py:91) for every ray.  No scattering.  p->with_melting selects
+ * the melting scheme as for the sweep; apply_sensitivity / integrate_model are ignored.  Needs a staged model and
+ * staged hydrometeors. */
+CPOL_API int  cpol_interp_subbeams(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *tables,
+                      cpol_subbeam_outputs *out);
+
+/* Sub-beam columns supplied by the caller (cpol_run_columns): the input of the reference's get_radar_observables
+ * (scatter/doppler_scatter.py:49) for n_rays radials of n_sub sub-radials each.  Per-gate arrays are
+ * [n_rays][n_sub][n_gates], the library's own sub-beam order. */
+typedef struct {
+    int32_t n_vars;             /* entries of `vals`: the variable order the staged hydrometeor descriptors (var_q,
+                                   var_t, var_qn) and cpol_sweep_params.var_u / var_v / var_w / var_rho index */
+    int32_t inputs_on_device;   /* 1: the per-gate arrays and has_melting are device pointers (read in place, never
+                                   written); 0: host memory.  The per-ray tables below are always host memory */
+    const float *const *vals;   /* [n_vars] per-gate float32 model values (the pointer array itself is host memory).
+                                   With q_melt: after the melting scheme (QR / QS / QG zeroed where it melted) */
+    const int8_t *mask;         /* per-gate mask codes (-1, 0, 1, 2) or NULL (all 0); feeds the radial mask only */
+    const float *elev;          /* per-gate elevation [deg], unfolded or folded: folded on the device (Q8) */
+    const double *wgate;        /* per-gate sub-beam weights (integration scheme 'ml') or NULL: sub_w        */
+    const float *q_melt;        /* [2] x per-gate QmS_v, QmG_v given by the caller, or NULL: with_melting = 1
+                                   diagnoses melting on the device from QR / QS / QG as cpol_run_sweep does */
+    const double *fw_melt;      /* [2] x per-gate fwet_mS, fwet_mG (with q_melt)                            */
+    const int8_t *has_melting;  /* [n_rays][n_sub] 0: the given melting fields of that sub-beam count as zero
+                                   (doppler_scatter.py:160-165), or NULL (all 1); only with q_melt        */
+    /* per-ray tables (host) */
+    const double *az_sincos;    /* [n_rays][n_sub][2] sin and cos of each sub-beam's azimuth (the first two entries
+                                   of the sweep's `geo` table); needed with simulate_doppler                */
+    const double *sub_w;        /* [n_sub] quadrature weights (required)                                     */
+    const double *nyquist;      /* [n_rays] or NULL, as in cpol_ray_tables_t                                 */
+    const double *sens_thr;     /* [n_gates] or NULL, as in cpol_ray_tables_t                                */
+    const double *varray;       /* [n_vbins] (Doppler scheme 3) or NULL                                     */
+} cpol_columns_t;
+
+/* The second half of cpol_run_sweep on caller-supplied sub-beam columns: PSD, scattering, sub-beam sums, ZH ... RVEL
+ * and the sensitivity cut, into the same cpol_outputs struct; lats / lons / dist / heights are not written (the columns carry
+ * no geometry).  p: n_rays, n_gates, n_sub and the radar / scheme fields as for cpol_run_sweep; n_hnodes, n_vnodes,
+ * geometry_mode and the site fields are ignored.  Needs staged hydrometeors, no staged model; works on a lane.
+ * CPOL_ERR_ARG (the context stays usable) on bad shapes, a missing variable pointer, a descriptor index >= n_vars
+ * or mask_sum8 with 2 * n_sub > 127. */
+CPOL_API int  cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *cols,
+                      cpol_outputs *out);
+
 /* CPOL_GEOM_SPACEBORNE helper: index of the first candidate gate below the
  * model-top ceiling for each (ray, vertical node): first_gate [n_rays*n_vnodes]
  * (host buffer).  `traj` [n_rays][n_vnodes][CPOL_TRAJ_STRIDE] and `site`
