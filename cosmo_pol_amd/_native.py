@@ -67,6 +67,11 @@ class SweepParams(C.Structure):
         ('c_zh', C.c_double),
         ('var_u', C.c_int32), ('var_v', C.c_int32), ('var_w', C.c_int32), ('var_rho', C.c_int32),
         ('n_vbins', C.c_int32), ('debug_flags', C.c_int32), ('c_spectrum', C.c_double),
+        # Doppler scheme 3: spectrum broadening (all zero = off)
+        ('turbulence_correction', C.c_int32), ('motion_correction', C.c_int32), ('var_edr', C.c_int32),
+        ('pad_broaden_', C.c_int32),
+        ('sigma_r', C.c_double), ('sigma_theta', C.c_double), ('motion_num', C.c_double), ('motion_den', C.c_double),
+        ('v_res', C.c_double),
     ]
 
 
@@ -119,7 +124,7 @@ EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_
            'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_interp_subbeams', 'cpol_run_columns', 'cpol_counters',
            'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free', 'cpol_host_alloc_near',
            'cpol_device_pci_bus_id', 'cpol_mem_info',
-           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math']
+           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_broaden_rows']
 
 TRAJ_STRIDE, GEO_STRIDE, SITE_STRIDE = 4, 8, 8      # CPOL_*_STRIDE of the header
 MELT_DEGREE, MELT_FUNCS = 10, 4                    # CPOL_MELT_DEGREE / CPOL_MELT_FUNCS
@@ -224,6 +229,8 @@ def load_library():
     lib.cpol_set_num_hydro.argtypes = [vp, C.c_int]
     lib.cpol_interp_points.restype = C.c_int
     lib.cpol_interp_points.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.cpol_broaden_rows.restype = C.c_int
+    lib.cpol_broaden_rows.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.cpol_ray_tables.restype = C.c_int
     lib.cpol_ray_tables.argtypes = [C.POINTER(SweepParams), vp, vp, vp, vp, vp, vp]
     lib.cpol_run_sweep.restype = C.c_int
@@ -574,6 +581,17 @@ class Context(object):
         out = np.empty((self.n_vars, n), dtype=np.float32)
         rc = self.lib.cpol_interp_points(self.h, n, _ptr(coords), _ptr(heights), _ptr(out))
         self._check(rc, 'cpol_interp_points')
+        return out
+
+    def broaden_rows(self, rows, sigma_bins):
+        """The filter of the spectrum broadening on explicit float32 rows [n_rows, n_v], one sigma in bins per row."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        sigma_bins = np.ascontiguousarray(sigma_bins, dtype=np.float64)
+        if rows.ndim != 2 or sigma_bins.shape != (rows.shape[0],):
+            raise ValueError('broaden_rows: rows [n_rows, n_v] and one sigma per row')
+        out = np.empty_like(rows)
+        rc = self.lib.cpol_broaden_rows(self.h, _ptr(rows), rows.shape[0], rows.shape[1], _ptr(sigma_bins), _ptr(out))
+        self._check(rc, 'cpol_broaden_rows')
         return out
 
     def run_sweep(self, params, tables, outputs):

@@ -136,6 +136,7 @@ struct cpol_ctx {
     int stg_next = 0;
     DevBuf b_traj, b_wgate, b_clk, b_rayc, b_poly, d_geoM;
     DevBuf b_beam, b_spectrum, b_outwin;
+    DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
     DevBuf b_out[16], b_szinteg, b_sztotal, b_model, b_ticket, b_mask8;
@@ -700,7 +701,7 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
                      &ctx->b_vn, &ctx->b_icefirst, &ctx->b_rvel, &ctx->b_proj, &ctx->b_blkranked, &ctx->b_rec, &ctx->b_vmask, &ctx->b_gscan, &ctx->b_defer,
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8,
-                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo};
+                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon};
     for (DevBuf *b : all) free_buf(*b);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
@@ -1255,6 +1256,39 @@ int cpol_interp_points(cpol_ctx *ctx, int n, const float *coords, const float *h
     return CPOL_OK;
 }
 
+// the filter kernel of the spectrum broadening: one workgroup per row, a wavefront for short rows
+static void launch_broaden(const SpecBroadenArgs &ba, long n_rows, hipStream_t st)
+{
+    const size_t lds = (size_t)ba.n_v * sizeof(float);
+    if (ba.n_v <= CPOL_BROAD_WAVE_BINS) hipLaunchKernelGGL((k_spec_broaden<64>), dim3((unsigned)n_rows), dim3(64), lds, st, ba);
+    else hipLaunchKernelGGL((k_spec_broaden<256>), dim3((unsigned)n_rows), dim3(256), lds, st, ba);
+}
+
+int cpol_broaden_rows(cpol_ctx *ctx, const float *rows, int n_rows, int n_v, const double *sigma_bins, float *out)
+{
+    if (!ctx || !rows || !sigma_bins || !out || n_rows < 1 || n_v < 2 || n_v > 4097) {
+        if (ctx) ctx->err = "cpol_broaden_rows: bad arguments (n_rows >= 1, n_v in [2, 4097])";
+        return CPOL_ERR_ARG;
+    }
+    (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf r, s, o;
+    int rc;
+    const size_t rb = (size_t)n_rows * n_v * sizeof(float);
+    if ((rc = upload(ctx, r, rows, rb)) != CPOL_OK) return rc;
+    if ((rc = upload(ctx, s, sigma_bins, (size_t)n_rows * sizeof(double))) != CPOL_OK) { free_buf(r); return rc; }
+    if ((rc = ensure(ctx, o, rb)) != CPOL_OK) { free_buf(r); free_buf(s); return rc; }
+    SpecBroadenArgs ba{};
+    ba.in = (const float *)r.p; ba.out = (float *)o.p; ba.sigma = (const double *)s.p;
+    ba.on = nullptr; ba.rows_per_switch = 1; ba.n_v = n_v;
+    launch_broaden(ba, n_rows, ctx->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, o.p, rb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    free_buf(r); free_buf(s); free_buf(o);
+    return CPOL_OK;
+}
+
 int cpol_ray_tables(const cpol_sweep_params *p, const double *az_deg, const double *el_deg,
                     const double *pts_h_deg, const double *pts_v_deg, double *traj_out,
                     double *geo_out)
@@ -1570,6 +1604,19 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             return CPOL_ERR_ARG;
         }
     }
+    const bool broaden = p->turbulence_correction != 0 || p->motion_correction != 0;
+    if (broaden) {
+        if (!dop3) { ctx->err = "cpol_run_sweep: turbulence_correction / motion_correction need Doppler scheme 3"; return CPOL_ERR_ARG; }
+        if (p->turbulence_correction && (p->var_edr < 0 || p->var_edr >= n_vars)) {
+            ctx->err = "cpol_run_sweep: turbulence_correction needs var_edr, the staged index of the eddy dissipation rate";
+            return CPOL_ERR_ARG;
+        }
+        if (!(p->v_res > 0.0) || (p->turbulence_correction && (!(p->sigma_r > 0.0) || !(p->sigma_theta > 0.0))) ||
+            (p->motion_correction && !(p->motion_den > 0.0))) {
+            ctx->err = "cpol_run_sweep: spectrum broadening needs v_res > 0, sigma_r, sigma_theta > 0 (turbulence), motion_den > 0 (motion)";
+            return CPOL_ERR_ARG;
+        }
+    }
     if (dop2)
         for (int j = 0; j < n_hyd; ++j)
             if (!ctx->hs.h[j].rcsw) { ctx->err = "cpol_run_sweep: Doppler scheme 2 needs cpol_stage_doppler_weights"; return CPOL_ERR_ARG; }
@@ -1623,6 +1670,10 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     if (dop3) {
         ENSURE(ctx->b_beam, (size_t)n_sbg * n_vb * sizeof(float));
+        if (broaden) {
+            ENSURE(ctx->b_bsigma, (size_t)n_sbg * sizeof(double));
+            ENSURE(ctx->b_bon, (size_t)n_rays * n_sub * sizeof(int));
+        }
     }
     // ---- outputs: where the kernels write each array, and how it reaches the caller ----
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
@@ -2520,6 +2571,27 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             }
         }
         hipLaunchKernelGGL(k_spec_gate, dim3((unsigned)n_sbg), dim3(CPOL_SPEC_THREADS), lds, st, ctx->hs, ctx->ss, sp);
+        if (broaden) {
+            // ---- turbulence / antenna motion: width and switch per sub-beam, then the filter row by row ----
+            SpecWidthArgs wa{};
+            wa.vals = (const float *)ctx->b_vals.p;
+            wa.elev = (const float *)ctx->b_elev.p;
+            wa.sigma = (double *)ctx->b_bsigma.p;
+            wa.on = (int *)ctx->b_bon.p;
+            wa.n_sbg = n_sbg; wa.n_gates = ng;
+            wa.turb = p->turbulence_correction != 0; wa.motion = p->motion_correction != 0; wa.var_edr = p->var_edr;
+            wa.range0 = p->range0; wa.range_step = p->range_step;
+            wa.sigma_r = p->sigma_r; wa.sigma_theta = p->sigma_theta;
+            wa.c_near = pow(CPOL_TURB_A, 3 / 2.); wa.c_far = pow(1.35 * CPOL_TURB_A, 3 / 2.);
+            wa.motion_num = p->motion_num; wa.motion_den = p->motion_den;
+            wa.v_res = p->v_res;
+            hipLaunchKernelGGL(k_spec_width, dim3(n_rays * n_sub), dim3(64), 0, st, wa);
+            SpecBroadenArgs ba{};
+            ba.in = (const float *)ctx->b_beam.p; ba.out = (float *)ctx->b_beam.p;
+            ba.sigma = (const double *)ctx->b_bsigma.p; ba.on = (const int *)ctx->b_bon.p;
+            ba.rows_per_switch = ng; ba.n_v = n_vb;
+            launch_broaden(ba, n_sbg, st);
+        }
         if (p->with_attenuation) {
             SpecAttenArgs sa2{};
             sa2.key = (const int *)ctx->b_key.p;

@@ -6,6 +6,7 @@
 //   get_refl                        scatter/doppler_c.c:11-32
 //   per-sub-beam attenuation, weights, accumulation   scatter/doppler_scatter.py:297-305, 353-391
 //   RVEL from the spectrum, aliasing                  scatter/doppler_scatter.py:422-437
+//   spectral_width_turb / _motion, broaden_spectrum   scatter/doppler_scatter.py:360-369, 727-801
 // Hydrometeors with power-law fall speeds (R, S, G, H, I) and, since round 6, the melting species (mS, mG): their fall
 // speed V(D) = phi V_rain(D_r(D)) + (1 - phi) V_dry(D) has no closed inverse, the reference inverts it at EVERY gate by
 // linear interpolation over the n_d nodes (V(D_k), D_k), D_k = linspace(d_min(fw), d_max(fw), n_d) -- `set_psd` clears the
@@ -287,6 +288,190 @@ __global__ __launch_bounds__(CPOL_SPEC_THREADS) void k_spec_gate(HydroSet hs, Sp
         }
         if (keep) out[v] = refl * a.c_spec;
     }
+}
+
+// ---- broadening of the spectrum by turbulence and antenna motion (doppler_scatter.py:360-369, 727-801) ----
+// Per sub-beam, between get_doppler_spectrum and the attenuation correction: a width per gate (two standard deviations in
+// m/s, added LINEARLY, :361-366), the sub-beam's switch `np.sum(width) > 0` (:368 -- one non-finite width, an EDR that is
+// NaN or negative at a masked gate, makes the sum NaN and leaves the WHOLE sub-beam unbroadened), then per gate
+// scipy.ndimage.gaussian_filter of the float32 row with sigma = width / v_res bins (truncate 4, mode 'reflect', float64
+// accumulation in SciPy's order) and the rescale row / sum(filtered) * sum(original) in float32: a row without power
+// becomes 0 / 0 = NaN and, through the sum over the sub-beams, so do the gate's spectrum and RVEL.
+// Departures, for inputs the reference raises on or cannot finish: a sigma <= 1e-15 bins inside a broadened sub-beam filters as
+// the identity (what gaussian_filter's own guard does; the rescale still runs); an infinite width switches the sub-beam off
+// like a NaN; the radius int(4 sigma + 0.5) is cut at CPOL_BROAD_MAX_RADIUS taps (sigma > 16384 bins).
+struct SpecWidthArgs {
+    const float *vals;          // [n_vars][n_sbg]
+    const float *elev;          // folded elevation [n_sbg] (the reference folds elev_profile in place before it gets here, Q8)
+    double *sigma;              // [n_sbg] width / v_res: the filter's sigma in bins
+    int *on;                    // [n_rays * n_sub] the sub-beam's switch
+    long n_sbg;
+    int n_gates;
+    int turb, motion, var_edr;
+    double range0, range_step;  // RANGE_RADAR[g] = range0 + g * range_step
+    double sigma_r, sigma_theta;
+    double c_near, c_far;       // A^1.5 and (1.35 A)^1.5, evaluated by the host's libm as Python does
+    double motion_num, motion_den;      // (WAVELENGTH / 100) * antenna_speed and 2 pi deg2rad(3dB_beamwidth)
+    double v_res;
+};
+
+// one wavefront per (ray, sub-beam).  NumPy-2 promotion of spectral_width_turb / spectral_width_motion: the float32 EDR
+// times the two Python floats of the far branch stays float32, as does the float32 cosine times the motion numerator.
+__global__ __launch_bounds__(64) void k_spec_width(SpecWidthArgs a)
+{
+    const long rs = blockIdx.x;
+    const int lane = threadIdx.x;
+    double sum = 0.0;
+    bool finite = true;
+    for (int g0 = 0; g0 < a.n_gates; g0 += 64) {
+        const int g = g0 + lane;
+        if (g >= a.n_gates) continue;
+        const long sbg = rs * a.n_gates + g;
+        double w = 0.0;
+        if (a.turb) {
+            const double r = a.range0 + a.range_step * (double)g;
+            const float E = a.vals[(long)a.var_edr * a.n_sbg + sbg];
+            double t;
+            if (a.sigma_r < (0.1 * r) * a.sigma_theta) {              // sigma_r << r sigma_theta (Doviak & Zrnic p. 409)
+                t = pow(((((r * (double)E) * a.sigma_theta) * a.c_near) / 0.72), 1 / 3.);
+            } else {
+                const float num = (E * (float)a.sigma_r) * (float)a.c_far;
+                const double x = (r * a.sigma_theta) / a.sigma_r;
+                const double den = pow(11. / 15. + 4. / 15. * (x * x), -3 / 2.);
+                t = pow((double)num / den, 1 / 3.);
+            }
+            w += t;
+        }
+        if (a.motion) {
+            const float th = a.elev[sbg] * 0.017453292f;              // np.deg2rad of a float32
+            const float c32 = (float)cos((double)th);
+            const float num = (float)a.motion_num * c32;
+            w += (double)num / a.motion_den;
+        }
+        a.sigma[sbg] = w / a.v_res;
+        if (!(fabs(w) <= 1.7976931348623157e308)) finite = false;     // NaN or infinite
+        else sum += w;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += shfl_f64(sum, lane ^ off);
+    const bool all_finite = __all(finite ? 1 : 0) != 0;
+    if (lane == 0) a.on[rs] = (all_finite && sum > 0.0) ? 1 : 0;
+}
+
+#define CPOL_TURB_A 1.6                 // global_constants.py:124
+#define CPOL_BROAD_CHUNK 256            // filter taps staged in LDS at a time
+#define CPOL_BROAD_MAX_OUT 17           // bins per thread: 4097 bins / 256 threads, 1024 bins / 64 threads
+#ifndef CPOL_BROAD_WAVE_BINS
+#define CPOL_BROAD_WAVE_BINS 1024       // rows up to this length are filtered by one wavefront, longer ones by 256 threads
+#endif
+#define CPOL_BROAD_MAX_RADIUS 65536
+
+template <int T> __device__ __forceinline__ float broad_sum32(float x, float *red)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+    if (T > 64) {
+        __syncthreads();                                  // (red may still be read from the previous sum)
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+        __syncthreads();
+        x = red[0];
+        for (int w = 1; w < T / 64; ++w) x += red[w];
+    }
+    return x;
+}
+
+template <int T> __device__ __forceinline__ double broad_sum64(double x, double *red)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += shfl_f64(x, (threadIdx.x & 63) ^ off);
+    if (T > 64) {
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+        __syncthreads();
+        x = red[0];
+        for (int w = 1; w < T / 64; ++w) x += red[w];
+    }
+    return x;
+}
+
+// One row of broaden_spectrum by the T threads of a workgroup: `in` -> `out` (may be the same row), sigma in bins.
+// xL: [n_v] floats of LDS.  The taps follow NI_Correlate1D's symmetric form: the centre tap, then the pairs
+// (x[i - k] + x[i + k]) w[k] from k = radius down to 1, accumulated in float64 and rounded once; the weights
+// exp(-0.5 / sigma^2 * k^2) / sum are made CPOL_BROAD_CHUNK at a time, so LDS does not grow with sigma.  Reflection
+// (d c b a | a b c d | d c b a) by position modulo 2 n_v: any radius works.
+template <int T> __device__ void broaden_row(const float *in, float *out, int n_v, double sigma, float *xL)
+{
+    __shared__ double wL[CPOL_BROAD_CHUNK];
+    __shared__ double red64[4];
+    __shared__ float red32[4];
+    const int tid = threadIdx.x;
+    float part = 0.0f;
+    for (int v = tid; v < n_v; v += T) { const float x = in[v]; xL[v] = x; part += x; }
+    __syncthreads();
+    const float orig = broad_sum32<T>(part, red32);
+    double acc[CPOL_BROAD_MAX_OUT];
+#pragma unroll
+    for (int o = 0; o < CPOL_BROAD_MAX_OUT; ++o) { const int v = tid + o * T; acc[o] = v < n_v ? (double)xL[v] : 0.0; }
+    if (sigma > 1e-15) {                                  // (gaussian_filter skips an axis whose sigma is not above 1e-15)
+        const double r4 = 4.0 * sigma + 0.5;
+        const int radius = r4 < (double)CPOL_BROAD_MAX_RADIUS ? (int)r4 : CPOL_BROAD_MAX_RADIUS;
+        const double c = -0.5 / (sigma * sigma);
+        double ws = 0.0;
+        for (int k = 1 + tid; k <= radius; k += T) ws += exp(c * ((double)k * (double)k));
+        const double total = 1.0 + 2.0 * broad_sum64<T>(ws, red64);
+        const double w0 = 1.0 / total;
+#pragma unroll
+        for (int o = 0; o < CPOL_BROAD_MAX_OUT; ++o) acc[o] = acc[o] * w0;
+        const int period = 2 * n_v;
+        for (int k_hi = radius; k_hi >= 1; k_hi -= CPOL_BROAD_CHUNK) {
+            const int cnt = min(CPOL_BROAD_CHUNK, k_hi);
+            __syncthreads();                              // (the previous chunk has been read)
+            for (int t = tid; t < cnt; t += T) { const double k = (double)(k_hi - t); wL[t] = exp(c * (k * k)) / total; }
+            __syncthreads();
+            // (bins outside, taps inside.  Taps outside with the bins of a thread as independent chains needs the two reflected
+            // positions of every bin in registers: 143 VGPRs, 240 us instead of 186 us on the 360 x 60 x 257 sweep of DESIGN.md 3.10)
+#pragma unroll
+            for (int o = 0; o < CPOL_BROAD_MAX_OUT; ++o) {
+                const int v = tid + o * T;
+                if (v >= n_v) continue;
+                int mL = (v - k_hi) % period; if (mL < 0) mL += period;
+                int mR = (v + k_hi) % period;
+                double s = acc[o];
+                for (int t = 0; t < cnt; ++t) {
+                    const float xl = xL[mL < n_v ? mL : period - 1 - mL], xr = xL[mR < n_v ? mR : period - 1 - mR];
+                    s += ((double)xl + (double)xr) * wL[t];
+                    mL = mL + 1 == period ? 0 : mL + 1;
+                    mR = mR == 0 ? period - 1 : mR - 1;
+                }
+                acc[o] = s;
+            }
+        }
+    }
+    float y[CPOL_BROAD_MAX_OUT];
+    part = 0.0f;
+#pragma unroll
+    for (int o = 0; o < CPOL_BROAD_MAX_OUT; ++o) { y[o] = (float)acc[o]; if (tid + o * T < n_v) part += y[o]; }
+    const float conv = broad_sum32<T>(part, red32);
+#pragma unroll
+    for (int o = 0; o < CPOL_BROAD_MAX_OUT; ++o) { const int v = tid + o * T; if (v < n_v) out[v] = y[o] / conv * orig; }
+}
+
+struct SpecBroadenArgs {
+    const float *in;            // [n_rows][n_v]
+    float *out;                 // [n_rows][n_v] (the sweep filters its sub-beam spectra in place)
+    const double *sigma;        // [n_rows] in bins
+    const int *on;              // [n_rows / rows_per_switch] or NULL (every row)
+    int rows_per_switch;        // n_gates
+    int n_v;
+};
+
+// one workgroup per row (= sub-beam gate): 64 threads for rows up to CPOL_BROAD_WAVE_BINS bins, 256 beyond
+template <int T> __global__ __launch_bounds__(T) void k_spec_broaden(SpecBroadenArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds_row[];
+    const long row = blockIdx.x;
+    if (a.on && !a.on[row / a.rows_per_switch]) return;   // rows of a sub-beam whose switch is off are not touched
+    broaden_row<T>(a.in + row * a.n_v, a.out + row * a.n_v, a.n_v, a.sigma[row], lds_row);
 }
 
 // ---- per (ray, sub-beam): attenuation of the spectrum (doppler_scatter.py:297-305, 372-384)

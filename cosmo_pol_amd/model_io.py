@@ -30,6 +30,8 @@ are taken as they are -- or the raw model output, from which they are derived he
 (COSMO's thermodynamic constants; *parity unpinned*: pycosmo's own expressions are not in
 /root/reference.)  W on half levels (nz + 1) is averaged onto full levels; `level 0 = model
 top` as in COSMO output.  Full-level heights are the means of the adjacent half levels.
+The eddy dissipation rate `EDR` (radar_operator.py:251-254) is read under that name, as the file holds it, when the
+caller asks for it (`want_edr`: Doppler scheme 3 with the turbulence correction); a file without it is not an error.
 """
 import os
 
@@ -165,7 +167,7 @@ def derive(raw, want_2mom, want_refractivity):
     return out
 
 
-def read_model_file(filename, cfilename=None, want_refractivity=False):
+def read_model_file(filename, cfilename=None, want_refractivity=False, want_edr=False):
     """-> dict(data={name: [nz, ny, nx] float32}, zlevels [nz, ny, nx] float32, proj_info, resolution (dlon, dlat),
     time, scheme '1mom' | '2mom', derived_from_raw bool).  Raises ValueError like the reference when a necessary
     variable is missing (radar_operator.py:264-275)."""
@@ -191,6 +193,12 @@ def read_model_file(filename, cfilename=None, want_refractivity=False):
             if raw['W'].shape[0] == nz + 1:                      # W on half levels
                 raw['W'] = (0.5 * (raw['W'][:-1].astype(np.float64) + raw['W'][1:])).astype(np.float32)
             data = derive(raw, two_mom, want_refractivity)
+        if want_edr and 'EDR' in names:
+            # the eddy dissipation rate, taken as the file holds it (on half levels: averaged onto the full ones, like W)
+            edr = _levels_first(src.get('EDR'))
+            if edr.shape[0] == data['T'].shape[0] + 1:
+                edr = (0.5 * (edr[:-1].astype(np.float64) + edr[1:])).astype(np.float32)
+            data['EDR'] = edr
         nz, ny, nx = data['T'].shape
         for k, v in data.items():
             if v.shape != (nz, ny, nx):

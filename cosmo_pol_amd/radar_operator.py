@@ -471,7 +471,7 @@ class RadarOperator(object):
         pointer.  ValueError when a necessary variable is missing, as in the reference (:264-275)."""
         from . import model_io
         want_n = self.__config['refraction']['scheme'] == 2
-        m = model_io.read_model_file(filename, cfilename, want_refractivity=want_n)
+        m = model_io.read_model_file(filename, cfilename, want_refractivity=want_n, want_edr=self._wants_edr())
         if want_n and 'N' not in m['data']:
             # (radar_operator.py:237-247)
             print('Necessary variables for computation of atm. refractivity were not found in file. '
@@ -481,12 +481,25 @@ class RadarOperator(object):
         self.load_model_arrays(m['data'], m['zlevels'], m['proj_info'], m['resolution'], time=m['time'])
         print('-------done------')
 
+    def _wants_edr(self):
+        """The eddy dissipation rate is a model variable only for the turbulence broadening of the Doppler spectrum
+        (radar_operator.py:251-254)."""
+        d = self.__config['doppler']
+        return d['scheme'] == 3 and d['turbulence_correction'] == 1
+
     def load_model_arrays(self, data, zlevels, proj_info, resolution, time=None):
         """data: {name: [nz, ny, nx] float32} with the names of the reference
-        (U, V, W, QR_v, QS_v, QG_v, QI_v, RHO, T [+ QH_v, QN*_v]); zlevels
+        (U, V, W, QR_v, QS_v, QG_v, QI_v, RHO, T [+ QH_v, QN*_v] [+ EDR]); zlevels
         [nz, ny, nx] (level 0 = model top); proj_info with Lo1, La1, Lo2, La2,
         Latitude_of_southern_pole, Longitude_of_southern_pole; resolution
-        (dlon, dlat)."""
+        (dlon, dlat).  EDR (eddy dissipation rate) is staged only with Doppler scheme 3 and
+        doppler/turbulence_correction = 1; without it that correction is switched off with the reference's notice."""
+        if self._wants_edr() and 'EDR' not in data:
+            # (radar_operator.py:255-262: the reference edits its configuration in the same way)
+            print('Necessary variable for correction of turbulence broadening: Eddy dissipitation rate '
+                  'was not found in file. No  turbulence correction will be done.')
+            self.__config['doppler']['turbulence_correction'] = 0
+            self._cache = {}
         two_mom = all(k in data for k in hyd.BASE_VARIABLES_2MOM)
         missing = [k for k in hyd.BASE_VARIABLES if k not in data]
         if missing:
@@ -511,6 +524,8 @@ class RadarOperator(object):
         conf = self.__config
         self._drop_lanes()
         names = hyd.variable_list(conf)
+        if self._wants_edr() and 'EDR' in self.dic_vars:
+            names = names + ['EDR']            # last: the indices of every other variable stay what they are without it
         p = self._proj
         llc = np.asarray((float(p['Lo1']), float(p['La1']))).astype('float32')
         urc = np.asarray((float(p['Lo2']), float(p['La2']))).astype('float32')
@@ -583,8 +598,44 @@ class RadarOperator(object):
 
     # ------------------------------------------------------------------ per-radial seam
     def _column_names(self):
-        """Variable order of the columns: the staged model's, or the configuration's when no model is loaded."""
-        return list(self._staged_vars) if self._model_staged else hyd.variable_list(self.__config)
+        """Variable order of the columns: the staged model's, or the configuration's when no model is loaded (with the
+        turbulence broadening of the Doppler spectrum: followed by EDR)."""
+        if self._model_staged:
+            self._sync_edr()
+            return list(self._staged_vars)
+        return hyd.variable_list(self.__config) + (['EDR'] if self._wants_edr() else [])
+
+    def _sync_edr(self):
+        """EDR is staged exactly when the configuration in force broadens by turbulence: a configuration set after the
+        model was loaded restages the cube, or switches the correction off when the model has no EDR."""
+        want = self._wants_edr()
+        if want and 'EDR' not in self.dic_vars:
+            print('Necessary variable for correction of turbulence broadening: Eddy dissipitation rate '
+                  'was not found in file. No  turbulence correction will be done.')
+            self.__config['doppler']['turbulence_correction'] = 0
+            self._cache = {}
+            want = False
+        if want != ('EDR' in self._staged_vars):
+            self._stage_model()
+
+    def _fill_broadening(self, p, names, range0):
+        """The broadening fields of cpol_sweep_params for a scheme-3 launch (doppler_scatter.py:360-369, 727-777): the
+        constants as the reference's statements give them."""
+        conf = self.__config
+        turb = bool(conf['doppler']['turbulence_correction']) and 'EDR' in names
+        motion = bool(conf['doppler']['motion_correction'])
+        if not (turb or motion):
+            return
+        bw = conf['radar']['3dB_beamwidth']
+        va = self.constants.VARRAY
+        p.turbulence_correction, p.motion_correction = int(turb), int(motion)
+        p.var_edr = names.index('EDR') if turb else -1
+        p.range0 = range0
+        p.sigma_r = float(0.35 * conf['radar']['radial_resolution'])
+        p.sigma_theta = float(np.deg2rad(bw) / (4. * np.sqrt(np.log(2))))
+        p.motion_num = float(self.constants.WAVELENGTH / 100. * conf['radar']['antenna_speed'])
+        p.motion_den = float(2 * np.pi * np.deg2rad(bw))
+        p.v_res = float(va[2] - va[1])
 
     def interpolate_rays(self, azimuths, elevations, melting=True, on_device=False, lane=0):
         """The first half of simulate_rays (cpol_interp_subbeams): the sub-beam columns of the rays (az[i], el[i]) as the
@@ -797,6 +848,7 @@ class RadarOperator(object):
             cols.varray = varray.ctypes.data
             p.n_vbins = len(varray)
             p.c_spectrum = float(self.constants.WAVELENGTH ** 4 / (np.pi ** 5 * conf['radar']['K_squared'] ** 2))
+            self._fill_broadening(p, names, float(self.constants.RANGE_RADAR[0]))
         p.geometry_mode = N.GEOM_GROUND_43
         p.range_step = float(conf['radar']['radial_resolution'])
         p.wavelength = float(self.constants.WAVELENGTH)
@@ -885,6 +937,8 @@ class RadarOperator(object):
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
                   pinned=False, subbeams=None):
+        if self._model_staged:
+            self._sync_edr()
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -924,11 +978,6 @@ class RadarOperator(object):
             doppler = (conf['doppler']['scheme'] in (1, 2, 3) and conf['radar'].get('type') != 'GPM'
                        and mode != N.GEOM_SPACEBORNE)
             spectrum = doppler and conf['doppler']['scheme'] == 3
-            if spectrum and (conf['doppler']['turbulence_correction'] or conf['doppler']['motion_correction']):
-                # both corrections are dead upstream: spectral_width_turb / _motion read a module-level
-                # CONFIG that is still None (doppler_scatter.py:24, 737, 771), EDR is never loaded
-                raise NotImplementedError('doppler/turbulence_correction and doppler/motion_correction '
-                                          'raise in the reference as well; not reproduced')
             p.simulate_doppler = int(conf['doppler']['scheme']) if doppler else 0
             vi = {v: i for i, v in enumerate(self._staged_vars)}
             p.var_u, p.var_v, p.var_w = vi['U'], vi['V'], vi['W']
@@ -956,6 +1005,8 @@ class RadarOperator(object):
             p.k_squared = float(conf['radar']['K_squared'])
             p.radial_res = float(conf['radar']['radial_resolution'])
             p.c_zh = float(self.constants.WAVELENGTH ** 4 / (np.pi ** 5 * conf['radar']['K_squared']))
+            if spectrum:
+                self._fill_broadening(p, list(self._staged_vars), range0)
 
             thr = (self._cached(('sens', n_gates),
                                 lambda: geo.sensitivity_threshold(conf, self.constants, n_gates))
@@ -997,7 +1048,7 @@ class RadarOperator(object):
         if version and paths is None and site is None:
             p, t, keep, doppler, spectrum, varray = self._cached(
                 ('prepared', version, n_gates, range0, mode, bool(apply_sensitivity), want_model, device_outputs is not None,
-                 int(self.debug_flags)),
+                 int(self.debug_flags), self._staged_serial),
                 prepare, lru=16)
         else:
             p, t, keep, doppler, spectrum, varray = prepare()

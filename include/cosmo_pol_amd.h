@@ -185,6 +185,19 @@ typedef struct {
                                    form (4 passes, reciprocal roots + Newton, short series): what
                                    tests/test_gpu_fullsize.py and tools/fast_sub_check.py compare the short form with */
     double  c_spectrum;         /* wavelength^4 / (pi^5 K^2 K^2)  (doppler_scatter.py:709) */
+    /* Doppler scheme 3: broadening of every sub-beam's spectrum by turbulence and antenna motion
+       (doppler_scatter.py:360-369, 727-801).  All zero = off: a caller that zero-initialises the struct and knows nothing of
+       these fields gets the unbroadened spectrum.  Either switch outside scheme 3, turbulence without a valid var_edr, or a
+       switch with v_res <= 0 is CPOL_ERR_ARG (the context stays usable). */
+    int32_t turbulence_correction;  /* 1: add spectral_width_turb(RANGE_RADAR, EDR) to the width of every gate          */
+    int32_t motion_correction;      /* 1: add spectral_width_motion(elevation)                                         */
+    int32_t var_edr;                /* staged-variable index of the eddy dissipation rate (read only with turbulence)  */
+    int32_t pad_broaden_;
+    double  sigma_r;                /* 0.35 * radial_resolution [m]                                                    */
+    double  sigma_theta;            /* deg2rad(3dB_beamwidth) / (4 sqrt(ln 2))                                         */
+    double  motion_num;             /* (wavelength / 100) * antenna_speed -- the reference's statement, mm / 100       */
+    double  motion_den;             /* 2 pi deg2rad(3dB_beamwidth)                                                     */
+    double  v_res;                  /* VARRAY[2] - VARRAY[1] [m/s]: sigma in bins = width / v_res                      */
 } cpol_sweep_params;
 
 #define CPOL_DEBUG_EXACT_SUBBEAMS 1
@@ -401,6 +414,14 @@ CPOL_API int  cpol_stage_spectrum_tables(cpol_ctx *ctx, int slot, const float *r
  * sentinels (-9999 above the model top, NaN below topography). */
 CPOL_API int  cpol_interp_points(cpol_ctx *ctx, int n, const float *coords, const float *heights,
                         float *out);
+
+/* The filter of the Doppler-spectrum broadening on explicit rows (the device function the sweep runs, one row per
+ * workgroup): rows [n_rows][n_v] float32, sigma_bins [n_rows] float64 (standard deviation in bins) -> out [n_rows][n_v]
+ * float32 = scipy.ndimage.gaussian_filter(row, sigma) (truncate 4, mode 'reflect', any radius), rescaled to the float32
+ * sum of the input row; a row without power becomes NaN; sigma <= 1e-15 or NaN filters as the identity.  Host
+ * buffers; n_v in [2, 4097].  Needs no staged model or tables. */
+CPOL_API int  cpol_broaden_rows(cpol_ctx *ctx, const float *rows, int n_rows, int n_v, const double *sigma_bins,
+                       float *out);
 
 /* fills per-ray tables with libm (C callers); Python callers use numpy.
  * traj_out: [n_rays][n_vnodes][CPOL_TRAJ_STRIDE] doubles (el_rad, sin el, cos el, el_deg);
