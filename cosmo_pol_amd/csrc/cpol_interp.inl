@@ -960,11 +960,18 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
 #if CPOL_GATE1_PRESENT
     unsigned pres = 0;                                     // (KEEP = false: bit s = this gate has pres_var[s] > 0)
 #endif
-    if (g.status == 0) {
+    // The mask the sub-beam carries: the geometry's, or -- inside the model -- the one the reference reads off the interpolated
+    // VALUES of variable 0 (interpolation.py:398-411: `== -9999` -> +1, NaN -> -1, then every variable NaN at a masked gate).  A
+    // gate all of whose eight neighbours hold -9999 interpolates to exactly -9999; one at the edge of such a block mixes the
+    // sentinel with data, matches neither test and stays valid with its huge negative value, as in the reference.
+    int status = g.status;
+    if (status == 0) {
+        float v0 = 0.0f;
         int v = 0;
         for (; v + 4 <= m.n_vars; v += 4) {
             float o[4];
             gate_value4(m, g, h32, v, o);
+            if (v == 0) v0 = o[0];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (KEEP) sv[(v + j) * blockDim.x] = o[j];
@@ -977,6 +984,7 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
         }
         for (; v < m.n_vars; ++v) {
             const float o = gate_value(m, g, h32, v);
+            if (v == 0) v0 = o;
             if (KEEP) sv[v * blockDim.x] = o;
             else a.vals[(long)v * n_sbg + sbg] = o;
 #if CPOL_GATE1_PRESENT
@@ -984,12 +992,19 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
                 for (int s = 0; s < a.n_pres; ++s) pres |= (a.pres_var[s] == v && o > 0.f) ? 1u << s : 0u;
 #endif
         }
-    } else {
+        if (v0 == -9999.0f) status = 1;
+        else if (!(v0 == v0)) status = -1;
+#if CPOL_GATE1_PRESENT
+        if (status != 0) pres = 0;                         // (a masked gate holds no item)
+#endif
+    }
+    if (status != 0) {
+        // (KEEP: the caller drops its copy of a gate whose status is not 0)
         for (int v = 0; v < m.n_vars; ++v)
             if (!KEEP || ((a.store_mask >> v) & 1u)) a.vals[(long)v * n_sbg + sbg] = qnan;
     }
     ITRACE(itr, 5);                                        // the variables gathered and interpolated (KEEP: in LDS)
-    a.mask[sbg] = (signed char)g.status;
+    a.mask[sbg] = (signed char)status;
 
     if (EXPORT) {
         x->lats[sbg] = lat_deg; x->lons[sbg] = lon_deg;
@@ -1025,7 +1040,7 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     {
         ITRACE(itr, 6);                                    // everything stored
         const unsigned long w = ((unsigned long)blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64;
-        const unsigned long long n_ok = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(g.status == 0));
+        const unsigned long long n_ok = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(status == 0));
         if ((threadIdx.x & 63) == 0 && w < CPOL_SUBSUM_TRACE_N) {
             for (int q = 0; q < 7; ++q) g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + q] = itr[q];
             g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
@@ -1033,7 +1048,7 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
         }
     }
 #endif
-    return g.status;
+    return status;
 }
 
 __global__ __launch_bounds__(256) CPOL_INTERP_ATTR void k_interp_sweep(ModelDev m, InterpArgs a)

@@ -728,7 +728,9 @@ class RadarOperator(object):
             values = {k: (c[k][0, s].astype(np.float64) if k in ('QmS_v', 'QmG_v') else c[k][0, s]) for k in names}
             r = Radial(values, c['mask'][0, s].astype(np.float64), c['lats'][0, s], c['lons'][0, s], c['dist'][0, s],
                        c['heights'][0, s], elev_profile=c['elev'][0, s], quad_pt=[float(x) for x in c['quad_pts'][0, s]],
-                       quad_weight=(w[0, s] if np.ndim(w) == 3 else float(w[s])))
+                       # (a NumPy float64 as the reference's `weights[i, j]`: integrate_radials then forms the float32 values'
+                       # products in float64, interpolation.py:60-75; a Python float would leave them in float32)
+                       quad_weight=(w[0, s] if np.ndim(w) == 3 else np.float64(w[s])))
             if 'mask_ml' in c:
                 r.mask_ml = c['mask_ml'][0, s].astype(bool)
                 r.has_melting = bool(c['has_melting'][0, s])

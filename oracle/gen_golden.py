@@ -342,6 +342,138 @@ RADIAL_CASES.update({
                          'integration': {'nh_GH': 3, 'nv_GH': 1}}, 300.0, 40.0, ('R', 'S', 'G', 'I'), False),
 })
 
+# ---- bad model values (NaN, the reference's own -9999 sentinel, negative or off-table values) ----
+# A bad-value case is an existing case's configuration plus a deterministic planting applied to the synthetic cube.  One
+# planting is (variable, value, r_lo, r_hi): every level of the grid columns whose distance from the centre of the cube --
+# the radar site -- lies in [r_lo, r_hi) grid cells takes `value`; 'neg' negates what is there.  Rings, so that every
+# azimuth and every sub-beam of a radial crosses them.  (One cell of the test cube is ~2.2 km.)
+PLANTINGS = {
+    # data-born masks (interpolation.py:398-411) under melting + ice: NaN / -9999 in variable 0, NaN in W (RVEL alone)
+    'bad_c3_masks': ('c3_melt_ice', [('U', np.nan, 3.0, 5.0), ('U', -9999.0, 8.0, 12.5), ('W', np.nan, 14.0, 16.0)]),
+    # mask 0, bad values: NaN in a mass density / T / RHO, negative mass density, T off both T axes (rain below and above
+    # 262-314 K near the radar, snow below and above 200-276 K farther out)
+    'bad_c3_values': ('c3_melt_ice', [('T', 150.0, 0.0, 1.5), ('T', 330.0, 2.5, 3.5), ('QR_v', np.nan, 4.5, 5.5),
+                                      ('QS_v', 'neg', 8.0, 9.5), ('T', np.nan, 11.0, 12.0), ('T', 150.0, 13.5, 14.5),
+                                      ('T', 330.0, 15.5, 16.5), ('RHO', np.nan, 17.5, 18.5)]),
+    # sub-beams: both data-born masks, a NaN and a negative mass density seen by 3 x 5 sub-beams at different ranges
+    'bad_c4_sub15': ('c4_subbeams', [('U', np.nan, 3.0, 4.5), ('QR_v', np.nan, 5.0, 6.5), ('U', -9999.0, 7.5, 15.0),
+                                        ('QG_v', 'neg', 15.0, 17.0)]),
+    # scheme 'ml' with melting: negative rain, wet fractions below the first and above the last node of the wc axis (rain /
+    # snow + graupel of 1e-8 / 1e-9 kg m-3 against ~1e-3 of the partner), a NaN partner of the melting scheme
+    'bad_q_ml': ('q_ml', [('QR_v', 'neg', 0.0, 1.5), ('QS_v', 1e-9, 3.0, 5.0), ('QG_v', 1e-9, 3.0, 5.0),
+                          ('QR_v', 1e-8, 6.0, 7.5), ('QG_v', np.nan, 8.5, 9.5), ('U', np.nan, 11.0, 12.5)]),
+    # 2-moment: QN zero, negative and NaN under a positive Q; a NaN mass density
+    'bad_c5_2mom': ('c5_2mom', [('QNR_v', 0.0, 0.5, 2.8), ('QNR_v', 'neg', 3.5, 4.5), ('QNS_v', 0.0, 5.0, 7.3),
+                                ('QNS_v', 'neg', 7.6, 8.4), ('QNG_v', np.nan, 8.8, 9.4), ('QS_v', np.nan, 9.8, 10.4),
+                                ('QNI_v', np.nan, 11.5, 12.5)]),
+    # Doppler spectrum with sub-beams (35 deg: ~0.11 cells per gate, 6.7 cells in all): NaN in W and in U
+    'bad_d3_ice_sub': ('d3_1mom_ice_sub', [('W', np.nan, 2.4, 3.0), ('U', np.nan, 6.0, 7.5)]),
+}
+BAD_VALUE_CASES = list(PLANTINGS) + ['bad_hi_elev_fold']
+
+for _name, (_base, _p) in PLANTINGS.items():
+    RADIAL_CASES[_name] = RADIAL_CASES[_base]
+# clean data, 89.6 deg: the upper vertical quadrature node looks beyond the zenith, its elevation is folded to 180 - e
+# (doppler_scatter.py:173-176)
+RADIAL_CASES['bad_hi_elev_fold'] = (
+    {'radar': {'range': 20000, 'radial_resolution': 250},
+     'microphysics': {'with_ice_crystals': 0, 'with_melting': 0, 'with_attenuation': 0},
+     'integration': {'nh_GH': 1, 'nv_GH': 3}}, 10.0, 89.6, ('R', 'S', 'G'), False)
+
+
+# what each bad-value case is there for: effect -> counted by coverage_counts() from the fixture alone, at least
+# MIN_EFFECT_GATES gates each (and, every case, at least a third of the gates with a finite ZH)
+MIN_EFFECT_GATES = 5
+MIN_COUNT = {'spectrum_rows_kept': 20, 'spectrum_bins_kept': 40}          # effects with a minimum of their own
+COVERAGE = {
+    'bad_c3_masks': ['mask_m1_data', 'mask_p1_data', 'edge_m9999', 'rvel_nan_W'],
+    'bad_c3_values': ['nan_QR_v', 'neg_QS_v', 'nan_T', 'nan_RHO', 'mask0_nan_ZH', 't_below_axes', 't_above_axes'],
+    'bad_c4_sub15': ['mask_m1_data', 'mask_p1_data', 'mask_m1_two_subbeams', 'mask_p1_two_subbeams', 'edge_m9999',
+                        'nan_QR_v', 'neg_QG_v'],
+    'bad_q_ml': ['mask_m1_data', 'mask_m1_two_subbeams', 'neg_QR_v', 'nan_QG_v', 'mask0_nan_ZH', 'wc_first_bin',
+                 'wc_below_axis', 'wc_last_bin'],
+    'bad_c5_2mom': ['zero_QNR_v', 'neg_QNR_v', 'zero_QNS_v', 'neg_QNS_v', 'nan_QNG_v', 'nan_QNI_v', 'nan_QS_v',
+                    'mask0_nan_ZH'],
+    'bad_d3_ice_sub': ['mask_m1_data', 'mask_m1_two_subbeams', 'rvel_nan_W', 'spectrum_rows_kept',
+                       'spectrum_bins_kept', 'spectrum_rows_lost'],
+    'bad_hi_elev_fold': ['elev_above_90'],
+}
+
+
+def coverage_counts(d):
+    """Gates of a bad-value fixture (the arrays of its .npz) that show each effect.  A data-born mask counts only where
+    the reference's run on the UNPLANTED cube (clean_*) has mask 0: geometry cannot stand in for it."""
+    with np.errstate(invalid='ignore'):
+        zh = np.asarray(d['obs_ZH'])
+        fin = np.isfinite(zh)
+        m, mc = np.asarray(d['obs_mask']), np.asarray(d['clean_obs_mask'])
+        sm, smc = np.asarray(d['sub_mask_all']), np.asarray(d['clean_sub_mask_all'])
+        c0 = np.asarray(d['subc_mask']) == 0                  # the central sub-beam
+        out = {'finite_ZH': int(fin.sum()), 'n_gates': int(zh.size),
+               'mask_m1_data': int(((m == -1) & (mc == 0)).sum()),
+               'mask_p1_data': int(((m == 1) & (mc == 0)).sum()),
+               'mask0_nan_ZH': int(((m == 0) & ~fin & np.isfinite(d['clean_obs_ZH'])).sum()),
+               'edge_m9999': int((c0 & (np.asarray(d['subc_U']) < -100.)).sum()),
+               'rvel_nan_W': int((fin & c0 & np.isnan(d['subc_W']) & np.isnan(d['obs_RVEL'])
+                                  & np.isfinite(d['clean_obs_RVEL'])).sum()),
+               't_below_axes': int((fin & (np.asarray(d['subc_T']) < 200.)).sum()),
+               't_above_axes': int((fin & (np.asarray(d['subc_T']) > 314.)).sum())}
+        # the second best sub-beam: >= MIN_EFFECT_GATES there means more than one sub-beam crosses the planting
+        for tag, val in (('m1', -1), ('p1', 1)):
+            per_sub = np.sort(((sm == val) & (smc == 0)).sum(axis=1))
+            out['mask_%s_two_subbeams' % tag] = int(per_sub[-2]) if per_sub.size > 1 else 0
+        for k in d.keys() if hasattr(d, 'keys') else d.files:
+            if k.startswith('subc_') and k not in ('subc_mask', 'subc_lats', 'subc_lons', 'subc_s', 'subc_h', 'subc_e'):
+                v, a = k[5:], np.asarray(d[k])
+                out['nan_' + v] = int((c0 & np.isnan(a)).sum())
+                out['neg_' + v] = int((c0 & (a < 0)).sum())
+                if v.startswith('QN'):
+                    out['zero_' + v] = int((c0 & (a == 0) & (np.asarray(d['subc_Q' + v[2:]]) > 0)).sum())
+        for h in ('mS', 'mG'):
+            if 'subc_fwet_' + h in d:
+                fw, q = np.asarray(d['subc_fwet_' + h]), np.asarray(d['subc_Q%s_v' % h])
+                # (the wc axis of the melting tables: linspace(1e-3, 0.999, 100), bin = floor, clipped: lut.py:336-341)
+                b = np.floor((fw - 1e-3) / (0.998 / 99))
+                out['wc_first_bin'] = out.get('wc_first_bin', 0) + int((fin & (q > 0) & (b <= 0)).sum())
+                out['wc_below_axis'] = out.get('wc_below_axis', 0) + int((fin & (q > 0) & (b < 0)).sum())
+                out['wc_last_bin'] = out.get('wc_last_bin', 0) + int((fin & (q > 0) & (b >= 99)).sum())
+        e_all = np.asarray(d['sub_e_all'])
+        out['elev_above_90'] = int(((e_all > 90.) & (sm == 0)).sum(axis=1).max())
+        if 'obs_DSPECTRUM' in d:
+            sp, spc = np.asarray(d['obs_DSPECTRUM']), np.asarray(d['clean_obs_DSPECTRUM'])
+            row = lambda a: np.isfinite(a).all(axis=1) & (a != 0).any(axis=1)
+            out['spectrum_rows_kept'] = int(row(sp).sum())
+            out['spectrum_bins_kept'] = int((np.isfinite(sp) & (sp != 0)).sum())
+            out['spectrum_rows_lost'] = int((row(spc) & ~row(sp)).sum())
+    return out
+
+
+def coverage_failures(name, d):
+    c = coverage_counts(d)
+    bad = ['%s: %d < %d' % (k, c.get(k, 0), MIN_COUNT.get(k, MIN_EFFECT_GATES)) for k in COVERAGE[name]
+           if c.get(k, 0) < MIN_COUNT.get(k, MIN_EFFECT_GATES)]
+    if 3 * c['finite_ZH'] < c['n_gates']:
+        bad.append('finite ZH at %d of %d gates' % (c['finite_ZH'], c['n_gates']))
+    return bad, c
+
+
+def plant_bad_values(cube, plantings):
+    """Applies `plantings` (PLANTINGS) to the data of a synthetic cube, in place."""
+    any_var = next(iter(cube['data'].values()))
+    ny, nx = any_var.shape[1:]
+    yy, xx = np.meshgrid(np.arange(ny) - (ny - 1) / 2., np.arange(nx) - (nx - 1) / 2., indexing='ij')
+    r = np.hypot(yy, xx)
+    for var, value, r_lo, r_hi in plantings:
+        sel = (r >= r_lo) & (r < r_hi)
+        a = cube['data'][var]
+        if isinstance(value, str):
+            assert value == 'neg'
+            a[:, sel] = -a[:, sel]
+        else:
+            a[:, sel] = np.float32(value)
+    return cube
+
+
 LUT_KW = dict(seed=20260301, n_e=8, n_t=None)
 
 
@@ -355,9 +487,9 @@ def write_antenna_csv(path=ANTENNA_CSV):
     np.savetxt(path, np.column_stack([ang, 10 * np.log10(p)]), delimiter=',', fmt='%.6f')
 
 
-def radial_case_inputs(name):
+def radial_case_inputs(name, clean=False):
     """Deterministic inputs of an end-to-end radial case (shared with
-    tests/)."""
+    tests/).  clean: a bad-value case without its planting."""
     from cosmo_pol_amd import synthetic
     over, az, el, hyds, two = RADIAL_CASES[name]
     base = {'radar': {'coords': [46.5, 7.5, 1000], 'frequency': 5.6, '3dB_beamwidth': 1.,
@@ -366,6 +498,8 @@ def radial_case_inputs(name):
     for sec, dd in over.items():
         base.setdefault(sec, {}).update(dd)
     cube = synthetic.small_test_cube(hydrometeors=hyds, two_moment=two, **CUBE_KW)
+    if name in PLANTINGS and not clean:
+        plant_bad_values(cube, PLANTINGS[name][1])
     return base, az, el, cube, two
 
 
@@ -391,12 +525,26 @@ def gen_radials(out, only_cases=None):
             if h not in lut_cache[key]:
                 lut_cache[key][h] = synthetic.make_lut(h, freq, scheme, **LUT_KW)
         luts = ref_luts({h: lut_cache[key][h] for h in hl})
-        dv = ref_shim.KeyListDict()
-        for n in (ORDER_2MOM if two else ORDER):
-            dv[n] = ref_shim.ModelVar(n, cube['data'][n].copy(), cube['zlevels'],
-                                      cube['proj_info'], cube['resolution'])
-        subs = get_interpolated_radial(dv, az, el, N=0)
+        def interpolate(cube):
+            dv = ref_shim.KeyListDict()
+            for n in (ORDER_2MOM if two else ORDER):
+                dv[n] = ref_shim.ModelVar(n, cube['data'][n].copy(), cube['zlevels'],
+                                          cube['proj_info'], cube['resolution'])
+            return get_interpolated_radial(dv, az, el, N=0)
+        subs = interpolate(cube)
         d = dict(azimuth=az, elevation=el, n_sub=len(subs))
+        if name in BAD_VALUE_CASES:
+            # every sub-beam's mask and elevation (before get_radar_observables folds it in place), and the reference on
+            # the UNPLANTED cube: what coverage_counts() needs
+            d['sub_mask_all'] = np.array([sb.mask for sb in subs])
+            d['sub_e_all'] = np.array([sb.elev_profile for sb in subs])
+            csubs = interpolate(radial_case_inputs(name, clean=True)[3])
+            d['clean_sub_mask_all'] = np.array([sb.mask for sb in csubs])
+            cobs = get_radar_observables(csubs, luts)
+            d['clean_obs_mask'] = cobs.mask
+            for n in ('ZH', 'RVEL', 'DSPECTRUM'):
+                if n in cobs.values:
+                    d['clean_obs_' + n] = np.asarray(cobs.values[n])
         ng = len(subs[0].dist_profile)
         d['quad_w'] = np.array([np.broadcast_to(sb.quad_weight, (ng,)) for sb in subs])
         d['quad_pts'] = np.array([sb.quad_pt for sb in subs], dtype=np.float64)
@@ -440,6 +588,10 @@ def gen_radials(out, only_cases=None):
             d['cutll_' + n] = np.asarray(cut.values[n])
         print(name, 'n_sub', len(subs), 'valid items', n_valid,
               'finite ZH', int(np.isfinite(obs.values['ZH']).sum()), '/', len(obs.values['ZH']))
+        if name in BAD_VALUE_CASES:
+            bad, counts = coverage_failures(name, d)
+            print('  coverage', {k: counts[k] for k in COVERAGE[name]})
+            assert not bad, (name, bad)
         out['radial_' + name] = d
 
 

@@ -20,7 +20,51 @@ CASES = {
     # (119 gates of 300 m at 35 deg: the sub-beams leave the top at gates 120 / 119 / 117)
     'd3_turb_masked': ('d3_1mom_ice_sub', {'radar': {'range': 35700}, 'integration': {'nh_GH': 1, 'nv_GH': 3},
                                            'doppler': {'turbulence_correction': 1}}, None),
+    # bad values in the model data under the turbulence switch (see PLANTINGS below): the base case is d3_turb_motion_sub
+    'bad_d3_turb_edr': ('d3_1mom_ice_sub', {'doppler': {'turbulence_correction': 1, 'motion_correction': 1}}, None),
+    'bad_d3_turb_umask': ('d3_1mom_ice_sub', {'doppler': {'turbulence_correction': 1, 'motion_correction': 1}}, None),
 }
+
+# rings of grid columns (oracle/gen_golden.py::plant_bad_values) planted into the cube AFTER the EDR field was added.
+# NaN in EDR leaves the mask at 0 and makes the turbulence width of those gates NaN; NaN in U masks the gates (-1, from the
+# data) and with them EDR.  Either way `np.sum(width) > 0` is false and the sub-beam stays unbroadened (quirk Q13) -- every
+# sub-beam, since a ring is crossed by all of them -- while d3_turb_motion_sub, the same configuration on the clean cube, is
+# broadened in all three.
+PLANTINGS = {
+    'bad_d3_turb_edr': [('EDR', np.nan, 2.4, 3.0)],
+    'bad_d3_turb_umask': [('U', np.nan, 6.0, 7.5)],
+}
+CLEAN_TWIN = {'bad_d3_turb_edr': 'd3_turb_motion_sub', 'bad_d3_turb_umask': 'd3_turb_motion_sub'}
+MIN_EFFECT_GATES = 5
+
+
+def coverage_failures(name, g, clean):
+    """What a planted broadening fixture `g` must show, against the fixture `clean` of its twin on the unplanted cube; ->
+    (list of unmet conditions, counts).  Checked by the generator and asserted again by tests/test_bad_value_fixtures.py."""
+    n_sub = int(g['n_sub'])
+    c = {'switch': [int(g['sub%d_switch' % s]) for s in range(n_sub)],
+         'clean_switch': [int(clean['sub%d_switch' % s]) for s in range(n_sub)]}
+    nan_edr_mask0, born = [], []
+    for s in range(n_sub):
+        m, mc = g['sub%d_mask' % s], clean['sub%d_mask' % s]
+        nan_edr_mask0.append(int(((m == 0) & np.isnan(g['sub%d_EDR' % s]) & np.isnan(g['sub%d_width' % s])).sum()))
+        born.append(int(((m == -1) & (mc == 0) & np.isnan(g['sub%d_EDR' % s])).sum()))
+    sp = g['obs_DSPECTRUM']
+    row = np.isfinite(sp).all(axis=1) & (sp != 0).any(axis=1)
+    c.update(nan_edr_mask0=nan_edr_mask0, mask_m1_data=born, rows_kept=int(row.sum()),
+             bins_kept=int((np.isfinite(sp) & (sp != 0)).sum()), finite_ZH=int(np.isfinite(g['obs_ZH']).sum()),
+             n_gates=int(g['obs_ZH'].size), differs_from_clean=not np.array_equal(sp, clean['obs_DSPECTRUM'], equal_nan=True))
+    want = nan_edr_mask0 if name == 'bad_d3_turb_edr' else born
+    bad = []
+    if min(want) < MIN_EFFECT_GATES:
+        bad.append('planting met at %s gates of the sub-beams' % want)
+    if name == 'bad_d3_turb_edr' and any(born):
+        bad.append('NaN EDR must leave the masks alone: %s' % born)
+    if any(c['switch']) or not all(c['clean_switch']):
+        bad.append('switch %s, on the clean cube %s' % (c['switch'], c['clean_switch']))
+    if c['rows_kept'] < 20 or c['bins_kept'] < 40 or 3 * c['finite_ZH'] < c['n_gates'] or not c['differs_from_clean']:
+        bad.append('too little left: %s' % c)
+    return bad, c
 
 
 def edr_field(shape, seed=20261016):
@@ -38,6 +82,8 @@ def case_inputs(name):
         over.setdefault(sec, {}).update(dd)
     if over['doppler'].get('turbulence_correction'):
         cube['data']['EDR'] = edr_field(cube['data']['T'].shape)
+    if name in PLANTINGS:
+        gen_golden.plant_bad_values(cube, PLANTINGS[name])
     return over, az, (el if el_over is None else el_over), cube, two
 
 
