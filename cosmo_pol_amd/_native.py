@@ -117,6 +117,27 @@ class Counters(C.Structure):
                 ('ms_total', C.c_float), ('n_table_items', C.c_int32), ('pad_', C.c_int32)]
 
 
+MAX_VARS, MAX_RAW_FIELDS, MAX_LOAD = 24, 32, 8          # CPOL_MAX_VARS / CPOL_MAX_RAW_FIELDS / CPOL_MAX_LOAD
+RECIPE_COPY, RECIPE_HALF_MEAN, RECIPE_RHO, RECIPE_TIMES_RHO, RECIPE_ZEROS = range(5)
+
+
+class PackedPlane(C.Structure):
+    """cpol_packed_plane: one GRIB-1 message's bit string and scale factors."""
+    _fields_ = [('octets', C.c_void_p), ('n_octets', C.c_int64), ('ref_value', C.c_double), ('bin_scale', C.c_int32),
+                ('dec_scale', C.c_int32), ('n_bits', C.c_int32), ('flip_rows', C.c_int32), ('field', C.c_int32),
+                ('level', C.c_int32)]
+
+
+class PackedModel(C.Structure):
+    """cpol_packed_model: the raw fields of the planes and the recipe of every staged variable."""
+    _fields_ = [('nz', C.c_int32), ('ny', C.c_int32), ('nx', C.c_int32), ('n_fields', C.c_int32),
+                ('field_levels', C.c_int32 * MAX_RAW_FIELDS), ('field_p', C.c_int32), ('field_t', C.c_int32),
+                ('field_qv', C.c_int32), ('field_hhl', C.c_int32), ('n_load', C.c_int32),
+                ('field_load', C.c_int32 * MAX_LOAD), ('n_vars', C.c_int32), ('recipe', C.c_int32 * MAX_VARS),
+                ('source', C.c_int32 * MAX_VARS), ('r_d', C.c_double), ('rv_rd_m1', C.c_double),
+                ('llc', C.c_float * 2), ('urc', C.c_float * 2), ('res', C.c_float * 2), ('south_pole', C.c_double * 2)]
+
+
 EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_set_stream',
            'cpol_get_stream',
            'cpol_synchronize', 'cpol_stage_model', 'cpol_stage_hydro', 'cpol_set_num_hydro',
@@ -124,7 +145,8 @@ EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_
            'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_interp_subbeams', 'cpol_run_columns', 'cpol_counters',
            'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free', 'cpol_host_alloc_near',
            'cpol_device_pci_bus_id', 'cpol_mem_info',
-           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_broaden_rows']
+           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_broaden_rows',
+           'cpol_stage_model_packed', 'cpol_unpack_planes']
 
 TRAJ_STRIDE, GEO_STRIDE, SITE_STRIDE = 4, 8, 8      # CPOL_*_STRIDE of the header
 MELT_DEGREE, MELT_FUNCS = 10, 4                    # CPOL_MELT_DEGREE / CPOL_MELT_FUNCS
@@ -221,6 +243,10 @@ def load_library():
     lib.cpol_stage_model.restype = C.c_int
     lib.cpol_stage_model.argtypes = [vp, C.c_int, C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int,
                                      vp, vp, vp, vp]
+    lib.cpol_stage_model_packed.restype = C.c_int
+    lib.cpol_stage_model_packed.argtypes = [vp, C.POINTER(PackedModel), C.POINTER(PackedPlane), C.c_int]
+    lib.cpol_unpack_planes.restype = C.c_int
+    lib.cpol_unpack_planes.argtypes = [vp, C.POINTER(PackedPlane), C.c_int, C.c_int, C.c_int, vp]
     lib.cpol_stage_hydro.restype = C.c_int
     lib.cpol_stage_hydro.argtypes = [vp, C.c_int, C.POINTER(HydroDesc), vp, vp, vp, vp, C.c_int]
     lib.cpol_stage_doppler_weights.restype = C.c_int
@@ -540,6 +566,39 @@ class Context(object):
                                        _ptr(llc), _ptr(urc), _ptr(res), _ptr(sp))
         self._check(rc, 'cpol_stage_model')
         self.n_vars = len(arrays)
+
+    @staticmethod
+    def packed_planes(planes):
+        """[(octets: uint8 array, R, E, D, n_bits, flip, field, level)] -> (PackedPlane array, what keeps the octets alive)."""
+        arr = (PackedPlane * len(planes))()
+        keep = []
+        for d, (octets, R, E, D, n_bits, flip, field, level) in zip(arr, planes):
+            octets = np.ascontiguousarray(octets, dtype=np.uint8)
+            keep.append(octets)
+            d.octets, d.n_octets = (octets.ctypes.data if octets.size else None), octets.size
+            d.ref_value, d.bin_scale, d.dec_scale, d.n_bits = float(R), int(E), int(D), int(n_bits)
+            d.flip_rows, d.field, d.level = int(bool(flip)), int(field), int(level)
+        return arr, keep
+
+    def unpack_planes(self, planes, ny, nx):
+        """k_grib_unpack on caller planes (see packed_planes; field / level unused) -> float32 [n, ny, nx]."""
+        arr, keep = self.packed_planes(planes)
+        out = np.empty((len(planes), ny, nx), dtype=np.float32)
+        rc = self.lib.cpol_unpack_planes(self.h, arr, len(planes), int(ny), int(nx), _ptr(out))
+        self._check(rc, 'cpol_unpack_planes')
+        return out
+
+    def stage_model_packed(self, model, planes):
+        """model: PackedModel; planes as for packed_planes.  Unpacks, derives and stages on the device."""
+        arr, keep = self.packed_planes(planes)
+        rc = self.lib.cpol_stage_model_packed(self.h, C.byref(model), arr, len(planes))
+        self._check(rc, 'cpol_stage_model_packed')
+        self.n_vars = int(model.n_vars)
+
+    def ingest_times(self):
+        """Milliseconds of the last stage_model_packed: octets to the device, k_grib_unpack, k_model_derive, the whole call."""
+        v = self.debug_read('ingest_times', (4,), np.float64)
+        return {'upload_ms': v[0], 'unpack_ms': v[1], 'derive_ms': v[2], 'total_ms': v[3]}
 
     def stage_hydro(self, slot, desc, table, pre=None, dnu=None, aux=None):
         table = np.ascontiguousarray(table, dtype=np.float64)

@@ -30,6 +30,7 @@
 #include "cpol_final.inl"
 #include "cpol_gate.inl"
 #include "cpol_spectrum.inl"
+#include "cpol_ingest.inl"
 
 namespace {
 
@@ -78,6 +79,7 @@ struct cpol_ctx {
     bool model_staged = false;
     ModelDev model{};
     DevBuf d_H, d_V;
+    double ingest_ms[4] = {0, 0, 0, 0};   // the last cpol_stage_model_packed (cpol_debug_read "ingest_times")
     // hydrometeors
     HydroSet hs{};
     SpecSet ss{};
@@ -952,6 +954,39 @@ int cpol_enable_timing(cpol_ctx *ctx, int on)
     return CPOL_OK;
 }
 
+// a model is staged on the context itself, never on a lane, and not while lanes of it exist
+static bool model_on_lane(cpol_ctx *ctx, const char *who)
+{
+    if (!ctx->parent && !ctx->n_children) return false;
+    ctx->err = std::string(who) + ": not on a lane, and not while lanes of this context exist (cpol_fork)";
+    return true;
+}
+
+// the context bookkeeping behind a freshly written d_H / d_V (cpol_stage_model, cpol_stage_model_packed)
+static void model_staged_tail(cpol_ctx *ctx, int n_vars, int nz, int ny, int nx, size_t h_bytes, const float llc[2],
+                              const float urc[2], const float res[2], const double south_pole[2])
+{
+    ModelDev &m = ctx->model;
+    m.H = (const float *)ctx->d_H.p;
+    m.HT = (const float2 *)((const char *)ctx->d_H.p + h_bytes);
+    m.V = (const float *)ctx->d_V.p;
+    m.n_vars = n_vars; m.nz = nz; m.ny = ny; m.nx = nx;
+    m.llc0 = llc[0]; m.llc1 = llc[1];
+    m.urc0 = urc[0]; m.urc1 = urc[1];
+    m.res0 = res[0]; m.res1 = res[1];
+    m.rres0 = 1.0 / (double)m.res0; m.rres1 = 1.0 / (double)m.res1;      // (IEEE division on the host: correctly rounded)
+    // rotation constants (oracle/cosmo_pol_oracle/geodesy.py: rotation_constants)
+    const double theta = (90.0 + south_pole[0]) * CPOL_DEG, phi = south_pole[1] * CPOL_DEG;
+    const double ct = cos(theta), st = sin(theta), cp = cos(phi), sp = sin(phi);
+    m.ctcp = ct * cp; m.ctsp = ct * sp; m.st = st; m.nsp = -sp; m.cp = cp;
+    m.nstcp = -st * cp; m.stsp = st * sp; m.ct = ct;
+    ctx->model_staged = true;
+    ctx->stage_serial++;
+    // the coordinate polynomials of the resident table sets hold the PREVIOUS model's rotated-pole matrix (round-5 advisor
+    // finding: a second cube with another south pole, the same rays again -> wrong grid cells without an error)
+    for (auto &ts : ctx->tsets) ts.poly_version = 0;
+}
+
 int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const float *zlevels,
                      int nz, int ny, int nx, const float llc[2], const float urc[2],
                      const float res[2], const double south_pole[2])
@@ -962,10 +997,7 @@ int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const 
         return CPOL_ERR_ARG;
     }
     (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
-    if (ctx->parent || ctx->n_children) {
-        ctx->err = "cpol_stage_model: not on a lane, and not while lanes of this context exist (cpol_fork)";
-        return CPOL_ERR_ARG;
-    }
+    if (model_on_lane(ctx, "cpol_stage_model")) return CPOL_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     const long ncell = (long)ny * nx;
     const size_t plane_bytes = (size_t)nz * ncell * sizeof(float);
@@ -988,26 +1020,207 @@ int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const 
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
     free_buf(tmp);
-    ModelDev &m = ctx->model;
-    m.H = (const float *)ctx->d_H.p;
-    m.HT = (const float2 *)((const char *)ctx->d_H.p + h_bytes);
-    m.V = (const float *)ctx->d_V.p;
-    m.n_vars = n_vars; m.nz = nz; m.ny = ny; m.nx = nx;
-    m.llc0 = llc[0]; m.llc1 = llc[1];
-    m.urc0 = urc[0]; m.urc1 = urc[1];
-    m.res0 = res[0]; m.res1 = res[1];
-    m.rres0 = 1.0 / (double)m.res0; m.rres1 = 1.0 / (double)m.res1;      // (IEEE division on the host: correctly rounded)
-    // rotation constants (oracle/cosmo_pol_oracle/geodesy.py: rotation_constants)
-    const double theta = (90.0 + south_pole[0]) * CPOL_DEG, phi = south_pole[1] * CPOL_DEG;
-    const double ct = cos(theta), st = sin(theta), cp = cos(phi), sp = sin(phi);
-    m.ctcp = ct * cp; m.ctsp = ct * sp; m.st = st; m.nsp = -sp; m.cp = cp;
-    m.nstcp = -st * cp; m.stsp = st * sp; m.ct = ct;
-    ctx->model_staged = true;
-    ctx->stage_serial++;
-    // the coordinate polynomials of the resident table sets hold the PREVIOUS model's rotated-pole matrix (round-5 advisor
-    // finding: a second cube with another south pole, the same rays again -> wrong grid cells without an error)
-    for (auto &ts : ctx->tsets) ts.poly_version = 0;
+    model_staged_tail(ctx, n_vars, nz, ny, nx, h_bytes, llc, urc, res, south_pole);
     return CPOL_OK;
+}
+
+// ---------------------------------------------------------------- packed (GRIB-1) model input
+namespace {
+
+size_t packed_slot(const cpol_packed_plane &p) { return p.n_bits ? (((size_t)p.n_octets + 8 + 15) & ~(size_t)15) : 0; }
+
+const char *packed_plane_fault(const cpol_packed_plane &p, long ncell)
+{
+    if (p.n_bits < 0 || p.n_bits > 32) return "n_bits outside 0 ... 32";
+    if (p.n_bits && (!p.octets || p.n_octets < 0 || (unsigned long long)p.n_octets * 8ull < (unsigned long long)ncell * (unsigned)p.n_bits))
+        return "fewer octets than ny * nx * n_bits bits";
+    if (p.dec_scale < -300 || p.dec_scale > 300 || p.bin_scale < -32767 || p.bin_scale > 32767) return "scale factor out of range";
+    return nullptr;
+}
+
+// The octets of every plane into one device arena, each bit string at a 16-byte-aligned start with >= 8 octets of slack
+// behind it (k_grib_unpack reads whole words), and the descriptor table in one upload.  The caller's (pageable, usually
+// file-mapped) memory goes to the runtime's own staging, one copy per plane: page-locked bounce buffers filled by memcpy
+// were 5 % slower.
+int upload_packed(cpol_ctx *ctx, const cpol_packed_plane *planes, int n, const std::vector<long> &out_plane,
+                  DevBuf &arena, DevBuf &desc)
+{
+    std::vector<PackedPlaneDev> pd((size_t)n);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        const cpol_packed_plane &p = planes[i];
+        PackedPlaneDev &d = pd[(size_t)i];
+        d.off = total;
+        d.ref = p.ref_value;
+        d.dec = 1.0;
+        for (int j = 0; j < (p.dec_scale < 0 ? -p.dec_scale : p.dec_scale); ++j) d.dec *= 10.0;
+        d.bin_scale = p.bin_scale;
+        d.dec_sign = (p.dec_scale > 0) - (p.dec_scale < 0);
+        d.n_bits = p.n_bits;
+        d.flip = p.flip_rows != 0;
+        d.out_plane = out_plane[(size_t)i];
+        total += packed_slot(p);
+    }
+    ENSURE(arena, total + 16);
+    int rc = upload(ctx, desc, pd.data(), pd.size() * sizeof(PackedPlaneDev));
+    if (rc != CPOL_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (planes[i].n_bits)
+            HIPCHK(hipMemcpyAsync((char *)arena.p + pd[(size_t)i].off, planes[i].octets, (size_t)planes[i].n_octets,
+                                  hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));      // (pd is this function's: nothing may read it afterwards)
+    return CPOL_OK;
+}
+
+void launch_unpack(cpol_ctx *ctx, const DevBuf &arena, const DevBuf &desc, float *out, int n, int ny, int nx)
+{
+    const long ncell = (long)ny * nx;
+    for (int first = 0; first < n; first += 32768) {           // (grid.y <= 65535)
+        const int m = n - first < 32768 ? n - first : 32768;
+        hipLaunchKernelGGL(k_grib_unpack, dim3((unsigned)cdiv(ncell, 256), (unsigned)m), dim3(256), 0, ctx->stream,
+                           (const unsigned *)arena.p, (const PackedPlaneDev *)desc.p + first, out, ny, nx);
+    }
+}
+
+double wall_ms()
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return 1e3 * (double)ts.tv_sec + 1e-6 * (double)ts.tv_nsec;
+}
+
+}  // namespace
+
+int cpol_unpack_planes(cpol_ctx *ctx, const cpol_packed_plane *planes, int n_planes, int ny, int nx, float *out)
+{
+    if (!ctx || !planes || !out || n_planes < 1 || ny < 1 || nx < 1 || (long)ny * nx >= (1L << 31)) {
+        if (ctx) ctx->err = "cpol_unpack_planes: bad arguments";
+        return CPOL_ERR_ARG;
+    }
+    const long ncell = (long)ny * nx;
+    std::vector<long> out_plane((size_t)n_planes);
+    for (int i = 0; i < n_planes; ++i) {
+        const char *why = packed_plane_fault(planes[i], ncell);
+        if (why) { ctx->err = std::string("cpol_unpack_planes: plane ") + std::to_string(i) + ": " + why; return CPOL_ERR_ARG; }
+        out_plane[(size_t)i] = i;
+    }
+    (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf arena, desc, cube;
+    const size_t cube_bytes = (size_t)n_planes * ncell * sizeof(float);
+    int rc = ensure(ctx, cube, cube_bytes);
+    if (rc == CPOL_OK) rc = upload_packed(ctx, planes, n_planes, out_plane, arena, desc);
+    if (rc == CPOL_OK) {
+        launch_unpack(ctx, arena, desc, (float *)cube.p, n_planes, ny, nx);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out, cube.p, cube_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { ctx->err = std::string("cpol_unpack_planes: ") + hipGetErrorString(e); rc = CPOL_ERR_HIP; }
+    }
+    free_buf(arena); free_buf(desc); free_buf(cube);
+    return rc;
+}
+
+int cpol_stage_model_packed(cpol_ctx *ctx, const cpol_packed_model *m, const cpol_packed_plane *planes, int n_planes)
+{
+    if (!ctx || !m || !planes) {
+        if (ctx) ctx->err = "cpol_stage_model_packed: bad arguments";
+        return CPOL_ERR_ARG;
+    }
+    const int nz = m->nz, ny = m->ny, nx = m->nx, n_vars = m->n_vars, nf = m->n_fields;
+    auto bad = [&](const std::string &why) { ctx->err = "cpol_stage_model_packed: " + why; return CPOL_ERR_ARG; };
+    if (n_vars < 1 || n_vars > CPOL_MAX_VARS || nz < 3 || ny < 2 || nx < 2) return bad("bad shape (need nz >= 3, ny, nx >= 2)");
+    if (nf < 1 || nf > CPOL_MAX_RAW_FIELDS || m->n_load < 0 || m->n_load > CPOL_MAX_LOAD) return bad("bad field counts");
+    // ---- everything is checked before anything changes
+    std::vector<int> base((size_t)nf + 1, 0);
+    for (int f = 0; f < nf; ++f) {
+        if (m->field_levels[f] != nz && m->field_levels[f] != nz + 1) return bad("a raw field must have nz or nz + 1 levels");
+        base[(size_t)f + 1] = base[(size_t)f] + m->field_levels[f];
+    }
+    const int total_planes = base[(size_t)nf];
+    auto full = [&](int f) { return f >= 0 && f < nf && m->field_levels[f] == nz; };
+    auto any = [&](int f) { return f >= 0 && f < nf; };
+    if (!full(m->field_p) || !full(m->field_t) || !full(m->field_qv) || !any(m->field_hhl)) return bad("P, T, QV on nz levels and HHL are needed");
+    for (int j = 0; j < m->n_load; ++j) if (!full(m->field_load[j])) return bad("a condensate field must have nz levels");
+    for (int v = 0; v < n_vars; ++v) {
+        const int r = m->recipe[v], f = m->source[v];
+        if (r == CPOL_RECIPE_COPY || r == CPOL_RECIPE_TIMES_RHO) { if (!full(f)) return bad("COPY / TIMES_RHO need a raw field on nz levels"); }
+        else if (r == CPOL_RECIPE_HALF_MEAN) { if (!any(f) || m->field_levels[f] != nz + 1) return bad("HALF_MEAN needs a raw field on nz + 1 levels"); }
+        else if (r != CPOL_RECIPE_RHO && r != CPOL_RECIPE_ZEROS) return bad("unknown recipe");
+    }
+    if (n_planes != total_planes) return bad("the planes must cover every level of every raw field exactly once");
+    const long ncell = (long)ny * nx;
+    std::vector<long> out_plane((size_t)n_planes);
+    std::vector<char> seen((size_t)total_planes, 0);
+    for (int i = 0; i < n_planes; ++i) {
+        const cpol_packed_plane &p = planes[i];
+        if (!any(p.field) || p.level < 0 || p.level >= m->field_levels[p.field]) return bad("plane " + std::to_string(i) + ": field / level out of range");
+        const int o = base[(size_t)p.field] + p.level;
+        if (seen[(size_t)o]) return bad("plane " + std::to_string(i) + ": this (field, level) came before");
+        seen[(size_t)o] = 1;
+        out_plane[(size_t)i] = o;
+        const char *why = packed_plane_fault(p, ncell);
+        if (why) return bad("plane " + std::to_string(i) + ": " + why);
+    }
+    (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
+    if (model_on_lane(ctx, "cpol_stage_model_packed")) return CPOL_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    const double t_start = wall_ms();
+    const size_t plane_bytes = (size_t)nz * ncell * sizeof(float);
+    const size_t h_bytes = (plane_bytes + 7) & ~(size_t)7;        // + (top, lowest level) per column behind the levels
+    DevBuf arena, desc, cube;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int rc = ensure(ctx, cube, (size_t)total_planes * ncell * sizeof(float));
+    if (rc == CPOL_OK) rc = upload_packed(ctx, planes, n_planes, out_plane, arena, desc);
+    const double t_up = wall_ms();
+    if (rc == CPOL_OK) rc = ensure(ctx, ctx->d_H, h_bytes + (size_t)ncell * sizeof(float2));
+    if (rc == CPOL_OK) rc = ensure(ctx, ctx->d_V, plane_bytes * n_vars);
+    if (rc == CPOL_OK) {
+        DeriveArgs a{};
+        a.planes = (const float *)cube.p;
+        a.V = (float *)ctx->d_V.p; a.H = (float *)ctx->d_H.p; a.HT = (float2 *)((char *)ctx->d_H.p + h_bytes);
+        a.ncell = ncell; a.nz = nz; a.n_vars = n_vars;
+        a.base_p = base[(size_t)m->field_p]; a.base_t = base[(size_t)m->field_t]; a.base_qv = base[(size_t)m->field_qv];
+        a.base_hhl = base[(size_t)m->field_hhl]; a.hhl_half = m->field_levels[m->field_hhl] == nz + 1;
+        a.n_load = m->n_load;
+        for (int j = 0; j < m->n_load; ++j) a.base_load[j] = base[(size_t)m->field_load[j]];
+        for (int v = 0; v < n_vars; ++v) {
+            a.recipe[v] = m->recipe[v];
+            a.base_src[v] = (m->recipe[v] == CPOL_RECIPE_RHO || m->recipe[v] == CPOL_RECIPE_ZEROS) ? 0 : base[(size_t)m->source[v]];
+        }
+        a.r_d = m->r_d; a.rv_rd_m1 = m->rv_rd_m1;
+        // 64 cells x kc levels x n_vars through LDS: the largest kc (a multiple of 4, <= 16) whose tile stays under 60 KB
+        const bool vec4 = ((long)nz * n_vars) % 4 == 0;
+        size_t lds = 0;
+        for (a.kc = 16; a.kc >= 4; a.kc -= 4) {
+            a.rowlen = vec4 ? a.kc * n_vars + 4 : ((a.kc * n_vars) | 1);
+            lds = ((size_t)64 * a.rowlen + (size_t)64 * (a.kc + 1)) * sizeof(float);
+            if (lds <= (size_t)60 * 1024) break;
+        }
+        for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+        if (ev[0]) (void)hipEventRecord(ev[0], ctx->stream);
+        launch_unpack(ctx, arena, desc, (float *)cube.p, n_planes, ny, nx);
+        if (ev[1]) (void)hipEventRecord(ev[1], ctx->stream);
+        const dim3 grid((unsigned)cdiv(ncell, 64), (unsigned)cdiv(nz, a.kc));
+        if (vec4) hipLaunchKernelGGL((k_model_derive<true>), grid, dim3(256), lds, ctx->stream, a);
+        else hipLaunchKernelGGL((k_model_derive<false>), grid, dim3(256), lds, ctx->stream, a);
+        if (ev[2]) (void)hipEventRecord(ev[2], ctx->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { ctx->err = std::string("cpol_stage_model_packed: ") + hipGetErrorString(e); rc = CPOL_ERR_HIP; }
+    }
+    free_buf(arena); free_buf(desc); free_buf(cube);
+    if (rc == CPOL_OK) {
+        float ms_unpack = 0.f, ms_derive = 0.f;
+        if (ev[0] && ev[1] && ev[2]) { (void)hipEventElapsedTime(&ms_unpack, ev[0], ev[1]); (void)hipEventElapsedTime(&ms_derive, ev[1], ev[2]); }
+        model_staged_tail(ctx, n_vars, nz, ny, nx, h_bytes, m->llc, m->urc, m->res, m->south_pole);
+        ctx->ingest_ms[0] = t_up - t_start; ctx->ingest_ms[1] = ms_unpack; ctx->ingest_ms[2] = ms_derive;
+        ctx->ingest_ms[3] = wall_ms() - t_start;
+    } else if (ctx->d_H.p == nullptr || ctx->d_V.p == nullptr || rc == CPOL_ERR_HIP) {
+        ctx->model_staged = false;       // the cube behind the model descriptor is gone or half written
+    }
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    return rc;
 }
 
 static int n_par_of(int rule)
@@ -2935,6 +3148,26 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         memcpy(dst, ctx->host_ns, sizeof ctx->host_ns);
         for (double &v : ctx->host_ns) v = 0.0;
         return (int64_t)sizeof ctx->host_ns;
+    }
+    if (!strcmp(name, "ingest_times")) {
+        if (!dst || max_bytes < (int64_t)sizeof ctx->ingest_ms) return CPOL_ERR_ARG;
+        memcpy(dst, ctx->ingest_ms, sizeof ctx->ingest_ms);
+        return (int64_t)sizeof ctx->ingest_ms;
+    }
+    if (!strcmp(name, "model_v") || !strcmp(name, "model_h") || !strcmp(name, "model_ht")) {
+        // the staged model as it lies in device memory
+        const cpol_ctx *own = ctx->parent ? ctx->parent : ctx;
+        if (!own->model_staged) { ctx->err = "cpol_debug_read: no model staged"; return CPOL_ERR_ARG; }
+        const ModelDev &md = own->model;
+        const int64_t ncell = (int64_t)md.ny * md.nx;
+        const void *from = name[6] == 'v' ? (const void *)md.V : name[7] == 't' ? (const void *)md.HT : (const void *)md.H;
+        const int64_t nb = name[6] == 'v' ? ncell * md.nz * md.n_vars * 4 : name[7] == 't' ? ncell * 8 : ncell * md.nz * 4;
+        if (!dst || nb > max_bytes) { ctx->err = "cpol_debug_read: destination too small"; return CPOL_ERR_ARG; }
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(dst, from, (size_t)nb, hipMemcpyDeviceToHost) != hipSuccess) {
+            ctx->err = "cpol_debug_read: copy failed";
+            return CPOL_ERR_HIP;
+        }
+        return nb;
     }
     if (!strcmp(name, "cache")) {
         // [integral-table cache entries, scattering-table cache entries, integral-table builds] (table_id)

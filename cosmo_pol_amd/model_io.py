@@ -8,10 +8,14 @@ and gets back the DERIVED variables of BASE_VARIABLES (:35-36) -- mass and numbe
 DENSITIES `Q*_v`, `QN*_v`, the air density RHO, the refractivity N -- each carrying
 `attributes['z-levels']` [nz, ny, nx], `['proj_info']` (Lo1, La1, Lo2, La2,
 Latitude_of_southern_pole, Longitude_of_southern_pole), `['resolution']` and `['time']`
-(interpolation.py:547-561, radar_operator.py:191).  pycosmo and every GRIB decoder are
-absent from this environment and the reference ships no sample file, so GRIB stays
-refused; what IS read here, with the same variable names and the same attributes:
+(interpolation.py:547-561, radar_operator.py:191).  pycosmo and every GRIB library are
+absent from this environment and the reference ships no sample file, so what is read
+here, with the same variable names and the same attributes, is:
 
+  * GRIB edition 1 (cosmo_pol_amd/grib1.py: the subset COSMO writes -- simple packing, no bitmap,
+    (rotated) lat/lon grid; names through a replaceable code table, `grib_table`; anything else is
+    refused with a pointer to pycosmo and `cdo -f nc copy`), model file and c-file alike: the raw
+    model output on model levels, HHL on half levels (*parity with pycosmo unpinned*, as below);
   * NetCDF classic (`.nc`, through scipy.io.netcdf_file), COSMO's own netCDF conventions:
     variables [time,] level, rlat, rlon; coordinate variables `rlon`, `rlat` (degrees, rotated);
     a `rotated_pole` variable with `grid_north_pole_latitude / _longitude`; the half-level
@@ -94,16 +98,41 @@ class _NetCDF(object):
         self.f.close()
 
 
-def _open(path):
+class _Grib1(object):
+    """A GRIB edition-1 file (grib1.Grib1File) behind the names / get / attr / close interface of the other sources."""
+
+    def __init__(self, path, table=None):
+        from . import grib1
+        self.g = grib1.Grib1File(path, table)
+
+    def names(self):
+        return self.g.names()
+
+    def get(self, k):
+        return self.g.get(k)
+
+    def attr(self, var, k):
+        if var is not None or not self.g.fields:
+            return None
+        if k in PROJ_KEYS:
+            return self.g.proj_info()[k]
+        if k == 'time':
+            return self.g.time()
+        return None
+
+    def close(self):
+        self.g.close()
+
+
+def _open(path, grib_table=None):
+    if hasattr(path, 'names'):                  # an open source of the caller's (it stays the caller's to close)
+        return path
     if not os.path.exists(path):
         raise IOError('model file %r does not exist' % (path,))
     with open(path, 'rb') as f:
         magic = f.read(8)
     if magic[:4] == b'GRIB':
-        raise NotImplementedError(
-            'GRIB input needs pycosmo (cosmo_pol/radar_operator.py:229), which is not installable here and of '
-            'which /root/reference holds no source: convert the file to NetCDF classic (e.g. `fxconvert nc` / '
-            '`cdo -f nc copy`) or pass arrays to RadarOperator.load_model_arrays')
+        return _Grib1(path, grib_table)         # (refuses what it does not read: another edition, bitmaps ...)
     if magic[:3] == b'CDF':
         return _NetCDF(path)
     if magic[:4] == b'\x89HDF':
@@ -167,11 +196,12 @@ def derive(raw, want_2mom, want_refractivity):
     return out
 
 
-def read_model_file(filename, cfilename=None, want_refractivity=False, want_edr=False):
-    """-> dict(data={name: [nz, ny, nx] float32}, zlevels [nz, ny, nx] float32, proj_info, resolution (dlon, dlat),
+def read_model_file(filename, cfilename=None, want_refractivity=False, want_edr=False, grib_table=None):
+    """`grib_table`: {(table version, parameter, level type): name} replacing grib1.DEFAULT_TABLE for GRIB files.
+    -> dict(data={name: [nz, ny, nx] float32}, zlevels [nz, ny, nx] float32, proj_info, resolution (dlon, dlat),
     time, scheme '1mom' | '2mom', derived_from_raw bool).  Raises ValueError like the reference when a necessary
     variable is missing (radar_operator.py:264-275)."""
-    src = _open(filename)
+    src = _open(filename, grib_table)
     csrc = None
     try:
         names = src.names()
@@ -209,7 +239,7 @@ def read_model_file(filename, cfilename=None, want_refractivity=False, want_edr=
             if s is None:
                 if cfilename is None:
                     break
-                csrc = s = _open(cfilename)
+                csrc = s = _open(cfilename, grib_table)
             n = s.names()
             if 'z-levels' in n:
                 zl = _levels_first(s.get('z-levels'))
@@ -243,8 +273,9 @@ def read_model_file(filename, cfilename=None, want_refractivity=False, want_edr=
         return {'data': data, 'zlevels': zl, 'proj_info': proj, 'resolution': (float(res[0]), float(res[1])),
                 'time': time, 'scheme': '2mom' if two_mom else '1mom', 'derived_from_raw': not have_derived}
     finally:
-        src.close()
-        if csrc is not None:
+        if src is not filename:
+            src.close()
+        if csrc is not None and csrc is not cfilename:
             csrc.close()
 
 
@@ -265,6 +296,12 @@ def write_npz(path, data, zlevels=None, hhl=None, proj_info=None, rlon=None, rla
     if time is not None:
         out['time'] = np.array(time)
     np.savez(path, **out)
+
+
+def write_grib1(path, fields, rlon, rlat, south_pole, n_bits=16, decimal_scale=0, **kwargs):
+    """GRIB edition 1, one message per level (grib1.write_grib1: simple packing, rotated grid, PDS of 28 octets)."""
+    from . import grib1
+    grib1.write_grib1(path, fields, rlon, rlat, south_pole, n_bits=n_bits, decimal_scale=decimal_scale, **kwargs)
 
 
 def write_netcdf(path, data, rlon, rlat, north_pole, hhl=None, time_hours=0.0):

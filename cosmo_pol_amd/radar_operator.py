@@ -43,6 +43,27 @@ class ModelVar(object):
         self.attributes = attributes
 
 
+class LazyModelVar(ModelVar):
+    """A ModelVar whose `data` is built on first access (a model ingested on the device keeps the file's index, not
+    decoded arrays: the host decoder runs only for a caller who reads them)."""
+
+    def __init__(self, name, make, attributes):
+        self.name = name
+        self._make = make
+        self._data = None
+        self.attributes = attributes
+
+    @property
+    def data(self):
+        if self._data is None:
+            self._data = self._make()
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        self._data = value
+
+
 class LazyDict(MutableMapping):
     """A mapping whose values are built on first access (`add(key, make)`): the containers returned by
     get_PPI / get_RHI / get_GPM_swath carry a dozen derived arrays per scan (dB fields, NaN masks,
@@ -280,6 +301,9 @@ class RadarOperator(object):
         self.current_microphys_scheme = '1mom'
         self.dic_vars = None
         self.N = 0
+        self.grib_table = None                 # {(table version, parameter, level type): name} replacing grib1.DEFAULT_TABLE
+        self._packed = None                    # a model ingested on the device: the open GRIB sources (load_model_file)
+        self._zl = None
         self.lut_sz = None
         self._model_staged = False
         self._staged_serial = 0
@@ -369,6 +393,7 @@ class RadarOperator(object):
                 except OSError:
                     pass
                 self._affinity_before = None
+        self._drop_packed()
         self.dic_vars = None
         self.lut_sz = None
         self.__config = None
@@ -462,16 +487,30 @@ class RadarOperator(object):
 
     # ------------------------------------------------------------------ model
     def load_model_file(self, filename, cfilename=None):
-        """Loads the model variables from a file (cosmo_pol/radar_operator.py:217-309): NetCDF classic
-        in COSMO's conventions or an .npz archive with the same names (cosmo_pol_amd/model_io.py), the
-        c-file `cfilename` supplying the half-level heights HHL when the file has none.  The file may hold
-        the raw model output (P, T, QV, QR, QC, QI, QS, QG, U, V, W [+ QH, QNH, QNR, QNS, QNG]), from which
-        the densities, RHO and -- for refraction scheme 2 -- the refractivity N are derived as pycosmo does
-        for the reference, or the derived variables themselves.  GRIB needs pycosmo and is refused with a
-        pointer.  ValueError when a necessary variable is missing, as in the reference (:264-275)."""
+        """Loads the model variables from a file (cosmo_pol/radar_operator.py:217-309): GRIB edition 1 as COSMO writes
+        it (cosmo_pol_amd/grib1.py; names through `self.grib_table`), NetCDF classic in COSMO's conventions or an .npz
+        archive with the same names (cosmo_pol_amd/model_io.py), the c-file `cfilename` supplying the half-level
+        heights HHL when the file has none.  The file may hold the raw model output (P, T, QV, QR, QC, QI, QS, QG, U,
+        V, W [+ QH, QNH, QNR, QNS, QNG]), from which the densities, RHO and -- for refraction scheme 2 -- the
+        refractivity N are derived as pycosmo does for the reference, or the derived variables themselves.
+        A GRIB-1 file of raw output whose heights come from itself or from a GRIB-1 c-file is unpacked, derived and
+        staged on the GPU (the packed octets travel as they are; `dic_vars[...].data`, `N.data` and the level heights
+        are then decoded on the host only when read); every other combination goes through the host
+        (model_io.read_model_file).  Both ways stage the same bits for the configuration in force.  One difference
+        afterwards: the device path keeps the file's index, so an `EDR` in the file is staged when
+        `doppler/turbulence_correction` is switched on later; the host path read `EDR` only if the correction was on at
+        load time and otherwise switches it off again with the reference's notice.  ValueError when a necessary variable
+        is missing, as in the reference (:264-275).  A file that is refused (NotImplementedError, ValueError) leaves
+        the operator and its staged cube as they were; after a device error during the ingest no model is staged."""
         from . import model_io
         want_n = self.__config['refraction']['scheme'] == 2
-        m = model_io.read_model_file(filename, cfilename, want_refractivity=want_n, want_edr=self._wants_edr())
+        packed = self._open_packed(filename, cfilename)
+        if packed is not None:
+            self._load_model_packed(packed[0], packed[1], want_n)
+            print('-------done------')
+            return
+        m = model_io.read_model_file(filename, cfilename, want_refractivity=want_n, want_edr=self._wants_edr(),
+                                     grib_table=self.grib_table)
         if want_n and 'N' not in m['data']:
             # (radar_operator.py:237-247)
             print('Necessary variables for computation of atm. refractivity were not found in file. '
@@ -480,6 +519,129 @@ class RadarOperator(object):
         print('Reading variables ', sorted(m['data']), ' from file')
         self.load_model_arrays(m['data'], m['zlevels'], m['proj_info'], m['resolution'], time=m['time'])
         print('-------done------')
+
+    # (the device ingest of GRIB-1 files)
+    @staticmethod
+    def _is_grib1(path):
+        if path is None or not os.path.exists(path):
+            return False
+        with open(path, 'rb') as f:
+            magic = f.read(8)
+        return len(magic) == 8 and magic[:4] == b'GRIB' and magic[7] == 1
+
+    def _open_packed(self, filename, cfilename):
+        """(model source, c-file source | None) when the files take the device path, else None (host path).  The choice
+        follows from the files alone: a GRIB-1 file of raw output with HHL in itself or in a GRIB-1 c-file."""
+        from . import model_io
+        if not self._is_grib1(filename):
+            return None
+        g = model_io._Grib1(filename, self.grib_table)
+        c = None
+        try:
+            names = g.names()
+            if all(k in names for k in model_io.BASE_VARIABLES) or not all(k in names for k in model_io.RAW_BASE) \
+                    or 'z-levels' in names:
+                g.close()
+                return None                      # (derived variables, or the host path's ValueError naming what is missing)
+            if 'HHL' not in names:
+                if not self._is_grib1(cfilename):
+                    g.close()
+                    return None
+                c = model_io._Grib1(cfilename, self.grib_table)
+                if 'HHL' not in c.names():
+                    c.close()
+                    g.close()
+                    return None
+            return g, c
+        except BaseException:
+            g.close()
+            if c is not None:
+                c.close()
+            raise
+
+    def _drop_packed(self):
+        p, self._packed = getattr(self, '_packed', None), None
+        if p is not None:
+            p['g'].close()
+            if p['c'] is not None:
+                p['c'].close()
+
+    @property
+    def _zlevels(self):
+        if self._zl is None and self._packed is not None:
+            self._zl = self._packed_host()['zlevels']
+        return self._zl
+
+    @_zlevels.setter
+    def _zlevels(self, value):
+        self._zl = value
+
+    def _packed_host(self):
+        """The host decode of the files ingested on the device (model_io.read_model_file on the open sources), once."""
+        from . import model_io
+        p = self._packed
+        if p['host'] is None:
+            p['host'] = model_io.read_model_file(p['g'], p['c'], want_refractivity=p['want_n'], want_edr=True)
+        return p['host']
+
+    def _load_model_packed(self, g, c, want_n):
+        """Checks of model_io.read_model_file on the index alone, then the operator's state as load_model_arrays leaves
+        it -- with lazily decoded arrays -- and the device ingest (_stage_model).  Raises before anything changes."""
+        from . import model_io
+        try:
+            G, H = g.g, (g if c is None else c).g
+            names = G.names()
+            nz = G.n_levels('T')
+            two_mom = all(k in names for k in model_io.RAW_2MOM)
+            raw = model_io.RAW_BASE + ([k for k in model_io.RAW_2MOM + ['QNI'] if k in names] if two_mom else [])
+            for k in raw + (['EDR'] if 'EDR' in names else []):
+                n = G.n_levels(k)
+                if n != nz and not (k in ('W', 'EDR') and n == nz + 1):
+                    raise ValueError('variable %s has %d levels, T has %d' % (k, n, nz))
+            if H.n_levels('HHL') not in (nz, nz + 1) or H.shape() != G.shape():
+                raise ValueError('level heights have shape %s, the variables %s'
+                                 % ((H.n_levels('HHL'),) + H.shape(), (nz,) + G.shape()))
+            top, low = H.get('HHL', levels=(0, H.n_levels('HHL') - 1))
+            if top.mean() < low.mean():
+                raise ValueError('level 0 must be the model top (heights decreasing with the level index)')
+            ny, nx = G.shape()
+            proj = G.proj_info()
+            res = ((proj['Lo2'] - proj['Lo1']) / max(nx - 1, 1), (proj['La2'] - proj['La1']) / max(ny - 1, 1))
+            time = G.time()
+        except BaseException:
+            g.close()
+            if c is not None:
+                c.close()
+            raise
+        keys = list(hyd.BASE_VARIABLES) + (list(hyd.BASE_VARIABLES_2MOM) if two_mom else []) + (['EDR'] if 'EDR' in names else [])
+        print('Using %s scheme' % ('2-moment' if two_mom else '1-moment'))
+        print('Reading variables ', sorted(keys + (['N'] if want_n else [])), ' from file')
+        self._note_missing_edr('EDR' in keys)
+        previous = (self._packed, self.dic_vars, self.N, self._zl, getattr(self, '_proj', None), getattr(self, '_res', None))
+        self._packed = {'g': g, 'c': c, 'two_mom': two_mom, 'want_n': want_n, 'host': None, 'nz': nz}
+        attrs = LazyDict()
+        attrs.add('z-levels', lambda: self._zlevels)
+        attrs['proj_info'], attrs['resolution'], attrs['time'] = proj, (float(res[0]), float(res[1])), time
+        host = self._packed_host
+        self.dic_vars = {k: LazyModelVar(k, lambda k=k: host()['data'][k], attrs) for k in keys}
+        self.N = LazyModelVar('N', lambda: host()['data']['N'], attrs) if want_n else 0
+        self._zl = None
+        try:
+            self._adopt_model(proj, attrs['resolution'], two_mom)
+        except BaseException as e:
+            g.close()
+            if c is not None:
+                c.close()
+            self._packed, self.dic_vars, self.N, self._zl, self._proj, self._res = previous
+            if not isinstance(e, ValueError):
+                # (CPOL_ERR_ARG -- ValueError -- is raised before the library changes anything: the operator keeps the cube
+                # it had; after anything else the library holds no staged model)
+                self._model_staged = False
+            raise
+        if previous[0] is not None:
+            previous[0]['g'].close()
+            if previous[0]['c'] is not None:
+                previous[0]['c'].close()
 
     def _wants_edr(self):
         """The eddy dissipation rate is a model variable only for the turbulence broadening of the Doppler spectrum
@@ -494,22 +656,29 @@ class RadarOperator(object):
         Latitude_of_southern_pole, Longitude_of_southern_pole; resolution
         (dlon, dlat).  EDR (eddy dissipation rate) is staged only with Doppler scheme 3 and
         doppler/turbulence_correction = 1; without it that correction is switched off with the reference's notice."""
-        if self._wants_edr() and 'EDR' not in data:
+        self._note_missing_edr('EDR' in data)
+        two_mom = all(k in data for k in hyd.BASE_VARIABLES_2MOM)
+        missing = [k for k in hyd.BASE_VARIABLES if k not in data]
+        if missing:
+            raise ValueError('Not all necessary variables could be found: missing %s' % missing)
+        attrs = {'z-levels': zlevels, 'proj_info': proj_info, 'resolution': resolution,
+                 'time': time}
+        self._drop_packed()
+        self.dic_vars = {k: ModelVar(k, v, attrs) for k, v in data.items() if k != 'N'}
+        self.N = ModelVar('N', data['N'], attrs) if 'N' in data else 0     # refractivity
+        self._zlevels = zlevels
+        self._adopt_model(proj_info, resolution, two_mom)
+
+    def _note_missing_edr(self, have_edr):
+        if self._wants_edr() and not have_edr:
             # (radar_operator.py:255-262: the reference edits its configuration in the same way)
             print('Necessary variable for correction of turbulence broadening: Eddy dissipitation rate '
                   'was not found in file. No  turbulence correction will be done.')
             self.__config['doppler']['turbulence_correction'] = 0
             self._cache = {}
-        two_mom = all(k in data for k in hyd.BASE_VARIABLES_2MOM)
-        missing = [k for k in hyd.BASE_VARIABLES if k not in data]
-        if missing:
-            raise ValueError('Not all necessary variables could be found: missing %s' % missing)
+
+    def _adopt_model(self, proj_info, resolution, two_mom):
         scheme = '2mom' if two_mom else '1mom'
-        attrs = {'z-levels': zlevels, 'proj_info': proj_info, 'resolution': resolution,
-                 'time': time}
-        self.dic_vars = {k: ModelVar(k, v, attrs) for k, v in data.items() if k != 'N'}
-        self.N = ModelVar('N', data['N'], attrs) if 'N' in data else 0     # refractivity
-        self._zlevels = zlevels
         self._proj = proj_info
         self._res = resolution
         if scheme != self.__config['microphysics']['scheme']:
@@ -531,11 +700,65 @@ class RadarOperator(object):
         urc = np.asarray((float(p['Lo2']), float(p['La2']))).astype('float32')
         res = np.asarray(self._res, dtype=np.float32)
         sp = [float(p['Latitude_of_southern_pole']), float(p['Longitude_of_southern_pole'])]
-        self._ctx.stage_model([self.dic_vars[n].data for n in names], self._zlevels, llc, urc,
-                              res, sp)
+        if self._packed is not None:
+            self._ctx.stage_model_packed(*self._packed_plan(names, llc, urc, res, sp))
+        else:
+            self._ctx.stage_model([self.dic_vars[n].data for n in names], self._zlevels, llc, urc,
+                                  res, sp)
         self._staged_vars = names
         self._model_staged = True
         self._staged_serial = getattr(self, '_staged_serial', 0) + 1      # (host caches that depend on the cube)
+
+    def _packed_plan(self, names, llc, urc, res, sp):
+        """(cpol_packed_model, planes) of the device ingest for the staged variables `names`: the raw fields each of them
+        needs and its recipe -- the statements of model_io.derive and read_model_file."""
+        from . import model_io
+        pk = self._packed
+        G, H, nz = pk['g'].g, (pk['g'] if pk['c'] is None else pk['c']).g, pk['nz']
+        have = G.names()
+        fields = []                               # (file, raw name)
+
+        def field(name, src=G):
+            if (src, name) not in fields:
+                fields.append((src, name))
+            return fields.index((src, name))
+
+        m = N.PackedModel()
+        m.nz, (m.ny, m.nx) = nz, G.shape()
+        m.field_p, m.field_t, m.field_qv, m.field_hhl = field('P'), field('T'), field('QV'), field('HHL', H)
+        load = [k for k in ('QC', 'QR', 'QS', 'QG', 'QI') if k in have]
+        m.n_load = len(load)
+        for j, k in enumerate(load):
+            m.field_load[j] = field(k)
+        m.n_vars = len(names)
+        for v, name in enumerate(names):
+            if name == 'RHO':
+                m.recipe[v] = N.RECIPE_RHO
+            elif name.endswith('_v'):
+                rawname = name[:-2]
+                if rawname in have:
+                    m.recipe[v], m.source[v] = N.RECIPE_TIMES_RHO, field(rawname)
+                else:
+                    m.recipe[v] = N.RECIPE_ZEROS
+            else:
+                half = G.n_levels(name) == nz + 1
+                m.recipe[v], m.source[v] = (N.RECIPE_HALF_MEAN if half else N.RECIPE_COPY), field(name)
+        if len(fields) > N.MAX_RAW_FIELDS:
+            raise ValueError('more than %d raw fields' % N.MAX_RAW_FIELDS)
+        m.n_fields = len(fields)
+        m.r_d, m.rv_rd_m1 = model_io.R_D, model_io.R_V / model_io.R_D - 1.0
+        m.llc[:], m.urc[:], m.res[:], m.south_pole[:] = list(llc), list(urc), list(res), list(sp)
+        planes = []
+        octets = {}
+        for f, (src, name) in enumerate(fields):
+            if src not in octets:
+                octets[src] = np.frombuffer(src.buf, dtype=np.uint8)
+            pl = src.planes(name)
+            m.field_levels[f] = len(pl)
+            for k, e in enumerate(pl):
+                planes.append((octets[src][e['data_offset']:e['data_offset'] + e['n_octets']], e['R'], e['E'], e['D'],
+                               e['n_bits'], e['scanning'] == 0x00, f, k))
+        return m, planes
 
     def get_pos_and_time(self):
         c = self.__config['radar']['coords']

@@ -327,6 +327,57 @@ CPOL_API int  cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *da
                       const float llc[2], const float urc[2], const float res[2],
                       const double south_pole[2]);
 
+/* ---- model input in GRIB-1 simple packing, unpacked and derived on the device ------------------------------
+ * One packed plane (one GRIB message): the bit string of BDS octet 12 onwards as it lies in the file (host memory),
+ * and what turns its unsigned integers X into values (cosmo_pol_amd/grib1.py), in float64:
+ *   t = R + ldexp(X, E);  D > 0: t / 10^D;  D < 0: t * 10^-D;  value = (float)t        (n_bits = 0: X = 0) */
+typedef struct {
+    const void *octets;         /* value i at bit i * n_bits, most significant bit first; NULL allowed with n_bits = 0 */
+    int64_t  n_octets;          /* >= ceil(ny * nx * n_bits / 8)                                                   */
+    double   ref_value;         /* R (the IBM single of BDS octets 7-10, converted exactly)                         */
+    int32_t  bin_scale;         /* E                                                                                */
+    int32_t  dec_scale;         /* D                                                                                */
+    int32_t  n_bits;            /* 0 ... 32                                                                         */
+    int32_t  flip_rows;         /* 1: rows stored north to south (scanning mode 0x00): flipped on unpacking          */
+    int32_t  field;             /* raw-field index (stage_model_packed) | unused (unpack_planes: plane i -> out[i])  */
+    int32_t  level;             /* 0-based level of the raw field (0 = model top)                                   */
+} cpol_packed_plane;
+
+#define CPOL_MAX_RAW_FIELDS 32
+#define CPOL_MAX_LOAD       8
+/* how a staged variable comes out of the raw fields (model_io.derive / read_model_file, operand by operand in float64) */
+#define CPOL_RECIPE_COPY       0    /* the raw field `source` as it is (U, V, T; W or EDR on nz levels)              */
+#define CPOL_RECIPE_HALF_MEAN  1    /* float32(0.5 * (x[k] + x[k + 1])) of a raw field on nz + 1 levels (W, EDR)     */
+#define CPOL_RECIPE_RHO        2    /* air density P / (r_d T (1 + rv_rd_m1 QV - load))                              */
+#define CPOL_RECIPE_TIMES_RHO  3    /* raw field `source` x the unrounded air density (Q*_v, QN*_v)                  */
+#define CPOL_RECIPE_ZEROS      4    /* 0 (QNI_v of a file without QNI)                                              */
+typedef struct {
+    int32_t nz, ny, nx;                             /* full levels, rows, columns                                   */
+    int32_t n_fields;                               /* raw fields the planes belong to                              */
+    int32_t field_levels[CPOL_MAX_RAW_FIELDS];      /* levels of each raw field: nz, or nz + 1 (half levels)         */
+    int32_t field_p, field_t, field_qv, field_hhl;  /* raw-field indices; HHL on nz + 1 levels (means) or nz (copy)  */
+    int32_t n_load;                                 /* condensate fields subtracted in the density, in the order     */
+    int32_t field_load[CPOL_MAX_LOAD];              /* they are summed (QC, QR, QS, QG, QI: those present)           */
+    int32_t n_vars;                                 /* staged variables, in the order of the hydrometeor descriptors */
+    int32_t recipe[CPOL_MAX_VARS];                  /* CPOL_RECIPE_*                                                */
+    int32_t source[CPOL_MAX_VARS];                  /* raw-field index of COPY / HALF_MEAN / TIMES_RHO               */
+    double  r_d, rv_rd_m1;                          /* R_d and R_v / R_d - 1 as the host folds them                  */
+    float   llc[2], urc[2], res[2];                 /* as for cpol_stage_model                                       */
+    double  south_pole[2];
+} cpol_packed_model;
+
+/* The staging of cpol_stage_model from packed planes: the octets travel to the device as they are, k_grib_unpack
+ * turns them into float32 planes in a scratch cube (freed before the call returns), k_model_derive writes the
+ * staged variables, the level heights and the (top, lowest) pairs.  Every (field, level) of `m` must come exactly
+ * once.  The staged cube carries the bits model_io.read_model_file + cpol_stage_model give for the same file.
+ * CPOL_ERR_ARG leaves the context and its staged model as they were. */
+CPOL_API int  cpol_stage_model_packed(cpol_ctx *ctx, const cpol_packed_model *m, const cpol_packed_plane *planes,
+                             int n_planes);
+/* k_grib_unpack alone: n_planes planes of ny x nx values -> out [n_planes][ny][nx] float32 (host memory), rows
+ * south to north.  Needs no staged model or tables. */
+CPOL_API int  cpol_unpack_planes(cpol_ctx *ctx, const cpol_packed_plane *planes, int n_planes, int ny, int nx,
+                        float *out);
+
 /* table: float64 [n_e][n_t][n_d][12]; pre: [n_d] (or NULL) host-evaluated
  * N0*D^mu | D^mu; dnu: [n_d] D^nu; aux: family-specific per-bin tables.
  * Melting family with tab_degree = CPOL_MELT_DEGREE: aux = [n_t][2] (centre and 1 / half-width
@@ -519,7 +570,10 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * tables listed directly, [5] k_subbeam_sum, [6] table items evaluated in place, [7] the one
  * sub-beam on the coordinate polynomials, [8] n_sub, [9] lanes alive, [10] the build's CPOL_SCAN_FORM (1: wavefront range scans), [11] a HIP
  * graph was replayed; "poly_central", "host_times", "cache", "itab_check", "itab_times",
- * "itab_detail<slot>" (see cosmo_pol_amd/_native.py).  Returns bytes copied or < 0. */
+ * "itab_detail<slot>" (see cosmo_pol_amd/_native.py); the staged model as it lies in device memory: "model_v" float32
+ * [ny][nx][nz][n_vars], "model_h" float32 [ny][nx][nz], "model_ht" float32 [ny][nx][2] (model top, lowest level);
+ * "ingest_times" float64 [4]: milliseconds of the last packed staging (octets to the device, k_grib_unpack,
+ * k_model_derive, the whole call).  Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
 /* test hook: evaluates one of the device math helpers of the melting-species kernel on
