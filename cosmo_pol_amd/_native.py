@@ -146,7 +146,9 @@ EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_
            'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free', 'cpol_host_alloc_near',
            'cpol_device_pci_bus_id', 'cpol_mem_info',
            'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_broaden_rows',
-           'cpol_stage_model_packed', 'cpol_unpack_planes']
+           'cpol_stage_model_packed', 'cpol_unpack_planes',
+           'cpol_stage_member', 'cpol_num_members', 'cpol_select_member', 'cpol_run_sweep_members']
+MEMBERS_PER_CALL = 64                               # members one cpol_run_sweep_members call takes
 
 TRAJ_STRIDE, GEO_STRIDE, SITE_STRIDE = 4, 8, 8      # CPOL_*_STRIDE of the header
 MELT_DEGREE, MELT_FUNCS = 10, 4                    # CPOL_MELT_DEGREE / CPOL_MELT_FUNCS
@@ -290,6 +292,14 @@ def load_library():
     lib.cpol_host_alloc_near.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     lib.cpol_mem_info.restype = C.c_int
     lib.cpol_mem_info.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.cpol_stage_member.restype = C.c_int
+    lib.cpol_stage_member.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
+    lib.cpol_num_members.restype = C.c_int
+    lib.cpol_num_members.argtypes = [vp]
+    lib.cpol_select_member.restype = C.c_int
+    lib.cpol_select_member.argtypes = [vp, C.c_int]
+    lib.cpol_run_sweep_members.restype = C.c_int
+    lib.cpol_run_sweep_members.argtypes = [vp, C.POINTER(SweepParams), C.POINTER(RayTables), vp, C.c_int, C.POINTER(Outputs)]
     lib.cpol_device_pci_bus_id.restype = C.c_int
     lib.cpol_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_int]
     _lib = lib
@@ -566,6 +576,32 @@ class Context(object):
                                        _ptr(llc), _ptr(urc), _ptr(res), _ptr(sp))
         self._check(rc, 'cpol_stage_model')
         self.n_vars = len(arrays)
+        self.model_shape = (nz, ny, nx)
+
+    def stage_member(self, member, arrays):
+        """The variables of ensemble member `member` (same order and [nz, ny, nx] shape as the staged cube, which is member 0)."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+        want = getattr(self, 'model_shape', None)
+        if want is None or len(arrays) != getattr(self, 'n_vars', -1):
+            raise ValueError('stage_member: needs a staged model with the same number of variables')
+        for a in arrays:
+            if a.shape != want:            # (the library reads nz * ny * nx values from every pointer)
+                raise ValueError('member variable shape %s != staged cube shape %s' % (a.shape, want))
+        ptrs = (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+        self._check(self.lib.cpol_stage_member(self.h, int(member), len(arrays), ptrs), 'cpol_stage_member')
+
+    def num_members(self):
+        return int(self.lib.cpol_num_members(self.h))
+
+    def select_member(self, member):
+        self._check(self.lib.cpol_select_member(self.h, int(member)), 'cpol_select_member')
+
+    def run_sweep_members(self, params, tables, members, outputs):
+        members = np.ascontiguousarray(members, dtype=np.int32)
+        self.submitted += 1
+        rc = self.lib.cpol_run_sweep_members(self.h, C.byref(params), C.byref(tables), _ptr(members), len(members),
+                                             C.byref(outputs))
+        self._check(rc, 'cpol_run_sweep_members')
 
     @staticmethod
     def packed_planes(planes):
@@ -594,6 +630,7 @@ class Context(object):
         rc = self.lib.cpol_stage_model_packed(self.h, C.byref(model), arr, len(planes))
         self._check(rc, 'cpol_stage_model_packed')
         self.n_vars = int(model.n_vars)
+        self.model_shape = (int(model.nz), int(model.ny), int(model.nx))
 
     def ingest_times(self):
         """Milliseconds of the last stage_model_packed: octets to the device, k_grib_unpack, k_model_derive, the whole call."""

@@ -79,6 +79,10 @@ struct cpol_ctx {
     bool model_staged = false;
     ModelDev model{};
     DevBuf d_H, d_V;
+    // ensemble members (cpol_stage_member): the cubes of members 1, 2, ... -- member 0 is d_V; same shape, grid and level heights
+    // (d_H is shared).  Owned by the root context; a lane reads its parent's.  member_sel: whose cube model.V points to
+    std::vector<DevBuf> members;
+    int member_sel = 0;
     double ingest_ms[4] = {0, 0, 0, 0};   // the last cpol_stage_model_packed (cpol_debug_read "ingest_times")
     // hydrometeors
     HydroSet hs{};
@@ -696,6 +700,8 @@ void cpol_destroy(cpol_ctx *ctx)
         if (sg.p) (void)hipHostFree(sg.p);
     }
     for (auto &ts : ctx->tsets) { free_buf(ts.buf); free_buf(ts.poly); }
+    if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
+    ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
                      &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
@@ -778,6 +784,7 @@ int cpol_fork(cpol_ctx *parent, cpol_ctx **out)
     c->parent = parent;
     c->model_staged = parent->model_staged;
     c->model = parent->model;
+    c->member_sel = parent->member_sel;
     c->hs = parent->hs;
     c->ss = parent->ss;
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) c->hydro_staged[j] = parent->hydro_staged[j];
@@ -963,6 +970,14 @@ static bool model_on_lane(cpol_ctx *ctx, const char *who)
 }
 
 // the context bookkeeping behind a freshly written d_H / d_V (cpol_stage_model, cpol_stage_model_packed)
+// the cubes of members >= 1 go with the cube they were staged beside (cpol_stage_model, cpol_stage_model_packed, cpol_destroy)
+static void drop_members(cpol_ctx *ctx)
+{
+    for (auto &b : ctx->members) free_buf(b);
+    ctx->members.clear();
+    ctx->member_sel = 0;
+}
+
 static void model_staged_tail(cpol_ctx *ctx, int n_vars, int nz, int ny, int nx, size_t h_bytes, const float llc[2],
                               const float urc[2], const float res[2], const double south_pole[2])
 {
@@ -982,6 +997,7 @@ static void model_staged_tail(cpol_ctx *ctx, int n_vars, int nz, int ny, int nx,
     m.nstcp = -st * cp; m.stsp = st * sp; m.ct = ct;
     ctx->model_staged = true;
     ctx->stage_serial++;
+    drop_members(ctx);                  // (a new member 0: the others belonged to the previous one)
     // the coordinate polynomials of the resident table sets hold the PREVIOUS model's rotated-pole matrix (round-5 advisor
     // finding: a second cube with another south pole, the same rays again -> wrong grid cells without an error)
     for (auto &ts : ctx->tsets) ts.poly_version = 0;
@@ -1021,6 +1037,96 @@ int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const 
     HIPCHK(hipGetLastError());
     free_buf(tmp);
     model_staged_tail(ctx, n_vars, nz, ny, nx, h_bytes, llc, urc, res, south_pole);
+    return CPOL_OK;
+}
+
+// ---------------------------------------------------------------- ensemble members
+static cpol_ctx *root_of(cpol_ctx *ctx) { return ctx->parent ? ctx->parent : ctx; }
+
+// the cube of member k as the kernels read it, or NULL
+static const float *member_cube(cpol_ctx *ctx, int k)
+{
+    cpol_ctx *r = root_of(ctx);
+    if (!r->model_staged || k < 0 || k > (int)r->members.size()) return nullptr;
+    return (const float *)(k == 0 ? r->d_V.p : r->members[(size_t)k - 1].p);
+}
+
+int cpol_num_members(cpol_ctx *ctx)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    cpol_ctx *r = root_of(ctx);
+    return r->model_staged ? 1 + (int)r->members.size() : 0;
+}
+
+int cpol_stage_member(cpol_ctx *ctx, int member, int n_vars, const float *const *data)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    if (!data || member < 0) { ctx->err = "cpol_stage_member: bad arguments"; return CPOL_ERR_ARG; }
+    (void)hipGetLastError();
+    if (model_on_lane(ctx, "cpol_stage_member")) return CPOL_ERR_ARG;
+    if (!ctx->model_staged) { ctx->err = "cpol_stage_member: stage member 0 first (cpol_stage_model)"; return CPOL_ERR_ARG; }
+    const ModelDev &m = ctx->model;
+    if (n_vars != m.n_vars) { ctx->err = "cpol_stage_member: n_vars differs from the staged cube's"; return CPOL_ERR_ARG; }
+    if (member > (int)ctx->members.size() + 1) {
+        ctx->err = "cpol_stage_member: members are staged in order (member <= cpol_num_members)";
+        return CPOL_ERR_ARG;
+    }
+    for (int v = 0; v < n_vars; ++v)
+        if (!data[v]) { ctx->err = "cpol_stage_member: a variable pointer is NULL"; return CPOL_ERR_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const long ncell = (long)m.ny * m.nx;
+    const size_t plane_bytes = (size_t)m.nz * ncell * sizeof(float);
+    const bool fresh = member == (int)ctx->members.size() + 1;
+    // (every allocation before the first write: out of memory leaves what was staged before as it was)
+    DevBuf tmp;
+    int rc = ensure(ctx, tmp, plane_bytes);
+    if (rc != CPOL_OK) return rc;
+    if (fresh) {
+        try { ctx->members.emplace_back(); } catch (...) { free_buf(tmp); ctx->err = "cpol_stage_member: out of host memory"; return CPOL_ERR_NOMEM; }
+        // (exactly the cube: the head room `ensure` gives a grow-only work buffer would be 12 % of every member)
+        DevBuf &mb = ctx->members.back();
+        const hipError_t e = hipMalloc(&mb.p, plane_bytes * n_vars);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->members.pop_back();
+            free_buf(tmp);
+            ctx->err = std::string("cpol_stage_member: hipMalloc failed: ") + hipGetErrorString(e);
+            return CPOL_ERR_NOMEM;
+        }
+        mb.cap = plane_bytes * n_vars;
+    }
+    float *const dst = (float *)(member == 0 ? ctx->d_V.p : ctx->members[(size_t)member - 1].p);
+    const int blk = 256, grd = cdiv(ncell, blk);
+    for (int v = 0; v < n_vars; ++v) {
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tmp.p, data[v], plane_bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            if (fresh) { free_buf(ctx->members.back()); ctx->members.pop_back(); }
+            free_buf(tmp);
+            ctx->err = std::string("cpol_stage_member: copy failed: ") + hipGetErrorString(e);
+            return CPOL_ERR_HIP;
+        }
+        hipLaunchKernelGGL(k_stage_variable, dim3(grd), dim3(blk), 0, ctx->stream, (const float *)tmp.p, dst, m.nz, ncell, n_vars, v);
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipGetLastError());
+    free_buf(tmp);
+    // (kernel arguments of a captured graph may hold this cube: the key changes.  The scattering and integral tables do not
+    // depend on the model: lut_serial stays)
+    ctx->stage_serial++;
+    return CPOL_OK;
+}
+
+int cpol_select_member(cpol_ctx *ctx, int member)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    const float *V = member_cube(ctx, member);
+    if (!V) { ctx->err = "cpol_select_member: no such member staged"; return CPOL_ERR_ARG; }
+    // ModelDev travels to the kernels by value: the next launch reads the other cube.  What is keyed by the cube -- the
+    // captured HIP graph -- is keyed by stage_serial; the coordinate polynomials and per-ray tables depend on the grid alone
+    if (ctx->model.V != V) ctx->stage_serial++;
+    ctx->model.V = V;
+    ctx->member_sel = member;
     return CPOL_OK;
 }
 
@@ -1566,8 +1672,18 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
 //   and one vertical node per sub-beam and no ray paths;
 // - cpol_interp_subbeams (sub_out != NULL): the sequence up to and including k_interp_sweep, then the geometry of every
 //   sub-beam (k_interp_export), the 'ml' weights, the melting scheme and the copies to sub_out -- no scattering.
+// - cpol_run_sweep_members (mem != NULL): a sweep of mem->n_members * mem->n_rays rays whose first half runs ONCE over
+//   mem->n_rays rays (k_trajectory where the sweep would run it, then k_interp_members instead of k_interp_sweep) and writes
+//   member mm into the rows [mm * mem->n_rays, ...) of the work arrays; `t` holds the per-ray tables repeated for every member.
+//   The launch-form rules are the column call's: no interpolating forms, no graph replay.
+struct MembersCall {
+    int n_members, n_rays;
+    const float *V[CPOL_MEMBERS_PER_CALL];
+};
+
 static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
-                        const cpol_columns_t *cols, cpol_subbeam_outputs *sub_out, cpol_outputs *out)
+                        const cpol_columns_t *cols, cpol_subbeam_outputs *sub_out, cpol_outputs *out,
+                        const MembersCall *mem = nullptr)
 {
     if (!ctx) return CPOL_ERR_ARG;
     if (!p || !t || !out || !(ctx->model_staged || cols) || ctx->hs.n_hydro < 1 || p->n_rays < 1 ||
@@ -1591,6 +1707,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const int n_vars = cols ? cols->n_vars : ctx->model.n_vars, n_hyd = ctx->hs.n_hydro, n_keys = ctx->hs.n_keys;
     const long n_rg = (long)n_rays * ng;
     const long n_sbg = n_rg * n_sub;
+    const int geo_rays = mem ? mem->n_rays : n_rays;     // the rays the geometry is evaluated for (ensemble: once for all members)
     if (n_sbg >= (1L << 31)) { ctx->err = "cpol_run_sweep: too many sub-beam gates in one call"; return CPOL_ERR_ARG; }
     {
         // re-validated here: a C caller may have reached this state through cpol_stage_hydro alone
@@ -1743,12 +1860,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             ENSURE(set->poly, (size_t)n_rays * n_h * 2 * CPOL_GEO_NP * sizeof(double));
             TrajArgs tp{};
             tp.geo = (const double *)ctx->v_geo;
-            tp.n_rays = n_rays; tp.n_h = n_h; tp.n_v = n_v; tp.n_gates = ng; tp.mode = mode;
+            tp.n_rays = geo_rays; tp.n_h = n_h; tp.n_v = n_v; tp.n_gates = ng; tp.mode = mode;
             tp.lon1 = p->radar_lon; tp.sin_u1 = p->sin_u1; tp.cos_u1 = p->cos_u1;
             tp.poly = (double *)set->poly.p;
             tp.poly_M = (const double *)ctx->d_geoM.p;
             tp.poly_scale = geo_poly_scale;
-            hipLaunchKernelGGL(k_trajectory, dim3((unsigned)cdiv((long)n_rays * n_h, 256 / CPOL_GEO_NP)), dim3(256), 0, ctx->stream, ctx->model, tp);
+            hipLaunchKernelGGL(k_trajectory, dim3((unsigned)cdiv((long)geo_rays * n_h, 256 / CPOL_GEO_NP)), dim3(256), 0, ctx->stream, ctx->model, tp);
             set->poly_version = set->version;
             set->poly_scale = geo_poly_scale;
             set->poly_site[0] = p->radar_lon; set->poly_site[1] = p->sin_u1; set->poly_site[2] = p->cos_u1;
@@ -1983,12 +2100,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // every slot on a table, no debug reads: the gate kernel classifies its gates itself (k_interp_classify,
     // cpol_fused.inl)
     // (never for columns: the forms that interpolate, k_interp_classify and k_interp_gate1, are replaced by k_columns_ingest)
-    const bool fused = ctx->fuse_classify != 0 && rare_direct && !gate1 && !ml && !dop3 && !ctx->keep_debug && !cols && !sub_out;
+    const bool fused = ctx->fuse_classify != 0 && rare_direct && !gate1 && !ml && !dop3 && !ctx->keep_debug && !cols && !sub_out && !mem;
     // k_interp_gate1 (CPOL_FUSE_GATE1=1, not the default): the single-beam kernel interpolates its gates too.  Measured: the
     // isolated C2 sweep 95.4 -> 88.6 us (one lane back to back: 70 -> 62 us per sweep), but with three lanes in flight 42.2 ->
     // 44.8 us per sweep, and the Ku swath of config 5 (9 800 rays) 0.93 -> 1.18 ms: at the 3 wavefronts per SIMD k_gate1 needs,
     // the interpolation -- VALU-bound at 5 -- loses more than the saved launch and the 14 MB of vals[] give back.
-    const bool fused_gate1 = ctx->fuse_gate1 != 0 && gate1 && !cols;
+    const bool fused_gate1 = ctx->fuse_gate1 != 0 && gate1 && !cols && !mem;
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
@@ -1999,6 +2116,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     for (int k = 0; k < 14; ++k) {
         obytes[k] = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
         produced[k] = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
+        if (mem && k >= O_LAT && k <= O_HGT) obytes[k] = obytes[k] / (size_t)mem->n_members;      // (the geometry once, not per member)
         own[k] = &ctx->b_out[k];
     }
     obytes[O_RVEL] = (size_t)n_rg * sizeof(double);            produced[O_RVEL] = doppler;    own[O_RVEL] = &ctx->b_rvel;
@@ -2060,7 +2178,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     auto launch_all = [&]() -> int {
     // ---- 1. ray paths: evaluated inside k_interp_sweep; host-supplied paths are uploaded ----
     if (mode == CPOL_GEOM_HOST_PATHS) {
-        HIPCHK(hipMemcpyAsync(ctx->b_traj.p, t->paths, (size_t)n_rays * n_v * 3 * ng * sizeof(float),
+        HIPCHK(hipMemcpyAsync(ctx->b_traj.p, t->paths, (size_t)geo_rays * n_v * 3 * ng * sizeof(float),
                               hipMemcpyHostToDevice, st));
     }
     if (ray_prep || (ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols)) {
@@ -2071,7 +2189,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ta.ray_traj = (const double *)ctx->v_traj_in;
         ta.site = t->site ? (const double *)ctx->v_site : nullptr;
         ta.traj_out = paths ? (float *)ctx->b_traj.p : nullptr;
-        ta.n_rays = n_rays; ta.n_v = n_v; ta.n_gates = ng; ta.mode = mode;
+        ta.n_rays = geo_rays; ta.n_v = n_v; ta.n_gates = ng; ta.mode = mode;
         ta.range0 = p->range0; ta.range_step = p->range_step;
         ta.ke = p->ke; ta.re = p->re; ta.alt = p->radar_alt;
         ta.geo = (const double *)ctx->v_geo;
@@ -2083,7 +2201,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             ta.poly_scale = geo_poly_scale;
             ta.sin_u1 = p->sin_u1; ta.cos_u1 = p->cos_u1;
         }
-        hipLaunchKernelGGL(k_trajectory, dim3((unsigned)(n_rays * n_v), paths ? cdiv(ng, 256) : 1), dim3(256), 0, st, ctx->model, ta);
+        hipLaunchKernelGGL(k_trajectory, dim3((unsigned)(geo_rays * n_v), paths ? cdiv(ng, 256) : 1), dim3(256), 0, st, ctx->model, ta);
     }
     if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_TRAJ], st));
 
@@ -2112,7 +2230,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ia.dist = (float *)T[O_DIST];
     ia.heights = (float *)T[O_HGT];
     ia.error_flag = d_errflag;
-    ia.n_rays = n_rays; ia.n_gates = ng; ia.n_sub = n_sub; ia.n_h = n_h; ia.n_v = n_v;
+    ia.n_rays = geo_rays; ia.n_gates = ng; ia.n_sub = n_sub; ia.n_h = n_h; ia.n_v = n_v;
     ia.central_sub = n_sub / 2;
     ia.sin_u1 = p->sin_u1; ia.cos_u1 = p->cos_u1; ia.lon1 = p->radar_lon;
     ia.site = t->site ? (const double *)ctx->v_site : nullptr;
@@ -2124,7 +2242,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ia.poly_scale = (geo_poly || poly_central) ? geo_poly_scale : 0.0;
     ia.poly_central = poly_central ? 1 : 0;
     static const int use_present = getenv("CPOL_GATE1_PRESENT") ? atoi(getenv("CPOL_GATE1_PRESENT")) : 1;
-    if (gate1_ray && use_present && CPOL_GATE1_PRESENT && !cols) {      // (columns: no presence words are written)
+    if (gate1_ray && use_present && CPOL_GATE1_PRESENT && !cols && !mem) {      // (columns, members: no presence words are written)
         ia.present = (unsigned *)ctx->b_present.p;
         ia.n_pres = n_hyd;
         for (int j = 0; j < n_hyd; ++j) ia.pres_var[j] = ctx->hs.h[j].d.var_q;
@@ -2163,6 +2281,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         // (a grid-stride pass; at least enough workgroups to clear the counter set)
         const long blocks = std::max<long>(std::min<long>(cdiv(n_sbg, 256 * 4), 2048), cdiv(cnt_stride, 256));
         hipLaunchKernelGGL(k_columns_ingest, dim3((unsigned)blocks), dim3(256), 0, st, ig);
+    } else if (mem) {
+        // ---- 2m. the geometry of every sub-beam gate once, then the values of every member ----
+        MemberArgs ma{};
+        for (int k = 0; k < mem->n_members; ++k) ma.V[k] = mem->V[k];
+        ma.n_members = mem->n_members;
+        ma.n_sbg1 = (long)geo_rays * n_sub * ng;
+        hipLaunchKernelGGL(k_interp_members, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma);
     } else if (!fused && !fused_gate1 && !exp_skip_interp)
     hipLaunchKernelGGL(k_interp_sweep, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st,
                        ctx->model, ia);
@@ -2857,7 +2982,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const double t_buffers = now_ns();
     ctx->counters_dirty = true;         // until the sequence is queued completely (cleared where sweep_serial advances)
     // graph key: every value that ends up in a kernel argument
-    const bool graphable = ctx->use_graph && dev && !tm_psd && !ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out &&
+    const bool graphable = ctx->use_graph && dev && !tm_psd && !ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out && !mem &&
                            !dop3 && reuse && !want_szt && !want_model;
     if (graphable) {
         uint64_t key = 1469598103934665603ull;
@@ -3026,6 +3151,59 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
     t.nyquist = c->nyquist;
     t.varray = c->varray;
     return run_sequence(ctx, &q, &t, c, nullptr, out);
+}
+
+int cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t, const int32_t *members,
+                           int n_members, cpol_outputs *out)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    if (!p || !t || !out || !members || n_members < 1 || n_members > CPOL_MEMBERS_PER_CALL || p->n_rays < 1 || p->n_vnodes < 1 ||
+        p->n_hnodes < 1 || !t->traj || !t->geo) {
+        ctx->err = "cpol_run_sweep_members: bad arguments (1 <= n_members <= 64 per call)";
+        return CPOL_ERR_ARG;
+    }
+    if (out->model_vars) {
+        ctx->err = "cpol_run_sweep_members: antenna-integrated model variables are not part of an ensemble call (outputs->model_vars must be NULL)";
+        return CPOL_ERR_ARG;
+    }
+    MembersCall mc{};
+    mc.n_members = n_members;
+    mc.n_rays = p->n_rays;
+    for (int k = 0; k < n_members; ++k) {
+        mc.V[k] = member_cube(ctx, members[k]);
+        if (!mc.V[k]) { ctx->err = "cpol_run_sweep_members: a requested member is not staged"; return CPOL_ERR_ARG; }
+        for (int j = 0; j < k; ++j)
+            if (members[j] == members[k]) { ctx->err = "cpol_run_sweep_members: a member is requested twice"; return CPOL_ERR_ARG; }
+    }
+    if ((long)p->n_rays * n_members >= (1L << 31)) { ctx->err = "cpol_run_sweep_members: too many rows"; return CPOL_ERR_ARG; }
+    // the second half runs over n_members * n_rays rows, row m * n_rays + r = ray r of member m: the per-ray tables repeated
+    const size_t nr = (size_t)p->n_rays, M = (size_t)n_members;
+    const size_t w_traj = (size_t)p->n_vnodes * CPOL_TRAJ_STRIDE, w_geo = (size_t)p->n_hnodes * CPOL_GEO_STRIDE;
+    std::vector<double> traj, geo, site, nyq;
+    try {
+        traj.resize(M * nr * w_traj);
+        geo.resize(M * nr * w_geo);
+        if (t->site) site.resize(M * nr * CPOL_SITE_STRIDE);
+        if (t->nyquist) nyq.resize(M * nr);
+    } catch (...) {
+        ctx->err = "cpol_run_sweep_members: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    for (size_t k = 0; k < M; ++k) {
+        memcpy(traj.data() + k * nr * w_traj, t->traj, nr * w_traj * sizeof(double));
+        memcpy(geo.data() + k * nr * w_geo, t->geo, nr * w_geo * sizeof(double));
+        if (t->site) memcpy(site.data() + k * nr * CPOL_SITE_STRIDE, t->site, nr * CPOL_SITE_STRIDE * sizeof(double));
+        if (t->nyquist) memcpy(nyq.data() + k * nr, t->nyquist, nr * sizeof(double));
+    }
+    cpol_ray_tables_t tt = *t;
+    tt.traj = traj.data();
+    tt.geo = geo.data();
+    if (t->site) tt.site = site.data();
+    if (t->nyquist) tt.nyquist = nyq.data();
+    cpol_sweep_params q = *p;
+    q.n_rays = p->n_rays * n_members;
+    q.integrate_model = 0;
+    return run_sequence(ctx, &q, &tt, nullptr, nullptr, out, &mc);
 }
 
 int cpol_spaceborne_first_gate(cpol_ctx *ctx, const cpol_sweep_params *p, const double *traj,

@@ -688,9 +688,13 @@ struct ExportArgs {
     float *dist, *heights, *elev;
 };
 
-template <bool KEEP, bool EXPORT = false>
+// MEMBERS (k_interp_members, an ensemble sweep): the geometry once, as written here; every store of values, mask and elevation goes
+// to the rows of EVERY requested member (mb; cpol_members.inl), whose values come from their own cubes.
+#include "cpol_members.inl"
+
+template <bool KEEP, bool EXPORT = false, bool MEMBERS = false>
 __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &a, float *sv, long &sbg_out, float &elev_out,
-                                           const ExportArgs *x = nullptr)
+                                           const ExportArgs *x = nullptr, const MemberArgs *mb = nullptr)
 {
     // ---- which (ray, sub-beam, block of gates) this workgroup takes ----
     // The hardware deals workgroups to the 8 XCDs round robin by their linear index, and every XCD has its own L2.  With
@@ -740,11 +744,15 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     if (!(s32 == s32) || !(h32 == h32)) {
         // no gate here (ray shorter than the batch: spaceborne / host paths): counts
         // as "above the model", produces no item
+        if constexpr (MEMBERS) {
+            members_fill(m, a, *mb, sbg, 1, 0.0f, qnan, qnan);
+        } else {
         a.mask[sbg] = 1;
         for (int v = 0; v < m.n_vars; ++v)
             if (!KEEP || ((a.store_mask >> v) & 1u)) a.vals[(long)v * n_sbg + sbg] = qnan;
         a.elev[sbg] = 0.0f;
         if (a.coords) { a.coords[2 * sbg] = qnan; a.coords[2 * sbg + 1] = qnan; }
+        }
         if (EXPORT) {
             x->lats[sbg] = __builtin_nan(""); x->lons[sbg] = __builtin_nan("");
             x->dist[sbg] = qnan; x->heights[sbg] = qnan; x->elev[sbg] = e32;
@@ -934,12 +942,16 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     if (rlon < m.llc0 || rlat < m.llc1 || rlon > m.urc0 || rlat > m.urc1 ||
         !(rlon == rlon) || !(rlat == rlat)) {
         atomicOr(a.error_flag, 1);          // sticky until reported (cpol_synchronize / cpol_counters)
+        if constexpr (MEMBERS) {
+            members_fill(m, a, *mb, sbg, 2, e32, rlat, rlon);
+        } else {
         a.mask[sbg] = 2;
         for (int v = 0; v < m.n_vars; ++v)
             if (!KEEP || ((a.store_mask >> v) & 1u)) a.vals[(long)v * n_sbg + sbg] = __builtin_nanf("");
         a.elev[sbg] = e32;
         elev_out = e32;
         if (a.coords) { a.coords[2 * sbg] = rlat; a.coords[2 * sbg + 1] = rlon; }
+        }
         if (EXPORT) {
             x->lats[sbg] = __builtin_nan(""); x->lons[sbg] = __builtin_nan("");
             x->dist[sbg] = s32; x->heights[sbg] = h32; x->elev[sbg] = e32;
@@ -957,6 +969,17 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     GateGeom g;
     ITRACE(itr, 1);                                        // trajectory + grid coordinates
     gate_geometry(m, rlat, rlon, h32, g ITRACE_PASS);
+    if constexpr (MEMBERS) {
+        members_values(m, a, *mb, g, sbg, h32, e32, rlat, rlon);
+        if (sub == a.central_sub) {         // the central sub-beam's coordinates: once, not per member
+            const long rg = (long)ray * a.n_gates + gate;
+            if (a.lats) a.lats[rg] = lat_deg;
+            if (a.lons) a.lons[rg] = lon_deg;
+            if (a.dist) a.dist[rg] = s32;
+            if (a.heights) a.heights[rg] = h32;
+        }
+        return g.status;
+    }
 #if CPOL_GATE1_PRESENT
     unsigned pres = 0;                                     // (KEEP = false: bit s = this gate has pres_var[s] > 0)
 #endif
@@ -1066,6 +1089,16 @@ __global__ __launch_bounds__(256) void k_interp_export(ModelDev m, InterpArgs a,
     long sbg;
     float e;
     interp_gate<false, true>(m, a, nullptr, sbg, e, &x);
+}
+
+// The gate kernel of an ensemble sweep (cpol_run_sweep_members): the geometry of every sub-beam gate once, the values of every
+// requested member.  grid = k_interp_sweep's over the rays of ONE member, with its dealing of rays to the XCDs.
+__global__ __launch_bounds__(256) void k_interp_members(ModelDev m, InterpArgs a, MemberArgs mb)
+{
+    clear_counters(a.zero_buf, a.zero_n, a.zero_buf2, a.zero_n2);
+    long sbg;
+    float e;
+    interp_gate<false, false, true>(m, a, nullptr, sbg, e, nullptr, &mb);
 }
 
 // ---- caller-supplied sub-beam columns (cpol_run_columns) ----

@@ -307,6 +307,11 @@ class RadarOperator(object):
         self.lut_sz = None
         self._model_staged = False
         self._staged_serial = 0
+        self._n_members = 0                    # ensemble members staged beside the model (load_model_ensemble); the model is member 0
+        self._member = 0                       # the member every ordinary call reads (select_member)
+        self.ensemble_shared_from = 4          # form=None of the ensemble calls: 'shared' from this many sub-beams per radial
+                                               # (CPOL_RAY_PREP_MIN_SUB: where the sweep's geometry is heavy enough to be worth sharing;
+                                               # below it 'per_member' keeps the fused single-beam kernels -- DESIGN.md section 7c)
         self._staged_hydro = None
         self.constants = None
         if output_variables in ['all', 'only_model', 'only_radar']:
@@ -708,6 +713,8 @@ class RadarOperator(object):
         self._staged_vars = names
         self._model_staged = True
         self._staged_serial = getattr(self, '_staged_serial', 0) + 1      # (host caches that depend on the cube)
+        # (a freshly staged cube is alone: the library dropped the members that lay beside the previous one)
+        self._n_members, self._member = 1, 0
 
     def _packed_plan(self, names, llc, urc, res, sp):
         """(cpol_packed_model, planes) of the device ingest for the staged variables `names`: the raw fields each of them
@@ -1161,7 +1168,7 @@ class RadarOperator(object):
 
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False, subbeams=None):
+                  pinned=False, subbeams=None, members=None):
         if self._model_staged:
             self._sync_edr()
         conf = self.__config
@@ -1187,7 +1194,7 @@ class RadarOperator(object):
             if paths is not None or site is not None or not self.reuse_device_tables:
                 version = 0
 
-        want_model = self.output_variables in ('all', 'only_model')
+        want_model = self.output_variables in ('all', 'only_model') and members is None
 
         def prepare(paths=paths, site=site):
             """The argument structs of cpol_run_sweep for this set of rays (and the arrays they point into)."""
@@ -1288,6 +1295,9 @@ class RadarOperator(object):
                 setattr(o, k, ptr)
         else:
             shape = (n_rays, n_gates)
+            gshape = shape                        # (gate coordinates: once, whatever the number of members)
+            if members is not None:               # an ensemble call: a leading member axis on every radar field
+                shape = (len(members),) + shape
             spec = [(k, np.float32, shape) for k in RADAR_FIELDS]
             if doppler:
                 spec.append(('RVEL', np.float64, shape))
@@ -1302,8 +1312,8 @@ class RadarOperator(object):
             gkey = ('geom', version, n_gates) if version else None
             geom = self._cache.get(gkey) if gkey else None
             if geom is None:
-                spec += [('lats', np.float64, shape), ('lons', np.float64, shape),
-                         ('dist', np.float32, shape), ('heights', np.float32, shape)]
+                spec += [('lats', np.float64, gshape), ('lons', np.float64, gshape),
+                         ('dist', np.float32, gshape), ('heights', np.float32, gshape)]
             if want_model:
                 spec.append(('model_vars', np.float64, (len(self._staged_vars),) + shape))
             # every host output is a view of ONE block of page-locked memory from the operator's pool
@@ -1322,7 +1332,10 @@ class RadarOperator(object):
                 off += nb
             del slab
         ctx = self._lane(lane)
-        ctx.run_sweep(p, t, o)
+        if members is not None:
+            ctx.run_sweep_members(p, t, members, o)
+        else:
+            ctx.run_sweep(p, t, o)
         del keep
         if device_outputs is None and 'mask_sum8' in res:
             # `mask` is made from its one-byte form when it is first read (after wait(lane) for a pinned call, like every
@@ -1368,6 +1381,203 @@ class RadarOperator(object):
                 del c[k]
         c[key] = make()
         return c[key]
+
+    # ------------------------------------------------------------------ ensembles
+    # (replaces in the reference: nothing -- it runs one model state per process)
+    @property
+    def n_members(self):
+        """Model states staged on the device: 0 without a model, 1 after load_model_*, M after load_model_ensemble."""
+        return self._n_members if self._model_staged else 0
+
+    def _member_input(self, i, m, zlevels, proj_info, resolution, cfilename):
+        from . import model_io
+        if isinstance(m, (str, bytes, os.PathLike)):
+            want_n = self.__config['refraction']['scheme'] == 2 and i == 0
+            f = model_io.read_model_file(m, cfilename, want_refractivity=want_n, want_edr=self._wants_edr(),
+                                         grib_table=self.grib_table)
+            return {'data': f['data'], 'zlevels': f['zlevels'], 'proj_info': f['proj_info'],
+                    'resolution': f['resolution'], 'time': f.get('time')}
+        if zlevels is None or proj_info is None or resolution is None:
+            raise ValueError('ensemble member %d is a dict of arrays: zlevels, proj_info and resolution are needed' % i)
+        return {'data': m, 'zlevels': zlevels, 'proj_info': proj_info, 'resolution': resolution, 'time': None}
+
+    def load_model_ensemble(self, members, zlevels=None, proj_info=None, resolution=None, cfilename=None):
+        """Loads M >= 2 states of ONE model -- ensemble members, or a series of forecast times -- under the operator's one set of
+        scattering and integral tables.  Each member is a file name (anything load_model_file reads; decoded on the host)
+        or a `data` dict as for load_model_arrays (then zlevels, proj_info and resolution are given once, for all).  Every
+        member must have the same variables, shape, grid and z-levels; ValueError names the member and what differs, and
+        leaves the operator as it was.  Member 0 becomes "the model": every existing call behaves exactly as after
+        load_model_arrays(member 0); select_member / the *_ensemble calls reach the others.  Device memory per further
+        member: the cube alone (n_vars x nz x ny x nx x 4 bytes).  Any later load_model_* or restaging of the cube (a
+        configuration that changes the variable set) drops the members again."""
+        if self.distributed:
+            raise NotImplementedError('ensembles with a process group: sharding members or rays over ranks is not built')
+        members = list(members)
+        from . import ensemble
+        ins = [self._member_input(i, m, zlevels, proj_info, resolution, cfilename) for i, m in enumerate(members)]
+        ensemble.check_members(ins)
+        m0 = ins[0]
+        self.load_model_arrays(m0['data'], m0['zlevels'], m0['proj_info'], m0['resolution'], time=m0['time'])
+        names = self._staged_vars
+        for i, m in enumerate(ins[1:], start=1):
+            missing = [k for k in names if k not in m['data']]
+            if missing:
+                raise ValueError('ensemble member %d: missing %s' % (i, missing))
+            self._ctx.stage_member(i, [m['data'][k] for k in names])
+        self._n_members = len(ins)
+        self._member_times = [m['time'] for m in ins]
+
+    def select_member(self, m):
+        """Every later ordinary call (simulate_rays, get_PPI, interpolate_rays, submit_volume ...) on every lane reads member
+        `m`: a pointer swap on the device, no copy.  Host-side views (`dic_vars`, the refractivity N of refraction scheme 2)
+        stay member 0's."""
+        m = int(m)
+        if not 0 <= m < self.n_members:
+            raise ValueError('select_member(%d): %d member(s) staged' % (m, self.n_members))
+        with self._lock:
+            for c in [self._ctx] + list(self._lane_ctx):
+                c.select_member(m)
+            self._member = m
+
+    def _members_arg(self, members):
+        if self.distributed:
+            raise NotImplementedError('ensembles with a process group: sharding members or rays over ranks is not built')
+        if self.output_variables != 'only_radar':
+            raise NotImplementedError("ensemble calls do not return antenna-integrated model variables "
+                                      "(use output_variables='only_radar')")
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        members = list(range(self.n_members)) if members is None else [int(m) for m in members]
+        if not members:
+            raise ValueError('members: empty list')
+        for m in members:
+            if not 0 <= m < self.n_members:
+                raise ValueError('member %d: %d member(s) staged' % (m, self.n_members))
+        if len(set(members)) != len(members):
+            raise ValueError('members: %r lists a member twice' % (members,))
+        return members
+
+    def simulate_rays_ensemble(self, azimuths, elevations, members=None, on_device=False, device_outputs=None,
+                               apply_sensitivity=True, lane=0, form=None, pinned=False):
+        """simulate_rays for several members of the ensemble at once: the dict of simulate_rays with a leading member axis
+        (in the order of `members`; None = all) on the radar fields, `mask` included, and the gate coordinates once.
+        form='shared': cpol_run_sweep_members -- geometry once per sub-beam gate, then the members; the member list is cut
+        into chunks whose work buffers (cpol_mem_info's per_gate x sub-beam gates x members) fit
+        `sequence_memory_budget`.  form='per_member': select_member + the ordinary sweep, member by member (keeps the fused
+        single-beam kernels).  form=None: 'shared' from `ensemble_shared_from` sub-beams per radial.  Either way every
+        member's arrays carry the bits of simulate_rays on an operator loaded with that member alone.
+        `device_outputs`: {field: device pointer} of [n_members, n_rays, n_gates] arrays (geometry: [n_rays, n_gates]).
+        `pinned`: as for simulate_rays when the members fit one chunk; with several chunks the call waits."""
+        members = self._members_arg(members)
+        conf = self.__config
+        coords = conf['radar']['coords']
+        if coords[2] > K.MAX_MODEL_HEIGHT:
+            raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
+        if conf['refraction']['scheme'] == 2:
+            raise NotImplementedError('ensemble calls use the 4/3-earth ray paths (refraction scheme 1)')
+        from . import ensemble
+        sub = self._cached('sub', lambda: quadrature.subbeams(conf))
+        if form is None:
+            form = ensemble.choose_form(sub.n_sub, self.ensemble_shared_from)
+        if form not in ('shared', 'per_member'):
+            raise ValueError("form must be 'shared', 'per_member' or None")
+        rr = self.constants.RANGE_RADAR
+        n_rays = len(np.asarray(azimuths).reshape(-1))
+        ctx = self._lane(lane)
+        if form == 'shared':
+            free, _, per_gate = ctx.mem_info()
+            budget = self.sequence_memory_budget if self.sequence_memory_budget is not None else free // 3
+            chunks = ensemble.plan_member_chunks(members, per_gate * sub.n_sub * len(rr) * n_rays, budget)
+        else:
+            chunks = [[m] for m in members]
+        parts, done = [], 0
+        try:
+            for chunk in chunks:
+                dev = None
+                if device_outputs is not None:
+                    dev = self._offset_outputs(device_outputs, done, n_rays, len(rr))
+                if form == 'per_member':
+                    ctx.select_member(chunk[0])
+                    r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
+                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned)
+                else:
+                    r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
+                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned and len(chunks) == 1,
+                                       members=chunk)
+                parts.append(r)
+                done += len(chunk)
+        finally:
+            if form == 'per_member':
+                ctx.select_member(self._member)
+        if device_outputs is not None:
+            return parts[-1]
+        if form == 'shared' and len(parts) == 1:
+            return parts[0]
+        if pinned:
+            self.wait(lane)                        # (the members are joined on the host: their copies must have landed)
+        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
+        join = np.stack if form == 'per_member' else np.concatenate
+        return {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys()}
+
+    def _offset_outputs(self, device_outputs, n_before, n_rays, n_gates):
+        """The caller's device pointers moved behind the `n_before` members already written (gate coordinates: not moved)."""
+        n_vb = len(self.constants.VARRAY) if self.__config['doppler']['scheme'] == 3 else 0
+        width = {'RVEL': 8, 'mask': 8, 'DSPECTRUM': 8 * n_vb, 'sz_total': 4 * N.N_SZ, 'mask_sum8': 1}
+        out = {}
+        for k, ptr in device_outputs.items():
+            if k in ('lats', 'lons', 'dist', 'heights'):
+                out[k] = ptr
+            else:
+                out[k] = int(ptr) + n_before * n_rays * n_gates * width.get(k, 4)
+        return out
+
+    def _ensemble_scans(self, scan_type, members, sweeps, elevations, azimuths):
+        members = self._members_arg(members)
+        per = [[] for _ in members]
+        for az, el in sweeps:
+            res = self.simulate_rays_ensemble(az, el, members=members)
+            for j in range(len(members)):
+                one = {k: (v[j] if isinstance(v, np.ndarray) and k not in ('lats', 'lons', 'dist', 'heights') else v)
+                       for k, v in res.items()}
+                per[j].append(self._package(one, az, el))
+        pos = self.get_pos_and_time()
+        times = getattr(self, '_member_times', None) or [None] * self.n_members
+        out = []
+        for j, m in enumerate(members):
+            pt = dict(pos)
+            if times[m] is not None:
+                pt['time'] = times[m]
+            out.append(self._finish_scan(RadarScan(scan_type, list(elevations), list(azimuths), self.constants.RANGE_RADAR,
+                                                   pt, per[j])))
+        return out
+
+    def get_PPI_ensemble(self, elevations, azimuths=None, az_step=None, az_start=0, az_stop=359, members=None):
+        """get_PPI for the members of the ensemble: a list of RadarScan, one per member of `members` (None = all), each what
+        get_PPI gives on an operator loaded with that member alone (sensitivity cut and packaging as there)."""
+        if np.isscalar(elevations):
+            elevations = [elevations]
+        if az_step is None:
+            az_step = self.__config['radar']['3dB_beamwidth']
+        if azimuths is None or np.any(np.equal(azimuths, None)):
+            if az_start > az_stop:
+                azimuths = np.hstack((np.arange(az_start, 360., az_step), np.arange(0, az_stop + az_step, az_step)))
+            else:
+                azimuths = np.arange(az_start, az_stop + az_step, az_step)
+        azimuths = np.asarray(azimuths, dtype=float)
+        sweeps = [(azimuths, np.full(len(azimuths), float(e))) for e in elevations]
+        return self._ensemble_scans('ppi', members, sweeps, elevations, azimuths)
+
+    def get_RHI_ensemble(self, azimuths, elevations=None, elev_step=None, elev_start=0, elev_stop=90, members=None):
+        """get_RHI for the members of the ensemble: a list of RadarScan, one per member (see get_PPI_ensemble)."""
+        if np.isscalar(azimuths):
+            azimuths = [azimuths]
+        if elevations is None or np.any(np.equal(elevations, None)):
+            if elev_step is None:
+                elev_step = self.__config['radar']['3dB_beamwidth']
+            elevations = np.arange(elev_start, elev_stop + elev_step, elev_step)
+        elevations = np.asarray(elevations, dtype=float)
+        sweeps = [(np.full(len(elevations), float(a)), elevations) for a in azimuths]
+        return self._ensemble_scans('rhi', members, sweeps, elevations, azimuths)
 
     def _simulate_sweeps(self, sweeps):
         """[(az, el), ...] -> packaged sweeps.  The reference runs the sweeps of a scan one

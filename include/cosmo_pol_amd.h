@@ -28,6 +28,10 @@
  *                       cut_at_sensitivity (doppler_scatter.py:804) for the
  *                       whole sweep: ONE call per sweep instead of one
  *                       pool.map task per radial (radar_operator.py:429-432)
+ *   cpol_stage_member, cpol_num_members, cpol_select_member, cpol_run_sweep_members
+ *                       nothing: the reference runs one model state per process (one
+ *                       RadarOperator, one load_model_file; an ensemble is a shell loop
+ *                       that reloads the lookup tables for every member)
  */
 #ifndef COSMO_POL_AMD_H
 #define COSMO_POL_AMD_H
@@ -327,6 +331,24 @@ CPOL_API int  cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *da
                       const float llc[2], const float urc[2], const float res[2],
                       const double south_pole[2]);
 
+/* ---- ensemble members: many model states under ONE set of scattering / integral tables ------------------------------------
+ * Replaces in the reference: nothing -- the reference runs one model state per process.
+ * The cube staged by cpol_stage_model / cpol_stage_model_packed is member 0.  cpol_stage_member stages the variables of
+ * another state of the SAME model: same n_vars and variable order, same [nz][ny][nx] shape, same grid, same level heights
+ * (they are staged once, with member 0, and shared).  member = cpol_num_members(ctx) appends, a smaller index restages that
+ * member in place (0: the cube of cpol_stage_model, heights kept).  Device memory per member: exactly n_vars * nz * ny * nx * 4
+ * bytes.  Staging a member does not touch the scattering tables or the integral tables (no rebuild).  Out of memory:
+ * CPOL_ERR_NOMEM, the context stays usable with what was staged before.  cpol_stage_model and cpol_stage_model_packed drop all
+ * members >= 1.  Like the cube, members belong to the root context and are shared by its lanes: stage before cpol_fork (the
+ * call fails on a lane and on a context with live lanes). */
+CPOL_API int  cpol_stage_member(cpol_ctx *ctx, int member, int n_vars, const float *const *data);
+/* staged members including member 0 (0: no model staged); on a lane: its parent's */
+CPOL_API int  cpol_num_members(cpol_ctx *ctx);
+/* Every later cpol_run_sweep, cpol_interp_subbeams and cpol_interp_points of THIS context (a lane has its own selection; a new
+ * lane starts with its parent's) reads the variables of `member`: a pointer swap, no copy.  A sweep after cpol_select_member(k)
+ * carries the bits of a context staged with member k alone; a captured HIP graph is captured again.  CPOL_ERR_ARG: not staged. */
+CPOL_API int  cpol_select_member(cpol_ctx *ctx, int member);
+
 /* ---- model input in GRIB-1 simple packing, unpacked and derived on the device ------------------------------
  * One packed plane (one GRIB message): the bit string of BDS octet 12 onwards as it lies in the file (host memory),
  * and what turns its unsigned integers X into values (cosmo_pol_amd/grib1.py), in float64:
@@ -544,6 +566,21 @@ typedef struct {
  * or mask_sum8 with 2 * n_sub > 127. */
 CPOL_API int  cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *cols,
                       cpol_outputs *out);
+
+/* One scan over MANY members (replaces in the reference: nothing -- it runs one model state per process).  The ray paths,
+ * the geodesy, the rotated-pole transform, the grid cell and the level search of every sub-beam gate are evaluated ONCE
+ * (k_interp_members: in the forms cpol_run_sweep takes for the same rays), the variables of every requested member are
+ * gathered and interpolated behind them, and the second half of the launch sequence runs over n_members * n_rays rows (row
+ * m * n_rays + r = ray r of members[m]) as cpol_run_columns runs it: no interpolating forms, no graph replay
+ * ("launch_forms" reports them).  Every member's arrays carry the bits of cpol_run_sweep after cpol_select_member.
+ * members: n_members distinct staged member indices in any order, at most 64 per call.  p and tables: as for cpol_run_sweep
+ * (n_rays = the rays of ONE member).  out: the per-gate arrays are [n_members][n_rays * n_gates] (sz_total, DSPECTRUM and
+ * mask_sum8 likewise); lats, lons, dist and heights are [n_rays * n_gates], once; model_vars must be NULL (p->integrate_model is
+ * ignored).  All three outputs_on_device modes; works on a lane; the context's selected member is not changed.
+ * CPOL_ERR_ARG (the context stays usable): a member not staged or listed twice, model_vars requested, mask_sum8 with
+ * 2 * n_sub > 127, more than 2^31 - 1 sub-beam gates in all.  Work memory: cpol_mem_info's per_gate x n_members per sub-beam gate. */
+CPOL_API int  cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *tables,
+                            const int32_t *members, int n_members, cpol_outputs *out);
 
 /* CPOL_GEOM_SPACEBORNE helper: index of the first candidate gate below the
  * model-top ceiling for each (ray, vertical node): first_gate [n_rays*n_vnodes]
