@@ -69,3 +69,25 @@ def assert_close_nan(a, b, rtol, atol=0.0, name=''):
     bad = err > tol
     assert not bad.any(), '%s: %d/%d exceed tol, worst rel %.3e' % (
         name, bad.sum(), ok.sum(), np.max(err / np.maximum(np.abs(b[ok]), 1e-300)))
+
+
+def assert_radial_equals_oracle(rad, subs):
+    """The sub-radials of get_interpolated_radial against the oracle's interpolate_radial: values (melting fields included),
+    masks, elevation, distance and height bit for bit, latitude / longitude to 1e-11."""
+    assert len(rad) == len(subs)
+    for s, (r, sb) in enumerate(zip(rad, subs)):
+        assert set(sb.values) <= set(r.values), set(sb.values) - set(r.values)
+        for k, v in sb.values.items():
+            assert np.array_equal(r.values[k], v, equal_nan=True), (s, k)
+        assert np.array_equal(r.mask, sb.mask), s
+        assert np.array_equal(r.elev_profile, sb.elev_profile), s
+        assert np.array_equal(r.dist_profile, sb.dist_profile), s
+        assert np.array_equal(r.heights_profile, sb.heights_profile), s
+        np.testing.assert_allclose(r.lats_profile, sb.lats_profile, rtol=0, atol=1e-11)
+        np.testing.assert_allclose(r.lons_profile, sb.lons_profile, rtol=0, atol=1e-11)
+        np.testing.assert_allclose(r.quad_pt, sb.quad_pt, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(np.asarray(r.quad_weight, dtype=float), np.asarray(sb.quad_weight, dtype=float),
+                                   rtol=1e-12, atol=0)
+        assert r.has_melting == sb.has_melting, s
+        if sb.mask_ml is not None:
+            assert np.array_equal(r.mask_ml, sb.mask_ml), s

@@ -228,22 +228,7 @@ def test_interpolated_radial_vs_oracle(golden, name):
     rad = op.get_interpolated_radial(az, el)
     subs = beam.interpolate_radial(ocube, conf, az, el)
     assert len(rad) == len(subs) == int(g['n_sub'])
-    for s, (r, sb) in enumerate(zip(rad, subs)):
-        assert set(sb.values) <= set(r.values), set(sb.values) - set(r.values)
-        for k, v in sb.values.items():
-            assert np.array_equal(r.values[k], v, equal_nan=True), (s, k)
-        assert np.array_equal(r.mask, sb.mask), s
-        assert np.array_equal(r.elev_profile, sb.elev_profile), s
-        assert np.array_equal(r.dist_profile, sb.dist_profile), s
-        assert np.array_equal(r.heights_profile, sb.heights_profile), s
-        np.testing.assert_allclose(r.lats_profile, sb.lats_profile, rtol=0, atol=1e-11)
-        np.testing.assert_allclose(r.lons_profile, sb.lons_profile, rtol=0, atol=1e-11)
-        np.testing.assert_allclose(r.quad_pt, sb.quad_pt, rtol=0, atol=1e-12)
-        np.testing.assert_allclose(np.asarray(r.quad_weight, dtype=float), np.asarray(sb.quad_weight, dtype=float),
-                                   rtol=1e-12, atol=0)
-        assert r.has_melting == sb.has_melting, s
-        if sb.mask_ml is not None:
-            assert np.array_equal(r.mask_ml, sb.mask_ml), s
+    _cases.assert_radial_equals_oracle(rad, subs)
     for tag, r in (('subc_', rad[int(len(rad) / 2)]), ('subf_', rad[0])):
         for k in r.values:
             if tag + k in g.files:
