@@ -174,6 +174,7 @@ struct cpol_ctx {
     int fuse_gate1 = 0;                // CPOL_FUSE_GATE1=1: k_interp_gate1 instead of k_interp_sweep + k_gate1 (measured slower where it matters)
     int fuse_classify = 1;             // CPOL_FUSE_CLASSIFY=0: k_interp_sweep + k_classify instead of k_interp_classify (read when the context is created)
     int gate1 = 1;                     // CPOL_GATE1=0 / 2: never / also with melting species: the single-beam fused kernel (read when the context is created)
+    int subsum = 1;                    // CPOL_SUBSUM=0: the plain form: k_psd_lookup stores every item's columns and one thread of k_final walks the sub-beams in order (read when the context is created)
     int subsum_scalar = 0;             // CPOL_SUBSUM_FORM=scalar: the cooperative form of k_subbeam_sum takes its rows through the scalar cache instead of LDS
     int upload_kernel = 0;             // CPOL_TABLE_UPLOAD=kernel: the per-ray tables by k_upload_tables instead of hipMemcpyAsync (a measurement knob)
     int last_forms[12] = {0};          // the launch forms of the last sweep (cpol_debug_read "launch_forms"): [0] g1r, [1] k_gate1_ray, [2] single-beam gate kernel,
@@ -649,6 +650,7 @@ int cpol_create(int device, cpol_ctx **out)
     if (getenv("CPOL_RARE_OVERLAP")) ctx->rare_overlap = atoi(getenv("CPOL_RARE_OVERLAP")) != 0 ? 1 : 0;
     if (getenv("CPOL_RARE_DIRECT")) ctx->rare_direct = atoi(getenv("CPOL_RARE_DIRECT")) != 0 ? 1 : 0;
     if (getenv("CPOL_GATE1")) ctx->gate1 = atoi(getenv("CPOL_GATE1"));
+    if (getenv("CPOL_SUBSUM")) ctx->subsum = atoi(getenv("CPOL_SUBSUM")) != 0 ? 1 : 0;
     if (getenv("CPOL_SUBSUM_FORM")) ctx->subsum_scalar = !strcmp(getenv("CPOL_SUBSUM_FORM"), "scalar") ? 1 : 0;
     if (getenv("CPOL_SUBSUM_CHAIN")) ctx->subsum_chain = atoi(getenv("CPOL_SUBSUM_CHAIN")) != 0 ? 1 : 0;
     if (getenv("CPOL_SUBSUM_TEAM")) ctx->subsum_team = atoi(getenv("CPOL_SUBSUM_TEAM"));
@@ -763,6 +765,7 @@ int cpol_fork(cpol_ctx *parent, cpol_ctx **out)
     }
     c->use_graph = parent->use_graph;
     c->subsum_coop = parent->subsum_coop;
+    c->subsum = parent->subsum;
     c->subsum_small = parent->subsum_small;
     c->subsum_team = parent->subsum_team;
     c->subsum_chain = parent->subsum_chain;
@@ -2012,7 +2015,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const bool async_host = p->outputs_on_device == 2;    // pinned host buffers, no wait
     // the sub-beam sums by one thread per (gate, hydrometeor) with the 1-D table items evaluated in
     // place (k_subbeam_sum); CPOL_SUBSUM=0: k_psd_lookup stores them and k_final walks the rows
-    static const bool subsum_enabled = !(getenv("CPOL_SUBSUM") && atoi(getenv("CPOL_SUBSUM")) == 0);
+    const bool subsum_enabled = ctx->subsum != 0;     // (read when the context is created)
     bool subsum = subsum_enabled;
     {
         bool any1d = false;

@@ -444,8 +444,8 @@ CPOL_API int  cpol_set_num_hydro(cpol_ctx *ctx, int n_hydro);
  * 0: none), then where it was found, then the number of (block, function) pairs above the limit;
  * "itab_detail<slot>": per lambda panel and per function; "itab_times": device ms of build / gate.
  * Environment (read at every build): CPOL_ITAB=0 no tables at all, CPOL_ITAB_MELT=0 none for the
- * melting species, CPOL_ITAB_MAX_DEV=<x> another limit than 1e-10.  (Per sweep: CPOL_SUBSUM=0,
- * CPOL_LOOKUP_TILE=0, see INTEGRATION.md.)
+ * melting species, CPOL_ITAB_MAX_DEV=<x> another limit than 1e-10.  (Read by cpol_create: CPOL_SUBSUM=0;
+ * per sweep: CPOL_LOOKUP_TILE=0, see INTEGRATION.md.)
  * COST: a few ms of kernels per gamma / ice slot, ~90 ms per melting slot on full-size tables
  * (46 x 100 slices); TRANSIENT device memory of the build = n_e * n_t * n_panels * 12 (1-D) or
  * * 122 (2-D) synthetic items x ~164 B: 1 GB for a gamma slot, ~3.5 GB for a melting slot of that
