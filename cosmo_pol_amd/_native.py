@@ -15,6 +15,7 @@ CPOL_MAX_VARS = 24
 CPOL_MAX_HYDRO = 8
 CPOL_MAX_PAR = 6
 N_SZ = 12
+MAX_GATES = 5460                                    # CPOL_MAX_GATES: gates of a ray (the three scan rows in 64 KB of LDS)
 
 PSD_GAMMA, PSD_ICE_FIELD, PSD_MELTING = 0, 1, 2
 (RULE_RAIN_1MOM, RULE_SNOW_1MOM, RULE_GRAUPEL_1MOM, RULE_TWO_MOMENT, RULE_ICE_1MOM,
@@ -145,7 +146,7 @@ EXPORTS = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_
            'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_interp_subbeams', 'cpol_run_columns', 'cpol_counters',
            'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free', 'cpol_host_alloc_near',
            'cpol_device_pci_bus_id', 'cpol_mem_info',
-           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_broaden_rows',
+           'cpol_enable_timing', 'cpol_debug_read', 'cpol_debug_math', 'cpol_debug_scan', 'cpol_broaden_rows',
            'cpol_stage_model_packed', 'cpol_unpack_planes',
            'cpol_stage_member', 'cpol_num_members', 'cpol_select_member', 'cpol_run_sweep_members']
 MEMBERS_PER_CALL = 64                               # members one cpol_run_sweep_members call takes
@@ -280,6 +281,8 @@ def load_library():
     lib.cpol_stage_spectrum_tables.argtypes = [vp, C.c_int, vp, vp]
     lib.cpol_debug_math.restype = C.c_int
     lib.cpol_debug_math.argtypes = [vp, C.c_int, vp, vp, C.c_int]
+    lib.cpol_debug_scan.restype = C.c_int
+    lib.cpol_debug_scan.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int]
     lib.cpol_prepare.restype = C.c_int
     lib.cpol_prepare.argtypes = [vp]
     lib.cpol_stage_t_function.restype = C.c_int
@@ -756,6 +759,17 @@ class Context(object):
         y = np.empty_like(x)
         self._check(self.lib.cpol_debug_math(self.h, int(op), _ptr(x), _ptr(y), x.size),
                     'cpol_debug_math')
+        return y
+
+    def debug_scan(self, form, mul, x):
+        """The kernels' own range scan of every row of x [n_rows, n] float32: form 1 the wavefront form, 0 the one-lane loop; mul:
+        running product, else running sum."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError('debug_scan: x must be [n_rows, n]')
+        y = np.empty_like(x)
+        self._check(self.lib.cpol_debug_scan(self.h, int(form), int(bool(mul)), _ptr(x), _ptr(y), x.shape[0], x.shape[1]),
+                    'cpol_debug_scan')
         return y
 
     FORM_NAMES = ('g1r', 'gate1_ray', 'gate1', 'interp_classify', 'rare_direct', 'subbeam_sum', 'final_inplace',

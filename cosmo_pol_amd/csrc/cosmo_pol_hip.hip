@@ -610,6 +610,42 @@ int build_itabs(cpol_ctx *ctx)
 
 }  // namespace
 
+// The range scans keep [3][n_gates] float32 of a ray in dynamic LDS, and a workgroup may ask for 64 KB in all without a kernel
+// attribute -- its STATIC part included: k_gate1_ray_scan has 12 bytes of it (s_lookup, s_last, s_done), k_final and k_scan_rays
+// none.  CPOL_MAX_GATES (the header) leaves CPOL_SCAN_LDS_STATIC bytes for it, whichever kernel runs the scans; cpol_create
+// compares that figure with what the compiler reports for each of them.
+#define CPOL_SCAN_LDS_STATIC 16
+static_assert((size_t)3 * CPOL_MAX_GATES * sizeof(float) + CPOL_SCAN_LDS_STATIC <= 64 * 1024 &&
+              (size_t)3 * (CPOL_MAX_GATES + 1) * sizeof(float) + CPOL_SCAN_LDS_STATIC > 64 * 1024,
+              "CPOL_MAX_GATES: the most gates whose three scan rows fit 64 KB of LDS next to the scan kernels' static part");
+
+static bool scan_kernels_fit_lds()
+{
+    const void *const kernels[4] = {(const void *)k_gate1_ray_scan, (const void *)k_scan_rays, (const void *)k_final<CPOL_FINAL_THREADS>,
+                                    (const void *)k_final<2 * CPOL_FINAL_THREADS>};
+    for (const void *k : kernels) {
+        hipFuncAttributes fa{};
+        if (hipFuncGetAttributes(&fa, k) != hipSuccess || fa.sharedSizeBytes > CPOL_SCAN_LDS_STATIC) return false;
+    }
+    return true;
+}
+
+// test hook (cpol_debug_scan): one wavefront per row takes the row through LDS and runs one of the product's two range-scan
+// functions on it as they are (cpol_final.inl; both are compiled whatever CPOL_SCAN_FORM says)
+template <bool MUL, bool WAVE>
+__global__ __launch_bounds__(64) void k_debug_scan(const float *__restrict__ x, float *__restrict__ y, int n)
+{
+    extern __shared__ float s_dbg_row[];               // [n]
+    const int lane = threadIdx.x;
+    const long base = (long)blockIdx.x * n;
+    for (int g = lane; g < n; g += 64) s_dbg_row[g] = x[base + g];
+    __syncthreads();
+    if (WAVE) scan_lds_wave_exact<MUL>(s_dbg_row, n, lane);
+    else if (lane == 0) scan_lds_sequential<MUL>(s_dbg_row, n);
+    __syncthreads();
+    for (int g = lane; g < n; g += 64) y[base + g] = s_dbg_row[g];
+}
+
 extern "C" {
 
 int cpol_create(int device, cpol_ctx **out)
@@ -626,6 +662,13 @@ int cpol_create(int device, cpol_ctx **out)
         return CPOL_ERR_HIP;
     }
     ctx->own_stream = true;
+    static const bool scans_fit = scan_kernels_fit_lds();      // (once per process: a build whose scan kernels outgrew CPOL_SCAN_LDS_STATIC)
+    if (!scans_fit) {
+        (void)hipGetLastError();
+        (void)hipStreamDestroy(ctx->stream);
+        delete ctx;
+        return CPOL_ERR_HIP;
+    }
     if (getenv("CPOL_ERRWORD") && !strcmp(getenv("CPOL_ERRWORD"), "pageable")) ctx->h_errword = nullptr;      // (measurement knob: round 4's read)
     else if (hipHostMalloc((void **)&ctx->h_errword, 64, hipHostMallocDefault) != hipSuccess) { ctx->h_errword = nullptr; (void)hipGetLastError(); }
     if (hipMalloc((void **)&ctx->d_errword, sizeof(int)) != hipSuccess ||
@@ -1725,6 +1768,11 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             ctx->err = "cpol_run_sweep: launch-grid limits exceeded (n_rays * n_sub < 2^31, n_gates <= 65535 * 256) or bad outputs_on_device";
             return CPOL_ERR_ARG;
         }
+        // (refused here, before the table uploads and the geometry kernel are queued: nothing of the call has reached the device)
+        if (ng > CPOL_MAX_GATES) {
+            ctx->err = "cpol_run_sweep: n_gates too large for the range scans (3 * n_gates floats of LDS: at most CPOL_MAX_GATES gates)";
+            return CPOL_ERR_ARG;
+        }
     }
     int rc;
 
@@ -1960,7 +2008,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // (every argument check and every allocation of the sequence happens before its first launch: an error return
     // further down would leave the sweep's counter set half used; see counters_dirty)
-    if ((size_t)3 * ng * sizeof(float) > 64 * 1024) { ctx->err = "cpol_run_sweep: n_gates too large for the range scans (3 * n_gates floats of LDS)"; return CPOL_ERR_ARG; }
     if (out->mask_sum8 && 2 * n_sub > 127) { ctx->err = "cpol_run_sweep: outputs->mask_sum8 needs 2 * n_sub <= 127 (one byte per gate)"; return CPOL_ERR_ARG; }
     // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
     const void *col_src[CPOL_MAX_VARS + 6] = {};
@@ -3286,6 +3333,35 @@ int cpol_counters(cpol_ctx *ctx, cpol_counters_t *out)
         return report_domain_error(ctx);
     }
     *out = ctx->counters;
+    return CPOL_OK;
+}
+
+int cpol_debug_scan(cpol_ctx *ctx, int form, int mul, const float *x, float *y, int n_rows, int n)
+{
+    if (!ctx) return CPOL_ERR_ARG;
+    if (!x || !y || n_rows < 1 || n_rows > 65535 || n < 1 || (size_t)n * sizeof(float) > 64 * 1024 || form < 0 || form > 1) {
+        ctx->err = "cpol_debug_scan: form 0 / 1, 1 <= n_rows <= 65535, 1 <= n <= 16384 (a row of float32 in 64 KB of LDS)";
+        return CPOL_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n_rows * n * sizeof(float), lds = (size_t)n * sizeof(float);
+    DevBuf dx, dy;
+    int rc;
+    if ((rc = upload(ctx, dx, x, bytes))) return rc;
+    if ((rc = ensure(ctx, dy, bytes))) { free_buf(dx); return rc; }
+    const dim3 grid((unsigned)n_rows), block(64);
+    const float *px = (const float *)dx.p;
+    float *py = (float *)dy.p;
+    if (form == 1 && mul) hipLaunchKernelGGL((k_debug_scan<true, true>), grid, block, lds, ctx->stream, px, py, n);
+    else if (form == 1) hipLaunchKernelGGL((k_debug_scan<false, true>), grid, block, lds, ctx->stream, px, py, n);
+    else if (mul) hipLaunchKernelGGL((k_debug_scan<true, false>), grid, block, lds, ctx->stream, px, py, n);
+    else hipLaunchKernelGGL((k_debug_scan<false, false>), grid, block, lds, ctx->stream, px, py, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(y, dy.p, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    free_buf(dx);
+    free_buf(dy);
+    if (e != hipSuccess) { ctx->err = std::string("cpol_debug_scan: ") + hipGetErrorString(e); return CPOL_ERR_HIP; }
     return CPOL_OK;
 }
 

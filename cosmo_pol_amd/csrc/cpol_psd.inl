@@ -261,6 +261,9 @@ __global__ void k_debug_math(int op, const double *__restrict__ x, double *__res
         const float q = n / d, p = div32_by(n, rcp_for_div32(d));
         y[i] = (__float_as_int(q) == __float_as_int(p) || (q != q && p != p)) ? 0.0 : 1.0;
         break; }
+    case 8:         // the two-way attenuation factor of a gate exactly as gate_finish forms it: x[i] holds a float32, the float32 result comes back as a double
+        y[i] = (double)(float)exp10((double)(float)x[i]);
+        break;
     default: y[i] = x[i];
     }
 }

@@ -65,6 +65,9 @@ enum {
 #define CPOL_MAX_VARS   24
 #define CPOL_MAX_HYDRO  8
 #define CPOL_N_SZ       12      /* columns of a LUT row (compute_lut_sz.py:265-297) */
+#define CPOL_MAX_GATES  5460    /* gates of a ray: the operands of its three range scans (3 x n_gates float32) lie in the
+                                   64 KB of LDS a workgroup may ask for, 16 bytes of which stay with the scan kernels'
+                                   own variables; more gates: CPOL_ERR_ARG before anything is launched */
 #define CPOL_TRAJ_STRIDE 4      /* doubles per (ray, vertical node) entry of the `traj` table */
 #define CPOL_GEO_STRIDE  8      /* doubles per (ray, horizontal node) entry of the `geo` table */
 #define CPOL_SITE_STRIDE 8      /* doubles per ray of the `site` table */
@@ -562,8 +565,8 @@ typedef struct {
  * and the sensitivity cut, into the same cpol_outputs struct; lats / lons / dist / heights are not written (the columns carry
  * no geometry).  p: n_rays, n_gates, n_sub and the radar / scheme fields as for cpol_run_sweep; n_hnodes, n_vnodes,
  * geometry_mode and the site fields are ignored.  Needs staged hydrometeors, no staged model; works on a lane.
- * CPOL_ERR_ARG (the context stays usable) on bad shapes, a missing variable pointer, a descriptor index >= n_vars
- * or mask_sum8 with 2 * n_sub > 127. */
+ * CPOL_ERR_ARG (the context stays usable) on bad shapes, a missing variable pointer, a descriptor index >= n_vars,
+ * n_gates > CPOL_MAX_GATES (as for cpol_run_sweep: refused before anything is queued) or mask_sum8 with 2 * n_sub > 127. */
 CPOL_API int  cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *cols,
                       cpol_outputs *out);
 
@@ -614,8 +617,16 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
 /* test hook: evaluates one of the device math helpers of the melting-species kernel on
- * host arrays (op 0 exp, 1 log, 2 cbrt, 3 cbrt via x^(-1/6), 4 x^(1/6), 5 x^(1/4), 6 1/x) */
+ * host arrays (op 0 exp, 1 log, 2 cbrt, 3 cbrt via x^(-1/6), 4 x^(1/6), 5 x^(1/4), 6 1/x; 7: float32 pairs (n, d) in
+ * the words of x, 0 where the reciprocal division has the bits of n / d; 8: the attenuation factor of a gate as the
+ * kernels form it, (float)exp10((double)x) of a float32 x held in the double, the float32 result as a double) */
 CPOL_API int  cpol_debug_math(cpol_ctx *ctx, int op, const double *x, double *y, int n);
+
+/* test hook: the range-scan functions of the kernels themselves on n_rows rows of n float32 (host arrays x -> y, row
+ * after row): one workgroup per row copies it into LDS, runs the running sum (mul = 0) or product (mul != 0) of the
+ * wavefront form (form 1: the shifted adds / multiplies the sweeps use) or the one-lane loop (form 0), and copies it
+ * back.  CPOL_ERR_ARG: form not 0 / 1, n_rows < 1 or > 65535, n < 1 or n > 16384 (a row in 64 KB of LDS). */
+CPOL_API int  cpol_debug_scan(cpol_ctx *ctx, int form, int mul, const float *x, float *y, int n_rows, int n);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ BEFORE = ['cpol_create', 'cpol_destroy', 'cpol_fork', 'cpol_last_error', 'cpol_s
           'cpol_stage_t_function', 'cpol_prepare', 'cpol_interp_points', 'cpol_ray_tables', 'cpol_run_sweep', 'cpol_interp_subbeams',
           'cpol_run_columns', 'cpol_counters', 'cpol_spaceborne_first_gate', 'cpol_host_alloc', 'cpol_host_free',
           'cpol_host_alloc_near', 'cpol_device_pci_bus_id', 'cpol_mem_info', 'cpol_enable_timing', 'cpol_debug_read',
-          'cpol_debug_math', 'cpol_broaden_rows', 'cpol_stage_model_packed', 'cpol_unpack_planes']
+          'cpol_debug_math', 'cpol_debug_scan', 'cpol_broaden_rows', 'cpol_stage_model_packed', 'cpol_unpack_planes']
 
 
 def test_member_prototypes_match_header(tmp_path):
