@@ -82,7 +82,10 @@ class RayTables(C.Structure):
                 ('site', C.c_void_p), ('paths', C.c_void_p), ('nyquist', C.c_void_p),
                 ('version', C.c_uint64), ('varray', C.c_void_p), ('sub_smooth', C.c_void_p),
                 ('ml_filter', C.c_void_p),
-                ('ml_radius', C.c_int32), ('pad_', C.c_int32)]
+                ('ml_radius', C.c_int32), ('pad_', C.c_int32),
+                # time blend (cpol_run_sweep_members only; all zero = off)
+                ('ray_state', C.c_void_p), ('ray_weight', C.c_void_p),
+                ('time_blend', C.c_int32), ('pad_time_', C.c_int32)]
 
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',

@@ -149,6 +149,8 @@ struct cpol_ctx {
     DevBuf b_present;                  // k_gate1_ray's sweeps: one word per (ray, 64-gate tile), which hydrometeor slots may have an item there (k_interp_sweep writes, k_gate1_ray reads)
     DevBuf b_colin;                    // cpol_run_columns with host inputs: the caller's columns on the device, read by k_columns_ingest
     DevBuf b_xscr, b_xgeo;             // cpol_interp_subbeams: the long-form gate kernel's scratch values, the geometry of every sub-beam
+    DevBuf b_timed;                    // a time-blended sweep: [n_rays] state indices, then [n_rays] weights (k_interp_timed reads them)
+    std::vector<char> timed_shadow;    // ... and what b_timed holds (host copy): unchanged brackets are not uploaded again
     // last sweep shapes (debug reads)
     long last_n_sbg = 0, last_n_rg = 0;
     int last_n_rays = 0, last_n_gates = 0, last_n_sub = 0, last_n_v = 0, last_n_keys = 0;
@@ -754,7 +756,7 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
                      &ctx->b_vn, &ctx->b_icefirst, &ctx->b_rvel, &ctx->b_proj, &ctx->b_blkranked, &ctx->b_rec, &ctx->b_vmask, &ctx->b_gscan, &ctx->b_defer,
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8,
-                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon};
+                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
@@ -1722,9 +1724,14 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
 //   mem->n_rays rays (k_trajectory where the sweep would run it, then k_interp_members instead of k_interp_sweep) and writes
 //   member mm into the rows [mm * mem->n_rays, ...) of the work arrays; `t` holds the per-ray tables repeated for every member.
 //   The launch-form rules are the column call's: no interpolating forms, no graph replay.
+//   With mem->timed (cpol_ray_tables_t.time_blend) the sweep keeps its n_rays rows: k_interp_timed writes ONE block of rows, the
+//   values of ray r blended from mem->V[ray_state[r]] and the cube behind it; `t` is the caller's; the rest as above.
 struct MembersCall {
     int n_members, n_rays;
     const float *V[CPOL_MEMBERS_PER_CALL];
+    bool timed;
+    const int32_t *ray_state;           // [n_rays] host (timed)
+    const float *ray_weight;            // [n_rays] host (timed)
 };
 
 static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
@@ -1738,6 +1745,11 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ctx->err = "cpol_run_sweep: model / hydrometeors not staged or bad arguments";
         return CPOL_ERR_ARG;
     }
+    if (t->time_blend != 0 && !(mem && mem->timed)) {
+        ctx->err = "cpol_ray_tables_t.time_blend belongs to cpol_run_sweep_members alone";
+        return CPOL_ERR_ARG;
+    }
+    const bool timed = mem && mem->timed;
     const double t_enter = now_ns();
     (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
     for (int j = 0; j < ctx->hs.n_hydro; ++j)
@@ -1753,7 +1765,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const int n_vars = cols ? cols->n_vars : ctx->model.n_vars, n_hyd = ctx->hs.n_hydro, n_keys = ctx->hs.n_keys;
     const long n_rg = (long)n_rays * ng;
     const long n_sbg = n_rg * n_sub;
-    const int geo_rays = mem ? mem->n_rays : n_rays;     // the rays the geometry is evaluated for (ensemble: once for all members)
+    const int geo_rays = mem ? mem->n_rays : n_rays;     // the rays the geometry is evaluated for (ensemble: once for all members; timed: n_rays)
     if (n_sbg >= (1L << 31)) { ctx->err = "cpol_run_sweep: too many sub-beam gates in one call"; return CPOL_ERR_ARG; }
     {
         // re-validated here: a C caller may have reached this state through cpol_stage_hydro alone
@@ -1920,6 +1932,36 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             set->poly_version = set->version;
             set->poly_scale = geo_poly_scale;
             set->poly_site[0] = p->radar_lon; set->poly_site[1] = p->sin_u1; set->poly_site[2] = p->cos_u1;
+        }
+    }
+    if (timed) {
+        // the per-ray brackets: through a slot of the page-locked staging ring (a copy from the caller's pageable arrays would make the
+        // call wait for the stream), one host-to-device copy, skipped when the context's device copy already holds these values
+        const size_t nb = (size_t)n_rays * sizeof(int32_t), total = 2 * nb;
+        void *const was = ctx->b_timed.p;
+        ENSURE(ctx->b_timed, total);
+        if (ctx->b_timed.p != was) ctx->timed_shadow.clear();
+        if (ctx->timed_shadow.size() != total || memcmp(ctx->timed_shadow.data(), mem->ray_state, nb) != 0 ||
+            memcmp(ctx->timed_shadow.data() + nb, mem->ray_weight, nb) != 0) {
+            ctx->timed_shadow.clear();                           // (not valid until the copy is queued)
+            cpol_ctx::Staging &sg = ctx->stg[ctx->stg_next];
+            ctx->stg_next = (ctx->stg_next + 1) % 4;
+            if (sg.used) HIPCHK(hipEventSynchronize(sg.ev));    // its last copy has left the buffer
+            if (sg.cap < total) {
+                if (sg.p) (void)hipHostFree(sg.p);
+                sg.p = nullptr; sg.cap = 0;
+                HIPCHK(hipHostMalloc(&sg.p, total + total / 4 + 4096, hipHostMallocDefault));
+                sg.cap = total + total / 4 + 4096;
+            }
+            if (!sg.ev) HIPCHK(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+            memcpy(sg.p, mem->ray_state, nb);
+            memcpy((char *)sg.p + nb, mem->ray_weight, nb);
+            HIPCHK(hipMemcpyAsync(ctx->b_timed.p, sg.p, total, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipEventRecord(sg.ev, ctx->stream));
+            sg.used = true;
+            try {
+                ctx->timed_shadow.assign((const char *)sg.p, (const char *)sg.p + total);
+            } catch (...) { ctx->timed_shadow.clear(); }
         }
     }
     ENSURE(ctx->b_vals, (size_t)n_vars * n_sbg * sizeof(float));
@@ -2166,7 +2208,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     for (int k = 0; k < 14; ++k) {
         obytes[k] = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
         produced[k] = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
-        if (mem && k >= O_LAT && k <= O_HGT) obytes[k] = obytes[k] / (size_t)mem->n_members;      // (the geometry once, not per member)
+        if (mem && !timed && k >= O_LAT && k <= O_HGT) obytes[k] = obytes[k] / (size_t)mem->n_members;      // (the geometry once, not per member)
         own[k] = &ctx->b_out[k];
     }
     obytes[O_RVEL] = (size_t)n_rg * sizeof(double);            produced[O_RVEL] = doppler;    own[O_RVEL] = &ctx->b_rvel;
@@ -2337,6 +2379,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         for (int k = 0; k < mem->n_members; ++k) ma.V[k] = mem->V[k];
         ma.n_members = mem->n_members;
         ma.n_sbg1 = (long)geo_rays * n_sub * ng;
+        if (timed) {
+            TimedArgs tg{};                 // (the per-ray brackets: uploaded above, with the work buffers)
+            tg.ray_state = (const int *)ctx->b_timed.p;
+            tg.ray_weight = (const float *)((const int32_t *)ctx->b_timed.p + n_rays);
+            hipLaunchKernelGGL(k_interp_timed, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma, tg);
+        } else
         hipLaunchKernelGGL(k_interp_members, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma);
     } else if (!fused && !fused_gate1 && !exp_skip_interp)
     hipLaunchKernelGGL(k_interp_sweep, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st,
@@ -3211,6 +3259,40 @@ int cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol
         p->n_hnodes < 1 || !t->traj || !t->geo) {
         ctx->err = "cpol_run_sweep_members: bad arguments (1 <= n_members <= 64 per call)";
         return CPOL_ERR_ARG;
+    }
+    if (t->time_blend != 0) {
+        // ---- ONE scan, every ray blended from the two states that bracket its time ----
+        if (t->time_blend != 1 || !t->ray_state || !t->ray_weight) {
+            ctx->err = "cpol_run_sweep_members: time_blend is 0 or 1 and needs ray_state and ray_weight";
+            return CPOL_ERR_ARG;
+        }
+        if (p->geometry_mode != CPOL_GEOM_GROUND_43) {
+            ctx->err = "cpol_run_sweep_members: time_blend takes ground radars on the 4/3-earth ray paths (no spaceborne geometry, no host paths)";
+            return CPOL_ERR_ARG;
+        }
+        MembersCall mc{};
+        mc.n_members = n_members;
+        mc.n_rays = p->n_rays;
+        mc.timed = true;
+        mc.ray_state = t->ray_state;
+        mc.ray_weight = t->ray_weight;
+        for (int k = 0; k < n_members; ++k) {
+            mc.V[k] = member_cube(ctx, members[k]);
+            if (!mc.V[k]) { ctx->err = "cpol_run_sweep_members: a requested member is not staged"; return CPOL_ERR_ARG; }
+        }
+        for (int r = 0; r < p->n_rays; ++r) {
+            const int32_t lo = t->ray_state[r];
+            const float w = t->ray_weight[r];
+            if (!(w >= 0.0f && w < 1.0f)) {             // (NaN fails both)
+                ctx->err = "cpol_run_sweep_members: time_blend: a ray_weight outside [0, 1) or not finite";
+                return CPOL_ERR_ARG;
+            }
+            if (lo < 0 || lo >= n_members || (w != 0.0f && lo + 1 >= n_members)) {
+                ctx->err = "cpol_run_sweep_members: time_blend: a ray_state (or the state behind it, with a weight > 0) outside `members`";
+                return CPOL_ERR_ARG;
+            }
+        }
+        return run_sequence(ctx, p, t, nullptr, nullptr, out, &mc);
     }
     if (out->model_vars) {
         ctx->err = "cpol_run_sweep_members: antenna-integrated model variables are not part of an ensemble call (outputs->model_vars must be NULL)";

@@ -692,9 +692,11 @@ struct ExportArgs {
 // to the rows of EVERY requested member (mb; cpol_members.inl), whose values come from their own cubes.
 #include "cpol_members.inl"
 
-template <bool KEEP, bool EXPORT = false, bool MEMBERS = false>
+// TIMED (k_interp_timed, a time-blended sweep; with MEMBERS): the rows are those of ONE sweep, and the values of a ray come from the two
+// states of mb that bracket its time, blended by its weight (tm; cpol_members.inl).
+template <bool KEEP, bool EXPORT = false, bool MEMBERS = false, bool TIMED = false>
 __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &a, float *sv, long &sbg_out, float &elev_out,
-                                           const ExportArgs *x = nullptr, const MemberArgs *mb = nullptr)
+                                           const ExportArgs *x = nullptr, const MemberArgs *mb = nullptr, const TimedArgs *tm = nullptr)
 {
     // ---- which (ray, sub-beam, block of gates) this workgroup takes ----
     // The hardware deals workgroups to the 8 XCDs round robin by their linear index, and every XCD has its own L2.  With
@@ -745,7 +747,7 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
         // no gate here (ray shorter than the batch: spaceborne / host paths): counts
         // as "above the model", produces no item
         if constexpr (MEMBERS) {
-            members_fill(m, a, *mb, sbg, 1, 0.0f, qnan, qnan);
+            members_fill(m, a, TIMED ? 1 : mb->n_members, mb->n_sbg1, sbg, 1, 0.0f, qnan, qnan);
         } else {
         a.mask[sbg] = 1;
         for (int v = 0; v < m.n_vars; ++v)
@@ -943,7 +945,7 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
         !(rlon == rlon) || !(rlat == rlat)) {
         atomicOr(a.error_flag, 1);          // sticky until reported (cpol_synchronize / cpol_counters)
         if constexpr (MEMBERS) {
-            members_fill(m, a, *mb, sbg, 2, e32, rlat, rlon);
+            members_fill(m, a, TIMED ? 1 : mb->n_members, mb->n_sbg1, sbg, 2, e32, rlat, rlon);
         } else {
         a.mask[sbg] = 2;
         for (int v = 0; v < m.n_vars; ++v)
@@ -970,6 +972,9 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     ITRACE(itr, 1);                                        // trajectory + grid coordinates
     gate_geometry(m, rlat, rlon, h32, g ITRACE_PASS);
     if constexpr (MEMBERS) {
+        if constexpr (TIMED)                // (the ray's bracket: wave-uniform, scalar loads)
+            members_values<true>(m, a, *mb, g, sbg, h32, e32, rlat, rlon, tm->ray_state[ray], tm->ray_weight[ray]);
+        else
         members_values(m, a, *mb, g, sbg, h32, e32, rlat, rlon);
         if (sub == a.central_sub) {         // the central sub-beam's coordinates: once, not per member
             const long rg = (long)ray * a.n_gates + gate;
@@ -1099,6 +1104,16 @@ __global__ __launch_bounds__(256) void k_interp_members(ModelDev m, InterpArgs a
     long sbg;
     float e;
     interp_gate<false, false, true>(m, a, nullptr, sbg, e, nullptr, &mb);
+}
+
+// The gate kernel of a time-blended sweep (cpol_run_sweep_members with cpol_ray_tables_t.time_blend): the geometry of every sub-beam
+// gate once, its values from the two states that bracket the ray's time.  grid = k_interp_sweep's, with its dealing of rays to the XCDs.
+__global__ __launch_bounds__(256) void k_interp_timed(ModelDev m, InterpArgs a, MemberArgs mb, TimedArgs tm)
+{
+    clear_counters(a.zero_buf, a.zero_n, a.zero_buf2, a.zero_n2);
+    long sbg;
+    float e;
+    interp_gate<false, false, true, true>(m, a, nullptr, sbg, e, nullptr, &mb, &tm);
 }
 
 // ---- caller-supplied sub-beam columns (cpol_run_columns) ----

@@ -12,6 +12,7 @@ callable (hydrometeors, frequency, scheme) -> {h: table}),
 `load_model_arrays(...)` (pycosmo / GRIB are not available here).
 """
 import copy
+import datetime
 from collections.abc import MutableMapping
 import ctypes as C
 import math
@@ -1168,7 +1169,7 @@ class RadarOperator(object):
 
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False, subbeams=None, members=None):
+                  pinned=False, subbeams=None, members=None, timed=None):
         if self._model_staged:
             self._sync_edr()
         conf = self.__config
@@ -1287,6 +1288,14 @@ class RadarOperator(object):
 
         if subbeams is not None:
             return self._export_subbeams(p, t, keep, sub, az, el, n_gates, lane, **subbeams)
+        if timed is not None:
+            # a time-blended sweep (simulate_rays_at): the states it may read, and per ray the earlier state's index in that
+            # list and the weight of the one behind it.  (A copy: the prepared structs are shared between calls.)
+            tm_states, tm_lo, tm_w = timed
+            t = N.RayTables.from_buffer_copy(t)
+            t.time_blend = 1
+            t.ray_state, t.ray_weight = tm_lo.ctypes.data, tm_w.ctypes.data
+            keep = list(keep) + [tm_lo, tm_w]
         o = N.Outputs()
         res = {}
         geom = None
@@ -1334,6 +1343,8 @@ class RadarOperator(object):
         ctx = self._lane(lane)
         if members is not None:
             ctx.run_sweep_members(p, t, members, o)
+        elif timed is not None:
+            ctx.run_sweep_members(p, t, tm_states, o)
         else:
             ctx.run_sweep(p, t, o)
         del keep
@@ -1578,6 +1589,145 @@ class RadarOperator(object):
         elevations = np.asarray(elevations, dtype=float)
         sweeps = [(np.full(len(elevations), float(a)), elevations) for a in azimuths]
         return self._ensemble_scans('rhi', members, sweeps, elevations, azimuths)
+
+    # ------------------------------------------------------------------ time-interpolated scans
+    # (replaces in the reference: nothing -- it simulates every ray at the time of the one model state it read)
+    def load_model_series(self, states, times=None, zlevels=None, proj_info=None, resolution=None, cfilename=None):
+        """load_model_ensemble for a series of forecast times, plus the times: `states` as its `members`, `times` one per
+        state -- numbers (seconds on one clock) or datetimes, strictly increasing; None takes each file's own time
+        (ValueError if a state has none).  State 0 becomes "the model"; the *_at calls simulate rays at any time inside
+        the series.  Whatever drops the members (a later load_model_*, a restaged cube) drops the series too."""
+        from . import timeline
+        states = list(states)
+        if times is not None and len(list(times)) != len(states):
+            raise ValueError('load_model_series: %d times for %d states' % (len(list(times)), len(states)))
+        if times is not None:
+            secs = timeline.check_series(timeline.as_seconds(list(times)))      # (before anything is staged)
+        self.load_model_ensemble(states, zlevels=zlevels, proj_info=proj_info, resolution=resolution, cfilename=cfilename)
+        if times is None:
+            own = list(self._member_times)
+            for i, t in enumerate(own):
+                if t is None:
+                    raise ValueError('load_model_series: state %d carries no time of its own; give `times`' % i)
+            secs = timeline.check_series(timeline.as_seconds(own))
+        self._series = (self._staged_serial, len(states), secs)
+
+    @property
+    def series_times(self):
+        """float64 seconds of the staged series (read-only), or None when no series is staged."""
+        sr = getattr(self, '_series', None)
+        if sr is None or not self._model_staged or sr[0] != self._staged_serial or sr[1] != self._n_members:
+            return None
+        out = sr[2].view()
+        out.flags.writeable = False
+        return out
+
+    def _timed_check(self):
+        if self.distributed:
+            raise NotImplementedError('time-interpolated scans with a process group: sharding rays over ranks is not built')
+        conf = self.__config
+        if conf['radar']['coords'][2] > K.MAX_MODEL_HEIGHT:
+            raise NotImplementedError('spaceborne geometry: time-interpolated scans take ground radars')
+        if conf['refraction']['scheme'] == 2:
+            raise NotImplementedError('time-interpolated scans use the 4/3-earth ray paths (refraction scheme 1): with '
+                                      'scheme 2 the ray path would depend on the time')
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        if self.series_times is None:
+            raise ValueError('no series staged (load_model_series)')
+
+    def simulate_rays_at(self, azimuths, elevations, times, on_device=False, device_outputs=None, apply_sensitivity=True,
+                         lane=0, pinned=False):
+        """simulate_rays with the model at the time of every ray: `times` is one value (number or datetime, on the clock
+        of load_model_series) or one per ray, inside the series -- ValueError otherwise, no extrapolation.  A ray between
+        two states reads both, blended per staged variable by timeline.blend_states' rule on the device (k_interp_timed);
+        a ray on a state's time reads that state alone.  The dict of simulate_rays (model variables with
+        output_variables='all'), every array with the bits of simulate_rays on an operator loaded with the host-blended
+        cube.  Only the states the rays need are listed for the library; rays that need more than 64 are cut into
+        consecutive groups (host outputs only; with several groups a pinned call waits)."""
+        self._timed_check()
+        from . import timeline
+        az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
+        el = np.asarray(elevations, dtype=np.float64).reshape(-1)
+        if az.shape != el.shape:
+            raise ValueError('azimuths and elevations must have the same length')
+        tt = timeline.as_seconds(times)
+        if tt.ndim == 0 or tt.size == 1:
+            tt = np.full(len(az), float(tt.reshape(-1)[0]))
+        tt = tt.reshape(-1)
+        if len(tt) != len(az):
+            raise ValueError('times: one value, or one per ray (%d rays, %d times)' % (len(az), len(tt)))
+        lo, w = timeline.bracket(self.series_times, tt)
+        groups = timeline.plan_ray_groups(lo, w, N.MEMBERS_PER_CALL)
+        if len(groups) > 1 and device_outputs is not None:
+            raise ValueError('simulate_rays_at: the rays read more than %d states; with device outputs split the rays'
+                             % N.MEMBERS_PER_CALL)
+        coords = self.__config['radar']['coords']
+        rr = self.constants.RANGE_RADAR
+        parts = []
+        for r0, r1, first, count in groups:
+            tm = (np.arange(first, first + count, dtype=np.int32), np.ascontiguousarray(lo[r0:r1] - first, dtype=np.int32),
+                  np.ascontiguousarray(w[r0:r1], dtype=np.float32))
+            parts.append(self._run_rays(az[r0:r1], el[r0:r1], coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
+                                        device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
+                                        pinned=pinned and len(groups) == 1, timed=tm))
+        if len(parts) == 1:
+            return parts[0]
+        return {k: (v if not isinstance(v, np.ndarray) else
+                    np.concatenate([q[k] for q in parts], axis=1 if k == 'model_vars' else 0))
+                for k, v in parts[0].items()}
+
+    def _scan_at(self, scan_type, sweeps, times, elevations, azimuths):
+        self._timed_check()
+        from . import timeline
+        times = [times] if np.isscalar(times) or isinstance(times, (datetime.datetime, np.datetime64)) else list(times)
+        if len(times) != len(sweeps):
+            raise ValueError('times: one value or one array per sweep (%d sweeps, %d entries)' % (len(sweeps), len(times)))
+        full = []
+        for (az, el), t in zip(sweeps, times):
+            t = timeline.as_seconds(t)
+            full.append((az, el, np.full(len(az), float(t)) if t.ndim == 0 else t.reshape(-1)))
+        out = []
+        for group in self._sweep_groups(full):                # (the memory-budget rule of the ordinary scans)
+            res = self.simulate_rays_at(np.concatenate([g[0] for g in group]), np.concatenate([g[1] for g in group]),
+                                        np.concatenate([g[2] for g in group]))
+            r0 = 0
+            for az, el, _ in group:
+                r1 = r0 + len(az)
+                part = {k: (v[:, r0:r1] if k in ('model_vars',) else v[r0:r1]) if isinstance(v, np.ndarray) else v
+                        for k, v in res.items()}
+                out.append(self._package(part, az, el))
+                r0 = r1
+        return self._finish_scan(RadarScan(scan_type, list(elevations), list(azimuths), self.constants.RANGE_RADAR,
+                                           self.get_pos_and_time(), out))
+
+    def get_PPI_at(self, elevations, times, azimuths=None, az_step=None, az_start=0, az_stop=359):
+        """get_PPI with the model at the time of every sweep or ray: `times` holds one value per sweep, or one array (a time
+        per ray) per sweep.  The RadarScan get_PPI returns; every sweep equals simulate_rays_at of its rays."""
+        if np.isscalar(elevations):
+            elevations = [elevations]
+        if az_step is None:
+            az_step = self.__config['radar']['3dB_beamwidth']
+        if azimuths is None or np.any(np.equal(azimuths, None)):
+            if az_start > az_stop:
+                azimuths = np.hstack((np.arange(az_start, 360., az_step), np.arange(0, az_stop + az_step, az_step)))
+            else:
+                azimuths = np.arange(az_start, az_stop + az_step, az_step)
+        azimuths = np.asarray(azimuths, dtype=float)
+        sweeps = [(azimuths, np.full(len(azimuths), float(e))) for e in elevations]
+        return self._scan_at('ppi', sweeps, times, elevations, azimuths)
+
+    def get_RHI_at(self, azimuths, times, elevations=None, elev_step=None, elev_start=0, elev_stop=90):
+        """get_RHI with the model at the time of every sweep or ray (see get_PPI_at)."""
+        if np.isscalar(azimuths):
+            azimuths = [azimuths]
+        if elevations is None or np.any(np.equal(elevations, None)):
+            if elev_step is None:
+                elev_step = self.__config['radar']['3dB_beamwidth']
+            elevations = np.arange(elev_start, elev_stop + elev_step, elev_step)
+        elevations = np.asarray(elevations, dtype=float)
+        sweeps = [(np.full(len(elevations), float(a)), elevations) for a in azimuths]
+        return self._scan_at('rhi', sweeps, times, elevations, azimuths)
 
     def _simulate_sweeps(self, sweeps):
         """[(az, el), ...] -> packaged sweeps.  The reference runs the sweeps of a scan one

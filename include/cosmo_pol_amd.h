@@ -251,6 +251,13 @@ typedef struct {
     const double *ml_filter;    /* [2 * ml_radius + 1] filter taps (scipy gaussian_filter) */
     int32_t ml_radius;
     int32_t pad_;
+    /* time blend (cpol_run_sweep_members only; all zero = off: a caller that zero-initialises the struct and knows nothing of
+       these fields gets the ensemble call).  Set in any other entry point that takes tables: CPOL_ERR_ARG.  They are per-ray
+       tables and live here, not in cpol_sweep_params, whose last member stays v_res. */
+    const int32_t *ray_state;   /* [n_rays] host: index INTO `members` of the earlier state                          */
+    const float   *ray_weight;  /* [n_rays] host: weight of the later state, 0 <= w < 1; 0 = the earlier state alone */
+    int32_t time_blend;         /* 1: ONE scan whose ray r reads members[ray_state[r]] blended with members[ray_state[r] + 1] */
+    int32_t pad_time_;
 } cpol_ray_tables_t;
 
 typedef struct {
@@ -581,7 +588,21 @@ CPOL_API int  cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const 
  * mask_sum8 likewise); lats, lons, dist and heights are [n_rays * n_gates], once; model_vars must be NULL (p->integrate_model is
  * ignored).  All three outputs_on_device modes; works on a lane; the context's selected member is not changed.
  * CPOL_ERR_ARG (the context stays usable): a member not staged or listed twice, model_vars requested, mask_sum8 with
- * 2 * n_sub > 127, more than 2^31 - 1 sub-beam gates in all.  Work memory: cpol_mem_info's per_gate x n_members per sub-beam gate. */
+ * 2 * n_sub > 127, more than 2^31 - 1 sub-beam gates in all.  Work memory: cpol_mem_info's per_gate x n_members per sub-beam gate.
+ *
+ * TIME BLEND (tables->time_blend = 1; replaces in the reference: nothing -- it reads one model state, at its own time).  ONE scan of
+ * p->n_rays rays whose ray r sees the model between two staged states: `members` lists the states the call may read (at most
+ * 64, in the order of the series; a state may be listed twice), tables->ray_state[r] is the index INTO `members` of the earlier
+ * state and tables->ray_weight[r] the float32 weight w of the later one, members[ray_state[r] + 1].  Every one of the eight
+ * neighbour values of a sub-beam gate is blended per staged variable in float32 -- w == 0: a, the later state is not read;
+ * otherwise a + w * (b - a), three operations in that order; -9999 where a or b is -9999 -- before the vertical
+ * interpolation (k_interp_timed: the geometry once per sub-beam gate, in cpol_run_sweep's forms), so every output carries the
+ * bits of cpol_run_sweep on a context staged with the cube blended that way on the host.  out: the shapes of cpol_run_sweep,
+ * [n_rays * n_gates]; model_vars and p->integrate_model are honoured.  Work memory: per_gate x 1.  The second half runs over
+ * n_rays rows under the rules above (no interpolating forms, no graph replay).  All three outputs_on_device modes; works on
+ * a lane; the selected member is not changed.  CPOL_ERR_ARG (the context stays usable, nothing is queued): ray_state or
+ * ray_weight NULL, a ray_state outside `members`, ray_state + 1 outside it with a weight != 0, a weight outside [0, 1) or not
+ * finite, CPOL_GEOM_SPACEBORNE or CPOL_GEOM_HOST_PATHS. */
 CPOL_API int  cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *tables,
                             const int32_t *members, int n_members, cpol_outputs *out);
 
