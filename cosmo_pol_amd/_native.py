@@ -565,6 +565,21 @@ class Context(object):
     def enable_debug(self, on=True):
         self.lib.cpol_debug_read(self.h, b'enable' if on else b'disable', None, 0)
 
+    def set_stencil_budget(self, nbytes):
+        """Bytes of device memory the gate stencils of this (root) context may hold; 0 turns them off.  Refused (ValueError) while
+        lanes of the context exist; lowering it below what is held drops every stencil.  (cpol_debug_read "stencil_budget".)"""
+        v = C.c_uint64(int(nbytes))
+        self._check(int(self.lib.cpol_debug_read(self.h, b'stencil_budget', C.byref(v), 8)), 'cpol_debug_read(stencil_budget)')
+
+    def stencil_state(self):
+        """{'form': of this context's last sweep (0 full, 1 recording, 2 replay), and of the root's store: 'entries', 'bytes',
+        'records', 'replays', 'drops'} (cpol_debug_read "stencil")."""
+        out = np.zeros(6, dtype=np.float64)
+        n = self.lib.cpol_debug_read(self.h, b'stencil', _ptr(out), out.nbytes)
+        if n != out.nbytes:
+            self._check(int(n) if n < 0 else ERR_ARG, 'cpol_debug_read(stencil)')
+        return dict(zip(('form', 'entries', 'bytes', 'records', 'replays', 'drops'), (int(x) for x in out)))
+
     def stage_model(self, arrays, zlevels, llc, urc, res, south_pole):
         arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
         zlevels = np.ascontiguousarray(zlevels, dtype=np.float32)

@@ -15,6 +15,7 @@
 // = 6 launches for a 1-moment sweep (10 before the ray-path, unit-list and final merges).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <mutex>
 #include <stdio.h>
 #include <time.h>
 #include <string.h>
@@ -57,6 +58,26 @@ struct ItabCacheEntry {
     ItabDev t{};
     double check = 0.0, check_at = 0.0, check_edge = 0.0;
     uint64_t used = 0;          // build serial of the last use (LRU; entries of the current build are pinned)
+};
+
+// ---- gate stencils (cpol_interp.inl: k_interp_record / k_interp_replay) ----
+// Everything interp_gate reads before gate_value, compared bytewise (zeroed before it is filled: no stray padding)
+struct StencilKey {
+    uint64_t version, heights;  // the caller's table version; the root's heights identity
+    long shape[6];              // of the table set
+    double range0, range_step, ke, re, alt, lon, sin_u1, cos_u1, poly_scale;
+    int mode, poly, exact, pad;
+};
+
+struct StencilEntry {
+    StencilKey key;
+    uint64_t id = 0;
+    int state = 0;              // 0 noted (seen once), 1 its recording launch is being queued, 2 recorded
+    bool refused = false;       // the record did not fit the budget or the device: the geometry keeps the full form
+    void *buf = nullptr;
+    size_t bytes = 0;
+    long n_pad = 0;             // gates, rounded up to 64
+    hipEvent_t ev = nullptr;    // behind the recording launch, on the recorder's stream
 };
 
 }  // namespace
@@ -182,6 +203,21 @@ struct cpol_ctx {
     int last_forms[12] = {0};          // the launch forms of the last sweep (cpol_debug_read "launch_forms"): [0] g1r, [1] k_gate1_ray, [2] single-beam gate kernel,
                                        // [3] k_interp_classify, [4] items off the tables listed directly, [5] k_subbeam_sum, [6] table items evaluated in place,
                                        // [7] coordinate polynomials for the one sub-beam, [8] n_sub, [9] lanes alive, [10] CPOL_SCAN_FORM (1: the range scans by a whole wavefront), [11] HIP graph replayed
+    // Gate stencils.  The store lives on the ROOT context (lanes die at every model load; they reach it through `parent`), its
+    // bookkeeping under st_mu.  No entry is freed while lanes exist or sweeps are in flight: entries die in cpol_destroy, when the
+    // heights identity changes (cpol_stage_model*, which refuse to run while lanes exist and drain the stream) and when the budget is
+    // lowered below what is held ("stencil_budget", refused while lanes exist).
+    std::mutex st_mu;
+    std::vector<StencilEntry *> st_entries;
+    size_t st_budget = (size_t)1 << 30, st_bytes = 0;
+    uint64_t st_heights = 1;           // heights identity: H, HT, nz / ny / nx, llc / urc / res, the rotation constants
+    uint64_t st_next_id = 1, st_records = 0, st_replays = 0, st_drops = 0;
+    double model_pole[2] = {0.0, 0.0};
+    DevBuf d_hdiff;                    // k_stage_heights_cmp's flag
+    // ... and per context (lane): the form of its last sweep (0 full, 1 recording, 2 replay), the entries whose recording launch its
+    // stream is known to run behind (one hipStreamWaitEvent per (lane, entry))
+    int last_stencil = 0;
+    std::vector<uint64_t> st_seen;
     int last_poly_central = 0;         // the last sweep's one sub-beam took the coordinate polynomials (cpol_debug_read "poly_central")
     int geo_poly_central = 1;          // CPOL_GEO_POLY_CENTRAL=0: a single-beam sweep keeps the long form of the geodesy for its (central) sub-beam even when
                                        // nobody asks for the float64 latitude / longitude; 2: the polynomials also with the debug reads enabled (tools/fast_sub_check.py)
@@ -709,6 +745,8 @@ int cpol_create(int device, cpol_ctx **out)
     return CPOL_OK;
 }
 
+static void stencil_drop_all(cpol_ctx *root);
+
 void cpol_destroy(cpol_ctx *ctx)
 {
     if (!ctx) return;
@@ -747,6 +785,8 @@ void cpol_destroy(cpol_ctx *ctx)
         if (sg.p) (void)hipHostFree(sg.p);
     }
     for (auto &ts : ctx->tsets) { free_buf(ts.buf); free_buf(ts.poly); }
+    if (!ctx->parent) stencil_drop_all(ctx);                         // (the gate stencils)
+    free_buf(ctx->d_hdiff);
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
@@ -853,6 +893,7 @@ const char *cpol_last_error(cpol_ctx *ctx) { return ctx ? ctx->err.c_str() : "nu
 int cpol_set_stream(cpol_ctx *ctx, void *hip_stream)
 {
     if (!ctx) return CPOL_ERR_ARG;
+    ctx->st_seen.clear();               // (gate stencils: another stream has waited for no recording launch yet)
     if (ctx->own_stream) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamDestroy(ctx->stream);
@@ -1017,6 +1058,114 @@ static bool model_on_lane(cpol_ctx *ctx, const char *who)
     return true;
 }
 
+// ---- gate stencils: the store of the root context ----
+// every entry dies (the caller holds no lanes and has drained -- or drains here -- the root's stream)
+static void stencil_drop_all(cpol_ctx *root)
+{
+    (void)hipStreamSynchronize(root->stream);
+    std::lock_guard<std::mutex> lk(root->st_mu);
+    for (StencilEntry *e : root->st_entries) {
+        if (e->buf) (void)hipFree(e->buf);
+        if (e->ev) (void)hipEventDestroy(e->ev);
+        delete e;
+    }
+    root->st_drops += root->st_entries.size();
+    root->st_entries.clear();
+    root->st_bytes = 0;
+    root->st_seen.clear();
+}
+
+// the level heights, the grid or the rotation are about to change: a new identity, no entry survives
+static void stencil_new_heights(cpol_ctx *root)
+{
+    stencil_drop_all(root);
+    root->st_heights++;
+}
+
+static void stencil_views(const StencilEntry *e, StencilDev *sd)
+{
+    char *b = (char *)e->buf;
+    const size_t n = (size_t)e->n_pad;
+    sd->z1 = (StencilZ *)b;                  b += 16 * n;
+    sd->z2 = (StencilZ *)b;                  b += 16 * n;
+    sd->cell = (int2 *)b;                    b += 8 * n;
+    sd->c1 = (StencilC1 *)b;                 b += 8 * n;
+    sd->s = (float *)b;                      b += 4 * n;
+    sd->h = (float *)b;                      b += 4 * n;
+    sd->e = (float *)b;                      b += 4 * n;
+    sd->x = (float *)b;                      b += 4 * n;
+    sd->y = (float *)b;                      b += 4 * n;
+    sd->status = (signed char *)b;
+}
+
+// The form of this sweep's gate kernel: 0 full (first sight of the key: noted; or no room), 1 recording (second sight; *made is the
+// entry, published by stencil_recorded once the launch and its event are queued), 2 replay (the stream waits for the recording
+// launch's event the first time this context meets the entry).
+static int stencil_pick(cpol_ctx *ctx, const StencilKey &key, long n_rg, StencilDev *sd, StencilEntry **made)
+{
+    cpol_ctx *r = ctx->parent ? ctx->parent : ctx;
+    std::lock_guard<std::mutex> lk(r->st_mu);
+    if (!r->st_budget) return 0;
+    StencilEntry *e = nullptr;
+    for (StencilEntry *x : r->st_entries)
+        if (memcmp(&x->key, &key, sizeof key) == 0) { e = x; break; }
+    if (!e) {
+        // first sight: a note (no device memory).  The notes of geometries that never came again do not pile up without bound
+        if (r->st_entries.size() >= 4096) {
+            for (size_t i = 0; i < r->st_entries.size(); ++i)
+                if (r->st_entries[i]->state == 0) { delete r->st_entries[i]; r->st_entries.erase(r->st_entries.begin() + (long)i); break; }
+            if (r->st_entries.size() >= 4096) return 0;
+        }
+        try {
+            e = new StencilEntry();
+            e->key = key;
+            e->id = r->st_next_id++;
+            r->st_entries.push_back(e);
+        } catch (...) { delete e; }
+        return 0;
+    }
+    if (e->refused || e->state == 1) return 0;
+    if (e->state == 0) {
+        const long n_pad = (n_rg + 63) & ~63L;
+        const size_t bytes = (size_t)n_pad * CPOL_STENCIL_BYTES_PER_GATE;
+        if (bytes > r->st_budget || r->st_bytes > r->st_budget - bytes) { e->refused = true; return 0; }
+        if (hipMalloc(&e->buf, bytes) != hipSuccess) { (void)hipGetLastError(); e->buf = nullptr; e->refused = true; return 0; }
+        if (hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(e->buf);
+            e->buf = nullptr; e->ev = nullptr; e->refused = true;
+            return 0;
+        }
+        e->bytes = bytes; e->n_pad = n_pad; e->state = 1;
+        r->st_bytes += bytes;
+        stencil_views(e, sd);
+        *made = e;
+        return 1;
+    }
+    stencil_views(e, sd);
+    bool seen = false;
+    for (uint64_t id : ctx->st_seen) seen = seen || id == e->id;
+    if (!seen) {
+        if (hipStreamWaitEvent(ctx->stream, e->ev, 0) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        try { ctx->st_seen.push_back(e->id); } catch (...) { }      // (not remembered: it waits again, harmlessly)
+    }
+    r->st_replays++;
+    return 2;
+}
+
+// behind the recording launch: its event, then the entry is there for every lane
+static int stencil_recorded(cpol_ctx *ctx, StencilEntry *e)
+{
+    cpol_ctx *r = ctx->parent ? ctx->parent : ctx;
+    const hipError_t rc = hipEventRecord(e->ev, ctx->stream);
+    std::lock_guard<std::mutex> lk(r->st_mu);
+    if (rc != hipSuccess) { (void)hipGetLastError(); e->refused = true; return 0; }      // (it keeps its memory until the store is dropped)
+    e->state = 2;
+    r->st_records++;
+    try { ctx->st_seen.push_back(e->id); } catch (...) { }
+    return 1;
+}
+
 // the context bookkeeping behind a freshly written d_H / d_V (cpol_stage_model, cpol_stage_model_packed)
 // the cubes of members >= 1 go with the cube they were staged beside (cpol_stage_model, cpol_stage_model_packed, cpol_destroy)
 static void drop_members(cpol_ctx *ctx)
@@ -1043,6 +1192,7 @@ static void model_staged_tail(cpol_ctx *ctx, int n_vars, int nz, int ny, int nx,
     const double ct = cos(theta), st = sin(theta), cp = cos(phi), sp = sin(phi);
     m.ctcp = ct * cp; m.ctsp = ct * sp; m.st = st; m.nsp = -sp; m.cp = cp;
     m.nstcp = -st * cp; m.stsp = st * sp; m.ct = ct;
+    ctx->model_pole[0] = south_pole[0]; ctx->model_pole[1] = south_pole[1];
     ctx->model_staged = true;
     ctx->stage_serial++;
     drop_members(ctx);                  // (a new member 0: the others belonged to the previous one)
@@ -1066,13 +1216,40 @@ int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const 
     const long ncell = (long)ny * nx;
     const size_t plane_bytes = (size_t)nz * ncell * sizeof(float);
     const size_t h_bytes = (plane_bytes + 7) & ~(size_t)7;        // + (top, lowest level) per column behind the levels
+    // Gate stencils outlive a model load whose heights identity is the resident one: the same grid and pole, bytewise, and level
+    // heights that are bit for bit what d_H holds -- compared exactly, by the staging kernel itself as it overwrites them.
+    void *const h_was = ctx->d_H.p;
+    bool keep_stencils;
+    {
+        const ModelDev &m0 = ctx->model;
+        const float grid_new[6] = {llc[0], llc[1], urc[0], urc[1], res[0], res[1]};
+        const float grid_old[6] = {m0.llc0, m0.llc1, m0.urc0, m0.urc1, m0.res0, m0.res1};
+        std::lock_guard<std::mutex> lk(ctx->st_mu);
+        keep_stencils = ctx->model_staged && !ctx->st_entries.empty() && m0.nz == nz && m0.ny == ny && m0.nx == nx &&
+                        memcmp(grid_new, grid_old, sizeof grid_new) == 0 && memcmp(south_pole, ctx->model_pole, 2 * sizeof(double)) == 0;
+    }
+    if (keep_stencils && ensure(ctx, ctx->d_hdiff, sizeof(int)) != CPOL_OK) keep_stencils = false;
+    if (!keep_stencils) stencil_new_heights(ctx);
+    // (from here on an early return leaves heights that may be half written: the store goes with them unless the end is reached)
+    struct DropUnlessKept {
+        cpol_ctx *c; bool armed;
+        ~DropUnlessKept() { if (armed) stencil_new_heights(c); }
+    } guard{ctx, keep_stencils};
     ENSURE(ctx->d_H, h_bytes + (size_t)ncell * sizeof(float2));
     ENSURE(ctx->d_V, plane_bytes * n_vars);
+    if (keep_stencils && ctx->d_H.p != h_was) { stencil_new_heights(ctx); guard.armed = keep_stencils = false; }
     DevBuf tmp;
     int rc = ensure(ctx, tmp, plane_bytes);
     if (rc != CPOL_OK) return rc;
     const int blk = 256, grd = cdiv(ncell, blk);
+    int h_differs = 0;
     HIPCHK(hipMemcpyAsync(tmp.p, zlevels, plane_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (keep_stencils) {
+        HIPCHK(hipMemsetAsync(ctx->d_hdiff.p, 0, sizeof(int), ctx->stream));
+        hipLaunchKernelGGL(k_stage_heights_cmp, dim3(grd), dim3(blk), 0, ctx->stream, (const float *)tmp.p,
+                           (float *)ctx->d_H.p, (float2 *)((char *)ctx->d_H.p + h_bytes), nz, ncell, (int *)ctx->d_hdiff.p);
+        HIPCHK(hipMemcpyAsync(&h_differs, ctx->d_hdiff.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));   // (read behind the loop's synchronisation)
+    } else
     hipLaunchKernelGGL(k_stage_heights, dim3(grd), dim3(blk), 0, ctx->stream, (const float *)tmp.p,
                        (float *)ctx->d_H.p, (float2 *)((char *)ctx->d_H.p + h_bytes), nz, ncell);
     for (int v = 0; v < n_vars; ++v) {
@@ -1084,6 +1261,7 @@ int cpol_stage_model(cpol_ctx *ctx, int n_vars, const float *const *data, const 
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipGetLastError());
     free_buf(tmp);
+    if (keep_stencils && h_differs == 0) guard.armed = false;      // (otherwise the guard drops the store: another identity)
     model_staged_tail(ctx, n_vars, nz, ny, nx, h_bytes, llc, urc, res, south_pole);
     return CPOL_OK;
 }
@@ -1319,6 +1497,7 @@ int cpol_stage_model_packed(cpol_ctx *ctx, const cpol_packed_model *m, const cpo
     (void)hipGetLastError();            // a stale error of another user of the runtime in this thread is not ours
     if (model_on_lane(ctx, "cpol_stage_model_packed")) return CPOL_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
+    stencil_new_heights(ctx);           // (the levels are derived on the device: no cheap comparison, a new heights identity)
     const double t_start = wall_ms();
     const size_t plane_bytes = (size_t)nz * ncell * sizeof(float);
     const size_t h_bytes = (plane_bytes + 7) & ~(size_t)7;        // + (top, lowest level) per column behind the levels
@@ -2386,9 +2565,33 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             hipLaunchKernelGGL(k_interp_timed, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma, tg);
         } else
         hipLaunchKernelGGL(k_interp_members, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma);
-    } else if (!fused && !fused_gate1 && !exp_skip_interp)
-    hipLaunchKernelGGL(k_interp_sweep, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st,
-                       ctx->model, ia);
+    } else if (!fused && !fused_gate1 && !exp_skip_interp) {
+        // A launch that is plain k_interp_sweep, of a single beam whose float32 grid coordinates alone are wanted, under a caller's
+        // version tag: the gate stencil of its (geometry, heights) pair -- noted at first sight, recorded at the second, replayed from
+        // the third on (cpol_interp.inl).  Everything else keeps k_interp_sweep.
+        int form = 0;
+        StencilDev sd{};
+        StencilEntry *made = nullptr;
+        if (n_sub == 1 && !sub_out && !ia.traj && !ia.lats && !ia.lons && !ia.coords && t->version != 0 && !ctx->use_graph &&
+            ctx->model.nz < 32768) {
+            StencilKey key;
+            memset(&key, 0, sizeof key);
+            key.version = t->version;
+            key.heights = (ctx->parent ? ctx->parent : ctx)->st_heights;
+            memcpy(key.shape, shape, sizeof shape);
+            key.range0 = p->range0; key.range_step = p->range_step; key.ke = p->ke; key.re = p->re; key.alt = p->radar_alt;
+            key.lon = p->radar_lon; key.sin_u1 = p->sin_u1; key.cos_u1 = p->cos_u1; key.poly_scale = ia.poly_scale;
+            key.mode = mode; key.poly = (ia.poly ? 1 : 0) + 2 * ia.poly_central; key.exact = ia.exact_sub;
+            form = stencil_pick(ctx, key, n_rg, &sd, &made);
+        }
+        const dim3 grid((unsigned)(n_rays * n_sub), cdiv(ng, 256));
+        if (form == 2) hipLaunchKernelGGL(k_interp_replay, grid, dim3(256), 0, st, ctx->model, ia, sd);
+        else if (form == 1) {
+            hipLaunchKernelGGL(k_interp_record, grid, dim3(256), 0, st, ctx->model, ia, sd);
+            stencil_recorded(ctx, made);
+        } else hipLaunchKernelGGL(k_interp_sweep, grid, dim3(256), 0, st, ctx->model, ia);
+        ctx->last_stencil = form;
+    }
     if (tm && !fused && !fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
     if (sub_out) {
         // ---- 2''. cpol_interp_subbeams: geometry of every sub-beam, 'ml' weights, melting, copies; no scattering ----
@@ -3077,6 +3280,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const int forms[12] = {g1r, (int)gate1_ray, (int)gate1, (int)fused, (int)rare_direct, (int)subsum, (int)final_inplace, (int)poly_single,
                            n_sub, ctx->parent ? ctx->parent->n_children : ctx->n_children, CPOL_SCAN_FORM, 0};
     memcpy(ctx->last_forms, forms, sizeof forms);
+    ctx->last_stencil = 0;
     const double t_buffers = now_ns();
     ctx->counters_dirty = true;         // until the sequence is queued completely (cleared where sweep_serial advances)
     // graph key: every value that ends up in a kernel argument
@@ -3475,6 +3679,34 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         if (!dst || max_bytes < (int64_t)sizeof(int)) return CPOL_ERR_ARG;
         memcpy(dst, &ctx->last_poly_central, sizeof(int));
         return (int64_t)sizeof(int);
+    }
+    if (!strcmp(name, "stencil")) {
+        // gate stencils: [the form of this context's last sweep (0 full, 1 recording, 2 replay), entries of the root's store, bytes it
+        // holds, records made, replays, entries dropped]
+        cpol_ctx *own = ctx->parent ? ctx->parent : ctx;
+        std::lock_guard<std::mutex> lk(own->st_mu);
+        const double v[6] = {(double)ctx->last_stencil, (double)own->st_entries.size(), (double)own->st_bytes, (double)own->st_records,
+                             (double)own->st_replays, (double)own->st_drops};
+        if (!dst || max_bytes < (int64_t)sizeof v) return CPOL_ERR_ARG;
+        memcpy(dst, v, sizeof v);
+        return (int64_t)sizeof v;
+    }
+    if (!strcmp(name, "stencil_budget")) {
+        // a CONTROL name like "enable": *dst = uint64 bytes the root's store may hold (0: stencils off; default 1 GiB).  Refused while
+        // lanes exist; lowering it below what the store holds drops every entry (the root's stream is drained first)
+        if (!dst || max_bytes < (int64_t)sizeof(uint64_t)) { ctx->err = "cpol_debug_read(stencil_budget): dst = uint64 bytes"; return CPOL_ERR_ARG; }
+        if (model_on_lane(ctx, "cpol_debug_read(stencil_budget)")) return CPOL_ERR_ARG;
+        uint64_t bytes;
+        memcpy(&bytes, dst, sizeof bytes);
+        bool drop;
+        {
+            std::lock_guard<std::mutex> lk(ctx->st_mu);
+            drop = (size_t)bytes < ctx->st_bytes || bytes == 0;
+            ctx->st_budget = (size_t)bytes;
+            for (StencilEntry *e : ctx->st_entries) if (!e->buf) e->refused = false;
+        }
+        if (drop) { HIPCHK(hipSetDevice(ctx->device)); stencil_drop_all(ctx); }
+        return 0;
     }
     if (!strcmp(name, "launch_forms")) {
         if (!dst || max_bytes < (int64_t)sizeof ctx->last_forms) return CPOL_ERR_ARG;

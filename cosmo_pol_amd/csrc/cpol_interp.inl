@@ -23,6 +23,26 @@ __global__ void k_stage_heights(const float *__restrict__ src, float *__restrict
     top_low[cell] = make_float2(src[cell], src[(long)(nz - 1) * ncell + cell]);
 }
 
+// ... the same, and whether any level or (top, lowest) pair it writes differs in its bits from what was there (gate stencils:
+// cpol_stage_model keeps the records of the resident heights only if every bit stayed): *differs |= 1
+__global__ void k_stage_heights_cmp(const float *__restrict__ src, float *__restrict__ dst,
+                                    float2 *__restrict__ top_low, int nz, long ncell, int *__restrict__ differs)
+{
+    long cell = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (cell >= ncell) return;
+    bool diff = false;
+    for (int k = 0; k < nz; ++k) {
+        const float v = src[(long)k * ncell + cell];
+        diff = diff || __float_as_uint(dst[cell * nz + k]) != __float_as_uint(v);
+        dst[cell * nz + k] = v;
+    }
+    const float2 tl = make_float2(src[cell], src[(long)(nz - 1) * ncell + cell]);
+    const float2 was = top_low[cell];
+    diff = diff || __float_as_uint(was.x) != __float_as_uint(tl.x) || __float_as_uint(was.y) != __float_as_uint(tl.y);
+    top_low[cell] = tl;
+    if (diff) atomicOr(differs, 1);
+}
+
 // [nz][ny][nx] of variable v -> V[cell][nz][n_vars]
 __global__ void k_stage_variable(const float *__restrict__ src, float *__restrict__ dst,
                                  int nz, long ncell, int n_vars, int v)
@@ -344,8 +364,28 @@ struct GateGeom {
     double rz[4];          // 1 / (z1 - z2) for div32_by (CPOL_DIV_AS_PRODUCT)
 };
 
+// the four neighbour columns of grid cell (i0, i1); shared by gate_geometry and the stencil replay (stencil_load), which keeps (i0, i1)
+__device__ __forceinline__ void gate_cells(const ModelDev &m, int i0, int i1, GateGeom &g)
+{
+    int i0a = min(max(i0, 0), m.ny - 1), i0b = min(max(i0 + 1, 0), m.ny - 1);
+    int i1a = min(max(i1, 0), m.nx - 1), i1b = min(max(i1 + 1, 0), m.nx - 1);
+    g.cell[0] = (long)i0a * m.nx + i1a;
+    g.cell[1] = (long)i0a * m.nx + i1b;
+    g.cell[2] = (long)i0b * m.nx + i1a;
+    g.cell[3] = (long)i0b * m.nx + i1b;
+}
+
+// the reciprocals of the four column thicknesses (div32_by); shared likewise
+__device__ __forceinline__ void gate_rz(GateGeom &g)
+{
+#if CPOL_DIV_AS_PRODUCT
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g.rz[k] = rcp_for_div32(g.z1[k] - g.z2[k]);
+#endif
+}
+
 __device__ __forceinline__ void gate_geometry(const ModelDev &m, float rlat, float rlon, float h,
-                                              GateGeom &g ITRACE_ARG)
+                                              GateGeom &g ITRACE_ARG, int *i01 = nullptr)
 {
     // interpolation_c.c:43-57
 #if CPOL_DIV_AS_PRODUCT
@@ -357,6 +397,7 @@ __device__ __forceinline__ void gate_geometry(const ModelDev &m, float rlat, flo
 #endif
     int i0 = (int)floor((double)p0);
     int i1 = (int)floor((double)p1);
+    if (i01) { i01[0] = i0; i01[1] = i1; }                 // (the recording form alone asks: a null constant elsewhere)
     // fmodf(p, 1.0f) = p - trunc(p) with the sign of p: exact (the difference of a float and its integer part
     // is representable), so the same bits as the C library's loop (OCML: ~25 instructions each, these: 3)
     g.x = copysignf(p0 - truncf(p0), p0);
@@ -365,12 +406,7 @@ __device__ __forceinline__ void gate_geometry(const ModelDev &m, float rlat, flo
     g.dy = 1.0f - g.y;
     // the reference does not range-check; callers pass the domain check first.
     // Clamp so that a gate exactly on the upper domain edge cannot fault.
-    int i0a = min(max(i0, 0), m.ny - 1), i0b = min(max(i0 + 1, 0), m.ny - 1);
-    int i1a = min(max(i1, 0), m.nx - 1), i1b = min(max(i1 + 1, 0), m.nx - 1);
-    g.cell[0] = (long)i0a * m.nx + i1a;
-    g.cell[1] = (long)i0a * m.nx + i1b;
-    g.cell[2] = (long)i0b * m.nx + i1a;
-    g.cell[3] = (long)i0b * m.nx + i1b;
+    gate_cells(m, i0, i1, g);
     const int nz = m.nz;
     float t[4], top[4];
 #pragma unroll
@@ -480,10 +516,7 @@ __device__ __forceinline__ void gate_geometry(const ModelDev &m, float rlat, flo
             g.z2[k] = col[k][g.c1[k] + 1];
         }
     }
-#if CPOL_DIV_AS_PRODUCT
-#pragma unroll
-    for (int k = 0; k < 4; ++k) g.rz[k] = rcp_for_div32(g.z1[k] - g.z2[k]);
-#endif
+    gate_rz(g);
 }
 
 __device__ __forceinline__ float gate_value(const ModelDev &m, const GateGeom &g, float h, int v)
@@ -675,6 +708,62 @@ __device__ __forceinline__ double asin_small(double x)
     return x * p;
 }
 
+// ---- gate stencils (round 8): what a gate knows before it touches m.V, kept per (scan geometry, model heights) ----
+// A single-beam sweep of a geometry that comes again (an operational volume scan over the time-invariant level heights) spends
+// 7 of a wavefront's 13 us on work whose inputs did not change: the ray path, the grid coordinates, the topography and the level
+// search.  The RECORDING form of the gate kernel (k_interp_record) is the full form and also writes, per gate, the ray path
+// (s, h, e as float32), the gate's geometric class and -- inside the model -- the grid cell (i0, i1), the position in it (x, y), the
+// upper bracketing level of the four columns and their bracketing heights.  The REPLAY form (k_interp_replay) reads them back and
+// goes on from gate_value4 / gate_value with the full form's own statements: dx, dy, the four column indices (gate_cells) and the
+// reciprocals (gate_rz) are recomputed by the same functions from the same float32 / int operands, everything else is the stored
+// bit pattern itself -- every store of the replay has the full form's bits by construction.  The mask born from the VALUES
+// (-9999 / NaN of variable 0) is not in the record: it is made by the shared tail, sweep by sweep.
+// SoA over the n_rays * n_gates gates, 69 bytes per gate: a wavefront reads ten coalesced rows.
+struct __attribute__((aligned(8))) StencilC1 { short v[4]; };
+struct __attribute__((aligned(16))) StencilZ { float v[4]; };
+struct StencilDev {
+    StencilZ *z1, *z2;          // [n] bracketing heights of the four columns
+    int2 *cell;                 // [n] (i0, i1) before the clamp of gate_cells
+    StencilC1 *c1;              // [n] upper level of the bracketing pair, four columns (nz < 32768)
+    float *s, *h, *e;           // [n] ray_path's arc distance, height, elevation [deg, before folding]
+    float *x, *y;               // [n] fractional position in the cell
+    signed char *status;        // [n] 3 no gate here, 2 outside the domain, +1 / -1 above the model top / below topography, 0 inside
+};
+#define CPOL_STENCIL_BYTES_PER_GATE 69
+
+__device__ __forceinline__ void stencil_store(const StencilDev &sd, long i, const int i01[2], const GateGeom &g)
+{
+    sd.status[i] = (signed char)g.status;
+    if (g.status != 0) return;
+    sd.cell[i] = make_int2(i01[0], i01[1]);
+    sd.x[i] = g.x;
+    sd.y[i] = g.y;
+    StencilC1 c;
+    StencilZ z1, z2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { c.v[k] = (short)g.c1[k]; z1.v[k] = g.z1[k]; z2.v[k] = g.z2[k]; }
+    sd.c1[i] = c;
+    sd.z1[i] = z1;
+    sd.z2[i] = z2;
+}
+
+__device__ __forceinline__ void stencil_load(const ModelDev &m, const StencilDev &sd, long i, int status, GateGeom &g)
+{
+    g.status = status;
+    if (status != 0) return;
+    const int2 c01 = sd.cell[i];
+    const StencilC1 c = sd.c1[i];
+    const StencilZ z1 = sd.z1[i], z2 = sd.z2[i];
+    g.x = sd.x[i];
+    g.y = sd.y[i];
+    g.dx = 1.0f - g.x;
+    g.dy = 1.0f - g.y;
+    gate_cells(m, c01.x, c01.y, g);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { g.c1[k] = c.v[k]; g.z1[k] = z1.v[k]; g.z2[k] = z2.v[k]; }
+    gate_rz(g);
+}
+
 // One sub-beam gate: ray path, geodesic, rotated-pole coordinates, level search, the variables.  Returns the
 // gate's status (0: inside the model, values valid; 1 / -1 / 2: above / below / outside, values NaN; 3: no such
 // gate in this launch) and its index.  KEEP = false: every variable goes to a.vals[] (k_interp_sweep).
@@ -694,9 +783,12 @@ struct ExportArgs {
 
 // TIMED (k_interp_timed, a time-blended sweep; with MEMBERS): the rows are those of ONE sweep, and the values of a ray come from the two
 // states of mb that bracket its time, blended by its weight (tm; cpol_members.inl).
-template <bool KEEP, bool EXPORT = false, bool MEMBERS = false, bool TIMED = false>
+// STENCIL (single-beam sweeps, n_sub = 1, no a.traj / a.coords / a.lats / a.lons): 1 = the full form, which also writes the gate's
+// record to sd (k_interp_record); 2 = everything up to and including gate_geometry comes from sd (k_interp_replay).
+template <bool KEEP, bool EXPORT = false, bool MEMBERS = false, bool TIMED = false, int STENCIL = 0>
 __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &a, float *sv, long &sbg_out, float &elev_out,
-                                           const ExportArgs *x = nullptr, const MemberArgs *mb = nullptr, const TimedArgs *tm = nullptr)
+                                           const ExportArgs *x = nullptr, const MemberArgs *mb = nullptr, const TimedArgs *tm = nullptr,
+                                           const StencilDev *sd = nullptr)
 {
     // ---- which (ray, sub-beam, block of gates) this workgroup takes ----
     // The hardware deals workgroups to the 8 XCDs round robin by their linear index, and every XCD has its own L2.  With
@@ -736,14 +828,22 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     elev_out = 0.0f;
 
     float s32, h32, e32;
+    int st_class = 0;                       // (STENCIL == 2: the recorded class of the gate)
+    if constexpr (STENCIL == 2) {
+        st_class = sd->status[sbg];
+        s32 = sd->s[sbg]; h32 = sd->h[sbg]; e32 = sd->e[sbg];
+    } else {
     if (a.traj) {
         const float *tr = a.traj + ((long)(ray * a.n_v + jv) * 3) * a.n_gates;
         s32 = tr[gate]; h32 = tr[a.n_gates + gate]; e32 = tr[2 * a.n_gates + gate];
     } else {
         ray_path(a.rp, ray, ray * a.n_v + jv, gate, s32, h32, e32);
     }
+    }
+    if constexpr (STENCIL == 1) { sd->s[sbg] = s32; sd->h[sbg] = h32; sd->e[sbg] = e32; }
     const float qnan = __builtin_nanf("");
     if (!(s32 == s32) || !(h32 == h32)) {
+        if constexpr (STENCIL == 1) sd->status[sbg] = 3;
         // no gate here (ray shorter than the batch: spaceborne / host paths): counts
         // as "above the model", produces no item
         if constexpr (MEMBERS) {
@@ -770,6 +870,9 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     }
     float rlon, rlat;
     double lat_deg = 0.0, lon_deg = 0.0;
+    if constexpr (STENCIL == 2) {
+        rlon = rlat = 0.0f;                 // (nobody reads them: a replayed launch has no a.coords)
+    } else {
     // (wave-uniform: a wavefront walks ONE sub-beam; exact_sub is a kernel argument)
     const bool use_poly = a.poly && (sub != a.central_sub || a.poly_central) && !a.exact_sub;
     const bool short_form = sub != a.central_sub && !a.exact_sub && !a.poly;      // (the closed short form of round 4: CPOL_GEO_POLY=0)
@@ -941,9 +1044,11 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
     if (poly_ok) { rlat = rlat_p; rlon = rlon_p; }     // (want_latlon: the long form ran for lat_deg / lon_deg alone)
 
     // interpolation.py:572-575 (IndexError in the reference)
-    if (rlon < m.llc0 || rlat < m.llc1 || rlon > m.urc0 || rlat > m.urc1 ||
-        !(rlon == rlon) || !(rlat == rlat)) {
-        atomicOr(a.error_flag, 1);          // sticky until reported (cpol_synchronize / cpol_counters)
+    }
+    if (STENCIL == 2 ? st_class == 2 : (rlon < m.llc0 || rlat < m.llc1 || rlon > m.urc0 || rlat > m.urc1 ||
+        !(rlon == rlon) || !(rlat == rlat))) {
+        if constexpr (STENCIL == 1) sd->status[sbg] = 2;
+        atomicOr(a.error_flag, 1);          // sticky until reported (cpol_synchronize / cpol_counters); a replayed sweep raises it as well
         if constexpr (MEMBERS) {
             members_fill(m, a, TIMED ? 1 : mb->n_members, mb->n_sbg1, sbg, 2, e32, rlat, rlon);
         } else {
@@ -970,6 +1075,13 @@ __device__ __forceinline__ int interp_gate(const ModelDev &m, const InterpArgs &
 
     GateGeom g;
     ITRACE(itr, 1);                                        // trajectory + grid coordinates
+    if constexpr (STENCIL == 2) {
+        stencil_load(m, *sd, sbg, st_class, g);
+    } else if constexpr (STENCIL == 1) {
+        int i01[2];
+        gate_geometry(m, rlat, rlon, h32, g ITRACE_PASS, i01);
+        stencil_store(*sd, sbg, i01, g);
+    } else
     gate_geometry(m, rlat, rlon, h32, g ITRACE_PASS);
     if constexpr (MEMBERS) {
         if constexpr (TIMED)                // (the ray's bracket: wave-uniform, scalar loads)
@@ -1085,6 +1197,23 @@ __global__ __launch_bounds__(256) CPOL_INTERP_ATTR void k_interp_sweep(ModelDev 
     long sbg;
     float e;
     interp_gate<false>(m, a, nullptr, sbg, e);
+}
+
+// The recording and the replay form of a single-beam sweep's gate kernel (gate stencils, above): grid and duties are k_interp_sweep's
+__global__ __launch_bounds__(256) void k_interp_record(ModelDev m, InterpArgs a, StencilDev sd)
+{
+    clear_counters(a.zero_buf, a.zero_n, a.zero_buf2, a.zero_n2);
+    long sbg;
+    float e;
+    interp_gate<false, false, false, false, 1>(m, a, nullptr, sbg, e, nullptr, nullptr, nullptr, &sd);
+}
+
+__global__ __launch_bounds__(256) void k_interp_replay(ModelDev m, InterpArgs a, StencilDev sd)
+{
+    clear_counters(a.zero_buf, a.zero_n, a.zero_buf2, a.zero_n2);
+    long sbg;
+    float e;
+    interp_gate<false, false, false, false, 2>(m, a, nullptr, sbg, e, nullptr, nullptr, nullptr, &sd);
 }
 
 // The geometry of every sub-beam gate (cpol_interp_subbeams): the gate kernel in its long form (a.exact_sub), values into a

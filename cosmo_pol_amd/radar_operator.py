@@ -251,7 +251,7 @@ class RadarOperator(object):
 
     def __init__(self, options_file=None, output_variables='all', *, device=0, lut_dir=None,
                  luts=None, config=None, distributed=False, gather_to=None, lanes=2, backend='hip',
-                 pyart_output=False):
+                 pyart_output=False, stencil_budget=None):
         if backend != 'hip':
             # by design: the product path is the HIP library or nothing (no CPU fallback)
             raise N.NativeError("backend %r: only 'hip' exists; the CPU restatement lives under "
@@ -259,6 +259,11 @@ class RadarOperator(object):
                                 % (backend,))
         print('Reading options defined in options file')
         self._ctx = N.Context(device)         # raises if the HIP library / GPU is missing
+        if stencil_budget is not None:
+            # bytes of device memory for gate stencils -- what a single-beam sweep knows of its gates before it reads the model's
+            # values, kept per (scan geometry, level heights) from the second time a geometry is seen (69 B per gate); 0: off,
+            # None: the library's default (1 GiB)
+            self._ctx.set_stencil_budget(stencil_budget)
         self._affinity_before = None
         if distributed:
             # one process per GPU: run this rank's threads next to its GPU (CPOL_NUMA_BIND=0: leave the
@@ -821,6 +826,11 @@ class RadarOperator(object):
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
                               paths=paths, lane=lane, pinned=pinned)
+
+    def stencil_state(self, lane=0):
+        """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
+        store's 'entries', 'bytes', 'records', 'replays', 'drops'."""
+        return self._lane(lane).stencil_state()
 
     def wait(self, lane=0):
         """Waits for the sweeps queued on `lane` (pinned / device outputs); raises IndexError

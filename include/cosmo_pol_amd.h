@@ -327,7 +327,9 @@ CPOL_API int  cpol_device_pci_bus_id(int device, char *buf, int len);
  * the work-buffer bytes ONE sub-beam gate of a launch sequence needs with the hydrometeors staged
  * now (`per_gate`: about 1.2 KB with six species): what a caller that packs many sweeps into one
  * cpol_run_sweep call sizes its batches by (the reference processes one radial at a time,
- * radar_operator.py:431) */
+ * radar_operator.py:431).  Not counted in `per_gate`: the gate stencil store of the root context -- 69 bytes per gate of
+ * every single-beam scan geometry seen twice, up to its budget (1 GiB unless cpol_debug_read "stencil_budget" says otherwise);
+ * cpol_debug_read "stencil" reports the bytes it holds, and `free_bytes` sees them as used memory */
 CPOL_API int  cpol_mem_info(cpol_ctx *ctx, size_t *free_bytes, size_t *total_bytes, size_t *per_gate);
 /* the HIP stream (hipStream_t) the context launches on: to order foreign work (copies,
  * collectives) against a sweep with events */
@@ -634,7 +636,15 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * "itab_detail<slot>" (see cosmo_pol_amd/_native.py); the staged model as it lies in device memory: "model_v" float32
  * [ny][nx][nz][n_vars], "model_h" float32 [ny][nx][nz], "model_ht" float32 [ny][nx][2] (model top, lowest level);
  * "ingest_times" float64 [4]: milliseconds of the last packed staging (octets to the device, k_grib_unpack,
- * k_model_derive, the whole call).  Returns bytes copied or < 0. */
+ * k_model_derive, the whole call).
+ * Gate stencils (single-beam sweeps under a caller's table version: from the third sweep of a geometry over unchanged level
+ * heights the gate kernel replays its ray paths, grid cells and bracketing levels from a per-gate record instead of
+ * computing them; bit-identical outputs): "stencil" float64 [6] -- the form of this context's last sweep (0 full, 1 recording,
+ * 2 replay), then of the root context's store: entries, bytes held, records made, replays, entries dropped.
+ * "stencil_budget" is a CONTROL name like "enable": dst points to a uint64, the bytes the store may hold (0: stencils off;
+ * default 1 GiB).  Root context only and refused (CPOL_ERR_ARG) while lanes of it exist; lowering it below what is held drops
+ * every entry.  Returns 0.
+ * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
 /* test hook: evaluates one of the device math helpers of the melting-species kernel on
