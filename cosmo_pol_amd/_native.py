@@ -93,8 +93,19 @@ OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H'
                  'DSPECTRUM', 'mask_sum8']
 
 
+SUPEROB_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL']    # the rows of `count`
+
+
+class Superob(C.Structure):
+    """cpol_superob: window averages of the per-gate fields (cosmo_pol_amd/superob.py states the rule)."""
+    _fields_ = ([('ray_window', C.c_int32), ('gate_window', C.c_int32), ('rays_per_block', C.c_int32), ('pad_', C.c_int32),
+                 ('min_valid_fraction', C.c_double)]
+                + [(n, C.c_void_p) for n in SUPEROB_FIELDS] + [('count', C.c_void_p)])
+
+
 class Outputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS]
+    # superob: NULL = off; stays the last member (cpol_outputs)
+    _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS] + [('superob', C.POINTER(Superob))]
 
 
 class SubbeamOutputs(C.Structure):
@@ -789,6 +800,47 @@ class Context(object):
         self._check(self.lib.cpol_debug_scan(self.h, int(form), int(bool(mul)), _ptr(x), _ptr(y), x.shape[0], x.shape[1]),
                     'cpol_debug_scan')
         return y
+
+    def superob_fields(self, fields, spec, rays_per_block=0, want=None):
+        """Test hook (cpol_debug_read "superob_fields"): k_superob on caller-supplied per-gate arrays {name: [n_rows, n_gates]}
+        of SUPEROB_FIELDS (float32; RVEL float64; ZDR is made from ZH and ZV) -> what superob.average returns for them: the
+        kernel on inputs no sweep produces.  `spec`: a superob.Superob.  `want`: the fields to ask the library for (default:
+        those whose inputs are given)."""
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('inp', C.c_void_p * len(SUPEROB_FIELDS)), ('so', Superob)]
+        h = Hook()
+        keep, shape = [], None
+        for i, k in enumerate(SUPEROB_FIELDS):
+            if k == 'ZDR' or k not in fields:
+                continue
+            a = np.ascontiguousarray(fields[k], dtype=np.float64 if k == 'RVEL' else np.float32)
+            if a.ndim != 2 or (shape is not None and a.shape != shape):
+                raise ValueError('superob_fields: every field is [n_rows, n_gates]')
+            shape = a.shape
+            keep.append(a)
+            h.inp[i] = a.ctypes.data
+        if shape is None:
+            raise ValueError('superob_fields: no field given')
+        h.n_rows, h.n_gates = shape
+        h.so.ray_window, h.so.gate_window, h.so.rays_per_block = spec.rays, spec.gates, int(rays_per_block)
+        h.so.min_valid_fraction = spec.min_valid_fraction
+        rpb = int(rays_per_block) or shape[0]
+        if rpb < 1 or shape[0] % rpb:
+            raise ValueError('superob_fields: rays_per_block %r does not divide %d rows' % (rays_per_block, shape[0]))
+        wshape = ((shape[0] // rpb) * (-(-rpb // spec.rays)), -(-shape[1] // spec.gates))
+        asked = [k for k in SUPEROB_FIELDS if (k in fields if k != 'ZDR' else ('ZH' in fields and 'ZV' in fields))]
+        if want is not None:
+            asked = [k for k in SUPEROB_FIELDS if k in want]
+        out = {k: np.empty(wshape, dtype=np.float64 if k == 'RVEL' else np.float32) for k in asked}
+        cnt = np.zeros((len(SUPEROB_FIELDS),) + wshape, dtype=np.uint16)
+        for k, a in out.items():
+            setattr(h.so, k, a.ctypes.data)
+        h.so.count = cnt.ctypes.data
+        rc = int(self.lib.cpol_debug_read(self.h, b'superob_fields', C.byref(h), C.sizeof(h)))
+        self._check(rc, 'cpol_debug_read(superob_fields)')
+        del keep
+        out['count'] = {k: cnt[SUPEROB_FIELDS.index(k)] for k in asked}
+        return out
 
     FORM_NAMES = ('g1r', 'gate1_ray', 'gate1', 'interp_classify', 'rare_direct', 'subbeam_sum', 'final_inplace',
                   'poly_central', 'n_sub', 'lanes_alive', 'scan_form', 'graph_replayed')

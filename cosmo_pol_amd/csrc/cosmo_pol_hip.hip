@@ -32,6 +32,7 @@
 #include "cpol_gate.inl"
 #include "cpol_spectrum.inl"
 #include "cpol_ingest.inl"
+#include "cpol_superob.inl"
 
 namespace {
 
@@ -162,7 +163,7 @@ struct cpol_ctx {
     struct Staging { void *p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } stg[4];
     int stg_next = 0;
     DevBuf b_traj, b_wgate, b_clk, b_rayc, b_poly, d_geoM;
-    DevBuf b_beam, b_spectrum, b_outwin;
+    DevBuf b_beam, b_spectrum, b_outwin, b_superob;
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
@@ -790,7 +791,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -1893,6 +1894,126 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
     return CPOL_OK;
 }
 
+// ---- superobservations (cpol_superob, cpol_superob.inl): the checks and the launch, shared by the launch sequence and the test hook ----
+enum { SO_RVEL = CPOL_SUPEROB_RVEL, SO_COUNT = CPOL_SUPEROB_FIELDS, SO_N };
+struct SuperobPlan {
+    long cells;
+    int rpb, wr, wc;
+    void *user[SO_N];           // the caller's pointers: ten fields, then count
+    size_t bytes[SO_N];
+};
+
+// every refusal of a cpol_superob for a call of n_rows rows (rays_default: what rays_per_block = 0 means); queues nothing
+static int superob_plan(cpol_ctx *ctx, const cpol_superob *so, int n_rows, int rays_default, int ng, bool doppler, SuperobPlan *pl)
+{
+    auto bad = [&](const char *why) { ctx->err = std::string("cpol_superob: ") + why; return CPOL_ERR_ARG; };
+    if (so->ray_window < 1 || so->gate_window < 1) return bad("ray_window and gate_window must be >= 1");
+    if ((long)so->ray_window * so->gate_window > 65535) return bad("ray_window * gate_window must be <= 65535 (count is uint16)");
+    if (!(so->min_valid_fraction > 0.0 && so->min_valid_fraction <= 1.0)) return bad("min_valid_fraction must lie in (0, 1]");
+    pl->rpb = so->rays_per_block ? so->rays_per_block : rays_default;
+    if (so->rays_per_block < 0 || n_rows % pl->rpb != 0) return bad("rays_per_block must be >= 0 and divide the rows of the call");
+    void *const f[SO_N] = {so->ZH, so->ZV, so->ZDR, so->KDP, so->DELTA_HV, so->PHIDP, so->RHOHV, so->ATT_H, so->ATT_V, so->RVEL,
+                           so->count};
+    pl->wr = cdiv(pl->rpb, so->ray_window);
+    pl->wc = cdiv(ng, so->gate_window);
+    pl->cells = (long)(n_rows / pl->rpb) * pl->wr * pl->wc;
+    bool any = false;
+    for (int k = 0; k < SO_N; ++k) {
+        pl->user[k] = f[k];
+        pl->bytes[k] = (size_t)pl->cells * (k == SO_RVEL ? sizeof(double) : k == SO_COUNT ? CPOL_SUPEROB_FIELDS * sizeof(uint16_t) : sizeof(float));
+        any = any || (f[k] && k != SO_COUNT);
+    }
+    if (!any) return bad("no output pointer set");
+    if (so->RVEL && !doppler) return bad("RVEL needs simulate_doppler");
+    return CPOL_OK;
+}
+
+// in: the per-gate device arrays in the order of `count`'s rows (slot ZDR unused, slot RVEL float64); T: where the kernel writes
+static int superob_launch(cpol_ctx *ctx, const cpol_superob *so, const SuperobPlan &pl, const void *const in[CPOL_SUPEROB_FIELDS],
+                          void *const T[SO_N], int ng, bool zero_rest, hipStream_t st)
+{
+    SuperobArgs sa{};
+    for (int k = 0; k < CPOL_SUPEROB_FIELDS; ++k) {
+        sa.in[k] = (k == SO_RVEL || k == CPOL_SUPEROB_ZDR) ? nullptr : (const float *)in[k];
+        sa.out[k] = k == SO_RVEL ? nullptr : (float *)T[k];
+        if (T[k]) sa.field[sa.n_fields++] = k;
+    }
+    sa.in_rvel = (const double *)in[SO_RVEL];
+    sa.out_rvel = (double *)T[SO_RVEL];
+    sa.count = (unsigned short *)T[SO_COUNT];
+    sa.n_cells = pl.cells;
+    sa.min_valid_fraction = so->min_valid_fraction;
+    sa.n_gates = ng; sa.R = so->ray_window; sa.G = so->gate_window;
+    sa.rays_per_block = pl.rpb; sa.win_rows = pl.wr; sa.win_cols = pl.wc;
+    sa.zero_rest = zero_rest;
+    hipLaunchKernelGGL(k_superob, dim3(cdiv(pl.cells, 256), sa.n_fields), dim3(256), 0, st, sa);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
+}
+
+// host-side copies of what k_superob wrote into a device block (count: only the rows of requested fields are the caller's to be written)
+static int superob_copy_out(cpol_ctx *ctx, const SuperobPlan &pl, void *const T[SO_N])
+{
+    int rc;
+    for (int k = 0; k < SO_COUNT; ++k)
+        if (pl.user[k] && (rc = copy_out(ctx, pl.user[k], T[k], pl.bytes[k], false))) return rc;
+    const size_t row = (size_t)pl.cells * sizeof(uint16_t);
+    for (int k = 0; k < SO_COUNT && pl.user[SO_COUNT]; ++k)
+        if (pl.user[k] && (rc = copy_out(ctx, (char *)pl.user[SO_COUNT] + k * row, (char *)T[SO_COUNT] + k * row, row, false))) return rc;
+    return CPOL_OK;
+}
+
+// where k_superob writes when the outputs are host memory and no window image holds them: the context's own block
+static int superob_own_block(cpol_ctx *ctx, const SuperobPlan &pl, void *T[SO_N])
+{
+    size_t total = 0, off = 0;
+    for (int k = 0; k < SO_N; ++k) if (pl.user[k]) total += (pl.bytes[k] + 255) & ~(size_t)255;
+    ENSURE(ctx->b_superob, total);
+    for (int k = 0; k < SO_N; ++k) {
+        T[k] = nullptr;
+        if (!pl.user[k]) continue;
+        T[k] = (char *)ctx->b_superob.p + off;
+        off += (pl.bytes[k] + 255) & ~(size_t)255;
+    }
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "superob_fields": k_superob on caller-supplied per-gate arrays (host memory in, host memory out,
+// blocking) -- the kernel on inputs no sweep produces (ZV missing where ZH is not, infinities, signed zeros, the largest window).
+struct SuperobHook {
+    int32_t n_rows, n_gates;
+    const void *in[CPOL_SUPEROB_FIELDS];    // [n_rows * n_gates] float32 (slot ZDR unused; slot RVEL float64); NULL = not given
+    cpol_superob so;                        // rays_per_block = 0: n_rows; a requested field needs its input (ZDR: ZH and ZV)
+};
+
+static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
+{
+    if (h->n_rows < 1 || h->n_gates < 1 || (long)h->n_rows * h->n_gates >= (1L << 31)) { ctx->err = "superob_fields: bad shape"; return CPOL_ERR_ARG; }
+    SuperobPlan pl{};
+    int rc = superob_plan(ctx, &h->so, h->n_rows, h->n_rows, h->n_gates, true, &pl);
+    if (rc != CPOL_OK) return rc;
+    for (int k = 0; k < CPOL_SUPEROB_FIELDS; ++k) {
+        const bool need = k == CPOL_SUPEROB_ZDR ? false : (pl.user[k] || (pl.user[CPOL_SUPEROB_ZDR] && k <= CPOL_SUPEROB_ZV));
+        if (need && !h->in[k]) { ctx->err = "superob_fields: a requested field has no input"; return CPOL_ERR_ARG; }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)h->n_rows * h->n_gates;
+    const void *in[CPOL_SUPEROB_FIELDS] = {};
+    const int own[CPOL_SUPEROB_FIELDS] = {0, 1, -1, 3, 4, 5, 6, 7, 8, -1};     // (the sweeps' own output buffers hold the inputs)
+    for (int k = 0; k < CPOL_SUPEROB_FIELDS; ++k) {
+        if (!h->in[k] || k == CPOL_SUPEROB_ZDR) continue;
+        DevBuf &b = k == SO_RVEL ? ctx->b_rvel : ctx->b_out[own[k]];
+        if ((rc = upload(ctx, b, h->in[k], n * (k == SO_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
+        in[k] = b.p;
+    }
+    void *T[SO_N];
+    if ((rc = superob_own_block(ctx, pl, T)) != CPOL_OK) return rc;
+    if ((rc = superob_launch(ctx, &h->so, pl, in, T, h->n_gates, false, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = superob_copy_out(ctx, pl, T)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -1964,6 +2085,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             ctx->err = "cpol_run_sweep: n_gates too large for the range scans (3 * n_gates floats of LDS: at most CPOL_MAX_GATES gates)";
             return CPOL_ERR_ARG;
         }
+    }
+    // superobservations (cpol_superob): every refusal here, before anything of the call is queued
+    const cpol_superob *const so = out->superob;
+    SuperobPlan so_pl{};
+    if (so) {
+        if (cols || sub_out) { ctx->err = "cpol_superob: cpol_run_sweep and cpol_run_sweep_members take superobservations, no other entry point"; return CPOL_ERR_ARG; }
+        const int rc_so = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl);
+        if (rc_so != CPOL_OK) return rc_so;
     }
     int rc;
 
@@ -2412,6 +2541,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             if (!win_hi || a + obytes[k] > win_hi) win_hi = a + obytes[k];
             win_sum += obytes[k];
         }
+    if (async_host && !ctx->keep_debug)                       // (the superobservation arrays count like every other array)
+        for (int k = 0; k < SO_N; ++k) {
+            if (!so_pl.user[k]) continue;
+            char *a = (char *)so_pl.user[k];
+            if (!win_lo || a < win_lo) win_lo = a;
+            if (!win_hi || a + so_pl.bytes[k] > win_hi) win_hi = a + so_pl.bytes[k];
+            win_sum += so_pl.bytes[k];
+        }
     const bool window = win_lo && (size_t)(win_hi - win_lo) <= win_sum + win_sum / 4 + 4096;
     // (the device image keeps the window's alignment modulo 64 B, so that every array of the image is
     // aligned exactly like its host counterpart: a float32 array at an address 4 mod 8 followed by a
@@ -2425,6 +2562,15 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (window && user_out[k]) { T[k] = (char *)ctx->b_outwin.p + win_skew + ((char *)user_out[k] - win_lo); continue; }
         ENSURE(*own[k], obytes[k]);
         T[k] = own[k]->p;
+    }
+    // ... and where k_superob writes: in place (device pointers), into the window's image, or into the context's own block
+    void *so_T[SO_N] = {};
+    if (so && !dev && !window) {
+        const int rc_so = superob_own_block(ctx, so_pl, so_T);
+        if (rc_so != CPOL_OK) return rc_so;
+    } else if (so) {
+        for (int k = 0; k < SO_N; ++k)
+            if (so_pl.user[k]) so_T[k] = dev ? so_pl.user[k] : (void *)((char *)ctx->b_outwin.p + win_skew + ((char *)so_pl.user[k] - win_lo));
     }
 
     // the bucket counters start at zero: cleared by k_interp_sweep (no fill kernel); the domain
@@ -3337,7 +3483,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ctx->err = "cpol_run_sweep: failure requested by the test hook (fail_next_sweep)";
         return CPOL_ERR_HIP;
     }
+    // ---- superobservations: ONE kernel behind the sequence (outside launch_all: the captured graph does not know it) ----
+    if (so) {
+        const void *const so_in[CPOL_SUPEROB_FIELDS] = {T[O_ZH], T[O_ZV], nullptr, T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
+                                                        T[O_ATTV], T[O_RVEL]};
+        if ((rc = superob_launch(ctx, so, so_pl, so_in, so_T, ng, window, st)) != CPOL_OK) return rc;
+    }
     // ---- outputs that the kernels did not write in place ----
+    if (so && !dev && !window && (rc = superob_copy_out(ctx, so_pl, so_T)) != CPOL_OK) return rc;
     if (window) {
         HIPCHK(hipMemcpyAsync(win_lo, (const char *)ctx->b_outwin.p + win_skew, (size_t)(win_hi - win_lo), hipMemcpyDeviceToHost, st));
     } else {
@@ -3399,6 +3552,7 @@ int cpol_interp_subbeams(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_r
 int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *c, cpol_outputs *out)
 {
     if (!ctx) return CPOL_ERR_ARG;
+    if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
         !c->vals || !c->elev || !c->sub_w) {
         ctx->err = "cpol_run_columns: bad shapes, or vals / elev / sub_w missing";
@@ -3690,6 +3844,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         if (!dst || max_bytes < (int64_t)sizeof v) return CPOL_ERR_ARG;
         memcpy(dst, v, sizeof v);
         return (int64_t)sizeof v;
+    }
+    if (!strcmp(name, "superob_fields")) {          // a CONTROL name: dst points to a SuperobHook
+        if (!dst || max_bytes < (int64_t)sizeof(SuperobHook)) { ctx->err = "cpol_debug_read(superob_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return superob_hook(ctx, (const SuperobHook *)dst);
     }
     if (!strcmp(name, "stencil_budget")) {
         // a CONTROL name like "enable": *dst = uint64 bytes the root's store may hold (0: stencils off; default 1 GiB).  Refused while

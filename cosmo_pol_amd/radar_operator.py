@@ -27,12 +27,13 @@ from . import constants as K
 from . import geometry as geo
 from . import hydrometeors as hyd
 from . import quadrature
+from . import superob as SO
 from .lut import load_all_lut
 
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
 DOPPLER_FIELDS = ['RVEL', 'DSPECTRUM']
 _DB_FIELDS = ('ZDR', 'ZV', 'ZH')
-_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1}
+_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2}
 
 
 class ModelVar(object):
@@ -804,6 +805,29 @@ class RadarOperator(object):
         reading the arrays.  (The copy of one sweep then overlaps the kernels of the sweeps on the
         other lanes.)  The gate coordinates (`lats`, `lons`, `dist`, `heights`) of an unchanged
         scan geometry are read-only arrays shared between results."""
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
+                                   paths=paths, lane=lane, pinned=pinned)
+
+    def simulate_rays_superob(self, azimuths, elevations, superob, keep_gates=False, rays_per_block=0, device_outputs=None,
+                              apply_sensitivity=True, paths=None, lane=0, pinned=False):
+        """simulate_rays handing back SUPEROBSERVATIONS: `superob` is a superob.Superob, and the result gains res['superob'] --
+        the window averages of the radar fields made on the device behind the sweep (superob.average states the rule;
+        [window rows, window columns] arrays), 'count' {field: uint16 array} and the window means of lats, lons, dist,
+        heights.  Without `keep_gates` the per-gate radar fields, the mask and -- with output_variables='all' -- the
+        antenna-integrated model variables (`model_vars`: not averaged, and per gate like the rest) are neither produced for
+        the host nor copied (the result keeps the shared gate coordinates); with it all arrive, with the bits of simulate_rays.
+        `rays_per_block`: windows do not cross blocks of that many rays (0: all rays of the call; the rays of one sweep when
+        the call holds several).  With `device_outputs`: its entry 'superob' is {field or 'count': device pointer}.
+        The other keywords: as for simulate_rays.  (A method of its own: the keyword list of simulate_rays is pinned.)
+        NotImplementedError with a process group (windows would cross the ray shards) and for spaceborne geometry."""
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
+                                   paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
+                                   rays_per_block=rays_per_block)
+
+    def _simulate_rays(self, azimuths, elevations, device_outputs=None, apply_sensitivity=True, paths=None, lane=0, pinned=False,
+                       superob=None, keep_gates=False, rays_per_block=0):
+        if superob is not None:
+            self._superob_check(superob)
         conf = self.__config
         coords = conf['radar']['coords']
         if coords[2] > K.MAX_MODEL_HEIGHT:
@@ -825,7 +849,8 @@ class RadarOperator(object):
         mode = N.GEOM_GROUND_43 if paths is None else N.GEOM_HOST_PATHS
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
-                              paths=paths, lane=lane, pinned=pinned)
+                              paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
+                              rays_per_block=rays_per_block)
 
     def stencil_state(self, lane=0):
         """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
@@ -1179,9 +1204,12 @@ class RadarOperator(object):
 
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False, subbeams=None, members=None, timed=None):
+                  pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0):
         if self._model_staged:
             self._sync_edr()
+        if superob is not None:
+            self._superob_check(superob)
+        gates = superob is None or keep_gates     # the per-gate radar fields travel to the host
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -1205,7 +1233,7 @@ class RadarOperator(object):
             if paths is not None or site is not None or not self.reuse_device_tables:
                 version = 0
 
-        want_model = self.output_variables in ('all', 'only_model') and members is None
+        want_model = self.output_variables in ('all', 'only_model') and members is None and gates
 
         def prepare(paths=paths, site=site):
             """The argument structs of cpol_run_sweep for this set of rays (and the arrays they point into)."""
@@ -1309,23 +1337,41 @@ class RadarOperator(object):
         o = N.Outputs()
         res = {}
         geom = None
+        so = so_rpb = None
+        if superob is not None:
+            # (the library refuses the same: the rows of the call are n_members x n_rays, a block never spans two members)
+            so_rpb = int(rays_per_block) or n_rays
+            if int(rays_per_block) < 0 or n_rays % so_rpb:
+                raise ValueError('rays_per_block %r does not divide the %d rays of the call' % (rays_per_block, n_rays))
+            so = N.Superob()
+            so.ray_window, so.gate_window, so.rays_per_block = superob.rays, superob.gates, so_rpb
+            so.min_valid_fraction = superob.min_valid_fraction
+            o.superob = C.pointer(so)
+            so_fields = [k for k in SO.FIELDS if k != 'RVEL' or doppler]
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
+                if k == 'superob':                # {field or 'count': device pointer}
+                    if so is None:
+                        raise ValueError("device_outputs['superob'] without superob=")
+                    for kk, pp in ptr.items():
+                        setattr(so, kk, pp)
+                    continue
                 setattr(o, k, ptr)
         else:
             shape = (n_rays, n_gates)
             gshape = shape                        # (gate coordinates: once, whatever the number of members)
             if members is not None:               # an ensemble call: a leading member axis on every radar field
                 shape = (len(members),) + shape
-            spec = [(k, np.float32, shape) for k in RADAR_FIELDS]
-            if doppler:
+            spec = [(k, np.float32, shape) for k in RADAR_FIELDS] if gates else []
+            if doppler and gates:
                 spec.append(('RVEL', np.float64, shape))
-            if spectrum:
+            if spectrum and gates:
                 spec.append(('DSPECTRUM', np.float64, shape + (len(varray),)))
             # (pinned calls only: a blocking call would have to widen the bytes on the caller's thread at once -- ~1 ns per gate,
             # more than the 7 bytes per gate cost on PCIe; measured on the c5 swaths, 1.7 M gates: 8.5 -> 12.7 ms per step)
             mask8 = self.compact_mask and pinned and 2 * sub.n_sub <= 127
-            spec.append(('mask_sum8', np.int8, shape) if mask8 else ('mask', np.float64, shape))
+            if gates:
+                spec.append(('mask_sum8', np.int8, shape) if mask8 else ('mask', np.float64, shape))
             # gate coordinates of the central sub-beam depend on the ray tables only: of an
             # unchanged table set (version tag) they are copied from the device once
             gkey = ('geom', version, n_gates) if version else None
@@ -1335,6 +1381,13 @@ class RadarOperator(object):
                          ('dist', np.float32, gshape), ('heights', np.float32, gshape)]
             if want_model:
                 spec.append(('model_vars', np.float64, (len(self._staged_vars),) + shape))
+            if so is not None:
+                # the window averages, in the same block: they ride the one copy
+                wshape = SO.shape(n_rays, n_gates, superob, so_rpb)
+                if members is not None:
+                    wshape = (len(members),) + wshape
+                spec += [(('superob', k), np.float64 if k == 'RVEL' else np.float32, wshape) for k in so_fields]
+                spec.append((('superob', 'count'), np.uint16, (len(SO.FIELDS),) + wshape))
             # every host output is a view of ONE block of page-locked memory from the operator's pool
             # (64-byte aligned arrays): the kernels write a device image of the block and a single
             # device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
@@ -1346,8 +1399,13 @@ class RadarOperator(object):
             base = slab.ctypes.data
             off = 0
             for (k, dt, sh), n_el, nb in zip(spec, counts, sizes):
-                res[k] = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
-                setattr(o, k, base + off)           # (= res[k].ctypes.data, without an interface object per array)
+                a = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
+                if isinstance(k, tuple):
+                    res.setdefault('superob', {})[k[1]] = a
+                    setattr(so, k[1], base + off)
+                else:
+                    res[k] = a
+                    setattr(o, k, base + off)       # (= res[k].ctypes.data, without an interface object per array)
                 off += nb
             del slab
         ctx = self._lane(lane)
@@ -1385,6 +1443,22 @@ class RadarOperator(object):
                     self._cache[gkey] = geom
             if geom is not None:
                 res.update(geom)
+            if so is not None:
+                w = res['superob']
+                cnt = w.pop('count')
+                w['count'] = {k: cnt[SO.FIELDS.index(k)] for k in so_fields}
+                if geom is not None:
+                    def window_geom():
+                        # (read-only, like the gate coordinates they are made of: shared by every later result of this table set)
+                        made = SO.coordinates(geom, superob, so_rpb)
+                        for a in made.values():
+                            a.flags.writeable = False
+                        return made
+                    w.update(self._cached(('superob_geom', gkey, superob.rays, superob.gates, so_rpb), window_geom, lru=16))
+                else:                             # (no table version: this call's own coordinate arrays)
+                    if pinned:
+                        ctx.synchronize()
+                    w.update(SO.coordinates(res, superob, so_rpb))
         res['n_sub'] = sub.n_sub
         return res
 
@@ -1479,7 +1553,8 @@ class RadarOperator(object):
         return members
 
     def simulate_rays_ensemble(self, azimuths, elevations, members=None, on_device=False, device_outputs=None,
-                               apply_sensitivity=True, lane=0, form=None, pinned=False):
+                               apply_sensitivity=True, lane=0, form=None, pinned=False, superob=None, keep_gates=False,
+                               rays_per_block=0):
         """simulate_rays for several members of the ensemble at once: the dict of simulate_rays with a leading member axis
         (in the order of `members`; None = all) on the radar fields, `mask` included, and the gate coordinates once.
         form='shared': cpol_run_sweep_members -- geometry once per sub-beam gate, then the members; the member list is cut
@@ -1488,7 +1563,9 @@ class RadarOperator(object):
         single-beam kernels).  form=None: 'shared' from `ensemble_shared_from` sub-beams per radial.  Either way every
         member's arrays carry the bits of simulate_rays on an operator loaded with that member alone.
         `device_outputs`: {field: device pointer} of [n_members, n_rays, n_gates] arrays (geometry: [n_rays, n_gates]).
-        `pinned`: as for simulate_rays when the members fit one chunk; with several chunks the call waits."""
+        `pinned`: as for simulate_rays when the members fit one chunk; with several chunks the call waits.
+        `superob`, `keep_gates`, `rays_per_block`: as for simulate_rays_superob; the arrays of res['superob'] gain the member axis (the
+        window coordinates come once).  A window never holds gates of two members."""
         members = self._members_arg(members)
         conf = self.__config
         coords = conf['radar']['coords']
@@ -1511,6 +1588,9 @@ class RadarOperator(object):
             chunks = ensemble.plan_member_chunks(members, per_gate * sub.n_sub * len(rr) * n_rays, budget)
         else:
             chunks = [[m] for m in members]
+        so_kw = dict(superob=superob, keep_gates=keep_gates, rays_per_block=rays_per_block)
+        if superob is not None and device_outputs is not None and len(chunks) > 1:
+            raise ValueError('simulate_rays_ensemble: superobservations into device outputs need the members in one chunk')
         parts, done = [], 0
         try:
             for chunk in chunks:
@@ -1520,11 +1600,11 @@ class RadarOperator(object):
                 if form == 'per_member':
                     ctx.select_member(chunk[0])
                     r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
-                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned)
+                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned, **so_kw)
                 else:
                     r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
                                        apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned and len(chunks) == 1,
-                                       members=chunk)
+                                       members=chunk, **so_kw)
                 parts.append(r)
                 done += len(chunk)
         finally:
@@ -1538,7 +1618,13 @@ class RadarOperator(object):
             self.wait(lane)                        # (the members are joined on the host: their copies must have landed)
         once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
         join = np.stack if form == 'per_member' else np.concatenate
-        return {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys()}
+        out = {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys() if k != 'superob'}
+        if superob is not None:
+            w0 = parts[0]['superob']
+            out['superob'] = {k: (v if k in once else join([p['superob'][k] for p in parts]))
+                              for k, v in w0.items() if k != 'count'}
+            out['superob']['count'] = {k: join([p['superob']['count'][k] for p in parts]) for k in w0['count']}
+        return out
 
     def _offset_outputs(self, device_outputs, n_before, n_rays, n_gates):
         """The caller's device pointers moved behind the `n_before` members already written (gate coordinates: not moved)."""
@@ -1546,7 +1632,7 @@ class RadarOperator(object):
         width = {'RVEL': 8, 'mask': 8, 'DSPECTRUM': 8 * n_vb, 'sz_total': 4 * N.N_SZ, 'mask_sum8': 1}
         out = {}
         for k, ptr in device_outputs.items():
-            if k in ('lats', 'lons', 'dist', 'heights'):
+            if k in ('lats', 'lons', 'dist', 'heights', 'superob'):
                 out[k] = ptr
             else:
                 out[k] = int(ptr) + n_before * n_rays * n_gates * width.get(k, 4)
@@ -1655,7 +1741,22 @@ class RadarOperator(object):
         output_variables='all'), every array with the bits of simulate_rays on an operator loaded with the host-blended
         cube.  Only the states the rays need are listed for the library; rays that need more than 64 are cut into
         consecutive groups (host outputs only; with several groups a pinned call waits)."""
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs,
+                                      apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned)
+
+    def simulate_rays_at_superob(self, azimuths, elevations, times, superob, keep_gates=False, rays_per_block=0,
+                                 device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
+        """simulate_rays_at handing back superobservations: `superob`, `keep_gates`, `rays_per_block` as for
+        simulate_rays_superob (ValueError when the rays fall into several groups of states: a window would cross them)."""
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs,
+                                      apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned, superob=superob,
+                                      keep_gates=keep_gates, rays_per_block=rays_per_block)
+
+    def _simulate_rays_at(self, azimuths, elevations, times, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False,
+                          superob=None, keep_gates=False, rays_per_block=0):
         self._timed_check()
+        if superob is not None:
+            self._superob_check(superob)
         from . import timeline
         az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
         el = np.asarray(elevations, dtype=np.float64).reshape(-1)
@@ -1672,6 +1773,9 @@ class RadarOperator(object):
         if len(groups) > 1 and device_outputs is not None:
             raise ValueError('simulate_rays_at: the rays read more than %d states; with device outputs split the rays'
                              % N.MEMBERS_PER_CALL)
+        if len(groups) > 1 and superob is not None:
+            raise ValueError('simulate_rays_at: the rays read more than %d states; superobservations need one group'
+                             % N.MEMBERS_PER_CALL)
         coords = self.__config['radar']['coords']
         rr = self.constants.RANGE_RADAR
         parts = []
@@ -1680,7 +1784,8 @@ class RadarOperator(object):
                   np.ascontiguousarray(w[r0:r1], dtype=np.float32))
             parts.append(self._run_rays(az[r0:r1], el[r0:r1], coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
                                         device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
-                                        pinned=pinned and len(groups) == 1, timed=tm))
+                                        pinned=pinned and len(groups) == 1, timed=tm, superob=superob, keep_gates=keep_gates,
+                                        rays_per_block=rays_per_block))
         if len(parts) == 1:
             return parts[0]
         return {k: (v if not isinstance(v, np.ndarray) else
@@ -1977,6 +2082,55 @@ class RadarOperator(object):
         elevation, returned as a RadarScan."""
         if not self._check_ready():
             return
+        elevations, azimuths, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        sweeps = self._simulate_sweeps(sweeps)
+        if sweeps is None:
+            return None                       # distributed with gather_to: rank `gather_to` holds the scan
+        return self._finish_scan(RadarScan('ppi', list(elevations), list(azimuths),
+                                           self.constants.RANGE_RADAR, self.get_pos_and_time(), sweeps))
+
+    def get_RHI(self, azimuths, elevations=None, elev_step=None, elev_start=0, elev_stop=90):
+        """Simulates RHI scan(s) (radar_operator.py:455-549); one sweep per azimuth."""
+        if not self._check_ready():
+            return
+        elevations, azimuths, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        sweeps = self._simulate_sweeps(sweeps)
+        if sweeps is None:
+            return None
+        return self._finish_scan(RadarScan('rhi', list(elevations), list(azimuths),
+                                           self.constants.RANGE_RADAR, self.get_pos_and_time(), sweeps))
+
+    # ------------------------------------------------------------------ superobservation scans
+    def _superob_check(self, superob):
+        """What a superobservation call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        themselves: they take ground radars.)"""
+        if not isinstance(superob, SO.Superob):
+            raise ValueError('superob: a cosmo_pol_amd.superob.Superob, got %r' % (superob,))
+        if self.distributed:
+            raise NotImplementedError('superobservations with a process group: the windows would cross the ray shards')
+
+    def _superob_sweeps(self, sweeps, spec, keep_gates):
+        """One pinned call per sweep over the lanes, one wait at the end: every sweep carries the bits of its own
+        simulate_rays_superob(..., spec)."""
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        n_par = max(1, min(self.lanes, len(sweeps)))
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                res.append(self.simulate_rays_superob(az, el, spec, keep_gates=keep_gates, pinned=True, lane=k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        return res
+
+    def _ppi_sweeps(self, elevations, azimuths, az_step, az_start, az_stop):
+        """get_PPI's defaults -> (elevations, azimuths, [(az, el) per sweep])"""
         if np.isscalar(elevations):
             elevations = [elevations]
         if az_step is None:
@@ -1988,17 +2142,10 @@ class RadarOperator(object):
             else:
                 azimuths = np.arange(az_start, az_stop + az_step, az_step)
         azimuths = np.asarray(azimuths, dtype=float)
-        sweeps = self._simulate_sweeps([(azimuths, np.full(len(azimuths), float(e)))
-                                        for e in elevations])
-        if sweeps is None:
-            return None                       # distributed with gather_to: rank `gather_to` holds the scan
-        return self._finish_scan(RadarScan('ppi', list(elevations), list(azimuths),
-                                           self.constants.RANGE_RADAR, self.get_pos_and_time(), sweeps))
+        return elevations, azimuths, [(azimuths, np.full(len(azimuths), float(e))) for e in elevations]
 
-    def get_RHI(self, azimuths, elevations=None, elev_step=None, elev_start=0, elev_stop=90):
-        """Simulates RHI scan(s) (radar_operator.py:455-549); one sweep per azimuth."""
-        if not self._check_ready():
-            return
+    def _rhi_sweeps(self, azimuths, elevations, elev_step, elev_start, elev_stop):
+        """get_RHI's defaults -> (elevations, azimuths, [(az, el) per sweep])"""
         if np.isscalar(azimuths):
             azimuths = [azimuths]
         if elevations is None or np.any(np.equal(elevations, None)):
@@ -2006,12 +2153,18 @@ class RadarOperator(object):
                 elev_step = self.__config['radar']['3dB_beamwidth']
             elevations = np.arange(elev_start, elev_stop + elev_step, elev_step)
         elevations = np.asarray(elevations, dtype=float)
-        sweeps = self._simulate_sweeps([(np.full(len(elevations), float(a)), elevations)
-                                        for a in azimuths])
-        if sweeps is None:
-            return None
-        return self._finish_scan(RadarScan('rhi', list(elevations), list(azimuths),
-                                           self.constants.RANGE_RADAR, self.get_pos_and_time(), sweeps))
+        return elevations, azimuths, [(np.full(len(elevations), float(a)), elevations) for a in azimuths]
+
+    def get_PPI_superob(self, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, keep_gates=False):
+        """The sweeps of get_PPI as superobservations: a list with one simulate_rays_superob(..., spec) result per elevation
+        (res['superob']: window averages, counts, window coordinates).  Windows stay inside their sweep."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._superob_sweeps(sweeps, spec, keep_gates)
+
+    def get_RHI_superob(self, azimuths, spec, elevations=None, elev_step=None, elev_start=0, elev_stop=90, keep_gates=False):
+        """The sweeps of get_RHI as superobservations: one result per azimuth (see get_PPI_superob)."""
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._superob_sweeps(sweeps, spec, keep_gates)
 
     def get_VPROF(self):
         """90-degree vertical profile (the reference's version is broken as

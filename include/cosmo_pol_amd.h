@@ -260,6 +260,43 @@ typedef struct {
     int32_t pad_time_;
 } cpol_ray_tables_t;
 
+/* Superobservations: what a data-assimilation system consumes instead of one value per gate -- averages of the per-gate
+ * fields over windows of ray_window rays x gate_window gates, with the number of gates that went into each.  Replaces in
+ * the reference: nothing (it hands back per-gate radials).  Pointed to by cpol_outputs.superob; honoured by cpol_run_sweep
+ * and cpol_run_sweep_members (ensemble and time blend), refused by cpol_run_columns.
+ * INPUT: the per-gate fields of the call as the launch sequence leaves them (after the range scans and the sensitivity cut;
+ * censored gates are NaN): n_rows rows of n_gates gates, n_rows = n_rays, or n_members * n_rays for an ensemble call.
+ * WINDOWS tile the rows in blocks of rays_per_block rows: window row i of a block holds its rays [i R, min((i + 1) R,
+ * rays_per_block)), window column j the gates [j G, min((j + 1) G, n_gates)); a window never crosses a block (so it stays
+ * inside one member, one sweep of a grouped scan); the last windows may be partial; no azimuth wrap-around.  n_cells =
+ * (n_rows / rays_per_block) * ceil(rays_per_block / R) * ceil(n_gates / G), blocks stacked in row order, columns fastest.
+ * PER FIELD: a gate counts when its value is not NaN, n = the counting gates; per ray of the window in ascending order s_r =
+ * the float64 sum of its counting values in ascending gate order from +0.0; S = the float64 sum of the s_r in ascending ray
+ * order from +0.0; the superobservation is S / n (float64 division), rounded once to float32 for the float32 fields; NaN when
+ * n < need = max(1, (int)ceil(min_valid_fraction * N)), N = the gates the window actually holds.
+ * ZDR is the ratio of the window's mean powers: over the gates where ZH and ZV both count, S_H and S_V by the rule above,
+ * ZDR = (float)(S_H / S_V), n = those gates.  RVEL after aliasing: the mean of the folded velocities, nothing is unfolded.
+ * mask, model_vars, sz_total and DSPECTRUM are not averaged.
+ * The output pointers follow p->outputs_on_device like every other array (mode 2: they count for the one-copy window rule).
+ * CPOL_ERR_ARG, nothing queued, the context usable: a window < 1, R * G > 65535 (count is uint16), min_valid_fraction outside
+ * (0, 1] or NaN, rays_per_block < 0 or not dividing n_rows, none of the ten field pointers set, RVEL without Doppler.
+ * ONE kernel (k_superob) runs behind the launch sequence and before the output copy: the per-gate arrays, the launch forms,
+ * the gate stencils and a captured graph are what they are without it.  A per-gate array the caller leaves NULL is still
+ * produced on the device (the context's own buffer) and simply not copied. */
+typedef struct cpol_superob {
+    int32_t ray_window;         /* R >= 1                                                                  */
+    int32_t gate_window;        /* G >= 1                                                                  */
+    int32_t rays_per_block;     /* 0: p->n_rays of the call; else it must divide the call's row count      */
+    int32_t pad_;
+    double  min_valid_fraction; /* in (0, 1]                                                               */
+    /* all [n_cells]; NULL = not wanted */
+    float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
+    double *RVEL;
+    uint16_t *count;            /* [10][n_cells] or NULL: n of every field, rows in the order ZH, ZV, ZDR, KDP, DELTA_HV, PHIDP,
+                                   RHOHV, ATT_H, ATT_V, RVEL; only the rows of requested fields are written (mode 2 under the
+                                   window rule: the other rows lie inside the window and arrive as zeros) */
+} cpol_superob;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -275,6 +312,8 @@ typedef struct {
                                    domain; doppler_scatter.py:472-477), one byte per gate instead of the eight of `mask`.
                                    mask = mask_sum8 / n_sub, then values in (-1, 0] -> 0: the caller's two NumPy statements.
                                    Needs 2 * n_sub <= 127.  When it is asked for and `mask` is not, `mask` is not written. */
+    cpol_superob *superob;      /* NULL (a zero-initialised struct): off.  Window averages of the fields above, see cpol_superob.
+                                   Stays the LAST member */
 } cpol_outputs;
 
 typedef struct {
@@ -644,6 +683,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * "stencil_budget" is a CONTROL name like "enable": dst points to a uint64, the bytes the store may hold (0: stencils off;
  * default 1 GiB).  Root context only and refused (CPOL_ERR_ARG) while lanes of it exist; lowering it below what is held drops
  * every entry.  Returns 0.
+ * "superob_fields" is a CONTROL name too, a test hook: k_superob on caller-supplied per-gate arrays.  dst points to
+ * { int32_t n_rows, n_gates; const void *in[10]; cpol_superob so; } -- `in` in the order of cpol_superob.count's rows, host arrays
+ * [n_rows * n_gates] float32 (slot ZDR unused, slot RVEL float64, NULL = not given), `so` with host output pointers
+ * (rays_per_block = 0: n_rows); blocking; cpol_superob's refusals, and CPOL_ERR_ARG for a requested field without its input.
+ * Returns 0.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
