@@ -25,6 +25,7 @@
 
 #include "cpol_device.h"
 #include "cpol_tile.h"
+#include "cpol_forms.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -33,6 +34,11 @@
 #include "cpol_spectrum.inl"
 #include "cpol_ingest.inl"
 #include "cpol_superob.inl"
+
+static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
+              FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
+              (int)FORMS_MODE_GAMMA_UNIFORM == (int)PSD_MODE_GAMMA_UNIFORM && (int)FORMS_MODE_ICE == (int)PSD_MODE_ICE &&
+              (int)FORMS_MODE_MELTING == (int)PSD_MODE_MELTING, "cpol_forms.h: the build constants of the kernel files");
 
 namespace {
 
@@ -92,7 +98,7 @@ struct cpol_ctx {
     cpol_ctx *parent = nullptr;
     int n_children = 0;
     // HIP graph of the sweep's launch sequence (device outputs, unchanged arguments)
-    bool use_graph = false;
+    Knobs knobs;                       // the launch-rule knobs of the environment (cpol_forms.h), read when the context is created
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};     // one per counter set (the sets alternate sweep by sweep)
     uint64_t graph_key[2] = {0, 0};
     uint64_t stage_serial = 0;         // bumped by every staging call (kernel arguments change)
@@ -184,23 +190,6 @@ struct cpol_ctx {
     bool counters_dirty = false;       // a launch sequence began and did not end in sweep_serial advancing (an error return after
                                        // its first launch): both counter sets are cleared before the next sequence uses one
     int last_par = 0;                  // the set the last sweep used
-    int subsum_coop_rounds = 6;        // CPOL_SUBSUM_COOP_ROUNDS: scalar-cache rounds per wavefront and sub-beam before the gather tail
-    int rare_overlap = 0;              // CPOL_RARE_OVERLAP=1: k_psd_rare beside k_psd_lookup on a sibling stream instead of behind it (measured: the share of
-                                       // one of 8 GPUs 1.42 -> 1.37 ms alone, 0.97 -> 0.99 with three lanes; the C3 sweep 151 -> 167 us: the fork and join cost
-                                       // more than the idle launch -- off)
-    int rare_direct = 1;               // CPOL_RARE_DIRECT=0: keep the counting sort of the items outside the tables (read when the context is created)
-    int lookup_list = 1;               // CPOL_LOOKUP_LIST=0: k_psd_lookup starts one wavefront per tile instead of workgroups that list the tiles with work among their own; 2: the list for every launch size
-    int lookup_split = 0;              // CPOL_LOOKUP_SPLIT=<n>: wavefronts per tile of k_psd_lookup (0: by launch size)
-    int gate1_ray = -1;                // -1 (default): 1 in a context with lanes (sweeps in flight side by side: three launches instead of four per sweep are 6-8 % of
-                                       // c2's throughput), 0 without (the isolated sweep: 88 against 91 us); CPOL_GATE1_RAY=0: never; 1: k_gate1_ray (items off the tables integrated in place, the range scans by k_scan_rays: a single-beam sweep
-                                       // of three lean launches, no integrating launch); 2: also with tables that lost panels; 3: the scans inside the gate kernel (a ticket per ray)
-    int gate1_species = 1;             // CPOL_GATE1_SPECIES=0 / 2: never / always k_gate1_species (one wavefront per species; default: small launches)
-    int fuse_gate1 = 0;                // CPOL_FUSE_GATE1=1: k_interp_gate1 instead of k_interp_sweep + k_gate1 (measured slower where it matters)
-    int fuse_classify = 1;             // CPOL_FUSE_CLASSIFY=0: k_interp_sweep + k_classify instead of k_interp_classify (read when the context is created)
-    int gate1 = 1;                     // CPOL_GATE1=0 / 2: never / also with melting species: the single-beam fused kernel (read when the context is created)
-    int subsum = 1;                    // CPOL_SUBSUM=0: the plain form: k_psd_lookup stores every item's columns and one thread of k_final walks the sub-beams in order (read when the context is created)
-    int subsum_scalar = 0;             // CPOL_SUBSUM_FORM=scalar: the cooperative form of k_subbeam_sum takes its rows through the scalar cache instead of LDS
-    int upload_kernel = 0;             // CPOL_TABLE_UPLOAD=kernel: the per-ray tables by k_upload_tables instead of hipMemcpyAsync (a measurement knob)
     int last_forms[12] = {0};          // the launch forms of the last sweep (cpol_debug_read "launch_forms"): [0] g1r, [1] k_gate1_ray, [2] single-beam gate kernel,
                                        // [3] k_interp_classify, [4] items off the tables listed directly, [5] k_subbeam_sum, [6] table items evaluated in place,
                                        // [7] coordinate polynomials for the one sub-beam, [8] n_sub, [9] lanes alive, [10] CPOL_SCAN_FORM (1: the range scans by a whole wavefront), [11] HIP graph replayed
@@ -220,16 +209,6 @@ struct cpol_ctx {
     int last_stencil = 0;
     std::vector<uint64_t> st_seen;
     int last_poly_central = 0;         // the last sweep's one sub-beam took the coordinate polynomials (cpol_debug_read "poly_central")
-    int geo_poly_central = 1;          // CPOL_GEO_POLY_CENTRAL=0: a single-beam sweep keeps the long form of the geodesy for its (central) sub-beam even when
-                                       // nobody asks for the float64 latitude / longitude; 2: the polynomials also with the debug reads enabled (tools/fast_sub_check.py)
-    int geo_poly = 1;                  // CPOL_GEO_POLY=0: the non-central sub-beams take the short closed form of the geodesy instead of the per-ray polynomials
-    int psd_rare = 1;                  // CPOL_PSD_RARE=0: one launch per integrating flavour also when the units are directly listed items (read when the context is created)
-    int subsum_small = 0;              // CPOL_SUBSUM_SMALL=1: experiment: the gather form of k_subbeam_sum with three wavefronts per (tile, hydrometeor) and the whole block in flight (measured slower)
-    int subsum_chain = 1;              // CPOL_SUBSUM_CHAIN=0: the team's terms pass through LDS and a barrier per round instead of its float32 sums waiting in LDS, handed
-                                       // from sub-beam to sub-beam (share of one of 8 GPUs: 385 against 334 us)
-    int subsum_team = -1;              // CPOL_SUBSUM_TEAM=W: k_subbeam_sum_team<W> (W = 2..8 wavefronts per (tile, species)) for every launch; 0: never (the one-wavefront
-                                       // forms alone); -1 (default): W = 4 for the launches too small for the LDS form
-    int subsum_coop = -1;              // CPOL_SUBSUM_COOP: k_subbeam_sum takes its coefficients through the scalar cache: 0 never, 1 always, -1 by launch size
     bool last_subsum = false;          // the 1-D table items of the last sweep never went through res[] (k_subbeam_sum)
     bool keep_debug = false;
     // host time of cpol_run_sweep by section (ns, summed; cpol_debug_read "host_times"): [0] calls, [1] per-ray tables
@@ -716,32 +695,7 @@ int cpol_create(int device, cpol_ctx **out)
         delete ctx;
         return CPOL_ERR_HIP;
     }
-    // opt-in (CPOL_USE_GRAPH=1): replaying the captured sequence cuts the host time of a sweep
-    // 4x (0.12 -> 0.03 ms) but is no faster on the device (0.232 vs 0.222 ms single lane) and
-    // slows three-lane throughput by a quarter when graph launches and plain launches mix
-    ctx->use_graph = getenv("CPOL_USE_GRAPH") && atoi(getenv("CPOL_USE_GRAPH")) != 0;
-    // CPOL_SUBSUM_COOP=0 / 1: k_subbeam_sum never / always takes the coefficient rows through the scalar cache
-    // (default: by launch size; the results are identical)
-    if (getenv("CPOL_SUBSUM_COOP")) ctx->subsum_coop = atoi(getenv("CPOL_SUBSUM_COOP")) != 0 ? 1 : 0;
-    if (getenv("CPOL_LOOKUP_LIST")) ctx->lookup_list = std::max(0, std::min(2, atoi(getenv("CPOL_LOOKUP_LIST"))));
-    if (getenv("CPOL_LOOKUP_SPLIT")) ctx->lookup_split = std::max(0, std::min(16, atoi(getenv("CPOL_LOOKUP_SPLIT"))));
-    if (getenv("CPOL_GATE1_SPECIES")) ctx->gate1_species = std::max(0, std::min(2, atoi(getenv("CPOL_GATE1_SPECIES"))));
-    if (getenv("CPOL_GATE1_RAY")) ctx->gate1_ray = std::max(-1, std::min(3, atoi(getenv("CPOL_GATE1_RAY"))));   // (2: also with tables that lost panels; 3: the scans inside the gate kernel)
-    if (getenv("CPOL_FUSE_GATE1")) ctx->fuse_gate1 = atoi(getenv("CPOL_FUSE_GATE1")) != 0 ? 1 : 0;
-    if (getenv("CPOL_FUSE_CLASSIFY")) ctx->fuse_classify = atoi(getenv("CPOL_FUSE_CLASSIFY")) != 0 ? 1 : 0;
-    if (getenv("CPOL_RARE_OVERLAP")) ctx->rare_overlap = atoi(getenv("CPOL_RARE_OVERLAP")) != 0 ? 1 : 0;
-    if (getenv("CPOL_RARE_DIRECT")) ctx->rare_direct = atoi(getenv("CPOL_RARE_DIRECT")) != 0 ? 1 : 0;
-    if (getenv("CPOL_GATE1")) ctx->gate1 = atoi(getenv("CPOL_GATE1"));
-    if (getenv("CPOL_SUBSUM")) ctx->subsum = atoi(getenv("CPOL_SUBSUM")) != 0 ? 1 : 0;
-    if (getenv("CPOL_SUBSUM_FORM")) ctx->subsum_scalar = !strcmp(getenv("CPOL_SUBSUM_FORM"), "scalar") ? 1 : 0;
-    if (getenv("CPOL_SUBSUM_CHAIN")) ctx->subsum_chain = atoi(getenv("CPOL_SUBSUM_CHAIN")) != 0 ? 1 : 0;
-    if (getenv("CPOL_SUBSUM_TEAM")) ctx->subsum_team = atoi(getenv("CPOL_SUBSUM_TEAM"));
-    if (getenv("CPOL_SUBSUM_SMALL")) ctx->subsum_small = atoi(getenv("CPOL_SUBSUM_SMALL")) != 0 ? 1 : 0;
-    if (getenv("CPOL_TABLE_UPLOAD")) ctx->upload_kernel = strcmp(getenv("CPOL_TABLE_UPLOAD"), "kernel") == 0 ? 1 : 0;
-    if (getenv("CPOL_GEO_POLY_CENTRAL")) ctx->geo_poly_central = std::max(0, std::min(2, atoi(getenv("CPOL_GEO_POLY_CENTRAL"))));
-    if (getenv("CPOL_GEO_POLY")) ctx->geo_poly = atoi(getenv("CPOL_GEO_POLY")) != 0 ? 1 : 0;
-    if (getenv("CPOL_PSD_RARE")) ctx->psd_rare = atoi(getenv("CPOL_PSD_RARE")) != 0 ? 1 : 0;
-    if (getenv("CPOL_SUBSUM_COOP_ROUNDS")) ctx->subsum_coop_rounds = std::max(0, std::min(64, atoi(getenv("CPOL_SUBSUM_COOP_ROUNDS"))));
+    ctx->knobs = knobs_from_env();
     *out = ctx;
     return CPOL_OK;
 }
@@ -849,27 +803,7 @@ int cpol_fork(cpol_ctx *parent, cpol_ctx **out)
         parent->err = "cpol_fork: hipMalloc failed";
         return CPOL_ERR_NOMEM;
     }
-    c->use_graph = parent->use_graph;
-    c->subsum_coop = parent->subsum_coop;
-    c->subsum = parent->subsum;
-    c->subsum_small = parent->subsum_small;
-    c->subsum_team = parent->subsum_team;
-    c->subsum_chain = parent->subsum_chain;
-    c->psd_rare = parent->psd_rare;
-    c->geo_poly = parent->geo_poly;
-    c->geo_poly_central = parent->geo_poly_central;
-    c->upload_kernel = parent->upload_kernel;
-    c->subsum_scalar = parent->subsum_scalar;
-    c->rare_direct = parent->rare_direct;
-    c->rare_overlap = parent->rare_overlap;
-    c->fuse_classify = parent->fuse_classify;
-    c->fuse_gate1 = parent->fuse_gate1;
-    c->gate1_species = parent->gate1_species;
-    c->gate1_ray = parent->gate1_ray;
-    c->lookup_split = parent->lookup_split;
-    c->lookup_list = parent->lookup_list;
-    c->gate1 = parent->gate1;
-    c->subsum_coop_rounds = parent->subsum_coop_rounds;
+    c->knobs = parent->knobs;
     c->parent = parent;
     c->model_staged = parent->model_staged;
     c->model = parent->model;
@@ -2034,6 +1968,33 @@ struct MembersCall {
     const float *ray_weight;            // [n_rays] host (timed)
 };
 
+// the next slot of the page-locked staging ring, grown to `bytes`; its last copy has left the buffer (t_free: when that was known)
+static int staging_slot(cpol_ctx *ctx, size_t bytes, cpol_ctx::Staging **slot, double *t_free = nullptr)
+{
+    cpol_ctx::Staging &sg = ctx->stg[ctx->stg_next];
+    ctx->stg_next = (ctx->stg_next + 1) % 4;
+    if (sg.used) HIPCHK(hipEventSynchronize(sg.ev));
+    if (t_free) *t_free = now_ns();
+    if (sg.cap < bytes) {
+        if (sg.p) (void)hipHostFree(sg.p);
+        sg.p = nullptr; sg.cap = 0;
+        HIPCHK(hipHostMalloc(&sg.p, bytes + bytes / 4 + 4096, hipHostMallocDefault));
+        sg.cap = bytes + bytes / 4 + 4096;
+    }
+    if (!sg.ev) HIPCHK(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+    *slot = &sg;
+    return CPOL_OK;
+}
+
+// the output window of the pinned-host mode: [lo, hi) widened to the caller's array a, sum: the bytes of the arrays alone
+static void window_add(void *a_, size_t bytes, char *&lo, char *&hi, size_t &sum)
+{
+    char *a = (char *)a_;
+    if (!lo || a < lo) lo = a;
+    if (!hi || a + bytes > hi) hi = a + bytes;
+    sum += bytes;
+}
+
 static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
                         const cpol_columns_t *cols, cpol_subbeam_outputs *sub_out, cpol_outputs *out,
                         const MembersCall *mem = nullptr)
@@ -2147,18 +2108,11 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         set->version = 0;                                        // (not valid until the copy is queued)
         set->poly_version = 0;                                   // (other rays: their polynomials are made again)
         ENSURE(set->buf, total);
-        cpol_ctx::Staging &sg = ctx->stg[ctx->stg_next];
-        ctx->stg_next = (ctx->stg_next + 1) % 4;
+        cpol_ctx::Staging *sgp = nullptr;
         const double t_s0 = now_ns();
-        if (sg.used) HIPCHK(hipEventSynchronize(sg.ev));        // its last copy has left the buffer
-        const double t_s1 = now_ns();
-        if (sg.cap < total) {
-            if (sg.p) (void)hipHostFree(sg.p);
-            sg.p = nullptr; sg.cap = 0;
-            HIPCHK(hipHostMalloc(&sg.p, total + total / 4 + 4096, hipHostMallocDefault));
-            sg.cap = total + total / 4 + 4096;
-        }
-        if (!sg.ev) HIPCHK(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+        double t_s1 = t_s0;
+        if ((rc = staging_slot(ctx, total, &sgp, &t_s1)) != CPOL_OK) return rc;
+        cpol_ctx::Staging &sg = *sgp;
         size_t off = 0;
         for (int k = 0; k < 11; ++k) {
             const Item &it = items[k];
@@ -2168,7 +2122,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             off += (it.bytes + 63) & ~(size_t)63;
         }
         const double t_s2 = now_ns();
-        if (ctx->upload_kernel) {
+        if (ctx->knobs.upload_kernel) {
             const long n16 = (long)(total / 16);          // (every table is padded to 64 bytes)
             hipLaunchKernelGGL(k_upload_tables, dim3((unsigned)std::min<long>(cdiv(n16, 256), 256)), dim3(256), 0, ctx->stream,
                                (uint4 *)set->buf.p, (const uint4 *)sg.p, n16);
@@ -2185,27 +2139,40 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     const double t_tables = now_ns();
     // ---- work buffers ----
-    // several sub-beams: the ray paths (shared by the horizontal nodes of a vertical node) and the per-ray
-    // constants of the geodesic come from k_trajectory instead of once per sub-beam gate
-    const bool ray_prep = n_sub >= CPOL_RAY_PREP_MIN_SUB && !cols;
-    const bool prep_paths = ray_prep && n_h > 1 && mode != CPOL_GEOM_HOST_PATHS;
-    if (mode == CPOL_GEOM_HOST_PATHS || ctx->keep_debug || prep_paths)
+    // which kernels this call launches and in which form: every rule in cpol_forms.h, decided here once
+    FormIn fi;
+    fi.n_rays = n_rays; fi.n_gates = ng; fi.n_sub = n_sub; fi.n_h = n_h; fi.geo_rays = geo_rays;
+    fi.columns = cols != nullptr; fi.sub_export = sub_out != nullptr; fi.members = mem != nullptr; fi.timed = timed;
+    fi.melt_given = melt_given; fi.ml = ml; fi.skip_melting = sub_out && sub_out->skip_melting;
+    fi.geometry_mode = mode; fi.doppler = p->simulate_doppler;
+    fi.site = t->site != nullptr; fi.versioned = t->version != 0; fi.with_melting = p->with_melting != 0;
+    fi.exact_sub = (p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS) != 0;
+    fi.want_latlon = out->lats || out->lons; fi.want_sz_total = out->sz_total != nullptr;
+    fi.want_model = p->integrate_model && out->model_vars; fi.reuse = reuse;
+    fi.outputs_on_device = p->outputs_on_device;
+    fi.keep_debug = ctx->keep_debug; fi.timing = ctx->timing; fi.nz = ctx->model.nz;
+    fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
+    fi.scan_form = CPOL_SCAN_FORM;
+    fi.n_hydro = n_hyd;
+    for (int j = 0; j < n_hyd; ++j) {
+        const cpol_hydro_desc &d = ctx->hs.h[j].d;
+        const ItabDev &tj = ctx->its.t[j];
+        FormSpecies &s = fi.s[j];
+        s.tab = tj.tab != nullptr; s.two_d = tj.two_d != 0; s.writes_vn = tj.writes_vn != 0;
+        s.pan_lo = tj.pan_lo; s.pan_hi = tj.pan_hi; s.n_pan = tj.n_pan;
+        s.psd_family = d.psd_family; s.numeric_intv = d.numeric_intv; s.q_source = d.q_source; s.uniform_grid = d.uniform_grid;
+        s.tab_degree = d.tab_degree; s.rule = d.rule; s.var_q = d.var_q;
+        s.pre = ctx->hs.h[j].pre != nullptr; s.dnu = ctx->hs.h[j].dnu != nullptr;
+    }
+    const ProcessKnobs &pk = process_knobs();
+    const Forms f = choose_forms(fi, ctx->knobs, pk);
+    if (mode == CPOL_GEOM_HOST_PATHS || ctx->keep_debug || f.prep_paths)
         ENSURE(ctx->b_traj, (size_t)n_rays * n_v * 3 * ng * sizeof(float));
-    if (ray_prep) ENSURE(ctx->b_rayc, ((size_t)n_rays * n_h + n_rays) * 2 * sizeof(double));
-    // the rotated coordinates of the non-central sub-beams as polynomials of the arc distance (cpol_interp.inl: k_trajectory):
-    // ground radars on the 4/3-earth ray paths, one site (CPOL_GEO_POLY=0: the short closed form of round 4)
-    const bool geo_poly = ray_prep && ctx->geo_poly && mode == CPOL_GEOM_GROUND_43 && !t->site;
-    // single-beam sweeps (round 5): the one sub-beam takes the polynomials too when its float64 latitude / longitude are not
-    // outputs; they belong to the resident table set of the rays and are made once per (version, range grid)
-    const bool poly_single = !ray_prep && !cols && ctx->geo_poly && ctx->geo_poly_central && mode == CPOL_GEOM_GROUND_43 && !t->site &&
-                             (!ctx->keep_debug || ctx->geo_poly_central == 2) && t->version != 0 && !(p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS);
-    // (round 6: also when the float64 latitude / longitude are outputs -- the long form then runs for those two arrays alone and
-    // the float32 grid coordinates still come from the guarded polynomials: identical calls give identical bits whether or not the
-    // caller fetches the gate coordinates, round-5 advisor finding)
+    if (f.ray_prep) ENSURE(ctx->b_rayc, ((size_t)n_rays * n_h + n_rays) * 2 * sizeof(double));
     // arc distance <= slant range; a margin of 1e-3 for the asin of the 4/3-earth formula
     const double geo_poly_scale = 2.0 / ((p->range0 + (double)(ng - 1) * p->range_step) * 1.001);
-    if (geo_poly || poly_single) {
-        if (geo_poly) ENSURE(ctx->b_poly, (size_t)n_rays * n_h * 2 * CPOL_GEO_NP * sizeof(double));
+    if (f.geo_poly || f.poly_single) {
+        if (f.geo_poly) ENSURE(ctx->b_poly, (size_t)n_rays * n_h * 2 * CPOL_GEO_NP * sizeof(double));
         if (!ctx->d_geoM.p) {
             // Chebyshev-node values -> monomial coefficients (as build_itabs' M), extended precision on the host
             constexpr int NP = CPOL_GEO_NP;
@@ -2226,7 +2193,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             if (rc != CPOL_OK) return rc;
             HIPCHK(hipStreamSynchronize(ctx->stream));           // (M is a stack array)
         }
-        if (poly_single && (!set->poly.p || set->poly_version != set->version || set->poly_scale != geo_poly_scale ||
+        if (f.poly_single && (!set->poly.p || set->poly_version != set->version || set->poly_scale != geo_poly_scale ||
                             set->poly_site[0] != p->radar_lon || set->poly_site[1] != p->sin_u1 || set->poly_site[2] != p->cos_u1)) {
             ENSURE(set->poly, (size_t)n_rays * n_h * 2 * CPOL_GEO_NP * sizeof(double));
             TrajArgs tp{};
@@ -2252,16 +2219,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (ctx->timed_shadow.size() != total || memcmp(ctx->timed_shadow.data(), mem->ray_state, nb) != 0 ||
             memcmp(ctx->timed_shadow.data() + nb, mem->ray_weight, nb) != 0) {
             ctx->timed_shadow.clear();                           // (not valid until the copy is queued)
-            cpol_ctx::Staging &sg = ctx->stg[ctx->stg_next];
-            ctx->stg_next = (ctx->stg_next + 1) % 4;
-            if (sg.used) HIPCHK(hipEventSynchronize(sg.ev));    // its last copy has left the buffer
-            if (sg.cap < total) {
-                if (sg.p) (void)hipHostFree(sg.p);
-                sg.p = nullptr; sg.cap = 0;
-                HIPCHK(hipHostMalloc(&sg.p, total + total / 4 + 4096, hipHostMallocDefault));
-                sg.cap = total + total / 4 + 4096;
-            }
-            if (!sg.ev) HIPCHK(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
+            cpol_ctx::Staging *sgp = nullptr;
+            if ((rc = staging_slot(ctx, total, &sgp)) != CPOL_OK) return rc;
+            cpol_ctx::Staging &sg = *sgp;
             memcpy(sg.p, mem->ray_state, nb);
             memcpy((char *)sg.p + nb, mem->ray_weight, nb);
             HIPCHK(hipMemcpyAsync(ctx->b_timed.p, sg.p, total, hipMemcpyHostToDevice, ctx->stream));
@@ -2354,7 +2314,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     if (doppler) {
         ENSURE(ctx->b_vn, (size_t)n_hyd * n_sbg * 2 * sizeof(double));
         ENSURE(ctx->b_icefirst, (size_t)n_rays * n_sub * sizeof(IceFirst));
-        if (!dop3 && n_sub >= 4) ENSURE(ctx->b_proj, (size_t)n_sbg * sizeof(double));     // k_rvel_terms
+        if (f.rvel_terms) ENSURE(ctx->b_proj, (size_t)n_sbg * sizeof(double));
     }
     // (every argument check and every allocation of the sequence happens before its first launch: an error return
     // further down would leave the sweep's counter set half used; see counters_dirty)
@@ -2381,17 +2341,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // (lats, lons, dist, heights, elev) and mask_ml
     const size_t xa8 = ((size_t)n_sbg * sizeof(double) + 255) & ~(size_t)255, xa4 = ((size_t)n_sbg * sizeof(float) + 255) & ~(size_t)255;
     const size_t xa1 = ((size_t)n_sbg + 255) & ~(size_t)255;
-    int melt_qr = -1, melt_qs = -1, melt_qg = -1;
-    for (int j = 0; j < n_hyd; ++j) {
-        const cpol_hydro_desc &d = ctx->hs.h[j].d;
-        if (d.q_source != CPOL_Q_MODEL) continue;
-        if (d.rule == CPOL_RULE_RAIN_1MOM) melt_qr = d.var_q;
-        if (d.rule == CPOL_RULE_SNOW_1MOM) melt_qs = d.var_q;
-        if (d.rule == CPOL_RULE_GRAUPEL_1MOM) melt_qg = d.var_q;
-    }
-    const bool sub_melt = sub_out && p->with_melting && !sub_out->skip_melting;
+    const bool melt_vars = f.melt_qr >= 0 && f.melt_qs >= 0 && f.melt_qg >= 0;      // 1-moment rain, snow and graupel slots are staged
     if (sub_out) {
-        if (p->with_melting && (melt_qr < 0 || melt_qs < 0 || melt_qg < 0)) {
+        if (p->with_melting && !melt_vars) {
             ctx->err = "cpol_interp_subbeams: melting needs 1-moment rain, snow and graupel slots";
             return CPOL_ERR_ARG;
         }
@@ -2410,102 +2362,28 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
            O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N };
     const bool dev = p->outputs_on_device == 1;
     const bool async_host = p->outputs_on_device == 2;    // pinned host buffers, no wait
-    // the sub-beam sums by one thread per (gate, hydrometeor) with the 1-D table items evaluated in
-    // place (k_subbeam_sum); CPOL_SUBSUM=0: k_psd_lookup stores them and k_final walks the rows
-    const bool subsum_enabled = ctx->subsum != 0;     // (read when the context is created)
-    bool subsum = subsum_enabled;
-    {
-        bool any1d = false;
-        for (int j = 0; j < n_hyd; ++j) any1d = any1d || (ctx->its.t[j].tab && !ctx->its.t[j].two_d);
-        // (not with Doppler scheme 3: k_spec_atten reads every item's columns from res[]; with one
-        // sub-beam there is nothing to accumulate and the extra launch costs more than it saves)
-        subsum = subsum && any1d && !dop3;
-    }
-    // ... with fewer than 4 sub-beams k_final itself evaluates them in place (no extra launch, and
-    // k_psd_lookup no longer writes 96 B per item for k_final to read back)
-    // -- where that saves the k_psd_lookup launch altogether (no melting species, no Doppler sums from the tables: the
-    // C2 sweep 122 -> 119 us and 46 MB less traffic).  Where k_psd_lookup runs anyway it keeps storing the columns: the
-    // gathers inside the per-ray workgroups of k_final cost more than the stored rows (C3 sweep at 3 deg: 199 against
-    // 188 us; 512-thread workgroups held to 128 / 168 VGPRs: 138 / 159 us on the C2 sweep; round 4)
-    bool final_inplace = subsum && n_sub < 4;
-    for (int j = 0; j < n_hyd && final_inplace; ++j) {
-        const ItabDev &tj = ctx->its.t[j];
-        if (tj.tab && (tj.two_d || (doppler && tj.writes_vn))) final_inplace = false;
-    }
-    subsum = subsum && n_sub >= 4;
-    // The single-beam fast path (cpol_gate.inl): one sub-beam per radial and every slot on an integral table --
-    // k_gate1 takes a gate from its interpolated model values to its polarimetric variables in one kernel
-    // (k_classify + k_psd_lookup + the per-gate half of k_final), items outside the tables go to the integrating
-    // kernels as one-item work units without the counting sort.  CPOL_GATE1=0 (or CPOL_SUBSUM=0, debug reads, a
-    // slot without a table, Doppler scheme 3) keeps the general launch sequence; the results are bit-identical.
-    // Not with melting species: their 2-D blocks are walked by whole wavefronts, which inside this one fat kernel
-    // (six species in sequence per thread) is no faster than k_classify + k_psd_lookup, and the four idle
-    // launches of the integrating flavours cost more than the two bucket launches they replace (C3 sweep at
-    // 3 deg: 203 us this way against 188; the kernel handles them -- CPOL_GATE1=2 forces it, tests do).
-    const int gate1_env = ctx->gate1;
-    // (columns with given melting fields: k_classify's GIVEN form; the single-beam kernels diagnose melting themselves)
-    bool gate1 = gate1_env != 0 && subsum_enabled && n_sub == 1 && !ctx->keep_debug && !dop3 && !ml && !melt_given && !sub_out;
-    for (int j = 0; j < n_hyd && gate1; ++j)
-        gate1 = ctx->its.t[j].tab != nullptr && (gate1_env == 2 || !ctx->its.t[j].two_d);
-    if (gate1) final_inplace = true;       // (k_final's recomputed gates take the table items from their records)
-    if (gate1) {
+    if (f.gate1) {
         ENSURE(ctx->b_gscan, (size_t)3 * n_rg * sizeof(float));
         ENSURE(ctx->b_defer, (size_t)n_rg);
     }
-    // k_gate1_ray (cpol_gate.inl): the single-beam kernel with one wavefront per species, the ray's range scans by the
-    // workgroup that finishes the ray last and the items outside the tables integrated in place -- the sweep is
-    // k_interp_sweep + that kernel, no integrating launch, no k_final.  Only where the in-place integration mirrors the
-    // integrating kernels: gamma-family species without Doppler-scheme-2 sums and without per-ray fall-speed totals
-    // (numeric_intv), whose tables kept all panels but the tail (an item off the table costs a wavefront ~40 us:
-    // fine for the handful a volume has, not for a table that lost half of its panels to the accuracy gate).
-    const int g1r = ctx->gate1_ray >= 0 ? ctx->gate1_ray
-                  : ((ctx->parent ? ctx->parent->n_children : ctx->n_children) >= 2 ? 1 : 0);
-    bool gate1_ray = gate1 && g1r && !ctx->fuse_gate1 && !p->with_melting && !dop2 && n_rays <= 65535;
-    for (int j = 0; j < n_hyd && gate1_ray; ++j) {
-        const cpol_hydro_desc &d = ctx->hs.h[j].d;
-        const ItabDev &tj = ctx->its.t[j];
-        gate1_ray = d.psd_family == CPOL_PSD_GAMMA && !d.numeric_intv && d.q_source == CPOL_Q_MODEL && tj.tab && !tj.two_d &&
-                    ((tj.pan_lo == 0 && tj.pan_hi >= tj.n_pan - 2) || g1r >= 2) && ctx->hs.h[j].pre && ctx->hs.h[j].dnu;
-    }
-    {
-        const long g1_waves = n_rg * n_hyd / 64 / 1024;
-        gate1_ray = gate1_ray && (ctx->gate1_species == 2 || (ctx->gate1_species == 1 && g1_waves < 48));
-    }
-    if (gate1_ray && CPOL_GATE1_PRESENT) {
+    if (f.gate1_ray && CPOL_GATE1_PRESENT) {
         // (the presence words: every one "anything may be here" until k_interp_sweep has written it -- a wavefront none of whose gates
         // exists leaves its word alone)
         void *const was = ctx->b_present.p;
         ENSURE(ctx->b_present, (size_t)n_rays * cdiv(ng, 64) * sizeof(unsigned));
         if (ctx->b_present.p != was) HIPCHK(hipMemsetAsync(ctx->b_present.p, 0xFF, ctx->b_present.cap, ctx->stream));
     }
-    if (gate1_ray && g1r == 3) {
+    if (f.gate1_ray && f.g1r == 3) {
         void *const was = ctx->b_ticket.p;
         ENSURE(ctx->b_ticket, (size_t)n_rays * sizeof(int));
         if (ctx->b_ticket.p != was || was_dirty)                 // (the kernel leaves every ticket at 0 behind it)
             HIPCHK(hipMemsetAsync(ctx->b_ticket.p, 0, ctx->b_ticket.cap, ctx->stream));
     }
-    // Every slot on an integral table: the items outside the tables (a handful per volume) are listed directly as
-    // one-item work units by k_classify / k_gate1 -- key in b_pos, gate in b_perm, count in b_totals -- and the
-    // counting sort (LDS ranking in k_classify, k_bucket_scan, k_bucket_scatter) is not run at all.  CPOL_RARE_DIRECT=0,
-    // debug reads (bucket counts) or a slot without a table keep the sort: with EVERY item integrated one item per
-    // work unit would waste 63 of 64 lanes.
-    bool rare_direct = gate1 || (ctx->rare_direct != 0 && !ctx->keep_debug);
-    for (int j = 0; j < n_hyd && rare_direct; ++j) rare_direct = ctx->its.t[j].tab != nullptr;
-    if (rare_direct) unit_cap = (long)n_hyd * n_sbg;           // (virtual units: no b_units entries are written)
+    if (f.rare_direct) unit_cap = (long)n_hyd * n_sbg;           // (virtual units: no b_units entries are written)
     else ENSURE(ctx->b_units, (size_t)unit_cap * sizeof(WorkUnit));
-    const bool want_szi = ctx->keep_debug || subsum;
+    const bool want_szi = ctx->keep_debug || f.subsum;
     if (want_szi) ENSURE(ctx->b_szinteg, (size_t)n_rg * n_hyd * CPOL_N_SZ * sizeof(float));
-    const bool want_szt = out->sz_total != nullptr || ctx->keep_debug;
-    const bool want_model = p->integrate_model && out->model_vars;
-    // every slot on a table, no debug reads: the gate kernel classifies its gates itself (k_interp_classify,
-    // cpol_fused.inl)
-    // (never for columns: the forms that interpolate, k_interp_classify and k_interp_gate1, are replaced by k_columns_ingest)
-    const bool fused = ctx->fuse_classify != 0 && rare_direct && !gate1 && !ml && !dop3 && !ctx->keep_debug && !cols && !sub_out && !mem;
-    // k_interp_gate1 (CPOL_FUSE_GATE1=1, not the default): the single-beam kernel interpolates its gates too.  Measured: the
-    // isolated C2 sweep 95.4 -> 88.6 us (one lane back to back: 70 -> 62 us per sweep), but with three lanes in flight 42.2 ->
-    // 44.8 us per sweep, and the Ku swath of config 5 (9 800 rays) 0.93 -> 1.18 ms: at the 3 wavefronts per SIMD k_gate1 needs,
-    // the interpolation -- VALU-bound at 5 -- loses more than the saved launch and the 14 MB of vals[] give back.
-    const bool fused_gate1 = ctx->fuse_gate1 != 0 && gate1 && !cols && !mem;
+    const bool want_szt = f.want_szt, want_model = fi.want_model;
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
@@ -2533,22 +2411,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // ONE device-to-host copy moves it (instead of up to 18 copies of a few hundred KB each)
     char *win_lo = nullptr, *win_hi = nullptr;
     size_t win_sum = 0;
-    if (async_host && !ctx->keep_debug)
-        for (int k = 0; k < O_N; ++k) {
-            if (!produced[k] || !user_out[k]) continue;
-            char *a = (char *)user_out[k];
-            if (!win_lo || a < win_lo) win_lo = a;
-            if (!win_hi || a + obytes[k] > win_hi) win_hi = a + obytes[k];
-            win_sum += obytes[k];
-        }
-    if (async_host && !ctx->keep_debug)                       // (the superobservation arrays count like every other array)
-        for (int k = 0; k < SO_N; ++k) {
-            if (!so_pl.user[k]) continue;
-            char *a = (char *)so_pl.user[k];
-            if (!win_lo || a < win_lo) win_lo = a;
-            if (!win_hi || a + so_pl.bytes[k] > win_hi) win_hi = a + so_pl.bytes[k];
-            win_sum += so_pl.bytes[k];
-        }
+    if (async_host && !ctx->keep_debug) {
+        for (int k = 0; k < O_N; ++k)
+            if (produced[k] && user_out[k]) window_add(user_out[k], obytes[k], win_lo, win_hi, win_sum);
+        for (int k = 0; k < SO_N; ++k)                        // (the superobservation arrays count like every other array)
+            if (so_pl.user[k]) window_add(so_pl.user[k], so_pl.bytes[k], win_lo, win_hi, win_sum);
+    }
     const bool window = win_lo && (size_t)(win_hi - win_lo) <= win_sum + win_sum / 4 + 4096;
     // (the device image keeps the window's alignment modulo 64 B, so that every array of the image is
     // aligned exactly like its host counterpart: a float32 array at an address 4 mod 8 followed by a
@@ -2589,6 +2457,19 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_T0], st));
     }
 
+    const auto ml_args = [&]() {            // k_ml_weights (on the values before melting), for the sweep and for the sub-beam export
+        MlArgs ma{};
+        ma.vals = (const float *)ctx->b_vals.p;
+        ma.sub_w = (const double *)ctx->v_subw;
+        ma.sub_smooth = (const int *)ctx->v_subsmooth;
+        ma.taps = (const double *)ctx->v_mlfilter;
+        ma.wgate = (double *)ctx->b_wgate.p;
+        ma.n_sbg = n_sbg; ma.n_sub = n_sub; ma.n_gates = ng; ma.radius = t->ml_radius;
+        ma.with_melting = p->with_melting;
+        ma.var_qr = f.melt_qr; ma.var_qs = f.melt_qs; ma.var_qg = f.melt_qg;
+        return ma;
+    };
+
     // The launch sequence of a sweep.  Opt-in (CPOL_USE_GRAPH=1): with device outputs and
     // nothing to upload it is captured into a HIP graph and replayed while the arguments stay
     // the same (one graph launch instead of ten kernel launches).
@@ -2598,10 +2479,10 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         HIPCHK(hipMemcpyAsync(ctx->b_traj.p, t->paths, (size_t)geo_rays * n_v * 3 * ng * sizeof(float),
                               hipMemcpyHostToDevice, st));
     }
-    if (ray_prep || (ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols)) {
+    if (f.traj_launch) {
         // ray paths + per-ray constants ahead of the sweep kernel (and the parity access to the paths,
         // cpol_debug_read "traj"): same device functions as the in-place evaluation
-        const bool paths = mode != CPOL_GEOM_HOST_PATHS && (prep_paths || ctx->keep_debug);
+        const bool paths = f.traj_paths;
         TrajArgs ta{};
         ta.ray_traj = (const double *)ctx->v_traj_in;
         ta.site = t->site ? (const double *)ctx->v_site : nullptr;
@@ -2610,9 +2491,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ta.range0 = p->range0; ta.range_step = p->range_step;
         ta.ke = p->ke; ta.re = p->re; ta.alt = p->radar_alt;
         ta.geo = (const double *)ctx->v_geo;
-        ta.ray_const = ray_prep ? (double *)ctx->b_rayc.p : nullptr;
+        ta.ray_const = f.ray_prep ? (double *)ctx->b_rayc.p : nullptr;
         ta.n_h = n_h; ta.lon1 = p->radar_lon;
-        if (geo_poly) {
+        if (f.geo_poly) {
             ta.poly = (double *)ctx->b_poly.p;
             ta.poly_M = (const double *)ctx->d_geoM.p;
             ta.poly_scale = geo_poly_scale;
@@ -2624,8 +2505,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
 
     // ---- 2. gate interpolation ----
     InterpArgs ia{};
-    ia.traj = (mode == CPOL_GEOM_HOST_PATHS || prep_paths) ? (const float *)ctx->b_traj.p : nullptr;
-    ia.ray_const = ray_prep ? (const double *)ctx->b_rayc.p : nullptr;
+    ia.traj = (mode == CPOL_GEOM_HOST_PATHS || f.prep_paths) ? (const float *)ctx->b_traj.p : nullptr;
+    ia.ray_const = f.ray_prep ? (const double *)ctx->b_rayc.p : nullptr;
     ia.rp.ray_traj = (const double *)ctx->v_traj_in;
     ia.rp.site = t->site ? (const double *)ctx->v_site : nullptr;
     ia.rp.n_v = n_v; ia.rp.mode = mode;
@@ -2653,19 +2534,16 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ia.site = t->site ? (const double *)ctx->v_site : nullptr;
     ia.exact_sub = (p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS) ? 1 : 0;
     // (the one sub-beam of a single-beam sweep: the polynomials of its table set, unless its float64 coordinates are outputs)
-    const bool poly_central = poly_single;
-    if (poly_central && !ctx->keep_debug && !user_out[O_LAT] && !user_out[O_LON]) ia.lats = ia.lons = nullptr;   // (nobody reads the library's own copies)
-    ia.poly = geo_poly ? (const double *)ctx->b_poly.p : poly_central ? (const double *)set->poly.p : nullptr;
-    ia.poly_scale = (geo_poly || poly_central) ? geo_poly_scale : 0.0;
-    ia.poly_central = poly_central ? 1 : 0;
-    static const int use_present = getenv("CPOL_GATE1_PRESENT") ? atoi(getenv("CPOL_GATE1_PRESENT")) : 1;
-    if (gate1_ray && use_present && CPOL_GATE1_PRESENT && !cols && !mem) {      // (columns, members: no presence words are written)
+    if (f.drop_latlon) ia.lats = ia.lons = nullptr;
+    ia.poly = f.geo_poly ? (const double *)ctx->b_poly.p : f.poly_single ? (const double *)set->poly.p : nullptr;
+    ia.poly_scale = (f.geo_poly || f.poly_single) ? geo_poly_scale : 0.0;
+    ia.poly_central = f.poly_single ? 1 : 0;
+    if (f.present && CPOL_GATE1_PRESENT) {
         ia.present = (unsigned *)ctx->b_present.p;
         ia.n_pres = n_hyd;
         for (int j = 0; j < n_hyd; ++j) ia.pres_var[j] = ctx->hs.h[j].d.var_q;
     }
     ctx->last_poly_central = ia.poly_central;
-    static const int exp_skip_interp = getenv("CPOL_EXP_SKIP") ? (atoi(getenv("CPOL_EXP_SKIP")) & 1) : 0;
     if (cols) {
         // ---- 2'. the caller's columns instead of the interpolation ----
         const void *src[CPOL_MAX_VARS + 6];
@@ -2711,15 +2589,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             hipLaunchKernelGGL(k_interp_timed, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma, tg);
         } else
         hipLaunchKernelGGL(k_interp_members, dim3((unsigned)(geo_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ia, ma);
-    } else if (!fused && !fused_gate1 && !exp_skip_interp) {
-        // A launch that is plain k_interp_sweep, of a single beam whose float32 grid coordinates alone are wanted, under a caller's
-        // version tag: the gate stencil of its (geometry, heights) pair -- noted at first sight, recorded at the second, replayed from
-        // the third on (cpol_interp.inl).  Everything else keeps k_interp_sweep.
+    } else if (f.plain_interp) {
+        // (the gate stencil of the (geometry, heights) pair where the rules allow it, cpol_forms.h: noted at first sight, recorded at
+        // the second, replayed from the third on)
         int form = 0;
         StencilDev sd{};
         StencilEntry *made = nullptr;
-        if (n_sub == 1 && !sub_out && !ia.traj && !ia.lats && !ia.lons && !ia.coords && t->version != 0 && !ctx->use_graph &&
-            ctx->model.nz < 32768) {
+        if (f.stencil) {
             StencilKey key;
             memset(&key, 0, sizeof key);
             key.version = t->version;
@@ -2738,7 +2614,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         } else hipLaunchKernelGGL(k_interp_sweep, grid, dim3(256), 0, st, ctx->model, ia);
         ctx->last_stencil = form;
     }
-    if (tm && !fused && !fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
+    if (tm && !f.fused && !f.fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
     if (sub_out) {
         // ---- 2''. cpol_interp_subbeams: geometry of every sub-beam, 'ml' weights, melting, copies; no scattering ----
         InterpArgs ix = ia;
@@ -2758,21 +2634,10 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         xa.elev = (float *)(xg + 2 * xa8 + 2 * xa4);
         signed char *const mlmask = (signed char *)(xg + 2 * xa8 + 3 * xa4);
         hipLaunchKernelGGL(k_interp_export, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ix, xa);
-        if (ml) {                                 // (on the values before melting, as in the sweep)
-            MlArgs ma{};
-            ma.vals = (const float *)ctx->b_vals.p;
-            ma.sub_w = (const double *)ctx->v_subw;
-            ma.sub_smooth = (const int *)ctx->v_subsmooth;
-            ma.taps = (const double *)ctx->v_mlfilter;
-            ma.wgate = (double *)ctx->b_wgate.p;
-            ma.n_sbg = n_sbg; ma.n_sub = n_sub; ma.n_gates = ng; ma.radius = t->ml_radius;
-            ma.with_melting = p->with_melting;
-            ma.var_qr = melt_qr; ma.var_qs = melt_qs; ma.var_qg = melt_qg;
-            hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ma);
-        }
-        if (sub_melt)
+        if (ml) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ml_args());
+        if (f.sub_melt)
             hipLaunchKernelGGL(k_melt_subbeams, dim3((unsigned)cdiv(n_sbg, 256)), dim3(256), 0, st, (float *)ctx->b_vals.p, n_sbg,
-                               melt_qr, melt_qs, melt_qg, (float *)ctx->b_qmelt.p, (double *)ctx->b_fwmelt.p, mlmask);
+                               f.melt_qr, f.melt_qs, f.melt_qg, (float *)ctx->b_qmelt.p, (double *)ctx->b_fwmelt.p, mlmask);
         const hipMemcpyKind kind = sub_out->outputs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         struct Cp { void *dst; const void *src; size_t bytes; };
         const Cp cps[11] = {
@@ -2783,9 +2648,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             {sub_out->lons, xa.lons, (size_t)n_sbg * sizeof(double)},
             {sub_out->dist, xa.dist, (size_t)n_sbg * sizeof(float)},
             {sub_out->heights, xa.heights, (size_t)n_sbg * sizeof(float)},
-            {sub_melt ? sub_out->q_melt : nullptr, ctx->b_qmelt.p, (size_t)2 * n_sbg * sizeof(float)},
-            {sub_melt ? sub_out->fw_melt : nullptr, ctx->b_fwmelt.p, (size_t)2 * n_sbg * sizeof(double)},
-            {sub_melt ? sub_out->mask_ml : nullptr, mlmask, (size_t)n_sbg},
+            {f.sub_melt ? sub_out->q_melt : nullptr, ctx->b_qmelt.p, (size_t)2 * n_sbg * sizeof(float)},
+            {f.sub_melt ? sub_out->fw_melt : nullptr, ctx->b_fwmelt.p, (size_t)2 * n_sbg * sizeof(double)},
+            {f.sub_melt ? sub_out->mask_ml : nullptr, mlmask, (size_t)n_sbg},
             {ml ? sub_out->wgate : nullptr, ctx->b_wgate.p, (size_t)n_sbg * sizeof(double)},
         };
         for (const Cp &c : cps)
@@ -2837,24 +2702,15 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             ctx->err = "cpol_run_sweep: simulate_doppler needs var_u / var_v / var_w";
             return CPOL_ERR_ARG;
         }
-        for (int j = 0; j < n_hyd && !dop3; ++j) {
-            const cpol_hydro_desc &d = ctx->hs.h[j].d;
-            // 1: vn[] per gate -- written by the PSD stage (scheme 2, melting species) or, for the analytic
-            // moments of the gamma species under scheme 1, by k_classify; 2: summed over the ray (1-moment
-            // ice, numeric integrate_V) and credited to the first valid gate
-            fa.vsrc[j] = (dop2 || d.psd_family == CPOL_PSD_MELTING) ? 1
-                       : (d.psd_family == CPOL_PSD_ICE_FIELD || d.numeric_intv) ? 2 : 1;
-        }
+        for (int j = 0; j < n_hyd; ++j) fa.vsrc[j] = f.vsrc[j];
     }
 
-    fa.eval_1d = final_inplace ? 1 : 0;
+    fa.eval_1d = f.final_inplace ? 1 : 0;
     fa.rec = (const double2 *)ctx->b_rec.p;
     for (int j = 0; j < n_hyd; ++j) fa.key_base[j] = ctx->hs.h[j].key_base;
-    bool any_vsrc2 = false;
-    for (int j = 0; j < n_hyd; ++j) any_vsrc2 = any_vsrc2 || (doppler && !dop3 && fa.vsrc[j] == 2);
-    if (gate1) {
+    if (f.gate1) {
         fa.pre_gate = 1;
-        fa.ice_redo = any_vsrc2 ? 1 : 0;
+        fa.ice_redo = f.any_vsrc2 ? 1 : 0;
         fa.defer = (const unsigned char *)ctx->b_defer.p;
         fa.sk = (const float *)ctx->b_gscan.p;
         fa.sh = fa.sk + n_rg;
@@ -2875,7 +2731,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ca.n_sbg = n_sbg;
     ca.present = ia.present;              // (k_gate1_ray: the presence words k_interp_sweep has just written)
     ca.with_melting = p->with_melting;
-    ca.var_qr = ca.var_qs = ca.var_qg = -1;
+    ca.var_qr = f.melt_qr; ca.var_qs = f.melt_qs; ca.var_qg = f.melt_qg;
     ca.doppler = doppler ? 1 : 0;
     ca.tfun_snow = ctx->tfun[CPOL_TFUN_SNOW_N0];
     ca.tfun_ice = ctx->tfun[CPOL_TFUN_ICE_MOM2_A];
@@ -2887,63 +2743,27 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ca.vmask = (unsigned char *)ctx->b_vmask.p;
     ca.vn = (doppler && !dop2 && !dop3) ? (double *)ctx->b_vn.p : nullptr;     // analytic moments (Doppler scheme 1)
     ca.keep_par = (ctx->keep_debug || dop3) ? 1 : 0;
-    if (rare_direct) {
+    if (f.rare_direct) {
         ca.rare_key = (int *)ctx->b_pos.p;
         ca.rare_perm = (int *)ctx->b_perm.p;
         ca.rare_totals = (unsigned long long *)tot_p;
     }
-    // k_psd_lookup's workgroups first list the tiles among their own that hold a species with a 2-D table (LookupArgs::tile_scan):
-    // when the lookup walks tiles and has nothing but the 2-D tables to evaluate, from 262 144 tiles on (C4 volume, 735 000 tiles:
-    // 1.30 -> 1.20 ms; its share of 1/8, 92 000 tiles: 247 -> 239-257 us, nothing gained.  Measured and dropped on the way: the
-    // list in global memory, made by k_interp_classify with one bit per tile and an atomicOr per item -- lookup 1.30 -> 1.09 ms
-    // and 239 -> 205 us, but the classification 3.24 -> 4.31 ms: device-scope atomics; made by a kernel of its own with one
-    // atomicAdd per wavefront and pass -- the same lookup times, and 244 / 51 us for that kernel: one address, ~11 ns per atomic)
-    static const int tile_env = getenv("CPOL_LOOKUP_TILE") ? atoi(getenv("CPOL_LOOKUP_TILE")) : 1;
-    constexpr int TILE_GATES = 1 << CPOL_TILE_GATES_LOG2, TILE_RAYS = 64 >> CPOL_TILE_GATES_LOG2;
-    bool use_tile_list = false;
-    const long n_tiles = (long)cdiv(n_rays, TILE_RAYS) * n_sub * cdiv(ng, TILE_GATES);
-    if (ctx->lookup_list && rare_direct && !gate1 && tile_env && n_rays >= TILE_RAYS && (subsum || final_inplace) && (n_tiles >= 262144 || ctx->lookup_list == 2) && n_tiles < (1L << 31)) {
-        bool any_2d = false, other = false;
-        for (int j = 0; j < n_hyd; ++j) {
-            const ItabDev &tj = ctx->its.t[j];
-            if (!tj.tab) continue;
-            if (tj.two_d) any_2d = true;
-            else if ((dop3 && ctx->hs.h[j].d.psd_family == CPOL_PSD_ICE_FIELD) || (final_inplace && doppler && tj.writes_vn)) other = true;
-        }
-        use_tile_list = any_2d && !other;
-    }
-    for (int j = 0; j < n_hyd; ++j) {
-        const cpol_hydro_desc &d = ctx->hs.h[j].d;
-        if (d.q_source != CPOL_Q_MODEL) continue;
-        if (d.rule == CPOL_RULE_RAIN_1MOM) ca.var_qr = d.var_q;
-        if (d.rule == CPOL_RULE_SNOW_1MOM) ca.var_qs = d.var_q;
-        if (d.rule == CPOL_RULE_GRAUPEL_1MOM) ca.var_qg = d.var_q;
-    }
-    if (p->with_melting && (ca.var_qr < 0 || ca.var_qs < 0 || ca.var_qg < 0)) {
+    if (p->with_melting && !melt_vars) {
         ctx->err = "cpol_run_sweep: melting needs 1-moment rain, snow and graupel slots";
         return CPOL_ERR_ARG;
     }
     if (ml) {
-        MlArgs ma{};
-        ma.vals = (const float *)ctx->b_vals.p;
-        ma.sub_w = (const double *)ctx->v_subw;
-        ma.sub_smooth = (const int *)ctx->v_subsmooth;
-        ma.taps = (const double *)ctx->v_mlfilter;
-        ma.wgate = (double *)ctx->b_wgate.p;
-        ma.n_sbg = n_sbg; ma.n_sub = n_sub; ma.n_gates = ng; ma.radius = t->ml_radius;
-        ma.with_melting = p->with_melting;
-        ma.var_qr = ca.var_qr; ma.var_qs = ca.var_qs; ma.var_qg = ca.var_qg;
-        if (!cols) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ma);     // (columns: ingested)
+        if (!cols) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ml_args());     // (columns: ingested)
         ca.wgate = (const double *)ctx->b_wgate.p;
     }
     // the variables later kernels read: U, V, W (the Doppler terms); all of them for the integrated model variables
     ia.store_mask = want_model ? 0xffffffffu : 0u;
     if (doppler) ia.store_mask |= (1u << p->var_u) | (1u << p->var_v) | (1u << p->var_w);
-    if (fused) {
+    if (f.fused) {
         hipLaunchKernelGGL(k_interp_classify, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256),
                            (size_t)n_vars * 256 * sizeof(float), st, ctx->model, ia, ctx->hs, ctx->its, ca);
         if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
-    } else if (gate1) {
+    } else if (f.gate1) {
         GateArgs ga{};
         ga.sk = (float *)ctx->b_gscan.p;
         ga.sh = ga.sk + n_rg;
@@ -2953,22 +2773,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ga.perm = (int *)ctx->b_perm.p;
         ga.totals = (unsigned long long *)tot_p;
         ga.res = (double *)ctx->b_res.p;
-        ga.store_items = any_vsrc2 ? 1 : 0;
+        ga.store_items = f.any_vsrc2 ? 1 : 0;
         ga.analytic_vn = ca.vn ? 1 : 0;
         if (doppler) ca.vn = (double *)ctx->b_vn.p;        // (also the table-borne sums of a species summed over the ray)
-        bool melt_tab = false;
-        for (int j = 0; j < n_hyd; ++j) melt_tab = melt_tab || ctx->its.t[j].two_d;
+        const bool melt_tab = f.any_2d, fused_gate1 = f.fused_gate1;
         const dim3 ggrid((unsigned)n_rays, cdiv(ng, CPOL_GATE1_THREADS));
         const size_t glds = (size_t)n_vars * CPOL_GATE1_THREADS * sizeof(float);
-        // one wavefront per species (k_gate1_species) where no melting species and no per-ray fall-speed sums are involved
-        // -- for small launches: the C2 sweep (8 wavefronts per SIMD) 33.6 -> 30.7 us and 42.9 -> 39.2 us per sweep with three
-        // lanes in flight; the C5 Ku swath (235 per SIMD, five species) 429 -> 674 us: every species' wavefront repeats the
-        // gate's loads and wavefronts 1.. idle while wavefront 0 finishes the gates; five C2 sweeps as one sequence (44 per
-        // SIMD) 112 -> 100 us (CPOL_GATE1_SPECIES=0 / 2: never / always)
-        const long g1_waves_per_simd = n_rg * n_hyd / 64 / 1024;
-        const bool by_species = (ctx->gate1_species == 2 || (ctx->gate1_species == 1 && g1_waves_per_simd < 48)) &&
-                                !fused_gate1 && !melt_tab && !ga.store_items && !p->with_melting;
-        if (gate1_ray && by_species) {
+        if (f.gate1_ray) {
             // the whole rest of the sweep in this launch: no integrating kernels, no k_final
             ga.ticket = (int *)ctx->b_ticket.p;
             ScanRayArgs rr{};
@@ -2979,17 +2790,15 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             const size_t lds_terms = (size_t)n_hyd * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES), lds_scan = (size_t)3 * ng * sizeof(float);
             const dim3 rgrid((unsigned)cdiv(ng, 64), (unsigned)n_rays);
             const dim3 tgrid((unsigned)gate1_tiles(n_rays, ng).n_blocks);      // k_gate1_ray: ray x gate tiles (cpol_tile.h)
-            if (g1r == 3) {
+            if (f.g1r == 3) {
                 hipLaunchKernelGGL(k_gate1_ray_scan, rgrid, dim3(64 * n_hyd), lds_terms > lds_scan ? lds_terms : lds_scan, st,
                                    ctx->hs, ctx->its, ca, fa, ga, rr);
             } else {
-                // (CPOL_EXP_SKIP, timing experiments only -- wrong results: bit 0 the gate interpolation, bit 1 this kernel, bit 2 the scans)
-                static const int exp_skip = getenv("CPOL_EXP_SKIP") ? atoi(getenv("CPOL_EXP_SKIP")) : 0;
-                if (!(exp_skip & 2))
+                if (!(pk.exp_skip & 2))
                 hipLaunchKernelGGL(k_gate1_ray, tgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr);
                 if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
                 if (tm_psd) { HIPCHK(hipEventRecord(ctx->ev[EV_BUCKET], st)); HIPCHK(hipEventRecord(ctx->ev[EV_PSD], st)); }
-                if (!(exp_skip & 4))
+                if (!(pk.exp_skip & 4))
                 hipLaunchKernelGGL(k_scan_rays, dim3((unsigned)n_rays), dim3(256), lds_scan, st, fa, ga, rr);
                 if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_FINAL], st));
                 HIPCHK(hipGetLastError());
@@ -3001,7 +2810,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             HIPCHK(hipGetLastError());
             return CPOL_OK;
         }
-        if (by_species) hipLaunchKernelGGL(k_gate1_species, dim3((unsigned)cdiv(n_rg, 64)), dim3(64 * n_hyd),
+        if (f.by_species) hipLaunchKernelGGL(k_gate1_species, dim3((unsigned)cdiv(n_rg, 64)), dim3(64 * n_hyd),
                                            (size_t)n_hyd * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES), st, ctx->hs, ctx->its, ca, fa, ga);
         else if (fused_gate1 && melt_tab) hipLaunchKernelGGL((k_interp_gate1<true>), ggrid, dim3(CPOL_GATE1_THREADS), glds, st,
                                                         ctx->model, ia, ctx->hs, ctx->its, ca, fa, ga);
@@ -3038,15 +2847,11 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                             (d.psd_family == CPOL_PSD_MELTING && d.tab_degree == CPOL_MELT_DEGREE) ||
                             (d.psd_family == CPOL_PSD_ICE_FIELD && d.uniform_grid && d.tab_degree == CPOL_ICE_DEGREE)) ? 7 : 6;
     }
-    // (Measured and dropped: this chain -- scan, scatter, the integrating kernels, all idle when every item lies
-    // on a table -- on a sibling stream beside k_psd_lookup, forked and joined with events: the isolated C2 sweep
-    // 122 -> 135 us, the C3 volume 468 -> 476 us, the 225-ray C4 share 1.568 -> 1.553 ms: a cross-stream event
-    // costs the device about as much as the three idle launches it would hide.)
-    if (!rare_direct)
+    if (!f.rare_direct)
     hipLaunchKernelGGL(k_bucket_scan, dim3(1), dim3(1024), 0, st, sa);
     // (a fixed grid: the workgroups stride over the k_classify gate ranges and skip the empty ones)
     const long n_cblk = cdiv(n_sbg, CPOL_CLASSIFY_THREADS);
-    if (!rare_direct)
+    if (!f.rare_direct)
     hipLaunchKernelGGL(k_bucket_scatter, dim3((unsigned)(n_cblk < 2048 ? n_cblk : 2048)), dim3(256), 0, st,
                        (const int *)ctx->b_key.p, (const int *)ctx->b_pos.p,
                        (int *)ctx->b_perm.p, (const int *)ctx->b_blkranked.p,
@@ -3054,69 +2859,44 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     if (tm_psd) HIPCHK(hipEventRecord(ctx->ev[EV_BUCKET], st));
 
     // ---- 5a. items on an integral table: 15 x 11 coefficients gathered, no diameter-bin loop ----
-    bool rare_forked = false;           // k_psd_rare goes to a sibling stream that forked in front of k_psd_lookup
-    {
-        bool any = false;
-        for (int j = 0; j < n_hyd; ++j) any = any || ctx->its.t[j].tab != nullptr;
-        if (any) {
-            LookupArgs la{};
-            la.key = (const int *)ctx->b_key.p;
-            la.vmask = (const unsigned char *)ctx->b_vmask.p;
-            la.rec = (const double2 *)ctx->b_rec.p;
-            la.par = (const double *)ctx->b_par.p;
-            la.par_w = dop3 ? (double *)ctx->b_par.p : nullptr;
-            la.res = (double *)ctx->b_res.p;
-            la.vn = doppler ? (double *)ctx->b_vn.p : nullptr;
-            la.n_sbg = n_sbg;
-            la.skip_res_1d = (subsum || final_inplace) ? 1 : 0;
-            la.vn_1d = final_inplace ? 1 : 0;
-            bool launch = !(subsum || final_inplace);   // with k_subbeam_sum / in-place evaluation in k_final: only for 2-D tables, Doppler sums and the ice intercept
-            for (int j = 0; j < n_hyd && !launch; ++j) {
-                const ItabDev &tj = ctx->its.t[j];
-                if (!tj.tab) continue;
-                launch = tj.two_d || (la.par_w && ctx->hs.h[j].d.psd_family == CPOL_PSD_ICE_FIELD) ||
-                         (final_inplace && la.vn && tj.writes_vn);      // (k_subbeam_sum evaluates the Doppler sums itself)
+    if (f.any_tab) {
+        LookupArgs la{};
+        la.key = (const int *)ctx->b_key.p;
+        la.vmask = (const unsigned char *)ctx->b_vmask.p;
+        la.rec = (const double2 *)ctx->b_rec.p;
+        la.par = (const double *)ctx->b_par.p;
+        la.par_w = dop3 ? (double *)ctx->b_par.p : nullptr;
+        la.res = (double *)ctx->b_res.p;
+        la.vn = doppler ? (double *)ctx->b_vn.p : nullptr;
+        la.n_sbg = n_sbg;
+        la.skip_res_1d = (f.subsum || f.final_inplace) ? 1 : 0;
+        la.vn_1d = f.final_inplace ? 1 : 0;
+        la.tile = f.lookup_tile ? 1 : 0;
+        la.n_rays = n_rays; la.n_sub = n_sub; la.n_gates = ng;
+        la.split = f.lookup_split;
+        long grid_x = cdiv(la.tile ? f.n_tiles * 64 : n_sbg, CPOL_LOOKUP_THREADS);
+        if (f.use_tile_list && la.tile) {
+            // a fixed grid walks the list: workgroups that own many tiles each: the chip filled `fill` times over (5 wavefronts per SIMD
+            // resident), a workgroup's list never longer than its LDS array
+            la.tile_scan = 1;
+            la.n_tiles = f.n_tiles;
+            for (int j = 0; j < n_hyd; ++j) if (ctx->its.t[j].tab && ctx->its.t[j].two_d) la.species2d |= 1u << j;
+            const long cap_wg = std::max<long>(pk.lookup_fill * 1024 * 5 * CPOL_WAVE / CPOL_LOOKUP_THREADS, cdiv(f.n_tiles, CPOL_LOOKUP_LIST_CAP));
+            if (grid_x > cap_wg) grid_x = cap_wg;
+        }
+        if (f.lookup_launch) {
+            if (f.rare_fork) {             // k_psd_rare, below, goes to a sibling stream that forks HERE and joins before the sub-beam sums
+                if (!ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+                HIPCHK(hipEventRecord(ctx->ev_fork, st));
             }
-            bool two_d = false;
-            for (int j = 0; j < n_hyd; ++j) two_d = two_d || (ctx->its.t[j].tab && ctx->its.t[j].two_d);
-            la.tile = (two_d && tile_env && n_rays >= TILE_RAYS) ? 1 : 0;
-            la.n_rays = n_rays; la.n_sub = n_sub; la.n_gates = ng;
-            const long n_thr = la.tile ? (long)cdiv(n_rays, TILE_RAYS) * n_sub * cdiv(ng, TILE_GATES) * 64 : n_sbg;
-            // few wavefronts (a single sweep with one sub-beam): the walk of the busiest tile is the kernel's duration;
-            // its distinct blocks and species are dealt to `split` wavefronts (CPOL_LOOKUP_SPLIT=<n>; default by launch size)
-            const long lookup_waves_per_simd = n_thr / 64 / 1024;
-            la.split = ctx->lookup_split > 0 ? ctx->lookup_split : (la.tile && lookup_waves_per_simd < 16) ? 4 : 1;
-            long grid_x = cdiv(n_thr, CPOL_LOOKUP_THREADS);
-            if (use_tile_list && la.tile) {
-                // a fixed grid walks the list: enough wavefronts to fill the chip three times over (5 per SIMD resident), never more than tiles
-                // workgroups that own many tiles each: the chip filled `fill` times over (5 wavefronts per SIMD resident), a workgroup's
-                // list never longer than its LDS array
-                la.tile_scan = 1;
-                la.n_tiles = n_tiles;
-                for (int j = 0; j < n_hyd; ++j) if (ctx->its.t[j].tab && ctx->its.t[j].two_d) la.species2d |= 1u << j;
-                static const long fill = getenv("CPOL_LOOKUP_FILL") ? atol(getenv("CPOL_LOOKUP_FILL")) : 12;      // (C4 volume, 1 / 3 / 6 / 12 / 24 / 48: 1.28 / 1.25 / 1.24 / 1.20 / 1.23 / 1.26 ms)
-                const long cap_wg = std::max<long>(fill * 1024 * 5 * CPOL_WAVE / CPOL_LOOKUP_THREADS, cdiv(n_tiles, CPOL_LOOKUP_LIST_CAP));
-                if (grid_x > cap_wg) grid_x = cap_wg;
-            }
-            if (launch && !gate1) {
-                // the items outside the tables (k_psd_rare, below) and the 2-D table items (here) are disjoint and both wait for
-                // the classification alone: k_psd_rare goes to a sibling stream that forks HERE and joins before the sub-beam
-                // sums -- its one busy workgroup (69-80 us for a single item of the C4 volume) runs beside the lookup
-                if (ctx->rare_overlap && rare_direct && ctx->psd_rare && !ctx->use_graph && !ctx->keep_debug) {
-                    if (!ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-                    HIPCHK(hipEventRecord(ctx->ev_fork, st));
-                    rare_forked = true;
-                }
-                hipLaunchKernelGGL(k_psd_lookup, dim3((unsigned)grid_x, la.split), dim3(CPOL_LOOKUP_THREADS), 0, st, ctx->hs, ctx->its, la);
-            }
+            hipLaunchKernelGGL(k_psd_lookup, dim3((unsigned)grid_x, la.split), dim3(CPOL_LOOKUP_THREADS), 0, st, ctx->hs, ctx->its, la);
         }
     }
-
 
     // ---- 5. PSD x scattering table: one launch per kernel flavour present ----
     {
         PsdArgs pa{};
-        pa.unit_key = rare_direct ? (const int *)ctx->b_pos.p : nullptr;
+        pa.unit_key = f.rare_direct ? (const int *)ctx->b_pos.p : nullptr;
         pa.units = (const WorkUnit *)ctx->b_units.p;
         pa.totals = tot_p;
         pa.perm = (const int *)ctx->b_perm.p;
@@ -3126,52 +2906,23 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         pa.n_sbg = n_sbg;
         pa.par_w = dop3 ? (double *)ctx->b_par.p : nullptr;
         pa.clk = nullptr;
-        static const int ice_force_sum = getenv("CPOL_ICE_FORCE_SUM") ? atoi(getenv("CPOL_ICE_FORCE_SUM")) : 0;
-        pa.ice_force_sum = ice_force_sum;
+        pa.ice_force_sum = pk.ice_force_sum;
         if (ctx->keep_debug) {
             ENSURE(ctx->b_clk, 2048 * 4 * sizeof(long long));
             HIPCHK(hipMemsetAsync(ctx->b_clk.p, 0, 2048 * 4 * sizeof(long long), st));
             pa.clk = (long long *)ctx->b_clk.p;
         }
-        bool need[4] = {false, false, false, false};
-        // CPOL_PSD_ONLY: experiment knob (tools/psd_flavours.py): bit mask of the flavours to launch
-        // (1 gamma-exp, 2 recurrence, 4 ice, 8 melting); results are then incomplete
-        static const int only = getenv("CPOL_PSD_ONLY") ? atoi(getenv("CPOL_PSD_ONLY")) : 15;
-        for (int j = 0; j < n_hyd; ++j) {
-            const cpol_hydro_desc &d = ctx->hs.h[j].d;
-            int mode = d.psd_family == CPOL_PSD_ICE_FIELD ? PSD_MODE_ICE
-                     : d.psd_family == CPOL_PSD_MELTING ? PSD_MODE_MELTING
-                     : d.uniform_grid ? PSD_MODE_GAMMA_UNIFORM : PSD_MODE_GAMMA_EXP;
-            if (only & (1 << mode)) need[mode] = true;
-        }
-        // persistent grids: 1024 workgroups walk the unit list with a static stride (smaller
-        // grids, 512 / 768, measured equal or slower; CPOL_PSD_GRID* are experiment knobs)
-        static const long grid_u = getenv("CPOL_PSD_GRID") ? atol(getenv("CPOL_PSD_GRID")) : 1024;
-        static const long grid_g = getenv("CPOL_PSD_GRID_GENERIC") ? atol(getenv("CPOL_PSD_GRID_GENERIC")) : 1024;
         // (items listed directly: the units are single items outside the tables, a handful per volume -- a small
         // grid costs an idle launch less; a flood of them is still processed, by 128 workgroups)
-        const long cap_u = rare_direct ? 128 : grid_u, cap_g = rare_direct ? 128 : grid_g;
+        const long cap_u = f.rare_direct ? 128 : pk.psd_grid, cap_g = f.rare_direct ? 128 : pk.psd_grid_generic;
         const dim3 grd_u((unsigned)(unit_cap < cap_u ? unit_cap : cap_u));
         const dim3 grd((unsigned)(unit_cap < cap_g ? unit_cap : cap_g)), blk(CPOL_PSD_THREADS);
-        // The flavours touch disjoint items and could run side by side.  Measured (MI355X, one
-        // sweep): on sibling streams (fork after the bucket sort, join before the final stage) the
-        // PSD stage took 762 vs 734 us on C3 and 29.2 vs 27.1 ms on C4 -- every flavour is a
-        // persistent grid that fills the chip and is VALU-bound, so overlap only adds the event
-        // traffic.  Back to back on the sweep's stream is the default; CPOL_PSD_SIBLINGS=1 forks.
-        static const bool siblings = getenv("CPOL_PSD_SIBLINGS") && atoi(getenv("CPOL_PSD_SIBLINGS")) != 0;
         const int order[4] = {PSD_MODE_MELTING, PSD_MODE_ICE, PSD_MODE_GAMMA_UNIFORM, PSD_MODE_GAMMA_EXP};
-        // items listed directly (every slot on a table): ONE launch runs every flavour (k_psd_rare); CPOL_PSD_RARE=0: a launch
-        // per flavour as before (same bits: tests/test_gpu_edges.py)
-        if (rare_direct && ctx->psd_rare && only == 15 && !siblings && !ctx->keep_debug) {
-            int modes = 0;
-            for (int m = 0; m < 4; ++m) if (need[m]) modes |= 1 << m;
-            for (int jj = 0; jj < n_hyd; ++jj) {
-                const cpol_hydro_desc &dd = ctx->hs.h[jj].d;
-                if (dd.psd_family == CPOL_PSD_MELTING && dd.tab_degree != CPOL_MELT_DEGREE) modes |= 16;
-            }
+        if (f.psd_rare_one) {              // ONE launch runs every flavour
+            const int modes = f.psd_modes;
             pa.ice_same_launch = 1;
             hipStream_t sr = st;
-            if (rare_forked) {
+            if (f.rare_fork) {
                 if (!ctx->aux[0]) HIPCHK(hipStreamCreateWithFlags(&ctx->aux[0], hipStreamNonBlocking));
                 if (!ctx->ev_join[0]) HIPCHK(hipEventCreateWithFlags(&ctx->ev_join[0], hipEventDisableTiming));
                 sr = ctx->aux[0];
@@ -3179,16 +2930,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             }
             if (dop2) hipLaunchKernelGGL((k_psd_rare<true>), grd, blk, 0, sr, ctx->hs, pa, modes);
             else hipLaunchKernelGGL((k_psd_rare<false>), grd, blk, 0, sr, ctx->hs, pa, modes);
-            if (rare_forked) {
+            if (f.rare_fork) {
                 HIPCHK(hipEventRecord(ctx->ev_join[0], sr));
                 HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[0], 0));
-                rare_forked = false;
             }
-            for (int m = 0; m < 4; ++m) need[m] = false;
         }
-        int n_need = 0;
-        for (int m = 0; m < 4; ++m) n_need += need[m] ? 1 : 0;
-        const bool fork = siblings && n_need > 1;
+        const bool fork = f.psd_fork;
         if (fork) {
             if (!ctx->ev_fork) HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
             HIPCHK(hipEventRecord(ctx->ev_fork, st));
@@ -3196,7 +2943,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         int n_aux = 0;
         for (int q = 0, launched = 0; q < 4; ++q) {
             const int M = order[q];
-            if (!need[M]) continue;
+            if (!f.psd_need[M]) continue;
             hipStream_t s_ = st;
             if (fork && launched > 0) {
                 const int i = n_aux++;
@@ -3209,8 +2956,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             switch (M) {
             case PSD_MODE_GAMMA_UNIFORM: {
                 const dim3 blk_u(CPOL_PSD_THREADS_U);
-                // CPOL_PSD_LDS_PAD: experiment knob (extra dynamic LDS limits the workgroups per CU)
-                static const size_t lds_pad = getenv("CPOL_PSD_LDS_PAD") ? atol(getenv("CPOL_PSD_LDS_PAD")) : 0;
+                const size_t lds_pad = (size_t)pk.psd_lds_pad;
                 if (dop2) hipLaunchKernelGGL((k_psd_uniform<true>), grd_u, blk_u, lds_pad, s_, ctx->hs, pa);
                 else hipLaunchKernelGGL((k_psd_uniform<false>), grd_u, blk_u, lds_pad, s_, ctx->hs, pa);
                 break; }
@@ -3218,46 +2964,31 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                 if (dop2) hipLaunchKernelGGL((k_psd<PSD_MODE_GAMMA_EXP, true>), grd, blk, 0, s_, ctx->hs, pa);
                 else hipLaunchKernelGGL((k_psd<PSD_MODE_GAMMA_EXP, false>), grd, blk, 0, s_, ctx->hs, pa);
                 break;
-            case PSD_MODE_ICE: {
-                // slots with lambda tables: k_psd_ice2 takes the units inside the tabulated range
-                // (all of them, in practice), k_psd<ICE> sums the others
-                bool tab = false;
-                for (int jj = 0; jj < n_hyd; ++jj) {
-                    const cpol_hydro_desc &dd = ctx->hs.h[jj].d;
-                    if (dd.psd_family == CPOL_PSD_ICE_FIELD && dd.uniform_grid && dd.tab_degree == CPOL_ICE_DEGREE) tab = true;
-                }
-                if (tab) {
+            case PSD_MODE_ICE:
+                if (f.psd_ice_tab) {
                     if (dop2) hipLaunchKernelGGL((k_psd_ice2<true>), grd, blk, 0, s_, ctx->hs, pa);
                     else hipLaunchKernelGGL((k_psd_ice2<false>), grd, blk, 0, s_, ctx->hs, pa);
                 }
                 if (dop2) hipLaunchKernelGGL((k_psd<PSD_MODE_ICE, true>), grd, blk, 0, s_, ctx->hs, pa);
                 else hipLaunchKernelGGL((k_psd<PSD_MODE_ICE, false>), grd, blk, 0, s_, ctx->hs, pa);
-                break; }
-            default: {
-                // melting slots with fw tables go to the table-driven kernel, the others (none
-                // in the product's own staging) to the direct one; each skips foreign units
-                bool tab = false, direct = false;
-                for (int jj = 0; jj < n_hyd; ++jj) {
-                    const cpol_hydro_desc &dd = ctx->hs.h[jj].d;
-                    if (dd.psd_family != CPOL_PSD_MELTING) continue;
-                    (dd.tab_degree == CPOL_MELT_DEGREE ? tab : direct) = true;
-                }
-                if (tab) {
+                break;
+            default:
+                if (f.psd_melt_tab) {
                     if (dop2) hipLaunchKernelGGL((k_psd_melting_tab<true>), grd, blk, 0, s_, ctx->hs, pa);
                     else hipLaunchKernelGGL((k_psd_melting_tab<false>), grd, blk, 0, s_, ctx->hs, pa);
                 }
-                if (direct) {
+                if (f.psd_melt_direct) {
                     if (dop2) hipLaunchKernelGGL((k_psd_melting<true>), grd, blk, 0, s_, ctx->hs, pa);
                     else hipLaunchKernelGGL((k_psd_melting<false>), grd, blk, 0, s_, ctx->hs, pa);
                 }
-                break; }
+                break;
             }
             if (s_ != st) HIPCHK(hipEventRecord(ctx->ev_join[n_aux - 1], s_));
         }
         for (int i = 0; i < n_aux; ++i) HIPCHK(hipStreamWaitEvent(st, ctx->ev_join[i], 0));
     }
     // ---- 5d. sub-beam sums per (gate, hydrometeor); the items on 1-D tables are evaluated here ----
-    if (subsum) {
+    if (f.subsum) {
         SubsumArgs sa2{};
         sa2.key = (const int *)ctx->b_key.p;
         sa2.vmask = (const unsigned char *)ctx->b_vmask.p;
@@ -3268,55 +2999,30 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         sa2.wgate = ml ? (const double *)ctx->b_wgate.p : nullptr;
         sa2.sz_integ = (float *)ctx->b_szinteg.p;
         sa2.n_rays = n_rays; sa2.n_gates = ng; sa2.n_sub = n_sub; sa2.n_hydro = n_hyd;
-        // lanes of a wavefront = a tile of neighbouring rays x consecutive gates (16 x 4 from 16 rays on)
-        int tl = CPOL_TILE_GATES_LOG2;
-        while (tl < 6 && (CPOL_WAVE >> tl) > n_rays) ++tl;
+        const int tl = f.sum_tile_log2;   // lanes of a wavefront = a tile of neighbouring rays x consecutive gates
         sa2.tile_log2 = tl;
-        sa2.coop_rounds = ctx->subsum_coop_rounds;
-        const long tiles = (long)cdiv(n_rays, CPOL_WAVE >> tl) * cdiv(ng, 1 << tl);
-        // the scalar-cache form needs many wavefronts per SIMD to hide its waits (C4 volume, rays per sweep:
-        // 45 / 90 / 180 / 360 -> PSD stage 1.08 / 1.56 / 2.08 / 3.57 ms against 0.85 / 1.48 / 2.35 / 4.71 ms with
-        // the gather): from ~32 wavefronts per SIMD on (the scalar-cache form; see below for the LDS form).  CPOL_SUBSUM_COOP=0 / 1: never / always.
-        // With lanes (cpol_fork) other sweeps share the GPU and hide the waits: measured with three lanes in
-        // flight, the share of one of 8 / 4 GPUs (11 / 21 wavefronts per SIMD): 1.30 / 2.24 ms per volume share
-        // against 1.31 / ~2.5 ms with the gather -- from ~12 there.
-        const long waves_per_simd = tiles * n_hyd / 1024;
-        const int lanes_alive = ctx->parent ? ctx->parent->n_children : ctx->n_children;
-        // (round 4, with the validity bits read up front: the share of one of 8 GPUs -- 11 wavefronts per SIMD --
-        // with three lanes in flight 1.19 ms per volume share this way against 1.27 with the gather: from 8 there)
-        // (the LDS form, round 4: the share of one of 8 / 4 / 2 GPUs alone -- 11 / 21 / 43 wavefronts per SIMD -- PSD stage 905 / 1281 /
-        // 1748 us against 846 / 1413 / 2312 with the gather: from 16 there)
-        const bool coop = ctx->subsum_coop == 1 || (ctx->subsum_coop < 0 && waves_per_simd >= (lanes_alive >= 2 ? 8 : 16));
-        // CPOL_SUBSUM_SMALL=1 (experiment, never the default): the gather form with three wavefronts per (tile,
-        // hydrometeor), 4 columns each, and all rows of the block requested at once -- see the note on SPLIT in
-        // cpol_final.inl: slower than the plain gather on the share (571 vs 533 us) and with lanes (1.41 vs 1.27 ms)
-        const bool small = !coop && ctx->subsum_small == 1;
-        // the cooperative form: coefficient rows through LDS (default since round 4) or through the scalar cache
-        // (CPOL_SUBSUM_FORM=scalar, read when the context is created)
-        // the team form (round 5: W wavefronts per (tile, species) share the sub-beams, the float32 sums stay ordered): what bounds a small
-        // launch is the length of its longest wavefront's chain (cpol_final.inl).  Share of one of 8 / 4 / 2 GPUs alone (11 / 21 / 43
-        // wavefronts per SIMD), ms per volume share: 1.47 / 2.18 / 3.57 with the rule above, 1.23 / 2.00 / 3.53 with W = 2 (W = 4: 1.23 /
-        // 2.05 / 3.66; W = 4 with the sums handed on in LDS instead of a barrier per round -- the default -- 1.16 / 1.98 / 3.44); with three lanes in flight 0.97 / 1.71 either way (a context WITH lanes that runs one share at
-        // a time: 1.42 with the LDS form its rule picked, 1.23 with the team); the whole volume 1.71 (LDS form) against 1.94 ms.
-        const int team = ctx->subsum_team >= 0 ? ctx->subsum_team       // (a form forced through CPOL_SUBSUM_COOP stays what was asked for)
-                       : (ctx->subsum_coop < 0 && waves_per_simd < 50 ? 4 : 0);      // (whatever the lanes: a context with lanes may still run one sweep at a time)
-#define CPOL_TEAM_CASE(W) case W: if (ctx->subsum_chain) hipLaunchKernelGGL((k_subbeam_sum_team<W, true>), dim3((unsigned)tiles, n_hyd), dim3(CPOL_WAVE * W), 0, st, ctx->hs, ctx->its, sa2); \
-                          else hipLaunchKernelGGL((k_subbeam_sum_team<W, false>), dim3((unsigned)tiles, n_hyd), dim3(CPOL_WAVE * W), 0, st, ctx->hs, ctx->its, sa2); break;
-        if (team >= 2 && team <= 8)
-            switch (team) { CPOL_TEAM_CASE(2) CPOL_TEAM_CASE(3) CPOL_TEAM_CASE(4) CPOL_TEAM_CASE(5) CPOL_TEAM_CASE(6) CPOL_TEAM_CASE(7)
-                            case 8: hipLaunchKernelGGL((k_subbeam_sum_team<8, true>), dim3((unsigned)tiles, n_hyd), dim3(CPOL_WAVE * 8), 0, st, ctx->hs, ctx->its, sa2); break; }
+        sa2.coop_rounds = ctx->knobs.subsum_coop_rounds;
+        const dim3 sgrid((unsigned)((long)cdiv(n_rays, CPOL_WAVE >> tl) * cdiv(ng, 1 << tl)), n_hyd);
+#define CPOL_TEAM_CASE(W) case W: if (f.sum_chain) hipLaunchKernelGGL((k_subbeam_sum_team<W, true>), sgrid, dim3(CPOL_WAVE * W), 0, st, ctx->hs, ctx->its, sa2); \
+                          else hipLaunchKernelGGL((k_subbeam_sum_team<W, false>), sgrid, dim3(CPOL_WAVE * W), 0, st, ctx->hs, ctx->its, sa2); break;
+        switch (f.sum_form) {
+        case SUM_TEAM:
+            switch (f.sum_team) { CPOL_TEAM_CASE(2) CPOL_TEAM_CASE(3) CPOL_TEAM_CASE(4) CPOL_TEAM_CASE(5) CPOL_TEAM_CASE(6) CPOL_TEAM_CASE(7)
+                                  case 8: hipLaunchKernelGGL((k_subbeam_sum_team<8, true>), sgrid, dim3(CPOL_WAVE * 8), 0, st, ctx->hs, ctx->its, sa2); break; }
+            break;
 #undef CPOL_TEAM_CASE
-        else if (coop && ctx->subsum_scalar) hipLaunchKernelGGL(k_subbeam_sum_scalar, dim3((unsigned)tiles, n_hyd), dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2);
-        else if (coop) hipLaunchKernelGGL(k_subbeam_sum_lds, dim3((unsigned)tiles, n_hyd), dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2);
-        else if (small) hipLaunchKernelGGL((k_subbeam_sum_gather<3, 10>), dim3((unsigned)tiles, n_hyd * 3), dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2);
-        else hipLaunchKernelGGL((k_subbeam_sum_gather<1, 2>), dim3((unsigned)tiles, n_hyd), dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2);
+        case SUM_SCALAR: hipLaunchKernelGGL(k_subbeam_sum_scalar, sgrid, dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2); break;
+        case SUM_LDS: hipLaunchKernelGGL(k_subbeam_sum_lds, sgrid, dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2); break;
+        case SUM_SMALL: hipLaunchKernelGGL((k_subbeam_sum_gather<3, 10>), dim3(sgrid.x, n_hyd * 3), dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2); break;
+        default: hipLaunchKernelGGL((k_subbeam_sum_gather<1, 2>), sgrid, dim3(CPOL_SUBSUM_THREADS), 0, st, ctx->hs, ctx->its, sa2);
+        }
     }
     if (tm_psd) HIPCHK(hipEventRecord(ctx->ev[EV_PSD], st));
 
     // ---- 6. accumulation + polarimetric variables + scans (the arguments: see 2b above) ----
     if (doppler)
         for (int j = 0; j < n_hyd && !dop3; ++j)
-            if (fa.vsrc[j] == 2)
+            if (f.vsrc[j] == 2)
                 hipLaunchKernelGGL(k_ice_first, dim3(n_rays * n_sub), dim3(64), 0, st,
                                    (const unsigned char *)ctx->b_vmask.p, j,
                                    (const double *)ctx->b_vn.p + (long)j * n_sbg * 2,
@@ -3401,19 +3107,16 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         hipLaunchKernelGGL(k_spec_final, dim3((unsigned)n_rg), dim3(64), 0, st, sf);
         ra.RVEL = (double *)T[O_RVEL];       // censored with the other observables in k_final
     }
-    fa.pre_integ = subsum ? 1 : 0;
-    if (subsum) fa.sz_integ = (float *)ctx->b_szinteg.p;
+    fa.pre_integ = f.subsum ? 1 : 0;
+    if (f.subsum) fa.sz_integ = (float *)ctx->b_szinteg.p;
     fa.proj = nullptr;
-    if (fa.RVEL && n_sub >= 4) {
+    if (f.rvel_terms) {
         // the per-sub-beam velocity terms by one thread per sub-beam gate (k_final adds them in order)
         hipLaunchKernelGGL(k_rvel_terms, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st,
                            fa, (double *)ctx->b_proj.p);
         fa.proj = (const double *)ctx->b_proj.p;
     }
-    // (one workgroup per ray: with no more rays than CUs the kernel lasts as long as ONE workgroup -- 512
-    // threads halve its gate loop; the share of one of 8 GPUs of a 5 x 360-ray volume is 225 rays)
-    static const int final512 = getenv("CPOL_FINAL_512") ? atoi(getenv("CPOL_FINAL_512")) : -1;   // experiment knob
-    if ((final512 == 1 || (final512 < 0 && n_rays <= 256)) && ng > CPOL_FINAL_THREADS)
+    if (f.final_512)             // (one workgroup per ray; few rays: 512 threads halve its gate loop)
         hipLaunchKernelGGL((k_final<2 * CPOL_FINAL_THREADS>), dim3(n_rays), dim3(2 * CPOL_FINAL_THREADS), (size_t)3 * ng * sizeof(float), st, fa, ra, ctx->its);
     else
         hipLaunchKernelGGL((k_final<CPOL_FINAL_THREADS>), dim3(n_rays), dim3(CPOL_FINAL_THREADS), (size_t)3 * ng * sizeof(float), st, fa, ra, ctx->its);
@@ -3423,16 +3126,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     return CPOL_OK;
     };
 
-    const int forms[12] = {g1r, (int)gate1_ray, (int)gate1, (int)fused, (int)rare_direct, (int)subsum, (int)final_inplace, (int)poly_single,
-                           n_sub, ctx->parent ? ctx->parent->n_children : ctx->n_children, CPOL_SCAN_FORM, 0};
+    int forms[12];
+    forms_record(fi, f, forms);
     memcpy(ctx->last_forms, forms, sizeof forms);
     ctx->last_stencil = 0;
     const double t_buffers = now_ns();
     ctx->counters_dirty = true;         // until the sequence is queued completely (cleared where sweep_serial advances)
     // graph key: every value that ends up in a kernel argument
-    const bool graphable = ctx->use_graph && dev && !tm_psd && !ctx->keep_debug && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out && !mem &&
-                           !dop3 && reuse && !want_szt && !want_model;
-    if (graphable) {
+    if (f.graphable) {
         uint64_t key = 1469598103934665603ull;
         auto mix = [&](const void *ptr, size_t n) {
             const unsigned char *c = (const unsigned char *)ptr;
@@ -3448,7 +3149,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                          ctx->b_res.p, ctx->b_vn.p, ctx->b_icefirst.p, ctx->b_wgate.p, ctx->b_blkranked.p, ctx->b_rec.p,
                          ctx->b_vmask.p, ctx->b_rayc.p, ctx->v_traj_in, ctx->v_geo, ctx->v_subh,
                          ctx->v_subv, ctx->v_subw, ctx->v_sens, ctx->v_site, ctx->v_nyq,
-                         ctx->v_subsmooth, ctx->v_mlfilter, (void *)st, poly_single ? set->poly.p : nullptr, gate1_ray ? ctx->b_present.p : nullptr};
+                         ctx->v_subsmooth, ctx->v_mlfilter, (void *)st, f.poly_single ? set->poly.p : nullptr, f.gate1_ray ? ctx->b_present.p : nullptr};
         mix(arena, sizeof arena);
         // (the launch forms chosen above from state outside *p: a graph captured before the lanes were forked must not keep
         // replaying the four-launch sequence once k_gate1_ray is the default, nor the reverse)
@@ -3514,7 +3215,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ctx->last_par = par;
     ++ctx->sweep_serial;
     ctx->counters_dirty = false;
-    ctx->last_n_keys = n_keys; ctx->last_subsum = subsum || final_inplace;
+    ctx->last_n_keys = n_keys; ctx->last_subsum = f.subsum || f.final_inplace;
     ctx->counters.n_subbeam_gates = n_sbg;
     ctx->counters.n_gates = n_rg;
 
