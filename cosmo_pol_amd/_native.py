@@ -103,9 +103,24 @@ class Superob(C.Structure):
                 + [(n, C.c_void_p) for n in SUPEROB_FIELDS] + [('count', C.c_void_p)])
 
 
+MEMBER_STATS_FIELDS = SUPEROB_FIELDS                 # the rows of cpol_member_stats.count
+MEMBER_STATS_KINDS = ('mean', 'spread', 'min', 'max')
+
+
+class MemberStats(C.Structure):
+    """cpol_member_stats: the call's member(s) folded into the context's running ensemble statistics
+    (cosmo_pol_amd/ensemble_stats.py states the rule).  phase: bit 0 begins a pass, bit 1 finishes it."""
+    _fields_ = ([('phase', C.c_int32), ('min_members', C.c_int32), ('fields', C.c_uint32),
+                 ('n_thresholds', C.c_int32 * len(MEMBER_STATS_FIELDS)), ('pad_', C.c_int32),
+                 ('thresholds', C.c_void_p * len(MEMBER_STATS_FIELDS))]
+                + [(n, C.c_void_p * len(MEMBER_STATS_FIELDS)) for n in MEMBER_STATS_KINDS]
+                + [('count', C.c_void_p), ('exceed', C.c_void_p * len(MEMBER_STATS_FIELDS))])
+
+
 class Outputs(C.Structure):
-    # superob: NULL = off; stays the last member (cpol_outputs)
-    _fields_ = [(n, C.c_void_p) for n in OUTPUT_FIELDS] + [('superob', C.POINTER(Superob))]
+    # member_stats, superob: NULL = off; superob stays the last member (cpol_outputs)
+    _fields_ = ([(n, C.c_void_p) for n in OUTPUT_FIELDS]
+                + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
 
 class SubbeamOutputs(C.Structure):
@@ -840,6 +855,68 @@ class Context(object):
         self._check(rc, 'cpol_debug_read(superob_fields)')
         del keep
         out['count'] = {k: cnt[SUPEROB_FIELDS.index(k)] for k in asked}
+        return out
+
+    @staticmethod
+    def member_stats_struct(spec, names, phase):
+        """(MemberStats for a call of a pass that folds the fields `names` under `spec` (an ensemble_stats.EnsembleStats),
+        what keeps its threshold arrays alive)."""
+        ms = MemberStats()
+        ms.phase, ms.min_members = int(phase), spec.min_members
+        keep = []
+        for k in names:
+            i = MEMBER_STATS_FIELDS.index(k)
+            ms.fields |= 1 << i
+            thr = np.ascontiguousarray(spec.exceed.get(k, ()), dtype=np.float64)
+            if thr.size:
+                keep.append(thr)
+                ms.n_thresholds[i], ms.thresholds[i] = thr.size, thr.ctypes.data
+        return ms, keep
+
+    def member_stats_fields(self, fields, spec, phase=3, n_cells=None, names=None):
+        """Test hook (cpol_debug_read "member_stats_fields"): the product's k_member_fold / k_member_finish and this context's
+        running state on caller-supplied members {name: [n_members, n_cells]} of MEMBER_STATS_FIELDS (float32; RVEL float64).
+        `spec`: an ensemble_stats.EnsembleStats; `phase`: bit 0 begins a pass, bit 1 finishes it -- a pass may be cut into
+        calls; `fields` may be empty (no member; then `n_cells` and `names` say what the pass holds).  A finishing call
+        returns what ensemble_stats.finish returns, every other call None."""
+        class Hook(C.Structure):
+            _fields_ = [('n_members', C.c_int32), ('n_cells', C.c_int64), ('inp', C.c_void_p * len(MEMBER_STATS_FIELDS)),
+                        ('ms', MemberStats)]
+        h = Hook()
+        keep, shape = [], None
+        for i, k in enumerate(MEMBER_STATS_FIELDS):
+            if k not in fields:
+                continue
+            a = np.ascontiguousarray(fields[k], dtype=np.float64 if k == 'RVEL' else np.float32)
+            if a.ndim != 2 or (shape is not None and a.shape != shape):
+                raise ValueError('member_stats_fields: every field is [n_members, n_cells]')
+            shape = a.shape
+            keep.append(a)
+            h.inp[i] = a.ctypes.data
+        if names is None:
+            names = spec.resolve([k for k in MEMBER_STATS_FIELDS if k in fields])
+        if shape is None:
+            shape = (0, int(n_cells))
+        h.n_members, h.n_cells = shape
+        h.ms, thr_keep = self.member_stats_struct(spec, names, phase)
+        out = None
+        if int(phase) & 2:
+            nc = shape[1]
+            out = {kind: {k: np.empty(nc, dtype=np.float64 if k == 'RVEL' else np.float32) for k in names} for kind in spec.kinds}
+            cnt = np.zeros((len(MEMBER_STATS_FIELDS), nc), dtype=np.uint16)
+            out['exceed'] = {k: np.empty((len(spec.exceed[k]), nc), dtype=np.uint16) for k in names if k in spec.exceed}
+            for k in names:
+                i = MEMBER_STATS_FIELDS.index(k)
+                for kind in spec.kinds:
+                    getattr(h.ms, kind)[i] = out[kind][k].ctypes.data
+                if k in out['exceed']:
+                    h.ms.exceed[i] = out['exceed'][k].ctypes.data
+            h.ms.count = cnt.ctypes.data
+        rc = int(self.lib.cpol_debug_read(self.h, b'member_stats_fields', C.byref(h), C.sizeof(h)))
+        self._check(rc, 'cpol_debug_read(member_stats_fields)')
+        del keep, thr_keep
+        if out is not None:
+            out['count'] = {k: cnt[MEMBER_STATS_FIELDS.index(k)] for k in names}
         return out
 
     FORM_NAMES = ('g1r', 'gate1_ray', 'gate1', 'interp_classify', 'rare_direct', 'subbeam_sum', 'final_inplace',

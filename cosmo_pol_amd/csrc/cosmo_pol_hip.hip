@@ -34,6 +34,7 @@
 #include "cpol_spectrum.inl"
 #include "cpol_ingest.inl"
 #include "cpol_superob.inl"
+#include "cpol_member_stats.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -170,6 +171,18 @@ struct cpol_ctx {
     int stg_next = 0;
     DevBuf b_traj, b_wgate, b_clk, b_rayc, b_poly, d_geoM;
     DevBuf b_beam, b_spectrum, b_outwin, b_superob;
+    // ensemble statistics (cpol_member_stats): the running state of this context's pass, and the block k_member_finish writes
+    // when the outputs are host memory outside a window image
+    DevBuf b_mstate, b_msout;
+    struct MemberPass {
+        bool open = false;
+        long n_cells = 0, folded = 0;
+        unsigned fields = 0;
+        int min_members = 0;
+        int n_thr[CPOL_MS_FIELDS] = {};
+        double thr[CPOL_MS_FIELDS][CPOL_MS_MAX_THR] = {};
+        MemberState st[CPOL_MS_FIELDS] = {};
+    } mpass;
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
@@ -745,7 +758,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_mstate, &ctx->b_msout, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -1948,6 +1961,202 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
     return CPOL_OK;
 }
 
+// ---- ensemble statistics (cpol_member_stats, cpol_member_stats.inl): the checks, the pass and the launches, shared by the
+// launch sequence and the test hook ----
+enum { MS_MEAN = 0, MS_SPREAD = CPOL_MS_FIELDS, MS_MIN = 2 * CPOL_MS_FIELDS, MS_MAX = 3 * CPOL_MS_FIELDS, MS_COUNT = 4 * CPOL_MS_FIELDS,
+       MS_EXCEED, MS_N = MS_EXCEED + CPOL_MS_FIELDS };
+struct MemberStatsPlan {
+    long cells;
+    int n_sets;
+    bool begin, finish;
+    int n_thr[CPOL_MS_FIELDS];
+    double thr[CPOL_MS_FIELDS][CPOL_MS_MAX_THR];    // as the kernels compare them (float32 fields: rounded once)
+    void *user[MS_N];                               // a finishing call: the caller's pointers (folded fields only)
+    size_t bytes[MS_N];
+};
+
+// every refusal of a cpol_member_stats for a call that folds n_sets row sets of n_cells cells; queues and changes nothing
+static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_cells, int n_sets, bool doppler, MemberStatsPlan *pl)
+{
+    auto bad = [&](const char *why) { ctx->err = std::string("cpol_member_stats: ") + why; return CPOL_ERR_ARG; };
+    const cpol_ctx::MemberPass &ps = ctx->mpass;
+    if (ms->phase < 0 || ms->phase > 3) return bad("phase must lie in 0..3 (bit 0: begin, bit 1: finish)");
+    if (ms->min_members < 1) return bad("min_members must be >= 1");
+    if (ms->fields == 0 || (ms->fields >> CPOL_MS_FIELDS) != 0) return bad("fields: a mask over the ten fields, at least one");
+    if (((ms->fields >> CPOL_MS_RVEL) & 1u) && !doppler) return bad("RVEL needs simulate_doppler");
+    if (n_cells < 1 || n_cells >= (1L << 31)) return bad("n_cells must lie in [1, 2^31)");
+    *pl = MemberStatsPlan{};
+    pl->cells = n_cells;
+    pl->n_sets = n_sets;
+    pl->begin = (ms->phase & 1) != 0;
+    pl->finish = (ms->phase & 2) != 0;
+    for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+        const int nt = ms->n_thresholds[k];
+        if (nt < 0 || nt > CPOL_MS_MAX_THR) return bad("n_thresholds must lie in 0..8");
+        if (!((ms->fields >> k) & 1u)) continue;          // (the thresholds of a field that is not folded are not read)
+        if (nt > 0 && !ms->thresholds[k]) return bad("n_thresholds > 0 needs the thresholds");
+        pl->n_thr[k] = nt;
+        for (int t = 0; t < nt; ++t) {
+            const double v = ms->thresholds[k][t];
+            if (v != v) return bad("a threshold is NaN");
+            pl->thr[k][t] = k == CPOL_MS_RVEL ? v : (double)(float)v;
+        }
+    }
+    if (!pl->begin) {
+        if (!ps.open) return bad("no pass is open: the first call of a pass carries the begin bit");
+        bool same = ps.n_cells == n_cells && ps.fields == ms->fields && ps.min_members == ms->min_members;
+        for (int k = 0; k < CPOL_MS_FIELDS && same; ++k) {
+            same = ps.n_thr[k] == pl->n_thr[k];
+            for (int t = 0; t < pl->n_thr[k] && same; ++t) same = ps.thr[k][t] == pl->thr[k][t];
+        }
+        if (!same) return bad("n_cells, fields, thresholds or min_members differ from the open pass");
+    }
+    if ((pl->begin ? 0 : ps.folded) + n_sets > 65535) return bad("more than 65535 members in a pass (the counts are uint16)");
+    if (pl->finish) {
+        bool any = false;
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+            if (!((ms->fields >> k) & 1u)) continue;
+            const size_t w = k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float);
+            void *const f[4] = {ms->mean[k], ms->spread[k], ms->min[k], ms->max[k]};
+            for (int a = 0; a < 4; ++a) { pl->user[a * CPOL_MS_FIELDS + k] = f[a]; pl->bytes[a * CPOL_MS_FIELDS + k] = (size_t)n_cells * w; }
+            if (pl->n_thr[k] > 0) {
+                pl->user[MS_EXCEED + k] = ms->exceed[k];
+                pl->bytes[MS_EXCEED + k] = (size_t)pl->n_thr[k] * n_cells * sizeof(uint16_t);
+            }
+        }
+        pl->user[MS_COUNT] = ms->count;
+        pl->bytes[MS_COUNT] = (size_t)CPOL_MS_FIELDS * n_cells * sizeof(uint16_t);
+        for (int k = 0; k < MS_N; ++k) any = any || pl->user[k];
+        if (!any) return bad("a finishing call needs an output pointer");
+    }
+    return CPOL_OK;
+}
+
+// where k_member_finish writes when the outputs are host memory and no window image holds them: the context's own block
+static int member_stats_own_block(cpol_ctx *ctx, const MemberStatsPlan &pl, void *T[MS_N])
+{
+    size_t total = 0, off = 0;
+    for (int k = 0; k < MS_N; ++k) if (pl.user[k]) total += (pl.bytes[k] + 255) & ~(size_t)255;
+    ENSURE(ctx->b_msout, total);
+    for (int k = 0; k < MS_N; ++k) {
+        T[k] = nullptr;
+        if (!pl.user[k]) continue;
+        T[k] = (char *)ctx->b_msout.p + off;
+        off += (pl.bytes[k] + 255) & ~(size_t)255;
+    }
+    return CPOL_OK;
+}
+
+// The pass (begun here, when the call carries the begin bit: the state block is sized and the pass's terms are noted), the fold
+// of the call's row sets and, for a finishing call, the outputs.  in: the per-gate device arrays in the order of `count`'s rows
+// (slot RVEL float64), row set m at element m * cells; T: where k_member_finish writes.
+static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const MemberStatsPlan &pl, const void *const in[CPOL_MS_FIELDS],
+                               void *const T[MS_N], bool zero_rest, hipStream_t st)
+{
+    cpol_ctx::MemberPass &ps = ctx->mpass;
+    if (pl.begin) {
+        const size_t a2 = ((size_t)pl.cells * sizeof(uint16_t) + 255) & ~(size_t)255, a4 = ((size_t)pl.cells * sizeof(float) + 255) & ~(size_t)255;
+        const size_t a8 = ((size_t)pl.cells * sizeof(double) + 255) & ~(size_t)255;
+        size_t total = 0;
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k)
+            if ((ms->fields >> k) & 1u) total += a2 + 2 * a8 + 2 * (k == CPOL_MS_RVEL ? a8 : a4) + (size_t)pl.n_thr[k] * a2;
+        ps.open = false;                                      // (a begin that fails below leaves no pass behind)
+        ENSURE(ctx->b_mstate, total);
+        char *q = (char *)ctx->b_mstate.p;
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+            ps.st[k] = MemberState{};
+            if (!((ms->fields >> k) & 1u)) continue;
+            ps.st[k].n = (unsigned short *)q; q += a2;
+            ps.st[k].mean = (double *)q;      q += a8;
+            ps.st[k].m2 = (double *)q;        q += a8;
+            ps.st[k].lo = q;                  q += k == CPOL_MS_RVEL ? a8 : a4;
+            ps.st[k].hi = q;                  q += k == CPOL_MS_RVEL ? a8 : a4;
+            ps.st[k].k = (unsigned short *)q; q += (size_t)pl.n_thr[k] * a2;      // (indexed [t][n_cells]: rows n_cells elements apart)
+        }
+        ps.n_cells = pl.cells; ps.fields = ms->fields; ps.min_members = ms->min_members; ps.folded = 0;
+        memcpy(ps.n_thr, pl.n_thr, sizeof ps.n_thr);
+        memcpy(ps.thr, pl.thr, sizeof ps.thr);
+        ps.open = true;
+    }
+    MemberStatsArgs a{};
+    for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+        if (!((ps.fields >> k) & 1u)) continue;
+        a.field[a.n_fields++] = k;
+        a.in[k] = in[k];
+        a.st[k] = ps.st[k];
+        a.n_thr[k] = ps.n_thr[k];
+    }
+    memcpy(a.thr, ps.thr, sizeof a.thr);
+    a.n_sets = pl.n_sets; a.begin = pl.begin; a.need = ps.min_members; a.n_cells = pl.cells;
+    const dim3 grid(cdiv(pl.cells, 256), a.n_fields);
+    if (pl.n_sets > 0 || pl.begin) {
+        hipLaunchKernelGGL(k_member_fold, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        ps.folded += pl.n_sets;
+    }
+    if (pl.finish) {
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+            a.o_mean[k] = T[MS_MEAN + k]; a.o_spread[k] = T[MS_SPREAD + k]; a.o_min[k] = T[MS_MIN + k]; a.o_max[k] = T[MS_MAX + k];
+            a.o_exceed[k] = (unsigned short *)T[MS_EXCEED + k];
+        }
+        a.o_count = (unsigned short *)T[MS_COUNT];
+        a.zero_rest = zero_rest;
+        hipLaunchKernelGGL(k_member_finish, grid, dim3(256), 0, st, a);
+        HIPCHK(hipGetLastError());
+        ps.open = false;
+    }
+    return CPOL_OK;
+}
+
+// host-side copies of what k_member_finish wrote into the context's own block (count: the rows of folded fields alone)
+static int member_stats_copy_out(cpol_ctx *ctx, const MemberStatsPlan &pl, unsigned fields, void *const T[MS_N])
+{
+    int rc;
+    for (int k = 0; k < MS_N; ++k)
+        if (k != MS_COUNT && pl.user[k] && (rc = copy_out(ctx, pl.user[k], T[k], pl.bytes[k], false))) return rc;
+    const size_t row = (size_t)pl.cells * sizeof(uint16_t);
+    for (int k = 0; k < CPOL_MS_FIELDS && pl.user[MS_COUNT]; ++k)
+        if (((fields >> k) & 1u) && (rc = copy_out(ctx, (char *)pl.user[MS_COUNT] + k * row, (char *)T[MS_COUNT] + k * row, row, false))) return rc;
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "member_stats_fields": the product's fold and finish on caller-supplied members (host memory
+// in, host memory out, blocking), phase by phase -- the kernels on inputs no sweep produces and on passes cut at will.
+struct MemberStatsHook {
+    int32_t n_members;
+    int64_t n_cells;
+    const void *in[CPOL_MS_FIELDS];         // [n_members][n_cells] float32 (slot RVEL float64)
+    cpol_member_stats ms;
+};
+
+static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
+{
+    if (h->n_members < 0 || h->n_cells < 1 || h->n_cells >= (1L << 31) || (long)h->n_members * h->n_cells >= (1L << 31)) {
+        ctx->err = "member_stats_fields: bad shape";
+        return CPOL_ERR_ARG;
+    }
+    MemberStatsPlan pl{};
+    int rc = member_stats_plan(ctx, &h->ms, (long)h->n_cells, h->n_members, true, &pl);
+    if (rc != CPOL_OK) return rc;
+    for (int k = 0; k < CPOL_MS_FIELDS; ++k)
+        if (((h->ms.fields >> k) & 1u) && h->n_members > 0 && !h->in[k]) { ctx->err = "member_stats_fields: a folded field has no input"; return CPOL_ERR_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)h->n_members * (size_t)h->n_cells;
+    const void *in[CPOL_MS_FIELDS] = {};
+    for (int k = 0; k < CPOL_MS_FIELDS && n > 0; ++k) {     // (the sweeps' own output buffers hold the inputs)
+        if (!((h->ms.fields >> k) & 1u)) continue;
+        DevBuf &b = k == CPOL_MS_RVEL ? ctx->b_rvel : ctx->b_out[k];
+        if ((rc = upload(ctx, b, h->in[k], n * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
+        in[k] = b.p;
+    }
+    void *T[MS_N] = {};
+    if (pl.finish && (rc = member_stats_own_block(ctx, pl, T)) != CPOL_OK) return rc;
+    if ((rc = member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream)) != CPOL_OK) return rc;
+    if (pl.finish && (rc = member_stats_copy_out(ctx, pl, h->ms.fields, T)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -2054,6 +2263,16 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (cols || sub_out) { ctx->err = "cpol_superob: cpol_run_sweep and cpol_run_sweep_members take superobservations, no other entry point"; return CPOL_ERR_ARG; }
         const int rc_so = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl);
         if (rc_so != CPOL_OK) return rc_so;
+    }
+    // ensemble statistics (cpol_member_stats): likewise
+    const cpol_member_stats *const ms = out->member_stats;
+    MemberStatsPlan ms_pl{};
+    if (ms) {
+        if (cols || sub_out) { ctx->err = "cpol_member_stats: cpol_run_sweep and cpol_run_sweep_members take ensemble statistics, no other entry point"; return CPOL_ERR_ARG; }
+        if (so) { ctx->err = "cpol_member_stats: not together with superobservations (outputs->superob) in one call"; return CPOL_ERR_ARG; }
+        if (timed) { ctx->err = "cpol_member_stats: a time-blended call (tables->time_blend) folds no members"; return CPOL_ERR_ARG; }
+        const int rc_ms = member_stats_plan(ctx, ms, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl);
+        if (rc_ms != CPOL_OK) return rc_ms;
     }
     int rc;
 
@@ -2416,6 +2635,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             if (produced[k] && user_out[k]) window_add(user_out[k], obytes[k], win_lo, win_hi, win_sum);
         for (int k = 0; k < SO_N; ++k)                        // (the superobservation arrays count like every other array)
             if (so_pl.user[k]) window_add(so_pl.user[k], so_pl.bytes[k], win_lo, win_hi, win_sum);
+        for (int k = 0; k < MS_N; ++k)                        // (and those of a finishing cpol_member_stats)
+            if (ms_pl.user[k]) window_add(ms_pl.user[k], ms_pl.bytes[k], win_lo, win_hi, win_sum);
     }
     const bool window = win_lo && (size_t)(win_hi - win_lo) <= win_sum + win_sum / 4 + 4096;
     // (the device image keeps the window's alignment modulo 64 B, so that every array of the image is
@@ -2439,6 +2660,15 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     } else if (so) {
         for (int k = 0; k < SO_N; ++k)
             if (so_pl.user[k]) so_T[k] = dev ? so_pl.user[k] : (void *)((char *)ctx->b_outwin.p + win_skew + ((char *)so_pl.user[k] - win_lo));
+    }
+    // ... and where k_member_finish writes: the same three places
+    void *ms_T[MS_N] = {};
+    if (ms && ms_pl.finish && !dev && !window) {
+        const int rc_ms = member_stats_own_block(ctx, ms_pl, ms_T);
+        if (rc_ms != CPOL_OK) return rc_ms;
+    } else if (ms && ms_pl.finish) {
+        for (int k = 0; k < MS_N; ++k)
+            if (ms_pl.user[k]) ms_T[k] = dev ? ms_pl.user[k] : (void *)((char *)ctx->b_outwin.p + win_skew + ((char *)ms_pl.user[k] - win_lo));
     }
 
     // the bucket counters start at zero: cleared by k_interp_sweep (no fill kernel); the domain
@@ -3190,8 +3420,16 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                                         T[O_ATTV], T[O_RVEL]};
         if ((rc = superob_launch(ctx, so, so_pl, so_in, so_T, ng, window, st)) != CPOL_OK) return rc;
     }
+    // ---- ensemble statistics: the call's member(s) folded into the context's running state behind the sequence, and the
+    // outputs of a finishing call (outside launch_all, like k_superob) ----
+    if (ms) {
+        const void *const ms_in[CPOL_MS_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
+                                                   T[O_ATTV], T[O_RVEL]};
+        if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st)) != CPOL_OK) return rc;
+    }
     // ---- outputs that the kernels did not write in place ----
     if (so && !dev && !window && (rc = superob_copy_out(ctx, so_pl, so_T)) != CPOL_OK) return rc;
+    if (ms && ms_pl.finish && !dev && !window && (rc = member_stats_copy_out(ctx, ms_pl, ms->fields, ms_T)) != CPOL_OK) return rc;
     if (window) {
         HIPCHK(hipMemcpyAsync(win_lo, (const char *)ctx->b_outwin.p + win_skew, (size_t)(win_hi - win_lo), hipMemcpyDeviceToHost, st));
     } else {
@@ -3254,6 +3492,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
 {
     if (!ctx) return CPOL_ERR_ARG;
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
         !c->vals || !c->elev || !c->sub_w) {
         ctx->err = "cpol_run_columns: bad shapes, or vals / elev / sub_w missing";
@@ -3545,6 +3784,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         if (!dst || max_bytes < (int64_t)sizeof v) return CPOL_ERR_ARG;
         memcpy(dst, v, sizeof v);
         return (int64_t)sizeof v;
+    }
+    if (!strcmp(name, "member_stats_fields")) {     // a CONTROL name: dst points to a MemberStatsHook
+        if (!dst || max_bytes < (int64_t)sizeof(MemberStatsHook)) { ctx->err = "cpol_debug_read(member_stats_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return member_stats_hook(ctx, (const MemberStatsHook *)dst);
     }
     if (!strcmp(name, "superob_fields")) {          // a CONTROL name: dst points to a SuperobHook
         if (!dst || max_bytes < (int64_t)sizeof(SuperobHook)) { ctx->err = "cpol_debug_read(superob_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }

@@ -1,0 +1,138 @@
+// cpol_member_stats.inl -- ensemble statistics: the members of a pass folded, one after another, into a running state per gate
+// (cpol_member_stats): mean, spread, extremes, the members that count and the members above thresholds.
+//
+// Reference functions replaced (wolfidan/cosmo_pol): none -- the reference runs one model state per process.  The rule is the
+// one of include/cosmo_pol_amd.h and cosmo_pol_amd/ensemble_stats.py (`fold`, `finish`), ORDER-EXACT: a strict left fold over
+// the members (Welford's update: one float64 subtraction, division, addition, subtraction, multiplication, addition per
+// counting value), then one float64 division, square root and rounding.  Only IEEE operations, and the TU is compiled with
+// -ffp-contract=off -fno-fast-math: the kernels give the bits of the NumPy statement however the pass is cut into calls.
+// The division by n is part of the rule: no reciprocal.
+
+#define CPOL_MS_FIELDS 10           // ZH, ZV, ZDR, KDP, DELTA_HV, PHIDP, RHOHV, ATT_H, ATT_V, RVEL (the rows of `count`)
+#define CPOL_MS_RVEL 9
+#define CPOL_MS_MAX_THR 8
+
+// the running state of one folded field, SoA: the lanes of a wavefront touch consecutive addresses of every array
+struct MemberState {
+    unsigned short *n;              // [n_cells]
+    double *mean, *m2;              // [n_cells]
+    void *lo, *hi;                  // [n_cells] of the field's type
+    unsigned short *k;              // [n_thr][n_cells]
+};
+
+struct MemberStatsArgs {
+    const void *in[CPOL_MS_FIELDS];         // per-gate fields, row set m at element m * n_cells (float32; slot RVEL float64)
+    MemberState st[CPOL_MS_FIELDS];
+    double thr[CPOL_MS_FIELDS][CPOL_MS_MAX_THR];    // float32 fields: already rounded to float32
+    int n_thr[CPOL_MS_FIELDS];
+    int field[CPOL_MS_FIELDS];              // the folded fields = gridDim.y
+    int n_fields;
+    int n_sets;                             // row sets (members) of this call
+    int begin;                              // 1: the state starts here (nothing is loaded)
+    int need;                               // min_members
+    long n_cells;
+    // k_member_finish
+    void *o_mean[CPOL_MS_FIELDS], *o_spread[CPOL_MS_FIELDS], *o_min[CPOL_MS_FIELDS], *o_max[CPOL_MS_FIELDS];
+    unsigned short *o_count;                // [10][n_cells] or NULL
+    unsigned short *o_exceed[CPOL_MS_FIELDS];
+    int zero_rest;                          // 1: the rows of `count` of fields not folded are written as zeros
+};
+
+// x / n (n a whole number, 1 <= n <= 65535) rounded ONCE, whatever the quotient.  The device's float64 division is correctly
+// rounded for a normal quotient; a SUBNORMAL one can come out one unit of the subnormal grid off (measured: 4 of 160 000 means
+// of 1e-310-sized members, always away from the CPU's division by one unit).  The residual x - q n of such a quotient is a small
+// multiple of 2^-1074, so the fma gives it exactly, and it says which neighbour of q is the nearest (ties to even).
+__device__ __forceinline__ double member_div(double x, double n)
+{
+    double q = x / n;
+    if (__builtin_fabs(q) < 2.2250738585072014e-308) {       // (false for NaN)
+        const double ulp = 4.9406564584124654e-324;
+        const double r = __builtin_fma(-q, n, x);
+        const double r2 = r + r, nu = n * ulp;
+        const bool odd = (__double_as_longlong(q) & 1) != 0;
+        if (r2 > nu || (r2 == nu && odd)) q = q + ulp;
+        else if (r2 < -nu || (r2 == -nu && odd)) q = q - ulp;
+    }
+    return q;
+}
+
+template <typename T>
+__device__ __forceinline__ void member_fold_field(const MemberStatsArgs &a, int f, long c)
+{
+    const MemberState &s = a.st[f];
+    const int n_thr = a.n_thr[f];
+    unsigned n = 0;
+    double mean = 0.0, m2 = 0.0;
+    T lo = (T)__builtin_inf(), hi = (T)-__builtin_inf();
+    unsigned k[CPOL_MS_MAX_THR];
+    T thr[CPOL_MS_MAX_THR];
+#pragma unroll
+    for (int t = 0; t < CPOL_MS_MAX_THR; ++t) { k[t] = 0; thr[t] = (T)a.thr[f][t]; }
+    if (!a.begin) {
+        n = s.n[c]; mean = s.mean[c]; m2 = s.m2[c];
+        lo = ((const T *)s.lo)[c]; hi = ((const T *)s.hi)[c];
+#pragma unroll
+        for (int t = 0; t < CPOL_MS_MAX_THR; ++t)
+            if (t < n_thr) k[t] = s.k[(long)t * a.n_cells + c];
+    }
+    const T *__restrict__ x = (const T *)a.in[f];
+    for (int m = 0; m < a.n_sets; ++m) {
+        const T v = x[(long)m * a.n_cells + c];
+        if (v == v) {
+            n = n + 1;
+            const double d = (double)v - mean;
+            mean = mean + member_div(d, (double)n);
+            m2 = m2 + d * ((double)v - mean);
+            if (v < lo) lo = v;
+            if (v > hi) hi = v;
+#pragma unroll
+            for (int t = 0; t < CPOL_MS_MAX_THR; ++t)
+                if (t < n_thr) k[t] += v > thr[t];
+        }
+    }
+    s.n[c] = (unsigned short)n; s.mean[c] = mean; s.m2[c] = m2;
+    ((T *)s.lo)[c] = lo; ((T *)s.hi)[c] = hi;
+#pragma unroll
+    for (int t = 0; t < CPOL_MS_MAX_THR; ++t)
+        if (t < n_thr) s.k[(long)t * a.n_cells + c] = (unsigned short)k[t];
+}
+
+// One lane per (cell, folded field); the members of the call at stride n_cells; the state is loaded and stored once per call.
+__global__ __launch_bounds__(256) void k_member_fold(const MemberStatsArgs a)
+{
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const int f = a.field[blockIdx.y];
+    if (f == CPOL_MS_RVEL) member_fold_field<double>(a, f, c);
+    else member_fold_field<float>(a, f, c);
+}
+
+template <typename T>
+__device__ __forceinline__ void member_finish_field(const MemberStatsArgs &a, int f, long c)
+{
+    const MemberState &s = a.st[f];
+    const int n = s.n[c];
+    const T nan = (T)__builtin_nan("");
+    if (a.o_mean[f]) ((T *)a.o_mean[f])[c] = n >= a.need ? (T)s.mean[c] : nan;
+    if (a.o_spread[f]) ((T *)a.o_spread[f])[c] = n >= max(a.need, 2) ? (T)__builtin_sqrt(member_div(s.m2[c], (double)(n - 1))) : nan;
+    if (a.o_min[f]) ((T *)a.o_min[f])[c] = n >= a.need ? ((const T *)s.lo)[c] : nan;
+    if (a.o_max[f]) ((T *)a.o_max[f])[c] = n >= a.need ? ((const T *)s.hi)[c] : nan;
+    if (a.o_count) a.o_count[(long)f * a.n_cells + c] = (unsigned short)n;
+    if (a.o_exceed[f])
+        for (int t = 0; t < a.n_thr[f]; ++t) a.o_exceed[f][(long)t * a.n_cells + c] = s.k[(long)t * a.n_cells + c];
+}
+
+__global__ __launch_bounds__(256) void k_member_finish(const MemberStatsArgs a)
+{
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const int f = a.field[blockIdx.y];
+    if (f == CPOL_MS_RVEL) member_finish_field<double>(a, f, c);
+    else member_finish_field<float>(a, f, c);
+    if (a.o_count && a.zero_rest && blockIdx.y == 0) {
+        unsigned folded = 0;
+        for (int j = 0; j < a.n_fields; ++j) folded |= 1u << a.field[j];
+        for (int j = 0; j < CPOL_MS_FIELDS; ++j)
+            if (!((folded >> j) & 1u)) a.o_count[(long)j * a.n_cells + c] = 0;
+    }
+}

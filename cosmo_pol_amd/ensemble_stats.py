@@ -1,0 +1,204 @@
+"""Ensemble statistics: per gate the mean, the spread, the extremes of the members of an ensemble, the number of members
+that saw an echo and the number of members above thresholds.
+
+Replaces in the reference: nothing -- cosmo_pol runs one model state per process.  A probabilistic forecast or its
+verification against observed radar wants none of the members themselves, only these few arrays whose size does not depend
+on the number of members.  The fold runs on the device behind the sweeps' kernels (k_member_fold, k_member_finish,
+cpol_member_stats.inl), before the copy to the host; the pure host-side pieces live here so that they are testable without a
+GPU: the specification and its refusals, and the NumPy statement of the rule that DEFINES what the kernels compute (`fold`,
+`finish`, `reduce`).  The operator's entry points are in radar_operator.py.
+
+The rule.  A cell is a gate of the call.  Fields are the ten of superob.FIELDS in that order (ZH, ZV, ZDR, KDP, DELTA_HV,
+PHIDP, RHOHV, ATT_H, ATT_V: float32; RVEL: float64; T below).  ZDR is folded from each member's own per-gate ZDR like any
+other field: members are not averaged by an antenna, so the power-ratio rule of superobservations does not apply.  mask,
+model variables and the Doppler spectrum are not folded.  The state of a pass, per cell and folded field:
+    n uint16 = 0;  mean, M2 float64 = +0.0;  lo, hi of type T = +inf, -inf;  k_t uint16 = 0, one per threshold
+Members are folded one after another, in the order of the member list.  A member's value v counts iff v == v (a censored or
+outside gate is NaN and changes nothing but the member total).  If it counts:
+    n = n + 1;  d = float64(v) - mean;  mean = mean + d / float64(n);  M2 = M2 + d * (float64(v) - mean)   (the new mean)
+    if v < lo: lo = v;  if v > hi: hi = v;  k_t += (v > thr_t) for each threshold
+with the thresholds compared in type T (thr_t: the caller's number rounded once to float32 for the float32 fields) and every
+operation one IEEE operation.  Finishing, need = min_members >= 1:
+    mean = T(mean) where n >= need, else NaN;  spread = T(sqrt(M2 / float64(n - 1))) where n >= max(need, 2), else NaN (the
+    sample standard deviation);  min = lo and max = hi where n >= need, else NaN;  count = n and exceed_t = k_t always
+Counts, not probabilities: `probability` divides by the members folded (a NaN reads as "no echo", the right reading of a
+censored gate) or by the members that counted.  A strict left fold: the result does not depend on how the member list was
+cut into calls.  At most 65535 members per pass and 8 thresholds per field."""
+import numpy as np
+
+# the rows of cpol_member_stats.count, in this order (= superob.FIELDS)
+FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL')
+MAX_MEMBERS = 65535
+MAX_THRESHOLDS = 8
+KINDS = ('mean', 'spread', 'min', 'max')
+
+
+def dtype_of(field):
+    return np.float64 if field == 'RVEL' else np.float32
+
+
+def dbz(x):
+    """A reflectivity in dBZ as the linear value the fields carry: 10 ** (x / 10)."""
+    return 10.0 ** (np.asarray(x, dtype=np.float64) / 10.0) if np.ndim(x) else 10.0 ** (float(x) / 10.0)
+
+
+class EnsembleStats(object):
+    """What to reduce an ensemble to: `mean`, `spread`, `extremes` (min and max) switch those outputs; `exceed` {field:
+    [thresholds in the field's own (linear) units]} asks for the number of members above each; `fields`: the fields to
+    fold (None: every field of FIELDS the call produces); `min_members`: mean, min and max are NaN where fewer members
+    counted (spread needs two at least).  The count of counting members always comes.  ValueError for what the library
+    refuses with CPOL_ERR_ARG: an unknown field, min_members outside 1..65535, more than 8 thresholds for a field, a
+    NaN threshold, thresholds for a field that is not folded."""
+
+    def __init__(self, mean=True, spread=True, extremes=False, exceed=None, fields=None, min_members=1):
+        self.mean, self.spread, self.extremes = bool(mean), bool(spread), bool(extremes)
+        if fields is not None:
+            fields = tuple(fields)
+            for k in fields:
+                if k not in FIELDS:
+                    raise ValueError('EnsembleStats: unknown field %r (one of %s)' % (k, FIELDS))
+            if not fields or len(set(fields)) != len(fields):
+                raise ValueError('EnsembleStats: fields %r is empty or lists a field twice' % (fields,))
+            fields = tuple(k for k in FIELDS if k in fields)
+        self.fields = fields
+        if isinstance(min_members, bool) or int(min_members) != min_members or not 1 <= int(min_members) <= MAX_MEMBERS:
+            raise ValueError('EnsembleStats: min_members %r outside 1..%d' % (min_members, MAX_MEMBERS))
+        self.min_members = int(min_members)
+        self.exceed = {}
+        for k, thr in (exceed or {}).items():
+            if k not in FIELDS:
+                raise ValueError('EnsembleStats: exceed: unknown field %r' % (k,))
+            if fields is not None and k not in fields:
+                raise ValueError('EnsembleStats: exceed: %r is not among the folded fields %r' % (k, fields))
+            thr = np.atleast_1d(np.asarray(thr, dtype=np.float64))
+            if thr.ndim != 1 or not 1 <= thr.size <= MAX_THRESHOLDS:
+                raise ValueError('EnsembleStats: exceed[%r]: 1 to %d thresholds, got shape %r' % (k, MAX_THRESHOLDS, thr.shape))
+            if np.isnan(thr).any():
+                raise ValueError('EnsembleStats: exceed[%r]: a threshold is NaN' % (k,))
+            self.exceed[k] = thr.copy()
+
+    def resolve(self, available):
+        """The fields a call folds, in the order of FIELDS: `fields`, or every field of `available`.  ValueError when a
+        requested field (or a field with thresholds) is not available (RVEL without Doppler)."""
+        available = [k for k in FIELDS if k in available]
+        want = self.fields if self.fields is not None else tuple(available)
+        for k in tuple(want) + tuple(self.exceed):
+            if k not in available:
+                raise ValueError('EnsembleStats: field %r is not produced by this call (RVEL needs a Doppler scheme)' % (k,))
+        if not want:
+            raise ValueError('EnsembleStats: no field to fold')
+        return tuple(want)
+
+    def thresholds(self, field):
+        """The thresholds of `field` as the fold compares them: rounded once to the field's dtype."""
+        return self.exceed.get(field, np.zeros(0)).astype(dtype_of(field))
+
+    @property
+    def kinds(self):
+        return tuple(k for k, on in zip(KINDS, (self.mean, self.spread, self.extremes, self.extremes)) if on)
+
+    @property
+    def key(self):
+        return (self.mean, self.spread, self.extremes, self.fields, self.min_members,
+                tuple((k, tuple(v)) for k, v in sorted(self.exceed.items())))
+
+    def __repr__(self):
+        return 'EnsembleStats(mean=%r, spread=%r, extremes=%r, exceed=%r, fields=%r, min_members=%d)' % (
+            self.mean, self.spread, self.extremes, {k: list(v) for k, v in self.exceed.items()}, self.fields, self.min_members)
+
+
+def begin(spec, fields, shape):
+    """The state of a pass that has folded nothing: {'spec', 'n_members', 'fields': {name: {'n', 'mean', 'M2', 'lo', 'hi',
+    'k'}}} for cells of `shape`."""
+    shape = tuple(shape)
+    st = {}
+    for k in fields:
+        T = dtype_of(k)
+        thr = spec.thresholds(k)
+        st[k] = {'n': np.zeros(shape, np.uint16), 'mean': np.zeros(shape, np.float64), 'M2': np.zeros(shape, np.float64),
+                 'lo': np.full(shape, np.inf, T), 'hi': np.full(shape, -np.inf, T),
+                 'k': np.zeros((len(thr),) + shape, np.uint16), 'thr': thr}
+    return {'spec': spec, 'n_members': 0, 'fields': st}
+
+
+def fold(state, rows):
+    """Folds the members of `rows` {name: [n_members, ...cells]} into `state`, one after another: the rule at the top of this
+    module in NumPy, statement by statement.  Returns `state`."""
+    n_new = None
+    for name, s in state['fields'].items():
+        T = dtype_of(name)
+        x = np.asarray(rows[name])
+        if x.dtype != T or x.shape[1:] != s['n'].shape:
+            raise ValueError('fold: %s must be %s [n_members%s], got %s %r'
+                             % (name, np.dtype(T).name, ''.join(', %d' % d for d in s['n'].shape), x.dtype, x.shape))
+        if n_new is not None and x.shape[0] != n_new:
+            raise ValueError('fold: the fields hold different numbers of members')
+        n_new = x.shape[0]
+        if state['n_members'] + n_new > MAX_MEMBERS:
+            raise ValueError('fold: more than %d members in a pass' % MAX_MEMBERS)
+        n, mean, M2, lo, hi, k = s['n'], s['mean'], s['M2'], s['lo'], s['hi'], s['k']
+        with np.errstate(all='ignore'):
+            for v in x:
+                c = v == v
+                v64 = v.astype(np.float64)
+                n = (n + c).astype(np.uint16)
+                d = v64 - mean
+                new = mean + d / n.astype(np.float64)
+                M2 = np.where(c, M2 + d * (v64 - new), M2)
+                mean = np.where(c, new, mean)
+                lo = np.where(c & (v < lo), v, lo)
+                hi = np.where(c & (v > hi), v, hi)
+                for t, thr in enumerate(s['thr']):
+                    k[t] = k[t] + (c & (v > thr))
+        s.update(n=n, mean=mean, M2=M2, lo=lo, hi=hi)
+    state['n_members'] += n_new or 0
+    return state
+
+
+def finish(state, spec=None):
+    """The outputs of a pass: {'mean', 'spread', 'min', 'max': {name: array in the field's dtype} (those `spec` asks for),
+    'count': {name: uint16}, 'exceed': {name: uint16 [n_thresholds, ...cells]}, 'n_members'}."""
+    spec = spec or state['spec']
+    need = spec.min_members
+    out = {kind: {} for kind in spec.kinds}
+    out.update(count={}, exceed={}, n_members=state['n_members'])
+    for name, s in state['fields'].items():
+        T = dtype_of(name)
+        n = s['n'].astype(np.int64)
+        nan = np.array(np.nan, T)
+        if spec.mean:
+            out['mean'][name] = np.where(n >= need, s['mean'].astype(T), nan)
+        if spec.spread:
+            with np.errstate(all='ignore'):
+                sd = np.sqrt(s['M2'] / (n - 1).astype(np.float64)).astype(T)
+            out['spread'][name] = np.where(n >= max(need, 2), sd, nan)
+        if spec.extremes:
+            out['min'][name] = np.where(n >= need, s['lo'], nan)
+            out['max'][name] = np.where(n >= need, s['hi'], nan)
+        out['count'][name] = s['n'].copy()
+        if len(s['thr']):
+            out['exceed'][name] = s['k'].copy()
+    return out
+
+
+def reduce(fields, spec):
+    """`fields` {name: [n_members, ...cells]} as simulate_rays_ensemble returns them (other entries are ignored) -> the
+    statistics of `finish`: the slow way to them, and the definition of what the device computes."""
+    have = [k for k in FIELDS if k in fields]
+    names = spec.resolve(have)
+    rows = {k: np.asarray(fields[k]) for k in names}
+    return finish(fold(begin(spec, names, rows[names[0]].shape[1:]), rows), spec)
+
+
+def probability(stats, field, of='members'):
+    """exceed / n_members (of='members': a member without an echo counts as below every threshold) or exceed / count
+    (of='valid': among the members that counted; NaN where none did) -> float64 [n_thresholds, ...cells]."""
+    if of not in ('members', 'valid'):
+        raise ValueError("probability: of is 'members' or 'valid'")
+    k = stats['exceed'][field].astype(np.float64)
+    if of == 'members':
+        if stats['n_members'] < 1:
+            raise ValueError('probability: no member was folded')
+        return k / float(stats['n_members'])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return k / stats['count'][field].astype(np.float64)

@@ -27,6 +27,7 @@ from . import constants as K
 from . import geometry as geo
 from . import hydrometeors as hyd
 from . import quadrature
+from . import ensemble_stats as ES
 from . import superob as SO
 from .lut import load_all_lut
 
@@ -1204,12 +1205,22 @@ class RadarOperator(object):
 
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0):
+                  pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0,
+                  member_stats=None):
         if self._model_staged:
             self._sync_edr()
         if superob is not None:
             self._superob_check(superob)
-        gates = superob is None or keep_gates     # the per-gate radar fields travel to the host
+        if member_stats is not None:
+            # (spec, phase, keep_members): this call's member(s) folded into the lane's running ensemble statistics
+            ms_spec, ms_phase, ms_keep = member_stats
+            if superob is not None:
+                raise ValueError('ensemble statistics and superobservations do not share a call '
+                                 '(statistics of window averages are left to the host)')
+            if timed is not None or subbeams is not None:
+                raise ValueError('ensemble statistics are taken by the ensemble sweeps, not by time-blended or sub-beam calls')
+        # the per-gate radar fields travel to the host
+        gates = (superob is None or keep_gates) and (member_stats is None or ms_keep)
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -1348,8 +1359,27 @@ class RadarOperator(object):
             so.min_valid_fraction = superob.min_valid_fraction
             o.superob = C.pointer(so)
             so_fields = [k for k in SO.FIELDS if k != 'RVEL' or doppler]
+        ms = ms_names = None
+        if member_stats is not None:
+            ms_names = ms_spec.resolve([k for k in ES.FIELDS if k != 'RVEL' or doppler])
+            ms, ms_thr = N.Context.member_stats_struct(ms_spec, ms_names, ms_phase)
+            keep = list(keep) + ms_thr
+            o.member_stats = C.pointer(ms)
+        ms_out = ms is not None and bool(ms_phase & 2)      # a finishing call: the statistics arrive with it
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
+                if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed': {field: device pointer}, 'count': pointer}
+                    if ms is None:
+                        raise ValueError("device_outputs['stats'] without ensemble statistics")
+                    for kind, pp in (ptr.items() if ms_out else ()):
+                        if kind == 'count':
+                            ms.count = pp
+                            continue
+                        if kind not in ES.KINDS + ('exceed',):
+                            raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
+                        for kk, q in pp.items():
+                            getattr(ms, kind)[ES.FIELDS.index(kk)] = q
+                    continue
                 if k == 'superob':                # {field or 'count': device pointer}
                     if so is None:
                         raise ValueError("device_outputs['superob'] without superob=")
@@ -1388,6 +1418,12 @@ class RadarOperator(object):
                     wshape = (len(members),) + wshape
                 spec += [(('superob', k), np.float64 if k == 'RVEL' else np.float32, wshape) for k in so_fields]
                 spec.append((('superob', 'count'), np.uint16, (len(SO.FIELDS),) + wshape))
+            if ms_out:
+                # the statistics, in the same block: they ride the one copy
+                for kind in ms_spec.kinds:
+                    spec += [(('stats', kind, k), ES.dtype_of(k), gshape) for k in ms_names]
+                spec.append((('stats', 'count'), np.uint16, (len(ES.FIELDS),) + gshape))
+                spec += [(('stats', 'exceed', k), np.uint16, (len(ms_spec.exceed[k]),) + gshape) for k in ms_names if k in ms_spec.exceed]
             # every host output is a view of ONE block of page-locked memory from the operator's pool
             # (64-byte aligned arrays): the kernels write a device image of the block and a single
             # device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
@@ -1400,7 +1436,14 @@ class RadarOperator(object):
             off = 0
             for (k, dt, sh), n_el, nb in zip(spec, counts, sizes):
                 a = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
-                if isinstance(k, tuple):
+                if isinstance(k, tuple) and k[0] == 'stats':
+                    if k[1] == 'count':
+                        res.setdefault('stats', {})['count'] = a
+                        ms.count = base + off
+                    else:
+                        res.setdefault('stats', {}).setdefault(k[1], {})[k[2]] = a
+                        getattr(ms, k[1])[ES.FIELDS.index(k[2])] = base + off
+                elif isinstance(k, tuple):
                     res.setdefault('superob', {})[k[1]] = a
                     setattr(so, k[1], base + off)
                 else:
@@ -1459,6 +1502,11 @@ class RadarOperator(object):
                     if pinned:
                         ctx.synchronize()
                     w.update(SO.coordinates(res, superob, so_rpb))
+        if ms_out and device_outputs is None:
+            w = res['stats']
+            cnt = w.pop('count')
+            w['count'] = {k: cnt[ES.FIELDS.index(k)] for k in ms_names}
+            w.setdefault('exceed', {})
         res['n_sub'] = sub.n_sub
         return res
 
@@ -1566,6 +1614,32 @@ class RadarOperator(object):
         `pinned`: as for simulate_rays when the members fit one chunk; with several chunks the call waits.
         `superob`, `keep_gates`, `rays_per_block`: as for simulate_rays_superob; the arrays of res['superob'] gain the member axis (the
         window coordinates come once).  A window never holds gates of two members."""
+        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned,
+                                   dict(superob=superob, keep_gates=keep_gates, rays_per_block=rays_per_block))
+
+    def simulate_rays_ensemble_stats(self, azimuths, elevations, stats, members=None, keep_members=False, form=None, lane=0,
+                                     pinned=False, device_outputs=None, apply_sensitivity=True):
+        """simulate_rays_ensemble handing back ENSEMBLE STATISTICS instead of the members: `stats` is an
+        ensemble_stats.EnsembleStats, and the result is the gate coordinates once and res['stats'] = {'mean', 'spread', 'min',
+        'max': {field: [n_rays, n_gates]} (those `stats` asks for), 'count': {field: uint16}, 'exceed': {field: uint16 [n_thr,
+        n_rays, n_gates]}, 'n_members': M} -- folded on the device behind the sweeps' kernels, member after member in the order
+        of `members` (ensemble_stats.fold / finish state the rule; the device result carries the bits of
+        ensemble_stats.reduce(simulate_rays_ensemble(...), stats)).  Without `keep_members` no per-member array is produced for
+        the host or copied; with it everything simulate_rays_ensemble returns comes back beside the statistics.
+        `form`, `members`, `lane`, `apply_sensitivity`: as for simulate_rays_ensemble; whatever the form and however
+        `sequence_memory_budget` cuts the member list, the first call of the pass begins it, the last finishes it, all go to
+        the one lane, and the bits are the same.  `pinned`: do not wait (call wait(lane)); with several calls it waits.
+        `device_outputs`: {'stats': {'mean' | 'spread' | 'min' | 'max' | 'exceed': {field: device pointer}, 'count': device
+        pointer of [10, n_rays, n_gates]}} (and, with keep_members, the per-member pointers of simulate_rays_ensemble).
+        NotImplementedError where simulate_rays_ensemble raises it: a process group, spaceborne geometry, refraction scheme 2."""
+        if not isinstance(stats, ES.EnsembleStats):
+            raise ValueError('stats: a cosmo_pol_amd.ensemble_stats.EnsembleStats, got %r' % (stats,))
+        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, {},
+                                   stats=stats, keep_members=keep_members)
+
+    def _ensemble_rays(self, azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, so_kw,
+                       stats=None, keep_members=False):
+        superob = so_kw.get('superob')
         members = self._members_arg(members)
         conf = self.__config
         coords = conf['radar']['coords']
@@ -1588,12 +1662,16 @@ class RadarOperator(object):
             chunks = ensemble.plan_member_chunks(members, per_gate * sub.n_sub * len(rr) * n_rays, budget)
         else:
             chunks = [[m] for m in members]
-        so_kw = dict(superob=superob, keep_gates=keep_gates, rays_per_block=rays_per_block)
         if superob is not None and device_outputs is not None and len(chunks) > 1:
             raise ValueError('simulate_rays_ensemble: superobservations into device outputs need the members in one chunk')
+        if stats is not None and len(members) > ES.MAX_MEMBERS:
+            raise ValueError('ensemble statistics: at most %d members in a pass' % ES.MAX_MEMBERS)
         parts, done = [], 0
         try:
-            for chunk in chunks:
+            for i, chunk in enumerate(chunks):
+                if stats is not None:
+                    # the pass: begun by the first call, finished by the last, every call on this lane
+                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if i == len(chunks) - 1 else 0), keep_members))
                 dev = None
                 if device_outputs is not None:
                     dev = self._offset_outputs(device_outputs, done, n_rays, len(rr))
@@ -1610,15 +1688,24 @@ class RadarOperator(object):
         finally:
             if form == 'per_member':
                 ctx.select_member(self._member)
+        if stats is not None and 'stats' in parts[-1]:
+            parts[-1]['stats']['n_members'] = len(members)
         if device_outputs is not None:
             return parts[-1]
         if form == 'shared' and len(parts) == 1:
             return parts[0]
+        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
+        if stats is not None and not keep_members:
+            # (no per-member array came: the coordinates of the first call, the statistics of the last)
+            if pinned and len(parts) > 1:
+                self.wait(lane)
+            return dict({k: v for k, v in parts[0].items() if k in once}, stats=parts[-1]['stats'])
         if pinned:
             self.wait(lane)                        # (the members are joined on the host: their copies must have landed)
-        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
         join = np.stack if form == 'per_member' else np.concatenate
-        out = {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys() if k != 'superob'}
+        out = {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys() if k not in ('superob', 'stats')}
+        if stats is not None:
+            out['stats'] = parts[-1]['stats']
         if superob is not None:
             w0 = parts[0]['superob']
             out['superob'] = {k: (v if k in once else join([p['superob'][k] for p in parts]))
@@ -1632,7 +1719,7 @@ class RadarOperator(object):
         width = {'RVEL': 8, 'mask': 8, 'DSPECTRUM': 8 * n_vb, 'sz_total': 4 * N.N_SZ, 'mask_sum8': 1}
         out = {}
         for k, ptr in device_outputs.items():
-            if k in ('lats', 'lons', 'dist', 'heights', 'superob'):
+            if k in ('lats', 'lons', 'dist', 'heights', 'superob', 'stats'):
                 out[k] = ptr
             else:
                 out[k] = int(ptr) + n_before * n_rays * n_gates * width.get(k, 4)
@@ -2165,6 +2252,37 @@ class RadarOperator(object):
         """The sweeps of get_RHI as superobservations: one result per azimuth (see get_PPI_superob)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._superob_sweeps(sweeps, spec, keep_gates)
+
+    # ------------------------------------------------------------------ ensemble statistics scans
+    def _ensemble_stats_sweeps(self, sweeps, stats, members):
+        """One pinned simulate_rays_ensemble_stats per sweep over the lanes, one wait at the end: every sweep's pass stays on
+        its lane and carries the bits of its own call."""
+        members = self._members_arg(members)
+        n_par = max(1, min(self.lanes, len(sweeps)))
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                res.append(self.simulate_rays_ensemble_stats(az, el, stats, members=members, pinned=True, lane=k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        return res
+
+    def get_PPI_ensemble_stats(self, elevations, stats, azimuths=None, az_step=None, az_start=0, az_stop=359, members=None):
+        """The sweeps of get_PPI reduced over the ensemble: a list with one simulate_rays_ensemble_stats(..., stats) result
+        per elevation (res['stats']), the sweeps spread over the lanes."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._ensemble_stats_sweeps(sweeps, stats, members)
+
+    def get_RHI_ensemble_stats(self, azimuths, stats, elevations=None, elev_step=None, elev_start=0, elev_stop=90, members=None):
+        """The sweeps of get_RHI reduced over the ensemble: one result per azimuth (see get_PPI_ensemble_stats)."""
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._ensemble_stats_sweeps(sweeps, stats, members)
 
     def get_VPROF(self):
         """90-degree vertical profile (the reference's version is broken as

@@ -297,6 +297,56 @@ typedef struct cpol_superob {
                                    window rule: the other rows lie inside the window and arrive as zeros) */
 } cpol_superob;
 
+/* Ensemble statistics: what a probabilistic forecast or its verification consumes instead of every member's per-gate arrays
+ * -- per gate the mean, the spread, the extremes, the number of members with an echo and the number of members above
+ * thresholds.  Replaces in the reference: nothing (it runs one model state per process).  Pointed to by
+ * cpol_outputs.member_stats; honoured by cpol_run_sweep (folds ONE member: the rows of the call, the context's selected
+ * member) and by cpol_run_sweep_members without time blend (folds the call's n_members row sets in the order of `members`).
+ * A RUNNING FOLD with state on the device, one state per context: a pass is open from a call with the begin bit until a call
+ * with the finish bit or the next begin; the result does not depend on how the member list was cut into calls.
+ * INPUT: the per-gate fields of the call as the launch sequence leaves them (after the range scans and the sensitivity cut;
+ * censored gates are NaN).  A cell is a gate of the call, n_cells = n_rays * n_gates (n_rays of ONE member).
+ * FIELDS: the ten of cpol_superob.count's rows in that order (bit k of `fields`): ZH, ZV, ZDR, KDP, DELTA_HV, PHIDP, RHOHV,
+ * ATT_H, ATT_V float32, RVEL float64 (type T below).  ZDR is folded from each member's own per-gate ZDR like any other field.
+ * mask, model_vars, sz_total and DSPECTRUM are not folded.
+ * STATE per cell and folded field: n uint16 = 0; mean, M2 float64 = +0.0; lo, hi of type T = +inf, -inf; k_t uint16 = 0, one
+ * per threshold.  Members are folded one after another, in the order of the call's member list and of the calls of the pass.
+ * For a member's value v: it counts iff v == v (a NaN changes nothing).  If it counts:
+ *     n = n + 1;  d = (double)v - mean;  mean = mean + d / (double)n;  M2 = M2 + d * ((double)v - mean)   (the new mean);
+ *     if (v < lo) lo = v;  if (v > hi) hi = v;  k_t += (v > thr_t) for each threshold,
+ * thresholds compared in type T (thr_t: the caller's double rounded once to float32 for the float32 fields); every operation
+ * one IEEE operation (no contraction, no reciprocal; a subnormal quotient is rounded once too).
+ * FINISHING, need = min_members >= 1: mean = (T)mean where n >= need, else NaN; spread = (T)sqrt(M2 / (double)(n - 1)) where
+ * n >= max(need, 2), else NaN (the sample standard deviation); min = lo and max = hi where n >= need, else NaN; count = n and
+ * exceed_t = k_t always.  Counts, not probabilities: the host divides by the members folded or by count, as it likes.
+ * The output pointers are read only by a finishing call and follow p->outputs_on_device like every other array (mode 2:
+ * they count for the one-copy window rule).  Pointers of a field outside `fields` are ignored.
+ * CPOL_ERR_ARG, nothing queued, the state of an open pass untouched, the context usable: phase outside 0..3; min_members < 1;
+ * fields zero or with a bit >= 10; RVEL without Doppler; an n_thresholds outside 0..8, or positive with a NULL pointer; a NaN
+ * threshold; a fold with no pass open and no begin bit; a fold whose n_cells, fields, thresholds or min_members differ from
+ * the open pass; more than 65535 members in a pass; a finishing call with no output pointer at all; outputs->superob set in
+ * the same call; tables->time_blend; cpol_run_columns and cpol_interp_subbeams.
+ * TWO kernels (k_member_fold, k_member_finish) run behind the launch sequence and before the output copy: the per-gate
+ * arrays, the launch forms, the gate stencils and a captured graph are what they are without it.  A per-gate array the
+ * caller leaves NULL is still produced on the device (the context's own buffer) and simply not copied. */
+#define CPOL_MEMBER_STATS_FIELDS 10
+#define CPOL_MEMBER_STATS_MAX_THRESHOLDS 8
+typedef struct cpol_member_stats {
+    int32_t phase;              /* bit 0: begin a pass (clear the state, then fold); bit 1: finish it (fold, then write the
+                                   outputs); 0: fold only                                                          */
+    int32_t min_members;        /* need >= 1                                                                       */
+    uint32_t fields;            /* bit k: fold field k                                                             */
+    int32_t n_thresholds[CPOL_MEMBER_STATS_FIELDS];     /* 0..8 per field                                          */
+    int32_t pad_;
+    const double *thresholds[CPOL_MEMBER_STATS_FIELDS]; /* host arrays [n_thresholds[k]], the field's own (linear) units */
+    /* outputs, each [n_cells], float32 except slot RVEL (float64); NULL = not wanted */
+    void *mean[CPOL_MEMBER_STATS_FIELDS], *spread[CPOL_MEMBER_STATS_FIELDS];
+    void *min[CPOL_MEMBER_STATS_FIELDS], *max[CPOL_MEMBER_STATS_FIELDS];
+    uint16_t *count;            /* [10][n_cells] or NULL: n of every field; only the rows of folded fields are written (mode 2
+                                   under the window rule: the other rows arrive as zeros)                          */
+    uint16_t *exceed[CPOL_MEMBER_STATS_FIELDS];         /* [n_thresholds[k]][n_cells] or NULL                      */
+} cpol_member_stats;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -312,7 +362,9 @@ typedef struct {
                                    domain; doppler_scatter.py:472-477), one byte per gate instead of the eight of `mask`.
                                    mask = mask_sum8 / n_sub, then values in (-1, 0] -> 0: the caller's two NumPy statements.
                                    Needs 2 * n_sub <= 127.  When it is asked for and `mask` is not, `mask` is not written. */
-    cpol_superob *superob;      /* NULL (a zero-initialised struct): off.  Window averages of the fields above, see cpol_superob.
+    cpol_member_stats *member_stats;    /* NULL (a zero-initialised struct): off.  The call's member(s) folded into the
+                                   context's running ensemble statistics, see cpol_member_stats */
+    cpol_superob *superob;     /* NULL (a zero-initialised struct): off.  Window averages of the fields above, see cpol_superob.
                                    Stays the LAST member */
 } cpol_outputs;
 
@@ -688,6 +740,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * [n_rows * n_gates] float32 (slot ZDR unused, slot RVEL float64, NULL = not given), `so` with host output pointers
  * (rays_per_block = 0: n_rows); blocking; cpol_superob's refusals, and CPOL_ERR_ARG for a requested field without its input.
  * Returns 0.
+ * "member_stats_fields" is its sibling for the ensemble statistics: k_member_fold / k_member_finish and the context's running
+ * state on caller-supplied members.  dst points to { int32_t n_members; int64_t n_cells; const void *in[10]; cpol_member_stats
+ * ms; } -- `in[k]` a host array [n_members][n_cells] (float32, slot RVEL float64; needed for every folded field when n_members
+ * > 0; n_members = 0 folds nothing), `ms` with host output pointers; blocking; honours ms.phase, so a pass can be cut into
+ * calls; cpol_member_stats' refusals (Doppler counts as on).  Returns 0.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
