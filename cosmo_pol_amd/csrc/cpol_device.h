@@ -155,7 +155,9 @@ __device__ __forceinline__ double shfl_f64(double v, int src) {
                                   // absent from its tile (60 % of them on the C2 sweep, 2.4 us of life each) loads nothing, writes nothing, takes its
                                   // ticket and leaves.  Same bits (edges, headline, parity tests), and no gain: pipelined sweep 33.2 against 32.7 us,
                                   // isolated 79.6 against 77.8 (k_interp_sweep pays for the words) -- the wave slots those wavefronts held were not
-                                  // what the kernel waits for (profiles/r6_variants.txt, item 13)
+                                  // what the kernel waits for (profiles/r6_variants.txt, item 13).  Round 9: the words by scalar loads, the absent
+                                  // wavefront returns without a ticket -- +1.6 % on c2, short of the A/B rule; the default build finds its empty
+                                  // wavefronts itself (cpol_gate.inl, profiles/r9_variants.txt)
 #endif
 #if defined(CPOL_SUBSUM_TRACE) || defined(CPOL_LOOKUP_TRACE) || defined(CPOL_INTERP_TRACE)
 // (CPOL_INTERP_TRACE, tools/interp_trace.py: the phases of every wavefront of k_interp_sweep / k_interp_classify)

@@ -500,9 +500,9 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     // form keeps 64 gates of one ray (its scan needs whole rays)
     constexpr bool TILED = RAY && !TICKET;
     const int lane = lane_id();
-    int ray_b = 0, gate_b = 0;
+    int ray_b = 0, gate_b = 0, ray0 = 0, gate0 = 0;
     if (TILED) {
-        int ray0 = 0, gate0 = 0, dray, dgate;
+        int dray, dgate;
         if (!gate1_tile_of_block(gate1_tiles(f.n_rays, f.n_gates), blockIdx.x, ray0, gate0)) return;   // (padding: the whole workgroup)
         gate1_lane_in_tile(lane, dray, dgate);
         ray_b = ray0 + dray;
@@ -517,8 +517,14 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         gate_b = (int)blockIdx.x * 64 + lane;
 #endif
     }
+#ifdef CPOL_SUBSUM_TRACE
+    const unsigned long long g1_enter = wall_clock64();      // the wavefront has its slot (in front of the barrier)
+#endif
     if (threadIdx.x == 0) { s_lookup = 0; s_done = 0; }
     if (LAST_WAVE) __syncthreads();
+#ifdef CPOL_SUBSUM_TRACE
+    const unsigned long long g1_barrier = wall_clock64();    // every wavefront of the workgroup has arrived
+#endif
     const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                    // the wavefront's hydrometeor
     const long i0 = RAY ? (long)ray_b * f.n_gates + gate_b : (long)blockIdx.x * 64 + lane;
     const bool in = TILED ? ray_b < f.n_rays && gate_b < f.n_gates : RAY ? gate_b < f.n_gates : i0 < a.n_sbg;
@@ -533,31 +539,79 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 
     // (round 6) k_interp_sweep's word of this tile: bit q clear = no gate of the tile has a positive mass density of slot q, so the slot
     // has no item here (classify_item: valid needs qm > 0).  The wavefront of such a slot -- 60 % of them on the C2 sweep, 2.4 us of
-    // life each for two loads and 15 LDS columns of zeros -- loads nothing, writes nothing, takes its ticket and leaves; the
+    // life each for two loads and 15 LDS columns of zeros -- loads nothing, writes nothing and leaves; the
     // finishing wavefront reads the same word and leaves the slot's LDS columns alone (x + 0.0f = x: the same bits).
+    // (round 9) The words come through the SCALAR data cache: a tile of R rays x G gates (G <= 64, 64-gate aligned columns) touches
+    // one word per ray at wave-uniform addresses, so R scalar loads in flight together and ORs replace the per-lane vector load and
+    // its six-step shuffle OR.  A ray beyond n_rays reads the word of the sweep's last ray instead, which is a ray of this tile
+    // and in the OR already.  (Measured: 0.7-1.0 us from entry until the words are known, in every wavefront -- another XCD's
+    // k_interp_replay wrote them; profiles/r9_variants.txt.)
+    // The wavefronts of the slots present share the ticket among themselves (n_here of them: the one that finds n_here - 1 tickets
+    // taken finishes the gates); the wavefront of an absent slot has nothing in LDS to hand over, takes no ticket and returns
+    // right here.  Where the tile holds no species at all wavefront 0 stays and finishes the gates from the columns of +0.0f of
+    // the absent-slot branch below; a lone wavefront finishes without the ticket's atomic.
     unsigned pmask = ~0u;
+    int n_here = n_h;                                                                  // wavefronts whose slot is present in the tile
 #if CPOL_GATE1_PRESENT
     if (LAST_WAVE && a.present) {
-        // (the words are per (ray, 64-gate tile): the OR of those the tile's gates lie in, the same in every wavefront)
-        unsigned acc = in ? a.present[(long)ray_b * ((f.n_gates + 63) >> 6) + (gate_b >> 6)] : 0u;
+        constexpr int R = 64 >> CPOL_GATE1_TILE_GATES_LOG2;
+        const unsigned *__restrict__ words = a.present + (__builtin_amdgcn_readfirstlane(gate0) >> 6);     // (the tile's column of words)
+        const unsigned r0 = __builtin_amdgcn_readfirstlane(ray0), nw = (unsigned)(f.n_gates + 63) >> 6;
+        unsigned word[R];                                                              // (the R loads in flight together)
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc |= (unsigned)__shfl_xor((int)acc, off);
-        pmask = __builtin_amdgcn_readfirstlane(acc);
+        for (int r = 0; r < R; ++r) word[r] = words[min(r0 + r, (unsigned)f.n_rays - 1u) * nw];
+        unsigned acc = 0u;
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc |= word[r];
+        pmask = acc;
+        n_here = __popc(pmask & ((1u << n_h) - 1u));
     }
 #endif
     const bool here = (pmask >> j) & 1u;                                               // (wave-uniform)
+#ifdef CPOL_SUBSUM_TRACE
+    unsigned long long g1t[6], g1_valid = 0, g1_hw = 0, g1_pre = 0;
+    if (LAST_WAVE) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const unsigned long long g1_present = wall_clock64();                          // the presence words have arrived
+        // (bits 40-51 / 52-63 of the record's word 6: entry -> barrier passed, entry -> presence known, in ticks of 10 ns)
+        g1_pre = (min(g1_barrier - g1_enter, 4095ull) << 40) | (min(g1_present - g1_enter, 4095ull) << 52);
+        if (!here && !(n_here == 0 && j == 0)) {
+            const unsigned long w = ((unsigned long)blockIdx.y * gridDim.x + blockIdx.x) * n_h + j;
+            if (lane == 0 && w < CPOL_SUBSUM_TRACE_N) {
+                g_subsum_trace[CPOL_SUBSUM_TRACE_W * w] = g1_enter;
+                for (int q = 1; q < 4; ++q) g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + q] = g1_present;
+                g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 5] = 0;
+                g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 6] = ((unsigned long long)j << 32) | g1_pre;
+                g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                                                              (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
+                g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 4] = wall_clock64();          // about to leave
+            }
+        }
+    }
+#endif
+    if (LAST_WAVE && !here && !(n_here == 0 && j == 0)) return;                        // (the slot is free for the next workgroup's wavefronts)
     const bool inl = in && here;
     const float e = inl ? a.elev[i] : 0.f;
     const float T = inl ? a.vals[d.var_t * n + i] : 0.f;
     const float qm = inl ? a.vals[d.var_q * n + i] : 0.f;                              // (q_source == CPOL_Q_MODEL: no melting species here)
 #ifdef CPOL_SUBSUM_TRACE
     // (-DCPOL_SUBSUM_TRACE build, tools/gate1_trace.py: the phases of every wavefront of k_gate1_ray on the 100-MHz clock)
-    unsigned long long g1t[6], g1_valid = 0, g1_hw = 0;
-    g1t[0] = wall_clock64();
+    g1t[0] = LAST_WAVE ? g1_enter : wall_clock64();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     g1t[1] = wall_clock64();                           // the gate's model values have arrived
 #endif
-    ClassItem it;
+    // (round 9) A wavefront none of whose gates has a positive mass density of its species holds no item (classify_item: valid needs
+    // qm > 0): every term it would put into LDS is the +0.0f, the 0.0 and the flag 0 of a slot absent from the tile.  It skips the
+    // parameters, the gather and its 15 LDS columns, says so with a bit beside its ticket, and the finishing wavefront takes the
+    // absent-slot branch for it: the same bits.  (Empty wavefronts are 60 % of a C2 sweep and lived 2.7 us each.)
+    const bool gone = LAST_WAVE && here && !__builtin_amdgcn_ballot_w64(inl && qm > 0.f);      // (wave-uniform)
+    ClassItem it = {};
+    double2 wv = make_double2(0.0, 0.0);
+    int my_lookup = 0;
+#ifdef CPOL_SUBSUM_TRACE
+    g1t[2] = g1t[3] = g1t[1];
+#endif
+    if (!gone) {
     classify_item(h, t, a, a.vals, n, i, i, inl, qm, 0.0, T, d.var_t, e, it);
 #ifdef CPOL_SUBSUM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -566,7 +620,6 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     double2 v[CPOL_N_SZ / 2];
 #pragma unroll
     for (int c = 0; c < CPOL_N_SZ / 2; ++c) v[c] = make_double2(0.0, 0.0);
-    double2 wv = make_double2(0.0, 0.0);
     bool have = false;
 #if CPOL_GATE1_LDS
     {
@@ -676,7 +729,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         g1t[3] = wall_clock64();                       // coefficient gather + Horner chains
     }
 #endif
-    int my_lookup = it.lookup ? 1 : 0;
+    my_lookup = it.lookup ? 1 : 0;
     bool off_table = it.valid && !it.lookup;
     if (RAY) {
         // (items outside the integral table: integrated further down, when the columns of the others have left the registers)
@@ -735,6 +788,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) my_lookup += __shfl_xor(my_lookup, off);
+    }   // (!gone)
     if (LAST_WAVE) {
         // this wavefront's share of the sweep's table-item count, then its ticket: release (its LDS stores are complete),
         // acquire for the wavefront that finds every other ticket taken
@@ -742,15 +796,22 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
             const unsigned slot = ((blockIdx.x + blockIdx.y * gridDim.x) * 4u + (unsigned)j) & (CPOL_COUNT_SLOTS - 1);
             atomicAdd(a.n_lookup + 2 + slot, my_lookup);
         }
-        int old = 0;
-        if (lane == 0) old = __hip_atomic_fetch_add(&s_done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-        old = __builtin_amdgcn_readfirstlane(old);
+        // (the tickets count in the low byte; above it bit 8 + q: the wavefront of slot q had no item -- `gone`)
+        const unsigned mine = gone ? 0x100u << j : 0u;
+        int old = n_here - 1;                         // (n_here <= 1: nobody to wait for -- no atomic)
+        unsigned gone_slots = mine >> 8;
+        if (n_here > 1) {
+            if (lane == 0) old = __hip_atomic_fetch_add(&s_done, (int)(1u + mine), __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            old = __builtin_amdgcn_readfirstlane(old);
+            gone_slots |= (unsigned)old >> 8;
+            old &= 0xFF;
+        }
 #ifdef CPOL_SUBSUM_TRACE
         g1t[4] = wall_clock64();                       // terms in LDS, ticket taken
-        g1_valid = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(it.valid)) | ((unsigned long long)j << 32);
+        g1_valid = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(it.valid)) | ((unsigned long long)j << 32) | g1_pre;
         g1_hw = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                 (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
-        if (old != n_h - 1) {
+        if (old != n_here - 1) {
             const unsigned long w = ((unsigned long)blockIdx.y * gridDim.x + blockIdx.x) * n_h + j;
             if (lane == 0 && w < CPOL_SUBSUM_TRACE_N) {
                 for (int q = 0; q < 5; ++q) g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + q] = g1t[q];
@@ -760,8 +821,9 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
             }
         }
 #endif
-        if (old != n_h - 1) return;                   // (not the last: the slot is free for the next workgroup's wavefronts)
+        if (old != n_here - 1) return;                // (not the last of the slots present: the slot is free for the next workgroup's wavefronts)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        pmask &= ~gone_slots;                         // (their LDS columns were never written)
     } else {
     __syncthreads();                                  // (s_lookup = 0 is visible; the species' terms are in LDS)
     if (lane == 0 && my_lookup) atomicAdd(&s_lookup, my_lookup);

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Where a wavefront of k_gate1_ray spends its time (library built with -DCPOL_SUBSUM_TRACE):
    tools/variants.sh "g1trace|-DCPOL_SUBSUM_TRACE||python tools/gate1_trace.py"
-Every wavefront (gate tile, ray, species) records the 100-MHz clock at: start, model values arrived, PSD parameters done,
-gather + Horner done, terms in LDS + ticket taken, and -- the wavefront that took the last ticket -- gates finished.
+Every wavefront (gate tile, ray, species) records the 100-MHz clock at: entry (in front of the workgroup barrier), barrier
+passed, presence words arrived, model values arrived, PSD parameters done, gather + Horner done, terms in LDS + ticket taken,
+and -- the wavefront that finishes the tile -- gates finished.  A wavefront that returns behind the presence test (its
+species absent from the tile) records entry, barrier, presence and the moment it leaves; its life is entry -> leaving.
 ONE isolated c2 sweep on one lane (CPOL_GATE1_RAY=1), and one of three lanes in flight."""
 import contextlib
 import json
@@ -22,10 +24,12 @@ def report(tag, tr):
     used = tr[:, 0] > 0
     t = tr[used].astype(np.int64)
     nv = (tr[used, 6] & np.uint64(0xFFFFFFFF)).astype(np.int64)
-    sp = (tr[used, 6] >> np.uint64(32)).astype(np.int64)
+    sp = ((tr[used, 6] >> np.uint64(32)) & np.uint64(0xFF)).astype(np.int64)
+    t_bar = ((tr[used, 6] >> np.uint64(40)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> barrier passed
+    t_pre = ((tr[used, 6] >> np.uint64(52)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> presence words known
     base = t[:, 0].min()
     us = lambda a: a / 100.0
-    ph = np.stack([t[:, 1] - t[:, 0], t[:, 2] - t[:, 1], t[:, 3] - t[:, 2], t[:, 4] - t[:, 3]], axis=1)
+    ph = np.stack([np.maximum(t[:, 1] - t[:, 0] - t_pre, 0), t[:, 2] - t[:, 1], t[:, 3] - t[:, 2], t[:, 4] - t[:, 3]], axis=1)
     last = t[:, 5] > 0
     fin = np.where(last, t[:, 5] - t[:, 4], 0)
     life = np.where(last, t[:, 5], t[:, 4]) - t[:, 0]
@@ -36,6 +40,9 @@ def report(tag, tr):
     for name, m in (('with_items', heavy), ('empty', ~heavy)):
         if m.any():
             out[name] = {'n': int(m.sum()), 'mean_valid_lanes': round(float(nv[m].mean()), 1),
+                         'us_barrier': round(float(us(t_bar[m]).mean()), 2), 'us_presence': round(float(us(t_pre[m] - t_bar[m]).mean()), 2),
+                         'finishers': int((m & last).sum()),
+                         'us_life_not_finishing': round(float(us(life[m & ~last]).mean()), 2) if (m & ~last).any() else None,
                          'us_values': round(float(us(ph[m, 0]).mean()), 2), 'us_parameters': round(float(us(ph[m, 1]).mean()), 2),
                          'us_gather_horner': round(float(us(ph[m, 2]).mean()), 2), 'us_lds_ticket': round(float(us(ph[m, 3]).mean()), 2),
                          'us_life_mean': round(float(us(life[m]).mean()), 2), 'us_life_p95': round(float(np.percentile(us(life[m]), 95)), 2)}
