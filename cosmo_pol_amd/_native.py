@@ -109,12 +109,16 @@ MEMBER_STATS_KINDS = ('mean', 'spread', 'min', 'max')
 
 class MemberStats(C.Structure):
     """cpol_member_stats: the call's member(s) folded into the context's running ensemble statistics
-    (cosmo_pol_amd/ensemble_stats.py states the rule).  phase: bit 0 begins a pass, bit 1 finishes it."""
+    (cosmo_pol_amd/ensemble_stats.py states the rule).  phase: bit 0 begins a pass, bit 1 finishes it.  The quantile terms
+    are appended: a zero-initialised struct has none."""
     _fields_ = ([('phase', C.c_int32), ('min_members', C.c_int32), ('fields', C.c_uint32),
                  ('n_thresholds', C.c_int32 * len(MEMBER_STATS_FIELDS)), ('pad_', C.c_int32),
                  ('thresholds', C.c_void_p * len(MEMBER_STATS_FIELDS))]
                 + [(n, C.c_void_p * len(MEMBER_STATS_FIELDS)) for n in MEMBER_STATS_KINDS]
-                + [('count', C.c_void_p), ('exceed', C.c_void_p * len(MEMBER_STATS_FIELDS))])
+                + [('count', C.c_void_p), ('exceed', C.c_void_p * len(MEMBER_STATS_FIELDS)),
+                   ('quantile_capacity', C.c_int32), ('quantile_method', C.c_int32),
+                   ('n_quantiles', C.c_int32 * len(MEMBER_STATS_FIELDS)), ('quantiles', C.c_void_p * len(MEMBER_STATS_FIELDS)),
+                   ('quantile', C.c_void_p * len(MEMBER_STATS_FIELDS))])
 
 
 class Outputs(C.Structure):
@@ -858,9 +862,10 @@ class Context(object):
         return out
 
     @staticmethod
-    def member_stats_struct(spec, names, phase):
+    def member_stats_struct(spec, names, phase, capacity=None):
         """(MemberStats for a call of a pass that folds the fields `names` under `spec` (an ensemble_stats.EnsembleStats),
-        what keeps its threshold arrays alive)."""
+        what keeps its threshold and quantile arrays alive).  `capacity`: the members the whole pass holds, read when `spec`
+        is an EnsembleQuantiles (the device keeps that many rows per field with quantiles); None: the limit of 128."""
         ms = MemberStats()
         ms.phase, ms.min_members = int(phase), spec.min_members
         keep = []
@@ -871,14 +876,27 @@ class Context(object):
             if thr.size:
                 keep.append(thr)
                 ms.n_thresholds[i], ms.thresholds[i] = thr.size, thr.ctypes.data
+        qs = getattr(spec, 'quantiles', None)
+        if qs:
+            from . import ensemble_stats as ES
+            ms.quantile_capacity = ES.MAX_QUANTILE_MEMBERS if capacity is None else int(capacity)
+            ms.quantile_method = ES.METHODS.index(spec.method)
+            for k in names:
+                if k in qs:
+                    i = MEMBER_STATS_FIELDS.index(k)
+                    q = np.ascontiguousarray(qs[k], dtype=np.float64)
+                    keep.append(q)
+                    ms.n_quantiles[i], ms.quantiles[i] = q.size, q.ctypes.data
         return ms, keep
 
-    def member_stats_fields(self, fields, spec, phase=3, n_cells=None, names=None):
+    def member_stats_fields(self, fields, spec, phase=3, n_cells=None, names=None, capacity=None):
         """Test hook (cpol_debug_read "member_stats_fields"): the product's k_member_fold / k_member_finish and this context's
         running state on caller-supplied members {name: [n_members, n_cells]} of MEMBER_STATS_FIELDS (float32; RVEL float64).
         `spec`: an ensemble_stats.EnsembleStats; `phase`: bit 0 begins a pass, bit 1 finishes it -- a pass may be cut into
-        calls; `fields` may be empty (no member; then `n_cells` and `names` say what the pass holds).  A finishing call
-        returns what ensemble_stats.finish returns, every other call None."""
+        calls; `fields` may be empty (no member; then `n_cells` and `names` say what the pass holds).  `capacity` (an
+        EnsembleQuantiles): the members of the whole pass; None: those of this call, and at least 1.  A finishing call
+        returns what ensemble_stats.finish returns ('quantile' included when `spec` asks for quantiles), every other call
+        None."""
         class Hook(C.Structure):
             _fields_ = [('n_members', C.c_int32), ('n_cells', C.c_int64), ('inp', C.c_void_p * len(MEMBER_STATS_FIELDS)),
                         ('ms', MemberStats)]
@@ -898,7 +916,7 @@ class Context(object):
         if shape is None:
             shape = (0, int(n_cells))
         h.n_members, h.n_cells = shape
-        h.ms, thr_keep = self.member_stats_struct(spec, names, phase)
+        h.ms, thr_keep = self.member_stats_struct(spec, names, phase, capacity=max(shape[0], 1) if capacity is None else capacity)
         out = None
         if int(phase) & 2:
             nc = shape[1]
@@ -912,6 +930,11 @@ class Context(object):
                 if k in out['exceed']:
                     h.ms.exceed[i] = out['exceed'][k].ctypes.data
             h.ms.count = cnt.ctypes.data
+            qs = getattr(spec, 'quantiles', None)
+            if qs:
+                out['quantile'] = {k: np.empty((len(qs[k]), nc), dtype=np.float64 if k == 'RVEL' else np.float32) for k in names if k in qs}
+                for k, a in out['quantile'].items():
+                    h.ms.quantile[MEMBER_STATS_FIELDS.index(k)] = a.ctypes.data
         rc = int(self.lib.cpol_debug_read(self.h, b'member_stats_fields', C.byref(h), C.sizeof(h)))
         self._check(rc, 'cpol_debug_read(member_stats_fields)')
         del keep, thr_keep

@@ -174,6 +174,7 @@ struct cpol_ctx {
     // ensemble statistics (cpol_member_stats): the running state of this context's pass, and the block k_member_finish writes
     // when the outputs are host memory outside a window image
     DevBuf b_mstate, b_msout;
+    DevBuf b_mstash;                       // ... and the members of the fields with quantiles: [capacity][n_cells] each, sized when a pass begins
     struct MemberPass {
         bool open = false;
         long n_cells = 0, folded = 0;
@@ -182,6 +183,12 @@ struct cpol_ctx {
         int n_thr[CPOL_MS_FIELDS] = {};
         double thr[CPOL_MS_FIELDS][CPOL_MS_MAX_THR] = {};
         MemberState st[CPOL_MS_FIELDS] = {};
+        // quantiles: the terms as the caller gave them, and each such field's stash
+        int q_capacity = 0, q_method = 0;
+        bool q_any = false;
+        int n_q[CPOL_MS_FIELDS] = {};
+        double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q] = {};
+        void *stash[CPOL_MS_FIELDS] = {};
     } mpass;
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
@@ -758,7 +765,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_mstate, &ctx->b_msout, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -1964,13 +1971,16 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
 // ---- ensemble statistics (cpol_member_stats, cpol_member_stats.inl): the checks, the pass and the launches, shared by the
 // launch sequence and the test hook ----
 enum { MS_MEAN = 0, MS_SPREAD = CPOL_MS_FIELDS, MS_MIN = 2 * CPOL_MS_FIELDS, MS_MAX = 3 * CPOL_MS_FIELDS, MS_COUNT = 4 * CPOL_MS_FIELDS,
-       MS_EXCEED, MS_N = MS_EXCEED + CPOL_MS_FIELDS };
+       MS_EXCEED, MS_QUANTILE = MS_EXCEED + CPOL_MS_FIELDS, MS_N = MS_QUANTILE + CPOL_MS_FIELDS };
 struct MemberStatsPlan {
     long cells;
     int n_sets;
     bool begin, finish;
     int n_thr[CPOL_MS_FIELDS];
     double thr[CPOL_MS_FIELDS][CPOL_MS_MAX_THR];    // as the kernels compare them (float32 fields: rounded once)
+    bool q_any;                                     // a folded field has quantiles
+    int n_q[CPOL_MS_FIELDS];
+    double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q];
     void *user[MS_N];                               // a finishing call: the caller's pointers (folded fields only)
     size_t bytes[MS_N];
 };
@@ -2002,6 +2012,22 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
             pl->thr[k][t] = k == CPOL_MS_RVEL ? v : (double)(float)v;
         }
     }
+    if (ms->quantile_method < 0 || ms->quantile_method > 3) return bad("quantile_method must lie in 0..3 (linear, lower, higher, nearest)");
+    if (ms->quantile_capacity < 0 || ms->quantile_capacity > CPOL_MS_MAX_Q_MEMBERS) return bad("quantile_capacity must lie in 0..128");
+    for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+        const int nq = ms->n_quantiles[k];
+        if (nq < 0 || nq > CPOL_MS_MAX_Q) return bad("n_quantiles must lie in 0..8");
+        if (!((ms->fields >> k) & 1u) || nq == 0) continue;   // (the quantile lists of a field that is not folded are not read)
+        if (!ms->quantiles[k]) return bad("n_quantiles > 0 needs the quantiles");
+        if (ms->quantile_capacity == 0) return bad("quantiles need quantile_capacity >= 1");
+        pl->n_q[k] = nq;
+        pl->q_any = true;
+        for (int t = 0; t < nq; ++t) {
+            const double v = ms->quantiles[k][t];
+            if (!(v >= 0.0 && v <= 1.0)) return bad("a quantile is NaN or outside [0, 1]");
+            pl->q[k][t] = v;
+        }
+    }
     if (!pl->begin) {
         if (!ps.open) return bad("no pass is open: the first call of a pass carries the begin bit");
         bool same = ps.n_cells == n_cells && ps.fields == ms->fields && ps.min_members == ms->min_members;
@@ -2010,7 +2036,15 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
             for (int t = 0; t < pl->n_thr[k] && same; ++t) same = ps.thr[k][t] == pl->thr[k][t];
         }
         if (!same) return bad("n_cells, fields, thresholds or min_members differ from the open pass");
+        same = ps.q_capacity == ms->quantile_capacity && ps.q_method == ms->quantile_method;
+        for (int k = 0; k < CPOL_MS_FIELDS && same; ++k) {
+            same = ps.n_q[k] == pl->n_q[k];
+            for (int t = 0; t < pl->n_q[k] && same; ++t) same = ps.q[k][t] == pl->q[k][t];
+        }
+        if (!same) return bad("quantile_capacity, quantile_method or the quantiles differ from the open pass");
     }
+    if (pl->q_any && (pl->begin ? 0 : ps.folded) + n_sets > ms->quantile_capacity)
+        return bad("more members than quantile_capacity in a pass with quantiles");
     if ((pl->begin ? 0 : ps.folded) + n_sets > 65535) return bad("more than 65535 members in a pass (the counts are uint16)");
     if (pl->finish) {
         bool any = false;
@@ -2022,6 +2056,10 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
             if (pl->n_thr[k] > 0) {
                 pl->user[MS_EXCEED + k] = ms->exceed[k];
                 pl->bytes[MS_EXCEED + k] = (size_t)pl->n_thr[k] * n_cells * sizeof(uint16_t);
+            }
+            if (pl->n_q[k] > 0) {
+                pl->user[MS_QUANTILE + k] = ms->quantile[k];
+                pl->bytes[MS_QUANTILE + k] = (size_t)pl->n_q[k] * n_cells * w;
             }
         }
         pl->user[MS_COUNT] = ms->count;
@@ -2060,8 +2098,22 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
         size_t total = 0;
         for (int k = 0; k < CPOL_MS_FIELDS; ++k)
             if ((ms->fields >> k) & 1u) total += a2 + 2 * a8 + 2 * (k == CPOL_MS_RVEL ? a8 : a4) + (size_t)pl.n_thr[k] * a2;
+        size_t stash_total = 0;                               // the members of the fields with quantiles: [capacity][cells] each
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k)
+            if (pl.n_q[k] > 0) stash_total += ((size_t)ms->quantile_capacity * pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)) + 255) & ~(size_t)255;
         ps.open = false;                                      // (a begin that fails below leaves no pass behind)
         ENSURE(ctx->b_mstate, total);
+        if (stash_total) ENSURE(ctx->b_mstash, stash_total);
+        char *qs = (char *)ctx->b_mstash.p;
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+            ps.stash[k] = nullptr;
+            if (pl.n_q[k] == 0) continue;
+            ps.stash[k] = qs;
+            qs += ((size_t)ms->quantile_capacity * pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)) + 255) & ~(size_t)255;
+        }
+        ps.q_capacity = ms->quantile_capacity; ps.q_method = ms->quantile_method; ps.q_any = pl.q_any;
+        memcpy(ps.n_q, pl.n_q, sizeof ps.n_q);
+        memcpy(ps.q, pl.q, sizeof ps.q);
         char *q = (char *)ctx->b_mstate.p;
         for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
             ps.st[k] = MemberState{};
@@ -2085,7 +2137,9 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
         a.in[k] = in[k];
         a.st[k] = ps.st[k];
         a.n_thr[k] = ps.n_thr[k];
+        a.stash[k] = ps.stash[k];
     }
+    a.row0 = (int)ps.folded;
     memcpy(a.thr, ps.thr, sizeof a.thr);
     a.n_sets = pl.n_sets; a.begin = pl.begin; a.need = ps.min_members; a.n_cells = pl.cells;
     const dim3 grid(cdiv(pl.cells, 256), a.n_fields);
@@ -2103,6 +2157,25 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
         a.zero_rest = zero_rest;
         hipLaunchKernelGGL(k_member_finish, grid, dim3(256), 0, st, a);
         HIPCHK(hipGetLastError());
+        // the quantiles of the fields that have them and whose output is wanted: one wavefront per 64 cells, each lane's counting
+        // members sorted in its own LDS column (members x 64 keys of the widest field: <= 32 KiB, with RVEL <= 64 KiB)
+        MemberQuantileArgs qa{};
+        int n_qf = 0;
+        size_t key_bytes = sizeof(float);
+        for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+            if (ps.n_q[k] == 0 || !ps.stash[k] || !T[MS_QUANTILE + k]) continue;
+            qa.field[n_qf++] = k;
+            qa.stash[k] = ps.stash[k];
+            qa.out[k] = T[MS_QUANTILE + k];
+            qa.n_q[k] = ps.n_q[k];
+            if (k == CPOL_MS_RVEL) key_bytes = sizeof(double);
+        }
+        if (n_qf > 0) {                                       // (member_stats_plan: folded <= quantile_capacity <= 128)
+            memcpy(qa.q, ps.q, sizeof qa.q);
+            qa.members = (int)ps.folded; qa.method = ps.q_method; qa.need = ps.min_members; qa.n_cells = pl.cells;
+            hipLaunchKernelGGL(k_member_quantile, dim3(cdiv(pl.cells, 64), n_qf), dim3(64), (size_t)ps.folded * 64 * key_bytes, st, qa);
+            HIPCHK(hipGetLastError());
+        }
         ps.open = false;
     }
     return CPOL_OK;

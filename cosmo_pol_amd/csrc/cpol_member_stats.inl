@@ -1,5 +1,7 @@
 // cpol_member_stats.inl -- ensemble statistics: the members of a pass folded, one after another, into a running state per gate
-// (cpol_member_stats): mean, spread, extremes, the members that count and the members above thresholds.
+// (cpol_member_stats): mean, spread, extremes, the members that count and the members above thresholds; and, for the fields
+// that ask for them, quantiles of the members (k_member_quantile: the fold stashes the members, a finishing call sorts each
+// cell's counting members in LDS and reads the order statistics).
 //
 // Reference functions replaced (wolfidan/cosmo_pol): none -- the reference runs one model state per process.  The rule is the
 // one of include/cosmo_pol_amd.h and cosmo_pol_amd/ensemble_stats.py (`fold`, `finish`), ORDER-EXACT: a strict left fold over
@@ -11,6 +13,8 @@
 #define CPOL_MS_FIELDS 10           // ZH, ZV, ZDR, KDP, DELTA_HV, PHIDP, RHOHV, ATT_H, ATT_V, RVEL (the rows of `count`)
 #define CPOL_MS_RVEL 9
 #define CPOL_MS_MAX_THR 8
+#define CPOL_MS_MAX_Q 8
+#define CPOL_MS_MAX_Q_MEMBERS 128
 
 // the running state of one folded field, SoA: the lanes of a wavefront touch consecutive addresses of every array
 struct MemberState {
@@ -36,6 +40,22 @@ struct MemberStatsArgs {
     unsigned short *o_count;                // [10][n_cells] or NULL
     unsigned short *o_exceed[CPOL_MS_FIELDS];
     int zero_rest;                          // 1: the rows of `count` of fields not folded are written as zeros
+    // quantiles: where k_member_fold keeps the members of a field with quantiles ([capacity][n_cells] of the field's type; NULL:
+    // the field has none), and the row of this call's first member
+    void *stash[CPOL_MS_FIELDS];
+    int row0;
+};
+
+struct MemberQuantileArgs {
+    const void *stash[CPOL_MS_FIELDS];      // [members][n_cells] of the field's type, rows in fold order
+    void *out[CPOL_MS_FIELDS];              // [n_q][n_cells] of the field's type
+    double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q];
+    int n_q[CPOL_MS_FIELDS];
+    int field[CPOL_MS_FIELDS];              // the fields with quantiles whose output is wanted = gridDim.y
+    int members;                            // rows of the stash that hold a member (<= 128): the LDS column's height
+    int method;                             // 0 linear, 1 lower, 2 higher, 3 nearest
+    int need;
+    long n_cells;
 };
 
 // x / n (n a whole number, 1 <= n <= 65535) rounded ONCE, whatever the quotient.  The device's float64 division is correctly
@@ -76,8 +96,10 @@ __device__ __forceinline__ void member_fold_field(const MemberStatsArgs &a, int 
             if (t < n_thr) k[t] = s.k[(long)t * a.n_cells + c];
     }
     const T *__restrict__ x = (const T *)a.in[f];
+    T *const stash = (T *)a.stash[f];         // (wave-uniform: a pass without quantiles runs what it ran without them)
     for (int m = 0; m < a.n_sets; ++m) {
         const T v = x[(long)m * a.n_cells + c];
+        if (stash) stash[(long)(a.row0 + m) * a.n_cells + c] = v;
         if (v == v) {
             n = n + 1;
             const double d = (double)v - mean;
@@ -135,4 +157,89 @@ __global__ __launch_bounds__(256) void k_member_finish(const MemberStatsArgs a)
         for (int j = 0; j < CPOL_MS_FIELDS; ++j)
             if (!((folded >> j) & 1u)) a.o_count[(long)j * a.n_cells + c] = 0;
     }
+}
+
+// ---- quantiles ----
+// The rule's order as an unsigned compare: the bits of a negative value flipped, the sign bit of a non-negative one set
+// (-0.0 before +0.0, -inf first, +inf last; NaNs never get here).
+__device__ __forceinline__ unsigned member_key(float v)
+{
+    const unsigned u = __float_as_uint(v);
+    return (u >> 31) ? ~u : u | 0x80000000u;
+}
+__device__ __forceinline__ unsigned long long member_key(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : u | 0x8000000000000000ull;
+}
+__device__ __forceinline__ float member_unkey(unsigned k) { return __uint_as_float((k >> 31) ? k & 0x7fffffffu : ~k); }
+__device__ __forceinline__ double member_unkey(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k));
+}
+
+// One lane per cell; the lane's counting members as keys, sorted by insertion, in its own LDS column col[j * 64] (layout
+// [member][lane]: the lanes of a wavefront touch consecutive words, a lane's column walks at stride 64 words).  No lane reads
+// another lane's column: no barrier.
+template <typename T, typename K>
+__device__ __forceinline__ void member_quantile_field(const MemberQuantileArgs &a, int f, long c, K *__restrict__ col)
+{
+    const T *__restrict__ x = (const T *)a.stash[f];
+    int n = 0;
+    for (int m = 0; m < a.members; ++m) {
+        const T v = x[(long)m * a.n_cells + c];
+        if (v == v) {
+            const K key = member_key(v);
+            int j = n;
+            while (j > 0) {
+                const K prev = col[(j - 1) * 64];
+                if (!(key < prev)) break;
+                col[j * 64] = prev;
+                --j;
+            }
+            col[j * 64] = key;
+            ++n;
+        }
+    }
+    T *__restrict__ out = (T *)a.out[f];
+    const int n_q = a.n_q[f];
+    for (int t = 0; t < n_q; ++t) {
+        T r = (T)__builtin_nan("");
+        if (n >= a.need && n > 0) {
+            const double h = a.q[f][t] * (double)(n - 1);       // 0 <= h <= n - 1
+            int i = (int)h;                                     // floor
+            if (a.method == 0) {
+                const double g = h - (double)i;
+                const T xa = member_unkey(col[i * 64]);
+                r = xa;
+                if (g != 0.0) {                                 // (then i + 1 <= n - 1)
+                    const T xb = member_unkey(col[(i + 1) * 64]);
+                    const double da = (double)xa, db = (double)xb;
+                    if (da != db) {
+                        const double d = db - da;
+                        const double p = g * d;
+                        double s = da + p;
+                        if (s > db) s = db;
+                        r = (T)s;
+                    }
+                }
+            } else {
+                if (a.method == 2) i += (double)i < h;
+                else if (a.method == 3) i = (int)__builtin_rint(h);
+                r = member_unkey(col[i * 64]);
+            }
+        }
+        out[(long)t * a.n_cells + c] = r;
+    }
+}
+
+// Grid (cells / 64, fields with quantiles); ONE wavefront per workgroup; dynamic LDS: members x 64 keys of the widest field.
+__global__ __launch_bounds__(64) void k_member_quantile(const MemberQuantileArgs a)
+{
+    extern __shared__ unsigned long long member_q_lds[];
+    const long c = (long)blockIdx.x * 64 + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const int f = a.field[blockIdx.y];
+    if (f == CPOL_MS_RVEL) member_quantile_field<double, unsigned long long>(a, f, c, member_q_lds + threadIdx.x);
+    else member_quantile_field<float, unsigned>(a, f, c, (unsigned *)member_q_lds + threadIdx.x);
 }

@@ -23,18 +23,49 @@ operation one IEEE operation.  Finishing, need = min_members >= 1:
     sample standard deviation);  min = lo and max = hi where n >= need, else NaN;  count = n and exceed_t = k_t always
 Counts, not probabilities: `probability` divides by the members folded (a NaN reads as "no echo", the right reading of a
 censored gate) or by the members that counted.  A strict left fold: the result does not depend on how the member list was
-cut into calls.  At most 65535 members per pass and 8 thresholds per field."""
+cut into calls.  At most 65535 members per pass and 8 thresholds per field.
+
+Quantiles (EnsembleQuantiles; k_member_quantile on the device).  Per cell and per field with quantiles:
+    the counting values of the pass -- the members' values v with v == v, exactly the ones the fold counts, n of them -- are
+    ordered ascending by <, with -0.0 before +0.0: a total order on everything that is not NaN, +-inf included.  Sorted they
+    are x[0] ... x[n-1].  For a quantile q in [0, 1]: h = q * float64(n - 1), one IEEE multiplication.  One method per pass:
+    linear (0): i = floor(h); g = h - float64(i); a = float64(x[i]).  g == 0: a.  Else b = float64(x[i+1]); a == b: a.  Else
+                r = a + g * (b - a), three separate float64 operations, then if r > b: r = b.  The quantile is T(r), rounded once.
+                An infinite bracket gives what IEEE gives: between -inf and any other value that is NaN, between a finite
+                value and +inf it is +inf.
+    lower (1): x[floor(h)];  higher (2): x[ceil(h)];  nearest (3): x[rint(h)], ties to even.  These three return a member's own
+                bits and make no trip through float64, so they commute with every increasing map (`db`).
+    The result is NaN where n < need (min_members, as for the mean).
+Because the order is total the quantiles are a symmetric function of the members: they depend neither on the order of the member
+list nor on how the pass is cut into calls (unlike the last bits of the mean).  At most 8 quantiles per field, and a pass with
+quantiles holds at most 128 members: the device keeps every member of such a field until the pass finishes."""
 import numpy as np
 
 # the rows of cpol_member_stats.count, in this order (= superob.FIELDS)
 FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL')
 MAX_MEMBERS = 65535
 MAX_THRESHOLDS = 8
+MAX_QUANTILES = 8
+MAX_QUANTILE_MEMBERS = 128
+METHODS = ('linear', 'lower', 'higher', 'nearest')      # cpol_member_stats.quantile_method, in this order
 KINDS = ('mean', 'spread', 'min', 'max')
 
 
 def dtype_of(field):
     return np.float64 if field == 'RVEL' else np.float32
+
+
+def db(x):
+    """10 * log10 of a linear array, computed in float64 and rounded once to the array's own float type: dBZ of ZH and ZV, dB
+    of ZDR.  log10 is increasing, and an
+    order statistic commutes with an increasing map: the 'lower', 'higher' and 'nearest' quantiles of a linear field ARE the
+    quantiles of the field in dB after db() on the result, bit for bit.  'linear' interpolates between two members and does
+    not commute (nor do mean and spread)."""
+    x = np.asarray(x)
+    if x.dtype.kind != 'f':
+        x = x.astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return (10.0 * np.log10(x.astype(np.float64))).astype(x.dtype)
 
 
 def dbz(x):
@@ -107,9 +138,117 @@ class EnsembleStats(object):
             self.mean, self.spread, self.extremes, {k: list(v) for k, v in self.exceed.items()}, self.fields, self.min_members)
 
 
+class EnsembleQuantiles(EnsembleStats):
+    """EnsembleStats plus QUANTILES of the members per gate: `quantiles` {field: [q, ...]} (a scalar is accepted), each q in
+    [0, 1], at most 8 per field; `method`: 'linear' (the default), 'lower', 'higher' or 'nearest', one for the pass (the rule
+    at the top of this module).  The other keywords are those of EnsembleStats.  The result gains 'quantile': {field: array
+    [n_q, ...cells] in the field's type}.  A pass with quantiles holds at most 128 members.  ValueError for an unknown field,
+    a field outside `fields`, 0 or more than 8 values for a field, a q that is NaN or outside [0, 1], an unknown method."""
+
+    def __init__(self, quantiles, method='linear', **kw):
+        EnsembleStats.__init__(self, **kw)
+        if method not in METHODS:
+            raise ValueError('EnsembleQuantiles: method %r (one of %s)' % (method, METHODS))
+        self.method = method
+        if not isinstance(quantiles, dict):
+            raise ValueError('EnsembleQuantiles: quantiles is {field: [q, ...]}, got %r' % (quantiles,))
+        self.quantiles = {}
+        for k, q in quantiles.items():
+            if k not in FIELDS:
+                raise ValueError('EnsembleQuantiles: quantiles: unknown field %r' % (k,))
+            if self.fields is not None and k not in self.fields:
+                raise ValueError('EnsembleQuantiles: quantiles: %r is not among the folded fields %r' % (k, self.fields))
+            q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+            if q.ndim != 1 or not 1 <= q.size <= MAX_QUANTILES:
+                raise ValueError('EnsembleQuantiles: quantiles[%r]: 1 to %d values, got shape %r' % (k, MAX_QUANTILES, q.shape))
+            if not np.all((q >= 0.0) & (q <= 1.0)):         # (false for NaN)
+                raise ValueError('EnsembleQuantiles: quantiles[%r]: every q lies in [0, 1], got %r' % (k, list(q)))
+            self.quantiles[k] = q.copy()
+
+    @classmethod
+    def median(cls, fields=None, **kw):
+        """The median (q = 0.5) of `fields` (None: of the fields of the `fields` keyword, or of every field of FIELDS but
+        RVEL, which needs a Doppler scheme)."""
+        if fields is None:
+            fields = kw.get('fields') or FIELDS[:-1]
+        return cls({k: [0.5] for k in fields}, **kw)
+
+    def resolve(self, available):
+        names = EnsembleStats.resolve(self, available)
+        for k in self.quantiles:
+            if k not in names:
+                raise ValueError('EnsembleQuantiles: field %r is not produced by this call (RVEL needs a Doppler scheme)' % (k,))
+        return names
+
+    @property
+    def key(self):
+        return EnsembleStats.key.fget(self) + (self.method, tuple((k, tuple(v)) for k, v in sorted(self.quantiles.items())))
+
+    def __repr__(self):
+        return 'EnsembleQuantiles(quantiles=%r, method=%r, mean=%r, spread=%r, extremes=%r, exceed=%r, fields=%r, min_members=%d)' % (
+            {k: list(v) for k, v in self.quantiles.items()}, self.method, self.mean, self.spread, self.extremes,
+            {k: list(v) for k, v in self.exceed.items()}, self.fields, self.min_members)
+
+
+def _quantiles_of(spec):
+    return getattr(spec, 'quantiles', None) or {}
+
+
+def order_key(x):
+    """The monotone integer key of the rule's order: the bits of a negative value flipped, the sign bit of a non-negative one
+    set -- -0.0 comes before +0.0.  NaN gets the largest key (no other value has it)."""
+    x = np.asarray(x)
+    U = {4: np.uint32, 8: np.uint64}[x.dtype.itemsize]
+    u = x.view(U)
+    sign = U(1) << U(8 * x.dtype.itemsize - 1)
+    key = np.where(u & sign != 0, ~u, u | sign)
+    return np.where(x != x, ~U(0), key)
+
+
+def quantiles(x, q, method='linear', need=1):
+    """The rule's quantiles `q` of the members x [n_members, ...cells] (float32 or float64) -> [len(q), ...cells] in x's type."""
+    x = np.asarray(x)
+    T = x.dtype.type
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    cells = x.shape[1:]
+    out = np.full((len(q),) + cells, np.nan, T)
+    if x.shape[0] == 0:
+        return out
+    order = np.argsort(order_key(x), axis=0, kind='stable')       # (NaNs last; equal keys are equal bits)
+    xs = np.take_along_axis(x, order, axis=0)
+    n = np.sum(x == x, axis=0).astype(np.int64)
+    top = np.maximum(n - 1, 0)
+
+    def at(i):
+        return np.take_along_axis(xs, np.minimum(i, top)[None], axis=0)[0]
+
+    with np.errstate(all='ignore'):
+        for t, qt in enumerate(q):
+            h = qt * (n - 1).astype(np.float64)
+            if method == 'linear':
+                i = np.floor(h)
+                g = h - i
+                i = i.astype(np.int64)
+                a, b = at(i).astype(np.float64), at(i + 1).astype(np.float64)
+                d = b - a
+                r = a + g * d
+                r = np.where(r > b, b, r)
+                r = np.where((g == 0.0) | (a == b), a, r).astype(T)
+            elif method == 'lower':
+                r = at(np.floor(h).astype(np.int64))
+            elif method == 'higher':
+                r = at(np.ceil(h).astype(np.int64))
+            elif method == 'nearest':
+                r = at(np.rint(h).astype(np.int64))
+            else:
+                raise ValueError('quantiles: method %r (one of %s)' % (method, METHODS))
+            out[t] = np.where(n >= need, r, T(np.nan))
+    return out
+
+
 def begin(spec, fields, shape):
     """The state of a pass that has folded nothing: {'spec', 'n_members', 'fields': {name: {'n', 'mean', 'M2', 'lo', 'hi',
-    'k'}}} for cells of `shape`."""
+    'k'}}} for cells of `shape`; a field with quantiles also keeps its members, 'x': the rows in fold order."""
     shape = tuple(shape)
     st = {}
     for k in fields:
@@ -118,6 +257,8 @@ def begin(spec, fields, shape):
         st[k] = {'n': np.zeros(shape, np.uint16), 'mean': np.zeros(shape, np.float64), 'M2': np.zeros(shape, np.float64),
                  'lo': np.full(shape, np.inf, T), 'hi': np.full(shape, -np.inf, T),
                  'k': np.zeros((len(thr),) + shape, np.uint16), 'thr': thr}
+        if k in _quantiles_of(spec):
+            st[k]['x'] = np.zeros((0,) + shape, T)
     return {'spec': spec, 'n_members': 0, 'fields': st}
 
 
@@ -136,6 +277,10 @@ def fold(state, rows):
         n_new = x.shape[0]
         if state['n_members'] + n_new > MAX_MEMBERS:
             raise ValueError('fold: more than %d members in a pass' % MAX_MEMBERS)
+        if 'x' in s:
+            if state['n_members'] + n_new > MAX_QUANTILE_MEMBERS:
+                raise ValueError('fold: more than %d members in a pass with quantiles' % MAX_QUANTILE_MEMBERS)
+            s['x'] = np.concatenate([s['x'], x])
         n, mean, M2, lo, hi, k = s['n'], s['mean'], s['M2'], s['lo'], s['hi'], s['k']
         with np.errstate(all='ignore'):
             for v in x:
@@ -157,11 +302,14 @@ def fold(state, rows):
 
 def finish(state, spec=None):
     """The outputs of a pass: {'mean', 'spread', 'min', 'max': {name: array in the field's dtype} (those `spec` asks for),
-    'count': {name: uint16}, 'exceed': {name: uint16 [n_thresholds, ...cells]}, 'n_members'}."""
+    'count': {name: uint16}, 'exceed': {name: uint16 [n_thresholds, ...cells]}, 'n_members'}, and 'quantile': {name: [n_q,
+    ...cells] in the field's dtype} when `spec` asks for quantiles."""
     spec = spec or state['spec']
     need = spec.min_members
     out = {kind: {} for kind in spec.kinds}
     out.update(count={}, exceed={}, n_members=state['n_members'])
+    if _quantiles_of(spec):
+        out['quantile'] = {}
     for name, s in state['fields'].items():
         T = dtype_of(name)
         n = s['n'].astype(np.int64)
@@ -178,6 +326,8 @@ def finish(state, spec=None):
         out['count'][name] = s['n'].copy()
         if len(s['thr']):
             out['exceed'][name] = s['k'].copy()
+        if name in _quantiles_of(spec):
+            out['quantile'][name] = quantiles(s['x'], spec.quantiles[name], spec.method, need)
     return out
 
 

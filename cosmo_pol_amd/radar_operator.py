@@ -1212,8 +1212,11 @@ class RadarOperator(object):
         if superob is not None:
             self._superob_check(superob)
         if member_stats is not None:
-            # (spec, phase, keep_members): this call's member(s) folded into the lane's running ensemble statistics
-            ms_spec, ms_phase, ms_keep = member_stats
+            # (spec, phase, keep_members[, members of the whole pass]): this call's member(s) folded into the lane's running
+            # ensemble statistics
+            ms_spec, ms_phase, ms_keep = member_stats[:3]
+            ms_capacity = member_stats[3] if len(member_stats) > 3 else None
+            ms_q = getattr(ms_spec, 'quantiles', None) or {}
             if superob is not None:
                 raise ValueError('ensemble statistics and superobservations do not share a call '
                                  '(statistics of window averages are left to the host)')
@@ -1362,20 +1365,20 @@ class RadarOperator(object):
         ms = ms_names = None
         if member_stats is not None:
             ms_names = ms_spec.resolve([k for k in ES.FIELDS if k != 'RVEL' or doppler])
-            ms, ms_thr = N.Context.member_stats_struct(ms_spec, ms_names, ms_phase)
+            ms, ms_thr = N.Context.member_stats_struct(ms_spec, ms_names, ms_phase, capacity=ms_capacity)
             keep = list(keep) + ms_thr
             o.member_stats = C.pointer(ms)
         ms_out = ms is not None and bool(ms_phase & 2)      # a finishing call: the statistics arrive with it
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
-                if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed': {field: device pointer}, 'count': pointer}
+                if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': pointer}
                     if ms is None:
                         raise ValueError("device_outputs['stats'] without ensemble statistics")
                     for kind, pp in (ptr.items() if ms_out else ()):
                         if kind == 'count':
                             ms.count = pp
                             continue
-                        if kind not in ES.KINDS + ('exceed',):
+                        if kind not in ES.KINDS + ('exceed', 'quantile'):
                             raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
                         for kk, q in pp.items():
                             getattr(ms, kind)[ES.FIELDS.index(kk)] = q
@@ -1424,6 +1427,7 @@ class RadarOperator(object):
                     spec += [(('stats', kind, k), ES.dtype_of(k), gshape) for k in ms_names]
                 spec.append((('stats', 'count'), np.uint16, (len(ES.FIELDS),) + gshape))
                 spec += [(('stats', 'exceed', k), np.uint16, (len(ms_spec.exceed[k]),) + gshape) for k in ms_names if k in ms_spec.exceed]
+                spec += [(('stats', 'quantile', k), ES.dtype_of(k), (len(ms_q[k]),) + gshape) for k in ms_names if k in ms_q]
             # every host output is a view of ONE block of page-locked memory from the operator's pool
             # (64-byte aligned arrays): the kernels write a device image of the block and a single
             # device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
@@ -1507,6 +1511,8 @@ class RadarOperator(object):
             cnt = w.pop('count')
             w['count'] = {k: cnt[ES.FIELDS.index(k)] for k in ms_names}
             w.setdefault('exceed', {})
+            if ms_q:
+                w.setdefault('quantile', {})
         res['n_sub'] = sub.n_sub
         return res
 
@@ -1624,12 +1630,13 @@ class RadarOperator(object):
         'max': {field: [n_rays, n_gates]} (those `stats` asks for), 'count': {field: uint16}, 'exceed': {field: uint16 [n_thr,
         n_rays, n_gates]}, 'n_members': M} -- folded on the device behind the sweeps' kernels, member after member in the order
         of `members` (ensemble_stats.fold / finish state the rule; the device result carries the bits of
-        ensemble_stats.reduce(simulate_rays_ensemble(...), stats)).  Without `keep_members` no per-member array is produced for
+        ensemble_stats.reduce(simulate_rays_ensemble(...), stats)).  An ensemble_stats.EnsembleQuantiles adds 'quantile': {field:
+        [n_q, n_rays, n_gates]} (medians, percentiles; at most 128 members, ValueError beyond).  Without `keep_members` no per-member array is produced for
         the host or copied; with it everything simulate_rays_ensemble returns comes back beside the statistics.
         `form`, `members`, `lane`, `apply_sensitivity`: as for simulate_rays_ensemble; whatever the form and however
         `sequence_memory_budget` cuts the member list, the first call of the pass begins it, the last finishes it, all go to
         the one lane, and the bits are the same.  `pinned`: do not wait (call wait(lane)); with several calls it waits.
-        `device_outputs`: {'stats': {'mean' | 'spread' | 'min' | 'max' | 'exceed': {field: device pointer}, 'count': device
+        `device_outputs`: {'stats': {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': device
         pointer of [10, n_rays, n_gates]}} (and, with keep_members, the per-member pointers of simulate_rays_ensemble).
         NotImplementedError where simulate_rays_ensemble raises it: a process group, spaceborne geometry, refraction scheme 2."""
         if not isinstance(stats, ES.EnsembleStats):
@@ -1640,6 +1647,10 @@ class RadarOperator(object):
     def _ensemble_rays(self, azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, so_kw,
                        stats=None, keep_members=False):
         superob = so_kw.get('superob')
+        if stats is not None and getattr(stats, 'quantiles', None):
+            # (before anything runs: the device keeps every member of a field with quantiles until the pass finishes)
+            if (self.n_members if members is None else len(list(members))) > ES.MAX_QUANTILE_MEMBERS:
+                raise ValueError('ensemble quantiles: at most %d members in a pass' % ES.MAX_QUANTILE_MEMBERS)
         members = self._members_arg(members)
         conf = self.__config
         coords = conf['radar']['coords']
@@ -1671,7 +1682,7 @@ class RadarOperator(object):
             for i, chunk in enumerate(chunks):
                 if stats is not None:
                     # the pass: begun by the first call, finished by the last, every call on this lane
-                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if i == len(chunks) - 1 else 0), keep_members))
+                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if i == len(chunks) - 1 else 0), keep_members, len(members)))
                 dev = None
                 if device_outputs is not None:
                     dev = self._offset_outputs(device_outputs, done, n_rays, len(rr))

@@ -328,9 +328,30 @@ typedef struct cpol_superob {
  * the same call; tables->time_blend; cpol_run_columns and cpol_interp_subbeams.
  * TWO kernels (k_member_fold, k_member_finish) run behind the launch sequence and before the output copy: the per-gate
  * arrays, the launch forms, the gate stencils and a captured graph are what they are without it.  A per-gate array the
- * caller leaves NULL is still produced on the device (the context's own buffer) and simply not copied. */
+ * caller leaves NULL is still produced on the device (the context's own buffer) and simply not copied.
+ * QUANTILES (quantile_capacity > 0; a third kernel, k_member_quantile, behind k_member_finish).  Per cell and per field with
+ * n_quantiles[k] > 0: the counting values of the pass (v == v, exactly the ones the fold counts; n of them) are ordered
+ * ascending by <, with -0.0 before +0.0 -- a total order on everything that is not NaN, +-inf included; sorted they are
+ * x[0] ... x[n-1].  For a quantile q in [0, 1]: h = q * (double)(n - 1), one IEEE multiplication.  quantile_method, one per pass:
+ *     0 linear:  i = floor(h); g = h - (double)i; a = (double)x[i].  g == 0: a.  Else b = (double)x[i+1]; a == b: a.  Else
+ *                r = a + g * (b - a), three separate float64 operations without contraction, then if (r > b) r = b.  The
+ *                quantile is (T)r, rounded once.  An infinite bracket gives what IEEE gives: between -inf and any other
+ *                value that is NaN, between a finite value and +inf it is +inf.
+ *     1 lower:   x[floor(h)];   2 higher: x[ceil(h)];   3 nearest: x[rint(h)], ties to even.  A member's own bits, no trip
+ *                through float64.
+ * The quantile is NaN where n < need.  Because the order is total the result is a symmetric function of the members: it depends
+ * neither on the order of the member list nor on how the pass is cut into calls.  The device keeps every member of a field with
+ * quantiles until the pass finishes: a stash of quantile_capacity * n_cells * sizeof(T) bytes per such field, owned by the
+ * context, sized when the pass begins and freed with the context.  A pass with quantiles holds at most quantile_capacity <= 128
+ * members; the other statistics keep their limit of 65535.  The quantile lists of a field that is not folded are not read.
+ * CPOL_ERR_ARG in addition, on the same terms: quantile_method outside 0..3; quantile_capacity outside 0..128; quantiles with
+ * capacity 0; an n_quantiles outside 0..8, or positive with a NULL array; a q that is NaN or outside [0, 1]; a fold whose
+ * capacity, method or quantile lists differ from the open pass; a call that would take a pass with quantiles beyond its
+ * capacity.  A finishing call whose only output pointers are quantile pointers is a valid finishing call. */
 #define CPOL_MEMBER_STATS_FIELDS 10
 #define CPOL_MEMBER_STATS_MAX_THRESHOLDS 8
+#define CPOL_MEMBER_STATS_MAX_QUANTILES 8
+#define CPOL_MEMBER_STATS_MAX_QUANTILE_MEMBERS 128
 typedef struct cpol_member_stats {
     int32_t phase;              /* bit 0: begin a pass (clear the state, then fold); bit 1: finish it (fold, then write the
                                    outputs); 0: fold only                                                          */
@@ -345,6 +366,14 @@ typedef struct cpol_member_stats {
     uint16_t *count;            /* [10][n_cells] or NULL: n of every field; only the rows of folded fields are written (mode 2
                                    under the window rule: the other rows arrive as zeros)                          */
     uint16_t *exceed[CPOL_MEMBER_STATS_FIELDS];         /* [n_thresholds[k]][n_cells] or NULL                      */
+    /* quantiles: appended, so that nothing above moves and a zero-initialised struct has none */
+    int32_t quantile_capacity;  /* 0: no quantiles.  Else the members this pass may hold, 1..128; the stash is sized by it
+                                   when the pass begins                                                            */
+    int32_t quantile_method;    /* 0 linear, 1 lower, 2 higher, 3 nearest                                          */
+    int32_t n_quantiles[CPOL_MEMBER_STATS_FIELDS];      /* 0..8 per field                                          */
+    const double *quantiles[CPOL_MEMBER_STATS_FIELDS];  /* host arrays [n_quantiles[k]], each in [0, 1]            */
+    void *quantile[CPOL_MEMBER_STATS_FIELDS];           /* outputs [n_quantiles[k]][n_cells], float32 (slot RVEL float64);
+                                                           NULL = not wanted; read by a finishing call             */
 } cpol_member_stats;
 
 typedef struct {
@@ -740,8 +769,8 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * [n_rows * n_gates] float32 (slot ZDR unused, slot RVEL float64, NULL = not given), `so` with host output pointers
  * (rays_per_block = 0: n_rows); blocking; cpol_superob's refusals, and CPOL_ERR_ARG for a requested field without its input.
  * Returns 0.
- * "member_stats_fields" is its sibling for the ensemble statistics: k_member_fold / k_member_finish and the context's running
- * state on caller-supplied members.  dst points to { int32_t n_members; int64_t n_cells; const void *in[10]; cpol_member_stats
+ * "member_stats_fields" is its sibling for the ensemble statistics: k_member_fold / k_member_finish / k_member_quantile and the
+ * context's running state on caller-supplied members.  dst points to { int32_t n_members; int64_t n_cells; const void *in[10]; cpol_member_stats
  * ms; } -- `in[k]` a host array [n_members][n_cells] (float32, slot RVEL float64; needed for every folded field when n_members
  * > 0; n_members = 0 folds nothing), `ms` with host output pointers; blocking; honours ms.phase, so a pass can be cut into
  * calls; cpol_member_stats' refusals (Doppler counts as on).  Returns 0.
