@@ -26,6 +26,7 @@
 #include "cpol_device.h"
 #include "cpol_tile.h"
 #include "cpol_forms.h"
+#include "cpol_place.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -190,6 +191,7 @@ struct cpol_ctx {
         double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q] = {};
         void *stash[CPOL_MS_FIELDS] = {};
     } mpass;
+    size_t spec_lds_allowed = 64 * 1024;   // (root context) the largest dynamic LDS asked for k_spec_gate so far (hipFuncSetAttribute)
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
@@ -1848,17 +1850,49 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
     return CPOL_OK;
 }
 
+// The device pointers of a placement plan (cpol_place.h): the buffers of the context grown to what the plan asks for, their bases
+// added.  sweep_own[i]: the buffer of the sweep's own array i (the sweep's arrays come first in the list; NULL: the list has none)
+static int place_resolve(cpol_ctx *ctx, const PlaceArray *arr, int n, const PlacePlan &plan, DevBuf *const *sweep_own, void **T)
+{
+    DevBuf *const block[PLACE_PRODUCTS] = {nullptr, &ctx->b_superob, &ctx->b_msout};
+    if (plan.window) ENSURE(ctx->b_outwin, plan.win_bytes);
+    for (int q = 0; q < PLACE_PRODUCTS; ++q)
+        if (plan.block_bytes[q]) ENSURE(*block[q], plan.block_bytes[q]);
+    for (int i = 0; i < n; ++i) {
+        const PlaceWhere &w = plan.where[i];
+        T[i] = nullptr;
+        if (w.kind == PLACE_IN_PLACE) T[i] = (void *)arr[i].user;
+        else if (w.kind == PLACE_WINDOW) T[i] = (char *)ctx->b_outwin.p + plan.win_skew + w.offset;
+        else if (w.kind == PLACE_OWN && arr[i].product == PLACE_SWEEP) {
+            ENSURE(*sweep_own[i], arr[i].bytes);
+            T[i] = sweep_own[i]->p;
+        } else if (w.kind == PLACE_OWN) T[i] = (char *)block[arr[i].product]->p + w.offset;
+    }
+    return CPOL_OK;
+}
+
+// ... and the copies of what neither lies in the window image (ONE copy, by the caller) nor was written in place
+static int place_copy_out(cpol_ctx *ctx, const PlaceArray *arr, const PlacePlan &plan, void *const *T, bool dst_on_device)
+{
+    int rc;
+    for (int c = 0; c < plan.n_copies; ++c) {
+        const PlaceCopy &cp = plan.copies[c];
+        if ((rc = copy_out(ctx, (char *)arr[cp.array].user + cp.offset, (const char *)T[cp.array] + cp.offset, cp.bytes, dst_on_device))) return rc;
+    }
+    return CPOL_OK;
+}
+
 // ---- superobservations (cpol_superob, cpol_superob.inl): the checks and the launch, shared by the launch sequence and the test hook ----
 enum { SO_RVEL = CPOL_SUPEROB_RVEL, SO_COUNT = CPOL_SUPEROB_FIELDS, SO_N };
 struct SuperobPlan {
     long cells;
     int rpb, wr, wc;
-    void *user[SO_N];           // the caller's pointers: ten fields, then count
-    size_t bytes[SO_N];
 };
 
-// every refusal of a cpol_superob for a call of n_rows rows (rays_default: what rays_per_block = 0 means); queues nothing
-static int superob_plan(cpol_ctx *ctx, const cpol_superob *so, int n_rows, int rays_default, int ng, bool doppler, SuperobPlan *pl)
+// every refusal of a cpol_superob for a call of n_rows rows (rays_default: what rays_per_block = 0 means); queues nothing.
+// arr[SO_N]: the caller's arrays for the placement plan (cpol_place.h): ten fields, then count
+static int superob_plan(cpol_ctx *ctx, const cpol_superob *so, int n_rows, int rays_default, int ng, bool doppler, SuperobPlan *pl,
+                        PlaceArray *arr)
 {
     auto bad = [&](const char *why) { ctx->err = std::string("cpol_superob: ") + why; return CPOL_ERR_ARG; };
     if (so->ray_window < 1 || so->gate_window < 1) return bad("ray_window and gate_window must be >= 1");
@@ -1873,10 +1907,16 @@ static int superob_plan(cpol_ctx *ctx, const cpol_superob *so, int n_rows, int r
     pl->cells = (long)(n_rows / pl->rpb) * pl->wr * pl->wc;
     bool any = false;
     for (int k = 0; k < SO_N; ++k) {
-        pl->user[k] = f[k];
-        pl->bytes[k] = (size_t)pl->cells * (k == SO_RVEL ? sizeof(double) : k == SO_COUNT ? CPOL_SUPEROB_FIELDS * sizeof(uint16_t) : sizeof(float));
+        arr[k] = PlaceArray{};
+        arr[k].user = (uintptr_t)f[k];
+        arr[k].bytes = (size_t)pl->cells * (k == SO_RVEL ? sizeof(double) : k == SO_COUNT ? CPOL_SUPEROB_FIELDS * sizeof(uint16_t) : sizeof(float));
+        arr[k].produced = true;
+        arr[k].product = PLACE_SUPEROB;
         any = any || (f[k] && k != SO_COUNT);
     }
+    arr[SO_COUNT].rows = CPOL_SUPEROB_FIELDS;           // (count: the rows of requested fields alone are the caller's to be written)
+    for (int k = 0; k < SO_COUNT; ++k)
+        if (f[k]) arr[SO_COUNT].row_mask |= 1u << k;
     if (!any) return bad("no output pointer set");
     if (so->RVEL && !doppler) return bad("RVEL needs simulate_doppler");
     return CPOL_OK;
@@ -1905,33 +1945,6 @@ static int superob_launch(cpol_ctx *ctx, const cpol_superob *so, const SuperobPl
     return CPOL_OK;
 }
 
-// host-side copies of what k_superob wrote into a device block (count: only the rows of requested fields are the caller's to be written)
-static int superob_copy_out(cpol_ctx *ctx, const SuperobPlan &pl, void *const T[SO_N])
-{
-    int rc;
-    for (int k = 0; k < SO_COUNT; ++k)
-        if (pl.user[k] && (rc = copy_out(ctx, pl.user[k], T[k], pl.bytes[k], false))) return rc;
-    const size_t row = (size_t)pl.cells * sizeof(uint16_t);
-    for (int k = 0; k < SO_COUNT && pl.user[SO_COUNT]; ++k)
-        if (pl.user[k] && (rc = copy_out(ctx, (char *)pl.user[SO_COUNT] + k * row, (char *)T[SO_COUNT] + k * row, row, false))) return rc;
-    return CPOL_OK;
-}
-
-// where k_superob writes when the outputs are host memory and no window image holds them: the context's own block
-static int superob_own_block(cpol_ctx *ctx, const SuperobPlan &pl, void *T[SO_N])
-{
-    size_t total = 0, off = 0;
-    for (int k = 0; k < SO_N; ++k) if (pl.user[k]) total += (pl.bytes[k] + 255) & ~(size_t)255;
-    ENSURE(ctx->b_superob, total);
-    for (int k = 0; k < SO_N; ++k) {
-        T[k] = nullptr;
-        if (!pl.user[k]) continue;
-        T[k] = (char *)ctx->b_superob.p + off;
-        off += (pl.bytes[k] + 255) & ~(size_t)255;
-    }
-    return CPOL_OK;
-}
-
 // The test hook cpol_debug_read "superob_fields": k_superob on caller-supplied per-gate arrays (host memory in, host memory out,
 // blocking) -- the kernel on inputs no sweep produces (ZV missing where ZH is not, infinities, signed zeros, the largest window).
 struct SuperobHook {
@@ -1944,10 +1957,11 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
 {
     if (h->n_rows < 1 || h->n_gates < 1 || (long)h->n_rows * h->n_gates >= (1L << 31)) { ctx->err = "superob_fields: bad shape"; return CPOL_ERR_ARG; }
     SuperobPlan pl{};
-    int rc = superob_plan(ctx, &h->so, h->n_rows, h->n_rows, h->n_gates, true, &pl);
+    PlaceArray arr[SO_N];
+    int rc = superob_plan(ctx, &h->so, h->n_rows, h->n_rows, h->n_gates, true, &pl, arr);
     if (rc != CPOL_OK) return rc;
     for (int k = 0; k < CPOL_SUPEROB_FIELDS; ++k) {
-        const bool need = k == CPOL_SUPEROB_ZDR ? false : (pl.user[k] || (pl.user[CPOL_SUPEROB_ZDR] && k <= CPOL_SUPEROB_ZV));
+        const bool need = k == CPOL_SUPEROB_ZDR ? false : (arr[k].user || (arr[CPOL_SUPEROB_ZDR].user && k <= CPOL_SUPEROB_ZV));
         if (need && !h->in[k]) { ctx->err = "superob_fields: a requested field has no input"; return CPOL_ERR_ARG; }
     }
     HIPCHK(hipSetDevice(ctx->device));
@@ -1960,10 +1974,12 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
         if ((rc = upload(ctx, b, h->in[k], n * (k == SO_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
         in[k] = b.p;
     }
+    PlacePlan plan;
+    place_outputs(arr, SO_N, 0, false, &plan);
     void *T[SO_N];
-    if ((rc = superob_own_block(ctx, pl, T)) != CPOL_OK) return rc;
+    if ((rc = place_resolve(ctx, arr, SO_N, plan, nullptr, T)) != CPOL_OK) return rc;
     if ((rc = superob_launch(ctx, &h->so, pl, in, T, h->n_gates, false, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = superob_copy_out(ctx, pl, T)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return CPOL_OK;
 }
@@ -1981,12 +1997,12 @@ struct MemberStatsPlan {
     bool q_any;                                     // a folded field has quantiles
     int n_q[CPOL_MS_FIELDS];
     double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q];
-    void *user[MS_N];                               // a finishing call: the caller's pointers (folded fields only)
-    size_t bytes[MS_N];
 };
 
-// every refusal of a cpol_member_stats for a call that folds n_sets row sets of n_cells cells; queues and changes nothing
-static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_cells, int n_sets, bool doppler, MemberStatsPlan *pl)
+// every refusal of a cpol_member_stats for a call that folds n_sets row sets of n_cells cells; queues and changes nothing.
+// arr[MS_N]: a finishing call's arrays for the placement plan (cpol_place.h): the caller's pointers, folded fields only
+static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_cells, int n_sets, bool doppler, MemberStatsPlan *pl,
+                             PlaceArray *arr)
 {
     auto bad = [&](const char *why) { ctx->err = std::string("cpol_member_stats: ") + why; return CPOL_ERR_ARG; };
     const cpol_ctx::MemberPass &ps = ctx->mpass;
@@ -1996,6 +2012,7 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
     if (((ms->fields >> CPOL_MS_RVEL) & 1u) && !doppler) return bad("RVEL needs simulate_doppler");
     if (n_cells < 1 || n_cells >= (1L << 31)) return bad("n_cells must lie in [1, 2^31)");
     *pl = MemberStatsPlan{};
+    for (int k = 0; k < MS_N; ++k) { arr[k] = PlaceArray{}; arr[k].product = PLACE_STATS; }
     pl->cells = n_cells;
     pl->n_sets = n_sets;
     pl->begin = (ms->phase & 1) != 0;
@@ -2048,39 +2065,20 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
     if ((pl->begin ? 0 : ps.folded) + n_sets > 65535) return bad("more than 65535 members in a pass (the counts are uint16)");
     if (pl->finish) {
         bool any = false;
+        const auto asked = [&](int i, void *user, size_t bytes) { arr[i].user = (uintptr_t)user; arr[i].bytes = bytes; arr[i].produced = true; };
         for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
             if (!((ms->fields >> k) & 1u)) continue;
             const size_t w = k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float);
             void *const f[4] = {ms->mean[k], ms->spread[k], ms->min[k], ms->max[k]};
-            for (int a = 0; a < 4; ++a) { pl->user[a * CPOL_MS_FIELDS + k] = f[a]; pl->bytes[a * CPOL_MS_FIELDS + k] = (size_t)n_cells * w; }
-            if (pl->n_thr[k] > 0) {
-                pl->user[MS_EXCEED + k] = ms->exceed[k];
-                pl->bytes[MS_EXCEED + k] = (size_t)pl->n_thr[k] * n_cells * sizeof(uint16_t);
-            }
-            if (pl->n_q[k] > 0) {
-                pl->user[MS_QUANTILE + k] = ms->quantile[k];
-                pl->bytes[MS_QUANTILE + k] = (size_t)pl->n_q[k] * n_cells * w;
-            }
+            for (int a = 0; a < 4; ++a) asked(a * CPOL_MS_FIELDS + k, f[a], (size_t)n_cells * w);
+            if (pl->n_thr[k] > 0) asked(MS_EXCEED + k, ms->exceed[k], (size_t)pl->n_thr[k] * n_cells * sizeof(uint16_t));
+            if (pl->n_q[k] > 0) asked(MS_QUANTILE + k, ms->quantile[k], (size_t)pl->n_q[k] * n_cells * w);
         }
-        pl->user[MS_COUNT] = ms->count;
-        pl->bytes[MS_COUNT] = (size_t)CPOL_MS_FIELDS * n_cells * sizeof(uint16_t);
-        for (int k = 0; k < MS_N; ++k) any = any || pl->user[k];
+        asked(MS_COUNT, ms->count, (size_t)CPOL_MS_FIELDS * n_cells * sizeof(uint16_t));
+        arr[MS_COUNT].rows = CPOL_MS_FIELDS;            // (count: the rows of folded fields alone are the caller's to be written)
+        arr[MS_COUNT].row_mask = ms->fields;
+        for (int k = 0; k < MS_N; ++k) any = any || arr[k].user;
         if (!any) return bad("a finishing call needs an output pointer");
-    }
-    return CPOL_OK;
-}
-
-// where k_member_finish writes when the outputs are host memory and no window image holds them: the context's own block
-static int member_stats_own_block(cpol_ctx *ctx, const MemberStatsPlan &pl, void *T[MS_N])
-{
-    size_t total = 0, off = 0;
-    for (int k = 0; k < MS_N; ++k) if (pl.user[k]) total += (pl.bytes[k] + 255) & ~(size_t)255;
-    ENSURE(ctx->b_msout, total);
-    for (int k = 0; k < MS_N; ++k) {
-        T[k] = nullptr;
-        if (!pl.user[k]) continue;
-        T[k] = (char *)ctx->b_msout.p + off;
-        off += (pl.bytes[k] + 255) & ~(size_t)255;
     }
     return CPOL_OK;
 }
@@ -2181,18 +2179,6 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
     return CPOL_OK;
 }
 
-// host-side copies of what k_member_finish wrote into the context's own block (count: the rows of folded fields alone)
-static int member_stats_copy_out(cpol_ctx *ctx, const MemberStatsPlan &pl, unsigned fields, void *const T[MS_N])
-{
-    int rc;
-    for (int k = 0; k < MS_N; ++k)
-        if (k != MS_COUNT && pl.user[k] && (rc = copy_out(ctx, pl.user[k], T[k], pl.bytes[k], false))) return rc;
-    const size_t row = (size_t)pl.cells * sizeof(uint16_t);
-    for (int k = 0; k < CPOL_MS_FIELDS && pl.user[MS_COUNT]; ++k)
-        if (((fields >> k) & 1u) && (rc = copy_out(ctx, (char *)pl.user[MS_COUNT] + k * row, (char *)T[MS_COUNT] + k * row, row, false))) return rc;
-    return CPOL_OK;
-}
-
 // The test hook cpol_debug_read "member_stats_fields": the product's fold and finish on caller-supplied members (host memory
 // in, host memory out, blocking), phase by phase -- the kernels on inputs no sweep produces and on passes cut at will.
 struct MemberStatsHook {
@@ -2209,7 +2195,8 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
         return CPOL_ERR_ARG;
     }
     MemberStatsPlan pl{};
-    int rc = member_stats_plan(ctx, &h->ms, (long)h->n_cells, h->n_members, true, &pl);
+    PlaceArray arr[MS_N];
+    int rc = member_stats_plan(ctx, &h->ms, (long)h->n_cells, h->n_members, true, &pl, arr);
     if (rc != CPOL_OK) return rc;
     for (int k = 0; k < CPOL_MS_FIELDS; ++k)
         if (((h->ms.fields >> k) & 1u) && h->n_members > 0 && !h->in[k]) { ctx->err = "member_stats_fields: a folded field has no input"; return CPOL_ERR_ARG; }
@@ -2222,10 +2209,12 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
         if ((rc = upload(ctx, b, h->in[k], n * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
         in[k] = b.p;
     }
-    void *T[MS_N] = {};
-    if (pl.finish && (rc = member_stats_own_block(ctx, pl, T)) != CPOL_OK) return rc;
+    PlacePlan plan;
+    place_outputs(arr, MS_N, 0, false, &plan);
+    void *T[MS_N];
+    if ((rc = place_resolve(ctx, arr, MS_N, plan, nullptr, T)) != CPOL_OK) return rc;
     if ((rc = member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream)) != CPOL_OK) return rc;
-    if (pl.finish && (rc = member_stats_copy_out(ctx, pl, h->ms.fields, T)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return CPOL_OK;
 }
@@ -2266,15 +2255,6 @@ static int staging_slot(cpol_ctx *ctx, size_t bytes, cpol_ctx::Staging **slot, d
     if (!sg.ev) HIPCHK(hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
     *slot = &sg;
     return CPOL_OK;
-}
-
-// the output window of the pinned-host mode: [lo, hi) widened to the caller's array a, sum: the bytes of the arrays alone
-static void window_add(void *a_, size_t bytes, char *&lo, char *&hi, size_t &sum)
-{
-    char *a = (char *)a_;
-    if (!lo || a < lo) lo = a;
-    if (!hi || a + bytes > hi) hi = a + bytes;
-    sum += bytes;
 }
 
 static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ray_tables_t *t,
@@ -2329,12 +2309,17 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             return CPOL_ERR_ARG;
         }
     }
+    // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
+    enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_N = A_MS + MS_N };
+    static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
+    PlaceArray arr[A_N];
     // superobservations (cpol_superob): every refusal here, before anything of the call is queued
     const cpol_superob *const so = out->superob;
     SuperobPlan so_pl{};
     if (so) {
         if (cols || sub_out) { ctx->err = "cpol_superob: cpol_run_sweep and cpol_run_sweep_members take superobservations, no other entry point"; return CPOL_ERR_ARG; }
-        const int rc_so = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl);
+        const int rc_so = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl, arr + A_SO);
         if (rc_so != CPOL_OK) return rc_so;
     }
     // ensemble statistics (cpol_member_stats): likewise
@@ -2344,7 +2329,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (cols || sub_out) { ctx->err = "cpol_member_stats: cpol_run_sweep and cpol_run_sweep_members take ensemble statistics, no other entry point"; return CPOL_ERR_ARG; }
         if (so) { ctx->err = "cpol_member_stats: not together with superobservations (outputs->superob) in one call"; return CPOL_ERR_ARG; }
         if (timed) { ctx->err = "cpol_member_stats: a time-blended call (tables->time_blend) folds no members"; return CPOL_ERR_ARG; }
-        const int rc_ms = member_stats_plan(ctx, ms, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl);
+        const int rc_ms = member_stats_plan(ctx, ms, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_MS);
         if (rc_ms != CPOL_OK) return rc_ms;
     }
     int rc;
@@ -2376,6 +2361,104 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     const bool reuse = set != nullptr;
     if (!set) set = lru;
+    // which kernels this call launches and in which form: every rule in cpol_forms.h, decided here once
+    FormIn fi;
+    fi.n_rays = n_rays; fi.n_gates = ng; fi.n_sub = n_sub; fi.n_h = n_h; fi.geo_rays = geo_rays;
+    fi.columns = cols != nullptr; fi.sub_export = sub_out != nullptr; fi.members = mem != nullptr; fi.timed = timed;
+    fi.melt_given = melt_given; fi.ml = ml; fi.skip_melting = sub_out && sub_out->skip_melting;
+    fi.geometry_mode = mode; fi.doppler = p->simulate_doppler;
+    fi.site = t->site != nullptr; fi.versioned = t->version != 0; fi.with_melting = p->with_melting != 0;
+    fi.exact_sub = (p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS) != 0;
+    fi.want_latlon = out->lats || out->lons; fi.want_sz_total = out->sz_total != nullptr;
+    fi.want_model = p->integrate_model && out->model_vars; fi.reuse = reuse;
+    fi.outputs_on_device = p->outputs_on_device;
+    fi.keep_debug = ctx->keep_debug; fi.timing = ctx->timing; fi.nz = ctx->model.nz;
+    fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
+    fi.scan_form = CPOL_SCAN_FORM;
+    fi.n_hydro = n_hyd;
+    for (int j = 0; j < n_hyd; ++j) {
+        const cpol_hydro_desc &d = ctx->hs.h[j].d;
+        const ItabDev &tj = ctx->its.t[j];
+        FormSpecies &s = fi.s[j];
+        s.tab = tj.tab != nullptr; s.two_d = tj.two_d != 0; s.writes_vn = tj.writes_vn != 0;
+        s.pan_lo = tj.pan_lo; s.pan_hi = tj.pan_hi; s.n_pan = tj.n_pan;
+        s.psd_family = d.psd_family; s.numeric_intv = d.numeric_intv; s.q_source = d.q_source; s.uniform_grid = d.uniform_grid;
+        s.tab_degree = d.tab_degree; s.rule = d.rule; s.var_q = d.var_q;
+        s.pre = ctx->hs.h[j].pre != nullptr; s.dnu = ctx->hs.h[j].dnu != nullptr;
+    }
+    const ProcessKnobs &pk = process_knobs();
+    const Forms f = choose_forms(fi, ctx->knobs, pk);
+    // ---- the remaining refusals: every argument check of the call happens here, before a table set or a staging slot is taken
+    // and before anything is queued -- a refused call leaves nothing on the device and the context as it found it ----
+    const bool doppler = p->simulate_doppler != 0;
+    const bool dop2 = p->simulate_doppler == 2;
+    const bool dop3 = p->simulate_doppler == 3;
+    const int n_vb = p->n_vbins;
+    bool spec_melt = false;                // Doppler scheme 3: a melting species is staged (its fall-speed tables take LDS of k_spec_gate)
+    size_t spec_lds = 0;                   // ... and the LDS of a workgroup of k_spec_gate
+    if (dop3) {
+        if (n_vb < 2 || n_vb > 4097 || !t->varray || p->var_rho < 0 || p->var_rho >= n_vars) {
+            ctx->err = "cpol_run_sweep: Doppler scheme 3 needs n_vbins in [2, 4097], tables->varray and var_rho";
+            return CPOL_ERR_ARG;
+        }
+        for (int j = 0; j < n_hyd; ++j) {
+            if (!ctx->ss.s[j].rcs32) { ctx->err = "cpol_run_sweep: Doppler scheme 3 needs cpol_stage_spectrum_tables"; return CPOL_ERR_ARG; }
+            if (ctx->hs.h[j].d.n_d != ctx->hs.h[0].d.n_d) {     // the LDS image is sized from slot 0
+                ctx->err = "cpol_run_sweep: Doppler scheme 3 needs the same number of diameter bins in every table";
+                return CPOL_ERR_ARG;
+            }
+        }
+        for (int j = 0; j < n_hyd; ++j) spec_melt = spec_melt || ctx->hs.h[j].d.psd_family == CPOL_PSD_MELTING;
+        // [2][n_d] + [threads] float64 (only with melting species), [n_hyd][n_d] + [n_hyd + 1][n_v] float32 (cpol_spectrum.inl)
+        spec_lds = (spec_melt ? ((size_t)2 * ctx->hs.h[0].d.n_d + CPOL_SPEC_THREADS) * sizeof(double) : 0)
+                   + ((size_t)n_hyd * (ctx->hs.h[0].d.n_d + n_vb) + n_vb) * sizeof(float);
+        if (spec_lds > 160 * 1024 - 256) {
+            // (gfx950: 160 KB of LDS per CU, all of it available to ONE workgroup of k_spec_gate when the launch asks for it --
+            // six species with FFT_length = 2048, the upper end of the reference's valid range (cfg.py:91), need 100 KB)
+            ctx->err = "cpol_run_sweep: Doppler scheme 3: n_hydro x (n_d + n_vbins) exceeds the 160 KB of LDS of a gfx950 CU";
+            return CPOL_ERR_ARG;
+        }
+    }
+    const bool broaden = p->turbulence_correction != 0 || p->motion_correction != 0;
+    if (broaden) {
+        if (!dop3) { ctx->err = "cpol_run_sweep: turbulence_correction / motion_correction need Doppler scheme 3"; return CPOL_ERR_ARG; }
+        if (p->turbulence_correction && (p->var_edr < 0 || p->var_edr >= n_vars)) {
+            ctx->err = "cpol_run_sweep: turbulence_correction needs var_edr, the staged index of the eddy dissipation rate";
+            return CPOL_ERR_ARG;
+        }
+        if (!(p->v_res > 0.0) || (p->turbulence_correction && (!(p->sigma_r > 0.0) || !(p->sigma_theta > 0.0))) ||
+            (p->motion_correction && !(p->motion_den > 0.0))) {
+            ctx->err = "cpol_run_sweep: spectrum broadening needs v_res > 0, sigma_r, sigma_theta > 0 (turbulence), motion_den > 0 (motion)";
+            return CPOL_ERR_ARG;
+        }
+    }
+    if (dop2)
+        for (int j = 0; j < n_hyd; ++j)
+            if (!ctx->hs.h[j].rcsw) { ctx->err = "cpol_run_sweep: Doppler scheme 2 needs cpol_stage_doppler_weights"; return CPOL_ERR_ARG; }
+    if (out->mask_sum8 && 2 * n_sub > 127) { ctx->err = "cpol_run_sweep: outputs->mask_sum8 needs 2 * n_sub <= 127 (one byte per gate)"; return CPOL_ERR_ARG; }
+    const bool melt_vars = f.melt_qr >= 0 && f.melt_qs >= 0 && f.melt_qg >= 0;      // 1-moment rain, snow and graupel slots are staged
+    if (sub_out && p->with_melting && !melt_vars) {
+        ctx->err = "cpol_interp_subbeams: melting needs 1-moment rain, snow and graupel slots";
+        return CPOL_ERR_ARG;
+    }
+    if (!sub_out) {                        // (the export stops before the kernels that read these)
+        if (doppler && (p->var_u < 0 || p->var_v < 0 || p->var_w < 0 || p->var_u >= n_vars || p->var_v >= n_vars || p->var_w >= n_vars)) {
+            ctx->err = "cpol_run_sweep: simulate_doppler needs var_u / var_v / var_w";
+            return CPOL_ERR_ARG;
+        }
+        if (p->with_melting && !melt_vars) {
+            ctx->err = "cpol_run_sweep: melting needs 1-moment rain, snow and graupel slots";
+            return CPOL_ERR_ARG;
+        }
+    }
+    if (spec_lds > 64 * 1024) {
+        // beyond the default 64 KB per workgroup: ask for it (an attribute of the kernel; the largest request so far is kept)
+        cpol_ctx *const root = root_of(ctx);
+        if (spec_lds > root->spec_lds_allowed) {
+            HIPCHK(hipFuncSetAttribute((const void *)k_spec_gate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_lds));
+            root->spec_lds_allowed = spec_lds;
+        }
+    }
     set->last_use = ++ctx->tset_clock;
     if (reuse) {
         for (int k = 0; k < 11; ++k) *views[k] = set->views[k];
@@ -2431,33 +2514,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     const double t_tables = now_ns();
     // ---- work buffers ----
-    // which kernels this call launches and in which form: every rule in cpol_forms.h, decided here once
-    FormIn fi;
-    fi.n_rays = n_rays; fi.n_gates = ng; fi.n_sub = n_sub; fi.n_h = n_h; fi.geo_rays = geo_rays;
-    fi.columns = cols != nullptr; fi.sub_export = sub_out != nullptr; fi.members = mem != nullptr; fi.timed = timed;
-    fi.melt_given = melt_given; fi.ml = ml; fi.skip_melting = sub_out && sub_out->skip_melting;
-    fi.geometry_mode = mode; fi.doppler = p->simulate_doppler;
-    fi.site = t->site != nullptr; fi.versioned = t->version != 0; fi.with_melting = p->with_melting != 0;
-    fi.exact_sub = (p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS) != 0;
-    fi.want_latlon = out->lats || out->lons; fi.want_sz_total = out->sz_total != nullptr;
-    fi.want_model = p->integrate_model && out->model_vars; fi.reuse = reuse;
-    fi.outputs_on_device = p->outputs_on_device;
-    fi.keep_debug = ctx->keep_debug; fi.timing = ctx->timing; fi.nz = ctx->model.nz;
-    fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
-    fi.scan_form = CPOL_SCAN_FORM;
-    fi.n_hydro = n_hyd;
-    for (int j = 0; j < n_hyd; ++j) {
-        const cpol_hydro_desc &d = ctx->hs.h[j].d;
-        const ItabDev &tj = ctx->its.t[j];
-        FormSpecies &s = fi.s[j];
-        s.tab = tj.tab != nullptr; s.two_d = tj.two_d != 0; s.writes_vn = tj.writes_vn != 0;
-        s.pan_lo = tj.pan_lo; s.pan_hi = tj.pan_hi; s.n_pan = tj.n_pan;
-        s.psd_family = d.psd_family; s.numeric_intv = d.numeric_intv; s.q_source = d.q_source; s.uniform_grid = d.uniform_grid;
-        s.tab_degree = d.tab_degree; s.rule = d.rule; s.var_q = d.var_q;
-        s.pre = ctx->hs.h[j].pre != nullptr; s.dnu = ctx->hs.h[j].dnu != nullptr;
-    }
-    const ProcessKnobs &pk = process_knobs();
-    const Forms f = choose_forms(fi, ctx->knobs, pk);
     if (mode == CPOL_GEOM_HOST_PATHS || ctx->keep_debug || f.prep_paths)
         ENSURE(ctx->b_traj, (size_t)n_rays * n_v * 3 * ng * sizeof(float));
     if (f.ray_prep) ENSURE(ctx->b_rayc, ((size_t)n_rays * n_h + n_rays) * 2 * sizeof(double));
@@ -2562,55 +2618,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     long unit_cap = (long)n_hyd * n_sbg / 64 + n_keys + 64;
     ENSURE(ctx->b_perm, (size_t)n_hyd * n_sbg * sizeof(int));
     ENSURE(ctx->b_res, (size_t)n_hyd * n_sbg * CPOL_N_SZ * sizeof(double));
-    const bool doppler = p->simulate_doppler != 0;
-    const bool dop2 = p->simulate_doppler == 2;
-    const bool dop3 = p->simulate_doppler == 3;
-    const int n_vb = p->n_vbins;
-    bool spec_melt = false;                // Doppler scheme 3: a melting species is staged (its fall-speed tables take LDS of k_spec_gate)
-    if (dop3) {
-        if (n_vb < 2 || n_vb > 4097 || !t->varray || p->var_rho < 0 || p->var_rho >= n_vars) {
-            ctx->err = "cpol_run_sweep: Doppler scheme 3 needs n_vbins in [2, 4097], tables->varray and var_rho";
-            return CPOL_ERR_ARG;
-        }
-        for (int j = 0; j < n_hyd; ++j) {
-            if (!ctx->ss.s[j].rcs32) { ctx->err = "cpol_run_sweep: Doppler scheme 3 needs cpol_stage_spectrum_tables"; return CPOL_ERR_ARG; }
-            if (ctx->hs.h[j].d.n_d != ctx->hs.h[0].d.n_d) {     // the LDS image is sized from slot 0
-                ctx->err = "cpol_run_sweep: Doppler scheme 3 needs the same number of diameter bins in every table";
-                return CPOL_ERR_ARG;
-            }
-        }
-        for (int j = 0; j < n_hyd; ++j) spec_melt = spec_melt || ctx->hs.h[j].d.psd_family == CPOL_PSD_MELTING;
-        if ((spec_melt ? ((size_t)2 * ctx->hs.h[0].d.n_d + 256) * sizeof(double) : 0) + ((size_t)n_hyd * (ctx->hs.h[0].d.n_d + n_vb) + n_vb) * sizeof(float) > 160 * 1024 - 256) {
-            // (gfx950: 160 KB of LDS per CU, all of it available to ONE workgroup of k_spec_gate when the launch asks for it --
-            // six species with FFT_length = 2048, the upper end of the reference's valid range (cfg.py:91), need 100 KB)
-            ctx->err = "cpol_run_sweep: Doppler scheme 3: n_hydro x (n_d + n_vbins) exceeds the 160 KB of LDS of a gfx950 CU";
-            return CPOL_ERR_ARG;
-        }
-    }
-    const bool broaden = p->turbulence_correction != 0 || p->motion_correction != 0;
-    if (broaden) {
-        if (!dop3) { ctx->err = "cpol_run_sweep: turbulence_correction / motion_correction need Doppler scheme 3"; return CPOL_ERR_ARG; }
-        if (p->turbulence_correction && (p->var_edr < 0 || p->var_edr >= n_vars)) {
-            ctx->err = "cpol_run_sweep: turbulence_correction needs var_edr, the staged index of the eddy dissipation rate";
-            return CPOL_ERR_ARG;
-        }
-        if (!(p->v_res > 0.0) || (p->turbulence_correction && (!(p->sigma_r > 0.0) || !(p->sigma_theta > 0.0))) ||
-            (p->motion_correction && !(p->motion_den > 0.0))) {
-            ctx->err = "cpol_run_sweep: spectrum broadening needs v_res > 0, sigma_r, sigma_theta > 0 (turbulence), motion_den > 0 (motion)";
-            return CPOL_ERR_ARG;
-        }
-    }
-    if (dop2)
-        for (int j = 0; j < n_hyd; ++j)
-            if (!ctx->hs.h[j].rcsw) { ctx->err = "cpol_run_sweep: Doppler scheme 2 needs cpol_stage_doppler_weights"; return CPOL_ERR_ARG; }
     if (doppler) {
         ENSURE(ctx->b_vn, (size_t)n_hyd * n_sbg * 2 * sizeof(double));
         ENSURE(ctx->b_icefirst, (size_t)n_rays * n_sub * sizeof(IceFirst));
         if (f.rvel_terms) ENSURE(ctx->b_proj, (size_t)n_sbg * sizeof(double));
     }
-    // (every argument check and every allocation of the sequence happens before its first launch: an error return
+    // (every allocation of the sequence happens before its first launch, like every argument check above: an error return
     // further down would leave the sweep's counter set half used; see counters_dirty)
-    if (out->mask_sum8 && 2 * n_sub > 127) { ctx->err = "cpol_run_sweep: outputs->mask_sum8 needs 2 * n_sub <= 127 (one byte per gate)"; return CPOL_ERR_ARG; }
     // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
     const void *col_src[CPOL_MAX_VARS + 6] = {};
     size_t col_bytes[CPOL_MAX_VARS + 6] = {};
@@ -2633,12 +2647,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // (lats, lons, dist, heights, elev) and mask_ml
     const size_t xa8 = ((size_t)n_sbg * sizeof(double) + 255) & ~(size_t)255, xa4 = ((size_t)n_sbg * sizeof(float) + 255) & ~(size_t)255;
     const size_t xa1 = ((size_t)n_sbg + 255) & ~(size_t)255;
-    const bool melt_vars = f.melt_qr >= 0 && f.melt_qs >= 0 && f.melt_qg >= 0;      // 1-moment rain, snow and graupel slots are staged
     if (sub_out) {
-        if (p->with_melting && !melt_vars) {
-            ctx->err = "cpol_interp_subbeams: melting needs 1-moment rain, snow and graupel slots";
-            return CPOL_ERR_ARG;
-        }
         ENSURE(ctx->b_xscr, (size_t)n_vars * xa4 + xa1 + xa4);
         ENSURE(ctx->b_xgeo, 2 * xa8 + 3 * xa4 + xa1);
     }
@@ -2650,8 +2659,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         }
     }
     // ---- outputs: where the kernels write each array, and how it reaches the caller ----
-    enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N };
     const bool dev = p->outputs_on_device == 1;
     const bool async_host = p->outputs_on_device == 2;    // pinned host buffers, no wait
     if (f.gate1) {
@@ -2680,69 +2687,30 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
                                  out->DSPECTRUM, out->mask_sum8};
-    size_t obytes[O_N];
-    bool produced[O_N];
-    DevBuf *own[O_N];
+    DevBuf *own[O_N];              // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
+    for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
-        obytes[k] = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
-        produced[k] = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
-        if (mem && !timed && k >= O_LAT && k <= O_HGT) obytes[k] = obytes[k] / (size_t)mem->n_members;      // (the geometry once, not per member)
-        own[k] = &ctx->b_out[k];
+        arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
+        arr[k].produced = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
+        if (mem && !timed && k >= O_LAT && k <= O_HGT) arr[k].bytes = arr[k].bytes / (size_t)mem->n_members;      // (the geometry once, not per member)
     }
-    obytes[O_RVEL] = (size_t)n_rg * sizeof(double);            produced[O_RVEL] = doppler;    own[O_RVEL] = &ctx->b_rvel;
-    obytes[O_MODEL] = (size_t)n_vars * n_rg * sizeof(double);  produced[O_MODEL] = want_model; own[O_MODEL] = &ctx->b_model;
-    obytes[O_SZT] = (size_t)n_rg * CPOL_N_SZ * sizeof(float);  produced[O_SZT] = want_szt;    own[O_SZT] = &ctx->b_sztotal;
-    obytes[O_SPEC] = (size_t)n_rg * n_vb * sizeof(double);     produced[O_SPEC] = dop3;       own[O_SPEC] = &ctx->b_spectrum;
+    arr[O_RVEL].bytes = (size_t)n_rg * sizeof(double);            arr[O_RVEL].produced = doppler;     own[O_RVEL] = &ctx->b_rvel;
+    arr[O_MODEL].bytes = (size_t)n_vars * n_rg * sizeof(double);  arr[O_MODEL].produced = want_model; own[O_MODEL] = &ctx->b_model;
+    arr[O_SZT].bytes = (size_t)n_rg * CPOL_N_SZ * sizeof(float);  arr[O_SZT].produced = want_szt;     own[O_SZT] = &ctx->b_sztotal;
+    arr[O_SZT].own_under_debug = true;                            // (cpol_debug_read "sz_total" reads the context's copy)
+    arr[O_SPEC].bytes = (size_t)n_rg * n_vb * sizeof(double);     arr[O_SPEC].produced = dop3;        own[O_SPEC] = &ctx->b_spectrum;
     // the radial mask as one byte per gate (the sum of the sub-beams' codes): only when asked for; the float64 form is then
     // written only if it is asked for too
-    obytes[O_MASK8] = (size_t)n_rg;                            produced[O_MASK8] = out->mask_sum8 != nullptr; own[O_MASK8] = &ctx->b_mask8;
-    if (out->mask_sum8 && !out->mask && !ctx->keep_debug) produced[O_MASK] = false;
-    void *T[O_N];
-    // pinned-host mode: when the requested arrays lie in one window of the caller's slab (only
-    // alignment padding between them) the kernels write into a device image of that window and
-    // ONE device-to-host copy moves it (instead of up to 18 copies of a few hundred KB each)
-    char *win_lo = nullptr, *win_hi = nullptr;
-    size_t win_sum = 0;
-    if (async_host && !ctx->keep_debug) {
-        for (int k = 0; k < O_N; ++k)
-            if (produced[k] && user_out[k]) window_add(user_out[k], obytes[k], win_lo, win_hi, win_sum);
-        for (int k = 0; k < SO_N; ++k)                        // (the superobservation arrays count like every other array)
-            if (so_pl.user[k]) window_add(so_pl.user[k], so_pl.bytes[k], win_lo, win_hi, win_sum);
-        for (int k = 0; k < MS_N; ++k)                        // (and those of a finishing cpol_member_stats)
-            if (ms_pl.user[k]) window_add(ms_pl.user[k], ms_pl.bytes[k], win_lo, win_hi, win_sum);
-    }
-    const bool window = win_lo && (size_t)(win_hi - win_lo) <= win_sum + win_sum / 4 + 4096;
-    // (the device image keeps the window's alignment modulo 64 B, so that every array of the image is
-    // aligned exactly like its host counterpart: a float32 array at an address 4 mod 8 followed by a
-    // float64 array must not shift the latter to a misaligned device address)
-    const size_t win_skew = window ? ((size_t)(uintptr_t)win_lo & 63) : 0;
-    if (window) ENSURE(ctx->b_outwin, (size_t)(win_hi - win_lo) + 64);
-    for (int k = 0; k < O_N; ++k) {
-        T[k] = nullptr;
-        if (!produced[k]) continue;
-        if (dev && user_out[k] && !(ctx->keep_debug && k == O_SZT)) { T[k] = user_out[k]; continue; }   // in place
-        if (window && user_out[k]) { T[k] = (char *)ctx->b_outwin.p + win_skew + ((char *)user_out[k] - win_lo); continue; }
-        ENSURE(*own[k], obytes[k]);
-        T[k] = own[k]->p;
-    }
-    // ... and where k_superob writes: in place (device pointers), into the window's image, or into the context's own block
-    void *so_T[SO_N] = {};
-    if (so && !dev && !window) {
-        const int rc_so = superob_own_block(ctx, so_pl, so_T);
-        if (rc_so != CPOL_OK) return rc_so;
-    } else if (so) {
-        for (int k = 0; k < SO_N; ++k)
-            if (so_pl.user[k]) so_T[k] = dev ? so_pl.user[k] : (void *)((char *)ctx->b_outwin.p + win_skew + ((char *)so_pl.user[k] - win_lo));
-    }
-    // ... and where k_member_finish writes: the same three places
-    void *ms_T[MS_N] = {};
-    if (ms && ms_pl.finish && !dev && !window) {
-        const int rc_ms = member_stats_own_block(ctx, ms_pl, ms_T);
-        if (rc_ms != CPOL_OK) return rc_ms;
-    } else if (ms && ms_pl.finish) {
-        for (int k = 0; k < MS_N; ++k)
-            if (ms_pl.user[k]) ms_T[k] = dev ? ms_pl.user[k] : (void *)((char *)ctx->b_outwin.p + win_skew + ((char *)ms_pl.user[k] - win_lo));
-    }
+    arr[O_MASK8].bytes = (size_t)n_rg;                            arr[O_MASK8].produced = out->mask_sum8 != nullptr; own[O_MASK8] = &ctx->b_mask8;
+    if (out->mask_sum8 && !out->mask && !ctx->keep_debug) arr[O_MASK].produced = false;
+    // in place (device pointers), into the device image of the caller's pinned window, or into buffers of the context: one rule
+    // for the three products (cpol_place.h); the bases are added here
+    PlacePlan plan;
+    place_outputs(arr, A_N, p->outputs_on_device, ctx->keep_debug, &plan);
+    const bool window = plan.window;
+    void *T_all[A_N];
+    if ((rc = place_resolve(ctx, arr, A_N, plan, own, T_all)) != CPOL_OK) return rc;
+    void *const *const T = T_all, *const *const so_T = T_all + A_SO, *const *const ms_T = T_all + A_MS;
 
     // the bucket counters start at zero: cleared by k_interp_sweep (no fill kernel); the domain
     // error word is sticky (cleared when reported)
@@ -3000,11 +2968,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         fa.n_h = n_h;
         fa.var_u = p->var_u; fa.var_v = p->var_v; fa.var_w = p->var_w;
         fa.nyquist = t->nyquist ? (const double *)ctx->v_nyq : nullptr;
-        if (fa.var_u < 0 || fa.var_v < 0 || fa.var_w < 0 || fa.var_u >= n_vars ||
-            fa.var_v >= n_vars || fa.var_w >= n_vars) {
-            ctx->err = "cpol_run_sweep: simulate_doppler needs var_u / var_v / var_w";
-            return CPOL_ERR_ARG;
-        }
         for (int j = 0; j < n_hyd; ++j) fa.vsrc[j] = f.vsrc[j];
     }
 
@@ -3050,10 +3013,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ca.rare_key = (int *)ctx->b_pos.p;
         ca.rare_perm = (int *)ctx->b_perm.p;
         ca.rare_totals = (unsigned long long *)tot_p;
-    }
-    if (p->with_melting && !melt_vars) {
-        ctx->err = "cpol_run_sweep: melting needs 1-moment rain, snow and graupel slots";
-        return CPOL_ERR_ARG;
     }
     if (ml) {
         if (!cols) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ml_args());     // (columns: ingested)
@@ -3352,19 +3311,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         sp.n_sbg = n_sbg; sp.n_gates = ng; sp.n_sub = n_sub; sp.n_h = n_h; sp.n_v = n_vb;
         sp.var_u = p->var_u; sp.var_v = p->var_v; sp.var_w = p->var_w; sp.var_rho = p->var_rho;
         sp.c_spec = (float)p->c_spectrum;
-        // [2][n_d] + [threads] float64 (only with melting species), [n_hyd][n_d] + [n_hyd + 1][n_v] float32 (cpol_spectrum.inl)
         sp.n_melt_rows = spec_melt ? 2 : 0;
-        const size_t lds = (spec_melt ? ((size_t)2 * ctx->hs.h[0].d.n_d + CPOL_SPEC_THREADS) * sizeof(double) : 0)
-                           + ((size_t)n_hyd * (ctx->hs.h[0].d.n_d + n_vb) + n_vb) * sizeof(float);
-        if (lds > 64 * 1024) {
-            // beyond the default 64 KB per workgroup: ask for it (an attribute of the kernel; the largest request so far is kept)
-            static size_t lds_allowed = 64 * 1024;
-            if (lds > lds_allowed) {
-                HIPCHK(hipFuncSetAttribute((const void *)k_spec_gate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                lds_allowed = lds;
-            }
-        }
-        hipLaunchKernelGGL(k_spec_gate, dim3((unsigned)n_sbg), dim3(CPOL_SPEC_THREADS), lds, st, ctx->hs, ctx->ss, sp);
+        hipLaunchKernelGGL(k_spec_gate, dim3((unsigned)n_sbg), dim3(CPOL_SPEC_THREADS), spec_lds, st, ctx->hs, ctx->ss, sp);
         if (broaden) {
             // ---- turbulence / antenna motion: width and switch per sub-beam, then the filter row by row ----
             SpecWidthArgs wa{};
@@ -3444,7 +3392,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         };
         mix(p, sizeof *p);
         mix(&t->version, sizeof t->version);
-        mix(T, sizeof T);
+        mix(T, O_N * sizeof *T);
         mix(&ctx->stage_serial, sizeof ctx->stage_serial);
         void *arena[] = {ctx->b_traj.p, ctx->b_vals.p, ctx->b_mask.p, ctx->b_elev.p, ctx->b_qmelt.p,
                          ctx->b_fwmelt.p, ctx->b_key.p, ctx->b_pos.p, ctx->b_par.p, (void *)cnt_p,
@@ -3501,16 +3449,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st)) != CPOL_OK) return rc;
     }
     // ---- outputs that the kernels did not write in place ----
-    if (so && !dev && !window && (rc = superob_copy_out(ctx, so_pl, so_T)) != CPOL_OK) return rc;
-    if (ms && ms_pl.finish && !dev && !window && (rc = member_stats_copy_out(ctx, ms_pl, ms->fields, ms_T)) != CPOL_OK) return rc;
-    if (window) {
-        HIPCHK(hipMemcpyAsync(win_lo, (const char *)ctx->b_outwin.p + win_skew, (size_t)(win_hi - win_lo), hipMemcpyDeviceToHost, st));
-    } else {
-        for (int k = 0; k < O_N; ++k) {
-            if (!produced[k] || !user_out[k] || T[k] == user_out[k]) continue;
-            if ((rc = copy_out(ctx, user_out[k], T[k], obytes[k], dev))) return rc;
-        }
-    }
+    if (window)
+        HIPCHK(hipMemcpyAsync((void *)plan.win_lo, (const char *)ctx->b_outwin.p + plan.win_skew, (size_t)(plan.win_hi - plan.win_lo), hipMemcpyDeviceToHost, st));
+    if ((rc = place_copy_out(ctx, arr, plan, T_all, dev)) != CPOL_OK) return rc;
 
     {
         const double t_done = now_ns();
