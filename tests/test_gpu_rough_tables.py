@@ -61,12 +61,13 @@ def _run_hip(over, luts, cube, az, el, itab):
             os.environ['CPOL_ITAB'] = old
 
 
-def _record(rec):
-    print('ROUGH', json.dumps(rec))
+def _record(rec, name='rough_table_records.jsonl', tag='ROUGH'):
+    """Prints a record and appends it to the records file `name` of this run (tests/test_gpu_buckets.py writes its own through here)."""
+    print(tag, json.dumps(rec))
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     try:
         os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, 'rough_table_records.jsonl'), 'a') as f:
+        with open(os.path.join(out, name), 'a') as f:
             f.write(json.dumps(rec) + '\n')
     except OSError:
         pass
