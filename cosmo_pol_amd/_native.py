@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
                  'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'sz_total',
-                 'DSPECTRUM', 'mask_sum8']
+                 'DSPECTRUM', 'mask_sum8', 'spectrum_moments']
 
 
 SUPEROB_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL']    # the rows of `count`
@@ -121,9 +121,20 @@ class MemberStats(C.Structure):
                    ('quantile', C.c_void_p * len(MEMBER_STATS_FIELDS))])
 
 
+SPECTRUM_MOMENTS_FIELDS = ['POWER', 'VMEAN', 'WIDTH', 'SKEWNESS', 'KURTOSIS', 'VPEAK', 'VLOW', 'VHIGH']    # the rows of `moments`
+
+
+class SpectrumMoments(C.Structure):
+    """cpol_spectrum_moments: the moments of every gate's Doppler spectrum (cosmo_pol_amd/spectrum_moments.py states the
+    rule).  fields: bit k = row k of `moments` [8][n_rays * n_gates]."""
+    _fields_ = [('fields', C.c_uint32), ('min_bins', C.c_int32), ('min_power', C.c_double), ('moments', C.c_void_p),
+                ('count', C.c_void_p)]
+
+
 class Outputs(C.Structure):
-    # member_stats, superob: NULL = off; superob stays the last member (cpol_outputs)
-    _fields_ = ([(n, C.c_void_p) for n in OUTPUT_FIELDS]
+    # spectrum_moments (the last of OUTPUT_FIELDS: a pointer to a struct, not an array), member_stats, superob: NULL = off;
+    # superob stays the last member (cpol_outputs)
+    _fields_ = ([(n, C.POINTER(SpectrumMoments) if n == 'spectrum_moments' else C.c_void_p) for n in OUTPUT_FIELDS]
                 + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
 
@@ -860,6 +871,42 @@ class Context(object):
         del keep
         out['count'] = {k: cnt[SUPEROB_FIELDS.index(k)] for k in asked}
         return out
+
+    @staticmethod
+    def spectrum_moments_struct(spec):
+        """SpectrumMoments for a call under `spec` (a spectrum_moments.SpectrumMoments); the output pointers are the caller's."""
+        sm = SpectrumMoments()
+        sm.fields, sm.min_bins, sm.min_power = spec.mask, spec.min_bins, spec.min_power
+        return sm
+
+    def spectrum_moments_rows(self, spectrum, varray, spec, out=None):
+        """Test hook (cpol_debug_read "spectrum_moments_rows"): k_spec_moments on caller-supplied spectra [n_rows, n_v]
+        (float64, every row a gate) and velocity bins [n_v] -> what spectrum_moments.moments returns for them: the kernel on
+        rows no sweep produces.  `spec`: a spectrum_moments.SpectrumMoments.  `out`: a float64 [8, n_rows] array the library
+        writes the requested rows of (default: a fresh one); the result's arrays are its rows."""
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_v', C.c_int32), ('spectrum', C.c_void_p), ('varray', C.c_void_p),
+                        ('sm', SpectrumMoments)]
+        S = np.ascontiguousarray(spectrum, dtype=np.float64)
+        V = np.ascontiguousarray(varray, dtype=np.float64)
+        if S.ndim != 2 or V.ndim != 1 or S.shape[1] != V.shape[0]:
+            raise ValueError('spectrum_moments_rows: spectrum is [n_rows, n_v], varray [n_v]')
+        n_rows = S.shape[0]
+        if out is None:
+            out = np.empty((len(SPECTRUM_MOMENTS_FIELDS), n_rows), dtype=np.float64)
+        if out.shape != (len(SPECTRUM_MOMENTS_FIELDS), n_rows) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError('spectrum_moments_rows: out is a contiguous float64 [8, n_rows] array')
+        cnt = np.zeros(n_rows, dtype=np.uint16)
+        h = Hook()
+        h.n_rows, h.n_v = S.shape
+        h.spectrum, h.varray = S.ctypes.data, V.ctypes.data
+        h.sm = self.spectrum_moments_struct(spec)
+        h.sm.moments, h.sm.count = out.ctypes.data, cnt.ctypes.data
+        rc = int(self.lib.cpol_debug_read(self.h, b'spectrum_moments_rows', C.byref(h), C.sizeof(h)))
+        self._check(rc, 'cpol_debug_read(spectrum_moments_rows)')
+        res = {k: out[SPECTRUM_MOMENTS_FIELDS.index(k)] for k in spec.fields}
+        res['count'] = cnt
+        return res
 
     @staticmethod
     def member_stats_struct(spec, names, phase, capacity=None):

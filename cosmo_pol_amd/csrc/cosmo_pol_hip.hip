@@ -172,6 +172,7 @@ struct cpol_ctx {
     int stg_next = 0;
     DevBuf b_traj, b_wgate, b_clk, b_rayc, b_poly, d_geoM;
     DevBuf b_beam, b_spectrum, b_outwin, b_superob;
+    DevBuf b_smom, b_smcount, b_smvar;     // spectrum moments (cpol_spectrum_moments): the two output arrays; the hook's velocity bins
     // ensemble statistics (cpol_member_stats): the running state of this context's pass, and the block k_member_finish writes
     // when the outputs are host memory outside a window image
     DevBuf b_mstate, b_msout;
@@ -767,7 +768,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -1851,7 +1852,7 @@ static int copy_out(cpol_ctx *ctx, void *dst, const void *src, size_t bytes, boo
 }
 
 // The device pointers of a placement plan (cpol_place.h): the buffers of the context grown to what the plan asks for, their bases
-// added.  sweep_own[i]: the buffer of the sweep's own array i (the sweep's arrays come first in the list; NULL: the list has none)
+// added.  sweep_own[i]: the buffer of array i where it is one of the sweep's own (product PLACE_SWEEP; NULL: the list has none)
 static int place_resolve(cpol_ctx *ctx, const PlaceArray *arr, int n, const PlacePlan &plan, DevBuf *const *sweep_own, void **T)
 {
     DevBuf *const block[PLACE_PRODUCTS] = {nullptr, &ctx->b_superob, &ctx->b_msout};
@@ -2219,6 +2220,82 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
     return CPOL_OK;
 }
 
+// ---- spectrum moments (cpol_spectrum_moments, k_spec_moments in cpol_spectrum.inl): the checks and the launch, shared by the
+// launch sequence and the test hook ----
+enum { SM_MOMENTS = 0, SM_COUNT, SM_N };
+
+// every refusal of a cpol_spectrum_moments for a call of n_rg gates; queues nothing.  arr[SM_N]: the caller's arrays for the
+// placement plan (cpol_place.h): arrays of the sweep itself, each with a grow-only buffer of its own
+static int spec_moments_plan(cpol_ctx *ctx, const cpol_spectrum_moments *sm, long n_rg, bool dop3, PlaceArray *arr)
+{
+    auto bad = [&](const char *why) { ctx->err = std::string("cpol_spectrum_moments: ") + why; return CPOL_ERR_ARG; };
+    if (!dop3) return bad("the moments are those of the Doppler spectrum: simulate_doppler must be 3");
+    if (sm->fields == 0 || (sm->fields >> CPOL_SM_FIELDS) != 0) return bad("fields must name at least one of the 8 rows and no other bit");
+    if (sm->min_bins < 1 || sm->min_bins > 65535) return bad("min_bins must lie in 1 ... 65535");
+    if (!(sm->min_power >= 0.0 && sm->min_power <= 1.7976931348623157e308)) return bad("min_power must be >= 0 and finite");
+    if (!sm->moments) return bad("moments is NULL");
+    arr[SM_MOMENTS] = PlaceArray{};
+    arr[SM_MOMENTS].user = (uintptr_t)sm->moments;
+    arr[SM_MOMENTS].bytes = (size_t)CPOL_SM_FIELDS * n_rg * sizeof(double);
+    arr[SM_MOMENTS].rows = CPOL_SM_FIELDS;              // (only the rows in `fields` are the caller's to be written)
+    arr[SM_MOMENTS].row_mask = sm->fields;
+    arr[SM_COUNT] = PlaceArray{};
+    arr[SM_COUNT].user = (uintptr_t)sm->count;
+    arr[SM_COUNT].bytes = (size_t)n_rg * sizeof(uint16_t);
+    arr[SM_MOMENTS].produced = arr[SM_COUNT].produced = true;
+    arr[SM_MOMENTS].product = arr[SM_COUNT].product = PLACE_SWEEP;
+    return CPOL_OK;
+}
+
+// spectrum [n_rg][n_v] and varray [n_v]: device arrays; T: where the kernel writes
+static int spec_moments_launch(cpol_ctx *ctx, const cpol_spectrum_moments *sm, const double *spectrum, const double *varray,
+                               void *const T[SM_N], long n_rg, int n_v, bool zero_rest, hipStream_t st)
+{
+    SpecMomentsArgs ma{};
+    ma.spectrum = spectrum; ma.varray = varray;
+    ma.moments = (double *)T[SM_MOMENTS];
+    ma.count = (unsigned short *)T[SM_COUNT];
+    ma.n_rg = n_rg; ma.n_v = n_v;
+    ma.fields = sm->fields; ma.min_bins = sm->min_bins; ma.min_power = sm->min_power;
+    ma.zero_rest = zero_rest;
+    hipLaunchKernelGGL(k_spec_moments, dim3((unsigned)cdiv(n_rg, CPOL_SM_GATES_PER_BLOCK)), dim3(64 * CPOL_SM_GATES_PER_BLOCK), 0, st, ma);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "spectrum_moments_rows": k_spec_moments on caller-supplied spectra (host memory in, host memory
+// out, blocking) -- the kernel on rows no sweep produces (every row length, infinities, subnormals, ties, rows without a bin).
+struct SpecMomentsHook {
+    int32_t n_rows, n_v;
+    const double *spectrum;                 // [n_rows][n_v]: every row a gate
+    const double *varray;                   // [n_v]
+    cpol_spectrum_moments sm;               // host output pointers sized for n_rows gates
+};
+
+static int spec_moments_hook(cpol_ctx *ctx, const SpecMomentsHook *h)
+{
+    if (h->n_rows < 1 || h->n_v < 1 || h->n_v > 4097 || !h->spectrum || !h->varray) {
+        ctx->err = "spectrum_moments_rows: bad shape (n_rows >= 1, n_v in 1 ... 4097) or a NULL input";
+        return CPOL_ERR_ARG;
+    }
+    PlaceArray arr[SM_N];
+    int rc = spec_moments_plan(ctx, &h->sm, h->n_rows, true, arr);
+    if (rc != CPOL_OK) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, ctx->b_spectrum, h->spectrum, (size_t)h->n_rows * h->n_v * sizeof(double))) != CPOL_OK) return rc;
+    if ((rc = upload(ctx, ctx->b_smvar, h->varray, (size_t)h->n_v * sizeof(double))) != CPOL_OK) return rc;
+    PlacePlan plan;
+    place_outputs(arr, SM_N, 0, false, &plan);
+    DevBuf *const own[SM_N] = {&ctx->b_smom, &ctx->b_smcount};
+    void *T[SM_N];
+    if ((rc = place_resolve(ctx, arr, SM_N, plan, own, T)) != CPOL_OK) return rc;
+    if ((rc = spec_moments_launch(ctx, &h->sm, (const double *)ctx->b_spectrum.p, (const double *)ctx->b_smvar.p, T, h->n_rows, h->n_v,
+                                  false, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -2311,7 +2388,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_N = A_MS + MS_N };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     PlaceArray arr[A_N];
     // superobservations (cpol_superob): every refusal here, before anything of the call is queued
@@ -2331,6 +2408,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (timed) { ctx->err = "cpol_member_stats: a time-blended call (tables->time_blend) folds no members"; return CPOL_ERR_ARG; }
         const int rc_ms = member_stats_plan(ctx, ms, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_MS);
         if (rc_ms != CPOL_OK) return rc_ms;
+    }
+    // spectrum moments (cpol_spectrum_moments): likewise
+    const cpol_spectrum_moments *const sm = out->spectrum_moments;
+    if (sm) {
+        if (cols || sub_out || mem) { ctx->err = "cpol_spectrum_moments: cpol_run_sweep takes spectrum moments, no other entry point"; return CPOL_ERR_ARG; }
+        if (so || ms) { ctx->err = "cpol_spectrum_moments: not together with superobservations or ensemble statistics in one call"; return CPOL_ERR_ARG; }
+        const int rc_sm = spec_moments_plan(ctx, sm, n_rg, p->simulate_doppler == 3, arr + A_SM);
+        if (rc_sm != CPOL_OK) return rc_sm;
     }
     int rc;
 
@@ -2687,7 +2772,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
                                  out->DSPECTRUM, out->mask_sum8};
-    DevBuf *own[O_N];              // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
+    DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
+    own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
     for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
@@ -2710,7 +2796,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const bool window = plan.window;
     void *T_all[A_N];
     if ((rc = place_resolve(ctx, arr, A_N, plan, own, T_all)) != CPOL_OK) return rc;
-    void *const *const T = T_all, *const *const so_T = T_all + A_SO, *const *const ms_T = T_all + A_MS;
+    void *const *const T = T_all, *const *const so_T = T_all + A_SO, *const *const ms_T = T_all + A_MS, *const *const sm_T = T_all + A_SM;
 
     // the bucket counters start at zero: cleared by k_interp_sweep (no fill kernel); the domain
     // error word is sticky (cleared when reported)
@@ -3448,6 +3534,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                                    T[O_ATTV], T[O_RVEL]};
         if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st)) != CPOL_OK) return rc;
     }
+    // ---- spectrum moments: ONE kernel behind the sequence, on the spectrum wherever it was placed (outside launch_all too) ----
+    if (sm && (rc = spec_moments_launch(ctx, sm, (const double *)T[O_SPEC], (const double *)ctx->v_varray, sm_T, n_rg, n_vb, window, st)) != CPOL_OK)
+        return rc;
     // ---- outputs that the kernels did not write in place ----
     if (window)
         HIPCHK(hipMemcpyAsync((void *)plan.win_lo, (const char *)ctx->b_outwin.p + plan.win_skew, (size_t)(plan.win_hi - plan.win_lo), hipMemcpyDeviceToHost, st));
@@ -3506,6 +3595,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
 {
     if (!ctx) return CPOL_ERR_ARG;
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
         !c->vals || !c->elev || !c->sub_w) {
@@ -3572,6 +3662,7 @@ int cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol
         ctx->err = "cpol_run_sweep_members: bad arguments (1 <= n_members <= 64 per call)";
         return CPOL_ERR_ARG;
     }
+    if (out->spectrum_moments) { ctx->err = "cpol_run_sweep_members: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (t->time_blend != 0) {
         // ---- ONE scan, every ray blended from the two states that bracket its time ----
         if (t->time_blend != 1 || !t->ray_state || !t->ray_weight) {
@@ -3802,6 +3893,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "member_stats_fields")) {     // a CONTROL name: dst points to a MemberStatsHook
         if (!dst || max_bytes < (int64_t)sizeof(MemberStatsHook)) { ctx->err = "cpol_debug_read(member_stats_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return member_stats_hook(ctx, (const MemberStatsHook *)dst);
+    }
+    if (!strcmp(name, "spectrum_moments_rows")) {   // a CONTROL name: dst points to a SpecMomentsHook
+        if (!dst || max_bytes < (int64_t)sizeof(SpecMomentsHook)) { ctx->err = "cpol_debug_read(spectrum_moments_rows): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return spec_moments_hook(ctx, (const SpecMomentsHook *)dst);
     }
     if (!strcmp(name, "superob_fields")) {          // a CONTROL name: dst points to a SuperobHook
         if (!dst || max_bytes < (int64_t)sizeof(SuperobHook)) { ctx->err = "cpol_debug_read(superob_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }

@@ -582,3 +582,99 @@ __global__ __launch_bounds__(64) void k_spec_final(SpecFinalArgs a)
     }
 }
 
+// ---- spectrum moments (cpol_spectrum_moments): power, mean velocity, width, skewness, kurtosis, peak and edges per gate ----
+// Reference functions replaced (wolfidan/cosmo_pol): none -- the reference forms no moment of the spectrum but RVEL.  The
+// rule is the one of include/cosmo_pol_amd.h and cosmo_pol_amd/spectrum_moments.py (`moments`), ORDER-EXACT: every sum is
+// 64 lane sums over the counting bins v = l, l + 64, ... in ascending order from +0.0, then the butterfly off = 32 ... 1 in
+// which every lane adds its partner's value to its own (IEEE addition commutes: the 64 lanes end with the same bits).  Only
+// IEEE adds, multiplies, divides and one square root; the TU is compiled with -ffp-contract=off -fno-fast-math.
+#define CPOL_SM_FIELDS 8            // POWER, VMEAN, WIDTH, SKEWNESS, KURTOSIS, VPEAK, VLOW, VHIGH (the rows of `moments`)
+#define CPOL_SM_GATES_PER_BLOCK 4   // one wavefront per gate, four gates per workgroup
+
+struct SpecMomentsArgs {
+    const double *spectrum;     // [n_rg][n_v] as k_spec_final leaves it (censored bins are NaN)
+    const double *varray;       // [n_v]
+    double *moments;            // [8][n_rg]
+    unsigned short *count;      // [n_rg] or NULL
+    long n_rg;
+    int n_v;
+    unsigned fields;            // bit k: row k is written
+    int min_bins;
+    double min_power;
+    int zero_rest;              // 1: the rows of `moments` nobody asked for are written as zeros (a window image)
+};
+
+__device__ __forceinline__ double spec_moments_sum(double a, int lane)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a = a + shfl_f64(a, lane ^ off);
+    return a;
+}
+
+// Pass 1 reads the row once (lanes on consecutive float64 bins: 512 B per wavefront load), pass 2 reads it again -- 2 KB to
+// 32 KB per gate, which the cache still holds.  A gate with fewer counting bins than min_bins leaves after pass 1.
+__global__ __launch_bounds__(64 * CPOL_SM_GATES_PER_BLOCK) void k_spec_moments(const SpecMomentsArgs a)
+{
+    const long rg = (long)blockIdx.x * CPOL_SM_GATES_PER_BLOCK + (threadIdx.x >> 6);
+    if (rg >= a.n_rg) return;                                           // (wave-uniform; the kernel has no barrier)
+    const int lane = threadIdx.x & 63;
+    const double *__restrict__ S = a.spectrum + rg * a.n_v;
+    const double *__restrict__ V = a.varray;
+    double aP = 0.0, aM = 0.0, pk = -1.0;                               // (a counting bin is > min_power >= 0)
+    int n = 0, ipk = 0x7fffffff, ilo = 0x7fffffff, ihi = -1;
+    for (int v = lane; v < a.n_v; v += 64) {
+        const double s = S[v];
+        if (s == s && s > a.min_power) {
+            aP = aP + s;
+            aM = aM + V[v] * s;
+            ++n;
+            if (s > pk) { pk = s; ipk = v; }
+            if (v < ilo) ilo = v;
+            ihi = v;
+        }
+    }
+    const double P = spec_moments_sum(aP, lane), M = spec_moments_sum(aM, lane);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        n += __shfl(n, lane ^ off);
+        ilo = min(ilo, __shfl(ilo, lane ^ off));
+        ihi = max(ihi, __shfl(ihi, lane ^ off));
+        const double pk2 = shfl_f64(pk, lane ^ off);
+        const int ipk2 = __shfl(ipk, lane ^ off);
+        if (pk2 > pk || (pk2 == pk && ipk2 < ipk)) { pk = pk2; ipk = ipk2; }     // larger value, then lower index
+    }
+    const double nan = __builtin_nan("");
+    double out[CPOL_SM_FIELDS] = {nan, nan, nan, nan, nan, nan, nan, nan};
+    if (n >= a.min_bins) {                                              // (wave-uniform; min_bins >= 1: n >= 1 here)
+        const double vbar = M / P;
+        double a2 = 0.0, a3 = 0.0, a4 = 0.0;
+        for (int v = lane; v < a.n_v; v += 64) {
+            const double s = S[v];
+            if (s == s && s > a.min_power) {
+                const double d = V[v] - vbar;
+                const double d2 = d * d;
+                a2 = a2 + d2 * s;
+                a3 = a3 + (d2 * d) * s;
+                a4 = a4 + (d2 * d2) * s;
+            }
+        }
+        const double C2 = spec_moments_sum(a2, lane), C3 = spec_moments_sum(a3, lane), C4 = spec_moments_sum(a4, lane);
+        const double var = C2 / P;
+        const double width = sqrt(var);
+        out[0] = P;
+        out[1] = vbar;
+        out[2] = width;
+        out[3] = (C3 / P) / (var * width);
+        out[4] = (C4 / P) / (var * var);
+        out[5] = V[ipk];
+        out[6] = V[ilo];
+        out[7] = V[ihi];
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int k = 0; k < CPOL_SM_FIELDS; ++k) {
+        if ((a.fields >> k) & 1u) a.moments[(long)k * a.n_rg + rg] = out[k];
+        else if (a.zero_rest) a.moments[(long)k * a.n_rg + rg] = 0.0;
+    }
+    if (a.count) a.count[rg] = (unsigned short)n;
+}

@@ -28,6 +28,7 @@ from . import geometry as geo
 from . import hydrometeors as hyd
 from . import quadrature
 from . import ensemble_stats as ES
+from . import spectrum_moments as SM
 from . import superob as SO
 from .lut import load_all_lut
 
@@ -825,10 +826,37 @@ class RadarOperator(object):
                                    paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
                                    rays_per_block=rays_per_block)
 
+    def simulate_rays_moments(self, azimuths, elevations, moments, keep_spectrum=False, device_outputs=None,
+                              apply_sensitivity=True, paths=None, lane=0, pinned=False):
+        """simulate_rays handing back SPECTRUM MOMENTS (Doppler scheme 3): `moments` is a spectrum_moments.SpectrumMoments,
+        and the result gains res['moments'] -- {field: float64 [n_rays, n_gates]} for its fields and 'count' (uint16, the
+        bins that counted), made on the device behind the sweep from the spectrum as the call delivers it
+        (spectrum_moments.moments states the rule).  Without `keep_spectrum` DSPECTRUM is neither produced for the host nor
+        copied and its key is absent; with it the result carries every array of simulate_rays, bit for bit.  With
+        `device_outputs`: its entry 'moments' is {'moments': device pointer of [8, n_rays, n_gates] float64 (only the rows of
+        the requested fields are written), 'count': device pointer}.  The other keywords: as for simulate_rays.  (A method
+        of its own: the keyword list of simulate_rays is pinned.)  ValueError when the configured Doppler scheme is not 3;
+        NotImplementedError with a process group and for spaceborne geometry."""
+        self._moments_check(moments)
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
+                                   paths=paths, lane=lane, pinned=pinned, moments=moments, keep_spectrum=keep_spectrum)
+
+    def _moments_check(self, moments):
+        """What a spectrum-moments call refuses before it builds anything."""
+        if not isinstance(moments, SM.SpectrumMoments):
+            raise ValueError('moments: a cosmo_pol_amd.spectrum_moments.SpectrumMoments, got %r' % (moments,))
+        if self.__config['doppler']['scheme'] != 3:
+            raise ValueError('spectrum moments need the Doppler spectrum: doppler scheme 3, configured is %r'
+                             % (self.__config['doppler']['scheme'],))
+        if self.distributed:
+            raise NotImplementedError('spectrum moments with a process group: the distributed scans collect no moments')
+
     def _simulate_rays(self, azimuths, elevations, device_outputs=None, apply_sensitivity=True, paths=None, lane=0, pinned=False,
-                       superob=None, keep_gates=False, rays_per_block=0):
+                       superob=None, keep_gates=False, rays_per_block=0, moments=None, keep_spectrum=False):
         if superob is not None:
             self._superob_check(superob)
+        if moments is not None:
+            self._moments_check(moments)
         conf = self.__config
         coords = conf['radar']['coords']
         if coords[2] > K.MAX_MODEL_HEIGHT:
@@ -851,7 +879,7 @@ class RadarOperator(object):
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
                               paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
-                              rays_per_block=rays_per_block)
+                              rays_per_block=rays_per_block, moments=moments, keep_spectrum=keep_spectrum)
 
     def stencil_state(self, lane=0):
         """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
@@ -1206,11 +1234,16 @@ class RadarOperator(object):
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
                   pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0,
-                  member_stats=None):
+                  member_stats=None, moments=None, keep_spectrum=False):
         if self._model_staged:
             self._sync_edr()
         if superob is not None:
             self._superob_check(superob)
+        if moments is not None:
+            self._moments_check(moments)
+            if superob is not None or member_stats is not None or members is not None or timed is not None or subbeams is not None:
+                raise ValueError('spectrum moments are taken by the plain sweeps: no superobservations, ensembles, time blend '
+                                 'or sub-beam calls')
         if member_stats is not None:
             # (spec, phase, keep_members[, members of the whole pass]): this call's member(s) folded into the lane's running
             # ensemble statistics
@@ -1369,6 +1402,12 @@ class RadarOperator(object):
             keep = list(keep) + ms_thr
             o.member_stats = C.pointer(ms)
         ms_out = ms is not None and bool(ms_phase & 2)      # a finishing call: the statistics arrive with it
+        sm = None
+        if moments is not None:
+            if not spectrum:                      # (a GPM-type radar: no Doppler whatever the scheme says)
+                raise ValueError('spectrum moments need the Doppler spectrum, and this radar simulates none')
+            sm = N.Context.spectrum_moments_struct(moments)
+            o.spectrum_moments = C.pointer(sm)
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
                 if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': pointer}
@@ -1382,6 +1421,14 @@ class RadarOperator(object):
                             raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
                         for kk, q in pp.items():
                             getattr(ms, kind)[ES.FIELDS.index(kk)] = q
+                    continue
+                if k == 'moments':                # {'moments': device pointer of [8, n_rays, n_gates], 'count': device pointer}
+                    if sm is None:
+                        raise ValueError("device_outputs['moments'] without moments=")
+                    for kk, pp in ptr.items():
+                        if kk not in ('moments', 'count'):
+                            raise ValueError("device_outputs['moments']: unknown entry %r" % (kk,))
+                        setattr(sm, kk, pp)
                     continue
                 if k == 'superob':                # {field or 'count': device pointer}
                     if so is None:
@@ -1398,7 +1445,7 @@ class RadarOperator(object):
             spec = [(k, np.float32, shape) for k in RADAR_FIELDS] if gates else []
             if doppler and gates:
                 spec.append(('RVEL', np.float64, shape))
-            if spectrum and gates:
+            if spectrum and gates and (sm is None or keep_spectrum):
                 spec.append(('DSPECTRUM', np.float64, shape + (len(varray),)))
             # (pinned calls only: a blocking call would have to widen the bytes on the caller's thread at once -- ~1 ns per gate,
             # more than the 7 bytes per gate cost on PCIe; measured on the c5 swaths, 1.7 M gates: 8.5 -> 12.7 ms per step)
@@ -1421,6 +1468,10 @@ class RadarOperator(object):
                     wshape = (len(members),) + wshape
                 spec += [(('superob', k), np.float64 if k == 'RVEL' else np.float32, wshape) for k in so_fields]
                 spec.append((('superob', 'count'), np.uint16, (len(SO.FIELDS),) + wshape))
+            if sm is not None:
+                # the moments, in the same block: they ride the one copy (rows nobody asked for arrive as zeros)
+                spec.append((('moments', 'moments'), np.float64, (len(SM.FIELDS),) + shape))
+                spec.append((('moments', 'count'), np.uint16, shape))
             if ms_out:
                 # the statistics, in the same block: they ride the one copy
                 for kind in ms_spec.kinds:
@@ -1447,6 +1498,9 @@ class RadarOperator(object):
                     else:
                         res.setdefault('stats', {}).setdefault(k[1], {})[k[2]] = a
                         getattr(ms, k[1])[ES.FIELDS.index(k[2])] = base + off
+                elif isinstance(k, tuple) and k[0] == 'moments':
+                    res.setdefault('moments', {})[k[1]] = a
+                    setattr(sm, k[1], base + off)
                 elif isinstance(k, tuple):
                     res.setdefault('superob', {})[k[1]] = a
                     setattr(so, k[1], base + off)
@@ -1506,6 +1560,10 @@ class RadarOperator(object):
                     if pinned:
                         ctx.synchronize()
                     w.update(SO.coordinates(res, superob, so_rpb))
+        if sm is not None and device_outputs is None:
+            w = res['moments']
+            rows = w.pop('moments')
+            w.update({k: rows[SM.FIELDS.index(k)] for k in moments.fields})
         if ms_out and device_outputs is None:
             w = res['stats']
             cnt = w.pop('count')
@@ -2263,6 +2321,39 @@ class RadarOperator(object):
         """The sweeps of get_RHI as superobservations: one result per azimuth (see get_PPI_superob)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._superob_sweeps(sweeps, spec, keep_gates)
+
+    # ------------------------------------------------------------------ spectrum moments scans
+    def _moments_sweeps(self, sweeps, moments, keep_spectrum):
+        """One pinned call per sweep over the lanes, one wait at the end: every sweep carries the bits of its own
+        simulate_rays_moments(..., moments)."""
+        self._moments_check(moments)
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        n_par = max(1, min(self.lanes, len(sweeps)))
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                res.append(self.simulate_rays_moments(az, el, moments, keep_spectrum=keep_spectrum, pinned=True, lane=k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        return res
+
+    def get_PPI_moments(self, elevations, moments, azimuths=None, az_step=None, az_start=0, az_stop=359, keep_spectrum=False):
+        """The sweeps of get_PPI with spectrum moments: a list with one simulate_rays_moments(..., moments) result per
+        elevation (res['moments']), the sweeps spread over the lanes."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._moments_sweeps(sweeps, moments, keep_spectrum)
+
+    def get_RHI_moments(self, azimuths, moments, elevations=None, elev_step=None, elev_start=0, elev_stop=90, keep_spectrum=False):
+        """The sweeps of get_RHI with spectrum moments: one result per azimuth (see get_PPI_moments)."""
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._moments_sweeps(sweeps, moments, keep_spectrum)
 
     # ------------------------------------------------------------------ ensemble statistics scans
     def _ensemble_stats_sweeps(self, sweeps, stats, members):

@@ -376,6 +376,43 @@ typedef struct cpol_member_stats {
                                                            NULL = not wanted; read by a finishing call             */
 } cpol_member_stats;
 
+/* Spectrum moments: what a user of a Doppler radar simulation compares with a radar instead of the spectrum itself -- per gate
+ * the power, the mean velocity, the spectrum width, skewness and kurtosis, the peak and the edges of the gate's Doppler spectrum
+ * AS THE CALL DELIVERS IT.  Replaces in the reference: nothing (it forms no moment of the spectrum but RVEL).  Pointed to by
+ * cpol_outputs.spectrum_moments; honoured by cpol_run_sweep with simulate_doppler == 3.
+ * INPUT per gate: the row S[0 .. n_v-1] of DSPECTRUM as k_spec_final leaves it, float64 -- after the sub-beam accumulation and
+ * after the bin-by-bin sensitivity cut, so censored bins are NaN -- and V[v], the caller's float64 varray.  The gate-level ZH
+ * censoring of the other observables is NOT applied and nothing is folded into the Nyquist interval: the result is what the
+ * rule below gives on the host for the delivered DSPECTRUM.
+ * COUNTING: a bin counts iff S[v] == S[v] && S[v] > min_power (min_power >= 0, finite, linear units); n = the counting bins.
+ * ORDERED SUM R[t] of a per-bin term t, float64, every operation one IEEE operation (no contraction, no reciprocal):
+ *     for lane l = 0 .. 63: a_l = +0.0; then for v = l, l + 64, l + 128, ... ascending below n_v, if bin v counts:
+ *     a_l = a_l + t[v]; then for off = 32, 16, 8, 4, 2, 1: every lane at once a_l = a_l + a_(l xor off); R[t] = a_0 (all lanes
+ *     hold the same value).
+ * PASS 1: P = R[S]; M = R[V * S] (the product formed first, then added); vbar = M / P.
+ * PASS 2, per counting bin d = V[v] - vbar, d2 = d * d: C2 = R[d2 * S]; C3 = R[(d2 * d) * S]; C4 = R[(d2 * d2) * S].
+ * FINISHING: var = C2 / P; WIDTH = sqrt(var); SKEWNESS = (C3 / P) / (var * WIDTH); KURTOSIS = (C4 / P) / (var * var);
+ * POWER = P; VMEAN = vbar; VPEAK = V[i], i the lowest index among the counting bins that hold the largest S; VLOW = V[lowest
+ * counting index]; VHIGH = V[highest counting index].  Every field is NaN where n < min_bins; count = n always (uint16).
+ * Not special-cased: n == 1 gives WIDTH = 0 and NaN for skewness and kurtosis; overflow gives the inf or NaN IEEE gives.
+ * ROWS of `moments` (bit k of `fields`): POWER, VMEAN, WIDTH, SKEWNESS, KURTOSIS, VPEAK, VLOW, VHIGH.
+ * The output pointers follow p->outputs_on_device like every other array (mode 2: they count for the one-copy window rule; rows
+ * of `moments` outside `fields` that lie inside the window arrive as zeros).
+ * CPOL_ERR_ARG, nothing queued, the context usable: the struct set outside Doppler scheme 3; fields zero or with a bit >= 8;
+ * min_bins < 1 or > 65535; min_power negative, NaN or infinite; moments NULL; outputs->superob or outputs->member_stats set in
+ * the same call; cpol_run_sweep_members and cpol_run_columns.
+ * ONE kernel (k_spec_moments, one wavefront per gate) runs behind the launch sequence and before the output copy: the per-gate
+ * arrays, the launch forms, the gate stencils and a captured graph are what they are without it.  When the caller leaves
+ * DSPECTRUM NULL the spectrum is still produced on the device (the context's own buffer) and simply not copied. */
+#define CPOL_SPECTRUM_MOMENTS_FIELDS 8
+typedef struct cpol_spectrum_moments {
+    uint32_t fields;            /* bit k: row k wanted                                                             */
+    int32_t  min_bins;          /* need >= 1                                                                       */
+    double   min_power;         /* >= 0, finite                                                                    */
+    double  *moments;           /* [8][n_rays * n_gates]; only the rows in `fields` are the caller's to be written */
+    uint16_t *count;            /* [n_rays * n_gates] or NULL                                                      */
+} cpol_spectrum_moments;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -391,7 +428,9 @@ typedef struct {
                                    domain; doppler_scatter.py:472-477), one byte per gate instead of the eight of `mask`.
                                    mask = mask_sum8 / n_sub, then values in (-1, 0] -> 0: the caller's two NumPy statements.
                                    Needs 2 * n_sub <= 127.  When it is asked for and `mask` is not, `mask` is not written. */
-    cpol_member_stats *member_stats;    /* NULL (a zero-initialised struct): off.  The call's member(s) folded into the
+    cpol_spectrum_moments *spectrum_moments;    /* NULL (a zero-initialised struct): off.  The moments of every gate's Doppler
+                                   spectrum (Doppler scheme 3), see cpol_spectrum_moments */
+    cpol_member_stats *member_stats;   /* NULL (a zero-initialised struct): off.  The call's member(s) folded into the
                                    context's running ensemble statistics, see cpol_member_stats */
     cpol_superob *superob;     /* NULL (a zero-initialised struct): off.  Window averages of the fields above, see cpol_superob.
                                    Stays the LAST member */
@@ -774,6 +813,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * ms; } -- `in[k]` a host array [n_members][n_cells] (float32, slot RVEL float64; needed for every folded field when n_members
  * > 0; n_members = 0 folds nothing), `ms` with host output pointers; blocking; honours ms.phase, so a pass can be cut into
  * calls; cpol_member_stats' refusals (Doppler counts as on).  Returns 0.
+ * "spectrum_moments_rows" is the sibling for the spectrum moments: k_spec_moments on caller-supplied spectra.  dst points to
+ * { int32_t n_rows, n_v; const double *spectrum; const double *varray; cpol_spectrum_moments sm; } -- host arrays, `spectrum`
+ * [n_rows][n_v], every row treated as a gate, `varray` [n_v], `sm` with host output pointers sized for n_rows gates; blocking;
+ * needs no staged model or tables; cpol_spectrum_moments' refusals (Doppler scheme 3 counts as on), and CPOL_ERR_ARG for
+ * n_rows < 1, n_v outside 1..4097 or a NULL input.  Returns 0.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
