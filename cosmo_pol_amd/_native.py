@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
                  'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'sz_total',
-                 'DSPECTRUM', 'mask_sum8', 'spectrum_moments']
+                 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
 SUPEROB_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL']    # the rows of `count`
@@ -121,6 +121,14 @@ class MemberStats(C.Structure):
                    ('quantile', C.c_void_p * len(MEMBER_STATS_FIELDS))])
 
 
+class MemberVerify(C.Structure):
+    """cpol_member_verify: the members of a pass of ensemble statistics scored against observations
+    (cosmo_pol_amd/ensemble_verify.py states the rule).  fields: bit k = verify field k; a zero-initialised struct verifies
+    nothing."""
+    _fields_ = ([('fields', C.c_uint32), ('fair', C.c_int32)]
+                + [(n, C.c_void_p * len(MEMBER_STATS_FIELDS)) for n in ('obs', 'below', 'equal', 'crps')])
+
+
 SPECTRUM_MOMENTS_FIELDS = ['POWER', 'VMEAN', 'WIDTH', 'SKEWNESS', 'KURTOSIS', 'VPEAK', 'VLOW', 'VHIGH']    # the rows of `moments`
 
 
@@ -132,9 +140,10 @@ class SpectrumMoments(C.Structure):
 
 
 class Outputs(C.Structure):
-    # spectrum_moments (the last of OUTPUT_FIELDS: a pointer to a struct, not an array), member_stats, superob: NULL = off;
-    # superob stays the last member (cpol_outputs)
-    _fields_ = ([(n, C.POINTER(SpectrumMoments) if n == 'spectrum_moments' else C.c_void_p) for n in OUTPUT_FIELDS]
+    # spectrum_moments (the last of OUTPUT_FIELDS) and member_verify (directly before mask_sum8): pointers to a struct, not
+    # arrays; member_stats, superob likewise: NULL = off; superob stays the last member (cpol_outputs)
+    _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify)}.get(n, C.c_void_p))
+                 for n in OUTPUT_FIELDS]
                 + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
 
@@ -924,10 +933,11 @@ class Context(object):
                 keep.append(thr)
                 ms.n_thresholds[i], ms.thresholds[i] = thr.size, thr.ctypes.data
         qs = getattr(spec, 'quantiles', None)
-        if qs:
+        if qs or getattr(spec, 'verify', None):             # (a verified field keeps its members like a field with quantiles)
             from . import ensemble_stats as ES
             ms.quantile_capacity = ES.MAX_QUANTILE_MEMBERS if capacity is None else int(capacity)
             ms.quantile_method = ES.METHODS.index(spec.method)
+        if qs:
             for k in names:
                 if k in qs:
                     i = MEMBER_STATS_FIELDS.index(k)
@@ -936,7 +946,7 @@ class Context(object):
                     ms.n_quantiles[i], ms.quantiles[i] = q.size, q.ctypes.data
         return ms, keep
 
-    def member_stats_fields(self, fields, spec, phase=3, n_cells=None, names=None, capacity=None):
+    def member_stats_fields(self, fields, spec, phase=3, n_cells=None, names=None, capacity=None, _hook=None):
         """Test hook (cpol_debug_read "member_stats_fields"): the product's k_member_fold / k_member_finish and this context's
         running state on caller-supplied members {name: [n_members, n_cells]} of MEMBER_STATS_FIELDS (float32; RVEL float64).
         `spec`: an ensemble_stats.EnsembleStats; `phase`: bit 0 begins a pass, bit 1 finishes it -- a pass may be cut into
@@ -947,7 +957,8 @@ class Context(object):
         class Hook(C.Structure):
             _fields_ = [('n_members', C.c_int32), ('n_cells', C.c_int64), ('inp', C.c_void_p * len(MEMBER_STATS_FIELDS)),
                         ('ms', MemberStats)]
-        h = Hook()
+        # (_hook: member_verify_fields' struct, which begins like this one, and its control name)
+        h, control = _hook if _hook is not None else (Hook(), b'member_stats_fields')
         keep, shape = [], None
         for i, k in enumerate(MEMBER_STATS_FIELDS):
             if k not in fields:
@@ -982,11 +993,53 @@ class Context(object):
                 out['quantile'] = {k: np.empty((len(qs[k]), nc), dtype=np.float64 if k == 'RVEL' else np.float32) for k in names if k in qs}
                 for k, a in out['quantile'].items():
                     h.ms.quantile[MEMBER_STATS_FIELDS.index(k)] = a.ctypes.data
-        rc = int(self.lib.cpol_debug_read(self.h, b'member_stats_fields', C.byref(h), C.sizeof(h)))
-        self._check(rc, 'cpol_debug_read(member_stats_fields)')
+        rc = int(self.lib.cpol_debug_read(self.h, control, C.byref(h), C.sizeof(h)))
+        self._check(rc, 'cpol_debug_read(%s)' % control.decode())
         del keep, thr_keep
         if out is not None:
             out['count'] = {k: cnt[MEMBER_STATS_FIELDS.index(k)] for k in names}
+        return out
+
+    @staticmethod
+    def member_verify_struct(spec):
+        """MemberVerify for a call of a pass under `spec` (an ensemble_verify.EnsembleVerification): fields and fair, which go
+        with every call; the observation and output pointers are the finishing call's."""
+        mv = MemberVerify()
+        for k in spec.verify:
+            mv.fields |= 1 << MEMBER_STATS_FIELDS.index(k)
+        mv.fair = int(spec.fair)
+        return mv
+
+    def member_verify_fields(self, fields, observations, spec, phase=3, n_cells=None, names=None, capacity=None):
+        """Test hook (cpol_debug_read "member_verify_fields"): member_stats_fields with a verification beside it
+        (k_member_verify).  `spec`: an ensemble_verify.EnsembleVerification; `observations` {name: [n_cells]} of the verified
+        fields (read by a finishing call; None otherwise).  A finishing call returns what ensemble_verify.finish returns, every
+        other call None."""
+        class Hook(C.Structure):
+            _fields_ = [('n_members', C.c_int32), ('n_cells', C.c_int64), ('inp', C.c_void_p * len(MEMBER_STATS_FIELDS)),
+                        ('ms', MemberStats), ('mv', MemberVerify)]
+        h = Hook()
+        h.mv = self.member_verify_struct(spec)
+        keep = []
+        if int(phase) & 2:
+            nc = int(n_cells) if not fields else np.shape(next(iter(fields.values())))[1]
+            ver = {'below': {}, 'equal': {}, 'crps': {}}
+            for k in spec.verify:
+                i = MEMBER_STATS_FIELDS.index(k)
+                T = np.float64 if k == 'RVEL' else np.float32
+                y = np.ascontiguousarray(observations[k], dtype=T)
+                if y.shape != (nc,):
+                    raise ValueError('member_verify_fields: every observation is [n_cells]')
+                keep.append(y)
+                h.mv.obs[i] = y.ctypes.data
+                for kind, dt in (('below', np.uint16), ('equal', np.uint16), ('crps', T)):
+                    ver[kind][k] = np.empty(nc, dtype=dt)
+                    getattr(h.mv, kind)[i] = ver[kind][k].ctypes.data
+        out = self.member_stats_fields(fields, spec, phase=phase, n_cells=n_cells, names=names, capacity=capacity,
+                                       _hook=(h, b'member_verify_fields'))
+        del keep
+        if out is not None:
+            out['verify'] = ver
         return out
 
     FORM_NAMES = ('g1r', 'gate1_ray', 'gate1', 'interp_classify', 'rare_direct', 'subbeam_sum', 'final_inplace',

@@ -176,7 +176,8 @@ struct cpol_ctx {
     // ensemble statistics (cpol_member_stats): the running state of this context's pass, and the block k_member_finish writes
     // when the outputs are host memory outside a window image
     DevBuf b_mstate, b_msout;
-    DevBuf b_mstash;                       // ... and the members of the fields with quantiles: [capacity][n_cells] each, sized when a pass begins
+    DevBuf b_mstash;                       // ... and the members of the fields with quantiles or a verification: [capacity][n_cells] each, sized when a pass begins
+    DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
     struct MemberPass {
         bool open = false;
         long n_cells = 0, folded = 0;
@@ -191,6 +192,10 @@ struct cpol_ctx {
         int n_q[CPOL_MS_FIELDS] = {};
         double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q] = {};
         void *stash[CPOL_MS_FIELDS] = {};
+        // verification (cpol_member_verify): the pass was begun with the struct, and its terms
+        bool v_on = false;
+        unsigned v_fields = 0;
+        int v_fair = 0;
     } mpass;
     size_t spec_lds_allowed = 64 * 1024;   // (root context) the largest dynamic LDS asked for k_spec_gate so far (hipFuncSetAttribute)
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
@@ -768,7 +773,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -1988,7 +1993,8 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
 // ---- ensemble statistics (cpol_member_stats, cpol_member_stats.inl): the checks, the pass and the launches, shared by the
 // launch sequence and the test hook ----
 enum { MS_MEAN = 0, MS_SPREAD = CPOL_MS_FIELDS, MS_MIN = 2 * CPOL_MS_FIELDS, MS_MAX = 3 * CPOL_MS_FIELDS, MS_COUNT = 4 * CPOL_MS_FIELDS,
-       MS_EXCEED, MS_QUANTILE = MS_EXCEED + CPOL_MS_FIELDS, MS_N = MS_QUANTILE + CPOL_MS_FIELDS };
+       MS_EXCEED, MS_QUANTILE = MS_EXCEED + CPOL_MS_FIELDS, MS_BELOW = MS_QUANTILE + CPOL_MS_FIELDS, MS_EQUAL = MS_BELOW + CPOL_MS_FIELDS,
+       MS_CRPS = MS_EQUAL + CPOL_MS_FIELDS, MS_N = MS_CRPS + CPOL_MS_FIELDS };
 struct MemberStatsPlan {
     long cells;
     int n_sets;
@@ -1998,14 +2004,19 @@ struct MemberStatsPlan {
     bool q_any;                                     // a folded field has quantiles
     int n_q[CPOL_MS_FIELDS];
     double q[CPOL_MS_FIELDS][CPOL_MS_MAX_Q];
+    bool v_on;                                      // the call carries a cpol_member_verify
+    unsigned v_fields;
+    int v_fair;
 };
 
-// every refusal of a cpol_member_stats for a call that folds n_sets row sets of n_cells cells; queues and changes nothing.
+// every refusal of a cpol_member_stats, and of the cpol_member_verify beside it (mv; NULL: none), for a call that folds n_sets row
+// sets of n_cells cells; queues and changes nothing.
 // arr[MS_N]: a finishing call's arrays for the placement plan (cpol_place.h): the caller's pointers, folded fields only
-static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_cells, int n_sets, bool doppler, MemberStatsPlan *pl,
-                             PlaceArray *arr)
+static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, const cpol_member_verify *mv, long n_cells, int n_sets, bool doppler,
+                             MemberStatsPlan *pl, PlaceArray *arr)
 {
     auto bad = [&](const char *why) { ctx->err = std::string("cpol_member_stats: ") + why; return CPOL_ERR_ARG; };
+    auto bad_v = [&](const char *why) { ctx->err = std::string("cpol_member_verify: ") + why; return CPOL_ERR_ARG; };
     const cpol_ctx::MemberPass &ps = ctx->mpass;
     if (ms->phase < 0 || ms->phase > 3) return bad("phase must lie in 0..3 (bit 0: begin, bit 1: finish)");
     if (ms->min_members < 1) return bad("min_members must be >= 1");
@@ -2046,6 +2057,13 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
             pl->q[k][t] = v;
         }
     }
+    if (mv) {
+        if (mv->fields == 0 || (mv->fields >> CPOL_MS_FIELDS) != 0) return bad_v("fields: a mask over the ten fields, at least one");
+        if (mv->fields & ~ms->fields) return bad_v("a verified field is not among the folded fields (member_stats->fields)");
+        if (mv->fair != 0 && mv->fair != 1) return bad_v("fair must be 0 or 1");
+        if (ms->quantile_capacity == 0) return bad_v("a verified field keeps its members: member_stats->quantile_capacity >= 1");
+        pl->v_on = true; pl->v_fields = mv->fields; pl->v_fair = mv->fair;
+    }
     if (!pl->begin) {
         if (!ps.open) return bad("no pass is open: the first call of a pass carries the begin bit");
         bool same = ps.n_cells == n_cells && ps.fields == ms->fields && ps.min_members == ms->min_members;
@@ -2060,9 +2078,12 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
             for (int t = 0; t < pl->n_q[k] && same; ++t) same = ps.q[k][t] == pl->q[k][t];
         }
         if (!same) return bad("quantile_capacity, quantile_method or the quantiles differ from the open pass");
+        if (pl->v_on && !ps.v_on) return bad_v("the open pass was begun without the struct");
+        if (!pl->v_on && ps.v_on) return bad_v("the open pass was begun with the struct: every call of the pass carries it");
+        if (pl->v_on && (ps.v_fields != pl->v_fields || ps.v_fair != pl->v_fair)) return bad_v("fields or fair differ from the open pass");
     }
-    if (pl->q_any && (pl->begin ? 0 : ps.folded) + n_sets > ms->quantile_capacity)
-        return bad("more members than quantile_capacity in a pass with quantiles");
+    if ((pl->q_any || pl->v_on) && (pl->begin ? 0 : ps.folded) + n_sets > ms->quantile_capacity)
+        return bad("more members than quantile_capacity in a pass with quantiles or a verification");
     if ((pl->begin ? 0 : ps.folded) + n_sets > 65535) return bad("more than 65535 members in a pass (the counts are uint16)");
     if (pl->finish) {
         bool any = false;
@@ -2078,6 +2099,14 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
         asked(MS_COUNT, ms->count, (size_t)CPOL_MS_FIELDS * n_cells * sizeof(uint16_t));
         arr[MS_COUNT].rows = CPOL_MS_FIELDS;            // (count: the rows of folded fields alone are the caller's to be written)
         arr[MS_COUNT].row_mask = ms->fields;
+        for (int k = 0; k < CPOL_MS_FIELDS && pl->v_on; ++k) {
+            if (!((pl->v_fields >> k) & 1u)) continue;
+            if (!mv->obs[k]) return bad_v("a finishing call needs the observations (obs) of every verified field");
+            if (!mv->below[k] && !mv->equal[k] && !mv->crps[k]) return bad_v("a finishing call needs an output pointer for every verified field");
+            asked(MS_BELOW + k, mv->below[k], (size_t)n_cells * sizeof(uint16_t));
+            asked(MS_EQUAL + k, mv->equal[k], (size_t)n_cells * sizeof(uint16_t));
+            asked(MS_CRPS + k, mv->crps[k], (size_t)n_cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)));
+        }
         for (int k = 0; k < MS_N; ++k) any = any || arr[k].user;
         if (!any) return bad("a finishing call needs an output pointer");
     }
@@ -2087,8 +2116,11 @@ static int member_stats_plan(cpol_ctx *ctx, const cpol_member_stats *ms, long n_
 // The pass (begun here, when the call carries the begin bit: the state block is sized and the pass's terms are noted), the fold
 // of the call's row sets and, for a finishing call, the outputs.  in: the per-gate device arrays in the order of `count`'s rows
 // (slot RVEL float64), row set m at element m * cells; T: where k_member_finish writes.
+// mv (NULL: none): the verification of a finishing call, its observations host arrays (obs_on_host: copied to b_mvobs on `st`
+// first) or arrays the device reads in place.
 static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const MemberStatsPlan &pl, const void *const in[CPOL_MS_FIELDS],
-                               void *const T[MS_N], bool zero_rest, hipStream_t st)
+                               void *const T[MS_N], bool zero_rest, hipStream_t st, const cpol_member_verify *mv = nullptr,
+                               bool obs_on_host = false)
 {
     cpol_ctx::MemberPass &ps = ctx->mpass;
     if (pl.begin) {
@@ -2099,20 +2131,21 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
             if ((ms->fields >> k) & 1u) total += a2 + 2 * a8 + 2 * (k == CPOL_MS_RVEL ? a8 : a4) + (size_t)pl.n_thr[k] * a2;
         size_t stash_total = 0;                               // the members of the fields with quantiles: [capacity][cells] each
         for (int k = 0; k < CPOL_MS_FIELDS; ++k)
-            if (pl.n_q[k] > 0) stash_total += ((size_t)ms->quantile_capacity * pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)) + 255) & ~(size_t)255;
+            if (pl.n_q[k] > 0 || ((pl.v_fields >> k) & 1u)) stash_total += ((size_t)ms->quantile_capacity * pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)) + 255) & ~(size_t)255;
         ps.open = false;                                      // (a begin that fails below leaves no pass behind)
         ENSURE(ctx->b_mstate, total);
         if (stash_total) ENSURE(ctx->b_mstash, stash_total);
         char *qs = (char *)ctx->b_mstash.p;
         for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
             ps.stash[k] = nullptr;
-            if (pl.n_q[k] == 0) continue;
+            if (pl.n_q[k] == 0 && !((pl.v_fields >> k) & 1u)) continue;
             ps.stash[k] = qs;
             qs += ((size_t)ms->quantile_capacity * pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)) + 255) & ~(size_t)255;
         }
         ps.q_capacity = ms->quantile_capacity; ps.q_method = ms->quantile_method; ps.q_any = pl.q_any;
         memcpy(ps.n_q, pl.n_q, sizeof ps.n_q);
         memcpy(ps.q, pl.q, sizeof ps.q);
+        ps.v_on = pl.v_on; ps.v_fields = pl.v_fields; ps.v_fair = pl.v_fair;
         char *q = (char *)ctx->b_mstate.p;
         for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
             ps.st[k] = MemberState{};
@@ -2175,6 +2208,39 @@ static int member_stats_launch(cpol_ctx *ctx, const cpol_member_stats *ms, const
             hipLaunchKernelGGL(k_member_quantile, dim3(cdiv(pl.cells, 64), n_qf), dim3(64), (size_t)ps.folded * 64 * key_bytes, st, qa);
             HIPCHK(hipGetLastError());
         }
+        // the verification of the fields that have one and whose output is wanted: the same column, sorted once more, read
+        // against the observation (member_stats_plan: folded <= quantile_capacity <= 128; obs is there for every verified field)
+        if (mv && ps.v_on) {
+            MemberVerifyArgs va{};
+            int n_vf = 0;
+            size_t vkey_bytes = sizeof(float), obs_total = 0;
+            const size_t a4 = ((size_t)pl.cells * sizeof(float) + 255) & ~(size_t)255, a8 = ((size_t)pl.cells * sizeof(double) + 255) & ~(size_t)255;
+            for (int k = 0; k < CPOL_MS_FIELDS; ++k) {
+                if (!((ps.v_fields >> k) & 1u) || !ps.stash[k]) continue;
+                if (!T[MS_BELOW + k] && !T[MS_EQUAL + k] && !T[MS_CRPS + k]) continue;
+                va.field[n_vf++] = k;
+                va.stash[k] = ps.stash[k];
+                va.obs[k] = mv->obs[k];
+                va.below[k] = (unsigned short *)T[MS_BELOW + k]; va.equal[k] = (unsigned short *)T[MS_EQUAL + k]; va.crps[k] = T[MS_CRPS + k];
+                if (k == CPOL_MS_RVEL) vkey_bytes = sizeof(double);
+                obs_total += k == CPOL_MS_RVEL ? a8 : a4;
+            }
+            if (n_vf > 0 && obs_on_host) {
+                ENSURE(ctx->b_mvobs, obs_total);
+                char *o = (char *)ctx->b_mvobs.p;
+                for (int j = 0; j < n_vf; ++j) {
+                    const int k = va.field[j];
+                    HIPCHK(hipMemcpyAsync(o, mv->obs[k], (size_t)pl.cells * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)), hipMemcpyHostToDevice, st));
+                    va.obs[k] = o;
+                    o += k == CPOL_MS_RVEL ? a8 : a4;
+                }
+            }
+            if (n_vf > 0) {
+                va.members = (int)ps.folded; va.fair = ps.v_fair; va.need = ps.min_members; va.n_cells = pl.cells;
+                hipLaunchKernelGGL(k_member_verify, dim3(cdiv(pl.cells, 64), n_vf), dim3(64), (size_t)ps.folded * 64 * vkey_bytes, st, va);
+                HIPCHK(hipGetLastError());
+            }
+        }
         ps.open = false;
     }
     return CPOL_OK;
@@ -2189,7 +2255,17 @@ struct MemberStatsHook {
     cpol_member_stats ms;
 };
 
-static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
+// ... and "member_verify_fields": the same with a verification beside it (host observations and outputs)
+struct MemberVerifyHook {
+    int32_t n_members;
+    int64_t n_cells;
+    const void *in[CPOL_MS_FIELDS];
+    cpol_member_stats ms;
+    cpol_member_verify mv;
+};
+static_assert(offsetof(MemberVerifyHook, ms) == offsetof(MemberStatsHook, ms), "the two hooks share their head");
+
+static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h, const cpol_member_verify *mv = nullptr)
 {
     if (h->n_members < 0 || h->n_cells < 1 || h->n_cells >= (1L << 31) || (long)h->n_members * h->n_cells >= (1L << 31)) {
         ctx->err = "member_stats_fields: bad shape";
@@ -2197,7 +2273,7 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
     }
     MemberStatsPlan pl{};
     PlaceArray arr[MS_N];
-    int rc = member_stats_plan(ctx, &h->ms, (long)h->n_cells, h->n_members, true, &pl, arr);
+    int rc = member_stats_plan(ctx, &h->ms, mv, (long)h->n_cells, h->n_members, true, &pl, arr);
     if (rc != CPOL_OK) return rc;
     for (int k = 0; k < CPOL_MS_FIELDS; ++k)
         if (((h->ms.fields >> k) & 1u) && h->n_members > 0 && !h->in[k]) { ctx->err = "member_stats_fields: a folded field has no input"; return CPOL_ERR_ARG; }
@@ -2214,7 +2290,7 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h)
     place_outputs(arr, MS_N, 0, false, &plan);
     void *T[MS_N];
     if ((rc = place_resolve(ctx, arr, MS_N, plan, nullptr, T)) != CPOL_OK) return rc;
-    if ((rc = member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream, mv, true)) != CPOL_OK) return rc;
     if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return CPOL_OK;
@@ -2401,12 +2477,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // ensemble statistics (cpol_member_stats): likewise
     const cpol_member_stats *const ms = out->member_stats;
+    const cpol_member_verify *const mv = out->member_verify;        // (the verification of the pass: with member_stats only)
     MemberStatsPlan ms_pl{};
+    if (mv && !ms) { ctx->err = "cpol_member_verify: needs ensemble statistics (outputs->member_stats) in the same call"; return CPOL_ERR_ARG; }
     if (ms) {
         if (cols || sub_out) { ctx->err = "cpol_member_stats: cpol_run_sweep and cpol_run_sweep_members take ensemble statistics, no other entry point"; return CPOL_ERR_ARG; }
         if (so) { ctx->err = "cpol_member_stats: not together with superobservations (outputs->superob) in one call"; return CPOL_ERR_ARG; }
         if (timed) { ctx->err = "cpol_member_stats: a time-blended call (tables->time_blend) folds no members"; return CPOL_ERR_ARG; }
-        const int rc_ms = member_stats_plan(ctx, ms, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_MS);
+        const int rc_ms = member_stats_plan(ctx, ms, mv, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_MS);
         if (rc_ms != CPOL_OK) return rc_ms;
     }
     // spectrum moments (cpol_spectrum_moments): likewise
@@ -3532,7 +3610,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     if (ms) {
         const void *const ms_in[CPOL_MS_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
                                                    T[O_ATTV], T[O_RVEL]};
-        if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st)) != CPOL_OK) return rc;
+        if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st, mv, p->outputs_on_device == 0)) != CPOL_OK) return rc;
     }
     // ---- spectrum moments: ONE kernel behind the sequence, on the spectrum wherever it was placed (outside launch_all too) ----
     if (sm && (rc = spec_moments_launch(ctx, sm, (const double *)T[O_SPEC], (const double *)ctx->v_varray, sm_T, n_rg, n_vb, window, st)) != CPOL_OK)
@@ -3597,6 +3675,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->member_verify) { ctx->err = "cpol_run_columns: ensemble verification (outputs->member_verify) is taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
         !c->vals || !c->elev || !c->sub_w) {
         ctx->err = "cpol_run_columns: bad shapes, or vals / elev / sub_w missing";
@@ -3893,6 +3972,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "member_stats_fields")) {     // a CONTROL name: dst points to a MemberStatsHook
         if (!dst || max_bytes < (int64_t)sizeof(MemberStatsHook)) { ctx->err = "cpol_debug_read(member_stats_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return member_stats_hook(ctx, (const MemberStatsHook *)dst);
+    }
+    if (!strcmp(name, "member_verify_fields")) {    // a CONTROL name: dst points to a MemberVerifyHook
+        if (!dst || max_bytes < (int64_t)sizeof(MemberVerifyHook)) { ctx->err = "cpol_debug_read(member_verify_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return member_stats_hook(ctx, (const MemberStatsHook *)dst, &((const MemberVerifyHook *)dst)->mv);
     }
     if (!strcmp(name, "spectrum_moments_rows")) {   // a CONTROL name: dst points to a SpecMomentsHook
         if (!dst || max_bytes < (int64_t)sizeof(SpecMomentsHook)) { ctx->err = "cpol_debug_read(spectrum_moments_rows): dst = the hook's struct"; return CPOL_ERR_ARG; }

@@ -3,6 +3,9 @@
 // that ask for them, quantiles of the members (k_member_quantile: the fold stashes the members, a finishing call sorts each
 // cell's counting members in LDS and reads the order statistics).
 //
+// k_member_verify scores the same members against an observation per cell (cpol_member_verify): the observation's rank among them
+// and the CRPS, read off the column sorted once more.
+//
 // Reference functions replaced (wolfidan/cosmo_pol): none -- the reference runs one model state per process.  The rule is the
 // one of include/cosmo_pol_amd.h and cosmo_pol_amd/ensemble_stats.py (`fold`, `finish`), ORDER-EXACT: a strict left fold over
 // the members (Welford's update: one float64 subtraction, division, addition, subtraction, multiplication, addition per
@@ -54,6 +57,18 @@ struct MemberQuantileArgs {
     int field[CPOL_MS_FIELDS];              // the fields with quantiles whose output is wanted = gridDim.y
     int members;                            // rows of the stash that hold a member (<= 128): the LDS column's height
     int method;                             // 0 linear, 1 lower, 2 higher, 3 nearest
+    int need;
+    long n_cells;
+};
+
+struct MemberVerifyArgs {
+    const void *stash[CPOL_MS_FIELDS];      // [members][n_cells] of the field's type, rows in fold order
+    const void *obs[CPOL_MS_FIELDS];        // [n_cells] of the field's type; NaN: no observation
+    unsigned short *below[CPOL_MS_FIELDS], *equal[CPOL_MS_FIELDS];      // [n_cells] or NULL
+    void *crps[CPOL_MS_FIELDS];             // [n_cells] of the field's type or NULL
+    int field[CPOL_MS_FIELDS];              // the verified fields whose output is wanted = gridDim.y
+    int members;                            // rows of the stash that hold a member (<= 128): the LDS column's height
+    int fair;                               // 1: the pair term is divided by n (n - 1)
     int need;
     long n_cells;
 };
@@ -242,4 +257,75 @@ __global__ __launch_bounds__(64) void k_member_quantile(const MemberQuantileArgs
     const int f = a.field[blockIdx.y];
     if (f == CPOL_MS_RVEL) member_quantile_field<double, unsigned long long>(a, f, c, member_q_lds + threadIdx.x);
     else member_quantile_field<float, unsigned>(a, f, c, (unsigned *)member_q_lds + threadIdx.x);
+}
+
+// ---- verification against observations ----
+// One lane per cell, the column of k_member_quantile: the lane's counting members as keys, sorted by insertion, in its own LDS
+// column col[j * 64].  One walk counts the keys below and equal to the observation's; one walk forms A = sum |x_i - y| and one
+// B = sum (2 i - n + 1) x_i over the sorted values, ascending, in float64.  crps = A / n - B / D, D = n n or n (n - 1), each
+// quotient rounded once (member_div), clamped at +0.0.  No lane reads another lane's column: no barrier.
+template <typename T, typename K>
+__device__ __forceinline__ void member_verify_field(const MemberVerifyArgs &a, int f, long c, K *__restrict__ col)
+{
+    const T *__restrict__ x = (const T *)a.stash[f];
+    int n = 0;
+    for (int m = 0; m < a.members; ++m) {
+        const T v = x[(long)m * a.n_cells + c];
+        if (v == v) {
+            const K key = member_key(v);
+            int j = n;
+            while (j > 0) {
+                const K prev = col[(j - 1) * 64];
+                if (!(key < prev)) break;
+                col[j * 64] = prev;
+                --j;
+            }
+            col[j * 64] = key;
+            ++n;
+        }
+    }
+    const T y = ((const T *)a.obs[f])[c];
+    const bool seen = y == y;
+    if (a.below[f] || a.equal[f]) {
+        unsigned below = 0, equal = 0;
+        if (seen) {
+            const K ky = member_key(y);
+            for (int i = 0; i < n; ++i) {
+                const K k = col[i * 64];
+                below += k < ky;
+                equal += k == ky;
+            }
+        }
+        if (a.below[f]) a.below[f][c] = (unsigned short)below;
+        if (a.equal[f]) a.equal[f][c] = (unsigned short)equal;
+    }
+    if (a.crps[f]) {
+        T r = (T)__builtin_nan("");
+        if (seen && n >= a.need && n > a.fair) {             // (n > 0; fair: n >= 2)
+            const double yd = (double)y;
+            double A = 0.0, B = 0.0;
+            for (int i = 0; i < n; ++i) A = A + __builtin_fabs((double)member_unkey(col[i * 64]) - yd);
+            for (int i = 0; i < n; ++i) {
+                const double p = (double)(2 * i - n + 1) * (double)member_unkey(col[i * 64]);
+                B = B + p;
+            }
+            const int D = a.fair ? n * (n - 1) : n * n;     // <= 16384
+            double s = member_div(A, (double)n) - member_div(B, (double)D);
+            if (s < 0.0) s = 0.0;
+            r = (T)s;
+        }
+        ((T *)a.crps[f])[c] = r;
+    }
+}
+
+// Grid (cells / 64, verified fields whose output is wanted); ONE wavefront per workgroup; dynamic LDS: members x 64 keys of the
+// widest field -- the shape of k_member_quantile.
+__global__ __launch_bounds__(64) void k_member_verify(const MemberVerifyArgs a)
+{
+    extern __shared__ unsigned long long member_v_lds[];
+    const long c = (long)blockIdx.x * 64 + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const int f = a.field[blockIdx.y];
+    if (f == CPOL_MS_RVEL) member_verify_field<double, unsigned long long>(a, f, c, member_v_lds + threadIdx.x);
+    else member_verify_field<float, unsigned>(a, f, c, (unsigned *)member_v_lds + threadIdx.x);
 }

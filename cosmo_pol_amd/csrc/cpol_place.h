@@ -13,7 +13,7 @@ enum { PLACE_SWEEP = 0, PLACE_SUPEROB, PLACE_STATS, PLACE_PRODUCTS };      // th
 // window; at `offset` into a buffer of the context -- the sweep's arrays each into a grow-only buffer of their own (offset 0: the
 // debug reads and the test hooks read those), the other products packed into one block per product
 enum { PLACE_NONE = 0, PLACE_IN_PLACE, PLACE_WINDOW, PLACE_OWN };
-constexpr int PLACE_MAX_ARRAYS = 96;
+constexpr int PLACE_MAX_ARRAYS = 128;
 constexpr int PLACE_MAX_COPIES = PLACE_MAX_ARRAYS + 32;
 constexpr size_t PLACE_PAD = 256;              // every array of a packed block starts at a multiple of it
 

@@ -38,7 +38,10 @@ Quantiles (EnsembleQuantiles; k_member_quantile on the device).  Per cell and pe
     The result is NaN where n < need (min_members, as for the mean).
 Because the order is total the quantiles are a symmetric function of the members: they depend neither on the order of the member
 list nor on how the pass is cut into calls (unlike the last bits of the mean).  At most 8 quantiles per field, and a pass with
-quantiles holds at most 128 members: the device keeps every member of such a field until the pass finishes."""
+quantiles holds at most 128 members: the device keeps every member of such a field until the pass finishes.
+
+Verification against observations -- the rank of an observed value among the members and the CRPS per gate -- builds on the same
+kept members: ensemble_verify.py (EnsembleVerification, a subclass of EnsembleQuantiles; k_member_verify on the device)."""
 import numpy as np
 
 # the rows of cpol_member_stats.count, in this order (= superob.FIELDS)
@@ -248,7 +251,7 @@ def quantiles(x, q, method='linear', need=1):
 
 def begin(spec, fields, shape):
     """The state of a pass that has folded nothing: {'spec', 'n_members', 'fields': {name: {'n', 'mean', 'M2', 'lo', 'hi',
-    'k'}}} for cells of `shape`; a field with quantiles also keeps its members, 'x': the rows in fold order."""
+    'k'}}} for cells of `shape`; a field with quantiles (or a verification) also keeps its members, 'x': the rows in fold order."""
     shape = tuple(shape)
     st = {}
     for k in fields:
@@ -257,7 +260,7 @@ def begin(spec, fields, shape):
         st[k] = {'n': np.zeros(shape, np.uint16), 'mean': np.zeros(shape, np.float64), 'M2': np.zeros(shape, np.float64),
                  'lo': np.full(shape, np.inf, T), 'hi': np.full(shape, -np.inf, T),
                  'k': np.zeros((len(thr),) + shape, np.uint16), 'thr': thr}
-        if k in _quantiles_of(spec):
+        if k in _quantiles_of(spec) or k in getattr(spec, 'verify', ()):      # (ensemble_verify: a verified field keeps them too)
             st[k]['x'] = np.zeros((0,) + shape, T)
     return {'spec': spec, 'n_members': 0, 'fields': st}
 

@@ -28,6 +28,7 @@ from . import geometry as geo
 from . import hydrometeors as hyd
 from . import quadrature
 from . import ensemble_stats as ES
+from . import ensemble_verify as EV
 from . import spectrum_moments as SM
 from . import superob as SO
 from .lut import load_all_lut
@@ -1249,7 +1250,9 @@ class RadarOperator(object):
             # ensemble statistics
             ms_spec, ms_phase, ms_keep = member_stats[:3]
             ms_capacity = member_stats[3] if len(member_stats) > 3 else None
+            ms_obs = member_stats[4] if len(member_stats) > 4 else None      # {field: [n_rays, n_gates]}: the finishing call's
             ms_q = getattr(ms_spec, 'quantiles', None) or {}
+            ms_v = getattr(ms_spec, 'verify', None) or ()
             if superob is not None:
                 raise ValueError('ensemble statistics and superobservations do not share a call '
                                  '(statistics of window averages are left to the host)')
@@ -1395,13 +1398,18 @@ class RadarOperator(object):
             so.min_valid_fraction = superob.min_valid_fraction
             o.superob = C.pointer(so)
             so_fields = [k for k in SO.FIELDS if k != 'RVEL' or doppler]
-        ms = ms_names = None
+        ms = ms_names = mv = o_holder = None
         if member_stats is not None:
             ms_names = ms_spec.resolve([k for k in ES.FIELDS if k != 'RVEL' or doppler])
             ms, ms_thr = N.Context.member_stats_struct(ms_spec, ms_names, ms_phase, capacity=ms_capacity)
             keep = list(keep) + ms_thr
             o.member_stats = C.pointer(ms)
+            if ms_v:                              # (fields and fair go with every call of the pass)
+                mv = N.Context.member_verify_struct(ms_spec)
+                o.member_verify = C.pointer(mv)
         ms_out = ms is not None and bool(ms_phase & 2)      # a finishing call: the statistics arrive with it
+        if ms_out and ms_v and device_outputs is None:
+            ms_obs = EV.check_observations(ms_spec, ms_names, ms_obs, (n_rays, n_gates))
         sm = None
         if moments is not None:
             if not spectrum:                      # (a GPM-type radar: no Doppler whatever the scheme says)
@@ -1416,6 +1424,12 @@ class RadarOperator(object):
                     for kind, pp in (ptr.items() if ms_out else ()):
                         if kind == 'count':
                             ms.count = pp
+                            continue
+                        if kind in ('obs',) + EV.OUTPUTS:     # the verification: observations in, ranks and CRPS out
+                            if not ms_v:
+                                raise ValueError("device_outputs['stats'][%r] without an EnsembleVerification" % (kind,))
+                            for kk, q in pp.items():
+                                getattr(mv, kind)[ES.FIELDS.index(kk)] = q
                             continue
                         if kind not in ES.KINDS + ('exceed', 'quantile'):
                             raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
@@ -1479,6 +1493,19 @@ class RadarOperator(object):
                 spec.append((('stats', 'count'), np.uint16, (len(ES.FIELDS),) + gshape))
                 spec += [(('stats', 'exceed', k), np.uint16, (len(ms_spec.exceed[k]),) + gshape) for k in ms_names if k in ms_spec.exceed]
                 spec += [(('stats', 'quantile', k), ES.dtype_of(k), (len(ms_q[k]),) + gshape) for k in ms_names if k in ms_q]
+                for k in ms_v:
+                    spec += [(('stats', 'verify', 'below', k), np.uint16, gshape), (('stats', 'verify', 'equal', k), np.uint16, gshape),
+                             (('stats', 'verify', 'crps', k), ES.dtype_of(k), gshape)]
+                if ms_v:
+                    # ... and the observations in a page-locked block of their own, which the device reads in place.  (A clean
+                    # block: no writer is named, so none whose last copy may still be in flight -- the host writes it now.)
+                    o_sizes = [-(-n_rays * n_gates * _ITEMSIZE[ES.dtype_of(k)] // 64) * 64 for k in ms_v]
+                    o_slab, o_holder = self._pool.take(sum(o_sizes))
+                    o_off = 0
+                    for k, nb in zip(ms_v, o_sizes):
+                        o_slab[o_off:o_off + n_rays * n_gates * _ITEMSIZE[ES.dtype_of(k)]].view(ES.dtype_of(k))[:] = ms_obs[k].reshape(-1)
+                        mv.obs[ES.FIELDS.index(k)] = o_slab.ctypes.data + o_off
+                        o_off += nb
             # every host output is a view of ONE block of page-locked memory from the operator's pool
             # (64-byte aligned arrays): the kernels write a device image of the block and a single
             # device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
@@ -1495,6 +1522,9 @@ class RadarOperator(object):
                     if k[1] == 'count':
                         res.setdefault('stats', {})['count'] = a
                         ms.count = base + off
+                    elif k[1] == 'verify':
+                        res.setdefault('stats', {}).setdefault('verify', {}).setdefault(k[2], {})[k[3]] = a
+                        getattr(mv, k[2])[ES.FIELDS.index(k[3])] = base + off
                     else:
                         res.setdefault('stats', {}).setdefault(k[1], {})[k[2]] = a
                         getattr(ms, k[1])[ES.FIELDS.index(k[2])] = base + off
@@ -1517,6 +1547,9 @@ class RadarOperator(object):
         else:
             ctx.run_sweep(p, t, o)
         del keep
+        if o_holder is not None:                  # (the observations' block: k_member_verify reads it until this call is done)
+            o_holder['ctx'], o_holder['serial'] = ctx, ctx.submitted
+            del o_slab
         if device_outputs is None and 'mask_sum8' in res:
             # `mask` is made from its one-byte form when it is first read (after wait(lane) for a pinned call, like every
             # other array of the result)
@@ -1696,19 +1729,57 @@ class RadarOperator(object):
         the one lane, and the bits are the same.  `pinned`: do not wait (call wait(lane)); with several calls it waits.
         `device_outputs`: {'stats': {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': device
         pointer of [10, n_rays, n_gates]}} (and, with keep_members, the per-member pointers of simulate_rays_ensemble).
+        An ensemble_verify.EnsembleVerification needs observations: simulate_rays_ensemble_verify takes it (ValueError here).
         NotImplementedError where simulate_rays_ensemble raises it: a process group, spaceborne geometry, refraction scheme 2."""
         if not isinstance(stats, ES.EnsembleStats):
             raise ValueError('stats: a cosmo_pol_amd.ensemble_stats.EnsembleStats, got %r' % (stats,))
+        if isinstance(stats, EV.EnsembleVerification):
+            raise ValueError('an EnsembleVerification needs observations: simulate_rays_ensemble_verify(azimuths, elevations, stats, '
+                             'observations, ...) takes it')
         return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, {},
                                    stats=stats, keep_members=keep_members)
 
+    def simulate_rays_ensemble_verify(self, azimuths, elevations, stats, observations=None, members=None, keep_members=False, form=None,
+                                      lane=0, pinned=False, device_outputs=None, apply_sensitivity=True):
+        """simulate_rays_ensemble_stats with a VERIFICATION of the ensemble against an observed sweep: `stats` is an
+        ensemble_verify.EnsembleVerification, `observations` {field: [n_rays, n_gates]} holds a NumPy array of the field's type for
+        every verified field (linear units, NaN = no observation), and res['stats'] gains 'verify': {'below' | 'equal': {field:
+        uint16 [n_rays, n_gates]}, 'crps': {field: [n_rays, n_gates]}} -- the rank of the observation among the members and the CRPS
+        per gate, formed on the device behind the statistics (k_member_verify; ensemble_verify states the rule, and the device
+        result carries the bits of ensemble_verify.reduce(simulate_rays_ensemble(...), observations, stats)).  At most 128 members.
+        `fields` and `fair` go with every call of the pass, the observations with the last.  The other keywords are those of
+        simulate_rays_ensemble_stats.  With `device_outputs` the observations are device pointers, device_outputs['stats']['obs'] =
+        {field: pointer} (`observations` stays None), and 'below' | 'equal' | 'crps': {field: pointer} take the scores.
+        ValueError for observations of a wrong shape or dtype, a verified field without one, more than 128 members."""
+        if not isinstance(stats, EV.EnsembleVerification):
+            raise ValueError('stats: a cosmo_pol_amd.ensemble_verify.EnsembleVerification, got %r' % (stats,))
+        dev_obs = (device_outputs or {}).get('stats', {}).get('obs')
+        if (observations is None) == (dev_obs is None):
+            raise ValueError("an EnsembleVerification needs observations (NumPy arrays), or with device_outputs the device "
+                             "pointers device_outputs['stats']['obs'], and not both")
+        if dev_obs is not None:
+            for k in stats.verify:
+                if k not in dev_obs:
+                    raise ValueError("device_outputs['stats']['obs']: no observations for the verified field %r" % (k,))
+        else:
+            if device_outputs is not None:
+                raise ValueError("with device_outputs the observations are device pointers under device_outputs['stats']['obs']")
+            n_rays = len(np.asarray(azimuths).reshape(-1))
+            observations = EV.check_observations(stats, stats.verify, observations, (n_rays, len(self.constants.RANGE_RADAR)))
+        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, {},
+                                   stats=stats, keep_members=keep_members, observations=observations)
+
     def _ensemble_rays(self, azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, so_kw,
-                       stats=None, keep_members=False):
+                       stats=None, keep_members=False, observations=None):
         superob = so_kw.get('superob')
         if stats is not None and getattr(stats, 'quantiles', None):
             # (before anything runs: the device keeps every member of a field with quantiles until the pass finishes)
             if (self.n_members if members is None else len(list(members))) > ES.MAX_QUANTILE_MEMBERS:
                 raise ValueError('ensemble quantiles: at most %d members in a pass' % ES.MAX_QUANTILE_MEMBERS)
+        if stats is not None and getattr(stats, 'verify', None):
+            # (likewise for a verified field)
+            if (self.n_members if members is None else len(list(members))) > EV.MAX_MEMBERS:
+                raise ValueError('ensemble verification: at most %d members in a pass' % EV.MAX_MEMBERS)
         members = self._members_arg(members)
         conf = self.__config
         coords = conf['radar']['coords']
@@ -1740,7 +1811,10 @@ class RadarOperator(object):
             for i, chunk in enumerate(chunks):
                 if stats is not None:
                     # the pass: begun by the first call, finished by the last, every call on this lane
-                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if i == len(chunks) - 1 else 0), keep_members, len(members)))
+                    # (the observations of a verification go with the last)
+                    last = i == len(chunks) - 1
+                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if last else 0), keep_members, len(members),
+                                               observations if last else None))
                 dev = None
                 if device_outputs is not None:
                     dev = self._offset_outputs(device_outputs, done, n_rays, len(rr))
@@ -2356,15 +2430,24 @@ class RadarOperator(object):
         return self._moments_sweeps(sweeps, moments, keep_spectrum)
 
     # ------------------------------------------------------------------ ensemble statistics scans
-    def _ensemble_stats_sweeps(self, sweeps, stats, members):
+    def _ensemble_stats_sweeps(self, sweeps, stats, members, observations=None):
         """One pinned simulate_rays_ensemble_stats per sweep over the lanes, one wait at the end: every sweep's pass stays on
-        its lane and carries the bits of its own call."""
+        its lane and carries the bits of its own call.  `observations`: one dict per sweep (an EnsembleVerification)."""
         members = self._members_arg(members)
+        if observations is None:
+            observations = [None] * len(sweeps)
+        observations = list(observations)
+        if len(observations) != len(sweeps):
+            raise ValueError('observations: one dict per sweep (%d sweeps, got %d)' % (len(sweeps), len(observations)))
         n_par = max(1, min(self.lanes, len(sweeps)))
         res, failure = [], None
         try:
             for k, (az, el) in enumerate(sweeps):
-                res.append(self.simulate_rays_ensemble_stats(az, el, stats, members=members, pinned=True, lane=k % n_par))
+                if isinstance(stats, EV.EnsembleVerification):
+                    res.append(self.simulate_rays_ensemble_verify(az, el, stats, observations[k], members=members, pinned=True,
+                                                                  lane=k % n_par))
+                else:
+                    res.append(self.simulate_rays_ensemble_stats(az, el, stats, members=members, pinned=True, lane=k % n_par))
         finally:
             for i in range(n_par):
                 try:
@@ -2381,10 +2464,28 @@ class RadarOperator(object):
         _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
         return self._ensemble_stats_sweeps(sweeps, stats, members)
 
+    def get_PPI_ensemble_verify(self, elevations, stats, observations, azimuths=None, az_step=None, az_start=0, az_stop=359,
+                                members=None):
+        """get_PPI_ensemble_stats with an ensemble_verify.EnsembleVerification: `observations` is a list with one {field:
+        [n_rays, n_gates]} per elevation, and every result is that of simulate_rays_ensemble_verify."""
+        if not isinstance(stats, EV.EnsembleVerification):
+            raise ValueError('stats: a cosmo_pol_amd.ensemble_verify.EnsembleVerification, got %r' % (stats,))
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._ensemble_stats_sweeps(sweeps, stats, members, observations)
+
     def get_RHI_ensemble_stats(self, azimuths, stats, elevations=None, elev_step=None, elev_start=0, elev_stop=90, members=None):
         """The sweeps of get_RHI reduced over the ensemble: one result per azimuth (see get_PPI_ensemble_stats)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._ensemble_stats_sweeps(sweeps, stats, members)
+
+    def get_RHI_ensemble_verify(self, azimuths, stats, observations, elevations=None, elev_step=None, elev_start=0, elev_stop=90,
+                                members=None):
+        """get_RHI_ensemble_stats with an ensemble_verify.EnsembleVerification: one dict of observations per azimuth (see
+        get_PPI_ensemble_verify)."""
+        if not isinstance(stats, EV.EnsembleVerification):
+            raise ValueError('stats: a cosmo_pol_amd.ensemble_verify.EnsembleVerification, got %r' % (stats,))
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._ensemble_stats_sweeps(sweeps, stats, members, observations)
 
     def get_VPROF(self):
         """90-degree vertical profile (the reference's version is broken as

@@ -24,12 +24,28 @@ written into the JSON.
 NOT measured: sub-beam volumes, several lanes in flight, device-resident outputs, other sets of statistics.
 
   python tools/member_stats_profile.py --out profiles/member_stats_profile.json
+
+--verify: the VERIFICATION of the ensemble against an observed sweep, M = 21, the operator's own form, in
+fresh processes that alternate:
+  V   simulate_rays_ensemble_verify(..., EnsembleVerification(verify=['ZH'], exceed=B's)), B's statistics plus the ranks and the
+      CRPS of ZH against an observed sweep (member 0's ZH times 1.3, every seventh gate without an observation);
+  B   the statistics call of above without the verification, in the same process as V;
+  A   the per-member hand-over, and separately the host part of the slow way on the members it handed over
+      (ensemble_verify.verify: A_host_ms);
+  B on this tree and B on --parent-tree DIR (a checkout of the parent commit with its library built), each measured by the
+  tree's own default mode of this tool, --repeat processes of each, alternating: the condition is that the statistics call
+  without the struct lies inside the parent's run-to-run spread.
+k_member_verify's own time comes from rocprofv3's kernel statistics of a `--verify-worker --trace` run (--kernel-stats).
+
+  python tools/member_stats_profile.py --verify --parent-tree DIR --out profiles/member_verify_profile.json
 """
 import argparse
 import csv
 import json
 import os
+import subprocess
 import sys
+import time
 
 import numpy as np
 
@@ -52,7 +68,8 @@ def result_bytes(res):
         s = res['stats']
         cells = next(iter(s['count'].values())).size
         n += 10 * cells * 2                                 # the count block: ten rows, whatever is folded
-        n += sum(a.nbytes for kind, v in s.items() if kind not in ('count', 'n_members') for a in v.values())
+        n += sum(a.nbytes for kind, v in s.items() if kind not in ('count', 'n_members', 'verify') for a in v.values())
+        n += sum(a.nbytes for v in s.get('verify', {}).values() for a in v.values())
     return int(n)
 
 
@@ -62,17 +79,149 @@ def kernel_stats(path):
     with open(path) as f:
         for row in csv.DictReader(f):
             name = row.get('Name', '')
-            for k in ('k_member_fold', 'k_member_finish', 'k_member_quantile'):
+            for k in ('k_member_fold', 'k_member_finish', 'k_member_quantile', 'k_member_verify'):
                 if name.startswith(k):
                     out[k] = {'calls': int(row['Calls']), 'avg_us': float(row['AverageNs']) / 1e3,
                               'min_us': float(row['MinNs']) / 1e3, 'max_us': float(row['MaxNs']) / 1e3}
     return out
 
 
+def verify_worker(args):
+    """One process of --verify: V, B and A on the 21-member sweep, alternating windows; one JSON line."""
+    from ensemble_profile import timed
+    from timed_profile import perturbed
+    import bench
+    from cosmo_pol_amd import RadarOperator
+    from cosmo_pol_amd import ensemble_stats as ES
+    from cosmo_pol_amd import ensemble_verify as EV
+    conf, hyds, cube, luts = bench.make_inputs('c2', small=args.small)
+    n_rays, m = 360, 21
+    az, el = np.arange(float(n_rays)), np.full(n_rays, 1.0)
+    states = [cube['data']] + [perturbed(cube['data'], 100 + i) for i in range(1, m)]
+    op = RadarOperator(config=conf, luts=luts, output_variables='only_radar', lanes=1)
+    op.load_model_ensemble(states, cube['zlevels'], cube['proj_info'], cube['resolution'])
+    exceed = {'ZH': [ES.dbz(20.0), ES.dbz(35.0)]}
+    spec, vspec = ES.EnsembleStats(exceed=exceed), EV.EnsembleVerification(verify=['ZH'], exceed=exceed)
+    ra = op.simulate_rays_ensemble(az, el)
+    y = (np.array(ra['ZH'][0]) * np.float32(1.3)).astype(np.float32)
+    y.reshape(-1)[::7] = np.nan
+    obs = {'ZH': y}
+
+    def run_v():
+        return op.simulate_rays_ensemble_verify(az, el, vspec, obs, pinned=True)
+
+    def run_b():
+        return op.simulate_rays_ensemble_stats(az, el, spec, pinned=True)
+
+    def run_a():
+        return op.simulate_rays_ensemble(az, el, pinned=True)
+    for _ in range(4):                                      # every table set, gate coordinate and stencil in place
+        ra, rb, rv = run_a(), run_b(), run_v()
+    op.wait()
+    if args.trace:
+        op.close()
+        return
+    rec = {'n_rays': n_rays, 'n_gates': int(y.shape[1]), 'members': m, 'V_ms': [], 'B_ms': [], 'A_ms': [], 'A_host_ms': [],
+           'V_bytes_handed_over': result_bytes(rv), 'V_observation_bytes_to_device': int(y.nbytes), 'B_bytes_handed_over': result_bytes(rb),
+           'A_bytes_handed_over': result_bytes(ra), 'launch_forms_V': {k: int(v) for k, v in op._ctx.launch_forms().items()},
+           'statistics_V': repr(vspec), 'statistics_B': repr(spec)}
+    members = np.array(ra['ZH'])
+    for _ in range(args.repeat):                            # the host part of the slow way, on the members A handed over
+        t0 = time.perf_counter()
+        ref = EV.verify(members, y)
+        rec['A_host_ms'].append((time.perf_counter() - t0) * 1e3)
+    got = rv['stats']['verify']
+    rec['V_equals_host_rule'] = bool(all(np.array_equal(got[k]['ZH'], ref[k], equal_nan=k == 'crps') for k in EV.OUTPUTS))
+    rec['crps_nanmean'] = float(np.nanmean(ref['crps']))
+    del ra, rb, rv, members, got, ref
+    for rep in range(args.repeat):
+        for tag, run in (('V', run_v), ('B', run_b), ('A', run_a)):
+            ms, n = timed(run, op.wait, args.window)
+            rec[tag + '_ms'].append(ms)
+            print('rep %d  %s: %.4f ms per call (%d calls)' % (rep, tag, ms, n), flush=True)
+    op.close()
+    print(json.dumps(rec))
+
+
+def last_json_line(text):
+    """the last JSON object of a process's output: the worker's one line, or the default mode's indented result"""
+    text = '\n' + text
+    at = len(text)
+    while True:
+        at = text.rindex('\n{', 0, at)
+        try:
+            return json.JSONDecoder().raw_decode(text[at + 1:])[0]
+        except ValueError:
+            continue
+
+
+def verify_driver(args):
+    """--verify: the worker and the default mode of this tree and of the parent's, in fresh processes, alternating."""
+    here = os.path.abspath(__file__)
+    common = ['--repeat', '1', '--window', str(args.window)] + (['--small'] if args.small else [])
+    plans = [('worker', [sys.executable, here, '--verify-worker'] + common, ROOT),
+             ('branch', [sys.executable, here, '--members', '21'] + common, ROOT)]
+    if args.parent_tree:
+        tree = os.path.abspath(args.parent_tree)
+        plans.append(('parent', [sys.executable, os.path.join(tree, 'tools', 'member_stats_profile.py'), '--members', '21'] + common, tree))
+    runs = {tag: [] for tag, _, _ in plans}
+    for rep in range(args.repeat):
+        for tag, cmd, cwd in plans:
+            r = subprocess.run(cmd, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.process_timeout)
+            if r.returncode != 0:
+                raise SystemExit('member_stats_profile: %s ended with %d:\n%s' % (tag, r.returncode, r.stdout[-3000:]))
+            rec = last_json_line(r.stdout)
+            runs[tag].append(rec)
+            shown = rec['V_ms'] if tag == 'worker' else rec['calls']['M21_shared']['B_ms']
+            print('rep %d  %-7s %s' % (rep, tag, ['%.4f' % v for v in shown]), flush=True)
+    w = runs['worker']
+    result = {'workload': '21 members, %d rays x %d gates, one lane, page-locked outputs' % (w[0]['n_rays'], w[0]['n_gates']),
+              'method': 'windows of at least %.2f s closed by waiting for the lane; %d fresh processes of each kind, alternating'
+                        % (args.window, args.repeat),
+              'not_measured': 'sub-beam volumes, several lanes in flight, device-resident observations and outputs, more than one '
+                              'verified field, RVEL (float64 keys), ensembles of other sizes',
+              'calls': {}}
+    for k in ('statistics_V', 'statistics_B', 'launch_forms_V', 'V_equals_host_rule', 'crps_nanmean', 'V_bytes_handed_over',
+              'V_observation_bytes_to_device', 'B_bytes_handed_over', 'A_bytes_handed_over'):
+        result[k] = w[0][k]
+    for tag in ('V', 'B', 'A', 'A_host'):
+        v = [x for r in w for x in r[tag + '_ms']]
+        result['calls'][tag] = {'ms': v, 'ms_median': float(np.median(v)), 'spread': float((max(v) - min(v)) / np.median(v))}
+    c = result['calls']
+    result['V_minus_B_ms'] = c['V']['ms_median'] - c['B']['ms_median']
+    result['V_over_A_plus_host'] = c['V']['ms_median'] / (c['A']['ms_median'] + c['A_host']['ms_median'])
+    result['bytes_A_over_V'] = result['A_bytes_handed_over'] / (result['V_bytes_handed_over'] + result['V_observation_bytes_to_device'])
+    for form in ('shared', 'per_member'):
+        b = [x for r in runs['branch'] for x in r['calls']['M21_' + form]['B_ms']]
+        c['B_default_mode_' + form] = {'ms': b, 'ms_median': float(np.median(b))}
+        if 'parent' in runs:
+            p = [x for r in runs['parent'] for x in r['calls']['M21_' + form]['B_ms']]
+            c['B_parent_' + form] = {'ms': p, 'ms_median': float(np.median(p))}
+            result['B_over_parent_' + form] = float(np.median(b) / np.median(p))
+            # inside the run-to-run spread of the two: the median of either lies inside the range the other's processes span
+            result['B_inside_spread_of_parent_' + form] = bool(min(p) <= np.median(b) <= max(p) or min(b) <= np.median(p) <= max(b))
+    if 'parent' not in runs:
+        result['not_measured'] += '; the parent commit (no --parent-tree)'
+    if args.kernel_stats:
+        result['kernels'] = kernel_stats(args.kernel_stats)
+    else:
+        result['not_measured'] += "; the kernels' own times (no --kernel-stats)"
+    line = json.dumps(result, indent=1, sort_keys=True)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+
+
 def main():
     from ensemble_profile import timed
     from timed_profile import perturbed
     ap = argparse.ArgumentParser()
+    ap.add_argument('--verify', action='store_true', help='the verification against an observed sweep, with the parent commit as the control')
+    ap.add_argument('--verify-worker', action='store_true', help='one process of --verify')
+    ap.add_argument('--parent-tree', default=None, help='a checkout of the parent commit with its library built')
+    ap.add_argument('--process-timeout', type=float, default=400.0)
     ap.add_argument('--members', default='3,21')
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--window', type=float, default=0.5)
@@ -83,9 +232,13 @@ def main():
     ap.add_argument('--kernel-stats', default=None, help="rocprofv3's kernel statistics file of a --trace run")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.verify:
+        return verify_driver(args)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('member_stats_profile: needs a GPU')
+    if args.verify_worker:
+        return verify_worker(args)
     import bench
     from cosmo_pol_amd import RadarOperator
     conf, hyds, cube, luts = bench.make_inputs('c2', small=args.small)
