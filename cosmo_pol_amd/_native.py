@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
                  'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'sz_total',
-                 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
+                 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
 SUPEROB_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL']    # the rows of `count`
@@ -139,10 +139,22 @@ class SpectrumMoments(C.Structure):
                 ('count', C.c_void_p)]
 
 
+HISTOGRAM_FIELDS = SUPEROB_FIELDS                   # the fields of a cpol_histogram: the rows of cpol_superob.count
+
+
+class Histogram(C.Structure):
+    """cpol_histogram: counts of the per-gate fields of a call over many gates (cosmo_pol_amd/histogram.py states the rule)."""
+    _fields_ = [('fields', C.c_uint32), ('phase', C.c_int32), ('ordinate', C.c_int32), ('n_y', C.c_int32),
+                ('rays_per_block', C.c_int32), ('n_x', C.c_int32 * len(HISTOGRAM_FIELDS)),
+                ('edges_x', C.c_void_p * len(HISTOGRAM_FIELDS)), ('edges_y', C.c_void_p),
+                ('counts', C.c_void_p * len(HISTOGRAM_FIELDS))]
+
+
 class Outputs(C.Structure):
-    # spectrum_moments (the last of OUTPUT_FIELDS) and member_verify (directly before mask_sum8): pointers to a struct, not
+    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8) and histogram (directly before DSPECTRUM): pointers to a struct, not
     # arrays; member_stats, superob likewise: NULL = off; superob stays the last member (cpol_outputs)
-    _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify)}.get(n, C.c_void_p))
+    _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify),
+                      'histogram': C.POINTER(Histogram)}.get(n, C.c_void_p))
                  for n in OUTPUT_FIELDS]
                 + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
@@ -880,6 +892,100 @@ class Context(object):
         del keep
         out['count'] = {k: cnt[SUPEROB_FIELDS.index(k)] for k in asked}
         return out
+
+    @staticmethod
+    def histogram_struct(spec, phase=3, rays_per_block=0, model_index=None):
+        """(Histogram for a call under `spec` (a histogram.Histogram), the arrays it points into): the edges as the caller gave
+        them (float64; the library rounds them), the counts pointers the caller's.  model_index: the row of model_vars an
+        ordinate ('model', name) stands for."""
+        from . import histogram as HG
+        h = Histogram()
+        h.fields, h.phase, h.rays_per_block = spec.mask, int(phase), int(rays_per_block)
+        keep = []
+        for k in spec.fields:
+            e = np.ascontiguousarray(spec.given[k], dtype=np.float64)
+            keep.append(e)
+            h.n_x[HISTOGRAM_FIELDS.index(k)] = len(e) - 1
+            h.edges_x[HISTOGRAM_FIELDS.index(k)] = e.ctypes.data
+        o = spec.ordinate
+        if o is not None:
+            if isinstance(o, tuple):
+                if model_index is None or int(model_index) < 0:
+                    raise ValueError('histogram: the ordinate %r needs the index of its model variable' % (o,))
+                h.ordinate = HG.ORD_MODEL + int(model_index)
+            else:
+                h.ordinate = {'heights': HG.ORD_HEIGHTS, 'dist': HG.ORD_DIST}.get(o, HG.ORD_FIELD + HISTOGRAM_FIELDS.index(o) if o in HISTOGRAM_FIELDS else -1)
+            e = np.ascontiguousarray(spec.ordinate_given, dtype=np.float64)
+            keep.append(e)
+            h.n_y, h.edges_y = len(e) - 1, e.ctypes.data
+        return h, keep
+
+    def histogram_stretch(self):
+        """The gates a workgroup of k_hist owns (cpol_debug_read "histogram_stretch")."""
+        v = C.c_int32(0)
+        n = int(self.lib.cpol_debug_read(self.h, b'histogram_stretch', C.byref(v), 4))
+        if n != 4:
+            self._check(n, 'cpol_debug_read(histogram_stretch)')
+        return int(v.value)
+
+    def histogram_fields(self, per_gate, spec, rays_per_block=0, phase=3, tamper=None):
+        """Test hook (cpol_debug_read "histogram_fields"): k_hist and the context's running state on caller-supplied rows ->
+        what histogram.count returns for them.  per_gate: {field: [..., n_gates]} (float32; RVEL float64; leading axes are
+        rows), 'heights' / 'dist' [n_rays, n_gates] (n_rays divides the rows), 'model_vars' {name: like a field, float64} --
+        whatever is given is handed over; `spec`: a histogram.Histogram.  `tamper(h)`: changes the cpol_histogram before the
+        call (the refusal tests).  A finishing call returns {field: uint64 counts}, any other None."""
+        from . import histogram as HG
+
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('n_rays', C.c_int32), ('n_model_vars', C.c_int32),
+                        ('inp', C.c_void_p * len(HISTOGRAM_FIELDS)), ('heights', C.c_void_p), ('dist', C.c_void_p),
+                        ('model_vars', C.c_void_p), ('h', Histogram)]
+        hk = Hook()
+        keep, shape = [], None
+        for i, k in enumerate(HISTOGRAM_FIELDS):
+            if k not in per_gate:
+                continue
+            a = np.ascontiguousarray(per_gate[k], dtype=HG.dtype_of(k))
+            a = a.reshape(-1, a.shape[-1])
+            if shape is not None and a.shape != shape:
+                raise ValueError('histogram_fields: every field has the same rows and gates')
+            shape = a.shape
+            keep.append(a)
+            hk.inp[i] = a.ctypes.data
+        if shape is None:
+            raise ValueError('histogram_fields: no field given')
+        hk.n_rows, hk.n_gates = shape
+        hk.n_rays = shape[0]
+        for k in ('heights', 'dist'):
+            if k in per_gate:
+                a = np.ascontiguousarray(per_gate[k], dtype=np.float32)
+                a = a.reshape(-1, a.shape[-1])
+                if a.shape[1] != shape[1] or (hk.n_rays != shape[0] and hk.n_rays != a.shape[0]):
+                    raise ValueError('histogram_fields: heights and dist are [n_rays, n_gates]')
+                hk.n_rays = a.shape[0]
+                keep.append(a)
+                setattr(hk, k, a.ctypes.data)
+        names = list(per_gate.get('model_vars', {}))
+        if names:
+            mv = np.ascontiguousarray(np.stack([np.asarray(per_gate['model_vars'][n], dtype=np.float64).reshape(shape) for n in names]))
+            keep.append(mv)
+            hk.n_model_vars, hk.model_vars = len(names), mv.ctypes.data
+        mi = names.index(spec.ordinate[1]) if isinstance(spec.ordinate, tuple) and spec.ordinate[1] in names else None
+        hk.h, ekeep = self.histogram_struct(spec, phase, rays_per_block, model_index=mi if mi is not None else 0)
+        keep += ekeep
+        nb = 1 if not int(rays_per_block) or int(rays_per_block) < 0 or shape[0] % int(rays_per_block) else shape[0] // int(rays_per_block)
+        out = {}
+        if int(phase) & 2:
+            for k in spec.fields:
+                sh = (nb, len(spec.edges[k]) + 1) if spec.ordinate is None else (nb, spec.n_y_cells, len(spec.edges[k]) + 1)
+                out[k] = np.full(sh, 0xDEADBEEF, dtype=np.uint64)
+                hk.h.counts[HISTOGRAM_FIELDS.index(k)] = out[k].ctypes.data
+        if tamper is not None:
+            keep.append(tamper(hk.h))
+        rc = int(self.lib.cpol_debug_read(self.h, b'histogram_fields', C.byref(hk), C.sizeof(hk)))
+        self._check(rc, 'cpol_debug_read(histogram_fields)')
+        del keep
+        return out if int(phase) & 2 else None
 
     @staticmethod
     def spectrum_moments_struct(spec):

@@ -27,6 +27,7 @@
 #include "cpol_tile.h"
 #include "cpol_forms.h"
 #include "cpol_place.h"
+#include "cpol_hist.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -36,6 +37,7 @@
 #include "cpol_ingest.inl"
 #include "cpol_superob.inl"
 #include "cpol_member_stats.inl"
+#include "cpol_hist.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -177,6 +179,11 @@ struct cpol_ctx {
     // when the outputs are host memory outside a window image
     DevBuf b_mstate, b_msout;
     DevBuf b_mstash;                       // ... and the members of the fields with quantiles or a verification: [capacity][n_cells] each, sized when a pass begins
+    // sweep histograms (cpol_histogram): the running state of this context's pass (the uint64 counts themselves), the rounded
+    // edges of the pass, the counts of a finishing call outside a window image and the caller's device memory; the pass (cpol_hist.h)
+    DevBuf b_hstate, b_hedges, b_hcounts[CPOL_HIST_FIELDS];
+    HistPass hpass;
+    std::vector<char> hedges_host;         // ... and what b_hedges holds (the source of its copy)
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
     struct MemberPass {
         bool open = false;
@@ -198,6 +205,7 @@ struct cpol_ctx {
         int v_fair = 0;
     } mpass;
     size_t spec_lds_allowed = 64 * 1024;   // (root context) the largest dynamic LDS asked for k_spec_gate so far (hipFuncSetAttribute)
+    size_t hist_lds_allowed[2][3] = {{64 * 1024, 64 * 1024, 64 * 1024}, {64 * 1024, 64 * 1024, 64 * 1024}};   // (root context) the same per instantiation of k_hist: [T is float64][the ordinate's type]
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
@@ -773,7 +781,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -2372,6 +2380,173 @@ static int spec_moments_hook(cpol_ctx *ctx, const SpecMomentsHook *h)
     return CPOL_OK;
 }
 
+// ---- sweep histograms (cpol_histogram, k_hist in cpol_hist.inl): the checks (cpol_hist.h), the pass and the launches, shared by
+// the launch sequence and the test hook ----
+// every refusal of a cpol_histogram for the call `c`; queues nothing and leaves the pass as it is.  arr[CPOL_HIST_FIELDS]: the
+// caller's counts for the placement plan (cpol_place.h): arrays of the sweep itself, each with a grow-only buffer of its own,
+// produced by a finishing call alone
+static int hist_plan(cpol_ctx *ctx, const cpol_histogram *h, const HistCall &c, HistPlan *pl, PlaceArray *arr)
+{
+    const char *why = nullptr;
+    try {
+        why = hist_check(h, c, ctx->hpass, pl);
+    } catch (...) {
+        ctx->err = "cpol_histogram: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    if (why) { ctx->err = std::string("cpol_histogram: ") + why; return CPOL_ERR_ARG; }
+    for (int k = 0; k < CPOL_HIST_FIELDS; ++k) {
+        arr[k] = PlaceArray{};
+        if (!pl->finish || !pl->cells[k]) continue;
+        arr[k].user = (uintptr_t)h->counts[k];
+        arr[k].bytes = (size_t)pl->n_blocks * pl->cells[k] * sizeof(uint64_t);
+        arr[k].produced = true;
+        arr[k].product = PLACE_SWEEP;
+    }
+    return CPOL_OK;
+}
+
+// in: the per-gate device arrays in the order of the fields (slot RVEL float64); y: the ordinate's device array, holding y_gates
+// gates; n_rg: the gates of the call; T: where a finishing call's counts go.  Begins, counts, finishes; then the pass is advanced
+static int hist_launch(cpol_ctx *ctx, const cpol_histogram *h, const HistPlan &pl, const void *const in[CPOL_HIST_FIELDS], const void *y,
+                       long y_gates, long n_rg, int ng, void *const T[CPOL_HIST_FIELDS], hipStream_t st)
+{
+    // the edges of the pass on the device: per requested field its abscissa's, then the ordinate's, each at a multiple of 8 bytes
+    size_t e_off[CPOL_HIST_FIELDS] = {}, e_y = 0, e_bytes = 0;
+    for (int i = 0; i < pl.n_fields; ++i) {
+        const int k = pl.field[i];
+        e_off[k] = e_bytes;
+        e_bytes += ((size_t)pl.n_ex[k] * (hist_field_type(k) == HIST_T_F64 ? 8 : 4) + 7) & ~(size_t)7;
+    }
+    e_y = e_bytes;
+    e_bytes += ((size_t)pl.n_ey * 8 + 7) & ~(size_t)7;
+    if (pl.begin) {
+        std::vector<char> &blob = ctx->hedges_host;     // (kept by the context: it outlives the copy whatever the runtime does)
+        try { blob.assign(e_bytes, 0); } catch (...) { ctx->err = "cpol_histogram: out of host memory"; return CPOL_ERR_NOMEM; }
+        const auto put = [&](size_t off, const std::vector<double> &e, int type) {
+            for (size_t j = 0; j < e.size(); ++j) {
+                if (type == HIST_T_F64) memcpy(blob.data() + off + 8 * j, &e[j], 8);
+                else { const float f = (float)e[j]; memcpy(blob.data() + off + 4 * j, &f, 4); }
+            }
+        };
+        for (int i = 0; i < pl.n_fields; ++i) put(e_off[pl.field[i]], pl.ex[pl.field[i]], hist_field_type(pl.field[i]));
+        put(e_y, pl.ey, pl.ord_type);
+        ENSURE(ctx->b_hstate, (size_t)pl.state_cells * sizeof(uint64_t));
+        ENSURE(ctx->b_hedges, e_bytes);
+        HIPCHK(hipMemsetAsync(ctx->b_hstate.p, 0, (size_t)pl.state_cells * sizeof(uint64_t), st));
+        HIPCHK(hipMemcpyAsync(ctx->b_hedges.p, blob.data(), e_bytes, hipMemcpyHostToDevice, st));
+        ctx->hpass.open = false;                  // (whatever fails from here on, no half-begun pass stays open)
+    }
+    const auto pow2_below = [](int n) { int s = 1; while (2 * s <= n) s *= 2; return n > 0 ? s : 0; };
+    const long block_gates = pl.rows_per_block * (long)ng;
+    const long stretches = cdiv(block_gates, (long)HIST_STRETCH);
+    for (int i = 0; i < pl.n_fields; ++i) {
+        const int k = pl.field[i];
+        HistArgs ha{};
+        ha.x = in[k]; ha.y = y;
+        ha.ex = (const char *)ctx->b_hedges.p + e_off[k];
+        ha.ey = (const char *)ctx->b_hedges.p + e_y;
+        ha.state = (unsigned long long *)ctx->b_hstate.p + pl.state_off[k];
+        ha.block_gates = block_gates;
+        ha.y_gates = y_gates > 0 ? y_gates : n_rg;
+        ha.n_ex = pl.n_ex[k]; ha.n_ey = pl.n_ey;
+        ha.step_x = pow2_below(pl.n_ex[k]); ha.step_y = pow2_below(pl.n_ey);
+        ha.nx2 = pl.n_ex[k] + 1;
+        ha.cells = pl.cells[k];
+        ha.stretches = (int)stretches;
+        const bool x64 = hist_field_type(k) == HIST_T_F64;
+        const size_t lds = (((size_t)pl.n_ex[k] * (x64 ? 8 : 4) + 7) & ~(size_t)7) +
+                           (pl.ord_type == HIST_T_NONE ? 0 : (((size_t)pl.n_ey * (pl.ord_type == HIST_T_F64 ? 8 : 4) + 7) & ~(size_t)7)) +
+                           (size_t)pl.cells[k] * sizeof(unsigned);
+        const void *fn = nullptr;
+        size_t &allowed = root_of(ctx)->hist_lds_allowed[x64 ? 1 : 0][pl.ord_type];
+        if (lds > allowed) {
+            // beyond the default 64 KB per workgroup: ask for it (an attribute of the kernel's instantiation; the largest
+            // request so far is kept)
+            hist_launch_field(x64, pl.ord_type, 0, 0, st, ha, &fn);
+            HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            allowed = lds;
+        }
+        const unsigned grid = (unsigned)(pl.n_blocks * stretches);
+        hist_launch_field(x64, pl.ord_type, grid, lds, st, ha, &fn);
+        HIPCHK(hipGetLastError());
+    }
+    if (pl.finish)
+        for (int i = 0; i < pl.n_fields; ++i) {
+            const int k = pl.field[i];
+            HIPCHK(hipMemcpyAsync(T[k], (const unsigned long long *)ctx->b_hstate.p + pl.state_off[k],
+                                  (size_t)pl.n_blocks * pl.cells[k] * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+        }
+    try {
+        hist_advance(h, pl, &ctx->hpass);
+    } catch (...) {
+        ctx->hpass.open = false;
+        ctx->err = "cpol_histogram: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "histogram_fields": k_hist and the running state on caller-supplied rows (host memory in, host
+// memory out, blocking) -- the kernel on rows no sweep produces (every value class, every stretch length, the largest tables).
+struct HistHook {
+    int32_t n_rows, n_gates, n_rays, n_model_vars;
+    const void *in[CPOL_HIST_FIELDS];       // [n_rows * n_gates] float32 (slot RVEL float64); NULL = not given
+    const float *heights, *dist;            // [n_rays * n_gates]
+    const double *model_vars;               // [n_model_vars][n_rows * n_gates]
+    cpol_histogram h;
+};
+
+static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
+{
+    if (hk->n_rows < 1 || hk->n_gates < 1 || (long)hk->n_rows * hk->n_gates >= (1L << 31) || hk->n_rays < 1 || hk->n_rows % hk->n_rays != 0 ||
+        hk->n_model_vars < 0 || hk->n_model_vars > CPOL_MAX_VARS) {
+        ctx->err = "histogram_fields: bad shape (n_rays divides n_rows)";
+        return CPOL_ERR_ARG;
+    }
+    HistCall c;
+    c.n_rows = hk->n_rows; c.n_gates = hk->n_gates; c.doppler = true; c.n_model_vars = hk->model_vars ? hk->n_model_vars : 0;
+    HistPlan pl;
+    PlaceArray arr[CPOL_HIST_FIELDS];
+    int rc = hist_plan(ctx, &hk->h, c, &pl, arr);
+    if (rc != CPOL_OK) return rc;
+    const int ord = hk->h.ordinate;
+    const int ord_field = (ord >= HIST_ORD_FIELD && ord < HIST_ORD_FIELD + CPOL_HIST_FIELDS) ? ord - HIST_ORD_FIELD : -1;
+    for (int k = 0; k < CPOL_HIST_FIELDS; ++k)
+        if ((pl.cells[k] || k == ord_field) && !hk->in[k]) { ctx->err = "histogram_fields: a requested field or the ordinate has no input"; return CPOL_ERR_ARG; }
+    if ((ord == HIST_ORD_HEIGHTS && !hk->heights) || (ord == HIST_ORD_DIST && !hk->dist)) { ctx->err = "histogram_fields: the ordinate has no input"; return CPOL_ERR_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)hk->n_rows * hk->n_gates, n_geo = (size_t)hk->n_rays * hk->n_gates;
+    const void *in[CPOL_HIST_FIELDS] = {};
+    for (int k = 0; k < CPOL_HIST_FIELDS; ++k) {          // (the sweeps' own output buffers hold the inputs)
+        if (!hk->in[k]) continue;
+        DevBuf &b = k == HIST_RVEL ? ctx->b_rvel : ctx->b_out[k];
+        if ((rc = upload(ctx, b, hk->in[k], n * (k == HIST_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
+        in[k] = b.p;
+    }
+    const void *y = nullptr;
+    long y_gates = (long)n;
+    if (ord == HIST_ORD_HEIGHTS || ord == HIST_ORD_DIST) {
+        DevBuf &b = ctx->b_out[ord == HIST_ORD_HEIGHTS ? 13 : 12];
+        if ((rc = upload(ctx, b, ord == HIST_ORD_HEIGHTS ? hk->heights : hk->dist, n_geo * sizeof(float))) != CPOL_OK) return rc;
+        y = b.p; y_gates = (long)n_geo;
+    } else if (ord_field >= 0) y = in[ord_field];
+    else if (ord >= HIST_ORD_MODEL) {
+        if ((rc = upload(ctx, ctx->b_model, hk->model_vars, (size_t)hk->n_model_vars * n * sizeof(double))) != CPOL_OK) return rc;
+        y = (const double *)ctx->b_model.p + (size_t)(ord - HIST_ORD_MODEL) * n;
+    }
+    PlacePlan plan;
+    place_outputs(arr, CPOL_HIST_FIELDS, 0, false, &plan);
+    DevBuf *own[CPOL_HIST_FIELDS];
+    for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[k] = &ctx->b_hcounts[k];
+    void *T[CPOL_HIST_FIELDS];
+    if ((rc = place_resolve(ctx, arr, CPOL_HIST_FIELDS, plan, own, T)) != CPOL_OK) return rc;
+    if ((rc = hist_launch(ctx, &hk->h, pl, in, y, y_gates, (long)n, hk->n_gates, T, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -2464,9 +2639,16 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
+    // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
+    static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
     PlaceArray arr[A_N];
+    // (a histogram shares a call with no other product: refused before the other product's own checks speak)
+    if (out->histogram && (out->superob || out->member_stats || out->spectrum_moments)) {
+        ctx->err = "cpol_histogram: not together with superobservations, ensemble statistics or spectrum moments in one call";
+        return CPOL_ERR_ARG;
+    }
     // superobservations (cpol_superob): every refusal here, before anything of the call is queued
     const cpol_superob *const so = out->superob;
     SuperobPlan so_pl{};
@@ -2494,6 +2676,18 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         if (so || ms) { ctx->err = "cpol_spectrum_moments: not together with superobservations or ensemble statistics in one call"; return CPOL_ERR_ARG; }
         const int rc_sm = spec_moments_plan(ctx, sm, n_rg, p->simulate_doppler == 3, arr + A_SM);
         if (rc_sm != CPOL_OK) return rc_sm;
+    }
+    // sweep histograms (cpol_histogram): likewise
+    const cpol_histogram *const hg = out->histogram;
+    HistPlan hg_pl;
+    if (hg) {
+        if (cols || sub_out) { ctx->err = "cpol_histogram: cpol_run_sweep and cpol_run_sweep_members take histograms, no other entry point"; return CPOL_ERR_ARG; }
+        HistCall hc;
+        hc.n_rows = n_rays; hc.n_gates = ng; hc.doppler = p->simulate_doppler != 0;
+        hc.n_model_vars = p->integrate_model ? n_vars : 0;
+        hc.other_product = so || ms || sm;
+        const int rc_hg = hist_plan(ctx, hg, hc, &hg_pl, arr + A_HG);
+        if (rc_hg != CPOL_OK) return rc_hg;
     }
     int rc;
 
@@ -2533,7 +2727,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     fi.site = t->site != nullptr; fi.versioned = t->version != 0; fi.with_melting = p->with_melting != 0;
     fi.exact_sub = (p->debug_flags & CPOL_DEBUG_EXACT_SUBBEAMS) != 0;
     fi.want_latlon = out->lats || out->lons; fi.want_sz_total = out->sz_total != nullptr;
-    fi.want_model = p->integrate_model && out->model_vars; fi.reuse = reuse;
+    // (a histogram over a model variable: the model variables are integrated as if they had been asked for)
+    fi.want_model = p->integrate_model && (out->model_vars || (hg && hg->ordinate >= HIST_ORD_MODEL)); fi.reuse = reuse;
     fi.outputs_on_device = p->outputs_on_device;
     fi.keep_debug = ctx->keep_debug; fi.timing = ctx->timing; fi.nz = ctx->model.nz;
     fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
@@ -2852,6 +3047,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                  out->DSPECTRUM, out->mask_sum8};
     DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
     own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
+    if (hg) for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_HG + k] = &ctx->b_hcounts[k];      // (and a finishing call's counts)
     for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
@@ -3615,6 +3811,19 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // ---- spectrum moments: ONE kernel behind the sequence, on the spectrum wherever it was placed (outside launch_all too) ----
     if (sm && (rc = spec_moments_launch(ctx, sm, (const double *)T[O_SPEC], (const double *)ctx->v_varray, sm_T, n_rg, n_vb, window, st)) != CPOL_OK)
         return rc;
+    // ---- sweep histograms: one kernel per requested field behind the sequence, into the context's running state; a finishing
+    // call's counts go where the plan placed them (outside launch_all too) ----
+    if (hg) {
+        const void *const hg_in[CPOL_HIST_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
+                                                     T[O_ATTV], T[O_RVEL]};
+        const int ord = hg->ordinate;
+        const void *y = nullptr;
+        long y_gates = n_rg;
+        if (ord == HIST_ORD_HEIGHTS || ord == HIST_ORD_DIST) { y = T[ord == HIST_ORD_HEIGHTS ? O_HGT : O_DIST]; y_gates = (long)geo_rays * ng; }
+        else if (ord >= HIST_ORD_MODEL) y = (const double *)T[O_MODEL] + (size_t)(ord - HIST_ORD_MODEL) * n_rg;
+        else if (ord >= HIST_ORD_FIELD) y = hg_in[ord - HIST_ORD_FIELD];
+        if ((rc = hist_launch(ctx, hg, hg_pl, hg_in, y, y_gates, n_rg, ng, T_all + A_HG, st)) != CPOL_OK) return rc;
+    }
     // ---- outputs that the kernels did not write in place ----
     if (window)
         HIPCHK(hipMemcpyAsync((void *)plan.win_lo, (const char *)ctx->b_outwin.p + plan.win_skew, (size_t)(plan.win_hi - plan.win_lo), hipMemcpyDeviceToHost, st));
@@ -3673,6 +3882,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
 {
     if (!ctx) return CPOL_ERR_ARG;
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->histogram) { ctx->err = "cpol_run_columns: sweep histograms (outputs->histogram) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->member_verify) { ctx->err = "cpol_run_columns: ensemble verification (outputs->member_verify) is taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
@@ -3980,6 +4190,16 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "spectrum_moments_rows")) {   // a CONTROL name: dst points to a SpecMomentsHook
         if (!dst || max_bytes < (int64_t)sizeof(SpecMomentsHook)) { ctx->err = "cpol_debug_read(spectrum_moments_rows): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return spec_moments_hook(ctx, (const SpecMomentsHook *)dst);
+    }
+    if (!strcmp(name, "histogram_fields")) {        // a CONTROL name: dst points to a HistHook
+        if (!dst || max_bytes < (int64_t)sizeof(HistHook)) { ctx->err = "cpol_debug_read(histogram_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return hist_hook(ctx, (const HistHook *)dst);
+    }
+    if (!strcmp(name, "histogram_stretch")) {
+        if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;
+        const int32_t v = HIST_STRETCH;
+        memcpy(dst, &v, sizeof v);
+        return (int64_t)sizeof v;
     }
     if (!strcmp(name, "superob_fields")) {          // a CONTROL name: dst points to a SuperobHook
         if (!dst || max_bytes < (int64_t)sizeof(SuperobHook)) { ctx->err = "cpol_debug_read(superob_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }

@@ -31,12 +31,14 @@ from . import ensemble_stats as ES
 from . import ensemble_verify as EV
 from . import spectrum_moments as SM
 from . import superob as SO
+from . import histogram as HG
 from .lut import load_all_lut
 
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
 DOPPLER_FIELDS = ['RVEL', 'DSPECTRUM']
 _DB_FIELDS = ('ZDR', 'ZV', 'ZH')
-_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2}
+_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2, np.uint64: 8}
+_PRODUCT_OUTPUTS = frozenset(('histogram', 'stats', 'moments', 'superob'))     # entries of device_outputs that are dicts of a product
 
 
 class ModelVar(object):
@@ -853,7 +855,7 @@ class RadarOperator(object):
             raise NotImplementedError('spectrum moments with a process group: the distributed scans collect no moments')
 
     def _simulate_rays(self, azimuths, elevations, device_outputs=None, apply_sensitivity=True, paths=None, lane=0, pinned=False,
-                       superob=None, keep_gates=False, rays_per_block=0, moments=None, keep_spectrum=False):
+                       superob=None, keep_gates=False, rays_per_block=0, moments=None, keep_spectrum=False, histogram=None):
         if superob is not None:
             self._superob_check(superob)
         if moments is not None:
@@ -880,7 +882,7 @@ class RadarOperator(object):
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
                               paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
-                              rays_per_block=rays_per_block, moments=moments, keep_spectrum=keep_spectrum)
+                              rays_per_block=rays_per_block, moments=moments, keep_spectrum=keep_spectrum, histogram=histogram)
 
     def stencil_state(self, lane=0):
         """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
@@ -1235,7 +1237,7 @@ class RadarOperator(object):
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
                   pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0,
-                  member_stats=None, moments=None, keep_spectrum=False):
+                  member_stats=None, moments=None, keep_spectrum=False, histogram=None):
         if self._model_staged:
             self._sync_edr()
         if superob is not None:
@@ -1258,8 +1260,16 @@ class RadarOperator(object):
                                  '(statistics of window averages are left to the host)')
             if timed is not None or subbeams is not None:
                 raise ValueError('ensemble statistics are taken by the ensemble sweeps, not by time-blended or sub-beam calls')
+        hg_spec = None
+        if histogram is not None:
+            # (spec, phase, rays_per_block, keep_gates): this call's gates counted into the lane's running histogram
+            hg_spec, hg_phase, hg_rpb, hg_keep = histogram
+            self._histogram_check(hg_spec)
+            if superob is not None or member_stats is not None or moments is not None or subbeams is not None:
+                raise ValueError('histograms do not share a call with superobservations, ensemble statistics, spectrum moments '
+                                 'or the sub-beam export')
         # the per-gate radar fields travel to the host
-        gates = (superob is None or keep_gates) and (member_stats is None or ms_keep)
+        gates = (superob is None or keep_gates) and (member_stats is None or ms_keep) and (hg_spec is None or hg_keep)
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -1284,6 +1294,15 @@ class RadarOperator(object):
                 version = 0
 
         want_model = self.output_variables in ('all', 'only_model') and members is None and gates
+        # a histogram over a model variable: the library integrates the model variables for it, asked for or not
+        hg_model = hg_spec is not None and isinstance(hg_spec.ordinate, tuple)
+        if hg_model:
+            if self.output_variables not in ('all', 'only_model') or members is not None:
+                raise ValueError("histogram: the ordinate %r needs a call that produces model_vars (output_variables 'all' or "
+                                 "'only_model', no ensemble call)" % (hg_spec.ordinate,))
+            if hg_spec.ordinate[1] not in self._staged_vars:
+                raise ValueError('histogram: no staged model variable %r' % (hg_spec.ordinate[1],))
+        integrate = want_model or hg_model
 
         def prepare(paths=paths, site=site):
             """The argument structs of cpol_run_sweep for this set of rays (and the arrays they point into)."""
@@ -1292,7 +1311,7 @@ class RadarOperator(object):
             p.n_hnodes, p.n_vnodes = len(sub.pts_hor), len(sub.pts_ver)
             p.with_melting = int(conf['microphysics']['with_melting'])
             p.with_attenuation = int(conf['microphysics']['with_attenuation'])
-            p.integrate_model = int(want_model)
+            p.integrate_model = int(integrate)
             p.outputs_on_device = 1 if device_outputs is not None else 2     # host outputs: page-locked, one copy
             # Doppler schemes 1 (analytic mean fall speed), 2 (rcs-weighted) and 3 (the full spectrum); none for GPM
             # (doppler_scatter.py:83-87)
@@ -1368,7 +1387,7 @@ class RadarOperator(object):
         # again): ~25 us of attribute traffic per call otherwise, half of what a c2 sweep takes on the device
         if version and paths is None and site is None:
             p, t, keep, doppler, spectrum, varray = self._cached(
-                ('prepared', version, n_gates, range0, mode, bool(apply_sensitivity), want_model, device_outputs is not None,
+                ('prepared', version, n_gates, range0, mode, bool(apply_sensitivity), integrate, device_outputs is not None,
                  int(self.debug_flags), self._staged_serial),
                 prepare, lru=16)
         else:
@@ -1416,8 +1435,26 @@ class RadarOperator(object):
                 raise ValueError('spectrum moments need the Doppler spectrum, and this radar simulates none')
             sm = N.Context.spectrum_moments_struct(moments)
             o.spectrum_moments = C.pointer(sm)
+        hg = None
+        if hg_spec is not None:
+            n_rows = n_rays * (len(members) if members is not None else 1)
+            HG.n_blocks(n_rows, hg_rpb)               # (ValueError: the library refuses the same)
+            hg, hg_keepalive = N.Context.histogram_struct(
+                hg_spec, hg_phase, hg_rpb, model_index=self._staged_vars.index(hg_spec.ordinate[1]) if hg_model else None)
+            keep = list(keep) + hg_keepalive
+            o.histogram = C.pointer(hg)
+        hg_out = hg is not None and bool(int(hg_phase) & 2)      # a finishing call: the counts arrive with it
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
+                if k not in _PRODUCT_OUTPUTS:     # an array of the sweep itself (one look-up, however many products there are)
+                    setattr(o, k, ptr)
+                    continue
+                if k == 'histogram':              # {field: device pointer of its uint64 counts}
+                    if hg is None:
+                        raise ValueError("device_outputs['histogram'] without a histogram")
+                    for kk, pp in (ptr.items() if hg_out else ()):
+                        hg.counts[HG.FIELDS.index(kk)] = pp
+                    continue
                 if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': pointer}
                     if ms is None:
                         raise ValueError("device_outputs['stats'] without ensemble statistics")
@@ -1449,8 +1486,6 @@ class RadarOperator(object):
                         raise ValueError("device_outputs['superob'] without superob=")
                     for kk, pp in ptr.items():
                         setattr(so, kk, pp)
-                    continue
-                setattr(o, k, ptr)
         else:
             shape = (n_rays, n_gates)
             gshape = shape                        # (gate coordinates: once, whatever the number of members)
@@ -1486,6 +1521,9 @@ class RadarOperator(object):
                 # the moments, in the same block: they ride the one copy (rows nobody asked for arrive as zeros)
                 spec.append((('moments', 'moments'), np.float64, (len(SM.FIELDS),) + shape))
                 spec.append((('moments', 'count'), np.uint16, shape))
+            if hg_out:
+                # the counts, in the same block: they ride the one copy
+                spec += [(('histogram', k), np.uint64, HG.shape(hg_spec, k, n_rows, hg_rpb)) for k in hg_spec.fields]
             if ms_out:
                 # the statistics, in the same block: they ride the one copy
                 for kind in ms_spec.kinds:
@@ -1531,6 +1569,9 @@ class RadarOperator(object):
                 elif isinstance(k, tuple) and k[0] == 'moments':
                     res.setdefault('moments', {})[k[1]] = a
                     setattr(sm, k[1], base + off)
+                elif isinstance(k, tuple) and k[0] == 'histogram':
+                    res.setdefault('histogram', {}).setdefault('counts', {})[k[1]] = a
+                    hg.counts[HG.FIELDS.index(k[1])] = base + off
                 elif isinstance(k, tuple):
                     res.setdefault('superob', {})[k[1]] = a
                     setattr(so, k[1], base + off)
@@ -1593,6 +1634,9 @@ class RadarOperator(object):
                     if pinned:
                         ctx.synchronize()
                     w.update(SO.coordinates(res, superob, so_rpb))
+        if hg_out and device_outputs is None:
+            res['histogram']['edges'] = {k: hg_spec.edges[k] for k in hg_spec.fields}
+            res['histogram']['ordinate_edges'] = hg_spec.ordinate_edges
         if sm is not None and device_outputs is None:
             w = res['moments']
             rows = w.pop('moments')
@@ -1782,11 +1826,7 @@ class RadarOperator(object):
                 raise ValueError('ensemble verification: at most %d members in a pass' % EV.MAX_MEMBERS)
         members = self._members_arg(members)
         conf = self.__config
-        coords = conf['radar']['coords']
-        if coords[2] > K.MAX_MODEL_HEIGHT:
-            raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
-        if conf['refraction']['scheme'] == 2:
-            raise NotImplementedError('ensemble calls use the 4/3-earth ray paths (refraction scheme 1)')
+        coords = self._ensemble_coords()
         from . import ensemble
         sub = self._cached('sub', lambda: quadrature.subbeams(conf))
         if form is None:
@@ -1797,9 +1837,7 @@ class RadarOperator(object):
         n_rays = len(np.asarray(azimuths).reshape(-1))
         ctx = self._lane(lane)
         if form == 'shared':
-            free, _, per_gate = ctx.mem_info()
-            budget = self.sequence_memory_budget if self.sequence_memory_budget is not None else free // 3
-            chunks = ensemble.plan_member_chunks(members, per_gate * sub.n_sub * len(rr) * n_rays, budget)
+            chunks = self._shared_member_chunks(ctx, members, sub.n_sub * len(rr) * n_rays)
         else:
             chunks = [[m] for m in members]
         if superob is not None and device_outputs is not None and len(chunks) > 1:
@@ -1855,6 +1893,24 @@ class RadarOperator(object):
                               for k, v in w0.items() if k != 'count'}
             out['superob']['count'] = {k: join([p['superob']['count'][k] for p in parts]) for k in w0['count']}
         return out
+
+    def _ensemble_coords(self):
+        """The radar's coordinates for an ensemble call; NotImplementedError for the geometries such a call does not take."""
+        conf = self.__config
+        coords = conf['radar']['coords']
+        if coords[2] > K.MAX_MODEL_HEIGHT:
+            raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
+        if conf['refraction']['scheme'] == 2:
+            raise NotImplementedError('ensemble calls use the 4/3-earth ray paths (refraction scheme 1)')
+        return coords
+
+    def _shared_member_chunks(self, ctx, members, sub_gates):
+        """The member list of a 'shared' call cut into chunks whose work buffers (cpol_mem_info's per_gate x `sub_gates`
+        sub-beam gates x members) fit `sequence_memory_budget` (None: a third of the free device memory)."""
+        from . import ensemble
+        free, _, per_gate = ctx.mem_info()
+        budget = self.sequence_memory_budget if self.sequence_memory_budget is not None else free // 3
+        return ensemble.plan_member_chunks(members, per_gate * sub_gates, budget)
 
     def _offset_outputs(self, device_outputs, n_before, n_rays, n_gates):
         """The caller's device pointers moved behind the `n_before` members already written (gate coordinates: not moved)."""
@@ -1983,10 +2039,12 @@ class RadarOperator(object):
                                       keep_gates=keep_gates, rays_per_block=rays_per_block)
 
     def _simulate_rays_at(self, azimuths, elevations, times, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False,
-                          superob=None, keep_gates=False, rays_per_block=0):
+                          superob=None, keep_gates=False, rays_per_block=0, histogram=None):
         self._timed_check()
         if superob is not None:
             self._superob_check(superob)
+        if histogram is not None:
+            self._histogram_check(histogram[0])
         from . import timeline
         az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
         el = np.asarray(elevations, dtype=np.float64).reshape(-1)
@@ -2006,6 +2064,9 @@ class RadarOperator(object):
         if len(groups) > 1 and superob is not None:
             raise ValueError('simulate_rays_at: the rays read more than %d states; superobservations need one group'
                              % N.MEMBERS_PER_CALL)
+        if len(groups) > 1 and histogram is not None:
+            raise ValueError('simulate_rays_at: the rays read more than %d states; a histogram call needs one group (cut the rays '
+                             'and fold the calls into one pass with phase=)' % N.MEMBERS_PER_CALL)
         coords = self.__config['radar']['coords']
         rr = self.constants.RANGE_RADAR
         parts = []
@@ -2015,7 +2076,7 @@ class RadarOperator(object):
             parts.append(self._run_rays(az[r0:r1], el[r0:r1], coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
                                         device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
                                         pinned=pinned and len(groups) == 1, timed=tm, superob=superob, keep_gates=keep_gates,
-                                        rays_per_block=rays_per_block))
+                                        rays_per_block=rays_per_block, histogram=histogram))
         if len(parts) == 1:
             return parts[0]
         return {k: (v if not isinstance(v, np.ndarray) else
@@ -2395,6 +2456,129 @@ class RadarOperator(object):
         """The sweeps of get_RHI as superobservations: one result per azimuth (see get_PPI_superob)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._superob_sweeps(sweeps, spec, keep_gates)
+
+    # ------------------------------------------------------------------ sweep histograms
+    # (replaces in the reference: nothing -- its users pull every per-gate array to the host and call np.histogram2d there)
+    def _histogram_check(self, hist):
+        """What a histogram call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        themselves: they take ground radars.)"""
+        if not isinstance(hist, HG.Histogram):
+            raise ValueError('hist: a cosmo_pol_amd.histogram.Histogram, got %r' % (hist,))
+        if self.distributed:
+            raise NotImplementedError('histograms with a process group: sharding rays over ranks is not built')
+        if 'RVEL' in hist.fields or hist.ordinate == 'RVEL':
+            conf = self.__config
+            if conf['doppler']['scheme'] not in (1, 2, 3) or conf['radar'].get('type') == 'GPM':
+                raise ValueError('histogram: RVEL needs a Doppler scheme')
+
+    def simulate_rays_histogram(self, azimuths, elevations, hist, keep_gates=False, phase=3, rays_per_block=0, device_outputs=None,
+                                lane=0, pinned=False):
+        """simulate_rays handing back a HISTOGRAM of its gates: `hist` is a histogram.Histogram, and a finishing call's result
+        gains res['histogram'] = {'counts': {field: uint64 [n_blocks, (n_y + 2,) n_x + 2]}, 'edges': {field: the rounded
+        edges}, 'ordinate_edges': ...} -- counted on the device behind the sweep's kernels (histogram.count states the rule,
+        and the counts are exactly its counts of the call's own per-gate arrays).  Without `keep_gates` no per-gate radar field
+        is produced for the host or copied; with it the result carries every array of simulate_rays, bit for bit.
+        `phase`: bit 0 begins the lane's pass (clears), bit 1 finishes it (the counts come back); 0 only counts -- the sweeps
+        of a volume, or a year of model states, fold into one CFAD.  `rays_per_block`: 0 one histogram of all rays, else a
+        divisor of the rays: one histogram per block of rays.  `device_outputs`: its entry 'histogram' is {field: device pointer
+        of the counts}.  (A method of its own: the keyword list of simulate_rays is pinned.)  ValueError for what the library
+        refuses; NotImplementedError with a process group and for spaceborne geometry."""
+        self._histogram_check(hist)
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                   histogram=(hist, int(phase), int(rays_per_block), keep_gates))
+
+    def simulate_rays_at_histogram(self, azimuths, elevations, times, hist, keep_gates=False, phase=3, rays_per_block=0,
+                                   device_outputs=None, lane=0, pinned=False):
+        """simulate_rays_at handing back a histogram: `hist`, `keep_gates`, `phase`, `rays_per_block` as for
+        simulate_rays_histogram (ValueError when the rays fall into several groups of states)."""
+        self._histogram_check(hist)
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                      histogram=(hist, int(phase), int(rays_per_block), keep_gates))
+
+    def simulate_rays_ensemble_histogram(self, azimuths, elevations, hist, members=None, per_member=True, keep_gates=False,
+                                         phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
+        """simulate_rays_ensemble (form 'shared') handing back histograms: with `per_member` one histogram per member, in the
+        order of `members` (the leading axis of the counts; rays_per_block = n_rays: each equals the member's own
+        simulate_rays_histogram), without it one histogram of all members' gates.  The gate coordinates come once, and an
+        ordinate 'heights' or 'dist' is every member's.  `keep_gates`: the per-member arrays of simulate_rays_ensemble come back
+        too.  `phase`: as for simulate_rays_histogram; when `sequence_memory_budget` cuts the member list into several calls,
+        per_member needs phase=3 (every chunk is a pass of its own and the blocks are joined), and the one histogram of all
+        members folds the chunks into the pass.  NotImplementedError where simulate_rays_ensemble raises it."""
+        self._histogram_check(hist)
+        members = self._members_arg(members)
+        coords = self._ensemble_coords()
+        sub = self._cached('sub', lambda: quadrature.subbeams(self.__config))
+        rr = self.constants.RANGE_RADAR
+        n_rays = len(np.asarray(azimuths).reshape(-1))
+        chunks = self._shared_member_chunks(self._lane(lane), members, sub.n_sub * len(rr) * n_rays)
+        phase = int(phase)
+        if len(chunks) > 1 and device_outputs is not None:
+            raise ValueError('simulate_rays_ensemble_histogram: device outputs need the members in one chunk')
+        if len(chunks) > 1 and per_member and phase != 3:
+            raise ValueError('simulate_rays_ensemble_histogram: per-member histograms of a member list cut into several calls '
+                             'need phase=3')
+        parts = []
+        for i, chunk in enumerate(chunks):
+            if per_member or len(chunks) == 1:
+                ph = phase
+            else:
+                ph = (phase & 1 if i == 0 else 0) | (phase & 2 if i == len(chunks) - 1 else 0)
+            parts.append(self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
+                                        device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
+                                        pinned=pinned and len(chunks) == 1, members=chunk,
+                                        histogram=(hist, ph, n_rays if per_member else 0, keep_gates)))
+        if len(parts) == 1 or device_outputs is not None:
+            return parts[-1]
+        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
+        out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts]))
+               for k in parts[0].keys() if k != 'histogram'}
+        if 'histogram' in parts[-1]:
+            out['histogram'] = dict(parts[-1]['histogram'])
+            if per_member:
+                out['histogram']['counts'] = {k: np.concatenate([q['histogram']['counts'][k] for q in parts])
+                                              for k in hist.fields}
+        return out
+
+    def _histogram_sweeps(self, sweeps, hist, per_sweep, keep_gates, rays_per_block):
+        """The sweeps of a scan counted: per sweep (one pinned call per sweep over the lanes, one wait at the end), or all
+        folded into ONE pass, which stays on lane 0 as the statistics' passes stay on theirs."""
+        self._histogram_check(hist)
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        n_par = max(1, min(self.lanes, len(sweeps))) if per_sweep else 1
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                phase = 3 if per_sweep else (1 if k == 0 else 0) | (2 if k == len(sweeps) - 1 else 0)
+                res.append(self.simulate_rays_histogram(az, el, hist, keep_gates=keep_gates, phase=phase,
+                                                        rays_per_block=rays_per_block, pinned=True, lane=k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        if per_sweep:
+            return res
+        return {'histogram': res[-1].pop('histogram'), 'sweeps': res}
+
+    def get_PPI_histogram(self, elevations, hist, azimuths=None, az_step=None, az_start=0, az_stop=359, per_sweep=False,
+                          keep_gates=False):
+        """The sweeps of get_PPI counted into a histogram.  By default ALL sweeps fold into one pass (the volume's CFAD):
+        {'histogram': as for simulate_rays_histogram, 'sweeps': [what each call returned: the per-gate arrays with
+        keep_gates]}.  With `per_sweep` a list with one simulate_rays_histogram(..., hist) result per elevation, the sweeps
+        spread over the lanes."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._histogram_sweeps(sweeps, hist, per_sweep, keep_gates, 0)
+
+    def get_RHI_histogram(self, azimuths, hist, elevations=None, elev_step=None, elev_start=0, elev_stop=90, per_sweep=False,
+                          keep_gates=False):
+        """The sweeps of get_RHI counted into a histogram: one pass over all azimuths, or one result per azimuth (see
+        get_PPI_histogram)."""
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._histogram_sweeps(sweeps, hist, per_sweep, keep_gates, 0)
 
     # ------------------------------------------------------------------ spectrum moments scans
     def _moments_sweeps(self, sweeps, moments, keep_spectrum):

@@ -458,6 +458,62 @@ typedef struct cpol_member_verify {
     void *crps[CPOL_MEMBER_STATS_FIELDS];           /* [n_cells] float32 (slot RVEL float64)                       */
 } cpol_member_verify;
 
+/* Sweep histograms: CFADs, joint counts and plain histograms of the per-gate fields of a call, counted on the device, for the
+ * user who wants a DISTRIBUTION over many gates instead of one value per gate.  Replaces in the reference: nothing (its users
+ * pull every per-gate array to the host and call np.histogram2d there).  Pointed to by cpol_outputs.histogram; honoured by
+ * cpol_run_sweep and cpol_run_sweep_members (the ensemble and the time blend).  cosmo_pol_amd/histogram.py states the same rule
+ * in NumPy (`count`).
+ * INPUT: the per-gate fields of the call as the launch sequence leaves them: after the range scans and the sensitivity cut,
+ * censored gates NaN; n_rows rows of n_gates gates (n_rows = n_rays, or n_members * n_rays in an ensemble call).
+ * FIELDS: the ten of cpol_superob.count's rows, in that order.  The type T is float32, except RVEL: float64.
+ * ABSCISSA: field k has n_x[k] >= 1 bins between n_x[k] + 1 edges.  The caller gives the edges as float64 in the field's own
+ * linear units; they are rounded once to T and must then be finite and strictly ascending.  The bin of a value v is
+ * ix = #{ j : e[j] <= v }, compared in T, in 0 ... n_x + 1: bin 0 is underflow, bin n_x + 1 overflow.  This is
+ * np.searchsorted(e_T, v, side='right'): comparisons only, no arithmetic, so the device cannot differ from NumPy.  +-inf land in
+ * the outer bins by themselves; -0.0 on an edge at +0.0 lands at or above it, as IEEE <= says.
+ * ORDINATE, optional, one per struct: code 0 none (1-D); 1 `heights` (float32); 2 `dist` (float32); 16 + k field k (its type);
+ * 32 + v row v of `model_vars` (float64; only where the call produces model_vars: a CFAD by temperature).  n_y >= 1 bins, n_y + 1
+ * edges, the same rule: iy in 0 ... n_y + 1.  In an ensemble call without time blend the geometry arrays hold n_rays rows once:
+ * row r takes the ordinate of row r mod n_rays.
+ * COUNTING: a gate counts for field k iff v == v, and with an ordinate also y == y; a counting gate adds 1 to
+ * counts[k][block][iy][ix].
+ * BLOCKS: rays_per_block = 0 gives one histogram for all rows of the call.  Otherwise it must divide n_rows, and block b holds
+ * the rows [b * rpb, (b + 1) * rpb): rpb = n_rays one histogram per member, rpb = 1 one per ray.
+ * COUNTS: uint64, [n_blocks][n_y + 2][n_x[k] + 2], or [n_blocks][n_x[k] + 2] without an ordinate.
+ * A RUNNING PASS, like cpol_member_stats.phase: bit 0 begins (clears, then counts), bit 1 finishes (counts, then writes out), 0
+ * only counts.  The state is one per context, lives on the device and holds the counts themselves.  The calls of a pass may have
+ * different n_rays, n_gates and geometry when rays_per_block == 0 (a volume's sweeps, a year of model states fold into one CFAD);
+ * with rays_per_block > 0 every call must give the same number of blocks.  The result is a sum of integers: it depends neither
+ * on how the pass is cut into calls nor on any order of addition.
+ * LIMITS (conditions, not measurements): n_x[k] + 1 and n_y + 1 at most 1024; (n_x[k] + 2) * (n_y + 2) at most 16 384 cells per
+ * field (one field's table fits 64 KiB of LDS as uint32); n_blocks * sum_k cells_k at most 2^27 (1 GiB of state).
+ * The counts pointers follow p->outputs_on_device like every other array (mode 2: they count for the one-copy window rule); they
+ * are read by a finishing call only.
+ * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: phase outside 0..3; fields zero or with a bit >= 10;
+ * RVEL, as field or ordinate, without Doppler; an unknown ordinate code; ordinate 32 + v when the call makes no model_vars, or
+ * with v >= n_vars; an ordinate set while n_y < 1 or edges_y is NULL; n_y != 0 with ordinate 0; an n_x of a requested field < 1
+ * or over the limit; a NULL edge array; an edge that is NaN or infinite; edges not strictly ascending AFTER ROUNDING TO T; any
+ * of the three limits exceeded; rays_per_block < 0 or not dividing n_rows; a counting call with no pass open and no begin bit; a
+ * call whose fields, edges, ordinate or block count differ from the open pass; a finishing call with no counts pointer for any
+ * requested field; outputs->superob, member_stats or spectrum_moments in the same call; cpol_run_columns and
+ * cpol_interp_subbeams.
+ * ONE kernel per requested field (k_hist, cpol_hist.inl) runs behind the launch sequence and before the output copy: the
+ * per-gate arrays, the launch forms, the gate stencils and a captured graph are what they are without it.  A per-gate array the
+ * caller leaves NULL is still produced on the device and is not copied.  With ordinate 32 + v the call produces model_vars as
+ * if the caller had asked for them (p->integrate_model must be set). */
+#define CPOL_HIST_FIELDS 10
+typedef struct cpol_histogram {
+    uint32_t fields;            /* bit k: field k counted                                                          */
+    int32_t  phase;             /* bit 0 begins the pass, bit 1 finishes it                                        */
+    int32_t  ordinate;          /* 0 none, 1 heights, 2 dist, 16 + k field k, 32 + v row v of model_vars           */
+    int32_t  n_y;               /* bins of the ordinate (0 without one)                                            */
+    int32_t  rays_per_block;    /* 0: one block of all rows; else divides the rows of the call                     */
+    int32_t  n_x[CPOL_HIST_FIELDS];             /* bins of field k's abscissa                                      */
+    const double *edges_x[CPOL_HIST_FIELDS];    /* [n_x[k] + 1], the field's own linear units                      */
+    const double *edges_y;                      /* [n_y + 1] or NULL                                               */
+    uint64_t *counts[CPOL_HIST_FIELDS];         /* [n_blocks][n_y + 2][n_x[k] + 2]; read by a finishing call        */
+} cpol_histogram;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -467,6 +523,8 @@ typedef struct {
     float  *dist, *heights;
     double *model_vars;         /* [n_vars][n_rays*n_gates] (integrate_model)   */
     float  *sz_total;           /* [n_rays*n_gates][12]  (debug / parity)       */
+    cpol_histogram *histogram;  /* NULL (a zero-initialised struct): off.  Counts of the radar fields above over many gates,
+                                   see cpol_histogram */
     double *DSPECTRUM;          /* [n_rays*n_gates][n_vbins]  (Doppler scheme 3) */
     cpol_member_verify *member_verify;  /* NULL (a zero-initialised struct): off.  The members of the pass of member_stats scored
                                    against observations, see cpol_member_verify */
@@ -868,6 +926,14 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * [n_rows][n_v], every row treated as a gate, `varray` [n_v], `sm` with host output pointers sized for n_rows gates; blocking;
  * needs no staged model or tables; cpol_spectrum_moments' refusals (Doppler scheme 3 counts as on), and CPOL_ERR_ARG for
  * n_rows < 1, n_v outside 1..4097 or a NULL input.  Returns 0.
+ * "histogram_fields" is the sibling of "superob_fields" for the sweep histograms: k_hist and the context's running state on
+ * caller-supplied rows.  dst points to { int32_t n_rows, n_gates, n_rays, n_model_vars; const void *in[10]; const float *heights,
+ * *dist; const double *model_vars; cpol_histogram h; } -- host arrays: `in` in the order of the fields, [n_rows * n_gates]
+ * float32 (slot RVEL float64), needed for every requested field and for a field taken as ordinate; heights and dist
+ * [n_rays * n_gates] (n_rays divides n_rows: row r takes row r mod n_rays); model_vars [n_model_vars][n_rows * n_gates]; `h` with
+ * host edge and output pointers; blocking; honours h.phase; needs no staged model or tables; cpol_histogram's refusals (Doppler
+ * counts as on), and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
+ * "histogram_stretch" copies one int32: the gates a workgroup of k_hist owns.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
