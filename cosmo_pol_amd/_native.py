@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
                  'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'sz_total',
-                 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
+                 'composite', 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
 SUPEROB_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V', 'RVEL']    # the rows of `count`
@@ -150,11 +150,23 @@ class Histogram(C.Structure):
                 ('counts', C.c_void_p * len(HISTOGRAM_FIELDS))]
 
 
+COMPOSITE_FIELDS = SUPEROB_FIELDS[:9]               # the fields of a cpol_composite: the nine float32 ones
+
+
+class Composite(C.Structure):
+    """cpol_composite: maps of the per-gate fields of a call on a radar-centred grid (cosmo_pol_amd/composite.py states the rule)."""
+    _fields_ = [('fields', C.c_uint32), ('phase', C.c_int32), ('products', C.c_uint32), ('rays_per_block', C.c_int32),
+                ('n_x', C.c_int32), ('n_y', C.c_int32), ('use_slab', C.c_int32), ('n_thresholds', C.c_int32 * len(COMPOSITE_FIELDS)),
+                ('h_lo', C.c_double), ('h_hi', C.c_double), ('thresholds', (C.c_double * 4) * len(COMPOSITE_FIELDS)),
+                ('edges_x', C.c_void_p), ('edges_y', C.c_void_p), ('ray_sin', C.c_void_p), ('ray_cos', C.c_void_p),
+                ('values', C.c_void_p * len(COMPOSITE_FIELDS)), ('count', C.c_void_p)]
+
+
 class Outputs(C.Structure):
-    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8) and histogram (directly before DSPECTRUM): pointers to a struct, not
+    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8), histogram (directly before DSPECTRUM) and composite (directly before histogram): pointers to a struct, not
     # arrays; member_stats, superob likewise: NULL = off; superob stays the last member (cpol_outputs)
     _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify),
-                      'histogram': C.POINTER(Histogram)}.get(n, C.c_void_p))
+                      'histogram': C.POINTER(Histogram), 'composite': C.POINTER(Composite)}.get(n, C.c_void_p))
                  for n in OUTPUT_FIELDS]
                 + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
@@ -986,6 +998,98 @@ class Context(object):
         self._check(rc, 'cpol_debug_read(histogram_fields)')
         del keep
         return out if int(phase) & 2 else None
+
+    @staticmethod
+    def composite_struct(spec, phase=3, rays_per_block=0, azimuths=None):
+        """(Composite for a call under `spec` (a composite.Composite), the arrays it points into): the edges, the thresholds and
+        the slab as the caller gave them (float64; the library rounds thresholds and slab), ray_sin / ray_cos of `azimuths`
+        (degrees; None leaves them NULL), the output pointers the caller's."""
+        from . import composite as CP
+        c = Composite()
+        c.fields, c.phase, c.products, c.rays_per_block = spec.mask, int(phase), spec.product_mask, int(rays_per_block)
+        c.n_x, c.n_y = spec.n_x, spec.n_y
+        keep = [spec.x_edges, spec.y_edges]
+        c.edges_x, c.edges_y = spec.x_edges.ctypes.data, spec.y_edges.ctypes.data
+        if spec.height_range is not None:
+            c.use_slab, c.h_lo, c.h_hi = 1, spec.height_range_given[0], spec.height_range_given[1]
+        for k in spec.fields:
+            i = COMPOSITE_FIELDS.index(k)
+            t = spec.thresholds_given[k]
+            c.n_thresholds[i] = len(t)
+            for j, v in enumerate(t):
+                c.thresholds[i][j] = float(v)
+        if azimuths is not None:
+            rs, rc = CP.ray_tables(azimuths)
+            rs, rc = np.ascontiguousarray(rs), np.ascontiguousarray(rc)
+            keep += [rs, rc]
+            c.ray_sin, c.ray_cos = rs.ctypes.data, rc.ctypes.data
+        return c, keep
+
+    def composite_stretch(self):
+        """The gates a workgroup of k_comp owns (cpol_debug_read "composite_stretch")."""
+        v = C.c_int32(0)
+        n = int(self.lib.cpol_debug_read(self.h, b'composite_stretch', C.byref(v), 4))
+        if n != 4:
+            self._check(n, 'cpol_debug_read(composite_stretch)')
+        return int(v.value)
+
+    def composite_fields(self, fields, dist, heights, azimuths, spec, rays_per_block=0, phase=3, lane_form=0, tamper=None):
+        """Test hook (cpol_debug_read "composite_fields"): the plan, the placement, k_comp, k_comp_finish and the context's
+        running state on caller-supplied rows -> what composite.finish returns for them.  fields: {field: float32 [..., n_gates]}
+        (leading axes are rows); dist, heights: float32 [n_rays, n_gates] (n_rays divides the rows); azimuths [n_rays] degrees;
+        `spec`: a composite.Composite; lane_form: 0 the kept form of k_comp, 1 lanes combined inside the wavefront, 2 every lane
+        on its own.  `tamper(c)`: changes the cpol_composite before the call (the refusal tests).  A finishing call returns
+        {'values': {field: {plane: array}}, 'count': {field: array}}, any other None."""
+        from . import composite as CP
+
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('n_rays', C.c_int32), ('lane_form', C.c_int32),
+                        ('inp', C.c_void_p * len(COMPOSITE_FIELDS)), ('heights', C.c_void_p), ('dist', C.c_void_p),
+                        ('c', Composite)]
+        hk = Hook()
+        keep, shape = [], None
+        for i, k in enumerate(COMPOSITE_FIELDS):
+            if k not in fields:
+                continue
+            a = np.ascontiguousarray(fields[k], dtype=np.float32)
+            a = a.reshape(-1, a.shape[-1])
+            if shape is not None and a.shape != shape:
+                raise ValueError('composite_fields: every field has the same rows and gates')
+            shape = a.shape
+            keep.append(a)
+            hk.inp[i] = a.ctypes.data
+        if shape is None:
+            raise ValueError('composite_fields: no field given')
+        hk.n_rows, hk.n_gates = shape
+        geo = []
+        for a in (dist, heights):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            a = a.reshape(-1, a.shape[-1])
+            if a.shape[1] != shape[1] or shape[0] % a.shape[0] or (geo and geo[0].shape != a.shape):
+                raise ValueError('composite_fields: heights and dist are [n_rays, n_gates], n_rays dividing the rows')
+            geo.append(a)
+        keep += geo
+        hk.n_rays, hk.dist, hk.heights, hk.lane_form = geo[0].shape[0], geo[0].ctypes.data, geo[1].ctypes.data, int(lane_form)
+        hk.c, ckeep = self.composite_struct(spec, phase, rays_per_block, azimuths=azimuths)
+        keep += ckeep
+        rpb = int(rays_per_block)
+        nb = 1 if rpb <= 0 or shape[0] % rpb else shape[0] // rpb
+        vals, cnt = {}, None
+        if int(phase) & 2:
+            for k in spec.fields:
+                vals[k] = np.full((nb, len(spec.planes(k)), spec.n_y, spec.n_x), -7.0, dtype=np.float32)
+                hk.c.values[COMPOSITE_FIELDS.index(k)] = vals[k].ctypes.data
+            cnt = np.full((nb, len(spec.fields), spec.n_y, spec.n_x), 0xDEADBEEF, dtype=np.uint64)
+            hk.c.count = cnt.ctypes.data
+        if tamper is not None:
+            keep.append(tamper(hk.c))
+        rc = int(self.lib.cpol_debug_read(self.h, b'composite_fields', C.byref(hk), C.sizeof(hk)))
+        self._check(rc, 'cpol_debug_read(composite_fields)')
+        del keep
+        if not int(phase) & 2:
+            return None
+        return {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
+                'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
 
     @staticmethod
     def spectrum_moments_struct(spec):

@@ -1,0 +1,339 @@
+"""Gridded composites (cpol_composite): the column maximum, the lowest gate and echo-top heights of the per-gate fields of a
+call on a radar-centred map, reduced on the device.  This module states the rule in NumPy (`compose`, `finish`);
+include/cosmo_pol_amd.h states the same text, and the GPU tests compare the kernels (cosmo_pol_amd/csrc/cpol_comp.inl) with it
+exactly: every result is a maximum, a minimum or a count of integers.
+
+THE RULE
+  Input      the per-gate fields of the call as the launch sequence leaves them: after the range scans and the sensitivity
+             cut, censored gates NaN; n_rows rows of n_gates gates (n_rows = n_rays, or n_members * n_rays in an ensemble
+             call).  With them `dist` (float32, ground distance of the central sub-beam) and `heights` (float32) of the same
+             call, and per ray two float64 numbers ray_sin[r], ray_cos[r] given by the caller: np.sin(np.deg2rad(az)),
+             np.cos(np.deg2rad(az)) (`ray_tables`).  The library computes no trigonometric function for this product.
+             Geometry arrays that hold n_rays rows once are read at g mod (n_rays * n_gates), the per-ray pair at row mod n_rays.
+  Plane      radar-centred, east x and north y: x = float64(dist) * ray_sin, y = float64(dist) * ray_cos, one float64
+             multiplication each.
+  Grid       n_x + 1 and n_y + 1 float64 edges, finite and strictly ascending, at most MAX_EDGES per axis.
+             ix = #{ j : ex[j] <= x } - 1 = np.searchsorted(ex, x, side='right') - 1, likewise iy: comparisons alone.  The gate
+             lies in the grid iff 0 <= ix < n_x and 0 <= iy < n_y; there are no under- or overflow cells (a gate on the last
+             edge is outside), and a gate outside the grid does not count.
+  Slab       optional, [h_lo, h_hi): both bounds rounded once to float32, the test h_lo <= h and h < h_hi in float32.  Without a
+             slab every height counts.
+  Fields     the nine float32 fields of FIELDS, bit k as in histogram.FIELDS.  RVEL is float64 and is refused.
+  Counting   a gate counts for field k iff v == v, dist == dist, h == h, it lies in the grid and it lies in the slab.
+  Key        of a float32 with bits b: key = b ^ (0xFFFFFFFF if b >> 31 else 0x80000000), a total order
+             -inf < ... < -0.0 < +0.0 < ... < +inf.  Keys 0 and 0xFFFFFFFF belong to NaN bit patterns: no counting value
+             produces them, and they mark an empty cell.
+  Products   per requested field, the same for all fields of a spec:
+             'max'       planes max, height_of_max: one uint64 per cell, the MAXIMUM of key(v) << 32 | key(h) over the
+                         counting gates; ties in the value go to the greater height.
+             'lowest'    planes lowest, height_of_lowest: one uint64 per cell, the MINIMUM of key(h) << 32 | key(v); ties in
+                         the height go to the smaller value.
+             'echo_top'  planes echo_top_0 ...: 1 to MAX_THRESHOLDS thresholds per field in the field's own linear units, each
+                         rounded once to float32; per plane one uint32 per cell, the maximum of key(h) over the counting gates
+                         with v >= t.
+             count       always: uint64 per cell and field, the number of counting gates.
+  Blocks     rays_per_block = 0: one map of all rows of the call.  Otherwise it must divide n_rows, and block b holds the rows
+             [b * rpb, (b + 1) * rpb): rpb = n_rays one map per member.
+  A pass     a begin sets the max states to 0, the min states to all ones and the counts to 0.  With rays_per_block == 0 the
+             calls of a pass may differ in n_rays, n_gates and geometry: the sweeps of a volume fold into one composite.  The
+             result depends neither on how the pass is cut into calls nor on any order.
+  Outputs    per requested field float32 [n_blocks][n_planes][n_y][n_x], the planes in the order max, height_of_max, lowest,
+             height_of_lowest, echo_top_0 ..., planes not requested absent, empty cells NaN; count uint64
+             [n_blocks][n_requested_fields][n_y][n_x], the fields ascending.
+  Limits     at most MAX_EDGES edges per axis; the state of all blocks and fields at most MAX_STATE_BYTES; fewer than 2^31
+             workgroups."""
+import numpy as np
+
+FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V')
+PRODUCTS = ('max', 'lowest', 'echo_top')             # bit 0, 1, 2 of cpol_composite.products
+MAX_EDGES = 1024                 # n + 1 of either axis
+MAX_THRESHOLDS = 4               # echo-top planes of one field
+MAX_STATE_BYTES = 1 << 30        # the state of all blocks and fields
+STRETCH = 1024                   # gates per workgroup of k_comp (COMP_STRETCH in cpol_comp.h; checked against the library)
+
+_U32, _U64 = np.uint32, np.uint64
+_LOW_EMPTY = _U64(0xFFFFFFFFFFFFFFFF)
+
+
+def key32(a):
+    """The ordered key (uint32) of float32 values."""
+    b = np.ascontiguousarray(a, dtype=np.float32).view(_U32)
+    return b ^ np.where(b >> _U32(31), _U32(0xFFFFFFFF), _U32(0x80000000)).astype(_U32)
+
+
+def unkey32(k):
+    """The float32 values of ordered keys: the inverse of key32."""
+    k = np.ascontiguousarray(k, dtype=_U32)
+    return (k ^ np.where(k >> _U32(31), _U32(0x80000000), _U32(0xFFFFFFFF)).astype(_U32)).view(np.float32)
+
+
+def _edges(e, what):
+    a = np.array(e, dtype=np.float64)
+    if a.ndim != 1 or a.size < 2:
+        raise ValueError('%s: at least two edges in a 1-D sequence' % what)
+    if a.size > MAX_EDGES:
+        raise ValueError('%s: at most %d edges' % (what, MAX_EDGES))
+    if not np.all(np.isfinite(a)):
+        raise ValueError('%s: an edge is NaN or infinite' % what)
+    if not np.all(a[1:] > a[:-1]):
+        raise ValueError('%s: the edges are not strictly ascending' % what)
+    return a
+
+
+def _f32(v):
+    with np.errstate(over='ignore'):
+        return np.float32(v)
+
+
+class Composite(object):
+    """What a composite call reduces: `fields` (names out of FIELDS), the float64 `x_edges` (east) and `y_edges` (north) of the
+    radar-centred grid in metres (`grid` makes a uniform one), `products` out of PRODUCTS, `thresholds` for 'echo_top' ({field:
+    1 ... 4 thresholds in the field's own linear units}, or one sequence for every field; `from_db` makes them from dBZ) and the
+    optional `height_range` (h_lo, h_hi): only gates with h_lo <= height < h_hi count.  A slab around a nominal height with
+    'max' alone is a pseudo-CAPPI.  ValueError for what the library refuses."""
+
+    def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None):
+        if isinstance(fields, str):
+            fields = (fields,)
+        fields = tuple(fields)
+        if not fields:
+            raise ValueError('fields: at least one of %s' % ', '.join(FIELDS))
+        for k in fields:
+            if k == 'RVEL':
+                raise ValueError('RVEL is float64 and is not composed')
+            if k not in FIELDS:
+                raise ValueError('unknown field %r (one of %s)' % (k, ', '.join(FIELDS)))
+        self.fields = tuple(k for k in FIELDS if k in fields)
+        self.x_edges = _edges(x_edges, 'x_edges')
+        self.y_edges = _edges(y_edges, 'y_edges')
+        if isinstance(products, str):
+            products = (products,)
+        products = tuple(products)
+        if not products:
+            raise ValueError('products: at least one of %s' % ', '.join(PRODUCTS))
+        for q in products:
+            if q not in PRODUCTS:
+                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS)))
+        self.products = tuple(q for q in PRODUCTS if q in products)
+        self.thresholds = {k: np.zeros(0, dtype=np.float32) for k in self.fields}
+        self.thresholds_given = {k: np.zeros(0, dtype=np.float64) for k in self.fields}
+        if 'echo_top' in self.products:
+            if thresholds is None:
+                raise ValueError("'echo_top' needs thresholds")
+            if not isinstance(thresholds, dict):
+                thresholds = {k: thresholds for k in self.fields}
+            for k in thresholds:
+                if k not in self.fields:
+                    raise ValueError('thresholds of %r, which is not a field of the composite' % (k,))
+            for k in self.fields:
+                t = np.array(thresholds.get(k, ()), dtype=np.float64).reshape(-1)
+                if not 1 <= t.size <= MAX_THRESHOLDS:
+                    raise ValueError("'echo_top' needs 1 ... %d thresholds for %s" % (MAX_THRESHOLDS, k))
+                if np.any(np.isnan(t)):
+                    raise ValueError('a threshold of %s is NaN' % k)
+                self.thresholds_given[k] = t
+                with np.errstate(over='ignore'):
+                    self.thresholds[k] = t.astype(np.float32)
+        elif thresholds is not None:
+            raise ValueError("thresholds without 'echo_top'")
+        self.height_range = None
+        if height_range is not None:
+            lo, hi = height_range
+            lo, hi = _f32(lo), _f32(hi)
+            if not lo < hi:
+                raise ValueError('height_range: h_lo < h_hi after rounding to float32, got %r' % (height_range,))
+            self.height_range = (lo, hi)
+            self.height_range_given = (float(height_range[0]), float(height_range[1]))
+
+    @property
+    def n_x(self):
+        return len(self.x_edges) - 1
+
+    @property
+    def n_y(self):
+        return len(self.y_edges) - 1
+
+    @property
+    def mask(self):
+        """cpol_composite.fields."""
+        return sum(1 << FIELDS.index(k) for k in self.fields)
+
+    @property
+    def product_mask(self):
+        """cpol_composite.products."""
+        return sum(1 << PRODUCTS.index(q) for q in self.products)
+
+    def planes(self, field):
+        """The names of the planes of values[field], in their order."""
+        if field not in self.fields:
+            raise ValueError('%r is not a field of the composite' % (field,))
+        out = []
+        if 'max' in self.products:
+            out += ['max', 'height_of_max']
+        if 'lowest' in self.products:
+            out += ['lowest', 'height_of_lowest']
+        return out + ['echo_top_%d' % j for j in range(len(self.thresholds[field]))]
+
+    @property
+    def key(self):
+        return (self.fields, self.products, self.x_edges.tobytes(), self.y_edges.tobytes(),
+                tuple(self.thresholds[k].tobytes() for k in self.fields),
+                None if self.height_range is None else (self.height_range[0].tobytes(), self.height_range[1].tobytes()))
+
+    def __eq__(self, other):
+        return isinstance(other, Composite) and self.key == other.key
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        s = 'Composite(%s, %d x %d cells, products=%s' % ('+'.join(self.fields), self.n_x, self.n_y, '+'.join(self.products))
+        if 'echo_top' in self.products:
+            s += ', thresholds={%s}' % ', '.join('%s: %s' % (k, [float(t) for t in self.thresholds[k]]) for k in self.fields)
+        if self.height_range is not None:
+            s += ', height_range=[%g, %g)' % self.height_range
+        return s + ')'
+
+
+def grid(half_width, cell):
+    """The edges of a uniform axis from -half_width to +half_width (metres) in cells of `cell`: -half_width + cell * j for
+    j = 0 ... n with n = round(2 * half_width / cell).  The same array serves east and north."""
+    half_width, cell = float(half_width), float(cell)
+    if not (cell > 0.0 and half_width > 0.0 and np.isfinite(half_width)):
+        raise ValueError('grid: half_width > 0 and cell > 0')
+    n = int(round(2.0 * half_width / cell))
+    if n < 1 or n + 1 > MAX_EDGES:
+        raise ValueError('grid: %d cells; 1 ... %d' % (n, MAX_EDGES - 1))
+    return -half_width + cell * np.arange(n + 1, dtype=np.float64)
+
+
+def from_db(t):
+    """dBZ thresholds as linear ones, 10 ** (t / 10): the fields are linear, and the device takes no logarithm."""
+    return 10.0 ** (np.asarray(t, dtype=np.float64) / 10.0)
+
+
+def centers(edges):
+    """The midpoints of the cells between `edges`."""
+    e = np.asarray(edges, dtype=np.float64)
+    return 0.5 * (e[1:] + e[:-1])
+
+
+def n_blocks(n_rows, rays_per_block=0):
+    rpb = int(rays_per_block)
+    if rpb < 0 or (rpb and n_rows % rpb):
+        raise ValueError('rays_per_block %r does not divide the %d rows of the call' % (rays_per_block, n_rows))
+    return n_rows // rpb if rpb else 1
+
+
+def shape(spec, field, n_rows=1, rays_per_block=0):
+    """The shape of values[field] for a call of n_rows rows."""
+    return (n_blocks(n_rows, rays_per_block), len(spec.planes(field)), spec.n_y, spec.n_x)
+
+
+def count_shape(spec, n_rows=1, rays_per_block=0):
+    """The shape of the count array."""
+    return (n_blocks(n_rows, rays_per_block), len(spec.fields), spec.n_y, spec.n_x)
+
+
+def state_bytes(spec, blocks):
+    """The bytes of the running state of `blocks` blocks (cpol_comp.h: the echo-top states of a field padded to 8 bytes)."""
+    per = int(blocks) * spec.n_x * spec.n_y
+    total = 0
+    for k in spec.fields:
+        total += per * 8 * (1 + ('max' in spec.products) + ('lowest' in spec.products))
+        total += (per * 4 * len(spec.thresholds[k]) + 7) & ~7
+    return total
+
+
+def ray_tables(azimuths):
+    """(ray_sin, ray_cos) of azimuths in degrees, float64: what the library is given."""
+    az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
+    return np.sin(np.deg2rad(az)), np.cos(np.deg2rad(az))
+
+
+def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0):
+    """The rule in NumPy: one call folded into a running state.  fields: {name: float32 [..., n_gates]} for the fields of
+    `spec` (leading axes are flattened to rows); dist, heights: float32 [n_rays, n_gates] with n_rays dividing the rows (row r
+    takes row r mod n_rays); azimuths: [n_rays] degrees.  `state` (what a former call returned) continues a pass, None begins
+    one.  Returns the state; `finish` decodes it."""
+    dist = np.asarray(dist)
+    heights = np.asarray(heights)
+    if dist.dtype != np.float32 or heights.dtype != np.float32:
+        raise ValueError('compose: dist and heights must be float32')
+    ng = dist.shape[-1]
+    dist, heights = dist.reshape(-1, ng), heights.reshape(-1, ng)
+    n_rays = dist.shape[0]
+    rs, rc = ray_tables(azimuths)
+    if heights.shape != dist.shape or len(rs) != n_rays:
+        raise ValueError('compose: dist and heights are [n_rays, n_gates], azimuths [n_rays]')
+    x = dist.astype(np.float64) * rs[:, None]
+    y = dist.astype(np.float64) * rc[:, None]
+    ix = np.searchsorted(spec.x_edges, x, side='right') - 1
+    iy = np.searchsorted(spec.y_edges, y, side='right') - 1
+    geo = (dist == dist) & (heights == heights) & (ix >= 0) & (ix < spec.n_x) & (iy >= 0) & (iy < spec.n_y)
+    if spec.height_range is not None:
+        geo &= (spec.height_range[0] <= heights) & (heights < spec.height_range[1])
+    cell = np.where(geo, iy * spec.n_x + ix, 0)
+    kh = key32(heights)
+    cells = spec.n_x * spec.n_y
+    nb = None
+    for k in spec.fields:
+        v = np.asarray(fields[k])
+        if v.dtype != np.float32:
+            raise ValueError('compose: %s must be float32' % k)
+        if v.shape[-1] != ng:
+            raise ValueError('compose: %s has %d gates, dist %d' % (k, v.shape[-1], ng))
+        v = v.reshape(-1, ng)
+        rows = v.shape[0]
+        if rows % n_rays:
+            raise ValueError('compose: %s has %d rows, the geometry %d' % (k, rows, n_rays))
+        if nb is None:
+            nb = n_blocks(rows, rays_per_block)
+            if state is None:
+                state = {'spec': spec, 'n_blocks': nb, 'fields': {
+                    q: {'max': np.zeros(nb * cells, dtype=_U64), 'lowest': np.full(nb * cells, _LOW_EMPTY, dtype=_U64),
+                        'top': np.zeros((len(spec.thresholds[q]), nb * cells), dtype=_U32),
+                        'count': np.zeros(nb * cells, dtype=_U64)} for q in spec.fields}}
+            if state['spec'] != spec or state['n_blocks'] != nb:
+                raise ValueError('compose: the spec or the block count differ from the state')
+        sel = np.arange(rows) % n_rays
+        ok = (v == v) & geo[sel]
+        where = (cell[sel] + (np.arange(rows) // (rows // nb))[:, None] * cells)[ok]
+        kv = key32(v)[ok].astype(_U64)
+        kh_k = kh[sel][ok]
+        st = state['fields'][k]
+        np.add.at(st['count'], where, _U64(1))
+        if 'max' in spec.products:
+            np.maximum.at(st['max'], where, (kv << _U64(32)) | kh_k.astype(_U64))
+        if 'lowest' in spec.products:
+            np.minimum.at(st['lowest'], where, (kh_k.astype(_U64) << _U64(32)) | kv)
+        vv = v[ok]
+        for j, t in enumerate(spec.thresholds[k]):
+            above = vv >= t
+            np.maximum.at(st['top'][j], where[above], kh_k[above])
+    return state
+
+
+def finish(state):
+    """The state of a pass decoded: {'values': {field: {plane: float32 [n_blocks, n_y, n_x]}}, 'count': {field: uint64
+    [n_blocks, n_y, n_x]}}; empty cells NaN."""
+    spec, nb = state['spec'], state['n_blocks']
+    sh = (nb, spec.n_y, spec.n_x)
+    nan = np.float32(np.nan)
+    out = {'values': {}, 'count': {}}
+    for k in spec.fields:
+        st = state['fields'][k]
+        planes = {}
+        if 'max' in spec.products:
+            s = st['max']
+            planes['max'] = np.where(s == 0, nan, unkey32((s >> _U64(32)).astype(_U32))).reshape(sh)
+            planes['height_of_max'] = np.where(s == 0, nan, unkey32((s & _U64(0xFFFFFFFF)).astype(_U32))).reshape(sh)
+        if 'lowest' in spec.products:
+            s = st['lowest']
+            planes['lowest'] = np.where(s == _LOW_EMPTY, nan, unkey32((s & _U64(0xFFFFFFFF)).astype(_U32))).reshape(sh)
+            planes['height_of_lowest'] = np.where(s == _LOW_EMPTY, nan, unkey32((s >> _U64(32)).astype(_U32))).reshape(sh)
+        for j in range(len(spec.thresholds[k])):
+            planes['echo_top_%d' % j] = np.where(st['top'][j] == 0, nan, unkey32(st['top'][j])).reshape(sh)
+        out['values'][k] = planes
+        out['count'][k] = st['count'].reshape(sh).copy()
+    return out

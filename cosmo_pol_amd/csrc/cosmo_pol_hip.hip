@@ -28,6 +28,7 @@
 #include "cpol_forms.h"
 #include "cpol_place.h"
 #include "cpol_hist.h"
+#include "cpol_comp.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -38,6 +39,7 @@
 #include "cpol_superob.inl"
 #include "cpol_member_stats.inl"
 #include "cpol_hist.inl"
+#include "cpol_comp.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -184,6 +186,13 @@ struct cpol_ctx {
     DevBuf b_hstate, b_hedges, b_hcounts[CPOL_HIST_FIELDS];
     HistPass hpass;
     std::vector<char> hedges_host;         // ... and what b_hedges holds (the source of its copy)
+    // gridded composites (cpol_composite): the running state of this context's pass (max, min, echo-top and count states), the
+    // edges of the pass, the per-ray sines and cosines of the call, the maps of a finishing call outside a window image and the
+    // caller's device memory (nine `values`, then `count`); the pass (cpol_comp.h)
+    DevBuf b_cstate, b_cedges, b_crays, b_cout[CPOL_COMP_FIELDS + 1];
+    CompPass cpass;
+    CompPlan cplan;                        // ... and the plan of the call at hand (kept here: a call without the struct constructs none)
+    std::vector<double> cedges_host;       // ... and what b_cedges holds (the source of its copy)
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
     struct MemberPass {
         bool open = false;
@@ -781,7 +790,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -2547,6 +2556,170 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
     return CPOL_OK;
 }
 
+// ---- gridded composites (cpol_composite, k_comp and k_comp_finish in cpol_comp.inl): the checks (cpol_comp.h), the pass and the
+// launches, shared by the launch sequence and the test hook ----
+#ifndef CPOL_COMP_COMBINE
+#define CPOL_COMP_COMBINE 1        // the kept lane form of k_comp: 1 lanes that share a cell combined inside the wavefront, 0 every lane on its own
+#endif
+enum { CP_COUNT = CPOL_COMP_FIELDS, CP_N };
+// every refusal of a cpol_composite for the call `c`; queues nothing and leaves the pass as it is.  arr[CP_N]: the caller's nine
+// `values` and `count` for the placement plan (cpol_place.h): arrays of the sweep itself, each with a grow-only buffer of its
+// own, produced by a finishing call alone
+static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &call, CompPlan *pl, PlaceArray *arr)
+{
+    const char *why = nullptr;
+    try {
+        why = comp_check(c, call, ctx->cpass, pl);
+    } catch (...) {
+        ctx->err = "cpol_composite: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    if (why) { ctx->err = std::string("cpol_composite: ") + why; return CPOL_ERR_ARG; }
+    for (int k = 0; k < CP_N; ++k) arr[k] = PlaceArray{};
+    if (!pl->finish) return CPOL_OK;
+    for (int i = 0; i < pl->n_fields; ++i) {
+        const int k = pl->field[i];
+        arr[k].user = (uintptr_t)c->values[k];
+        arr[k].bytes = (size_t)pl->n_blocks * pl->n_planes[k] * pl->cells * sizeof(float);
+        arr[k].produced = true;
+        arr[k].product = PLACE_SWEEP;
+    }
+    arr[CP_COUNT].user = (uintptr_t)c->count;
+    arr[CP_COUNT].bytes = (size_t)pl->n_blocks * pl->n_fields * pl->cells * sizeof(uint64_t);
+    arr[CP_COUNT].produced = true;
+    arr[CP_COUNT].product = PLACE_SWEEP;
+    return CPOL_OK;
+}
+
+// in: the per-gate device arrays in the order of the fields; dist, hgt: the geometry's device arrays, holding geo_rays rows of ng
+// gates; n_rg: the gates of the call; T: where a finishing call's maps go (nine `values`, then `count`); lane_form: 0 the kept
+// form of k_comp, 1 combined, 2 every lane on its own.  Begins, composes, finishes; then the pass is advanced
+static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &pl, const void *const in[CPOL_COMP_FIELDS], const void *dist,
+                       const void *hgt, int geo_rays, long n_rg, int ng, void *const T[CP_N], int lane_form, hipStream_t st)
+{
+    const size_t n_ex = (size_t)pl.n_x + 1, n_ey = (size_t)pl.n_y + 1;
+    if (pl.begin) {
+        std::vector<double> &blob = ctx->cedges_host;     // (kept by the context: it outlives the copy whatever the runtime does)
+        try {
+            blob.assign(pl.ex.begin(), pl.ex.end());
+            blob.insert(blob.end(), pl.ey.begin(), pl.ey.end());
+        } catch (...) { ctx->err = "cpol_composite: out of host memory"; return CPOL_ERR_NOMEM; }
+        ENSURE(ctx->b_cstate, (size_t)pl.state_bytes);
+        ENSURE(ctx->b_cedges, (n_ex + n_ey) * sizeof(double));
+        // the begin values: max states and counts 0, min states all ones
+        HIPCHK(hipMemsetAsync(ctx->b_cstate.p, 0, (size_t)pl.zero_bytes, st));
+        if (pl.state_bytes > pl.zero_bytes)
+            HIPCHK(hipMemsetAsync((char *)ctx->b_cstate.p + pl.zero_bytes, 0xFF, (size_t)(pl.state_bytes - pl.zero_bytes), st));
+        HIPCHK(hipMemcpyAsync(ctx->b_cedges.p, blob.data(), (n_ex + n_ey) * sizeof(double), hipMemcpyHostToDevice, st));
+        ctx->cpass.open = false;                  // (whatever fails from here on, no half-begun pass stays open)
+    }
+    // the per-ray sines and cosines of this call
+    ENSURE(ctx->b_crays, 2 * (size_t)geo_rays * sizeof(double));
+    HIPCHK(hipMemcpyAsync(ctx->b_crays.p, c->ray_sin, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync((double *)ctx->b_crays.p + geo_rays, c->ray_cos, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
+    const auto pow2_below = [](int n) { int s = 1; while (2 * s <= n) s *= 2; return n > 0 ? s : 0; };
+    const long block_gates = pl.rows_per_block * (long)ng;
+    const long stretches = cdiv(block_gates, (long)COMP_STRETCH);
+    char *const base = (char *)ctx->b_cstate.p;
+    const auto at = [&](long off) { return off < 0 ? nullptr : base + off; };
+    const bool combine = lane_form == 0 ? CPOL_COMP_COMBINE != 0 : lane_form == 1;
+    for (int i = 0; i < pl.n_fields; ++i) {
+        const int k = pl.field[i];
+        CompArgs ca{};
+        ca.v = (const float *)in[k]; ca.dist = (const float *)dist; ca.hgt = (const float *)hgt;
+        ca.ex = (const double *)ctx->b_cedges.p; ca.ey = ca.ex + n_ex;
+        ca.ray_sin = (const double *)ctx->b_crays.p; ca.ray_cos = ca.ray_sin + geo_rays;
+        ca.smax = (unsigned long long *)at(pl.off_max[k]); ca.slow = (unsigned long long *)at(pl.off_low[k]);
+        ca.scount = (unsigned long long *)at(pl.off_count[k]); ca.stop = (unsigned *)at(pl.off_top[k]);
+        ca.block_gates = block_gates;
+        ca.geo_gates = (long)geo_rays * ng;
+        ca.n_gates = ng;
+        ca.n_ex = (int)n_ex; ca.n_ey = (int)n_ey;
+        ca.step_x = pow2_below((int)n_ex); ca.step_y = pow2_below((int)n_ey);
+        ca.n_x = pl.n_x; ca.n_y = pl.n_y; ca.cells = (int)pl.cells;
+        ca.stretches = (int)stretches;
+        ca.n_thr = pl.n_thr[k]; ca.slab = pl.slab ? 1 : 0;
+        ca.h_lo = pl.h_lo; ca.h_hi = pl.h_hi;
+        for (int j = 0; j < pl.n_thr[k]; ++j) ca.thr[j] = pl.thr[k][(size_t)j];
+        const unsigned grid = (unsigned)(pl.n_blocks * stretches);
+        const size_t lds = (n_ex + n_ey) * sizeof(double);          // (at most 16 KiB)
+        if (combine) hipLaunchKernelGGL(k_comp<true>, dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+        else hipLaunchKernelGGL(k_comp<false>, dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+        HIPCHK(hipGetLastError());
+    }
+    if (pl.finish)
+        for (int i = 0; i < pl.n_fields; ++i) {
+            const int k = pl.field[i];
+            CompFinishArgs fa{};
+            fa.smax = (const unsigned long long *)at(pl.off_max[k]); fa.slow = (const unsigned long long *)at(pl.off_low[k]);
+            fa.scount = (const unsigned long long *)at(pl.off_count[k]); fa.stop = (const unsigned *)at(pl.off_top[k]);
+            fa.values = (float *)T[k];
+            fa.count = (unsigned long long *)T[CP_COUNT] + (size_t)pl.slot[k] * pl.cells;
+            fa.n = pl.n_blocks * pl.cells;
+            fa.cells = (int)pl.cells; fa.n_planes = pl.n_planes[k]; fa.n_fields = pl.n_fields; fa.n_thr = pl.n_thr[k];
+            hipLaunchKernelGGL(k_comp_finish, dim3((unsigned)cdiv(fa.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, fa);
+            HIPCHK(hipGetLastError());
+        }
+    (void)n_rg;
+    try {
+        comp_advance(c, pl, &ctx->cpass);
+    } catch (...) {
+        ctx->cpass.open = false;
+        ctx->err = "cpol_composite: out of host memory";
+        return CPOL_ERR_NOMEM;
+    }
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "composite_fields": the plan, the placement, both kernels and the running state on
+// caller-supplied rows (host memory in, host memory out, blocking) -- the kernels on rows no sweep produces (every value class,
+// every stretch length, runs of equal cells across wavefront and workgroup boundaries, the largest grids).
+struct CompHook {
+    int32_t n_rows, n_gates, n_rays, lane_form;
+    const float *in[CPOL_COMP_FIELDS];      // [n_rows * n_gates]; NULL = not given
+    const float *heights, *dist;            // [n_rays * n_gates]
+    cpol_composite c;
+};
+
+static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
+{
+    if (hk->n_rows < 1 || hk->n_gates < 1 || (long)hk->n_rows * hk->n_gates >= (1L << 31) || hk->n_rays < 1 || hk->n_rows % hk->n_rays != 0 ||
+        hk->lane_form < 0 || hk->lane_form > 2) {
+        ctx->err = "composite_fields: bad shape (n_rays divides n_rows) or lane form";
+        return CPOL_ERR_ARG;
+    }
+    CompCall call;
+    call.n_rows = hk->n_rows; call.n_gates = hk->n_gates;
+    CompPlan pl;
+    PlaceArray arr[CP_N];
+    int rc = comp_plan(ctx, &hk->c, call, &pl, arr);
+    if (rc != CPOL_OK) return rc;
+    for (int i = 0; i < pl.n_fields; ++i)
+        if (!hk->in[pl.field[i]]) { ctx->err = "composite_fields: a requested field has no input"; return CPOL_ERR_ARG; }
+    if (!hk->heights || !hk->dist) { ctx->err = "composite_fields: heights and dist are needed"; return CPOL_ERR_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)hk->n_rows * hk->n_gates, n_geo = (size_t)hk->n_rays * hk->n_gates;
+    const void *in[CPOL_COMP_FIELDS] = {};
+    for (int k = 0; k < CPOL_COMP_FIELDS; ++k) {          // (the sweeps' own output buffers hold the inputs)
+        if (!hk->in[k]) continue;
+        if ((rc = upload(ctx, ctx->b_out[k], hk->in[k], n * sizeof(float))) != CPOL_OK) return rc;
+        in[k] = ctx->b_out[k].p;
+    }
+    if ((rc = upload(ctx, ctx->b_out[12], hk->dist, n_geo * sizeof(float))) != CPOL_OK) return rc;
+    if ((rc = upload(ctx, ctx->b_out[13], hk->heights, n_geo * sizeof(float))) != CPOL_OK) return rc;
+    PlacePlan plan;
+    place_outputs(arr, CP_N, 0, false, &plan);
+    DevBuf *own[CP_N];
+    for (int k = 0; k < CP_N; ++k) own[k] = &ctx->b_cout[k];
+    void *T[CP_N];
+    if ((rc = place_resolve(ctx, arr, CP_N, plan, own, T)) != CPOL_OK) return rc;
+    if ((rc = comp_launch(ctx, &hk->c, pl, in, ctx->b_out[12].p, ctx->b_out[13].p, hk->n_rays, (long)n, hk->n_gates, T, hk->lane_form,
+                          ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -2639,11 +2812,18 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
     static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
+    // (and so do a composite's nine `values` and its `count`: the three never share a call)
+    static_assert(CP_N <= SO_N, "the composite's maps in the slots of the superobservations");
     PlaceArray arr[A_N];
+    // (a composite shares a call with no other product: refused before the other product's own checks speak)
+    if (out->composite && (out->superob || out->histogram || out->member_stats || out->spectrum_moments)) {
+        ctx->err = "cpol_composite: not together with superobservations, histograms, ensemble statistics or spectrum moments in one call";
+        return CPOL_ERR_ARG;
+    }
     // (a histogram shares a call with no other product: refused before the other product's own checks speak)
     if (out->histogram && (out->superob || out->member_stats || out->spectrum_moments)) {
         ctx->err = "cpol_histogram: not together with superobservations, ensemble statistics or spectrum moments in one call";
@@ -2688,6 +2868,18 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         hc.other_product = so || ms || sm;
         const int rc_hg = hist_plan(ctx, hg, hc, &hg_pl, arr + A_HG);
         if (rc_hg != CPOL_OK) return rc_hg;
+    }
+    // gridded composites (cpol_composite): likewise
+    const cpol_composite *const cp = out->composite;
+    CompPlan &cp_pl = ctx->cplan;
+    if (cp) {
+        if (cols || sub_out) { ctx->err = "cpol_composite: cpol_run_sweep and cpol_run_sweep_members take composites, no other entry point"; return CPOL_ERR_ARG; }
+        CompCall cc;
+        cc.n_rows = n_rays; cc.n_gates = ng;
+        cc.spaceborne = t->site != nullptr || p->geometry_mode == CPOL_GEOM_SPACEBORNE;
+        cc.other_product = so || ms || sm || hg;
+        const int rc_cp = comp_plan(ctx, cp, cc, &cp_pl, arr + A_CP);
+        if (rc_cp != CPOL_OK) return rc_cp;
     }
     int rc;
 
@@ -3048,6 +3240,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
     own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
     if (hg) for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_HG + k] = &ctx->b_hcounts[k];      // (and a finishing call's counts)
+    if (cp) for (int k = 0; k < CP_N; ++k) own[A_CP + k] = &ctx->b_cout[k];                      // (and a finishing call's maps)
     for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
@@ -3824,6 +4017,12 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         else if (ord >= HIST_ORD_FIELD) y = hg_in[ord - HIST_ORD_FIELD];
         if ((rc = hist_launch(ctx, hg, hg_pl, hg_in, y, y_gates, n_rg, ng, T_all + A_HG, st)) != CPOL_OK) return rc;
     }
+    // ---- gridded composites: one kernel per requested field behind the sequence, into the context's running state; a finishing
+    // call decodes the state into the maps where the plan placed them (outside launch_all too) ----
+    if (cp) {
+        const void *const cp_in[CPOL_COMP_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV]};
+        if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, st)) != CPOL_OK) return rc;
+    }
     // ---- outputs that the kernels did not write in place ----
     if (window)
         HIPCHK(hipMemcpyAsync((void *)plan.win_lo, (const char *)ctx->b_outwin.p + plan.win_skew, (size_t)(plan.win_hi - plan.win_lo), hipMemcpyDeviceToHost, st));
@@ -3882,6 +4081,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
 {
     if (!ctx) return CPOL_ERR_ARG;
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->composite) { ctx->err = "cpol_run_columns: gridded composites (outputs->composite) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->histogram) { ctx->err = "cpol_run_columns: sweep histograms (outputs->histogram) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
@@ -4198,6 +4398,16 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "histogram_stretch")) {
         if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;
         const int32_t v = HIST_STRETCH;
+        memcpy(dst, &v, sizeof v);
+        return (int64_t)sizeof v;
+    }
+    if (!strcmp(name, "composite_fields")) {        // a CONTROL name: dst points to a CompHook
+        if (!dst || max_bytes < (int64_t)sizeof(CompHook)) { ctx->err = "cpol_debug_read(composite_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return comp_hook(ctx, (const CompHook *)dst);
+    }
+    if (!strcmp(name, "composite_stretch")) {
+        if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;
+        const int32_t v = COMP_STRETCH;
         memcpy(dst, &v, sizeof v);
         return (int64_t)sizeof v;
     }

@@ -1,0 +1,175 @@
+// cpol_comp.h -- gridded composites (cpol_composite): every refusal, the rounding of the slab and the thresholds to float32, the
+// plane list, the layout of the running state and the block arithmetic of a call, decided by comp_check() from plain numbers.
+// Plain C++ without HIP types, so that a host program can include it (tests/c_host/comp_check.cpp, tests/test_composite_cpu.py
+// check it without a GPU).  The kernels are k_comp and k_comp_finish (cpol_comp.inl); the rule is stated in
+// include/cosmo_pol_amd.h and cosmo_pol_amd/composite.py.
+#pragma once
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "cpol_hist.h"
+
+constexpr int COMP_FIELDS = CPOL_COMP_FIELDS;
+constexpr int COMP_MAX_THR = CPOL_COMP_MAX_THRESHOLDS;
+constexpr int COMP_MAX_EDGES = HIST_MAX_EDGES;     // n + 1 of either axis: both axes' float64 edges fit 16 KiB of LDS
+constexpr long COMP_MAX_STATE_BYTES = 1L << 30;    // the state of all blocks and fields
+// gates per workgroup of k_comp: a workgroup reads both axes' edges into LDS once (4.8 KB for a 300 x 300 grid), so a stretch
+// is long enough for its own 12 KB of gates to outweigh them; the 180 000 gates of a 360 x 500 sweep give 176 workgroups
+constexpr int COMP_STRETCH = 1024;
+constexpr int COMP_THREADS = 256;                  // threads of a workgroup of k_comp and k_comp_finish
+constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP;
+
+// what the entry point knows of the call
+struct CompCall {
+    long n_rows = 0;               // n_rays, or n_members * n_rays
+    int n_gates = 0;
+    bool spaceborne = false;       // per-ray radar positions: no one plane holds the gates
+    bool other_product = false;    // superobservations, histograms, ensemble statistics or spectrum moments in the same call
+};
+
+// the open pass of a context (the states themselves live on the device)
+struct CompPass {
+    bool open = false;
+    uint32_t fields = 0, products = 0;
+    long n_blocks = 0;
+    bool slab = false;
+    float h_lo = 0.f, h_hi = 0.f;
+    std::vector<float> thr[COMP_FIELDS];           // the ROUNDED thresholds
+    std::vector<double> ex, ey;
+};
+
+// a call that passed: the numbers the launches need
+struct CompPlan {
+    int n_fields = 0;
+    int field[COMP_FIELDS] = {};                   // the requested fields, ascending
+    int slot[COMP_FIELDS] = {};                    // field k's row of `count`
+    int n_thr[COMP_FIELDS] = {};
+    int n_planes[COMP_FIELDS] = {};                // of values[k]: 2 (MAX) + 2 (LOWEST) + n_thr
+    int n_x = 0, n_y = 0;
+    long cells = 0;                                // n_x * n_y
+    uint32_t products = 0;
+    bool slab = false;
+    float h_lo = 0.f, h_hi = 0.f;
+    std::vector<float> thr[COMP_FIELDS];
+    std::vector<double> ex, ey;
+    long n_blocks = 1, rows_per_block = 0;
+    // the state, in bytes: first what a begin sets to 0 -- per field the MAX states (uint64 [n_blocks][cells]), the counts
+    // (likewise) and the echo-top states (uint32 [n_blocks][n_thr][cells], padded to 8 bytes) -- then what it sets to all ones:
+    // per field the LOWEST states (uint64 [n_blocks][cells]).  -1: the field has none
+    long off_max[COMP_FIELDS] = {}, off_count[COMP_FIELDS] = {}, off_top[COMP_FIELDS] = {}, off_low[COMP_FIELDS] = {};
+    long zero_bytes = 0, state_bytes = 0;
+    bool begin = false, finish = false;
+};
+
+// a threshold or slab bound rounded once to float32 (at or beyond the midpoint between FLT_MAX and 2^128: infinity, as IEEE rounds)
+inline float comp_f32(double v)
+{
+    if (std::fabs(v) >= 0x1.ffffffp+127) return std::copysign(HUGE_VALF, (float)std::copysign(1.0, v));
+    return (float)v;
+}
+
+// every refusal of a cpol_composite for a call; NULL: accepted and *pl filled; else the reason (CPOL_ERR_ARG).  Touches neither
+// the pass nor anything else: the caller opens / closes the pass once the call is queued.
+inline const char *comp_check(const cpol_composite *c, const CompCall &call, const CompPass &pass, CompPlan *pl)
+{
+    *pl = CompPlan{};
+    if (call.other_product) return "not together with superobservations, histograms, ensemble statistics or spectrum moments in one call";
+    if (call.spaceborne) return "a spaceborne call (per-ray radar positions) has no radar-centred plane";
+    if (c->phase < 0 || c->phase > 3) return "phase must lie in 0 ... 3";
+    if (((c->fields >> COMP_FIELDS) & 1u)) return "RVEL is float64 and is not composed";
+    if (c->fields == 0 || (c->fields >> COMP_FIELDS) != 0) return "fields must name at least one of the 9 float32 fields and no other bit";
+    if (c->products == 0 || (c->products & ~COMP_PRODUCTS) != 0) return "products must name MAX, LOWEST or ECHO_TOP and no other bit";
+    pl->products = c->products;
+    const bool tops = (c->products & CPOL_COMP_ECHO_TOP) != 0;
+    for (int k = 0; k < COMP_FIELDS; ++k) {
+        if (!((c->fields >> k) & 1u)) continue;
+        const int nt = c->n_thresholds[k];
+        if (tops && (nt < 1 || nt > COMP_MAX_THR)) return "ECHO_TOP needs 1 ... 4 thresholds for every requested field";
+        if (!tops && nt != 0) return "thresholds without ECHO_TOP";
+        pl->thr[k].resize((size_t)nt);
+        for (int j = 0; j < nt; ++j) {
+            const double t = c->thresholds[k][j];
+            if (!(t == t)) return "a threshold is NaN";
+            pl->thr[k][(size_t)j] = comp_f32(t);
+        }
+        pl->slot[k] = pl->n_fields;
+        pl->field[pl->n_fields++] = k;
+        pl->n_thr[k] = nt;
+        pl->n_planes[k] = ((c->products & CPOL_COMP_MAX) ? 2 : 0) + ((c->products & CPOL_COMP_LOWEST) ? 2 : 0) + nt;
+    }
+    if (c->use_slab) {
+        pl->slab = true;
+        pl->h_lo = comp_f32(c->h_lo);
+        pl->h_hi = comp_f32(c->h_hi);
+        if (!(pl->h_lo < pl->h_hi)) return "the height slab needs h_lo < h_hi after rounding to float32";
+    }
+    if (c->n_x < 1 || c->n_y < 1) return "n_x and n_y must be >= 1";
+    if (c->n_x + 1 > COMP_MAX_EDGES || c->n_y + 1 > COMP_MAX_EDGES) return "n_x + 1 and n_y + 1 must be at most 1024";
+    if (!c->edges_x || !c->edges_y) return "edges_x or edges_y is NULL";
+    if (!c->ray_sin || !c->ray_cos) return "ray_sin or ray_cos is NULL";
+    pl->n_x = c->n_x; pl->n_y = c->n_y;
+    pl->cells = (long)c->n_x * c->n_y;
+    if (c->rays_per_block < 0 || (c->rays_per_block > 0 && call.n_rows % c->rays_per_block != 0))
+        return "rays_per_block must be >= 0 and divide the rows of the call";
+    pl->rows_per_block = c->rays_per_block ? c->rays_per_block : call.n_rows;
+    pl->n_blocks = call.n_rows / pl->rows_per_block;
+    // the state (n_blocks <= 2^31 rows, cells < 2^20, at most 9 * 28 bytes per cell and block: no overflow of long)
+    const long per = pl->n_blocks * pl->cells;
+    long off = 0;
+    for (int i = 0; i < pl->n_fields; ++i) {
+        const int k = pl->field[i];
+        pl->off_max[k] = pl->off_top[k] = pl->off_low[k] = -1;
+        if (c->products & CPOL_COMP_MAX) { pl->off_max[k] = off; off += per * 8; }
+        pl->off_count[k] = off; off += per * 8;
+        if (pl->n_thr[k]) { pl->off_top[k] = off; off += (per * pl->n_thr[k] * 4 + 7) & ~7L; }
+        if (off > COMP_MAX_STATE_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
+    }
+    pl->zero_bytes = off;
+    if (c->products & CPOL_COMP_LOWEST)
+        for (int i = 0; i < pl->n_fields; ++i) { pl->off_low[pl->field[i]] = off; off += per * 8; }
+    if (off > COMP_MAX_STATE_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
+    pl->state_bytes = off;
+    // (one workgroup per stretch of a block: the grid of one launch; out of reach while the call holds fewer than 2^31 gates)
+    if (pl->n_blocks * ((pl->rows_per_block * (long)call.n_gates + COMP_STRETCH - 1) / COMP_STRETCH) >= (1L << 31))
+        return "too many workgroups in one call";
+    const char *why;
+    if ((why = hist_round_edges(c->edges_x, c->n_x + 1, HIST_T_F64, &pl->ex))) return why;
+    if ((why = hist_round_edges(c->edges_y, c->n_y + 1, HIST_T_F64, &pl->ey))) return why;
+    pl->begin = (c->phase & 1) != 0;
+    pl->finish = (c->phase & 2) != 0;
+    if (!pl->begin) {
+        if (!pass.open) return "a composing call with no pass open and no begin bit";
+        if (pass.fields != c->fields || pass.products != c->products || pass.n_blocks != pl->n_blocks)
+            return "fields, products or block count differ from the open pass";
+        if (pass.slab != pl->slab || (pl->slab && (pass.h_lo != pl->h_lo || pass.h_hi != pl->h_hi)))
+            return "the height slab differs from the open pass";
+        for (int i = 0; i < pl->n_fields; ++i)
+            if (pass.thr[pl->field[i]] != pl->thr[pl->field[i]]) return "thresholds differ from the open pass";
+        if (pass.ex != pl->ex || pass.ey != pl->ey) return "edges differ from the open pass";
+    }
+    if (pl->finish) {
+        if (!c->count) return "a finishing call needs count";
+        for (int i = 0; i < pl->n_fields; ++i)
+            if (!c->values[pl->field[i]]) return "a finishing call needs values for every requested field";
+    }
+    return nullptr;
+}
+
+// after the call is queued: the pass as it now stands
+inline void comp_advance(const cpol_composite *c, const CompPlan &pl, CompPass *pass)
+{
+    if (pl.begin) {
+        pass->open = true;
+        pass->fields = c->fields;
+        pass->products = c->products;
+        pass->n_blocks = pl.n_blocks;
+        pass->slab = pl.slab; pass->h_lo = pl.h_lo; pass->h_hi = pl.h_hi;
+        for (int k = 0; k < COMP_FIELDS; ++k) pass->thr[k] = pl.thr[k];
+        pass->ex = pl.ex;
+        pass->ey = pl.ey;
+    }
+    if (pl.finish) pass->open = false;
+}

@@ -1,0 +1,155 @@
+// cpol_comp.inl -- gridded composites: the column maximum, the lowest gate and echo-top heights of the per-gate fields of a call
+// on a radar-centred map (cpol_composite).
+//
+// Reference functions replaced (wolfidan/cosmo_pol): none -- the reference hands back per-gate radials, and its users compute per
+// gate where it lies and scatter with np.maximum.at.  The rule is the one of include/cosmo_pol_amd.h and
+// cosmo_pol_amd/composite.py (`compose`, `finish`): the cell of a gate is found by ONE float64 multiplication per axis (the
+// caller gives sine and cosine) and comparisons alone, and every result is a maximum, a minimum or a sum of INTEGERS (the ordered
+// keys of the float32 values) -- whatever order the hardware works in, the maps are those of NumPy.  No float atomics, no
+// compare-and-swap loops, no trigonometric function.
+
+struct CompArgs {
+    const float *v;                 // the field [n_rows * n_gates]
+    const float *dist, *hgt;        // [geo_gates]
+    const double *ex, *ey;          // the edges on the device [n_ex], [n_ey]
+    const double *ray_sin, *ray_cos;   // [n_rays]
+    unsigned long long *smax, *slow, *scount;  // this field's states [n_blocks][cells] (NULL: product not requested)
+    unsigned *stop;                 // [n_blocks][n_thr][cells]
+    long block_gates;               // rows_per_block * n_gates: the gates of one block
+    long geo_gates;                 // the gates the geometry arrays hold (an ensemble call: n_rays rows once); gate g reads g % geo_gates
+    int n_gates;
+    int n_ex, n_ey;                 // edges (n + 1)
+    int step_x, step_y;             // the largest power of two <= n_ex / n_ey: the first step of the search
+    int n_x, n_y, cells;            // cells = n_x * n_y
+    int stretches;                  // stretches of one block
+    int n_thr, slab;
+    float h_lo, h_hi;
+    float thr[COMP_MAX_THR];        // rounded
+};
+
+// the ordered key of a float32: a total order -inf < ... < -0.0 < +0.0 < ... < +inf; 0 and 0xFFFFFFFF are keys of NaNs alone
+__device__ __forceinline__ unsigned comp_key(float f)
+{
+    const unsigned b = __float_as_uint(f);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+__device__ __forceinline__ float comp_unkey(unsigned k)
+{
+    return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
+// A workgroup owns one stretch of COMP_STRETCH consecutive gates of ONE block and ONE field (a launch per requested field) and
+// never crosses a block boundary; the edges of both axes lie in LDS.  Per gate: two branch-free binary searches, the slab test,
+// the keys.  Consecutive gates of a ray fall into the same or neighbouring cells, so with COMBINE the lanes of a wavefront that
+// form a run of one cell are combined first (a segmented max / min over __shfl_up, bounded by the run's first lane: exact, max
+// and min being associative and commutative, and the count of a run is its length), and only the LAST lane of each run issues
+// the global integer atomics.  Without COMBINE every counting lane issues its own.
+template <bool COMBINE>
+__global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
+{
+    extern __shared__ double comp_lds[];
+    const int tid = threadIdx.x;
+    double *const ex = comp_lds, *const ey = comp_lds + a.n_ex;
+    for (int j = tid; j < a.n_ex; j += COMP_THREADS) ex[j] = a.ex[j];
+    for (int j = tid; j < a.n_ey; j += COMP_THREADS) ey[j] = a.ey[j];
+    __syncthreads();
+    const long b = (long)blockIdx.x / a.stretches;
+    const long s = (long)blockIdx.x % a.stretches;
+    const long g0 = b * a.block_gates + s * (long)COMP_STRETCH;
+    const long g1 = min(g0 + (long)COMP_STRETCH, (b + 1) * a.block_gates);
+    const bool want_max = a.smax != nullptr, want_low = a.slow != nullptr;
+    const long cell0 = b * (long)a.cells;
+    // (every lane of the workgroup takes every turn of the loop: the shuffles below need whole wavefronts)
+    for (long base = g0; base < g1; base += COMP_THREADS) {
+        const long g = base + tid;
+        int cell = -1;
+        unsigned long long kmax = 0ull, klow = ~0ull;
+        unsigned top[COMP_MAX_THR] = {0u, 0u, 0u, 0u};
+        if (g < g1) {
+            const float v = a.v[g];
+            const long gg = g < a.geo_gates ? g : g % a.geo_gates;      // (the geometry of an ensemble call: n_rays rows once)
+            const int ray = (int)(gg / a.n_gates);
+            const float d = a.dist[gg], h = a.hgt[gg];
+            const double x = (double)d * a.ray_sin[ray], y = (double)d * a.ray_cos[ray];
+            const int ix = hist_bin<double>(ex, a.n_ex, a.step_x, x) - 1;
+            const int iy = hist_bin<double>(ey, a.n_ey, a.step_y, y) - 1;
+            bool counts = v == v && d == d && h == h && ix >= 0 && ix < a.n_x && iy >= 0 && iy < a.n_y;
+            if (a.slab) counts = counts && a.h_lo <= h && h < a.h_hi;
+            if (counts) {
+                cell = iy * a.n_x + ix;
+                const unsigned kv = comp_key(v), kh = comp_key(h);
+                kmax = ((unsigned long long)kv << 32) | kh;
+                klow = ((unsigned long long)kh << 32) | kv;
+#pragma unroll
+                for (int j = 0; j < COMP_MAX_THR; ++j) top[j] = (j < a.n_thr && v >= a.thr[j]) ? kh : 0u;
+            }
+        }
+        unsigned long long n = 1ull;
+        bool issue = cell >= 0;
+        if (COMBINE) {
+            const int lane = tid & 63;
+            const int before = __shfl_up(cell, 1);
+            const bool head = lane == 0 || before != cell || cell < 0;                    // (a gate that does not count: a run of its own)
+            const unsigned long long heads = __ballot(head) & (~0ull >> (63 - lane));     // the heads at or below this lane
+            const int run = lane - (63 - __clzll((long long)heads));                       // lanes of this run before this one
+            for (int dlt = 1; dlt < 64 && __any(run >= dlt); dlt <<= 1) {
+                const bool take = run >= dlt;
+                if (want_max) { const unsigned long long o = __shfl_up(kmax, dlt); if (take && o > kmax) kmax = o; }
+                if (want_low) { const unsigned long long o = __shfl_up(klow, dlt); if (take && o < klow) klow = o; }
+#pragma unroll
+                for (int j = 0; j < COMP_MAX_THR; ++j)
+                    if (j < a.n_thr) { const unsigned o = __shfl_up(top[j], dlt); if (take && o > top[j]) top[j] = o; }
+            }
+            const int after = __shfl_down(cell, 1);
+            issue = issue && (lane == 63 || after != cell);
+            n = (unsigned long long)(run + 1);
+        }
+        if (issue) {
+            const long c = cell0 + cell;
+            atomicAdd(&a.scount[c], n);
+            if (want_max) atomicMax(&a.smax[c], kmax);
+            if (want_low) atomicMin(&a.slow[c], klow);
+#pragma unroll
+            for (int j = 0; j < COMP_MAX_THR; ++j)
+                if (j < a.n_thr && top[j]) atomicMax(&a.stop[(b * a.n_thr + j) * (long)a.cells + cell], top[j]);
+        }
+    }
+}
+
+struct CompFinishArgs {
+    const unsigned long long *smax, *slow, *scount;   // as in CompArgs
+    const unsigned *stop;
+    float *values;                  // [n_blocks][n_planes][cells]
+    unsigned long long *count;      // [n_blocks][n_fields][cells], at this field's row of block 0
+    long n;                         // n_blocks * cells
+    int cells, n_planes, n_fields, n_thr;
+};
+
+// A finishing call: one thread per (block, cell) of one field decodes the states into the planes of `values` -- the key
+// inverted, a cell whose state still holds the begin value NaN -- and copies the count.
+__global__ __launch_bounds__(COMP_THREADS) void k_comp_finish(const CompFinishArgs a)
+{
+    const long i = (long)blockIdx.x * COMP_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const long b = i / a.cells, c = i % a.cells;
+    const float nan = __uint_as_float(0x7FC00000u);
+    float *out = a.values + b * (long)a.n_planes * a.cells + c;
+    if (a.smax) {
+        const unsigned long long s = a.smax[i];
+        out[0] = s ? comp_unkey((unsigned)(s >> 32)) : nan;
+        out[a.cells] = s ? comp_unkey((unsigned)s) : nan;
+        out += 2 * (long)a.cells;
+    }
+    if (a.slow) {
+        const unsigned long long s = a.slow[i];
+        out[0] = s != ~0ull ? comp_unkey((unsigned)s) : nan;
+        out[a.cells] = s != ~0ull ? comp_unkey((unsigned)(s >> 32)) : nan;
+        out += 2 * (long)a.cells;
+    }
+    for (int j = 0; j < a.n_thr; ++j) {
+        const unsigned s = a.stop[(b * a.n_thr + j) * (long)a.cells + c];
+        out[(long)j * a.cells] = s ? comp_unkey(s) : nan;
+    }
+    a.count[b * (long)a.n_fields * a.cells + c] = a.scount[i];
+}

@@ -32,13 +32,14 @@ from . import ensemble_verify as EV
 from . import spectrum_moments as SM
 from . import superob as SO
 from . import histogram as HG
+from . import composite as CP
 from .lut import load_all_lut
 
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
 DOPPLER_FIELDS = ['RVEL', 'DSPECTRUM']
 _DB_FIELDS = ('ZDR', 'ZV', 'ZH')
 _ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2, np.uint64: 8}
-_PRODUCT_OUTPUTS = frozenset(('histogram', 'stats', 'moments', 'superob'))     # entries of device_outputs that are dicts of a product
+_PRODUCT_OUTPUTS = frozenset(('histogram', 'composite', 'stats', 'moments', 'superob'))     # entries of device_outputs that are dicts of a product
 
 
 class ModelVar(object):
@@ -1260,14 +1261,20 @@ class RadarOperator(object):
                                  '(statistics of window averages are left to the host)')
             if timed is not None or subbeams is not None:
                 raise ValueError('ensemble statistics are taken by the ensemble sweeps, not by time-blended or sub-beam calls')
-        hg_spec = None
+        hg_spec = cp_spec = None
         if histogram is not None:
-            # (spec, phase, rays_per_block, keep_gates): this call's gates counted into the lane's running histogram
+            # (spec, phase, rays_per_block, keep_gates): this call's gates counted into the lane's running histogram -- or, with a
+            # composite.Composite as spec, folded into the lane's running composite.  (The two reductions over gates never share a
+            # call and ride ONE argument, so that the plain call pays one test for both.)
             hg_spec, hg_phase, hg_rpb, hg_keep = histogram
-            self._histogram_check(hg_spec)
+            if isinstance(hg_spec, CP.Composite):
+                cp_spec = hg_spec
+                self._composite_check(cp_spec)    # (a spaceborne call, per-ray radar positions, is refused by the library)
+            else:
+                self._histogram_check(hg_spec)
             if superob is not None or member_stats is not None or moments is not None or subbeams is not None:
-                raise ValueError('histograms do not share a call with superobservations, ensemble statistics, spectrum moments '
-                                 'or the sub-beam export')
+                raise ValueError('histograms and composites do not share a call with superobservations, ensemble statistics, '
+                                 'spectrum moments or the sub-beam export')
         # the per-gate radar fields travel to the host
         gates = (superob is None or keep_gates) and (member_stats is None or ms_keep) and (hg_spec is None or hg_keep)
         conf = self.__config
@@ -1295,7 +1302,7 @@ class RadarOperator(object):
 
         want_model = self.output_variables in ('all', 'only_model') and members is None and gates
         # a histogram over a model variable: the library integrates the model variables for it, asked for or not
-        hg_model = hg_spec is not None and isinstance(hg_spec.ordinate, tuple)
+        hg_model = hg_spec is not None and cp_spec is None and isinstance(hg_spec.ordinate, tuple)
         if hg_model:
             if self.output_variables not in ('all', 'only_model') or members is not None:
                 raise ValueError("histogram: the ordinate %r needs a call that produces model_vars (output_variables 'all' or "
@@ -1439,18 +1446,34 @@ class RadarOperator(object):
         if hg_spec is not None:
             n_rows = n_rays * (len(members) if members is not None else 1)
             HG.n_blocks(n_rows, hg_rpb)               # (ValueError: the library refuses the same)
-            hg, hg_keepalive = N.Context.histogram_struct(
-                hg_spec, hg_phase, hg_rpb, model_index=self._staged_vars.index(hg_spec.ordinate[1]) if hg_model else None)
+            if cp_spec is not None:               # (sine and cosine of the azimuths come from here: the library computes neither)
+                hg, hg_keepalive = N.Context.composite_struct(cp_spec, hg_phase, hg_rpb, azimuths=az)
+                o.composite = C.pointer(hg)
+            else:
+                hg, hg_keepalive = N.Context.histogram_struct(
+                    hg_spec, hg_phase, hg_rpb, model_index=self._staged_vars.index(hg_spec.ordinate[1]) if hg_model else None)
+                o.histogram = C.pointer(hg)
             keep = list(keep) + hg_keepalive
-            o.histogram = C.pointer(hg)
         hg_out = hg is not None and bool(int(hg_phase) & 2)      # a finishing call: the counts arrive with it
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
                 if k not in _PRODUCT_OUTPUTS:     # an array of the sweep itself (one look-up, however many products there are)
                     setattr(o, k, ptr)
                     continue
+                if k == 'composite':              # {'values': {field: device pointer of its float32 planes}, 'count': device pointer}
+                    if cp_spec is None:
+                        raise ValueError("device_outputs['composite'] without a composite")
+                    for kk, pp in (ptr.items() if hg_out else ()):
+                        if kk == 'count':
+                            hg.count = pp
+                        elif kk == 'values':
+                            for f, q in pp.items():
+                                hg.values[CP.FIELDS.index(f)] = q
+                        else:
+                            raise ValueError("device_outputs['composite']: unknown entry %r" % (kk,))
+                    continue
                 if k == 'histogram':              # {field: device pointer of its uint64 counts}
-                    if hg is None:
+                    if hg is None or cp_spec is not None:
                         raise ValueError("device_outputs['histogram'] without a histogram")
                     for kk, pp in (ptr.items() if hg_out else ()):
                         hg.counts[HG.FIELDS.index(kk)] = pp
@@ -1522,8 +1545,13 @@ class RadarOperator(object):
                 spec.append((('moments', 'moments'), np.float64, (len(SM.FIELDS),) + shape))
                 spec.append((('moments', 'count'), np.uint16, shape))
             if hg_out:
-                # the counts, in the same block: they ride the one copy
-                spec += [(('histogram', k), np.uint64, HG.shape(hg_spec, k, n_rows, hg_rpb)) for k in hg_spec.fields]
+                if cp_spec is not None:
+                    # the maps, in the same block: they ride the one copy
+                    spec += [(('composite', k), np.float32, CP.shape(cp_spec, k, n_rows, hg_rpb)) for k in cp_spec.fields]
+                    spec.append((('composite', 'count'), np.uint64, CP.count_shape(cp_spec, n_rows, hg_rpb)))
+                else:
+                    # the counts, in the same block: they ride the one copy
+                    spec += [(('histogram', k), np.uint64, HG.shape(hg_spec, k, n_rows, hg_rpb)) for k in hg_spec.fields]
             if ms_out:
                 # the statistics, in the same block: they ride the one copy
                 for kind in ms_spec.kinds:
@@ -1573,8 +1601,15 @@ class RadarOperator(object):
                     res.setdefault('histogram', {}).setdefault('counts', {})[k[1]] = a
                     hg.counts[HG.FIELDS.index(k[1])] = base + off
                 elif isinstance(k, tuple):
-                    res.setdefault('superob', {})[k[1]] = a
-                    setattr(so, k[1], base + off)
+                    if k[0] == 'composite':
+                        res.setdefault('composite', {})[k[1]] = a
+                        if k[1] == 'count':
+                            hg.count = base + off
+                        else:
+                            hg.values[CP.FIELDS.index(k[1])] = base + off
+                    else:
+                        res.setdefault('superob', {})[k[1]] = a
+                        setattr(so, k[1], base + off)
                 else:
                     res[k] = a
                     setattr(o, k, base + off)       # (= res[k].ctypes.data, without an interface object per array)
@@ -1635,8 +1670,15 @@ class RadarOperator(object):
                         ctx.synchronize()
                     w.update(SO.coordinates(res, superob, so_rpb))
         if hg_out and device_outputs is None:
-            res['histogram']['edges'] = {k: hg_spec.edges[k] for k in hg_spec.fields}
-            res['histogram']['ordinate_edges'] = hg_spec.ordinate_edges
+            if cp_spec is not None:
+                w = res['composite']
+                cnt = w.pop('count')
+                res['composite'] = {'values': {k: {q: w[k][:, j] for j, q in enumerate(cp_spec.planes(k))} for k in cp_spec.fields},
+                                    'count': {k: cnt[:, i] for i, k in enumerate(cp_spec.fields)},
+                                    'x_edges': cp_spec.x_edges, 'y_edges': cp_spec.y_edges}
+            else:
+                res['histogram']['edges'] = {k: hg_spec.edges[k] for k in hg_spec.fields}
+                res['histogram']['ordinate_edges'] = hg_spec.ordinate_edges
         if sm is not None and device_outputs is None:
             w = res['moments']
             rows = w.pop('moments')
@@ -2044,7 +2086,7 @@ class RadarOperator(object):
         if superob is not None:
             self._superob_check(superob)
         if histogram is not None:
-            self._histogram_check(histogram[0])
+            (self._composite_check if isinstance(histogram[0], CP.Composite) else self._histogram_check)(histogram[0])
         from . import timeline
         az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
         el = np.asarray(elevations, dtype=np.float64).reshape(-1)
@@ -2065,7 +2107,7 @@ class RadarOperator(object):
             raise ValueError('simulate_rays_at: the rays read more than %d states; superobservations need one group'
                              % N.MEMBERS_PER_CALL)
         if len(groups) > 1 and histogram is not None:
-            raise ValueError('simulate_rays_at: the rays read more than %d states; a histogram call needs one group (cut the rays '
+            raise ValueError('simulate_rays_at: the rays read more than %d states; a histogram or composite call needs one group (cut the rays '
                              'and fold the calls into one pass with phase=)' % N.MEMBERS_PER_CALL)
         coords = self.__config['radar']['coords']
         rr = self.constants.RANGE_RADAR
@@ -2579,6 +2621,113 @@ class RadarOperator(object):
         get_PPI_histogram)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._histogram_sweeps(sweeps, hist, per_sweep, keep_gates, 0)
+
+    # ------------------------------------------------------------------ gridded composites
+    # (replaces in the reference: nothing -- its users pull every per-gate array to the host, compute per gate where it lies and
+    # scatter with np.maximum.at)
+    def _composite_check(self, spec):
+        """What a composite call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        themselves: they take ground radars.)"""
+        if not isinstance(spec, CP.Composite):
+            raise ValueError('spec: a cosmo_pol_amd.composite.Composite, got %r' % (spec,))
+        if self.distributed:
+            raise NotImplementedError('composites with a process group: sharding rays over ranks is not built')
+
+    def simulate_rays_composite(self, azimuths, elevations, spec, keep_gates=False, phase=3, rays_per_block=0, device_outputs=None,
+                                lane=0, pinned=False):
+        """simulate_rays handing back MAPS of its gates on a radar-centred grid: `spec` is a composite.Composite, and a finishing
+        call's result gains res['composite'] = {'values': {field: {plane: float32 [n_blocks, n_y, n_x]}}, 'count': {field: uint64
+        [n_blocks, n_y, n_x]}, 'x_edges', 'y_edges'} -- the column maximum, the lowest gate and the echo tops, reduced on the
+        device behind the sweep's kernels (composite.compose / composite.finish state the rule, and the maps are exactly theirs of
+        the call's own per-gate arrays, `dist`, `heights` and azimuths).  Without `keep_gates` no per-gate radar field is
+        produced for the host or copied; with it the result carries every array of simulate_rays, bit for bit.
+        `phase`: bit 0 begins the lane's pass, bit 1 finishes it (the maps come back); 0 only folds -- the sweeps of a volume
+        fold into one composite.  `rays_per_block`: 0 one map of all rays, else a divisor of the rays: one map per block of rays.
+        `device_outputs`: its entry 'composite' is {'values': {field: device pointer}, 'count': device pointer}.  ValueError for
+        what the library refuses; NotImplementedError with a process group and for spaceborne geometry."""
+        self._composite_check(spec)
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                   histogram=(spec, int(phase), int(rays_per_block), keep_gates))
+
+    def simulate_rays_at_composite(self, azimuths, elevations, times, spec, keep_gates=False, phase=3, rays_per_block=0,
+                                   device_outputs=None, lane=0, pinned=False):
+        """simulate_rays_at handing back a composite: `spec`, `keep_gates`, `phase`, `rays_per_block` as for
+        simulate_rays_composite (ValueError when the rays fall into several groups of states)."""
+        self._composite_check(spec)
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                      histogram=(spec, int(phase), int(rays_per_block), keep_gates))
+
+    def simulate_rays_ensemble_composite(self, azimuths, elevations, spec, members=None, per_member=True, keep_gates=False,
+                                         phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
+        """simulate_rays_ensemble (form 'shared') handing back composites: with `per_member` one map per member, in the order
+        of `members` (the leading axis of every plane; rays_per_block = n_rays: each equals the member's own
+        simulate_rays_composite), without it one map of all members' gates.  The gate coordinates come once.  `keep_gates`:
+        the per-member arrays of simulate_rays_ensemble come back too.  `phase`: as for simulate_rays_composite; when
+        `sequence_memory_budget` cuts the member list into several calls, per_member needs phase=3 (every chunk is a pass of its
+        own and the blocks are joined), and the one map of all members folds the chunks into the pass.  NotImplementedError
+        where simulate_rays_ensemble raises it."""
+        self._composite_check(spec)
+        members = self._members_arg(members)
+        coords = self._ensemble_coords()
+        sub = self._cached('sub', lambda: quadrature.subbeams(self.__config))
+        rr = self.constants.RANGE_RADAR
+        n_rays = len(np.asarray(azimuths).reshape(-1))
+        chunks = self._shared_member_chunks(self._lane(lane), members, sub.n_sub * len(rr) * n_rays)
+        phase = int(phase)
+        if len(chunks) > 1 and device_outputs is not None:
+            raise ValueError('simulate_rays_ensemble_composite: device outputs need the members in one chunk')
+        if len(chunks) > 1 and per_member and phase != 3:
+            raise ValueError('simulate_rays_ensemble_composite: per-member maps of a member list cut into several calls need phase=3')
+        parts = []
+        for i, chunk in enumerate(chunks):
+            if per_member or len(chunks) == 1:
+                ph = phase
+            else:
+                ph = (phase & 1 if i == 0 else 0) | (phase & 2 if i == len(chunks) - 1 else 0)
+            parts.append(self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
+                                        device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
+                                        pinned=pinned and len(chunks) == 1, members=chunk,
+                                        histogram=(spec, ph, n_rays if per_member else 0, keep_gates)))
+        if len(parts) == 1 or device_outputs is not None:
+            return parts[-1]
+        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
+        out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts]))
+               for k in parts[0].keys() if k != 'composite'}
+        if 'composite' in parts[-1]:
+            out['composite'] = dict(parts[-1]['composite'])
+            if per_member:
+                out['composite']['values'] = {k: {q: np.concatenate([w['composite']['values'][k][q] for w in parts])
+                                                  for q in spec.planes(k)} for k in spec.fields}
+                out['composite']['count'] = {k: np.concatenate([w['composite']['count'][k] for w in parts]) for k in spec.fields}
+        return out
+
+    def get_PPI_composite(self, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, per_sweep=False,
+                          keep_gates=False):
+        """The sweeps of get_PPI composed onto a map.  By default ALL sweeps fold into one pass (the volume's composite):
+        {'composite': as for simulate_rays_composite, 'sweeps': [what each call returned: the per-gate arrays with keep_gates]}.
+        With `per_sweep` a list with one simulate_rays_composite(..., spec) result per elevation, the sweeps spread over the
+        lanes.  (An RHI has no such entry: its plan view is a line.)"""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        self._composite_check(spec)
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        n_par = max(1, min(self.lanes, len(sweeps))) if per_sweep else 1
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                phase = 3 if per_sweep else (1 if k == 0 else 0) | (2 if k == len(sweeps) - 1 else 0)
+                res.append(self.simulate_rays_composite(az, el, spec, keep_gates=keep_gates, phase=phase, pinned=True, lane=k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        if per_sweep:
+            return res
+        return {'composite': res[-1].pop('composite'), 'sweeps': res}
 
     # ------------------------------------------------------------------ spectrum moments scans
     def _moments_sweeps(self, sweeps, moments, keep_spectrum):

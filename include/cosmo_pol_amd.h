@@ -514,6 +514,80 @@ typedef struct cpol_histogram {
     uint64_t *counts[CPOL_HIST_FIELDS];         /* [n_blocks][n_y + 2][n_x[k] + 2]; read by a finishing call        */
 } cpol_histogram;
 
+/* Gridded composites: the column maximum, the lowest gate and echo-top heights of the per-gate fields of a call on a
+ * radar-centred map, reduced on the device, for the user who wants a MAP instead of one value per gate.  Replaces in the
+ * reference: nothing (its users pull every per-gate array to the host, compute per gate where it lies and scatter with
+ * np.maximum.at).  Pointed to by cpol_outputs.composite; honoured by cpol_run_sweep and cpol_run_sweep_members (the ensemble and
+ * the time blend).  cosmo_pol_amd/composite.py states the same rule in NumPy (`compose`, `finish`).
+ * INPUT: the per-gate fields of the call as the launch sequence leaves them: after the range scans and the sensitivity cut,
+ * censored gates NaN; n_rows rows of n_gates gates (n_rows = n_rays, or n_members * n_rays in an ensemble call).  With them
+ * `dist` (float32, ground distance of the central sub-beam) and `heights` (float32) of the same call, and per ray two float64
+ * numbers ray_sin[r], ray_cos[r] GIVEN BY THE CALLER (the Python layer: np.sin(np.deg2rad(az)), np.cos(np.deg2rad(az))): the
+ * library computes no trigonometric function for this product, so the device and the rule cannot differ there.  Geometry arrays
+ * that hold n_rays rows once (an ensemble call without time blend) are read at g mod (n_rays * n_gates), the per-ray pair at
+ * row mod n_rays.
+ * PLANE: radar-centred, east x and north y: x = (double)dist * ray_sin, y = (double)dist * ray_cos -- ONE float64
+ * multiplication each (the library is built with -ffp-contract=off).
+ * GRID: n_x + 1 and n_y + 1 float64 edges, finite and strictly ascending, at most 1024 per axis.  ix = #{ j : ex[j] <= x } - 1,
+ * likewise iy: comparisons alone, np.searchsorted(e, x, side='right') - 1.  The gate lies in the grid iff 0 <= ix < n_x and
+ * 0 <= iy < n_y: there are no under- or overflow cells (a gate on the last edge is outside), and a gate outside does not count.
+ * HEIGHT SLAB, optional (use_slab): [h_lo, h_hi), both bounds rounded once to float32, the test h_lo <= h && h < h_hi in
+ * float32.  Without a slab every height counts.
+ * FIELDS: the nine float32 fields ZH ... ATT_V, bit k as in cpol_histogram.fields.  RVEL (float64) is refused.
+ * COUNTING: a gate counts for field k iff v == v, dist == dist, h == h, it lies in the grid and it lies in the slab.
+ * THE ORDERED KEY of a float32 with bits b: key = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000), a total order
+ * -inf < ... < -0.0 < +0.0 < ... < +inf.  Keys 0 and 0xFFFFFFFF belong to NaN bit patterns: no counting value produces them,
+ * and they mark an empty cell.
+ * PRODUCTS per requested field, a bit mask, the same for all fields of a struct:
+ *   CPOL_COMP_MAX      `max`, `height_of_max`: one uint64 per cell, the MAXIMUM of key(v) << 32 | key(h) over the counting
+ *                      gates; ties in the value go to the greater height.
+ *   CPOL_COMP_LOWEST   `lowest`, `height_of_lowest`: one uint64 per cell, the MINIMUM of key(h) << 32 | key(v); ties in the
+ *                      height go to the smaller value.
+ *   CPOL_COMP_ECHO_TOP `echo_top_0` ... : n_thresholds[k] in 1 ... 4 planes for field k, thresholds in the field's own linear
+ *                      units, each rounded once to float32 (not NaN); per plane one uint32 per cell, the maximum of key(h) over
+ *                      the counting gates with v >= t.  Without this bit every n_thresholds must be 0.
+ *   `count` is always produced: uint64 per cell and field, the number of counting gates.
+ * BLOCKS AND PASS, exactly as in cpol_histogram: rays_per_block = 0 one map of all rows, else it divides n_rows (n_rays: one map
+ * per member).  phase bit 0 begins (max states 0, min states all ones, counts 0), bit 1 finishes.  The state is one per context,
+ * on the device.  With rays_per_block == 0 the calls of a pass may differ in n_rays, n_gates and geometry: the sweeps of a volume
+ * fold into one composite.  Every result is a max, a min or a sum of integers: it depends neither on how the pass is cut into
+ * calls nor on any order.
+ * OUTPUTS, read by a finishing call only: per requested field one float32 array values[k], [n_blocks][n_planes][n_y][n_x], the
+ * planes in the fixed order max, height_of_max, lowest, height_of_lowest, echo_top_0 ..., planes not requested absent, empty
+ * cells NaN; one uint64 array count, [n_blocks][n_requested_fields][n_y][n_x], the fields ascending.  The pointers follow
+ * p->outputs_on_device like every other array.
+ * LIMITS (conditions, not measurements): at most 1024 edges per axis; the state of all blocks and fields at most 1 GiB; fewer
+ * than 2^31 workgroups.
+ * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: phase outside 0..3; fields zero or with a bit >= 9
+ * (RVEL); products zero or with an unknown bit; n_thresholds outside 1..4 with ECHO_TOP or non-zero without; a NaN threshold;
+ * a slab with h_lo >= h_hi after rounding (or a NaN bound); n_x or n_y < 1 or over the limit; a NULL edge array; an edge NaN or
+ * infinite; edges not strictly ascending; a limit exceeded; rays_per_block < 0 or not dividing n_rows; NULL ray_sin or ray_cos; a
+ * counting call with no pass open and no begin bit; a call whose fields, products, thresholds, slab, edges or block count differ
+ * from the open pass; a finishing call without `count` or without `values` of a requested field; a spaceborne call (per-ray
+ * radar positions: tables->site); outputs->superob, histogram, member_stats or spectrum_moments in the same call;
+ * cpol_run_columns and cpol_interp_subbeams.
+ * ONE kernel per requested field (k_comp, cpol_comp.inl) runs behind the launch sequence and before the output copy, and a
+ * finishing call adds k_comp_finish per field: the per-gate arrays, the launch forms, the gate stencils and a captured graph are
+ * what they are without it.  A per-gate array the caller leaves NULL is still produced on the device and is not copied. */
+#define CPOL_COMP_FIELDS 9
+#define CPOL_COMP_MAX_THRESHOLDS 4
+enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4 };
+typedef struct cpol_composite {
+    uint32_t fields;            /* bit k: field k composed                                                         */
+    int32_t  phase;             /* bit 0 begins the pass, bit 1 finishes it                                        */
+    uint32_t products;          /* CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP                           */
+    int32_t  rays_per_block;    /* 0: one block of all rows; else divides the rows of the call                     */
+    int32_t  n_x, n_y;          /* cells east and north                                                            */
+    int32_t  use_slab;          /* 0: every height counts; else [h_lo, h_hi)                                       */
+    int32_t  n_thresholds[CPOL_COMP_FIELDS];    /* echo-top planes of field k                                      */
+    double   h_lo, h_hi;        /* rounded once to float32                                                         */
+    double   thresholds[CPOL_COMP_FIELDS][CPOL_COMP_MAX_THRESHOLDS];    /* the field's own linear units            */
+    const double *edges_x, *edges_y;            /* [n_x + 1], [n_y + 1]                                            */
+    const double *ray_sin, *ray_cos;            /* [n_rays]: sine and cosine of each ray's azimuth                 */
+    float    *values[CPOL_COMP_FIELDS];         /* [n_blocks][n_planes][n_y][n_x]; read by a finishing call        */
+    uint64_t *count;                            /* [n_blocks][n_requested_fields][n_y][n_x]; likewise              */
+} cpol_composite;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -523,6 +597,8 @@ typedef struct {
     float  *dist, *heights;
     double *model_vars;         /* [n_vars][n_rays*n_gates] (integrate_model)   */
     float  *sz_total;           /* [n_rays*n_gates][12]  (debug / parity)       */
+    cpol_composite *composite;  /* NULL (a zero-initialised struct): off.  Maps of the radar fields above (column maximum, lowest
+                                   gate, echo tops), see cpol_composite */
     cpol_histogram *histogram;  /* NULL (a zero-initialised struct): off.  Counts of the radar fields above over many gates,
                                    see cpol_histogram */
     double *DSPECTRUM;          /* [n_rays*n_gates][n_vbins]  (Doppler scheme 3) */
@@ -934,6 +1010,14 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * host edge and output pointers; blocking; honours h.phase; needs no staged model or tables; cpol_histogram's refusals (Doppler
  * counts as on), and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
  * "histogram_stretch" copies one int32: the gates a workgroup of k_hist owns.
+ * "composite_fields" is the same for the gridded composites: the plan, the placement, k_comp, k_comp_finish and the context's
+ * running state on caller-supplied rows.  dst points to { int32_t n_rows, n_gates, n_rays, lane_form; const float *in[9];
+ * const float *heights, *dist; cpol_composite c; } -- host arrays: `in` in the order of the fields, [n_rows * n_gates] float32,
+ * needed for every requested field; heights and dist [n_rays * n_gates] (n_rays divides n_rows: row r takes row r mod n_rays);
+ * `c` with host edge, ray and output pointers (ray_sin, ray_cos [n_rays]); lane_form 0: the kernel's kept form, 1: lanes that
+ * share a cell combined inside the wavefront, 2: every lane on its own; blocking; honours c.phase; needs no staged model or
+ * tables; cpol_composite's refusals, and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
+ * "composite_stretch" copies one int32: the gates a workgroup of k_comp owns.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 

@@ -1,0 +1,318 @@
+#!/usr/bin/env python
+"""tools/composite_profile.py -- gridded composites against the per-gate hand-over they replace.
+
+Seeded inputs from bench.make_inputs('c2'): the 360 x 500 bench sweep, one lane; wall time per call around BLOCKING calls with
+page-locked outputs (each ends in a device synchronise), in fresh processes that alternate:
+
+  a          simulate_rays: every per-gate array delivered;
+  b          simulate_rays_composite(..., the ZH MAX composite on a 1 km grid of +-150 km): the map alone, no per-gate array;
+  c          the same with keep_gates=True: both;
+  parent_a   (--parent-tree DIR: a checkout of the parent commit with its library built) call (a) with DIR's package: the control
+             for "existing calls did not get slower";
+  vol_dev    the 5-elevation volume through get_PPI_composite: one pass, the map alone;
+  vol_host   the same five sweeps with every per-gate array delivered (get_PPI's lanes), then composite.compose on the host;
+  ens_dev    the --members ensemble (the cube and seeded perturbations, form 'shared'): per-member maps from the device;
+  bench / parent_bench   (--bench) `python bench.py --gpus 1 --steps 20 --warmup 5` of this tree and of DIR: the result line.
+
+The bytes handed over are counted from the arrays of the results (the shared gate coordinates are copied once per table set: not
+counted).  Kernel times come from runs of their own under the profiler,
+    rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/composite_profile.py --worker forms --trace
+(--worker forms: the per-gate arrays of the bench sweep fed to k_comp through the test hook in BOTH lane forms -- lanes that
+share a cell combined inside the wavefront, and every lane on its own -- for the MAX composite and for every product at once);
+pass the kernel statistics files with --kernel-stats NAME=FILE to have k_comp's and k_comp_finish's figures written into the JSON.
+
+NOT measured: several lanes in flight, device-resident outputs, more than one field per call on the single sweep, rays_per_block > 0
+on the single sweep, sub-beam volumes, the ensemble's per-gate hand-over.
+
+  python tools/composite_profile.py --repeat 3 --out profiles/composite_profile.json
+  python tools/composite_profile.py --worker b            (one process, one JSON line)
+"""
+import argparse
+import csv
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GEOM = ('lats', 'lons', 'dist', 'heights')
+N_RAYS = 360
+ELEVATIONS = [1.0, 3.0, 5.0, 8.0, 12.0]
+WORKERS = ('a', 'b', 'c', 'vol_dev', 'vol_host', 'ens_dev', 'forms')
+
+
+def result_bytes(res):
+    """bytes of the arrays a call copied to the host"""
+    if isinstance(res, list):
+        return sum(result_bytes(r) for r in res)
+    keys = list(res.keys())
+    n = 0
+    for k in keys:
+        if k in GEOM or (k == 'mask' and 'mask_sum8' in keys):
+            continue
+        if isinstance(res[k], np.ndarray):
+            n += res[k].nbytes
+    w = res.get('composite', {})
+    for planes in w.get('values', {}).values():
+        n += sum(a.nbytes for a in planes.values())
+    n += sum(a.nbytes for a in w.get('count', {}).values())
+    for s in res.get('sweeps', []):
+        n += result_bytes(s)
+    return int(n)
+
+
+def worker(a):
+    tree = os.path.abspath(a.tree)
+    for p in (tree, os.path.join(tree, 'tools')):
+        sys.path.insert(0, p)
+    import bench
+    from cosmo_pol_amd import RadarOperator
+    conf, hyds, cube, luts = bench.make_inputs('c2')
+    az, el = np.arange(float(N_RAYS)), np.full(N_RAYS, 1.0)
+    grid = (cube['zlevels'], cube['proj_info'], cube['resolution'])
+    op = RadarOperator(config=conf, luts=luts, output_variables='only_radar')
+    if a.worker == 'ens_dev':
+        from timed_profile import perturbed
+        op.load_model_ensemble([cube['data']] + [perturbed(cube['data'], 100 + m) for m in range(1, a.members)], *grid)
+    else:
+        op.load_model_arrays(cube['data'], *grid)
+    spec = None
+    if a.worker != 'a':
+        from cosmo_pol_amd import composite as CP
+        e = CP.grid(150e3, 1e3)
+        spec = CP.Composite('ZH', e, e)
+    if a.worker == 'forms':
+        # both lane forms of k_comp on the bench sweep's own arrays, through the test hook (the kernels alone are of interest)
+        res = op.simulate_rays(az, el)
+        every = CP.Composite('ZH', e, e, products=('max', 'lowest', 'echo_top'), thresholds=CP.from_db([18.0, 35.0]))
+        for _ in range(max(1, a.warmup)):
+            for form in (1, 2):
+                for s in (spec, every):
+                    op._ctx.composite_fields({'ZH': np.array(res['ZH'])}, res['dist'], res['heights'], az, s, lane_form=form)
+        op.close()
+        return
+    if a.worker == 'a':
+        run = lambda: op.simulate_rays(az, el)
+    elif a.worker == 'ens_dev':
+        run = lambda: op.simulate_rays_ensemble_composite(az, el, spec)
+    elif a.worker == 'vol_dev':
+        run = lambda: op.get_PPI_composite(ELEVATIONS, spec, azimuths=az)
+    elif a.worker == 'vol_host':
+        def run():
+            sweeps = [op.simulate_rays(az, np.full(N_RAYS, e_), pinned=True, lane=i % op.lanes) for i, e_ in enumerate(ELEVATIONS)]
+            for i in range(op.lanes):
+                op.wait(i)
+            state = None
+            for s in sweeps:
+                state = CP.compose(spec, {'ZH': s['ZH']}, s['dist'], s['heights'], az, state=state)
+            return {'sweeps': sweeps, 'host_composite': CP.finish(state)}
+    else:
+        run = lambda: op.simulate_rays_composite(az, el, spec, keep_gates=a.worker == 'c')
+    for _ in range(a.warmup):
+        res = run()
+    if a.trace:
+        op.close()
+        return
+    t = []
+    for _ in range(a.steps):
+        t0 = time.perf_counter()
+        res = run()
+        t.append((time.perf_counter() - t0) * 1e3)
+    out = {'call': a.worker, 'n_rays': N_RAYS, 'n_gates': len(op.constants.RANGE_RADAR), 'steps': a.steps,
+           'ms_per_call_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
+           'bytes_handed_over': result_bytes(res)}
+    if a.worker == 'ens_dev':
+        out['members'] = a.members
+    if a.worker.startswith('vol'):
+        out['elevations'] = ELEVATIONS
+    if 'ZH' in res:
+        out['zh_checksum'] = float(np.nansum(res['ZH'], dtype=np.float64))
+    w = res.get('host_composite') or res.get('composite')
+    if w:
+        n, m = w['count']['ZH'], w['values']['ZH']['max']
+        out['counted'] = int(n.sum())
+        out['cells_non_empty'] = int((n > 0).sum())
+        out['cells'] = int(n.size)
+        out['max_checksum'] = float(np.nansum(m, dtype=np.float64))
+    print(json.dumps(out))
+    op.close()
+
+
+def kernel_name(n):
+    """k_comp_finish, k_comp_combined (the wavefront combine), k_comp_per_lane, or the bare name of another kernel"""
+    n = n.split('(')[0]
+    if 'k_comp_finish' in n:
+        return 'k_comp_finish'
+    if 'k_comp' in n:
+        arg = n.split('<', 1)[1] if '<' in n else ''
+        return 'k_comp_combined' if ('true' in arg or '1' in arg) else 'k_comp_per_lane'
+    return n.split('<')[0].strip().split(' ')[-1]
+
+
+def kernel_table_db(path):
+    """the same from the database rocprofv3 writes where it writes no CSV (rocpd: one row per dispatch)"""
+    import sqlite3
+    db = sqlite3.connect(path)
+    cols = [r[1] for r in db.execute('pragma table_info(rocpd_info_kernel_symbol)')]
+    name = 'kernel_name' if 'kernel_name' in cols else [c for c in cols if 'name' in c][0]
+    out = {}
+    for n, t0, t1, grid, wg, lds in db.execute('select s.%s, d.start, d.end, d.grid_size_x, d.workgroup_size_x, d.group_segment_size '
+                                               'from rocpd_kernel_dispatch d join rocpd_info_kernel_symbol s on d.kernel_id = s.id' % name):
+        r = out.setdefault(kernel_name(n), {'calls': 0, 'total_us': 0.0, 'min_us': float('inf'), 'max_us': 0.0})
+        us = (t1 - t0) / 1e3
+        r['calls'] += 1
+        r['total_us'] += us
+        r['min_us'], r['max_us'] = min(r['min_us'], us), max(r['max_us'], us)
+        r['workgroups'], r['lds_bytes'] = grid // max(wg, 1), lds
+    for r in out.values():
+        r['avg_us'] = r['total_us'] / max(1, r['calls'])
+    return out
+
+
+def kernel_table(path):
+    """{kernel: {'calls', 'total_us', 'avg_us', 'min_us', 'max_us'}} from rocprofv3's kernel statistics"""
+    if path.endswith('.db'):
+        return kernel_table_db(path)
+    out = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            name = kernel_name(row.get('Name', ''))
+            if not name:
+                continue
+            r = out.setdefault(name, {'calls': 0, 'total_us': 0.0, 'min_us': float('inf'), 'max_us': 0.0})
+            r['calls'] += int(row['Calls'])
+            r['total_us'] += float(row['TotalDurationNs']) / 1e3
+            r['min_us'] = min(r['min_us'], float(row['MinNs']) / 1e3)
+            r['max_us'] = max(r['max_us'], float(row['MaxNs']) / 1e3)
+    for r in out.values():
+        r['avg_us'] = r['total_us'] / max(1, r['calls'])
+    return out
+
+
+def last_json_line(text):
+    for line in reversed(text.strip().split('\n')):
+        if line.startswith('{'):
+            return json.loads(line)
+    raise RuntimeError('no JSON line in:\n' + text[-2000:])
+
+
+def inside(x, y):
+    """each median inside the other's run-to-run range"""
+    return bool(min(y) <= float(np.median(x)) <= max(y) and min(x) <= float(np.median(y)) <= max(x))
+
+
+def driver(a):
+    here = os.path.abspath(__file__)
+    tags = ['a', 'b', 'c', 'vol_dev', 'vol_host']
+    if a.parent_tree:
+        tags.insert(1, 'parent_a')
+    if a.members:
+        tags += ['ens_dev']
+    if a.bench:
+        tags += ['bench'] + (['parent_bench'] if a.parent_tree else [])
+    if a.calls:
+        tags = [t for t in a.calls.split(',') if t and t != 'none']       # (none: only --kernel-stats, with --update)
+    runs = {t: [] for t in tags}
+    common = ['--steps', str(a.steps), '--warmup', str(a.warmup), '--members', str(a.members or 0)]
+    for rep in range(a.repeat):
+        for tag in tags:
+            tree = os.path.abspath(a.parent_tree) if tag.startswith('parent_') else ROOT
+            if tag.endswith('bench'):
+                cmd = [sys.executable, os.path.join(tree, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5']
+            else:
+                cmd = [sys.executable, here, '--worker', tag.replace('parent_', ''), '--tree', tree] + common
+            r = subprocess.run(cmd, cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.process_timeout)
+            if r.returncode != 0:
+                raise SystemExit('composite_profile: %s ended with %d:\n%s' % (tag, r.returncode, r.stdout[-3000:]))
+            rec = last_json_line(r.stdout)
+            runs[tag].append(rec)
+            if tag.endswith('bench'):
+                print('rep %d  %-12s value %.4e gates/s, %.4f ms per step' % (rep, tag, rec['value'], rec['ms_per_step']), flush=True)
+            else:
+                print('rep %d  %-12s %.4f ms per call (min %.4f, max %.4f)' % (rep, tag, rec['ms_per_call_median'], rec['ms_min'],
+                                                                              rec['ms_max']), flush=True)
+    result = {'workload': 'bench.make_inputs(c2): %d rays x 500 gates, one lane; the volume: elevations %s' % (N_RAYS, ELEVATIONS),
+              'method': 'blocking calls with page-locked outputs, %d steps after %d warm-up calls per process, %d fresh processes per '
+                        'call, alternating' % (a.steps, a.warmup, a.repeat),
+              'not_measured': 'several lanes in flight, device-resident outputs, more than one field per call on the single sweep, '
+                              "rays_per_block > 0 on the single sweep, sub-beam volumes, the ensemble's per-gate hand-over",
+              'calls': {}}
+    for tag, recs in runs.items():
+        if tag.endswith('bench'):
+            v = [r['value'] for r in recs]
+            result['calls'][tag] = {'value_median': float(np.median(v)), 'values': v, 'ms_per_step': [r['ms_per_step'] for r in recs],
+                                    'spread': float((max(v) - min(v)) / np.median(v))}
+            continue
+        med = [r['ms_per_call_median'] for r in recs]
+        c = {'ms_per_call_median_of_processes': float(np.median(med)), 'ms_per_call_medians': med,
+             'spread': float((max(med) - min(med)) / np.median(med))}
+        for k in ('bytes_handed_over', 'zh_checksum', 'max_checksum', 'counted', 'cells_non_empty', 'cells', 'members', 'elevations'):
+            if k in recs[0]:
+                c[k] = recs[0][k]
+        result['calls'][tag] = c
+    if a.update and a.out and os.path.exists(a.out):
+        # a second session of the driver (another list of --calls): its calls and kernel tables join the file's
+        with open(a.out) as f:
+            old = json.load(f)
+        old['calls'].update(result['calls'])
+        old['method'] = result['method'] if old.get('method') == result['method'] else old.get('method', '') + '; ' + result['method']
+        result = old
+    calls = result['calls']
+    ms = lambda tag: calls[tag]['ms_per_call_median_of_processes']       # noqa: E731
+    if all(t in calls for t in ('a', 'b', 'c')):
+        result['b_over_a_ms'] = ms('b') / ms('a')
+        result['c_over_a_ms'] = ms('c') / ms('a')
+        result['bytes_a_over_b'] = calls['a']['bytes_handed_over'] / calls['b']['bytes_handed_over']
+    if 'vol_dev' in calls and 'vol_host' in calls:
+        result['vol_dev_over_vol_host_ms'] = ms('vol_dev') / ms('vol_host')
+        result['vol_maps_equal'] = bool(calls['vol_dev'].get('max_checksum') == calls['vol_host'].get('max_checksum')
+                                        and calls['vol_dev'].get('counted') == calls['vol_host'].get('counted'))
+    if 'parent_a' in calls and 'a' in calls:
+        ca, pa = calls['a'], calls['parent_a']
+        result['control_sweep'] = {'a_over_parent_a_ms': ms('a') / ms('parent_a'),
+                                   'each_median_inside_the_others_range': inside(ca['ms_per_call_medians'], pa['ms_per_call_medians']),
+                                   'checksum_equal': bool(pa.get('zh_checksum') == ca.get('zh_checksum'))}
+    if 'parent_bench' in calls and 'bench' in calls:
+        b, pb = calls['bench'], calls['parent_bench']
+        result['control_bench'] = {'value_over_parent': b['value_median'] / pb['value_median'],
+                                   'each_median_inside_the_others_range': inside(b['values'], pb['values'])}
+    for item in a.kernel_stats or []:
+        name, path = item.split('=', 1)
+        tb = kernel_table(path)
+        result.setdefault('kernels', {})[name] = {k: tb.get(k) for k in ('k_comp_combined', 'k_comp_per_lane', 'k_comp_finish')}
+    line = json.dumps(result, indent=1, sort_keys=True)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write(line + '\n')
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--worker', choices=WORKERS, default=None, help='one process of one call: prints one JSON line')
+    ap.add_argument('--tree', default=ROOT, help='with --worker: the checkout whose package and bench inputs are used')
+    ap.add_argument('--trace', action='store_true', help='with --worker: the warm-up calls alone, for rocprofv3 --kernel-trace')
+    ap.add_argument('--steps', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--members', type=int, default=21, help='members of the ensemble call (0: none)')
+    ap.add_argument('--repeat', type=int, default=3, help='fresh processes per call')
+    ap.add_argument('--calls', default=None, help='the calls of this session of the driver, comma-separated (default: all that apply)')
+    ap.add_argument('--update', action='store_true', help='join the calls of this session to those --out already holds')
+    ap.add_argument('--bench', action='store_true', help="bench.py's result line too (of the parent tree as well)")
+    ap.add_argument('--process-timeout', type=float, default=400.0)
+    ap.add_argument('--parent-tree', default=None, help='a checkout of the parent commit with its library built')
+    ap.add_argument('--kernel-stats', action='append', default=None, metavar='NAME=FILE')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    if a.worker:
+        worker(a)
+    else:
+        driver(a)
+
+
+if __name__ == '__main__':
+    main()
