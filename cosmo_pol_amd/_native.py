@@ -4,6 +4,7 @@ There is NO CPU fallback: if the HIP library is missing or fails to load the
 import raises, and every entry point raises on a non-zero status.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -545,6 +546,26 @@ class PinnedPool(object):
         for a in blocks:
             self.lib.cpol_host_free(None, C.c_void_p(a))
         self._free_returned()
+
+
+_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2, np.uint64: 8}
+
+
+def carve_block(pool, spec, writer=None):
+    """`spec` [(key, dtype, shape), ...] -> (views, addresses, holder): one block of `pool` (`take`) cut into 64-byte
+    aligned arrays, in the order of `spec`.  Every host output of a call is such a view: the kernels write a device image
+    of the block and a single device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
+    returns to the pool when the last of them is dropped, whatever happens to the lanes or the operator in between."""
+    counts = [math.prod(sh) for _, _, sh in spec]
+    sizes = [-(-n_el * _ITEMSIZE[dt] // 64) * 64 for n_el, (_, dt, _) in zip(counts, spec)]
+    slab, holder = pool.take(sum(sizes), writer=writer)
+    base = slab.ctypes.data               # (base + off = the view's .ctypes.data, without an interface object per array)
+    views, addresses, off = [], [], 0
+    for (_, dt, sh), n_el, nb in zip(spec, counts, sizes):
+        views.append(slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh))
+        addresses.append(base + off)
+        off += nb
+    return views, addresses, holder
 
 
 class Context(object):

@@ -44,6 +44,8 @@ THE RULE
              workgroups."""
 import numpy as np
 
+from .histogram import Counts
+
 FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V')
 PRODUCTS = ('max', 'lowest', 'echo_top')             # bit 0, 1, 2 of cpol_composite.products
 MAX_EDGES = 1024                 # n + 1 of either axis
@@ -337,3 +339,62 @@ def finish(state):
         out['values'][k] = planes
         out['count'][k] = st['count'].reshape(sh).copy()
     return out
+
+
+class Maps(object):
+    """The composite of ONE sweep call, as RadarOperator._run_rays takes a product ("How a product plugs into a
+    sweep call"): this call's gates folded into the lane's running composite.  `phase` and `rays_per_block` may be set anew
+    between the calls of a pass; the maps arrive with a finishing call (phase bit 1)."""
+    name = 'composite'
+    spectrum, model_var = True, None
+    refuses = Counts.refuses              # (the two reductions over gates refuse the same calls)
+
+    def __init__(self, spec, keep_gates=False, phase=3, rays_per_block=0, distributed=False):
+        # what a composite call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        # themselves: they take ground radars; a spaceborne call, per-ray radar positions, is refused by the library.)
+        if not isinstance(spec, Composite):
+            raise ValueError('spec: a cosmo_pol_amd.composite.Composite, got %r' % (spec,))
+        if distributed:
+            raise NotImplementedError('composites with a process group: sharding rays over ranks is not built')
+        self.spec, self.gates, self.phase, self.rays_per_block = spec, bool(keep_gates), int(phase), int(rays_per_block)
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        self.n_rows = len(az) * (n_members or 1)
+        n_blocks(self.n_rows, self.rays_per_block)            # (ValueError: the library refuses the same)
+        # (sine and cosine of the azimuths come from here: the library computes neither)
+        self.c, keep = native.Context.composite_struct(self.spec, self.phase, self.rays_per_block, azimuths=az)
+        return {'composite': self.c}, keep
+
+    def arrays(self):
+        # the maps, in the sweep's own block: they ride the one copy
+        if not self.phase & 2:
+            return []
+        return ([(k, np.float32, shape(self.spec, k, self.n_rows, self.rays_per_block)) for k in self.spec.fields]
+                + [('count', np.uint64, count_shape(self.spec, self.n_rows, self.rays_per_block))])
+
+    def bind(self, path, address):
+        if path == 'count':
+            self.c.count = address
+        else:
+            self.c.values[FIELDS.index(path)] = address
+
+    def bind_device(self, entry):         # {'values': {field: device pointer of its float32 planes}, 'count': device pointer}
+        for k, ptr in (entry.items() if self.phase & 2 else ()):
+            if k not in ('values', 'count'):
+                raise ValueError("device_outputs['composite']: unknown entry %r" % (k,))
+            for f, q in (ptr.items() if k == 'values' else (('count', ptr),)):
+                self.bind(f, q)
+
+    def finish(self, w, coords):
+        spec, cnt = self.spec, w.pop('count')
+        return {'values': {k: {q: w[k][:, j] for j, q in enumerate(spec.planes(k))} for k in spec.fields},
+                'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}, 'x_edges': spec.x_edges, 'y_edges': spec.y_edges}
+
+    def join(self, parts, cat):
+        """The chunks of an ensemble call: one map per member (rays_per_block set) -> the blocks joined; else the chunks were
+        one pass and the last call holds its maps."""
+        out = dict(parts[-1])
+        if self.rays_per_block:
+            out['values'] = {k: {q: cat([w['values'][k][q] for w in parts]) for q in self.spec.planes(k)} for k in self.spec.fields}
+            out['count'] = {k: cat([w['count'][k] for w in parts]) for k in self.spec.fields}
+        return out

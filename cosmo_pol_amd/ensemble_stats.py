@@ -52,6 +52,7 @@ MAX_QUANTILES = 8
 MAX_QUANTILE_MEMBERS = 128
 METHODS = ('linear', 'lower', 'higher', 'nearest')      # cpol_member_stats.quantile_method, in this order
 KINDS = ('mean', 'spread', 'min', 'max')
+VERIFY_OUTPUTS = ('below', 'equal', 'crps')             # what a verification adds (ensemble_verify.py)
 
 
 def dtype_of(field):
@@ -355,3 +356,98 @@ def probability(stats, field, of='members'):
         return k / float(stats['n_members'])
     with np.errstate(invalid='ignore', divide='ignore'):
         return k / stats['count'][field].astype(np.float64)
+
+
+class Fold(object):
+    """The ensemble statistics -- quantiles and verification with them: one struct pair, one pass -- of ONE sweep call, as
+    RadarOperator._run_rays takes a product ("How a product plugs into a sweep call"): this call's member(s) folded
+    into the lane's running statistics.  `phase` is set anew for every call of a pass (bit 0 begins it, bit 1 finishes it: the
+    statistics arrive with that call); `capacity`: the members of the whole pass; `observations`: the finishing call's, for a
+    verification ({field: [n_rays, n_gates]}, as ensemble_verify.check_observations hands them back)."""
+    name = 'stats'
+    spectrum, model_var = True, None
+    over_members = True                   # (an ensemble call: its chunks form one pass, and only the last holds the result)
+    refuses = dict.fromkeys(('timed', 'subbeams'),
+                            'ensemble statistics are taken by the ensemble sweeps, not by time-blended or sub-beam calls')
+
+    def __init__(self, spec, keep_members=False, phase=3, capacity=None, observations=None):
+        self.quantiles = getattr(spec, 'quantiles', None) or {}
+        self.verify = getattr(spec, 'verify', None) or ()
+        n = capacity or 0
+        # (before anything runs: the device keeps every member of a field with quantiles, and likewise of a verified field,
+        # until the pass finishes)
+        if self.quantiles and n > MAX_QUANTILE_MEMBERS:
+            raise ValueError('ensemble quantiles: at most %d members in a pass' % MAX_QUANTILE_MEMBERS)
+        if self.verify and n > MAX_QUANTILE_MEMBERS:
+            raise ValueError('ensemble verification: at most %d members in a pass' % MAX_QUANTILE_MEMBERS)
+        if n > MAX_MEMBERS:
+            raise ValueError('ensemble statistics: at most %d members in a pass' % MAX_MEMBERS)
+        self.spec, self.gates, self.phase, self.capacity, self.observations = spec, bool(keep_members), int(phase), capacity, observations
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        self.names = self.spec.resolve([k for k in FIELDS if k != 'RVEL' or doppler])
+        self.ms, keep = native.Context.member_stats_struct(self.spec, self.names, self.phase, capacity=self.capacity)
+        structs = {'member_stats': self.ms}
+        self.gshape = (len(az), n_gates)          # (per gate, whatever the number of members)
+        if self.verify:                           # (fields and fair go with every call of the pass)
+            self.mv = structs['member_verify'] = native.Context.member_verify_struct(self.spec)
+            if self.phase & 2 and take is not None:
+                # ... and the observations in a page-locked block of their own, which the device reads in place.  (A clean
+                # block: no writer is named, so none whose last copy may still be in flight -- the host writes it now.)
+                views, addresses = take([(k, dtype_of(k), self.gshape) for k in self.verify])
+                for k, v, a in zip(self.verify, views, addresses):
+                    v[...] = self.observations[k]
+                    self.bind(('obs', k), a)
+                keep = keep + views               # (the block: k_member_verify reads it until this call is done)
+        return structs, keep
+
+    def arrays(self):
+        # the statistics, in the sweep's own block: they ride the one copy
+        if not self.phase & 2:
+            return []
+        spec, names, g = self.spec, self.names, self.gshape
+        out = [((kind, k), dtype_of(k), g) for kind in spec.kinds for k in names]
+        out.append(('count', np.uint16, (len(FIELDS),) + g))
+        out += [(('exceed', k), np.uint16, (len(spec.exceed[k]),) + g) for k in names if k in spec.exceed]
+        out += [(('quantile', k), dtype_of(k), (len(self.quantiles[k]),) + g) for k in names if k in self.quantiles]
+        for k in self.verify:
+            out += [(('below', k), np.uint16, g), (('equal', k), np.uint16, g), (('crps', k), dtype_of(k), g)]
+        return out
+
+    def bind(self, path, address):
+        if path == 'count':
+            self.ms.count = address
+        else:                             # (the verification: observations in, ranks and CRPS out -- the second struct)
+            kind, k = path
+            getattr(self.mv if kind in ('obs',) + VERIFY_OUTPUTS else self.ms, kind)[FIELDS.index(k)] = address
+
+    def bind_device(self, entry):
+        # {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': pointer}; with a
+        # verification also 'obs' | 'below' | 'equal' | 'crps': {field: device pointer}
+        for kind, ptrs in (entry.items() if self.phase & 2 else ()):
+            if kind == 'count':
+                self.bind(kind, ptrs)
+                continue
+            if kind in ('obs',) + VERIFY_OUTPUTS:
+                if not self.verify:
+                    raise ValueError("device_outputs['stats'][%r] without an EnsembleVerification" % (kind,))
+            elif kind not in KINDS + ('exceed', 'quantile'):
+                raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
+            for k, ptr in ptrs.items():
+                self.bind((kind, k), ptr)
+
+    def finish(self, views, coords):
+        cnt = views.pop('count')
+        w = {}
+        for (kind, k), a in views.items():
+            (w.setdefault('verify', {}) if kind in VERIFY_OUTPUTS else w).setdefault(kind, {})[k] = a
+        w['count'] = {k: cnt[FIELDS.index(k)] for k in self.names}
+        w.setdefault('exceed', {})
+        if self.quantiles:
+            w.setdefault('quantile', {})
+        if self.capacity is not None:
+            w['n_members'] = self.capacity
+        return w
+
+    def join(self, parts, cat):
+        return parts[-1]                  # (one pass: the finishing call holds the statistics)

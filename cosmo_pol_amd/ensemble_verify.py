@@ -38,7 +38,7 @@ from . import ensemble_stats as ES
 
 FIELDS = ES.FIELDS
 MAX_MEMBERS = ES.MAX_QUANTILE_MEMBERS
-OUTPUTS = ('below', 'equal', 'crps')
+OUTPUTS = ES.VERIFY_OUTPUTS
 
 
 class EnsembleVerification(ES.EnsembleQuantiles):

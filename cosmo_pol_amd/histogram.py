@@ -228,3 +228,60 @@ def frequencies(counts):
     tot = c.sum(axis=-1, keepdims=True)
     with np.errstate(invalid='ignore', divide='ignore'):
         return np.where(tot > 0, c / tot, np.nan)
+
+
+class Counts(object):
+    """The histogram of ONE sweep call, as RadarOperator._run_rays takes a product ("How a product plugs into a
+    sweep call"): this call's gates counted into the lane's running histogram.  `phase` and `rays_per_block` may be set anew
+    between the calls of a pass; the counts arrive with a finishing call (phase bit 1)."""
+    name = 'histogram'
+    spectrum = True
+    refuses = {'subbeams': 'histograms and composites do not share a call with superobservations, ensemble statistics, '
+                           'spectrum moments or the sub-beam export',
+               'groups': 'a histogram or composite call needs one group (cut the rays and fold the calls into one pass with '
+                         'phase=)'}
+
+    def __init__(self, spec, keep_gates=False, phase=3, rays_per_block=0, doppler=True, distributed=False):
+        # what a histogram call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        # themselves: they take ground radars.)
+        if not isinstance(spec, Histogram):
+            raise ValueError('hist: a cosmo_pol_amd.histogram.Histogram, got %r' % (spec,))
+        if distributed:
+            raise NotImplementedError('histograms with a process group: sharding rays over ranks is not built')
+        if ('RVEL' in spec.fields or spec.ordinate == 'RVEL') and not doppler:
+            raise ValueError('histogram: RVEL needs a Doppler scheme')
+        self.spec, self.gates, self.phase, self.rays_per_block = spec, bool(keep_gates), int(phase), int(rays_per_block)
+        # an ordinate ('model', name): the library integrates the model variables for it, asked for or not
+        self.model_var = spec.ordinate[1] if isinstance(spec.ordinate, tuple) else None
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        self.n_rows = len(az) * (n_members or 1)
+        n_blocks(self.n_rows, self.rays_per_block)            # (ValueError: the library refuses the same)
+        self.h, keep = native.Context.histogram_struct(
+            self.spec, self.phase, self.rays_per_block,
+            model_index=staged_vars.index(self.model_var) if self.model_var is not None else None)
+        return {'histogram': self.h}, keep
+
+    def arrays(self):
+        # the counts, in the sweep's own block: they ride the one copy
+        return ([(k, np.uint64, shape(self.spec, k, self.n_rows, self.rays_per_block)) for k in self.spec.fields]
+                if self.phase & 2 else [])
+
+    def bind(self, path, address):
+        self.h.counts[FIELDS.index(path)] = address
+
+    def bind_device(self, entry):         # {field: device pointer of its uint64 counts}
+        for k, ptr in (entry.items() if self.phase & 2 else ()):
+            self.bind(k, ptr)
+
+    def finish(self, w, coords):
+        return {'counts': w, 'edges': {k: self.spec.edges[k] for k in self.spec.fields},
+                'ordinate_edges': self.spec.ordinate_edges}
+
+    def join(self, parts, cat):
+        """The chunks of an ensemble call: one histogram per member (rays_per_block set) -> the blocks joined; else the
+        chunks were one pass and the last call holds its counts."""
+        out = dict(parts[-1])
+        if self.rays_per_block:
+            out['counts'] = {k: cat([q['counts'][k] for q in parts]) for k in self.spec.fields}
+        return out

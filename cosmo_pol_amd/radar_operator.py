@@ -15,7 +15,6 @@ import copy
 import datetime
 from collections.abc import MutableMapping
 import ctypes as C
-import math
 import os
 import threading
 
@@ -38,8 +37,10 @@ from .lut import load_all_lut
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
 DOPPLER_FIELDS = ['RVEL', 'DSPECTRUM']
 _DB_FIELDS = ('ZDR', 'ZV', 'ZH')
-_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2, np.uint64: 8}
-_PRODUCT_OUTPUTS = frozenset(('histogram', 'composite', 'stats', 'moments', 'superob'))     # entries of device_outputs that are dicts of a product
+# entries of device_outputs that are dicts of a product (`product.name`), and what such an entry lacks without its product
+_PRODUCT_OUTPUTS = {'histogram': 'a histogram', 'composite': 'a composite', 'stats': 'ensemble statistics', 'moments': 'moments=',
+                    'superob': 'superob='}
+_COORDS = ('lats', 'lons', 'dist', 'heights')
 
 
 class ModelVar(object):
@@ -827,8 +828,8 @@ class RadarOperator(object):
         The other keywords: as for simulate_rays.  (A method of its own: the keyword list of simulate_rays is pinned.)
         NotImplementedError with a process group (windows would cross the ray shards) and for spaceborne geometry."""
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
-                                   paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
-                                   rays_per_block=rays_per_block)
+                                   paths=paths, lane=lane, pinned=pinned,
+                                   product=SO.Windows(superob, keep_gates, rays_per_block, self.distributed))
 
     def simulate_rays_moments(self, azimuths, elevations, moments, keep_spectrum=False, device_outputs=None,
                               apply_sensitivity=True, paths=None, lane=0, pinned=False):
@@ -841,26 +842,12 @@ class RadarOperator(object):
         the requested fields are written), 'count': device pointer}.  The other keywords: as for simulate_rays.  (A method
         of its own: the keyword list of simulate_rays is pinned.)  ValueError when the configured Doppler scheme is not 3;
         NotImplementedError with a process group and for spaceborne geometry."""
-        self._moments_check(moments)
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
-                                   paths=paths, lane=lane, pinned=pinned, moments=moments, keep_spectrum=keep_spectrum)
-
-    def _moments_check(self, moments):
-        """What a spectrum-moments call refuses before it builds anything."""
-        if not isinstance(moments, SM.SpectrumMoments):
-            raise ValueError('moments: a cosmo_pol_amd.spectrum_moments.SpectrumMoments, got %r' % (moments,))
-        if self.__config['doppler']['scheme'] != 3:
-            raise ValueError('spectrum moments need the Doppler spectrum: doppler scheme 3, configured is %r'
-                             % (self.__config['doppler']['scheme'],))
-        if self.distributed:
-            raise NotImplementedError('spectrum moments with a process group: the distributed scans collect no moments')
+                                   paths=paths, lane=lane, pinned=pinned,
+                                   product=SM.Rows(moments, keep_spectrum, self.__config['doppler']['scheme'], self.distributed))
 
     def _simulate_rays(self, azimuths, elevations, device_outputs=None, apply_sensitivity=True, paths=None, lane=0, pinned=False,
-                       superob=None, keep_gates=False, rays_per_block=0, moments=None, keep_spectrum=False, histogram=None):
-        if superob is not None:
-            self._superob_check(superob)
-        if moments is not None:
-            self._moments_check(moments)
+                       product=None):
         conf = self.__config
         coords = conf['radar']['coords']
         if coords[2] > K.MAX_MODEL_HEIGHT:
@@ -882,8 +869,7 @@ class RadarOperator(object):
         mode = N.GEOM_GROUND_43 if paths is None else N.GEOM_HOST_PATHS
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
-                              paths=paths, lane=lane, pinned=pinned, superob=superob, keep_gates=keep_gates,
-                              rays_per_block=rays_per_block, moments=moments, keep_spectrum=keep_spectrum, histogram=histogram)
+                              paths=paths, lane=lane, pinned=pinned, product=product)
 
     def stencil_state(self, lane=0):
         """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
@@ -1184,14 +1170,8 @@ class RadarOperator(object):
             if want_model:
                 spec.append(('model_vars', np.float64, (len(names),) + shape))
             if pinned:
-                counts = [math.prod(sh) for _, _, sh in spec]
-                sizes = [-(-n_el * _ITEMSIZE[dt] // 64) * 64 for n_el, (_, dt, _) in zip(counts, spec)]
-                slab, holder = self._pool.take(sum(sizes), writer=self._lane(lane))
-                off = 0
-                for (k, dt, sh), n_el, nb in zip(spec, counts, sizes):
-                    res[k] = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
-                    off += nb
-                del slab
+                views, _, holder = N.carve_block(self._pool, spec, writer=self._lane(lane))
+                res = {k: a for (k, _, _), a in zip(spec, views)}
             else:
                 res = {k: np.empty(sh, dtype=dt) for k, dt, sh in spec}
             for k, v in res.items():
@@ -1237,46 +1217,18 @@ class RadarOperator(object):
 
     def _run_rays(self, azimuths, elevations, coords, n_gates, range0, mode, device_outputs=None,
                   apply_sensitivity=True, paths=None, site=None, sub=None, tables=None, lane=0,
-                  pinned=False, subbeams=None, members=None, timed=None, superob=None, keep_gates=False, rays_per_block=0,
-                  member_stats=None, moments=None, keep_spectrum=False, histogram=None):
+                  pinned=False, subbeams=None, members=None, timed=None, product=None):
+        """`product`: what is computed on the device behind the sweep and handed back beside it -- or instead of it -- under
+        res[product.name]: a product object ("How a product plugs into a sweep call"), built, and its spec checked,
+        by the public method.  The plain call pays one test for all of them."""
         if self._model_staged:
             self._sync_edr()
-        if superob is not None:
-            self._superob_check(superob)
-        if moments is not None:
-            self._moments_check(moments)
-            if superob is not None or member_stats is not None or members is not None or timed is not None or subbeams is not None:
-                raise ValueError('spectrum moments are taken by the plain sweeps: no superobservations, ensembles, time blend '
-                                 'or sub-beam calls')
-        if member_stats is not None:
-            # (spec, phase, keep_members[, members of the whole pass]): this call's member(s) folded into the lane's running
-            # ensemble statistics
-            ms_spec, ms_phase, ms_keep = member_stats[:3]
-            ms_capacity = member_stats[3] if len(member_stats) > 3 else None
-            ms_obs = member_stats[4] if len(member_stats) > 4 else None      # {field: [n_rays, n_gates]}: the finishing call's
-            ms_q = getattr(ms_spec, 'quantiles', None) or {}
-            ms_v = getattr(ms_spec, 'verify', None) or ()
-            if superob is not None:
-                raise ValueError('ensemble statistics and superobservations do not share a call '
-                                 '(statistics of window averages are left to the host)')
-            if timed is not None or subbeams is not None:
-                raise ValueError('ensemble statistics are taken by the ensemble sweeps, not by time-blended or sub-beam calls')
-        hg_spec = cp_spec = None
-        if histogram is not None:
-            # (spec, phase, rays_per_block, keep_gates): this call's gates counted into the lane's running histogram -- or, with a
-            # composite.Composite as spec, folded into the lane's running composite.  (The two reductions over gates never share a
-            # call and ride ONE argument, so that the plain call pays one test for both.)
-            hg_spec, hg_phase, hg_rpb, hg_keep = histogram
-            if isinstance(hg_spec, CP.Composite):
-                cp_spec = hg_spec
-                self._composite_check(cp_spec)    # (a spaceborne call, per-ray radar positions, is refused by the library)
-            else:
-                self._histogram_check(hg_spec)
-            if superob is not None or member_stats is not None or moments is not None or subbeams is not None:
-                raise ValueError('histograms and composites do not share a call with superobservations, ensemble statistics, '
-                                 'spectrum moments or the sub-beam export')
-        # the per-gate radar fields travel to the host
-        gates = (superob is None or keep_gates) and (member_stats is None or ms_keep) and (hg_spec is None or hg_keep)
+        gates = True                              # the per-gate radar fields travel to the host
+        if product is not None:
+            for kind, arg in (('members', members), ('timed', timed), ('subbeams', subbeams)):
+                if arg is not None and kind in product.refuses:
+                    raise ValueError(product.refuses[kind])
+            gates = product.gates
         conf = self.__config
         az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
         el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
@@ -1302,13 +1254,13 @@ class RadarOperator(object):
 
         want_model = self.output_variables in ('all', 'only_model') and members is None and gates
         # a histogram over a model variable: the library integrates the model variables for it, asked for or not
-        hg_model = hg_spec is not None and cp_spec is None and isinstance(hg_spec.ordinate, tuple)
+        hg_model = product is not None and product.model_var is not None
         if hg_model:
             if self.output_variables not in ('all', 'only_model') or members is not None:
                 raise ValueError("histogram: the ordinate %r needs a call that produces model_vars (output_variables 'all' or "
-                                 "'only_model', no ensemble call)" % (hg_spec.ordinate,))
-            if hg_spec.ordinate[1] not in self._staged_vars:
-                raise ValueError('histogram: no staged model variable %r' % (hg_spec.ordinate[1],))
+                                 "'only_model', no ensemble call)" % (('model', product.model_var),))
+            if product.model_var not in self._staged_vars:
+                raise ValueError('histogram: no staged model variable %r' % (product.model_var,))
         integrate = want_model or hg_model
 
         def prepare(paths=paths, site=site):
@@ -1412,103 +1364,29 @@ class RadarOperator(object):
             keep = list(keep) + [tm_lo, tm_w]
         o = N.Outputs()
         res = {}
-        geom = None
-        so = so_rpb = None
-        if superob is not None:
-            # (the library refuses the same: the rows of the call are n_members x n_rays, a block never spans two members)
-            so_rpb = int(rays_per_block) or n_rays
-            if int(rays_per_block) < 0 or n_rays % so_rpb:
-                raise ValueError('rays_per_block %r does not divide the %d rays of the call' % (rays_per_block, n_rays))
-            so = N.Superob()
-            so.ray_window, so.gate_window, so.rays_per_block = superob.rays, superob.gates, so_rpb
-            so.min_valid_fraction = superob.min_valid_fraction
-            o.superob = C.pointer(so)
-            so_fields = [k for k in SO.FIELDS if k != 'RVEL' or doppler]
-        ms = ms_names = mv = o_holder = None
-        if member_stats is not None:
-            ms_names = ms_spec.resolve([k for k in ES.FIELDS if k != 'RVEL' or doppler])
-            ms, ms_thr = N.Context.member_stats_struct(ms_spec, ms_names, ms_phase, capacity=ms_capacity)
-            keep = list(keep) + ms_thr
-            o.member_stats = C.pointer(ms)
-            if ms_v:                              # (fields and fair go with every call of the pass)
-                mv = N.Context.member_verify_struct(ms_spec)
-                o.member_verify = C.pointer(mv)
-        ms_out = ms is not None and bool(ms_phase & 2)      # a finishing call: the statistics arrive with it
-        if ms_out and ms_v and device_outputs is None:
-            ms_obs = EV.check_observations(ms_spec, ms_names, ms_obs, (n_rays, n_gates))
-        sm = None
-        if moments is not None:
-            if not spectrum:                      # (a GPM-type radar: no Doppler whatever the scheme says)
-                raise ValueError('spectrum moments need the Doppler spectrum, and this radar simulates none')
-            sm = N.Context.spectrum_moments_struct(moments)
-            o.spectrum_moments = C.pointer(sm)
-        hg = None
-        if hg_spec is not None:
-            n_rows = n_rays * (len(members) if members is not None else 1)
-            HG.n_blocks(n_rows, hg_rpb)               # (ValueError: the library refuses the same)
-            if cp_spec is not None:               # (sine and cosine of the azimuths come from here: the library computes neither)
-                hg, hg_keepalive = N.Context.composite_struct(cp_spec, hg_phase, hg_rpb, azimuths=az)
-                o.composite = C.pointer(hg)
-            else:
-                hg, hg_keepalive = N.Context.histogram_struct(
-                    hg_spec, hg_phase, hg_rpb, model_index=self._staged_vars.index(hg_spec.ordinate[1]) if hg_model else None)
-                o.histogram = C.pointer(hg)
-            keep = list(keep) + hg_keepalive
-        hg_out = hg is not None and bool(int(hg_phase) & 2)      # a finishing call: the counts arrive with it
+        geom = part = None
+        held = ()                                 # the holders of blocks that the device reads in place during this call
+        if product is not None:
+            held = []
+
+            def take(spec):
+                """A clean block (no writer is named) for arrays of the product that the host writes now."""
+                views, addresses, holder = N.carve_block(self._pool, spec)
+                held.append(holder)
+                return views, addresses
+            structs, alive = product.attach(N, az, n_gates, len(members) if members is not None else None, doppler, spectrum,
+                                            self._staged_vars, take if device_outputs is None else None)
+            for slot, struct in structs.items():
+                setattr(o, slot, C.pointer(struct))
+            keep = list(keep) + alive
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
                 if k not in _PRODUCT_OUTPUTS:     # an array of the sweep itself (one look-up, however many products there are)
                     setattr(o, k, ptr)
-                    continue
-                if k == 'composite':              # {'values': {field: device pointer of its float32 planes}, 'count': device pointer}
-                    if cp_spec is None:
-                        raise ValueError("device_outputs['composite'] without a composite")
-                    for kk, pp in (ptr.items() if hg_out else ()):
-                        if kk == 'count':
-                            hg.count = pp
-                        elif kk == 'values':
-                            for f, q in pp.items():
-                                hg.values[CP.FIELDS.index(f)] = q
-                        else:
-                            raise ValueError("device_outputs['composite']: unknown entry %r" % (kk,))
-                    continue
-                if k == 'histogram':              # {field: device pointer of its uint64 counts}
-                    if hg is None or cp_spec is not None:
-                        raise ValueError("device_outputs['histogram'] without a histogram")
-                    for kk, pp in (ptr.items() if hg_out else ()):
-                        hg.counts[HG.FIELDS.index(kk)] = pp
-                    continue
-                if k == 'stats':                  # {'mean' | 'spread' | 'min' | 'max' | 'exceed' | 'quantile': {field: device pointer}, 'count': pointer}
-                    if ms is None:
-                        raise ValueError("device_outputs['stats'] without ensemble statistics")
-                    for kind, pp in (ptr.items() if ms_out else ()):
-                        if kind == 'count':
-                            ms.count = pp
-                            continue
-                        if kind in ('obs',) + EV.OUTPUTS:     # the verification: observations in, ranks and CRPS out
-                            if not ms_v:
-                                raise ValueError("device_outputs['stats'][%r] without an EnsembleVerification" % (kind,))
-                            for kk, q in pp.items():
-                                getattr(mv, kind)[ES.FIELDS.index(kk)] = q
-                            continue
-                        if kind not in ES.KINDS + ('exceed', 'quantile'):
-                            raise ValueError("device_outputs['stats']: unknown entry %r" % (kind,))
-                        for kk, q in pp.items():
-                            getattr(ms, kind)[ES.FIELDS.index(kk)] = q
-                    continue
-                if k == 'moments':                # {'moments': device pointer of [8, n_rays, n_gates], 'count': device pointer}
-                    if sm is None:
-                        raise ValueError("device_outputs['moments'] without moments=")
-                    for kk, pp in ptr.items():
-                        if kk not in ('moments', 'count'):
-                            raise ValueError("device_outputs['moments']: unknown entry %r" % (kk,))
-                        setattr(sm, kk, pp)
-                    continue
-                if k == 'superob':                # {field or 'count': device pointer}
-                    if so is None:
-                        raise ValueError("device_outputs['superob'] without superob=")
-                    for kk, pp in ptr.items():
-                        setattr(so, kk, pp)
+                elif product is None or product.name != k:
+                    raise ValueError('device_outputs[%r] without %s' % (k, _PRODUCT_OUTPUTS[k]))
+                else:
+                    product.bind_device(ptr)
         else:
             shape = (n_rays, n_gates)
             gshape = shape                        # (gate coordinates: once, whatever the number of members)
@@ -1517,7 +1395,7 @@ class RadarOperator(object):
             spec = [(k, np.float32, shape) for k in RADAR_FIELDS] if gates else []
             if doppler and gates:
                 spec.append(('RVEL', np.float64, shape))
-            if spectrum and gates and (sm is None or keep_spectrum):
+            if spectrum and gates and (product is None or product.spectrum):
                 spec.append(('DSPECTRUM', np.float64, shape + (len(varray),)))
             # (pinned calls only: a blocking call would have to widen the bytes on the caller's thread at once -- ~1 ns per gate,
             # more than the 7 bytes per gate cost on PCIe; measured on the c5 swaths, 1.7 M gates: 8.5 -> 12.7 ms per step)
@@ -1533,88 +1411,19 @@ class RadarOperator(object):
                          ('dist', np.float32, gshape), ('heights', np.float32, gshape)]
             if want_model:
                 spec.append(('model_vars', np.float64, (len(self._staged_vars),) + shape))
-            if so is not None:
-                # the window averages, in the same block: they ride the one copy
-                wshape = SO.shape(n_rays, n_gates, superob, so_rpb)
-                if members is not None:
-                    wshape = (len(members),) + wshape
-                spec += [(('superob', k), np.float64 if k == 'RVEL' else np.float32, wshape) for k in so_fields]
-                spec.append((('superob', 'count'), np.uint16, (len(SO.FIELDS),) + wshape))
-            if sm is not None:
-                # the moments, in the same block: they ride the one copy (rows nobody asked for arrive as zeros)
-                spec.append((('moments', 'moments'), np.float64, (len(SM.FIELDS),) + shape))
-                spec.append((('moments', 'count'), np.uint16, shape))
-            if hg_out:
-                if cp_spec is not None:
-                    # the maps, in the same block: they ride the one copy
-                    spec += [(('composite', k), np.float32, CP.shape(cp_spec, k, n_rows, hg_rpb)) for k in cp_spec.fields]
-                    spec.append((('composite', 'count'), np.uint64, CP.count_shape(cp_spec, n_rows, hg_rpb)))
-                else:
-                    # the counts, in the same block: they ride the one copy
-                    spec += [(('histogram', k), np.uint64, HG.shape(hg_spec, k, n_rows, hg_rpb)) for k in hg_spec.fields]
-            if ms_out:
-                # the statistics, in the same block: they ride the one copy
-                for kind in ms_spec.kinds:
-                    spec += [(('stats', kind, k), ES.dtype_of(k), gshape) for k in ms_names]
-                spec.append((('stats', 'count'), np.uint16, (len(ES.FIELDS),) + gshape))
-                spec += [(('stats', 'exceed', k), np.uint16, (len(ms_spec.exceed[k]),) + gshape) for k in ms_names if k in ms_spec.exceed]
-                spec += [(('stats', 'quantile', k), ES.dtype_of(k), (len(ms_q[k]),) + gshape) for k in ms_names if k in ms_q]
-                for k in ms_v:
-                    spec += [(('stats', 'verify', 'below', k), np.uint16, gshape), (('stats', 'verify', 'equal', k), np.uint16, gshape),
-                             (('stats', 'verify', 'crps', k), ES.dtype_of(k), gshape)]
-                if ms_v:
-                    # ... and the observations in a page-locked block of their own, which the device reads in place.  (A clean
-                    # block: no writer is named, so none whose last copy may still be in flight -- the host writes it now.)
-                    o_sizes = [-(-n_rays * n_gates * _ITEMSIZE[ES.dtype_of(k)] // 64) * 64 for k in ms_v]
-                    o_slab, o_holder = self._pool.take(sum(o_sizes))
-                    o_off = 0
-                    for k, nb in zip(ms_v, o_sizes):
-                        o_slab[o_off:o_off + n_rays * n_gates * _ITEMSIZE[ES.dtype_of(k)]].view(ES.dtype_of(k))[:] = ms_obs[k].reshape(-1)
-                        mv.obs[ES.FIELDS.index(k)] = o_slab.ctypes.data + o_off
-                        o_off += nb
-            # every host output is a view of ONE block of page-locked memory from the operator's pool
-            # (64-byte aligned arrays): the kernels write a device image of the block and a single
-            # device-to-host copy, queued behind them, moves it.  The block belongs to the arrays: it
-            # returns to the pool when the last of them is dropped, whatever happens to the lanes or
-            # the operator in between.
-            counts = [math.prod(sh) for _, _, sh in spec]
-            sizes = [-(-n_el * _ITEMSIZE[dt] // 64) * 64 for n_el, (_, dt, _) in zip(counts, spec)]
-            slab, holder = self._pool.take(sum(sizes), writer=self._lane(lane))
-            base = slab.ctypes.data
-            off = 0
-            for (k, dt, sh), n_el, nb in zip(spec, counts, sizes):
-                a = slab[off:off + n_el * _ITEMSIZE[dt]].view(dt).reshape(sh)
-                if isinstance(k, tuple) and k[0] == 'stats':
-                    if k[1] == 'count':
-                        res.setdefault('stats', {})['count'] = a
-                        ms.count = base + off
-                    elif k[1] == 'verify':
-                        res.setdefault('stats', {}).setdefault('verify', {}).setdefault(k[2], {})[k[3]] = a
-                        getattr(mv, k[2])[ES.FIELDS.index(k[3])] = base + off
-                    else:
-                        res.setdefault('stats', {}).setdefault(k[1], {})[k[2]] = a
-                        getattr(ms, k[1])[ES.FIELDS.index(k[2])] = base + off
-                elif isinstance(k, tuple) and k[0] == 'moments':
-                    res.setdefault('moments', {})[k[1]] = a
-                    setattr(sm, k[1], base + off)
-                elif isinstance(k, tuple) and k[0] == 'histogram':
-                    res.setdefault('histogram', {}).setdefault('counts', {})[k[1]] = a
-                    hg.counts[HG.FIELDS.index(k[1])] = base + off
-                elif isinstance(k, tuple):
-                    if k[0] == 'composite':
-                        res.setdefault('composite', {})[k[1]] = a
-                        if k[1] == 'count':
-                            hg.count = base + off
-                        else:
-                            hg.values[CP.FIELDS.index(k[1])] = base + off
-                    else:
-                        res.setdefault('superob', {})[k[1]] = a
-                        setattr(so, k[1], base + off)
-                else:
-                    res[k] = a
-                    setattr(o, k, base + off)       # (= res[k].ctypes.data, without an interface object per array)
-                off += nb
-            del slab
+            # every host output is a view of ONE block of page-locked memory from the operator's pool (N.carve_block); the
+            # product's arrays lie behind the sweep's own in the same block: they ride the one copy
+            extra = product.arrays() if product is not None else []
+            views, addresses, holder = N.carve_block(self._pool, spec + extra, writer=self._lane(lane))
+            for (k, _, _), a, address in zip(spec, views, addresses):
+                res[k] = a
+                setattr(o, k, address)
+            if extra:
+                part = {}
+                for (k, _, _), a, address in zip(extra, views[len(spec):], addresses[len(spec):]):
+                    part[k] = a
+                    product.bind(k, address)
+            del views
         ctx = self._lane(lane)
         if members is not None:
             ctx.run_sweep_members(p, t, members, o)
@@ -1622,10 +1431,9 @@ class RadarOperator(object):
             ctx.run_sweep_members(p, t, tm_states, o)
         else:
             ctx.run_sweep(p, t, o)
+        for h in held:                            # (the device reads such a block until this call is done)
+            h['ctx'], h['serial'] = ctx, ctx.submitted
         del keep
-        if o_holder is not None:                  # (the observations' block: k_member_verify reads it until this call is done)
-            o_holder['ctx'], o_holder['serial'] = ctx, ctx.submitted
-            del o_slab
         if device_outputs is None and 'mask_sum8' in res:
             # `mask` is made from its one-byte form when it is first read (after wait(lane) for a pinned call, like every
             # other array of the result)
@@ -1643,53 +1451,28 @@ class RadarOperator(object):
                 if pinned:
                     ctx.synchronize()                   # once per table set: the arrays are complete
                 # (own read-only copies: shared by every later result of this table set)
-                geom = {k: res[k].copy() for k in ('lats', 'lons', 'dist', 'heights')}
-                for a in geom.values():
+                made = {k: res[k].copy() for k in _COORDS}
+                for a in made.values():
                     a.flags.writeable = False
-                with self._lock:
-                    old = [k for k in self._cache if isinstance(k, tuple) and k and k[0] == 'geom']
-                    for k in old[:max(0, len(old) - 7)]:
-                        del self._cache[k]
-                    self._cache[gkey] = geom
+                geom = self._cached(gkey, lambda: made, lru=8)
             if geom is not None:
                 res.update(geom)
-            if so is not None:
-                w = res['superob']
-                cnt = w.pop('count')
-                w['count'] = {k: cnt[SO.FIELDS.index(k)] for k in so_fields}
-                if geom is not None:
-                    def window_geom():
+            if part is not None:
+                def coords(key, make):
+                    """Coordinate arrays of the product's own, made of the gate coordinates by make(those)."""
+                    if geom is None:              # (no table version: this call's own coordinate arrays)
+                        if pinned:
+                            ctx.synchronize()
+                        return make(res)
+
+                    def frozen():
                         # (read-only, like the gate coordinates they are made of: shared by every later result of this table set)
-                        made = SO.coordinates(geom, superob, so_rpb)
+                        made = make(geom)
                         for a in made.values():
                             a.flags.writeable = False
                         return made
-                    w.update(self._cached(('superob_geom', gkey, superob.rays, superob.gates, so_rpb), window_geom, lru=16))
-                else:                             # (no table version: this call's own coordinate arrays)
-                    if pinned:
-                        ctx.synchronize()
-                    w.update(SO.coordinates(res, superob, so_rpb))
-        if hg_out and device_outputs is None:
-            if cp_spec is not None:
-                w = res['composite']
-                cnt = w.pop('count')
-                res['composite'] = {'values': {k: {q: w[k][:, j] for j, q in enumerate(cp_spec.planes(k))} for k in cp_spec.fields},
-                                    'count': {k: cnt[:, i] for i, k in enumerate(cp_spec.fields)},
-                                    'x_edges': cp_spec.x_edges, 'y_edges': cp_spec.y_edges}
-            else:
-                res['histogram']['edges'] = {k: hg_spec.edges[k] for k in hg_spec.fields}
-                res['histogram']['ordinate_edges'] = hg_spec.ordinate_edges
-        if sm is not None and device_outputs is None:
-            w = res['moments']
-            rows = w.pop('moments')
-            w.update({k: rows[SM.FIELDS.index(k)] for k in moments.fields})
-        if ms_out and device_outputs is None:
-            w = res['stats']
-            cnt = w.pop('count')
-            w['count'] = {k: cnt[ES.FIELDS.index(k)] for k in ms_names}
-            w.setdefault('exceed', {})
-            if ms_q:
-                w.setdefault('quantile', {})
+                    return self._cached((product.name + '_geom', gkey) + key, frozen, lru=16)
+                res[product.name] = product.finish(part, coords)
         res['n_sub'] = sub.n_sub
         return res
 
@@ -1702,7 +1485,7 @@ class RadarOperator(object):
         if key in c:
             return c[key]
         if lru is not None:
-            old = [k for k in c if isinstance(k, tuple) and k and k[0] == key[0]]
+            old = [k for k in c if k[:1] == key[:1]]
             for k in old[:max(0, len(old) - lru + 1)]:
                 del c[k]
         c[key] = make()
@@ -1798,7 +1581,7 @@ class RadarOperator(object):
         `superob`, `keep_gates`, `rays_per_block`: as for simulate_rays_superob; the arrays of res['superob'] gain the member axis (the
         window coordinates come once).  A window never holds gates of two members."""
         return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned,
-                                   dict(superob=superob, keep_gates=keep_gates, rays_per_block=rays_per_block))
+                                   None if superob is None else SO.Windows(superob, keep_gates, rays_per_block, self.distributed))
 
     def simulate_rays_ensemble_stats(self, azimuths, elevations, stats, members=None, keep_members=False, form=None, lane=0,
                                      pinned=False, device_outputs=None, apply_sensitivity=True):
@@ -1822,8 +1605,9 @@ class RadarOperator(object):
         if isinstance(stats, EV.EnsembleVerification):
             raise ValueError('an EnsembleVerification needs observations: simulate_rays_ensemble_verify(azimuths, elevations, stats, '
                              'observations, ...) takes it')
-        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, {},
-                                   stats=stats, keep_members=keep_members)
+        members = None if members is None else list(members)
+        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned,
+                                   ES.Fold(stats, keep_members, capacity=self.n_members if members is None else len(members)))
 
     def simulate_rays_ensemble_verify(self, azimuths, elevations, stats, observations=None, members=None, keep_members=False, form=None,
                                       lane=0, pinned=False, device_outputs=None, apply_sensitivity=True):
@@ -1852,20 +1636,12 @@ class RadarOperator(object):
                 raise ValueError("with device_outputs the observations are device pointers under device_outputs['stats']['obs']")
             n_rays = len(np.asarray(azimuths).reshape(-1))
             observations = EV.check_observations(stats, stats.verify, observations, (n_rays, len(self.constants.RANGE_RADAR)))
-        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, {},
-                                   stats=stats, keep_members=keep_members, observations=observations)
+        members = None if members is None else list(members)
+        return self._ensemble_rays(azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned,
+                                   ES.Fold(stats, keep_members, capacity=self.n_members if members is None else len(members),
+                                           observations=observations))
 
-    def _ensemble_rays(self, azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, so_kw,
-                       stats=None, keep_members=False, observations=None):
-        superob = so_kw.get('superob')
-        if stats is not None and getattr(stats, 'quantiles', None):
-            # (before anything runs: the device keeps every member of a field with quantiles until the pass finishes)
-            if (self.n_members if members is None else len(list(members))) > ES.MAX_QUANTILE_MEMBERS:
-                raise ValueError('ensemble quantiles: at most %d members in a pass' % ES.MAX_QUANTILE_MEMBERS)
-        if stats is not None and getattr(stats, 'verify', None):
-            # (likewise for a verified field)
-            if (self.n_members if members is None else len(list(members))) > EV.MAX_MEMBERS:
-                raise ValueError('ensemble verification: at most %d members in a pass' % EV.MAX_MEMBERS)
+    def _ensemble_rays(self, azimuths, elevations, members, device_outputs, apply_sensitivity, lane, form, pinned, product=None):
         members = self._members_arg(members)
         conf = self.__config
         coords = self._ensemble_coords()
@@ -1882,58 +1658,50 @@ class RadarOperator(object):
             chunks = self._shared_member_chunks(ctx, members, sub.n_sub * len(rr) * n_rays)
         else:
             chunks = [[m] for m in members]
-        if superob is not None and device_outputs is not None and len(chunks) > 1:
+        # a product over the members: the chunks are ONE pass, and only its last call holds the result; any other comes per member
+        fold = product is not None and product.over_members
+        if product is not None and not fold and device_outputs is not None and len(chunks) > 1:
             raise ValueError('simulate_rays_ensemble: superobservations into device outputs need the members in one chunk')
-        if stats is not None and len(members) > ES.MAX_MEMBERS:
-            raise ValueError('ensemble statistics: at most %d members in a pass' % ES.MAX_MEMBERS)
         parts, done = [], 0
         try:
             for i, chunk in enumerate(chunks):
-                if stats is not None:
+                if fold:
                     # the pass: begun by the first call, finished by the last, every call on this lane
-                    # (the observations of a verification go with the last)
-                    last = i == len(chunks) - 1
-                    so_kw = dict(member_stats=(stats, (1 if i == 0 else 0) | (2 if last else 0), keep_members, len(members),
-                                               observations if last else None))
+                    product.phase = (1 if i == 0 else 0) | (2 if i == len(chunks) - 1 else 0)
                 dev = None
                 if device_outputs is not None:
                     dev = self._offset_outputs(device_outputs, done, n_rays, len(rr))
                 if form == 'per_member':
                     ctx.select_member(chunk[0])
                     r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
-                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned, **so_kw)
+                                       apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned, product=product)
                 else:
                     r = self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43, device_outputs=dev,
                                        apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned and len(chunks) == 1,
-                                       members=chunk, **so_kw)
+                                       members=chunk, product=product)
                 parts.append(r)
                 done += len(chunk)
         finally:
             if form == 'per_member':
                 ctx.select_member(self._member)
-        if stats is not None and 'stats' in parts[-1]:
-            parts[-1]['stats']['n_members'] = len(members)
         if device_outputs is not None:
             return parts[-1]
         if form == 'shared' and len(parts) == 1:
             return parts[0]
-        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
-        if stats is not None and not keep_members:
-            # (no per-member array came: the coordinates of the first call, the statistics of the last)
+        once = _COORDS + ('n_sub',)
+        join = np.stack if form == 'per_member' else np.concatenate
+        if fold and not product.gates:
+            # (no per-member array came: the coordinates of the first call, the result of the last)
             if pinned and len(parts) > 1:
                 self.wait(lane)
-            return dict({k: v for k, v in parts[0].items() if k in once}, stats=parts[-1]['stats'])
-        if pinned:
-            self.wait(lane)                        # (the members are joined on the host: their copies must have landed)
-        join = np.stack if form == 'per_member' else np.concatenate
-        out = {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys() if k not in ('superob', 'stats')}
-        if stats is not None:
-            out['stats'] = parts[-1]['stats']
-        if superob is not None:
-            w0 = parts[0]['superob']
-            out['superob'] = {k: (v if k in once else join([p['superob'][k] for p in parts]))
-                              for k, v in w0.items() if k != 'count'}
-            out['superob']['count'] = {k: join([p['superob']['count'][k] for p in parts]) for k in w0['count']}
+            out = {k: v for k, v in parts[0].items() if k in once}
+        else:
+            if pinned:
+                self.wait(lane)                    # (the members are joined on the host: their copies must have landed)
+            out = {k: (parts[0][k] if k in once else join([p[k] for p in parts])) for k in parts[0].keys()
+                   if product is None or k != product.name}
+        if product is not None:
+            out[product.name] = product.join([p.get(product.name) for p in parts], join)
         return out
 
     def _ensemble_coords(self):
@@ -2077,16 +1845,12 @@ class RadarOperator(object):
         """simulate_rays_at handing back superobservations: `superob`, `keep_gates`, `rays_per_block` as for
         simulate_rays_superob (ValueError when the rays fall into several groups of states: a window would cross them)."""
         return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs,
-                                      apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned, superob=superob,
-                                      keep_gates=keep_gates, rays_per_block=rays_per_block)
+                                      apply_sensitivity=apply_sensitivity, lane=lane, pinned=pinned,
+                                      product=SO.Windows(superob, keep_gates, rays_per_block, self.distributed))
 
     def _simulate_rays_at(self, azimuths, elevations, times, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False,
-                          superob=None, keep_gates=False, rays_per_block=0, histogram=None):
+                          product=None):
         self._timed_check()
-        if superob is not None:
-            self._superob_check(superob)
-        if histogram is not None:
-            (self._composite_check if isinstance(histogram[0], CP.Composite) else self._histogram_check)(histogram[0])
         from . import timeline
         az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
         el = np.asarray(elevations, dtype=np.float64).reshape(-1)
@@ -2103,12 +1867,8 @@ class RadarOperator(object):
         if len(groups) > 1 and device_outputs is not None:
             raise ValueError('simulate_rays_at: the rays read more than %d states; with device outputs split the rays'
                              % N.MEMBERS_PER_CALL)
-        if len(groups) > 1 and superob is not None:
-            raise ValueError('simulate_rays_at: the rays read more than %d states; superobservations need one group'
-                             % N.MEMBERS_PER_CALL)
-        if len(groups) > 1 and histogram is not None:
-            raise ValueError('simulate_rays_at: the rays read more than %d states; a histogram or composite call needs one group (cut the rays '
-                             'and fold the calls into one pass with phase=)' % N.MEMBERS_PER_CALL)
+        if len(groups) > 1 and product is not None:     # (a window, or a block of a pass, would cross the groups)
+            raise ValueError('simulate_rays_at: the rays read more than %d states; %s' % (N.MEMBERS_PER_CALL, product.refuses['groups']))
         coords = self.__config['radar']['coords']
         rr = self.constants.RANGE_RADAR
         parts = []
@@ -2117,8 +1877,7 @@ class RadarOperator(object):
                   np.ascontiguousarray(w[r0:r1], dtype=np.float32))
             parts.append(self._run_rays(az[r0:r1], el[r0:r1], coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
                                         device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
-                                        pinned=pinned and len(groups) == 1, timed=tm, superob=superob, keep_gates=keep_gates,
-                                        rays_per_block=rays_per_block, histogram=histogram))
+                                        pinned=pinned and len(groups) == 1, timed=tm, product=product))
         if len(parts) == 1:
             return parts[0]
         return {k: (v if not isinstance(v, np.ndarray) else
@@ -2193,19 +1952,7 @@ class RadarOperator(object):
             # the copy of one sweep runs beside the kernels of the next (a 5-elevation volume with melting layer: 0.93 ms against
             # 1.37 ms as ONE launch sequence, whose one copy overlaps nothing; bench.py's c3 step / `api_ms`).  Same bits
             # (tests/test_gpu_headline.py::test_c3_step_vs_oracle_and_blocking_path).
-            n_par = min(self.lanes, len(sweeps))
-            res, failure = [], None
-            try:
-                for k, (az, el) in enumerate(sweeps):
-                    res.append(self.simulate_rays(az, el, pinned=True, lane=k % n_par))
-            finally:
-                for i in range(n_par):
-                    try:
-                        self.wait(i)                  # (every lane is drained, whatever happened: no copy may outlive the call)
-                    except Exception as exc:          # noqa: BLE001  (re-raised below: the first failure of the scan)
-                        failure = failure or exc
-            if failure is not None:
-                raise failure
+            res = self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays(az, el, pinned=True, lane=lane))
             return [self._package(r, az, el) for r, (az, el) in zip(res, sweeps)]
         if self.volume_in_one_sequence and len(sweeps) > 1:
             # all sweeps of the scan as ONE launch sequence (rays of different elevations / azimuths in one
@@ -2242,6 +1989,37 @@ class RadarOperator(object):
                 free.put(lane)
         with ThreadPoolExecutor(max_workers=n_par) as pool:
             return list(pool.map(one, sweeps))
+
+    def _over_lanes(self, sweeps, call, n_par=None):
+        """[call(az, el, lane) per sweep]: one pinned call per sweep, queued over `n_par` lanes (None: all the operator has),
+        and one wait per lane at the end.  Every lane is drained whatever happened; the first failure is re-raised."""
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        if n_par is None:
+            n_par = max(1, min(self.lanes, len(sweeps)))
+        res, failure = [], None
+        try:
+            for k, (az, el) in enumerate(sweeps):
+                res.append(call(az, el, k % n_par))
+        finally:
+            for i in range(n_par):
+                try:
+                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
+                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
+                    failure = failure or exc
+        if failure is not None:
+            raise failure
+        return res
+
+    def _pass_over_sweeps(self, name, sweeps, call, per_sweep):
+        """The sweeps of a scan reduced by call(az, el, phase, lane): per sweep (a list of results, the sweeps spread over the
+        lanes), or all folded into ONE pass -- begun by the first sweep, finished by the last -- which stays on lane 0 as
+        the statistics' passes stay on theirs: {name: the pass's result, 'sweeps': [what each call returned]}."""
+        if per_sweep:
+            return self._over_lanes(sweeps, lambda az, el, lane: call(az, el, 3, lane))
+        phases = iter([(1 if k == 0 else 0) | (2 if k == len(sweeps) - 1 else 0) for k in range(len(sweeps))])
+        res = self._over_lanes(sweeps, lambda az, el, lane: call(az, el, next(phases), lane), n_par=1)
+        return {name: res[-1].pop(name), 'sweeps': res}
 
     def _sweep_groups(self, sweeps):
         """Consecutive sweeps whose launch sequence fits the memory budget (at least one sweep per group).  (`free` counts
@@ -2434,33 +2212,11 @@ class RadarOperator(object):
                                            self.constants.RANGE_RADAR, self.get_pos_and_time(), sweeps))
 
     # ------------------------------------------------------------------ superobservation scans
-    def _superob_check(self, superob):
-        """What a superobservation call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
-        themselves: they take ground radars.)"""
-        if not isinstance(superob, SO.Superob):
-            raise ValueError('superob: a cosmo_pol_amd.superob.Superob, got %r' % (superob,))
-        if self.distributed:
-            raise NotImplementedError('superobservations with a process group: the windows would cross the ray shards')
-
     def _superob_sweeps(self, sweeps, spec, keep_gates):
         """One pinned call per sweep over the lanes, one wait at the end: every sweep carries the bits of its own
         simulate_rays_superob(..., spec)."""
-        if not self._check_ready():
-            raise ValueError('no model loaded')
-        n_par = max(1, min(self.lanes, len(sweeps)))
-        res, failure = [], None
-        try:
-            for k, (az, el) in enumerate(sweeps):
-                res.append(self.simulate_rays_superob(az, el, spec, keep_gates=keep_gates, pinned=True, lane=k % n_par))
-        finally:
-            for i in range(n_par):
-                try:
-                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
-                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
-                    failure = failure or exc
-        if failure is not None:
-            raise failure
-        return res
+        return self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays_superob(az, el, spec, keep_gates=keep_gates,
+                                                                                        pinned=True, lane=lane))
 
     def _ppi_sweeps(self, elevations, azimuths, az_step, az_start, az_stop):
         """get_PPI's defaults -> (elevations, azimuths, [(az, el) per sweep])"""
@@ -2501,17 +2257,10 @@ class RadarOperator(object):
 
     # ------------------------------------------------------------------ sweep histograms
     # (replaces in the reference: nothing -- its users pull every per-gate array to the host and call np.histogram2d there)
-    def _histogram_check(self, hist):
-        """What a histogram call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
-        themselves: they take ground radars.)"""
-        if not isinstance(hist, HG.Histogram):
-            raise ValueError('hist: a cosmo_pol_amd.histogram.Histogram, got %r' % (hist,))
-        if self.distributed:
-            raise NotImplementedError('histograms with a process group: sharding rays over ranks is not built')
-        if 'RVEL' in hist.fields or hist.ordinate == 'RVEL':
-            conf = self.__config
-            if conf['doppler']['scheme'] not in (1, 2, 3) or conf['radar'].get('type') == 'GPM':
-                raise ValueError('histogram: RVEL needs a Doppler scheme')
+    def _doppler(self):
+        """RVEL is simulated: a Doppler scheme, and no GPM-type radar."""
+        conf = self.__config
+        return conf['doppler']['scheme'] in (1, 2, 3) and conf['radar'].get('type') != 'GPM'
 
     def simulate_rays_histogram(self, azimuths, elevations, hist, keep_gates=False, phase=3, rays_per_block=0, device_outputs=None,
                                 lane=0, pinned=False):
@@ -2525,17 +2274,15 @@ class RadarOperator(object):
         divisor of the rays: one histogram per block of rays.  `device_outputs`: its entry 'histogram' is {field: device pointer
         of the counts}.  (A method of its own: the keyword list of simulate_rays is pinned.)  ValueError for what the library
         refuses; NotImplementedError with a process group and for spaceborne geometry."""
-        self._histogram_check(hist)
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                   histogram=(hist, int(phase), int(rays_per_block), keep_gates))
+                                   product=HG.Counts(hist, keep_gates, phase, rays_per_block, self._doppler(), self.distributed))
 
     def simulate_rays_at_histogram(self, azimuths, elevations, times, hist, keep_gates=False, phase=3, rays_per_block=0,
                                    device_outputs=None, lane=0, pinned=False):
         """simulate_rays_at handing back a histogram: `hist`, `keep_gates`, `phase`, `rays_per_block` as for
         simulate_rays_histogram (ValueError when the rays fall into several groups of states)."""
-        self._histogram_check(hist)
         return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                      histogram=(hist, int(phase), int(rays_per_block), keep_gates))
+                                      product=HG.Counts(hist, keep_gates, phase, rays_per_block, self._doppler(), self.distributed))
 
     def simulate_rays_ensemble_histogram(self, azimuths, elevations, hist, members=None, per_member=True, keep_gates=False,
                                          phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
@@ -2546,65 +2293,45 @@ class RadarOperator(object):
         too.  `phase`: as for simulate_rays_histogram; when `sequence_memory_budget` cuts the member list into several calls,
         per_member needs phase=3 (every chunk is a pass of its own and the blocks are joined), and the one histogram of all
         members folds the chunks into the pass.  NotImplementedError where simulate_rays_ensemble raises it."""
-        self._histogram_check(hist)
+        return self._ensemble_reduced(azimuths, elevations, HG.Counts(hist, keep_gates, phase, 0, self._doppler(), self.distributed),
+                                      'histograms', members, per_member, device_outputs, apply_sensitivity, lane, pinned)
+
+    def _ensemble_reduced(self, azimuths, elevations, product, what, members, per_member, device_outputs, apply_sensitivity, lane,
+                          pinned):
+        """An ensemble call (form 'shared') whose gates a histogram or a composite reduces: a block per member (`what` they
+        are called), or one of all members' gates."""
         members = self._members_arg(members)
         coords = self._ensemble_coords()
         sub = self._cached('sub', lambda: quadrature.subbeams(self.__config))
         rr = self.constants.RANGE_RADAR
         n_rays = len(np.asarray(azimuths).reshape(-1))
         chunks = self._shared_member_chunks(self._lane(lane), members, sub.n_sub * len(rr) * n_rays)
-        phase = int(phase)
+        name, phase = product.name, product.phase
         if len(chunks) > 1 and device_outputs is not None:
-            raise ValueError('simulate_rays_ensemble_histogram: device outputs need the members in one chunk')
+            raise ValueError('simulate_rays_ensemble_%s: device outputs need the members in one chunk' % name)
         if len(chunks) > 1 and per_member and phase != 3:
-            raise ValueError('simulate_rays_ensemble_histogram: per-member histograms of a member list cut into several calls '
-                             'need phase=3')
+            raise ValueError('simulate_rays_ensemble_%s: per-member %s of a member list cut into several calls need phase=3'
+                             % (name, what))
+        product.rays_per_block = n_rays if per_member else 0
         parts = []
         for i, chunk in enumerate(chunks):
-            if per_member or len(chunks) == 1:
-                ph = phase
-            else:
-                ph = (phase & 1 if i == 0 else 0) | (phase & 2 if i == len(chunks) - 1 else 0)
+            if not per_member and len(chunks) > 1:    # (one block of all members: the chunks fold into the pass)
+                product.phase = (phase & 1 if i == 0 else 0) | (phase & 2 if i == len(chunks) - 1 else 0)
             parts.append(self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
                                         device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
-                                        pinned=pinned and len(chunks) == 1, members=chunk,
-                                        histogram=(hist, ph, n_rays if per_member else 0, keep_gates)))
+                                        pinned=pinned and len(chunks) == 1, members=chunk, product=product))
         if len(parts) == 1 or device_outputs is not None:
             return parts[-1]
-        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
-        out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts]))
-               for k in parts[0].keys() if k != 'histogram'}
-        if 'histogram' in parts[-1]:
-            out['histogram'] = dict(parts[-1]['histogram'])
-            if per_member:
-                out['histogram']['counts'] = {k: np.concatenate([q['histogram']['counts'][k] for q in parts])
-                                              for k in hist.fields}
+        once = _COORDS + ('n_sub',)
+        out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts])) for k in parts[0].keys() if k != name}
+        if name in parts[-1]:
+            out[name] = product.join([q.get(name) for q in parts], np.concatenate)
         return out
 
     def _histogram_sweeps(self, sweeps, hist, per_sweep, keep_gates, rays_per_block):
-        """The sweeps of a scan counted: per sweep (one pinned call per sweep over the lanes, one wait at the end), or all
-        folded into ONE pass, which stays on lane 0 as the statistics' passes stay on theirs."""
-        self._histogram_check(hist)
-        if not self._check_ready():
-            raise ValueError('no model loaded')
-        n_par = max(1, min(self.lanes, len(sweeps))) if per_sweep else 1
-        res, failure = [], None
-        try:
-            for k, (az, el) in enumerate(sweeps):
-                phase = 3 if per_sweep else (1 if k == 0 else 0) | (2 if k == len(sweeps) - 1 else 0)
-                res.append(self.simulate_rays_histogram(az, el, hist, keep_gates=keep_gates, phase=phase,
-                                                        rays_per_block=rays_per_block, pinned=True, lane=k % n_par))
-        finally:
-            for i in range(n_par):
-                try:
-                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
-                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
-                    failure = failure or exc
-        if failure is not None:
-            raise failure
-        if per_sweep:
-            return res
-        return {'histogram': res[-1].pop('histogram'), 'sweeps': res}
+        """The sweeps of a scan counted: per sweep, or all folded into ONE pass (_pass_over_sweeps)."""
+        return self._pass_over_sweeps('histogram', sweeps, lambda az, el, phase, lane: self.simulate_rays_histogram(
+            az, el, hist, keep_gates=keep_gates, phase=phase, rays_per_block=rays_per_block, pinned=True, lane=lane), per_sweep)
 
     def get_PPI_histogram(self, elevations, hist, azimuths=None, az_step=None, az_start=0, az_stop=359, per_sweep=False,
                           keep_gates=False):
@@ -2625,14 +2352,6 @@ class RadarOperator(object):
     # ------------------------------------------------------------------ gridded composites
     # (replaces in the reference: nothing -- its users pull every per-gate array to the host, compute per gate where it lies and
     # scatter with np.maximum.at)
-    def _composite_check(self, spec):
-        """What a composite call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
-        themselves: they take ground radars.)"""
-        if not isinstance(spec, CP.Composite):
-            raise ValueError('spec: a cosmo_pol_amd.composite.Composite, got %r' % (spec,))
-        if self.distributed:
-            raise NotImplementedError('composites with a process group: sharding rays over ranks is not built')
-
     def simulate_rays_composite(self, azimuths, elevations, spec, keep_gates=False, phase=3, rays_per_block=0, device_outputs=None,
                                 lane=0, pinned=False):
         """simulate_rays handing back MAPS of its gates on a radar-centred grid: `spec` is a composite.Composite, and a finishing
@@ -2645,17 +2364,15 @@ class RadarOperator(object):
         fold into one composite.  `rays_per_block`: 0 one map of all rays, else a divisor of the rays: one map per block of rays.
         `device_outputs`: its entry 'composite' is {'values': {field: device pointer}, 'count': device pointer}.  ValueError for
         what the library refuses; NotImplementedError with a process group and for spaceborne geometry."""
-        self._composite_check(spec)
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                   histogram=(spec, int(phase), int(rays_per_block), keep_gates))
+                                   product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed))
 
     def simulate_rays_at_composite(self, azimuths, elevations, times, spec, keep_gates=False, phase=3, rays_per_block=0,
                                    device_outputs=None, lane=0, pinned=False):
         """simulate_rays_at handing back a composite: `spec`, `keep_gates`, `phase`, `rays_per_block` as for
         simulate_rays_composite (ValueError when the rays fall into several groups of states)."""
-        self._composite_check(spec)
         return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                      histogram=(spec, int(phase), int(rays_per_block), keep_gates))
+                                      product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed))
 
     def simulate_rays_ensemble_composite(self, azimuths, elevations, spec, members=None, per_member=True, keep_gates=False,
                                          phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
@@ -2666,40 +2383,8 @@ class RadarOperator(object):
         `sequence_memory_budget` cuts the member list into several calls, per_member needs phase=3 (every chunk is a pass of its
         own and the blocks are joined), and the one map of all members folds the chunks into the pass.  NotImplementedError
         where simulate_rays_ensemble raises it."""
-        self._composite_check(spec)
-        members = self._members_arg(members)
-        coords = self._ensemble_coords()
-        sub = self._cached('sub', lambda: quadrature.subbeams(self.__config))
-        rr = self.constants.RANGE_RADAR
-        n_rays = len(np.asarray(azimuths).reshape(-1))
-        chunks = self._shared_member_chunks(self._lane(lane), members, sub.n_sub * len(rr) * n_rays)
-        phase = int(phase)
-        if len(chunks) > 1 and device_outputs is not None:
-            raise ValueError('simulate_rays_ensemble_composite: device outputs need the members in one chunk')
-        if len(chunks) > 1 and per_member and phase != 3:
-            raise ValueError('simulate_rays_ensemble_composite: per-member maps of a member list cut into several calls need phase=3')
-        parts = []
-        for i, chunk in enumerate(chunks):
-            if per_member or len(chunks) == 1:
-                ph = phase
-            else:
-                ph = (phase & 1 if i == 0 else 0) | (phase & 2 if i == len(chunks) - 1 else 0)
-            parts.append(self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), N.GEOM_GROUND_43,
-                                        device_outputs=device_outputs, apply_sensitivity=apply_sensitivity, lane=lane,
-                                        pinned=pinned and len(chunks) == 1, members=chunk,
-                                        histogram=(spec, ph, n_rays if per_member else 0, keep_gates)))
-        if len(parts) == 1 or device_outputs is not None:
-            return parts[-1]
-        once = ('lats', 'lons', 'dist', 'heights', 'n_sub')
-        out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts]))
-               for k in parts[0].keys() if k != 'composite'}
-        if 'composite' in parts[-1]:
-            out['composite'] = dict(parts[-1]['composite'])
-            if per_member:
-                out['composite']['values'] = {k: {q: np.concatenate([w['composite']['values'][k][q] for w in parts])
-                                                  for q in spec.planes(k)} for k in spec.fields}
-                out['composite']['count'] = {k: np.concatenate([w['composite']['count'][k] for w in parts]) for k in spec.fields}
-        return out
+        return self._ensemble_reduced(azimuths, elevations, CP.Maps(spec, keep_gates, phase, 0, self.distributed), 'maps', members,
+                                      per_member, device_outputs, apply_sensitivity, lane, pinned)
 
     def get_PPI_composite(self, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, per_sweep=False,
                           keep_gates=False):
@@ -2708,48 +2393,15 @@ class RadarOperator(object):
         With `per_sweep` a list with one simulate_rays_composite(..., spec) result per elevation, the sweeps spread over the
         lanes.  (An RHI has no such entry: its plan view is a line.)"""
         _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
-        self._composite_check(spec)
-        if not self._check_ready():
-            raise ValueError('no model loaded')
-        n_par = max(1, min(self.lanes, len(sweeps))) if per_sweep else 1
-        res, failure = [], None
-        try:
-            for k, (az, el) in enumerate(sweeps):
-                phase = 3 if per_sweep else (1 if k == 0 else 0) | (2 if k == len(sweeps) - 1 else 0)
-                res.append(self.simulate_rays_composite(az, el, spec, keep_gates=keep_gates, phase=phase, pinned=True, lane=k % n_par))
-        finally:
-            for i in range(n_par):
-                try:
-                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
-                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
-                    failure = failure or exc
-        if failure is not None:
-            raise failure
-        if per_sweep:
-            return res
-        return {'composite': res[-1].pop('composite'), 'sweeps': res}
+        return self._pass_over_sweeps('composite', sweeps, lambda az, el, phase, lane: self.simulate_rays_composite(
+            az, el, spec, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane), per_sweep)
 
     # ------------------------------------------------------------------ spectrum moments scans
     def _moments_sweeps(self, sweeps, moments, keep_spectrum):
         """One pinned call per sweep over the lanes, one wait at the end: every sweep carries the bits of its own
         simulate_rays_moments(..., moments)."""
-        self._moments_check(moments)
-        if not self._check_ready():
-            raise ValueError('no model loaded')
-        n_par = max(1, min(self.lanes, len(sweeps)))
-        res, failure = [], None
-        try:
-            for k, (az, el) in enumerate(sweeps):
-                res.append(self.simulate_rays_moments(az, el, moments, keep_spectrum=keep_spectrum, pinned=True, lane=k % n_par))
-        finally:
-            for i in range(n_par):
-                try:
-                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
-                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
-                    failure = failure or exc
-        if failure is not None:
-            raise failure
-        return res
+        return self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays_moments(az, el, moments, keep_spectrum=keep_spectrum,
+                                                                                        pinned=True, lane=lane))
 
     def get_PPI_moments(self, elevations, moments, azimuths=None, az_step=None, az_start=0, az_stop=359, keep_spectrum=False):
         """The sweeps of get_PPI with spectrum moments: a list with one simulate_rays_moments(..., moments) result per
@@ -2768,28 +2420,14 @@ class RadarOperator(object):
         its lane and carries the bits of its own call.  `observations`: one dict per sweep (an EnsembleVerification)."""
         members = self._members_arg(members)
         if observations is None:
-            observations = [None] * len(sweeps)
+            return self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays_ensemble_stats(az, el, stats, members=members,
+                                                                                                   pinned=True, lane=lane))
         observations = list(observations)
         if len(observations) != len(sweeps):
             raise ValueError('observations: one dict per sweep (%d sweeps, got %d)' % (len(sweeps), len(observations)))
-        n_par = max(1, min(self.lanes, len(sweeps)))
-        res, failure = [], None
-        try:
-            for k, (az, el) in enumerate(sweeps):
-                if isinstance(stats, EV.EnsembleVerification):
-                    res.append(self.simulate_rays_ensemble_verify(az, el, stats, observations[k], members=members, pinned=True,
-                                                                  lane=k % n_par))
-                else:
-                    res.append(self.simulate_rays_ensemble_stats(az, el, stats, members=members, pinned=True, lane=k % n_par))
-        finally:
-            for i in range(n_par):
-                try:
-                    self.wait(i)                      # (every lane is drained, whatever happened: no copy may outlive the call)
-                except Exception as exc:              # noqa: BLE001  (re-raised below: the first failure of the scan)
-                    failure = failure or exc
-        if failure is not None:
-            raise failure
-        return res
+        obs = iter(observations)
+        return self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays_ensemble_verify(az, el, stats, next(obs), members=members,
+                                                                                                pinned=True, lane=lane))
 
     def get_PPI_ensemble_stats(self, elevations, stats, azimuths=None, az_step=None, az_start=0, az_stop=359, members=None):
         """The sweeps of get_PPI reduced over the ensemble: a list with one simulate_rays_ensemble_stats(..., stats) result

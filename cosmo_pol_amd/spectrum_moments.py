@@ -142,3 +142,48 @@ def moments(spectrum, varray, spec):
     out = {k: np.where(few, np.nan, made[k]).reshape(lead) for k in spec.fields}
     out['count'] = n.astype(np.uint16).reshape(lead)
     return out
+
+
+class Rows(object):
+    """The spectrum moments of ONE sweep call, as RadarOperator._run_rays takes a product ("How a product plugs
+    into a sweep call").  `spectrum`: DSPECTRUM travels to the host too (keep_spectrum)."""
+    name = 'moments'
+    gates, model_var = True, None         # the per-gate fields travel as in the plain call
+    refuses = dict.fromkeys(('members', 'timed', 'subbeams'),
+                            'spectrum moments are taken by the plain sweeps: no superobservations, ensembles, time blend '
+                            'or sub-beam calls')
+
+    def __init__(self, spec, keep_spectrum=False, scheme=3, distributed=False):
+        # what a spectrum-moments call refuses before it builds anything
+        if not isinstance(spec, SpectrumMoments):
+            raise ValueError('moments: a cosmo_pol_amd.spectrum_moments.SpectrumMoments, got %r' % (spec,))
+        if scheme != 3:
+            raise ValueError('spectrum moments need the Doppler spectrum: doppler scheme 3, configured is %r' % (scheme,))
+        if distributed:
+            raise NotImplementedError('spectrum moments with a process group: the distributed scans collect no moments')
+        self.spec, self.spectrum = spec, bool(keep_spectrum)
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        if not spectrum:                  # (a GPM-type radar: no Doppler whatever the scheme says)
+            raise ValueError('spectrum moments need the Doppler spectrum, and this radar simulates none')
+        self.sm = native.Context.spectrum_moments_struct(self.spec)
+        self.shape = (len(az), n_gates)
+        return {'spectrum_moments': self.sm}, []
+
+    def arrays(self):
+        # the moments, in the sweep's own block: they ride the one copy (rows nobody asked for arrive as zeros)
+        return [('moments', np.float64, (len(FIELDS),) + self.shape), ('count', np.uint16, self.shape)]
+
+    def bind(self, path, address):
+        setattr(self.sm, path, address)
+
+    def bind_device(self, entry):         # {'moments': device pointer of [8, n_rays, n_gates], 'count': device pointer}
+        for k, ptr in entry.items():
+            if k not in ('moments', 'count'):
+                raise ValueError("device_outputs['moments']: unknown entry %r" % (k,))
+            self.bind(k, ptr)
+
+    def finish(self, w, coords):
+        rows = w.pop('moments')
+        w.update({k: rows[FIELDS.index(k)] for k in self.spec.fields})
+        return w

@@ -162,3 +162,60 @@ def coordinates(geom, spec, rays_per_block=0):
         S, _, N = _sums(x.astype(np.float64), np.ones(x.shape, dtype=bool), every, rpb)
         out[k] = (S / N.astype(np.float64)).astype(x.dtype)
     return out
+
+
+class Windows(object):
+    """The superobservations of ONE sweep call, as RadarOperator._run_rays takes a product ("How a product plugs
+    into a sweep call"): `gates` -- the per-gate fields travel to the host too; `refuses` -- the kinds of call it does not
+    share; attach / arrays / bind / bind_device / finish / join -- its struct, its arrays and its part of the result."""
+    name = 'superob'                      # the entry of the result and of device_outputs
+    spectrum, model_var = True, None      # DSPECTRUM travels with the gates; no model variable is integrated for it
+    over_members = False                  # (an ensemble call: windows per member, not a reduction over the members)
+    refuses = {'groups': 'superobservations need one group'}
+
+    def __init__(self, spec, keep_gates=False, rays_per_block=0, distributed=False):
+        # what a superobservation call refuses before it builds anything.  (Spaceborne geometry is refused by the ray calls
+        # themselves: they take ground radars.)
+        if not isinstance(spec, Superob):
+            raise ValueError('superob: a cosmo_pol_amd.superob.Superob, got %r' % (spec,))
+        if distributed:
+            raise NotImplementedError('superobservations with a process group: the windows would cross the ray shards')
+        self.spec, self.gates, self.rays_per_block = spec, bool(keep_gates), rays_per_block
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        n_rays = len(az)
+        # (the library refuses the same: the rows of the call are n_members x n_rays, a block never spans two members)
+        self.rpb = int(self.rays_per_block) or n_rays
+        if int(self.rays_per_block) < 0 or n_rays % self.rpb:
+            raise ValueError('rays_per_block %r does not divide the %d rays of the call' % (self.rays_per_block, n_rays))
+        self.so = so = native.Superob()
+        so.ray_window, so.gate_window, so.rays_per_block = self.spec.rays, self.spec.gates, self.rpb
+        so.min_valid_fraction = self.spec.min_valid_fraction
+        self.fields = [k for k in FIELDS if k != 'RVEL' or doppler]
+        self.wshape = shape(n_rays, n_gates, self.spec, self.rpb)
+        if n_members is not None:         # an ensemble call: a leading member axis (the window coordinates come once)
+            self.wshape = (n_members,) + self.wshape
+        return {'superob': so}, []
+
+    def arrays(self):
+        # the window averages, in the sweep's own block: they ride the one copy
+        return ([(k, np.float64 if k == 'RVEL' else np.float32, self.wshape) for k in self.fields]
+                + [('count', np.uint16, (len(FIELDS),) + self.wshape)])
+
+    def bind(self, path, address):
+        setattr(self.so, path, address)
+
+    def bind_device(self, entry):         # {field or 'count': device pointer}
+        for k, ptr in entry.items():
+            self.bind(k, ptr)
+
+    def finish(self, w, coords):
+        cnt = w.pop('count')
+        w['count'] = {k: cnt[FIELDS.index(k)] for k in self.fields}
+        w.update(coords((self.spec.rays, self.spec.gates, self.rpb), lambda g: coordinates(g, self.spec, self.rpb)))
+        return w
+
+    def join(self, parts, cat):
+        out = {k: (v if k in COORDINATES else cat([p[k] for p in parts])) for k, v in parts[0].items() if k != 'count'}
+        out['count'] = {k: cat([p['count'][k] for p in parts]) for k in parts[0]['count']}
+        return out

@@ -461,12 +461,16 @@ def test_refusals_of_the_sweeps_and_the_operator():
         op.simulate_rays_ensemble_stats(az, el, (True, True))
     with pytest.raises(ValueError):
         op.simulate_rays_ensemble_stats(az, el, spec, members=[0, 0])
+    # (a call takes ONE product, so statistics never meet superobservations: what an ensemble call refuses of
+    # superobservations, and the calls the statistics do not share)
     with pytest.raises(ValueError, match='superobservations'):
-        op._run_rays(az, el, op.config['radar']['coords'], full['ZH'].shape[2], 0.0, N.GEOM_GROUND_43,
-                     superob=SO.Superob(1, 1), member_stats=(spec, 3, False))
+        op._ensemble_rays(az, el, None, {'ZH': 1}, True, 0, 'per_member', False, SO.Windows(SO.Superob(1, 1)))
     with pytest.raises(ValueError, match='time-blended'):
         op._run_rays(az, el, op.config['radar']['coords'], full['ZH'].shape[2], 0.0, N.GEOM_GROUND_43,
-                     timed=([0, 1], lo, w), member_stats=(spec, 3, False))
+                     timed=([0, 1], lo, w), product=ES.Fold(spec, False))
+    with pytest.raises(ValueError, match='sub-beam'):
+        op._run_rays(az, el, op.config['radar']['coords'], full['ZH'].shape[2], 0.0, N.GEOM_GROUND_43,
+                     subbeams={}, product=ES.Fold(spec, False))
     if 'RVEL' not in full:
         with pytest.raises(ValueError, match='RVEL'):
             op.simulate_rays_ensemble_stats(az, el, ES.EnsembleStats(fields=['RVEL']))
