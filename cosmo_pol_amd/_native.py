@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
-                 'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'sz_total',
+                 'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'fractions', 'sz_total',
                  'composite', 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
@@ -163,11 +163,20 @@ class Composite(C.Structure):
                 ('values', C.c_void_p * len(COMPOSITE_FIELDS)), ('count', C.c_void_p)]
 
 
+class Fractions(C.Structure):
+    """cpol_fractions: the fractions skill score's sums of one finished plane of a composite against an observed map
+    (cosmo_pol_amd/neighbourhood.py states the rule)."""
+    _fields_ = [('field', C.c_int32), ('plane', C.c_int32), ('n_thresholds', C.c_int32), ('n_radii', C.c_int32),
+                ('thresholds', C.c_double * 4), ('radii', C.c_int32 * 8), ('observed', C.c_void_p), ('domain', C.c_void_p),
+                ('sums', C.c_void_p), ('totals', C.c_void_p)]
+
+
 class Outputs(C.Structure):
-    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8), histogram (directly before DSPECTRUM) and composite (directly before histogram): pointers to a struct, not
+    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8), histogram (directly before DSPECTRUM), composite (directly before histogram) and fractions (directly before sz_total, in front of the members that are pinned where they are): pointers to a struct, not
     # arrays; member_stats, superob likewise: NULL = off; superob stays the last member (cpol_outputs)
     _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify),
-                      'histogram': C.POINTER(Histogram), 'composite': C.POINTER(Composite)}.get(n, C.c_void_p))
+                      'histogram': C.POINTER(Histogram), 'composite': C.POINTER(Composite),
+                      'fractions': C.POINTER(Fractions)}.get(n, C.c_void_p))
                  for n in OUTPUT_FIELDS]
                 + [('member_stats', C.POINTER(MemberStats)), ('superob', C.POINTER(Superob))])
 
@@ -548,7 +557,7 @@ class PinnedPool(object):
         self._free_returned()
 
 
-_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint16: 2, np.uint64: 8}
+_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint8: 1, np.uint16: 2, np.uint64: 8}
 
 
 def carve_block(pool, spec, writer=None):
@@ -1111,6 +1120,66 @@ class Context(object):
             return None
         return {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
                 'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
+
+    @staticmethod
+    def fractions_struct(spec):
+        """(Fractions for a call under `spec` (a neighbourhood.Fractions), the arrays it points into): the field and the plane as
+        indices, the thresholds as the caller gave them (float64; the library rounds them), the radii; `observed`, `domain` and
+        the output pointers are the caller's."""
+        f = Fractions()
+        f.field, f.plane = COMPOSITE_FIELDS.index(spec.field), int(spec.plane_index)
+        f.n_thresholds, f.n_radii = len(spec.thresholds_given), len(spec.radii)
+        for j, v in enumerate(spec.thresholds_given):
+            f.thresholds[j] = float(v)
+        for j, r in enumerate(spec.radii):
+            f.radii[j] = int(r)
+        return f, []
+
+    def fractions_maps(self, maps, observed, spec, domain=None, tamper=None):
+        """Test hook (cpol_debug_read "fractions_maps"): the checks and k_frac_rows, k_frac_cols, k_frac_score on caller-supplied
+        maps -> what neighbourhood.sums returns for them.  maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]); observed: float32
+        [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
+        and `radii` (the maps need not be those of spec.composite's grid).  `tamper(f)`: changes the cpol_fractions before the call
+        (the refusal tests)."""
+        from . import neighbourhood as NB
+
+        class Hook(C.Structure):
+            _fields_ = [('n_blocks', C.c_int32), ('n_y', C.c_int32), ('n_x', C.c_int32), ('pad_', C.c_int32), ('maps', C.c_void_p),
+                        ('f', Fractions)]
+        m = np.ascontiguousarray(maps, dtype=np.float32)
+        if m.ndim == 2:
+            m = m[None]
+        o = np.ascontiguousarray(observed, dtype=np.float32)
+        if m.ndim != 3 or o.shape != m.shape[1:]:
+            raise ValueError('fractions_maps: maps [n_blocks, n_y, n_x], observed [n_y, n_x]')
+        keep = [m, o]
+        hk = Hook()
+        hk.n_blocks, hk.n_y, hk.n_x = m.shape
+        hk.maps = m.ctypes.data
+        f = Fractions()
+        f.n_thresholds, f.n_radii = len(spec.thresholds_given), len(spec.radii)
+        for j, v in enumerate(spec.thresholds_given):
+            f.thresholds[j] = float(v)
+        for j, r in enumerate(spec.radii):
+            f.radii[j] = int(r)
+        f.observed = o.ctypes.data
+        if domain is not None:
+            d = np.ascontiguousarray(domain, dtype=np.uint8)
+            if d.shape != o.shape:
+                raise ValueError('fractions_maps: domain [n_y, n_x]')
+            keep.append(d)
+            f.domain = d.ctypes.data
+        nt, nr = f.n_thresholds, f.n_radii
+        s = np.full((m.shape[0], nt, nr, 3), 0xDEADBEEF, dtype=np.uint64)
+        t = np.full((m.shape[0], nt, 3), 0xDEADBEEF, dtype=np.uint64)
+        f.sums, f.totals = s.ctypes.data, t.ctypes.data
+        hk.f = f
+        if tamper is not None:
+            keep.append(tamper(hk.f))
+        rc = int(self.lib.cpol_debug_read(self.h, b'fractions_maps', C.byref(hk), C.sizeof(hk)))
+        self._check(rc, 'cpol_debug_read(fractions_maps)')
+        del keep
+        return NB.result(spec, s, t)
 
     @staticmethod
     def spectrum_moments_struct(spec):

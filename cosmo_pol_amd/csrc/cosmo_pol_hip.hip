@@ -29,6 +29,7 @@
 #include "cpol_place.h"
 #include "cpol_hist.h"
 #include "cpol_comp.h"
+#include "cpol_frac.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -40,6 +41,7 @@
 #include "cpol_member_stats.inl"
 #include "cpol_hist.inl"
 #include "cpol_comp.inl"
+#include "cpol_frac.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -193,6 +195,11 @@ struct cpol_ctx {
     CompPass cpass;
     CompPlan cplan;                        // ... and the plan of the call at hand (kept here: a call without the struct constructs none)
     std::vector<double> cedges_host;       // ... and what b_cedges holds (the source of its copy)
+    // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
+    // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
+    // the call at hand
+    DevBuf b_fsat, b_fobs, b_fout[2], b_fmaps;
+    FracPlan fplan;
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
     struct MemberPass {
         bool open = false;
@@ -790,7 +797,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -2720,6 +2727,88 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
     return CPOL_OK;
 }
 
+// ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
+// (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
+enum { FR_SUMS, FR_TOTALS, FR_N };
+// arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
+// composite's `count`
+static void frac_place(const cpol_fractions *f, const FracPlan &pl, PlaceArray *arr)
+{
+    arr[FR_SUMS] = arr[FR_TOTALS] = PlaceArray{};
+    arr[FR_SUMS].user = (uintptr_t)f->sums;     arr[FR_SUMS].bytes = pl.sums_bytes;
+    arr[FR_TOTALS].user = (uintptr_t)f->totals; arr[FR_TOTALS].bytes = pl.totals_bytes;
+    for (int k = 0; k < FR_N; ++k) { arr[k].produced = true; arr[k].product = PLACE_SWEEP; }
+}
+
+// plane: block 0's plane on the device; obs_on_host: `observed` and `domain` are host arrays (copied to b_fobs on `st` first),
+// else memory the device reads in place; T: where `sums` and `totals` go
+static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &pl, const float *plane, long plane_stride, bool obs_on_host,
+                       void *const T[FR_N], hipStream_t st)
+{
+    ENSURE(ctx->b_fsat, (size_t)pl.scratch_bytes);
+    FracArgs a{};
+    a.plane = plane; a.plane_stride = plane_stride;
+    a.obs = f->observed; a.domain = f->domain;
+    if (obs_on_host) {
+        const size_t ob = ((size_t)pl.cells * sizeof(float) + 255) & ~(size_t)255;
+        ENSURE(ctx->b_fobs, ob + (size_t)pl.cells);
+        HIPCHK(hipMemcpyAsync(ctx->b_fobs.p, f->observed, (size_t)pl.cells * sizeof(float), hipMemcpyHostToDevice, st));
+        a.obs = (const float *)ctx->b_fobs.p;
+        if (f->domain) {
+            HIPCHK(hipMemcpyAsync((char *)ctx->b_fobs.p + ob, f->domain, (size_t)pl.cells, hipMemcpyHostToDevice, st));
+            a.domain = (const unsigned char *)ctx->b_fobs.p + ob;
+        }
+    }
+    a.sat = (unsigned *)ctx->b_fsat.p;
+    a.sums = (unsigned long long *)T[FR_SUMS]; a.totals = (unsigned long long *)T[FR_TOTALS];
+    a.table = pl.table; a.n_blocks = pl.n_blocks;
+    a.n_x = pl.n_x; a.n_y = pl.n_y; a.cells = (int)pl.cells;
+    a.n_thr = pl.n_thr; a.n_radii = pl.n_radii;
+    a.row_groups = (pl.n_y + FRAC_ROWS - 1) / FRAC_ROWS; a.col_chunks = pl.col_chunks; a.score_groups = pl.score_groups;
+    for (int j = 0; j < pl.n_thr; ++j) a.thr[j] = pl.thr[j];
+    for (int j = 0; j < pl.n_radii; ++j) a.radii[j] = pl.radii[j];
+    HIPCHK(hipMemsetAsync(T[FR_SUMS], 0, pl.sums_bytes, st));
+    HIPCHK(hipMemsetAsync(T[FR_TOTALS], 0, pl.totals_bytes, st));
+    hipLaunchKernelGGL(k_frac_rows, dim3((unsigned)pl.grid_rows), dim3(FRAC_THREADS), 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_frac_cols, dim3((unsigned)pl.grid_cols), dim3(64), 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_frac_score, dim3((unsigned)pl.grid_score), dim3(FRAC_THREADS), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "fractions_maps": the checks and the three kernels on caller-supplied maps (host memory in, host
+// memory out, blocking) -- the kernels on maps no sweep produces (every value class, rows and columns across wavefront chunks,
+// windows clipped at every border, the smallest and the longest grids).
+struct FracHook {
+    int32_t n_blocks, n_y, n_x, pad_;
+    const float *maps;                      // [n_blocks][n_y][n_x]
+    cpol_fractions f;
+};
+
+static int frac_hook(cpol_ctx *ctx, const FracHook *hk)
+{
+    if (!hk->maps) { ctx->err = "fractions_maps: maps is NULL"; return CPOL_ERR_ARG; }
+    FracPlan pl;
+    const char *why = frac_check_maps(&hk->f, hk->n_x, hk->n_y, hk->n_blocks, &pl);
+    if (why) { ctx->err = std::string("cpol_fractions: ") + why; return CPOL_ERR_ARG; }
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = upload(ctx, ctx->b_fmaps, hk->maps, (size_t)pl.n_blocks * pl.cells * sizeof(float))) != CPOL_OK) return rc;
+    PlaceArray arr[FR_N];
+    frac_place(&hk->f, pl, arr);
+    PlacePlan plan;
+    place_outputs(arr, FR_N, 0, false, &plan);
+    DevBuf *own[FR_N] = {&ctx->b_fout[0], &ctx->b_fout[1]};
+    void *T[FR_N];
+    if ((rc = place_resolve(ctx, arr, FR_N, plan, own, T)) != CPOL_OK) return rc;
+    if ((rc = frac_launch(ctx, &hk->f, pl, (const float *)ctx->b_fmaps.p, pl.cells, true, T, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+
 // The launch sequence of cpol_run_sweep, and its two halves:
 // - cpol_run_columns (cols != NULL): k_columns_ingest copies the caller's sub-beam columns where k_interp_sweep would have
 //   written the interpolated ones; `t` then holds the per-ray tables cpol_run_columns made of them, with one horizontal
@@ -2812,12 +2901,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_MS };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
     static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
     // (and so do a composite's nine `values` and its `count`: the three never share a call)
     static_assert(CP_N <= SO_N, "the composite's maps in the slots of the superobservations");
+    // (the sums of a neighbourhood verification, which comes with a composite alone, take slots of the ensemble statistics)
+    static_assert(FR_N <= MS_N, "the fractions' sums in the slots of the ensemble statistics");
     PlaceArray arr[A_N];
     // (a composite shares a call with no other product: refused before the other product's own checks speak)
     if (out->composite && (out->superob || out->histogram || out->member_stats || out->spectrum_moments)) {
@@ -2880,6 +2971,14 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         cc.other_product = so || ms || sm || hg;
         const int rc_cp = comp_plan(ctx, cp, cc, &cp_pl, arr + A_CP);
         if (rc_cp != CPOL_OK) return rc_cp;
+    }
+    // neighbourhood verification (cpol_fractions): likewise, against the composite's plan, which passed
+    const cpol_fractions *const fr = out->fractions;
+    FracPlan &fr_pl = ctx->fplan;
+    if (fr) {
+        const char *const why = frac_check(fr, cp, cp ? &cp_pl : nullptr, &fr_pl);
+        if (why) { ctx->err = std::string("cpol_fractions: ") + why; return CPOL_ERR_ARG; }
+        frac_place(fr, fr_pl, arr + A_FR);
     }
     int rc;
 
@@ -3241,6 +3340,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
     if (hg) for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_HG + k] = &ctx->b_hcounts[k];      // (and a finishing call's counts)
     if (cp) for (int k = 0; k < CP_N; ++k) own[A_CP + k] = &ctx->b_cout[k];                      // (and a finishing call's maps)
+    if (fr) for (int k = 0; k < FR_N; ++k) own[A_FR + k] = &ctx->b_fout[k];                      // (and their scores)
     for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
@@ -4022,6 +4122,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     if (cp) {
         const void *const cp_in[CPOL_COMP_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV]};
         if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, st)) != CPOL_OK) return rc;
+        // ---- neighbourhood verification: three kernels behind k_comp_finish, on the finished plane where the plan placed it ----
+        if (fr && (rc = frac_launch(ctx, fr, fr_pl, (const float *)T_all[A_CP + fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride,
+                                    p->outputs_on_device == 0, T_all + A_FR, st)) != CPOL_OK) return rc;
     }
     // ---- outputs that the kernels did not write in place ----
     if (window)
@@ -4082,6 +4185,7 @@ int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_colum
     if (!ctx) return CPOL_ERR_ARG;
     if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->composite) { ctx->err = "cpol_run_columns: gridded composites (outputs->composite) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    if (out && out->fractions) { ctx->err = "cpol_run_columns: neighbourhood verification (outputs->fractions) is taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->histogram) { ctx->err = "cpol_run_columns: sweep histograms (outputs->histogram) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
     if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
     if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
@@ -4404,6 +4508,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "composite_fields")) {        // a CONTROL name: dst points to a CompHook
         if (!dst || max_bytes < (int64_t)sizeof(CompHook)) { ctx->err = "cpol_debug_read(composite_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return comp_hook(ctx, (const CompHook *)dst);
+    }
+    if (!strcmp(name, "fractions_maps")) {          // a CONTROL name: dst points to a FracHook
+        if (!dst || max_bytes < (int64_t)sizeof(FracHook)) { ctx->err = "cpol_debug_read(fractions_maps): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return frac_hook(ctx, (const FracHook *)dst);
     }
     if (!strcmp(name, "composite_stretch")) {
         if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;

@@ -1,0 +1,94 @@
+// cpol_frac.h -- neighbourhood verification (cpol_fractions): every refusal, the rounding of the thresholds to float32, where the
+// scored plane lies in the composite's `values`, the layout of the summed-area tables and the grids of the three launches,
+// decided by frac_check() from plain numbers.  Plain C++ without HIP types, so that a host program can include it
+// (tests/c_host/frac_check.cpp, tests/test_neighbourhood_cpu.py check it without a GPU).  The kernels are k_frac_rows,
+// k_frac_cols and k_frac_score (cpol_frac.inl); the rule is stated in include/cosmo_pol_amd.h and
+// cosmo_pol_amd/neighbourhood.py.
+#pragma once
+
+#include "cpol_comp.h"
+
+constexpr int FRAC_MAX_THR = CPOL_FRAC_MAX_THRESHOLDS;
+constexpr int FRAC_MAX_RADII = CPOL_FRAC_MAX_RADII;
+constexpr int FRAC_MAX_RADIUS = CPOL_FRAC_MAX_RADIUS;
+constexpr int FRAC_MAX_SIDE = COMP_MAX_EDGES - 1;     // cells per axis: the composite's limit
+// the summed-area tables of all blocks and thresholds plus the observation's: the composite's cap for the sum of both
+constexpr long FRAC_MAX_SCRATCH_BYTES = COMP_MAX_STATE_BYTES;
+constexpr int FRAC_THREADS = 256;                     // threads of a workgroup of the three kernels: four wavefronts
+constexpr int FRAC_ROWS = FRAC_THREADS / 64;          // rows of a workgroup of k_frac_rows: one per wavefront
+// cells of a workgroup of k_frac_score, four per thread: a 300 x 300 map gives 88 workgroups per (block, threshold), each with
+// ONE atomic addition per sum
+constexpr int FRAC_CELLS = 4 * FRAC_THREADS;
+
+// a call that passed: the numbers the launches need
+struct FracPlan {
+    int n_thr = 0, n_radii = 0;
+    float thr[FRAC_MAX_THR] = {};                     // the ROUNDED thresholds
+    int radii[FRAC_MAX_RADII] = {};
+    int n_x = 0, n_y = 0;
+    long cells = 0, n_blocks = 0;
+    // one summed-area table: uint32 [n_y + 1][n_x + 1], row 0 and column 0 zero, so that a clipped window is four look-ups with no
+    // branch.  Table (s * n_thr + t) belongs to source s and threshold t; sources 0 ... n_blocks - 1 are the blocks of the plane,
+    // source n_blocks is the observation: built once, read by every block
+    long table = 0, n_tables = 0, scratch_bytes = 0;
+    int field = 0;                                    // (sweep calls) the field whose `values` hold the plane ...
+    long plane_first = 0, plane_stride = 0;           // ... block b's plane begins plane_first + b * plane_stride floats into it
+    long grid_rows = 0, grid_cols = 0, grid_score = 0;   // workgroups of the three launches
+    int col_chunks = 0, score_groups = 0;             // 64-column chunks of a table; workgroups of k_frac_score per (block, threshold)
+    size_t sums_bytes = 0, totals_bytes = 0;
+};
+
+// what does not depend on the composite: thresholds, radii, pointers, the scratch and the grids for n_blocks maps of n_y x n_x
+inline const char *frac_check_maps(const cpol_fractions *f, int n_x, int n_y, long n_blocks, FracPlan *pl)
+{
+    if (n_x < 1 || n_y < 1 || n_x > FRAC_MAX_SIDE || n_y > FRAC_MAX_SIDE || n_blocks < 1) return "the maps need 1 ... 1023 cells per axis and at least one block";
+    if (f->n_thresholds < 1 || f->n_thresholds > FRAC_MAX_THR) return "n_thresholds must lie in 1 ... 4";
+    for (int j = 0; j < f->n_thresholds; ++j) {
+        const double t = f->thresholds[j];
+        if (!(t == t)) return "a threshold is NaN";
+        pl->thr[j] = comp_f32(t);
+    }
+    if (f->n_radii < 1 || f->n_radii > FRAC_MAX_RADII) return "n_radii must lie in 1 ... 8";
+    for (int j = 0; j < f->n_radii; ++j) {
+        if (f->radii[j] < 0 || f->radii[j] > FRAC_MAX_RADIUS) return "a radius must lie in 0 ... 1023";
+        if (j > 0 && f->radii[j] <= f->radii[j - 1]) return "the radii must be strictly ascending";
+        pl->radii[j] = f->radii[j];
+    }
+    if (!f->observed) return "observed is NULL";
+    if (!f->sums || !f->totals) return "sums or totals is NULL";
+    pl->n_thr = f->n_thresholds; pl->n_radii = f->n_radii;
+    pl->n_x = n_x; pl->n_y = n_y; pl->cells = (long)n_x * n_y; pl->n_blocks = n_blocks;
+    pl->table = (long)(n_y + 1) * (n_x + 1);
+    // (n_blocks < 2^31 rows of a call, at most 4 thresholds and 2^20 entries of 4 bytes: no overflow of long)
+    pl->n_tables = (n_blocks + 1) * pl->n_thr;
+    pl->scratch_bytes = pl->n_tables * pl->table * 4;
+    if (pl->scratch_bytes > FRAC_MAX_SCRATCH_BYTES) return "the summed-area tables of all blocks and thresholds must be at most 1 GiB";
+    pl->col_chunks = (n_x + 63) / 64;
+    pl->score_groups = (int)((pl->cells + FRAC_CELLS - 1) / FRAC_CELLS);
+    pl->grid_rows = (n_blocks + 1) * ((n_y + FRAC_ROWS - 1) / FRAC_ROWS);
+    pl->grid_cols = pl->n_tables * pl->col_chunks;
+    pl->grid_score = n_blocks * pl->n_thr * pl->score_groups;
+    // (each launch has fewer workgroups than the tables have entries, 2^28 under the cap: out of reach, stated for the reader)
+    if (pl->grid_rows >= (1L << 31) || pl->grid_cols >= (1L << 31) || pl->grid_score >= (1L << 31)) return "too many workgroups in one call";
+    pl->sums_bytes = (size_t)n_blocks * pl->n_thr * pl->n_radii * 3 * sizeof(uint64_t);
+    pl->totals_bytes = (size_t)n_blocks * pl->n_thr * 3 * sizeof(uint64_t);
+    return nullptr;
+}
+
+// every refusal of a cpol_fractions for a sweep call; c: the call's cpol_composite (NULL: none), cp: its plan, which passed
+// comp_check.  NULL: accepted and *pl filled; else the reason (CPOL_ERR_ARG).  Touches nothing else.
+inline const char *frac_check(const cpol_fractions *f, const cpol_composite *c, const CompPlan *cp, FracPlan *pl)
+{
+    *pl = FracPlan{};
+    if (!c || !cp) return "needs a composite (outputs->composite) in the same call";
+    if (!cp->finish) return "the composite call does not finish its pass (phase & 2): the maps do not exist yet";
+    if (f->field < 0 || f->field >= COMP_FIELDS || !((c->fields >> f->field) & 1u)) return "field is not among the composed fields (composite->fields)";
+    const int n_planes = cp->n_planes[f->field];
+    if (f->plane < 0 || f->plane >= n_planes) return "plane lies outside the planes of the field";
+    const char *why = frac_check_maps(f, cp->n_x, cp->n_y, cp->n_blocks, pl);
+    if (why) return why;
+    pl->field = f->field;
+    pl->plane_first = (long)f->plane * pl->cells;
+    pl->plane_stride = (long)n_planes * pl->cells;
+    return nullptr;
+}

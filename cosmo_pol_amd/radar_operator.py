@@ -32,6 +32,7 @@ from . import spectrum_moments as SM
 from . import superob as SO
 from . import histogram as HG
 from . import composite as CP
+from . import neighbourhood as NB
 from .lut import load_all_lut
 
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
@@ -2395,6 +2396,66 @@ class RadarOperator(object):
         _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
         return self._pass_over_sweeps('composite', sweeps, lambda az, el, phase, lane: self.simulate_rays_composite(
             az, el, spec, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane), per_sweep)
+
+    # ------------------------------------------------------------------ neighbourhood verification of composites
+    # (replaces in the reference: nothing -- its users grid the radials, threshold both maps and run box filters on the host)
+    def _fss_product(self, spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block):
+        """The product object of a composite call with scores; `observed` and `domain` checked (host arrays), or device pointers
+        under device_outputs['composite'] and `observed` None."""
+        if not isinstance(spec, NB.Fractions):
+            raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
+        entry = (device_outputs or {}).get('composite', {})
+        if int(phase) & 2:
+            if (observed is None) == (entry.get('observed') is None):
+                raise ValueError("a Fractions call needs the observed map (a NumPy array), or with device_outputs the device "
+                                 "pointer device_outputs['composite']['observed'], and not both")
+            if observed is not None and device_outputs is not None:
+                raise ValueError("with device_outputs the observed map is a device pointer under device_outputs['composite']['observed']")
+            if observed is None and domain is not None:
+                raise ValueError("with device_outputs the domain is a device pointer under device_outputs['composite']['domain']")
+        if observed is not None:
+            observed, domain = NB.check_maps(spec, observed, domain)
+        return NB.Scores(spec, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
+
+    def simulate_rays_composite_fss(self, azimuths, elevations, spec, observed, domain=None, keep_gates=False, phase=3,
+                                    rays_per_block=0, device_outputs=None, lane=0, pinned=False):
+        """simulate_rays_composite with the finished plane SCORED against an observed map on the device: `spec` is a
+        neighbourhood.Fractions (its composite, the field and plane to score, thresholds and radii), `observed` float32
+        [n_y, n_x] on the composite's grid in the field's linear units (NaN = no echo or no data), `domain` an optional uint8
+        [n_y, n_x] mask of the verification domain.  A finishing call's res['composite'] gains 'fractions': {'diff2' |
+        'forecast2' | 'observed2': uint64 [n_blocks, n_thr, n_radii], 'n_forecast' | 'n_observed' | 'n_domain': uint64
+        [n_blocks, n_thr], 'thresholds', 'radii'} -- exactly neighbourhood.sums of the map the same call returns;
+        neighbourhood.fss, bias and contingency make the scores of them.  A pass is scored only by the call that finishes it.
+        The other keywords are those of simulate_rays_composite.  `device_outputs`: its entry 'composite' may carry 'observed',
+        'domain', 'sums' and 'totals' as device pointers (`observed` stays None).  ValueError for an observed map or a domain of
+        a wrong shape or dtype and for what the library refuses."""
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                   product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block))
+
+    def simulate_rays_at_composite_fss(self, azimuths, elevations, times, spec, observed, domain=None, keep_gates=False, phase=3,
+                                       rays_per_block=0, device_outputs=None, lane=0, pinned=False):
+        """simulate_rays_at_composite with scores: `spec`, `observed`, `domain` as for simulate_rays_composite_fss."""
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                      product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block))
+
+    def simulate_rays_ensemble_composite_fss(self, azimuths, elevations, spec, observed, domain=None, members=None, per_member=True,
+                                             keep_gates=False, phase=3, device_outputs=None, apply_sensitivity=True, lane=0,
+                                             pinned=False):
+        """simulate_rays_ensemble_composite with scores: with `per_member` one row of scores per member (the leading axis of
+        every array of 'fractions', in the order of `members`; each equals the member's own simulate_rays_composite_fss),
+        without it the scores of the one map of all members' gates.  `spec`, `observed`, `domain` as for
+        simulate_rays_composite_fss; the rest as for simulate_rays_ensemble_composite."""
+        return self._ensemble_reduced(azimuths, elevations, self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, 0),
+                                      'maps', members, per_member, device_outputs, apply_sensitivity, lane, pinned)
+
+    def get_PPI_composite_fss(self, elevations, spec, observed, domain=None, azimuths=None, az_step=None, az_start=0, az_stop=359,
+                              per_sweep=False, keep_gates=False):
+        """get_PPI_composite with scores.  By default the volume folds into one pass, which is scored ONCE, at its end:
+        {'composite': as for simulate_rays_composite_fss, 'sweeps': [...]}.  With `per_sweep` a list with one
+        simulate_rays_composite_fss(..., spec, observed) result per elevation."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._pass_over_sweeps('composite', sweeps, lambda az, el, phase, lane: self.simulate_rays_composite_fss(
+            az, el, spec, observed, domain=domain, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane), per_sweep)
 
     # ------------------------------------------------------------------ spectrum moments scans
     def _moments_sweeps(self, sweeps, moments, keep_spectrum):

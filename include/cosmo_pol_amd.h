@@ -588,6 +588,56 @@ typedef struct cpol_composite {
     uint64_t *count;                            /* [n_blocks][n_requested_fields][n_y][n_x]; likewise              */
 } cpol_composite;
 
+/* Neighbourhood verification: the sums of the fractions skill score (FSS; Roberts and Lean 2008) of ONE finished plane of a
+ * composite against an observed map on the same grid, per block, threshold and neighbourhood size, reduced on the device, for
+ * the user who verifies MAPS against observations.  Replaces in the reference: nothing (its users pull every map to the host and
+ * run box filters there).  Pointed to by cpol_outputs.fractions; honoured only beside cpol_outputs.composite in a call that
+ * FINISHES the composite's pass (phase & 2).  cosmo_pol_amd/neighbourhood.py states the same rule in NumPy (`sums`).
+ * INPUT: the plane `plane` (an index into the fixed plane order of cpol_composite: max, height_of_max, lowest, height_of_lowest,
+ * echo_top_0 ..., planes not requested absent) of field `field`, float32 m[n_blocks][n_y][n_x] exactly as k_comp_finish leaves
+ * it where it lies on the device, empty cells NaN; `observed`, float32 o[n_y][n_x] on the same grid in the field's own linear
+ * units, NaN = no echo or no data; `domain`, uint8 [n_y][n_x], non-zero = the cell belongs to the verification domain (NULL:
+ * every cell does).
+ * THRESHOLDS: 1 ... 4, each rounded once to float32, not NaN; -inf and +inf are allowed.
+ * RADII: 1 ... 8 integers r, strictly ascending, 0 <= r <= 1023; the window is (2r + 1) x (2r + 1) cells.
+ * BINARY MAPS, float32 comparisons alone: F[b][t] = domain && m == m && m >= thr[t]; O[t] = domain && o == o && o >= thr[t].
+ * WINDOW COUNTS: NF[b][t][w][y][x] = the number of set cells (y', x') of F[b][t] with |y' - y| <= r_w and |x' - x| <= r_w INSIDE
+ * the grid (the window is clipped at the border: nothing is set outside the grid); NO[t][w] likewise of O[t].
+ * SUMS over the cells of the domain, uint64: diff2 = sum (NF - NO)^2, forecast2 = sum NF^2, observed2 = sum NO^2 per (b, t, w);
+ * n_forecast = sum F, n_observed = sum O, n_domain = sum domain per (b, t).  FSS = 1 - diff2 / (forecast2 + observed2) is the
+ * caller's division (neighbourhood.fss).
+ * NO OVERFLOW (a condition, not a measurement): the grid has at most 1023 x 1023 < 2^20 cells (cpol_composite: at most 1024
+ * edges per axis), so a window count is <= 1023^2 < 2^20 and fits the uint32 summed-area tables; its square and the square of a
+ * difference are < 2^40; a sum over at most 2^20 cells is < 2^60 < 2^64.
+ * Every intermediate is an integer: the result depends neither on the order of the additions nor on how the work is cut.
+ * OUTPUTS: sums uint64 [n_blocks][n_thresholds][n_radii][3] (diff2, forecast2, observed2); totals uint64
+ * [n_blocks][n_thresholds][3] (n_forecast, n_observed, n_domain).  n_blocks is the composite's.  `sums` and `totals` follow
+ * p->outputs_on_device like the composite's `count`; `observed` and `domain` lie where cpol_member_verify.obs lies: host arrays
+ * with outputs_on_device 0 (copied to the device first), else memory the device reads in place.
+ * LIMITS (conditions, not measurements): the summed-area tables of all blocks and thresholds and of the observation,
+ * (n_blocks + 1) * n_thresholds * (n_y + 1) * (n_x + 1) * 4 bytes, at most 1 GiB; fewer than 2^31 workgroups per launch.
+ * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: fractions without composite; a composite call that
+ * does not finish; a field that is not in composite->fields; a plane index outside the field's planes; n_thresholds outside
+ * 1..4; a NaN threshold; n_radii outside 1..8; a radius < 0 or > 1023; radii not strictly ascending; NULL observed, sums or
+ * totals; a limit exceeded.
+ * Three kernels (k_frac_rows, k_frac_cols, k_frac_score, cpol_frac.inl) run behind k_comp_finish and before the output copy; a
+ * call without the struct queues exactly what it queued before. */
+#define CPOL_FRAC_MAX_THRESHOLDS 4
+#define CPOL_FRAC_MAX_RADII 8
+#define CPOL_FRAC_MAX_RADIUS 1023
+typedef struct cpol_fractions {
+    int32_t  field;             /* the field whose plane is scored: one of composite->fields                        */
+    int32_t  plane;             /* index into that field's plane order                                             */
+    int32_t  n_thresholds;      /* 1 ... 4                                                                         */
+    int32_t  n_radii;           /* 1 ... 8                                                                         */
+    double   thresholds[CPOL_FRAC_MAX_THRESHOLDS];      /* the field's own linear units, rounded once to float32   */
+    int32_t  radii[CPOL_FRAC_MAX_RADII];                /* strictly ascending, 0 ... 1023                          */
+    const float   *observed;    /* [n_y][n_x]                                                                      */
+    const uint8_t *domain;      /* [n_y][n_x] or NULL = every cell                                                 */
+    uint64_t *sums;             /* [n_blocks][n_thresholds][n_radii][3]                                            */
+    uint64_t *totals;           /* [n_blocks][n_thresholds][3]                                                     */
+} cpol_fractions;
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -596,6 +646,8 @@ typedef struct {
     double *lats, *lons;        /* central sub-beam                             */
     float  *dist, *heights;
     double *model_vars;         /* [n_vars][n_rays*n_gates] (integrate_model)   */
+    cpol_fractions *fractions;  /* NULL (a zero-initialised struct): off.  The fractions skill score's sums of one finished
+                                   plane of `composite` against an observed map, see cpol_fractions */
     float  *sz_total;           /* [n_rays*n_gates][12]  (debug / parity)       */
     cpol_composite *composite;  /* NULL (a zero-initialised struct): off.  Maps of the radar fields above (column maximum, lowest
                                    gate, echo tops), see cpol_composite */
@@ -1018,6 +1070,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * share a cell combined inside the wavefront, 2: every lane on its own; blocking; honours c.phase; needs no staged model or
  * tables; cpol_composite's refusals, and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
  * "composite_stretch" copies one int32: the gates a workgroup of k_comp owns.
+ * "fractions_maps" is the same for the neighbourhood verification: the checks and the three kernels of cpol_frac.inl on
+ * caller-supplied maps.  dst points to { int32_t n_blocks, n_y, n_x, pad; const float *maps; cpol_fractions f; } -- host arrays:
+ * maps [n_blocks][n_y][n_x] float32 (what a finished plane would hold; f.field and f.plane are not read), f.observed, f.domain
+ * (or NULL), f.sums and f.totals; 1 <= n_x, n_y <= 1023; blocking; needs no staged model, tables or composite pass;
+ * cpol_fractions' refusals, and CPOL_ERR_ARG for a bad shape or NULL maps.  Returns 0.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
