@@ -71,7 +71,7 @@ class SweepParams(C.Structure):
         ('n_vbins', C.c_int32), ('debug_flags', C.c_int32), ('c_spectrum', C.c_double),
         # Doppler scheme 3: spectrum broadening (all zero = off)
         ('turbulence_correction', C.c_int32), ('motion_correction', C.c_int32), ('var_edr', C.c_int32),
-        ('pad_broaden_', C.c_int32),
+        ('terrain_shadow', C.c_int32),              # 1: sub-beams stay blocked behind the topography (cosmo_pol_amd/shadow.py); the former padding
         ('sigma_r', C.c_double), ('sigma_theta', C.c_double), ('motion_num', C.c_double), ('motion_den', C.c_double),
         ('v_res', C.c_double),
     ]
@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
-                 'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'model_vars', 'fractions', 'sz_total',
+                 'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'visibility', 'model_vars', 'fractions', 'sz_total',
                  'composite', 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
@@ -893,6 +893,21 @@ class Context(object):
         self._check(self.lib.cpol_debug_scan(self.h, int(form), int(bool(mul)), _ptr(x), _ptr(y), x.shape[0], x.shape[1]),
                     'cpol_debug_scan')
         return y
+
+    def debug_shadow(self, mask, vals):
+        """k_terrain_shadow alone (the test hook cpol_debug_read "terrain_shadow_rows"): mask [n_rows, n_gates] int8 codes and vals [n_vars, n_rows, n_gates] float32
+        -> their shadowed copies (cosmo_pol_amd/shadow.py states the rule)."""
+        mask = np.array(mask, dtype=np.int8, order='C')
+        vals = np.array(vals, dtype=np.float32, order='C')
+        if mask.ndim != 2 or vals.ndim != 3 or vals.shape[1:] != mask.shape:
+            raise ValueError('debug_shadow: mask [n_rows, n_gates] and vals [n_vars, n_rows, n_gates]')
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('n_vars', C.c_int32), ('pad_', C.c_int32),
+                        ('mask', C.c_void_p), ('vals', C.c_void_p)]
+        h = Hook(mask.shape[0], mask.shape[1], vals.shape[0], 0, mask.ctypes.data, vals.ctypes.data)
+        self._check(int(self.lib.cpol_debug_read(self.h, b'terrain_shadow_rows', C.byref(h), C.sizeof(h))),
+                    'cpol_debug_read(terrain_shadow_rows)')
+        return mask, vals
 
     def superob_fields(self, fields, spec, rays_per_block=0, want=None):
         """Test hook (cpol_debug_read "superob_fields"): k_superob on caller-supplied per-gate arrays {name: [n_rows, n_gates]}

@@ -205,4 +205,10 @@ def sanity_check(config):
     if config['radar']['K_squared'] is None:
         from .dielectric import K_squared
         config['radar']['K_squared'] = float(K_squared(config['radar']['frequency']))
+    # terrain shadowing and the visibility array (cosmo_pol_amd/shadow.py): keys of this package alone, read with .get like
+    # antenna_params -- not part of DEFAULTS / VALID_VALUES, which mirror the reference
+    for key in ('terrain_shadow', 'terrain_visibility'):
+        v = integ.get(key)
+        if v is not None and not (isinstance(v, (bool, int, np.integer)) and int(v) in (0, 1)):
+            raise ValueError('integration/%s must be 0 or 1, not %r' % (key, v))
     return config

@@ -42,6 +42,7 @@
 #include "cpol_hist.inl"
 #include "cpol_comp.inl"
 #include "cpol_frac.inl"
+#include "cpol_shadow.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -225,7 +226,7 @@ struct cpol_ctx {
     DevBuf b_bsigma, b_bon;                // spectrum broadening: sigma in bins per sub-beam gate, switch per (ray, sub-beam)
     DevBuf b_vals, b_mask, b_elev, b_coords, b_qmelt, b_fwmelt, b_key, b_par, b_count, b_offset,
         b_units, b_totals, b_perm, b_res, b_pos, b_vn, b_icefirst, b_rvel, b_proj, b_blkranked, b_rec, b_vmask, b_gscan, b_defer;
-    DevBuf b_out[16], b_szinteg, b_sztotal, b_model, b_ticket, b_mask8;
+    DevBuf b_out[16], b_szinteg, b_sztotal, b_model, b_ticket, b_mask8, b_vis;
     DevBuf b_present;                  // k_gate1_ray's sweeps: one word per (ray, 64-gate tile), which hydrometeor slots may have an item there (k_interp_sweep writes, k_gate1_ray reads)
     DevBuf b_colin;                    // cpol_run_columns with host inputs: the caller's columns on the device, read by k_columns_ingest
     DevBuf b_xscr, b_xgeo;             // cpol_interp_subbeams: the long-form gate kernel's scratch values, the geometry of every sub-beam
@@ -802,7 +803,7 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
                      &ctx->b_vn, &ctx->b_icefirst, &ctx->b_rvel, &ctx->b_proj, &ctx->b_blkranked, &ctx->b_rec, &ctx->b_vmask, &ctx->b_gscan, &ctx->b_defer,
-                     &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8,
+                     &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
                      &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
     for (auto &b : ctx->b_out) free_buf(b);
@@ -2901,7 +2902,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_MS };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_MS };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
     static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
@@ -2998,6 +2999,22 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ctx->err = "cpol_run_sweep: sub_smooth needs ml_filter / ml_radius";
         return CPOL_ERR_ARG;
     }
+    // terrain shadowing and the visibility (include/cosmo_pol_amd.h, "Terrain shadowing"): refused here, with nothing queued
+    if (p->terrain_shadow != 0 && p->terrain_shadow != 1) { ctx->err = "cpol_run_sweep: terrain_shadow is 0 or 1"; return CPOL_ERR_ARG; }
+    const bool shadow = p->terrain_shadow == 1;
+    if (shadow && cols) {
+        ctx->err = "cpol_run_columns: terrain_shadow is not taken: the caller's masks stand (shadow them first, cosmo_pol_amd/shadow.py)";
+        return CPOL_ERR_ARG;
+    }
+    if (shadow && (t->site || mode == CPOL_GEOM_SPACEBORNE)) {
+        ctx->err = "cpol_run_sweep: terrain_shadow is not taken with spaceborne geometry (the gates of a swath run from the satellite downward)";
+        return CPOL_ERR_ARG;
+    }
+    if (out->visibility && ml) {
+        ctx->err = "cpol_run_sweep: outputs->visibility is not defined with per-gate weights (integration scheme 'ml')";
+        return CPOL_ERR_ARG;
+    }
+    // (k_terrain_shadow's grid, a quarter of the n_rays * n_sub rows, stays below 2^31: the launch-grid limits above refuse more)
     const long shape[6] = {n_rays, ng, n_sub, n_h, n_v, (ml_tab ? 64 + t->ml_radius * 128L : 0) + (long)mode * 8 + (t->nyquist ? 4 : 0) + (t->site ? 2 : 0) + (cut ? 1 : 0)
                            + (t->varray ? 16 + p->n_vbins * 65536L : 0)};
     void **const views[11] = {&ctx->v_traj_in, &ctx->v_site, &ctx->v_geo, &ctx->v_subh, &ctx->v_subv, &ctx->v_subw,
@@ -3024,6 +3041,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     fi.keep_debug = ctx->keep_debug; fi.timing = ctx->timing; fi.nz = ctx->model.nz;
     fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
     fi.scan_form = CPOL_SCAN_FORM;
+    fi.shadow = shadow;
     fi.n_hydro = n_hyd;
     for (int j = 0; j < n_hyd; ++j) {
         const cpol_hydro_desc &d = ctx->hs.h[j].d;
@@ -3335,7 +3353,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
-                                 out->DSPECTRUM, out->mask_sum8};
+                                 out->DSPECTRUM, out->mask_sum8, out->visibility};
     DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
     own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
     if (hg) for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_HG + k] = &ctx->b_hcounts[k];      // (and a finishing call's counts)
@@ -3356,6 +3374,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // written only if it is asked for too
     arr[O_MASK8].bytes = (size_t)n_rg;                            arr[O_MASK8].produced = out->mask_sum8 != nullptr; own[O_MASK8] = &ctx->b_mask8;
     if (out->mask_sum8 && !out->mask && !ctx->keep_debug) arr[O_MASK].produced = false;
+    // the visible share of the antenna pattern: geometry rows only (an ensemble call: once, like the gate coordinates); only when asked for
+    arr[O_VIS].bytes = (size_t)geo_rays * ng * sizeof(double);    arr[O_VIS].produced = out->visibility != nullptr; own[O_VIS] = &ctx->b_vis;
     // in place (device pointers), into the device image of the caller's pinned window, or into buffers of the context: one rule
     // for the three products (cpol_place.h); the bases are added here
     PlacePlan plan;
@@ -3538,6 +3558,22 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         } else hipLaunchKernelGGL(k_interp_sweep, grid, dim3(256), 0, st, ctx->model, ia);
         ctx->last_stencil = form;
     }
+    // ---- 2s. terrain shadowing: every sub-beam stays blocked behind its first gate below the topography (cpol_shadow.inl); the
+    // forms that interpolate and go on in one launch are off (cpol_forms.h), so b_mask / b_vals hold the whole launch's columns ----
+    if (shadow && !(pk.exp_skip & 1))
+        hipLaunchKernelGGL(k_terrain_shadow, dim3((unsigned)cdiv((long)n_rays * n_sub, CPOL_SHADOW_THREADS / 64)), dim3(CPOL_SHADOW_THREADS), 0, st,
+                           (signed char *)ctx->b_mask.p, (float *)ctx->b_vals.p, (long)n_rays * n_sub, ng, n_vars);
+    // the visible share of the antenna pattern, from the codes as they now stand (the geometry rows: the first member's in an
+    // ensemble call; the sum of the weights as FinalArgs::sum_w below).  The forms that interpolate inside the classifying kernel
+    // write the codes there: the launch then follows that kernel
+    const auto launch_visibility = [&]() {
+        double sum_w = 0;
+        for (int s = 0; s < n_sub; ++s) sum_w += t->sub_w[s];
+        const long n_vis = (long)geo_rays * ng;
+        hipLaunchKernelGGL(k_visibility, dim3((unsigned)cdiv(n_vis, 256)), dim3(256), 0, st, (const signed char *)ctx->b_mask.p,
+                           (const double *)ctx->v_subw, (double *)T[O_VIS], n_vis, ng, n_sub, sum_w);
+    };
+    if (T[O_VIS] && !f.fused && !f.fused_gate1) launch_visibility();
     if (tm && !f.fused && !f.fused_gate1) HIPCHK(hipEventRecord(ctx->ev[EV_INTERP], st));
     if (sub_out) {
         // ---- 2''. cpol_interp_subbeams: geometry of every sub-beam, 'ml' weights, melting, copies; no scattering ----
@@ -3744,6 +3780,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     } else
     hipLaunchKernelGGL(k_classify<false>, dim3(cdiv(n_sbg, CPOL_CLASSIFY_THREADS)),
                        dim3(CPOL_CLASSIFY_THREADS), 0, st, ctx->hs, ctx->its, ca);
+    if (T[O_VIS] && (f.fused || f.fused_gate1)) launch_visibility();
     if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
 
     // ---- 4. counting sort by LUT slice ----
@@ -4443,6 +4480,41 @@ int cpol_debug_scan(cpol_ctx *ctx, int form, int mul, const float *x, float *y, 
     return CPOL_OK;
 }
 
+// The test hook cpol_debug_read "terrain_shadow_rows": k_terrain_shadow alone on caller arrays (host memory, in and out, blocking) --
+// rows no sweep produces (every position of the first hit against the 64-gate chunks, finite values under a hit)
+struct ShadowHook {
+    int32_t n_rows, n_gates, n_vars, pad_;
+    int8_t *mask;                           // [n_rows][n_gates] codes, shadowed in place
+    float *vals;                            // [n_vars][n_rows * n_gates], shadowed in place
+};
+
+static int shadow_hook(cpol_ctx *ctx, const ShadowHook *h)
+{
+    int8_t *const mask = h->mask;
+    float *const vals = h->vals;
+    const int n_rows = h->n_rows, n_gates = h->n_gates, n_vars = h->n_vars;
+    if (!mask || !vals || n_rows < 1 || n_gates < 1 || n_vars < 1 || n_vars > CPOL_MAX_VARS || (long)n_rows * n_gates >= (1L << 31)) {
+        ctx->err = "cpol_debug_read(terrain_shadow_rows): mask and vals, n_rows, n_gates >= 1, 1 <= n_vars <= CPOL_MAX_VARS, n_rows * n_gates < 2^31";
+        return CPOL_ERR_ARG;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t mb = (size_t)n_rows * n_gates, vb = mb * n_vars * sizeof(float);
+    DevBuf dm, dv;
+    int rc;
+    if ((rc = upload(ctx, dm, mask, mb))) return rc;
+    if ((rc = upload(ctx, dv, vals, vb))) { free_buf(dm); return rc; }
+    hipLaunchKernelGGL(k_terrain_shadow, dim3((unsigned)cdiv((long)n_rows, CPOL_SHADOW_THREADS / 64)), dim3(CPOL_SHADOW_THREADS), 0, ctx->stream,
+                       (signed char *)dm.p, (float *)dv.p, (long)n_rows, n_gates, n_vars);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(mask, dm.p, mb, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(vals, dv.p, vb, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    free_buf(dm);
+    free_buf(dv);
+    if (e != hipSuccess) { ctx->err = std::string("cpol_debug_read(terrain_shadow_rows): ") + hipGetErrorString(e); return CPOL_ERR_HIP; }
+    return CPOL_OK;
+}
+
 int cpol_debug_math(cpol_ctx *ctx, int op, const double *x, double *y, int n)
 {
     if (!ctx || !x || !y || n < 1) return CPOL_ERR_ARG;
@@ -4518,6 +4590,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         const int32_t v = COMP_STRETCH;
         memcpy(dst, &v, sizeof v);
         return (int64_t)sizeof v;
+    }
+    if (!strcmp(name, "terrain_shadow_rows")) {     // a CONTROL name: dst points to a ShadowHook
+        if (!dst || max_bytes < (int64_t)sizeof(ShadowHook)) { ctx->err = "cpol_debug_read(terrain_shadow_rows): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return shadow_hook(ctx, (const ShadowHook *)dst);
     }
     if (!strcmp(name, "superob_fields")) {          // a CONTROL name: dst points to a SuperobHook
         if (!dst || max_bytes < (int64_t)sizeof(SuperobHook)) { ctx->err = "cpol_debug_read(superob_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }

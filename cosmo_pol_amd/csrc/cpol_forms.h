@@ -138,6 +138,7 @@ struct FormIn {
     bool keep_debug = false;
     int timing = 0, lanes = 0, nz = 0;
     int scan_form = 0;                 // CPOL_SCAN_FORM of the build (reported, decides nothing)
+    bool shadow = false;               // cpol_sweep_params.terrain_shadow: k_terrain_shadow between the interpolation and the classification
     int n_hydro = 0;
     FormSpecies s[CPOL_MAX_HYDRO];
 };
@@ -244,7 +245,9 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
     // isolated C2 sweep 95.4 -> 88.6 us (one lane back to back: 70 -> 62 us per sweep), but with three lanes in flight 42.2 ->
     // 44.8 us per sweep, and the Ku swath of config 5 (9 800 rays) 0.93 -> 1.18 ms: at the 3 wavefronts per SIMD k_gate1 needs,
     // the interpolation -- VALU-bound at 5 -- loses more than the saved launch and the 14 MB of vals[] give back.
-    f.fused_gate1 = k.fuse_gate1 != 0 && f.gate1 && !cols && !mem;
+    // (terrain shadowing: a gate's values depend on the gates in front of it on its sub-beam, which a kernel that interpolates and
+    // goes on in one launch has not seen -- the interpolation stays a launch of its own, k_terrain_shadow follows it)
+    f.fused_gate1 = k.fuse_gate1 != 0 && f.gate1 && !cols && !mem && !in.shadow;
     // which species' fall-speed sums k_final reads -- 1: vn[] per gate, written by the PSD stage (scheme 2, melting species) or,
     // for the analytic moments of the gamma species under scheme 1, by k_classify; 2: summed over the ray (1-moment ice, numeric
     // integrate_V) and credited to the first valid gate (k_ice_first)
@@ -274,7 +277,8 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
         f.gate1_ray = s.psd_family == CPOL_PSD_GAMMA && !s.numeric_intv && s.q_source == CPOL_Q_MODEL && s.tab && !s.two_d &&
                       ((s.pan_lo == 0 && s.pan_hi >= s.n_pan - 2) || f.g1r >= 2) && s.pre && s.dnu;
     }
-    f.present = f.gate1_ray && pk.gate1_present && !cols && !mem;      // (columns, members: no presence words are written)
+    // (columns, members: no presence words are written; terrain shadowing: they would be written from unshadowed values)
+    f.present = f.gate1_ray && pk.gate1_present && !cols && !mem && !in.shadow;
     // Every slot on an integral table: the items outside the tables (a handful per volume) are listed directly as
     // one-item work units by k_classify / k_gate1 -- key in b_pos, gate in b_perm, count in b_totals -- and the
     // counting sort (LDS ranking in k_classify, k_bucket_scan, k_bucket_scatter) is not run at all.  CPOL_RARE_DIRECT=0,
@@ -288,7 +292,8 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
     f.want_szt = in.want_sz_total || dbg;
     // every slot on a table, no debug reads: the gate kernel classifies its gates itself (k_interp_classify, cpol_fused.inl)
     // (never for columns: the forms that interpolate, k_interp_classify and k_interp_gate1, are replaced by k_columns_ingest)
-    f.fused = k.fuse_classify != 0 && f.rare_direct && !f.gate1 && !in.ml && !dop3 && !dbg && !cols && !sub_out && !mem;
+    // (nor with terrain shadowing: see fused_gate1 above -- the path CPOL_FUSE_CLASSIFY=0 takes)
+    f.fused = k.fuse_classify != 0 && f.rare_direct && !f.gate1 && !in.ml && !dop3 && !dbg && !cols && !sub_out && !mem && !in.shadow;
     f.plain_interp = !cols && !mem && !f.fused && !f.fused_gate1 && !(pk.exp_skip & 1);
     // A launch that is plain k_interp_sweep, of a single beam whose float32 grid coordinates alone are wanted, under a caller's
     // version tag: the gate stencil of its (geometry, heights) pair -- noted at first sight, recorded at the second, replayed from
@@ -396,7 +401,7 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
     // The launch sequence as a HIP graph (CPOL_USE_GRAPH=1): with device outputs and nothing to upload it is captured and
     // replayed while the arguments stay the same (one graph launch instead of ten kernel launches).
     f.graphable = k.use_graph && in.outputs_on_device == 1 && in.timing == 0 && !dbg && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out &&
-                  !mem && !dop3 && in.reuse && !f.want_szt && !in.want_model;
+                  !mem && !dop3 && in.reuse && !f.want_szt && !in.want_model && !in.shadow;
     return f;
 }
 

@@ -42,6 +42,7 @@ _DB_FIELDS = ('ZDR', 'ZV', 'ZH')
 _PRODUCT_OUTPUTS = {'histogram': 'a histogram', 'composite': 'a composite', 'stats': 'ensemble statistics', 'moments': 'moments=',
                     'superob': 'superob='}
 _COORDS = ('lats', 'lons', 'dist', 'heights')
+_ONCE = _COORDS + ('visibility',)             # per geometry row: once, whatever the number of members
 
 
 class ModelVar(object):
@@ -1033,7 +1034,10 @@ class RadarOperator(object):
         sub-beam's become the result's geometry) -- plus 'quad_pts' [n_rays, n_sub, 2] (azimuth, elevation in degrees)
         and 'quad_weights' [n_sub] (per-gate [n_rays, n_sub, n_gates] for integration scheme 'ml').  NumPy arrays or
         torch tensors on the operator's GPU (read in place after torch's current stream; never written).
-        Works without a loaded model.  Returns the dict of simulate_rays."""
+        Works without a loaded model.  Returns the dict of simulate_rays.
+        Terrain shadowing (integration/terrain_shadow) is NOT applied here: the caller's masks stand (cosmo_pol_amd.shadow.apply
+        shadows columns of interpolate_rays(melting=False) on the host).  With integration/terrain_visibility the result
+        carries 'visibility' of the masks as they came."""
         conf = self.__config
         names = self._column_names()
         missing = [k for k in names + ['elev', 'quad_pts', 'quad_weights'] if k not in columns]
@@ -1094,6 +1098,9 @@ class RadarOperator(object):
         w = columns['quad_weights']
         w = w if _is_torch(w) else np.asarray(w, dtype=np.float64)
         ml = len(tuple(w.shape)) == 3
+        want_vis = bool(conf['integration'].get('terrain_visibility', 0))
+        if want_vis and ml:
+            raise ValueError("integration/terrain_visibility: not defined with the per-gate weights of integration scheme 'ml'")
         if ml:
             cols.wgate = per_gate('quad_weights', np.float64)
             sub_w = np.ones(n_sub)
@@ -1138,6 +1145,7 @@ class RadarOperator(object):
             p.c_spectrum = float(self.constants.WAVELENGTH ** 4 / (np.pi ** 5 * conf['radar']['K_squared'] ** 2))
             self._fill_broadening(p, names, float(self.constants.RANGE_RADAR[0]))
         p.geometry_mode = N.GEOM_GROUND_43
+        p.terrain_shadow = 0                           # (the caller's masks stand)
         p.range_step = float(conf['radar']['radial_resolution'])
         p.wavelength = float(self.constants.WAVELENGTH)
         p.k_squared = float(conf['radar']['K_squared'])
@@ -1168,6 +1176,8 @@ class RadarOperator(object):
             if spectrum:
                 spec.append(('DSPECTRUM', np.float64, shape + (p.n_vbins,)))
             spec.append(('mask', np.float64, shape))
+            if want_vis:
+                spec.append(('visibility', np.float64, shape))
             if want_model:
                 spec.append(('model_vars', np.float64, (len(names),) + shape))
             if pinned:
@@ -1238,6 +1248,12 @@ class RadarOperator(object):
         n_rays = len(az)
         if sub is None:
             sub = self._cached('sub', lambda: quadrature.subbeams(conf))
+        # terrain shadowing and the visibility array (cosmo_pol_amd/shadow.py): every entry point built on this method honours them
+        shadow = bool(conf['integration'].get('terrain_shadow', 0))
+        want_vis = bool(conf['integration'].get('terrain_visibility', 0)) and subbeams is None
+        # (swaths: get_GPM_swath refuses shadowing before it comes here, and so does the library)
+        if want_vis and sub.sub_smooth is not None:
+            raise ValueError("integration/terrain_visibility: not defined with the per-gate weights of integration scheme 'ml'")
         version = 0
         if tables is not None:
             traj, geo_t = tables
@@ -1290,6 +1306,7 @@ class RadarOperator(object):
                                      / (np.pi ** 5 * conf['radar']['K_squared'] ** 2))
             p.geometry_mode = mode
             p.debug_flags = int(self.debug_flags)
+            p.terrain_shadow = int(shadow)
             if site is None:
                 re, ke = geo.earth_radius_for_refraction(coords)
                 sin_u1, cos_u1, _ = geo.radar_site_constants(coords)
@@ -1348,7 +1365,7 @@ class RadarOperator(object):
         if version and paths is None and site is None:
             p, t, keep, doppler, spectrum, varray = self._cached(
                 ('prepared', version, n_gates, range0, mode, bool(apply_sensitivity), integrate, device_outputs is not None,
-                 int(self.debug_flags), self._staged_serial),
+                 int(self.debug_flags), self._staged_serial, shadow),
                 prepare, lru=16)
         else:
             p, t, keep, doppler, spectrum, varray = prepare()
@@ -1410,6 +1427,8 @@ class RadarOperator(object):
             if geom is None:
                 spec += [('lats', np.float64, gshape), ('lons', np.float64, gshape),
                          ('dist', np.float32, gshape), ('heights', np.float32, gshape)]
+            if want_vis and gates:
+                spec.append(('visibility', np.float64, gshape))
             if want_model:
                 spec.append(('model_vars', np.float64, (len(self._staged_vars),) + shape))
             # every host output is a view of ONE block of page-locked memory from the operator's pool (N.carve_block); the
@@ -1689,7 +1708,7 @@ class RadarOperator(object):
             return parts[-1]
         if form == 'shared' and len(parts) == 1:
             return parts[0]
-        once = _COORDS + ('n_sub',)
+        once = _ONCE + ('n_sub',)
         join = np.stack if form == 'per_member' else np.concatenate
         if fold and not product.gates:
             # (no per-member array came: the coordinates of the first call, the result of the last)
@@ -1729,7 +1748,7 @@ class RadarOperator(object):
         width = {'RVEL': 8, 'mask': 8, 'DSPECTRUM': 8 * n_vb, 'sz_total': 4 * N.N_SZ, 'mask_sum8': 1}
         out = {}
         for k, ptr in device_outputs.items():
-            if k in ('lats', 'lons', 'dist', 'heights', 'superob', 'stats'):
+            if k in _ONCE + ('superob', 'stats'):
                 out[k] = ptr
             else:
                 out[k] = int(ptr) + n_before * n_rays * n_gates * width.get(k, 4)
@@ -1741,7 +1760,7 @@ class RadarOperator(object):
         for az, el in sweeps:
             res = self.simulate_rays_ensemble(az, el, members=members)
             for j in range(len(members)):
-                one = {k: (v[j] if isinstance(v, np.ndarray) and k not in ('lats', 'lons', 'dist', 'heights') else v)
+                one = {k: (v[j] if isinstance(v, np.ndarray) and k not in _ONCE else v)
                        for k, v in res.items()}
                 per[j].append(self._package(one, az, el))
         pos = self.get_pos_and_time()
@@ -2093,6 +2112,8 @@ class RadarOperator(object):
                  ('mask', np.float64), ('lats', np.float64), ('lons', np.float64)])
         if self.__config['doppler']['scheme'] in (1, 2, 3) and self.__config['radar'].get('type') != 'GPM':
             every.append(('RVEL', np.float64))               # (the spectrum itself is not gathered)
+        if self.__config['integration'].get('terrain_visibility', 0) and self.__config['radar'].get('type') != 'GPM':
+            every.append(('visibility', np.float64))
         if fields is None:
             return every
         known = dict(every)
@@ -2170,6 +2191,8 @@ class RadarOperator(object):
             for k in RADAR_FIELDS + DOPPLER_FIELDS:
                 if k in res:
                     fields[k] = res[k]
+        if 'visibility' in res:                   # (integration/terrain_visibility: the visible share of the antenna pattern)
+            fields['visibility'] = res['visibility']
         if self.output_variables in ('all', 'only_model'):
             for i, name in enumerate(self._staged_vars):
                 fields[name] = res['model_vars'][i]
@@ -2323,7 +2346,7 @@ class RadarOperator(object):
                                         pinned=pinned and len(chunks) == 1, members=chunk, product=product))
         if len(parts) == 1 or device_outputs is not None:
             return parts[-1]
-        once = _COORDS + ('n_sub',)
+        once = _ONCE + ('n_sub',)
         out = {k: (parts[0][k] if k in once else np.concatenate([q[k] for q in parts])) for k in parts[0].keys() if k != name}
         if name in parts[-1]:
             out[name] = product.join([q.get(name) for q in parts], np.concatenate)
@@ -2534,6 +2557,9 @@ class RadarOperator(object):
         from . import gpm
         if not self._check_ready():
             return
+        if self.__config['integration'].get('terrain_shadow', 0):
+            raise NotImplementedError('get_GPM_swath: integration/terrain_shadow is not for swaths (their gates run from the '
+                                      'satellite downward)')
         swath = gpm.read_swath(GPM_file, band)
         freq, res_m = gpm.band_settings(band)
         saved = self.config

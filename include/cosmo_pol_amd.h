@@ -199,7 +199,9 @@ typedef struct {
     int32_t turbulence_correction;  /* 1: add spectral_width_turb(RANGE_RADAR, EDR) to the width of every gate          */
     int32_t motion_correction;      /* 1: add spectral_width_motion(elevation)                                         */
     int32_t var_edr;                /* staged-variable index of the eddy dissipation rate (read only with turbulence)  */
-    int32_t pad_broaden_;
+    int32_t terrain_shadow;         /* 0 (a zero-initialised struct): every gate of a sub-beam depends on itself alone, as in the
+                                       reference.  1: TERRAIN SHADOWING -- a sub-beam stays blocked behind its first gate below the
+                                       topography, see "Terrain shadowing" below.  (The slot was padding: nothing moved.)           */
     double  sigma_r;                /* 0.35 * radial_resolution [m]                                                    */
     double  sigma_theta;            /* deg2rad(3dB_beamwidth) / (4 sqrt(ln 2))                                         */
     double  motion_num;             /* (wavelength / 100) * antenna_speed -- the reference's statement, mm / 100       */
@@ -638,6 +640,33 @@ typedef struct cpol_fractions {
     uint64_t *totals;           /* [n_blocks][n_thresholds][3]                                                     */
 } cpol_fractions;
 
+/* Terrain shadowing (cpol_sweep_params.terrain_shadow, cpol_outputs.visibility; cosmo_pol_amd/shadow.py states the same rule in
+ * NumPy).  Replaces in the reference: nothing that runs -- interpolation_c.c:92-102 writes NaN into every gate from the first one
+ * below the topography onward ("We hit a mountain") and its own loop overwrites those gates again, so that every gate depends on
+ * itself alone.  That accident stays the default (terrain_shadow = 0).
+ *
+ * A ROW is one sub-beam of one ray.  Its codes c[g], g = 0 .. n_gates-1, are as the interpolation leaves them: 0 valid, +1 above
+ * the model top, -1 below the topography or variable 0 NaN (2: outside the domain).
+ *   first = min{ g : c[g] == -1 }, or n_gates when there is none.
+ *   For every g >= first: c[g] = -1 and every staged model variable of that sub-beam gate becomes NaN (a +1 behind the hit becomes
+ *   -1; the NaN is the one the interpolation writes for a gate below the topography).
+ *   Gates g < first keep their bits.  The geometry arrays (lats, lons, dist, heights, elev) are never touched.
+ *   The step runs after the interpolation (in any interpolating form) and before melting, the 'ml' weights, the classification and
+ *   everything behind them: the rest of the launch sequence sees a shadowed gate exactly as it sees a gate below the topography.
+ * With terrain_shadow = 1 the sweep takes the unfused launch forms (k_interp_sweep / record / replay or the member forms, then
+ * k_terrain_shadow, then the second half): no k_interp_classify, no presence words, no graph replay.  cpol_interp_subbeams exports
+ * the shadowed columns.  In an ensemble call every member's rows are shadowed from that member's own codes.
+ *
+ * VISIBILITY, per ray and gate, float64: S = +0.0; for s ascending S += sub_w[s] where the (shadowed, if shadowing is on) code
+ * c[ray, s, gate] != -1; visibility = S / W with W the sum of sub_w[s] ascending from +0.0.  Exactly 1.0 where no sub-beam is
+ * blocked, exactly 0.0 where all are; without shadowing it reports the local below-topography sub-beams alone.  cpol_run_columns
+ * computes it from the ingested masks.
+ *
+ * CPOL_ERR_ARG, nothing queued, the context usable: terrain_shadow outside 0 / 1; terrain_shadow with spaceborne geometry (the
+ * gates of a swath run from the satellite downward); terrain_shadow in cpol_run_columns (the caller's masks stand, and nobody
+ * should believe they were shadowed); visibility with per-gate weights (integration scheme 'ml').
+ * cpol_debug_read "terrain_shadow_rows" runs k_terrain_shadow alone on caller arrays (a test hook, see cpol_debug_read). */
+
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
@@ -645,6 +674,9 @@ typedef struct {
     double *mask;
     double *lats, *lons;        /* central sub-beam                             */
     float  *dist, *heights;
+    double *visibility;         /* [n_rays*n_gates] float64, NULL = not wanted: the visible share of the antenna pattern per gate,
+                                   see "Terrain shadowing" below.  Geometry rows only: in ensemble and timed calls it is stored
+                                   once, like lats (an ensemble call reads the codes of its first member)                        */
     double *model_vars;         /* [n_vars][n_rays*n_gates] (integrate_model)   */
     cpol_fractions *fractions;  /* NULL (a zero-initialised struct): off.  The fractions skill score's sums of one finished
                                    plane of `composite` against an observed map, see cpol_fractions */
@@ -1036,6 +1068,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * "stencil_budget" is a CONTROL name like "enable": dst points to a uint64, the bytes the store may hold (0: stencils off;
  * default 1 GiB).  Root context only and refused (CPOL_ERR_ARG) while lanes of it exist; lowering it below what is held drops
  * every entry.  Returns 0.
+ * "terrain_shadow_rows" is a CONTROL name too, a test hook in the manner of cpol_debug_scan: k_terrain_shadow alone on caller
+ * arrays.  dst points to { int32_t n_rows, n_gates, n_vars, pad; int8_t *mask; float *vals; } -- host arrays, `mask`
+ * [n_rows][n_gates] codes and `vals` [n_vars][n_rows * n_gates], both shadowed in place by the rule of "Terrain shadowing" above;
+ * blocking; needs no staged model.  CPOL_ERR_ARG: a NULL pointer, n_rows / n_gates < 1, n_vars outside 1 .. CPOL_MAX_VARS,
+ * n_rows * n_gates >= 2^31.  Returns 0.
  * "superob_fields" is a CONTROL name too, a test hook: k_superob on caller-supplied per-gate arrays.  dst points to
  * { int32_t n_rows, n_gates; const void *in[10]; cpol_superob so; } -- `in` in the order of cpol_superob.count's rows, host arrays
  * [n_rows * n_gates] float32 (slot ZDR unused, slot RVEL float64, NULL = not given), `so` with host output pointers
