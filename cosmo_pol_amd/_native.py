@@ -160,7 +160,9 @@ class Composite(C.Structure):
                 ('n_x', C.c_int32), ('n_y', C.c_int32), ('use_slab', C.c_int32), ('n_thresholds', C.c_int32 * len(COMPOSITE_FIELDS)),
                 ('h_lo', C.c_double), ('h_hi', C.c_double), ('thresholds', (C.c_double * 4) * len(COMPOSITE_FIELDS)),
                 ('edges_x', C.c_void_p), ('edges_y', C.c_void_p), ('ray_sin', C.c_void_p), ('ray_cos', C.c_void_p),
-                ('values', C.c_void_p * len(COMPOSITE_FIELDS)), ('count', C.c_void_p)]
+                ('values', C.c_void_p * len(COMPOSITE_FIELDS)), ('count', C.c_void_p),
+                ('plane', C.c_int32), ('source', C.c_int32), ('gate_x', C.c_void_p), ('gate_y', C.c_void_p),
+                ('plane_version', C.c_uint64)]
 
 
 class Fractions(C.Structure):
@@ -1045,10 +1047,12 @@ class Context(object):
         return out if int(phase) & 2 else None
 
     @staticmethod
-    def composite_struct(spec, phase=3, rays_per_block=0, azimuths=None):
+    def composite_struct(spec, phase=3, rays_per_block=0, azimuths=None, gate_xy=None, source=0, plane_version=0):
         """(Composite for a call under `spec` (a composite.Composite), the arrays it points into): the edges, the thresholds and
         the slab as the caller gave them (float64; the library rounds thresholds and slab), ray_sin / ray_cos of `azimuths`
-        (degrees; None leaves them NULL), the output pointers the caller's."""
+        (degrees; None leaves them NULL), the output pointers the caller's.  gate_xy = (x, y), float64 arrays of the call's
+        geometry: the gate plane (CPOL_COMP_PLANE_GATES), kept on the device under `plane_version` when that is non-zero;
+        `source`: this call's number for the source_of_* planes."""
         from . import composite as CP
         c = Composite()
         c.fields, c.phase, c.products, c.rays_per_block = spec.mask, int(phase), spec.product_mask, int(rays_per_block)
@@ -1068,7 +1072,22 @@ class Context(object):
             rs, rc = np.ascontiguousarray(rs), np.ascontiguousarray(rc)
             keep += [rs, rc]
             c.ray_sin, c.ray_cos = rs.ctypes.data, rc.ctypes.data
+        if gate_xy is not None:
+            gx, gy = (np.ascontiguousarray(a, dtype=np.float64) for a in gate_xy)
+            if gx.shape != gy.shape:
+                raise ValueError('gate_xy: x %r and y %r differ in shape' % (gx.shape, gy.shape))
+            keep += [gx, gy]
+            c.plane, c.gate_x, c.gate_y, c.plane_version = 1, gx.ctypes.data, gy.ctypes.data, int(plane_version)
+        c.source = int(source)
         return c, keep
+
+    def composite_plane(self):
+        """(uploads, hits) of this context's gate-plane store (cpol_debug_read "composite_plane")."""
+        v = (C.c_int64 * 2)()
+        n = int(self.lib.cpol_debug_read(self.h, b'composite_plane', C.byref(v), 16))
+        if n != 16:
+            self._check(n, 'cpol_debug_read(composite_plane)')
+        return int(v[0]), int(v[1])
 
     def composite_stretch(self):
         """The gates a workgroup of k_comp owns (cpol_debug_read "composite_stretch")."""
@@ -1078,13 +1097,16 @@ class Context(object):
             self._check(n, 'cpol_debug_read(composite_stretch)')
         return int(v.value)
 
-    def composite_fields(self, fields, dist, heights, azimuths, spec, rays_per_block=0, phase=3, lane_form=0, tamper=None):
+    def composite_fields(self, fields, dist, heights, azimuths, spec, rays_per_block=0, phase=3, lane_form=0, tamper=None,
+                         gate_xy=None, source=0, plane_version=0):
         """Test hook (cpol_debug_read "composite_fields"): the plan, the placement, k_comp, k_comp_finish and the context's
         running state on caller-supplied rows -> what composite.finish returns for them.  fields: {field: float32 [..., n_gates]}
         (leading axes are rows); dist, heights: float32 [n_rays, n_gates] (n_rays divides the rows); azimuths [n_rays] degrees;
         `spec`: a composite.Composite; lane_form: 0 the kept form of k_comp, 1 lanes combined inside the wavefront, 2 every lane
-        on its own.  `tamper(c)`: changes the cpol_composite before the call (the refusal tests).  A finishing call returns
-        {'values': {field: {plane: array}}, 'count': {field: array}}, any other None."""
+        on its own.  `tamper(c)`: changes the cpol_composite before the call (the refusal tests).  gate_xy = (x, y), float64
+        [n_rays, n_gates]: the gate plane (`dist` and `azimuths` may then be None), under `plane_version` in the plane store;
+        `source`: the call's number.  A finishing call returns {'values': {field: {plane: array}}, 'count': {field: array}},
+        any other None."""
         from . import composite as CP
 
         class Hook(C.Structure):
@@ -1107,7 +1129,7 @@ class Context(object):
             raise ValueError('composite_fields: no field given')
         hk.n_rows, hk.n_gates = shape
         geo = []
-        for a in (dist, heights):
+        for a in (heights if dist is None else dist, heights):
             a = np.ascontiguousarray(a, dtype=np.float32)
             a = a.reshape(-1, a.shape[-1])
             if a.shape[1] != shape[1] or shape[0] % a.shape[0] or (geo and geo[0].shape != a.shape):
@@ -1115,7 +1137,12 @@ class Context(object):
             geo.append(a)
         keep += geo
         hk.n_rays, hk.dist, hk.heights, hk.lane_form = geo[0].shape[0], geo[0].ctypes.data, geo[1].ctypes.data, int(lane_form)
-        hk.c, ckeep = self.composite_struct(spec, phase, rays_per_block, azimuths=azimuths)
+        if dist is None:
+            hk.dist = None
+        if gate_xy is not None and any(np.size(a) != geo[1].size for a in gate_xy):
+            raise ValueError('composite_fields: gate_xy are [n_rays, n_gates] like heights')
+        hk.c, ckeep = self.composite_struct(spec, phase, rays_per_block, azimuths=azimuths, gate_xy=gate_xy, source=source,
+                                            plane_version=plane_version)
         keep += ckeep
         rpb = int(rays_per_block)
         nb = 1 if rpb <= 0 or shape[0] % rpb else shape[0] // rpb

@@ -41,13 +41,31 @@ THE RULE
              height_of_lowest, echo_top_0 ..., planes not requested absent, empty cells NaN; count uint64
              [n_blocks][n_requested_fields][n_y][n_x], the fields ascending.
   Limits     at most MAX_EDGES edges per axis; the state of all blocks and fields at most MAX_STATE_BYTES; fewer than 2^31
-             workgroups."""
+             workgroups.
+
+NETWORK COMPOSITES: several radars on one geographic or model grid.  Everything above stays as it is.
+  Plane      'radar' (CPOL_COMP_PLANE_RADAR = 0) is the plane above.  On a gate plane (CPOL_COMP_PLANE_GATES = 1) the caller
+             supplies per-gate coordinates gate_x, gate_y, float64 [n_rays * n_gates], read at g mod (n_rays * n_gates) exactly
+             as `dist` is: x = gate_x[g], y = gate_y[g], no multiplication; `dist` is not read and no azimuth is needed.  A gate
+             counts iff v == v, h == h, x == x, y == y, it lies in the grid and it lies in the slab; the cell search is the same
+             comparisons alone.  The library still computes no trigonometric function: every projection is the caller's
+             (`plane_xy`: longitude and latitude, the rotated grid of the model, or any callable).
+  Source     every call carries a number `source`, 0 ... 254, e.g. the index of its radar.  With the product 'source'
+             (CPOL_COMP_SOURCE = 16; it needs 'max' or 'lowest') the plane source_of_max holds the smallest `source` among the
+             counting gates of the whole pass whose key(v) << 32 | key(h) equals the cell's final MAX state, source_of_lowest the
+             same for the LOWEST state: float32 (exact small integers), empty cells NaN.  The planes are then max,
+             height_of_max, source_of_max, lowest, height_of_lowest, source_of_lowest, echo_top_0 ....  The definition is
+             symmetric in the calls: the pass still depends neither on how it is cut into calls nor on their order.  The state
+             gains one source byte per cell, block and product (begin value 255) and a per-call scratch state."""
 import numpy as np
 
 from .histogram import Counts
 
 FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V')
 PRODUCTS = ('max', 'lowest', 'echo_top')             # bit 0, 1, 2 of cpol_composite.products
+SOURCE, SOURCE_BIT = 'source', 16                    # CPOL_COMP_SOURCE (8 is no product and stays refused)
+NO_SOURCE = 255                                      # the begin value of a source byte; sources are 0 ... 254
+PLANES = ('radar', 'geographic', 'model')            # or a callable f(lats, lons) -> (x, y): see plane_xy
 MAX_EDGES = 1024                 # n + 1 of either axis
 MAX_THRESHOLDS = 4               # echo-top planes of one field
 MAX_STATE_BYTES = 1 << 30        # the state of all blocks and fields
@@ -92,9 +110,13 @@ class Composite(object):
     radar-centred grid in metres (`grid` makes a uniform one), `products` out of PRODUCTS, `thresholds` for 'echo_top' ({field:
     1 ... 4 thresholds in the field's own linear units}, or one sequence for every field; `from_db` makes them from dBZ) and the
     optional `height_range` (h_lo, h_hi): only gates with h_lo <= height < h_hi count.  A slab around a nominal height with
-    'max' alone is a pseudo-CAPPI.  ValueError for what the library refuses."""
+    'max' alone is a pseudo-CAPPI.  `plane`: 'radar' (the default: radar-centred metres), 'geographic' (x_edges longitudes,
+    y_edges latitudes, degrees), 'model' (rotated longitudes and latitudes of the staged model's grid) or a callable
+    f(lats, lons) -> (x, y): on every plane but 'radar' the sweep calls hand the library per-gate coordinates made by
+    `plane_xy`, and several radars may fold into one pass.  The product 'source' (beside 'max' or 'lowest') adds the planes
+    source_of_max / source_of_lowest: which call's `source` supplied the cell.  ValueError for what the library refuses."""
 
-    def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None):
+    def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None, plane='radar'):
         if isinstance(fields, str):
             fields = (fields,)
         fields = tuple(fields)
@@ -114,9 +136,14 @@ class Composite(object):
         if not products:
             raise ValueError('products: at least one of %s' % ', '.join(PRODUCTS))
         for q in products:
-            if q not in PRODUCTS:
-                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS)))
-        self.products = tuple(q for q in PRODUCTS if q in products)
+            if q not in PRODUCTS and q != SOURCE:
+                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS + (SOURCE,))))
+        self.products = tuple(q for q in PRODUCTS + (SOURCE,) if q in products)
+        if SOURCE in self.products and 'max' not in self.products and 'lowest' not in self.products:
+            raise ValueError("'source' needs 'max' or 'lowest'")
+        if not (callable(plane) or (isinstance(plane, str) and plane in PLANES)):
+            raise ValueError('plane: one of %s or a callable f(lats, lons) -> (x, y), got %r' % (', '.join(PLANES), plane))
+        self.plane = plane
         self.thresholds = {k: np.zeros(0, dtype=np.float32) for k in self.fields}
         self.thresholds_given = {k: np.zeros(0, dtype=np.float64) for k in self.fields}
         if 'echo_top' in self.products:
@@ -163,24 +190,30 @@ class Composite(object):
     @property
     def product_mask(self):
         """cpol_composite.products."""
-        return sum(1 << PRODUCTS.index(q) for q in self.products)
+        return sum(SOURCE_BIT if q == SOURCE else 1 << PRODUCTS.index(q) for q in self.products)
+
+    @property
+    def gate_plane(self):
+        """True where the sweep calls supply per-gate coordinates (CPOL_COMP_PLANE_GATES): every plane but 'radar'."""
+        return self.plane != 'radar'
 
     def planes(self, field):
         """The names of the planes of values[field], in their order."""
         if field not in self.fields:
             raise ValueError('%r is not a field of the composite' % (field,))
-        out = []
+        out, src = [], SOURCE in self.products
         if 'max' in self.products:
-            out += ['max', 'height_of_max']
+            out += ['max', 'height_of_max'] + ['source_of_max'] * src
         if 'lowest' in self.products:
-            out += ['lowest', 'height_of_lowest']
+            out += ['lowest', 'height_of_lowest'] + ['source_of_lowest'] * src
         return out + ['echo_top_%d' % j for j in range(len(self.thresholds[field]))]
 
     @property
     def key(self):
-        return (self.fields, self.products, self.x_edges.tobytes(), self.y_edges.tobytes(),
-                tuple(self.thresholds[k].tobytes() for k in self.fields),
-                None if self.height_range is None else (self.height_range[0].tobytes(), self.height_range[1].tobytes()))
+        k = (self.fields, self.products, self.x_edges.tobytes(), self.y_edges.tobytes(),
+             tuple(self.thresholds[k].tobytes() for k in self.fields),
+             None if self.height_range is None else (self.height_range[0].tobytes(), self.height_range[1].tobytes()))
+        return k if self.plane == 'radar' else k + (self.plane,)
 
     def __eq__(self, other):
         return isinstance(other, Composite) and self.key == other.key
@@ -194,6 +227,8 @@ class Composite(object):
             s += ', thresholds={%s}' % ', '.join('%s: %s' % (k, [float(t) for t in self.thresholds[k]]) for k in self.fields)
         if self.height_range is not None:
             s += ', height_range=[%g, %g)' % self.height_range
+        if self.plane != 'radar':
+            s += ', plane=%s' % (self.plane if isinstance(self.plane, str) else getattr(self.plane, '__name__', 'callable'))
         return s + ')'
 
 
@@ -238,13 +273,44 @@ def count_shape(spec, n_rows=1, rays_per_block=0):
 
 
 def state_bytes(spec, blocks):
-    """The bytes of the running state of `blocks` blocks (cpol_comp.h: the echo-top states of a field padded to 8 bytes)."""
+    """The bytes of the running state of `blocks` blocks (cpol_comp.h: the echo-top states of a field padded to 8 bytes).  With
+    'source': the source bytes behind it (one per cell, block and product, each array padded to 8 bytes) and the per-call
+    scratch state, as large as the running state without them."""
     per = int(blocks) * spec.n_x * spec.n_y
     total = 0
     for k in spec.fields:
         total += per * 8 * (1 + ('max' in spec.products) + ('lowest' in spec.products))
         total += (per * 4 * len(spec.thresholds[k]) + 7) & ~7
+    if SOURCE in spec.products:
+        total = 2 * total + len(spec.fields) * (('max' in spec.products) + ('lowest' in spec.products)) * ((per + 7) & ~7)
     return total
+
+
+def plane_xy(plane, lats, lons, south_pole=None):
+    """(x, y), float64, of the delivered float64 `lats` / `lons` of a call on `plane`: 'geographic' -> (lons, lats) in degrees as
+    they are; 'model' -> the rotated longitude and latitude through refraction.wgs_to_rotated with `south_pole` (lat, lon: the
+    staged model's pole); a callable f(lats, lons) -> (x, y): any projection of the user's.  The
+    library takes x and y as they come and computes no trigonometric function itself."""
+    lats = np.asarray(lats, dtype=np.float64)
+    lons = np.asarray(lons, dtype=np.float64)
+    if lats.shape != lons.shape:
+        raise ValueError('plane_xy: lats %r and lons %r differ in shape' % (lats.shape, lons.shape))
+    if callable(plane):
+        x, y = plane(lats, lons)
+    elif plane == 'geographic':
+        x, y = lons, lats
+    elif plane == 'model':
+        from .refraction import wgs_to_rotated
+        if south_pole is None:
+            raise ValueError("plane_xy: the 'model' plane needs south_pole = (lat, lon) of the model's rotated grid")
+        y, x = wgs_to_rotated(lats, lons, south_pole[0], south_pole[1])
+    else:
+        raise ValueError("plane_xy: 'geographic', 'model' or a callable (the radar plane has no per-gate coordinates), got %r" % (plane,))
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if x.shape != lats.shape or y.shape != lats.shape:
+        raise ValueError('plane_xy: the plane returned %r and %r for gates of shape %r' % (x.shape, y.shape, lats.shape))
+    return x, y
 
 
 def ray_tables(azimuths):
@@ -253,26 +319,47 @@ def ray_tables(azimuths):
     return np.sin(np.deg2rad(az)), np.cos(np.deg2rad(az))
 
 
-def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0):
+def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0, gate_xy=None, source=0):
     """The rule in NumPy: one call folded into a running state.  fields: {name: float32 [..., n_gates]} for the fields of
     `spec` (leading axes are flattened to rows); dist, heights: float32 [n_rays, n_gates] with n_rays dividing the rows (row r
     takes row r mod n_rays); azimuths: [n_rays] degrees.  `state` (what a former call returned) continues a pass, None begins
-    one.  Returns the state; `finish` decodes it."""
-    dist = np.asarray(dist)
+    one.  gate_xy = (x, y), float64 [n_rays, n_gates]: the gate plane -- the coordinates are taken as they are, `dist` and
+    `azimuths` are not read (both may be None) and a NaN coordinate does not count.  `source` (0 ... 254): this call's number
+    for the source_of_* planes of a spec with 'source'.  Returns the state; `finish` decodes it."""
+    source = int(source)
+    if not 0 <= source < NO_SOURCE:
+        raise ValueError('compose: source must lie in 0 ... %d' % (NO_SOURCE - 1))
+    with_source = SOURCE in spec.products
+    if source and not with_source:
+        raise ValueError("compose: a non-zero source without the product 'source'")
     heights = np.asarray(heights)
-    if dist.dtype != np.float32 or heights.dtype != np.float32:
-        raise ValueError('compose: dist and heights must be float32')
-    ng = dist.shape[-1]
-    dist, heights = dist.reshape(-1, ng), heights.reshape(-1, ng)
-    n_rays = dist.shape[0]
-    rs, rc = ray_tables(azimuths)
-    if heights.shape != dist.shape or len(rs) != n_rays:
-        raise ValueError('compose: dist and heights are [n_rays, n_gates], azimuths [n_rays]')
-    x = dist.astype(np.float64) * rs[:, None]
-    y = dist.astype(np.float64) * rc[:, None]
+    if gate_xy is None:
+        dist = np.asarray(dist)
+        if dist.dtype != np.float32 or heights.dtype != np.float32:
+            raise ValueError('compose: dist and heights must be float32')
+        ng = dist.shape[-1]
+        dist, heights = dist.reshape(-1, ng), heights.reshape(-1, ng)
+        n_rays = dist.shape[0]
+        rs, rc = ray_tables(azimuths)
+        if heights.shape != dist.shape or len(rs) != n_rays:
+            raise ValueError('compose: dist and heights are [n_rays, n_gates], azimuths [n_rays]')
+        x = dist.astype(np.float64) * rs[:, None]
+        y = dist.astype(np.float64) * rc[:, None]
+        located = dist == dist
+    else:
+        x, y = (np.asarray(a) for a in gate_xy)
+        if heights.dtype != np.float32 or x.dtype != np.float64 or y.dtype != np.float64:
+            raise ValueError('compose: heights must be float32, gate_xy float64')
+        ng = heights.shape[-1]
+        heights = heights.reshape(-1, ng)
+        n_rays = heights.shape[0]
+        if x.size != heights.size or y.size != heights.size:
+            raise ValueError('compose: gate_xy are [n_rays, n_gates] like heights')
+        x, y = x.reshape(n_rays, ng), y.reshape(n_rays, ng)
+        located = (x == x) & (y == y)
     ix = np.searchsorted(spec.x_edges, x, side='right') - 1
     iy = np.searchsorted(spec.y_edges, y, side='right') - 1
-    geo = (dist == dist) & (heights == heights) & (ix >= 0) & (ix < spec.n_x) & (iy >= 0) & (iy < spec.n_y)
+    geo = located & (heights == heights) & (ix >= 0) & (ix < spec.n_x) & (iy >= 0) & (iy < spec.n_y)
     if spec.height_range is not None:
         geo &= (spec.height_range[0] <= heights) & (heights < spec.height_range[1])
     cell = np.where(geo, iy * spec.n_x + ix, 0)
@@ -295,7 +382,9 @@ def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0)
                 state = {'spec': spec, 'n_blocks': nb, 'fields': {
                     q: {'max': np.zeros(nb * cells, dtype=_U64), 'lowest': np.full(nb * cells, _LOW_EMPTY, dtype=_U64),
                         'top': np.zeros((len(spec.thresholds[q]), nb * cells), dtype=_U32),
-                        'count': np.zeros(nb * cells, dtype=_U64)} for q in spec.fields}}
+                        'count': np.zeros(nb * cells, dtype=_U64),
+                        'source_of_max': np.full(nb * cells, NO_SOURCE, dtype=np.uint8),
+                        'source_of_lowest': np.full(nb * cells, NO_SOURCE, dtype=np.uint8)} for q in spec.fields}}
             if state['spec'] != spec or state['n_blocks'] != nb:
                 raise ValueError('compose: the spec or the block count differ from the state')
         sel = np.arange(rows) % n_rays
@@ -305,10 +394,20 @@ def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0)
         kh_k = kh[sel][ok]
         st = state['fields'][k]
         np.add.at(st['count'], where, _U64(1))
-        if 'max' in spec.products:
-            np.maximum.at(st['max'], where, (kv << _U64(32)) | kh_k.astype(_U64))
-        if 'lowest' in spec.products:
-            np.minimum.at(st['lowest'], where, (kh_k.astype(_U64) << _U64(32)) | kv)
+        for q, at, pack, won in (('max', np.maximum.at, (kv << _U64(32)) | kh_k.astype(_U64), np.greater),
+                                 ('lowest', np.minimum.at, (kh_k.astype(_U64) << _U64(32)) | kv, np.less)):
+            if q not in spec.products:
+                continue
+            before = st[q].copy() if with_source else None
+            at(st[q], where, pack)
+            if with_source:
+                # the smallest source among the gates of the whole pass that hold the final state: a state this call moved is
+                # this call's; one it reached without moving it keeps the smaller number
+                byte = st['source_of_' + q]
+                byte[won(st[q], before)] = source
+                mine = np.zeros(byte.shape, dtype=bool)
+                mine[where[pack == st[q][where]]] = True
+                byte[mine] = np.minimum(byte[mine], np.uint8(source))
         vv = v[ok]
         for j, t in enumerate(spec.thresholds[k]):
             above = vv >= t
@@ -330,10 +429,14 @@ def finish(state):
             s = st['max']
             planes['max'] = np.where(s == 0, nan, unkey32((s >> _U64(32)).astype(_U32))).reshape(sh)
             planes['height_of_max'] = np.where(s == 0, nan, unkey32((s & _U64(0xFFFFFFFF)).astype(_U32))).reshape(sh)
+            if SOURCE in spec.products:
+                planes['source_of_max'] = np.where(s == 0, nan, st['source_of_max'].astype(np.float32)).reshape(sh)
         if 'lowest' in spec.products:
             s = st['lowest']
             planes['lowest'] = np.where(s == _LOW_EMPTY, nan, unkey32((s & _U64(0xFFFFFFFF)).astype(_U32))).reshape(sh)
             planes['height_of_lowest'] = np.where(s == _LOW_EMPTY, nan, unkey32((s >> _U64(32)).astype(_U32))).reshape(sh)
+            if SOURCE in spec.products:
+                planes['source_of_lowest'] = np.where(s == _LOW_EMPTY, nan, st['source_of_lowest'].astype(np.float32)).reshape(sh)
         for j in range(len(spec.thresholds[k])):
             planes['echo_top_%d' % j] = np.where(st['top'][j] == 0, nan, unkey32(st['top'][j])).reshape(sh)
         out['values'][k] = planes
@@ -357,12 +460,35 @@ class Maps(object):
         if distributed:
             raise NotImplementedError('composites with a process group: sharding rays over ranks is not built')
         self.spec, self.gates, self.phase, self.rays_per_block = spec, bool(keep_gates), int(phase), int(rays_per_block)
+        self.gate_xy, self.plane_version, self.source = None, 0, 0
+
+    def set_plane(self, gate_xy, plane_version=0, source=0):
+        """The call's part of a network composite: gate_xy = (x, y), float64 [n_rays, n_gates] of THIS call's rays on the spec's
+        plane (plane_xy of the call's gate coordinates; None on the radar plane), `plane_version` non-zero where the library may
+        keep its device copy under that tag, and `source`, the call's number for the source_of_* planes.  May be set anew
+        between the calls of a pass, like `phase`."""
+        source = int(source)
+        if not 0 <= source < NO_SOURCE:
+            raise ValueError('source must lie in 0 ... %d, got %d' % (NO_SOURCE - 1, source))
+        if source and SOURCE not in self.spec.products:
+            raise ValueError("a non-zero source needs the product 'source'")
+        if gate_xy is not None and not self.spec.gate_plane:
+            raise ValueError("gate_xy goes with a plane other than 'radar'")
+        self.gate_xy, self.plane_version, self.source = gate_xy, int(plane_version), source
 
     def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
         self.n_rows = len(az) * (n_members or 1)
         n_blocks(self.n_rows, self.rays_per_block)            # (ValueError: the library refuses the same)
-        # (sine and cosine of the azimuths come from here: the library computes neither)
-        self.c, keep = native.Context.composite_struct(self.spec, self.phase, self.rays_per_block, azimuths=az)
+        xy = self.gate_xy
+        if self.spec.gate_plane and xy is None and take is not None:
+            raise ValueError('a composite on the plane %r needs the per-gate coordinates of the call (set_plane)' % (self.spec.plane,))
+        if xy is not None and any(np.shape(a) != (len(az), n_gates) for a in xy):
+            raise ValueError('gate_xy: two arrays [n_rays, n_gates] = %r' % ((len(az), n_gates),))
+        # (sine and cosine of the azimuths come from here, the plane coordinates from plane_xy: the library computes neither)
+        self.c, keep = native.Context.composite_struct(self.spec, self.phase, self.rays_per_block, azimuths=None if xy is not None else az,
+                                                       gate_xy=xy, source=self.source, plane_version=self.plane_version)
+        if self.spec.gate_plane:
+            self.c.plane = 1                      # (device outputs: bind_device brings gate_x and gate_y)
         return {'composite': self.c}, keep
 
     def arrays(self):
@@ -379,6 +505,10 @@ class Maps(object):
             self.c.values[FIELDS.index(path)] = address
 
     def bind_device(self, entry):         # {'values': {field: device pointer of its float32 planes}, 'count': device pointer}
+        entry = dict(entry)               # (a gate plane: 'gate_x', 'gate_y' device pointers of float64 [n_rays, n_gates], any phase)
+        for k in ('gate_x', 'gate_y'):
+            if k in entry:
+                setattr(self.c, k, entry.pop(k))
         for k, ptr in (entry.items() if self.phase & 2 else ()):
             if k not in ('values', 'count'):
                 raise ValueError("device_outputs['composite']: unknown entry %r" % (k,))

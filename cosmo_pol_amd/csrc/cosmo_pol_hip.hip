@@ -193,6 +193,20 @@ struct cpol_ctx {
     // edges of the pass, the per-ray sines and cosines of the call, the maps of a finishing call outside a window image and the
     // caller's device memory (nine `values`, then `count`); the pass (cpol_comp.h)
     DevBuf b_cstate, b_cedges, b_crays, b_cout[CPOL_COMP_FIELDS + 1];
+    // ... and the gate planes (CPOL_COMP_PLANE_GATES with host arrays): gate_x then gate_y of the last N_COMP_PLANES non-zero
+    // plane_version tags stay on the device, as the table sets do, so the radars of a network that alternate in one pass do not
+    // evict each other; a call without a tag uploads into b_cplane.  cplane_stat: {uploads, hits} (cpol_debug_read "composite_plane")
+    struct CompPlane {
+        uint64_t version = 0, last_use = 0;
+        size_t gates = 0;
+        DevBuf buf;
+    };
+    static constexpr int N_COMP_PLANES = 32;
+    static_assert(N_COMP_PLANES >= N_TABLE_SETS, "a gate plane per resident table set");
+    CompPlane cplanes[N_COMP_PLANES];
+    uint64_t cplane_clock = 0;
+    int64_t cplane_stat[2] = {0, 0};
+    DevBuf b_cplane;
     CompPass cpass;
     CompPlan cplan;                        // ... and the plan of the call at hand (kept here: a call without the struct constructs none)
     std::vector<double> cedges_host;       // ... and what b_cedges holds (the source of its copy)
@@ -798,7 +812,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -806,6 +820,7 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
                      &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
+    for (auto &cp : ctx->cplanes) free_buf(cp.buf);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
         free_buf(ctx->d_table[j]);
@@ -2601,9 +2616,11 @@ static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &cal
 
 // in: the per-gate device arrays in the order of the fields; dist, hgt: the geometry's device arrays, holding geo_rays rows of ng
 // gates; n_rg: the gates of the call; T: where a finishing call's maps go (nine `values`, then `count`); lane_form: 0 the kept
-// form of k_comp, 1 combined, 2 every lane on its own.  Begins, composes, finishes; then the pass is advanced
+// form of k_comp, 1 combined, 2 every lane on its own; plane_on_host: gate_x / gate_y of a gate plane are host arrays (copied on
+// `st`, or found in the plane store under plane_version), else memory the device reads in place.  Begins, composes (a SOURCE
+// pass: into the scratch state, then k_comp_merge), finishes; then the pass is advanced
 static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &pl, const void *const in[CPOL_COMP_FIELDS], const void *dist,
-                       const void *hgt, int geo_rays, long n_rg, int ng, void *const T[CP_N], int lane_form, hipStream_t st)
+                       const void *hgt, int geo_rays, long n_rg, int ng, void *const T[CP_N], int lane_form, bool plane_on_host, hipStream_t st)
 {
     const size_t n_ex = (size_t)pl.n_x + 1, n_ey = (size_t)pl.n_y + 1;
     if (pl.begin) {
@@ -2612,24 +2629,73 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             blob.assign(pl.ex.begin(), pl.ex.end());
             blob.insert(blob.end(), pl.ey.begin(), pl.ey.end());
         } catch (...) { ctx->err = "cpol_composite: out of host memory"; return CPOL_ERR_NOMEM; }
-        ENSURE(ctx->b_cstate, (size_t)pl.state_bytes);
+        ENSURE(ctx->b_cstate, (size_t)pl.total_bytes);
         ENSURE(ctx->b_cedges, (n_ex + n_ey) * sizeof(double));
-        // the begin values: max states and counts 0, min states all ones
+        // the begin values: max states and counts 0, min states all ones; SOURCE: the source bytes behind them all ones too
+        // (255), then the scratch state like the running one
         HIPCHK(hipMemsetAsync(ctx->b_cstate.p, 0, (size_t)pl.zero_bytes, st));
-        if (pl.state_bytes > pl.zero_bytes)
-            HIPCHK(hipMemsetAsync((char *)ctx->b_cstate.p + pl.zero_bytes, 0xFF, (size_t)(pl.state_bytes - pl.zero_bytes), st));
+        const long ones_end = pl.with_source ? pl.off_scratch : pl.state_bytes;
+        if (ones_end > pl.zero_bytes)
+            HIPCHK(hipMemsetAsync((char *)ctx->b_cstate.p + pl.zero_bytes, 0xFF, (size_t)(ones_end - pl.zero_bytes), st));
+        if (pl.with_source) {
+            char *const scratch = (char *)ctx->b_cstate.p + pl.off_scratch;
+            HIPCHK(hipMemsetAsync(scratch, 0, (size_t)pl.zero_bytes, st));
+            if (pl.state_bytes > pl.zero_bytes)
+                HIPCHK(hipMemsetAsync(scratch + pl.zero_bytes, 0xFF, (size_t)(pl.state_bytes - pl.zero_bytes), st));
+        }
         HIPCHK(hipMemcpyAsync(ctx->b_cedges.p, blob.data(), (n_ex + n_ey) * sizeof(double), hipMemcpyHostToDevice, st));
         ctx->cpass.open = false;                  // (whatever fails from here on, no half-begun pass stays open)
     }
-    // the per-ray sines and cosines of this call
-    ENSURE(ctx->b_crays, 2 * (size_t)geo_rays * sizeof(double));
-    HIPCHK(hipMemcpyAsync(ctx->b_crays.p, c->ray_sin, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync((double *)ctx->b_crays.p + geo_rays, c->ray_cos, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
+    const bool gates = pl.plane == CPOL_COMP_PLANE_GATES;
+    const double *gx = nullptr, *gy = nullptr;
+    if (!gates) {
+        // the per-ray sines and cosines of this call
+        ENSURE(ctx->b_crays, 2 * (size_t)geo_rays * sizeof(double));
+        HIPCHK(hipMemcpyAsync(ctx->b_crays.p, c->ray_sin, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((double *)ctx->b_crays.p + geo_rays, c->ray_cos, (size_t)geo_rays * sizeof(double), hipMemcpyHostToDevice, st));
+    } else if (!plane_on_host) {
+        gx = c->gate_x; gy = c->gate_y;
+    } else {
+        // the caller's per-gate coordinates: under a tag the store's copy (an upload on a miss, into the entry used longest ago),
+        // without one a copy per call
+        const size_t n_geo = (size_t)geo_rays * (size_t)ng;
+        DevBuf *buf = &ctx->b_cplane;
+        bool copy = true;
+        if (c->plane_version) {
+            cpol_ctx::CompPlane *e = nullptr, *lru = &ctx->cplanes[0];
+            for (auto &q : ctx->cplanes) {
+                if (q.version == c->plane_version && q.gates == n_geo && q.buf.p) { e = &q; break; }
+                if (q.last_use < lru->last_use) lru = &q;
+            }
+            copy = e == nullptr;
+            if (!e) { e = lru; e->version = 0; }
+            e->last_use = ++ctx->cplane_clock;
+            buf = &e->buf;
+            if (copy) {
+                ENSURE(*buf, 2 * n_geo * sizeof(double));
+                e->gates = n_geo;
+            }
+            ctx->cplane_stat[copy ? 0 : 1] += 1;
+            if (copy) {
+                HIPCHK(hipMemcpyAsync(buf->p, c->gate_x, n_geo * sizeof(double), hipMemcpyHostToDevice, st));
+                HIPCHK(hipMemcpyAsync((double *)buf->p + n_geo, c->gate_y, n_geo * sizeof(double), hipMemcpyHostToDevice, st));
+                e->version = c->plane_version;
+            }
+        } else {
+            ENSURE(*buf, 2 * n_geo * sizeof(double));
+            HIPCHK(hipMemcpyAsync(buf->p, c->gate_x, n_geo * sizeof(double), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync((double *)buf->p + n_geo, c->gate_y, n_geo * sizeof(double), hipMemcpyHostToDevice, st));
+        }
+        gx = (const double *)buf->p; gy = gx + n_geo;
+    }
     const auto pow2_below = [](int n) { int s = 1; while (2 * s <= n) s *= 2; return n > 0 ? s : 0; };
     const long block_gates = pl.rows_per_block * (long)ng;
     const long stretches = cdiv(block_gates, (long)COMP_STRETCH);
     char *const base = (char *)ctx->b_cstate.p;
     const auto at = [&](long off) { return off < 0 ? nullptr : base + off; };
+    // (a SOURCE pass: k_comp fills the per-call scratch state, which has the offsets of the running one)
+    const long into = pl.with_source ? pl.off_scratch : 0;
+    const auto st_at = [&](long off) { return off < 0 ? nullptr : base + into + off; };
     const bool combine = lane_form == 0 ? CPOL_COMP_COMBINE != 0 : lane_form == 1;
     for (int i = 0; i < pl.n_fields; ++i) {
         const int k = pl.field[i];
@@ -2637,8 +2703,9 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
         ca.v = (const float *)in[k]; ca.dist = (const float *)dist; ca.hgt = (const float *)hgt;
         ca.ex = (const double *)ctx->b_cedges.p; ca.ey = ca.ex + n_ex;
         ca.ray_sin = (const double *)ctx->b_crays.p; ca.ray_cos = ca.ray_sin + geo_rays;
-        ca.smax = (unsigned long long *)at(pl.off_max[k]); ca.slow = (unsigned long long *)at(pl.off_low[k]);
-        ca.scount = (unsigned long long *)at(pl.off_count[k]); ca.stop = (unsigned *)at(pl.off_top[k]);
+        ca.gx = gx; ca.gy = gy;
+        ca.smax = (unsigned long long *)st_at(pl.off_max[k]); ca.slow = (unsigned long long *)st_at(pl.off_low[k]);
+        ca.scount = (unsigned long long *)st_at(pl.off_count[k]); ca.stop = (unsigned *)st_at(pl.off_top[k]);
         ca.block_gates = block_gates;
         ca.geo_gates = (long)geo_rays * ng;
         ca.n_gates = ng;
@@ -2651,9 +2718,26 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
         for (int j = 0; j < pl.n_thr[k]; ++j) ca.thr[j] = pl.thr[k][(size_t)j];
         const unsigned grid = (unsigned)(pl.n_blocks * stretches);
         const size_t lds = (n_ex + n_ey) * sizeof(double);          // (at most 16 KiB)
-        if (combine) hipLaunchKernelGGL(k_comp<true>, dim3(grid), dim3(COMP_THREADS), lds, st, ca);
-        else hipLaunchKernelGGL(k_comp<false>, dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+        if (gates) {
+            if (combine) hipLaunchKernelGGL((k_comp<true, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+            else hipLaunchKernelGGL((k_comp<false, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+        } else {
+            if (combine) hipLaunchKernelGGL((k_comp<true, false>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+            else hipLaunchKernelGGL((k_comp<false, false>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+        }
         HIPCHK(hipGetLastError());
+        if (pl.with_source) {
+            CompMergeArgs ma{};
+            ma.rmax = (unsigned long long *)at(pl.off_max[k]); ma.rlow = (unsigned long long *)at(pl.off_low[k]);
+            ma.rcount = (unsigned long long *)at(pl.off_count[k]); ma.rtop = (unsigned *)at(pl.off_top[k]);
+            ma.smax = ca.smax; ma.slow = ca.slow; ma.scount = ca.scount; ma.stop = ca.stop;
+            ma.bmax = (unsigned char *)at(pl.off_src_max[k]); ma.blow = (unsigned char *)at(pl.off_src_low[k]);
+            ma.n = pl.n_blocks * pl.cells;
+            ma.cells = (int)pl.cells; ma.n_thr = pl.n_thr[k];
+            ma.source = (unsigned)pl.source;
+            hipLaunchKernelGGL(k_comp_merge, dim3((unsigned)cdiv(ma.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, ma);
+            HIPCHK(hipGetLastError());
+        }
     }
     if (pl.finish)
         for (int i = 0; i < pl.n_fields; ++i) {
@@ -2665,6 +2749,7 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             fa.count = (unsigned long long *)T[CP_COUNT] + (size_t)pl.slot[k] * pl.cells;
             fa.n = pl.n_blocks * pl.cells;
             fa.cells = (int)pl.cells; fa.n_planes = pl.n_planes[k]; fa.n_fields = pl.n_fields; fa.n_thr = pl.n_thr[k];
+            fa.bmax = (const unsigned char *)at(pl.off_src_max[k]); fa.blow = (const unsigned char *)at(pl.off_src_low[k]);
             hipLaunchKernelGGL(k_comp_finish, dim3((unsigned)cdiv(fa.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, fa);
             HIPCHK(hipGetLastError());
         }
@@ -2685,7 +2770,7 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
 struct CompHook {
     int32_t n_rows, n_gates, n_rays, lane_form;
     const float *in[CPOL_COMP_FIELDS];      // [n_rows * n_gates]; NULL = not given
-    const float *heights, *dist;            // [n_rays * n_gates]
+    const float *heights, *dist;            // [n_rays * n_gates]; dist may be NULL on a gate plane (c.gate_x, c.gate_y: host arrays)
     cpol_composite c;
 };
 
@@ -2704,7 +2789,8 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
     if (rc != CPOL_OK) return rc;
     for (int i = 0; i < pl.n_fields; ++i)
         if (!hk->in[pl.field[i]]) { ctx->err = "composite_fields: a requested field has no input"; return CPOL_ERR_ARG; }
-    if (!hk->heights || !hk->dist) { ctx->err = "composite_fields: heights and dist are needed"; return CPOL_ERR_ARG; }
+    const bool hk_gates = hk->c.plane == CPOL_COMP_PLANE_GATES;
+    if (!hk->heights || (!hk->dist && !hk_gates)) { ctx->err = "composite_fields: heights and dist are needed"; return CPOL_ERR_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)hk->n_rows * hk->n_gates, n_geo = (size_t)hk->n_rays * hk->n_gates;
     const void *in[CPOL_COMP_FIELDS] = {};
@@ -2713,7 +2799,7 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
         if ((rc = upload(ctx, ctx->b_out[k], hk->in[k], n * sizeof(float))) != CPOL_OK) return rc;
         in[k] = ctx->b_out[k].p;
     }
-    if ((rc = upload(ctx, ctx->b_out[12], hk->dist, n_geo * sizeof(float))) != CPOL_OK) return rc;
+    if (hk->dist && (rc = upload(ctx, ctx->b_out[12], hk->dist, n_geo * sizeof(float))) != CPOL_OK) return rc;
     if ((rc = upload(ctx, ctx->b_out[13], hk->heights, n_geo * sizeof(float))) != CPOL_OK) return rc;
     PlacePlan plan;
     place_outputs(arr, CP_N, 0, false, &plan);
@@ -2721,8 +2807,8 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
     for (int k = 0; k < CP_N; ++k) own[k] = &ctx->b_cout[k];
     void *T[CP_N];
     if ((rc = place_resolve(ctx, arr, CP_N, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = comp_launch(ctx, &hk->c, pl, in, ctx->b_out[12].p, ctx->b_out[13].p, hk->n_rays, (long)n, hk->n_gates, T, hk->lane_form,
-                          ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = comp_launch(ctx, &hk->c, pl, in, hk->dist ? ctx->b_out[12].p : nullptr, ctx->b_out[13].p, hk->n_rays, (long)n, hk->n_gates, T,
+                          hk->lane_form, true, ctx->stream)) != CPOL_OK) return rc;
     if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return CPOL_OK;
@@ -4158,7 +4244,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // call decodes the state into the maps where the plan placed them (outside launch_all too) ----
     if (cp) {
         const void *const cp_in[CPOL_COMP_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV]};
-        if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, st)) != CPOL_OK) return rc;
+        if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, p->outputs_on_device != 1, st)) != CPOL_OK) return rc;
         // ---- neighbourhood verification: three kernels behind k_comp_finish, on the finished plane where the plan placed it ----
         if (fr && (rc = frac_launch(ctx, fr, fr_pl, (const float *)T_all[A_CP + fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride,
                                     p->outputs_on_device == 0, T_all + A_FR, st)) != CPOL_OK) return rc;
@@ -4584,6 +4670,11 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "fractions_maps")) {          // a CONTROL name: dst points to a FracHook
         if (!dst || max_bytes < (int64_t)sizeof(FracHook)) { ctx->err = "cpol_debug_read(fractions_maps): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return frac_hook(ctx, (const FracHook *)dst);
+    }
+    if (!strcmp(name, "composite_plane")) {         // {uploads, hits} of this context's gate-plane store
+        if (!dst || max_bytes < (int64_t)sizeof ctx->cplane_stat) return CPOL_ERR_ARG;
+        memcpy(dst, ctx->cplane_stat, sizeof ctx->cplane_stat);
+        return (int64_t)sizeof ctx->cplane_stat;
     }
     if (!strcmp(name, "composite_stretch")) {
         if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;

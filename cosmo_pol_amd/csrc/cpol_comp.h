@@ -1,7 +1,10 @@
 // cpol_comp.h -- gridded composites (cpol_composite): every refusal, the rounding of the slab and the thresholds to float32, the
-// plane list, the layout of the running state and the block arithmetic of a call, decided by comp_check() from plain numbers.
+// plane list, the plane (radar-centred or the caller's per-gate coordinates), the source, the layout of the running state (with
+// SOURCE: its source bytes and the per-call scratch behind it) and the block arithmetic of a call, decided by comp_check() from
+// plain numbers.
 // Plain C++ without HIP types, so that a host program can include it (tests/c_host/comp_check.cpp, tests/test_composite_cpu.py
-// check it without a GPU).  The kernels are k_comp and k_comp_finish (cpol_comp.inl); the rule is stated in
+// check it without a GPU; comp_check_network.cpp, test_composite_network_cpu.py the network additions).  The kernels are k_comp,
+// k_comp_merge and k_comp_finish (cpol_comp.inl); the rule is stated in
 // include/cosmo_pol_amd.h and cosmo_pol_amd/composite.py.
 #pragma once
 
@@ -20,7 +23,8 @@ constexpr long COMP_MAX_STATE_BYTES = 1L << 30;    // the state of all blocks an
 // is long enough for its own 12 KB of gates to outweigh them; the 180 000 gates of a 360 x 500 sweep give 176 workgroups
 constexpr int COMP_STRETCH = 1024;
 constexpr int COMP_THREADS = 256;                  // threads of a workgroup of k_comp and k_comp_finish
-constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP;
+constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE;
+constexpr int COMP_NO_SOURCE = 255;               // the begin value of a source byte: no call has set the cell
 
 // what the entry point knows of the call
 struct CompCall {
@@ -34,6 +38,7 @@ struct CompCall {
 struct CompPass {
     bool open = false;
     uint32_t fields = 0, products = 0;
+    int plane = 0;
     long n_blocks = 0;
     bool slab = false;
     float h_lo = 0.f, h_hi = 0.f;
@@ -47,7 +52,7 @@ struct CompPlan {
     int field[COMP_FIELDS] = {};                   // the requested fields, ascending
     int slot[COMP_FIELDS] = {};                    // field k's row of `count`
     int n_thr[COMP_FIELDS] = {};
-    int n_planes[COMP_FIELDS] = {};                // of values[k]: 2 (MAX) + 2 (LOWEST) + n_thr
+    int n_planes[COMP_FIELDS] = {};                // of values[k]: 2 (MAX) + 2 (LOWEST) + n_thr, with SOURCE one more per MAX and LOWEST
     int n_x = 0, n_y = 0;
     long cells = 0;                                // n_x * n_y
     uint32_t products = 0;
@@ -61,6 +66,13 @@ struct CompPlan {
     // per field the LOWEST states (uint64 [n_blocks][cells]).  -1: the field has none
     long off_max[COMP_FIELDS] = {}, off_count[COMP_FIELDS] = {}, off_top[COMP_FIELDS] = {}, off_low[COMP_FIELDS] = {};
     long zero_bytes = 0, state_bytes = 0;
+    // behind the running state, with SOURCE alone: the source bytes (uint8 [n_blocks][cells] per field and product, begin value
+    // 255, each padded to 8 bytes: -1 the field has none), then the per-call scratch state, state_bytes with the offsets and the
+    // begin values of the running state.  total_bytes = state_bytes without SOURCE: what the 1 GiB limit counts
+    long off_src_max[COMP_FIELDS] = {}, off_src_low[COMP_FIELDS] = {};
+    long off_scratch = -1, total_bytes = 0;
+    int plane = 0, source = 0;
+    bool with_source = false;
     bool begin = false, finish = false;
 };
 
@@ -82,7 +94,13 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     if (((c->fields >> COMP_FIELDS) & 1u)) return "RVEL is float64 and is not composed";
     if (c->fields == 0 || (c->fields >> COMP_FIELDS) != 0) return "fields must name at least one of the 9 float32 fields and no other bit";
     if (c->products == 0 || (c->products & ~COMP_PRODUCTS) != 0) return "products must name MAX, LOWEST or ECHO_TOP and no other bit";
+    if (c->plane != CPOL_COMP_PLANE_RADAR && c->plane != CPOL_COMP_PLANE_GATES) return "plane must be CPOL_COMP_PLANE_RADAR or CPOL_COMP_PLANE_GATES";
+    if (c->source < 0 || c->source >= COMP_NO_SOURCE) return "source must lie in 0 ... 254";
+    pl->with_source = (c->products & CPOL_COMP_SOURCE) != 0;
+    if (c->source != 0 && !pl->with_source) return "a non-zero source without SOURCE";
+    if (pl->with_source && !(c->products & (CPOL_COMP_MAX | CPOL_COMP_LOWEST))) return "products: SOURCE needs MAX or LOWEST";
     pl->products = c->products;
+    pl->plane = c->plane; pl->source = c->source;
     const bool tops = (c->products & CPOL_COMP_ECHO_TOP) != 0;
     for (int k = 0; k < COMP_FIELDS; ++k) {
         if (!((c->fields >> k) & 1u)) continue;
@@ -98,7 +116,8 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         pl->slot[k] = pl->n_fields;
         pl->field[pl->n_fields++] = k;
         pl->n_thr[k] = nt;
-        pl->n_planes[k] = ((c->products & CPOL_COMP_MAX) ? 2 : 0) + ((c->products & CPOL_COMP_LOWEST) ? 2 : 0) + nt;
+        const int per_product = (c->products & CPOL_COMP_SOURCE) ? 3 : 2;
+        pl->n_planes[k] = ((c->products & CPOL_COMP_MAX) ? per_product : 0) + ((c->products & CPOL_COMP_LOWEST) ? per_product : 0) + nt;
     }
     if (c->use_slab) {
         pl->slab = true;
@@ -109,7 +128,9 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     if (c->n_x < 1 || c->n_y < 1) return "n_x and n_y must be >= 1";
     if (c->n_x + 1 > COMP_MAX_EDGES || c->n_y + 1 > COMP_MAX_EDGES) return "n_x + 1 and n_y + 1 must be at most 1024";
     if (!c->edges_x || !c->edges_y) return "edges_x or edges_y is NULL";
-    if (!c->ray_sin || !c->ray_cos) return "ray_sin or ray_cos is NULL";
+    if (c->plane == CPOL_COMP_PLANE_GATES) {
+        if (!c->gate_x || !c->gate_y) return "gate_x or gate_y is NULL";
+    } else if (!c->ray_sin || !c->ray_cos) return "ray_sin or ray_cos is NULL";
     pl->n_x = c->n_x; pl->n_y = c->n_y;
     pl->cells = (long)c->n_x * c->n_y;
     if (c->rays_per_block < 0 || (c->rays_per_block > 0 && call.n_rows % c->rays_per_block != 0))
@@ -132,6 +153,18 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         for (int i = 0; i < pl->n_fields; ++i) { pl->off_low[pl->field[i]] = off; off += per * 8; }
     if (off > COMP_MAX_STATE_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
     pl->state_bytes = off;
+    for (int k = 0; k < COMP_FIELDS; ++k) pl->off_src_max[k] = pl->off_src_low[k] = -1;
+    if (pl->with_source) {
+        for (int i = 0; i < pl->n_fields; ++i) {
+            const int k = pl->field[i];
+            if (c->products & CPOL_COMP_MAX) { pl->off_src_max[k] = off; off += (per + 7) & ~7L; }
+            if (c->products & CPOL_COMP_LOWEST) { pl->off_src_low[k] = off; off += (per + 7) & ~7L; }
+        }
+        pl->off_scratch = off;
+        off += pl->state_bytes;
+        if (off > COMP_MAX_STATE_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
+    }
+    pl->total_bytes = off;
     // (one workgroup per stretch of a block: the grid of one launch; out of reach while the call holds fewer than 2^31 gates)
     if (pl->n_blocks * ((pl->rows_per_block * (long)call.n_gates + COMP_STRETCH - 1) / COMP_STRETCH) >= (1L << 31))
         return "too many workgroups in one call";
@@ -144,6 +177,7 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         if (!pass.open) return "a composing call with no pass open and no begin bit";
         if (pass.fields != c->fields || pass.products != c->products || pass.n_blocks != pl->n_blocks)
             return "fields, products or block count differ from the open pass";
+        if (pass.plane != c->plane) return "the plane differs from the open pass";
         if (pass.slab != pl->slab || (pl->slab && (pass.h_lo != pl->h_lo || pass.h_hi != pl->h_hi)))
             return "the height slab differs from the open pass";
         for (int i = 0; i < pl->n_fields; ++i)
@@ -165,6 +199,7 @@ inline void comp_advance(const cpol_composite *c, const CompPlan &pl, CompPass *
         pass->open = true;
         pass->fields = c->fields;
         pass->products = c->products;
+        pass->plane = c->plane;
         pass->n_blocks = pl.n_blocks;
         pass->slab = pl.slab; pass->h_lo = pl.h_lo; pass->h_hi = pl.h_hi;
         for (int k = 0; k < COMP_FIELDS; ++k) pass->thr[k] = pl.thr[k];

@@ -1,5 +1,5 @@
 // cpol_comp.inl -- gridded composites: the column maximum, the lowest gate and echo-top heights of the per-gate fields of a call
-// on a radar-centred map (cpol_composite).
+// on a radar-centred map or on a plane of the caller's per-gate coordinates, of one radar or of a network (cpol_composite).
 //
 // Reference functions replaced (wolfidan/cosmo_pol): none -- the reference hands back per-gate radials, and its users compute per
 // gate where it lies and scatter with np.maximum.at.  The rule is the one of include/cosmo_pol_amd.h and
@@ -25,6 +25,7 @@ struct CompArgs {
     int n_thr, slab;
     float h_lo, h_hi;
     float thr[COMP_MAX_THR];        // rounded
+    const double *gx, *gy;          // the gate plane: the caller's x and y [geo_gates] (the radar plane reads neither)
 };
 
 // the ordered key of a float32: a total order -inf < ... < -0.0 < +0.0 < ... < +inf; 0 and 0xFFFFFFFF are keys of NaNs alone
@@ -45,7 +46,10 @@ __device__ __forceinline__ float comp_unkey(unsigned k)
 // form a run of one cell are combined first (a segmented max / min over __shfl_up, bounded by the run's first lane: exact, max
 // and min being associative and commutative, and the count of a run is its length), and only the LAST lane of each run issues
 // the global integer atomics.  Without COMBINE every counting lane issues its own.
-template <bool COMBINE>
+// GATES: the gate plane (CPOL_COMP_PLANE_GATES) -- x and y are two float64 loads per gate, gx[gg] and gy[gg], in place of `dist`
+// and the wave-uniform sine / cosine pair; no multiplication, and a NaN coordinate does not count.  Everything behind the
+// coordinates is the same code: consecutive gates of a ray still fall into the same or neighbouring cells on any sensible plane.
+template <bool COMBINE, bool GATES>
 __global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
 {
     extern __shared__ double comp_lds[];
@@ -69,12 +73,21 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
         if (g < g1) {
             const float v = a.v[g];
             const long gg = g < a.geo_gates ? g : g % a.geo_gates;      // (the geometry of an ensemble call: n_rays rows once)
-            const int ray = (int)(gg / a.n_gates);
-            const float d = a.dist[gg], h = a.hgt[gg];
-            const double x = (double)d * a.ray_sin[ray], y = (double)d * a.ray_cos[ray];
+            const float h = a.hgt[gg];
+            double x, y;
+            bool located;
+            if (GATES) {
+                x = a.gx[gg]; y = a.gy[gg];
+                located = x == x && y == y;
+            } else {
+                const int ray = (int)(gg / a.n_gates);
+                const float d = a.dist[gg];
+                x = (double)d * a.ray_sin[ray]; y = (double)d * a.ray_cos[ray];
+                located = d == d;
+            }
             const int ix = hist_bin<double>(ex, a.n_ex, a.step_x, x) - 1;
             const int iy = hist_bin<double>(ey, a.n_ey, a.step_y, y) - 1;
-            bool counts = v == v && d == d && h == h && ix >= 0 && ix < a.n_x && iy >= 0 && iy < a.n_y;
+            bool counts = v == v && located && h == h && ix >= 0 && ix < a.n_x && iy >= 0 && iy < a.n_y;
             if (a.slab) counts = counts && a.h_lo <= h && h < a.h_hi;
             if (counts) {
                 cell = iy * a.n_x + ix;
@@ -117,6 +130,54 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
     }
 }
 
+// ---- SOURCE (CPOL_COMP_SOURCE): which call supplied each cell ----
+struct CompMergeArgs {
+    unsigned long long *rmax, *rlow, *rcount;         // the running state of this field, as in CompArgs (NULL: not requested)
+    unsigned *rtop;
+    unsigned long long *smax, *slow, *scount;         // the scratch state the call's k_comp filled: the same layout
+    unsigned *stop;
+    unsigned char *bmax, *blow;     // the source bytes of the running MAX and LOWEST states [n_blocks][cells]
+    long n;                         // n_blocks * cells
+    int cells, n_thr;
+    unsigned source;                // of this call, 0 ... 254
+};
+
+// One pass of integer atomics cannot know the final state, so a call of a SOURCE pass composes into a scratch state of its own
+// (k_comp, unchanged) and this kernel folds it into the running state: one thread per (block, cell) of one field, ordered behind
+// k_comp by the stream, so plain loads and stores do.  A scratch state greater than the running MAX state takes the cell and
+// its source byte; an equal one that is not empty lowers the byte to the smaller source (LOWEST mirrored); counts add, echo
+// tops take the maximum.  The final byte is the smallest source among the calls that reached the final state, whatever their
+// order.  Every scratch word touched goes back to its begin value: no memset runs per call.
+__global__ __launch_bounds__(COMP_THREADS) void k_comp_merge(const CompMergeArgs a)
+{
+    const long i = (long)blockIdx.x * COMP_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned long long n = a.scount[i];
+    if (n == 0ull) return;          // (no gate of this call counted here: every scratch word of the cell holds its begin value)
+    a.rcount[i] += n;
+    a.scount[i] = 0ull;
+    const unsigned char src = (unsigned char)a.source;
+    if (a.smax) {
+        const unsigned long long s = a.smax[i], r = a.rmax[i];
+        if (s > r) { a.rmax[i] = s; a.bmax[i] = src; }
+        else if (s == r && src < a.bmax[i]) a.bmax[i] = src;
+        a.smax[i] = 0ull;
+    }
+    if (a.slow) {
+        const unsigned long long s = a.slow[i], r = a.rlow[i];
+        if (s < r) { a.rlow[i] = s; a.blow[i] = src; }
+        else if (s == r && src < a.blow[i]) a.blow[i] = src;
+        a.slow[i] = ~0ull;
+    }
+    const long b = i / a.cells, c = i % a.cells;
+    for (int j = 0; j < a.n_thr; ++j) {
+        const long at = (b * a.n_thr + j) * (long)a.cells + c;
+        const unsigned s = a.stop[at];
+        if (s > a.rtop[at]) a.rtop[at] = s;
+        if (s) a.stop[at] = 0u;
+    }
+}
+
 struct CompFinishArgs {
     const unsigned long long *smax, *slow, *scount;   // as in CompArgs
     const unsigned *stop;
@@ -124,6 +185,7 @@ struct CompFinishArgs {
     unsigned long long *count;      // [n_blocks][n_fields][cells], at this field's row of block 0
     long n;                         // n_blocks * cells
     int cells, n_planes, n_fields, n_thr;
+    const unsigned char *bmax, *blow;   // SOURCE: the source bytes (NULL: no source_of_* planes)
 };
 
 // A finishing call: one thread per (block, cell) of one field decodes the states into the planes of `values` -- the key
@@ -140,12 +202,14 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp_finish(const CompFinishAr
         out[0] = s ? comp_unkey((unsigned)(s >> 32)) : nan;
         out[a.cells] = s ? comp_unkey((unsigned)s) : nan;
         out += 2 * (long)a.cells;
+        if (a.bmax) { out[0] = s ? (float)a.bmax[i] : nan; out += a.cells; }
     }
     if (a.slow) {
         const unsigned long long s = a.slow[i];
         out[0] = s != ~0ull ? comp_unkey((unsigned)s) : nan;
         out[a.cells] = s != ~0ull ? comp_unkey((unsigned)(s >> 32)) : nan;
         out += 2 * (long)a.cells;
+        if (a.blow) { out[0] = s != ~0ull ? (float)a.blow[i] : nan; out += a.cells; }
     }
     for (int j = 0; j < a.n_thr; ++j) {
         const unsigned s = a.stop[(b * a.n_thr + j) * (long)a.cells + c];

@@ -51,6 +51,8 @@ class Fractions(object):
         planes = composite_spec.planes(field)
         if plane not in planes:
             raise ValueError('%r is not a plane of %s (%s)' % (plane, field, ', '.join(planes)))
+        if str(plane).startswith('source_of_'):
+            raise ValueError('%r names the radar of a cell and has no units to threshold: not a plane to score' % (plane,))
         t = np.array(thresholds, dtype=np.float64).reshape(-1)
         if not 1 <= t.size <= MAX_THRESHOLDS:
             raise ValueError('thresholds: 1 ... %d values, got %d' % (MAX_THRESHOLDS, t.size))
@@ -216,6 +218,9 @@ class Scores(object):
         self.maps = Maps(spec.composite, keep_gates, phase, rays_per_block, distributed)     # (the refusals are those of Maps)
         self.spec, self.gates, self.observed, self.domain = spec, self.maps.gates, observed, domain
         self.f = None
+
+    def set_plane(self, gate_xy, plane_version=0, source=0):
+        self.maps.set_plane(gate_xy, plane_version, source)
 
     phase = property(lambda self: self.maps.phase, lambda self, v: setattr(self.maps, 'phase', int(v)))
     rays_per_block = property(lambda self: self.maps.rays_per_block, lambda self, v: setattr(self.maps, 'rays_per_block', int(v)))

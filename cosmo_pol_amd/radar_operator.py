@@ -258,6 +258,7 @@ def _table_identity():
 
 class RadarOperator(object):
     _table_serial = 0          # tags of per-ray table sets handed to the library
+    _plane_serial = 0          # tags of the per-gate plane coordinates of composites (cpol_composite.plane_version)
 
     def __init__(self, options_file=None, output_variables='all', *, device=0, lut_dir=None,
                  luts=None, config=None, distributed=False, gather_to=None, lanes=2, backend='hip',
@@ -849,9 +850,9 @@ class RadarOperator(object):
                                    product=SM.Rows(moments, keep_spectrum, self.__config['doppler']['scheme'], self.distributed))
 
     def _simulate_rays(self, azimuths, elevations, device_outputs=None, apply_sensitivity=True, paths=None, lane=0, pinned=False,
-                       product=None):
+                       product=None, radar=None, source=0):
         conf = self.__config
-        coords = conf['radar']['coords']
+        coords = conf['radar']['coords'] if radar is None else self._radar_arg(radar)
         if coords[2] > K.MAX_MODEL_HEIGHT:
             raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
         rr = self.constants.RANGE_RADAR
@@ -869,9 +870,76 @@ class RadarOperator(object):
                     conf['radar'].get('type', 'ground'))
                 paths = refraction.ode_paths(rr, elevations, sub.pts_ver, coords, h_col, n_col)
         mode = N.GEOM_GROUND_43 if paths is None else N.GEOM_HOST_PATHS
+        if product is not None and hasattr(product, 'set_plane'):
+            self._set_plane(product, azimuths, elevations, coords, paths, source, device_outputs, lane)
         return self._run_rays(azimuths, elevations, coords, len(rr), float(rr[0]), mode,
                               device_outputs=device_outputs, apply_sensitivity=apply_sensitivity,
                               paths=paths, lane=lane, pinned=pinned, product=product)
+
+    @staticmethod
+    def _radar_arg(radar):
+        """`radar=` of a composite call: (lat, lon, alt) in place of config['radar']['coords'] for this call alone."""
+        c = np.asarray(radar, dtype=np.float64).reshape(-1)
+        if c.size != 3 or not np.all(np.isfinite(c)):
+            raise ValueError('radar: (latitude, longitude, altitude), three finite numbers, got %r' % (radar,))
+        return [float(v) for v in c]
+
+    def _ray_tables(self, az, el, coords, sub):
+        """(version, traj, geo) of a set of rays: per-ray tables depend only on (site, azimuths, elevations, quadrature nodes);
+        `version` lets the library keep its device copies when they did not change."""
+        key = ('rays', az.tobytes(), el.tobytes(), tuple(np.ravel(coords)))
+
+        def make():
+            RadarOperator._table_serial += 1
+            return (RadarOperator._table_serial,) + geo.ray_tables(coords, az, el, sub)
+        return self._cached(key, make, lru=32)      # (the sweeps of a network of radars: 3 radars x 5 elevations are 15 sets)
+
+    def _set_plane(self, product, azimuths, elevations, coords, paths, source, device_outputs, lane):
+        """Hands a composite product the part of a network composite that belongs to THIS call: its `source`, and on a plane other
+        than 'radar' the per-gate coordinates of the call's rays (composite.plane_xy of the gate coordinates `lats` / `lons`).
+        Of a table set with a version tag they are made once and cached beside the geometry (('geom', version, n_gates)),
+        read-only, under a plane_version of their own, so that the library keeps its device copy too.  When the table set's gate
+        coordinates are not cached yet they are fetched first: the first time a geometry is seen costs ONE plain call on `lane`.
+        Without a version tag (host ray paths, reuse_device_tables off) that plain call is made every time and plane_version is 0.
+        With device outputs the caller brings device pointers (device_outputs['composite']['gate_x' | 'gate_y'])."""
+        cspec = getattr(product, 'maps', product).spec
+        if not cspec.gate_plane or device_outputs is not None:
+            product.set_plane(None, 0, source)
+            return
+        conf = self.__config
+        az = np.ascontiguousarray(np.asarray(azimuths, dtype=np.float64).reshape(-1))
+        el = np.ascontiguousarray(np.asarray(elevations, dtype=np.float64).reshape(-1))
+        if az.shape != el.shape:
+            raise ValueError('azimuths and elevations must have the same length')
+        rr = self.constants.RANGE_RADAR
+        n_gates = len(rr)
+        pole = None
+        if cspec.plane == 'model':
+            if not self._model_staged:
+                raise ValueError("the plane 'model' needs a loaded model")
+            pole = (float(self._proj['Latitude_of_southern_pole']), float(self._proj['Longitude_of_southern_pole']))
+        version = 0
+        if paths is None and self.reuse_device_tables:
+            sub = self._cached('sub', lambda: quadrature.subbeams(conf))
+            version = self._ray_tables(az, el, coords, sub)[0]
+        pkey = ('plane', version, n_gates, cspec.plane, pole)
+        made = self._cache.get(pkey) if version else None
+        if made is None:
+            geom = self._cache.get(('geom', version, n_gates)) if version else None
+            if geom is None:
+                geom = self._run_rays(az, el, coords, n_gates, float(rr[0]), N.GEOM_GROUND_43 if paths is None else N.GEOM_HOST_PATHS,
+                                      paths=paths, lane=lane)
+            x, y = CP.plane_xy(cspec.plane, geom['lats'], geom['lons'], pole)
+            if version:
+                x, y = x.copy(), y.copy()         # (own read-only copies: shared by every later call of this table set)
+                x.flags.writeable = y.flags.writeable = False
+                def tagged():
+                    RadarOperator._plane_serial += 1
+                    return (RadarOperator._plane_serial, x, y)
+                made = self._cached(pkey, tagged, lru=32)
+            else:
+                made = (0, x, y)
+        product.set_plane((made[1], made[2]), made[0], source)
 
     def stencil_state(self, lane=0):
         """The gate stencils as the library reports them: 'form' of the last sweep on `lane` (0 full, 1 recording, 2 replay) and the
@@ -1258,14 +1326,7 @@ class RadarOperator(object):
         if tables is not None:
             traj, geo_t = tables
         else:
-            # per-ray tables depend only on (site, azimuths, elevations, quadrature nodes);
-            # `version` lets the library keep its device copies when they did not change
-            key = ('rays', az.tobytes(), el.tobytes(), tuple(np.ravel(coords)))
-
-            def make():
-                RadarOperator._table_serial += 1
-                return (RadarOperator._table_serial,) + geo.ray_tables(coords, az, el, sub)
-            version, traj, geo_t = self._cached(key, make, lru=8)
+            version, traj, geo_t = self._ray_tables(az, el, coords, sub)
             if paths is not None or site is not None or not self.reuse_device_tables:
                 version = 0
 
@@ -1474,7 +1535,7 @@ class RadarOperator(object):
                 made = {k: res[k].copy() for k in _COORDS}
                 for a in made.values():
                     a.flags.writeable = False
-                geom = self._cached(gkey, lambda: made, lru=8)
+                geom = self._cached(gkey, lambda: made, lru=32)
             if geom is not None:
                 res.update(geom)
             if part is not None:
@@ -1869,7 +1930,7 @@ class RadarOperator(object):
                                       product=SO.Windows(superob, keep_gates, rays_per_block, self.distributed))
 
     def _simulate_rays_at(self, azimuths, elevations, times, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False,
-                          product=None):
+                          product=None, radar=None, source=0):
         self._timed_check()
         from . import timeline
         az = np.asarray(azimuths, dtype=np.float64).reshape(-1)
@@ -1889,8 +1950,10 @@ class RadarOperator(object):
                              % N.MEMBERS_PER_CALL)
         if len(groups) > 1 and product is not None:     # (a window, or a block of a pass, would cross the groups)
             raise ValueError('simulate_rays_at: the rays read more than %d states; %s' % (N.MEMBERS_PER_CALL, product.refuses['groups']))
-        coords = self.__config['radar']['coords']
+        coords = self.__config['radar']['coords'] if radar is None else self._radar_arg(radar)
         rr = self.constants.RANGE_RADAR
+        if product is not None and hasattr(product, 'set_plane'):     # (one group: refused above otherwise)
+            self._set_plane(product, az, el, coords, None, source, device_outputs, lane)
         parts = []
         for r0, r1, first, count in groups:
             tm = (np.arange(first, first + count, dtype=np.int32), np.ascontiguousarray(lo[r0:r1] - first, dtype=np.int32),
@@ -2321,11 +2384,17 @@ class RadarOperator(object):
                                       'histograms', members, per_member, device_outputs, apply_sensitivity, lane, pinned)
 
     def _ensemble_reduced(self, azimuths, elevations, product, what, members, per_member, device_outputs, apply_sensitivity, lane,
-                          pinned):
+                          pinned, radar=None, source=0):
         """An ensemble call (form 'shared') whose gates a histogram or a composite reduces: a block per member (`what` they
         are called), or one of all members' gates."""
         members = self._members_arg(members)
         coords = self._ensemble_coords()
+        if radar is not None:
+            coords = self._radar_arg(radar)
+            if coords[2] > K.MAX_MODEL_HEIGHT:
+                raise NotImplementedError('spaceborne geometry: use get_GPM_swath')
+        if hasattr(product, 'set_plane'):
+            self._set_plane(product, azimuths, elevations, coords, None, source, device_outputs, lane)
         sub = self._cached('sub', lambda: quadrature.subbeams(self.__config))
         rr = self.constants.RANGE_RADAR
         n_rays = len(np.asarray(azimuths).reshape(-1))
@@ -2377,7 +2446,7 @@ class RadarOperator(object):
     # (replaces in the reference: nothing -- its users pull every per-gate array to the host, compute per gate where it lies and
     # scatter with np.maximum.at)
     def simulate_rays_composite(self, azimuths, elevations, spec, keep_gates=False, phase=3, rays_per_block=0, device_outputs=None,
-                                lane=0, pinned=False):
+                                lane=0, pinned=False, radar=None, source=0):
         """simulate_rays handing back MAPS of its gates on a radar-centred grid: `spec` is a composite.Composite, and a finishing
         call's result gains res['composite'] = {'values': {field: {plane: float32 [n_blocks, n_y, n_x]}}, 'count': {field: uint64
         [n_blocks, n_y, n_x]}, 'x_edges', 'y_edges'} -- the column maximum, the lowest gate and the echo tops, reduced on the
@@ -2386,29 +2455,40 @@ class RadarOperator(object):
         produced for the host or copied; with it the result carries every array of simulate_rays, bit for bit.
         `phase`: bit 0 begins the lane's pass, bit 1 finishes it (the maps come back); 0 only folds -- the sweeps of a volume
         fold into one composite.  `rays_per_block`: 0 one map of all rays, else a divisor of the rays: one map per block of rays.
-        `device_outputs`: its entry 'composite' is {'values': {field: device pointer}, 'count': device pointer}.  ValueError for
-        what the library refuses; NotImplementedError with a process group and for spaceborne geometry."""
+        `device_outputs`: its entry 'composite' is {'values': {field: device pointer}, 'count': device pointer} (on a gate plane
+        also 'gate_x', 'gate_y': device pointers of float64 [n_rays, n_gates]).
+        `radar`: (lat, lon, alt) in place of config['radar']['coords'] for this call alone -- band, beamwidth, range and
+        resolution stay the configuration's, so the radars of a network under one operator differ in position only; `source`
+        (0 ... 254): this call's number in the source_of_* planes of a spec with 'source'.  On a plane other than 'radar'
+        (composite.Composite(plane=)) the call hands the library per-gate coordinates made on the host from the gate
+        coordinates of its table set (composite.plane_xy), cached with them; the first time a geometry is seen this costs one
+        plain call on the lane (every time without reuse_device_tables or with host ray paths).
+        ValueError for what the library refuses; NotImplementedError with a process group and for spaceborne geometry."""
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                   product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed))
+                                   product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed), radar=radar, source=source)
 
     def simulate_rays_at_composite(self, azimuths, elevations, times, spec, keep_gates=False, phase=3, rays_per_block=0,
-                                   device_outputs=None, lane=0, pinned=False):
-        """simulate_rays_at handing back a composite: `spec`, `keep_gates`, `phase`, `rays_per_block` as for
-        simulate_rays_composite (ValueError when the rays fall into several groups of states)."""
+                                   device_outputs=None, lane=0, pinned=False, radar=None, source=0):
+        """simulate_rays_at handing back a composite: `spec`, `keep_gates`, `phase`, `rays_per_block`, `radar` (the radars of a
+        network differ in position only) and `source` as for simulate_rays_composite (ValueError when the rays fall into
+        several groups of states)."""
         return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                      product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed))
+                                      product=CP.Maps(spec, keep_gates, phase, rays_per_block, self.distributed), radar=radar,
+                                      source=source)
 
     def simulate_rays_ensemble_composite(self, azimuths, elevations, spec, members=None, per_member=True, keep_gates=False,
-                                         phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False):
+                                         phase=3, device_outputs=None, apply_sensitivity=True, lane=0, pinned=False, radar=None,
+                                         source=0):
         """simulate_rays_ensemble (form 'shared') handing back composites: with `per_member` one map per member, in the order
         of `members` (the leading axis of every plane; rays_per_block = n_rays: each equals the member's own
         simulate_rays_composite), without it one map of all members' gates.  The gate coordinates come once.  `keep_gates`:
         the per-member arrays of simulate_rays_ensemble come back too.  `phase`: as for simulate_rays_composite; when
         `sequence_memory_budget` cuts the member list into several calls, per_member needs phase=3 (every chunk is a pass of its
-        own and the blocks are joined), and the one map of all members folds the chunks into the pass.  NotImplementedError
-        where simulate_rays_ensemble raises it."""
+        own and the blocks are joined), and the one map of all members folds the chunks into the pass.  `radar` (the radars of a
+        network differ in position only) and `source`: as for simulate_rays_composite.  NotImplementedError where
+        simulate_rays_ensemble raises it."""
         return self._ensemble_reduced(azimuths, elevations, CP.Maps(spec, keep_gates, phase, 0, self.distributed), 'maps', members,
-                                      per_member, device_outputs, apply_sensitivity, lane, pinned)
+                                      per_member, device_outputs, apply_sensitivity, lane, pinned, radar=radar, source=source)
 
     def get_PPI_composite(self, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, per_sweep=False,
                           keep_gates=False):
@@ -2441,7 +2521,7 @@ class RadarOperator(object):
         return NB.Scores(spec, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
 
     def simulate_rays_composite_fss(self, azimuths, elevations, spec, observed, domain=None, keep_gates=False, phase=3,
-                                    rays_per_block=0, device_outputs=None, lane=0, pinned=False):
+                                    rays_per_block=0, device_outputs=None, lane=0, pinned=False, radar=None, source=0):
         """simulate_rays_composite with the finished plane SCORED against an observed map on the device: `spec` is a
         neighbourhood.Fractions (its composite, the field and plane to score, thresholds and radii), `observed` float32
         [n_y, n_x] on the composite's grid in the field's linear units (NaN = no echo or no data), `domain` an optional uint8
@@ -2451,25 +2531,31 @@ class RadarOperator(object):
         neighbourhood.fss, bias and contingency make the scores of them.  A pass is scored only by the call that finishes it.
         The other keywords are those of simulate_rays_composite.  `device_outputs`: its entry 'composite' may carry 'observed',
         'domain', 'sums' and 'totals' as device pointers (`observed` stays None).  ValueError for an observed map or a domain of
-        a wrong shape or dtype and for what the library refuses."""
+        a wrong shape or dtype and for what the library refuses.  `radar` (the radars of a network under one operator differ in
+        position only) and `source`: as for simulate_rays_composite."""
         return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                   product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block))
+                                   product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block),
+                                   radar=radar, source=source)
 
     def simulate_rays_at_composite_fss(self, azimuths, elevations, times, spec, observed, domain=None, keep_gates=False, phase=3,
-                                       rays_per_block=0, device_outputs=None, lane=0, pinned=False):
-        """simulate_rays_at_composite with scores: `spec`, `observed`, `domain` as for simulate_rays_composite_fss."""
+                                       rays_per_block=0, device_outputs=None, lane=0, pinned=False, radar=None, source=0):
+        """simulate_rays_at_composite with scores: `spec`, `observed`, `domain` as for simulate_rays_composite_fss; `radar` (the
+        radars of a network differ in position only) and `source` as for simulate_rays_composite."""
         return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
-                                      product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block))
+                                      product=self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block),
+                                      radar=radar, source=source)
 
     def simulate_rays_ensemble_composite_fss(self, azimuths, elevations, spec, observed, domain=None, members=None, per_member=True,
                                              keep_gates=False, phase=3, device_outputs=None, apply_sensitivity=True, lane=0,
-                                             pinned=False):
+                                             pinned=False, radar=None, source=0):
         """simulate_rays_ensemble_composite with scores: with `per_member` one row of scores per member (the leading axis of
         every array of 'fractions', in the order of `members`; each equals the member's own simulate_rays_composite_fss),
         without it the scores of the one map of all members' gates.  `spec`, `observed`, `domain` as for
-        simulate_rays_composite_fss; the rest as for simulate_rays_ensemble_composite."""
+        simulate_rays_composite_fss; the rest (`radar`, `source`: the radars of a network differ in position only) as for
+        simulate_rays_ensemble_composite."""
         return self._ensemble_reduced(azimuths, elevations, self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, 0),
-                                      'maps', members, per_member, device_outputs, apply_sensitivity, lane, pinned)
+                                      'maps', members, per_member, device_outputs, apply_sensitivity, lane, pinned, radar=radar,
+                                      source=source)
 
     def get_PPI_composite_fss(self, elevations, spec, observed, domain=None, azimuths=None, az_step=None, az_start=0, az_stop=359,
                               per_sweep=False, keep_gates=False):
@@ -2479,6 +2565,59 @@ class RadarOperator(object):
         _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
         return self._pass_over_sweeps('composite', sweeps, lambda az, el, phase, lane: self.simulate_rays_composite_fss(
             az, el, spec, observed, domain=domain, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane), per_sweep)
+
+    # ------------------------------------------------------------------ network composites
+    # (replaces in the reference: nothing -- it simulates one radar per run)
+    def _network_sweeps(self, radars, cspec, elevations, azimuths, az_step, az_start, az_stop):
+        """[(az, el, radar, source)] of every elevation of every radar, and the checks of a network call."""
+        radars = [self._radar_arg(r) for r in radars]
+        if not radars:
+            raise ValueError('radars: at least one (lat, lon, alt)')
+        if len(radars) > CP.NO_SOURCE:
+            raise ValueError('radars: at most %d (the source of a cell is one byte), got %d' % (CP.NO_SOURCE, len(radars)))
+        if not isinstance(cspec, CP.Composite):
+            raise ValueError('spec: a cosmo_pol_amd.composite.Composite, got %r' % (cspec,))
+        if len(radars) > 1 and not cspec.gate_plane:
+            raise ValueError("the plane 'radar' is centred on ONE radar: a network needs plane='geographic', 'model' or a callable")
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        with_source = CP.SOURCE in cspec.products
+        return [(az, el, r, i if with_source else 0) for i, r in enumerate(radars) for az, el in sweeps], len(sweeps)
+
+    def _network_pass(self, sweeps, per_radar, call):
+        """Every sweep of every radar folded into ONE pass on lane 0 (_pass_over_sweeps), scored -- if at all -- once, at its end."""
+        which = iter(sweeps)
+
+        def one(az, el, phase, lane):
+            _, _, radar, source = next(which)
+            return call(az, el, phase, lane, radar, source)
+        out = self._pass_over_sweeps('composite', [(az, el) for az, el, _, _ in sweeps], one, False)
+        flat = out['sweeps']
+        out['sweeps'] = [flat[i:i + per_radar] for i in range(0, len(flat), per_radar)]
+        return out
+
+    def get_network_composite(self, radars, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, keep_gates=False):
+        """The PPI volumes of SEVERAL radars composed onto one map: `radars` is a list of (lat, lon, alt), each scanned at
+        `elevations` (the azimuths as for get_PPI) with the configuration's band, beamwidth, range and resolution -- the radars
+        of a network under one operator differ in position only.  `spec`: a composite.Composite on the plane 'geographic',
+        'model' or a callable (ValueError for 'radar' with more than one radar, and for more than 255 radars).  Every elevation
+        of every radar folds into one pass on lane 0; with the product 'source' the planes source_of_max / source_of_lowest
+        hold the index in `radars` of the radar that supplied the cell.  Returns {'composite': as for simulate_rays_composite,
+        'sweeps': [per radar [per elevation: what the call returned, the per-gate arrays with keep_gates]]}."""
+        sweeps, per_radar = self._network_sweeps(radars, spec, elevations, azimuths, az_step, az_start, az_stop)
+        return self._network_pass(sweeps, per_radar, lambda az, el, phase, lane, radar, source: self.simulate_rays_composite(
+            az, el, spec, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane, radar=radar, source=source))
+
+    def get_network_composite_fss(self, radars, elevations, spec, observed, domain=None, azimuths=None, az_step=None, az_start=0,
+                                  az_stop=359, keep_gates=False):
+        """get_network_composite with scores: `spec` is a neighbourhood.Fractions over the network's composite, `observed` and
+        `domain` as for simulate_rays_composite_fss.  The pass is scored ONCE, at its end, against the observed network
+        composite: res['composite']['fractions']."""
+        if not isinstance(spec, NB.Fractions):
+            raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
+        sweeps, per_radar = self._network_sweeps(radars, spec.composite, elevations, azimuths, az_step, az_start, az_stop)
+        return self._network_pass(sweeps, per_radar, lambda az, el, phase, lane, radar, source: self.simulate_rays_composite_fss(
+            az, el, spec, observed, domain=domain, keep_gates=keep_gates, phase=phase, pinned=True, lane=lane, radar=radar,
+            source=source))
 
     # ------------------------------------------------------------------ spectrum moments scans
     def _moments_sweeps(self, sweeps, moments, keep_spectrum):

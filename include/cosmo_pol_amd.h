@@ -570,14 +570,45 @@ typedef struct cpol_histogram {
  * cpol_run_columns and cpol_interp_subbeams.
  * ONE kernel per requested field (k_comp, cpol_comp.inl) runs behind the launch sequence and before the output copy, and a
  * finishing call adds k_comp_finish per field: the per-gate arrays, the launch forms, the gate stencils and a captured graph are
- * what they are without it.  A per-gate array the caller leaves NULL is still produced on the device and is not copied. */
+ * what they are without it.  A per-gate array the caller leaves NULL is still produced on the device and is not copied.
+ *
+ * NETWORK COMPOSITES: several radars on one geographic or model grid.  Everything above stays as it is; a zero-initialised new
+ * member means the behaviour above.
+ * PLANE (`plane`): CPOL_COMP_PLANE_RADAR = 0 is the radar-centred plane above.  With CPOL_COMP_PLANE_GATES = 1 the caller
+ * supplies per-gate coordinates, const double gate_x[geo_rays * n_gates], gate_y[geo_rays * n_gates], read at g mod geo_gates
+ * exactly as `dist` is: x = gate_x[g], y = gate_y[g], no multiplication.  ray_sin / ray_cos may be NULL and `dist` is not read.
+ * A gate counts iff v == v, h == h, x == x, y == y, it lies in the grid and it lies in the slab; the cell search is the same
+ * comparisons alone.  The library still computes no trigonometric function for this product: every projection (longitude and
+ * latitude, a rotated model grid, any map projection) is made by the caller.  gate_x / gate_y lie where the caller's outputs
+ * lie: with outputs_on_device == 1 device memory that the device reads in place, else (0, and 2: page-locked host outputs) host
+ * arrays that the library copies on the call's stream before the call returns.
+ * `plane_version`: a non-zero value tells the library to keep its device copy of the two arrays under that tag and to skip the
+ * upload when it holds the tag already (the idiom of cpol_ray_tables_t.version: the caller changes the tag when the arrays
+ * change).  The copies are kept per context, at least as many as table sets, so the radars of a network alternating in one
+ * pass do not evict each other.  cpol_debug_read "composite_plane" returns int64 {uploads, hits}.
+ * SOURCE (`source`, 0 ... 254, and the product bit CPOL_COMP_SOURCE = 16, which needs MAX or LOWEST; bit 8 stays refused as an
+ * unknown bit, as it always was): a number the caller gives
+ * each call, e.g. the index of the radar.  New plane `source_of_max`: the smallest `source` among the counting gates of the
+ * whole pass whose key(v) << 32 | key(h) equals the cell's final MAX state; `source_of_lowest`: the same for the LOWEST state.
+ * Both are delivered as float32 (exact small integers), empty cells NaN.  Plane order: max, height_of_max, source_of_max,
+ * lowest, height_of_lowest, source_of_lowest, echo_top_0 ....  The definition is symmetric in the calls: the pass still depends
+ * neither on how it is cut into calls nor on their order.  The running state gains one source byte per cell, block and product
+ * (begin value 255) and a per-call scratch state of the layout and begin values of the running state: a call of a SOURCE pass
+ * composes into the scratch (k_comp, unchanged) and k_comp_merge folds it into the running state (greater: take state and
+ * source; equal and not empty: the smaller source; counts add, echo tops take the maximum) and leaves the scratch at its begin
+ * values.  A pass without SOURCE queues exactly what it queued before.
+ * CPOL_ERR_ARG in addition, nothing queued, an open pass untouched, the context usable: `plane` outside 0 / 1; PLANE_GATES
+ * with a NULL gate_x or gate_y (NULL ray_sin / ray_cos is refused on the radar plane alone); `source` outside 0 ... 254; a
+ * non-zero `source` without the SOURCE bit; SOURCE without MAX and without LOWEST; `plane` differing from the open pass (the
+ * SOURCE bit is part of `products`); the 1 GiB limit, which counts the source bytes and the scratch. */
 #define CPOL_COMP_FIELDS 9
 #define CPOL_COMP_MAX_THRESHOLDS 4
-enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4 };
+enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4, CPOL_COMP_SOURCE = 16 };     /* (8 is no product: refused) */
+enum { CPOL_COMP_PLANE_RADAR = 0, CPOL_COMP_PLANE_GATES = 1 };
 typedef struct cpol_composite {
     uint32_t fields;            /* bit k: field k composed                                                         */
     int32_t  phase;             /* bit 0 begins the pass, bit 1 finishes it                                        */
-    uint32_t products;          /* CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP                           */
+    uint32_t products;          /* CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE        */
     int32_t  rays_per_block;    /* 0: one block of all rows; else divides the rows of the call                     */
     int32_t  n_x, n_y;          /* cells east and north                                                            */
     int32_t  use_slab;          /* 0: every height counts; else [h_lo, h_hi)                                       */
@@ -588,6 +619,10 @@ typedef struct cpol_composite {
     const double *ray_sin, *ray_cos;            /* [n_rays]: sine and cosine of each ray's azimuth                 */
     float    *values[CPOL_COMP_FIELDS];         /* [n_blocks][n_planes][n_y][n_x]; read by a finishing call        */
     uint64_t *count;                            /* [n_blocks][n_requested_fields][n_y][n_x]; likewise              */
+    int32_t  plane;             /* CPOL_COMP_PLANE_RADAR (0) or CPOL_COMP_PLANE_GATES                              */
+    int32_t  source;            /* 0 ... 254: this call's number in the source_of_* planes (CPOL_COMP_SOURCE)      */
+    const double *gate_x, *gate_y;              /* PLANE_GATES: [geo_rays * n_gates], the caller's projection      */
+    uint64_t plane_version;     /* non-zero: the tag under which the library keeps gate_x / gate_y on the device   */
 } cpol_composite;
 
 /* Neighbourhood verification: the sums of the fractions skill score (FSS; Roberts and Lean 2008) of ONE finished plane of a
@@ -1105,7 +1140,10 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * needed for every requested field; heights and dist [n_rays * n_gates] (n_rays divides n_rows: row r takes row r mod n_rays);
  * `c` with host edge, ray and output pointers (ray_sin, ray_cos [n_rays]); lane_form 0: the kernel's kept form, 1: lanes that
  * share a cell combined inside the wavefront, 2: every lane on its own; blocking; honours c.phase; needs no staged model or
- * tables; cpol_composite's refusals, and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
+ * tables; cpol_composite's refusals, and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.  With c.plane =
+ * CPOL_COMP_PLANE_GATES c.gate_x and c.gate_y are host arrays [n_rays * n_gates] (kept under c.plane_version like a sweep's) and
+ * dist may be NULL; with CPOL_COMP_SOURCE in c.products the call runs k_comp_merge too, with c.source.
+ * "composite_plane" copies two int64: {uploads, hits} of the context's store of gate planes (cpol_composite.plane_version).
  * "composite_stretch" copies one int32: the gates a workgroup of k_comp owns.
  * "fractions_maps" is the same for the neighbourhood verification: the checks and the three kernels of cpol_frac.inl on
  * caller-supplied maps.  dst points to { int32_t n_blocks, n_y, n_x, pad; const float *maps; cpol_fractions f; } -- host arrays:
