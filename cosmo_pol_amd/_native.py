@@ -162,7 +162,11 @@ class Composite(C.Structure):
                 ('edges_x', C.c_void_p), ('edges_y', C.c_void_p), ('ray_sin', C.c_void_p), ('ray_cos', C.c_void_p),
                 ('values', C.c_void_p * len(COMPOSITE_FIELDS)), ('count', C.c_void_p),
                 ('plane', C.c_int32), ('source', C.c_int32), ('gate_x', C.c_void_p), ('gate_y', C.c_void_p),
-                ('plane_version', C.c_uint64)]
+                ('plane_version', C.c_uint64),
+                # height layers and the column: a zero-initialised tail means off
+                ('n_z', C.c_int32), ('gaps', C.c_int32), ('edges_z', C.c_void_p), ('n_table', C.c_int32 * len(COMPOSITE_FIELDS)),
+                ('table_v', C.c_void_p * len(COMPOSITE_FIELDS)), ('table_f', C.c_void_p * len(COMPOSITE_FIELDS)),
+                ('column', C.c_void_p * len(COMPOSITE_FIELDS)), ('column_layers', C.c_void_p * len(COMPOSITE_FIELDS))]
 
 
 class Fractions(C.Structure):
@@ -1079,6 +1083,13 @@ class Context(object):
             keep += [gx, gy]
             c.plane, c.gate_x, c.gate_y, c.plane_version = 1, gx.ctypes.data, gy.ctypes.data, int(plane_version)
         c.source = int(source)
+        if spec.n_z:
+            c.n_z, c.edges_z, c.gaps = spec.n_z, spec.z_edges_given.ctypes.data, CP.GAPS.index(spec.gaps)
+            keep.append(spec.z_edges_given)
+            for k, (tv, tf) in spec.column.items():
+                i = COMPOSITE_FIELDS.index(k)
+                c.n_table[i], c.table_v[i], c.table_f[i] = len(tv), tv.ctypes.data, tf.ctypes.data
+                keep += [tv, tf]
         return c, keep
 
     def composite_plane(self):
@@ -1106,7 +1117,8 @@ class Context(object):
         on its own.  `tamper(c)`: changes the cpol_composite before the call (the refusal tests).  gate_xy = (x, y), float64
         [n_rays, n_gates]: the gate plane (`dist` and `azimuths` may then be None), under `plane_version` in the plane store;
         `source`: the call's number.  A finishing call returns {'values': {field: {plane: array}}, 'count': {field: array}},
-        any other None."""
+        any other None.  A spec with height layers: the planes and counts carry the layer axis ([n_blocks, n_z, n_y, n_x]), and
+        with the product 'column' the result gains 'column' and 'column_layers' ({field: [n_blocks, n_y, n_x]})."""
         from . import composite as CP
 
         class Hook(C.Structure):
@@ -1146,13 +1158,19 @@ class Context(object):
         keep += ckeep
         rpb = int(rays_per_block)
         nb = 1 if rpb <= 0 or shape[0] % rpb else shape[0] // rpb
-        vals, cnt = {}, None
+        vals, cnt, col, lay = {}, None, {}, {}
+        z = (spec.n_z,) if spec.n_z else ()
         if int(phase) & 2:
             for k in spec.fields:
-                vals[k] = np.full((nb, len(spec.planes(k)), spec.n_y, spec.n_x), -7.0, dtype=np.float32)
+                vals[k] = np.full((nb,) + z + (len(spec.planes(k)), spec.n_y, spec.n_x), -7.0, dtype=np.float32)
                 hk.c.values[COMPOSITE_FIELDS.index(k)] = vals[k].ctypes.data
-            cnt = np.full((nb, len(spec.fields), spec.n_y, spec.n_x), 0xDEADBEEF, dtype=np.uint64)
+            cnt = np.full((nb,) + z + (len(spec.fields), spec.n_y, spec.n_x), 0xDEADBEEF, dtype=np.uint64)
             hk.c.count = cnt.ctypes.data
+            for k in spec.column:
+                col[k] = np.full((nb, spec.n_y, spec.n_x), -7.0, dtype=np.float64)
+                lay[k] = np.full((nb, spec.n_y, spec.n_x), 0xAB, dtype=np.uint8)
+                hk.c.column[COMPOSITE_FIELDS.index(k)] = col[k].ctypes.data
+                hk.c.column_layers[COMPOSITE_FIELDS.index(k)] = lay[k].ctypes.data
         if tamper is not None:
             keep.append(tamper(hk.c))
         rc = int(self.lib.cpol_debug_read(self.h, b'composite_fields', C.byref(hk), C.sizeof(hk)))
@@ -1160,8 +1178,14 @@ class Context(object):
         del keep
         if not int(phase) & 2:
             return None
-        return {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
-                'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
+        if not spec.n_z:
+            return {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
+                    'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
+        out = {'values': {k: {p: vals[k][:, :, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
+               'count': {k: cnt[:, :, i] for i, k in enumerate(spec.fields)}}
+        if spec.column:
+            out['column'], out['column_layers'] = col, lay
+        return out
 
     @staticmethod
     def fractions_struct(spec):

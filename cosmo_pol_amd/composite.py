@@ -56,7 +56,29 @@ NETWORK COMPOSITES: several radars on one geographic or model grid.  Everything 
              same for the LOWEST state: float32 (exact small integers), empty cells NaN.  The planes are then max,
              height_of_max, source_of_max, lowest, height_of_lowest, source_of_lowest, echo_top_0 ....  The definition is
              symmetric in the calls: the pass still depends neither on how it is cut into calls nor on their order.  The state
-             gains one source byte per cell, block and product (begin value 255) and a per-call scratch state."""
+             gains one source byte per cell, block and product (begin value 255) and a per-call scratch state.
+
+HEIGHT LAYERS AND THE COLUMN: a stack of CAPPIs in one pass, and column integrals such as VIL.  Without `z_edges` everything above
+stays as it is.
+  Layers     z_edges: 2 ... MAX_Z_EDGES height edges in metres, each rounded once to float32, strictly ascending after the
+             rounding and not NaN: n_z = 1 ... MAX_LAYERS layers.  A gate that counts above counts in layer l iff
+             ez[l] <= h < ez[l + 1] in float32: a gate on the last edge is outside, as on the x and y axes, and a gate below the
+             first edge or at or above the last counts nowhere.  Per (block, layer, cell) the state is the MAX state and the
+             count of above.  Planes max, height_of_max: float32 [n_blocks, n_z, n_y, n_x]; count uint64 likewise.  With layers
+             height_range (the first and last edge are the slab), 'lowest', 'echo_top' and 'source' are refused; several radars
+             still fold into one pass on a gate plane, `source` stays 0.
+  Column     the product 'column' (CPOL_COMP_COLUMN = 64) needs layers and 'max'.  Per field a table: table_v, float32
+             breakpoints in the field's linear units, 2 ... MAX_TABLE of them, finite and strictly ascending; table_f, float64
+             values at the breakpoints, finite.  For a layer whose maximum v exists: i = searchsorted(table_v, v, 'right') - 1;
+             i < 0: f = 0.0; i >= n - 1: f = table_f[n - 1] (the cap; +inf takes it); else
+             t = (float64(v) - float64(tv[i])) / (float64(tv[i + 1]) - float64(tv[i])), f = tf[i] + t * (tf[i + 1] - tf[i]),
+             every operation ONE float64 operation.  C = sum over l ascending from +0.0 of f_l * dz_l with
+             dz_l = float64(ez[l + 1]) - float64(ez[l]): one thread's loop, no order of the hardware enters.
+  Gaps       an empty layer: 'zero' adds nothing; 'hold': an empty layer with a counting layer below it and a counting layer
+             above it in the same cell takes the f of the nearest counting layer below; empty layers below the lowest or above
+             the highest counting layer add nothing.  A cell with no counting layer is NaN.
+  Outputs    column[field] float64 [n_blocks, n_y, n_x]; column_layers[field] uint8 [n_blocks, n_y, n_x], the layers that
+             contributed (under 'hold' the held ones included)."""
 import numpy as np
 
 from .histogram import Counts
@@ -64,6 +86,11 @@ from .histogram import Counts
 FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V')
 PRODUCTS = ('max', 'lowest', 'echo_top')             # bit 0, 1, 2 of cpol_composite.products
 SOURCE, SOURCE_BIT = 'source', 16                    # CPOL_COMP_SOURCE (8 is no product and stays refused)
+COLUMN, COLUMN_BIT = 'column', 64                    # CPOL_COMP_COLUMN (32 is no product and stays refused)
+GAPS = ('zero', 'hold')                              # cpol_composite.gaps
+MAX_LAYERS = 64                  # n_z; z_edges holds n_z + 1 values
+MAX_Z_EDGES = MAX_LAYERS + 1
+MAX_TABLE = 1024                 # breakpoints of a column table
 NO_SOURCE = 255                                      # the begin value of a source byte; sources are 0 ... 254
 PLANES = ('radar', 'geographic', 'model')            # or a callable f(lats, lons) -> (x, y): see plane_xy
 MAX_EDGES = 1024                 # n + 1 of either axis
@@ -114,9 +141,14 @@ class Composite(object):
     y_edges latitudes, degrees), 'model' (rotated longitudes and latitudes of the staged model's grid) or a callable
     f(lats, lons) -> (x, y): on every plane but 'radar' the sweep calls hand the library per-gate coordinates made by
     `plane_xy`, and several radars may fold into one pass.  The product 'source' (beside 'max' or 'lowest') adds the planes
-    source_of_max / source_of_lowest: which call's `source` supplied the cell.  ValueError for what the library refuses."""
+    source_of_max / source_of_lowest: which call's `source` supplied the cell.  `z_edges`: 2 ... 65 height edges in metres:
+    the planes gain a layer axis ([n_blocks, n_z, n_y, n_x]: a stack of CAPPIs in one pass); with the product 'column' and
+    `column` = {field: (table_v, table_f)} (`vil_table` makes the one of VIL) the result gains the column integral of the
+    interpolated table over the layers, `gaps` ('zero' or 'hold') saying what an empty layer adds.  ValueError for what the
+    library refuses."""
 
-    def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None, plane='radar'):
+    def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None, plane='radar',
+                 z_edges=None, column=None, gaps='zero'):
         if isinstance(fields, str):
             fields = (fields,)
         fields = tuple(fields)
@@ -136,9 +168,9 @@ class Composite(object):
         if not products:
             raise ValueError('products: at least one of %s' % ', '.join(PRODUCTS))
         for q in products:
-            if q not in PRODUCTS and q != SOURCE:
-                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS + (SOURCE,))))
-        self.products = tuple(q for q in PRODUCTS + (SOURCE,) if q in products)
+            if q not in PRODUCTS and q != SOURCE and q != COLUMN:
+                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS + (SOURCE, COLUMN))))
+        self.products = tuple(q for q in PRODUCTS + (SOURCE, COLUMN) if q in products)
         if SOURCE in self.products and 'max' not in self.products and 'lowest' not in self.products:
             raise ValueError("'source' needs 'max' or 'lowest'")
         if not (callable(plane) or (isinstance(plane, str) and plane in PLANES)):
@@ -173,6 +205,60 @@ class Composite(object):
                 raise ValueError('height_range: h_lo < h_hi after rounding to float32, got %r' % (height_range,))
             self.height_range = (lo, hi)
             self.height_range_given = (float(height_range[0]), float(height_range[1]))
+        # height layers and the column
+        self.z_edges = self.z_edges_given = None
+        self.column, self.gaps = {}, 'zero'
+        if z_edges is not None:
+            zg = np.array(z_edges, dtype=np.float64)
+            if zg.ndim != 1 or not 2 <= zg.size <= MAX_Z_EDGES:
+                raise ValueError('z_edges: 2 ... %d edges in a 1-D sequence' % MAX_Z_EDGES)
+            if np.any(np.isnan(zg)):
+                raise ValueError('z_edges: an edge is NaN')
+            with np.errstate(over='ignore'):
+                z = zg.astype(np.float32)
+            if not np.all(z[1:] > z[:-1]):
+                raise ValueError('z_edges: the edges are not strictly ascending after rounding to float32')
+            if self.height_range is not None:
+                raise ValueError('z_edges with height_range: the first and last edge are the slab')
+            for q in ('lowest', 'echo_top', SOURCE):
+                if q in self.products:
+                    raise ValueError('z_edges with %r: per layer the composite keeps the maximum and the count alone' % (q,))
+            self.z_edges, self.z_edges_given = z, zg
+        if COLUMN in self.products:
+            if self.z_edges is None:
+                raise ValueError("'column' needs z_edges")
+            if 'max' not in self.products:
+                raise ValueError("'column' needs 'max'")
+            if not isinstance(column, dict) or not column:
+                raise ValueError("'column' needs column = {field: (table_v, table_f)}")
+            if gaps not in GAPS:
+                raise ValueError('gaps: one of %s, got %r' % (', '.join(GAPS), gaps))
+            self.gaps = gaps
+            for k in column:
+                if k not in self.fields:
+                    raise ValueError('a column table of %r, which is not a field of the composite' % (k,))
+            for k in self.fields:
+                if k not in column:
+                    continue
+                tv, tf = column[k]
+                tvg = np.array(tv, dtype=np.float64).reshape(-1)
+                tf = np.array(tf, dtype=np.float64).reshape(-1)
+                if not 2 <= tvg.size <= MAX_TABLE:
+                    raise ValueError('the column table of %s: 2 ... %d breakpoints, got %d' % (k, MAX_TABLE, tvg.size))
+                if tf.size != tvg.size:
+                    raise ValueError('the column table of %s: %d breakpoints and %d values' % (k, tvg.size, tf.size))
+                with np.errstate(over='ignore'):
+                    tv32 = tvg.astype(np.float32)
+                if not (np.all(np.isfinite(tv32)) and np.all(np.isfinite(tf))):
+                    raise ValueError('the column table of %s: a breakpoint or a value is NaN or infinite' % k)
+                if not np.all(tv32[1:] > tv32[:-1]):
+                    raise ValueError('the column table of %s: the breakpoints are not strictly ascending in float32' % k)
+                self.column[k] = (tv32, tf)
+        else:
+            if column is not None:
+                raise ValueError("column tables without 'column'")
+            if gaps != 'zero':
+                raise ValueError("gaps without 'column'")
 
     @property
     def n_x(self):
@@ -183,6 +269,11 @@ class Composite(object):
         return len(self.y_edges) - 1
 
     @property
+    def n_z(self):
+        """The number of height layers; 0 without z_edges."""
+        return 0 if self.z_edges is None else len(self.z_edges) - 1
+
+    @property
     def mask(self):
         """cpol_composite.fields."""
         return sum(1 << FIELDS.index(k) for k in self.fields)
@@ -190,7 +281,7 @@ class Composite(object):
     @property
     def product_mask(self):
         """cpol_composite.products."""
-        return sum(SOURCE_BIT if q == SOURCE else 1 << PRODUCTS.index(q) for q in self.products)
+        return sum(SOURCE_BIT if q == SOURCE else COLUMN_BIT if q == COLUMN else 1 << PRODUCTS.index(q) for q in self.products)
 
     @property
     def gate_plane(self):
@@ -213,7 +304,11 @@ class Composite(object):
         k = (self.fields, self.products, self.x_edges.tobytes(), self.y_edges.tobytes(),
              tuple(self.thresholds[k].tobytes() for k in self.fields),
              None if self.height_range is None else (self.height_range[0].tobytes(), self.height_range[1].tobytes()))
-        return k if self.plane == 'radar' else k + (self.plane,)
+        k = k if self.plane == 'radar' else k + (self.plane,)
+        if self.z_edges is not None:          # (a plain spec keeps the key it had)
+            k = k + (('z', self.z_edges.tobytes(), self.gaps,
+                      tuple((f, tv.tobytes(), tf.tobytes()) for f, (tv, tf) in sorted(self.column.items()))),)
+        return k
 
     def __eq__(self, other):
         return isinstance(other, Composite) and self.key == other.key
@@ -229,6 +324,11 @@ class Composite(object):
             s += ', height_range=[%g, %g)' % self.height_range
         if self.plane != 'radar':
             s += ', plane=%s' % (self.plane if isinstance(self.plane, str) else getattr(self.plane, '__name__', 'callable'))
+        if self.z_edges is not None:
+            s += ', %d layers [%g, %g)' % (self.n_z, self.z_edges[0], self.z_edges[-1])
+        if self.column:
+            s += ', column={%s}, gaps=%s' % (', '.join('%s: %d points' % (k, len(self.column[k][0])) for k in self.fields
+                                                         if k in self.column), self.gaps)
         return s + ')'
 
 
@@ -263,20 +363,27 @@ def n_blocks(n_rows, rays_per_block=0):
 
 
 def shape(spec, field, n_rows=1, rays_per_block=0):
-    """The shape of values[field] for a call of n_rows rows."""
-    return (n_blocks(n_rows, rays_per_block), len(spec.planes(field)), spec.n_y, spec.n_x)
+    """The shape of values[field] for a call of n_rows rows; with layers the layer axis lies in front of the planes."""
+    z = (spec.n_z,) if spec.n_z else ()
+    return (n_blocks(n_rows, rays_per_block),) + z + (len(spec.planes(field)), spec.n_y, spec.n_x)
 
 
 def count_shape(spec, n_rows=1, rays_per_block=0):
-    """The shape of the count array."""
-    return (n_blocks(n_rows, rays_per_block), len(spec.fields), spec.n_y, spec.n_x)
+    """The shape of the count array; with layers the layer axis lies in front of the fields."""
+    z = (spec.n_z,) if spec.n_z else ()
+    return (n_blocks(n_rows, rays_per_block),) + z + (len(spec.fields), spec.n_y, spec.n_x)
+
+
+def column_shape(spec, n_rows=1, rays_per_block=0):
+    """The shape of column[field] and of column_layers[field]."""
+    return (n_blocks(n_rows, rays_per_block), spec.n_y, spec.n_x)
 
 
 def state_bytes(spec, blocks):
     """The bytes of the running state of `blocks` blocks (cpol_comp.h: the echo-top states of a field padded to 8 bytes).  With
     'source': the source bytes behind it (one per cell, block and product, each array padded to 8 bytes) and the per-call
-    scratch state, as large as the running state without them."""
-    per = int(blocks) * spec.n_x * spec.n_y
+    scratch state, as large as the running state without them.  With layers a block holds n_z planes of cells."""
+    per = int(blocks) * max(spec.n_z, 1) * spec.n_x * spec.n_y
     total = 0
     for k in spec.fields:
         total += per * 8 * (1 + ('max' in spec.products) + ('lowest' in spec.products))
@@ -362,9 +469,16 @@ def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0,
     geo = located & (heights == heights) & (ix >= 0) & (ix < spec.n_x) & (iy >= 0) & (iy < spec.n_y)
     if spec.height_range is not None:
         geo &= (spec.height_range[0] <= heights) & (heights < spec.height_range[1])
-    cell = np.where(geo, iy * spec.n_x + ix, 0)
-    kh = key32(heights)
+    cell = iy * spec.n_x + ix
     cells = spec.n_x * spec.n_y
+    if spec.n_z:
+        # the layer of a gate: comparisons in float32 alone; a block holds n_z planes of cells
+        iz = np.searchsorted(spec.z_edges, heights, side='right') - 1
+        geo &= (iz >= 0) & (iz < spec.n_z)
+        cell = iz * cells + cell
+        cells = spec.n_z * cells
+    cell = np.where(geo, cell, 0)
+    kh = key32(heights)
     nb = None
     for k in spec.fields:
         v = np.asarray(fields[k])
@@ -419,7 +533,7 @@ def finish(state):
     """The state of a pass decoded: {'values': {field: {plane: float32 [n_blocks, n_y, n_x]}}, 'count': {field: uint64
     [n_blocks, n_y, n_x]}}; empty cells NaN."""
     spec, nb = state['spec'], state['n_blocks']
-    sh = (nb, spec.n_y, spec.n_x)
+    sh = (nb, spec.n_z, spec.n_y, spec.n_x) if spec.n_z else (nb, spec.n_y, spec.n_x)
     nan = np.float32(np.nan)
     out = {'values': {}, 'count': {}}
     for k in spec.fields:
@@ -441,7 +555,83 @@ def finish(state):
             planes['echo_top_%d' % j] = np.where(st['top'][j] == 0, nan, unkey32(st['top'][j])).reshape(sh)
         out['values'][k] = planes
         out['count'][k] = st['count'].reshape(sh).copy()
+    if COLUMN in spec.products:
+        out['column'], out['column_layers'] = {}, {}
+        for k in spec.fields:
+            if k in spec.column:
+                out['column'][k], out['column_layers'][k] = column_of(spec, out['values'][k]['max'], field=k)
     return out
+
+
+def column_of(spec, max_planes, field=None):
+    """The column integral on its own: (column float64 [n_blocks, n_y, n_x], column_layers uint8 likewise) of the layered `max`
+    planes, float32 [n_blocks, n_z, n_y, n_x] (a layer without a counting gate NaN), under the table of `field` (the spec's only
+    table when None) and spec.gaps.  Statement by statement what k_comp_column does per cell: the layers ascending, every
+    operation one float64 operation."""
+    if COLUMN not in spec.products:
+        raise ValueError("column_of: the spec has no product 'column'")
+    if field is None:
+        if len(spec.column) != 1:
+            raise ValueError('column_of: name the field whose table is meant (%s)' % ', '.join(spec.column))
+        field = next(iter(spec.column))
+    if field not in spec.column:
+        raise ValueError('column_of: %r has no column table' % (field,))
+    tv, tf = spec.column[field]
+    n = len(tv)
+    m = np.asarray(max_planes)
+    if m.dtype != np.float32 or m.ndim != 4 or m.shape[1:] != (spec.n_z, spec.n_y, spec.n_x):
+        raise ValueError('column_of: max_planes are float32 [n_blocks, %d, %d, %d]' % (spec.n_z, spec.n_y, spec.n_x))
+    ez = spec.z_edges.astype(np.float64)
+    tv64 = tv.astype(np.float64)
+    sh = (m.shape[0], spec.n_y, spec.n_x)
+    have = m == m                                      # (NaN never reaches a state: NaN marks the empty layer)
+    any_layer = np.zeros(sh, dtype=bool)
+    top = np.full(sh, -1, dtype=np.int64)              # the highest counting layer of the cell
+    for l in range(spec.n_z):
+        any_layer |= have[:, l]
+        top = np.where(have[:, l], l, top)
+    total = np.zeros(sh, dtype=np.float64)             # +0.0
+    layers = np.zeros(sh, dtype=np.uint8)
+    held = np.zeros(sh, dtype=np.float64)
+    seen = np.zeros(sh, dtype=bool)                    # a counting layer lies below
+    with np.errstate(invalid='ignore', over='ignore'):
+        for l in range(spec.n_z):
+            v = m[:, l]
+            i = np.searchsorted(tv, np.where(have[:, l], v, tv[0]), side='right') - 1
+            ii = np.clip(i, 0, n - 2)
+            t = (v.astype(np.float64) - tv64[ii]) / (tv64[ii + 1] - tv64[ii])
+            d = tf[ii + 1] - tf[ii]
+            p = t * d
+            f = tf[ii] + p
+            f = np.where(i < 0, 0.0, np.where(i >= n - 1, tf[n - 1], f))
+            held = np.where(have[:, l], f, held)
+            adds = have[:, l]
+            if spec.gaps == 'hold':
+                adds = adds | (seen & (l < top))
+            seen = seen | have[:, l]
+            dz = ez[l + 1] - ez[l]
+            term = held * dz
+            total = np.where(adds, total + term, total)
+            layers = layers + adds.astype(np.uint8)
+    return np.where(any_layer, total, np.nan), layers
+
+
+def vil_table(db_min=-10.0, db_cap=56.0, step_db=0.25):
+    """The column table of the vertically integrated liquid (Greene and Clark 1972, "Vertically integrated liquid water -- a new
+    analysis tool", Mon. Wea. Rev. 100, 548-552): M = 3.44e-6 * Z ** (4 / 7) kg m^-3 with Z in mm^6 m^-3, so that the column
+    over layers in metres is kg m^-2.  Returns (float32 Z breakpoints every `step_db` from `db_min` to `db_cap` dBZ, float64
+    values): the values are evaluated at the ROUNDED breakpoints with np.power on the host -- the device takes no power.  Below
+    db_min a layer adds nothing; at and above db_cap the value stays that of db_cap (the cap against hail)."""
+    db_min, db_cap, step_db = float(db_min), float(db_cap), float(step_db)
+    if not (step_db > 0.0 and db_cap > db_min):
+        raise ValueError('vil_table: db_min < db_cap and step_db > 0')
+    n = int(round((db_cap - db_min) / step_db)) + 1
+    if not 2 <= n <= MAX_TABLE:
+        raise ValueError('vil_table: %d breakpoints; 2 ... %d' % (n, MAX_TABLE))
+    db = db_min + step_db * np.arange(n, dtype=np.float64)
+    db[-1] = db_cap
+    tv = (10.0 ** (db / 10.0)).astype(np.float32)
+    return tv, 3.44e-6 * np.power(tv.astype(np.float64), 4.0 / 7.0)
 
 
 class Maps(object):
@@ -495,12 +685,19 @@ class Maps(object):
         # the maps, in the sweep's own block: they ride the one copy
         if not self.phase & 2:
             return []
-        return ([(k, np.float32, shape(self.spec, k, self.n_rows, self.rays_per_block)) for k in self.spec.fields]
-                + [('count', np.uint64, count_shape(self.spec, self.n_rows, self.rays_per_block))])
+        out = ([(k, np.float32, shape(self.spec, k, self.n_rows, self.rays_per_block)) for k in self.spec.fields]
+               + [('count', np.uint64, count_shape(self.spec, self.n_rows, self.rays_per_block))])
+        if self.spec.column:
+            csh = column_shape(self.spec, self.n_rows, self.rays_per_block)
+            out += [(('column', k), np.float64, csh) for k in self.spec.fields if k in self.spec.column]
+            out += [(('column_layers', k), np.uint8, csh) for k in self.spec.fields if k in self.spec.column]
+        return out
 
     def bind(self, path, address):
         if path == 'count':
             self.c.count = address
+        elif isinstance(path, tuple):         # ('column' | 'column_layers', field)
+            getattr(self.c, path[0])[FIELDS.index(path[1])] = address
         else:
             self.c.values[FIELDS.index(path)] = address
 
@@ -510,15 +707,23 @@ class Maps(object):
             if k in entry:
                 setattr(self.c, k, entry.pop(k))
         for k, ptr in (entry.items() if self.phase & 2 else ()):
-            if k not in ('values', 'count'):
+            if k not in ('values', 'count', 'column', 'column_layers'):
                 raise ValueError("device_outputs['composite']: unknown entry %r" % (k,))
-            for f, q in (ptr.items() if k == 'values' else (('count', ptr),)):
+            for f, q in (ptr.items() if k == 'values' else (('count', ptr),) if k == 'count' else (((k, f), q) for f, q in ptr.items())):
                 self.bind(f, q)
 
     def finish(self, w, coords):
         spec, cnt = self.spec, w.pop('count')
-        return {'values': {k: {q: w[k][:, j] for j, q in enumerate(spec.planes(k))} for k in spec.fields},
-                'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}, 'x_edges': spec.x_edges, 'y_edges': spec.y_edges}
+        if not spec.n_z:
+            return {'values': {k: {q: w[k][:, j] for j, q in enumerate(spec.planes(k))} for k in spec.fields},
+                    'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}, 'x_edges': spec.x_edges, 'y_edges': spec.y_edges}
+        out = {'values': {k: {q: w[k][:, :, j] for j, q in enumerate(spec.planes(k))} for k in spec.fields},
+               'count': {k: cnt[:, :, i] for i, k in enumerate(spec.fields)}, 'x_edges': spec.x_edges, 'y_edges': spec.y_edges,
+               'z_edges': spec.z_edges}
+        if spec.column:
+            out['column'] = {k: w[('column', k)] for k in spec.fields if k in spec.column}
+            out['column_layers'] = {k: w[('column_layers', k)] for k in spec.fields if k in spec.column}
+        return out
 
     def join(self, parts, cat):
         """The chunks of an ensemble call: one map per member (rays_per_block set) -> the blocks joined; else the chunks were
@@ -527,4 +732,7 @@ class Maps(object):
         if self.rays_per_block:
             out['values'] = {k: {q: cat([w['values'][k][q] for w in parts]) for q in self.spec.planes(k)} for k in self.spec.fields}
             out['count'] = {k: cat([w['count'][k] for w in parts]) for k in self.spec.fields}
+            for q in ('column', 'column_layers'):
+                if q in out:
+                    out[q] = {k: cat([w[q][k] for w in parts]) for k in out[q]}
         return out

@@ -192,7 +192,9 @@ struct cpol_ctx {
     // gridded composites (cpol_composite): the running state of this context's pass (max, min, echo-top and count states), the
     // edges of the pass, the per-ray sines and cosines of the call, the maps of a finishing call outside a window image and the
     // caller's device memory (nine `values`, then `count`); the pass (cpol_comp.h)
-    DevBuf b_cstate, b_cedges, b_crays, b_cout[CPOL_COMP_FIELDS + 1];
+    // with height layers: b_ctab holds the float32 layer edges and the column tables (per field with one: the float64 values,
+    // then the float32 breakpoints), and b_cout gains nine `column` and nine `column_layers`
+    DevBuf b_cstate, b_cedges, b_crays, b_cout[3 * CPOL_COMP_FIELDS + 1], b_ctab;
     // ... and the gate planes (CPOL_COMP_PLANE_GATES with host arrays): gate_x then gate_y of the last N_COMP_PLANES non-zero
     // plane_version tags stay on the device, as the table sets do, so the radars of a network that alternate in one pass do not
     // evict each other; a call without a tag uploads into b_cplane.  cplane_stat: {uploads, hits} (cpol_debug_read "composite_plane")
@@ -210,6 +212,7 @@ struct cpol_ctx {
     CompPass cpass;
     CompPlan cplan;                        // ... and the plan of the call at hand (kept here: a call without the struct constructs none)
     std::vector<double> cedges_host;       // ... and what b_cedges holds (the source of its copy)
+    std::vector<double> ctab_host;         // ... and what b_ctab holds
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand
@@ -820,6 +823,8 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
                      &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
+    for (int k = CPOL_COMP_FIELDS + 1; k < 3 * CPOL_COMP_FIELDS + 1; ++k) free_buf(ctx->b_cout[k]);     // (column, column_layers)
+    free_buf(ctx->b_ctab);
     for (auto &cp : ctx->cplanes) free_buf(cp.buf);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
@@ -2584,10 +2589,10 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
 #ifndef CPOL_COMP_COMBINE
 #define CPOL_COMP_COMBINE 1        // the kept lane form of k_comp: 1 lanes that share a cell combined inside the wavefront, 0 every lane on its own
 #endif
-enum { CP_COUNT = CPOL_COMP_FIELDS, CP_N };
+enum { CP_COUNT = CPOL_COMP_FIELDS, CP_COLUMN, CP_LAYERS = CP_COLUMN + CPOL_COMP_FIELDS, CP_N = CP_LAYERS + CPOL_COMP_FIELDS };
 // every refusal of a cpol_composite for the call `c`; queues nothing and leaves the pass as it is.  arr[CP_N]: the caller's nine
-// `values` and `count` for the placement plan (cpol_place.h): arrays of the sweep itself, each with a grow-only buffer of its
-// own, produced by a finishing call alone
+// `values`, `count`, and with height layers the nine `column` and `column_layers`, for the placement plan (cpol_place.h): arrays
+// of the sweep itself, each with a grow-only buffer of its own, produced by a finishing call alone
 static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &call, CompPlan *pl, PlaceArray *arr)
 {
     const char *why = nullptr;
@@ -2603,12 +2608,19 @@ static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &cal
     for (int i = 0; i < pl->n_fields; ++i) {
         const int k = pl->field[i];
         arr[k].user = (uintptr_t)c->values[k];
-        arr[k].bytes = (size_t)pl->n_blocks * pl->n_planes[k] * pl->cells * sizeof(float);
+        arr[k].bytes = (size_t)pl->n_blocks * pl->n_planes[k] * pl->block_cells * sizeof(float);
         arr[k].produced = true;
         arr[k].product = PLACE_SWEEP;
+        if (pl->tv[k].empty()) continue;
+        arr[CP_COLUMN + k].user = (uintptr_t)c->column[k];
+        arr[CP_COLUMN + k].bytes = (size_t)pl->n_blocks * pl->cells * sizeof(double);
+        arr[CP_LAYERS + k].user = (uintptr_t)c->column_layers[k];
+        arr[CP_LAYERS + k].bytes = (size_t)pl->n_blocks * pl->cells;
+        arr[CP_COLUMN + k].produced = arr[CP_LAYERS + k].produced = true;
+        arr[CP_COLUMN + k].product = arr[CP_LAYERS + k].product = PLACE_SWEEP;
     }
     arr[CP_COUNT].user = (uintptr_t)c->count;
-    arr[CP_COUNT].bytes = (size_t)pl->n_blocks * pl->n_fields * pl->cells * sizeof(uint64_t);
+    arr[CP_COUNT].bytes = (size_t)pl->n_blocks * pl->n_fields * pl->block_cells * sizeof(uint64_t);
     arr[CP_COUNT].produced = true;
     arr[CP_COUNT].product = PLACE_SWEEP;
     return CPOL_OK;
@@ -2645,6 +2657,27 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
         }
         HIPCHK(hipMemcpyAsync(ctx->b_cedges.p, blob.data(), (n_ex + n_ey) * sizeof(double), hipMemcpyHostToDevice, st));
         ctx->cpass.open = false;                  // (whatever fails from here on, no half-begun pass stays open)
+        if (pl.n_z) {
+            // the layer edges and the tables: COMP_TAB_EDGE_WORDS doubles' room for the 65 float32 edges, then per field with a
+            // table n doubles and n floats (rounded up to whole doubles), in the order of the fields
+            std::vector<double> &tab = ctx->ctab_host;
+            try {
+                size_t words = COMP_TAB_EDGE_WORDS;
+                for (int k = 0; k < CPOL_COMP_FIELDS; ++k) words += pl.tv[k].size() + (pl.tv[k].size() + 1) / 2;
+                tab.assign(words, 0.0);
+            } catch (...) { ctx->err = "cpol_composite: out of host memory"; return CPOL_ERR_NOMEM; }
+            memcpy(tab.data(), pl.ez.data(), pl.ez.size() * sizeof(float));
+            size_t at_word = COMP_TAB_EDGE_WORDS;
+            for (int k = 0; k < CPOL_COMP_FIELDS; ++k) {
+                const size_t n = pl.tv[k].size();
+                if (!n) continue;
+                memcpy(tab.data() + at_word, pl.tf[k].data(), n * sizeof(double));
+                memcpy(tab.data() + at_word + n, pl.tv[k].data(), n * sizeof(float));
+                at_word += n + (n + 1) / 2;
+            }
+            ENSURE(ctx->b_ctab, tab.size() * sizeof(double));
+            HIPCHK(hipMemcpyAsync(ctx->b_ctab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        }
     }
     const bool gates = pl.plane == CPOL_COMP_PLANE_GATES;
     const double *gx = nullptr, *gy = nullptr;
@@ -2712,13 +2745,22 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
         ca.n_ex = (int)n_ex; ca.n_ey = (int)n_ey;
         ca.step_x = pow2_below((int)n_ex); ca.step_y = pow2_below((int)n_ey);
         ca.n_x = pl.n_x; ca.n_y = pl.n_y; ca.cells = (int)pl.cells;
+        ca.ez = (const float *)ctx->b_ctab.p; ca.n_z = pl.n_z; ca.step_z = pow2_below(pl.n_z + 1); ca.block_cells = pl.block_cells;
         ca.stretches = (int)stretches;
         ca.n_thr = pl.n_thr[k]; ca.slab = pl.slab ? 1 : 0;
         ca.h_lo = pl.h_lo; ca.h_hi = pl.h_hi;
         for (int j = 0; j < pl.n_thr[k]; ++j) ca.thr[j] = pl.thr[k][(size_t)j];
         const unsigned grid = (unsigned)(pl.n_blocks * stretches);
-        const size_t lds = (n_ex + n_ey) * sizeof(double);          // (at most 16 KiB)
-        if (gates) {
+        const size_t lds = (n_ex + n_ey) * sizeof(double) + (pl.n_z ? (size_t)(pl.n_z + 1) * sizeof(float) : 0);          // (at most 16 KiB + 260 B)
+        if (pl.n_z) {
+            if (gates) {
+                if (combine) hipLaunchKernelGGL((k_comp<true, true, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+                else hipLaunchKernelGGL((k_comp<false, true, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+            } else {
+                if (combine) hipLaunchKernelGGL((k_comp<true, false, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+                else hipLaunchKernelGGL((k_comp<false, false, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
+            }
+        } else if (gates) {
             if (combine) hipLaunchKernelGGL((k_comp<true, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
             else hipLaunchKernelGGL((k_comp<false, true>), dim3(grid), dim3(COMP_THREADS), lds, st, ca);
         } else {
@@ -2747,12 +2789,32 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             fa.scount = (const unsigned long long *)at(pl.off_count[k]); fa.stop = (const unsigned *)at(pl.off_top[k]);
             fa.values = (float *)T[k];
             fa.count = (unsigned long long *)T[CP_COUNT] + (size_t)pl.slot[k] * pl.cells;
-            fa.n = pl.n_blocks * pl.cells;
+            fa.n = pl.n_blocks * pl.block_cells;            // (height layers: n_blocks * n_z blocks of `cells`)
             fa.cells = (int)pl.cells; fa.n_planes = pl.n_planes[k]; fa.n_fields = pl.n_fields; fa.n_thr = pl.n_thr[k];
             fa.bmax = (const unsigned char *)at(pl.off_src_max[k]); fa.blow = (const unsigned char *)at(pl.off_src_low[k]);
             hipLaunchKernelGGL(k_comp_finish, dim3((unsigned)cdiv(fa.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, fa);
             HIPCHK(hipGetLastError());
         }
+    if (pl.finish && pl.column) {
+        // the column integrals: one launch per field with a table, behind k_comp_finish (it reads the MAX states alone)
+        size_t at_word = COMP_TAB_EDGE_WORDS;
+        for (int k = 0; k < CPOL_COMP_FIELDS; ++k) {
+            const size_t n = pl.tv[k].size();
+            if (!n) continue;
+            CompColumnArgs co{};
+            co.smax = (const unsigned long long *)at(pl.off_max[k]);
+            co.tf = (const double *)ctx->b_ctab.p + at_word;
+            co.tv = (const float *)(co.tf + n);
+            co.ez = (const float *)ctx->b_ctab.p;
+            co.column = (double *)T[CP_COLUMN + k];
+            co.layers = (unsigned char *)T[CP_LAYERS + k];
+            co.n = pl.n_blocks * pl.cells;
+            co.cells = (int)pl.cells; co.n_z = pl.n_z; co.n_tab = (int)n; co.step_t = pow2_below((int)n); co.gaps = pl.gaps;
+            hipLaunchKernelGGL(k_comp_column, dim3((unsigned)cdiv(co.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, co);
+            HIPCHK(hipGetLastError());
+            at_word += n + (n + 1) / 2;
+        }
+    }
     (void)n_rg;
     try {
         comp_advance(c, pl, &ctx->cpass);
@@ -2988,14 +3050,15 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     }
     // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_MS };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_CP + CP_N };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
     static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
     // (and so do a composite's nine `values` and its `count`: the three never share a call)
-    static_assert(CP_N <= SO_N, "the composite's maps in the slots of the superobservations");
-    // (the sums of a neighbourhood verification, which comes with a composite alone, take slots of the ensemble statistics)
-    static_assert(FR_N <= MS_N, "the fractions' sums in the slots of the ensemble statistics");
+    // (with the columns of its height layers they reach into the slots of the ensemble statistics, which share no call with them)
+    static_assert(CP_N <= SO_N + MS_N, "the composite's maps in the slots of the superobservations and the ensemble statistics");
+    // (the sums of a neighbourhood verification, which comes with a composite alone, take the slots behind the composite's)
+    static_assert(A_CP + CP_N + FR_N <= A_SM, "the fractions' sums in the slots of the ensemble statistics");
     PlaceArray arr[A_N];
     // (a composite shares a call with no other product: refused before the other product's own checks speak)
     if (out->composite && (out->superob || out->histogram || out->member_stats || out->spectrum_moments)) {

@@ -3,8 +3,9 @@
 // SOURCE: its source bytes and the per-call scratch behind it) and the block arithmetic of a call, decided by comp_check() from
 // plain numbers.
 // Plain C++ without HIP types, so that a host program can include it (tests/c_host/comp_check.cpp, tests/test_composite_cpu.py
-// check it without a GPU; comp_check_network.cpp, test_composite_network_cpu.py the network additions).  The kernels are k_comp,
-// k_comp_merge and k_comp_finish (cpol_comp.inl); the rule is stated in
+// check it without a GPU; comp_check_network.cpp, test_composite_network_cpu.py the network additions; comp_check_layers.cpp,
+// test_composite_layers_cpu.py the height layers and the column).  The kernels are k_comp,
+// k_comp_merge, k_comp_finish and k_comp_column (cpol_comp.inl); the rule is stated in
 // include/cosmo_pol_amd.h and cosmo_pol_amd/composite.py.
 #pragma once
 
@@ -23,7 +24,10 @@ constexpr long COMP_MAX_STATE_BYTES = 1L << 30;    // the state of all blocks an
 // is long enough for its own 12 KB of gates to outweigh them; the 180 000 gates of a 360 x 500 sweep give 176 workgroups
 constexpr int COMP_STRETCH = 1024;
 constexpr int COMP_THREADS = 256;                  // threads of a workgroup of k_comp and k_comp_finish
-constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE;
+constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE | CPOL_COMP_COLUMN;
+constexpr int COMP_MAX_LAYERS = CPOL_COMP_MAX_LAYERS;      // n_z: the float32 layer edges (at most 65) lie in LDS beside the x and y edges
+constexpr int COMP_MAX_TABLE = CPOL_COMP_MAX_TABLE;        // breakpoints of a column table: 4 KB + 8 KB of LDS in k_comp_column
+constexpr size_t COMP_TAB_EDGE_WORDS = 40;                 // float64 words at the head of the device's table block: room for the 65 float32 layer edges
 constexpr int COMP_NO_SOURCE = 255;               // the begin value of a source byte: no call has set the cell
 
 // what the entry point knows of the call
@@ -44,6 +48,11 @@ struct CompPass {
     float h_lo = 0.f, h_hi = 0.f;
     std::vector<float> thr[COMP_FIELDS];           // the ROUNDED thresholds
     std::vector<double> ex, ey;
+    // height layers and the column: the ROUNDED layer edges (empty: none), gaps, and per field the table as the begin found it
+    std::vector<float> ez;
+    int gaps = 0;
+    std::vector<float> tv[COMP_FIELDS];
+    std::vector<double> tf[COMP_FIELDS];
 };
 
 // a call that passed: the numbers the launches need
@@ -74,6 +83,14 @@ struct CompPlan {
     int plane = 0, source = 0;
     bool with_source = false;
     bool begin = false, finish = false;
+    // height layers and the column: n_z = 0 none -- else a block of every state holds n_z * cells entries (block_cells), and
+    // k_comp_finish serves n_blocks * n_z blocks of `cells`
+    int n_z = 0, gaps = 0;
+    long block_cells = 0;                          // max(n_z, 1) * cells
+    bool column = false;
+    std::vector<float> ez;                         // the ROUNDED layer edges [n_z + 1]
+    std::vector<float> tv[COMP_FIELDS];            // the tables (empty: no column of the field)
+    std::vector<double> tf[COMP_FIELDS];
 };
 
 // a threshold or slab bound rounded once to float32 (at or beyond the midpoint between FLT_MAX and 2^128: infinity, as IEEE rounds)
@@ -93,7 +110,8 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     if (c->phase < 0 || c->phase > 3) return "phase must lie in 0 ... 3";
     if (((c->fields >> COMP_FIELDS) & 1u)) return "RVEL is float64 and is not composed";
     if (c->fields == 0 || (c->fields >> COMP_FIELDS) != 0) return "fields must name at least one of the 9 float32 fields and no other bit";
-    if (c->products == 0 || (c->products & ~COMP_PRODUCTS) != 0) return "products must name MAX, LOWEST or ECHO_TOP and no other bit";
+    if (c->products == 0 || (c->products & ~COMP_PRODUCTS) != 0)
+        return "products must name MAX, LOWEST or ECHO_TOP and no other bit (beside them SOURCE, or COLUMN with height layers)";
     if (c->plane != CPOL_COMP_PLANE_RADAR && c->plane != CPOL_COMP_PLANE_GATES) return "plane must be CPOL_COMP_PLANE_RADAR or CPOL_COMP_PLANE_GATES";
     if (c->source < 0 || c->source >= COMP_NO_SOURCE) return "source must lie in 0 ... 254";
     pl->with_source = (c->products & CPOL_COMP_SOURCE) != 0;
@@ -125,6 +143,47 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         pl->h_hi = comp_f32(c->h_hi);
         if (!(pl->h_lo < pl->h_hi)) return "the height slab needs h_lo < h_hi after rounding to float32";
     }
+    // height layers and the column
+    if (c->n_z < 0 || c->n_z > COMP_MAX_LAYERS) return "n_z must lie in 0 ... 64";
+    pl->n_z = c->n_z;
+    pl->column = (c->products & CPOL_COMP_COLUMN) != 0;
+    if (pl->column && c->n_z == 0) return "COLUMN needs height layers (n_z, edges_z)";
+    if (pl->column && !(c->products & CPOL_COMP_MAX)) return "COLUMN needs MAX";
+    if (c->gaps != CPOL_COMP_GAPS_ZERO && c->gaps != CPOL_COMP_GAPS_HOLD) return "gaps must be CPOL_COMP_GAPS_ZERO or CPOL_COMP_GAPS_HOLD";
+    if (c->gaps != 0 && !pl->column) return "gaps without COLUMN";
+    pl->gaps = c->gaps;
+    if (c->n_z > 0) {
+        if (c->use_slab) return "height layers with a height slab: the first and last edge are the slab";
+        if (c->products & CPOL_COMP_LOWEST) return "height layers with LOWEST: per layer the maximum and the count alone";
+        if (c->products & CPOL_COMP_ECHO_TOP) return "height layers with ECHO_TOP: per layer the maximum and the count alone";
+        if (c->products & CPOL_COMP_SOURCE) return "height layers with SOURCE: per layer the maximum and the count alone";
+        if (!c->edges_z) return "edges_z is NULL";
+        pl->ez.resize((size_t)c->n_z + 1);
+        for (int j = 0; j <= c->n_z; ++j) {
+            if (!(c->edges_z[j] == c->edges_z[j])) return "a layer edge is NaN";
+            pl->ez[(size_t)j] = comp_f32(c->edges_z[j]);
+            if (j && !(pl->ez[(size_t)j - 1] < pl->ez[(size_t)j])) return "the layer edges are not strictly ascending after rounding to float32";
+        }
+    }
+    {
+        bool any_table = false;
+        for (int k = 0; k < COMP_FIELDS; ++k) {
+            const int n = c->n_table[k];
+            if (n == 0) continue;
+            if (!pl->column) return "a column table without COLUMN";
+            if (!((c->fields >> k) & 1u)) return "a column table of a field that is not requested";
+            if (n < 2 || n > COMP_MAX_TABLE) return "a column table needs 2 ... 1024 breakpoints";
+            if (!c->table_v[k] || !c->table_f[k]) return "table_v or table_f is NULL";
+            pl->tv[k].assign(c->table_v[k], c->table_v[k] + n);
+            pl->tf[k].assign(c->table_f[k], c->table_f[k] + n);
+            for (int j = 0; j < n; ++j) {
+                if (!std::isfinite(pl->tv[k][(size_t)j]) || !std::isfinite(pl->tf[k][(size_t)j])) return "a breakpoint or a value of a column table is NaN or infinite";
+                if (j && !(pl->tv[k][(size_t)j - 1] < pl->tv[k][(size_t)j])) return "the breakpoints of a column table are not strictly ascending";
+            }
+            any_table = true;
+        }
+        if (pl->column && !any_table) return "COLUMN needs a table for at least one requested field";
+    }
     if (c->n_x < 1 || c->n_y < 1) return "n_x and n_y must be >= 1";
     if (c->n_x + 1 > COMP_MAX_EDGES || c->n_y + 1 > COMP_MAX_EDGES) return "n_x + 1 and n_y + 1 must be at most 1024";
     if (!c->edges_x || !c->edges_y) return "edges_x or edges_y is NULL";
@@ -133,12 +192,14 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     } else if (!c->ray_sin || !c->ray_cos) return "ray_sin or ray_cos is NULL";
     pl->n_x = c->n_x; pl->n_y = c->n_y;
     pl->cells = (long)c->n_x * c->n_y;
+    pl->block_cells = (long)(c->n_z > 0 ? c->n_z : 1) * pl->cells;
     if (c->rays_per_block < 0 || (c->rays_per_block > 0 && call.n_rows % c->rays_per_block != 0))
         return "rays_per_block must be >= 0 and divide the rows of the call";
     pl->rows_per_block = c->rays_per_block ? c->rays_per_block : call.n_rows;
     pl->n_blocks = call.n_rows / pl->rows_per_block;
-    // the state (n_blocks <= 2^31 rows, cells < 2^20, at most 9 * 28 bytes per cell and block: no overflow of long)
-    const long per = pl->n_blocks * pl->cells;
+    // the state (n_blocks <= 2^31 rows, cells < 2^20, at most 9 * 28 bytes per cell and block, or 64 layers of 9 * 16 bytes: no
+    // overflow of long)
+    const long per = pl->n_blocks * pl->block_cells;
     long off = 0;
     for (int i = 0; i < pl->n_fields; ++i) {
         const int k = pl->field[i];
@@ -183,11 +244,18 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         for (int i = 0; i < pl->n_fields; ++i)
             if (pass.thr[pl->field[i]] != pl->thr[pl->field[i]]) return "thresholds differ from the open pass";
         if (pass.ex != pl->ex || pass.ey != pl->ey) return "edges differ from the open pass";
+        if (pass.ez != pl->ez) return "the height layers differ from the open pass";
+        if (pass.gaps != pl->gaps) return "gaps differ from the open pass";
+        for (int k = 0; k < COMP_FIELDS; ++k)
+            if (pass.tv[k] != pl->tv[k] || pass.tf[k] != pl->tf[k]) return "a column table differs from the open pass";
     }
     if (pl->finish) {
         if (!c->count) return "a finishing call needs count";
         for (int i = 0; i < pl->n_fields; ++i)
             if (!c->values[pl->field[i]]) return "a finishing call needs values for every requested field";
+        for (int k = 0; k < COMP_FIELDS; ++k)
+            if (!pl->tv[k].empty() && (!c->column[k] || !c->column_layers[k]))
+                return "a finishing call needs column and column_layers for every field with a table";
     }
     return nullptr;
 }
@@ -205,6 +273,9 @@ inline void comp_advance(const cpol_composite *c, const CompPlan &pl, CompPass *
         for (int k = 0; k < COMP_FIELDS; ++k) pass->thr[k] = pl.thr[k];
         pass->ex = pl.ex;
         pass->ey = pl.ey;
+        pass->ez = pl.ez;
+        pass->gaps = pl.gaps;
+        for (int k = 0; k < COMP_FIELDS; ++k) { pass->tv[k] = pl.tv[k]; pass->tf[k] = pl.tf[k]; }
     }
     if (pl.finish) pass->open = false;
 }

@@ -26,6 +26,9 @@ struct CompArgs {
     float h_lo, h_hi;
     float thr[COMP_MAX_THR];        // rounded
     const double *gx, *gy;          // the gate plane: the caller's x and y [geo_gates] (the radar plane reads neither)
+    const float *ez;                // LAYERS: the rounded layer edges on the device [n_z + 1]
+    long block_cells;               // LAYERS: n_z * cells, the states of one block
+    int n_z, step_z;                // LAYERS: the layers, and the largest power of two <= n_z + 1
 };
 
 // the ordered key of a float32: a total order -inf < ... < -0.0 < +0.0 < ... < +inf; 0 and 0xFFFFFFFF are keys of NaNs alone
@@ -49,21 +52,30 @@ __device__ __forceinline__ float comp_unkey(unsigned k)
 // GATES: the gate plane (CPOL_COMP_PLANE_GATES) -- x and y are two float64 loads per gate, gx[gg] and gy[gg], in place of `dist`
 // and the wave-uniform sine / cosine pair; no multiplication, and a NaN coordinate does not count.  Everything behind the
 // coordinates is the same code: consecutive gates of a ray still fall into the same or neighbouring cells on any sensible plane.
-template <bool COMBINE, bool GATES>
+// LAYERS: height layers (cpol_composite.n_z) -- the float32 layer edges lie in LDS behind the x and y edges, a third branch-free
+// search gives iz (comparisons in float32 alone: the slab test of the plain form is not compiled), and the cell index becomes
+// iz * cells + iy * n_x + ix within a block of n_z * cells.  The in-wavefront combine is the same code on that index: its runs
+// are runs of equal (layer, cell) -- long at a low elevation, a few gates at a steep one, where a ray changes layer every few
+// gates.  MAX and the count alone (comp_check refuses the other products with layers), so want_low and n_thr are off by the
+// arguments.  LAYERS = false is the kernel as it was.
+template <bool COMBINE, bool GATES, bool LAYERS = false>
 __global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
 {
     extern __shared__ double comp_lds[];
     const int tid = threadIdx.x;
     double *const ex = comp_lds, *const ey = comp_lds + a.n_ex;
+    float *const ez = (float *)(comp_lds + a.n_ex + a.n_ey);
     for (int j = tid; j < a.n_ex; j += COMP_THREADS) ex[j] = a.ex[j];
     for (int j = tid; j < a.n_ey; j += COMP_THREADS) ey[j] = a.ey[j];
+    if (LAYERS)
+        for (int j = tid; j <= a.n_z; j += COMP_THREADS) ez[j] = a.ez[j];
     __syncthreads();
     const long b = (long)blockIdx.x / a.stretches;
     const long s = (long)blockIdx.x % a.stretches;
     const long g0 = b * a.block_gates + s * (long)COMP_STRETCH;
     const long g1 = min(g0 + (long)COMP_STRETCH, (b + 1) * a.block_gates);
     const bool want_max = a.smax != nullptr, want_low = a.slow != nullptr;
-    const long cell0 = b * (long)a.cells;
+    const long cell0 = LAYERS ? b * a.block_cells : b * (long)a.cells;
     // (every lane of the workgroup takes every turn of the loop: the shuffles below need whole wavefronts)
     for (long base = g0; base < g1; base += COMP_THREADS) {
         const long g = base + tid;
@@ -88,9 +100,14 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp(const CompArgs a)
             const int ix = hist_bin<double>(ex, a.n_ex, a.step_x, x) - 1;
             const int iy = hist_bin<double>(ey, a.n_ey, a.step_y, y) - 1;
             bool counts = v == v && located && h == h && ix >= 0 && ix < a.n_x && iy >= 0 && iy < a.n_y;
-            if (a.slab) counts = counts && a.h_lo <= h && h < a.h_hi;
+            int iz = 0;
+            if (LAYERS) {
+                // (h NaN: no edge <= h, iz = -1; h on the last edge or above: iz = n_z)
+                iz = hist_bin<float>(ez, a.n_z + 1, a.step_z, h) - 1;
+                counts = counts && iz >= 0 && iz < a.n_z;
+            } else if (a.slab) counts = counts && a.h_lo <= h && h < a.h_hi;
             if (counts) {
-                cell = iy * a.n_x + ix;
+                cell = LAYERS ? iz * a.cells + iy * a.n_x + ix : iy * a.n_x + ix;
                 const unsigned kv = comp_key(v), kh = comp_key(h);
                 kmax = ((unsigned long long)kv << 32) | kh;
                 klow = ((unsigned long long)kh << 32) | kv;
@@ -216,4 +233,71 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp_finish(const CompFinishAr
         out[(long)j * a.cells] = s ? comp_unkey(s) : nan;
     }
     a.count[b * (long)a.n_fields * a.cells + c] = a.scount[i];
+}
+
+// ---- the column of the height layers (CPOL_COMP_COLUMN): VIL and its kin ----
+struct CompColumnArgs {
+    const unsigned long long *smax; // this field's MAX states [n_blocks][n_z][cells]
+    const double *tf;               // the table's values [n_tab] ...
+    const float *tv;                // ... and breakpoints [n_tab], on the device
+    const float *ez;                // the rounded layer edges [n_z + 1]
+    double *column;                 // [n_blocks][cells]
+    unsigned char *layers;          // [n_blocks][cells]
+    long n;                         // n_blocks * cells
+    int cells, n_z, n_tab;
+    int step_t;                     // the largest power of two <= n_tab
+    int gaps;                       // CPOL_COMP_GAPS_ZERO / CPOL_COMP_GAPS_HOLD
+};
+
+// One thread per (block, cell) of one field; the field's table (at most 4 KB of breakpoints and 8 KB of values) and the layer
+// edges lie in LDS.  The thread walks its cell's layers in ascending order -- stride `cells`, so the loads of a wavefront
+// coalesce -- and per counting layer decodes the key, searches the table (comparisons in float32 alone), interpolates with
+// separately rounded float64 operations (-ffp-contract=off) and adds f * dz to the running float64 sum: at most 64 terms in a
+// fixed order, so the sum is composite.column_of's bit for bit.  HOLD: an empty layer below the highest counting layer (found
+// by a first short loop over the states) and above the lowest repeats the f of the nearest counting layer below.  No atomics.
+__global__ __launch_bounds__(COMP_THREADS) void k_comp_column(const CompColumnArgs a)
+{
+    __shared__ double tf[COMP_MAX_TABLE];
+    __shared__ float tv[COMP_MAX_TABLE];
+    __shared__ float ez[COMP_MAX_LAYERS + 1];
+    for (int j = threadIdx.x; j < a.n_tab; j += COMP_THREADS) { tf[j] = a.tf[j]; tv[j] = a.tv[j]; }
+    for (int j = threadIdx.x; j <= a.n_z; j += COMP_THREADS) ez[j] = a.ez[j];
+    __syncthreads();
+    const long i = (long)blockIdx.x * COMP_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const long b = i / a.cells, c = i % a.cells;
+    const unsigned long long *const s = a.smax + b * (long)a.n_z * a.cells + c;
+    int top = -1;                   // the highest counting layer
+    if (a.gaps == CPOL_COMP_GAPS_HOLD)
+        for (int l = 0; l < a.n_z; ++l)
+            if (s[(long)l * a.cells]) top = l;
+    double sum = 0.0, held = 0.0;
+    int used = 0;
+    bool seen = false;              // a counting layer lies below
+    for (int l = 0; l < a.n_z; ++l) {
+        const unsigned long long st = s[(long)l * a.cells];
+        const bool have = st != 0ull;
+        if (have) {
+            const float v = comp_unkey((unsigned)(st >> 32));
+            const int j = hist_bin<float>(tv, a.n_tab, a.step_t, v) - 1;
+            if (j < 0) held = 0.0;
+            else if (j >= a.n_tab - 1) held = tf[a.n_tab - 1];
+            else {
+                const double t = ((double)v - (double)tv[j]) / ((double)tv[j + 1] - (double)tv[j]);
+                const double d = tf[j + 1] - tf[j];
+                const double p = t * d;
+                held = tf[j] + p;
+            }
+        }
+        const bool adds = have || (seen && l < top);
+        seen = seen || have;
+        if (adds) {
+            const double dz = (double)ez[l + 1] - (double)ez[l];
+            const double term = held * dz;
+            sum = sum + term;
+            ++used;
+        }
+    }
+    a.column[i] = seen ? sum : __longlong_as_double(0x7FF8000000000000ll);
+    a.layers[i] = (unsigned char)used;
 }

@@ -81,6 +81,7 @@ inline const char *frac_check(const cpol_fractions *f, const cpol_composite *c, 
 {
     *pl = FracPlan{};
     if (!c || !cp) return "needs a composite (outputs->composite) in the same call";
+    if (cp->n_z > 0) return "a composite with height layers is not scored (the planes carry a layer axis; the column is no plane)";
     if (!cp->finish) return "the composite call does not finish its pass (phase & 2): the maps do not exist yet";
     if (f->field < 0 || f->field >= COMP_FIELDS || !((c->fields >> f->field) & 1u)) return "field is not among the composed fields (composite->fields)";
     const int n_planes = cp->n_planes[f->field];

@@ -44,6 +44,8 @@ class Fractions(object):
     def __init__(self, composite_spec, field, thresholds, radii, plane='max'):
         if not isinstance(composite_spec, Composite):
             raise ValueError('composite_spec: a cosmo_pol_amd.composite.Composite, got %r' % (composite_spec,))
+        if composite_spec.n_z:
+            raise ValueError('a composite with height layers is not scored: its planes carry a layer axis, and the column is no plane')
         if field == 'RVEL':
             raise ValueError('RVEL is float64 and is not composed')
         if field not in composite_spec.fields:

@@ -600,10 +600,45 @@ typedef struct cpol_histogram {
  * CPOL_ERR_ARG in addition, nothing queued, an open pass untouched, the context usable: `plane` outside 0 / 1; PLANE_GATES
  * with a NULL gate_x or gate_y (NULL ray_sin / ray_cos is refused on the radar plane alone); `source` outside 0 ... 254; a
  * non-zero `source` without the SOURCE bit; SOURCE without MAX and without LOWEST; `plane` differing from the open pass (the
- * SOURCE bit is part of `products`); the 1 GiB limit, which counts the source bytes and the scratch. */
+ * SOURCE bit is part of `products`); the 1 GiB limit, which counts the source bytes and the scratch.
+ *
+ * HEIGHT LAYERS AND THE COLUMN: a stack of CAPPIs in one pass, and column integrals such as VIL.  Everything above stays as it
+ * is; the new members lie at the end of the struct and a zero-initialised tail means off.
+ * LAYERS (`n_z` = 1 ... 64, `edges_z`: n_z + 1 heights in metres, float64, each rounded once to float32 by the library; strictly
+ * ascending after the rounding and not NaN).  A gate that counts above counts in layer l iff ez[l] <= h && h < ez[l + 1] in
+ * float32: a gate on the last edge is outside, as on the x and y axes, and a gate below the first edge or at or above the last
+ * counts nowhere.  Per (block, layer, cell) the state is the MAX state and the count of above: a block of the state holds
+ * n_z * cells entries, the cell index iz * cells + iy * n_x + ix.  values[k] is float32 [n_blocks][n_z][2][n_y][n_x] (max,
+ * height_of_max per layer), count uint64 [n_blocks][n_z][n_requested_fields][n_y][n_x].  With layers use_slab, LOWEST, ECHO_TOP
+ * and SOURCE are refused (the first and last edge are the slab); a gate plane and several radars in one pass work as before,
+ * `source` stays 0.  cpol_fractions beside a layered composite is refused.
+ * COLUMN (the product bit CPOL_COMP_COLUMN = 64; it needs layers and MAX; bits 8 and 32 stay refused as unknown bits).  Per
+ * requested field k an optional table: n_table[k] = 2 ... 1024 breakpoints table_v[k] (float32, in the field's linear units,
+ * finite, strictly ascending) and values table_f[k] (float64, finite); n_table[k] = 0: no column of that field; at least one
+ * requested field has a table.  For a layer whose maximum v exists: i = #{ j : tv[j] <= v } - 1; i < 0: f = 0.0; i >= n - 1:
+ * f = tf[n - 1] (the cap; +inf takes it); else t = ((double)v - (double)tv[i]) / ((double)tv[i + 1] - (double)tv[i]),
+ * f = tf[i] + t * (tf[i + 1] - tf[i]) -- every operation ONE float64 operation (-ffp-contract=off).  The column of a cell is
+ * C = sum over l ascending, from +0.0, of f_l * dz_l with dz_l = (double)ez[l + 1] - (double)ez[l]: one thread adds at most 64
+ * terms in a fixed order, so the result is the NumPy rule's (composite.column_of) bit for bit.  `gaps`: CPOL_COMP_GAPS_ZERO = 0 an
+ * empty layer adds nothing; CPOL_COMP_GAPS_HOLD = 1 an empty layer with a counting layer below it and a counting layer above it
+ * in the same cell takes the f of the nearest counting layer below; empty layers below the lowest or above the highest counting
+ * layer add nothing.  A cell with no counting layer is NaN.  OUTPUTS of a finishing call: column[k] float64 [n_blocks][n_y][n_x]
+ * and column_layers[k] uint8 [n_blocks][n_y][n_x] (the layers that contributed, held ones included) for every field with a
+ * table; they follow p->outputs_on_device.  edges_z, table_v and table_f are host arrays, read by every call of the pass.
+ * k_comp<.., LAYERS = true> composes, k_comp_finish decodes n_blocks * n_z blocks, k_comp_column (one thread per block and
+ * cell, once per field with a table) integrates behind it.
+ * CPOL_ERR_ARG in addition: n_z outside 0 ... 64; n_z > 0 with a NULL edges_z, a NaN edge, edges not strictly ascending after
+ * the rounding, use_slab, LOWEST, ECHO_TOP or SOURCE; COLUMN without layers or without MAX; gaps outside 0 / 1, or non-zero
+ * without COLUMN; n_table[k] non-zero without COLUMN or for a field not requested; n_table[k] outside 2 ... 1024; a NULL table;
+ * a breakpoint or value NaN or infinite; breakpoints not strictly ascending; COLUMN with no table at all; layers, tables or gaps
+ * differing from the open pass; a finishing call with a NULL column or column_layers of a field with a table; the 1 GiB limit,
+ * which counts n_blocks * n_z * cells per MAX state and count. */
 #define CPOL_COMP_FIELDS 9
 #define CPOL_COMP_MAX_THRESHOLDS 4
-enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4, CPOL_COMP_SOURCE = 16 };     /* (8 is no product: refused) */
+enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4, CPOL_COMP_SOURCE = 16, CPOL_COMP_COLUMN = 64 };     /* (8 and 32 are no products: refused) */
+#define CPOL_COMP_MAX_LAYERS 64
+#define CPOL_COMP_MAX_TABLE 1024
+enum { CPOL_COMP_GAPS_ZERO = 0, CPOL_COMP_GAPS_HOLD = 1 };
 enum { CPOL_COMP_PLANE_RADAR = 0, CPOL_COMP_PLANE_GATES = 1 };
 typedef struct cpol_composite {
     uint32_t fields;            /* bit k: field k composed                                                         */
@@ -623,6 +658,14 @@ typedef struct cpol_composite {
     int32_t  source;            /* 0 ... 254: this call's number in the source_of_* planes (CPOL_COMP_SOURCE)      */
     const double *gate_x, *gate_y;              /* PLANE_GATES: [geo_rays * n_gates], the caller's projection      */
     uint64_t plane_version;     /* non-zero: the tag under which the library keeps gate_x / gate_y on the device   */
+    int32_t  n_z;               /* 0: no height layers; else 1 ... 64 layers                                       */
+    int32_t  gaps;              /* CPOL_COMP_GAPS_ZERO (0) or CPOL_COMP_GAPS_HOLD: an empty layer in the column    */
+    const double *edges_z;      /* [n_z + 1] metres, each rounded once to float32                                  */
+    int32_t  n_table[CPOL_COMP_FIELDS];         /* breakpoints of field k's column table; 0: no column of field k  */
+    const float  *table_v[CPOL_COMP_FIELDS];    /* [n_table[k]] breakpoints in the field's linear units            */
+    const double *table_f[CPOL_COMP_FIELDS];    /* [n_table[k]] values at the breakpoints                          */
+    double   *column[CPOL_COMP_FIELDS];         /* [n_blocks][n_y][n_x]; read by a finishing call                  */
+    uint8_t  *column_layers[CPOL_COMP_FIELDS];  /* [n_blocks][n_y][n_x]; likewise                                  */
 } cpol_composite;
 
 /* Neighbourhood verification: the sums of the fractions skill score (FSS; Roberts and Lean 2008) of ONE finished plane of a
@@ -1142,7 +1185,9 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * share a cell combined inside the wavefront, 2: every lane on its own; blocking; honours c.phase; needs no staged model or
  * tables; cpol_composite's refusals, and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.  With c.plane =
  * CPOL_COMP_PLANE_GATES c.gate_x and c.gate_y are host arrays [n_rays * n_gates] (kept under c.plane_version like a sweep's) and
- * dist may be NULL; with CPOL_COMP_SOURCE in c.products the call runs k_comp_merge too, with c.source.
+ * dist may be NULL; with CPOL_COMP_SOURCE in c.products the call runs k_comp_merge too, with c.source.  With height layers
+ * (c.n_z > 0) the call runs the layered k_comp, and a finishing call with CPOL_COMP_COLUMN runs k_comp_column and copies
+ * c.column / c.column_layers (host arrays) too.
  * "composite_plane" copies two int64: {uploads, hits} of the context's store of gate planes (cpol_composite.plane_version).
  * "composite_stretch" copies one int32: the gates a workgroup of k_comp owns.
  * "fractions_maps" is the same for the neighbourhood verification: the checks and the three kernels of cpol_frac.inl on

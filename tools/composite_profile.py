@@ -24,7 +24,20 @@ pass the kernel statistics files with --kernel-stats NAME=FILE to have k_comp's 
 NOT measured: several lanes in flight, device-resident outputs, more than one field per call on the single sweep, rays_per_block > 0
 on the single sweep, sub-beam volumes, the ensemble's per-gate hand-over.
 
+--layers: height layers and the column.  The 5-elevation volume on the 300 x 300 grid with 20 layers of 500 m,
+ZH with composite.vil_table(), written to profiles/composite_layers_profile.json:
+
+  lay_dev    get_PPI_composite with the layered spec: ONE pass gives the 20 CAPPIs and the VIL;
+  lay_slabs  what the library offered before for the same result: 20 get_PPI_composite passes, one height_range slab each, then
+             composite.column_of on the host over the stacked maps (the slabs' planes are bit for bit the layers': 'stack_equal');
+  b / parent_b, bench / parent_bench   the controls: the plain simulate_rays_composite call and bench.py's line, this tree and DIR.
+
+Kernel times of the layered k_comp against the plain one, and of k_comp_column, from
+    rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/composite_profile.py --worker lay_forms --trace
+(the five sweeps of the volume fed through the test hook: plain and layered spec, both lane forms).
+
   python tools/composite_profile.py --repeat 3 --out profiles/composite_profile.json
+  python tools/composite_profile.py --layers --repeat 3 --parent-tree DIR --bench
   python tools/composite_profile.py --worker b            (one process, one JSON line)
 """
 import argparse
@@ -41,7 +54,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOM = ('lats', 'lons', 'dist', 'heights')
 N_RAYS = 360
 ELEVATIONS = [1.0, 3.0, 5.0, 8.0, 12.0]
-WORKERS = ('a', 'b', 'c', 'vol_dev', 'vol_host', 'ens_dev', 'forms')
+WORKERS = ('a', 'b', 'c', 'vol_dev', 'vol_host', 'ens_dev', 'forms', 'lay_dev', 'lay_slabs', 'lay_forms')
+LAYER_EDGES = [500.0 * j for j in range(21)]          # 20 layers of 500 m
 
 
 def result_bytes(res):
@@ -59,6 +73,8 @@ def result_bytes(res):
     for planes in w.get('values', {}).values():
         n += sum(a.nbytes for a in planes.values())
     n += sum(a.nbytes for a in w.get('count', {}).values())
+    for q in ('column', 'column_layers'):
+        n += sum(a.nbytes for a in w.get(q, {}).values())
     for s in res.get('sweeps', []):
         n += result_bytes(s)
     return int(n)
@@ -94,7 +110,32 @@ def worker(a):
                     op._ctx.composite_fields({'ZH': np.array(res['ZH'])}, res['dist'], res['heights'], az, s, lane_form=form)
         op.close()
         return
-    if a.worker == 'a':
+    if a.worker.startswith('lay_'):
+        layered = CP.Composite('ZH', e, e, products=('max', 'column'), z_edges=LAYER_EDGES, column={'ZH': CP.vil_table()})
+    if a.worker == 'lay_forms':
+        # the volume's five sweeps through the test hook: the plain MAX composite and the layered one, both lane forms
+        sweeps = [op.simulate_rays(az, np.full(N_RAYS, e_)) for e_ in ELEVATIONS]
+        for _ in range(max(1, a.warmup)):
+            for form in (1, 2):
+                for s in (spec, layered):
+                    for i, r in enumerate(sweeps):
+                        op._ctx.composite_fields({'ZH': np.array(r['ZH'])}, r['dist'], r['heights'], az, s, lane_form=form,
+                                                 phase=(1 if i == 0 else 0) | (2 if i == len(sweeps) - 1 else 0))
+        op.close()
+        return
+    if a.worker == 'lay_dev':
+        run = lambda: op.get_PPI_composite(ELEVATIONS, layered, azimuths=az)
+    elif a.worker == 'lay_slabs':
+        slabs = [CP.Composite('ZH', e, e, height_range=(LAYER_EDGES[l], LAYER_EDGES[l + 1])) for l in range(len(LAYER_EDGES) - 1)]
+
+        def run():
+            maps = [op.get_PPI_composite(ELEVATIONS, s, azimuths=az)['composite'] for s in slabs]
+            stack = np.stack([m['values']['ZH']['max'] for m in maps], axis=1)
+            col, lay = CP.column_of(layered, stack)
+            return {'composite': {'values': {'ZH': {'max': stack, 'height_of_max': np.stack([m['values']['ZH']['height_of_max'] for m in maps], axis=1)}},
+                                  'count': {'ZH': np.stack([m['count']['ZH'] for m in maps], axis=1)}, 'column': {'ZH': col},
+                                  'column_layers': {'ZH': lay}}}
+    elif a.worker == 'a':
         run = lambda: op.simulate_rays(az, el)
     elif a.worker == 'ens_dev':
         run = lambda: op.simulate_rays_ensemble_composite(az, el, spec)
@@ -137,6 +178,13 @@ def worker(a):
         out['cells_non_empty'] = int((n > 0).sum())
         out['cells'] = int(n.size)
         out['max_checksum'] = float(np.nansum(m, dtype=np.float64))
+        if 'column' in w:
+            col = np.ascontiguousarray(w['column']['ZH'])
+            out['column_cells'] = int(np.isfinite(col).sum())
+            out['column_max_kg_m2'] = float(np.nanmax(col))
+            out['column_bits_xor'] = int(np.bitwise_xor.reduce(col.view(np.uint64).ravel()))       # (equal bits give equal words)
+            out['column_layers_sum'] = int(np.asarray(w['column_layers']['ZH'], dtype=np.int64).sum())
+            out['stack_bits_xor'] = int(np.bitwise_xor.reduce(np.ascontiguousarray(m).view(np.uint32).ravel()))
     print(json.dumps(out))
     op.close()
 
@@ -144,11 +192,14 @@ def worker(a):
 def kernel_name(n):
     """k_comp_finish, k_comp_combined (the wavefront combine), k_comp_per_lane, or the bare name of another kernel"""
     n = n.split('(')[0]
-    if 'k_comp_finish' in n:
-        return 'k_comp_finish'
+    for plain in ('k_comp_finish', 'k_comp_column', 'k_comp_merge'):
+        if plain in n:
+            return plain
     if 'k_comp' in n:
-        arg = n.split('<', 1)[1] if '<' in n else ''
-        return 'k_comp_combined' if ('true' in arg or '1' in arg) else 'k_comp_per_lane'
+        # k_comp<COMBINE, GATES, LAYERS>: the first argument names the lane form, the third the layered instantiation
+        args = [x.strip() for x in (n.split('<', 1)[1].split('>')[0] if '<' in n else '').split(',')]
+        on = lambda i: len(args) > i and args[i] in ('true', '1')       # noqa: E731
+        return ('k_comp_combined' if on(0) else 'k_comp_per_lane') + ('_layers' if on(2) else '')
     return n.split('<')[0].strip().split(' ')[-1]
 
 
@@ -211,6 +262,9 @@ def driver(a):
         tags.insert(1, 'parent_a')
     if a.members:
         tags += ['ens_dev']
+    if a.layers:
+        tags = ['lay_dev', 'lay_slabs', 'b'] + (['parent_b'] if a.parent_tree else [])
+        a.out = a.out or os.path.join(ROOT, 'profiles', 'composite_layers_profile.json')
     if a.bench:
         tags += ['bench'] + (['parent_bench'] if a.parent_tree else [])
     if a.calls:
@@ -249,7 +303,8 @@ def driver(a):
         med = [r['ms_per_call_median'] for r in recs]
         c = {'ms_per_call_median_of_processes': float(np.median(med)), 'ms_per_call_medians': med,
              'spread': float((max(med) - min(med)) / np.median(med))}
-        for k in ('bytes_handed_over', 'zh_checksum', 'max_checksum', 'counted', 'cells_non_empty', 'cells', 'members', 'elevations'):
+        for k in ('bytes_handed_over', 'zh_checksum', 'max_checksum', 'counted', 'cells_non_empty', 'cells', 'members', 'elevations',
+                  'column_cells', 'column_max_kg_m2', 'column_bits_xor', 'column_layers_sum', 'stack_bits_xor'):
             if k in recs[0]:
                 c[k] = recs[0][k]
         result['calls'][tag] = c
@@ -270,6 +325,18 @@ def driver(a):
         result['vol_dev_over_vol_host_ms'] = ms('vol_dev') / ms('vol_host')
         result['vol_maps_equal'] = bool(calls['vol_dev'].get('max_checksum') == calls['vol_host'].get('max_checksum')
                                         and calls['vol_dev'].get('counted') == calls['vol_host'].get('counted'))
+    if 'lay_dev' in calls and 'lay_slabs' in calls:
+        result['workload'] += '; --layers: the volume on the 300 x 300 grid, %d layers of 500 m, ZH with vil_table()' % (len(LAYER_EDGES) - 1)
+        result['lay_dev_over_lay_slabs_ms'] = ms('lay_dev') / ms('lay_slabs')
+        result['column_equal'] = bool(all(calls['lay_dev'].get(k) == calls['lay_slabs'].get(k) is not None
+                                          for k in ('column_bits_xor', 'column_layers_sum', 'column_cells')))
+        result['stack_equal'] = bool(all(calls['lay_dev'].get(k) == calls['lay_slabs'].get(k) is not None
+                                         for k in ('stack_bits_xor', 'counted', 'max_checksum')))
+    if 'parent_b' in calls and 'b' in calls:
+        cb, pb = calls['b'], calls['parent_b']
+        result['control_composite'] = {'b_over_parent_b_ms': ms('b') / ms('parent_b'),
+                                       'each_median_inside_the_others_range': inside(cb['ms_per_call_medians'], pb['ms_per_call_medians']),
+                                       'maps_equal': bool(pb.get('max_checksum') == cb.get('max_checksum') and pb.get('counted') == cb.get('counted'))}
     if 'parent_a' in calls and 'a' in calls:
         ca, pa = calls['a'], calls['parent_a']
         result['control_sweep'] = {'a_over_parent_a_ms': ms('a') / ms('parent_a'),
@@ -283,6 +350,9 @@ def driver(a):
         name, path = item.split('=', 1)
         tb = kernel_table(path)
         result.setdefault('kernels', {})[name] = {k: tb.get(k) for k in ('k_comp_combined', 'k_comp_per_lane', 'k_comp_finish')}
+        for k in ('k_comp_combined_layers', 'k_comp_per_lane_layers', 'k_comp_column'):       # (a run with height layers)
+            if k in tb:
+                result['kernels'][name][k] = tb[k]
     line = json.dumps(result, indent=1, sort_keys=True)
     print(line)
     if a.out:
@@ -302,6 +372,8 @@ def main():
     ap.add_argument('--repeat', type=int, default=3, help='fresh processes per call')
     ap.add_argument('--calls', default=None, help='the calls of this session of the driver, comma-separated (default: all that apply)')
     ap.add_argument('--update', action='store_true', help='join the calls of this session to those --out already holds')
+    ap.add_argument('--layers', action='store_true', help='height layers and the column: lay_dev against lay_slabs, the controls b / parent_b; '
+                    'writes profiles/composite_layers_profile.json unless --out names another file')
     ap.add_argument('--bench', action='store_true', help="bench.py's result line too (of the parent tree as well)")
     ap.add_argument('--process-timeout', type=float, default=400.0)
     ap.add_argument('--parent-tree', default=None, help='a checkout of the parent commit with its library built')
