@@ -280,6 +280,9 @@ struct cpol_ctx {
     std::vector<uint64_t> st_seen;
     int last_poly_central = 0;         // the last sweep's one sub-beam took the coordinate polynomials (cpol_debug_read "poly_central")
     bool last_subsum = false;          // the 1-D table items of the last sweep never went through res[] (k_subbeam_sum)
+    bool last_vmask = false;           // the last sweep left vmask[] of every sub-beam gate (the general launch sequence)
+    bool last_vn = false;              // ... and vn[] of every valid item (Doppler scheme 1)
+    bool last_icefirst = false;        // ... and k_ice_first ran (a species whose fall-speed sums are totals over the ray)
     bool keep_debug = false;
     // host time of cpol_run_sweep by section (ns, summed; cpol_debug_read "host_times"): [0] calls, [1] per-ray tables
     // (staging memcpy + the H2D copy call), [2] work-buffer checks / allocations, [3] kernel launches, [4] the
@@ -4332,6 +4335,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ++ctx->sweep_serial;
     ctx->counters_dirty = false;
     ctx->last_n_keys = n_keys; ctx->last_subsum = f.subsum || f.final_inplace;
+    ctx->last_vmask = !f.gate1;
+    ctx->last_vn = ctx->last_vmask && p->simulate_doppler == 1;
+    ctx->last_icefirst = ctx->last_vn && f.any_vsrc2;
     ctx->counters.n_subbeam_gates = n_sbg;
     ctx->counters.n_gates = n_rg;
 
@@ -4897,6 +4903,33 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
             return CPOL_ERR_ARG;
         }
         src = ctx->b_res.p; bytes = (int64_t)n_hyd * n_sbg * CPOL_N_SZ * 8;
+    }
+    else if (!strcmp(name, "item_vmask")) {
+        // the validity bits of every sub-beam gate (bit j: hydrometeor j present)
+        if (!ctx->last_vmask) {
+            ctx->err = "cpol_debug_read: item_vmask is incomplete (the single-beam kernels write it only where a species' fall-speed sums "
+                       "are totals over the ray; debug reads or CPOL_GATE1=0 keep the general launch sequence)";
+            return CPOL_ERR_ARG;
+        }
+        src = ctx->b_vmask.p; bytes = n_sbg;
+    }
+    else if (!strcmp(name, "item_vn")) {
+        // the fall-speed moments {v, n} of every item (defined where the item's bit of item_vmask is set)
+        if (!ctx->last_vn) {
+            ctx->err = "cpol_debug_read: item_vn is incomplete (read back for every sub-beam gate only under Doppler scheme 1 in the general "
+                       "launch sequence: the single-beam kernels keep the moments in registers; debug reads or CPOL_GATE1=0 keep them)";
+            return CPOL_ERR_ARG;
+        }
+        src = ctx->b_vn.p; bytes = (int64_t)n_hyd * n_sbg * 2 * 8;
+    }
+    else if (!strcmp(name, "ice_first")) {
+        // one record {int32 first_gate, int32 pad, float64 v, float64 n} per (ray, sub-beam) (k_ice_first)
+        if (!ctx->last_icefirst) {
+            ctx->err = "cpol_debug_read: ice_first is not written (k_ice_first runs under Doppler scheme 1 in the general launch sequence "
+                       "when a species' fall-speed sums are totals over the ray: 1-moment ice, numeric integrate_V)";
+            return CPOL_ERR_ARG;
+        }
+        src = ctx->b_icefirst.p; bytes = (int64_t)ctx->last_n_rays * ctx->last_n_sub * (int64_t)sizeof(IceFirst);
     }
     else if (!strcmp(name, "item_rec")) { src = ctx->b_rec.p; bytes = (int64_t)n_hyd * n_sbg * 16; }
     else if (!strcmp(name, "item_par")) { src = ctx->b_par.p; bytes = (int64_t)n_hyd * CPOL_MAX_PAR * n_sbg * 8; }

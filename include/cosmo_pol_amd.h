@@ -1129,7 +1129,12 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * [n_hydro][n_sbg], "sz_integ" float32 [n_rays*n_gates][n_hydro][12],
  * "traj" float32 [n_rays][n_vnodes][3][n_gates], "item_res" float64
  * [n_hydro][n_sbg][12], "sub_wgate" float64 [n_sbg] (integration scheme 'ml': the per-gate
- * sub-beam weights).  Without the debug reads enabled: "launch_forms" int32 [12] -- which launch
+ * sub-beam weights); after a sweep in the general launch sequence (refused after the single-beam
+ * kernels, which do not write them for every gate) "item_vmask" uint8 [n_sbg] (bit j: hydrometeor j valid)
+ * and, under Doppler scheme 1, "item_vn" float64 [n_hydro][n_sbg][2] -- the fall-speed sums {v, n} of every
+ * item, defined where its bit of "item_vmask" is set -- and, when a species' sums are totals over the ray
+ * (1-moment ice, numeric integrate_V), "ice_first" [n_rays * n_sub] records {int32 first_gate (0x7fffffff: none), int32 pad,
+ * float64 v, float64 n}.  Without the debug reads enabled: "launch_forms" int32 [12] -- which launch
  * sequence the last cpol_run_sweep of this context took: [0] the CPOL_GATE1_RAY rule in force,
  * [1] k_gate1_ray ran, [2] the single-beam gate kernel, [3] k_interp_classify, [4] items off the
  * tables listed directly, [5] k_subbeam_sum, [6] table items evaluated in place, [7] the one

@@ -93,9 +93,9 @@ static int cmd_forms(int argc, char **argv)
                              "n_sub", "lanes_alive", "scan_form", "graph_replayed"};
     for (int q = 0; q < 12; ++q) printf("%s=%d\n", names[q], rec[q]);
     printf("by_species=%d\nfused_gate1=%d\nstencil=%d\ngraphable=%d\nsum_form=%d\nsum_team=%d\nfinal_512=%d\nlookup_launch=%d\n"
-           "psd_rare_one=%d\npsd_modes=%d\nmelt_qr=%d\nmelt_qs=%d\nmelt_qg=%d\nplain_interp=%d\n",
+           "psd_rare_one=%d\npsd_modes=%d\nmelt_qr=%d\nmelt_qs=%d\nmelt_qg=%d\nplain_interp=%d\nsum_chain=%d\nrvel_terms=%d\n",
            (int)f.by_species, (int)f.fused_gate1, (int)f.stencil, (int)f.graphable, f.sum_form, f.sum_team, (int)f.final_512, (int)f.lookup_launch,
-           (int)f.psd_rare_one, f.psd_modes, f.melt_qr, f.melt_qs, f.melt_qg, (int)f.plain_interp);
+           (int)f.psd_rare_one, f.psd_modes, f.melt_qr, f.melt_qs, f.melt_qg, (int)f.plain_interp, (int)f.sum_chain, (int)f.rvel_terms);
     return 0;
 }
 

@@ -203,3 +203,41 @@ def test_knob_defaults_clamps_and_string_matches(exe):
                              ({'CPOL_PSD_SIBLINGS': '1'}, 'p.psd_siblings', 1), ({'CPOL_FINAL_512': '0'}, 'p.final_512', 0),
                              ({'CPOL_LOOKUP_FILL': '24'}, 'p.lookup_fill', 24), ({'CPOL_GATE1_PRESENT': '0'}, 'p.gate1_present', 0)):
         assert _values(_run(exe, ['knobs'], env)) == dict(DEFAULTS, **{field: want}), env
+
+
+# ---- the launch plan of tests/test_gpu_rvel.py, stage (E): launch_forms() names neither the k_subbeam_sum form, k_gate1_species,
+# k_rvel_terms nor the width of k_final, so the GPU test asserts those runs only through their knobs.  Here the same calls -- shape,
+# species, entry point, knobs -- go through choose_forms on the host: each knob set must select the form the plan names for it.
+# The expectations are the enum of cpol_forms.h (SUM_GATHER 0, SUM_SMALL 1, SUM_LDS 2, SUM_SCALAR 3, SUM_TEAM 4) and the rules' own
+# statements (k_rvel_terms from 4 sub-beams on; 512 threads beyond 256 gates with at most 256 rays unless CPOL_FINAL_512=0).
+RVEL_SPECIES = {'rsg': 'R,S,G', 'rsgi': 'R,S,G,I', 'melt': 'R,S,G,mS,mG,I', '2mom': 'R,S,G,G,N'}
+RVEL_SUM = {'default': dict(sum_form=4, sum_team=4, sum_chain=1), 'gather': dict(sum_form=0, sum_team=0), 'lds': dict(sum_form=2, sum_team=0),
+            'scalar': dict(sum_form=3, sum_team=0), 'small': dict(sum_form=1, sum_team=0), 'team2': dict(sum_form=4, sum_team=2, sum_chain=1),
+            'team3_barrier': dict(sum_form=4, sum_team=3, sum_chain=0), 'team8': dict(sum_form=4, sum_team=8, sum_chain=1)}
+RVEL_SINGLE = {'species0': dict(by_species=0), 'species2': dict(by_species=1), 'ray0': dict(by_species=1, gate1_ray=0),
+               'ray1': dict(gate1_ray=1), 'ray2': dict(gate1_ray=1), 'gate1_0': dict(by_species=0)}
+
+
+def test_rvel_launch_plan_selects_the_forms_it_names(exe):
+    import _rvel
+    import test_gpu_rvel as T
+    assert len(T.FORM_PLAN) > 50 and set(T.SUM_FORMS) == set(RVEL_SUM) - {'default'}
+    seen = set()
+    for name, form, knobs, want in T.FORM_PLAN:
+        c = _rvel.BY_NAME[name]
+        call = dict(n_rays=c.n_rays, n_gates=c.n_gates, n_sub=c.n_sub, n_h=c.n_sub, doppler=1, debug=0, ml=int(c.wgate),
+                    with_melting=int(c.melt), entry='columns_melt' if c.melt else 'columns', species=RVEL_SPECIES[c.sset])
+        got = _forms(exe, env={k: str(v) for k, v in knobs}, **call)
+        expect = dict(want, rvel_terms=int(c.n_sub >= 4), final_512=int(c.n_gates > 256 and c.n_rays <= 256))
+        if want.get('subbeam_sum'):
+            expect.update(RVEL_SUM[form])
+        if c.n_sub == 1 and c.sset == 'rsg':
+            expect.update(RVEL_SINGLE.get(form, dict(by_species=1)))
+        assert {k: got[k] for k in expect} == expect, (name, form, got)
+        seen |= {(k, v) for k, v in expect.items()}
+        # k_final at 256 threads, as the child of test_final_512_gives_the_same_bits runs it
+        assert _forms(exe, env=dict({k: str(v) for k, v in knobs}, CPOL_FINAL_512='0'), **call)['final_512'] == 0
+    for k in ('sum_form', 'sum_team'):
+        assert {v for kk, v in seen if kk == k} >= {0, 2, 3, 4} if k == 'sum_team' else {v for kk, v in seen if kk == k} == {0, 1, 2, 3, 4}
+    for k in ('by_species', 'gate1_ray', 'rvel_terms', 'final_512', 'sum_chain', 'final_inplace', 'gate1', 'subbeam_sum'):
+        assert {v for kk, v in seen if kk == k} == {0, 1}, k
