@@ -169,12 +169,30 @@ class Composite(C.Structure):
                 ('column', C.c_void_p * len(COMPOSITE_FIELDS)), ('column_layers', C.c_void_p * len(COMPOSITE_FIELDS))]
 
 
+OBJ_WORDS = 10                                      # CPOL_OBJ_WORDS: the uint32 words of a row of cpol_objects.table
+
+
+class Objects(C.Structure):
+    """cpol_objects: the object cells of the binary maps of a cpol_fractions (cosmo_pol_amd/objects.py states the rule)."""
+    _fields_ = [('connectivity', C.c_int32), ('min_area', C.c_int32), ('max_objects', C.c_int32), ('pad_', C.c_int32),
+                ('n_objects', C.c_void_p), ('table', C.c_void_p), ('labels', C.c_void_p)]
+
+
 class Fractions(C.Structure):
     """cpol_fractions: the fractions skill score's sums of one finished plane of a composite against an observed map
-    (cosmo_pol_amd/neighbourhood.py states the rule)."""
+    (cosmo_pol_amd/neighbourhood.py states the rule).  objects: NULL (a zero-initialised struct) = no object cells."""
     _fields_ = [('field', C.c_int32), ('plane', C.c_int32), ('n_thresholds', C.c_int32), ('n_radii', C.c_int32),
                 ('thresholds', C.c_double * 4), ('radii', C.c_int32 * 8), ('observed', C.c_void_p), ('domain', C.c_void_p),
-                ('sums', C.c_void_p), ('totals', C.c_void_p)]
+                ('sums', C.c_void_p), ('totals', C.c_void_p), ('objects', C.POINTER(Objects))]
+
+
+class _ObjectsNamed(object):
+    """What objects.result reads of a spec, for the test hook: the cells' terms and the thresholds as the library rounds them."""
+
+    def __init__(self, objects, spec):
+        self.connectivity, self.min_area = objects.connectivity, objects.min_area
+        with np.errstate(over='ignore'):
+            self.thresholds = np.array(spec.thresholds_given, dtype=np.float64).astype(np.float32)
 
 
 class Outputs(C.Structure):
@@ -563,7 +581,7 @@ class PinnedPool(object):
         self._free_returned()
 
 
-_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint8: 1, np.uint16: 2, np.uint64: 8}
+_ITEMSIZE = {np.float32: 4, np.float64: 8, np.int8: 1, np.uint8: 1, np.uint16: 2, np.uint64: 8, np.uint32: 4, np.int32: 4}
 
 
 def carve_block(pool, spec, writer=None):
@@ -1201,12 +1219,23 @@ class Context(object):
             f.radii[j] = int(r)
         return f, []
 
-    def fractions_maps(self, maps, observed, spec, domain=None, tamper=None):
+    @staticmethod
+    def objects_struct(spec, fractions):
+        """(Objects for a call under `spec` (an objects.Objects), hung on `fractions` (the call's Fractions); what must stay alive):
+        the output pointers are the caller's."""
+        o = Objects()
+        o.connectivity, o.min_area, o.max_objects = spec.connectivity, spec.min_area, spec.max_objects
+        fractions.objects = C.pointer(o)
+        return o, [o]
+
+    def fractions_maps(self, maps, observed, spec, domain=None, tamper=None, objects=None):
         """Test hook (cpol_debug_read "fractions_maps"): the checks and k_frac_rows, k_frac_cols, k_frac_score on caller-supplied
         maps -> what neighbourhood.sums returns for them.  maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]); observed: float32
         [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
         and `radii` (the maps need not be those of spec.composite's grid).  `tamper(f)`: changes the cpol_fractions before the call
-        (the refusal tests)."""
+        (the refusal tests).  `objects`: an objects.Objects or any object with `connectivity`, `min_area`, `max_objects` and
+        `labels`: the kernels of cpol_obj.inl run too, and the result is (the sums, what objects.cells returns for the maps);
+        `tamper` then finds the cpol_objects at f.objects.contents."""
         from . import neighbourhood as NB
 
         class Hook(C.Structure):
@@ -1239,12 +1268,25 @@ class Context(object):
         s = np.full((m.shape[0], nt, nr, 3), 0xDEADBEEF, dtype=np.uint64)
         t = np.full((m.shape[0], nt, 3), 0xDEADBEEF, dtype=np.uint64)
         f.sums, f.totals = s.ctypes.data, t.ctypes.data
+        if objects is not None:
+            from . import objects as OB
+            o, okeep = Context.objects_struct(objects, f)
+            n_obj = np.full((m.shape[0] + 1, nt), 0xDEADBEEF, dtype=np.uint32)
+            table = np.full((m.shape[0] + 1, nt, objects.max_objects, OBJ_WORDS), 0xDEADBEEF, dtype=np.uint32)
+            o.n_objects, o.table = n_obj.ctypes.data, table.ctypes.data
+            labels = None
+            if objects.labels:
+                labels = np.full((m.shape[0] + 1, nt) + m.shape[1:], -559038737, dtype=np.int32)
+                o.labels = labels.ctypes.data
+            keep += okeep
         hk.f = f
         if tamper is not None:
             keep.append(tamper(hk.f))
         rc = int(self.lib.cpol_debug_read(self.h, b'fractions_maps', C.byref(hk), C.sizeof(hk)))
         self._check(rc, 'cpol_debug_read(fractions_maps)')
         del keep
+        if objects is not None:
+            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec), n_obj, table, labels)
         return NB.result(spec, s, t)
 
     @staticmethod

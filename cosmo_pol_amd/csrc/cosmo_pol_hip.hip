@@ -30,6 +30,7 @@
 #include "cpol_hist.h"
 #include "cpol_comp.h"
 #include "cpol_frac.h"
+#include "cpol_obj.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -42,6 +43,7 @@
 #include "cpol_hist.inl"
 #include "cpol_comp.inl"
 #include "cpol_frac.inl"
+#include "cpol_obj.inl"
 #include "cpol_shadow.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
@@ -216,8 +218,12 @@ struct cpol_ctx {
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand
-    DevBuf b_fsat, b_fobs, b_fout[2], b_fmaps;
+    DevBuf b_fsat, b_fobs, b_fout[5], b_fmaps;
     FracPlan fplan;
+    // object cells (cpol_objects, beside a cpol_fractions): the labelling scratch and the plan of the call at hand; n_objects, table
+    // and labels are b_fout[2 ... 4]
+    DevBuf b_oscr;
+    ObjPlan oplan;
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
     struct MemberPass {
         bool open = false;
@@ -818,7 +824,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fout[2], &ctx->b_fout[3], &ctx->b_fout[4], &ctx->b_oscr, &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -2881,21 +2887,57 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
 
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
 // (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
-enum { FR_SUMS, FR_TOTALS, FR_N };
+enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_N };
 // arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
-// composite's `count`
-static void frac_place(const cpol_fractions *f, const FracPlan &pl, PlaceArray *arr)
+// composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for)
+static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, PlaceArray *arr)
 {
-    arr[FR_SUMS] = arr[FR_TOTALS] = PlaceArray{};
+    for (int k = 0; k < FR_N; ++k) { arr[k] = PlaceArray{}; arr[k].product = PLACE_SWEEP; }
     arr[FR_SUMS].user = (uintptr_t)f->sums;     arr[FR_SUMS].bytes = pl.sums_bytes;
     arr[FR_TOTALS].user = (uintptr_t)f->totals; arr[FR_TOTALS].bytes = pl.totals_bytes;
-    for (int k = 0; k < FR_N; ++k) { arr[k].produced = true; arr[k].product = PLACE_SWEEP; }
+    arr[FR_SUMS].produced = arr[FR_TOTALS].produced = true;
+    if (!op.on) return;
+    const cpol_objects *const o = f->objects;
+    arr[FR_OBJ_N].user = (uintptr_t)o->n_objects;    arr[FR_OBJ_N].bytes = op.n_bytes;           arr[FR_OBJ_N].produced = true;
+    arr[FR_OBJ_TABLE].user = (uintptr_t)o->table;    arr[FR_OBJ_TABLE].bytes = op.table_bytes;   arr[FR_OBJ_TABLE].produced = true;
+    arr[FR_OBJ_LABELS].user = (uintptr_t)o->labels;  arr[FR_OBJ_LABELS].bytes = op.labels_bytes; arr[FR_OBJ_LABELS].produced = op.labels;
+}
+
+// the kernels of cpol_obj.inl behind k_frac_score on `st`; fa: the maps as frac_launch resolved them
+static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, const ObjPlan &op, void *const T[FR_N], hipStream_t st)
+{
+    ENSURE(ctx->b_oscr, (size_t)op.scratch_bytes);
+    ObjArgs a{};
+    a.f = fa;
+    a.L = (unsigned *)ctx->b_oscr.p; a.aux = a.L + op.n_maps * op.cells; a.rowcnt = a.aux + op.n_maps * op.cells;
+    a.n_objects = (unsigned *)T[FR_OBJ_N]; a.table = (unsigned *)T[FR_OBJ_TABLE]; a.labels = op.labels ? (int *)T[FR_OBJ_LABELS] : nullptr;
+    a.n_maps = op.n_maps;
+    a.connectivity = op.connectivity; a.min_area = op.min_area; a.max_objects = op.max_objects;
+    HIPCHK(hipMemsetAsync(T[FR_OBJ_TABLE], 0, op.table_bytes, st));
+    const dim3 rows((unsigned)op.grid_rows), thr(OBJ_THREADS);
+    hipLaunchKernelGGL(k_obj_runs, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_merge, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_flatten, dim3((unsigned)op.grid_cells), thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_area, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_count, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_number, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_attr, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_decode, dim3((unsigned)op.grid_decode), thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
 }
 
 // plane: block 0's plane on the device; obs_on_host: `observed` and `domain` are host arrays (copied to b_fobs on `st` first),
 // else memory the device reads in place; T: where `sums` and `totals` go
-static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &pl, const float *plane, long plane_stride, bool obs_on_host,
-                       void *const T[FR_N], hipStream_t st)
+static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, const float *plane, long plane_stride,
+                       bool obs_on_host, void *const T[FR_N], hipStream_t st)
 {
     ENSURE(ctx->b_fsat, (size_t)pl.scratch_bytes);
     FracArgs a{};
@@ -2927,6 +2969,7 @@ static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &p
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_frac_score, dim3((unsigned)pl.grid_score), dim3(FRAC_THREADS), 0, st, a);
     HIPCHK(hipGetLastError());
+    if (op.on) return obj_launch(ctx, a, pl, op, T, st);
     return CPOL_OK;
 }
 
@@ -2945,17 +2988,20 @@ static int frac_hook(cpol_ctx *ctx, const FracHook *hk)
     FracPlan pl;
     const char *why = frac_check_maps(&hk->f, hk->n_x, hk->n_y, hk->n_blocks, &pl);
     if (why) { ctx->err = std::string("cpol_fractions: ") + why; return CPOL_ERR_ARG; }
+    ObjPlan op;
+    if ((why = obj_check(hk->f.objects, pl, &op)) != nullptr) { ctx->err = std::string("cpol_objects: ") + why; return CPOL_ERR_ARG; }
     HIPCHK(hipSetDevice(ctx->device));
     int rc;
     if ((rc = upload(ctx, ctx->b_fmaps, hk->maps, (size_t)pl.n_blocks * pl.cells * sizeof(float))) != CPOL_OK) return rc;
     PlaceArray arr[FR_N];
-    frac_place(&hk->f, pl, arr);
+    frac_place(&hk->f, pl, op, arr);
     PlacePlan plan;
     place_outputs(arr, FR_N, 0, false, &plan);
-    DevBuf *own[FR_N] = {&ctx->b_fout[0], &ctx->b_fout[1]};
+    DevBuf *own[FR_N];
+    for (int k = 0; k < FR_N; ++k) own[k] = &ctx->b_fout[k];
     void *T[FR_N];
     if ((rc = place_resolve(ctx, arr, FR_N, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = frac_launch(ctx, &hk->f, pl, (const float *)ctx->b_fmaps.p, pl.cells, true, T, ctx->stream)) != CPOL_OK) return rc;
+    if ((rc = frac_launch(ctx, &hk->f, pl, op, (const float *)ctx->b_fmaps.p, pl.cells, true, T, ctx->stream)) != CPOL_OK) return rc;
     if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return CPOL_OK;
@@ -3128,10 +3174,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // neighbourhood verification (cpol_fractions): likewise, against the composite's plan, which passed
     const cpol_fractions *const fr = out->fractions;
     FracPlan &fr_pl = ctx->fplan;
+    ObjPlan &ob_pl = ctx->oplan;
     if (fr) {
-        const char *const why = frac_check(fr, cp, cp ? &cp_pl : nullptr, &fr_pl);
+        const char *why = frac_check(fr, cp, cp ? &cp_pl : nullptr, &fr_pl);
         if (why) { ctx->err = std::string("cpol_fractions: ") + why; return CPOL_ERR_ARG; }
-        frac_place(fr, fr_pl, arr + A_FR);
+        // object cells (cpol_objects): likewise, against the fractions' plan, which passed
+        if ((why = obj_check(fr->objects, fr_pl, &ob_pl)) != nullptr) { ctx->err = std::string("cpol_objects: ") + why; return CPOL_ERR_ARG; }
+        frac_place(fr, fr_pl, ob_pl, arr + A_FR);
     }
     int rc;
 
@@ -4312,7 +4361,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         const void *const cp_in[CPOL_COMP_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV]};
         if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, p->outputs_on_device != 1, st)) != CPOL_OK) return rc;
         // ---- neighbourhood verification: three kernels behind k_comp_finish, on the finished plane where the plan placed it ----
-        if (fr && (rc = frac_launch(ctx, fr, fr_pl, (const float *)T_all[A_CP + fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride,
+        if (fr && (rc = frac_launch(ctx, fr, fr_pl, ob_pl, (const float *)T_all[A_CP + fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride,
                                     p->outputs_on_device == 0, T_all + A_FR, st)) != CPOL_OK) return rc;
     }
     // ---- outputs that the kernels did not write in place ----

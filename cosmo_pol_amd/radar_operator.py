@@ -33,6 +33,7 @@ from . import superob as SO
 from . import histogram as HG
 from . import composite as CP
 from . import neighbourhood as NB
+from . import objects as OB
 from .lut import load_all_lut
 
 RADAR_FIELDS = ['ZH', 'ZDR', 'ZV', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V']
@@ -2504,7 +2505,9 @@ class RadarOperator(object):
     # (replaces in the reference: nothing -- its users grid the radials, threshold both maps and run box filters on the host)
     def _fss_product(self, spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block):
         """The product object of a composite call with scores; `observed` and `domain` checked (host arrays), or device pointers
-        under device_outputs['composite'] and `observed` None."""
+        under device_outputs['composite'] and `observed` None.  `spec`: a neighbourhood.Fractions, or an objects.Objects over
+        one: the scores with the object cells of the same binary maps (objects.Cells)."""
+        cells, spec = (spec, spec.fractions) if isinstance(spec, OB.Objects) else (None, spec)
         if not isinstance(spec, NB.Fractions):
             raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
         entry = (device_outputs or {}).get('composite', {})
@@ -2518,6 +2521,8 @@ class RadarOperator(object):
                 raise ValueError("with device_outputs the domain is a device pointer under device_outputs['composite']['domain']")
         if observed is not None:
             observed, domain = NB.check_maps(spec, observed, domain)
+        if cells is not None:
+            return OB.Cells(cells, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
         return NB.Scores(spec, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
 
     def simulate_rays_composite_fss(self, azimuths, elevations, spec, observed, domain=None, keep_gates=False, phase=3,
@@ -2529,6 +2534,10 @@ class RadarOperator(object):
         'forecast2' | 'observed2': uint64 [n_blocks, n_thr, n_radii], 'n_forecast' | 'n_observed' | 'n_domain': uint64
         [n_blocks, n_thr], 'thresholds', 'radii'} -- exactly neighbourhood.sums of the map the same call returns;
         neighbourhood.fss, bias and contingency make the scores of them.  A pass is scored only by the call that finishes it.
+        With an objects.Objects (over a Fractions) as `spec` it gains 'objects' too: the object cells of the same binary maps,
+        of every block and once of the observed map, exactly objects.cells of the map the same call returns ({'n_objects',
+        'first', 'area', 'sum_x', 'sum_y', 'bbox', 'peak', 'peak_cell', 'labels' when asked, 'observed': the same,
+        'connectivity', 'min_area', 'thresholds'}); device_outputs['composite'] may then carry 'n_objects', 'table' and 'labels'.
         The other keywords are those of simulate_rays_composite.  `device_outputs`: its entry 'composite' may carry 'observed',
         'domain', 'sums' and 'totals' as device pointers (`observed` stays None).  ValueError for an observed map or a domain of
         a wrong shape or dtype and for what the library refuses.  `radar` (the radars of a network under one operator differ in
@@ -2611,8 +2620,8 @@ class RadarOperator(object):
                                   az_stop=359, keep_gates=False):
         """get_network_composite with scores: `spec` is a neighbourhood.Fractions over the network's composite, `observed` and
         `domain` as for simulate_rays_composite_fss.  The pass is scored ONCE, at its end, against the observed network
-        composite: res['composite']['fractions']."""
-        if not isinstance(spec, NB.Fractions):
+        composite: res['composite']['fractions'] (and 'objects' with an objects.Objects)."""
+        if not isinstance(spec, (NB.Fractions, OB.Objects)):
             raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
         sweeps, per_radar = self._network_sweeps(radars, spec.composite, elevations, azimuths, az_step, az_start, az_stop)
         return self._network_pass(sweeps, per_radar, lambda az, el, phase, lane, radar, source: self.simulate_rays_composite_fss(

@@ -705,6 +705,50 @@ typedef struct cpol_composite {
 #define CPOL_FRAC_MAX_THRESHOLDS 4
 #define CPOL_FRAC_MAX_RADII 8
 #define CPOL_FRAC_MAX_RADIUS 1023
+
+/* Object cells: the connected components of the binary maps of a cpol_fractions, numbered, with ten integer attributes each, for
+ * the user who verifies OBJECTS (SAL, MODE, CRA and every cell tracker start here).  Replaces in the reference: nothing (its users
+ * pull every map to the host and label it there).  Pointed to by cpol_fractions.objects: the cells ride on a scored finishing call
+ * (a caller who wants cells alone asks for one radius, 0).  cosmo_pol_amd/objects.py states the same rule in NumPy (`cells`).
+ * INPUT: the binary maps of cpol_fractions, unchanged: domain && m == m && m >= thr, float32 comparisons, thresholds rounded once.
+ * SOURCES: one map per source s and threshold t; sources 0 ... n_blocks - 1 are the blocks of the scored plane, source n_blocks is
+ * the observed map, labelled once per call.
+ * OBJECT: a maximal set of set cells connected through `connectivity` neighbours: 4 (edges) or 8 (edges and corners).
+ * FIRST CELL: the cell of an object with the smallest flat index iy * n_x + ix.
+ * FILTER: objects with fewer than `min_area` cells are dropped.
+ * NUMBERING: the kept objects are numbered 1 ... n in ascending order of their first cell (with min_area = 1 the numbering of
+ * scipy.ndimage.label).
+ * ATTRIBUTES, CPOL_OBJ_WORDS = 10 uint32 words per kept object, in this order: first (the flat index of the first cell); area;
+ * sum of ix; sum of iy; the inclusive bounding box x0, x1, y0, y1; peak_cell (the flat index of the peak); the float32 bits of
+ * the peak value.  The PEAK is the largest value m (o for the observed map) of the object's cells in the TOTAL order of the
+ * float32 values, in which -0.0 lies before +0.0 (the order of the ensemble quantiles): among -0.0 and +0.0 the peak is +0.0
+ * wherever it lies; among cells of equal bits the one with the smallest flat index.  (NaN cells are never set.)
+ * NO OVERFLOW (a condition, not a measurement): at most 1023 x 1023 cells, so an area is < 2^20, a sum of ix or iy is
+ * < 2^20 * 2^10 = 2^30, every index < 2^20: all fit uint32.  Every attribute is a count, an integer sum, an integer extreme or a
+ * comparison: the result does not depend on the order in which the hardware works.  Float sums over an object's cells (rain
+ * volume, weighted centroids) are not built; the label map is delivered so that the host can form them.
+ * OUTPUTS: n_objects uint32 [n_blocks + 1][n_thresholds]: the TRUE number of kept objects, also beyond max_objects; table uint32
+ * [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS], 8-byte aligned: row k - 1 belongs to object k, rows at or beyond
+ * n_objects are zero, objects beyond max_objects have no row; labels int32 [n_blocks + 1][n_thresholds][n_y][n_x] or NULL: the
+ * object's number, 0 for background and dropped objects, complete even when the table overflows.  The three follow
+ * p->outputs_on_device like `sums`.
+ * LIMITS: the labelling scratch, (n_blocks + 1) * n_thresholds * (2 * n_y * n_x + n_y) * 4 bytes, at most 1 GiB.
+ * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: connectivity other than 4 or 8; min_area < 1;
+ * max_objects outside 1 ... 65535; NULL n_objects or table; a table that is not 8-byte aligned; the limit exceeded.
+ * Kernels (k_obj_*, cpol_obj.inl) run behind k_frac_score: a label-equivalence union-find (L[i] <= i always, a union is an
+ * atomic minimum).  No kernel waits on another workgroup; every loop carries a strictly decreasing unsigned integer. */
+#define CPOL_OBJ_WORDS 10
+#define CPOL_OBJ_MAX_OBJECTS 65535
+typedef struct cpol_objects {
+    int32_t  connectivity;      /* 4 or 8                                                                          */
+    int32_t  min_area;          /* >= 1                                                                            */
+    int32_t  max_objects;       /* 1 ... 65535 table rows per (source, threshold)                                  */
+    int32_t  pad_;
+    uint32_t *n_objects;        /* [n_blocks + 1][n_thresholds]                                                    */
+    uint32_t *table;            /* [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS]                       */
+    int32_t  *labels;           /* [n_blocks + 1][n_thresholds][n_y][n_x] or NULL = not wanted                     */
+} cpol_objects;
+
 typedef struct cpol_fractions {
     int32_t  field;             /* the field whose plane is scored: one of composite->fields                        */
     int32_t  plane;             /* index into that field's plane order                                             */
@@ -716,6 +760,7 @@ typedef struct cpol_fractions {
     const uint8_t *domain;      /* [n_y][n_x] or NULL = every cell                                                 */
     uint64_t *sums;             /* [n_blocks][n_thresholds][n_radii][3]                                            */
     uint64_t *totals;           /* [n_blocks][n_thresholds][3]                                                     */
+    cpol_objects *objects;      /* NULL (a zero-initialised struct): off.  The object cells of the same binary maps */
 } cpol_fractions;
 
 /* Terrain shadowing (cpol_sweep_params.terrain_shadow, cpol_outputs.visibility; cosmo_pol_amd/shadow.py states the same rule in
@@ -1199,7 +1244,8 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * caller-supplied maps.  dst points to { int32_t n_blocks, n_y, n_x, pad; const float *maps; cpol_fractions f; } -- host arrays:
  * maps [n_blocks][n_y][n_x] float32 (what a finished plane would hold; f.field and f.plane are not read), f.observed, f.domain
  * (or NULL), f.sums and f.totals; 1 <= n_x, n_y <= 1023; blocking; needs no staged model, tables or composite pass;
- * cpol_fractions' refusals, and CPOL_ERR_ARG for a bad shape or NULL maps.  Returns 0.
+ * cpol_fractions' refusals, and CPOL_ERR_ARG for a bad shape or NULL maps.  Returns 0.  With f.objects (host arrays n_objects,
+ * table and labels or NULL) the call runs cpol_objects' checks and the kernels of cpol_obj.inl on the same maps too.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
