@@ -31,6 +31,7 @@
 #include "cpol_comp.h"
 #include "cpol_frac.h"
 #include "cpol_obj.h"
+#include "cpol_products.h"
 #include "cpol_interp.inl"
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
@@ -1942,6 +1943,37 @@ static int place_copy_out(cpol_ctx *ctx, const PlaceArray *arr, const PlacePlan 
     return CPOL_OK;
 }
 
+// The head the product hooks share: the caller's per-gate fields, n values each, into the sweep's own output buffers, where the
+// launch sequence leaves them -- the slots of `mask` that are given; slot 9 (RVEL) float64 into b_rvel, the rest float32 into b_out[k]
+static int hook_upload_fields(cpol_ctx *ctx, const void *const *src, int n_slots, unsigned mask, size_t n, const void **in)
+{
+    int rc;
+    for (int k = 0; k < n_slots; ++k) {
+        if (!((mask >> k) & 1u) || !src[k]) continue;
+        DevBuf &b = k == 9 ? ctx->b_rvel : ctx->b_out[k];
+        if ((rc = upload(ctx, b, src[k], n * (k == 9 ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
+        in[k] = b.p;
+    }
+    return CPOL_OK;
+}
+
+// ... and their tail: the plan of blocking host arrays, its device pointers, the hook's launch(T), the copies, the wait
+extern "C++" {
+template <int N, class Launch>
+static int hook_finish(cpol_ctx *ctx, const PlaceArray (&arr)[N], DevBuf *const *own, Launch launch)
+{
+    PlacePlan plan;
+    place_outputs(arr, N, 0, false, &plan);
+    void *T[N];
+    int rc;
+    if ((rc = place_resolve(ctx, arr, N, plan, own, T)) != CPOL_OK) return rc;
+    if ((rc = launch(T)) != CPOL_OK) return rc;
+    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return CPOL_OK;
+}
+}
+
 // ---- superobservations (cpol_superob, cpol_superob.inl): the checks and the launch, shared by the launch sequence and the test hook ----
 enum { SO_RVEL = CPOL_SUPEROB_RVEL, SO_COUNT = CPOL_SUPEROB_FIELDS, SO_N };
 struct SuperobPlan {
@@ -2025,23 +2057,9 @@ static int superob_hook(cpol_ctx *ctx, const SuperobHook *h)
         if (need && !h->in[k]) { ctx->err = "superob_fields: a requested field has no input"; return CPOL_ERR_ARG; }
     }
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)h->n_rows * h->n_gates;
     const void *in[CPOL_SUPEROB_FIELDS] = {};
-    const int own[CPOL_SUPEROB_FIELDS] = {0, 1, -1, 3, 4, 5, 6, 7, 8, -1};     // (the sweeps' own output buffers hold the inputs)
-    for (int k = 0; k < CPOL_SUPEROB_FIELDS; ++k) {
-        if (!h->in[k] || k == CPOL_SUPEROB_ZDR) continue;
-        DevBuf &b = k == SO_RVEL ? ctx->b_rvel : ctx->b_out[own[k]];
-        if ((rc = upload(ctx, b, h->in[k], n * (k == SO_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
-        in[k] = b.p;
-    }
-    PlacePlan plan;
-    place_outputs(arr, SO_N, 0, false, &plan);
-    void *T[SO_N];
-    if ((rc = place_resolve(ctx, arr, SO_N, plan, nullptr, T)) != CPOL_OK) return rc;
-    if ((rc = superob_launch(ctx, &h->so, pl, in, T, h->n_gates, false, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    if ((rc = hook_upload_fields(ctx, h->in, CPOL_SUPEROB_FIELDS, ~(1u << CPOL_SUPEROB_ZDR), (size_t)h->n_rows * h->n_gates, in)) != CPOL_OK) return rc;
+    return hook_finish(ctx, arr, nullptr, [&](void *const *T) { return superob_launch(ctx, &h->so, pl, in, T, h->n_gates, false, ctx->stream); });
 }
 
 // ---- ensemble statistics (cpol_member_stats, cpol_member_stats.inl): the checks, the pass and the launches, shared by the
@@ -2334,20 +2352,8 @@ static int member_stats_hook(cpol_ctx *ctx, const MemberStatsHook *h, const cpol
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)h->n_members * (size_t)h->n_cells;
     const void *in[CPOL_MS_FIELDS] = {};
-    for (int k = 0; k < CPOL_MS_FIELDS && n > 0; ++k) {     // (the sweeps' own output buffers hold the inputs)
-        if (!((h->ms.fields >> k) & 1u)) continue;
-        DevBuf &b = k == CPOL_MS_RVEL ? ctx->b_rvel : ctx->b_out[k];
-        if ((rc = upload(ctx, b, h->in[k], n * (k == CPOL_MS_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
-        in[k] = b.p;
-    }
-    PlacePlan plan;
-    place_outputs(arr, MS_N, 0, false, &plan);
-    void *T[MS_N];
-    if ((rc = place_resolve(ctx, arr, MS_N, plan, nullptr, T)) != CPOL_OK) return rc;
-    if ((rc = member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream, mv, true)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    if ((rc = hook_upload_fields(ctx, h->in, CPOL_MS_FIELDS, n > 0 ? h->ms.fields : 0u, n, in)) != CPOL_OK) return rc;
+    return hook_finish(ctx, arr, nullptr, [&](void *const *T) { return member_stats_launch(ctx, &h->ms, pl, in, T, false, ctx->stream, mv, true); });
 }
 
 // ---- spectrum moments (cpol_spectrum_moments, k_spec_moments in cpol_spectrum.inl): the checks and the launch, shared by the
@@ -2414,16 +2420,10 @@ static int spec_moments_hook(cpol_ctx *ctx, const SpecMomentsHook *h)
     HIPCHK(hipSetDevice(ctx->device));
     if ((rc = upload(ctx, ctx->b_spectrum, h->spectrum, (size_t)h->n_rows * h->n_v * sizeof(double))) != CPOL_OK) return rc;
     if ((rc = upload(ctx, ctx->b_smvar, h->varray, (size_t)h->n_v * sizeof(double))) != CPOL_OK) return rc;
-    PlacePlan plan;
-    place_outputs(arr, SM_N, 0, false, &plan);
     DevBuf *const own[SM_N] = {&ctx->b_smom, &ctx->b_smcount};
-    void *T[SM_N];
-    if ((rc = place_resolve(ctx, arr, SM_N, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = spec_moments_launch(ctx, &h->sm, (const double *)ctx->b_spectrum.p, (const double *)ctx->b_smvar.p, T, h->n_rows, h->n_v,
-                                  false, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    return hook_finish(ctx, arr, own, [&](void *const *T) {
+        return spec_moments_launch(ctx, &h->sm, (const double *)ctx->b_spectrum.p, (const double *)ctx->b_smvar.p, T, h->n_rows, h->n_v, false, ctx->stream);
+    });
 }
 
 // ---- sweep histograms (cpol_histogram, k_hist in cpol_hist.inl): the checks (cpol_hist.h), the pass and the launches, shared by
@@ -2564,12 +2564,7 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)hk->n_rows * hk->n_gates, n_geo = (size_t)hk->n_rays * hk->n_gates;
     const void *in[CPOL_HIST_FIELDS] = {};
-    for (int k = 0; k < CPOL_HIST_FIELDS; ++k) {          // (the sweeps' own output buffers hold the inputs)
-        if (!hk->in[k]) continue;
-        DevBuf &b = k == HIST_RVEL ? ctx->b_rvel : ctx->b_out[k];
-        if ((rc = upload(ctx, b, hk->in[k], n * (k == HIST_RVEL ? sizeof(double) : sizeof(float)))) != CPOL_OK) return rc;
-        in[k] = b.p;
-    }
+    if ((rc = hook_upload_fields(ctx, hk->in, CPOL_HIST_FIELDS, ~0u, n, in)) != CPOL_OK) return rc;
     const void *y = nullptr;
     long y_gates = (long)n;
     if (ord == HIST_ORD_HEIGHTS || ord == HIST_ORD_DIST) {
@@ -2581,16 +2576,9 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
         if ((rc = upload(ctx, ctx->b_model, hk->model_vars, (size_t)hk->n_model_vars * n * sizeof(double))) != CPOL_OK) return rc;
         y = (const double *)ctx->b_model.p + (size_t)(ord - HIST_ORD_MODEL) * n;
     }
-    PlacePlan plan;
-    place_outputs(arr, CPOL_HIST_FIELDS, 0, false, &plan);
     DevBuf *own[CPOL_HIST_FIELDS];
     for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[k] = &ctx->b_hcounts[k];
-    void *T[CPOL_HIST_FIELDS];
-    if ((rc = place_resolve(ctx, arr, CPOL_HIST_FIELDS, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = hist_launch(ctx, &hk->h, pl, in, y, y_gates, (long)n, hk->n_gates, T, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    return hook_finish(ctx, arr, own, [&](void *const *T) { return hist_launch(ctx, &hk->h, pl, in, y, y_gates, (long)n, hk->n_gates, T, ctx->stream); });
 }
 
 // ---- gridded composites (cpol_composite, k_comp and k_comp_finish in cpol_comp.inl): the checks (cpol_comp.h), the pass and the
@@ -2865,24 +2853,15 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)hk->n_rows * hk->n_gates, n_geo = (size_t)hk->n_rays * hk->n_gates;
     const void *in[CPOL_COMP_FIELDS] = {};
-    for (int k = 0; k < CPOL_COMP_FIELDS; ++k) {          // (the sweeps' own output buffers hold the inputs)
-        if (!hk->in[k]) continue;
-        if ((rc = upload(ctx, ctx->b_out[k], hk->in[k], n * sizeof(float))) != CPOL_OK) return rc;
-        in[k] = ctx->b_out[k].p;
-    }
+    if ((rc = hook_upload_fields(ctx, (const void *const *)hk->in, CPOL_COMP_FIELDS, ~0u, n, in)) != CPOL_OK) return rc;
     if (hk->dist && (rc = upload(ctx, ctx->b_out[12], hk->dist, n_geo * sizeof(float))) != CPOL_OK) return rc;
     if ((rc = upload(ctx, ctx->b_out[13], hk->heights, n_geo * sizeof(float))) != CPOL_OK) return rc;
-    PlacePlan plan;
-    place_outputs(arr, CP_N, 0, false, &plan);
     DevBuf *own[CP_N];
     for (int k = 0; k < CP_N; ++k) own[k] = &ctx->b_cout[k];
-    void *T[CP_N];
-    if ((rc = place_resolve(ctx, arr, CP_N, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = comp_launch(ctx, &hk->c, pl, in, hk->dist ? ctx->b_out[12].p : nullptr, ctx->b_out[13].p, hk->n_rays, (long)n, hk->n_gates, T,
-                          hk->lane_form, true, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    return hook_finish(ctx, arr, own, [&](void *const *T) {
+        return comp_launch(ctx, &hk->c, pl, in, hk->dist ? ctx->b_out[12].p : nullptr, ctx->b_out[13].p, hk->n_rays, (long)n, hk->n_gates, T,
+                           hk->lane_form, true, ctx->stream);
+    });
 }
 
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
@@ -2995,16 +2974,9 @@ static int frac_hook(cpol_ctx *ctx, const FracHook *hk)
     if ((rc = upload(ctx, ctx->b_fmaps, hk->maps, (size_t)pl.n_blocks * pl.cells * sizeof(float))) != CPOL_OK) return rc;
     PlaceArray arr[FR_N];
     frac_place(&hk->f, pl, op, arr);
-    PlacePlan plan;
-    place_outputs(arr, FR_N, 0, false, &plan);
     DevBuf *own[FR_N];
     for (int k = 0; k < FR_N; ++k) own[k] = &ctx->b_fout[k];
-    void *T[FR_N];
-    if ((rc = place_resolve(ctx, arr, FR_N, plan, own, T)) != CPOL_OK) return rc;
-    if ((rc = frac_launch(ctx, &hk->f, pl, op, (const float *)ctx->b_fmaps.p, pl.cells, true, T, ctx->stream)) != CPOL_OK) return rc;
-    if ((rc = place_copy_out(ctx, arr, plan, T, false)) != CPOL_OK) return rc;
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return CPOL_OK;
+    return hook_finish(ctx, arr, own, [&](void *const *T) { return frac_launch(ctx, &hk->f, pl, op, (const float *)ctx->b_fmaps.p, pl.cells, true, T, ctx->stream); });
 }
 
 // The launch sequence of cpol_run_sweep, and its two halves:
@@ -3097,92 +3069,65 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             return CPOL_ERR_ARG;
         }
     }
-    // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, the superobservations', the statistics'
+    // every output array of the call, for the placement plan (cpol_place.h): the sweep's own, then those of the call's ONE product
+    // (cpol_products.h) in the one slot range behind them, the fractions' behind the composite's
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
-           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_SO = O_N, A_MS = A_SO + SO_N, A_SM = A_MS + MS_N, A_N = A_SM + SM_N, A_HG = A_SO, A_CP = A_SO, A_FR = A_CP + CP_N };
+           O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_PR = O_N,
+           PR_MAX = std::max({(int)SO_N, (int)MS_N, (int)SM_N, (int)CPOL_HIST_FIELDS, (int)CP_N + (int)FR_N}), A_N = A_PR + PR_MAX };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
-    // (a histogram's counts take the slots of the superobservations: the two never share a call, and the list is full)
-    static_assert(CPOL_HIST_FIELDS <= SO_N, "the histogram's counts in the slots of the superobservations");
-    // (and so do a composite's nine `values` and its `count`: the three never share a call)
-    // (with the columns of its height layers they reach into the slots of the ensemble statistics, which share no call with them)
-    static_assert(CP_N <= SO_N + MS_N, "the composite's maps in the slots of the superobservations and the ensemble statistics");
-    // (the sums of a neighbourhood verification, which comes with a composite alone, take the slots behind the composite's)
-    static_assert(A_CP + CP_N + FR_N <= A_SM, "the fractions' sums in the slots of the ensemble statistics");
     PlaceArray arr[A_N];
-    // (a composite shares a call with no other product: refused before the other product's own checks speak)
-    if (out->composite && (out->superob || out->histogram || out->member_stats || out->spectrum_moments)) {
-        ctx->err = "cpol_composite: not together with superobservations, histograms, ensemble statistics or spectrum moments in one call";
-        return CPOL_ERR_ARG;
-    }
-    // (a histogram shares a call with no other product: refused before the other product's own checks speak)
-    if (out->histogram && (out->superob || out->member_stats || out->spectrum_moments)) {
-        ctx->err = "cpol_histogram: not together with superobservations, ensemble statistics or spectrum moments in one call";
-        return CPOL_ERR_ARG;
-    }
-    // superobservations (cpol_superob): every refusal here, before anything of the call is queued
+    DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array of the sweep keeps a grow-only buffer of its own
+    // the product and every refusal of it here, before anything of the call is queued
+    const CallProduct cq = call_product(cols ? CALL_COLUMNS : timed ? CALL_TIMED : mem ? CALL_MEMBERS : CALL_SWEEP, *out);
+    if (cq.refuse) { ctx->err = cq.refuse; return CPOL_ERR_ARG; }
     const cpol_superob *const so = out->superob;
-    SuperobPlan so_pl{};
-    if (so) {
-        if (cols || sub_out) { ctx->err = "cpol_superob: cpol_run_sweep and cpol_run_sweep_members take superobservations, no other entry point"; return CPOL_ERR_ARG; }
-        const int rc_so = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl, arr + A_SO);
-        if (rc_so != CPOL_OK) return rc_so;
-    }
-    // ensemble statistics (cpol_member_stats): likewise
     const cpol_member_stats *const ms = out->member_stats;
-    const cpol_member_verify *const mv = out->member_verify;        // (the verification of the pass: with member_stats only)
-    MemberStatsPlan ms_pl{};
-    if (mv && !ms) { ctx->err = "cpol_member_verify: needs ensemble statistics (outputs->member_stats) in the same call"; return CPOL_ERR_ARG; }
-    if (ms) {
-        if (cols || sub_out) { ctx->err = "cpol_member_stats: cpol_run_sweep and cpol_run_sweep_members take ensemble statistics, no other entry point"; return CPOL_ERR_ARG; }
-        if (so) { ctx->err = "cpol_member_stats: not together with superobservations (outputs->superob) in one call"; return CPOL_ERR_ARG; }
-        if (timed) { ctx->err = "cpol_member_stats: a time-blended call (tables->time_blend) folds no members"; return CPOL_ERR_ARG; }
-        const int rc_ms = member_stats_plan(ctx, ms, mv, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_MS);
-        if (rc_ms != CPOL_OK) return rc_ms;
-    }
-    // spectrum moments (cpol_spectrum_moments): likewise
+    const cpol_member_verify *const mv = out->member_verify;        // (the verification of the pass)
     const cpol_spectrum_moments *const sm = out->spectrum_moments;
-    if (sm) {
-        if (cols || sub_out || mem) { ctx->err = "cpol_spectrum_moments: cpol_run_sweep takes spectrum moments, no other entry point"; return CPOL_ERR_ARG; }
-        if (so || ms) { ctx->err = "cpol_spectrum_moments: not together with superobservations or ensemble statistics in one call"; return CPOL_ERR_ARG; }
-        const int rc_sm = spec_moments_plan(ctx, sm, n_rg, p->simulate_doppler == 3, arr + A_SM);
-        if (rc_sm != CPOL_OK) return rc_sm;
-    }
-    // sweep histograms (cpol_histogram): likewise
     const cpol_histogram *const hg = out->histogram;
+    const cpol_composite *const cp = out->composite;
+    const cpol_fractions *const fr = out->fractions;                // (the neighbourhood verification of the composite)
+    SuperobPlan so_pl{};
+    MemberStatsPlan ms_pl{};
     HistPlan hg_pl;
-    if (hg) {
-        if (cols || sub_out) { ctx->err = "cpol_histogram: cpol_run_sweep and cpol_run_sweep_members take histograms, no other entry point"; return CPOL_ERR_ARG; }
+    CompPlan &cp_pl = ctx->cplan;
+    FracPlan &fr_pl = ctx->fplan;
+    ObjPlan &ob_pl = ctx->oplan;
+    int rc = CPOL_OK;
+    switch (cq.product) {          // (the superobservations and the statistics are packed into their blocks; the others are arrays of the sweep)
+    case PRODUCT_SUPEROB: rc = superob_plan(ctx, so, n_rays, geo_rays, ng, p->simulate_doppler != 0, &so_pl, arr + A_PR); break;
+    case PRODUCT_MEMBER_STATS:
+        rc = member_stats_plan(ctx, ms, mv, (long)geo_rays * ng, n_rays / geo_rays, p->simulate_doppler != 0, &ms_pl, arr + A_PR);
+        break;
+    case PRODUCT_SPECTRUM_MOMENTS:
+        rc = spec_moments_plan(ctx, sm, n_rg, p->simulate_doppler == 3, arr + A_PR);
+        own[A_PR + SM_MOMENTS] = &ctx->b_smom; own[A_PR + SM_COUNT] = &ctx->b_smcount;
+        break;
+    case PRODUCT_HISTOGRAM: {
         HistCall hc;
         hc.n_rows = n_rays; hc.n_gates = ng; hc.doppler = p->simulate_doppler != 0;
         hc.n_model_vars = p->integrate_model ? n_vars : 0;
-        hc.other_product = so || ms || sm;
-        const int rc_hg = hist_plan(ctx, hg, hc, &hg_pl, arr + A_HG);
-        if (rc_hg != CPOL_OK) return rc_hg;
+        rc = hist_plan(ctx, hg, hc, &hg_pl, arr + A_PR);
+        for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_PR + k] = &ctx->b_hcounts[k];     // (a finishing call's counts)
+        break;
     }
-    // gridded composites (cpol_composite): likewise
-    const cpol_composite *const cp = out->composite;
-    CompPlan &cp_pl = ctx->cplan;
-    if (cp) {
-        if (cols || sub_out) { ctx->err = "cpol_composite: cpol_run_sweep and cpol_run_sweep_members take composites, no other entry point"; return CPOL_ERR_ARG; }
+    case PRODUCT_COMPOSITE: {
         CompCall cc;
         cc.n_rows = n_rays; cc.n_gates = ng;
         cc.spaceborne = t->site != nullptr || p->geometry_mode == CPOL_GEOM_SPACEBORNE;
-        cc.other_product = so || ms || sm || hg;
-        const int rc_cp = comp_plan(ctx, cp, cc, &cp_pl, arr + A_CP);
-        if (rc_cp != CPOL_OK) return rc_cp;
-    }
-    // neighbourhood verification (cpol_fractions): likewise, against the composite's plan, which passed
-    const cpol_fractions *const fr = out->fractions;
-    FracPlan &fr_pl = ctx->fplan;
-    ObjPlan &ob_pl = ctx->oplan;
-    if (fr) {
-        const char *why = frac_check(fr, cp, cp ? &cp_pl : nullptr, &fr_pl);
+        for (int k = 0; k < CP_N; ++k) own[A_PR + k] = &ctx->b_cout[k];                     // (a finishing call's maps, and their scores)
+        for (int k = 0; k < FR_N; ++k) own[A_PR + CP_N + k] = &ctx->b_fout[k];
+        if ((rc = comp_plan(ctx, cp, cc, &cp_pl, arr + A_PR)) != CPOL_OK || !fr) break;
+        // against the composite's plan, which passed; the object cells (cpol_objects) against the fractions' plan, which passed
+        const char *why = frac_check(fr, cp, &cp_pl, &fr_pl);
         if (why) { ctx->err = std::string("cpol_fractions: ") + why; return CPOL_ERR_ARG; }
-        // object cells (cpol_objects): likewise, against the fractions' plan, which passed
         if ((why = obj_check(fr->objects, fr_pl, &ob_pl)) != nullptr) { ctx->err = std::string("cpol_objects: ") + why; return CPOL_ERR_ARG; }
-        frac_place(fr, fr_pl, ob_pl, arr + A_FR);
+        frac_place(fr, fr_pl, ob_pl, arr + A_PR + CP_N);
+        break;
     }
-    int rc;
+    }
+    if (rc != CPOL_OK) return rc;
+    if (cq.refuse_after_plan) { ctx->err = cq.refuse_after_plan; return CPOL_ERR_ARG; }
 
     // ---- per-sweep host tables -> device (skipped when the caller's tag is unchanged) ----
     const int mode = p->geometry_mode;
@@ -3555,11 +3500,6 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
                                  out->DSPECTRUM, out->mask_sum8, out->visibility};
-    DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array keeps a grow-only buffer of its own
-    own[A_SM + SM_MOMENTS] = &ctx->b_smom; own[A_SM + SM_COUNT] = &ctx->b_smcount;     // (the spectrum moments are arrays of the sweep too)
-    if (hg) for (int k = 0; k < CPOL_HIST_FIELDS; ++k) own[A_HG + k] = &ctx->b_hcounts[k];      // (and a finishing call's counts)
-    if (cp) for (int k = 0; k < CP_N; ++k) own[A_CP + k] = &ctx->b_cout[k];                      // (and a finishing call's maps)
-    if (fr) for (int k = 0; k < FR_N; ++k) own[A_FR + k] = &ctx->b_fout[k];                      // (and their scores)
     for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
@@ -3584,7 +3524,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const bool window = plan.window;
     void *T_all[A_N];
     if ((rc = place_resolve(ctx, arr, A_N, plan, own, T_all)) != CPOL_OK) return rc;
-    void *const *const T = T_all, *const *const so_T = T_all + A_SO, *const *const ms_T = T_all + A_MS, *const *const sm_T = T_all + A_SM;
+    void *const *const T = T_all, *const *const pr_T = T_all + A_PR;
 
     // the bucket counters start at zero: cleared by k_interp_sweep (no fill kernel); the domain
     // error word is sticky (cleared when reported)
@@ -4326,44 +4266,35 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         ctx->err = "cpol_run_sweep: failure requested by the test hook (fail_next_sweep)";
         return CPOL_ERR_HIP;
     }
-    // ---- superobservations: ONE kernel behind the sequence (outside launch_all: the captured graph does not know it) ----
-    if (so) {
-        const void *const so_in[CPOL_SUPEROB_FIELDS] = {T[O_ZH], T[O_ZV], nullptr, T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
-                                                        T[O_ATTV], T[O_RVEL]};
-        if ((rc = superob_launch(ctx, so, so_pl, so_in, so_T, ng, window, st)) != CPOL_OK) return rc;
-    }
-    // ---- ensemble statistics: the call's member(s) folded into the context's running state behind the sequence, and the
-    // outputs of a finishing call (outside launch_all, like k_superob) ----
-    if (ms) {
-        const void *const ms_in[CPOL_MS_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
-                                                   T[O_ATTV], T[O_RVEL]};
-        if ((rc = member_stats_launch(ctx, ms, ms_pl, ms_in, ms_T, window, st, mv, p->outputs_on_device == 0)) != CPOL_OK) return rc;
-    }
-    // ---- spectrum moments: ONE kernel behind the sequence, on the spectrum wherever it was placed (outside launch_all too) ----
-    if (sm && (rc = spec_moments_launch(ctx, sm, (const double *)T[O_SPEC], (const double *)ctx->v_varray, sm_T, n_rg, n_vb, window, st)) != CPOL_OK)
-        return rc;
-    // ---- sweep histograms: one kernel per requested field behind the sequence, into the context's running state; a finishing
-    // call's counts go where the plan placed them (outside launch_all too) ----
-    if (hg) {
-        const void *const hg_in[CPOL_HIST_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH],
-                                                     T[O_ATTV], T[O_RVEL]};
+    // ---- the call's product behind the sequence (outside launch_all: the captured graph does not know it), on the per-gate fields
+    // wherever they were placed (slot RVEL float64), into pr_T, where the plan placed the product's arrays ----
+    const void *const fields[10] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV], T[O_RVEL]};
+    switch (cq.product) {
+    case PRODUCT_SUPEROB: rc = superob_launch(ctx, so, so_pl, fields, pr_T, ng, window, st); break;       // ONE kernel
+    // the call's member(s) folded into the context's running state, and the outputs of a finishing call
+    case PRODUCT_MEMBER_STATS: rc = member_stats_launch(ctx, ms, ms_pl, fields, pr_T, window, st, mv, p->outputs_on_device == 0); break;
+    case PRODUCT_SPECTRUM_MOMENTS:                                                                        // ONE kernel, on the spectrum
+        rc = spec_moments_launch(ctx, sm, (const double *)T[O_SPEC], (const double *)ctx->v_varray, pr_T, n_rg, n_vb, window, st);
+        break;
+    case PRODUCT_HISTOGRAM: {      // one kernel per requested field, into the context's running state; a finishing call's counts go to pr_T
         const int ord = hg->ordinate;
         const void *y = nullptr;
         long y_gates = n_rg;
         if (ord == HIST_ORD_HEIGHTS || ord == HIST_ORD_DIST) { y = T[ord == HIST_ORD_HEIGHTS ? O_HGT : O_DIST]; y_gates = (long)geo_rays * ng; }
         else if (ord >= HIST_ORD_MODEL) y = (const double *)T[O_MODEL] + (size_t)(ord - HIST_ORD_MODEL) * n_rg;
-        else if (ord >= HIST_ORD_FIELD) y = hg_in[ord - HIST_ORD_FIELD];
-        if ((rc = hist_launch(ctx, hg, hg_pl, hg_in, y, y_gates, n_rg, ng, T_all + A_HG, st)) != CPOL_OK) return rc;
+        else if (ord >= HIST_ORD_FIELD) y = fields[ord - HIST_ORD_FIELD];
+        rc = hist_launch(ctx, hg, hg_pl, fields, y, y_gates, n_rg, ng, pr_T, st);
+        break;
     }
-    // ---- gridded composites: one kernel per requested field behind the sequence, into the context's running state; a finishing
-    // call decodes the state into the maps where the plan placed them (outside launch_all too) ----
-    if (cp) {
-        const void *const cp_in[CPOL_COMP_FIELDS] = {T[O_ZH], T[O_ZV], T[O_ZDR], T[O_KDP], T[O_DHV], T[O_PHIDP], T[O_RHOHV], T[O_ATTH], T[O_ATTV]};
-        if ((rc = comp_launch(ctx, cp, cp_pl, cp_in, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, T_all + A_CP, 0, p->outputs_on_device != 1, st)) != CPOL_OK) return rc;
-        // ---- neighbourhood verification: three kernels behind k_comp_finish, on the finished plane where the plan placed it ----
-        if (fr && (rc = frac_launch(ctx, fr, fr_pl, ob_pl, (const float *)T_all[A_CP + fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride,
-                                    p->outputs_on_device == 0, T_all + A_FR, st)) != CPOL_OK) return rc;
+    case PRODUCT_COMPOSITE:        // likewise; a finishing call decodes the state into the maps at pr_T
+        rc = comp_launch(ctx, cp, cp_pl, fields, T[O_DIST], T[O_HGT], geo_rays, n_rg, ng, pr_T, 0, p->outputs_on_device != 1, st);
+        // the neighbourhood verification: three kernels behind k_comp_finish, on the finished plane where the plan placed it
+        if (rc == CPOL_OK && fr)
+            rc = frac_launch(ctx, fr, fr_pl, ob_pl, (const float *)pr_T[fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride, p->outputs_on_device == 0,
+                             pr_T + CP_N, st);
+        break;
     }
+    if (rc != CPOL_OK) return rc;
     // ---- outputs that the kernels did not write in place ----
     if (window)
         HIPCHK(hipMemcpyAsync((void *)plan.win_lo, (const char *)ctx->b_outwin.p + plan.win_skew, (size_t)(plan.win_hi - plan.win_lo), hipMemcpyDeviceToHost, st));
@@ -4424,13 +4355,8 @@ int cpol_interp_subbeams(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_r
 int cpol_run_columns(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_columns_t *c, cpol_outputs *out)
 {
     if (!ctx) return CPOL_ERR_ARG;
-    if (out && out->superob) { ctx->err = "cpol_run_columns: superobservations (outputs->superob) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
-    if (out && out->composite) { ctx->err = "cpol_run_columns: gridded composites (outputs->composite) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
-    if (out && out->fractions) { ctx->err = "cpol_run_columns: neighbourhood verification (outputs->fractions) is taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
-    if (out && out->histogram) { ctx->err = "cpol_run_columns: sweep histograms (outputs->histogram) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
-    if (out && out->spectrum_moments) { ctx->err = "cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
-    if (out && out->member_stats) { ctx->err = "cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
-    if (out && out->member_verify) { ctx->err = "cpol_run_columns: ensemble verification (outputs->member_verify) is taken by cpol_run_sweep and cpol_run_sweep_members"; return CPOL_ERR_ARG; }
+    const CallProduct cq = out ? call_product(CALL_COLUMNS, *out) : CallProduct{};      // (columns carry no product at all)
+    if (cq.at_entry) { ctx->err = cq.refuse; return CPOL_ERR_ARG; }
     if (!p || !c || !out || p->n_rays < 1 || p->n_gates < 1 || p->n_sub < 1 || c->n_vars < 1 || c->n_vars > CPOL_MAX_VARS ||
         !c->vals || !c->elev || !c->sub_w) {
         ctx->err = "cpol_run_columns: bad shapes, or vals / elev / sub_w missing";
@@ -4496,7 +4422,8 @@ int cpol_run_sweep_members(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol
         ctx->err = "cpol_run_sweep_members: bad arguments (1 <= n_members <= 64 per call)";
         return CPOL_ERR_ARG;
     }
-    if (out->spectrum_moments) { ctx->err = "cpol_run_sweep_members: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep"; return CPOL_ERR_ARG; }
+    const CallProduct cq = call_product(CALL_MEMBERS, *out);                            // (members carry no spectrum moments)
+    if (cq.at_entry) { ctx->err = cq.refuse; return CPOL_ERR_ARG; }
     if (t->time_blend != 0) {
         // ---- ONE scan, every ray blended from the two states that bracket its time ----
         if (t->time_blend != 1 || !t->ray_state || !t->ray_weight) {

@@ -35,7 +35,6 @@ struct CompCall {
     long n_rows = 0;               // n_rays, or n_members * n_rays
     int n_gates = 0;
     bool spaceborne = false;       // per-ray radar positions: no one plane holds the gates
-    bool other_product = false;    // superobservations, histograms, ensemble statistics or spectrum moments in the same call
 };
 
 // the open pass of a context (the states themselves live on the device)
@@ -105,7 +104,6 @@ inline float comp_f32(double v)
 inline const char *comp_check(const cpol_composite *c, const CompCall &call, const CompPass &pass, CompPlan *pl)
 {
     *pl = CompPlan{};
-    if (call.other_product) return "not together with superobservations, histograms, ensemble statistics or spectrum moments in one call";
     if (call.spaceborne) return "a spaceborne call (per-ray radar positions) has no radar-centred plane";
     if (c->phase < 0 || c->phase > 3) return "phase must lie in 0 ... 3";
     if (((c->fields >> COMP_FIELDS) & 1u)) return "RVEL is float64 and is not composed";

@@ -29,7 +29,6 @@ struct HistCall {
     int n_gates = 0;
     bool doppler = false;          // RVEL is produced
     int n_model_vars = 0;          // rows of model_vars the call produces (0: none)
-    bool other_product = false;    // superobservations, ensemble statistics or spectrum moments in the same call
 };
 
 // the open pass of a context (the counts themselves live on the device)
@@ -79,7 +78,6 @@ inline const char *hist_round_edges(const double *e, int n_edges, int type, std:
 inline const char *hist_check(const cpol_histogram *h, const HistCall &c, const HistPass &pass, HistPlan *pl)
 {
     *pl = HistPlan{};
-    if (c.other_product) return "not together with superobservations, ensemble statistics or spectrum moments in one call";
     if (h->phase < 0 || h->phase > 3) return "phase must lie in 0 ... 3";
     if (h->fields == 0 || (h->fields >> HIST_FIELDS) != 0) return "fields must name at least one of the 10 fields and no other bit";
     if (((h->fields >> HIST_RVEL) & 1u) && !c.doppler) return "RVEL needs simulate_doppler";

@@ -790,6 +790,8 @@ typedef struct cpol_fractions {
  * should believe they were shadowed); visibility with per-gate weights (integration scheme 'ml').
  * cpol_debug_read "terrain_shadow_rows" runs k_terrain_shadow alone on caller arrays (a test hook, see cpol_debug_read). */
 
+/* cpol_outputs.  A call takes AT MOST ONE product behind its arrays: superob, member_stats (member_verify rides on it),
+ * spectrum_moments, histogram or composite (fractions, with its objects, rides on it); any two are refused (CPOL_ERR_ARG). */
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;

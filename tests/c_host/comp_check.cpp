@@ -1,6 +1,6 @@
 // Host check of the composite validation (cosmo_pol_amd/csrc/cpol_comp.h); tests/test_composite_cpu.py drives it.
 //   comp_check CALL ...     the calls of one context in turn; the pass they open and close is kept between them.  One CALL:
-//       key=value,... with rows gates space other phase fields(hex) products rpb nx ny hlo hhi (either: a slab) rays(0: NULL
+//       key=value,... with rows gates space phase fields(hex) products rpb nx ny hlo hhi (either: a slab) rays(0: NULL
 //       ray_sin) count(0: NULL) values(0: NULL) and, after ';', lists  x=e0:e1:...  y=e0:e1:...  ("x=null": NULL pointer) and
 //       tK=t0:t1:...  (field K's thresholds; "nK=" overrides n_thresholds[K]) -- strtod syntax, so hex floats, nan and inf are taken
 // prints one line per call:
@@ -63,7 +63,7 @@ int main(int argc, char **argv)
         const auto num = [&](const char *k, long dflt) { return kv.count(k) ? strtol(kv[k].c_str(), nullptr, 0) : dflt; };
         CompCall c;
         c.n_rows = num("rows", 1); c.n_gates = (int)num("gates", 1);
-        c.spaceborne = num("space", 0) != 0; c.other_product = num("other", 0) != 0;
+        c.spaceborne = num("space", 0) != 0;
         cpol_composite s;
         memset(&s, 0, sizeof s);
         s.fields = (uint32_t)num("fields", 1); s.phase = (int32_t)num("phase", 3); s.products = (uint32_t)num("products", 1);

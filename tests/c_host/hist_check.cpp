@@ -1,6 +1,6 @@
 // Host check of the histogram validation (cosmo_pol_amd/csrc/cpol_hist.h); tests/test_histogram_cpu.py drives it.
 //   hist_check CALL ...     the calls of one context in turn; the pass they open and close is kept between them.  One CALL:
-//       key=value,... with rows gates dop nmv other phase fields(hex) ord ny rpb counts(0: no counts pointers) and, after ';',
+//       key=value,... with rows gates dop nmv phase fields(hex) ord ny rpb counts(0: no counts pointers) and, after ';',
 //       edge lists  xK=e0:e1:...  (field K's abscissa; "xK=null" leaves the pointer NULL) and  y=e0:e1:...  -- strtod syntax,
 //       so hex floats, nan and inf are taken
 // prints one line per call:
@@ -59,7 +59,7 @@ int main(int argc, char **argv)
         const auto num = [&](const char *k, long dflt) { return kv.count(k) ? strtol(kv[k].c_str(), nullptr, 0) : dflt; };
         HistCall c;
         c.n_rows = num("rows", 1); c.n_gates = (int)num("gates", 1); c.doppler = num("dop", 1) != 0;
-        c.n_model_vars = (int)num("nmv", 0); c.other_product = num("other", 0) != 0;
+        c.n_model_vars = (int)num("nmv", 0);
         cpol_histogram h;
         memset(&h, 0, sizeof h);
         h.fields = (uint32_t)num("fields", 1); h.phase = (int32_t)num("phase", 3); h.ordinate = (int32_t)num("ord", 0);

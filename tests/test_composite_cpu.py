@@ -456,7 +456,7 @@ def test_host_header_refusals(exe):
         'fields=0x1;x=2:1;y=0:1': 'ascending', 'fields=0x1;x=1:1;y=0:1': 'ascending', 'fields=0x1;x=1:2;y=0:1:1': 'ascending',
         'rays=0,' + ok: 'ray_sin', 'rows=6,rpb=-1,' + ok: 'rays_per_block', 'rows=6,rpb=4,' + ok: 'rays_per_block',
         'phase=0,' + ok: 'no pass open', 'phase=2,' + ok: 'no pass open',
-        'count=0,' + ok: 'count', 'values=0,' + ok: 'values', 'other=1,' + ok: 'not together', 'space=1,' + ok: 'spaceborne',
+        'count=0,' + ok: 'count', 'values=0,' + ok: 'values', 'space=1,' + ok: 'spaceborne',
     }
     for call, word in cases.items():
         line, = run(exe, call)

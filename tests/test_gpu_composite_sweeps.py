@@ -375,7 +375,7 @@ def test_refusals_leave_the_pass_and_the_context_usable():
     hs, hkeep = N.Context.histogram_struct(HG.Histogram({'ZH': [1.0, 2.0]}))
     ms, sm = N.MemberStats(), N.SpectrumMoments()
     for other, s in (('superob', so), ('histogram', hs), ('member_stats', ms), ('spectrum_moments', sm)):
-        with pytest.raises(ValueError, match='not together'):
+        with pytest.raises(ValueError, match='cpol_composite: not together'):
             call(outputs=lambda o, other=other, s=s: setattr(o, other, C.pointer(s)))
     with pytest.raises(ValueError, match='composite'):
         call(entry='run_columns')

@@ -435,12 +435,12 @@ def test_refusals_leave_the_context_usable():
     so.ray_window, so.gate_window, so.min_valid_fraction = 3, 5, 0.5
     zh = np.zeros(SO.shape(len(az), len(op.constants.RANGE_RADAR), SO.Superob(3, 5, 0.5)), dtype=np.float32)
     so.ZH = zh.ctypes.data
-    with pytest.raises(ValueError, match='not together'):
+    with pytest.raises(ValueError, match='cpol_histogram: not together'):
         call(outputs=lambda o: setattr(o, 'superob', C.pointer(so)))
     ms, sm = N.MemberStats(), N.SpectrumMoments()
-    with pytest.raises(ValueError, match='not together'):
+    with pytest.raises(ValueError, match='cpol_histogram: not together'):
         call(outputs=lambda o: setattr(o, 'member_stats', C.pointer(ms)))
-    with pytest.raises(ValueError, match='not together'):
+    with pytest.raises(ValueError, match='cpol_histogram: not together'):
         call(outputs=lambda o: setattr(o, 'spectrum_moments', C.pointer(sm)))
     with pytest.raises(ValueError, match='histogram'):
         call(entry='run_columns')

@@ -356,7 +356,7 @@ def test_host_header_refusals(exe):
         'fields=0x1,ord=1;x0=1:2;y=5:5.0000000001': 'ascending',
         'rows=6,rpb=-1,' + ok: 'rays_per_block', 'rows=6,rpb=4,' + ok: 'rays_per_block',
         'phase=0,' + ok: 'no pass open', 'phase=2,' + ok: 'no pass open',
-        'counts=0,' + ok: 'counts', 'other=1,' + ok: 'not together',
+        'counts=0,' + ok: 'counts',
     }
     for call, word in cases.items():
         line, = run(exe, call)
