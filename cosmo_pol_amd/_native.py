@@ -175,7 +175,10 @@ OBJ_WORDS = 10                                      # CPOL_OBJ_WORDS: the uint32
 class Objects(C.Structure):
     """cpol_objects: the object cells of the binary maps of a cpol_fractions (cosmo_pol_amd/objects.py states the rule)."""
     _fields_ = [('connectivity', C.c_int32), ('min_area', C.c_int32), ('max_objects', C.c_int32), ('pad_', C.c_int32),
-                ('n_objects', C.c_void_p), ('table', C.c_void_p), ('labels', C.c_void_p)]
+                ('n_objects', C.c_void_p), ('table', C.c_void_p), ('labels', C.c_void_p),
+                # the exact sums: a zero-initialised tail means off
+                ('sums', C.c_int32), ('n_weight', C.c_int32), ('weight_v', C.c_void_p), ('weight_f', C.c_void_p),
+                ('volume', C.c_void_p), ('skipped', C.c_void_p), ('field', C.c_void_p), ('field_cells', C.c_void_p)]
 
 
 class Fractions(C.Structure):
@@ -189,8 +192,9 @@ class Fractions(C.Structure):
 class _ObjectsNamed(object):
     """What objects.result reads of a spec, for the test hook: the cells' terms and the thresholds as the library rounds them."""
 
-    def __init__(self, objects, spec):
+    def __init__(self, objects, spec, grid):
         self.connectivity, self.min_area = objects.connectivity, objects.min_area
+        self.weight, (self.n_y, self.n_x) = getattr(objects, 'weight', None), grid
         with np.errstate(over='ignore'):
             self.thresholds = np.array(spec.thresholds_given, dtype=np.float64).astype(np.float32)
 
@@ -1226,7 +1230,14 @@ class Context(object):
         o = Objects()
         o.connectivity, o.min_area, o.max_objects = spec.connectivity, spec.min_area, spec.max_objects
         fractions.objects = C.pointer(o)
-        return o, [o]
+        keep = [o]
+        if getattr(spec, 'sums', False):
+            o.sums = 1
+            if spec.weight is not None:
+                tv, tf = (np.ascontiguousarray(spec.weight[0], dtype=np.float32), np.ascontiguousarray(spec.weight[1], dtype=np.float64))
+                o.n_weight, o.weight_v, o.weight_f = len(tv), tv.ctypes.data, tf.ctypes.data
+                keep += [tv, tf]
+        return o, keep
 
     def fractions_maps(self, maps, observed, spec, domain=None, tamper=None, objects=None):
         """Test hook (cpol_debug_read "fractions_maps"): the checks and k_frac_rows, k_frac_cols, k_frac_score on caller-supplied
@@ -1234,7 +1245,8 @@ class Context(object):
         [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
         and `radii` (the maps need not be those of spec.composite's grid).  `tamper(f)`: changes the cpol_fractions before the call
         (the refusal tests).  `objects`: an objects.Objects or any object with `connectivity`, `min_area`, `max_objects` and
-        `labels`: the kernels of cpol_obj.inl run too, and the result is (the sums, what objects.cells returns for the maps);
+        `labels` (and `sums` with `weight` for the exact sums): the kernels of cpol_obj.inl run too, and the result is (the sums,
+        what objects.cells returns for the maps);
         `tamper` then finds the cpol_objects at f.objects.contents."""
         from . import neighbourhood as NB
 
@@ -1278,6 +1290,12 @@ class Context(object):
             if objects.labels:
                 labels = np.full((m.shape[0] + 1, nt) + m.shape[1:], -559038737, dtype=np.int32)
                 o.labels = labels.ctypes.data
+            osums = None
+            if getattr(objects, 'sums', False):
+                osums = [np.full((m.shape[0] + 1, nt, objects.max_objects, 3), np.nan, dtype=np.float64),
+                         np.full((m.shape[0] + 1, nt, objects.max_objects), 0xDEADBEEF, dtype=np.uint32),
+                         np.full((m.shape[0] + 1, 3), np.nan, dtype=np.float64), np.full((m.shape[0] + 1, 2), 0xDEADBEEF, dtype=np.uint32)]
+                o.volume, o.skipped, o.field, o.field_cells = [q.ctypes.data for q in osums]
             keep += okeep
         hk.f = f
         if tamper is not None:
@@ -1286,7 +1304,7 @@ class Context(object):
         self._check(rc, 'cpol_debug_read(fractions_maps)')
         del keep
         if objects is not None:
-            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec), n_obj, table, labels)
+            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums)
         return NB.result(spec, s, t)
 
     @staticmethod

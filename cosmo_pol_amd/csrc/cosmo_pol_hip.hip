@@ -219,10 +219,11 @@ struct cpol_ctx {
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand
-    DevBuf b_fsat, b_fobs, b_fout[5], b_fmaps;
+    DevBuf b_fsat, b_fobs, b_fout[9], b_fmaps;
     FracPlan fplan;
     // object cells (cpol_objects, beside a cpol_fractions): the labelling scratch and the plan of the call at hand; n_objects, table
-    // and labels are b_fout[2 ... 4]
+    // and labels are b_fout[2 ... 4], volume, skipped, field and field_cells of the exact sums b_fout[5 ... 8]; the sums'
+    // accumulators and the weight table lie behind the labelling scratch (ObjPlan)
     DevBuf b_oscr;
     ObjPlan oplan;
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
@@ -825,7 +826,7 @@ void cpol_destroy(cpol_ctx *ctx)
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
     DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fout[2], &ctx->b_fout[3], &ctx->b_fout[4], &ctx->b_oscr, &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
+                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fout[2], &ctx->b_fout[3], &ctx->b_fout[4], &ctx->b_fout[5], &ctx->b_fout[6], &ctx->b_fout[7], &ctx->b_fout[8], &ctx->b_oscr, &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
                      &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
                      &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
                      &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
@@ -2866,7 +2867,8 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
 
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
 // (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
-enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_N };
+enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_OBJ_VOLUME, FR_OBJ_SKIPPED, FR_OBJ_FIELD, FR_OBJ_FIELD_CELLS, FR_N };
+static_assert(FR_N == 9, "cpol_ctx::b_fout holds one buffer per array");
 // arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
 // composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for)
 static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, PlaceArray *arr)
@@ -2880,6 +2882,11 @@ static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPla
     arr[FR_OBJ_N].user = (uintptr_t)o->n_objects;    arr[FR_OBJ_N].bytes = op.n_bytes;           arr[FR_OBJ_N].produced = true;
     arr[FR_OBJ_TABLE].user = (uintptr_t)o->table;    arr[FR_OBJ_TABLE].bytes = op.table_bytes;   arr[FR_OBJ_TABLE].produced = true;
     arr[FR_OBJ_LABELS].user = (uintptr_t)o->labels;  arr[FR_OBJ_LABELS].bytes = op.labels_bytes; arr[FR_OBJ_LABELS].produced = op.labels;
+    if (!op.sums) return;
+    arr[FR_OBJ_VOLUME].user = (uintptr_t)o->volume;            arr[FR_OBJ_VOLUME].bytes = op.volume_bytes;           arr[FR_OBJ_VOLUME].produced = true;
+    arr[FR_OBJ_SKIPPED].user = (uintptr_t)o->skipped;          arr[FR_OBJ_SKIPPED].bytes = op.skipped_bytes;         arr[FR_OBJ_SKIPPED].produced = true;
+    arr[FR_OBJ_FIELD].user = (uintptr_t)o->field;              arr[FR_OBJ_FIELD].bytes = op.field_bytes;             arr[FR_OBJ_FIELD].produced = true;
+    arr[FR_OBJ_FIELD_CELLS].user = (uintptr_t)o->field_cells;  arr[FR_OBJ_FIELD_CELLS].bytes = op.field_cells_bytes; arr[FR_OBJ_FIELD_CELLS].produced = true;
 }
 
 // the kernels of cpol_obj.inl behind k_frac_score on `st`; fa: the maps as frac_launch resolved them
@@ -2909,6 +2916,27 @@ static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, con
     hipLaunchKernelGGL(k_obj_attr, rows, thr, 0, st, a);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_obj_decode, dim3((unsigned)op.grid_decode), thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    if (!op.sums) return CPOL_OK;
+    // the exact sums: the accumulators behind the labelling scratch cleared, the weight table behind them
+    char *const scr = (char *)ctx->b_oscr.p;
+    a.acc = (unsigned long long *)(scr + op.acc_offset);
+    a.volume = (double *)T[FR_OBJ_VOLUME]; a.skipped = (unsigned *)T[FR_OBJ_SKIPPED];
+    a.field = (double *)T[FR_OBJ_FIELD]; a.field_cells = (unsigned *)T[FR_OBJ_FIELD_CELLS];
+    const size_t nw = op.weight_v.size();
+    a.n_weight = (int)nw;
+    if (nw) {
+        a.wf = (const double *)(scr + op.weight_offset); a.wv = (const float *)(a.wf + nw);
+        for (a.step_w = 1; 2 * a.step_w <= (int)nw; a.step_w *= 2) {}
+        HIPCHK(hipMemcpyAsync((void *)a.wf, op.weight_f.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void *)a.wv, op.weight_v.data(), nw * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)op.acc_bytes, st));
+    HIPCHK(hipMemsetAsync(a.skipped, 0, op.skipped_bytes, st));
+    HIPCHK(hipMemsetAsync(a.field_cells, 0, op.field_cells_bytes, st));
+    hipLaunchKernelGGL(k_obj_sums, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_sums_finish, dim3((unsigned)op.grid_finish), thr, 0, st, a);
     HIPCHK(hipGetLastError());
     return CPOL_OK;
 }

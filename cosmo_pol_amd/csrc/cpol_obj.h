@@ -13,6 +13,8 @@
 // index of the pair strictly decreases (it stops at the first return value >= it).  Neither waits for another thread.
 #pragma once
 
+#include <cmath>
+#include <vector>
 #include "cpol_frac.h"
 
 #if defined(__HIPCC__)
@@ -27,6 +29,9 @@ constexpr unsigned OBJ_NONE = 0xFFFFFFFFu;
 constexpr long OBJ_MAX_SCRATCH_BYTES = FRAC_MAX_SCRATCH_BYTES;
 constexpr int OBJ_THREADS = FRAC_THREADS;             // threads of a workgroup: four wavefronts, one row each
 constexpr int OBJ_ROWS = OBJ_THREADS / 64;
+// the exact sums: the bins of one accumulator row, int64 each: OBJ_SUM_VOL_BINS of the volume, then OBJ_SUM_MOM_BINS of each moment
+constexpr int OBJ_SUM_VOL_BINS = 16, OBJ_SUM_MOM_BINS = 32, OBJ_SUM_BINS = OBJ_SUM_VOL_BINS + 2 * OBJ_SUM_MOM_BINS;
+constexpr int OBJ_SUM_LIMBS = 6;                      // 384 bits hold every sum (obj_sum_round)
 // the words of a table row
 enum { OBJ_FIRST, OBJ_AREA, OBJ_SUM_X, OBJ_SUM_Y, OBJ_X0, OBJ_X1, OBJ_Y0, OBJ_Y1, OBJ_PEAK_CELL, OBJ_PEAK_BITS };
 
@@ -41,6 +46,14 @@ struct ObjPlan {
     long scratch_bytes = 0;
     long grid_rows = 0, grid_cells = 0, grid_decode = 0;   // workgroups: a wavefront per (source, row); a thread per cell; per table row
     size_t n_bytes = 0, table_bytes = 0, labels_bytes = 0;
+    // the exact sums (cpol_objects.sums): behind the labelling scratch, 8-byte aligned, the accumulators int64 [n_maps * max_objects
+    // + n_sources][OBJ_SUM_BINS], cleared in the call, then the weight table (n_weight float64 values, n_weight float32 breakpoints)
+    bool sums = false;
+    long n_sources = 0, acc_offset = 0, acc_bytes = 0, weight_offset = 0;
+    long grid_finish = 0;                             // workgroups: a thread per (table row or source, sum); k_obj_sums takes grid_rows
+    size_t volume_bytes = 0, skipped_bytes = 0, field_bytes = 0, field_cells_bytes = 0;
+    std::vector<float> weight_v;                      // empty: w = m
+    std::vector<double> weight_f;
 };
 
 // every refusal of a cpol_objects beside a cpol_fractions whose plan `fp` passed; o == NULL: off (*pl says so).  NULL: accepted
@@ -67,6 +80,37 @@ inline const char *obj_check(const cpol_objects *o, const FracPlan &fp, ObjPlan 
     pl->n_bytes = (size_t)pl->n_maps * sizeof(uint32_t);
     pl->table_bytes = (size_t)pl->n_maps * pl->max_objects * OBJ_WORDS * sizeof(uint32_t);
     pl->labels_bytes = pl->labels ? (size_t)pl->n_maps * pl->cells * sizeof(int32_t) : 0;
+    // the exact sums: a zero tail of the struct means off, and nothing above changes
+    if (o->sums != 0 && o->sums != 1) return "sums must be 0 or 1";
+    if (!o->sums) return nullptr;
+    if (!o->volume || !o->skipped || !o->field || !o->field_cells) return "volume, skipped, field or field_cells is NULL";
+    if (((uintptr_t)o->volume | (uintptr_t)o->field) & 7u) return "volume and field must be 8-byte aligned";
+    if (o->n_weight != 0) {
+        const int n = o->n_weight;
+        if (n < 2 || n > COMP_MAX_TABLE) return "a weight table needs 2 ... 1024 breakpoints";
+        if (!o->weight_v || !o->weight_f) return "weight_v or weight_f is NULL";
+        pl->weight_v.assign(o->weight_v, o->weight_v + n);
+        pl->weight_f.assign(o->weight_f, o->weight_f + n);
+        for (int j = 0; j < n; ++j) {
+            if (!std::isfinite(pl->weight_v[(size_t)j]) || !std::isfinite(pl->weight_f[(size_t)j])) return "a breakpoint or a value of the weight table is NaN or infinite";
+            if (j && !(pl->weight_v[(size_t)j - 1] < pl->weight_v[(size_t)j])) return "the breakpoints of the weight table are not strictly ascending";
+            if (j && !(pl->weight_f[(size_t)j - 1] <= pl->weight_f[(size_t)j])) return "the values of the weight table decrease";
+        }
+    }
+    pl->sums = true;
+    pl->n_sources = fp.n_blocks + 1;
+    pl->acc_offset = (pl->scratch_bytes + 7) & ~7L;
+    // (n_maps <= 4 * 2^28 / cells and max_objects < 2^16: below 2^53 bytes, no overflow of long)
+    pl->acc_bytes = (pl->n_maps * pl->max_objects + pl->n_sources) * OBJ_SUM_BINS * 8;
+    pl->weight_offset = pl->acc_offset + pl->acc_bytes;
+    pl->scratch_bytes = pl->weight_offset + (long)o->n_weight * 8 + (((long)o->n_weight * 4 + 7) & ~7L);
+    if (pl->scratch_bytes > OBJ_MAX_SCRATCH_BYTES) return "the labelling scratch and the sums' accumulators must be at most 1 GiB";
+    pl->grid_finish = ((pl->n_maps * pl->max_objects + pl->n_sources) * 3 + OBJ_THREADS - 1) / OBJ_THREADS;
+    if (pl->grid_finish >= (1L << 31)) return "too many workgroups in one call";
+    pl->volume_bytes = (size_t)pl->n_maps * pl->max_objects * 3 * sizeof(double);
+    pl->skipped_bytes = (size_t)pl->n_maps * pl->max_objects * sizeof(uint32_t);
+    pl->field_bytes = (size_t)pl->n_sources * 3 * sizeof(double);
+    pl->field_cells_bytes = (size_t)pl->n_sources * 2 * sizeof(uint32_t);
     return nullptr;
 }
 
@@ -169,3 +213,104 @@ OBJ_HD void obj_merge_cell(unsigned *L, int n_x, int y, int x, int connectivity)
 OBJ_HD unsigned obj_order(unsigned bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
 OBJ_HD unsigned obj_unorder(unsigned k) { return (k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k; }
 OBJ_HD unsigned long long obj_peak_key(unsigned bits, unsigned cell) { return ((unsigned long long)obj_order(bits) << 32) | (unsigned long long)(~cell); }
+
+// ---- the exact sums (cpol_objects.sums).  A finite float32 with the bits (sign, e, m) is  +-M * 2^(E - 150)  with E = max(e, 1) in
+// 1 ... 254 and M = m | (e ? 2^23 : 0) < 2^24: an INTEGER multiple of 2^-150 (of 2^-149 in fact).  Integer additions commute, so
+// atomics in any order leave the same accumulator, and ONE rounding at the end gives the float64 that no order can change.
+// THE ACCUMULATOR ROW, OBJ_SUM_BINS signed 64-bit bins (two's complement, added as unsigned long long):
+//   volume    bins 0 ... 15:  bin E >> 4 takes  +-M << (E & 15), below 2^39 in magnitude.  An object (and the field) has < 2^20 cells
+//             (NO OVERFLOW, cosmo_pol_amd.h), so |bin| < 2^59.
+//   moment_x  bins 16 ... 47: bin E >> 3 takes  +-(M * ix) << (E & 7).  The sum of ix over the cells is < 2^30 (the same clause), so
+//             |bin| < 2^24 * 2^7 * 2^30 = 2^61.
+//   moment_y  bins 48 ... 79: likewise with iy.
+// Conditions, not measurements: no bin can wrap.  The sum is  2^-150 * sum_b bin[b] * 2^(step * b)  with step 16 or 8: below 2^(8 *
+// 31 + 62) = 2^310 in magnitude, which the OBJ_SUM_LIMBS * 64 = 384 bits of obj_sum_round hold with their sign. ----
+
+// false: the value is +-inf or NaN and is not summed
+OBJ_HD bool obj_sum_split(unsigned bits, int *E, unsigned *M)
+{
+    const unsigned e = (bits >> 23) & 0xFFu, m = bits & 0x007FFFFFu;
+    *E = e ? (int)e : 1;
+    *M = e ? m | 0x00800000u : m;
+    return e != 0xFFu;
+}
+
+// the signed contribution  +-(M * mult) << shift  (mult <= 1023, shift <= 15 with mult 1 and <= 7 else: below 2^41)
+OBJ_HD long long obj_sum_term(unsigned bits, unsigned M, unsigned mult, int shift)
+{
+    const long long c = (long long)(((unsigned long long)M * mult) << shift);
+    return (bits & 0x80000000u) ? -c : c;
+}
+
+// The bits of the float64 nearest to  2^-150 * sum_b bins[b] * 2^(step * b)  (ties to even), +0.0 for an exact zero: the bins
+// propagated into one two's-complement integer of OBJ_SUM_LIMBS limbs, its sign and magnitude, the top 53 bits, then the guard bit
+// and the sticky rest.  The magnitude is >= 1 and < 2^310, so the result is a normal number: no underflow, no overflow.
+OBJ_HD unsigned long long obj_sum_round(const unsigned long long *bins, int n_bins, int step)
+{
+    unsigned long long limb[OBJ_SUM_LIMBS];
+    for (int k = 0; k < OBJ_SUM_LIMBS; ++k) limb[k] = 0ull;
+    for (int b = 0; b < n_bins; ++b) {
+        const unsigned long long v = bins[b], ext = (v >> 63) ? ~0ull : 0ull;
+        const int w = (b * step) >> 6, s = (b * step) & 63;
+        const unsigned long long lo = v << s, mid = s ? (v >> (64 - s)) | (ext << s) : ext;
+        unsigned long long carry = 0ull;
+        for (int k = w; k < OBJ_SUM_LIMBS; ++k) {
+            const unsigned long long piece = k == w ? lo : k == w + 1 ? mid : ext;
+            const unsigned long long a = limb[k] + piece, c = a + carry;
+            carry = (unsigned long long)(a < piece) | (unsigned long long)(c < carry);
+            limb[k] = c;
+        }
+    }
+    const bool neg = (limb[OBJ_SUM_LIMBS - 1] >> 63) != 0ull;
+    if (neg) {
+        unsigned long long carry = 1ull;
+        for (int k = 0; k < OBJ_SUM_LIMBS; ++k) {
+            const unsigned long long c = ~limb[k] + carry;
+            carry = (unsigned long long)(c < carry);
+            limb[k] = c;
+        }
+    }
+    int top = -1;
+    for (int k = 0; k < OBJ_SUM_LIMBS; ++k)
+        if (limb[k]) top = k;
+    if (top < 0) return 0ull;
+    const int p = 64 * top + 63 - __builtin_clzll(limb[top]);         // the highest set bit
+    unsigned long long mant;
+    if (p <= 52) mant = limb[0] << (52 - p);                          // (exact: nothing to round)
+    else {
+        const int r = p - 52, i = r >> 6, s = r & 63;                 // the 53 bits from bit r on
+        mant = limb[i] >> s;
+        if (s && i + 1 < OBJ_SUM_LIMBS) mant |= limb[i + 1] << (64 - s);
+        mant &= (1ull << 53) - 1ull;
+        const int g = r - 1, gi = g >> 6, gs = g & 63;
+        const bool guard = (limb[gi] >> gs) & 1ull;
+        bool sticky = (limb[gi] & ((1ull << gs) - 1ull)) != 0ull;
+        for (int k = 0; k < gi; ++k) sticky = sticky || limb[k] != 0ull;
+        if (guard && (sticky || (mant & 1ull))) ++mant;               // (2^53: the sum below carries it into the exponent)
+    }
+    return ((unsigned long long)neg << 63) | ((((unsigned long long)(p - 150 + 1023)) << 52) + (mant - (1ull << 52)));
+}
+
+// The weight of a cell: w = float32(f(v)), f the piecewise-linear function of composite.column_of (k_comp_column) over the table
+// (tv float32 strictly ascending, tf float64) of n breakpoints, statement by statement: j = #{ tv <= v } - 1 from comparisons in
+// float32 (step0: the largest power of two <= n); 0 below the table, tf[n - 1] at and above its end; else t, d, p and tf[j] + p,
+// one float64 operation each (no contraction); then ONE rounding to float32.  v is not NaN.
+OBJ_HD float obj_weight(const float *tv, const double *tf, int n, int step0, float v)
+{
+    int lo = 0;
+    for (int step = step0; step > 0; step >>= 1) {
+        const int t = lo + step;
+        if (t <= n && tv[t - 1] <= v) lo = t;
+    }
+    const int j = lo - 1;
+    double f;
+    if (j < 0) f = 0.0;
+    else if (j >= n - 1) f = tf[n - 1];
+    else {
+        const double t = ((double)v - (double)tv[j]) / ((double)tv[j + 1] - (double)tv[j]);
+        const double d = tf[j + 1] - tf[j];
+        const double p = t * d;
+        f = tf[j] + p;
+    }
+    return (float)f;
+}

@@ -18,6 +18,10 @@
 //                  into the table; the root's area gives way to its number;
 //   k_obj_attr     the labels, and per run segment the sums, the box and the peak into the table rows up to max_objects;
 //   k_obj_decode   a thread per table row: the box and the peak out of the forms the atomic maxima needed.
+// With cpol_objects.sums two more (the EXACT SUMS of the header; the accumulator row and its bounds: cpol_obj.h):
+//   k_obj_sums         the weight of a cell split ONCE into sign, exponent and integer; per threshold the cells of a chunk that share
+//                      an object and a bin are summed inside the wavefront and leave as ONE integer atomic; the field likewise;
+//   k_obj_sums_finish  a thread per sum: the bins into one integer, ONE rounding to float64 (obj_sum_round).
 
 struct ObjArgs {
     FracArgs f;                     // the maps: plane, obs, domain, the grid, the rounded thresholds
@@ -27,6 +31,15 @@ struct ObjArgs {
     int *labels;                    // [n_maps][cells] or NULL
     long n_maps;
     int connectivity, min_area, max_objects;
+    // the exact sums (NULL acc: off)
+    unsigned long long *acc;        // [n_maps * max_objects + n_blocks + 1][OBJ_SUM_BINS]: zero before k_obj_sums
+    double *volume;                 // [n_maps][max_objects][3]
+    unsigned *skipped;              // [n_maps][max_objects]: zero before k_obj_sums
+    double *field;                  // [n_blocks + 1][3]
+    unsigned *field_cells;          // [n_blocks + 1][2]: zero before k_obj_sums
+    const float *wv;                // the weight table on the device: breakpoints ...
+    const double *wf;               // ... and values [n_weight]; n_weight 0: w = m
+    int n_weight, step_w;           // step_w: the largest power of two <= n_weight
 };
 
 // the wavefront's source and row; false: no row (whole wavefronts leave: no barrier in these kernels)
@@ -235,6 +248,97 @@ __global__ __launch_bounds__(OBJ_THREADS) void k_obj_decode(const ObjArgs a)
     const unsigned lo = row[OBJ_PEAK_CELL], hi = row[OBJ_PEAK_BITS];
     row[OBJ_PEAK_CELL] = ~lo;
     row[OBJ_PEAK_BITS] = obj_unorder(hi);
+}
+
+// ---- the exact sums ----
+
+__device__ __forceinline__ long long obj_wave_sum(long long v)
+{
+    for (int dlt = 32; dlt > 0; dlt >>= 1) v += __shfl_xor(v, dlt);
+    return v;
+}
+
+// The lanes with `on` hold a key (accumulator row << 5 | bin of the moments, E >> 3; the volume's bin is half of it) and three
+// signed contributions.  While lanes remain: the first remaining lane's key, the ballot of the lanes with the same key, their
+// contributions summed across the wavefront (at most 64 terms below 2^41: no overflow), ONE atomic per sum by that lane.
+// TERMINATION: `left` is the same in every lane (a ballot) and loses at least the leading lane's bit in every turn: at most 64
+// turns.  Every lane of the wavefront calls this together.
+__device__ __forceinline__ void obj_sums_combine(unsigned long long *rows, bool on, unsigned key, long long cv, long long cx, long long cy, int lane)
+{
+    unsigned long long left = __ballot(on);
+    while (left) {
+        const int lead = __builtin_ctzll(left);
+        const unsigned k = __shfl(key, lead);
+        const bool mine = on && key == k;
+        const long long sv = obj_wave_sum(mine ? cv : 0ll), sx = obj_wave_sum(mine ? cx : 0ll), sy = obj_wave_sum(mine ? cy : 0ll);
+        if (lane == lead) {
+            unsigned long long *const row = rows + (size_t)(k >> 5) * OBJ_SUM_BINS;
+            const unsigned b = k & 31u;
+            if (sv) atomicAdd(row + (b >> 1), (unsigned long long)sv);
+            if (sx) atomicAdd(row + OBJ_SUM_VOL_BINS + b, (unsigned long long)sx);
+            if (sy) atomicAdd(row + OBJ_SUM_VOL_BINS + OBJ_SUM_MOM_BINS + b, (unsigned long long)sy);
+        }
+        left &= ~__ballot(mine);
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_obj_sums(const ObjArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;
+    const int n_x = a.f.n_x;
+    const float *const row_in = (src < a.f.n_blocks ? a.f.plane + src * a.f.plane_stride : a.f.obs) + (long)y * n_x;
+    const unsigned char *const row_dom = a.f.domain ? a.f.domain + (long)y * n_x : nullptr;
+    unsigned long long *const field_row = a.acc + ((size_t)a.n_maps * a.max_objects + src) * OBJ_SUM_BINS;
+    unsigned n_summed = 0u, n_skipped = 0u;
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+        const float v = in ? row_in[x] : 0.f;
+        const bool d = in && (!row_dom || row_dom[x] != 0) && v == v;
+        const float w = d && a.n_weight ? obj_weight(a.wv, a.wf, a.n_weight, a.step_w, v) : v;
+        const unsigned bits = __float_as_uint(w);
+        int E; unsigned M;
+        const bool finite = obj_sum_split(bits, &E, &M);
+        const bool sum = d && finite, skip = d && !finite;
+        const long long cv = sum ? obj_sum_term(bits, M, 1u, E & 15) : 0ll;
+        const long long cx = sum ? obj_sum_term(bits, M, (unsigned)x, E & 7) : 0ll;
+        const long long cy = sum ? obj_sum_term(bits, M, (unsigned)y, E & 7) : 0ll;
+        const unsigned bin = (unsigned)(E >> 3);
+        n_summed += (unsigned)__popcll(__ballot(sum));
+        n_skipped += (unsigned)__popcll(__ballot(skip));
+        obj_sums_combine(field_row, sum, bin, cv, cx, cy, lane);                    // (row 0 of field_row: the source's own)
+        for (int t = 0; t < a.f.n_thr; ++t) {
+            OBJ_CHUNK(t);
+            (void)m;
+            const unsigned number = set ? a.aux[base + root] : 0u;
+            const bool kept = number != 0u && number <= (unsigned)a.max_objects;    // (a set cell lies in the domain and is no NaN)
+            const long map = src * a.f.n_thr + t;
+            obj_sums_combine(a.acc + (size_t)map * a.max_objects * OBJ_SUM_BINS, kept && sum, ((number - 1u) << 5) | bin, cv, cx, cy, lane);
+            if (kept && skip) atomicAdd(a.skipped + map * a.max_objects + (number - 1u), 1u);
+        }
+    }
+    if (lane == 0) {
+        if (n_summed) atomicAdd(a.field_cells + 2 * src, n_summed);
+        if (n_skipped) atomicAdd(a.field_cells + 2 * src + 1, n_skipped);
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_obj_sums_finish(const ObjArgs a)
+{
+    const long i = (long)blockIdx.x * OBJ_THREADS + threadIdx.x;
+    const long n_rows = a.n_maps * a.max_objects;
+    if (i >= (n_rows + a.f.n_blocks + 1) * 3) return;
+    const long r = i / 3;
+    const int which = (int)(i - r * 3);
+    const unsigned long long *const row = a.acc + (size_t)r * OBJ_SUM_BINS;
+    // (the rows at or beyond n_objects took no atomic: +0.0)
+    const unsigned long long bits = which == 0 ? obj_sum_round(row, OBJ_SUM_VOL_BINS, 16)
+                                               : obj_sum_round(row + OBJ_SUM_VOL_BINS + (which - 1) * OBJ_SUM_MOM_BINS, OBJ_SUM_MOM_BINS, 8);
+    double *const out = r < n_rows ? a.volume + r * 3 : a.field + (r - n_rows) * 3;
+    out[which] = __longlong_as_double((long long)bits);
 }
 
 #undef OBJ_CHUNK

@@ -1,7 +1,8 @@
 """Object cells (cpol_objects): the connected components of the binary maps of a neighbourhood verification, numbered, with ten
-integer attributes each, found on the device behind the scores.  This module states the rule in NumPy (`cells`);
-include/cosmo_pol_amd.h states the same text, and the GPU tests compare the kernels (cosmo_pol_amd/csrc/cpol_obj.inl) with it
-exactly: every attribute is a count, an integer sum, an integer extreme or a comparison.
+integer attributes each and, when asked for, the EXACT float sums over their cells (rain volume, weighted moments), found on the
+device behind the scores.  This module states the rule in NumPy (`cells`, `exact_sum`, `weight_of`); include/cosmo_pol_amd.h
+states the same text, and the GPU tests compare the kernels (cosmo_pol_amd/csrc/cpol_obj.inl) with it exactly: every attribute
+is a count, an integer sum, an integer extreme or a comparison, and every float sum is a sum of integers rounded once.
 
 THE RULE
   Input      the binary maps of neighbourhood.Fractions, unchanged: F[b, t] = domain & (m == m) & (m >= thr[t]) of the scored
@@ -20,9 +21,27 @@ THE RULE
   Outputs    n_objects uint32 [n_blocks + 1, n_thr]: the true kept count, also beyond max_objects; table uint32 [n_blocks + 1,
              n_thr, max_objects, WORDS], rows at or beyond n_objects zero; labels int32 [n_blocks + 1, n_thr, n_y, n_x], 0 for
              background and dropped objects, complete even when the table overflows.  `result` names them.
-  Not built  float sums over an object's cells (rain volume, weighted centroids, SAL's S and L2): the label map is delivered so
-             that the host can form them.
-  Limits     the labelling scratch, (n_blocks + 1) * n_thr * (2 * n_y * n_x + n_y) * 4 bytes, at most MAX_SCRATCH_BYTES."""
+  Limits     the labelling scratch, (n_blocks + 1) * n_thr * (2 * n_y * n_x + n_y) * 4 bytes, at most MAX_SCRATCH_BYTES.
+
+EXACT SUMS (Objects(sums=True); `weighted_centroids` and `sal` read them)
+  Summand    for a cell with plane value m (o for the observed map) the summand is w = m.  With a weight table (table_v float32
+             strictly ascending, table_f float64) it is w = float32(f(m)), f the piecewise-linear function that
+             composite.column_of evaluates, statement by statement: searchsorted(..., 'right') - 1; t = (m - v_i) / (v_i+1 - v_i),
+             d, p = t * d, f_i + p, each one float64 operation; 0 below the table, table_f[-1] at and above its end; then one
+             rounding to float32 (`weight_of`).  table_f must be finite and non-decreasing, so that the peak of w is w(peak):
+             SAL on rain rate under a Z-R table (`zr_table`) instead of linear Z.
+  Skipped    a cell whose w is +-inf is not summed; it is counted in `skipped`.  NaN cells are never set.
+  Per object with a table row: volume = sum w, moment_x = sum w * ix, moment_y = sum w * iy over its cells, each sum formed
+             exactly (a float32 is an integer multiple of 2^-149, a product w * ix is exact: 24 + 10 bits) and rounded ONCE to
+             float64, round-to-nearest-even: math.fsum of the summands, whatever their order.  An exact zero is +0.0.
+  Per source independent of the threshold: the same three sums over every cell with domain && m == m, and the cells summed and
+             skipped.
+  The rule   `exact_sum`: integers alone.  The bits of a float32 are sign, E = max(e, 1) and a 24-bit M: the value is
+             +-M * 2^(E - 150).  The integers M << E (times ix) are added and the total rounded by hand.
+  Outputs    volume float64 [n_blocks + 1, n_thr, max_objects, 3], rows at or beyond n_objects zero; skipped uint32 [n_blocks + 1,
+             n_thr, max_objects]; field float64 [n_blocks + 1, 3]; field_cells uint32 [n_blocks + 1, 2].
+  Limits     the accumulators, SUM_BINS int64 per table row and per source, and the weight table count into the scratch limit.
+  Not built  matching and tracking of objects; cells of layered composites."""
 import numpy as np
 
 from . import neighbourhood as NB
@@ -30,6 +49,8 @@ from . import neighbourhood as NB
 WORDS = 10
 MAX_OBJECTS = 65535
 MAX_SCRATCH_BYTES = 1 << 30
+MAX_TABLE = 1024                                          # breakpoints of a weight table: the composite's MAX_TABLE
+SUM_BINS = 16 + 32 + 32                                   # int64 bins of one accumulator row (cpol_obj.h): volume, moment_x, moment_y
 FIRST, AREA, SUM_X, SUM_Y, X0, X1, Y0, Y1, PEAK_CELL, PEAK_BITS = range(WORDS)
 
 _U32, _I64 = np.uint32, np.int64
@@ -38,10 +59,11 @@ _U32, _I64 = np.uint32, np.int64
 class Objects(object):
     """What a call with object cells finds: the cells of the binary maps of `fractions` (a neighbourhood.Fractions) under
     `connectivity` 4 or 8, those below `min_area` cells dropped, up to `max_objects` (1 ... 65535) table rows per source and
-    threshold, with the label maps when `labels`.  ValueError for what the library refuses.  The Fractions is `fractions`; the
-    properties the scored entry points read of a spec are its own."""
+    threshold, with the label maps when `labels` and the exact sums when `sums`, under `weight` = (table_v, table_f) or None
+    (w = m).  ValueError for what the library refuses.  The Fractions is `fractions`; the properties the scored entry points read
+    of a spec are its own."""
 
-    def __init__(self, fractions, connectivity=4, min_area=1, max_objects=1024, labels=True):
+    def __init__(self, fractions, connectivity=4, min_area=1, max_objects=1024, labels=True, sums=False, weight=None):
         if not isinstance(fractions, NB.Fractions):
             raise ValueError('fractions: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (fractions,))
         for name, v in (('connectivity', connectivity), ('min_area', min_area), ('max_objects', max_objects)):
@@ -55,6 +77,11 @@ class Objects(object):
             raise ValueError('max_objects must lie in 1 ... %d, got %r' % (MAX_OBJECTS, max_objects))
         self.fractions = fractions
         self.connectivity, self.min_area, self.max_objects, self.labels = int(connectivity), int(min_area), int(max_objects), bool(labels)
+        self.sums, self.weight = bool(sums), None
+        if weight is not None:
+            if not self.sums:
+                raise ValueError('weight: a weight table belongs to sums=True')
+            self.weight = check_weight(weight)
 
     composite = property(lambda self: self.fractions.composite)
     thresholds = property(lambda self: self.fractions.thresholds)
@@ -63,7 +90,10 @@ class Objects(object):
 
     @property
     def key(self):
-        return (self.fractions.key, self.connectivity, self.min_area, self.max_objects, self.labels)
+        key = (self.fractions.key, self.connectivity, self.min_area, self.max_objects, self.labels)
+        if self.sums:
+            key += (True, None if self.weight is None else (self.weight[0].tobytes(), self.weight[1].tobytes()))
+        return key
 
     def __eq__(self, other):
         return isinstance(other, Objects) and self.key == other.key
@@ -72,13 +102,166 @@ class Objects(object):
         return hash(self.key)
 
     def __repr__(self):
-        return 'Objects(%r, connectivity=%d, min_area=%d, max_objects=%d, labels=%r)' % (
-            self.fractions, self.connectivity, self.min_area, self.max_objects, self.labels)
+        tail = ''
+        if self.sums:
+            tail = ', sums=True' + ('' if self.weight is None else ', weight=<%d breakpoints>' % len(self.weight[0]))
+        return 'Objects(%r, connectivity=%d, min_area=%d, max_objects=%d, labels=%r%s)' % (
+            self.fractions, self.connectivity, self.min_area, self.max_objects, self.labels, tail)
+
+
+def check_weight(weight):
+    """(table_v float32, table_f float64) of a weight table as the library takes it; ValueError for what it refuses."""
+    try:
+        tv, tf = weight
+        with np.errstate(over='ignore'):
+            tv, tf = np.ascontiguousarray(tv, dtype=np.float32), np.ascontiguousarray(tf, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('weight: (table_v, table_f), got %r' % (weight,))
+    if tv.ndim != 1 or tv.shape != tf.shape or not 2 <= tv.size <= MAX_TABLE:
+        raise ValueError('weight: two arrays of 2 ... %d breakpoints' % MAX_TABLE)
+    if not (np.isfinite(tv).all() and np.isfinite(tf).all()):
+        raise ValueError('weight: a breakpoint or a value is NaN or infinite')
+    if np.any(tv[1:] <= tv[:-1]):
+        raise ValueError('weight: the breakpoints are not strictly ascending')
+    if np.any(tf[1:] < tf[:-1]):
+        raise ValueError('weight: the values decrease')
+    return tv, tf
 
 
 def scratch_bytes(spec, blocks):
-    """The bytes of the labelling scratch of `blocks` blocks and the observation (cpol_obj.h)."""
-    return (int(blocks) + 1) * len(spec.thresholds) * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
+    """The bytes of the scratch of `blocks` blocks and the observation (cpol_obj.h): the labelling's and, with the exact sums,
+    behind it on an 8-byte boundary the accumulators and the weight table."""
+    maps = (int(blocks) + 1) * len(spec.thresholds)
+    n = maps * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
+    if getattr(spec, 'sums', False):
+        nw = 0 if spec.weight is None else len(spec.weight[0])
+        n = (n + 7) // 8 * 8 + (maps * spec.max_objects + int(blocks) + 1) * SUM_BINS * 8 + nw * 8 + (nw * 4 + 7) // 8 * 8
+    return n
+
+
+# ---------------------------------------------------------------------------------------------------- the exact sums
+def split(values):
+    """(negative bool, E int64, M int64, finite bool) of float32 values: a finite value is +-M * 2 ** (E - 150) with E = max(e, 1)
+    and M below 2 ** 24 (cpol_obj.h, obj_sum_split)."""
+    bits = np.ascontiguousarray(values, dtype=np.float32).view(_U32)
+    e = ((bits >> _U32(23)) & _U32(0xFF)).astype(_I64)
+    m = (bits & _U32(0x007FFFFF)).astype(_I64)
+    return (bits >> _U32(31)) != 0, np.maximum(e, 1), np.where(e > 0, m | 0x00800000, m), e != 0xFF
+
+
+def round_scaled(total):
+    """The float64 nearest to the Python integer `total` times 2 ** -150, ties to even, by hand: the top 53 bits, then half-to-even
+    on the remainder; +0.0 for zero (cpol_obj.h, obj_sum_round).  |total| < 2 ** 1000."""
+    total = int(total)
+    if total == 0:
+        return np.float64(0.0)
+    mag = abs(total)
+    p = mag.bit_length() - 1
+    if p <= 52:
+        mant = mag << (52 - p)
+    else:
+        r = p - 52
+        mant, rem, half = mag >> r, mag & ((1 << r) - 1), 1 << (r - 1)
+        if rem > half or (rem == half and mant & 1):
+            mant += 1                                     # (2 ** 53: the sum below carries it into the exponent)
+    bits = ((p - 150 + 1023) << 52) + (mant - (1 << 52)) | ((1 << 63) if total < 0 else 0)
+    return np.array([bits], dtype=np.uint64).view(np.float64)[0]
+
+
+def exact_sum(values, mult=None):
+    """float64: the sum of the finite float32 `values` (times the integers `mult`, 0 ... 1023, when given), formed exactly and
+    rounded once, round-to-nearest-even: math.fsum of the summands in any order.  Integer arithmetic alone."""
+    neg, E, M, finite = split(np.asarray(values, dtype=np.float32).reshape(-1))
+    if not finite.all():
+        raise ValueError('exact_sum: the values must be finite')
+    if mult is not None:
+        mult = np.asarray(mult).reshape(-1)
+        if mult.shape != M.shape or mult.dtype.kind not in 'iu' or (mult.size and (mult.min() < 0 or mult.max() > 1023)):
+            raise ValueError('exact_sum: mult: one integer in 0 ... 1023 per value')
+        M = M * mult.astype(_I64)
+    total = 0
+    for n, e, m in zip(neg.tolist(), E.tolist(), M.tolist()):
+        total += -(m << e) if n else m << e
+    return round_scaled(total)
+
+
+def weight_of(values, weight=None):
+    """float32: the summand w of float32 plane values under `weight` = (table_v, table_f) or None (w = m): float32(f(m)),
+    statement by statement what composite.column_of does per layer.  NaN stays NaN (such a cell is never summed)."""
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    if weight is None:
+        return v
+    tv, tf = weight
+    n = len(tv)
+    tv64 = tv.astype(np.float64)
+    have = v == v
+    with np.errstate(invalid='ignore', over='ignore'):
+        i = np.searchsorted(tv, np.where(have, v, tv[0]), side='right') - 1
+        ii = np.clip(i, 0, n - 2)
+        t = (v.astype(np.float64) - tv64[ii]) / (tv64[ii + 1] - tv64[ii])
+        d = tf[ii + 1] - tf[ii]
+        p = t * d
+        f = tf[ii] + p
+        f = np.where(i < 0, 0.0, np.where(i >= n - 1, tf[n - 1], f))
+        return np.where(have, f, np.nan).astype(np.float32)
+
+
+def zr_table(a=200.0, b=1.6, db_min=0.0, db_cap=60.0, step_db=0.25):
+    """The weight table of the rain rate under Z = a * R ** b (Marshall and Palmer 1948: a = 200, b = 1.6), Z in mm^6 m^-3, R in
+    mm h^-1: (float32 Z breakpoints every `step_db` from `db_min` to `db_cap` dBZ, float64 R = (Z / a) ** (1 / b) at the ROUNDED
+    breakpoints), in the manner of composite.vil_table.  Below db_min a cell adds nothing; at and above db_cap the rate stays
+    that of db_cap (the cap against hail).  The values never decrease."""
+    a, b, db_min, db_cap, step_db = float(a), float(b), float(db_min), float(db_cap), float(step_db)
+    if not (a > 0.0 and b > 0.0 and step_db > 0.0 and db_cap > db_min):
+        raise ValueError('zr_table: a > 0, b > 0, db_min < db_cap and step_db > 0')
+    n = int(round((db_cap - db_min) / step_db)) + 1
+    if not 2 <= n <= MAX_TABLE:
+        raise ValueError('zr_table: %d breakpoints; 2 ... %d' % (n, MAX_TABLE))
+    db = db_min + step_db * np.arange(n, dtype=np.float64)
+    db[-1] = db_cap
+    tv = (10.0 ** (db / 10.0)).astype(np.float32)
+    return tv, np.maximum.accumulate(np.power(tv.astype(np.float64) / a, 1.0 / b))
+
+
+def group_sums(w, ix, iy, group, n_groups):
+    """(float64 [n_groups, 3], uint32 [n_groups]): volume, moment_x and moment_y of the cells with weights `w` (float32, no NaN) at
+    (ix, iy) per group 0 ... n_groups - 1, and the cells skipped (w infinite).  The accumulator rows of cpol_obj.h in int64 -- no
+    bin can wrap: below 2 ** 20 cells, the sum of ix below 2 ** 30 -- then every row folded into ONE Python integer and rounded."""
+    neg, E, M, finite = split(w)
+    group = np.asarray(group, dtype=_I64)
+    skipped = np.bincount(group[~finite], minlength=n_groups).astype(_U32)
+    g, E, ix, iy = group[finite], E[finite], np.asarray(ix, dtype=_I64)[finite], np.asarray(iy, dtype=_I64)[finite]
+    M = np.where(neg[finite], -M[finite], M[finite])
+    acc = np.zeros((n_groups, SUM_BINS), dtype=_I64)
+    np.add.at(acc, (g, E >> 4), M << (E & 15))
+    np.add.at(acc, (g, 16 + (E >> 3)), (M * ix) << (E & 7))
+    np.add.at(acc, (g, 48 + (E >> 3)), (M * iy) << (E & 7))
+    out = np.zeros((n_groups, 3), dtype=np.float64)
+    for k, row in enumerate(acc.tolist()):
+        out[k, 0] = round_scaled(sum(v << (16 * b) for b, v in enumerate(row[:16]) if v))
+        out[k, 1] = round_scaled(sum(v << (8 * b) for b, v in enumerate(row[16:48]) if v))
+        out[k, 2] = round_scaled(sum(v << (8 * b) for b, v in enumerate(row[48:]) if v))
+    return out, skipped
+
+
+def sums_of_map(lab, n, w, max_objects):
+    """The exact sums of ONE label map: (float64 [max_objects, 3], uint32 [max_objects]) of the objects 1 ... min(n, max_objects);
+    w: the weights of the map's cells, float32."""
+    volume, skipped = np.zeros((max_objects, 3), dtype=np.float64), np.zeros(max_objects, dtype=_U32)
+    rows = min(int(n), max_objects)
+    if rows:
+        flat = np.flatnonzero((lab > 0) & (lab <= rows))
+        n_x = lab.shape[1]
+        volume[:rows], skipped[:rows] = group_sums(w.reshape(-1)[flat], flat % n_x, flat // n_x, lab.reshape(-1)[flat].astype(_I64) - 1, rows)
+    return volume, skipped
+
+
+def sums_of_field(values, w, dom):
+    """(float64 [3], uint32 [2]): the sums over every cell of the field with dom && m == m; the cells summed, the cells skipped."""
+    flat = np.flatnonzero(dom & (values == values))
+    n_x = values.shape[1]
+    s, k = group_sums(w.reshape(-1)[flat], flat % n_x, flat // n_x, np.zeros(flat.size, dtype=_I64), 1)
+    return s[0], np.array([flat.size - int(k[0]), k[0]], dtype=_U32)
 
 
 def _runs(binary):
@@ -189,22 +372,33 @@ def cells_of_map(binary, values, connectivity, min_area, max_objects):
     return _U32(n), _table(lab, n, values, max_objects), lab
 
 
-def result(spec, n_objects, table, labels=None):
+def result(spec, n_objects, table, labels=None, sums=None):
     """The output arrays named.  n_objects [n_blocks + 1, n_thr], table [n_blocks + 1, n_thr, max_objects, WORDS], labels
     [n_blocks + 1, n_thr, n_y, n_x] or None -> {'n_objects': uint32 [n_blocks, n_thr], 'first' | 'area' | 'sum_x' | 'sum_y' |
     'peak_cell': uint32 [n_blocks, n_thr, max_objects], 'bbox': uint32 [..., 4] (x0, x1, y0, y1), 'peak': float32 [...],
     'labels': int32 [n_blocks, n_thr, n_y, n_x] (when given), 'observed': the same of the observed map without the leading
-    axis, 'connectivity', 'min_area', 'thresholds'}."""
-    def named(n, tb, lb):
+    axis, 'connectivity', 'min_area', 'thresholds'}.  sums: None or the four arrays of the exact sums (volume [n_blocks + 1,
+    n_thr, max_objects, 3], skipped, field [n_blocks + 1, 3], field_cells [n_blocks + 1, 2]): 'volume' | 'moment_x' | 'moment_y':
+    float64 [n_blocks, n_thr, max_objects], 'skipped': uint32 likewise, 'field': {'volume', 'moment_x', 'moment_y': float64
+    [n_blocks], 'cells', 'skipped': uint32 [n_blocks]}, the same under 'observed', and 'weight' (the spec's table or None) and
+    'grid' (n_y, n_x) for `sal`."""
+    def named(n, tb, lb, sm=None):
         out = {'n_objects': n, 'first': tb[..., FIRST], 'area': tb[..., AREA], 'sum_x': tb[..., SUM_X], 'sum_y': tb[..., SUM_Y],
                'bbox': tb[..., X0:Y1 + 1], 'peak': tb[..., PEAK_BITS].view(np.float32),     # (views all: a pinned call fills them later)
                'peak_cell': tb[..., PEAK_CELL]}
         if lb is not None:
             out['labels'] = lb
+        if sm is not None:
+            vol, skipped, field, field_cells = sm
+            out.update(volume=vol[..., 0], moment_x=vol[..., 1], moment_y=vol[..., 2], skipped=skipped,
+                       field={'volume': field[..., 0], 'moment_x': field[..., 1], 'moment_y': field[..., 2],
+                              'cells': field_cells[..., 0], 'skipped': field_cells[..., 1]})
         return out
-    out = named(n_objects[:-1], table[:-1], None if labels is None else labels[:-1])
-    out['observed'] = named(n_objects[-1], table[-1], None if labels is None else labels[-1])
+    out = named(n_objects[:-1], table[:-1], None if labels is None else labels[:-1], None if sums is None else [q[:-1] for q in sums])
+    out['observed'] = named(n_objects[-1], table[-1], None if labels is None else labels[-1], None if sums is None else [q[-1] for q in sums])
     out.update(connectivity=spec.connectivity, min_area=spec.min_area, thresholds=spec.thresholds)
+    if sums is not None:
+        out.update(weight=spec.weight, grid=(int(spec.n_y), int(spec.n_x)))
     return out
 
 
@@ -231,17 +425,29 @@ def cells(spec, plane_maps, observed, domain=None):
     """The rule in NumPy.  spec: an Objects (or any object with its attributes whose `fractions` has `thresholds`, `n_y` and
     `n_x`); plane_maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]: one block), the scored plane as a composite's finish
     returns it; observed, domain: see neighbourhood.check_maps.  Returns what `result` describes -- exactly what the device
-    returns ('labels' only with spec.labels)."""
+    returns ('labels' only with spec.labels; the keys of the exact sums only with spec.sums)."""
     F, O, m, o = binary_maps(spec.fractions, plane_maps, observed, domain)
     n_blocks, n_thr = F.shape[:2]
+    with_sums = getattr(spec, 'sums', False)
+    if with_sums:
+        volume = np.zeros((n_blocks + 1, n_thr, spec.max_objects, 3), dtype=np.float64)
+        skipped = np.zeros((n_blocks + 1, n_thr, spec.max_objects), dtype=_U32)
+        field, field_cells = np.zeros((n_blocks + 1, 3), dtype=np.float64), np.zeros((n_blocks + 1, 2), dtype=_U32)
+        dom = np.ones(o.shape, dtype=bool) if domain is None else NB.check_maps(spec.fractions, observed, domain)[1] != 0
     n = np.zeros((n_blocks + 1, n_thr), dtype=_U32)
     table = np.zeros((n_blocks + 1, n_thr, spec.max_objects, WORDS), dtype=_U32)
     labels = np.zeros((n_blocks + 1, n_thr) + o.shape, dtype=np.int32)
     for s in range(n_blocks + 1):
+        if with_sums:
+            values = m[s] if s < n_blocks else o
+            w = weight_of(values, spec.weight)
+            field[s], field_cells[s] = sums_of_field(values, w, dom)
         for t in range(n_thr):
             binary, values = (F[s, t], m[s]) if s < n_blocks else (O[t], o)
             n[s, t], table[s, t], labels[s, t] = cells_of_map(binary, values, spec.connectivity, spec.min_area, spec.max_objects)
-    return result(spec, n, table, labels if spec.labels else None)
+            if with_sums:
+                volume[s, t], skipped[s, t] = sums_of_map(labels[s, t], n[s, t], w, spec.max_objects)
+    return result(spec, n, table, labels if spec.labels else None, (volume, skipped, field, field_cells) if with_sums else None)
 
 
 def centroids(res):
@@ -251,6 +457,68 @@ def centroids(res):
     with np.errstate(invalid='ignore', divide='ignore'):
         c = np.stack([res['sum_x'] / area + 0.5, res['sum_y'] / area + 0.5], axis=-1)
     return np.where((area > 0)[..., None], c, np.nan)
+
+
+def weighted_centroids(res):
+    """float64 [..., max_objects, 2] (x, y): the centroids of the objects weighted with w, moment / volume plus the half cell, in
+    GRID coordinates; NaN where the volume is 0 or there is no object.  `res`: a result with the exact sums, or its 'observed'."""
+    vol = res['volume']
+    with np.errstate(invalid='ignore', divide='ignore'):
+        c = np.stack([res['moment_x'] / vol + 0.5, res['moment_y'] / vol + 0.5], axis=-1)
+    return np.where(((res['area'] > 0) & (vol != 0))[..., None], c, np.nan)
+
+
+def _sal_side(side, t, n_max, weight):
+    """Of one side and threshold index t: the field mean D, the field centre (x, y), the summed object volume R, the
+    volume-weighted distance r of the object centroids to the field centre, the scaled volume V; leading axes kept."""
+    fld = side['field']
+    fv = fld['volume']
+    with np.errstate(invalid='ignore', divide='ignore'):
+        D = np.where(fld['cells'] > 0, fv / fld['cells'], np.nan)
+        fx, fy = np.where(fv != 0, fld['moment_x'] / fv, np.nan), np.where(fv != 0, fld['moment_y'] / fv, np.nan)
+        vol = side['volume'][..., t, :]
+        have = side['area'][..., t, :] > 0
+        cx = np.where(have, side['moment_x'][..., t, :] / vol, 0.0)
+        cy = np.where(have, side['moment_y'][..., t, :] / vol, 0.0)
+        dx, dy = cx - fx[..., None], cy - fy[..., None]
+        R = np.where(have, vol, 0.0).sum(axis=-1)
+        r = np.where(have, vol * np.sqrt(dx * dx + dy * dy), 0.0).sum(axis=-1) / R
+        peak = weight_of(side['peak'][..., t, :], weight).astype(np.float64)
+        V = np.where(have, vol * (vol / peak), 0.0).sum(axis=-1) / R
+    bad = (side['n_objects'][..., t] < 1) | (side['n_objects'][..., t] > n_max) | ~(R != 0)
+    return D, fx, fy, np.where(bad, np.nan, r), np.where(bad, np.nan, V)
+
+
+def sal(res, threshold=0, d=None):
+    """SAL (Wernli, Paulat, Hagen and Frei 2008, "SAL -- a novel quality measure for the verification of quantitative precipitation
+    forecasts", Mon. Wea. Rev. 136, 4470-4487) of every block against the observed map from a result with the exact sums, for the
+    objects of threshold index `threshold`: {'S', 'A', 'L', 'L1', 'L2'}, float64 [n_blocks].
+      A   = (D_f - D_o) / (0.5 * (D_f + D_o)),  D = the field volume over the field's summed cells;
+      L1  = |x_f - x_o| / d,  x = the field's centre of mass (moment / volume), d the largest distance in the domain: by default
+            the grid's diagonal in cells;
+      L2  = 2 * |r_f - r_o| / d,  r = sum R_n |x - x_n| / sum R_n over the objects, R_n the volume and x_n the weighted centroid;
+      S   = (V_f - V_o) / (0.5 * (V_f + V_o)),  V = sum R_n * (R_n / w(peak_n)) / sum R_n;  L = L1 + L2.
+    NaN where a side has no object or no volume; where a side has more objects than table rows the entries that need the objects
+    (S, L2, L) are NaN rather than silently partial."""
+    if 'volume' not in res:
+        raise ValueError('sal: the result has no exact sums (Objects(sums=True))')
+    t = int(threshold)
+    if not 0 <= t < len(res['thresholds']):
+        raise ValueError('sal: threshold index outside 0 ... %d' % (len(res['thresholds']) - 1))
+    n_y, n_x = res['grid']
+    d = float(np.sqrt(np.float64(n_x * n_x + n_y * n_y))) if d is None else float(d)
+    if not d > 0.0:
+        raise ValueError('sal: d must be positive')
+    n_max = res['volume'].shape[-1]
+    Df, xf, yf, rf, Vf = _sal_side(res, t, n_max, res['weight'])
+    Do, xo, yo, ro, Vo = _sal_side(res['observed'], t, n_max, res['weight'])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        A = (Df - Do) / (0.5 * (Df + Do))
+        dx, dy = xf - xo, yf - yo
+        L1 = np.sqrt(dx * dx + dy * dy) / d
+        L2 = 2.0 * np.abs(rf - ro) / d
+        S = (Vf - Vo) / (0.5 * (Vf + Vo))
+    return {'S': S, 'A': A, 'L': L1 + L2, 'L1': L1, 'L2': L2}
 
 
 def size_distribution(res, edges):
@@ -275,7 +543,8 @@ class Cells(object):
     name = 'composite'
     spectrum, model_var = True, None
     refuses = NB.Scores.refuses
-    _OWN = ('n_objects', 'table', 'labels')
+    _OWN = ('n_objects', 'table', 'labels', 'volume', 'skipped', 'field', 'field_cells')
+    _SUMS = _OWN[3:]
 
     def __init__(self, spec, observed=None, domain=None, keep_gates=False, phase=3, rays_per_block=0, distributed=False):
         if not isinstance(spec, Objects):
@@ -298,7 +567,8 @@ class Cells(object):
             return structs, keep
         self.n_blocks = self.scores.n_blocks
         if scratch_bytes(self.spec, self.n_blocks) > MAX_SCRATCH_BYTES:
-            raise ValueError('objects: the labelling scratch of %d blocks needs more than 1 GiB' % self.n_blocks)
+            raise ValueError('objects: the labelling scratch of %d blocks needs more than 1 GiB' % self.n_blocks if not self.spec.sums else
+                             'objects: the labelling scratch and the sums of %d blocks need more than 1 GiB' % self.n_blocks)
         self.o, okeep = native.Context.objects_struct(self.spec, self.scores.f)
         return structs, keep + okeep
 
@@ -311,6 +581,10 @@ class Cells(object):
                          ('table', np.uint32, (self.n_blocks + 1, nt, spec.max_objects, WORDS))]
             if spec.labels:
                 out.append(('labels', np.int32, (self.n_blocks + 1, nt, spec.n_y, spec.n_x)))
+            if spec.sums:
+                out += [('volume', np.float64, (self.n_blocks + 1, nt, spec.max_objects, 3)),
+                        ('skipped', np.uint32, (self.n_blocks + 1, nt, spec.max_objects)),
+                        ('field', np.float64, (self.n_blocks + 1, 3)), ('field_cells', np.uint32, (self.n_blocks + 1, 2))]
         return out
 
     def bind(self, path, address):
@@ -320,7 +594,7 @@ class Cells(object):
             self.scores.bind(path, address)
 
     def bind_device(self, entry):
-        # the scores' entries and 'n_objects' | 'table' | 'labels': device pointers
+        # the scores' entries and 'n_objects' | 'table' | 'labels' | 'volume' | 'skipped' | 'field' | 'field_cells': device pointers
         rest = {}
         for k, ptr in entry.items():
             if k in self._OWN and self.phase & 2:
@@ -332,8 +606,9 @@ class Cells(object):
     def finish(self, w, coords):
         n, table = w.pop('n_objects'), w.pop('table')
         labels = w.pop('labels') if self.spec.labels else None
+        sums = [w.pop(k) for k in self._SUMS] if self.spec.sums else None
         out = self.scores.finish(w, coords)
-        out['objects'] = result(self.spec, n, table, labels)
+        out['objects'] = result(self.spec, n, table, labels, sums)
         return out
 
     def join(self, parts, cat):
@@ -342,6 +617,8 @@ class Cells(object):
         out = self.scores.join(parts, cat)
         if self.rays_per_block:
             ob = [w['objects'] for w in parts]
-            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds')]
+            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds', 'weight', 'grid', 'field')]
             out['objects'] = dict(ob[-1], **{k: cat([q[k] for q in ob]) for k in stacked})
+            if 'field' in ob[-1]:
+                out['objects']['field'] = {k: cat([q['field'][k] for q in ob]) for k in ob[-1]['field']}
         return out

@@ -726,7 +726,7 @@ typedef struct cpol_composite {
  * NO OVERFLOW (a condition, not a measurement): at most 1023 x 1023 cells, so an area is < 2^20, a sum of ix or iy is
  * < 2^20 * 2^10 = 2^30, every index < 2^20: all fit uint32.  Every attribute is a count, an integer sum, an integer extreme or a
  * comparison: the result does not depend on the order in which the hardware works.  Float sums over an object's cells (rain
- * volume, weighted centroids) are not built; the label map is delivered so that the host can form them.
+ * volume, weighted centroids) are EXACT SUMS, below: they do not depend on that order either.
  * OUTPUTS: n_objects uint32 [n_blocks + 1][n_thresholds]: the TRUE number of kept objects, also beyond max_objects; table uint32
  * [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS], 8-byte aligned: row k - 1 belongs to object k, rows at or beyond
  * n_objects are zero, objects beyond max_objects have no row; labels int32 [n_blocks + 1][n_thresholds][n_y][n_x] or NULL: the
@@ -736,7 +736,39 @@ typedef struct cpol_composite {
  * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: connectivity other than 4 or 8; min_area < 1;
  * max_objects outside 1 ... 65535; NULL n_objects or table; a table that is not 8-byte aligned; the limit exceeded.
  * Kernels (k_obj_*, cpol_obj.inl) run behind k_frac_score: a label-equivalence union-find (L[i] <= i always, a union is an
- * atomic minimum).  No kernel waits on another workgroup; every loop carries a strictly decreasing unsigned integer. */
+ * atomic minimum).  No kernel waits on another workgroup; every loop carries a strictly decreasing unsigned integer.
+ *
+ * EXACT SUMS (`sums` = 1; the tail of the struct, a zero tail means off and a call without it queues exactly what it queued
+ * before): the rain volume and the weighted first moments of every object and of the whole field, for SAL (Wernli et al. 2008)
+ * and every weighted centroid.  cosmo_pol_amd/objects.py states the same rule (`exact_sum`, `weight_of`, `cells`).
+ * SUMMAND: for a cell with plane value m (o for the observed map) the summand is w = m.  With a weight table (weight_v float32
+ * strictly ascending, weight_f float64, n_weight breakpoints) it is w = float32(f(m)), f the piecewise-linear function that the
+ * column of the height layers evaluates (composite.column_of), statement by statement: j = #{ weight_v <= m } - 1 (searchsorted
+ * 'right' - 1, float32 comparisons); t = (m - v_j) / (v_j+1 - v_j), d = f_j+1 - f_j, p = t * d, f_j + p, each ONE float64
+ * operation; 0 below the table, weight_f[n - 1] at and above its end; then ONE rounding to float32.  weight_f must be finite and
+ * non-decreasing, so that the peak of w over an object is w(peak).
+ * SKIPPED CELLS: a cell whose w is +-inf is not summed; it is counted in `skipped`.  NaN cells are never set.
+ * PER KEPT OBJECT WITH A TABLE ROW: volume = sum w, moment_x = sum w * ix, moment_y = sum w * iy over its cells, each sum formed
+ * EXACTLY and rounded ONCE to float64, round-to-nearest-even; an exact zero is +0.0; `skipped` uint32.  A float32 is an integer
+ * multiple of 2^-149 and a product w * ix is exact (24 + 10 bits), so every sum is a sum of integers: it does not depend on the
+ * order of the additions, and the float64 is math.fsum of the summands.
+ * PER SOURCE, independent of the thresholds: the same three sums over every cell with domain && m == m (the whole field: SAL's
+ * amplitude and first location term), and field_cells uint32 [2] = the cells summed, the cells skipped.
+ * ACCUMULATORS (conditions, not measurements; cpol_obj.h): with the bits of w as +-M * 2^(E - 150), E = max(e, 1), M < 2^24,
+ * sixteen signed 64-bit bins of the volume (bin E >> 4 takes +-M << (E & 15) < 2^39; fewer than 2^20 cells: |bin| < 2^59) and
+ * thirty-two of each moment (bin E >> 3 takes +-(M * ix) << (E & 7); the sum of ix is < 2^30 by NO OVERFLOW above: |bin| <
+ * 2^61), added with integer atomics, then propagated into one 384-bit integer and rounded by hand: the top 53 bits, the guard bit
+ * and the sticky rest.
+ * OUTPUTS: volume float64 [n_blocks + 1][n_thresholds][max_objects][3] (volume, moment_x, moment_y), 8-byte aligned, rows at or
+ * beyond n_objects zero; skipped uint32 [n_blocks + 1][n_thresholds][max_objects]; field float64 [n_blocks + 1][3], 8-byte
+ * aligned; field_cells uint32 [n_blocks + 1][2].  The four follow p->outputs_on_device like `table`.
+ * LIMITS: the labelling scratch plus the accumulators, (16 + 32 + 32) * 8 bytes per table row and per source, plus the weight
+ * table, at most 1 GiB.
+ * CPOL_ERR_ARG as above: sums other than 0 or 1; a NULL output with sums on; volume or field not 8-byte aligned; n_weight
+ * other than 0 or 2 ... 1024; NULL weight_v or weight_f; a breakpoint or value that is NaN or infinite; breakpoints not strictly
+ * ascending; values that decrease; the limit exceeded.
+ * Two kernels behind k_obj_decode: k_obj_sums (a wavefront per source and row; equal (object, bin) keys are combined inside the
+ * wavefront before ONE atomic) and k_obj_sums_finish (a thread per sum: the rounding). */
 #define CPOL_OBJ_WORDS 10
 #define CPOL_OBJ_MAX_OBJECTS 65535
 typedef struct cpol_objects {
@@ -747,6 +779,15 @@ typedef struct cpol_objects {
     uint32_t *n_objects;        /* [n_blocks + 1][n_thresholds]                                                    */
     uint32_t *table;            /* [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS]                       */
     int32_t  *labels;           /* [n_blocks + 1][n_thresholds][n_y][n_x] or NULL = not wanted                     */
+    /* the exact sums: a zero-initialised tail means off */
+    int32_t  sums;              /* 0 or 1                                                                          */
+    int32_t  n_weight;          /* 0: w = m; else 2 ... CPOL_COMP_MAX_TABLE breakpoints of the weight table        */
+    const float  *weight_v;     /* [n_weight] breakpoints in the plane's units, strictly ascending                 */
+    const double *weight_f;     /* [n_weight] values at the breakpoints, finite and non-decreasing                 */
+    double   *volume;           /* [n_blocks + 1][n_thresholds][max_objects][3]: volume, moment_x, moment_y         */
+    uint32_t *skipped;          /* [n_blocks + 1][n_thresholds][max_objects]                                       */
+    double   *field;            /* [n_blocks + 1][3]: the same sums over the whole field of every source           */
+    uint32_t *field_cells;      /* [n_blocks + 1][2]: cells summed, cells skipped                                   */
 } cpol_objects;
 
 typedef struct cpol_fractions {
