@@ -181,6 +181,12 @@ class Objects(C.Structure):
                 ('volume', C.c_void_p), ('skipped', C.c_void_p), ('field', C.c_void_p), ('field_cells', C.c_void_p)]
 
 
+class ObjectsMatch(C.Structure):
+    """cpol_objects_match: a cpol_objects whose pad_ holds max_pieces, and behind it the outputs of the match (objects.py, MATCH).
+    cpol_fractions.objects points at `o`; the library reads beyond it only when o.pad_ != 0."""
+    _fields_ = [('o', Objects), ('n_pieces', C.c_void_p), ('pieces', C.c_void_p), ('covered', C.c_void_p)]
+
+
 class Fractions(C.Structure):
     """cpol_fractions: the fractions skill score's sums of one finished plane of a composite against an observed map
     (cosmo_pol_amd/neighbourhood.py states the rule).  objects: NULL (a zero-initialised struct) = no object cells."""
@@ -1226,11 +1232,19 @@ class Context(object):
     @staticmethod
     def objects_struct(spec, fractions):
         """(Objects for a call under `spec` (an objects.Objects), hung on `fractions` (the call's Fractions); what must stay alive):
-        the output pointers are the caller's."""
-        o = Objects()
+        the output pointers are the caller's.  With spec.match the Objects is the first member of an ObjectsMatch, which is the
+        first of what must stay alive and takes n_pieces, pieces and covered."""
+        if getattr(spec, 'match', False):
+            om = ObjectsMatch()
+            o = om.o                                  # (shares om's memory)
+            o.pad_ = spec.max_pieces
+            fractions.objects = C.cast(C.pointer(om), C.POINTER(Objects))
+            keep = [om]
+        else:
+            o = Objects()
+            fractions.objects = C.pointer(o)
+            keep = [o]
         o.connectivity, o.min_area, o.max_objects = spec.connectivity, spec.min_area, spec.max_objects
-        fractions.objects = C.pointer(o)
-        keep = [o]
         if getattr(spec, 'sums', False):
             o.sums = 1
             if spec.weight is not None:
@@ -1245,8 +1259,8 @@ class Context(object):
         [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
         and `radii` (the maps need not be those of spec.composite's grid).  `tamper(f)`: changes the cpol_fractions before the call
         (the refusal tests).  `objects`: an objects.Objects or any object with `connectivity`, `min_area`, `max_objects` and
-        `labels` (and `sums` with `weight` for the exact sums): the kernels of cpol_obj.inl run too, and the result is (the sums,
-        what objects.cells returns for the maps);
+        `labels` (and `sums` with `weight` for the exact sums, `match` with `max_pieces` for the match): the kernels of
+        cpol_obj.inl run too, and the result is (the sums, what objects.cells returns for the maps);
         `tamper` then finds the cpol_objects at f.objects.contents."""
         from . import neighbourhood as NB
 
@@ -1296,6 +1310,12 @@ class Context(object):
                          np.full((m.shape[0] + 1, nt, objects.max_objects), 0xDEADBEEF, dtype=np.uint32),
                          np.full((m.shape[0] + 1, 3), np.nan, dtype=np.float64), np.full((m.shape[0] + 1, 2), 0xDEADBEEF, dtype=np.uint32)]
                 o.volume, o.skipped, o.field, o.field_cells = [q.ctypes.data for q in osums]
+            omatch = None
+            if getattr(objects, 'match', False):
+                omatch = [np.full((m.shape[0], nt), 0xDEADBEEF, dtype=np.uint32),
+                          np.full((m.shape[0], nt, objects.max_pieces, OBJ_WORDS), 0xDEADBEEF, dtype=np.uint32),
+                          np.full((m.shape[0], nt, 2, objects.max_objects), 0xDEADBEEF, dtype=np.uint32)]
+                okeep[0].n_pieces, okeep[0].pieces, okeep[0].covered = [q.ctypes.data for q in omatch]
             keep += okeep
         hk.f = f
         if tamper is not None:
@@ -1304,7 +1324,7 @@ class Context(object):
         self._check(rc, 'cpol_debug_read(fractions_maps)')
         del keep
         if objects is not None:
-            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums)
+            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums, omatch)
         return NB.result(spec, s, t)
 
     @staticmethod

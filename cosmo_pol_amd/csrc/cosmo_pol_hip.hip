@@ -219,11 +219,12 @@ struct cpol_ctx {
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand
-    DevBuf b_fsat, b_fobs, b_fout[9], b_fmaps;
+    DevBuf b_fsat, b_fobs, b_fout[12], b_fmaps;
     FracPlan fplan;
     // object cells (cpol_objects, beside a cpol_fractions): the labelling scratch and the plan of the call at hand; n_objects, table
     // and labels are b_fout[2 ... 4], volume, skipped, field and field_cells of the exact sums b_fout[5 ... 8]; the sums'
-    // accumulators and the weight table lie behind the labelling scratch (ObjPlan)
+    // accumulators and the weight table lie behind the labelling scratch (ObjPlan); n_pieces, pieces and covered of the match
+    // b_fout[9 ... 11], the piece scratch behind everything else
     DevBuf b_oscr;
     ObjPlan oplan;
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
@@ -2867,8 +2868,9 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
 
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
 // (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
-enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_OBJ_VOLUME, FR_OBJ_SKIPPED, FR_OBJ_FIELD, FR_OBJ_FIELD_CELLS, FR_N };
-static_assert(FR_N == 9, "cpol_ctx::b_fout holds one buffer per array");
+enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_OBJ_VOLUME, FR_OBJ_SKIPPED, FR_OBJ_FIELD, FR_OBJ_FIELD_CELLS,
+       FR_OBJ_N_PIECES, FR_OBJ_PIECES, FR_OBJ_COVERED, FR_N };
+static_assert(FR_N == 12, "cpol_ctx::b_fout holds one buffer per array");
 // arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
 // composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for)
 static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, PlaceArray *arr)
@@ -2882,11 +2884,78 @@ static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPla
     arr[FR_OBJ_N].user = (uintptr_t)o->n_objects;    arr[FR_OBJ_N].bytes = op.n_bytes;           arr[FR_OBJ_N].produced = true;
     arr[FR_OBJ_TABLE].user = (uintptr_t)o->table;    arr[FR_OBJ_TABLE].bytes = op.table_bytes;   arr[FR_OBJ_TABLE].produced = true;
     arr[FR_OBJ_LABELS].user = (uintptr_t)o->labels;  arr[FR_OBJ_LABELS].bytes = op.labels_bytes; arr[FR_OBJ_LABELS].produced = op.labels;
+    if (op.match) {
+        const cpol_objects_match *const mo = (const cpol_objects_match *)o;       // (o->pad_ != 0: obj_check)
+        arr[FR_OBJ_N_PIECES].user = (uintptr_t)mo->n_pieces;  arr[FR_OBJ_N_PIECES].bytes = op.n_pieces_bytes;  arr[FR_OBJ_N_PIECES].produced = true;
+        arr[FR_OBJ_PIECES].user = (uintptr_t)mo->pieces;      arr[FR_OBJ_PIECES].bytes = op.pieces_bytes;      arr[FR_OBJ_PIECES].produced = true;
+        arr[FR_OBJ_COVERED].user = (uintptr_t)mo->covered;    arr[FR_OBJ_COVERED].bytes = op.covered_bytes;    arr[FR_OBJ_COVERED].produced = true;
+    }
     if (!op.sums) return;
     arr[FR_OBJ_VOLUME].user = (uintptr_t)o->volume;            arr[FR_OBJ_VOLUME].bytes = op.volume_bytes;           arr[FR_OBJ_VOLUME].produced = true;
     arr[FR_OBJ_SKIPPED].user = (uintptr_t)o->skipped;          arr[FR_OBJ_SKIPPED].bytes = op.skipped_bytes;         arr[FR_OBJ_SKIPPED].produced = true;
     arr[FR_OBJ_FIELD].user = (uintptr_t)o->field;              arr[FR_OBJ_FIELD].bytes = op.field_bytes;             arr[FR_OBJ_FIELD].produced = true;
     arr[FR_OBJ_FIELD_CELLS].user = (uintptr_t)o->field_cells;  arr[FR_OBJ_FIELD_CELLS].bytes = op.field_cells_bytes; arr[FR_OBJ_FIELD_CELLS].produced = true;
+}
+
+// the exact sums behind k_obj_decode; a: the arguments of the object kernels (its sums' members are filled here)
+static int obj_launch_sums(cpol_ctx *ctx, ObjArgs a, const ObjPlan &op, void *const T[FR_N], hipStream_t st)
+{
+    const dim3 rows((unsigned)op.grid_rows), thr(OBJ_THREADS);
+    // the exact sums: the accumulators behind the labelling scratch cleared, the weight table behind them
+    char *const scr = (char *)ctx->b_oscr.p;
+    a.acc = (unsigned long long *)(scr + op.acc_offset);
+    a.volume = (double *)T[FR_OBJ_VOLUME]; a.skipped = (unsigned *)T[FR_OBJ_SKIPPED];
+    a.field = (double *)T[FR_OBJ_FIELD]; a.field_cells = (unsigned *)T[FR_OBJ_FIELD_CELLS];
+    const size_t nw = op.weight_v.size();
+    a.n_weight = (int)nw;
+    if (nw) {
+        a.wf = (const double *)(scr + op.weight_offset); a.wv = (const float *)(a.wf + nw);
+        for (a.step_w = 1; 2 * a.step_w <= (int)nw; a.step_w *= 2) {}
+        HIPCHK(hipMemcpyAsync((void *)a.wf, op.weight_f.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync((void *)a.wv, op.weight_v.data(), nw * sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)op.acc_bytes, st));
+    HIPCHK(hipMemsetAsync(a.skipped, 0, op.skipped_bytes, st));
+    HIPCHK(hipMemsetAsync(a.field_cells, 0, op.field_cells_bytes, st));
+    hipLaunchKernelGGL(k_obj_sums, rows, thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_sums_finish, dim3((unsigned)op.grid_finish), thr, 0, st, a);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
+}
+
+// the match behind everything else: the piece arrays of the scratch through the objects' own kernels (cpol_obj.inl); a: the
+// arguments of the object kernels, whose L and aux k_obj_number left flattened and numbered
+static int obj_launch_match(cpol_ctx *ctx, const ObjArgs &a, const ObjPlan &op, void *const T[FR_N], hipStream_t st)
+{
+    MatchArgs g{};
+    g.L = a.L; g.aux = a.aux; g.max_objects = op.max_objects;
+    g.covered = (unsigned *)T[FR_OBJ_COVERED];
+    g.p.f = a.f;
+    g.p.L = (unsigned *)((char *)ctx->b_oscr.p + op.piece_offset); g.p.aux = g.p.L + op.piece_maps * op.cells; g.p.rowcnt = g.p.aux + op.piece_maps * op.cells;
+    g.p.n_objects = (unsigned *)T[FR_OBJ_N_PIECES]; g.p.table = (unsigned *)T[FR_OBJ_PIECES];
+    g.p.n_maps = op.piece_maps;
+    g.p.connectivity = op.connectivity; g.p.min_area = 1; g.p.max_objects = op.max_pieces;
+    HIPCHK(hipMemsetAsync(T[FR_OBJ_PIECES], 0, op.pieces_bytes, st));
+    HIPCHK(hipMemsetAsync(T[FR_OBJ_COVERED], 0, op.covered_bytes, st));
+    const dim3 rows((unsigned)op.grid_piece_rows), thr(OBJ_THREADS);
+    hipLaunchKernelGGL(k_match_runs, rows, thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_merge, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_flatten, dim3((unsigned)op.grid_piece_cells), thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_area, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_count, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_number, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_match_attr, rows, thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_match_decode, dim3((unsigned)op.grid_piece_decode), thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
 }
 
 // the kernels of cpol_obj.inl behind k_frac_score on `st`; fa: the maps as frac_launch resolved them
@@ -2917,28 +2986,11 @@ static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, con
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_obj_decode, dim3((unsigned)op.grid_decode), thr, 0, st, a);
     HIPCHK(hipGetLastError());
-    if (!op.sums) return CPOL_OK;
-    // the exact sums: the accumulators behind the labelling scratch cleared, the weight table behind them
-    char *const scr = (char *)ctx->b_oscr.p;
-    a.acc = (unsigned long long *)(scr + op.acc_offset);
-    a.volume = (double *)T[FR_OBJ_VOLUME]; a.skipped = (unsigned *)T[FR_OBJ_SKIPPED];
-    a.field = (double *)T[FR_OBJ_FIELD]; a.field_cells = (unsigned *)T[FR_OBJ_FIELD_CELLS];
-    const size_t nw = op.weight_v.size();
-    a.n_weight = (int)nw;
-    if (nw) {
-        a.wf = (const double *)(scr + op.weight_offset); a.wv = (const float *)(a.wf + nw);
-        for (a.step_w = 1; 2 * a.step_w <= (int)nw; a.step_w *= 2) {}
-        HIPCHK(hipMemcpyAsync((void *)a.wf, op.weight_f.data(), nw * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync((void *)a.wv, op.weight_v.data(), nw * sizeof(float), hipMemcpyHostToDevice, st));
+    if (op.sums) {
+        const int rc = obj_launch_sums(ctx, a, op, T, st);
+        if (rc != CPOL_OK) return rc;
     }
-    HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)op.acc_bytes, st));
-    HIPCHK(hipMemsetAsync(a.skipped, 0, op.skipped_bytes, st));
-    HIPCHK(hipMemsetAsync(a.field_cells, 0, op.field_cells_bytes, st));
-    hipLaunchKernelGGL(k_obj_sums, rows, thr, 0, st, a);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_obj_sums_finish, dim3((unsigned)op.grid_finish), thr, 0, st, a);
-    HIPCHK(hipGetLastError());
-    return CPOL_OK;
+    return op.match ? obj_launch_match(ctx, a, op, T, st) : CPOL_OK;
 }
 
 // plane: block 0's plane on the device; obs_on_host: `observed` and `domain` are host arrays (copied to b_fobs on `st` first),

@@ -3,7 +3,9 @@
 // from the ballot of its flags, find, union and the rule that says which cell unites with which cell of the row above.  Plain C++
 // that compiles for the host too (tests/c_host/obj_check.cpp drives the same functions single-threaded and compares with the
 // rule), so that a merge bug shows as a wrong label on the host, not as a hang on the device.  The kernels are k_obj_*
-// (cpol_obj.inl); the rule is stated in include/cosmo_pol_amd.h and cosmo_pol_amd/objects.py.
+// (cpol_obj.inl); the rule is stated in include/cosmo_pol_amd.h and cosmo_pol_amd/objects.py.  The match (cpol_objects_match)
+// runs the same run, union and find code on the overlap map of two label maps: its checks, sizes and per-cell functions are
+// here too (obj_check_match, obj_match_flag, obj_match_cover; tests/c_host/obj_match_check.cpp).
 //
 // THE LABEL ARRAY.  L[i] of a set cell i is the flat index of a cell of the same object with L[i] <= i; L[i] == i makes i a root;
 // an unset cell holds OBJ_NONE.  It starts as the first cell of the cell's row run (no atomic for horizontal connectivity).  A
@@ -54,14 +56,33 @@ struct ObjPlan {
     size_t volume_bytes = 0, skipped_bytes = 0, field_bytes = 0, field_cells_bytes = 0;
     std::vector<float> weight_v;                      // empty: w = m
     std::vector<double> weight_f;
+    // the match (cpol_objects_match): the overlap pieces of every block's label map and the observed one.  piece_maps = n_blocks *
+    // n_thr: piece map (b * n_thr + t).  The piece scratch, uint32: L, aux and rowcnt as above of piece_maps maps, behind everything
+    // above on an 8-byte boundary (what lies before it does not move)
+    bool match = false;
+    int max_pieces = 0;
+    long piece_maps = 0, piece_offset = 0, piece_bytes = 0;
+    long grid_piece_rows = 0, grid_piece_cells = 0, grid_piece_decode = 0;   // as grid_rows, grid_cells and grid_decode, of the piece maps
+    size_t n_pieces_bytes = 0, pieces_bytes = 0, covered_bytes = 0;
 };
 
+// the two halves of obj_check: the cells with the exact sums, then the match behind them
+inline const char *obj_check_cells(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl);
+inline const char *obj_check_match(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl);
+
 // every refusal of a cpol_objects beside a cpol_fractions whose plan `fp` passed; o == NULL: off (*pl says so).  NULL: accepted
-// and *pl filled; else the reason (CPOL_ERR_ARG).  Touches nothing else.
+// and *pl filled; else the reason (CPOL_ERR_ARG).  Touches nothing else.  o->pad_ != 0: *o is the first member of a
+// cpol_objects_match, and only then is anything behind the cpol_objects read.
 inline const char *obj_check(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
 {
     *pl = ObjPlan{};
     if (!o) return nullptr;
+    if (const char *why = obj_check_cells(o, fp, pl)) return why;
+    return obj_check_match(o, fp, pl);
+}
+
+inline const char *obj_check_cells(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
+{
     if (o->connectivity != 4 && o->connectivity != 8) return "connectivity must be 4 or 8";
     if (o->min_area < 1) return "min_area must be at least 1";
     if (o->max_objects < 1 || o->max_objects > OBJ_MAX_OBJECTS) return "max_objects must lie in 1 ... 65535";
@@ -111,6 +132,28 @@ inline const char *obj_check(const cpol_objects *o, const FracPlan &fp, ObjPlan 
     pl->skipped_bytes = (size_t)pl->n_maps * pl->max_objects * sizeof(uint32_t);
     pl->field_bytes = (size_t)pl->n_sources * 3 * sizeof(double);
     pl->field_cells_bytes = (size_t)pl->n_sources * 2 * sizeof(uint32_t);
+    return nullptr;
+}
+
+inline const char *obj_check_match(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
+{
+    if (o->pad_ < 0 || o->pad_ > OBJ_MAX_OBJECTS) return "pad_ (max_pieces of a cpol_objects_match) must lie in 0 ... 65535";
+    if (!o->pad_) return nullptr;
+    const cpol_objects_match *const mo = (const cpol_objects_match *)o;
+    if (!mo->n_pieces || !mo->pieces || !mo->covered) return "n_pieces, pieces or covered is NULL";
+    pl->match = true; pl->max_pieces = o->pad_;
+    pl->piece_maps = (long)fp.n_blocks * fp.n_thr;
+    pl->piece_offset = (pl->scratch_bytes + 7) & ~7L;
+    pl->piece_bytes = pl->piece_maps * (2 * pl->cells + fp.n_y) * 4;
+    pl->scratch_bytes = pl->piece_offset + pl->piece_bytes;
+    if (pl->scratch_bytes > OBJ_MAX_SCRATCH_BYTES) return "the labelling scratch, the sums' accumulators and the piece scratch must be at most 1 GiB";
+    pl->grid_piece_rows = (long)fp.n_blocks * ((fp.n_y + OBJ_ROWS - 1) / OBJ_ROWS);
+    pl->grid_piece_cells = (pl->piece_maps * pl->cells + OBJ_THREADS - 1) / OBJ_THREADS;
+    pl->grid_piece_decode = (pl->piece_maps * pl->max_pieces + OBJ_THREADS - 1) / OBJ_THREADS;
+    if (pl->grid_piece_rows >= (1L << 31) || pl->grid_piece_cells >= (1L << 31) || pl->grid_piece_decode >= (1L << 31)) return "too many workgroups in one call";
+    pl->n_pieces_bytes = (size_t)pl->piece_maps * sizeof(uint32_t);
+    pl->pieces_bytes = (size_t)pl->piece_maps * pl->max_pieces * OBJ_WORDS * sizeof(uint32_t);
+    pl->covered_bytes = (size_t)pl->piece_maps * 2 * pl->max_objects * sizeof(uint32_t);
     return nullptr;
 }
 
@@ -205,6 +248,43 @@ OBJ_HD void obj_merge_cell(unsigned *L, int n_x, int y, int x, int connectivity)
         if (am && !bm) obj_union(L, i, j - 1u);
         if (ap && !bp) obj_union(L, i, j + 1u);
     }
+}
+
+// ---- the match (cpol_objects_match): the per-cell logic of k_match_runs.  After the object phase L is flattened (L[cell] = the
+// root) and aux[root] = the kept number or 0. ----
+
+OBJ_HD unsigned obj_atomic_add(unsigned *p, unsigned v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicAdd(p, v);
+#else
+    const unsigned old = *p;
+    *p = old + v;
+    return old;
+#endif
+}
+
+// the kept number of the cell in the label map (L, aux), 0 for background and dropped objects: what `labels` would hold
+OBJ_HD unsigned obj_number_of(const unsigned *L, const unsigned *aux, unsigned cell)
+{
+    const unsigned root = L[cell];
+    return root == OBJ_NONE ? 0u : aux[root];
+}
+
+// the overlap flag of a cell from the two (root, number) lookups: *nf its number in the block's map, *no in the observed one
+OBJ_HD bool obj_match_flag(const unsigned *Lf, const unsigned *auxf, const unsigned *Lo, const unsigned *auxo, unsigned cell, unsigned *nf, unsigned *no)
+{
+    *nf = obj_number_of(Lf, auxf, cell);
+    *no = obj_number_of(Lo, auxo, cell);
+    return *nf != 0u && *no != 0u;
+}
+
+// what the lane at which a run of I begins in a chunk adds for its segment of `len` cells: a run of I lies inside one run of each
+// map, so nf and no are constant over it.  covered: [2][max_objects] of the (block, threshold); numbers beyond max_objects have no entry
+OBJ_HD void obj_match_cover(unsigned *covered, int max_objects, unsigned nf, unsigned no, unsigned len)
+{
+    if (nf <= (unsigned)max_objects) obj_atomic_add(covered + (nf - 1u), len);
+    if (no <= (unsigned)max_objects) obj_atomic_add(covered + max_objects + (no - 1u), len);
 }
 
 // ---- the peak: the value's place in the total order of float32 (-0.0 before +0.0) above the complement of the flat index, so that

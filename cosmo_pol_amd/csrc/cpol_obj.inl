@@ -22,6 +22,16 @@
 //   k_obj_sums         the weight of a cell split ONCE into sign, exponent and integer; per threshold the cells of a chunk that share
 //                      an object and a bin are summed inside the wavefront and leave as ONE integer atomic; the field likewise;
 //   k_obj_sums_finish  a thread per sum: the bins into one integer, ONE rounding to float64 (obj_sum_round).
+// With the match (cpol_objects_match; MATCH of the header) behind all of them, on the piece arrays of the scratch (a second ObjArgs
+// whose L, aux, rowcnt, table and n_objects are the pieces', n_maps = n_blocks * n_thr, min_area 1, max_objects = max_pieces, on a
+// grid without the observed map's source):
+//   k_match_runs   a wavefront per (block, row): the overlap flag of a cell from the two (root, number) lookups in the objects' L
+//                  and aux (never the `labels` output); the piece L = the first cell of the cell's run in I, from the ballot as in
+//                  k_obj_runs; `covered` with ONE integer atomic per run segment and side;
+//   k_obj_merge, k_obj_flatten, k_obj_area, k_obj_count, k_obj_number   unchanged: they read of ObjArgs only f.row_groups, f.n_x,
+//                  f.n_y, f.n_thr, f.cells, L, aux, rowcnt, table, n_objects, n_maps, connectivity, min_area and max_objects;
+//   k_match_attr   per run segment the sums and the box as in k_obj_attr; the piece's root lane stores `forecast` and `observed`;
+//   k_match_decode a thread per piece row: x0 out of its complement, y0 from the first cell.
 
 struct ObjArgs {
     FracArgs f;                     // the maps: plane, obs, domain, the grid, the rounded thresholds
@@ -339,6 +349,89 @@ __global__ __launch_bounds__(OBJ_THREADS) void k_obj_sums_finish(const ObjArgs a
                                                : obj_sum_round(row + OBJ_SUM_VOL_BINS + (which - 1) * OBJ_SUM_MOM_BINS, OBJ_SUM_MOM_BINS, 8);
     double *const out = r < n_rows ? a.volume + r * 3 : a.field + (r - n_rows) * 3;
     out[which] = __longlong_as_double((long long)bits);
+}
+
+// ---- the match ----
+
+struct MatchArgs {
+    ObjArgs p;                      // the pieces: f as the objects', L, aux, rowcnt the piece scratch, table = pieces, n_objects = n_pieces
+    const unsigned *L, *aux;        // the objects' arrays after k_obj_number: L flattened, aux[root] = the kept number or 0
+    unsigned *covered;              // [n_blocks * n_thr][2][max_objects]: zero before k_match_runs
+    int max_objects;
+};
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_match_runs(const MatchArgs g)
+{
+    const ObjArgs &a = g.p;
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;                    // (the grid has n_blocks sources: src is a block)
+    const int n_x = a.f.n_x;
+    int carry[FRAC_MAX_THR] = {-1, -1, -1, -1};
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+#pragma unroll
+        for (int t = 0; t < FRAC_MAX_THR; ++t) {
+            if (t >= a.f.n_thr) break;
+            const long map = src * a.f.n_thr + t;
+            const long fb = map * a.f.cells, ob = ((long)a.f.n_blocks * a.f.n_thr + t) * a.f.cells;
+            unsigned nf = 0u, no = 0u;
+            const bool set = in && obj_match_flag(g.L + fb, g.aux + fb, g.L + ob, g.aux + ob, cell, &nf, &no);
+            const unsigned long long m = __ballot(set);
+            unsigned first = OBJ_NONE;
+            if (set) first = (unsigned)(y * n_x + (obj_run_open(m, lane) && carry[t] >= 0 ? carry[t] : x0 + obj_run_first(m, lane)));
+            if (in) a.L[fb + cell] = first;
+            if (set && (lane == 0 || !((m >> (lane - 1)) & 1ull)))
+                obj_match_cover(g.covered + map * 2 * g.max_objects, g.max_objects, nf, no, (unsigned)obj_run_len(m, lane));
+            carry[t] = obj_carry(m, x0, carry[t]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_match_attr(const MatchArgs g)
+{
+    const ObjArgs &a = g.p;
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;
+    const int n_x = a.f.n_x;
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+        for (int t = 0; t < a.f.n_thr; ++t) {
+            OBJ_CHUNK(t);
+            const unsigned number = set ? a.aux[base + root] : 0u;
+            if (!set || number == 0u || number > (unsigned)a.max_objects) continue;
+            unsigned *const row = a.table + ((src * a.f.n_thr + t) * a.max_objects + (number - 1u)) * OBJ_WORDS;
+            if (root == cell) {                               // (one lane per piece: plain stores)
+                const long ob = ((long)a.f.n_blocks * a.f.n_thr + t) * a.f.cells;
+                row[OBJ_PEAK_CELL] = obj_number_of(g.L + base, g.aux + base, cell);
+                row[OBJ_PEAK_BITS] = obj_number_of(g.L + ob, g.aux + ob, cell);
+            }
+            if (lane != 0 && ((m >> (lane - 1)) & 1ull)) continue;
+            const unsigned n = (unsigned)obj_run_len(m, lane), ux = (unsigned)x, uy = (unsigned)y;
+            atomicAdd(row + OBJ_SUM_X, n * ux + n * (n - 1u) / 2u);
+            atomicAdd(row + OBJ_SUM_Y, n * uy);
+            atomicMax(row + OBJ_X0, (unsigned)(n_x - 1) - ux);                      // (k_match_decode turns it back)
+            atomicMax(row + OBJ_X1, ux + n - 1u);
+            atomicMax(row + OBJ_Y1, uy);
+        }
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_match_decode(const MatchArgs g)
+{
+    const ObjArgs &a = g.p;
+    const long i = (long)blockIdx.x * OBJ_THREADS + threadIdx.x;
+    if (i >= a.n_maps * a.max_objects) return;
+    const long map = i / a.max_objects;
+    if ((unsigned)(i - map * a.max_objects) >= a.n_objects[map]) return;
+    unsigned *const row = a.table + i * OBJ_WORDS;
+    row[OBJ_X0] = (unsigned)(a.f.n_x - 1) - row[OBJ_X0];
+    row[OBJ_Y0] = row[OBJ_FIRST] / (unsigned)a.f.n_x;
 }
 
 #undef OBJ_CHUNK

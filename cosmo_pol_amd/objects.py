@@ -41,7 +41,28 @@ EXACT SUMS (Objects(sums=True); `weighted_centroids` and `sal` read them)
   Outputs    volume float64 [n_blocks + 1, n_thr, max_objects, 3], rows at or beyond n_objects zero; skipped uint32 [n_blocks + 1,
              n_thr, max_objects]; field float64 [n_blocks + 1, 3]; field_cells uint32 [n_blocks + 1, 2].
   Limits     the accumulators, SUM_BINS int64 per table row and per source, and the weight table count into the scratch limit.
-  Not built  matching and tracking of objects; cells of layered composites."""
+
+MATCH (Objects(match=True); `pairs`, `match` and `contingency` read it).  It needs neither `labels` nor `sums`; neither changes.
+  For every block b and threshold t:
+  Label maps lf = the label map of source b, lo = that of the observed map (source n_blocks), both at threshold t exactly as
+             'labels' defines them: kept objects only (min_area applied), numbers 1 ... n_objects, complete beyond max_objects.
+  Overlap    I = (lf > 0) & (lo > 0).
+  Piece      a maximal set of cells of I connected through `connectivity`.  Every piece lies in exactly one forecast object and
+             one observed object.
+  Numbering  the pieces are numbered 1 ... n in ascending order of their first cell (the smallest flat index); no area filter.
+  Piece row  WORDS uint32: first, area, sum of ix, sum of iy, x0, x1, y0, y1 (an object row's first eight words), then forecast
+             (the piece's number in lf) and observed (its number in lo).  The no-overflow clause holds as for the objects.
+  Outputs    n_pieces uint32 [n_blocks, n_thr]: the true count, also beyond max_pieces; pieces uint32 [n_blocks, n_thr,
+             max_pieces, WORDS], rows at or beyond n_pieces zero; covered uint32 [n_blocks, n_thr, 2, max_objects]: side 0, entry
+             k - 1: the cells of forecast object k of block b that lie in I; side 1, entry k - 1: the cells of observed object k
+             that lie in I against block b; entries at or beyond min(n_objects, max_objects) of that side zero.  `covered` is
+             counted from the cells: complete whatever max_pieces is.
+  Invariants nothing overflowing: sum of the pieces' areas == sum of covered[0] == sum of covered[1] == the cells of I;
+             covered[0][k - 1] <= the area of object k.
+  The rule   `pieces_of_map`, built on `cells_of_map`.  Every number is a count, an integer sum, an integer extreme or a
+             comparison: the device result equals it exactly.
+  Limits     the piece scratch, n_blocks * n_thr * (2 * n_y * n_x + n_y) * 4 bytes, counts into the scratch limit.
+  Not built  tracking across calls; block-against-block matching; cells of layered composites."""
 import numpy as np
 
 from . import neighbourhood as NB
@@ -52,6 +73,7 @@ MAX_SCRATCH_BYTES = 1 << 30
 MAX_TABLE = 1024                                          # breakpoints of a weight table: the composite's MAX_TABLE
 SUM_BINS = 16 + 32 + 32                                   # int64 bins of one accumulator row (cpol_obj.h): volume, moment_x, moment_y
 FIRST, AREA, SUM_X, SUM_Y, X0, X1, Y0, Y1, PEAK_CELL, PEAK_BITS = range(WORDS)
+FORECAST, OBSERVED = PEAK_CELL, PEAK_BITS                 # a piece row: the two peak words give way to the two numbers
 
 _U32, _I64 = np.uint32, np.int64
 
@@ -60,10 +82,12 @@ class Objects(object):
     """What a call with object cells finds: the cells of the binary maps of `fractions` (a neighbourhood.Fractions) under
     `connectivity` 4 or 8, those below `min_area` cells dropped, up to `max_objects` (1 ... 65535) table rows per source and
     threshold, with the label maps when `labels` and the exact sums when `sums`, under `weight` = (table_v, table_f) or None
-    (w = m).  ValueError for what the library refuses.  The Fractions is `fractions`; the properties the scored entry points read
-    of a spec are its own."""
+    (w = m), and with the overlap pieces of every block against the observed map when `match`, up to `max_pieces` (1 ... 65535,
+    default max_objects) rows per block and threshold.  ValueError for what the library refuses.  The Fractions is `fractions`;
+    the properties the scored entry points read of a spec are its own."""
 
-    def __init__(self, fractions, connectivity=4, min_area=1, max_objects=1024, labels=True, sums=False, weight=None):
+    def __init__(self, fractions, connectivity=4, min_area=1, max_objects=1024, labels=True, sums=False, weight=None, match=False,
+                 max_pieces=None):
         if not isinstance(fractions, NB.Fractions):
             raise ValueError('fractions: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (fractions,))
         for name, v in (('connectivity', connectivity), ('min_area', min_area), ('max_objects', max_objects)):
@@ -82,6 +106,16 @@ class Objects(object):
             if not self.sums:
                 raise ValueError('weight: a weight table belongs to sums=True')
             self.weight = check_weight(weight)
+        self.match, self.max_pieces = bool(match), None
+        if max_pieces is not None and not self.match:
+            raise ValueError('max_pieces: belongs to match=True')
+        if self.match:
+            max_pieces = self.max_objects if max_pieces is None else max_pieces
+            if isinstance(max_pieces, (bool, np.bool_)) or not isinstance(max_pieces, (int, np.integer)):
+                raise ValueError('max_pieces: an integer, got %r' % (max_pieces,))
+            if not 1 <= max_pieces <= MAX_OBJECTS:
+                raise ValueError('max_pieces must lie in 1 ... %d, got %r' % (MAX_OBJECTS, max_pieces))
+            self.max_pieces = int(max_pieces)
 
     composite = property(lambda self: self.fractions.composite)
     thresholds = property(lambda self: self.fractions.thresholds)
@@ -93,6 +127,8 @@ class Objects(object):
         key = (self.fractions.key, self.connectivity, self.min_area, self.max_objects, self.labels)
         if self.sums:
             key += (True, None if self.weight is None else (self.weight[0].tobytes(), self.weight[1].tobytes()))
+        if self.match:
+            key += ('match', self.max_pieces)
         return key
 
     def __eq__(self, other):
@@ -105,6 +141,8 @@ class Objects(object):
         tail = ''
         if self.sums:
             tail = ', sums=True' + ('' if self.weight is None else ', weight=<%d breakpoints>' % len(self.weight[0]))
+        if self.match:
+            tail += ', match=True, max_pieces=%d' % self.max_pieces
         return 'Objects(%r, connectivity=%d, min_area=%d, max_objects=%d, labels=%r%s)' % (
             self.fractions, self.connectivity, self.min_area, self.max_objects, self.labels, tail)
 
@@ -130,12 +168,15 @@ def check_weight(weight):
 
 def scratch_bytes(spec, blocks):
     """The bytes of the scratch of `blocks` blocks and the observation (cpol_obj.h): the labelling's and, with the exact sums,
-    behind it on an 8-byte boundary the accumulators and the weight table."""
+    behind it on an 8-byte boundary the accumulators and the weight table, and with the match behind those on an 8-byte boundary
+    the piece scratch of `blocks` blocks."""
     maps = (int(blocks) + 1) * len(spec.thresholds)
     n = maps * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
     if getattr(spec, 'sums', False):
         nw = 0 if spec.weight is None else len(spec.weight[0])
         n = (n + 7) // 8 * 8 + (maps * spec.max_objects + int(blocks) + 1) * SUM_BINS * 8 + nw * 8 + (nw * 4 + 7) // 8 * 8
+    if getattr(spec, 'match', False):
+        n = (n + 7) // 8 * 8 + int(blocks) * len(spec.thresholds) * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
     return n
 
 
@@ -372,7 +413,23 @@ def cells_of_map(binary, values, connectivity, min_area, max_objects):
     return _U32(n), _table(lab, n, values, max_objects), lab
 
 
-def result(spec, n_objects, table, labels=None, sums=None):
+def pieces_of_map(lf, lo, connectivity, max_pieces, max_objects):
+    """The rule of the match for ONE pair of label maps (int32 [n_y, n_x], as `cells_of_map` returns them): (n_pieces uint32,
+    pieces uint32 [max_pieces, WORDS], covered uint32 [2, max_objects])."""
+    both = (lf > 0) & (lo > 0)
+    n, pieces, _ = cells_of_map(both, np.zeros(both.shape, dtype=np.float32), connectivity, 1, max_pieces)
+    rows = min(int(n), max_pieces)
+    pieces[:, PEAK_CELL:] = 0                             # (no peak: the two words are the numbers)
+    pieces[:rows, FORECAST] = lf.reshape(-1)[pieces[:rows, FIRST]]
+    pieces[:rows, OBSERVED] = lo.reshape(-1)[pieces[:rows, FIRST]]
+    covered = np.zeros((2, max_objects), dtype=_U32)
+    for side, lab in enumerate((lf, lo)):
+        k = lab[both].astype(_I64)
+        covered[side] = np.bincount(k[k <= max_objects] - 1, minlength=max_objects)
+    return n, pieces, covered
+
+
+def result(spec, n_objects, table, labels=None, sums=None, match=None):
     """The output arrays named.  n_objects [n_blocks + 1, n_thr], table [n_blocks + 1, n_thr, max_objects, WORDS], labels
     [n_blocks + 1, n_thr, n_y, n_x] or None -> {'n_objects': uint32 [n_blocks, n_thr], 'first' | 'area' | 'sum_x' | 'sum_y' |
     'peak_cell': uint32 [n_blocks, n_thr, max_objects], 'bbox': uint32 [..., 4] (x0, x1, y0, y1), 'peak': float32 [...],
@@ -381,7 +438,10 @@ def result(spec, n_objects, table, labels=None, sums=None):
     n_thr, max_objects, 3], skipped, field [n_blocks + 1, 3], field_cells [n_blocks + 1, 2]): 'volume' | 'moment_x' | 'moment_y':
     float64 [n_blocks, n_thr, max_objects], 'skipped': uint32 likewise, 'field': {'volume', 'moment_x', 'moment_y': float64
     [n_blocks], 'cells', 'skipped': uint32 [n_blocks]}, the same under 'observed', and 'weight' (the spec's table or None) and
-    'grid' (n_y, n_x) for `sal`."""
+    'grid' (n_y, n_x) for `sal`.  match: None or the three arrays of the match (n_pieces [n_blocks, n_thr], pieces [n_blocks,
+    n_thr, max_pieces, WORDS], covered [n_blocks, n_thr, 2, max_objects]): 'pieces': {'n_pieces': uint32 [n_blocks, n_thr],
+    'first' | 'area' | 'sum_x' | 'sum_y' | 'forecast' | 'observed': uint32 [n_blocks, n_thr, max_pieces], 'bbox': [..., 4]},
+    'covered' and 'covered_observed': uint32 [n_blocks, n_thr, max_objects]."""
     def named(n, tb, lb, sm=None):
         out = {'n_objects': n, 'first': tb[..., FIRST], 'area': tb[..., AREA], 'sum_x': tb[..., SUM_X], 'sum_y': tb[..., SUM_Y],
                'bbox': tb[..., X0:Y1 + 1], 'peak': tb[..., PEAK_BITS].view(np.float32),     # (views all: a pinned call fills them later)
@@ -399,6 +459,11 @@ def result(spec, n_objects, table, labels=None, sums=None):
     out.update(connectivity=spec.connectivity, min_area=spec.min_area, thresholds=spec.thresholds)
     if sums is not None:
         out.update(weight=spec.weight, grid=(int(spec.n_y), int(spec.n_x)))
+    if match is not None:
+        n_pieces, pc, covered = match
+        out['pieces'] = {'n_pieces': n_pieces, 'first': pc[..., FIRST], 'area': pc[..., AREA], 'sum_x': pc[..., SUM_X],
+                         'sum_y': pc[..., SUM_Y], 'bbox': pc[..., X0:Y1 + 1], 'forecast': pc[..., FORECAST], 'observed': pc[..., OBSERVED]}
+        out['covered'], out['covered_observed'] = covered[..., 0, :], covered[..., 1, :]
     return out
 
 
@@ -425,7 +490,8 @@ def cells(spec, plane_maps, observed, domain=None):
     """The rule in NumPy.  spec: an Objects (or any object with its attributes whose `fractions` has `thresholds`, `n_y` and
     `n_x`); plane_maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]: one block), the scored plane as a composite's finish
     returns it; observed, domain: see neighbourhood.check_maps.  Returns what `result` describes -- exactly what the device
-    returns ('labels' only with spec.labels; the keys of the exact sums only with spec.sums)."""
+    returns ('labels' only with spec.labels; the keys of the exact sums only with spec.sums, those of the match only with
+    spec.match)."""
     F, O, m, o = binary_maps(spec.fractions, plane_maps, observed, domain)
     n_blocks, n_thr = F.shape[:2]
     with_sums = getattr(spec, 'sums', False)
@@ -447,7 +513,15 @@ def cells(spec, plane_maps, observed, domain=None):
             n[s, t], table[s, t], labels[s, t] = cells_of_map(binary, values, spec.connectivity, spec.min_area, spec.max_objects)
             if with_sums:
                 volume[s, t], skipped[s, t] = sums_of_map(labels[s, t], n[s, t], w, spec.max_objects)
-    return result(spec, n, table, labels if spec.labels else None, (volume, skipped, field, field_cells) if with_sums else None)
+    match = None
+    if getattr(spec, 'match', False):
+        match = (np.zeros((n_blocks, n_thr), dtype=_U32), np.zeros((n_blocks, n_thr, spec.max_pieces, WORDS), dtype=_U32),
+                 np.zeros((n_blocks, n_thr, 2, spec.max_objects), dtype=_U32))
+        for b in range(n_blocks):
+            for t in range(n_thr):
+                match[0][b, t], match[1][b, t], match[2][b, t] = pieces_of_map(labels[b, t], labels[n_blocks, t], spec.connectivity,
+                                                                                spec.max_pieces, spec.max_objects)
+    return result(spec, n, table, labels if spec.labels else None, (volume, skipped, field, field_cells) if with_sums else None, match)
 
 
 def centroids(res):
@@ -521,6 +595,86 @@ def sal(res, threshold=0, d=None):
     return {'S': S, 'A': A, 'L': L1 + L2, 'L1': L1, 'L2': L2}
 
 
+def _match_side(res, threshold, who):
+    if 'pieces' not in res:
+        raise ValueError('%s: the result has no match (Objects(match=True))' % who)
+    t = int(threshold)
+    if not 0 <= t < len(res['thresholds']):
+        raise ValueError('%s: threshold index outside 0 ... %d' % (who, len(res['thresholds']) - 1))
+    return t
+
+
+def pairs(res, block, threshold=0):
+    """The distinct (forecast, observed) pairs of block `block` at threshold index `threshold` from a result with the match, sorted
+    ascending: {'forecast', 'observed', 'area', 'sum_x', 'sum_y', 'pieces': int64 [n_pairs]}, the sums over the pair's pieces and
+    their count.  ValueError when n_pieces > max_pieces: a partial fold is not returned."""
+    t = _match_side(res, threshold, 'pairs')
+    pc = res['pieces']
+    b = int(block)
+    n, rows = int(np.asarray(pc['n_pieces'])[b, t]), np.asarray(pc['area']).shape[-1]
+    if n > rows:
+        raise ValueError('pairs: %d pieces, %d rows (max_pieces): a partial fold is not returned' % (n, rows))
+    f, o = np.asarray(pc['forecast'])[b, t, :n].astype(_I64), np.asarray(pc['observed'])[b, t, :n].astype(_I64)
+    key, inverse = np.unique(f * (MAX_OBJECTS + 1) * 16 + o, return_inverse=True)        # (numbers are below 2^20 cells)
+    inverse = inverse.reshape(-1)
+    out = {'forecast': key // ((MAX_OBJECTS + 1) * 16), 'observed': key % ((MAX_OBJECTS + 1) * 16)}
+    for k in ('area', 'sum_x', 'sum_y'):
+        out[k] = np.bincount(inverse, weights=np.asarray(pc[k])[b, t, :n].astype(np.float64), minlength=key.size).astype(_I64)
+    out['pieces'] = np.bincount(inverse, minlength=key.size).astype(_I64)
+    return out
+
+
+def match(res, threshold=0):
+    """Per block and object of either side the partner with the largest pair area, and that area, from a result with the match at
+    threshold index `threshold`: {'partner', 'area': int64 [n_blocks, max_objects] for the forecast objects (the partner is an
+    observed object's number), 'observed_partner', 'observed_area' likewise for the observed objects against every block}.  Ties
+    go to the smallest number; 0 means none (and the rows without an object).  -1 throughout for a block whose pieces overflowed.
+    Partners beyond max_objects are named; objects beyond it have no row."""
+    t = _match_side(res, threshold, 'match')
+    n_blocks, rows = np.asarray(res['covered']).shape[0], np.asarray(res['covered']).shape[-1]
+    out = {k: np.zeros((n_blocks, rows), dtype=_I64) for k in ('partner', 'area', 'observed_partner', 'observed_area')}
+    for b in range(n_blocks):
+        if int(np.asarray(res['pieces']['n_pieces'])[b, t]) > np.asarray(res['pieces']['area']).shape[-1]:
+            for k in out:
+                out[k][b] = -1
+            continue
+        p = pairs(res, b, t)
+        for mine, other, kp, ka in (('forecast', 'observed', 'partner', 'area'), ('observed', 'forecast', 'observed_partner', 'observed_area')):
+            # ascending area, then descending partner: the last entry of an object is its largest pair with the smallest number
+            order = np.lexsort((-p[other], p['area'], p[mine]))
+            who, area, partner = p[mine][order], p['area'][order], p[other][order]
+            last = np.flatnonzero(np.append(who[1:] != who[:-1], True)) if who.size else np.zeros(0, dtype=_I64)
+            ok = who[last] <= rows
+            out[kp][b, who[last][ok] - 1], out[ka][b, who[last][ok] - 1] = partner[last][ok], area[last][ok]
+    return out
+
+
+def contingency(res, threshold=0, min_cover=0.0):
+    """Object hits, misses and false alarms of every block against the observed map from a result with the match, at threshold
+    index `threshold`: an observed object with covered_observed > min_cover * area is a hit, otherwise a miss; a forecast object
+    with covered <= min_cover * area is a false alarm.  {'hits', 'misses', 'false_alarms': int64 [n_blocks], 'pod' = hits /
+    (hits + misses), 'far' = false_alarms / (hits + false_alarms), 'csi' = hits / (hits + misses + false_alarms): float64, NaN
+    for 0 / 0}.  From `covered` alone, so valid when the pieces overflow; where a side has more objects than table rows the block's
+    counts are -1 and its scores NaN rather than silently partial."""
+    t = _match_side(res, threshold, 'contingency')
+    min_cover = float(min_cover)
+    if not 0.0 <= min_cover < 1.0:
+        raise ValueError('contingency: min_cover must lie in [0, 1)')
+    cov, cov_o = np.asarray(res['covered'])[:, t].astype(np.float64), np.asarray(res['covered_observed'])[:, t].astype(np.float64)
+    area, area_o = np.asarray(res['area'])[:, t].astype(np.float64), np.asarray(res['observed']['area'])[t].astype(np.float64)
+    rows = area.shape[-1]
+    hits = ((area_o > 0) & (cov_o > min_cover * area_o)).sum(axis=-1).astype(_I64)
+    misses = ((area_o > 0) & ~(cov_o > min_cover * area_o)).sum(axis=-1).astype(_I64)
+    alarms = ((area > 0) & (cov <= min_cover * area)).sum(axis=-1).astype(_I64)
+    bad = (np.asarray(res['n_objects'])[:, t] > rows) | (int(np.asarray(res['observed']['n_objects'])[t]) > rows)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        h, m, f = hits.astype(np.float64), misses.astype(np.float64), alarms.astype(np.float64)
+        pod, far, csi = h / (h + m), f / (h + f), h / (h + m + f)
+    out = {'hits': np.where(bad, -1, hits), 'misses': np.where(bad, -1, misses), 'false_alarms': np.where(bad, -1, alarms)}
+    out.update(pod=np.where(bad, np.nan, pod), far=np.where(bad, np.nan, far), csi=np.where(bad, np.nan, csi))
+    return out
+
+
 def size_distribution(res, edges):
     """int64 [..., len(edges) - 1]: the objects of every (block, threshold) counted by area in the bins [edges[k], edges[k + 1])
     (ascending cell counts).  Only the objects in the table are counted (n_objects may exceed max_objects)."""
@@ -543,15 +697,15 @@ class Cells(object):
     name = 'composite'
     spectrum, model_var = True, None
     refuses = NB.Scores.refuses
-    _OWN = ('n_objects', 'table', 'labels', 'volume', 'skipped', 'field', 'field_cells')
-    _SUMS = _OWN[3:]
+    _OWN = ('n_objects', 'table', 'labels', 'volume', 'skipped', 'field', 'field_cells', 'n_pieces', 'pieces', 'covered')
+    _SUMS, _MATCH = _OWN[3:7], _OWN[7:]
 
     def __init__(self, spec, observed=None, domain=None, keep_gates=False, phase=3, rays_per_block=0, distributed=False):
         if not isinstance(spec, Objects):
             raise ValueError('spec: a cosmo_pol_amd.objects.Objects, got %r' % (spec,))
         self.scores = NB.Scores(spec.fractions, observed, domain, keep_gates, phase, rays_per_block, distributed)
         self.spec, self.gates = spec, self.scores.gates
-        self.o = None
+        self.o = self.om = None
 
     def set_plane(self, gate_xy, plane_version=0, source=0):
         self.scores.set_plane(gate_xy, plane_version, source)
@@ -562,14 +716,17 @@ class Cells(object):
 
     def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
         structs, keep = self.scores.attach(native, az, n_gates, n_members, doppler, spectrum, staged_vars, take)
-        self.o = None
+        self.o = self.om = None
         if not self.phase & 2:                    # (no cpol_fractions in this call: nothing to hang on)
             return structs, keep
         self.n_blocks = self.scores.n_blocks
         if scratch_bytes(self.spec, self.n_blocks) > MAX_SCRATCH_BYTES:
-            raise ValueError('objects: the labelling scratch of %d blocks needs more than 1 GiB' % self.n_blocks if not self.spec.sums else
-                             'objects: the labelling scratch and the sums of %d blocks need more than 1 GiB' % self.n_blocks)
+            what = ('the labelling scratch, the sums and the pieces of %d blocks need' if self.spec.match else
+                    'the labelling scratch and the sums of %d blocks need' if self.spec.sums else 'the labelling scratch of %d blocks needs')
+            raise ValueError('objects: %s more than 1 GiB' % (what % self.n_blocks))
         self.o, okeep = native.Context.objects_struct(self.spec, self.scores.f)
+        if self.spec.match:
+            self.om = okeep[0]                    # (the ObjectsMatch around self.o: it takes the three arrays of the match)
         return structs, keep + okeep
 
     def arrays(self):
@@ -585,19 +742,25 @@ class Cells(object):
                 out += [('volume', np.float64, (self.n_blocks + 1, nt, spec.max_objects, 3)),
                         ('skipped', np.uint32, (self.n_blocks + 1, nt, spec.max_objects)),
                         ('field', np.float64, (self.n_blocks + 1, 3)), ('field_cells', np.uint32, (self.n_blocks + 1, 2))]
+            if spec.match:
+                out += [('n_pieces', np.uint32, (self.n_blocks, nt)), ('pieces', np.uint32, (self.n_blocks, nt, spec.max_pieces, WORDS)),
+                        ('covered', np.uint32, (self.n_blocks, nt, 2, spec.max_objects))]
         return out
 
     def bind(self, path, address):
-        if path in self._OWN:
+        if path in self._MATCH:
+            setattr(self.om, path, address)
+        elif path in self._OWN:
             setattr(self.o, path, address)
         else:
             self.scores.bind(path, address)
 
     def bind_device(self, entry):
-        # the scores' entries and 'n_objects' | 'table' | 'labels' | 'volume' | 'skipped' | 'field' | 'field_cells': device pointers
+        # the scores' entries and 'n_objects' | 'table' | 'labels' | 'volume' | 'skipped' | 'field' | 'field_cells' | 'n_pieces' |
+        # 'pieces' | 'covered': device pointers
         rest = {}
         for k, ptr in entry.items():
-            if k in self._OWN and self.phase & 2:
+            if k in self._OWN and self.phase & 2 and (k not in self._MATCH or self.spec.match):
                 self.bind(k, ptr)
             else:
                 rest[k] = ptr
@@ -607,8 +770,9 @@ class Cells(object):
         n, table = w.pop('n_objects'), w.pop('table')
         labels = w.pop('labels') if self.spec.labels else None
         sums = [w.pop(k) for k in self._SUMS] if self.spec.sums else None
+        match = [w.pop(k) for k in self._MATCH] if self.spec.match else None
         out = self.scores.finish(w, coords)
-        out['objects'] = result(self.spec, n, table, labels, sums)
+        out['objects'] = result(self.spec, n, table, labels, sums, match)
         return out
 
     def join(self, parts, cat):
@@ -617,8 +781,9 @@ class Cells(object):
         out = self.scores.join(parts, cat)
         if self.rays_per_block:
             ob = [w['objects'] for w in parts]
-            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds', 'weight', 'grid', 'field')]
+            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds', 'weight', 'grid', 'field', 'pieces')]
             out['objects'] = dict(ob[-1], **{k: cat([q[k] for q in ob]) for k in stacked})
-            if 'field' in ob[-1]:
-                out['objects']['field'] = {k: cat([q['field'][k] for q in ob]) for k in ob[-1]['field']}
+            for nested in ('field', 'pieces'):
+                if nested in ob[-1]:
+                    out['objects'][nested] = {k: cat([q[nested][k] for q in ob]) for k in ob[-1][nested]}
         return out

@@ -2538,6 +2538,8 @@ class RadarOperator(object):
         of every block and once of the observed map, exactly objects.cells of the map the same call returns ({'n_objects',
         'first', 'area', 'sum_x', 'sum_y', 'bbox', 'peak', 'peak_cell', 'labels' when asked, 'observed': the same,
         'connectivity', 'min_area', 'thresholds'}); device_outputs['composite'] may then carry 'n_objects', 'table' and 'labels'.
+        With Objects(match=True) 'objects' also holds the overlap pieces of every block's objects with the observed ones
+        ('pieces', 'covered', 'covered_observed': objects.py, MATCH), and the entry may carry 'n_pieces', 'pieces' and 'covered'.
         The other keywords are those of simulate_rays_composite.  `device_outputs`: its entry 'composite' may carry 'observed',
         'domain', 'sums' and 'totals' as device pointers (`observed` stays None).  ValueError for an observed map or a domain of
         a wrong shape or dtype and for what the library refuses.  `radar` (the radars of a network under one operator differ in

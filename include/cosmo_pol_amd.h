@@ -768,14 +768,44 @@ typedef struct cpol_composite {
  * other than 0 or 2 ... 1024; NULL weight_v or weight_f; a breakpoint or value that is NaN or infinite; breakpoints not strictly
  * ascending; values that decrease; the limit exceeded.
  * Two kernels behind k_obj_decode: k_obj_sums (a wavefront per source and row; equal (object, bin) keys are combined inside the
- * wavefront before ONE atomic) and k_obj_sums_finish (a thread per sum: the rounding). */
+ * wavefront before ONE atomic) and k_obj_sums_finish (a thread per sum: the rounding).
+ *
+ * MATCH (cpol_objects_match, below: a cpol_objects whose pad_ holds max_pieces, embedded as the first member; a zero pad_ means
+ * off and a call without it queues exactly what it queued before): which forecast object lies on which observed object and by how
+ * many cells, for object hits, misses and false alarms, MODE-style pairs and CRA displacement.  It needs neither `labels` nor the
+ * exact sums; both may be on beside it and neither changes.  cosmo_pol_amd/objects.py states the same rule (`pieces_of_map`).
+ * For every block b (0 ... n_blocks - 1) and threshold t:
+ * LABEL MAPS: lf is the label map of source b, lo that of the observed map (source n_blocks), both at threshold t exactly as
+ * `labels` defines them: kept objects only (min_area applied), numbers 1 ... n_objects, complete even beyond max_objects.
+ * OVERLAP MAP: I = (lf > 0) & (lo > 0).
+ * PIECE: a maximal set of cells of I connected through `connectivity`.  Every piece lies in exactly one forecast object and one
+ * observed object.
+ * NUMBERING: the pieces are numbered 1 ... n in ascending order of their first cell (the smallest flat index); no area filter.
+ * PIECE ROW, CPOL_OBJ_WORDS uint32 words: first, area, sum of ix, sum of iy, x0, x1, y0, y1 (the object row's first eight words),
+ * then forecast (the piece's number in lf) and observed (its number in lo).  NO OVERFLOW holds as above.
+ * OUTPUTS: n_pieces uint32 [n_blocks][n_thresholds]: the TRUE count, also beyond max_pieces; pieces uint32 [n_blocks]
+ * [n_thresholds][max_pieces][CPOL_OBJ_WORDS], rows at or beyond n_pieces zero; covered uint32 [n_blocks][n_thresholds][2]
+ * [max_objects]: side 0, entry k - 1: the cells of forecast object k of block b that lie in I; side 1, entry k - 1: the cells of
+ * observed object k that lie in I against block b; entries at or beyond min(n_objects, max_objects) of that side are zero.
+ * `covered` is counted from the cells, so it is complete whatever max_pieces is.  The three follow p->outputs_on_device like
+ * `table`.  Every number is a count, an integer sum, an integer extreme or a comparison: the result is exact in any order.
+ * INVARIANTS (nothing overflowing): sum of pieces.area == sum of covered[0] == sum of covered[1] == the cells of I; covered[0]
+ * [k - 1] <= the area of object k.
+ * LIMITS: the piece scratch, n_blocks * n_thresholds * (2 * n_y * n_x + n_y) * 4 bytes, lies behind the labelling scratch and the
+ * sums' accumulators; the total is at most 1 GiB.
+ * CPOL_ERR_ARG as above: pad_ outside 0 ... 65535; NULL n_pieces, pieces or covered with match on; the limit exceeded; too many
+ * workgroups.
+ * Kernels behind everything above: k_match_runs (the overlap flag from the two (root, number) lookups, the piece runs, `covered`
+ * with one integer atomic per run segment and side), then k_obj_merge, k_obj_flatten, k_obj_area, k_obj_count and k_obj_number on
+ * the piece arrays, k_match_attr and k_match_decode.
+ * NOT BUILT: tracking across calls; block-against-block matching; cells of layered composites. */
 #define CPOL_OBJ_WORDS 10
 #define CPOL_OBJ_MAX_OBJECTS 65535
 typedef struct cpol_objects {
     int32_t  connectivity;      /* 4 or 8                                                                          */
     int32_t  min_area;          /* >= 1                                                                            */
     int32_t  max_objects;       /* 1 ... 65535 table rows per (source, threshold)                                  */
-    int32_t  pad_;
+    int32_t  pad_;              /* 0, or max_pieces (1 ... 65535) when this struct is the first member of a cpol_objects_match */
     uint32_t *n_objects;        /* [n_blocks + 1][n_thresholds]                                                    */
     uint32_t *table;            /* [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS]                       */
     int32_t  *labels;           /* [n_blocks + 1][n_thresholds][n_y][n_x] or NULL = not wanted                     */
@@ -789,6 +819,14 @@ typedef struct cpol_objects {
     double   *field;            /* [n_blocks + 1][3]: the same sums over the whole field of every source           */
     uint32_t *field_cells;      /* [n_blocks + 1][2]: cells summed, cells skipped                                   */
 } cpol_objects;
+
+/* MATCH (above): cpol_fractions.objects points at `o`; the library reads beyond it only when o.pad_ != 0 */
+typedef struct cpol_objects_match {
+    cpol_objects o;             /* o.pad_ = max_pieces, 1 ... 65535 piece rows per (block, threshold)                 */
+    uint32_t *n_pieces;         /* [n_blocks][n_thresholds]                                                          */
+    uint32_t *pieces;           /* [n_blocks][n_thresholds][max_pieces][CPOL_OBJ_WORDS]                              */
+    uint32_t *covered;          /* [n_blocks][n_thresholds][2][max_objects]: forecast side, observed side             */
+} cpol_objects_match;
 
 typedef struct cpol_fractions {
     int32_t  field;             /* the field whose plane is scored: one of composite->fields                        */
@@ -1288,7 +1326,9 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * maps [n_blocks][n_y][n_x] float32 (what a finished plane would hold; f.field and f.plane are not read), f.observed, f.domain
  * (or NULL), f.sums and f.totals; 1 <= n_x, n_y <= 1023; blocking; needs no staged model, tables or composite pass;
  * cpol_fractions' refusals, and CPOL_ERR_ARG for a bad shape or NULL maps.  Returns 0.  With f.objects (host arrays n_objects,
- * table and labels or NULL) the call runs cpol_objects' checks and the kernels of cpol_obj.inl on the same maps too.
+ * table and labels or NULL) the call runs cpol_objects' checks and the kernels of cpol_obj.inl on the same maps too; with a
+ * non-zero f.objects->pad_ the struct is the first member of a cpol_objects_match, whose n_pieces, pieces and covered are host
+ * arrays, and the match runs as well.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 
