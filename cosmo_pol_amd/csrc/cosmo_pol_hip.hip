@@ -36,6 +36,7 @@
 #include "cpol_psd.inl"
 #include "cpol_fused.inl"
 #include "cpol_final.inl"
+#include "cpol_gate_ops.h"
 #include "cpol_gate.inl"
 #include "cpol_spectrum.inl"
 #include "cpol_ingest.inl"
@@ -3967,7 +3968,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
                                    ctx->hs, ctx->its, ca, fa, ga, rr);
             } else {
                 if (!(pk.exp_skip & 2))
-                hipLaunchKernelGGL(k_gate1_ray, tgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr);
+                hipLaunchKernelGGL(k_gate1_ray, tgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr,
+                                   gate1_finish_ops(fa, ga, t->sub_h, t->sub_w));
                 if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
                 if (tm_psd) { HIPCHK(hipEventRecord(ctx->ev[EV_BUCKET], st)); HIPCHK(hipEventRecord(ctx->ev[EV_PSD], st)); }
                 if (!(pk.exp_skip & 4))

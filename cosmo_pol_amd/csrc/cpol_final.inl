@@ -1004,7 +1004,13 @@ void k_subbeam_sum_team(HydroSet hs, ItabSet its, SubsumArgs a)
 // fall-speed sums (mom_v, mom_n) of the ONE sub-beam of a single-beam sweep come from the caller's registers
 // (k_gate1); else they are read from vn[] / ice_first[] (subbeam_proj).
 __device__ __forceinline__ void gate_finish(const FinalArgs &a, int ray, int gate, float (&tot)[CPOL_N_SZ], bool have_moments,
-                                            double mom_v, double mom_n, double wtot, float &k2_out, float &fh_out, float &fv_out)
+                                            double mom_v, double mom_n, double wtot, float &k2_out, float &fh_out, float &fv_out
+#ifdef CPOL_SUBSUM_TRACE
+                                            , unsigned long long *trace_fin = nullptr      // (k_gate1_ray: [0] the polarimetric part done and its stores
+                                                                                           // issued, [1] the last sub-beam's projection known -- every operand
+                                                                                           // of RVEL has arrived --, [2] RVEL and mask formed: arithmetic done)
+#endif
+                                            )
 {
     const long n_rg = (long)a.n_rays * a.n_gates;
     const long rg = (long)ray * a.n_gates + gate;
@@ -1057,6 +1063,9 @@ __device__ __forceinline__ void gate_finish(const FinalArgs &a, int ray, int gat
     a.DELTA_HV[rg] = (float)atan2((double)(tot[5] - tot[6]), (double)(-tot[4] - tot[7]));
 #endif
 
+#ifdef CPOL_SUBSUM_TRACE
+    if (trace_fin) trace_fin[0] = trace_fin[1] = wall_clock64();
+#endif
     // ---- radial velocity, Doppler scheme 1 (doppler_scatter.py:276-281, 313-333, 418-420) ----
     if (a.RVEL && !CPOL_SKIP_RVEL) {
         double rv = __builtin_nan(""), tw = 0.0;
@@ -1087,6 +1096,12 @@ __device__ __forceinline__ void gate_finish(const FinalArgs &a, int ray, int gat
             const long sbg = sbg0 + (long)s * a.n_gates;
             const double proj = a.proj ? a.proj[sbg] : have_moments ? proj_from_moments(a, ray, s, sbg, n_sbg, mom_v, mom_n)
                                                        : subbeam_proj(a, ray, s, gate, sbg, n_sbg);
+#ifdef CPOL_SUBSUM_TRACE
+            if (trace_fin) {
+                asm volatile("" :: "v"(proj));
+                trace_fin[1] = wall_clock64();
+            }
+#endif
             const double w = a.wgate ? a.wgate[sbg] : a.sub_w[s];
             if (proj == proj) tw += w;
             double x = (rv == rv) ? rv : 0.0;
@@ -1121,6 +1136,12 @@ __device__ __forceinline__ void gate_finish(const FinalArgs &a, int ray, int gat
     if (a.mask8) a.mask8[rg] = (signed char)(int)msum;        // (a sum of at most 63 codes in [-1, 2]: exact)
     msum /= (double)a.n_sub;
     if (msum > -1.0 && msum <= 0.0) msum = 0.0;
+#ifdef CPOL_SUBSUM_TRACE
+    if (trace_fin) {
+        asm volatile("" :: "v"(msum));
+        trace_fin[2] = wall_clock64();
+    }
+#endif
     if (a.mask) a.mask[rg] = msum;
 
     // ---- integrate_radials: NaN-skipping weighted sum (float64) ----

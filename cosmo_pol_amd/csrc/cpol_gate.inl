@@ -443,6 +443,166 @@ __device__ __forceinline__ void integrate_gamma_item_wave(const double *table, c
     __builtin_amdgcn_wave_barrier();
 }
 
+// ---- k_gate1_ray's finish of one gate of a single-beam sweep, from the compact record (cpol_gate_ops.h) ----
+// The statements of gate_finish and proj_from_moments (cpol_final.inl) for n_sub == 1 with sz_total, model_vars, wgate and proj
+// all NULL (Gate1FinishOps.generic clear), in the same order on the same types: the same bits.  What differs is WHEN the operands
+// are asked for.  gate_finish meets them one after the other -- the eight stores of the polarimetric part stand in front of
+// RVEL's loads and may alias them for all the compiler knows, the geometry row hangs on sub_h[s], U, V, W on the cosine -- four
+// to five dependent vector rounds of 0.4-0.5 us each in the wavefront that ends its workgroup's life (tools/gate1_trace.py:
+// 1.4 us between the polarimetric part and the projection).  Here gate1_finish_request asks for all of them in ONE round, ahead
+// of the LDS reads of the species' sums; gate_finish_single then only computes and stores.
+struct Gate1FinishIn {
+    signed char code;             // sub_mask
+    float elev, u, v, w;
+    double g0, g1;                // the geometry row's sin / cos of the sub-beam azimuth
+    double nyq;
+};
+
+__device__ __forceinline__ void gate1_finish_request(const Gate1FinishOps &o, int ray, long rg, Gate1FinishIn &in)
+{
+    const long n_sbg = (long)o.n_rays * o.n_gates;         // (one sub-beam: n_sbg = n_rg, the sub-beam gate is the gate)
+    in.code = o.sub_mask[rg];
+    in.elev = in.u = in.v = in.w = 0.f;
+    in.g0 = in.g1 = in.nyq = 0.0;
+    if (o.RVEL && !CPOL_SKIP_RVEL) {
+        const double *gc = o.geo_row + (long)ray * o.geo_stride;
+        in.elev = o.elev[rg];
+        in.u = o.vals[(long)o.var_u * n_sbg + rg];
+        in.v = o.vals[(long)o.var_v * n_sbg + rg];
+        in.w = o.vals[(long)o.var_w * n_sbg + rg];
+        in.g0 = gc[0];
+        in.g1 = gc[1];
+        if (o.nyquist) in.nyq = o.nyquist[ray];
+    }
+}
+
+__device__ __forceinline__ void gate_finish_single(const Gate1FinishOps &a, const Gate1FinishIn &in, long rg, float (&tot)[CPOL_N_SZ],
+                                                   double mom_v, double mom_n
+#ifdef CPOL_SUBSUM_TRACE
+                                                   , unsigned long long *trace_fin      // (as gate_finish's)
+#endif
+                                                   )
+{
+    const float qnan = __builtin_nanf("");
+#pragma unroll
+    for (int c = 0; c < CPOL_N_SZ; ++c) if (tot[c] == 0.0f) tot[c] = qnan;     // Q5
+
+    // ---- get_pol_from_sz (float32) ----
+    const float two_pi = (float)(2 * 3.14159265358979323846);
+    const float b = tot[0] - tot[1] - tot[2] + tot[3];
+    const float cc = tot[0] + tot[1] + tot[2] + tot[3];
+    const float xs_h = two_pi * b;
+    const float xs_v = two_pi * cc;
+    a.ZH[rg] = a.c_zh * xs_h;
+    a.ZV[rg] = a.c_zh * xs_v;
+    a.ZDR[rg] = xs_h / xs_v;
+    const float kdp = a.c_kdp * (tot[10] - tot[8]);
+    a.KDP[rg] = kdp;
+    const float k2 = 2.0f * kdp;
+    a.sk[rg] = (k2 == k2) ? k2 : 0.0f;                        // nan_cumsum
+    const float att_h = 4.343e-3f * (a.c_2w * tot[11]);
+    const float att_v = 4.343e-3f * (a.c_2w * tot[9]);
+    a.ATT_H[rg] = att_h;
+    a.ATT_V[rg] = att_v;
+    float fh_out = 1.0f, fv_out = 1.0f;
+    if (a.with_attenuation) {
+        // 10**(-0.1*A*(radial_res/1000.)) in float32 (doppler_scatter.py:413-414); NaN -> 1
+#if CPOL_EXP_FINISH_CHEAP          // (timing experiment only: wrong values)
+        float fh = 1.0f - 0.1f * att_h * a.res_km;
+        float fv = 1.0f - 0.1f * att_v * a.res_km;
+#else
+        float fh = (float)exp10((double)(-0.1f * att_h * a.res_km));
+        float fv = (float)exp10((double)(-0.1f * att_v * a.res_km));
+#endif
+        fh_out = (fh == fh) ? fh : 1.0f;
+        fv_out = (fv == fv) ? fv : 1.0f;
+    }
+    a.sh[rg] = fh_out;
+    a.sv[rg] = fv_out;
+    const float t47 = tot[4] + tot[7], t65 = tot[6] - tot[5];
+    const float aa = t47 * t47 + t65 * t65;
+    a.RHOHV[rg] = sqrtf(aa / (b * cc));
+#if CPOL_EXP_FINISH_CHEAP
+    a.DELTA_HV[rg] = (tot[5] - tot[6]) / (-tot[4] - tot[7]);
+#else
+    a.DELTA_HV[rg] = (float)atan2((double)(tot[5] - tot[6]), (double)(-tot[4] - tot[7]));
+#endif
+#ifdef CPOL_SUBSUM_TRACE
+    if (trace_fin) trace_fin[0] = trace_fin[1] = wall_clock64();
+#endif
+
+    // ---- radial velocity, Doppler scheme 1: the ONE sub-beam of gate_finish's loop, proj_from_moments in place ----
+    if (a.RVEL && !CPOL_SKIP_RVEL) {
+        double rv = __builtin_nan(""), tw = 0.0;
+        const double vh = mom_v / mom_n;
+        const float th = in.elev * 0.017453292f;          // np.deg2rad on float32
+        const double ct = (double)(float)cos((double)th), st = (double)(float)sin((double)th);
+        const double U = (double)in.u;
+        const double V = (double)in.v;
+        const double W = (double)in.w;
+        const double proj = (U * in.g0 + V * in.g1) * ct + (W - vh) * st;
+#ifdef CPOL_SUBSUM_TRACE
+        if (trace_fin) {
+            asm volatile("" :: "v"(proj));
+            trace_fin[1] = wall_clock64();
+        }
+#endif
+        const double w = a.sub_w0;
+        if (proj == proj) tw += w;
+        double x = (rv == rv) ? rv : 0.0;
+        double y = proj * w;
+        if (!(y == y)) y = 0.0;
+        rv = x + y;
+        rv = rv / tw;
+        if (a.nyquist) {
+            // aliasing (utilities.py:142-156)
+            const double nyq = in.nyq, pi = 3.14159265358979323846;
+            const double theta = (rv + nyq) / (2 * nyq) * pi - pi / 2.;
+            const double fold = atan(tan(theta));
+            rv = (fold + pi / 2) * (2 * nyq) / pi - nyq;
+        }
+        a.RVEL[rg] = rv;
+    }
+
+    // ---- radial mask (doppler_scatter.py:472-477) ----
+    double msum = 0.0;
+    msum += (double)in.code;
+    if (a.mask8) a.mask8[rg] = (signed char)(int)msum;
+    msum /= (double)1;
+    if (msum > -1.0 && msum <= 0.0) msum = 0.0;
+#ifdef CPOL_SUBSUM_TRACE
+    if (trace_fin) {
+        asm volatile("" :: "v"(msum));
+        trace_fin[2] = wall_clock64();
+    }
+#endif
+    if (a.mask) a.mask[rg] = msum;
+}
+
+// the sum over the species in order of one gate's terms in LDS ([n_h][12][64] float32), and of the fall-speed moments of those
+// that carry them (flag bit 2); a slot absent from the tile (its bit of pmask clear) wrote nothing
+__device__ __forceinline__ void gate1_species_sums(const float *s_acc, const double *s_mv, const double *s_mn, const unsigned *s_flag, int n_h,
+                                                   unsigned pmask, int lane, float (&tot)[CPOL_N_SZ], double &mom_v, double &mom_n)
+{
+    for (int q = 0; q < n_h; ++q) {
+        if (!((pmask >> q) & 1u)) {                 // (wave-uniform) absent from the tile: the column of +0.0f it would have written
+#pragma unroll                                      // (added all the same: -0.0f + 0.0f = +0.0f, the bits of the other forms)
+            for (int c = 0; c < CPOL_N_SZ; ++c) tot[c] = (q == 0) ? 0.f : tot[c] + 0.f;
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < CPOL_N_SZ; ++c) {
+            const float acc = s_acc[(q * CPOL_N_SZ + c) * 64 + lane];
+            tot[c] = (q == 0) ? acc : tot[c] + acc;
+        }
+        if (s_flag[q * 64 + lane] & 4u) {
+            const double vq = s_mv[q * 64 + lane], nq = s_mn[q * 64 + lane];
+            if (vq == vq) mom_v += vq;
+            if (nq == nq) mom_n += nq;
+        }
+    }
+}
+
 // RAY = false: k_gate1_species as described above (grid = ceil(n_rg / 64)).
 // RAY = true: an item outside its table is integrated on the spot (integrate_gamma_item_wave: no deferred gates, no
 // integrating launch behind this kernel).
@@ -477,7 +637,7 @@ __device__ __forceinline__ void integrate_gamma_item_wave(const double *table, c
 #define GATE1S_BLK_BYTES (CPOL_GATE1_LDS ? 2 * ((CPOL_ITAB1_NC * CPOL_ITAB_NFP / 2) > CPOL_WAVE ? (CPOL_ITAB1_NC * CPOL_ITAB_NFP / 2) : CPOL_WAVE) * 16 : 0)
 template <bool RAY, bool TICKET>
 __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const ItabSet &its, const ClassifyArgs &a, const FinalArgs &f,
-                                                   const GateArgs &g, const ScanRayArgs &r)
+                                                   const GateArgs &g, const ScanRayArgs &r, const Gate1FinishOps &fo)
 {
     constexpr int NC = CPOL_ITAB1_NC, NFP = CPOL_ITAB_NFP, NB = NC * NFP;
     extern __shared__ unsigned char s_raw[];
@@ -570,6 +730,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     const bool here = (pmask >> j) & 1u;                                               // (wave-uniform)
 #ifdef CPOL_SUBSUM_TRACE
     unsigned long long g1t[6], g1_valid = 0, g1_hw = 0, g1_pre = 0;
+    unsigned long long g1_rule = 0, g1f[5] = {0, 0, 0, 0, 0};      // (round 10: the clock behind the species' rule; the parts of the finish)
     if (LAST_WAVE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const unsigned long long g1_present = wall_clock64();                          // the presence words have arrived
@@ -612,7 +773,12 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     g1t[2] = g1t[3] = g1t[1];
 #endif
     if (!gone) {
+#ifdef CPOL_SUBSUM_TRACE
+    g1_rule = g1t[1];
+    classify_item(h, t, a, a.vals, n, i, i, inl, qm, 0.0, T, d.var_t, e, it, LAST_WAVE ? &g1_rule : nullptr);
+#else
     classify_item(h, t, a, a.vals, n, i, i, inl, qm, 0.0, T, d.var_t, e, it);
+#endif
 #ifdef CPOL_SUBSUM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     g1t[2] = wall_clock64();                           // PSD parameters, table position
@@ -789,6 +955,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) my_lookup += __shfl_xor(my_lookup, off);
     }   // (!gone)
+    bool fast = false;                                // (k_gate1_ray: the gates were finished from the compact record)
     if (LAST_WAVE) {
         // this wavefront's share of the sweep's table-item count, then its ticket: release (its LDS stores are complete),
         // acquire for the wavefront that finds every other ticket taken
@@ -808,7 +975,9 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         }
 #ifdef CPOL_SUBSUM_TRACE
         g1t[4] = wall_clock64();                       // terms in LDS, ticket taken
-        g1_valid = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(it.valid)) | ((unsigned long long)j << 32) | g1_pre;
+        // (round 10, bits 8-19 of word 6: model values arrived -> the species' rule done, in ticks of 10 ns; the valid lanes keep bits 0-7)
+        g1_valid = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(it.valid)) | ((unsigned long long)j << 32) | g1_pre |
+                   (min(g1_rule - g1t[1], 4095ull) << 8);
         g1_hw = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                 (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
         if (old != n_here - 1) {
@@ -824,6 +993,34 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         if (old != n_here - 1) return;                // (not the last of the slots present: the slot is free for the next workgroup's wavefronts)
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         pmask &= ~gone_slots;                         // (their LDS columns were never written)
+        if (!fo.generic) {                            // (wave-uniform)
+            // (round 10) the usual single-beam sweep: the finish from the compact record.  Every vector operand of the gate is asked
+            // for first, in one round; the species' sums come out of LDS while they are on their way; gate_finish_single computes
+            // and stores.  Nothing is ever deferred here (RAY: an item off its table was integrated above, no flag carries bit 1),
+            // so neither vmask nor defer is written, as below.
+            fast = true;
+            if (in) {
+                Gate1FinishIn fin;
+                gate1_finish_request(fo, ray_b, i, fin);
+                __builtin_amdgcn_sched_barrier(0);    // (the requests stay in front of the LDS reads)
+                float tot[CPOL_N_SZ];
+                double mom_v = 0.0, mom_n = 0.0;
+                gate1_species_sums(s_acc, s_mv, s_mn, s_flag, n_h, pmask, lane, tot, mom_v, mom_n);
+#ifdef CPOL_SUBSUM_TRACE
+                {
+                    float keep = 0.f;
+#pragma unroll
+                    for (int c = 0; c < CPOL_N_SZ; ++c) keep += tot[c];
+                    asm volatile("" :: "v"(keep), "v"(mom_v), "v"(mom_n));
+                    g1f[0] = wall_clock64();               // the species' sums read from LDS
+                }
+                gate_finish_single(fo, fin, i, tot, mom_v, mom_n, g1f + 1);
+                g1f[4] = wall_clock64();                   // every store issued
+#else
+                gate_finish_single(fo, fin, i, tot, mom_v, mom_n);
+#endif
+            }
+        }
     } else {
     __syncthreads();                                  // (s_lookup = 0 is visible; the species' terms are in LDS)
     if (lane == 0 && my_lookup) atomicAdd(&s_lookup, my_lookup);
@@ -832,7 +1029,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     // ---- the gate: deferred if any species is off its table; the items of a deferred gate are stored for final_gate ----
     unsigned vbits = 0;
     bool deferred = false;
-    for (int q = 0; q < n_h; ++q) {
+    for (int q = 0; q < (fast ? 0 : n_h); ++q) {
         const unsigned fl = ((pmask >> q) & 1u) ? s_flag[q * 64 + lane] : 0u;          // (a slot absent from the tile wrote nothing)
         vbits |= (fl & 1u) << q;
         deferred = deferred || (fl & 2u);
@@ -849,47 +1046,58 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         if (s_lookup) atomicAdd(a.n_lookup + 2 + slot, s_lookup);
     }
     }
-    if (j == 0 || LAST_WAVE) {
+    if (!fast && (j == 0 || LAST_WAVE)) {
         // ---- wavefront 0: sum over the species in order, get_pol_from_sz, RVEL, mask; the operands of the range scans ----
         if (in && deferred) a.vmask[i] = (unsigned char)vbits;
         if (in && !RAY) g.defer[i] = deferred ? 1 : 0;
         if (in && !deferred) {
             float tot[CPOL_N_SZ];
             double mom_v = 0.0, mom_n = 0.0;
-            for (int q = 0; q < n_h; ++q) {
-                if (!((pmask >> q) & 1u)) {                 // (wave-uniform) absent from the tile: the column of +0.0f it would have written
-#pragma unroll                                              // (added all the same: -0.0f + 0.0f = +0.0f, the bits of the other forms)
-                    for (int c = 0; c < CPOL_N_SZ; ++c) tot[c] = (q == 0) ? 0.f : tot[c] + 0.f;
-                    continue;
-                }
-#pragma unroll
-                for (int c = 0; c < CPOL_N_SZ; ++c) {
-                    const float acc = s_acc[(q * CPOL_N_SZ + c) * 64 + lane];
-                    tot[c] = (q == 0) ? acc : tot[c] + acc;
-                }
-                if (s_flag[q * 64 + lane] & 4u) {
-                    const double vq = s_mv[q * 64 + lane], nq = s_mn[q * 64 + lane];
-                    if (vq == vq) mom_v += vq;
-                    if (nq == nq) mom_n += nq;
-                }
-            }
+            gate1_species_sums(s_acc, s_mv, s_mn, s_flag, n_h, pmask, lane, tot, mom_v, mom_n);
             const int ray = (int)(i / f.n_gates), gate = (int)(i % f.n_gates);
             float k2, fh, fv;
+#ifdef CPOL_SUBSUM_TRACE
+            {
+                float keep = 0.f;
+#pragma unroll
+                for (int c = 0; c < CPOL_N_SZ; ++c) keep += tot[c];
+                asm volatile("" :: "v"(keep), "v"(mom_v), "v"(mom_n));
+                g1f[0] = wall_clock64();                   // the species' sums read from LDS
+            }
+            gate_finish(f, ray, gate, tot, want_rvel, mom_v, mom_n, 0.0, k2, fh, fv, LAST_WAVE ? g1f + 1 : nullptr);
+#else
             gate_finish(f, ray, gate, tot, want_rvel, mom_v, mom_n, 0.0, k2, fh, fv);
+#endif
             g.sk[i] = k2;
             g.sh[i] = fh;
             g.sv[i] = fv;
+#ifdef CPOL_SUBSUM_TRACE
+            g1f[4] = wall_clock64();                       // every store issued
+#endif
         }
     }
 #ifdef CPOL_SUBSUM_TRACE
     if (LAST_WAVE) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long g1_end = wall_clock64();  // the 64 gates finished (this wavefront took the last ticket)
+        // (round 10) the parts of the finish, per lane (a lane outside the sweep or of a deferred gate has none), the wavefront's
+        // latest of each: ticks since the ticket, 12 bits each -- LDS sums read, polarimetric part done and its stores issued,
+        // RVEL's operands arrived (the projection known), arithmetic done (RVEL and mask formed), stores issued
+        unsigned long long parts = 0;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            unsigned d = g1f[q] > g1t[4] ? (unsigned)min(g1f[q] - g1t[4], 4095ull) : 0u;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) d = max(d, (unsigned)__shfl_xor((int)d, off));
+            parts |= (unsigned long long)d << (12 * q);
+        }
         const unsigned long w = ((unsigned long)blockIdx.y * gridDim.x + blockIdx.x) * n_h + j;
         if (lane == 0 && w < CPOL_SUBSUM_TRACE_N) {
             for (int q = 0; q < 5; ++q) g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + q] = g1t[q];
-            g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 5] = wall_clock64();      // the 64 gates finished (this wavefront took the last ticket)
+            g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 5] = g1_end;
             g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 6] = g1_valid;
-            g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 7] = g1_hw;
+            // (word 7: XCC_ID stays in bits 32-35 -- the tool reads nothing else of the hardware registers --, the parts around it)
+            g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 7] = ((g1_hw >> 32) & 15ull) << 32 | (parts & 0xFFFFFFFFull) | (parts >> 32) << 36;
         }
     }
 #endif
@@ -975,14 +1183,14 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_species(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g)
 {
-    gate1_species_body<false, false>(hs, its, a, f, g, ScanRayArgs{});
+    gate1_species_body<false, false>(hs, its, a, f, g, ScanRayArgs{}, Gate1FinishOps{});
 }
 
 // grid = gate1_tiles(n_rays, n_gates).n_blocks, block = 64 * n_hydro, dynamic LDS = n_hydro * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES)
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
-                                                                                  ScanRayArgs r)
+                                                                                  ScanRayArgs r, Gate1FinishOps fo)
 {
-    gate1_species_body<true, false>(hs, its, a, f, g, r);
+    gate1_species_body<true, false>(hs, its, a, f, g, r, fo);
 }
 
 // the same with the ray's scans inside (the ticket: see gate1_species_body); CPOL_GATE1_RAY=3.  grid = (ceil(n_gates / 64), n_rays),
@@ -991,7 +1199,7 @@ __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray_scan(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
                                                                                        ScanRayArgs r)
 {
-    gate1_species_body<true, true>(hs, its, a, f, g, r);
+    gate1_species_body<true, true>(hs, its, a, f, g, r, Gate1FinishOps{});
 }
 
 // The range scans of a single-beam sweep whose gates k_gate1_ray has finished (no deferred gates: nothing of final_gate):

@@ -366,7 +366,11 @@ struct ClassItem {
 };
 
 __device__ __forceinline__ void classify_item(const HydroDev &h, const ItabDev &tj, const ClassifyArgs &a, const float *vals, long n, long i, long gi,
-                                              bool in, float qm, double fw, float T0, int var_t0, float e, ClassItem &o)
+                                              bool in, float qm, double fw, float T0, int var_t0, float e, ClassItem &o
+#ifdef CPOL_SUBSUM_TRACE
+                                              , unsigned long long *trace_rule = nullptr      // (k_gate1_ray: the clock behind the species' rule)
+#endif
+                                              )
 {
     const cpol_hydro_desc &d = h.d;
     // NaN -> false (doppler_scatter.py:185); scheme 'ml': only gates where the
@@ -459,6 +463,12 @@ __device__ __forceinline__ void classify_item(const HydroDev &h, const ItabDev &
         default: break;
         }
     }
+#ifdef CPOL_SUBSUM_TRACE
+    if (trace_rule) {                                      // (the rule's scalar operands have all arrived, its slope is formed)
+        asm volatile("" :: "v"(p0), "v"(p1), "v"(p2));
+        *trace_rule = wall_clock64();
+    }
+#endif
     // items whose lambda lies on the slot's integral table are finished from ONE 16-byte record {position on
     // the panel axis, scale of the item}; only the others are sorted by LUT slice for the integrating kernels
     bool lookup = false;

@@ -1,0 +1,17 @@
+"""The host-side filler of k_gate1_ray's finish record (cosmo_pol_amd/csrc/cpol_gate_ops.h): every field equals its source for
+two sweeps that differ in all of them, the record is a whole number of 64-byte lines, and `generic` is set by each of
+sz_total, model_vars, wgate, proj and n_sub != 1 alone and by nothing else."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_finish_record_equals_its_sources(tmp_path):
+    exe = str(tmp_path / 'gate_ops_check')
+    cmd = ['g++', '-std=c++17', '-O1', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'cosmo_pol_amd', 'csrc'),
+           os.path.join(ROOT, 'tests', 'c_host', 'gate_ops_check.cpp'), '-o', exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and 'GATE_OPS_OK' in r.stdout, r.stdout + r.stderr

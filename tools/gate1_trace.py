@@ -5,6 +5,11 @@ Every wavefront (gate tile, ray, species) records the 100-MHz clock at: entry (i
 passed, presence words arrived, model values arrived, PSD parameters done, gather + Horner done, terms in LDS + ticket taken,
 and -- the wavefront that finishes the tile -- gates finished.  A wavefront that returns behind the presence test (its
 species absent from the tile) records entry, barrier, presence and the moment it leaves; its life is entry -> leaving.
+Round 10: inside the PSD parameters the moment the species' rule is done (its scalar operands have all arrived, the slope is
+formed: `us_rule`, the rest of `us_parameters` is the table position and the fall-speed moments), and the finish in parts,
+each the latest lane's, counted from the ticket: the species' sums read from LDS, the polarimetric part done and its eight
+stores issued, RVEL's operands arrived (the projection known), arithmetic done (RVEL and mask formed), stores issued; what
+is left of the finish is the wait for the stores.
 ONE isolated c2 sweep on one lane (CPOL_GATE1_RAY=1), and one of three lanes in flight."""
 import contextlib
 import json
@@ -23,7 +28,8 @@ from cosmo_pol_amd import RadarOperator  # noqa: E402
 def report(tag, tr):
     used = tr[:, 0] > 0
     t = tr[used].astype(np.int64)
-    nv = (tr[used, 6] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    nv = (tr[used, 6] & np.uint64(0xFF)).astype(np.int64)
+    t_rule = ((tr[used, 6] >> np.uint64(8)) & np.uint64(0xFFF)).astype(np.int64)        # values arrived -> the species' rule done
     sp = ((tr[used, 6] >> np.uint64(32)) & np.uint64(0xFF)).astype(np.int64)
     t_bar = ((tr[used, 6] >> np.uint64(40)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> barrier passed
     t_pre = ((tr[used, 6] >> np.uint64(52)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> presence words known
@@ -44,10 +50,22 @@ def report(tag, tr):
                          'finishers': int((m & last).sum()),
                          'us_life_not_finishing': round(float(us(life[m & ~last]).mean()), 2) if (m & ~last).any() else None,
                          'us_values': round(float(us(ph[m, 0]).mean()), 2), 'us_parameters': round(float(us(ph[m, 1]).mean()), 2),
+                         'us_rule': round(float(us(t_rule[m]).mean()), 2),
                          'us_gather_horner': round(float(us(ph[m, 2]).mean()), 2), 'us_lds_ticket': round(float(us(ph[m, 3]).mean()), 2),
                          'us_life_mean': round(float(us(life[m]).mean()), 2), 'us_life_p95': round(float(np.percentile(us(life[m]), 95)), 2)}
     if last.any():
         out['finishing'] = {'n': int(last.sum()), 'us_finish_mean': round(float(us(fin[last]).mean()), 2)}
+        w7 = tr[used, 7][last]
+        parts = (w7 & np.uint64(0xFFFFFFFF)) | ((w7 >> np.uint64(36)) << np.uint64(32))
+        cum = np.stack([((parts >> np.uint64(12 * q)) & np.uint64(0xFFF)).astype(np.int64) for q in range(5)], axis=1)
+        full = (cum > 0).all(axis=1)                          # (a tile without RVEL or without a gate to finish has no parts)
+        if full.any():
+            c = cum[full]
+            names = ('us_sums_read', 'us_pol_done', 'us_operands_arrived', 'us_arithmetic_done', 'us_stores_issued')
+            out['finishing'].update({'n_parts': int(full.sum()), 'since_ticket': {k: round(float(us(c[:, q]).mean()), 2) for q, k in enumerate(names)},
+                                     'us_entry_to_operands': round(float(us(c[:, 2]).mean()), 2),
+                                     'us_operand_wait': round(float(us(c[:, 2] - c[:, 1]).mean()), 2),
+                                     'us_store_wait': round(float(us(fin[last][full] - c[:, 4]).mean()), 2)})
     out['by_species_us_life'] = {int(k): round(float(us(life[(sp == k) & heavy]).mean()), 2) for k in np.unique(sp) if ((sp == k) & heavy).any()}
     # per gate tile (blockIdx.x = the workgroup's linear index mod 8): how much work it holds, when its last wavefront ends, and
     # on which XCD (XCC_ID of the hardware register) its wavefronts ran
