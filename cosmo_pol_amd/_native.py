@@ -187,12 +187,30 @@ class ObjectsMatch(C.Structure):
     _fields_ = [('o', Objects), ('n_pieces', C.c_void_p), ('pieces', C.c_void_p), ('covered', C.c_void_p)]
 
 
+class FractionProbabilities(C.Structure):
+    """cpol_fraction_probabilities: the neighbourhood ensemble probabilities of the blocks of a cpol_fractions
+    (cosmo_pol_amd/neighbourhood.py states the rule: `ensemble_sums`).  member_sum, member_any: NULL = not wanted."""
+    _fields_ = [('prob_sums', C.c_void_p), ('reliability', C.c_void_p), ('member_sum', C.c_void_p), ('member_any', C.c_void_p)]
+
+
+FRAC_PROB_MAX_BLOCKS = 256                          # CPOL_FRAC_PROB_MAX_BLOCKS
+
+
 class Fractions(C.Structure):
     """cpol_fractions: the fractions skill score's sums of one finished plane of a composite against an observed map
     (cosmo_pol_amd/neighbourhood.py states the rule).  objects: NULL (a zero-initialised struct) = no object cells."""
     _fields_ = [('field', C.c_int32), ('plane', C.c_int32), ('n_thresholds', C.c_int32), ('n_radii', C.c_int32),
                 ('thresholds', C.c_double * 4), ('radii', C.c_int32 * 8), ('observed', C.c_void_p), ('domain', C.c_void_p),
                 ('sums', C.c_void_p), ('totals', C.c_void_p), ('objects', C.POINTER(Objects))]
+
+
+FRAC_ENSEMBLE = 0x10000                             # CPOL_FRAC_ENSEMBLE, or-ed into Fractions.n_radii
+
+
+class FractionsEnsemble(C.Structure):
+    """cpol_fractions_ensemble: a cpol_fractions whose n_radii carries CPOL_FRAC_ENSEMBLE, and behind it the pointer to the
+    neighbourhood ensemble probabilities.  cpol_outputs.fractions points at `f`; the library reads beyond it only with the flag."""
+    _fields_ = [('f', Fractions), ('probabilities', C.POINTER(FractionProbabilities))]
 
 
 class _ObjectsNamed(object):
@@ -1253,7 +1271,18 @@ class Context(object):
                 keep += [tv, tf]
         return o, keep
 
-    def fractions_maps(self, maps, observed, spec, domain=None, tamper=None, objects=None):
+    @staticmethod
+    def probabilities_struct(fractions):
+        """(the Fractions to hand to the library in place of `fractions`, the FractionProbabilities behind it; what must stay alive):
+        `fractions` copied into a FractionsEnsemble, its n_radii flagged; the first result shares the wrapper's memory (pointers
+        bound to it later are seen by the library), the output pointers are the caller's."""
+        fe, q = FractionsEnsemble(), FractionProbabilities()
+        fe.f = fractions
+        fe.f.n_radii = fractions.n_radii | FRAC_ENSEMBLE
+        fe.probabilities = C.pointer(q)
+        return fe.f, q, [fe, q]
+
+    def fractions_maps(self, maps, observed, spec, domain=None, tamper=None, objects=None, probabilities=None):
         """Test hook (cpol_debug_read "fractions_maps"): the checks and k_frac_rows, k_frac_cols, k_frac_score on caller-supplied
         maps -> what neighbourhood.sums returns for them.  maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]); observed: float32
         [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
@@ -1261,12 +1290,16 @@ class Context(object):
         (the refusal tests).  `objects`: an objects.Objects or any object with `connectivity`, `min_area`, `max_objects` and
         `labels` (and `sums` with `weight` for the exact sums, `match` with `max_pieces` for the match): the kernels of
         cpol_obj.inl run too, and the result is (the sums, what objects.cells returns for the maps);
-        `tamper` then finds the cpol_objects at f.objects.contents."""
+        `tamper` then finds the cpol_objects at f.objects.contents.  `probabilities`: a neighbourhood.Probabilities or any object
+        with `maps` and `any_maps` (which of the two maps are wanted): k_frac_members runs too, and the result gains, as its last
+        element, what neighbourhood.ensemble_sums returns for the maps; the cpol_fractions is then the first member of a
+        cpol_fractions_ensemble, and `tamper` finds the cpol_fraction_probabilities as the Python attribute f.probabilities."""
         from . import neighbourhood as NB
 
         class Hook(C.Structure):
+            # (f and the pointer behind it: a cpol_fractions_ensemble where f.n_radii says so)
             _fields_ = [('n_blocks', C.c_int32), ('n_y', C.c_int32), ('n_x', C.c_int32), ('pad_', C.c_int32), ('maps', C.c_void_p),
-                        ('f', Fractions)]
+                        ('f', Fractions), ('probabilities', C.POINTER(FractionProbabilities))]
         m = np.ascontiguousarray(maps, dtype=np.float32)
         if m.ndim == 2:
             m = m[None]
@@ -1317,15 +1350,36 @@ class Context(object):
                           np.full((m.shape[0], nt, 2, objects.max_objects), 0xDEADBEEF, dtype=np.uint32)]
                 okeep[0].n_pieces, okeep[0].pieces, okeep[0].covered = [q.ctypes.data for q in omatch]
             keep += okeep
+        q = None
+        if probabilities is not None:
+            q = FractionProbabilities()
+            f.n_radii |= FRAC_ENSEMBLE
+            hk.probabilities = C.pointer(q)
+            nb = m.shape[0]
+            # (a refused call may carry more blocks than the table has rows for: the arrays stay those of the limit)
+            pout = [np.full((nt, nr, 3), 0xDEADBEEF, dtype=np.uint64),
+                    np.full((nt, nr, min(nb, FRAC_PROB_MAX_BLOCKS) + 1, 2), 0xDEADBEEF, dtype=np.uint64),
+                    np.full((nt, nr) + m.shape[1:], 0xDEADBEEF, dtype=np.uint32) if probabilities.maps else None,
+                    np.full((nt, nr) + m.shape[1:], 0xDEADBEEF, dtype=np.uint32) if probabilities.any_maps else None]
+            q.prob_sums, q.reliability = pout[0].ctypes.data, pout[1].ctypes.data
+            q.member_sum = pout[2].ctypes.data if pout[2] is not None else None
+            q.member_any = pout[3].ctypes.data if pout[3] is not None else None
+            keep += [q] + pout
         hk.f = f
         if tamper is not None:
-            keep.append(tamper(hk.f))
+            fv = hk.f                                 # (shares hk's memory)
+            if q is not None:
+                fv.probabilities = q                  # (a Python attribute: the struct itself has no such member)
+            keep.append(tamper(fv))
         rc = int(self.lib.cpol_debug_read(self.h, b'fractions_maps', C.byref(hk), C.sizeof(hk)))
         self._check(rc, 'cpol_debug_read(fractions_maps)')
         del keep
+        out = [NB.result(spec, s, t)]
         if objects is not None:
-            return NB.result(spec, s, t), OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums, omatch)
-        return NB.result(spec, s, t)
+            out.append(OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums, omatch))
+        if probabilities is not None:
+            out.append(NB.ensemble_result(spec, m.shape[0], *pout))
+        return out[0] if len(out) == 1 else tuple(out)
 
     @staticmethod
     def spectrum_moments_struct(spec):

@@ -45,6 +45,7 @@
 #include "cpol_hist.inl"
 #include "cpol_comp.inl"
 #include "cpol_frac.inl"
+#include "cpol_frac_prob.inl"
 #include "cpol_obj.inl"
 #include "cpol_shadow.inl"
 
@@ -219,8 +220,9 @@ struct cpol_ctx {
     std::vector<double> ctab_host;         // ... and what b_ctab holds
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
-    // the call at hand
-    DevBuf b_fsat, b_fobs, b_fout[12], b_fmaps;
+    // the call at hand; prob_sums, reliability, member_sum and member_any of the neighbourhood ensemble probabilities
+    // (cpol_fraction_probabilities) are b_fout[12 ... 15]
+    DevBuf b_fsat, b_fobs, b_fout[16], b_fmaps;
     FracPlan fplan;
     // object cells (cpol_objects, beside a cpol_fractions): the labelling scratch and the plan of the call at hand; n_objects, table
     // and labels are b_fout[2 ... 4], volume, skipped, field and field_cells of the exact sums b_fout[5 ... 8]; the sums'
@@ -2870,13 +2872,22 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
 // (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
 enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_OBJ_VOLUME, FR_OBJ_SKIPPED, FR_OBJ_FIELD, FR_OBJ_FIELD_CELLS,
-       FR_OBJ_N_PIECES, FR_OBJ_PIECES, FR_OBJ_COVERED, FR_N };
-static_assert(FR_N == 12, "cpol_ctx::b_fout holds one buffer per array");
+       FR_OBJ_N_PIECES, FR_OBJ_PIECES, FR_OBJ_COVERED, FR_PROB_SUMS, FR_RELIABILITY, FR_MEMBER_SUM, FR_MEMBER_ANY, FR_N };
+static_assert(FR_N == 16, "cpol_ctx::b_fout holds one buffer per array");
 // arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
-// composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for)
+// composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for); last the four
+// arrays of the neighbourhood ensemble probabilities (pl.prob.on; the two maps when asked for)
 static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, PlaceArray *arr)
 {
     for (int k = 0; k < FR_N; ++k) { arr[k] = PlaceArray{}; arr[k].product = PLACE_SWEEP; }
+    if (pl.prob.on) {
+        const cpol_fraction_probabilities *const q = frac_probabilities(f);
+        const FracProbPlan &pp = pl.prob;
+        arr[FR_PROB_SUMS].user = (uintptr_t)q->prob_sums;      arr[FR_PROB_SUMS].bytes = pp.prob_sums_bytes;     arr[FR_PROB_SUMS].produced = true;
+        arr[FR_RELIABILITY].user = (uintptr_t)q->reliability;  arr[FR_RELIABILITY].bytes = pp.reliability_bytes; arr[FR_RELIABILITY].produced = true;
+        arr[FR_MEMBER_SUM].user = (uintptr_t)q->member_sum;    arr[FR_MEMBER_SUM].bytes = pp.member_sum_bytes;   arr[FR_MEMBER_SUM].produced = pp.member_sum;
+        arr[FR_MEMBER_ANY].user = (uintptr_t)q->member_any;    arr[FR_MEMBER_ANY].bytes = pp.member_any_bytes;   arr[FR_MEMBER_ANY].produced = pp.member_any;
+    }
     arr[FR_SUMS].user = (uintptr_t)f->sums;     arr[FR_SUMS].bytes = pl.sums_bytes;
     arr[FR_TOTALS].user = (uintptr_t)f->totals; arr[FR_TOTALS].bytes = pl.totals_bytes;
     arr[FR_SUMS].produced = arr[FR_TOTALS].produced = true;
@@ -2995,7 +3006,7 @@ static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, con
 }
 
 // plane: block 0's plane on the device; obs_on_host: `observed` and `domain` are host arrays (copied to b_fobs on `st` first),
-// else memory the device reads in place; T: where `sums` and `totals` go
+// else memory the device reads in place; T: where `sums` and `totals` (and the arrays of the objects and the probabilities) go
 static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &pl, const ObjPlan &op, const float *plane, long plane_stride,
                        bool obs_on_host, void *const T[FR_N], hipStream_t st)
 {
@@ -3029,13 +3040,28 @@ static int frac_launch(cpol_ctx *ctx, const cpol_fractions *f, const FracPlan &p
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_frac_score, dim3((unsigned)pl.grid_score), dim3(FRAC_THREADS), 0, st, a);
     HIPCHK(hipGetLastError());
+    if (pl.prob.on) {              // the neighbourhood ensemble probabilities: one kernel on the finished tables
+        const FracProbPlan &pp = pl.prob;
+        FracProbArgs q{};
+        q.f = a;
+        q.prob_sums = (unsigned long long *)T[FR_PROB_SUMS]; q.reliability = (unsigned long long *)T[FR_RELIABILITY];
+        q.member_sum = pp.member_sum ? (unsigned *)T[FR_MEMBER_SUM] : nullptr;
+        q.member_any = pp.member_any ? (unsigned *)T[FR_MEMBER_ANY] : nullptr;
+        q.n_members = (int)pl.n_blocks; q.table_entries = pp.table_entries;
+        HIPCHK(hipMemsetAsync(q.prob_sums, 0, pp.prob_sums_bytes, st));
+        HIPCHK(hipMemsetAsync(q.reliability, 0, pp.reliability_bytes, st));
+        hipLaunchKernelGGL(k_frac_members, dim3((unsigned)pp.grid), dim3(FRAC_THREADS), 0, st, q);
+        HIPCHK(hipGetLastError());
+    }
     if (op.on) return obj_launch(ctx, a, pl, op, T, st);
     return CPOL_OK;
 }
 
 // The test hook cpol_debug_read "fractions_maps": the checks and the three kernels on caller-supplied maps (host memory in, host
 // memory out, blocking) -- the kernels on maps no sweep produces (every value class, rows and columns across wavefront chunks,
-// windows clipped at every border, the smallest and the longest grids).
+// windows clipped at every border, the smallest and the longest grids).  f.objects rides the embedded struct, and with
+// CPOL_FRAC_ENSEMBLE in f.n_radii the pointer behind f makes the two a cpol_fractions_ensemble: with them the object kernels and
+// k_frac_members run on the same maps.
 struct FracHook {
     int32_t n_blocks, n_y, n_x, pad_;
     const float *maps;                      // [n_blocks][n_y][n_x]
@@ -4796,6 +4822,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     }
     if (!strcmp(name, "fractions_maps")) {          // a CONTROL name: dst points to a FracHook
         if (!dst || max_bytes < (int64_t)sizeof(FracHook)) { ctx->err = "cpol_debug_read(fractions_maps): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        if (frac_is_ensemble(&((const FracHook *)dst)->f) && max_bytes < (int64_t)(sizeof(FracHook) + sizeof(void *))) {
+            ctx->err = "cpol_debug_read(fractions_maps): CPOL_FRAC_ENSEMBLE needs the pointer behind f";
+            return CPOL_ERR_ARG;
+        }
         return frac_hook(ctx, (const FracHook *)dst);
     }
     if (!strcmp(name, "composite_plane")) {         // {uploads, hits} of this context's gate-plane store

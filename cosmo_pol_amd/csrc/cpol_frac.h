@@ -3,7 +3,9 @@
 // decided by frac_check() from plain numbers.  Plain C++ without HIP types, so that a host program can include it
 // (tests/c_host/frac_check.cpp, tests/test_neighbourhood_cpu.py check it without a GPU).  The kernels are k_frac_rows,
 // k_frac_cols and k_frac_score (cpol_frac.inl); the rule is stated in include/cosmo_pol_amd.h and
-// cosmo_pol_amd/neighbourhood.py.
+// cosmo_pol_amd/neighbourhood.py.  The neighbourhood ensemble probabilities (cpol_fraction_probabilities, k_frac_members in
+// cpol_frac_prob.inl) have their sub-plan and their refusals here too: frac_prob_check (tests/c_host/frac_prob_check.cpp,
+// tests/test_neighbourhood_prob_cpu.py).
 #pragma once
 
 #include "cpol_comp.h"
@@ -19,6 +21,24 @@ constexpr int FRAC_ROWS = FRAC_THREADS / 64;          // rows of a workgroup of 
 // cells of a workgroup of k_frac_score, four per thread: a 300 x 300 map gives 88 workgroups per (block, threshold), each with
 // ONE atomic addition per sum
 constexpr int FRAC_CELLS = 4 * FRAC_THREADS;
+constexpr int FRAC_PROB_MAX_BLOCKS = CPOL_FRAC_PROB_MAX_BLOCKS;   // bounds `reliability` and the LDS table of k_frac_members
+
+// a cpol_fractions that is the first member of a cpol_fractions_ensemble says so in n_radii (a positive count or-ed with
+// CPOL_FRAC_ENSEMBLE; a negative n_radii has the bit set too and is no flag): only then is anything behind the struct read
+inline bool frac_is_ensemble(const cpol_fractions *f) { return f->n_radii > 0 && (f->n_radii & CPOL_FRAC_ENSEMBLE) != 0; }
+inline int frac_n_radii(const cpol_fractions *f) { return frac_is_ensemble(f) ? f->n_radii & ~CPOL_FRAC_ENSEMBLE : f->n_radii; }
+inline const cpol_fraction_probabilities *frac_probabilities(const cpol_fractions *f)
+{
+    return frac_is_ensemble(f) ? ((const cpol_fractions_ensemble *)f)->probabilities : nullptr;
+}
+
+// the neighbourhood ensemble probabilities of a call that passed (cpol_fractions_ensemble.probabilities; on == false: off)
+struct FracProbPlan {
+    bool on = false, member_sum = false, member_any = false;
+    long grid = 0;                                    // workgroups of k_frac_members: n_thr * n_radii * score_groups
+    int table_entries = 0;                            // uint32 entries of its LDS table: (n_blocks + 1) * 2
+    size_t prob_sums_bytes = 0, reliability_bytes = 0, member_sum_bytes = 0, member_any_bytes = 0;
+};
 
 // a call that passed: the numbers the launches need
 struct FracPlan {
@@ -36,7 +56,42 @@ struct FracPlan {
     long grid_rows = 0, grid_cols = 0, grid_score = 0;   // workgroups of the three launches
     int col_chunks = 0, score_groups = 0;             // 64-column chunks of a table; workgroups of k_frac_score per (block, threshold)
     size_t sums_bytes = 0, totals_bytes = 0;
+    FracProbPlan prob;
 };
+
+// NO OVERFLOW of the ensemble sums (cosmo_pol_amd.h, cpol_fraction_probabilities): with c = min(2 r_max + 1, n_y) * min(2 r_max
+// + 1, n_x) the call passes only if M * c < 2^32 and n_y * n_x * (M * c)^2 < 2^64.  M * c < 2^8 * 2^20 and cells < 2^20 under
+// the limits that passed, so the product is < 2^76: formed in 128 bits, the check cannot overflow itself.
+inline bool frac_prob_overflows(int n_x, int n_y, long n_blocks, int r_max)
+{
+    const long side = 2L * r_max + 1;
+    const unsigned __int128 c = (unsigned __int128)(side < n_y ? side : n_y) * (unsigned __int128)(side < n_x ? side : n_x);
+    const unsigned __int128 mc = (unsigned __int128)n_blocks * c;
+    if (mc >> 32) return true;
+    return (((unsigned __int128)n_y * (unsigned __int128)n_x * mc * mc) >> 64) != 0;
+}
+
+// every refusal of a cpol_fraction_probabilities beside a cpol_fractions whose plan *pl passed so far; q == NULL: off.  NULL:
+// accepted and pl->prob filled; else the reason (CPOL_ERR_ARG).  Touches nothing else.
+inline const char *frac_prob_check(const cpol_fraction_probabilities *q, FracPlan *pl)
+{
+    pl->prob = FracProbPlan{};
+    if (!q) return nullptr;
+    if (!q->prob_sums || !q->reliability) return "probabilities: prob_sums or reliability is NULL";
+    if (pl->n_blocks > FRAC_PROB_MAX_BLOCKS) return "probabilities: at most 256 blocks (CPOL_FRAC_PROB_MAX_BLOCKS)";
+    if (frac_prob_overflows(pl->n_x, pl->n_y, pl->n_blocks, pl->radii[pl->n_radii - 1]))
+        return "probabilities: the sums could overflow (needs n_blocks * c < 2^32 and n_y * n_x * (n_blocks * c)^2 < 2^64, c the cells of the largest clipped window)";
+    FracProbPlan &pp = pl->prob;
+    pp.on = true; pp.member_sum = q->member_sum != nullptr; pp.member_any = q->member_any != nullptr;
+    pp.grid = (long)pl->n_thr * pl->n_radii * pl->score_groups;       // (at most 4 * 8 * 1022 workgroups)
+    pp.table_entries = ((int)pl->n_blocks + 1) * 2;
+    pp.prob_sums_bytes = (size_t)pl->n_thr * pl->n_radii * 3 * sizeof(uint64_t);
+    pp.reliability_bytes = (size_t)pl->n_thr * pl->n_radii * pp.table_entries * sizeof(uint64_t);
+    const size_t map_bytes = (size_t)pl->n_thr * pl->n_radii * (size_t)pl->cells * sizeof(uint32_t);
+    pp.member_sum_bytes = pp.member_sum ? map_bytes : 0;
+    pp.member_any_bytes = pp.member_any ? map_bytes : 0;
+    return nullptr;
+}
 
 // what does not depend on the composite: thresholds, radii, pointers, the scratch and the grids for n_blocks maps of n_y x n_x
 inline const char *frac_check_maps(const cpol_fractions *f, int n_x, int n_y, long n_blocks, FracPlan *pl)
@@ -48,15 +103,16 @@ inline const char *frac_check_maps(const cpol_fractions *f, int n_x, int n_y, lo
         if (!(t == t)) return "a threshold is NaN";
         pl->thr[j] = comp_f32(t);
     }
-    if (f->n_radii < 1 || f->n_radii > FRAC_MAX_RADII) return "n_radii must lie in 1 ... 8";
-    for (int j = 0; j < f->n_radii; ++j) {
+    const int n_radii = frac_n_radii(f);
+    if (n_radii < 1 || n_radii > FRAC_MAX_RADII) return "n_radii must lie in 1 ... 8";
+    for (int j = 0; j < n_radii; ++j) {
         if (f->radii[j] < 0 || f->radii[j] > FRAC_MAX_RADIUS) return "a radius must lie in 0 ... 1023";
         if (j > 0 && f->radii[j] <= f->radii[j - 1]) return "the radii must be strictly ascending";
         pl->radii[j] = f->radii[j];
     }
     if (!f->observed) return "observed is NULL";
     if (!f->sums || !f->totals) return "sums or totals is NULL";
-    pl->n_thr = f->n_thresholds; pl->n_radii = f->n_radii;
+    pl->n_thr = f->n_thresholds; pl->n_radii = n_radii;
     pl->n_x = n_x; pl->n_y = n_y; pl->cells = (long)n_x * n_y; pl->n_blocks = n_blocks;
     pl->table = (long)(n_y + 1) * (n_x + 1);
     // (n_blocks < 2^31 rows of a call, at most 4 thresholds and 2^20 entries of 4 bytes: no overflow of long)
@@ -72,7 +128,7 @@ inline const char *frac_check_maps(const cpol_fractions *f, int n_x, int n_y, lo
     if (pl->grid_rows >= (1L << 31) || pl->grid_cols >= (1L << 31) || pl->grid_score >= (1L << 31)) return "too many workgroups in one call";
     pl->sums_bytes = (size_t)n_blocks * pl->n_thr * pl->n_radii * 3 * sizeof(uint64_t);
     pl->totals_bytes = (size_t)n_blocks * pl->n_thr * 3 * sizeof(uint64_t);
-    return nullptr;
+    return frac_prob_check(frac_probabilities(f), pl);
 }
 
 // every refusal of a cpol_fractions for a sweep call; c: the call's cpol_composite (NULL: none), cp: its plan, which passed

@@ -22,7 +22,36 @@ THE RULE
              (n_forecast, n_observed, n_domain).  `result` names them.
   Score      FSS = 1 - diff2 / (forecast2 + observed2) in float64 on the host (`fss`), NaN where both maps are empty.
   Limits     the summed-area tables of all blocks and thresholds and of the observation, (n_blocks + 1) * n_thr * (n_y + 1) *
-             (n_x + 1) * 4 bytes, at most MAX_SCRATCH_BYTES."""
+             (n_x + 1) * 4 bytes, at most MAX_SCRATCH_BYTES.
+
+NEIGHBOURHOOD ENSEMBLE PROBABILITIES (cpol_fraction_probabilities; `Probabilities`, `ensemble_sums`; the kernel is k_frac_members,
+cosmo_pol_amd/csrc/cpol_frac_prob.inl): what a convective-scale ensemble publishes of its members' maps -- the neighbourhood
+ensemble probability (NEP) and the neighbourhood maximum ensemble probability (NMEP; Schwartz and Sobash 2017, Mon. Wea. Rev.
+145, 3397-3418), the ensemble FSS of the ensemble-mean fraction (Schwartz et al. 2010; Duc et al. 2013) and a reliability table,
+from which the Brier score, the reliability diagram and the ROC follow.
+THE RULE
+  Inputs are those of cpol_fractions, unchanged.  F[b][t], O[t], NF[b][t][w][y][x] and NO[t][w][y][x] are the binary maps and
+  clipped window counts defined there.  M = n_blocks; in an ensemble call a block is a member.
+  Per threshold t, radius index w and cell:
+    S[t][w][y][x] = sum over b of NF[b][t][w][y][x] (uint32).  NEP is S / (M * window_cells); the division is the host's.
+    A[t][w][y][x] = #{ b : NF[b][t][w][y][x] > 0 } (uint32, 0 ... M).  NMEP is A / M.
+    OA[t][w][y][x] = NO[t][w][y][x] > 0.
+  Both maps are written for EVERY cell of the grid.  The domain only decides which cells are set and which cells are summed.
+  Sums over the cells of the domain, uint64:
+    prob_sums[t][w][3] = (diff2, forecast2, observed2): diff2 = sum (S - M * NO)^2, forecast2 = sum S^2, observed2 = M^2 * sum
+    NO^2.  neighbourhood.fss applied to these three gives the ensemble FSS unchanged.  With M == 1 they equal block 0's row of
+    `sums`.
+    reliability[t][w][k][o], k = 0 ... M, o = 0 | 1: the number of domain cells with A == k and OA == o.  At radius 0 this is the
+    classic table "k of M members exceed, observed yes or no".  At larger radii it is the NMEP against the neighbourhood-maximum
+    observation.  Every [t][w] slice sums to n_domain.
+  Limits are conditions, not measurements.
+    1 <= n_blocks <= MAX_PROB_BLOCKS (256); it bounds `reliability` and the kernel's LDS table.
+    NO OVERFLOW, checked before anything is queued (`overflows`).  Let c = min(2 * r_max + 1, n_y) * min(2 * r_max + 1, n_x).
+    The call is refused unless M * c < 2^32 and n_y * n_x * (M * c)^2 < 2^64.  |S - M * NO| <= M * c, so the bound covers all
+    three sums.
+  The result depends neither on the order of the blocks nor on how the work is cut.
+  NOT BUILT: Probabilities over an objects.Objects in Python (the C structs may stand side by side); a member list cut into
+  several chunks (the sums are not additive over chunks)."""
 import numpy as np
 
 from .composite import FIELDS, Composite, Maps
@@ -31,6 +60,7 @@ MAX_THRESHOLDS = 4
 MAX_RADII = 8
 MAX_RADIUS = 1023
 MAX_SCRATCH_BYTES = 1 << 30
+MAX_PROB_BLOCKS = 256
 
 _U64, _I64 = np.uint64, np.int64
 
@@ -291,3 +321,233 @@ class Scores(object):
             out['fractions'] = dict(fr[-1], **{k: cat([q[k] for q in fr]) for k in
                                                ('diff2', 'forecast2', 'observed2', 'n_forecast', 'n_observed', 'n_domain')})
         return out
+
+
+# ---------------------------------------------------------------------------------------- neighbourhood ensemble probabilities
+class Probabilities(object):
+    """A `Fractions` whose scored call also reduces the neighbourhood ensemble probabilities of its blocks (the rule at the head of
+    this module): the sums of the ensemble FSS and the reliability table always, the S maps (`maps`: NEP = S / (M *
+    window_cells)) and the A maps (`any_maps`: NMEP = A / M) when asked for.  Accepted wherever a Fractions is.  ValueError over
+    an objects.Objects: that combination is not built in Python."""
+
+    def __init__(self, fractions, maps=False, any_maps=False):
+        if not isinstance(fractions, Fractions):
+            from .objects import Objects
+            if isinstance(fractions, Objects):
+                raise ValueError('Probabilities over an objects.Objects is not built in Python: wrap the Fractions, and ask for '
+                                 'the object cells in a call of their own')
+            raise ValueError('fractions: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (fractions,))
+        self.fractions, self.maps, self.any_maps = fractions, bool(maps), bool(any_maps)
+
+    composite = property(lambda self: self.fractions.composite)
+    thresholds = property(lambda self: self.fractions.thresholds)
+    thresholds_given = property(lambda self: self.fractions.thresholds_given)
+    radii = property(lambda self: self.fractions.radii)
+    n_x = property(lambda self: self.fractions.n_x)
+    n_y = property(lambda self: self.fractions.n_y)
+
+    @property
+    def key(self):
+        return (self.fractions.key, self.maps, self.any_maps)
+
+    def __eq__(self, other):
+        return isinstance(other, Probabilities) and self.key == other.key
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        return 'Probabilities(%r, maps=%r, any_maps=%r)' % (self.fractions, self.maps, self.any_maps)
+
+
+def _fractions_of(spec):
+    return spec.fractions if isinstance(spec, Probabilities) else spec
+
+
+def overflows(n_x, n_y, n_blocks, r_max):
+    """The NO OVERFLOW condition of the rule in Python integers: True where a call is refused."""
+    side = 2 * int(r_max) + 1
+    mc = int(n_blocks) * min(side, int(n_y)) * min(side, int(n_x))
+    return mc >= 1 << 32 or int(n_y) * int(n_x) * mc * mc >= 1 << 64
+
+
+def ensemble_result(spec, n_blocks, prob_sums, reliability, member_sum=None, member_any=None):
+    """The output arrays named: {'diff2' | 'forecast2' | 'observed2': uint64 [n_thr, n_radii], 'reliability': uint64 [n_thr,
+    n_radii, M + 1, 2], 'member_sum' | 'member_any': uint32 [n_thr, n_radii, n_y, n_x] when given, 'n_blocks', 'thresholds',
+    'radii'}."""
+    out = {'diff2': prob_sums[..., 0], 'forecast2': prob_sums[..., 1], 'observed2': prob_sums[..., 2], 'reliability': reliability,
+           'n_blocks': int(n_blocks), 'thresholds': spec.thresholds, 'radii': spec.radii}
+    if member_sum is not None:
+        out['member_sum'] = member_sum
+    if member_any is not None:
+        out['member_any'] = member_any
+    return out
+
+
+def ensemble_sums(spec, plane_maps, observed, domain=None):
+    """The rule of the neighbourhood ensemble probabilities in NumPy.  spec: a Fractions or a Probabilities; plane_maps: float32
+    [n_blocks, n_y, n_x] (or [n_y, n_x]: one block); observed, domain: see check_maps.  Returns what `ensemble_result` describes,
+    always with both maps.  ValueError for more than MAX_PROB_BLOCKS blocks and where the sums could overflow."""
+    spec = _fractions_of(spec)
+    m = np.asarray(plane_maps)
+    if m.dtype != np.float32:
+        raise ValueError('plane_maps must be float32, got %s' % m.dtype)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] != (spec.n_y, spec.n_x) or m.shape[0] < 1:
+        raise ValueError('plane_maps: [n_blocks, %d, %d], got %r' % (spec.n_y, spec.n_x, m.shape))
+    M = m.shape[0]
+    if M > MAX_PROB_BLOCKS:
+        raise ValueError('probabilities: at most %d blocks, got %d' % (MAX_PROB_BLOCKS, M))
+    if overflows(spec.n_x, spec.n_y, M, spec.radii[-1]):
+        raise ValueError('probabilities: the sums of %d blocks with radius %d could overflow' % (M, spec.radii[-1]))
+    o, domain = check_maps(spec, observed, domain)
+    dom = np.ones(o.shape, dtype=bool) if domain is None else domain != 0
+    thr = spec.thresholds[:, None, None]
+    nt, nr = len(spec.thresholds), len(spec.radii)
+    S = np.zeros((nt, nr) + o.shape, dtype=_I64)
+    A = np.zeros((nt, nr) + o.shape, dtype=_I64)
+    with np.errstate(invalid='ignore'):
+        O = dom & (o == o) & (o[None] >= thr)                               # [n_thr, n_y, n_x]
+        for b in range(M):                                                  # (a block at a time: 256 blocks need no 256 tables)
+            NF = _window_counts(dom & (m[b] == m[b]) & (m[b][None] >= thr), spec.radii)
+            S += NF
+            A += NF > 0
+    NO = _window_counts(O, spec.radii)                                      # [n_thr, n_radii, n_y, n_x]
+    # (uint64 from the squares on: the condition above bounds every term below 2^64 and every sum too, not below 2^63)
+    s = np.empty((nt, nr, 3), dtype=_U64)
+    Sd, NOd = S[..., dom], NO[..., dom] * M
+    for k, v in enumerate((np.abs(Sd - NOd), Sd, NOd)):
+        v = v.astype(_U64)
+        s[..., k] = (v * v).sum(axis=-1, dtype=_U64)
+    rel = np.zeros((nt, nr, M + 1, 2), dtype=_U64)
+    Ad, OAd = A[..., dom], (NO > 0)[..., dom]
+    for t in range(nt):
+        for w in range(nr):
+            rel[t, w] = np.bincount(Ad[t, w] * 2 + OAd[t, w], minlength=2 * (M + 1)).reshape(M + 1, 2).astype(_U64)
+    return ensemble_result(spec, M, s, rel, S.astype(np.uint32), A.astype(np.uint32))
+
+
+def window_cells(spec, domain=None):
+    """int64 [n_radii, n_y, n_x]: the cells of each clipped window -- what a set count NF is a fraction of.  With `domain` (uint8 or
+    bool [n_y, n_x]) the cells of the domain inside it: outside the domain nothing is set."""
+    spec = _fractions_of(spec)
+    inside = np.ones((spec.n_y, spec.n_x), dtype=bool) if domain is None else np.asarray(domain).reshape(spec.n_y, spec.n_x) != 0
+    return _window_counts(inside, spec.radii)
+
+
+def nep(res, cells):
+    """The neighbourhood ensemble probability, float64 [n_thr, n_radii, n_y, n_x]: member_sum / (n_blocks * cells), `cells` from
+    window_cells; NaN where a window holds no cell of the domain.  ValueError when the S maps were not asked for."""
+    if 'member_sum' not in res:
+        raise ValueError("nep: needs the S maps (Probabilities(maps=True)), the result has no 'member_sum'")
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return res['member_sum'].astype(np.float64) / (float(res['n_blocks']) * np.asarray(cells, dtype=np.float64))
+
+
+def nmep(res):
+    """The neighbourhood maximum ensemble probability, float64 [n_thr, n_radii, n_y, n_x]: member_any / n_blocks.  ValueError
+    when the A maps were not asked for."""
+    if 'member_any' not in res:
+        raise ValueError("nmep: needs the A maps (Probabilities(any_maps=True)), the result has no 'member_any'")
+    return res['member_any'].astype(np.float64) / float(res['n_blocks'])
+
+
+def _table(res):
+    n = res['reliability'].astype(np.float64)                               # [n_thr, n_radii, M + 1, 2]
+    return n, np.arange(n.shape[-2], dtype=np.float64) / float(n.shape[-2] - 1)
+
+
+def brier(res):
+    """The Brier score of the forecast probability k / M against the observed event, float64 [n_thr, n_radii], from the
+    reliability table: sum_k (n[k, 0] (k / M)^2 + n[k, 1] (k / M - 1)^2) / n_domain; NaN for an empty domain."""
+    n, p = _table(res)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return (n[..., 0] * p ** 2 + n[..., 1] * (p - 1.0) ** 2).sum(axis=-1) / n.sum(axis=(-2, -1))
+
+
+def reliability_curve(res):
+    """The reliability diagram: {'probability': k / M, float64 [M + 1]; 'observed_frequency': n[k, 1] / (n[k, 0] + n[k, 1]),
+    float64 [n_thr, n_radii, M + 1], NaN where no cell forecast k / M; 'count': uint64 [n_thr, n_radii, M + 1]}."""
+    n, p = _table(res)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return {'probability': p, 'observed_frequency': n[..., 1] / n.sum(axis=-1), 'count': res['reliability'].sum(axis=-1)}
+
+
+def roc(res):
+    """The relative operating characteristic of the decision "at least k members", k = 0 ... M + 1: {'pod': hits / observed yes,
+    'pofd': false alarms / observed no, float64 [n_thr, n_radii, M + 2], from (1, 1) at k = 0 down to (0, 0); NaN where the
+    event was never (always) observed; 'area': the trapezoid area under pod over pofd, float64 [n_thr, n_radii]}."""
+    n, _ = _table(res)
+    tail = np.concatenate([np.cumsum(n[..., ::-1, :], axis=-2)[..., ::-1, :], np.zeros(n.shape[:-2] + (1, 2))], axis=-2)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        pofd, pod = tail[..., 0] / tail[..., :1, 0], tail[..., 1] / tail[..., :1, 1]
+    area = -((pofd[..., 1:] - pofd[..., :-1]) * (pod[..., 1:] + pod[..., :-1]) / 2.0).sum(axis=-1)
+    return {'pod': pod, 'pofd': pofd, 'area': area}
+
+
+class EnsembleScores(Scores):
+    """A scored composite of ONE sweep call WITH the neighbourhood ensemble probabilities of its blocks: a `Scores`, and behind a
+    finishing call the cpol_fractions_ensemble around its cpol_fractions, which points to the cpol_fraction_probabilities.  The new slots are handled the way `sums`
+    and `totals` are."""
+    one_chunk = 'the sums are not additive over chunks'     # (_ensemble_reduced: needs the members in one chunk)
+    _OWN = ('prob_sums', 'reliability', 'member_sum', 'member_any')
+
+    def __init__(self, spec, observed=None, domain=None, keep_gates=False, phase=3, rays_per_block=0, distributed=False):
+        if not isinstance(spec, Probabilities):
+            raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Probabilities, got %r' % (spec,))
+        Scores.__init__(self, spec.fractions, observed, domain, keep_gates, phase, rays_per_block, distributed)
+        self.prob, self.q = spec, None
+
+    def _wanted(self):
+        return self._OWN[:2] + (('member_sum',) if self.prob.maps else ()) + (('member_any',) if self.prob.any_maps else ())
+
+    def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
+        structs, keep = Scores.attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take)
+        self.q = None
+        if self.f is None:                        # (no cpol_fractions in this call: nothing to hang on)
+            return structs, keep
+        if self.n_blocks > MAX_PROB_BLOCKS:
+            raise ValueError('probabilities: at most %d blocks, got %d' % (MAX_PROB_BLOCKS, self.n_blocks))
+        if overflows(self.spec.n_x, self.spec.n_y, self.n_blocks, self.spec.radii[-1]):
+            raise ValueError('probabilities: the sums of %d blocks with radius %d could overflow' % (self.n_blocks, self.spec.radii[-1]))
+        # the cpol_fractions becomes the first member of a cpol_fractions_ensemble; self.f is from here on the copy inside it
+        self.f, self.q, qkeep = native.Context.probabilities_struct(self.f)
+        return dict(structs, fractions=self.f), keep + qkeep
+
+    def arrays(self):
+        out = Scores.arrays(self)
+        if self.phase & 2:
+            spec, nt, nr = self.spec, len(self.spec.thresholds), len(self.spec.radii)
+            shapes = {'prob_sums': (np.uint64, (nt, nr, 3)), 'reliability': (np.uint64, (nt, nr, self.n_blocks + 1, 2)),
+                      'member_sum': (np.uint32, (nt, nr, spec.n_y, spec.n_x)), 'member_any': (np.uint32, (nt, nr, spec.n_y, spec.n_x))}
+            out = out + [(k,) + shapes[k] for k in self._wanted()]
+        return out
+
+    def bind(self, path, address):
+        if path in self._OWN:
+            setattr(self.q, path, address)
+        else:
+            Scores.bind(self, path, address)
+
+    def bind_device(self, entry):
+        # the scores' entries and 'prob_sums' | 'reliability' | 'member_sum' | 'member_any': device pointers
+        rest = {}
+        for k, ptr in entry.items():
+            if k in self._OWN and self.phase & 2 and k in self._wanted():
+                self.bind(k, ptr)
+            else:
+                rest[k] = ptr
+        Scores.bind_device(self, rest)
+
+    def finish(self, w, coords):
+        own = {k: w.pop(k) for k in self._wanted()}
+        out = Scores.finish(self, w, coords)
+        out['probabilities'] = ensemble_result(self.spec, self.n_blocks, own['prob_sums'], own['reliability'],
+                                               own.get('member_sum'), own.get('member_any'))
+        return out
+
+    def join(self, parts, cat):
+        if len(parts) > 1:
+            raise ValueError('probabilities: needs the members in one chunk (%s)' % self.one_chunk)
+        return Scores.join(self, parts, cat)

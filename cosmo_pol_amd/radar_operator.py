@@ -2401,6 +2401,8 @@ class RadarOperator(object):
         n_rays = len(np.asarray(azimuths).reshape(-1))
         chunks = self._shared_member_chunks(self._lane(lane), members, sub.n_sub * len(rr) * n_rays)
         name, phase = product.name, product.phase
+        if len(chunks) > 1 and getattr(product, 'one_chunk', None):
+            raise ValueError('simulate_rays_ensemble_%s: Probabilities needs the members in one chunk (%s)' % (name, product.one_chunk))
         if len(chunks) > 1 and device_outputs is not None:
             raise ValueError('simulate_rays_ensemble_%s: device outputs need the members in one chunk' % name)
         if len(chunks) > 1 and per_member and phase != 3:
@@ -2506,8 +2508,10 @@ class RadarOperator(object):
     def _fss_product(self, spec, observed, domain, device_outputs, keep_gates, phase, rays_per_block):
         """The product object of a composite call with scores; `observed` and `domain` checked (host arrays), or device pointers
         under device_outputs['composite'] and `observed` None.  `spec`: a neighbourhood.Fractions, or an objects.Objects over
-        one: the scores with the object cells of the same binary maps (objects.Cells)."""
+        one: the scores with the object cells of the same binary maps (objects.Cells), or a neighbourhood.Probabilities over
+        one: the scores with the neighbourhood ensemble probabilities of the blocks (neighbourhood.EnsembleScores)."""
         cells, spec = (spec, spec.fractions) if isinstance(spec, OB.Objects) else (None, spec)
+        prob, spec = (spec, spec.fractions) if isinstance(spec, NB.Probabilities) else (None, spec)
         if not isinstance(spec, NB.Fractions):
             raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
         entry = (device_outputs or {}).get('composite', {})
@@ -2523,6 +2527,8 @@ class RadarOperator(object):
             observed, domain = NB.check_maps(spec, observed, domain)
         if cells is not None:
             return OB.Cells(cells, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
+        if prob is not None:
+            return NB.EnsembleScores(prob, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
         return NB.Scores(spec, observed, domain, keep_gates, phase, rays_per_block, self.distributed)
 
     def simulate_rays_composite_fss(self, azimuths, elevations, spec, observed, domain=None, keep_gates=False, phase=3,
@@ -2540,6 +2546,12 @@ class RadarOperator(object):
         'connectivity', 'min_area', 'thresholds'}); device_outputs['composite'] may then carry 'n_objects', 'table' and 'labels'.
         With Objects(match=True) 'objects' also holds the overlap pieces of every block's objects with the observed ones
         ('pieces', 'covered', 'covered_observed': objects.py, MATCH), and the entry may carry 'n_pieces', 'pieces' and 'covered'.
+        With a neighbourhood.Probabilities (over a Fractions; over an Objects it is a ValueError: not built) as `spec` it gains
+        'probabilities': the neighbourhood ensemble probabilities of the call's blocks, exactly neighbourhood.ensemble_sums of
+        the maps the same call returns ({'diff2' | 'forecast2' | 'observed2': uint64 [n_thr, n_radii], 'reliability': uint64
+        [n_thr, n_radii, n_blocks + 1, 2], 'member_sum' | 'member_any': uint32 [n_thr, n_radii, n_y, n_x] when asked,
+        'n_blocks', 'thresholds', 'radii'}); neighbourhood.fss, nep, nmep, brier, reliability_curve and roc read it, and the
+        entry may carry 'prob_sums', 'reliability', 'member_sum' and 'member_any'.
         The other keywords are those of simulate_rays_composite.  `device_outputs`: its entry 'composite' may carry 'observed',
         'domain', 'sums' and 'totals' as device pointers (`observed` stays None).  ValueError for an observed map or a domain of
         a wrong shape or dtype and for what the library refuses.  `radar` (the radars of a network under one operator differ in
@@ -2562,7 +2574,9 @@ class RadarOperator(object):
         """simulate_rays_ensemble_composite with scores: with `per_member` one row of scores per member (the leading axis of
         every array of 'fractions', in the order of `members`; each equals the member's own simulate_rays_composite_fss),
         without it the scores of the one map of all members' gates.  `spec`, `observed`, `domain` as for
-        simulate_rays_composite_fss; the rest (`radar`, `source`: the radars of a network differ in position only) as for
+        simulate_rays_composite_fss: with a neighbourhood.Probabilities the members are the blocks of res['composite']
+        ['probabilities'] (NEP, NMEP, the ensemble FSS, the reliability table), with per_member=False there is one block, and a
+        member list that `sequence_memory_budget` cuts into several calls is a ValueError; the rest (`radar`, `source`: the radars of a network differ in position only) as for
         simulate_rays_ensemble_composite."""
         return self._ensemble_reduced(azimuths, elevations, self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, 0),
                                       'maps', members, per_member, device_outputs, apply_sensitivity, lane, pinned, radar=radar,
@@ -2623,7 +2637,7 @@ class RadarOperator(object):
         """get_network_composite with scores: `spec` is a neighbourhood.Fractions over the network's composite, `observed` and
         `domain` as for simulate_rays_composite_fss.  The pass is scored ONCE, at its end, against the observed network
         composite: res['composite']['fractions'] (and 'objects' with an objects.Objects)."""
-        if not isinstance(spec, (NB.Fractions, OB.Objects)):
+        if not isinstance(spec, (NB.Fractions, OB.Objects, NB.Probabilities)):
             raise ValueError('spec: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (spec,))
         sweeps, per_radar = self._network_sweeps(radars, spec.composite, elevations, azimuths, az_step, az_start, az_stop)
         return self._network_pass(sweeps, per_radar, lambda az, el, phase, lane, radar, source: self.simulate_rays_composite_fss(

@@ -701,7 +701,8 @@ typedef struct cpol_composite {
  * 1..4; a NaN threshold; n_radii outside 1..8; a radius < 0 or > 1023; radii not strictly ascending; NULL observed, sums or
  * totals; a limit exceeded.
  * Three kernels (k_frac_rows, k_frac_cols, k_frac_score, cpol_frac.inl) run behind k_comp_finish and before the output copy; a
- * call without the struct queues exactly what it queued before. */
+ * call without the struct queues exactly what it queued before.  The wrapper cpol_fractions_ensemble, below the object cells, reduces the
+ * blocks of the same call to neighbourhood ensemble probabilities on the same tables. */
 #define CPOL_FRAC_MAX_THRESHOLDS 4
 #define CPOL_FRAC_MAX_RADII 8
 #define CPOL_FRAC_MAX_RADIUS 1023
@@ -828,8 +829,54 @@ typedef struct cpol_objects_match {
     uint32_t *covered;          /* [n_blocks][n_thresholds][2][max_objects]: forecast side, observed side             */
 } cpol_objects_match;
 
+/* Neighbourhood ensemble probabilities: what a convective-scale ensemble publishes of its members' maps -- the neighbourhood
+ * ensemble probability (NEP) and the neighbourhood maximum ensemble probability (NMEP; Schwartz and Sobash 2017, Mon. Wea. Rev.
+ * 145, 3397-3418), the ensemble FSS of the ensemble-mean fraction (Schwartz et al. 2010; Duc et al. 2013) and a reliability
+ * table, from which the Brier score, the reliability diagram and the ROC follow.  Replaces in the reference: nothing (its users
+ * pull every member's map to the host and box-filter it there).  Pointed to by cpol_fractions_ensemble.probabilities (below: a
+ * cpol_fractions with CPOL_FRAC_ENSEMBLE in its n_radii, embedded as the first member, the way cpol_objects_match embeds a
+ * cpol_objects; cpol_fractions itself keeps its size and its last member): the product rides on a scored finishing call and
+ * reads the summed-area tables that call has built.  cosmo_pol_amd/neighbourhood.py states the same
+ * rule in NumPy (`ensemble_sums`).
+ * THE RULE
+ * Inputs are those of cpol_fractions, unchanged.  F[b][t], O[t], NF[b][t][w][y][x] and NO[t][w][y][x] are the binary maps and
+ * clipped window counts defined there.  M = n_blocks; in an ensemble call a block is a member.
+ * Per threshold t, radius index w and cell:
+ *   S[t][w][y][x] = sum over b of NF[b][t][w][y][x] (uint32).  NEP is S / (M * window_cells); the division is the host's.
+ *   A[t][w][y][x] = #{ b : NF[b][t][w][y][x] > 0 } (uint32, 0 ... M).  NMEP is A / M.
+ *   OA[t][w][y][x] = NO[t][w][y][x] > 0.
+ * Both maps are written for EVERY cell of the grid.  The domain only decides which cells are set and which cells are summed.
+ * Sums over the cells of the domain, uint64:
+ *   prob_sums[t][w][3] = (diff2, forecast2, observed2): diff2 = sum (S - M * NO)^2, forecast2 = sum S^2, observed2 = M^2 * sum
+ *   NO^2.  neighbourhood.fss applied to these three gives the ensemble FSS unchanged.  With M == 1 they equal block 0's row of
+ *   `sums`.
+ *   reliability[t][w][k][o], k = 0 ... M, o = 0 | 1: the number of domain cells with A == k and OA == o.  At radius 0 this is the
+ *   classic table "k of M members exceed, observed yes or no".  At larger radii it is the NMEP against the neighbourhood-maximum
+ *   observation.  Every [t][w] slice sums to n_domain.
+ * Limits are conditions, not measurements.
+ *   1 <= n_blocks <= CPOL_FRAC_PROB_MAX_BLOCKS (256); it bounds `reliability` and the kernel's LDS table.
+ *   NO OVERFLOW, checked before anything is queued.  Let c = min(2 * r_max + 1, n_y) * min(2 * r_max + 1, n_x).  The call is
+ *   refused unless M * c < 2^32 and n_y * n_x * (M * c)^2 < 2^64.  |S - M * NO| <= M * c, so the bound covers all three sums.
+ *   (It passes for 300 x 300 cells, 21 members, any radius; for 1023^2, 128 members, radius 20; for 1023^2, 256 members, radius
+ *   32.  It refuses 1023^2, 128 members, radius 1023.)
+ * The result depends neither on the order of the blocks nor on how the work is cut.
+ * OUTPUTS: prob_sums uint64 [n_thresholds][n_radii][3]; reliability uint64 [n_thresholds][n_radii][n_blocks + 1][2]; member_sum
+ * and member_any (the S and the A maps) uint32 [n_thresholds][n_radii][n_y][n_x], each or NULL = not wanted.  They follow
+ * p->outputs_on_device like `sums`.  The struct may stand beside `objects`: the two are independent readers of the same tables.
+ * CPOL_ERR_ARG, nothing queued, an open pass untouched, the context usable: NULL prob_sums or reliability; n_blocks > 256; the
+ * overflow condition.
+ * One kernel (k_frac_members, cpol_frac_prob.inl) runs directly behind k_frac_score and before the object kernels; it reads only
+ * the summed-area tables and the domain.  A call without the struct queues exactly what it queued before. */
+#define CPOL_FRAC_PROB_MAX_BLOCKS 256
+typedef struct cpol_fraction_probabilities {
+    uint64_t *prob_sums;        /* [n_thresholds][n_radii][3]                                                      */
+    uint64_t *reliability;      /* [n_thresholds][n_radii][n_blocks + 1][2]                                        */
+    uint32_t *member_sum;       /* [n_thresholds][n_radii][n_y][n_x] or NULL = not wanted: the S maps              */
+    uint32_t *member_any;       /* [n_thresholds][n_radii][n_y][n_x] or NULL = not wanted: the A maps              */
+} cpol_fraction_probabilities;
+
 typedef struct cpol_fractions {
-    int32_t  field;             /* the field whose plane is scored: one of composite->fields                        */
+    int32_t  field;           /* the field whose plane is scored: one of composite->fields                        */
     int32_t  plane;             /* index into that field's plane order                                             */
     int32_t  n_thresholds;      /* 1 ... 4                                                                         */
     int32_t  n_radii;           /* 1 ... 8                                                                         */
@@ -841,6 +888,16 @@ typedef struct cpol_fractions {
     uint64_t *totals;           /* [n_blocks][n_thresholds][3]                                                     */
     cpol_objects *objects;      /* NULL (a zero-initialised struct): off.  The object cells of the same binary maps */
 } cpol_fractions;
+
+/* NEIGHBOURHOOD ENSEMBLE PROBABILITIES (cpol_fraction_probabilities, above): cpol_outputs.fractions points at `f`; the library
+ * reads beyond it only when f.n_radii > 0 carries CPOL_FRAC_ENSEMBLE (n_radii = 1 ... 8, or-ed with the flag; a zero-initialised
+ * cpol_fractions has no flag: off).  With the flag and probabilities == NULL the product is off too. */
+#define CPOL_FRAC_ENSEMBLE 0x10000
+typedef struct cpol_fractions_ensemble {
+    cpol_fractions f;           /* f.n_radii = the number of radii | CPOL_FRAC_ENSEMBLE                               */
+    cpol_fraction_probabilities *probabilities;     /* NEP, NMEP, the ensemble FSS's sums and the reliability table of
+                                   the blocks of the same call; NULL: off                                             */
+} cpol_fractions_ensemble;
 
 /* Terrain shadowing (cpol_sweep_params.terrain_shadow, cpol_outputs.visibility; cosmo_pol_amd/shadow.py states the same rule in
  * NumPy).  Replaces in the reference: nothing that runs -- interpolation_c.c:92-102 writes NaN into every gate from the first one
@@ -1328,7 +1385,9 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * cpol_fractions' refusals, and CPOL_ERR_ARG for a bad shape or NULL maps.  Returns 0.  With f.objects (host arrays n_objects,
  * table and labels or NULL) the call runs cpol_objects' checks and the kernels of cpol_obj.inl on the same maps too; with a
  * non-zero f.objects->pad_ the struct is the first member of a cpol_objects_match, whose n_pieces, pieces and covered are host
- * arrays, and the match runs as well.
+ * arrays, and the match runs as well.  With CPOL_FRAC_ENSEMBLE in f.n_radii a pointer to a cpol_fraction_probabilities follows
+ * f (the two are a cpol_fractions_ensemble; max_bytes covers it; host arrays prob_sums, reliability, and member_sum, member_any
+ * or NULL), and the call runs its checks and k_frac_members on the same maps too.
  * Returns bytes copied or < 0. */
 CPOL_API int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_bytes);
 

@@ -18,6 +18,16 @@ Kernel times come from a run of its own under the profiler,
 pass the kernel statistics file with --kernel-stats NAME=FILE to have the figures of k_frac_rows, k_frac_cols and k_frac_score
 written into the JSON.
 
+With --probabilities the session measures the neighbourhood ensemble probabilities on the same workload and
+writes profiles/fraction_probabilities_profile.json:
+
+  ens_prob        ens_fss with a neighbourhood.Probabilities: the sums of the ensemble FSS and the reliability table too;
+  ens_prob_maps   the same with the S and the A maps (maps=True, any_maps=True);
+  ens_prob_host   ens_maps, then neighbourhood.ensemble_sums on the host: what the device call replaces;
+  ens_fss / parent_ens_fss   the call with the Fractions alone of this tree and of --parent-tree DIR: the control for "a call
+                  without the struct did not get slower" (with --bench: bench / parent_bench too);
+each record carries the bytes handed over (every array of res['composite']); k_frac_members comes from --kernel-stats.
+
 NOT measured: several lanes in flight, device-resident outputs, a domain mask, other grids, radii and member counts, the
 single sweep's score, a volume's score.
 
@@ -40,8 +50,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_RAYS = 360
 THRESHOLDS_DBZ = [18.0, 30.0, 40.0]
 RADII = [0, 1, 2, 5, 10, 20]
-WORKERS = ('ens_fss', 'ens_maps', 'ens_host', 'comp')
-KERNELS = ('k_frac_rows', 'k_frac_cols', 'k_frac_score', 'k_comp_combined', 'k_comp_finish')
+WORKERS = ('ens_fss', 'ens_maps', 'ens_host', 'comp', 'ens_prob', 'ens_prob_maps', 'ens_prob_host')
+KERNELS = ('k_frac_rows', 'k_frac_cols', 'k_frac_score', 'k_frac_members', 'k_comp_combined', 'k_comp_finish')
+
+
+def handed_over(w):
+    """The bytes of every array under a result's 'composite' entry."""
+    if isinstance(w, dict):
+        return sum(handed_over(v) for v in w.values())
+    return int(w.nbytes) if isinstance(w, np.ndarray) else 0
 
 
 def worker(a):
@@ -71,12 +88,20 @@ def worker(a):
             run = lambda: op.simulate_rays_ensemble_composite_fss(az, el, spec, observed)
         elif a.worker == 'ens_maps':
             run = lambda: op.simulate_rays_ensemble_composite(az, el, cspec)
+        elif a.worker in ('ens_prob', 'ens_prob_maps'):
+            pspec = NB.Probabilities(spec, maps=a.worker == 'ens_prob_maps', any_maps=a.worker == 'ens_prob_maps')
+            run = lambda: op.simulate_rays_ensemble_composite_fss(az, el, pspec, observed)
+        elif a.worker == 'ens_prob_host':
+            def run():
+                res = op.simulate_rays_ensemble_composite(az, el, cspec)
+                res['composite']['probabilities'] = NB.ensemble_sums(spec, res['composite']['values']['ZH']['max'], observed)
+                return res
         else:
             def run():
                 res = op.simulate_rays_ensemble_composite(az, el, cspec)
                 res['composite']['fractions'] = NB.sums(spec, res['composite']['values']['ZH']['max'], observed)
                 return res
-    if a.worker == 'ens_host':            # (seconds per call: the rule holds int64 [members, 3, 6, 300, 300] several times over)
+    if a.worker in ('ens_host', 'ens_prob_host'):            # (seconds per call: the rule holds int64 [members, 3, 6, 300, 300] several times over)
         a.warmup, a.steps = min(a.warmup, 1), min(a.steps, 3)
     for _ in range(a.warmup):
         res = run()
@@ -92,6 +117,17 @@ def worker(a):
     out = {'call': a.worker, 'n_rays': N_RAYS, 'n_gates': len(op.constants.RANGE_RADAR), 'steps': a.steps,
            'ms_per_call_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
            'max_checksum': float(np.nansum(w['values']['ZH']['max'], dtype=np.float64)), 'counted': int(w['count']['ZH'].sum())}
+    if a.worker != 'ens_prob_host':       # (the rule always makes both maps: not what a call hands over)
+        out['bytes_handed_over'] = handed_over(w)
+    if 'probabilities' in w:
+        pr = w['probabilities']
+        from cosmo_pol_amd import neighbourhood as NB
+        k_of = np.arange(pr['n_blocks'] + 1, dtype=np.uint64)[:, None] * np.array([1, 1000], np.uint64)
+        out['prob_checksum'] = [int(np.array(pr[k]).sum(dtype=np.uint64)) for k in ('diff2', 'forecast2', 'observed2')] + [
+            int((np.array(pr['reliability']) * k_of).sum(dtype=np.uint64))]
+        out['ensemble_fss'] = [[None if np.isnan(x) else float(x) for x in row] for row in NB.fss(pr)]
+        out['brier'] = [[None if np.isnan(x) else float(x) for x in row] for row in NB.brier(pr)]
+        out['thresholds_dbz'], out['radii'] = THRESHOLDS_DBZ, RADII
     if a.worker != 'comp':
         out['members'] = a.members
     if 'fractions' in w:
@@ -108,8 +144,10 @@ def worker(a):
 def driver(a):
     here = os.path.abspath(__file__)
     tags = ['ens_fss', 'ens_maps', 'ens_host', 'comp']
+    if a.probabilities:
+        tags = ['ens_fss', 'ens_prob', 'ens_prob_maps', 'ens_prob_host']
     if a.parent_tree:
-        tags.append('parent_comp')
+        tags.append('parent_ens_fss' if a.probabilities else 'parent_comp')
     if a.bench:
         tags += ['bench'] + (['parent_bench'] if a.parent_tree else [])
     if a.calls:
@@ -149,7 +187,8 @@ def driver(a):
         med = [r['ms_per_call_median'] for r in recs]
         c = {'ms_per_call_median_of_processes': float(np.median(med)), 'ms_per_call_medians': med,
              'spread': float((max(med) - min(med)) / np.median(med))}
-        for k in ('max_checksum', 'counted', 'members', 'sums_checksum', 'fss_member_0', 'thresholds_dbz', 'radii'):
+        for k in ('max_checksum', 'counted', 'members', 'sums_checksum', 'fss_member_0', 'thresholds_dbz', 'radii', 'bytes_handed_over',
+                  'prob_checksum', 'ensemble_fss', 'brier'):
             if k in recs[0]:
                 c[k] = recs[0][k]
         result['calls'][tag] = c
@@ -168,6 +207,21 @@ def driver(a):
         result['ens_fss_over_ens_host_ms'] = ms('ens_fss') / ms('ens_host')
         result['sums_equal'] = bool(calls['ens_fss'].get('sums_checksum') == calls['ens_host'].get('sums_checksum')
                                     and calls['ens_fss'].get('max_checksum') == calls['ens_host'].get('max_checksum'))
+    if all(t in calls for t in ('ens_fss', 'ens_prob', 'ens_prob_maps', 'ens_prob_host')):
+        result['probabilities_cost_ms'] = ms('ens_prob') - ms('ens_fss')
+        result['probabilities_with_maps_cost_ms'] = ms('ens_prob_maps') - ms('ens_fss')
+        result['ens_prob_over_ens_prob_host_ms'] = ms('ens_prob') / ms('ens_prob_host')
+        result['prob_sums_equal'] = bool(calls['ens_prob'].get('prob_checksum') == calls['ens_prob_host'].get('prob_checksum')
+                                         == calls['ens_prob_maps'].get('prob_checksum')
+                                         and calls['ens_prob'].get('max_checksum') == calls['ens_prob_host'].get('max_checksum'))
+    if 'parent_ens_fss' in calls and 'ens_fss' in calls:
+        cc, pc = calls['ens_fss'], calls['parent_ens_fss']
+        result['control_fractions'] = {'ens_fss_over_parent_ens_fss_ms': ms('ens_fss') / ms('parent_ens_fss'),
+                                       'range_ms': [min(cc['ms_per_call_medians']), max(cc['ms_per_call_medians'])],
+                                       'parent_range_ms': [min(pc['ms_per_call_medians']), max(pc['ms_per_call_medians'])],
+                                       'each_median_inside_the_others_range': inside(cc['ms_per_call_medians'], pc['ms_per_call_medians']),
+                                       'checksum_equal': bool(pc.get('max_checksum') == cc.get('max_checksum')
+                                                              and pc.get('sums_checksum') == cc.get('sums_checksum'))}
     if 'parent_comp' in calls and 'comp' in calls:
         cc, pc = calls['comp'], calls['parent_comp']
         result['control_composite'] = {'comp_over_parent_comp_ms': ms('comp') / ms('parent_comp'),
@@ -183,7 +237,9 @@ def driver(a):
     for item in a.kernel_stats or []:
         name, path = item.split('=', 1)
         tb = kernel_table(path)
-        result.setdefault('kernels', {})[name] = {k: tb.get(k) for k in KERNELS}
+        # (the profiler's database names kernels as the code object does, _Z14k_frac_members12FracProbArgs.kd: found by the bare name)
+        found = {k: tb.get(k) or next((v for n, v in sorted(tb.items()) if k in n), None) for k in KERNELS}
+        result.setdefault('kernels', {})[name] = found
     line = json.dumps(result, indent=1, sort_keys=True)
     print(line)
     if a.out:
@@ -203,12 +259,16 @@ def main():
     ap.add_argument('--repeat', type=int, default=3, help='fresh processes per call')
     ap.add_argument('--calls', default=None, help='the calls of this session of the driver, comma-separated (default: all that apply)')
     ap.add_argument('--update', action='store_true', help='join the calls of this session to those --out already holds')
+    ap.add_argument('--probabilities', action='store_true',
+                    help='the session of the neighbourhood ensemble probabilities (default --out: profiles/fraction_probabilities_profile.json)')
     ap.add_argument('--bench', action='store_true', help="bench.py's result line too (of the parent tree as well)")
     ap.add_argument('--process-timeout', type=float, default=400.0)
     ap.add_argument('--parent-tree', default=None, help='a checkout of the parent commit with its library built')
     ap.add_argument('--kernel-stats', action='append', default=None, metavar='NAME=FILE')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.probabilities and not a.out and not a.worker:
+        a.out = os.path.join(ROOT, 'profiles', 'fraction_probabilities_profile.json')
     if a.worker:
         worker(a)
     else:
