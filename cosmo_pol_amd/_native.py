@@ -169,6 +169,14 @@ class Composite(C.Structure):
                 ('column', C.c_void_p * len(COMPOSITE_FIELDS)), ('column_layers', C.c_void_p * len(COMPOSITE_FIELDS))]
 
 
+class CompositeSums(C.Structure):
+    """cpol_composite_sums: a cpol_composite whose products carry CPOL_COMP_SUM, and behind it the weight tables and the outputs
+    of the exact sums (composite.py, SUM).  cpol_outputs.composite points at `c`; the library reads beyond it only with the bit."""
+    _fields_ = [('c', Composite), ('n_weight', C.c_int32 * len(COMPOSITE_FIELDS)),
+                ('weight_v', C.c_void_p * len(COMPOSITE_FIELDS)), ('weight_f', C.c_void_p * len(COMPOSITE_FIELDS)),
+                ('sum', C.c_void_p * len(COMPOSITE_FIELDS)), ('sum_skipped', C.c_void_p * len(COMPOSITE_FIELDS))]
+
+
 OBJ_WORDS = 10                                      # CPOL_OBJ_WORDS: the uint32 words of a row of cpol_objects.table
 
 
@@ -1102,9 +1110,11 @@ class Context(object):
         the slab as the caller gave them (float64; the library rounds thresholds and slab), ray_sin / ray_cos of `azimuths`
         (degrees; None leaves them NULL), the output pointers the caller's.  gate_xy = (x, y), float64 arrays of the call's
         geometry: the gate plane (CPOL_COMP_PLANE_GATES), kept on the device under `plane_version` when that is non-zero;
-        `source`: this call's number for the source_of_* planes."""
+        `source`: this call's number for the source_of_* planes.  A spec with 'sum': the struct is a CompositeSums (its member
+        `c` is the Composite, which shares its memory) with the weight tables set."""
         from . import composite as CP
-        c = Composite()
+        wide = CompositeSums() if CP.SUM in spec.products else None
+        c = wide.c if wide is not None else Composite()
         c.fields, c.phase, c.products, c.rays_per_block = spec.mask, int(phase), spec.product_mask, int(rays_per_block)
         c.n_x, c.n_y = spec.n_x, spec.n_y
         keep = [spec.x_edges, spec.y_edges]
@@ -1136,6 +1146,12 @@ class Context(object):
                 i = COMPOSITE_FIELDS.index(k)
                 c.n_table[i], c.table_v[i], c.table_f[i] = len(tv), tv.ctypes.data, tf.ctypes.data
                 keep += [tv, tf]
+        if wide is not None:
+            for k, (tv, tf) in spec.weight.items():
+                i = COMPOSITE_FIELDS.index(k)
+                wide.n_weight[i], wide.weight_v[i], wide.weight_f[i] = len(tv), tv.ctypes.data, tf.ctypes.data
+                keep += [tv, tf]
+            return wide, keep
         return c, keep
 
     def composite_plane(self):
@@ -1164,13 +1180,17 @@ class Context(object):
         [n_rays, n_gates]: the gate plane (`dist` and `azimuths` may then be None), under `plane_version` in the plane store;
         `source`: the call's number.  A finishing call returns {'values': {field: {plane: array}}, 'count': {field: array}},
         any other None.  A spec with height layers: the planes and counts carry the layer axis ([n_blocks, n_z, n_y, n_x]), and
-        with the product 'column' the result gains 'column' and 'column_layers' ({field: [n_blocks, n_y, n_x]})."""
+        with the product 'column' the result gains 'column' and 'column_layers' ({field: [n_blocks, n_y, n_x]}).  A spec with
+        'sum': the call runs k_comp_sum (lane_form: 0 the kept form, 1 the runs of a wavefront summed first, 2 every lane on
+        its own) and a finishing call k_comp_sum_finish; the result gains 'sum' (float64) and 'sum_skipped' (uint32), shaped
+        like count[field]; `tamper` is given the CompositeSums."""
         from . import composite as CP
+        with_sum = CP.SUM in spec.products
 
         class Hook(C.Structure):
             _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('n_rays', C.c_int32), ('lane_form', C.c_int32),
                         ('inp', C.c_void_p * len(COMPOSITE_FIELDS)), ('heights', C.c_void_p), ('dist', C.c_void_p),
-                        ('c', Composite)]
+                        ('c', CompositeSums if with_sum else Composite)]
         hk = Hook()
         keep, shape = [], None
         for i, k in enumerate(COMPOSITE_FIELDS):
@@ -1202,6 +1222,8 @@ class Context(object):
         hk.c, ckeep = self.composite_struct(spec, phase, rays_per_block, azimuths=azimuths, gate_xy=gate_xy, source=source,
                                             plane_version=plane_version)
         keep += ckeep
+        hc = hk.c.c if with_sum else hk.c         # (the cpol_composite itself)
+        sums, skipped = {}, {}
         rpb = int(rays_per_block)
         nb = 1 if rpb <= 0 or shape[0] % rpb else shape[0] // rpb
         vals, cnt, col, lay = {}, None, {}, {}
@@ -1209,14 +1231,19 @@ class Context(object):
         if int(phase) & 2:
             for k in spec.fields:
                 vals[k] = np.full((nb,) + z + (len(spec.planes(k)), spec.n_y, spec.n_x), -7.0, dtype=np.float32)
-                hk.c.values[COMPOSITE_FIELDS.index(k)] = vals[k].ctypes.data
+                hc.values[COMPOSITE_FIELDS.index(k)] = vals[k].ctypes.data
             cnt = np.full((nb,) + z + (len(spec.fields), spec.n_y, spec.n_x), 0xDEADBEEF, dtype=np.uint64)
-            hk.c.count = cnt.ctypes.data
+            hc.count = cnt.ctypes.data
             for k in spec.column:
                 col[k] = np.full((nb, spec.n_y, spec.n_x), -7.0, dtype=np.float64)
                 lay[k] = np.full((nb, spec.n_y, spec.n_x), 0xAB, dtype=np.uint8)
-                hk.c.column[COMPOSITE_FIELDS.index(k)] = col[k].ctypes.data
-                hk.c.column_layers[COMPOSITE_FIELDS.index(k)] = lay[k].ctypes.data
+                hc.column[COMPOSITE_FIELDS.index(k)] = col[k].ctypes.data
+                hc.column_layers[COMPOSITE_FIELDS.index(k)] = lay[k].ctypes.data
+            for k in (spec.fields if with_sum else ()):
+                sums[k] = np.full((nb,) + z + (spec.n_y, spec.n_x), -7.0, dtype=np.float64)
+                skipped[k] = np.full((nb,) + z + (spec.n_y, spec.n_x), 0xDEADBEEF, dtype=np.uint32)
+                hk.c.sum[COMPOSITE_FIELDS.index(k)] = sums[k].ctypes.data
+                hk.c.sum_skipped[COMPOSITE_FIELDS.index(k)] = skipped[k].ctypes.data
         if tamper is not None:
             keep.append(tamper(hk.c))
         rc = int(self.lib.cpol_debug_read(self.h, b'composite_fields', C.byref(hk), C.sizeof(hk)))
@@ -1225,12 +1252,15 @@ class Context(object):
         if not int(phase) & 2:
             return None
         if not spec.n_z:
-            return {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
-                    'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
-        out = {'values': {k: {p: vals[k][:, :, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
-               'count': {k: cnt[:, :, i] for i, k in enumerate(spec.fields)}}
-        if spec.column:
-            out['column'], out['column_layers'] = col, lay
+            out = {'values': {k: {p: vals[k][:, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
+                   'count': {k: cnt[:, i] for i, k in enumerate(spec.fields)}}
+        else:
+            out = {'values': {k: {p: vals[k][:, :, j] for j, p in enumerate(spec.planes(k))} for k in spec.fields},
+                   'count': {k: cnt[:, :, i] for i, k in enumerate(spec.fields)}}
+            if spec.column:
+                out['column'], out['column_layers'] = col, lay
+        if with_sum:
+            out['sum'], out['sum_skipped'] = sums, skipped
         return out
 
     @staticmethod

@@ -78,7 +78,32 @@ stays as it is.
              above it in the same cell takes the f of the nearest counting layer below; empty layers below the lowest or above
              the highest counting layer add nothing.  A cell with no counting layer is NaN.
   Outputs    column[field] float64 [n_blocks, n_y, n_x]; column_layers[field] uint8 [n_blocks, n_y, n_x], the layers that
-             contributed (under 'hold' the held ones included)."""
+             contributed (under 'hold' the held ones included).
+
+SUM: the exact sum of the counting gates' weights per (block, layer, cell), for the cell MEAN and for rain accumulations (the
+product 'sum', CPOL_COMP_SUM = 256, and the struct cpol_composite_sums).  Everything above stays as it is.
+  1.  A gate counts for field k exactly as above: the same cell search, slab, layers, blocks and pass.
+  2.  The summand of a counting gate is w = v when field k has no weight table.  With a table (table_v float32, table_f float64)
+      it is w = float32(f(v)), f the piecewise-linear function of the column table above: 0 below the table, the last value at
+      and above its end, every operation one float64 operation, then ONE rounding to float32 (obj_weight in cpol_obj.h,
+      objects.weight_of).  The table conditions are those of the column table: 2 ... 1024 breakpoints, finite, strictly
+      ascending in float32, finite values; no monotonicity is demanded of the values.
+  3.  Per (block, layer, cell) `sum` is the EXACT sum of the finite w, rounded ONCE to float64 with ties to even: math.fsum of
+      the summands.  +0.0 when the exact sum is zero, NaN when no gate was summed.
+  4.  Per (block, layer, cell) `sum_skipped` (uint32) is the number of counting gates with w = +-inf.  Such a gate is not
+      summed, and it still counts in `count`.
+  5.  The mean is sum / (count - sum_skipped): one float64 division, formed on the host (`mean_of`), NaN where the divisor
+      is 0.
+  6.  Nothing depends on the order of the gates, the lane form, the block cut or how the pass is cut into calls.
+  How        a finite float32 is +-M * 2 ** (E - 150) with E in 1 ... 254 and M < 2 ** 24 (objects.split).  The state gains per
+             field and (block, layer, cell) a row of SUM_BINS signed 64-bit bins and one uint32 skipped word; bin E >> 3 takes
+             +-M << (E & 7), an INTEGER addition, and `finish` folds a row into one Python integer and rounds it once
+             (objects.round_scaled).  Integer additions commute: no order enters.
+  No overflow  a term is below 2 ** 31 in magnitude, so a bin cannot wrap while fewer than 2 ** 32 gates fold into one block of
+             a pass; the library refuses the call that would take a block beyond SUM_MAX_GATES.
+  Beside     'sum' stands beside at least one of 'max', 'lowest', 'echo_top'; 'sum' with 'source' is refused; with layers it
+             gives a 3-D grid of sums.  Not built: 'sum' alone, 'sum' with 'source', sums of RVEL, means in dB, a
+             carry-normalising kernel for passes beyond 2 ** 32 gates."""
 import numpy as np
 
 from .histogram import Counts
@@ -87,6 +112,9 @@ FIELDS = ('ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_
 PRODUCTS = ('max', 'lowest', 'echo_top')             # bit 0, 1, 2 of cpol_composite.products
 SOURCE, SOURCE_BIT = 'source', 16                    # CPOL_COMP_SOURCE (8 is no product and stays refused)
 COLUMN, COLUMN_BIT = 'column', 64                    # CPOL_COMP_COLUMN (32 is no product and stays refused)
+SUM, SUM_BIT = 'sum', 256                            # CPOL_COMP_SUM (128 is no product and stays refused)
+SUM_BINS = 32                                        # COMP_SUM_BINS: the int64 bins of a cell's row
+SUM_MAX_GATES = (1 << 32) - 1                        # COMP_SUM_MAX_GATES: the gates one block of a pass may fold
 GAPS = ('zero', 'hold')                              # cpol_composite.gaps
 MAX_LAYERS = 64                  # n_z; z_edges holds n_z + 1 values
 MAX_Z_EDGES = MAX_LAYERS + 1
@@ -132,6 +160,27 @@ def _f32(v):
         return np.float32(v)
 
 
+def _table(table, what):
+    """(table_v float32, table_f float64) of a weight table under the conditions of the column table."""
+    try:
+        tv, tf = table
+        tvg = np.array(tv, dtype=np.float64).reshape(-1)
+        tf = np.array(tf, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError('%s: (table_v, table_f), got %r' % (what, table))
+    if not 2 <= tvg.size <= MAX_TABLE:
+        raise ValueError('%s: 2 ... %d breakpoints, got %d' % (what, MAX_TABLE, tvg.size))
+    if tf.size != tvg.size:
+        raise ValueError('%s: %d breakpoints and %d values' % (what, tvg.size, tf.size))
+    with np.errstate(over='ignore'):
+        tv32 = tvg.astype(np.float32)
+    if not (np.all(np.isfinite(tv32)) and np.all(np.isfinite(tf))):
+        raise ValueError('%s: a breakpoint or a value is NaN or infinite' % what)
+    if not np.all(tv32[1:] > tv32[:-1]):
+        raise ValueError('%s: the breakpoints are not strictly ascending in float32' % what)
+    return tv32, tf
+
+
 class Composite(object):
     """What a composite call reduces: `fields` (names out of FIELDS), the float64 `x_edges` (east) and `y_edges` (north) of the
     radar-centred grid in metres (`grid` makes a uniform one), `products` out of PRODUCTS, `thresholds` for 'echo_top' ({field:
@@ -144,11 +193,14 @@ class Composite(object):
     source_of_max / source_of_lowest: which call's `source` supplied the cell.  `z_edges`: 2 ... 65 height edges in metres:
     the planes gain a layer axis ([n_blocks, n_z, n_y, n_x]: a stack of CAPPIs in one pass); with the product 'column' and
     `column` = {field: (table_v, table_f)} (`vil_table` makes the one of VIL) the result gains the column integral of the
-    interpolated table over the layers, `gaps` ('zero' or 'hold') saying what an empty layer adds.  ValueError for what the
+    interpolated table over the layers, `gaps` ('zero' or 'hold') saying what an empty layer adds.  The product 'sum' (beside
+    'max', 'lowest' or 'echo_top', never with 'source') adds the exact sum of the counting gates' weights per cell and the
+    number of gates it skipped (`mean_of` forms the mean): `weight` = {field: (table_v, table_f)} makes the summand of that
+    field float32(f(v)) (objects.zr_table(): the rain rate), a field without a table sums its values.  ValueError for what the
     library refuses."""
 
     def __init__(self, fields, x_edges, y_edges, products=('max',), thresholds=None, height_range=None, plane='radar',
-                 z_edges=None, column=None, gaps='zero'):
+                 z_edges=None, column=None, gaps='zero', weight=None):
         if isinstance(fields, str):
             fields = (fields,)
         fields = tuple(fields)
@@ -168,9 +220,13 @@ class Composite(object):
         if not products:
             raise ValueError('products: at least one of %s' % ', '.join(PRODUCTS))
         for q in products:
-            if q not in PRODUCTS and q != SOURCE and q != COLUMN:
-                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS + (SOURCE, COLUMN))))
-        self.products = tuple(q for q in PRODUCTS + (SOURCE, COLUMN) if q in products)
+            if q not in PRODUCTS and q != SOURCE and q != COLUMN and q != SUM:
+                raise ValueError('unknown product %r (one of %s)' % (q, ', '.join(PRODUCTS + (SOURCE, COLUMN, SUM))))
+        self.products = tuple(q for q in PRODUCTS + (SOURCE, COLUMN, SUM) if q in products)
+        if SUM in self.products and not any(q in self.products for q in PRODUCTS):
+            raise ValueError("'sum' stands beside 'max', 'lowest' or 'echo_top'")
+        if SUM in self.products and SOURCE in self.products:
+            raise ValueError("'sum' with 'source': the scratch-and-merge pass carries no sums")
         if SOURCE in self.products and 'max' not in self.products and 'lowest' not in self.products:
             raise ValueError("'source' needs 'max' or 'lowest'")
         if not (callable(plane) or (isinstance(plane, str) and plane in PLANES)):
@@ -259,6 +315,19 @@ class Composite(object):
                 raise ValueError("column tables without 'column'")
             if gaps != 'zero':
                 raise ValueError("gaps without 'column'")
+        # the exact sums
+        self.weight = {}
+        if weight is not None and SUM not in self.products:
+            raise ValueError("weight tables without 'sum'")
+        if weight is not None:
+            if not isinstance(weight, dict):
+                raise ValueError('weight: {field: (table_v, table_f)}, got %r' % (weight,))
+            for k in weight:
+                if k not in self.fields:
+                    raise ValueError('a weight table of %r, which is not a field of the composite' % (k,))
+            for k in self.fields:
+                if k in weight:
+                    self.weight[k] = _table(weight[k], 'the weight table of %s' % k)
 
     @property
     def n_x(self):
@@ -281,7 +350,8 @@ class Composite(object):
     @property
     def product_mask(self):
         """cpol_composite.products."""
-        return sum(SOURCE_BIT if q == SOURCE else COLUMN_BIT if q == COLUMN else 1 << PRODUCTS.index(q) for q in self.products)
+        return sum(SOURCE_BIT if q == SOURCE else COLUMN_BIT if q == COLUMN else SUM_BIT if q == SUM else 1 << PRODUCTS.index(q)
+                   for q in self.products)
 
     @property
     def gate_plane(self):
@@ -308,6 +378,8 @@ class Composite(object):
         if self.z_edges is not None:          # (a plain spec keeps the key it had)
             k = k + (('z', self.z_edges.tobytes(), self.gaps,
                       tuple((f, tv.tobytes(), tf.tobytes()) for f, (tv, tf) in sorted(self.column.items()))),)
+        if SUM in self.products:              # (a spec without 'sum' keeps the key it had)
+            k = k + (('w', tuple((f, tv.tobytes(), tf.tobytes()) for f, (tv, tf) in sorted(self.weight.items()))),)
         return k
 
     def __eq__(self, other):
@@ -329,6 +401,8 @@ class Composite(object):
         if self.column:
             s += ', column={%s}, gaps=%s' % (', '.join('%s: %d points' % (k, len(self.column[k][0])) for k in self.fields
                                                          if k in self.column), self.gaps)
+        if self.weight:
+            s += ', weight={%s}' % ', '.join('%s: %d points' % (k, len(self.weight[k][0])) for k in self.fields if k in self.weight)
         return s + ')'
 
 
@@ -379,15 +453,24 @@ def column_shape(spec, n_rows=1, rays_per_block=0):
     return (n_blocks(n_rows, rays_per_block), spec.n_y, spec.n_x)
 
 
+def sum_shape(spec, n_rows=1, rays_per_block=0):
+    """The shape of sum[field] and of sum_skipped[field]: that of count[field]."""
+    z = (spec.n_z,) if spec.n_z else ()
+    return (n_blocks(n_rows, rays_per_block),) + z + (spec.n_y, spec.n_x)
+
+
 def state_bytes(spec, blocks):
     """The bytes of the running state of `blocks` blocks (cpol_comp.h: the echo-top states of a field padded to 8 bytes).  With
     'source': the source bytes behind it (one per cell, block and product, each array padded to 8 bytes) and the per-call
-    scratch state, as large as the running state without them.  With layers a block holds n_z planes of cells."""
+    scratch state, as large as the running state without them.  With layers a block holds n_z planes of cells.  With 'sum':
+    per field and cell a row of SUM_BINS int64 bins and a uint32 skipped word (the words of a field padded to 8 bytes)."""
     per = int(blocks) * max(spec.n_z, 1) * spec.n_x * spec.n_y
     total = 0
     for k in spec.fields:
         total += per * 8 * (1 + ('max' in spec.products) + ('lowest' in spec.products))
         total += (per * 4 * len(spec.thresholds[k]) + 7) & ~7
+        if SUM in spec.products:
+            total += per * SUM_BINS * 8 + ((per * 4 + 7) & ~7)
     if SOURCE in spec.products:
         total = 2 * total + len(spec.fields) * (('max' in spec.products) + ('lowest' in spec.products)) * ((per + 7) & ~7)
     return total
@@ -499,6 +582,11 @@ def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0,
                         'count': np.zeros(nb * cells, dtype=_U64),
                         'source_of_max': np.full(nb * cells, NO_SOURCE, dtype=np.uint8),
                         'source_of_lowest': np.full(nb * cells, NO_SOURCE, dtype=np.uint8)} for q in spec.fields}}
+                if SUM in spec.products:
+                    state['sum_gates'] = 0
+                    for q in spec.fields:
+                        state['fields'][q]['sum'] = np.zeros((nb * cells, SUM_BINS), dtype=np.int64)
+                        state['fields'][q]['sum_skipped'] = np.zeros(nb * cells, dtype=_U32)
             if state['spec'] != spec or state['n_blocks'] != nb:
                 raise ValueError('compose: the spec or the block count differ from the state')
         sel = np.arange(rows) % n_rays
@@ -523,9 +611,19 @@ def compose(spec, fields, dist, heights, azimuths, state=None, rays_per_block=0,
                 mine[where[pack == st[q][where]]] = True
                 byte[mine] = np.minimum(byte[mine], np.uint8(source))
         vv = v[ok]
+        if SUM in spec.products:
+            # the exact sums: the weight, its split, the bins -- integer additions alone (no bin can wrap: sum_gates)
+            from .objects import split, weight_of
+            neg, E, M, finite = split(weight_of(vv, spec.weight.get(k)))
+            np.add.at(st['sum_skipped'], where[~finite], _U32(1))
+            np.add.at(st['sum'], (where[finite], E[finite] >> 3), np.where(neg[finite], -M[finite], M[finite]) << (E[finite] & 7))
         for j, t in enumerate(spec.thresholds[k]):
             above = vv >= t
             np.maximum.at(st['top'][j], where[above], kh_k[above])
+    if SUM in spec.products and nb is not None:
+        state['sum_gates'] += (rows // nb) * ng
+        if state['sum_gates'] > SUM_MAX_GATES:
+            raise ValueError("compose: more than 2 ** 32 - 1 gates would fold into one block of the pass ('sum')")
     return state
 
 
@@ -560,7 +658,28 @@ def finish(state):
         for k in spec.fields:
             if k in spec.column:
                 out['column'][k], out['column_layers'][k] = column_of(spec, out['values'][k]['max'], field=k)
+    if SUM in spec.products:
+        from .objects import round_scaled
+        out['sum'], out['sum_skipped'] = {}, {}
+        for k in spec.fields:
+            st = state['fields'][k]
+            total = np.full(st['count'].shape, np.nan, dtype=np.float64)
+            summed = np.flatnonzero(st['count'] != st['sum_skipped'].astype(_U64))
+            for i, row in zip(summed.tolist(), st['sum'][summed].tolist()):
+                total[i] = round_scaled(sum(v << (8 * b) for b, v in enumerate(row) if v))
+            out['sum'][k] = total.reshape(sh)
+            out['sum_skipped'][k] = st['sum_skipped'].reshape(sh).copy()
     return out
+
+
+def mean_of(res, field):
+    """The cell mean of `field` from a result with 'sum' (what `finish`, a composite call or the test hook returns):
+    sum / (count - sum_skipped), one float64 division, NaN where the divisor is 0."""
+    if 'sum' not in res or field not in res['sum']:
+        raise ValueError("mean_of: the result holds no 'sum' of %r" % (field,))
+    n = (np.asarray(res['count'][field]).astype(np.int64) - np.asarray(res['sum_skipped'][field]).astype(np.int64)).astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(n == 0.0, np.nan, np.asarray(res['sum'][field], dtype=np.float64) / np.where(n == 0.0, 1.0, n))
 
 
 def column_of(spec, max_planes, field=None):
@@ -675,8 +794,12 @@ class Maps(object):
         if xy is not None and any(np.shape(a) != (len(az), n_gates) for a in xy):
             raise ValueError('gate_xy: two arrays [n_rays, n_gates] = %r' % ((len(az), n_gates),))
         # (sine and cosine of the azimuths come from here, the plane coordinates from plane_xy: the library computes neither)
-        self.c, keep = native.Context.composite_struct(self.spec, self.phase, self.rays_per_block, azimuths=None if xy is not None else az,
-                                                       gate_xy=xy, source=self.source, plane_version=self.plane_version)
+        c, keep = native.Context.composite_struct(self.spec, self.phase, self.rays_per_block, azimuths=None if xy is not None else az,
+                                                  gate_xy=xy, source=self.source, plane_version=self.plane_version)
+        # (with 'sum' the struct is the wide one: the call points at its member `c`, which shares its memory)
+        self.wide = c if SUM in self.spec.products else None
+        self.c = c.c if self.wide is not None else c
+        keep = keep + [c]
         if self.spec.gate_plane:
             self.c.plane = 1                      # (device outputs: bind_device brings gate_x and gate_y)
         return {'composite': self.c}, keep
@@ -691,13 +814,17 @@ class Maps(object):
             csh = column_shape(self.spec, self.n_rows, self.rays_per_block)
             out += [(('column', k), np.float64, csh) for k in self.spec.fields if k in self.spec.column]
             out += [(('column_layers', k), np.uint8, csh) for k in self.spec.fields if k in self.spec.column]
+        if SUM in self.spec.products:
+            ssh = sum_shape(self.spec, self.n_rows, self.rays_per_block)
+            out += [((SUM, k), np.float64, ssh) for k in self.spec.fields]
+            out += [(('sum_skipped', k), np.uint32, ssh) for k in self.spec.fields]
         return out
 
     def bind(self, path, address):
         if path == 'count':
             self.c.count = address
-        elif isinstance(path, tuple):         # ('column' | 'column_layers', field)
-            getattr(self.c, path[0])[FIELDS.index(path[1])] = address
+        elif isinstance(path, tuple):         # ('column' | 'column_layers' | 'sum' | 'sum_skipped', field)
+            getattr(self.wide if path[0] in (SUM, 'sum_skipped') else self.c, path[0])[FIELDS.index(path[1])] = address
         else:
             self.c.values[FIELDS.index(path)] = address
 
@@ -707,12 +834,19 @@ class Maps(object):
             if k in entry:
                 setattr(self.c, k, entry.pop(k))
         for k, ptr in (entry.items() if self.phase & 2 else ()):
-            if k not in ('values', 'count', 'column', 'column_layers'):
+            if k not in ('values', 'count', 'column', 'column_layers') + ((SUM, 'sum_skipped') if self.wide is not None else ()):
                 raise ValueError("device_outputs['composite']: unknown entry %r" % (k,))
             for f, q in (ptr.items() if k == 'values' else (('count', ptr),) if k == 'count' else (((k, f), q) for f, q in ptr.items())):
                 self.bind(f, q)
 
     def finish(self, w, coords):
+        out = self._finish(w)
+        if SUM in self.spec.products:
+            out[SUM] = {k: w[(SUM, k)] for k in self.spec.fields}
+            out['sum_skipped'] = {k: w[('sum_skipped', k)] for k in self.spec.fields}
+        return out
+
+    def _finish(self, w):
         spec, cnt = self.spec, w.pop('count')
         if not spec.n_z:
             return {'values': {k: {q: w[k][:, j] for j, q in enumerate(spec.planes(k))} for k in spec.fields},
@@ -732,7 +866,7 @@ class Maps(object):
         if self.rays_per_block:
             out['values'] = {k: {q: cat([w['values'][k][q] for w in parts]) for q in self.spec.planes(k)} for k in self.spec.fields}
             out['count'] = {k: cat([w['count'][k] for w in parts]) for k in self.spec.fields}
-            for q in ('column', 'column_layers'):
+            for q in ('column', 'column_layers', SUM, 'sum_skipped'):
                 if q in out:
                     out[q] = {k: cat([w[q][k] for w in parts]) for k in out[q]}
         return out

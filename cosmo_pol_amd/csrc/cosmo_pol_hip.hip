@@ -199,7 +199,9 @@ struct cpol_ctx {
     // caller's device memory (nine `values`, then `count`); the pass (cpol_comp.h)
     // with height layers: b_ctab holds the float32 layer edges and the column tables (per field with one: the float64 values,
     // then the float32 breakpoints), and b_cout gains nine `column` and nine `column_layers`
-    DevBuf b_cstate, b_cedges, b_crays, b_cout[3 * CPOL_COMP_FIELDS + 1], b_ctab;
+    // with the exact sums (CPOL_COMP_SUM): b_cwtab holds the weight tables (per field with one: the float64 values, then the
+    // float32 breakpoints), and b_cout gains nine `sum` and nine `sum_skipped`
+    DevBuf b_cstate, b_cedges, b_crays, b_cout[5 * CPOL_COMP_FIELDS + 1], b_ctab, b_cwtab;
     // ... and the gate planes (CPOL_COMP_PLANE_GATES with host arrays): gate_x then gate_y of the last N_COMP_PLANES non-zero
     // plane_version tags stay on the device, as the table sets do, so the radars of a network that alternate in one pass do not
     // evict each other; a call without a tag uploads into b_cplane.  cplane_stat: {uploads, hits} (cpol_debug_read "composite_plane")
@@ -218,6 +220,7 @@ struct cpol_ctx {
     CompPlan cplan;                        // ... and the plan of the call at hand (kept here: a call without the struct constructs none)
     std::vector<double> cedges_host;       // ... and what b_cedges holds (the source of its copy)
     std::vector<double> ctab_host;         // ... and what b_ctab holds
+    std::vector<double> cwtab_host;        // ... and what b_cwtab holds
     // neighbourhood verification (cpol_fractions): the summed-area tables, the caller's observation and domain on the device (host
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand; prob_sums, reliability, member_sum and member_any of the neighbourhood ensemble probabilities
@@ -838,8 +841,9 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
                      &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
-    for (int k = CPOL_COMP_FIELDS + 1; k < 3 * CPOL_COMP_FIELDS + 1; ++k) free_buf(ctx->b_cout[k]);     // (column, column_layers)
+    for (int k = CPOL_COMP_FIELDS + 1; k < 5 * CPOL_COMP_FIELDS + 1; ++k) free_buf(ctx->b_cout[k]);     // (column, column_layers, sum, sum_skipped)
     free_buf(ctx->b_ctab);
+    free_buf(ctx->b_cwtab);
     for (auto &cp : ctx->cplanes) free_buf(cp.buf);
     for (auto &b : ctx->b_out) free_buf(b);
     for (int j = 0; j < CPOL_MAX_HYDRO; ++j) {
@@ -2591,9 +2595,15 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
 #ifndef CPOL_COMP_COMBINE
 #define CPOL_COMP_COMBINE 1        // the kept lane form of k_comp: 1 lanes that share a cell combined inside the wavefront, 0 every lane on its own
 #endif
-enum { CP_COUNT = CPOL_COMP_FIELDS, CP_COLUMN, CP_LAYERS = CP_COLUMN + CPOL_COMP_FIELDS, CP_N = CP_LAYERS + CPOL_COMP_FIELDS };
+enum { CP_COUNT = CPOL_COMP_FIELDS, CP_COLUMN, CP_LAYERS = CP_COLUMN + CPOL_COMP_FIELDS, CP_SUM = CP_LAYERS + CPOL_COMP_FIELDS,
+       CP_SKIPPED = CP_SUM + CPOL_COMP_FIELDS, CP_N = CP_SKIPPED + CPOL_COMP_FIELDS };
+static_assert(CP_N == 5 * CPOL_COMP_FIELDS + 1, "cpol_ctx::b_cout holds one buffer per array");
+#ifndef CPOL_COMP_SUM_COMBINE
+#define CPOL_COMP_SUM_COMBINE 1    // the kept lane form of k_comp_sum: 1 the runs of equal (cell, bin) summed inside the wavefront, 0 every lane on its own
+#endif
 // every refusal of a cpol_composite for the call `c`; queues nothing and leaves the pass as it is.  arr[CP_N]: the caller's nine
-// `values`, `count`, and with height layers the nine `column` and `column_layers`, for the placement plan (cpol_place.h): arrays
+// `values`, `count`, with height layers the nine `column` and `column_layers`, and with the exact sums the nine `sum` and
+// `sum_skipped`, for the placement plan (cpol_place.h): arrays
 // of the sweep itself, each with a grow-only buffer of its own, produced by a finishing call alone
 static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &call, CompPlan *pl, PlaceArray *arr)
 {
@@ -2613,6 +2623,15 @@ static int comp_plan(cpol_ctx *ctx, const cpol_composite *c, const CompCall &cal
         arr[k].bytes = (size_t)pl->n_blocks * pl->n_planes[k] * pl->block_cells * sizeof(float);
         arr[k].produced = true;
         arr[k].product = PLACE_SWEEP;
+        if (pl->sum) {
+            const cpol_composite_sums *const cs = (const cpol_composite_sums *)c;     // (the bit is set: comp_check)
+            arr[CP_SUM + k].user = (uintptr_t)cs->sum[k];
+            arr[CP_SUM + k].bytes = (size_t)pl->n_blocks * pl->block_cells * sizeof(double);
+            arr[CP_SKIPPED + k].user = (uintptr_t)cs->sum_skipped[k];
+            arr[CP_SKIPPED + k].bytes = (size_t)pl->n_blocks * pl->block_cells * sizeof(uint32_t);
+            arr[CP_SUM + k].produced = arr[CP_SKIPPED + k].produced = true;
+            arr[CP_SUM + k].product = arr[CP_SKIPPED + k].product = PLACE_SWEEP;
+        }
         if (pl->tv[k].empty()) continue;
         arr[CP_COLUMN + k].user = (uintptr_t)c->column[k];
         arr[CP_COLUMN + k].bytes = (size_t)pl->n_blocks * pl->cells * sizeof(double);
@@ -2680,6 +2699,27 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             ENSURE(ctx->b_ctab, tab.size() * sizeof(double));
             HIPCHK(hipMemcpyAsync(ctx->b_ctab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
         }
+        if (pl.sum) {
+            // the weight tables: per field with one n doubles and n floats (rounded up to whole doubles), in the order of the fields
+            std::vector<double> &tab = ctx->cwtab_host;
+            try {
+                size_t words = 0;
+                for (int k = 0; k < CPOL_COMP_FIELDS; ++k) words += pl.wv[k].size() + (pl.wv[k].size() + 1) / 2;
+                tab.assign(words, 0.0);
+            } catch (...) { ctx->err = "cpol_composite: out of host memory"; return CPOL_ERR_NOMEM; }
+            size_t at_word = 0;
+            for (int k = 0; k < CPOL_COMP_FIELDS; ++k) {
+                const size_t n = pl.wv[k].size();
+                if (!n) continue;
+                memcpy(tab.data() + at_word, pl.wf[k].data(), n * sizeof(double));
+                memcpy(tab.data() + at_word + n, pl.wv[k].data(), n * sizeof(float));
+                at_word += n + (n + 1) / 2;
+            }
+            if (!tab.empty()) {
+                ENSURE(ctx->b_cwtab, tab.size() * sizeof(double));
+                HIPCHK(hipMemcpyAsync(ctx->b_cwtab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st));
+            }
+        }
     }
     const bool gates = pl.plane == CPOL_COMP_PLANE_GATES;
     const double *gx = nullptr, *gy = nullptr;
@@ -2732,6 +2772,8 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
     const long into = pl.with_source ? pl.off_scratch : 0;
     const auto st_at = [&](long off) { return off < 0 ? nullptr : base + into + off; };
     const bool combine = lane_form == 0 ? CPOL_COMP_COMBINE != 0 : lane_form == 1;
+    const bool sum_combine = lane_form == 0 ? CPOL_COMP_SUM_COMBINE != 0 : lane_form == 1;
+    size_t w_word = 0;              // where the field's weight table begins in b_cwtab
     for (int i = 0; i < pl.n_fields; ++i) {
         const int k = pl.field[i];
         CompArgs ca{};
@@ -2782,6 +2824,36 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             hipLaunchKernelGGL(k_comp_merge, dim3((unsigned)cdiv(ma.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, ma);
             HIPCHK(hipGetLastError());
         }
+        if (pl.sum) {
+            // the exact sums of this field, behind its k_comp: the same grid, the same stretches (comp_check refuses SUM with SOURCE)
+            CompSumArgs sa{};
+            sa.a = ca;
+            sa.a.smax = sa.a.slow = sa.a.scount = nullptr; sa.a.stop = nullptr;
+            const size_t nw = pl.wv[k].size();
+            sa.n_w = (int)nw; sa.step_w = pow2_below((int)nw);
+            if (nw) {
+                sa.wf = (const double *)ctx->b_cwtab.p + w_word; sa.wv = (const float *)(sa.wf + nw);
+                w_word += nw + (nw + 1) / 2;
+            }
+            sa.bins = (unsigned long long *)at(pl.off_sum[k]); sa.skipped = (unsigned *)at(pl.off_skip[k]);
+            const size_t slds = (n_ex + n_ey + nw) * sizeof(double) + (nw + (pl.n_z ? (size_t)pl.n_z + 1 : 0)) * sizeof(float);   // (at most 28 KiB + 260 B)
+            if (pl.n_z) {
+                if (gates) {
+                    if (sum_combine) hipLaunchKernelGGL((k_comp_sum<true, true, true>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                    else hipLaunchKernelGGL((k_comp_sum<false, true, true>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                } else {
+                    if (sum_combine) hipLaunchKernelGGL((k_comp_sum<true, false, true>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                    else hipLaunchKernelGGL((k_comp_sum<false, false, true>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                }
+            } else if (gates) {
+                if (sum_combine) hipLaunchKernelGGL((k_comp_sum<true, true, false>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                else hipLaunchKernelGGL((k_comp_sum<false, true, false>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+            } else {
+                if (sum_combine) hipLaunchKernelGGL((k_comp_sum<true, false, false>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+                else hipLaunchKernelGGL((k_comp_sum<false, false, false>), dim3(grid), dim3(COMP_THREADS), slds, st, sa);
+            }
+            HIPCHK(hipGetLastError());
+        }
     }
     if (pl.finish)
         for (int i = 0; i < pl.n_fields; ++i) {
@@ -2795,6 +2867,14 @@ static int comp_launch(cpol_ctx *ctx, const cpol_composite *c, const CompPlan &p
             fa.cells = (int)pl.cells; fa.n_planes = pl.n_planes[k]; fa.n_fields = pl.n_fields; fa.n_thr = pl.n_thr[k];
             fa.bmax = (const unsigned char *)at(pl.off_src_max[k]); fa.blow = (const unsigned char *)at(pl.off_src_low[k]);
             hipLaunchKernelGGL(k_comp_finish, dim3((unsigned)cdiv(fa.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, fa);
+            HIPCHK(hipGetLastError());
+            if (!pl.sum) continue;
+            CompSumFinishArgs sf{};
+            sf.bins = (const unsigned long long *)at(pl.off_sum[k]); sf.skipped = (const unsigned *)at(pl.off_skip[k]);
+            sf.scount = fa.scount;
+            sf.sum = (double *)T[CP_SUM + k]; sf.sum_skipped = (unsigned *)T[CP_SKIPPED + k];
+            sf.n = fa.n;
+            hipLaunchKernelGGL(k_comp_sum_finish, dim3((unsigned)cdiv(sf.n, (long)COMP_THREADS)), dim3(COMP_THREADS), 0, st, sf);
             HIPCHK(hipGetLastError());
         }
     if (pl.finish && pl.column) {
@@ -2835,7 +2915,7 @@ struct CompHook {
     int32_t n_rows, n_gates, n_rays, lane_form;
     const float *in[CPOL_COMP_FIELDS];      // [n_rows * n_gates]; NULL = not given
     const float *heights, *dist;            // [n_rays * n_gates]; dist may be NULL on a gate plane (c.gate_x, c.gate_y: host arrays)
-    cpol_composite c;
+    cpol_composite c;               // with CPOL_COMP_SUM in c.products: the member `c` of a cpol_composite_sums, the last member of the hook's struct
 };
 
 static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
@@ -4818,6 +4898,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     }
     if (!strcmp(name, "composite_fields")) {        // a CONTROL name: dst points to a CompHook
         if (!dst || max_bytes < (int64_t)sizeof(CompHook)) { ctx->err = "cpol_debug_read(composite_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        if ((((const CompHook *)dst)->c.products & CPOL_COMP_SUM) && max_bytes < (int64_t)(offsetof(CompHook, c) + sizeof(cpol_composite_sums))) {
+            ctx->err = "cpol_debug_read(composite_fields): with CPOL_COMP_SUM the hook's struct ends in a cpol_composite_sums";
+            return CPOL_ERR_ARG;
+        }
         return comp_hook(ctx, (const CompHook *)dst);
     }
     if (!strcmp(name, "fractions_maps")) {          // a CONTROL name: dst points to a FracHook

@@ -6,7 +6,9 @@
 // check it without a GPU; comp_check_network.cpp, test_composite_network_cpu.py the network additions; comp_check_layers.cpp,
 // test_composite_layers_cpu.py the height layers and the column).  The kernels are k_comp,
 // k_comp_merge, k_comp_finish and k_comp_column (cpol_comp.inl); the rule is stated in
-// include/cosmo_pol_amd.h and cosmo_pol_amd/composite.py.
+// include/cosmo_pol_amd.h and cosmo_pol_amd/composite.py.  The exact sums (CPOL_COMP_SUM, cpol_composite_sums: the tail's
+// refusals, the bins of the state, the gates a pass may fold) are checked by comp_check_sums.cpp, test_composite_sums_cpu.py;
+// their kernels are k_comp_sum and k_comp_sum_finish.
 #pragma once
 
 #include <cmath>
@@ -24,11 +26,22 @@ constexpr long COMP_MAX_STATE_BYTES = 1L << 30;    // the state of all blocks an
 // is long enough for its own 12 KB of gates to outweigh them; the 180 000 gates of a 360 x 500 sweep give 176 workgroups
 constexpr int COMP_STRETCH = 1024;
 constexpr int COMP_THREADS = 256;                  // threads of a workgroup of k_comp and k_comp_finish
-constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE | CPOL_COMP_COLUMN;
+constexpr uint32_t COMP_PRODUCTS = CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP | CPOL_COMP_SOURCE | CPOL_COMP_COLUMN | CPOL_COMP_SUM;
 constexpr int COMP_MAX_LAYERS = CPOL_COMP_MAX_LAYERS;      // n_z: the float32 layer edges (at most 65) lie in LDS beside the x and y edges
 constexpr int COMP_MAX_TABLE = CPOL_COMP_MAX_TABLE;        // breakpoints of a column table: 4 KB + 8 KB of LDS in k_comp_column
 constexpr size_t COMP_TAB_EDGE_WORDS = 40;                 // float64 words at the head of the device's table block: room for the 65 float32 layer edges
 constexpr int COMP_NO_SOURCE = 255;               // the begin value of a source byte: no call has set the cell
+// ---- the exact sums (CPOL_COMP_SUM).  A finite float32 is  +-M * 2^(E - 150)  with E in 1 ... 254 and M < 2^24 (obj_sum_split,
+// cpol_obj.h).  THE ROW of a (block, layer, cell) and field: COMP_SUM_BINS signed 64-bit bins (two's complement, added as unsigned
+// long long); bin E >> 3 takes  +-M << (E & 7): the moment layout of cpol_obj.h with the multiplier 1, so obj_sum_round(row, 32, 8)
+// finishes a row unchanged.  NO OVERFLOW, a condition and not a measurement: a term is below 2^24 * 2^7 = 2^31 in magnitude, so
+// after n terms |bin| < n * 2^31, which is below 2^63 while n < 2^32: a bin cannot wrap while fewer than 2^32 gates fold into one
+// block of a pass.  CompPass keeps the gates folded per block so far, and comp_check refuses the call that would take them beyond
+// COMP_SUM_MAX_GATES.  The sum of a row is below 2^(8 * 31 + 63) = 2^311 in magnitude (in units of 2^-150): the 384 bits of
+// obj_sum_round hold it with its sign.  (k_comp_sum combines at most 64 terms of a wavefront before the atomic: below 2^37.) ----
+constexpr int COMP_SUM_BINS = 32;
+constexpr int COMP_SUM_ROW_BYTES = COMP_SUM_BINS * 8;
+constexpr unsigned long long COMP_SUM_MAX_GATES = 0xFFFFFFFFull;      // 2^32 - 1 gates per block of a pass
 
 // what the entry point knows of the call
 struct CompCall {
@@ -52,6 +65,10 @@ struct CompPass {
     int gaps = 0;
     std::vector<float> tv[COMP_FIELDS];
     std::vector<double> tf[COMP_FIELDS];
+    // the exact sums: per field the weight table as the begin found it (empty: w = v), and the gates folded into one block so far
+    std::vector<float> wv[COMP_FIELDS];
+    std::vector<double> wf[COMP_FIELDS];
+    unsigned long long sum_gates = 0;
 };
 
 // a call that passed: the numbers the launches need
@@ -90,6 +107,14 @@ struct CompPlan {
     std::vector<float> ez;                         // the ROUNDED layer edges [n_z + 1]
     std::vector<float> tv[COMP_FIELDS];            // the tables (empty: no column of the field)
     std::vector<double> tf[COMP_FIELDS];
+    // the exact sums (CPOL_COMP_SUM): in the part of the state that a begin sets to 0, behind the field's echo-top states, the
+    // rows of bins (int64 [n_blocks * block_cells][COMP_SUM_BINS]) and the skipped words (uint32 [n_blocks * block_cells], padded
+    // to 8 bytes); -1: off.  wv, wf: the weight tables (empty: w = v); sum_gates: the gates of a block once this call is folded
+    bool sum = false;
+    long off_sum[COMP_FIELDS] = {}, off_skip[COMP_FIELDS] = {};
+    std::vector<float> wv[COMP_FIELDS];
+    std::vector<double> wf[COMP_FIELDS];
+    unsigned long long sum_gates = 0;
 };
 
 // a threshold or slab bound rounded once to float32 (at or beyond the midpoint between FLT_MAX and 2^128: infinity, as IEEE rounds)
@@ -115,6 +140,11 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     pl->with_source = (c->products & CPOL_COMP_SOURCE) != 0;
     if (c->source != 0 && !pl->with_source) return "a non-zero source without SOURCE";
     if (pl->with_source && !(c->products & (CPOL_COMP_MAX | CPOL_COMP_LOWEST))) return "products: SOURCE needs MAX or LOWEST";
+    // the exact sums: only with the bit is *c the first member of a cpol_composite_sums, and only then is anything behind it read
+    pl->sum = (c->products & CPOL_COMP_SUM) != 0;
+    const cpol_composite_sums *const cs = pl->sum ? (const cpol_composite_sums *)c : nullptr;
+    if (pl->sum && !(c->products & (CPOL_COMP_MAX | CPOL_COMP_LOWEST | CPOL_COMP_ECHO_TOP))) return "products: SUM stands beside MAX, LOWEST or ECHO_TOP";
+    if (pl->sum && pl->with_source) return "products: SUM with SOURCE (the scratch-and-merge pass carries no sums)";
     pl->products = c->products;
     pl->plane = c->plane; pl->source = c->source;
     const bool tops = (c->products & CPOL_COMP_ECHO_TOP) != 0;
@@ -182,6 +212,19 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         }
         if (pl->column && !any_table) return "COLUMN needs a table for at least one requested field";
     }
+    for (int k = 0; cs && k < COMP_FIELDS; ++k) {
+        const int n = cs->n_weight[k];
+        if (n == 0) continue;
+        if (!((c->fields >> k) & 1u)) return "a weight table of a field that is not requested";
+        if (n < 2 || n > COMP_MAX_TABLE) return "a weight table needs 2 ... 1024 breakpoints";
+        if (!cs->weight_v[k] || !cs->weight_f[k]) return "weight_v or weight_f is NULL";
+        pl->wv[k].assign(cs->weight_v[k], cs->weight_v[k] + n);
+        pl->wf[k].assign(cs->weight_f[k], cs->weight_f[k] + n);
+        for (int j = 0; j < n; ++j) {
+            if (!std::isfinite(pl->wv[k][(size_t)j]) || !std::isfinite(pl->wf[k][(size_t)j])) return "a breakpoint or a value of a weight table is NaN or infinite";
+            if (j && !(pl->wv[k][(size_t)j - 1] < pl->wv[k][(size_t)j])) return "the breakpoints of a weight table are not strictly ascending";
+        }
+    }
     if (c->n_x < 1 || c->n_y < 1) return "n_x and n_y must be >= 1";
     if (c->n_x + 1 > COMP_MAX_EDGES || c->n_y + 1 > COMP_MAX_EDGES) return "n_x + 1 and n_y + 1 must be at most 1024";
     if (!c->edges_x || !c->edges_y) return "edges_x or edges_y is NULL";
@@ -198,6 +241,9 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
     // the state (n_blocks <= 2^31 rows, cells < 2^20, at most 9 * 28 bytes per cell and block, or 64 layers of 9 * 16 bytes: no
     // overflow of long)
     const long per = pl->n_blocks * pl->block_cells;
+    // (the exact sums: 260 bytes per cell and block -- beyond the limit before the product below could overflow)
+    if (pl->sum && per > COMP_MAX_STATE_BYTES / COMP_SUM_ROW_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
+    for (int k = 0; k < COMP_FIELDS; ++k) pl->off_sum[k] = pl->off_skip[k] = -1;
     long off = 0;
     for (int i = 0; i < pl->n_fields; ++i) {
         const int k = pl->field[i];
@@ -205,6 +251,10 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         if (c->products & CPOL_COMP_MAX) { pl->off_max[k] = off; off += per * 8; }
         pl->off_count[k] = off; off += per * 8;
         if (pl->n_thr[k]) { pl->off_top[k] = off; off += (per * pl->n_thr[k] * 4 + 7) & ~7L; }
+        if (pl->sum) {
+            pl->off_sum[k] = off; off += per * COMP_SUM_ROW_BYTES;
+            pl->off_skip[k] = off; off += (per * 4 + 7) & ~7L;
+        }
         if (off > COMP_MAX_STATE_BYTES) return "the state of all blocks and fields must be at most 1 GiB";
     }
     pl->zero_bytes = off;
@@ -246,6 +296,8 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         if (pass.gaps != pl->gaps) return "gaps differ from the open pass";
         for (int k = 0; k < COMP_FIELDS; ++k)
             if (pass.tv[k] != pl->tv[k] || pass.tf[k] != pl->tf[k]) return "a column table differs from the open pass";
+        for (int k = 0; k < COMP_FIELDS; ++k)
+            if (pass.wv[k] != pl->wv[k] || pass.wf[k] != pl->wf[k]) return "a weight table differs from the open pass";
     }
     if (pl->finish) {
         if (!c->count) return "a finishing call needs count";
@@ -254,6 +306,13 @@ inline const char *comp_check(const cpol_composite *c, const CompCall &call, con
         for (int k = 0; k < COMP_FIELDS; ++k)
             if (!pl->tv[k].empty() && (!c->column[k] || !c->column_layers[k]))
                 return "a finishing call needs column and column_layers for every field with a table";
+        for (int i = 0; cs && i < pl->n_fields; ++i)
+            if (!cs->sum[pl->field[i]] || !cs->sum_skipped[pl->field[i]]) return "a finishing call needs sum and sum_skipped for every requested field";
+    }
+    if (pl->sum) {
+        // NO OVERFLOW (above): the gates of one block once this call is folded (a call holds fewer than 2^31 * 1024 gates)
+        pl->sum_gates = (pl->begin ? 0ull : pass.sum_gates) + (unsigned long long)pl->rows_per_block * (unsigned long long)call.n_gates;
+        if (pl->sum_gates > COMP_SUM_MAX_GATES) return "SUM: more than 2^32 - 1 gates would fold into one block of the pass";
     }
     return nullptr;
 }
@@ -274,6 +333,8 @@ inline void comp_advance(const cpol_composite *c, const CompPlan &pl, CompPass *
         pass->ez = pl.ez;
         pass->gaps = pl.gaps;
         for (int k = 0; k < COMP_FIELDS; ++k) { pass->tv[k] = pl.tv[k]; pass->tf[k] = pl.tf[k]; }
+        for (int k = 0; k < COMP_FIELDS; ++k) { pass->wv[k] = pl.wv[k]; pass->wf[k] = pl.wf[k]; }
     }
+    pass->sum_gates = pl.sum_gates;               // (0 without SUM)
     if (pl.finish) pass->open = false;
 }

@@ -6,7 +6,8 @@
 // cosmo_pol_amd/composite.py (`compose`, `finish`): the cell of a gate is found by ONE float64 multiplication per axis (the
 // caller gives sine and cosine) and comparisons alone, and every result is a maximum, a minimum or a sum of INTEGERS (the ordered
 // keys of the float32 values) -- whatever order the hardware works in, the maps are those of NumPy.  No float atomics, no
-// compare-and-swap loops, no trigonometric function.
+// compare-and-swap loops, no trigonometric function.  The exact sums (CPOL_COMP_SUM: k_comp_sum, k_comp_sum_finish at the end of
+// this file) keep to that: a float32 is an integer multiple of 2^-149, the sums are sums of integers, rounded once.
 
 struct CompArgs {
     const float *v;                 // the field [n_rows * n_gates]
@@ -300,4 +301,127 @@ __global__ __launch_bounds__(COMP_THREADS) void k_comp_column(const CompColumnAr
     }
     a.column[i] = seen ? sum : __longlong_as_double(0x7FF8000000000000ll);
     a.layers[i] = (unsigned char)used;
+}
+
+// ---- the exact sums (CPOL_COMP_SUM, cpol_composite_sums): the cell mean, rain accumulations ----
+struct CompSumArgs {
+    CompArgs a;                     // as k_comp takes them (the states of k_comp are not read: smax, slow, scount, stop stay NULL)
+    const double *wf;               // the weight table's values [n_w] ...
+    const float *wv;                // ... and breakpoints [n_w], on the device (n_w == 0: w = v)
+    int n_w, step_w;                // step_w: the largest power of two <= n_w
+    unsigned long long *bins;       // this field's rows [n_blocks * block_cells][COMP_SUM_BINS], int64 as two's complement
+    unsigned *skipped;              // [n_blocks * block_cells]
+};
+
+// One launch per requested field behind that field's k_comp, with k_comp's ownership: a workgroup owns one stretch of COMP_STRETCH
+// consecutive gates of ONE block and never crosses a block boundary; the edges lie in LDS as in k_comp, the weight table behind
+// them (at most 8 KB of values and 4 KB of breakpoints), the layer edges last.  The cell of a gate: k_comp's statements.  Per
+// counting gate the weight w (obj_weight, or v itself), its split into sign, E and M (obj_sum_split), the term +-M << (E & 7)
+// (obj_sum_term, below 2^31) and the key (cell, E >> 3): the bin of the state the term goes to.  Consecutive gates of a ray share
+// the cell and nearly always the exponent bin, so with COMBINE the lanes of a wavefront that form a run of equal key are summed
+// first (a segmented INTEGER sum over __shfl_up, bounded by the run's first lane: at most 64 terms below 2^31, below 2^37, no
+// overflow; integer addition is associative and commutative, so the sum is exact whatever the grouping), and the LAST lane of
+// each run issues ONE 64-bit integer atomicAdd.  Without COMBINE every summed lane issues its own.  A gate whose w is not
+// finite adds one to the cell's skipped word (rare).  No float atomics, no compare-and-swap loops; the loop bounds: COMP_STRETCH /
+// COMP_THREADS turns, 6 steps of the scan, 11 of a search.  Every lane of the workgroup takes every turn of the gate loop.
+template <bool COMBINE, bool GATES, bool LAYERS>
+__global__ __launch_bounds__(COMP_THREADS) void k_comp_sum(const CompSumArgs s)
+{
+    extern __shared__ double comp_lds[];
+    const CompArgs &a = s.a;
+    const int tid = threadIdx.x;
+    double *const ex = comp_lds, *const ey = ex + a.n_ex, *const wf = ey + a.n_ey;
+    float *const wv = (float *)(wf + s.n_w), *const ez = wv + s.n_w;
+    for (int j = tid; j < a.n_ex; j += COMP_THREADS) ex[j] = a.ex[j];
+    for (int j = tid; j < a.n_ey; j += COMP_THREADS) ey[j] = a.ey[j];
+    for (int j = tid; j < s.n_w; j += COMP_THREADS) { wf[j] = s.wf[j]; wv[j] = s.wv[j]; }
+    if (LAYERS)
+        for (int j = tid; j <= a.n_z; j += COMP_THREADS) ez[j] = a.ez[j];
+    __syncthreads();
+    const long b = (long)blockIdx.x / a.stretches;
+    const long st = (long)blockIdx.x % a.stretches;
+    const long g0 = b * a.block_gates + st * (long)COMP_STRETCH;
+    const long g1 = min(g0 + (long)COMP_STRETCH, (b + 1) * a.block_gates);
+    const long cell0 = LAYERS ? b * a.block_cells : b * (long)a.cells;
+    // (every lane of the workgroup takes every turn of the loop: the shuffles below need whole wavefronts)
+    for (long base = g0; base < g1; base += COMP_THREADS) {
+        const long g = base + tid;
+        int cell = -1, key = -1;      // key: (cell, bin) of a summed gate
+        long long term = 0ll;
+        bool skip = false;
+        if (g < g1) {
+            const float v = a.v[g];
+            const long gg = g < a.geo_gates ? g : g % a.geo_gates;      // (the geometry of an ensemble call: n_rays rows once)
+            const float h = a.hgt[gg];
+            double x, y;
+            bool located;
+            if (GATES) {
+                x = a.gx[gg]; y = a.gy[gg];
+                located = x == x && y == y;
+            } else {
+                const int ray = (int)(gg / a.n_gates);
+                const float d = a.dist[gg];
+                x = (double)d * a.ray_sin[ray]; y = (double)d * a.ray_cos[ray];
+                located = d == d;
+            }
+            const int ix = hist_bin<double>(ex, a.n_ex, a.step_x, x) - 1;
+            const int iy = hist_bin<double>(ey, a.n_ey, a.step_y, y) - 1;
+            bool counts = v == v && located && h == h && ix >= 0 && ix < a.n_x && iy >= 0 && iy < a.n_y;
+            int iz = 0;
+            if (LAYERS) {
+                iz = hist_bin<float>(ez, a.n_z + 1, a.step_z, h) - 1;
+                counts = counts && iz >= 0 && iz < a.n_z;
+            } else if (a.slab) counts = counts && a.h_lo <= h && h < a.h_hi;
+            if (counts) {
+                cell = LAYERS ? iz * a.cells + iy * a.n_x + ix : iy * a.n_x + ix;
+                const float w = s.n_w ? obj_weight(wv, wf, s.n_w, s.step_w, v) : v;
+                const unsigned bits = __float_as_uint(w);
+                int E;
+                unsigned M;
+                if (obj_sum_split(bits, &E, &M)) {
+                    term = obj_sum_term(bits, M, 1u, E & 7);
+                    key = cell * COMP_SUM_BINS + (E >> 3);            // (cell < 2^26: below 2^31)
+                } else skip = true;
+            }
+        }
+        bool issue = key >= 0;
+        if (COMBINE) {
+            const int lane = tid & 63;
+            const int before = __shfl_up(key, 1);
+            const bool head = lane == 0 || before != key || key < 0;                      // (a gate that is not summed: a run of its own)
+            const unsigned long long heads = __ballot(head) & (~0ull >> (63 - lane));     // the heads at or below this lane
+            const int run = lane - (63 - __clzll((long long)heads));                       // lanes of this run before this one
+            for (int dlt = 1; dlt < 64 && __any(run >= dlt); dlt <<= 1) {
+                const long long o = __shfl_up(term, dlt);
+                if (run >= dlt) term += o;
+            }
+            const int after = __shfl_down(key, 1);
+            issue = issue && (lane == 63 || after != key);
+        }
+        if (issue) atomicAdd(&s.bins[(cell0 + cell) * (long)COMP_SUM_BINS + (key & (COMP_SUM_BINS - 1))], (unsigned long long)term);
+        if (skip) atomicAdd(&s.skipped[cell0 + cell], 1u);
+    }
+}
+
+struct CompSumFinishArgs {
+    const unsigned long long *bins;     // as in CompSumArgs
+    const unsigned *skipped;
+    const unsigned long long *scount;   // this field's counts, as in CompArgs
+    double *sum;                        // [n_blocks][n_z or absent][cells]
+    unsigned *sum_skipped;              // likewise
+    long n;                             // n_blocks * block_cells
+};
+
+// A finishing call: one thread per (block, layer, cell) of one field rounds the cell's row once (obj_sum_round: the bins
+// propagated into one integer, its top 53 bits, ties to even; +0.0 for an exact zero), writes NaN where no gate was summed
+// (count - skipped == 0) and copies the skipped word.
+__global__ __launch_bounds__(COMP_THREADS) void k_comp_sum_finish(const CompSumFinishArgs a)
+{
+    const long i = (long)blockIdx.x * COMP_THREADS + threadIdx.x;
+    if (i >= a.n) return;
+    const unsigned sk = a.skipped[i];
+    const unsigned long long n = a.scount[i];
+    const unsigned long long r = n - (unsigned long long)sk ? obj_sum_round(a.bins + i * (long)COMP_SUM_BINS, COMP_SUM_BINS, 8) : 0x7FF8000000000000ull;
+    a.sum[i] = __longlong_as_double((long long)r);
+    a.sum_skipped[i] = sk;
 }

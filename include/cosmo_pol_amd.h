@@ -632,10 +632,45 @@ typedef struct cpol_histogram {
  * without COLUMN; n_table[k] non-zero without COLUMN or for a field not requested; n_table[k] outside 2 ... 1024; a NULL table;
  * a breakpoint or value NaN or infinite; breakpoints not strictly ascending; COLUMN with no table at all; layers, tables or gaps
  * differing from the open pass; a finishing call with a NULL column or column_layers of a field with a table; the 1 GiB limit,
- * which counts n_blocks * n_z * cells per MAX state and count. */
+ * which counts n_blocks * n_z * cells per MAX state and count.
+ *
+ * SUM (the product bit CPOL_COMP_SUM = 256 and the struct cpol_composite_sums below; bits 8, 32 and 128 stay refused as unknown
+ * bits): the exact sum of the counting gates' weights per (block, layer, cell), for the cell MEAN and for rain accumulations.
+ * Everything above stays as it is; cpol_outputs.composite points at the member `c` of a cpol_composite_sums, and the library
+ * reads beyond `c` only when c.products carries the bit.  cosmo_pol_amd/composite.py states the same rule.
+ *   1. A gate counts for field k exactly as above: the same cell search, slab, layers, blocks and pass.
+ *   2. The summand of a counting gate is w = v when field k has no weight table (n_weight[k] == 0).  With a table (weight_v[k]
+ *      float32, weight_f[k] float64) it is w = float32(f(v)), f the piecewise-linear function of the column table above: 0 below
+ *      the table, the last value at and above its end, every operation one float64 operation, then ONE rounding to float32
+ *      (obj_weight in cpol_obj.h, objects.weight_of).  The table conditions are those of the column table: 2 ... 1024
+ *      breakpoints, finite, strictly ascending in float32, finite values; no monotonicity is demanded of the values.
+ *   3. Per (block, layer, cell) `sum` is the EXACT sum of the finite w, rounded ONCE to float64 with ties to even: math.fsum of
+ *      the summands.  +0.0 when the exact sum is zero, NaN when no gate was summed.
+ *   4. Per (block, layer, cell) `sum_skipped` (uint32) is the number of counting gates with w = +-inf.  Such a gate is not
+ *      summed, and it still counts in `count`.
+ *   5. The mean is sum / (count - sum_skipped): one float64 division, formed on the host (composite.mean_of), NaN where the
+ *      divisor is 0.
+ *   6. Nothing depends on the order of the gates, the lane form, the block cut or how the pass is cut into calls.
+ * HOW: a finite float32 is +-M * 2^(E - 150) with E in 1 ... 254 and M < 2^24 (cpol_obj.h).  The state gains per requested field
+ * and (block, layer, cell) a row of 32 signed 64-bit bins and one uint32 skipped word, zeroed by a begin; bin E >> 3 takes
+ * +-M << (E & 7) by a 64-bit INTEGER atomic add (k_comp_sum, one launch per field behind k_comp), and a finishing call rounds each
+ * row once (k_comp_sum_finish, obj_sum_round).  Integer additions commute: no order of the hardware enters.
+ * NO OVERFLOW (a condition, not a measurement): a term is below 2^31 in magnitude, so a bin cannot wrap while fewer than 2^32
+ * gates fold into one block of a pass.  The library keeps the gates folded per block (rows_per_block * n_gates per call, n_rows *
+ * n_gates with rays_per_block == 0) and refuses the call that would take them beyond 2^32 - 1, with nothing queued and the pass
+ * untouched.
+ * SUM stands beside at least one of MAX, LOWEST, ECHO_TOP (products = 256 alone is refused); SUM with SOURCE is refused; SUM with
+ * layers gives a 3-D grid of sums.  COLUMN, a gate plane, several radars in one pass, blocks per member and a cpol_fractions
+ * beside it work as before; the planes of values[k] do not change, so the scored plane cannot be the sum.
+ * CPOL_ERR_ARG in addition: SUM alone; SUM with SOURCE; n_weight[k] non-zero for a field not requested; n_weight[k] outside
+ * 2 ... 1024; a NULL table; a breakpoint or value NaN or infinite; breakpoints not strictly ascending; weight tables differing
+ * from the open pass; a finishing call with a NULL sum or sum_skipped of a requested field; the 1 GiB limit, which counts the
+ * bins and the skipped words; the 2^32 - 1 gates per block of a pass.
+ * NOT BUILT: SUM alone, SUM with SOURCE, sums of RVEL, means in dB, a carry-normalising kernel for passes beyond 2^32 gates. */
 #define CPOL_COMP_FIELDS 9
 #define CPOL_COMP_MAX_THRESHOLDS 4
-enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4, CPOL_COMP_SOURCE = 16, CPOL_COMP_COLUMN = 64 };     /* (8 and 32 are no products: refused) */
+enum { CPOL_COMP_MAX = 1, CPOL_COMP_LOWEST = 2, CPOL_COMP_ECHO_TOP = 4, CPOL_COMP_SOURCE = 16, CPOL_COMP_COLUMN = 64,
+       CPOL_COMP_SUM = 256 };                       /* (8, 32 and 128 are no products: refused) */
 #define CPOL_COMP_MAX_LAYERS 64
 #define CPOL_COMP_MAX_TABLE 1024
 enum { CPOL_COMP_GAPS_ZERO = 0, CPOL_COMP_GAPS_HOLD = 1 };
@@ -667,6 +702,16 @@ typedef struct cpol_composite {
     double   *column[CPOL_COMP_FIELDS];         /* [n_blocks][n_y][n_x]; read by a finishing call                  */
     uint8_t  *column_layers[CPOL_COMP_FIELDS];  /* [n_blocks][n_y][n_x]; likewise                                  */
 } cpol_composite;
+
+/* SUM (above): cpol_outputs.composite points at `c`; the library reads beyond it only when c.products carries CPOL_COMP_SUM. */
+typedef struct cpol_composite_sums {
+    cpol_composite c;                               /* c.products carries CPOL_COMP_SUM                            */
+    int32_t  n_weight[CPOL_COMP_FIELDS];            /* 0: w = v; else 2 ... CPOL_COMP_MAX_TABLE breakpoints         */
+    const float  *weight_v[CPOL_COMP_FIELDS];       /* [n_weight[k]] breakpoints in the field's linear units       */
+    const double *weight_f[CPOL_COMP_FIELDS];       /* [n_weight[k]] values at the breakpoints                     */
+    double   *sum[CPOL_COMP_FIELDS];                /* [n_blocks][n_z or absent][n_y][n_x]; a finishing call       */
+    uint32_t *sum_skipped[CPOL_COMP_FIELDS];        /* likewise                                                    */
+} cpol_composite_sums;
 
 /* Neighbourhood verification: the sums of the fractions skill score (FSS; Roberts and Lean 2008) of ONE finished plane of a
  * composite against an observed map on the same grid, per block, threshold and neighbourhood size, reduced on the device, for
@@ -1375,7 +1420,10 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * CPOL_COMP_PLANE_GATES c.gate_x and c.gate_y are host arrays [n_rays * n_gates] (kept under c.plane_version like a sweep's) and
  * dist may be NULL; with CPOL_COMP_SOURCE in c.products the call runs k_comp_merge too, with c.source.  With height layers
  * (c.n_z > 0) the call runs the layered k_comp, and a finishing call with CPOL_COMP_COLUMN runs k_comp_column and copies
- * c.column / c.column_layers (host arrays) too.
+ * c.column / c.column_layers (host arrays) too.  With CPOL_COMP_SUM in c.products `c` is the member `c` of a cpol_composite_sums,
+ * the last member of the hook's struct (max_bytes covers it): the call runs k_comp_sum behind k_comp (lane_form: 0 the kept form,
+ * 1 the runs of a wavefront summed first, 2 every lane on its own) and a finishing call k_comp_sum_finish, and copies sum /
+ * sum_skipped (host arrays) too.  Without the bit the hook takes and returns exactly what it did.
  * "composite_plane" copies two int64: {uploads, hits} of the context's store of gate planes (cpol_composite.plane_version).
  * "composite_stretch" copies one int32: the gates a workgroup of k_comp owns.
  * "fractions_maps" is the same for the neighbourhood verification: the checks and the three kernels of cpol_frac.inl on

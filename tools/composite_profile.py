@@ -36,6 +36,20 @@ Kernel times of the layered k_comp against the plain one, and of k_comp_column, 
     rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/composite_profile.py --worker lay_forms --trace
 (the five sweeps of the volume fed through the test hook: plain and layered spec, both lane forms).
 
+--sums: the exact sums (the product 'sum').  The ZH composite on the 300 x 300 grid with ('max', 'sum') under
+objects.zr_table() -- the mean rain rate per cell -- written to profiles/composite_sums_profile.json:
+
+  sum_dev / b          simulate_rays_composite with ('max', 'sum') against the same call with ('max',): the map alone;
+  sum_host             what a user did before: simulate_rays (every per-gate array), then the weight and np.bincount(weights=) on the host;
+  sum_vol_dev / vol_dev / sum_vol_host     the same three for the 5-elevation volume (get_PPI_composite; get_PPI's lanes and one bincount);
+  sum_ens_dev / ens_dev / sum_ens_host     the same three for the --members ensemble, one map per member;
+  b / parent_b, bench / parent_bench       the controls: the plain composite call and bench.py's line, this tree and DIR.
+
+Kernel times of k_comp_sum in both lane forms and of k_comp_sum_finish, beside k_comp's, from
+    rocprofv3 --kernel-trace --stats -d DIR -o NAME -- python tools/composite_profile.py --worker sum_forms --trace
+(the bench sweep's arrays through the test hook); the kernel list and launch counts of a call without 'sum' from the same kind of
+run of --worker b in this tree and in DIR (--kernel-stats control=FILE, parent_control=FILE: 'control_kernels_equal').
+
   python tools/composite_profile.py --repeat 3 --out profiles/composite_profile.json
   python tools/composite_profile.py --layers --repeat 3 --parent-tree DIR --bench
   python tools/composite_profile.py --worker b            (one process, one JSON line)
@@ -54,7 +68,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOM = ('lats', 'lons', 'dist', 'heights')
 N_RAYS = 360
 ELEVATIONS = [1.0, 3.0, 5.0, 8.0, 12.0]
-WORKERS = ('a', 'b', 'c', 'vol_dev', 'vol_host', 'ens_dev', 'forms', 'lay_dev', 'lay_slabs', 'lay_forms')
+WORKERS = ('a', 'b', 'c', 'vol_dev', 'vol_host', 'ens_dev', 'forms', 'lay_dev', 'lay_slabs', 'lay_forms',
+           'sum_dev', 'sum_host', 'sum_vol_dev', 'sum_vol_host', 'sum_ens_dev', 'sum_ens_host', 'sum_forms')
 LAYER_EDGES = [500.0 * j for j in range(21)]          # 20 layers of 500 m
 
 
@@ -73,7 +88,7 @@ def result_bytes(res):
     for planes in w.get('values', {}).values():
         n += sum(a.nbytes for a in planes.values())
     n += sum(a.nbytes for a in w.get('count', {}).values())
-    for q in ('column', 'column_layers'):
+    for q in ('column', 'column_layers', 'sum', 'sum_skipped'):
         n += sum(a.nbytes for a in w.get(q, {}).values())
     for s in res.get('sweeps', []):
         n += result_bytes(s)
@@ -90,7 +105,7 @@ def worker(a):
     az, el = np.arange(float(N_RAYS)), np.full(N_RAYS, 1.0)
     grid = (cube['zlevels'], cube['proj_info'], cube['resolution'])
     op = RadarOperator(config=conf, luts=luts, output_variables='only_radar')
-    if a.worker == 'ens_dev':
+    if a.worker in ('ens_dev', 'sum_ens_dev', 'sum_ens_host'):
         from timed_profile import perturbed
         op.load_model_ensemble([cube['data']] + [perturbed(cube['data'], 100 + m) for m in range(1, a.members)], *grid)
     else:
@@ -108,6 +123,33 @@ def worker(a):
             for form in (1, 2):
                 for s in (spec, every):
                     op._ctx.composite_fields({'ZH': np.array(res['ZH'])}, res['dist'], res['heights'], az, s, lane_form=form)
+        op.close()
+        return
+    if a.worker.startswith('sum_'):
+        from cosmo_pol_amd import objects as OB
+        zr = OB.zr_table()
+        summed = CP.Composite('ZH', e, e, products=('max', 'sum'), weight={'ZH': zr})
+        rs, rc = CP.ray_tables(az)
+
+        def host_sums(zh, dist):
+            """the mean rain rate per cell on the host: the weight of every gate, the cell of every gate, np.bincount(weights=)"""
+            d = np.asarray(dist, dtype=np.float64)
+            ix = np.searchsorted(e, d * rs[:, None], side='right') - 1
+            iy = np.searchsorted(e, d * rc[:, None], side='right') - 1
+            cells = (len(e) - 1) ** 2
+            cell = iy * (len(e) - 1) + ix
+            out = []
+            for m in np.asarray(zh).reshape(-1, *d.shape):
+                w = OB.weight_of(m, zr)
+                ok = np.isfinite(w) & (d == d) & (ix >= 0) & (ix < len(e) - 1) & (iy >= 0) & (iy < len(e) - 1)
+                out.append((np.bincount(cell[ok], weights=w[ok].astype(np.float64), minlength=cells), np.bincount(cell[ok], minlength=cells)))
+            return out
+    if a.worker == 'sum_forms':
+        # both lane forms of k_comp_sum (and of k_comp) on the bench sweep's own arrays, through the test hook
+        res = op.simulate_rays(az, el)
+        for _ in range(max(1, a.warmup)):
+            for form in (1, 2):
+                op._ctx.composite_fields({'ZH': np.array(res['ZH'])}, res['dist'], res['heights'], az, summed, lane_form=form)
         op.close()
         return
     if a.worker.startswith('lay_'):
@@ -135,6 +177,29 @@ def worker(a):
             return {'composite': {'values': {'ZH': {'max': stack, 'height_of_max': np.stack([m['values']['ZH']['height_of_max'] for m in maps], axis=1)}},
                                   'count': {'ZH': np.stack([m['count']['ZH'] for m in maps], axis=1)}, 'column': {'ZH': col},
                                   'column_layers': {'ZH': lay}}}
+    elif a.worker == 'sum_dev':
+        run = lambda: op.simulate_rays_composite(az, el, summed)
+    elif a.worker == 'sum_vol_dev':
+        run = lambda: op.get_PPI_composite(ELEVATIONS, summed, azimuths=az)
+    elif a.worker == 'sum_ens_dev':
+        run = lambda: op.simulate_rays_ensemble_composite(az, el, summed)
+    elif a.worker == 'sum_host':
+        def run():
+            res = op.simulate_rays(az, el)
+            res['host_sums'] = host_sums(res['ZH'], res['dist'])
+            return res
+    elif a.worker == 'sum_ens_host':
+        def run():
+            res = op.simulate_rays_ensemble(az, el)
+            res['host_sums'] = host_sums(res['ZH'], res['dist'])
+            return res
+    elif a.worker == 'sum_vol_host':
+        def run():
+            sweeps = [op.simulate_rays(az, np.full(N_RAYS, e_), pinned=True, lane=i % op.lanes) for i, e_ in enumerate(ELEVATIONS)]
+            for i in range(op.lanes):
+                op.wait(i)
+            parts = [host_sums(s['ZH'], s['dist'])[0] for s in sweeps]
+            return {'sweeps': sweeps, 'host_sums': [(sum(p[0] for p in parts), sum(p[1] for p in parts))]}
     elif a.worker == 'a':
         run = lambda: op.simulate_rays(az, el)
     elif a.worker == 'ens_dev':
@@ -165,9 +230,12 @@ def worker(a):
     out = {'call': a.worker, 'n_rays': N_RAYS, 'n_gates': len(op.constants.RANGE_RADAR), 'steps': a.steps,
            'ms_per_call_median': float(np.median(t)), 'ms_min': float(np.min(t)), 'ms_max': float(np.max(t)),
            'bytes_handed_over': result_bytes(res)}
-    if a.worker == 'ens_dev':
+    if 'ens' in a.worker:
         out['members'] = a.members
-    if a.worker.startswith('vol'):
+    if 'host_sums' in res:
+        out['host_sum_total'] = float(sum(t.sum() for t, _ in res['host_sums']))
+        out['summed'] = int(sum(n.sum() for _, n in res['host_sums']))
+    if 'vol' in a.worker:
         out['elevations'] = ELEVATIONS
     if 'ZH' in res:
         out['zh_checksum'] = float(np.nansum(res['ZH'], dtype=np.float64))
@@ -178,6 +246,12 @@ def worker(a):
         out['cells_non_empty'] = int((n > 0).sum())
         out['cells'] = int(n.size)
         out['max_checksum'] = float(np.nansum(m, dtype=np.float64))
+        if 'sum' in w:
+            out['sum_total'] = float(np.nansum(w['sum']['ZH']))
+            out['summed'] = int(n.sum()) - int(np.asarray(w['sum_skipped']['ZH'], dtype=np.int64).sum())
+            mean = CP.mean_of(w, 'ZH')
+            out['mean_rain_rate_max_mm_h'] = float(np.nanmax(mean))
+            out['sum_bits_xor'] = int(np.bitwise_xor.reduce(np.ascontiguousarray(w['sum']['ZH']).view(np.uint64).ravel()))
         if 'column' in w:
             col = np.ascontiguousarray(w['column']['ZH'])
             out['column_cells'] = int(np.isfinite(col).sum())
@@ -192,9 +266,14 @@ def worker(a):
 def kernel_name(n):
     """k_comp_finish, k_comp_combined (the wavefront combine), k_comp_per_lane, or the bare name of another kernel"""
     n = n.split('(')[0]
-    for plain in ('k_comp_finish', 'k_comp_column', 'k_comp_merge'):
+    for plain in ('k_comp_sum_finish', 'k_comp_finish', 'k_comp_column', 'k_comp_merge'):
         if plain in n:
             return plain
+    if 'k_comp_sum' in n:
+        # k_comp_sum<COMBINE, GATES, LAYERS>
+        args = [x.strip() for x in (n.split('<', 1)[1].split('>')[0] if '<' in n else '').split(',')]
+        on = lambda i: len(args) > i and args[i] in ('true', '1')       # noqa: E731
+        return ('k_comp_sum_combined' if on(0) else 'k_comp_sum_per_lane') + ('_layers' if on(2) else '')
     if 'k_comp' in n:
         # k_comp<COMBINE, GATES, LAYERS>: the first argument names the lane form, the third the layered instantiation
         args = [x.strip() for x in (n.split('<', 1)[1].split('>')[0] if '<' in n else '').split(',')]
@@ -265,6 +344,10 @@ def driver(a):
     if a.layers:
         tags = ['lay_dev', 'lay_slabs', 'b'] + (['parent_b'] if a.parent_tree else [])
         a.out = a.out or os.path.join(ROOT, 'profiles', 'composite_layers_profile.json')
+    if a.sums:
+        tags = ['sum_dev', 'b', 'sum_host', 'sum_vol_dev', 'vol_dev', 'sum_vol_host'] + (['sum_ens_dev', 'ens_dev', 'sum_ens_host'] if a.members else []) \
+            + (['parent_b'] if a.parent_tree else [])
+        a.out = a.out or os.path.join(ROOT, 'profiles', 'composite_sums_profile.json')
     if a.bench:
         tags += ['bench'] + (['parent_bench'] if a.parent_tree else [])
     if a.calls:
@@ -304,7 +387,8 @@ def driver(a):
         c = {'ms_per_call_median_of_processes': float(np.median(med)), 'ms_per_call_medians': med,
              'spread': float((max(med) - min(med)) / np.median(med))}
         for k in ('bytes_handed_over', 'zh_checksum', 'max_checksum', 'counted', 'cells_non_empty', 'cells', 'members', 'elevations',
-                  'column_cells', 'column_max_kg_m2', 'column_bits_xor', 'column_layers_sum', 'stack_bits_xor'):
+                  'column_cells', 'column_max_kg_m2', 'column_bits_xor', 'column_layers_sum', 'stack_bits_xor',
+                  'sum_total', 'host_sum_total', 'summed', 'mean_rain_rate_max_mm_h', 'sum_bits_xor'):
             if k in recs[0]:
                 c[k] = recs[0][k]
         result['calls'][tag] = c
@@ -332,6 +416,14 @@ def driver(a):
                                           for k in ('column_bits_xor', 'column_layers_sum', 'column_cells')))
         result['stack_equal'] = bool(all(calls['lay_dev'].get(k) == calls['lay_slabs'].get(k) is not None
                                          for k in ('stack_bits_xor', 'counted', 'max_checksum')))
+    for dev, plain, host, name in (('sum_dev', 'b', 'sum_host', 'sweep'), ('sum_vol_dev', 'vol_dev', 'sum_vol_host', 'volume'),
+                                   ('sum_ens_dev', 'ens_dev', 'sum_ens_host', 'ensemble')):
+        if all(t in calls for t in (dev, plain, host)):
+            if 'workload' in result and '--sums' not in result['workload']:
+                result['workload'] += "; --sums: ZH on the 300 x 300 grid, ('max', 'sum') under objects.zr_table()"
+            result['sums_' + name] = {'with_sum_over_max_alone_ms': ms(dev) / ms(plain), 'with_sum_minus_max_alone_ms': ms(dev) - ms(plain),
+                                      'device_over_host_ms': ms(dev) / ms(host), 'summed_gates_equal': bool(calls[dev].get('summed') == calls[host].get('summed')),
+                                      'host_total_minus_exact_total': calls[host].get('host_sum_total', 0.0) - calls[dev].get('sum_total', 0.0)}
     if 'parent_b' in calls and 'b' in calls:
         cb, pb = calls['b'], calls['parent_b']
         result['control_composite'] = {'b_over_parent_b_ms': ms('b') / ms('parent_b'),
@@ -350,9 +442,16 @@ def driver(a):
         name, path = item.split('=', 1)
         tb = kernel_table(path)
         result.setdefault('kernels', {})[name] = {k: tb.get(k) for k in ('k_comp_combined', 'k_comp_per_lane', 'k_comp_finish')}
-        for k in ('k_comp_combined_layers', 'k_comp_per_lane_layers', 'k_comp_column'):       # (a run with height layers)
+        for k in ('k_comp_combined_layers', 'k_comp_per_lane_layers', 'k_comp_column',            # (a run with height layers)
+                  'k_comp_sum_combined', 'k_comp_sum_per_lane', 'k_comp_sum_finish'):               # (a run with the exact sums)
             if k in tb:
                 result['kernels'][name][k] = tb[k]
+        if name in ('control', 'parent_control'):
+            # the whole kernel list of a call without 'sum': names and launch counts
+            result.setdefault('kernel_lists', {})[name] = {k: v['calls'] for k, v in sorted(tb.items())}
+    lists = result.get('kernel_lists', {})
+    if 'control' in lists and 'parent_control' in lists:
+        result['control_kernels_equal'] = bool(lists['control'] == lists['parent_control'])
     line = json.dumps(result, indent=1, sort_keys=True)
     print(line)
     if a.out:
@@ -374,6 +473,8 @@ def main():
     ap.add_argument('--update', action='store_true', help='join the calls of this session to those --out already holds')
     ap.add_argument('--layers', action='store_true', help='height layers and the column: lay_dev against lay_slabs, the controls b / parent_b; '
                     'writes profiles/composite_layers_profile.json unless --out names another file')
+    ap.add_argument('--sums', action='store_true', help="the exact sums: ('max', 'sum') under zr_table against ('max',) and against the host, "
+                    'sweep, volume and ensemble; writes profiles/composite_sums_profile.json unless --out names another file')
     ap.add_argument('--bench', action='store_true', help="bench.py's result line too (of the parent tree as well)")
     ap.add_argument('--process-timeout', type=float, default=400.0)
     ap.add_argument('--parent-tree', default=None, help='a checkout of the parent commit with its library built')
