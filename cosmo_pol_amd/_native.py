@@ -195,6 +195,18 @@ class ObjectsMatch(C.Structure):
     _fields_ = [('o', Objects), ('n_pieces', C.c_void_p), ('pieces', C.c_void_p), ('covered', C.c_void_p)]
 
 
+OBJ_TRACK = 1 << 30                                 # CPOL_OBJ_TRACK in cpol_objects.pad_
+
+
+class ObjectsTrack(C.Structure):
+    """cpol_objects_track: a cpol_objects_match whose o.pad_ carries OBJ_TRACK (its low 16 bits stay max_pieces of the match, 0 =
+    that match is off), and behind it the terms and the outputs of the track (objects.py, TRACK).  cpol_fractions.objects points
+    at `m.o`; the library reads beyond `m` only with OBJ_TRACK.  shifts_in: a host array."""
+    _fields_ = [('m', ObjectsMatch), ('max_shift', C.c_int32), ('max_pieces', C.c_int32), ('shifts_in', C.c_void_p),
+                ('correlation', C.c_void_p), ('shift', C.c_void_p), ('n_pieces', C.c_void_p), ('pieces', C.c_void_p),
+                ('covered', C.c_void_p)]
+
+
 class FractionProbabilities(C.Structure):
     """cpol_fraction_probabilities: the neighbourhood ensemble probabilities of the blocks of a cpol_fractions
     (cosmo_pol_amd/neighbourhood.py states the rule: `ensemble_sums`).  member_sum, member_any: NULL = not wanted."""
@@ -1278,11 +1290,24 @@ class Context(object):
         return f, []
 
     @staticmethod
-    def objects_struct(spec, fractions):
+    def objects_struct(spec, fractions, shifts=None):
         """(Objects for a call under `spec` (an objects.Objects), hung on `fractions` (the call's Fractions); what must stay alive):
         the output pointers are the caller's.  With spec.match the Objects is the first member of an ObjectsMatch, which is the
-        first of what must stay alive and takes n_pieces, pieces and covered."""
-        if getattr(spec, 'match', False):
+        first of what must stay alive and takes n_pieces, pieces and covered.  With spec.track that is in turn the first member
+        of an ObjectsTrack, the first of what must stay alive, which takes the five arrays of the track; `shifts`: the given
+        shifts of the call, int32 [n_blocks - 1, n_thr, 2] contiguous (objects.shifts_of_call), with spec.shifts."""
+        if getattr(spec, 'track', False):
+            ot = ObjectsTrack()
+            o = ot.m.o                                # (shares ot's memory)
+            o.pad_ = OBJ_TRACK | (spec.max_pieces if getattr(spec, 'match', False) else 0)
+            ot.max_shift = -1 if spec.max_shift is None else spec.max_shift
+            ot.max_pieces = spec.max_track_pieces
+            keep = [ot]
+            if spec.max_shift is None:
+                ot.shifts_in = shifts.ctypes.data
+                keep.append(shifts)
+            fractions.objects = C.cast(C.pointer(ot), C.POINTER(Objects))
+        elif getattr(spec, 'match', False):
             om = ObjectsMatch()
             o = om.o                                  # (shares om's memory)
             o.pad_ = spec.max_pieces
@@ -1318,7 +1343,8 @@ class Context(object):
         [n_y, n_x]; domain: uint8 [n_y, n_x] or None; `spec`: a neighbourhood.Fractions, or any object with `thresholds_given`
         and `radii` (the maps need not be those of spec.composite's grid).  `tamper(f)`: changes the cpol_fractions before the call
         (the refusal tests).  `objects`: an objects.Objects or any object with `connectivity`, `min_area`, `max_objects` and
-        `labels` (and `sums` with `weight` for the exact sums, `match` with `max_pieces` for the match): the kernels of
+        `labels` (and `sums` with `weight` for the exact sums, `match` with `max_pieces` for the match, `track` with `max_shift`,
+        `shifts` and `max_track_pieces` for the track, whose outputs are prefilled with 77): the kernels of
         cpol_obj.inl run too, and the result is (the sums, what objects.cells returns for the maps);
         `tamper` then finds the cpol_objects at f.objects.contents.  `probabilities`: a neighbourhood.Probabilities or any object
         with `maps` and `any_maps` (which of the two maps are wanted): k_frac_members runs too, and the result gains, as its last
@@ -1359,7 +1385,12 @@ class Context(object):
         f.sums, f.totals = s.ctypes.data, t.ctypes.data
         if objects is not None:
             from . import objects as OB
-            o, okeep = Context.objects_struct(objects, f)
+            with_track = getattr(objects, 'track', False)
+            n_pairs = max(m.shape[0] - 1, 0)
+            given = None
+            if with_track and objects.max_shift is None:      # (a call of one block still reaches the library, which refuses it)
+                given = np.ascontiguousarray(np.broadcast_to(objects.shifts, (max(n_pairs, 1), nt, 2)), dtype=np.int32)
+            o, okeep = Context.objects_struct(objects, f, given)
             n_obj = np.full((m.shape[0] + 1, nt), 0xDEADBEEF, dtype=np.uint32)
             table = np.full((m.shape[0] + 1, nt, objects.max_objects, OBJ_WORDS), 0xDEADBEEF, dtype=np.uint32)
             o.n_objects, o.table = n_obj.ctypes.data, table.ctypes.data
@@ -1378,7 +1409,18 @@ class Context(object):
                 omatch = [np.full((m.shape[0], nt), 0xDEADBEEF, dtype=np.uint32),
                           np.full((m.shape[0], nt, objects.max_pieces, OBJ_WORDS), 0xDEADBEEF, dtype=np.uint32),
                           np.full((m.shape[0], nt, 2, objects.max_objects), 0xDEADBEEF, dtype=np.uint32)]
-                okeep[0].n_pieces, okeep[0].pieces, okeep[0].covered = [q.ctypes.data for q in omatch]
+                om = okeep[0].m if with_track else okeep[0]
+                om.n_pieces, om.pieces, om.covered = [q.ctypes.data for q in omatch]
+            otrack = None
+            if with_track:
+                # (prefilled with 77: the zero rows are the library's, and a correlation that is not computed stays as it is)
+                side = 2 * (objects.max_shift or 0) + 1
+                otrack = [np.full((n_pairs, nt, side, side), 77, dtype=np.uint32), np.full((n_pairs, nt, 2), 77, dtype=np.int32),
+                          np.full((n_pairs, nt), 77, dtype=np.uint32),
+                          np.full((n_pairs, nt, objects.max_track_pieces, OBJ_WORDS), 77, dtype=np.uint32),
+                          np.full((n_pairs, nt, 2, objects.max_objects), 77, dtype=np.uint32)]
+                ot = okeep[0]
+                ot.correlation, ot.shift, ot.n_pieces, ot.pieces, ot.covered = [q.ctypes.data for q in otrack]
             keep += okeep
         q = None
         if probabilities is not None:
@@ -1406,7 +1448,12 @@ class Context(object):
         del keep
         out = [NB.result(spec, s, t)]
         if objects is not None:
-            out.append(OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums, omatch))
+            # (given shifts: no correlation is delivered; the array the library was handed all the same is 'track_correlation_buffer')
+            computed = otrack is not None and objects.max_shift is not None
+            out.append(OB.result(_ObjectsNamed(objects, spec, m.shape[1:]), n_obj, table, labels, osums, omatch,
+                                 otrack if otrack is None or computed else [None] + otrack[1:]))
+            if otrack is not None and not computed:
+                out[-1]['track_correlation_buffer'] = otrack[0]
         if probabilities is not None:
             out.append(NB.ensemble_result(spec, m.shape[0], *pout))
         return out[0] if len(out) == 1 else tuple(out)

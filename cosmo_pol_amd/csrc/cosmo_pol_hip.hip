@@ -225,12 +225,13 @@ struct cpol_ctx {
     // outputs), `sums` and `totals` outside a window image and the caller's device memory, the maps of the test hook; the plan of
     // the call at hand; prob_sums, reliability, member_sum and member_any of the neighbourhood ensemble probabilities
     // (cpol_fraction_probabilities) are b_fout[12 ... 15]
-    DevBuf b_fsat, b_fobs, b_fout[16], b_fmaps;
+    DevBuf b_fsat, b_fobs, b_fout[21], b_fmaps;
     FracPlan fplan;
     // object cells (cpol_objects, beside a cpol_fractions): the labelling scratch and the plan of the call at hand; n_objects, table
     // and labels are b_fout[2 ... 4], volume, skipped, field and field_cells of the exact sums b_fout[5 ... 8]; the sums'
     // accumulators and the weight table lie behind the labelling scratch (ObjPlan); n_pieces, pieces and covered of the match
-    // b_fout[9 ... 11], the piece scratch behind everything else
+    // b_fout[9 ... 11], the piece scratch behind everything else; correlation, shift, n_pieces, pieces and covered of the track
+    // (cpol_objects_track) b_fout[16 ... 20], the track scratch behind the piece scratch
     DevBuf b_oscr;
     ObjPlan oplan;
     DevBuf b_mvobs;                        // verification (cpol_member_verify) with host outputs: the caller's observations on the device
@@ -841,6 +842,7 @@ void cpol_destroy(cpol_ctx *ctx)
                      &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
                      &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
     for (DevBuf *b : all) free_buf(*b);
+    for (int k = 9; k < 21; ++k) free_buf(ctx->b_fout[k]);          // (the match, the probabilities, the track)
     for (int k = CPOL_COMP_FIELDS + 1; k < 5 * CPOL_COMP_FIELDS + 1; ++k) free_buf(ctx->b_cout[k]);     // (column, column_layers, sum, sum_skipped)
     free_buf(ctx->b_ctab);
     free_buf(ctx->b_cwtab);
@@ -2952,8 +2954,9 @@ static int comp_hook(cpol_ctx *ctx, const CompHook *hk)
 // ---- neighbourhood verification (cpol_fractions, k_frac_rows / k_frac_cols / k_frac_score in cpol_frac.inl): the checks
 // (cpol_frac.h) and the launches, shared by the launch sequence and the test hook ----
 enum { FR_SUMS, FR_TOTALS, FR_OBJ_N, FR_OBJ_TABLE, FR_OBJ_LABELS, FR_OBJ_VOLUME, FR_OBJ_SKIPPED, FR_OBJ_FIELD, FR_OBJ_FIELD_CELLS,
-       FR_OBJ_N_PIECES, FR_OBJ_PIECES, FR_OBJ_COVERED, FR_PROB_SUMS, FR_RELIABILITY, FR_MEMBER_SUM, FR_MEMBER_ANY, FR_N };
-static_assert(FR_N == 16, "cpol_ctx::b_fout holds one buffer per array");
+       FR_OBJ_N_PIECES, FR_OBJ_PIECES, FR_OBJ_COVERED, FR_PROB_SUMS, FR_RELIABILITY, FR_MEMBER_SUM, FR_MEMBER_ANY,
+       FR_TRACK_CORR, FR_TRACK_SHIFT, FR_TRACK_N, FR_TRACK_PIECES, FR_TRACK_COVERED, FR_N };
+static_assert(FR_N == 21, "cpol_ctx::b_fout holds one buffer per array");
 // arr[FR_N]: the caller's `sums` and `totals` for the placement plan (cpol_place.h): arrays of the sweep itself, like the
 // composite's `count`; behind them n_objects, table and labels of the object cells (op.on; labels when asked for); last the four
 // arrays of the neighbourhood ensemble probabilities (pl.prob.on; the two maps when asked for)
@@ -2981,6 +2984,14 @@ static void frac_place(const cpol_fractions *f, const FracPlan &pl, const ObjPla
         arr[FR_OBJ_N_PIECES].user = (uintptr_t)mo->n_pieces;  arr[FR_OBJ_N_PIECES].bytes = op.n_pieces_bytes;  arr[FR_OBJ_N_PIECES].produced = true;
         arr[FR_OBJ_PIECES].user = (uintptr_t)mo->pieces;      arr[FR_OBJ_PIECES].bytes = op.pieces_bytes;      arr[FR_OBJ_PIECES].produced = true;
         arr[FR_OBJ_COVERED].user = (uintptr_t)mo->covered;    arr[FR_OBJ_COVERED].bytes = op.covered_bytes;    arr[FR_OBJ_COVERED].produced = true;
+    }
+    if (op.track) {
+        const cpol_objects_track *const tr = (const cpol_objects_track *)o;       // (CPOL_OBJ_TRACK in o->pad_: obj_check)
+        arr[FR_TRACK_CORR].user = (uintptr_t)tr->correlation; arr[FR_TRACK_CORR].bytes = op.track_corr_bytes;      arr[FR_TRACK_CORR].produced = op.track_corr_wanted;
+        arr[FR_TRACK_SHIFT].user = (uintptr_t)tr->shift;      arr[FR_TRACK_SHIFT].bytes = op.track_shift_bytes;    arr[FR_TRACK_SHIFT].produced = true;
+        arr[FR_TRACK_N].user = (uintptr_t)tr->n_pieces;       arr[FR_TRACK_N].bytes = op.track_n_bytes;            arr[FR_TRACK_N].produced = true;
+        arr[FR_TRACK_PIECES].user = (uintptr_t)tr->pieces;    arr[FR_TRACK_PIECES].bytes = op.track_pieces_bytes;  arr[FR_TRACK_PIECES].produced = true;
+        arr[FR_TRACK_COVERED].user = (uintptr_t)tr->covered;  arr[FR_TRACK_COVERED].bytes = op.track_covered_bytes; arr[FR_TRACK_COVERED].produced = true;
     }
     if (!op.sums) return;
     arr[FR_OBJ_VOLUME].user = (uintptr_t)o->volume;            arr[FR_OBJ_VOLUME].bytes = op.volume_bytes;           arr[FR_OBJ_VOLUME].produced = true;
@@ -3050,6 +3061,60 @@ static int obj_launch_match(cpol_ctx *ctx, const ObjArgs &a, const ObjPlan &op, 
     return CPOL_OK;
 }
 
+// the track behind everything else: Ke of every block packed, the correlation and its argmax (or the given shifts copied into
+// `shift`), then the track's own piece arrays through the objects' kernels as in obj_launch_match; a: as there
+static int obj_launch_track(cpol_ctx *ctx, const ObjArgs &a, const ObjPlan &op, void *const T[FR_N], hipStream_t st)
+{
+    char *const scr = (char *)ctx->b_oscr.p;
+    TrackArgs g{};
+    g.L = a.L; g.aux = a.aux; g.max_objects = op.max_objects;
+    g.covered = (unsigned *)T[FR_TRACK_COVERED];
+    g.bits = (unsigned long long *)(scr + op.track_bits_offset);
+    g.shift = (int *)T[FR_TRACK_SHIFT];
+    g.S = op.track_shift; g.side = op.track_side; g.words = op.track_words; g.slabs = (int)op.track_slabs; g.track_maps = op.track_maps;
+    g.p.f = a.f;
+    g.p.L = (unsigned *)(scr + op.track_piece_offset); g.p.aux = g.p.L + op.track_maps * op.cells; g.p.rowcnt = g.p.aux + op.track_maps * op.cells;
+    g.p.n_objects = (unsigned *)T[FR_TRACK_N]; g.p.table = (unsigned *)T[FR_TRACK_PIECES];
+    g.p.n_maps = op.track_maps;
+    g.p.connectivity = op.connectivity; g.p.min_area = 1; g.p.max_objects = op.track_pieces;
+    HIPCHK(hipMemsetAsync(T[FR_TRACK_PIECES], 0, op.track_pieces_bytes, st));
+    HIPCHK(hipMemsetAsync(T[FR_TRACK_COVERED], 0, op.track_covered_bytes, st));
+    const dim3 thr(OBJ_THREADS);
+    hipLaunchKernelGGL(k_track_bits, dim3((unsigned)op.grid_track_bits), thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    if (op.track_corr) {
+        g.corr = op.track_corr_wanted ? (unsigned *)T[FR_TRACK_CORR] : (unsigned *)(scr + op.track_corr_offset);
+        HIPCHK(hipMemsetAsync(g.corr, 0, op.track_corr_bytes, st));
+        hipLaunchKernelGGL(k_track_corr, dim3((unsigned)op.grid_track_corr), thr, 0, st, g);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_track_shift, dim3((unsigned)op.grid_track_shift), thr, 0, st, g);
+        HIPCHK(hipGetLastError());
+    } else {
+        // (checked by obj_check_track before anything was queued; the plan outlives the copy)
+        HIPCHK(hipMemcpyAsync(g.shift, op.shifts_in.data(), op.track_shift_bytes, hipMemcpyHostToDevice, st));
+    }
+    const dim3 rows((unsigned)op.grid_track_rows);
+    hipLaunchKernelGGL(k_track_runs, rows, thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_merge, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_flatten, dim3((unsigned)op.grid_track_cells), thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_area, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_count, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_obj_number, rows, thr, 0, st, g.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_track_attr, rows, thr, 0, st, g);
+    HIPCHK(hipGetLastError());
+    MatchArgs d{};
+    d.p = g.p;
+    hipLaunchKernelGGL(k_match_decode, dim3((unsigned)op.grid_track_decode), thr, 0, st, d);
+    HIPCHK(hipGetLastError());
+    return CPOL_OK;
+}
+
 // the kernels of cpol_obj.inl behind k_frac_score on `st`; fa: the maps as frac_launch resolved them
 static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, const ObjPlan &op, void *const T[FR_N], hipStream_t st)
 {
@@ -3082,7 +3147,11 @@ static int obj_launch(cpol_ctx *ctx, const FracArgs &fa, const FracPlan &pl, con
         const int rc = obj_launch_sums(ctx, a, op, T, st);
         if (rc != CPOL_OK) return rc;
     }
-    return op.match ? obj_launch_match(ctx, a, op, T, st) : CPOL_OK;
+    if (op.match) {
+        const int rc = obj_launch_match(ctx, a, op, T, st);
+        if (rc != CPOL_OK) return rc;
+    }
+    return op.track ? obj_launch_track(ctx, a, op, T, st) : CPOL_OK;
 }
 
 // plane: block 0's plane on the device; obs_on_host: `observed` and `domain` are host arrays (copied to b_fobs on `st` first),

@@ -5,7 +5,10 @@
 // rule), so that a merge bug shows as a wrong label on the host, not as a hang on the device.  The kernels are k_obj_*
 // (cpol_obj.inl); the rule is stated in include/cosmo_pol_amd.h and cosmo_pol_amd/objects.py.  The match (cpol_objects_match)
 // runs the same run, union and find code on the overlap map of two label maps: its checks, sizes and per-cell functions are
-// here too (obj_check_match, obj_match_flag, obj_match_cover; tests/c_host/obj_match_check.cpp).
+// here too (obj_check_match, obj_match_flag, obj_match_cover; tests/c_host/obj_match_check.cpp).  The track
+// (cpol_objects_track) matches every block's label map, shifted, with the next block's: its checks and sizes (obj_check_track), the
+// window, count and key functions of the correlation and the shifted lookup are here as well (obj_track_*;
+// tests/c_host/obj_track_check.cpp).
 //
 // THE LABEL ARRAY.  L[i] of a set cell i is the flat index of a cell of the same object with L[i] <= i; L[i] == i makes i a root;
 // an unset cell holds OBJ_NONE.  It starts as the first cell of the cell's row run (no atomic for horizontal connectivity).  A
@@ -64,11 +67,23 @@ struct ObjPlan {
     long piece_maps = 0, piece_offset = 0, piece_bytes = 0;
     long grid_piece_rows = 0, grid_piece_cells = 0, grid_piece_decode = 0;   // as grid_rows, grid_cells and grid_decode, of the piece maps
     size_t n_pieces_bytes = 0, pieces_bytes = 0, covered_bytes = 0;
+    // the track (cpol_objects_track): the pieces of every block's label map, shifted, against the next block's.  track_maps =
+    // (n_blocks - 1) * n_thr: piece map (p * n_thr + t).  The track scratch behind everything above on an 8-byte boundary: the
+    // packed masks uint64 [n_blocks * n_thr][n_y][track_words], the piece scratch of track_maps maps, then (correlation computed
+    // but not wanted) the counters uint32 [track_maps][side][side]
+    bool track = false, track_corr = false, track_corr_wanted = false;   // track_corr: max_shift >= 0
+    int track_shift = 0, track_side = 0, track_words = 0, track_pieces = 0, n_pairs = 0;
+    long track_maps = 0, track_bits_offset = 0, track_piece_offset = 0, track_piece_bytes = 0, track_corr_offset = 0;
+    long grid_track_bits = 0, grid_track_corr = 0, track_slabs = 0, grid_track_shift = 0;   // workgroups of k_track_bits, _corr, _shift
+    long grid_track_rows = 0, grid_track_cells = 0, grid_track_decode = 0;                  // as grid_piece_*, of the track's piece maps
+    size_t track_corr_bytes = 0, track_shift_bytes = 0, track_n_bytes = 0, track_pieces_bytes = 0, track_covered_bytes = 0;
+    std::vector<int32_t> shifts_in;                   // the given shifts, checked (max_shift == -1)
 };
 
 // the two halves of obj_check: the cells with the exact sums, then the match behind them
 inline const char *obj_check_cells(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl);
 inline const char *obj_check_match(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl);
+inline const char *obj_check_track(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl);
 
 // every refusal of a cpol_objects beside a cpol_fractions whose plan `fp` passed; o == NULL: off (*pl says so).  NULL: accepted
 // and *pl filled; else the reason (CPOL_ERR_ARG).  Touches nothing else.  o->pad_ != 0: *o is the first member of a
@@ -78,7 +93,8 @@ inline const char *obj_check(const cpol_objects *o, const FracPlan &fp, ObjPlan 
     *pl = ObjPlan{};
     if (!o) return nullptr;
     if (const char *why = obj_check_cells(o, fp, pl)) return why;
-    return obj_check_match(o, fp, pl);
+    if (const char *why = obj_check_match(o, fp, pl)) return why;
+    return obj_check_track(o, fp, pl);
 }
 
 inline const char *obj_check_cells(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
@@ -137,11 +153,13 @@ inline const char *obj_check_cells(const cpol_objects *o, const FracPlan &fp, Ob
 
 inline const char *obj_check_match(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
 {
-    if (o->pad_ < 0 || o->pad_ > OBJ_MAX_OBJECTS) return "pad_ (max_pieces of a cpol_objects_match) must lie in 0 ... 65535";
-    if (!o->pad_) return nullptr;
+    // (bit 30, CPOL_OBJ_TRACK, announces a cpol_objects_track around the match: obj_check_track; the low bits stay max_pieces)
+    const int pad = o->pad_ < 0 ? -1 : o->pad_ & ~CPOL_OBJ_TRACK;
+    if (pad < 0 || pad > OBJ_MAX_OBJECTS) return "pad_ (max_pieces of a cpol_objects_match) must lie in 0 ... 65535";
+    if (!pad) return nullptr;
     const cpol_objects_match *const mo = (const cpol_objects_match *)o;
     if (!mo->n_pieces || !mo->pieces || !mo->covered) return "n_pieces, pieces or covered is NULL";
-    pl->match = true; pl->max_pieces = o->pad_;
+    pl->match = true; pl->max_pieces = pad;
     pl->piece_maps = (long)fp.n_blocks * fp.n_thr;
     pl->piece_offset = (pl->scratch_bytes + 7) & ~7L;
     pl->piece_bytes = pl->piece_maps * (2 * pl->cells + fp.n_y) * 4;
@@ -155,6 +173,107 @@ inline const char *obj_check_match(const cpol_objects *o, const FracPlan &fp, Ob
     pl->pieces_bytes = (size_t)pl->piece_maps * pl->max_pieces * OBJ_WORDS * sizeof(uint32_t);
     pl->covered_bytes = (size_t)pl->piece_maps * 2 * pl->max_objects * sizeof(uint32_t);
     return nullptr;
+}
+
+// ---- the track (cpol_objects_track) ----
+constexpr int OBJ_TRACK_MAX_SHIFT = CPOL_TRACK_MAX_SHIFT, OBJ_TRACK_MAX_GIVEN = CPOL_TRACK_MAX_GIVEN;
+constexpr int OBJ_TRACK_ROWS = 16;                    // the earlier rows one workgroup of k_track_corr takes
+
+// every refusal of the track behind a match that passed (or is off); reads behind the cpol_objects_match only with CPOL_OBJ_TRACK
+inline const char *obj_check_track(const cpol_objects *o, const FracPlan &fp, ObjPlan *pl)
+{
+    if (!(o->pad_ & CPOL_OBJ_TRACK)) return nullptr;  // (pad_ >= 0: obj_check_match)
+    const cpol_objects_track *const tr = (const cpol_objects_track *)o;
+    if (fp.n_blocks < 2) return "the track needs at least two blocks";
+    if (tr->max_shift < -1 || tr->max_shift > OBJ_TRACK_MAX_SHIFT) return "max_shift must lie in -1 ... 32";
+    if (tr->max_shift == -1 && !tr->shifts_in) return "max_shift == -1 needs shifts_in";
+    if (tr->max_shift >= 0 && tr->shifts_in) return "shifts_in belongs to max_shift == -1";
+    if (tr->max_pieces < 1 || tr->max_pieces > OBJ_MAX_OBJECTS) return "max_pieces of the track must lie in 1 ... 65535";
+    if (!tr->shift || !tr->n_pieces || !tr->pieces || !tr->covered) return "shift, n_pieces, pieces or covered of the track is NULL";
+    pl->n_pairs = (int)fp.n_blocks - 1;
+    pl->track_maps = (long)pl->n_pairs * fp.n_thr;
+    if (tr->max_shift == -1) {
+        pl->shifts_in.assign(tr->shifts_in, tr->shifts_in + pl->track_maps * 2);
+        for (const int32_t v : pl->shifts_in)
+            if (v < -OBJ_TRACK_MAX_GIVEN || v > OBJ_TRACK_MAX_GIVEN) return "a given shift must lie in -1023 ... 1023";
+    }
+    pl->track_corr = tr->max_shift >= 0; pl->track_corr_wanted = pl->track_corr && tr->correlation != nullptr;
+    pl->track_shift = pl->track_corr ? tr->max_shift : 0; pl->track_side = 2 * pl->track_shift + 1;
+    pl->track_pieces = tr->max_pieces;
+    pl->track_words = (fp.n_x + 63) / 64;
+    pl->track_bits_offset = (pl->scratch_bytes + 7) & ~7L;
+    pl->track_piece_offset = pl->track_bits_offset + (long)fp.n_blocks * fp.n_thr * fp.n_y * pl->track_words * 8;
+    pl->track_piece_bytes = pl->track_maps * (2 * pl->cells + fp.n_y) * 4;
+    pl->track_corr_offset = pl->track_piece_offset + pl->track_piece_bytes;
+    pl->track_corr_bytes = pl->track_corr ? (size_t)pl->track_maps * pl->track_side * pl->track_side * sizeof(uint32_t) : 0;
+    pl->scratch_bytes = pl->track_corr_offset + (pl->track_corr && !pl->track_corr_wanted ? (long)pl->track_corr_bytes : 0);
+    if (pl->scratch_bytes > OBJ_MAX_SCRATCH_BYTES) return "the scratch with the track's masks and piece maps must be at most 1 GiB";
+    const long row_groups = (fp.n_y + OBJ_ROWS - 1) / OBJ_ROWS;
+    pl->grid_track_bits = (long)fp.n_blocks * row_groups;
+    pl->track_slabs = (fp.n_y + OBJ_TRACK_ROWS - 1) / OBJ_TRACK_ROWS;
+    pl->grid_track_corr = pl->track_maps * pl->track_slabs;
+    pl->grid_track_shift = (pl->track_maps + OBJ_ROWS - 1) / OBJ_ROWS;
+    pl->grid_track_rows = (long)pl->n_pairs * row_groups;
+    pl->grid_track_cells = (pl->track_maps * pl->cells + OBJ_THREADS - 1) / OBJ_THREADS;
+    pl->grid_track_decode = (pl->track_maps * pl->track_pieces + OBJ_THREADS - 1) / OBJ_THREADS;
+    if (pl->grid_track_bits >= (1L << 31) || pl->grid_track_corr >= (1L << 31) || pl->grid_track_cells >= (1L << 31) ||
+        pl->grid_track_decode >= (1L << 31)) return "too many workgroups in one call";
+    pl->track_shift_bytes = (size_t)pl->track_maps * 2 * sizeof(int32_t);
+    pl->track_n_bytes = (size_t)pl->track_maps * sizeof(uint32_t);
+    pl->track_pieces_bytes = (size_t)pl->track_maps * pl->track_pieces * OBJ_WORDS * sizeof(uint32_t);
+    pl->track_covered_bytes = (size_t)pl->track_maps * 2 * pl->max_objects * sizeof(uint32_t);
+    pl->track = true;
+    return nullptr;
+}
+
+// The 64 cells of a packed row (`words` uint64, bit l of word w: cell 64 w + l; the bits at or beyond n_x zero) from cell
+// 64 w + dx on, |dx| < 64: the funnel shift of the words w and w + 1 (dx > 0) or w - 1 and w (dx < 0); cells outside the row are
+// unset
+OBJ_HD unsigned long long obj_track_window(const unsigned long long *row, int words, int w, int dx)
+{
+    const unsigned long long mid = row[w];
+    if (dx == 0) return mid;
+    if (dx > 0) return (mid >> dx) | (w + 1 < words ? row[w + 1] << (64 - dx) : 0ull);
+    return (mid << -dx) | (w > 0 ? row[w - 1] >> (64 + dx) : 0ull);
+}
+
+// what the earlier rows [y0, y1) of a pair add to the counter (dy, dx): the cells set in Ke at (y, x) and in Kl at (y + dy, x + dx).
+// A bound fixed before the loops start: (y1 - y0) * words turns
+OBJ_HD unsigned obj_track_count(const unsigned long long *ke, const unsigned long long *kl, int n_y, int words, int y0, int y1, int dy, int dx)
+{
+    unsigned n = 0u;
+    for (int y = y0; y < y1; ++y) {
+        const int yl = y + dy;
+        if (yl < 0 || yl >= n_y) continue;
+        const unsigned long long *const e = ke + (long)y * words, *const l = kl + (long)yl * words;
+        for (int w = 0; w < words; ++w) n += (unsigned)__builtin_popcountll(e[w] & obj_track_window(l, words, w, dx));
+    }
+    return n;
+}
+
+// The argmax of the shift as ONE unsigned 64-bit maximum: the count above the complement of (dy^2 + dx^2, dy + S, dx + S), so
+// that among equal counts the smallest distance, then the smallest dy, then the smallest dx wins.  S <= 32: dy^2 + dx^2 <= 2048
+// (12 bits), dy + S and dx + S <= 64 (7 bits each)
+OBJ_HD unsigned long long obj_track_key(unsigned count, int dy, int dx, int S)
+{
+    const unsigned low = ((unsigned)(dy * dy + dx * dx) << 14) | ((unsigned)(dy + S) << 7) | (unsigned)(dx + S);
+    return ((unsigned long long)count << 32) | (unsigned long long)(0xFFFFFFFFu - low);
+}
+OBJ_HD void obj_track_unkey(unsigned long long key, int S, int *dy, int *dx)
+{
+    const unsigned low = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+    *dy = (int)((low >> 7) & 127u) - S;
+    *dx = (int)(low & 127u) - S;
+}
+
+// the kept number of the earlier block's object at cell (y, x) of the LATER frame under the shift (dy, dx): the lookup at
+// (y - dy, x - dx), 0 outside the grid
+OBJ_HD unsigned obj_track_number(const unsigned *L, const unsigned *aux, int n_x, int n_y, int y, int x, int dy, int dx)
+{
+    const int ys = y - dy, xs = x - dx;
+    if (ys < 0 || ys >= n_y || xs < 0 || xs >= n_x) return 0u;
+    const unsigned root = L[ys * n_x + xs];               // (obj_number_of, below)
+    return root == OBJ_NONE ? 0u : aux[root];
 }
 
 // ---- the runs of a chunk of 64 cells from the ballot `m` of its flags (bit l: cell x0 + l is set) ----

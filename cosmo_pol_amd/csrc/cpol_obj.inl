@@ -32,6 +32,8 @@
 //                  f.n_y, f.n_thr, f.cells, L, aux, rowcnt, table, n_objects, n_maps, connectivity, min_area and max_objects;
 //   k_match_attr   per run segment the sums and the box as in k_obj_attr; the piece's root lane stores `forecast` and `observed`;
 //   k_match_decode a thread per piece row: x0 out of its complement, y0 from the first cell.
+// With the track (cpol_objects_track; TRACK of the header) behind all of them, on piece arrays of its own: k_track_bits,
+// k_track_corr, k_track_shift, k_track_runs, the five kernels above unchanged, k_track_attr, k_match_decode (at the end of this file).
 
 struct ObjArgs {
     FracArgs f;                     // the maps: plane, obs, domain, the grid, the rounded thresholds
@@ -432,6 +434,150 @@ __global__ __launch_bounds__(OBJ_THREADS) void k_match_decode(const MatchArgs g)
     unsigned *const row = a.table + i * OBJ_WORDS;
     row[OBJ_X0] = (unsigned)(a.f.n_x - 1) - row[OBJ_X0];
     row[OBJ_Y0] = row[OBJ_FIRST] / (unsigned)a.f.n_x;
+}
+
+// ---- the track (cpol_objects_track; TRACK of the header): block p against block p + 1, the earlier one shifted.  Behind
+// everything else; the piece arrays are the track's own (a third ObjArgs: n_maps = (n_blocks - 1) * n_thr, on a grid of
+// n_blocks - 1 sources), so the match against the observed map beside it changes nothing.
+//   k_track_bits   a wavefront per (block, row): Ke of every threshold from the (root, number) lookup, packed with the ballot;
+//   k_track_corr   a workgroup per (pair, threshold, slab of OBJ_TRACK_ROWS earlier rows), a thread per counter (dy, dx) in turn:
+//                  popcounts of earlier words against funnel-shifted later words in a register, ONE integer atomic per counter;
+//   k_track_shift  a wavefront per (pair, threshold): the argmax as one 64-bit maximum (obj_track_key);
+//   k_track_runs   k_match_runs with the earlier lookup at cell - shift, the shift read from device memory;
+//   k_track_attr   k_match_attr likewise; then k_match_decode as it is.
+struct TrackArgs {
+    ObjArgs p;                      // the track's pieces, as MatchArgs::p
+    const unsigned *L, *aux;        // the objects' arrays after k_obj_number
+    unsigned *covered;              // [n_pairs * n_thr][2][max_objects]: zero before k_track_runs
+    int max_objects;
+    unsigned long long *bits;       // [n_blocks * n_thr][n_y][words]
+    unsigned *corr;                 // [n_pairs * n_thr][side][side]: zero before k_track_corr (NULL: the shifts are given)
+    int *shift;                     // [n_pairs * n_thr][2]
+    int S, side, words, slabs;
+    long track_maps;
+};
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_track_bits(const TrackArgs g)
+{
+    const ObjArgs &a = g.p;
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;                    // (the grid has n_blocks sources)
+    const int n_x = a.f.n_x;
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+        for (int t = 0; t < a.f.n_thr; ++t) {
+            const long map = src * a.f.n_thr + t, fb = map * a.f.cells;
+            const unsigned long long m = __ballot(in && obj_number_of(g.L + fb, g.aux + fb, cell) != 0u);
+            if (lane == 0) g.bits[(map * a.f.n_y + y) * g.words + (x0 >> 6)] = m;
+        }
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_track_corr(const TrackArgs g)
+{
+    const ObjArgs &a = g.p;
+    const long map = (long)blockIdx.x / g.slabs;          // pair p, threshold t: map p * n_thr + t
+    const int y0 = (int)((long)blockIdx.x % g.slabs) * OBJ_TRACK_ROWS;
+    const int y1 = y0 + OBJ_TRACK_ROWS < a.f.n_y ? y0 + OBJ_TRACK_ROWS : a.f.n_y;
+    const long per = (long)a.f.n_y * g.words;
+    const unsigned long long *const ke = g.bits + map * per, *const kl = ke + a.f.n_thr * per;   // (block p + 1, the same threshold)
+    unsigned *const out = g.corr + map * g.side * g.side;
+    for (int c = (int)threadIdx.x; c < g.side * g.side; c += OBJ_THREADS) {
+        const unsigned n = obj_track_count(ke, kl, a.f.n_y, g.words, y0, y1, c / g.side - g.S, c % g.side - g.S);
+        if (n) atomicAdd(out + c, n);
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_track_shift(const TrackArgs g)
+{
+    const int lane = threadIdx.x & 63;
+    const long map = (long)blockIdx.x * OBJ_ROWS + (long)(threadIdx.x >> 6);
+    if (map >= g.track_maps) return;                      // (whole wavefronts leave)
+    const unsigned *const in = g.corr + map * g.side * g.side;
+    unsigned long long best = 0ull;                       // (below every key: a key's low word is never 0)
+    for (int c = lane; c < g.side * g.side; c += 64) {
+        const unsigned long long key = obj_track_key(in[c], c / g.side - g.S, c % g.side - g.S, g.S);
+        if (key > best) best = key;
+    }
+    for (int dlt = 32; dlt > 0; dlt >>= 1) {
+        const unsigned long long other = __shfl_xor(best, dlt);
+        if (other > best) best = other;
+    }
+    if (lane == 0) {
+        int dy, dx;
+        obj_track_unkey(best, g.S, &dy, &dx);
+        g.shift[2 * map] = dy;
+        g.shift[2 * map + 1] = dx;
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_track_runs(const TrackArgs g)
+{
+    const ObjArgs &a = g.p;
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;                    // (the grid has n_blocks - 1 sources: src is a pair)
+    const int n_x = a.f.n_x;
+    int carry[FRAC_MAX_THR] = {-1, -1, -1, -1};
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+#pragma unroll
+        for (int t = 0; t < FRAC_MAX_THR; ++t) {
+            if (t >= a.f.n_thr) break;
+            const long map = src * a.f.n_thr + t;
+            const long eb = map * a.f.cells, lb = eb + (long)a.f.n_thr * a.f.cells;      // the earlier block's map, the later one's
+            const int dy = g.shift[2 * map], dx = g.shift[2 * map + 1];
+            const unsigned ne = in ? obj_track_number(g.L + eb, g.aux + eb, n_x, a.f.n_y, y, x, dy, dx) : 0u;
+            const unsigned nl = in ? obj_number_of(g.L + lb, g.aux + lb, cell) : 0u;
+            const bool set = ne != 0u && nl != 0u;
+            const unsigned long long m = __ballot(set);
+            unsigned first = OBJ_NONE;
+            if (set) first = (unsigned)(y * n_x + (obj_run_open(m, lane) && carry[t] >= 0 ? carry[t] : x0 + obj_run_first(m, lane)));
+            if (in) a.L[eb + cell] = first;
+            // (a run of the overlap lies inside one run of each map, shifted or not: ne and nl are constant over it)
+            if (set && (lane == 0 || !((m >> (lane - 1)) & 1ull)))
+                obj_match_cover(g.covered + map * 2 * g.max_objects, g.max_objects, ne, nl, (unsigned)obj_run_len(m, lane));
+            carry[t] = obj_carry(m, x0, carry[t]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(OBJ_THREADS) void k_track_attr(const TrackArgs g)
+{
+    const ObjArgs &a = g.p;
+    const int lane = threadIdx.x & 63;
+    long src; int y;
+    if (!obj_row(a, &src, &y)) return;
+    const int n_x = a.f.n_x;
+    for (int x0 = 0; x0 < n_x; x0 += 64) {
+        const int x = x0 + lane;
+        const bool in = x < n_x;
+        const unsigned cell = (unsigned)(y * n_x + x);
+        for (int t = 0; t < a.f.n_thr; ++t) {
+            OBJ_CHUNK(t);
+            const unsigned number = set ? a.aux[base + root] : 0u;
+            if (!set || number == 0u || number > (unsigned)a.max_objects) continue;
+            const long map = src * a.f.n_thr + t;
+            unsigned *const row = a.table + (map * a.max_objects + (number - 1u)) * OBJ_WORDS;
+            if (root == cell) {                               // (one lane per piece: plain stores)
+                const long lb = base + (long)a.f.n_thr * a.f.cells;
+                row[OBJ_PEAK_CELL] = obj_track_number(g.L + base, g.aux + base, n_x, a.f.n_y, y, x, g.shift[2 * map], g.shift[2 * map + 1]);
+                row[OBJ_PEAK_BITS] = obj_number_of(g.L + lb, g.aux + lb, cell);
+            }
+            if (lane != 0 && ((m >> (lane - 1)) & 1ull)) continue;
+            const unsigned n = (unsigned)obj_run_len(m, lane), ux = (unsigned)x, uy = (unsigned)y;
+            atomicAdd(row + OBJ_SUM_X, n * ux + n * (n - 1u) / 2u);
+            atomicAdd(row + OBJ_SUM_Y, n * uy);
+            atomicMax(row + OBJ_X0, (unsigned)(n_x - 1) - ux);                      // (k_match_decode turns it back)
+            atomicMax(row + OBJ_X1, ux + n - 1u);
+            atomicMax(row + OBJ_Y1, uy);
+        }
+    }
 }
 
 #undef OBJ_CHUNK

@@ -62,7 +62,30 @@ MATCH (Objects(match=True); `pairs`, `match` and `contingency` read it).  It nee
   The rule   `pieces_of_map`, built on `cells_of_map`.  Every number is a count, an integer sum, an integer extreme or a
              comparison: the device result equals it exactly.
   Limits     the piece scratch, n_blocks * n_thr * (2 * n_y * n_x + n_y) * 4 bytes, counts into the scratch limit.
-  Not built  tracking across calls; block-against-block matching; cells of layered composites."""
+
+TRACK (Objects(track=True, max_shift=S | shifts=...); `links`, `tracks` and `motion` read it).  The blocks of the call are scan
+times: block p is followed into block p + 1.  It needs neither `labels`, `sums` nor `match`; none of them changes.
+  Pairs      a call has B = n_blocks >= 2 blocks and P = B - 1 pairs; pair p is (earlier = block p, later = block p + 1).
+  Per pair and threshold t: le, ll = the label maps of the two blocks exactly as 'labels' defines them (kept objects only,
+             min_area applied, complete beyond max_objects); Ke = le > 0, Kl = ll > 0.
+  Correlation for |dy|, |dx| <= S = max_shift (0 ... TRACK_MAX_SHIFT = 32): C[dy + S, dx + S] = #{(y, x): Ke[y, x] and
+             Kl[y + dy, x + dx]}, both cells inside the grid; uint32 (a count is below 2^20).  S may exceed the grid's sides:
+             such offsets count 0.  `correlation_of_pair`.
+  Shift      the (dy, dx) with the largest C; ties go to the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx.
+             An all-zero table gives (0, 0).  `shift_of`.
+  Given      instead of max_shift the caller may hand `shifts`: int32, broadcastable to [P, n_thr, 2] (dy, dx), |dy|, |dx| <=
+             TRACK_MAX_GIVEN = 1023 (a model-wind guess); no correlation is then computed or delivered.  The shape is checked at
+             the call, where P is known.
+  Overlap    le'[y, x] = le[y - dy, x - dx] inside the grid, 0 outside (`shift_labels`).  The pieces, n_pieces and covered of the
+             pair are pieces_of_map(le', ll, connectivity, max_track_pieces, max_objects), unchanged, in the later block's frame:
+             the word `forecast` is the object's number in the earlier block, `observed` its number in the later block;
+             covered[0] counts cells of the earlier objects, covered[1] cells of the later ones.  The invariants of MATCH hold.
+  Outputs    res['track'] = {'correlation': uint32 [P, n_thr, 2S + 1, 2S + 1] (None with given shifts), 'shift': int32 [P, n_thr,
+             2], 'n_pieces': uint32 [P, n_thr] (the true count), 'pieces': uint32 [P, n_thr, max_track_pieces, WORDS] (rows at or
+             beyond n_pieces zero), 'covered': uint32 [P, n_thr, 2, max_objects]}.  `track_of_maps`.
+  Limits     the track scratch, behind everything else on an 8-byte boundary: the packed masks, n_blocks * n_thr * n_y *
+             ceil(n_x / 64) * 8 bytes, and P * n_thr piece maps of (2 * n_y * n_x + n_y) * 4 bytes, counts into the scratch limit.
+  Not built  tracking across calls; tracks of layered composites; per-object (local) shifts; a process group."""
 import numpy as np
 
 from . import neighbourhood as NB
@@ -70,6 +93,7 @@ from . import neighbourhood as NB
 WORDS = 10
 MAX_OBJECTS = 65535
 MAX_SCRATCH_BYTES = 1 << 30
+TRACK_MAX_SHIFT, TRACK_MAX_GIVEN = 32, 1023                # CPOL_TRACK_MAX_SHIFT, CPOL_TRACK_MAX_GIVEN
 MAX_TABLE = 1024                                          # breakpoints of a weight table: the composite's MAX_TABLE
 SUM_BINS = 16 + 32 + 32                                   # int64 bins of one accumulator row (cpol_obj.h): volume, moment_x, moment_y
 FIRST, AREA, SUM_X, SUM_Y, X0, X1, Y0, Y1, PEAK_CELL, PEAK_BITS = range(WORDS)
@@ -83,11 +107,14 @@ class Objects(object):
     `connectivity` 4 or 8, those below `min_area` cells dropped, up to `max_objects` (1 ... 65535) table rows per source and
     threshold, with the label maps when `labels` and the exact sums when `sums`, under `weight` = (table_v, table_f) or None
     (w = m), and with the overlap pieces of every block against the observed map when `match`, up to `max_pieces` (1 ... 65535,
-    default max_objects) rows per block and threshold.  ValueError for what the library refuses.  The Fractions is `fractions`;
-    the properties the scored entry points read of a spec are its own."""
+    default max_objects) rows per block and threshold; and with the track of every block's objects into the next block when
+    `track` (TRACK above): exactly one of `max_shift` (0 ... 32: the displacement is found) and `shifts` (int32, broadcastable to
+    [n_blocks - 1, n_thr, 2]: it is given), up to `max_track_pieces` (1 ... 65535, default max_objects) rows per pair and
+    threshold.  ValueError for what the library refuses.  The Fractions is `fractions`; the properties the scored entry points
+    read of a spec are its own."""
 
     def __init__(self, fractions, connectivity=4, min_area=1, max_objects=1024, labels=True, sums=False, weight=None, match=False,
-                 max_pieces=None):
+                 max_pieces=None, track=False, max_shift=None, shifts=None, max_track_pieces=None):
         if not isinstance(fractions, NB.Fractions):
             raise ValueError('fractions: a cosmo_pol_amd.neighbourhood.Fractions, got %r' % (fractions,))
         for name, v in (('connectivity', connectivity), ('min_area', min_area), ('max_objects', max_objects)):
@@ -116,6 +143,28 @@ class Objects(object):
             if not 1 <= max_pieces <= MAX_OBJECTS:
                 raise ValueError('max_pieces must lie in 1 ... %d, got %r' % (MAX_OBJECTS, max_pieces))
             self.max_pieces = int(max_pieces)
+        self.track, self.max_shift, self.shifts, self.max_track_pieces = bool(track), None, None, None
+        if not self.track:
+            for name, v in (('max_shift', max_shift), ('shifts', shifts), ('max_track_pieces', max_track_pieces)):
+                if v is not None:
+                    raise ValueError('%s: belongs to track=True' % name)
+        else:
+            if (max_shift is None) == (shifts is None):
+                raise ValueError('track=True needs exactly one of max_shift and shifts')
+            if max_shift is not None:
+                if isinstance(max_shift, (bool, np.bool_)) or not isinstance(max_shift, (int, np.integer)):
+                    raise ValueError('max_shift: an integer, got %r' % (max_shift,))
+                if not 0 <= max_shift <= TRACK_MAX_SHIFT:
+                    raise ValueError('max_shift must lie in 0 ... %d, got %r' % (TRACK_MAX_SHIFT, max_shift))
+                self.max_shift = int(max_shift)
+            else:
+                self.shifts = check_shifts(shifts)
+            max_track_pieces = self.max_objects if max_track_pieces is None else max_track_pieces
+            if isinstance(max_track_pieces, (bool, np.bool_)) or not isinstance(max_track_pieces, (int, np.integer)):
+                raise ValueError('max_track_pieces: an integer, got %r' % (max_track_pieces,))
+            if not 1 <= max_track_pieces <= MAX_OBJECTS:
+                raise ValueError('max_track_pieces must lie in 1 ... %d, got %r' % (MAX_OBJECTS, max_track_pieces))
+            self.max_track_pieces = int(max_track_pieces)
 
     composite = property(lambda self: self.fractions.composite)
     thresholds = property(lambda self: self.fractions.thresholds)
@@ -129,6 +178,8 @@ class Objects(object):
             key += (True, None if self.weight is None else (self.weight[0].tobytes(), self.weight[1].tobytes()))
         if self.match:
             key += ('match', self.max_pieces)
+        if self.track:
+            key += ('track', self.max_shift, None if self.shifts is None else (self.shifts.shape, self.shifts.tobytes()), self.max_track_pieces)
         return key
 
     def __eq__(self, other):
@@ -143,6 +194,9 @@ class Objects(object):
             tail = ', sums=True' + ('' if self.weight is None else ', weight=<%d breakpoints>' % len(self.weight[0]))
         if self.match:
             tail += ', match=True, max_pieces=%d' % self.max_pieces
+        if self.track:
+            tail += ', track=True, %s, max_track_pieces=%d' % (
+                'max_shift=%d' % self.max_shift if self.shifts is None else 'shifts=<%s>' % 'x'.join(map(str, self.shifts.shape)), self.max_track_pieces)
         return 'Objects(%r, connectivity=%d, min_area=%d, max_objects=%d, labels=%r%s)' % (
             self.fractions, self.connectivity, self.min_area, self.max_objects, self.labels, tail)
 
@@ -166,10 +220,37 @@ def check_weight(weight):
     return tv, tf
 
 
+def check_shifts(shifts):
+    """int32 [..., 2] of given shifts as the library takes them (at most three axes, the last one (dy, dx)); ValueError else.
+    That they broadcast to [n_blocks - 1, n_thr, 2] is checked at the call (`shifts_of_call`)."""
+    try:
+        a = np.asarray(shifts)
+    except (TypeError, ValueError):
+        raise ValueError('shifts: an integer array [..., 2], got %r' % (shifts,))
+    if a.dtype.kind not in 'iu' or a.ndim < 1 or a.ndim > 3 or a.shape[-1] != 2:
+        raise ValueError('shifts: integers (dy, dx), broadcastable to [n_blocks - 1, n_thr, 2], got %s %r' % (a.dtype, a.shape))
+    if a.size and (a.min() < -TRACK_MAX_GIVEN or a.max() > TRACK_MAX_GIVEN):
+        raise ValueError('shifts: |dy| and |dx| at most %d' % TRACK_MAX_GIVEN)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def shifts_of_call(spec, n_blocks):
+    """int32 [n_blocks - 1, n_thr, 2], contiguous: the given shifts of a call of `n_blocks` blocks; ValueError when the spec's do not
+    broadcast to it, and for a call of one block."""
+    if n_blocks < 2:
+        raise ValueError('track: the call yields %d block; tracking needs at least two (rays_per_block, or a series of times)' % n_blocks)
+    shape = (n_blocks - 1, len(spec.thresholds), 2)
+    try:
+        return np.ascontiguousarray(np.broadcast_to(spec.shifts, shape), dtype=np.int32)
+    except ValueError:
+        raise ValueError('shifts: %r does not broadcast to [n_blocks - 1, n_thr, 2] = %r' % (spec.shifts.shape, shape))
+
+
 def scratch_bytes(spec, blocks):
     """The bytes of the scratch of `blocks` blocks and the observation (cpol_obj.h): the labelling's and, with the exact sums,
     behind it on an 8-byte boundary the accumulators and the weight table, and with the match behind those on an 8-byte boundary
-    the piece scratch of `blocks` blocks."""
+    the piece scratch of `blocks` blocks, and with the track behind those on an 8-byte boundary the packed masks of `blocks`
+    blocks and the piece scratch of `blocks` - 1 pairs."""
     maps = (int(blocks) + 1) * len(spec.thresholds)
     n = maps * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
     if getattr(spec, 'sums', False):
@@ -177,6 +258,9 @@ def scratch_bytes(spec, blocks):
         n = (n + 7) // 8 * 8 + (maps * spec.max_objects + int(blocks) + 1) * SUM_BINS * 8 + nw * 8 + (nw * 4 + 7) // 8 * 8
     if getattr(spec, 'match', False):
         n = (n + 7) // 8 * 8 + int(blocks) * len(spec.thresholds) * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
+    if getattr(spec, 'track', False):
+        n = (n + 7) // 8 * 8 + int(blocks) * len(spec.thresholds) * spec.n_y * ((spec.n_x + 63) // 64) * 8
+        n += (int(blocks) - 1) * len(spec.thresholds) * (2 * spec.n_y * spec.n_x + spec.n_y) * 4
     return n
 
 
@@ -429,7 +513,93 @@ def pieces_of_map(lf, lo, connectivity, max_pieces, max_objects):
     return n, pieces, covered
 
 
-def result(spec, n_objects, table, labels=None, sums=None, match=None):
+# ---------------------------------------------------------------------------------------------------- the track
+def correlation_of_pair(le, ll, S):
+    """uint32 [2S + 1, 2S + 1]: C[dy + S, dx + S] = the cells (y, x) with le[y, x] > 0 and ll[y + dy, x + dx] > 0, both inside the
+    grid, for |dy|, |dx| <= S (TRACK, Correlation).  le, ll: label maps (or bool maps) of one shape."""
+    ke, kl = np.asarray(le) > 0, np.asarray(ll) > 0
+    S = int(S)
+    if ke.ndim != 2 or ke.shape != kl.shape or S < 0:
+        raise ValueError('correlation_of_pair: two maps of one shape and S >= 0')
+    n_y, n_x = ke.shape
+    C = np.zeros((2 * S + 1, 2 * S + 1), dtype=_U32)
+    for dy in range(-min(S, n_y - 1), min(S, n_y - 1) + 1):
+        e_rows, l_rows = ke[max(0, -dy):n_y - max(0, dy)], kl[max(0, dy):n_y - max(0, -dy)]
+        for dx in range(-min(S, n_x - 1), min(S, n_x - 1) + 1):
+            C[dy + S, dx + S] = np.count_nonzero(e_rows[:, max(0, -dx):n_x - max(0, dx)] & l_rows[:, max(0, dx):n_x - max(0, -dx)])
+    return C
+
+
+def shift_of(C):
+    """(dy, dx): the offset with the largest count of a correlation table [2S + 1, 2S + 1]; ties go to the smallest dy^2 + dx^2,
+    then the smallest dy, then the smallest dx (TRACK, Shift).  An all-zero table gives (0, 0)."""
+    C = np.asarray(C)
+    if C.ndim != 2 or C.shape[0] != C.shape[1] or C.shape[0] % 2 != 1:
+        raise ValueError('shift_of: a table [2S + 1, 2S + 1], got %r' % (C.shape,))
+    S = C.shape[0] // 2
+    dy, dx = [q.reshape(-1) for q in np.meshgrid(np.arange(-S, S + 1), np.arange(-S, S + 1), indexing='ij')]
+    best = np.lexsort((dx, dy, dy * dy + dx * dx, -C.reshape(-1).astype(_I64)))[0]      # (the last key is the first criterion)
+    return int(dy[best]), int(dx[best])
+
+
+def shift_labels(le, dy, dx):
+    """le'[y, x] = le[y - dy, x - dx] inside the grid, 0 outside (TRACK, Overlap): the map moved by (dy, dx)."""
+    le = np.asarray(le)
+    n_y, n_x = le.shape
+    out = np.zeros_like(le)
+    dy, dx = int(dy), int(dx)
+    if abs(dy) < n_y and abs(dx) < n_x:
+        out[max(0, dy):n_y - max(0, -dy), max(0, dx):n_x - max(0, -dx)] = le[max(0, -dy):n_y - max(0, dy), max(0, -dx):n_x - max(0, dx)]
+    return out
+
+
+def track_of_labels(spec, labels):
+    """The track of the label maps int32 [n_blocks, n_thr, n_y, n_x] of a call's blocks: (correlation or None, shift, n_pieces,
+    pieces, covered) as TRACK's Outputs describe them."""
+    n_blocks, n_thr = labels.shape[:2]
+    P = n_blocks - 1
+    given = None if spec.shifts is None else shifts_of_call(spec, n_blocks)
+    if P < 1:
+        raise ValueError('track: %d block; tracking needs at least two' % n_blocks)
+    S = spec.max_shift
+    corr = None if given is not None else np.zeros((P, n_thr, 2 * S + 1, 2 * S + 1), dtype=_U32)
+    shift = np.zeros((P, n_thr, 2), dtype=np.int32)
+    n = np.zeros((P, n_thr), dtype=_U32)
+    pieces = np.zeros((P, n_thr, spec.max_track_pieces, WORDS), dtype=_U32)
+    covered = np.zeros((P, n_thr, 2, spec.max_objects), dtype=_U32)
+    for p in range(P):
+        for t in range(n_thr):
+            le, ll = labels[p, t], labels[p + 1, t]
+            if given is None:
+                corr[p, t] = correlation_of_pair(le, ll, S)
+                shift[p, t] = shift_of(corr[p, t])
+            else:
+                shift[p, t] = given[p, t]
+            n[p, t], pieces[p, t], covered[p, t] = pieces_of_map(shift_labels(le, *shift[p, t]), ll, spec.connectivity,
+                                                                 spec.max_track_pieces, spec.max_objects)
+    return corr, shift, n, pieces, covered
+
+
+def track_result(arrays):
+    """The five arrays of the track named: res['track']."""
+    return dict(zip(('correlation', 'shift', 'n_pieces', 'pieces', 'covered'), arrays))
+
+
+def track_of_maps(spec, plane_maps, domain=None):
+    """The rule of the track in NumPy: res['track'] of the scored plane's blocks float32 [n_blocks, n_y, n_x] under `spec` (an
+    Objects with track=True) -- exactly what the device returns.  The observed map plays no part."""
+    if not getattr(spec, 'track', False):
+        raise ValueError('track_of_maps: the spec has no track (Objects(track=True))')
+    m = np.asarray(plane_maps)
+    F = binary_maps(spec.fractions, m, np.zeros((spec.n_y, spec.n_x), dtype=np.float32), domain)[0]
+    labels = np.zeros(F.shape, dtype=np.int32)
+    for b in range(F.shape[0]):
+        for t in range(F.shape[1]):
+            labels[b, t] = cells_of_map(F[b, t], np.zeros(F.shape[2:], dtype=np.float32), spec.connectivity, spec.min_area, 1)[2]
+    return track_result(track_of_labels(spec, labels))
+
+
+def result(spec, n_objects, table, labels=None, sums=None, match=None, track=None):
     """The output arrays named.  n_objects [n_blocks + 1, n_thr], table [n_blocks + 1, n_thr, max_objects, WORDS], labels
     [n_blocks + 1, n_thr, n_y, n_x] or None -> {'n_objects': uint32 [n_blocks, n_thr], 'first' | 'area' | 'sum_x' | 'sum_y' |
     'peak_cell': uint32 [n_blocks, n_thr, max_objects], 'bbox': uint32 [..., 4] (x0, x1, y0, y1), 'peak': float32 [...],
@@ -441,7 +611,8 @@ def result(spec, n_objects, table, labels=None, sums=None, match=None):
     'grid' (n_y, n_x) for `sal`.  match: None or the three arrays of the match (n_pieces [n_blocks, n_thr], pieces [n_blocks,
     n_thr, max_pieces, WORDS], covered [n_blocks, n_thr, 2, max_objects]): 'pieces': {'n_pieces': uint32 [n_blocks, n_thr],
     'first' | 'area' | 'sum_x' | 'sum_y' | 'forecast' | 'observed': uint32 [n_blocks, n_thr, max_pieces], 'bbox': [..., 4]},
-    'covered' and 'covered_observed': uint32 [n_blocks, n_thr, max_objects]."""
+    'covered' and 'covered_observed': uint32 [n_blocks, n_thr, max_objects].  track: None or the five arrays of the track
+    (correlation or None, shift, n_pieces, pieces, covered: TRACK, Outputs): 'track', under those names."""
     def named(n, tb, lb, sm=None):
         out = {'n_objects': n, 'first': tb[..., FIRST], 'area': tb[..., AREA], 'sum_x': tb[..., SUM_X], 'sum_y': tb[..., SUM_Y],
                'bbox': tb[..., X0:Y1 + 1], 'peak': tb[..., PEAK_BITS].view(np.float32),     # (views all: a pinned call fills them later)
@@ -464,6 +635,8 @@ def result(spec, n_objects, table, labels=None, sums=None, match=None):
         out['pieces'] = {'n_pieces': n_pieces, 'first': pc[..., FIRST], 'area': pc[..., AREA], 'sum_x': pc[..., SUM_X],
                          'sum_y': pc[..., SUM_Y], 'bbox': pc[..., X0:Y1 + 1], 'forecast': pc[..., FORECAST], 'observed': pc[..., OBSERVED]}
         out['covered'], out['covered_observed'] = covered[..., 0, :], covered[..., 1, :]
+    if track is not None:
+        out['track'] = track_result(track)
     return out
 
 
@@ -491,7 +664,7 @@ def cells(spec, plane_maps, observed, domain=None):
     `n_x`); plane_maps: float32 [n_blocks, n_y, n_x] (or [n_y, n_x]: one block), the scored plane as a composite's finish
     returns it; observed, domain: see neighbourhood.check_maps.  Returns what `result` describes -- exactly what the device
     returns ('labels' only with spec.labels; the keys of the exact sums only with spec.sums, those of the match only with
-    spec.match)."""
+    spec.match, 'track' only with spec.track)."""
     F, O, m, o = binary_maps(spec.fractions, plane_maps, observed, domain)
     n_blocks, n_thr = F.shape[:2]
     with_sums = getattr(spec, 'sums', False)
@@ -521,7 +694,8 @@ def cells(spec, plane_maps, observed, domain=None):
             for t in range(n_thr):
                 match[0][b, t], match[1][b, t], match[2][b, t] = pieces_of_map(labels[b, t], labels[n_blocks, t], spec.connectivity,
                                                                                 spec.max_pieces, spec.max_objects)
-    return result(spec, n, table, labels if spec.labels else None, (volume, skipped, field, field_cells) if with_sums else None, match)
+    track = track_of_labels(spec, labels[:-1]) if getattr(spec, 'track', False) else None
+    return result(spec, n, table, labels if spec.labels else None, (volume, skipped, field, field_cells) if with_sums else None, match, track)
 
 
 def centroids(res):
@@ -675,6 +849,133 @@ def contingency(res, threshold=0, min_cover=0.0):
     return out
 
 
+def _track_side(res, threshold, who):
+    if 'track' not in res:
+        raise ValueError('%s: the result has no track (Objects(track=True))' % who)
+    t = int(threshold)
+    if not 0 <= t < len(res['thresholds']):
+        raise ValueError('%s: threshold index outside 0 ... %d' % (who, len(res['thresholds']) - 1))
+    return t
+
+
+def links(res, pair, threshold=0, min_cover=0.0):
+    """The distinct (earlier, later) object pairs of pair `pair` (block `pair` against block `pair` + 1) at threshold index
+    `threshold` from a result with the track, sorted ascending: {'earlier', 'later', 'area', 'sum_x', 'sum_y', 'pieces': int64
+    [n_links]} -- `pairs` applied to the track's pieces: the overlap area per link, after the shift, in the later block's frame.
+    With `min_cover` > 0 the links whose area is below min_cover * min(area of the earlier object, area of the later one) are
+    left out; the areas come from the table rows, so a link that names an object beyond max_objects is then a ValueError.
+    ValueError when n_pieces > max_track_pieces: a partial fold is not returned."""
+    t = _track_side(res, threshold, 'links')
+    tr = res['track']
+    p = int(pair)
+    if not 0 <= p < np.asarray(tr['n_pieces']).shape[0]:
+        raise ValueError('links: pair outside 0 ... %d' % (np.asarray(tr['n_pieces']).shape[0] - 1))
+    min_cover = float(min_cover)
+    if not 0.0 <= min_cover <= 1.0:
+        raise ValueError('links: min_cover must lie in [0, 1]')
+    pc = np.asarray(tr['pieces'])
+    n, rows = int(np.asarray(tr['n_pieces'])[p, t]), pc.shape[-2]
+    if n > rows:
+        raise ValueError('links: %d pieces, %d rows (max_track_pieces): a partial fold is not returned' % (n, rows))
+    named = {'n_pieces': tr['n_pieces'], 'area': pc[..., AREA], 'sum_x': pc[..., SUM_X], 'sum_y': pc[..., SUM_Y],
+             'forecast': pc[..., FORECAST], 'observed': pc[..., OBSERVED]}
+    f = pairs({'pieces': named, 'thresholds': res['thresholds']}, p, t)
+    out = {'earlier': f['forecast'], 'later': f['observed'], 'area': f['area'], 'sum_x': f['sum_x'], 'sum_y': f['sum_y'], 'pieces': f['pieces']}
+    if min_cover > 0.0 and out['area'].size:
+        area = np.asarray(res['area'])
+        if out['earlier'].max() > area.shape[-1] or out['later'].max() > area.shape[-1]:
+            raise ValueError('links: min_cover needs the areas, and a link names an object beyond max_objects')
+        least = np.minimum(area[p, t][out['earlier'] - 1], area[p + 1, t][out['later'] - 1]).astype(np.float64)
+        keep = out['area'] >= min_cover * least
+        out = {k: v[keep] for k, v in out.items()}
+    return out
+
+
+def tracks(res, threshold=0, min_cover=0.0):
+    """Track ids of every object of every block at threshold index `threshold` from a result with the track.  THE RULE, statement by
+    statement (blocks b = 0 ... B - 1, pairs p = 0 ... B - 2, objects by their numbers; an overlap is the area of a link of
+    `links(res, p, threshold, min_cover)`, so overlaps below min_cover * min(area, area) do not count):
+      1. The objects 1 ... n of block 0 open the tracks 1 ... n, in object order; birth 0, parent 0.
+      2. For pair p, the predecessor of a later object is the earlier object with the largest overlap with it; ties go to the
+         smallest number.  A later object without an overlap has none.
+      3. Of the later objects that share a predecessor, the one with the largest overlap with it (ties: the smallest number)
+         INHERITS the predecessor's track.
+      4. The other later objects, in ascending order of their numbers, open new tracks with birth p + 1: those with a predecessor
+         with `parent` = the predecessor's track (a split), those without with parent 0.
+      5. An earlier object none of whose overlaps inherits ends its track there.  If it overlapped anything, `merged_into` of its
+         track is the track of the later object it overlaps most (ties: the smallest number): a merge.
+      6. `death` of a track is the last block that holds an object of it (B - 1 for the tracks that reach the end of the call).
+    Returns {'track_id': [int64 [n_objects of block b] per block], 'inherited': [int64 [n, 2] (earlier, later) per pair: the
+    links of statement 3], 'birth', 'death', 'parent', 'merged_into': int64 [n_tracks], entry k - 1 of track k, 0 = none}.
+    ValueError when a needed n_pieces exceeds max_track_pieces: the links would be incomplete."""
+    t = _track_side(res, threshold, 'tracks')
+    n_obj = np.asarray(res['n_objects'])[:, t].astype(_I64)
+    B = n_obj.size
+    ids = [np.zeros(int(n), dtype=_I64) for n in n_obj]
+    ids[0][:] = np.arange(1, int(n_obj[0]) + 1)
+    birth, parent, merged, death = [0] * int(n_obj[0]), [0] * int(n_obj[0]), [0] * int(n_obj[0]), [0] * int(n_obj[0])
+    inherited = []
+    for p in range(B - 1):
+        L = links(res, p, t, min_cover)
+        e, l, a = L['earlier'], L['later'], L['area']
+        ne, nl = int(n_obj[p]), int(n_obj[p + 1])
+        # 2. the predecessor: per later object the link with the largest area, then the smallest earlier number
+        pred, pred_area = np.zeros(nl + 1, dtype=_I64), np.zeros(nl + 1, dtype=_I64)
+        order = np.lexsort((-e, a, l))                    # ascending area, then descending earlier: the last entry of a later object
+        last = np.flatnonzero(np.append(l[order][1:] != l[order][:-1], True)) if l.size else np.zeros(0, dtype=_I64)
+        pred[l[order][last]], pred_area[l[order][last]] = e[order][last], a[order][last]
+        # 3. the heir: per earlier object, among the later objects whose predecessor it is, the largest overlap, then the smallest number
+        heir = np.zeros(ne + 1, dtype=_I64)
+        for j in range(1, nl + 1):
+            i = int(pred[j])
+            if i and (heir[i] == 0 or pred_area[j] > pred_area[heir[i]]):
+                heir[i] = j
+        for i in range(1, ne + 1):
+            if heir[i]:
+                ids[p + 1][heir[i] - 1] = ids[p][i - 1]
+        inherited.append(np.array([(i, int(heir[i])) for i in range(1, ne + 1) if heir[i]], dtype=_I64).reshape(-1, 2))
+        # 4. everything else opens a track
+        for j in range(1, nl + 1):
+            if ids[p + 1][j - 1] == 0:
+                birth.append(p + 1)
+                parent.append(int(ids[p][pred[j] - 1]) if pred[j] else 0)
+                merged.append(0)
+                death.append(p + 1)
+                ids[p + 1][j - 1] = len(birth)
+        for k in ids[p + 1]:
+            death[k - 1] = p + 1
+        # 5. the earlier objects without an heir: the later object they overlap most, then the smallest number
+        order = np.lexsort((-l, a, e))
+        last = np.flatnonzero(np.append(e[order][1:] != e[order][:-1], True)) if e.size else np.zeros(0, dtype=_I64)
+        for i, j in zip(e[order][last].tolist(), l[order][last].tolist()):
+            if not heir[i]:
+                merged[int(ids[p][i - 1]) - 1] = int(ids[p + 1][j - 1])
+    as_array = lambda v: np.array(v, dtype=_I64)
+    return {'track_id': ids, 'inherited': inherited, 'birth': as_array(birth), 'death': as_array(death), 'parent': as_array(parent),
+            'merged_into': as_array(merged)}
+
+
+def motion(res, threshold=0):
+    """The motion between the blocks at threshold index `threshold` from a result with the track: {'shift': int32 [P, 2] (dy, dx),
+    the shift of every pair; 'links': per pair {'earlier', 'later': int64 [n], 'displacement': float64 [n, 2] (dy, dx)}: per
+    inherited link of `tracks` the later object's centroid minus the earlier one's, from the table rows' integer sums (sum / area);
+    NaN where an object lies beyond max_objects}."""
+    t = _track_side(res, threshold, 'motion')
+    tk = tracks(res, t)
+    area, sx, sy = [np.asarray(res[k])[:, t].astype(np.float64) for k in ('area', 'sum_x', 'sum_y')]
+    rows = area.shape[-1]
+    out = []
+    for p, link in enumerate(tk['inherited']):
+        e, l = link[:, 0], link[:, 1]
+        d = np.full((e.size, 2), np.nan)
+        ok = (e <= rows) & (l <= rows)
+        ei, li = e[ok] - 1, l[ok] - 1
+        d[ok, 0] = sy[p + 1][li] / area[p + 1][li] - sy[p][ei] / area[p][ei]
+        d[ok, 1] = sx[p + 1][li] / area[p + 1][li] - sx[p][ei] / area[p][ei]
+        out.append({'earlier': e, 'later': l, 'displacement': d})
+    return {'shift': np.asarray(res['track']['shift'])[:, t].copy(), 'links': out}
+
+
 def size_distribution(res, edges):
     """int64 [..., len(edges) - 1]: the objects of every (block, threshold) counted by area in the bins [edges[k], edges[k + 1])
     (ascending cell counts).  Only the objects in the table are counted (n_objects may exceed max_objects)."""
@@ -697,15 +998,16 @@ class Cells(object):
     name = 'composite'
     spectrum, model_var = True, None
     refuses = NB.Scores.refuses
-    _OWN = ('n_objects', 'table', 'labels', 'volume', 'skipped', 'field', 'field_cells', 'n_pieces', 'pieces', 'covered')
-    _SUMS, _MATCH = _OWN[3:7], _OWN[7:]
+    _OWN = ('n_objects', 'table', 'labels', 'volume', 'skipped', 'field', 'field_cells', 'n_pieces', 'pieces', 'covered',
+            'track_correlation', 'track_shift', 'track_n_pieces', 'track_pieces', 'track_covered')
+    _SUMS, _MATCH, _TRACK = _OWN[3:7], _OWN[7:10], _OWN[10:]
 
     def __init__(self, spec, observed=None, domain=None, keep_gates=False, phase=3, rays_per_block=0, distributed=False):
         if not isinstance(spec, Objects):
             raise ValueError('spec: a cosmo_pol_amd.objects.Objects, got %r' % (spec,))
         self.scores = NB.Scores(spec.fractions, observed, domain, keep_gates, phase, rays_per_block, distributed)
         self.spec, self.gates = spec, self.scores.gates
-        self.o = self.om = None
+        self.o = self.om = self.ot = None
 
     def set_plane(self, gate_xy, plane_version=0, source=0):
         self.scores.set_plane(gate_xy, plane_version, source)
@@ -716,16 +1018,28 @@ class Cells(object):
 
     def attach(self, native, az, n_gates, n_members, doppler, spectrum, staged_vars, take):
         structs, keep = self.scores.attach(native, az, n_gates, n_members, doppler, spectrum, staged_vars, take)
-        self.o = self.om = None
+        self.o = self.om = self.ot = None
         if not self.phase & 2:                    # (no cpol_fractions in this call: nothing to hang on)
             return structs, keep
         self.n_blocks = self.scores.n_blocks
+        shifts = None
+        if self.spec.track:                       # (the blocks must be times, and at least two: the library refuses one block too)
+            if n_members is not None:
+                raise ValueError('track: the blocks of an ensemble call are members, not times')
+            if self.n_blocks < 2:
+                raise ValueError('track: the call yields %d block; tracking needs at least two (rays_per_block, or a series of times)' % self.n_blocks)
+            if self.spec.shifts is not None:
+                shifts = shifts_of_call(self.spec, self.n_blocks)
         if scratch_bytes(self.spec, self.n_blocks) > MAX_SCRATCH_BYTES:
-            what = ('the labelling scratch, the sums and the pieces of %d blocks need' if self.spec.match else
+            what = ('the labelling scratch, the sums, the pieces and the track of %d blocks need' if self.spec.track else
+                    'the labelling scratch, the sums and the pieces of %d blocks need' if self.spec.match else
                     'the labelling scratch and the sums of %d blocks need' if self.spec.sums else 'the labelling scratch of %d blocks needs')
             raise ValueError('objects: %s more than 1 GiB' % (what % self.n_blocks))
-        self.o, okeep = native.Context.objects_struct(self.spec, self.scores.f)
-        if self.spec.match:
+        self.o, okeep = native.Context.objects_struct(self.spec, self.scores.f, shifts)
+        if self.spec.track:
+            self.ot = okeep[0]                    # (the ObjectsTrack around everything: it takes the five arrays of the track)
+            self.om = self.ot.m if self.spec.match else None
+        elif self.spec.match:
             self.om = okeep[0]                    # (the ObjectsMatch around self.o: it takes the three arrays of the match)
         return structs, keep + okeep
 
@@ -745,10 +1059,19 @@ class Cells(object):
             if spec.match:
                 out += [('n_pieces', np.uint32, (self.n_blocks, nt)), ('pieces', np.uint32, (self.n_blocks, nt, spec.max_pieces, WORDS)),
                         ('covered', np.uint32, (self.n_blocks, nt, 2, spec.max_objects))]
+            if spec.track:
+                P = self.n_blocks - 1
+                if spec.max_shift is not None:
+                    out.append(('track_correlation', np.uint32, (P, nt, 2 * spec.max_shift + 1, 2 * spec.max_shift + 1)))
+                out += [('track_shift', np.int32, (P, nt, 2)), ('track_n_pieces', np.uint32, (P, nt)),
+                        ('track_pieces', np.uint32, (P, nt, spec.max_track_pieces, WORDS)),
+                        ('track_covered', np.uint32, (P, nt, 2, spec.max_objects))]
         return out
 
     def bind(self, path, address):
-        if path in self._MATCH:
+        if path in self._TRACK:
+            setattr(self.ot, path[len('track_'):], address)
+        elif path in self._MATCH:
             setattr(self.om, path, address)
         elif path in self._OWN:
             setattr(self.o, path, address)
@@ -757,10 +1080,11 @@ class Cells(object):
 
     def bind_device(self, entry):
         # the scores' entries and 'n_objects' | 'table' | 'labels' | 'volume' | 'skipped' | 'field' | 'field_cells' | 'n_pieces' |
-        # 'pieces' | 'covered': device pointers
+        # 'pieces' | 'covered' | 'track_correlation' | 'track_shift' | 'track_n_pieces' | 'track_pieces' | 'track_covered': device pointers
         rest = {}
         for k, ptr in entry.items():
-            if k in self._OWN and self.phase & 2 and (k not in self._MATCH or self.spec.match):
+            if k in self._OWN and self.phase & 2 and (k not in self._MATCH or self.spec.match) and (
+                    k not in self._TRACK or (self.spec.track and (k != 'track_correlation' or self.spec.max_shift is not None))):
                 self.bind(k, ptr)
             else:
                 rest[k] = ptr
@@ -771,8 +1095,11 @@ class Cells(object):
         labels = w.pop('labels') if self.spec.labels else None
         sums = [w.pop(k) for k in self._SUMS] if self.spec.sums else None
         match = [w.pop(k) for k in self._MATCH] if self.spec.match else None
+        track = None
+        if self.spec.track:
+            track = [w.pop(k) if (k != 'track_correlation' or self.spec.max_shift is not None) else None for k in self._TRACK]
         out = self.scores.finish(w, coords)
-        out['objects'] = result(self.spec, n, table, labels, sums, match)
+        out['objects'] = result(self.spec, n, table, labels, sums, match, track)
         return out
 
     def join(self, parts, cat):
@@ -781,7 +1108,8 @@ class Cells(object):
         out = self.scores.join(parts, cat)
         if self.rays_per_block:
             ob = [w['objects'] for w in parts]
-            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds', 'weight', 'grid', 'field', 'pieces')]
+            stacked = [k for k in ob[-1] if k not in ('observed', 'connectivity', 'min_area', 'thresholds', 'weight', 'grid', 'field', 'pieces',
+                                                      'track')]      # (no track in an ensemble call: attach refuses it)
             out['objects'] = dict(ob[-1], **{k: cat([q[k] for q in ob]) for k in stacked})
             for nested in ('field', 'pieces'):
                 if nested in ob[-1]:

@@ -2546,6 +2546,10 @@ class RadarOperator(object):
         'connectivity', 'min_area', 'thresholds'}); device_outputs['composite'] may then carry 'n_objects', 'table' and 'labels'.
         With Objects(match=True) 'objects' also holds the overlap pieces of every block's objects with the observed ones
         ('pieces', 'covered', 'covered_observed': objects.py, MATCH), and the entry may carry 'n_pieces', 'pieces' and 'covered'.
+        With Objects(track=True, ...) and at least two blocks 'objects' also holds 'track': every block's objects followed into
+        the next block ('correlation', 'shift', 'n_pieces', 'pieces', 'covered': objects.py, TRACK; objects.links, tracks and
+        motion read it), and the entry may carry 'track_correlation', 'track_shift', 'track_n_pieces', 'track_pieces' and
+        'track_covered'; a call that yields one block is a ValueError.
         With a neighbourhood.Probabilities (over a Fractions; over an Objects it is a ValueError: not built) as `spec` it gains
         'probabilities': the neighbourhood ensemble probabilities of the call's blocks, exactly neighbourhood.ensemble_sums of
         the maps the same call returns ({'diff2' | 'forecast2' | 'observed2': uint64 [n_thr, n_radii], 'reliability': uint64
@@ -2577,7 +2581,9 @@ class RadarOperator(object):
         simulate_rays_composite_fss: with a neighbourhood.Probabilities the members are the blocks of res['composite']
         ['probabilities'] (NEP, NMEP, the ensemble FSS, the reliability table), with per_member=False there is one block, and a
         member list that `sequence_memory_budget` cuts into several calls is a ValueError; the rest (`radar`, `source`: the radars of a network differ in position only) as for
-        simulate_rays_ensemble_composite."""
+        simulate_rays_ensemble_composite.  An Objects with track=True is a ValueError: the blocks here are members, not times."""
+        if isinstance(spec, OB.Objects) and spec.track:
+            raise ValueError('track: the blocks of an ensemble call are members, not times')
         return self._ensemble_reduced(azimuths, elevations, self._fss_product(spec, observed, domain, device_outputs, keep_gates, phase, 0),
                                       'maps', members, per_member, device_outputs, apply_sensitivity, lane, pinned, radar=radar,
                                       source=source)

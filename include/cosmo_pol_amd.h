@@ -844,14 +844,53 @@ typedef struct cpol_composite_sums {
  * Kernels behind everything above: k_match_runs (the overlap flag from the two (root, number) lookups, the piece runs, `covered`
  * with one integer atomic per run segment and side), then k_obj_merge, k_obj_flatten, k_obj_area, k_obj_count and k_obj_number on
  * the piece arrays, k_match_attr and k_match_decode.
- * NOT BUILT: tracking across calls; block-against-block matching; cells of layered composites. */
+ *
+ * TRACK (cpol_objects_track, below: a cpol_objects_match embedded as the first member, announced by CPOL_OBJ_TRACK, bit 30 of
+ * o.pad_; the low 16 bits of pad_ stay max_pieces of the match against the observed map, 0 meaning that match is off; a call
+ * without the bit queues exactly what it queued before): the objects of one block followed into the next one, for storm tracks,
+ * cell lifetimes, splits and merges and the motion field of a nowcast, when the blocks of the call are scan times.  It needs
+ * neither `labels`, the exact sums nor the match; all may be on beside it and none changes.  cosmo_pol_amd/objects.py states the
+ * same rule (`correlation_of_pair`, `shift_of`, `shift_labels`, `track_of_maps`).
+ * A call has B = n_blocks >= 2 blocks and P = B - 1 pairs; pair p is (earlier = block p, later = block p + 1).  Per pair and
+ * threshold t, le and ll are the label maps of the two blocks exactly as `labels` defines them, Ke = le > 0, Kl = ll > 0.
+ * CORRELATION: for |dy|, |dx| <= S = max_shift (0 ... CPOL_TRACK_MAX_SHIFT): C[dy + S][dx + S] = #{(y, x): Ke[y][x] and
+ * Kl[y + dy][x + dx]}, both cells inside the grid; uint32 (a count is below 2^20).  S may exceed the grid's sides: such offsets
+ * count 0.
+ * SHIFT: the (dy, dx) with the largest C; ties go to the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx.  An
+ * all-zero table gives (0, 0).
+ * GIVEN SHIFTS: max_shift = -1 and shifts_in int32 [P][n_thresholds][2] (dy, dx), a HOST array whatever outputs_on_device says,
+ * |dy|, |dx| <= CPOL_TRACK_MAX_GIVEN (1023), read and checked before anything is queued and copied into `shift`; no correlation
+ * is then computed and `correlation` is not touched.
+ * SHIFTED OVERLAP: le'[y][x] = le[y - dy][x - dx] inside the grid, 0 outside.  The pieces, n_pieces and covered of the pair are
+ * those of MATCH with lf = le' and lo = ll, in the later block's frame: `forecast` is the object's number in the earlier block,
+ * `observed` its number in the later block; covered side 0 counts cells of the earlier objects, side 1 cells of the later ones.
+ * The INVARIANTS of MATCH hold.
+ * OUTPUTS: correlation uint32 [P][n_thresholds][2S + 1][2S + 1] or NULL = not wanted (the counters then lie in the scratch);
+ * shift int32 [P][n_thresholds][2]; n_pieces uint32 [P][n_thresholds]: the TRUE count; pieces uint32 [P][n_thresholds]
+ * [max_pieces][CPOL_OBJ_WORDS], rows at or beyond n_pieces zero; covered uint32 [P][n_thresholds][2][max_objects].  All follow
+ * p->outputs_on_device like `table`.  Every number is an integer: the result is exact in any order.
+ * LIMITS: the track scratch lies behind everything above on an 8-byte boundary: the packed masks uint64 [n_blocks][n_thresholds]
+ * [n_y][ceil(n_x / 64)], then P * n_thresholds piece maps of (2 * n_y * n_x + n_y) * 4 bytes, then, with max_shift >= 0 and a
+ * NULL `correlation`, the counters; the total is at most 1 GiB.
+ * CPOL_ERR_ARG as above, with nothing queued: n_blocks < 2; max_shift outside -1 ... 32; max_shift == -1 without shifts_in, or
+ * shifts_in with max_shift >= 0; a given shift beyond +-1023; max_pieces outside 1 ... 65535; NULL shift, n_pieces, pieces or
+ * covered; the limit exceeded; too many workgroups.  pad_ negative or with any of bits 16 ... 29 set is refused as before.
+ * Kernels behind everything above: k_track_bits (Ke of every block and threshold packed with a ballot per 64 cells),
+ * k_track_corr (popcounts of earlier words against funnel-shifted later words; one integer atomic per counter and workgroup),
+ * k_track_shift (a wavefront per pair and threshold: the argmax under the tie order), k_track_runs (k_match_runs with the earlier
+ * block's lookup at cell - shift, the shift read from device memory), then k_obj_merge, k_obj_flatten, k_obj_area, k_obj_count
+ * and k_obj_number on the track's piece arrays, k_track_attr and k_match_decode.
+ * NOT BUILT: tracking across calls; tracks of layered composites; per-object (local) shifts; a process group. */
 #define CPOL_OBJ_WORDS 10
 #define CPOL_OBJ_MAX_OBJECTS 65535
+#define CPOL_OBJ_TRACK (1 << 30)    /* in cpol_objects.pad_: the struct is the first member of a cpol_objects_track */
+#define CPOL_TRACK_MAX_SHIFT 32
+#define CPOL_TRACK_MAX_GIVEN 1023
 typedef struct cpol_objects {
     int32_t  connectivity;      /* 4 or 8                                                                          */
     int32_t  min_area;          /* >= 1                                                                            */
     int32_t  max_objects;       /* 1 ... 65535 table rows per (source, threshold)                                  */
-    int32_t  pad_;              /* 0, or max_pieces (1 ... 65535) when this struct is the first member of a cpol_objects_match */
+    int32_t  pad_;              /* 0, or max_pieces (1 ... 65535) when this struct is the first member of a cpol_objects_match; CPOL_OBJ_TRACK */
     uint32_t *n_objects;        /* [n_blocks + 1][n_thresholds]                                                    */
     uint32_t *table;            /* [n_blocks + 1][n_thresholds][max_objects][CPOL_OBJ_WORDS]                       */
     int32_t  *labels;           /* [n_blocks + 1][n_thresholds][n_y][n_x] or NULL = not wanted                     */
@@ -873,6 +912,20 @@ typedef struct cpol_objects_match {
     uint32_t *pieces;           /* [n_blocks][n_thresholds][max_pieces][CPOL_OBJ_WORDS]                              */
     uint32_t *covered;          /* [n_blocks][n_thresholds][2][max_objects]: forecast side, observed side             */
 } cpol_objects_match;
+
+/* TRACK (above): cpol_fractions.objects points at `m.o`; the library reads beyond `m` only when m.o.pad_ has CPOL_OBJ_TRACK.
+ * The low 16 bits of m.o.pad_: max_pieces of the match against the observed map, 0 = that match is off (m's pointers unread). */
+typedef struct cpol_objects_track {
+    cpol_objects_match m;
+    int32_t  max_shift;         /* 0 ... CPOL_TRACK_MAX_SHIFT: the correlation's reach; -1: the shifts are given              */
+    int32_t  max_pieces;        /* 1 ... 65535 piece rows per (pair, threshold)                                              */
+    const int32_t *shifts_in;   /* host [n_blocks - 1][n_thresholds][2] (dy, dx) with max_shift == -1, else NULL              */
+    uint32_t *correlation;      /* [n_blocks - 1][n_thresholds][2 max_shift + 1][2 max_shift + 1] or NULL = not wanted        */
+    int32_t  *shift;            /* [n_blocks - 1][n_thresholds][2]: dy, dx                                                   */
+    uint32_t *n_pieces;         /* [n_blocks - 1][n_thresholds]                                                              */
+    uint32_t *pieces;           /* [n_blocks - 1][n_thresholds][max_pieces][CPOL_OBJ_WORDS]                                  */
+    uint32_t *covered;          /* [n_blocks - 1][n_thresholds][2][max_objects]: earlier side, later side                     */
+} cpol_objects_track;
 
 /* Neighbourhood ensemble probabilities: what a convective-scale ensemble publishes of its members' maps -- the neighbourhood
  * ensemble probability (NEP) and the neighbourhood maximum ensemble probability (NMEP; Schwartz and Sobash 2017, Mon. Wea. Rev.
