@@ -295,6 +295,8 @@ struct cpol_ctx {
     int last_stencil = 0;
     std::vector<uint64_t> st_seen;
     int last_poly_central = 0;         // the last sweep's one sub-beam took the coordinate polynomials (cpol_debug_read "poly_central")
+    const void *last_poly = nullptr;   // the coefficient array the last sweep's gate kernel read (b_poly or its table set's), [last_poly_fits][2][CPOL_GEO_NP]
+    long last_poly_fits = 0;           // (cpol_debug_read "geo_poly": a test hook)
     bool last_subsum = false;          // the 1-D table items of the last sweep never went through res[] (k_subbeam_sum)
     bool last_vmask = false;           // the last sweep left vmask[] of every sub-beam gate (the general launch sequence)
     bool last_vn = false;              // ... and vn[] of every valid item (Doppler scheme 1)
@@ -3885,6 +3887,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         for (int j = 0; j < n_hyd; ++j) ia.pres_var[j] = ctx->hs.h[j].d.var_q;
     }
     ctx->last_poly_central = ia.poly_central;
+    ctx->last_poly = ia.exact_sub ? nullptr : ia.poly;
+    ctx->last_poly_fits = (long)geo_rays * n_h;
     if (cols) {
         // ---- 2'. the caller's columns instead of the interpolation ----
         const void *src[CPOL_MAX_VARS + 6];
@@ -5179,6 +5183,12 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     else if (!strcmp(name, "sz_integ")) { src = ctx->b_szinteg.p; bytes = (int64_t)n_rg * n_hyd * CPOL_N_SZ * 4; }
     else if (!strcmp(name, "sz_total")) { src = ctx->b_sztotal.p; bytes = (int64_t)n_rg * CPOL_N_SZ * 4; }
     else if (!strcmp(name, "traj")) { src = ctx->b_traj.p; bytes = (int64_t)ctx->last_n_rays * ctx->last_n_v * 3 * ctx->last_n_gates * 4; }
+    else if (!strcmp(name, "geo_poly")) {
+        // the coordinate polynomials of the last sweep, float64 [n_rays][n_h][2][CPOL_GEO_NP] monomial coefficients in x (NaN: a fit that
+        // k_trajectory's sanity rules rejected); a test hook like cpol_debug_math
+        if (!ctx->last_poly) { ctx->err = "cpol_debug_read: the last sweep took no coordinate polynomials"; return CPOL_ERR_ARG; }
+        src = ctx->last_poly; bytes = (int64_t)ctx->last_poly_fits * 2 * CPOL_GEO_NP * 8;
+    }
     else if (!strcmp(name, "psd_clock")) { src = ctx->b_clk.p; bytes = 2048 * 4 * 8; }
     else if (!strcmp(name, "bucket_count")) { src = (const int *)ctx->b_count.p + ctx->last_par * ctx->count_stride; bytes = (int64_t)ctx->last_n_keys * 4; }
     else { ctx->err = std::string("cpol_debug_read: unknown buffer ") + name; return CPOL_ERR_ARG; }

@@ -229,16 +229,40 @@ __global__ __launch_bounds__(256) void k_trajectory(ModelDev m, TrajArgs a)
             __syncthreads();
             if (ok) {
                 double c0 = 0.0, c1 = 0.0;
-                // (round 6, advisor: a fit nobody compares with the long form must not be badly conditioned -- a rotated longitude that
-                // wraps at +-180 deg between two nodes, a point next to the rotated pole.  Node values more than a degree apart over a
+                // (round 6, advisor: a fit that no sweep compares with the long form -- tests/test_gpu_geo_poly.py does, at sites, poles and
+                // ranges of its own -- must not be badly conditioned: a rotated longitude that wraps at +-180 deg between two nodes, a point
+                // next to the rotated pole.  Node values more than a degree apart over a
                 // fraction of a 150-km ray, or not finite: the coefficients become NaN, the gate kernel's guard reads NaN as "neighbour
                 // in another cell" and every gate of this (ray, node) takes the long form)
+                // The node rule alone lets fits through that are wrong by many float32 ulp: a site within a few degrees of the rotated
+                // pole, where the rotated longitude turns like an arc tangent of s and degree 8 no longer follows it although no two
+                // nodes are a degree apart (host model of tests/_geopoly.py: 18 ulp at 50 km and 0.2 deg from the pole, 53 ulp at 500 km
+                // and 6 deg; below 1e-3 ulp from 47 deg on).  So a fit must also have CONVERGED: its two highest Chebyshev
+                // coefficients, |c7| + |c8| -- the monomial ones over 64 and 128: T7 = 64 x^7 - ..., T8 = 128 x^8 - ..., and T8 has no
+                // x^7 -- at most 2^-26 of the smallest node value of their coordinate, less than a quarter of its float32 ulp.  Behind
+                // both rules the model finds no fit further than 0.005 ulp from the long form; from 47 deg off the pole the tail stays below
+                // 1 / 200 of the threshold and nothing is rejected.  (A node value of 0 rejects the fit: the long form is always right.)
+                // Every thread forms the two coefficients for itself (rows 7 and 8 of M), so that an accepted fit keeps its bits.
                 bool sane = true;
+                double t7[2] = {0.0, 0.0}, t8[2] = {0.0, 0.0}, least[2];
+                least[0] = fabs(s_node[0][el][0]);
+                least[1] = fabs(s_node[1][el][0]);
                 for (int k = 0; k < NP; ++k) {
                     c0 = fma(a.poly_M[q * NP + k], s_node[0][el][k], c0);
                     c1 = fma(a.poly_M[q * NP + k], s_node[1][el][k], c1);
                     if (k > 0) sane = sane && fabs(s_node[0][el][k] - s_node[0][el][k - 1]) <= 1.0 && fabs(s_node[1][el][k] - s_node[1][el][k - 1]) <= 1.0;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        t7[j] = fma(a.poly_M[(NP - 2) * NP + k], s_node[j][el][k], t7[j]);
+                        t8[j] = fma(a.poly_M[(NP - 1) * NP + k], s_node[j][el][k], t8[j]);
+                        least[j] = fmin(least[j], fabs(s_node[j][el][k]));
+                    }
                 }
+                static_assert(NP == 9, "the tail rule reads the Chebyshev coefficients 7 and 8 off the monomial ones");
+                constexpr double tail_limit = 1.0 / 67108864.0;                     // 2^-26
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    sane = sane && fabs(t7[j]) * (1.0 / 64.0) + fabs(t8[j]) * (1.0 / 128.0) <= tail_limit * least[j];   // (NaN: false)
                 if (!sane) c0 = c1 = __builtin_nan("");
                 double *o = a.poly + e * (2 * NP);
                 o[q] = c0;

@@ -1410,7 +1410,9 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * [n_hydro][n_sbg], "sz_integ" float32 [n_rays*n_gates][n_hydro][12],
  * "traj" float32 [n_rays][n_vnodes][3][n_gates], "item_res" float64
  * [n_hydro][n_sbg][12], "sub_wgate" float64 [n_sbg] (integration scheme 'ml': the per-gate
- * sub-beam weights); after a sweep in the general launch sequence (refused after the single-beam
+ * sub-beam weights), "geo_poly" float64 [n_rays][n_hnodes][2][9] (a test hook: the coordinate polynomials the gate
+ * kernel of the last sweep read -- monomial coefficients of the rotated latitude, then longitude, in x = 2 s / s_max - 1; NaN: a fit
+ * that k_trajectory's sanity rules rejected; CPOL_ERR_ARG after a sweep that took none); after a sweep in the general launch sequence (refused after the single-beam
  * kernels, which do not write them for every gate) "item_vmask" uint8 [n_sbg] (bit j: hydrometeor j valid)
  * and, under Doppler scheme 1, "item_vn" float64 [n_hydro][n_sbg][2] -- the fall-speed sums {v, n} of every
  * item, defined where its bit of "item_vmask" is set -- and, when a species' sums are totals over the ray
