@@ -4148,7 +4148,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             } else {
                 if (!(pk.exp_skip & 2))
                 hipLaunchKernelGGL(k_gate1_ray, tgrid, dim3(64 * n_hyd), lds_terms, st, ctx->hs, ctx->its, ca, fa, ga, rr,
-                                   gate1_finish_ops(fa, ga, t->sub_h, t->sub_w));
+                                   gate1_finish_ops(fa, ga, t->sub_h, t->sub_w), gate1_species_set(ctx->hs, ctx->its, ca, fa, t->sub_w));
                 if (tm) HIPCHK(hipEventRecord(ctx->ev[EV_CLASSIFY], st));
                 if (tm_psd) { HIPCHK(hipEventRecord(ctx->ev[EV_BUCKET], st)); HIPCHK(hipEventRecord(ctx->ev[EV_PSD], st)); }
                 if (!(pk.exp_skip & 4))

@@ -603,6 +603,160 @@ __device__ __forceinline__ void gate1_species_sums(const float *s_acc, const dou
     }
 }
 
+// ---- k_gate1_ray's item of one gamma 1-moment species on a 1-D table, from the compact record (cpol_gate_ops.h; round 11) ----
+// The statements of classify_item (cpol_psd.inl) for CPOL_RULE_RAIN_1MOM / GRAUPEL_1MOM / SNOW_1MOM with par_slot == 0, no
+// wgate, a float32 second axis and analytic moments, and of the body's gather, in the same order on the same types: the same
+// bits.  What differs is WHEN things are asked for.  classify_item forms the item's scale and its two fall-speed moments --
+// three exponentials, four divisions by species constants -- in front of the gather, although the block's address needs only
+// the key and the logarithm the rule has formed.  Here the top coefficient row is requested as soon as the position on the
+// panel axis is known; the slope, the scale and the moments are formed while it travels (gate1_single_moments), and the
+// quotients by nu come from the record.
+// The record's operands of a wavefront in scalar registers.  Each field goes through an empty asm statement that "changes" it:
+// the compiler then neither fetches every field by itself, awaited in front of its use, nor drops a value it holds and
+// fetches it again later (a kernel argument is cheap to rematerialise -- and one more awaited round in the chain).  The
+// first line's part is taken at entry, the rest with the wavefront's model values on their way: two scalar rounds in all.
+// (A pointer that went through such a statement is no longer known to point into global memory and would be read with flat
+// loads, which also count as LDS traffic: its loads say so themselves, g1_global.)
+#define CPOL_G1_GLOBAL __attribute__((address_space(1)))
+typedef double g1_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float g1_global(const float *p, long i) { return ((const float CPOL_G1_GLOBAL *)p)[i]; }
+__device__ __forceinline__ double2 g1_global(const double2 *p, long i)
+{
+    const g1_f64x2 x = ((const g1_f64x2 CPOL_G1_GLOBAL *)p)[i];
+    return make_double2(x.x, x.y);
+}
+
+struct Gate1SingleOps {
+    // (first line)
+    const float *tfun_snow;
+    const double *tab;
+    int rule, flags, key_base, n_pan;
+    // (second and third line)
+    float e_lo, e_step, t_lo, t_step, a32;
+    int n_e, n_t, ppo, pan_lo, pan_hi;
+    double lambda_factor, lam_exponent, log2_lo;
+    double d0, vn_exp_v, vn_exp_n, dv_pre, dn_pre;
+};
+
+__device__ __forceinline__ void gate1_single_operands(const Gate1SpeciesOps &s, Gate1SingleOps &o)
+{
+    o.e_lo = s.e_lo; o.e_step = s.e_step; o.t_lo = s.t_lo; o.t_step = s.t_step; o.a32 = s.a32;
+    o.n_e = s.n_e; o.n_t = s.n_t; o.ppo = s.ppo; o.pan_lo = s.pan_lo; o.pan_hi = s.pan_hi;
+    o.lambda_factor = s.lambda_factor; o.lam_exponent = s.lam_exponent; o.log2_lo = s.log2_lo;
+    o.d0 = s.d0; o.vn_exp_v = s.vn_exp_v; o.vn_exp_n = s.vn_exp_n; o.dv_pre = s.dv_pre; o.dn_pre = s.dn_pre;
+    asm volatile("" : "+s"(o.e_lo), "+s"(o.e_step), "+s"(o.t_lo), "+s"(o.t_step), "+s"(o.a32), "+s"(o.n_e), "+s"(o.n_t), "+s"(o.ppo),
+                 "+s"(o.pan_lo), "+s"(o.pan_hi), "+s"(o.lambda_factor), "+s"(o.lam_exponent), "+s"(o.log2_lo));
+    asm volatile("" : "+s"(o.d0), "+s"(o.vn_exp_v), "+s"(o.vn_exp_n), "+s"(o.dv_pre), "+s"(o.dn_pre));
+}
+
+__device__ __forceinline__ void gate1_single_moments(const Gate1SpeciesOps &rec, const Gate1SingleOps &s, double ll, double p1, double &p0,
+                                                     double &scale, double &dv, double &dn)
+{
+    p0 = cp_exp(ll);                                       // = cp_pow(lambda_factor / q, lam_exponent)
+    scale = p1 * cp_exp(-(p0 * s.d0));                     // gamma N0 exp(-lambda d0)
+    if (s.flags & CPOL_G1S_HAS_VN) {                       // (wave-uniform)
+        if (s.flags & CPOL_G1S_N0_UNIFORM) {
+            dv = s.dv_pre * cp_exp(s.vn_exp_v * ll);
+            dn = s.dn_pre * cp_exp(s.vn_exp_n * ll);
+        } else {                                           // (snow: the lane's intercept; its four constants in one round from the record)
+            const double n0v = p1;
+            dv = rec.vel_factor * n0v * rec.alpha / rec.nu * cp_exp(s.vn_exp_v * ll);
+            dn = rec.ntot_factor * n0v / rec.nu * cp_exp(s.vn_exp_n * ll);
+        }
+    }
+}
+
+__device__ __forceinline__ void gate1_item_single(const Gate1SpeciesOps &rec, const Gate1SingleOps &s, bool in, float e, float T, float qm, ClassItem &o,
+                                                  double2 (&v)[CPOL_N_SZ / 2], double2 &wv, bool &have
+#ifdef CPOL_SUBSUM_TRACE
+                                                  , unsigned long long &trace_rule, unsigned long long &trace_req
+#endif
+                                                  )
+{
+    constexpr int NC = CPOL_ITAB1_NC, NFP = CPOL_ITAB_NFP, NB = NC * NFP;
+    const bool want_vn = s.flags & CPOL_G1S_WRITES_VN;
+    const bool valid = in && (qm > 0.f);
+    int key = -1;
+    double ll = 0.0, p1 = 0.0, pf = -1.0;
+    bool lookup = false;
+    if (valid) {
+        float n0 = 0.f;
+        bool tabulated = true;
+        if (s.rule == CPOL_RULE_SNOW_1MOM) {                // (tfun_lookup, requested as soon as T is in)
+            const unsigned idx = __float_as_uint(T) - CPOL_TFUN_FIRST_BITS;
+            tabulated = s.tfun_snow && idx < CPOL_TFUN_COUNT;
+#if CPOL_EXP_NO_TFUN               // (timing experiment only, wrong values: no gather into the 64-MB table)
+            if (tabulated) n0 = T * 1.0e-3f;
+#else
+            if (tabulated) n0 = g1_global(s.tfun_snow, idx);
+#endif
+        }
+        // lut.py:336-341: float32 arithmetic for float32 queries
+        const int eb = clip_bin((e - s.e_lo) / s.e_step, s.n_e);
+        const int tb = clip_bin((T - s.t_lo) / s.t_step, s.n_t);
+        key = s.key_base + eb * s.n_t + tb;
+        const double q = (double)qm;
+        if (s.rule == CPOL_RULE_SNOW_1MOM) {                // (wave-uniform)
+            // hydrometeors.py:896-899: float32 chain, then float64 from lambda_factor on
+            if (!tabulated) n0 = 13.5f * (565000.0f * exp_f32(-0.107f * (T - 273.15f))) / 1000.0f;
+            const float an0 = s.a32 * n0;
+            ll = s.lam_exponent * cp_log((double)an0 * s.lambda_factor / q);
+            p1 = (double)n0;
+        } else {
+            ll = s.lam_exponent * cp_log(s.lambda_factor / q);
+            p1 = 1.0;                                       // N0 folded into pre[]
+        }
+        pf = (ll * 1.4426950408889634 - s.log2_lo) * (double)s.ppo;
+        lookup = pf >= (double)s.pan_lo && pf < (double)s.pan_hi;   // NaN -> false
+    }
+#ifdef CPOL_SUBSUM_TRACE
+    asm volatile("" :: "v"(pf));
+    trace_rule = wall_clock64();                            // (the rule's operands have arrived, the position on the panel axis is formed)
+#endif
+    double p0 = 0.0, scale = 0.0, dv = 0.0, dn = 0.0;
+    if (lookup) {
+        // ---- 1-D block: the lane gathers the rows of its (slice, panel) block ----
+        const int pn = min((int)pf, s.n_pan - 1);
+        const double u = 2.0 * (pf - (double)pn) - 1.0;
+#if CPOL_EXP_ONE_BLOCK            // (timing experiment only: every lane reads the same block -- no gather)
+        const double2 *blk = reinterpret_cast<const double2 *>(s.tab);
+#else
+        const double2 *blk = reinterpret_cast<const double2 *>(s.tab + ((long)(key - s.key_base) * s.n_pan + pn) * NB);
+#endif
+#pragma unroll
+        for (int c = 0; c < CPOL_N_SZ / 2; ++c) v[c] = g1_global(blk, (NC - 1) * (NFP / 2) + c);
+        if (want_vn) wv = g1_global(blk, (NC - 1) * (NFP / 2) + CPOL_N_SZ / 2);
+        __builtin_amdgcn_sched_barrier(0);                  // (the top row is on its way before the exponentials start)
+#ifdef CPOL_SUBSUM_TRACE
+        trace_req = wall_clock64();
+#endif
+        gate1_single_moments(rec, s, ll, p1, p0, scale, dv, dn);
+#pragma unroll CPOL_GATE1S_ROW_UNROLL
+        for (int q = NC - 2; q >= 0; --q) {
+#pragma unroll
+            for (int c = 0; c < CPOL_N_SZ / 2; ++c) {
+                const double2 cq = g1_global(blk, q * (NFP / 2) + c);
+                v[c].x = fma(v[c].x, u, cq.x);
+                v[c].y = fma(v[c].y, u, cq.y);
+            }
+            if (want_vn) {
+                const double2 cq = g1_global(blk, q * (NFP / 2) + CPOL_N_SZ / 2);
+                wv.x = fma(wv.x, u, cq.x);
+                wv.y = fma(wv.y, u, cq.y);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CPOL_N_SZ / 2; ++c) { v[c].x *= scale; v[c].y *= scale; }
+        wv.x *= scale; wv.y *= scale;
+        have = true;
+    } else if (valid) {
+        // (off the table: integrate_gamma_item_wave takes key, p0 and p1; the moments as classify_item forms them)
+        gate1_single_moments(rec, s, ll, p1, p0, scale, dv, dn);
+    }
+    o.key = key; o.p0 = p0; o.p1 = p1; o.p2 = 0.0; o.pf = lookup ? pf : -1.0; o.scale = scale;
+    o.dv = dv; o.dn = dn; o.valid = valid; o.lookup = lookup; o.has_vn = valid && (s.flags & CPOL_G1S_HAS_VN);
+}
+
 // RAY = false: k_gate1_species as described above (grid = ceil(n_rg / 64)).
 // RAY = true: an item outside its table is integrated on the spot (integrate_gamma_item_wave: no deferred gates, no
 // integrating launch behind this kernel).
@@ -637,7 +791,7 @@ __device__ __forceinline__ void gate1_species_sums(const float *s_acc, const dou
 #define GATE1S_BLK_BYTES (CPOL_GATE1_LDS ? 2 * ((CPOL_ITAB1_NC * CPOL_ITAB_NFP / 2) > CPOL_WAVE ? (CPOL_ITAB1_NC * CPOL_ITAB_NFP / 2) : CPOL_WAVE) * 16 : 0)
 template <bool RAY, bool TICKET>
 __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const ItabSet &its, const ClassifyArgs &a, const FinalArgs &f,
-                                                   const GateArgs &g, const ScanRayArgs &r, const Gate1FinishOps &fo)
+                                                   const GateArgs &g, const ScanRayArgs &r, const Gate1FinishOps &fo, const Gate1SpeciesSet &so)
 {
     constexpr int NC = CPOL_ITAB1_NC, NFP = CPOL_ITAB_NFP, NB = NC * NFP;
     extern __shared__ unsigned char s_raw[];
@@ -660,10 +814,23 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     // form keeps 64 gates of one ray (its scan needs whole rays)
     constexpr bool TILED = RAY && !TICKET;
     const int lane = lane_id();
+    const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                    // the wavefront's hydrometeor
+    // (round 11) k_gate1_ray: what a wavefront reads in front of its ticket comes from its slot's compact record
+    // (cpol_gate_ops.h), the first 64-byte line in front of the value loads: the sweep's shape, the value pointers, the flags
+    const Gate1SpeciesOps &sj = so.s[LAST_WAVE ? j : 0];
+    const int sflags = LAST_WAVE ? sj.flags : CPOL_G1S_GENERIC;
+    const int n_rays_ = LAST_WAVE ? sj.n_rays : f.n_rays, n_gates_ = LAST_WAVE ? sj.n_gates : f.n_gates;
+    const float *sj_elev = sj.elev, *sj_t = sj.val_t, *sj_q = sj.val_q;
+    Gate1SingleOps sr = {};
+    if (LAST_WAVE) {                                    // (ONE round: the line is here, and what it holds stays in registers)
+        sr.tfun_snow = sj.tfun_snow; sr.tab = sj.tab; sr.rule = sj.rule; sr.flags = sflags; sr.key_base = sj.key_base; sr.n_pan = sj.n_pan;
+        asm volatile("" : "+s"(sj_elev), "+s"(sj_t), "+s"(sj_q), "+s"(sr.tfun_snow), "+s"(sr.tab), "+s"(sr.rule), "+s"(sr.flags),
+                     "+s"(sr.key_base), "+s"(sr.n_pan));
+    }
     int ray_b = 0, gate_b = 0, ray0 = 0, gate0 = 0;
     if (TILED) {
         int dray, dgate;
-        if (!gate1_tile_of_block(gate1_tiles(f.n_rays, f.n_gates), blockIdx.x, ray0, gate0)) return;   // (padding: the whole workgroup)
+        if (!gate1_tile_of_block(gate1_tiles(n_rays_, n_gates_), blockIdx.x, ray0, gate0)) return;   // (padding: the whole workgroup)
         gate1_lane_in_tile(lane, dray, dgate);
         ray_b = ray0 + dray;
         gate_b = gate0 + dgate;
@@ -685,17 +852,19 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #ifdef CPOL_SUBSUM_TRACE
     const unsigned long long g1_barrier = wall_clock64();    // every wavefront of the workgroup has arrived
 #endif
-    const int j = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                    // the wavefront's hydrometeor
-    const long i0 = RAY ? (long)ray_b * f.n_gates + gate_b : (long)blockIdx.x * 64 + lane;
-    const bool in = TILED ? ray_b < f.n_rays && gate_b < f.n_gates : RAY ? gate_b < f.n_gates : i0 < a.n_sbg;
+    const long i0 = RAY ? (long)ray_b * n_gates_ + gate_b : (long)blockIdx.x * 64 + lane;
+    const bool in = TILED ? ray_b < n_rays_ && gate_b < n_gates_ : RAY ? gate_b < n_gates_ : i0 < a.n_sbg;
     const long n = a.n_sbg;
     const long i = in ? i0 : 0;
     const HydroDev &h = hs.h[j];
     const cpol_hydro_desc &d = h.d;
     const ItabDev &t = its.t[j];
-    const bool want_rvel = f.RVEL != nullptr;
-    const bool want_vn = want_rvel && t.writes_vn;                                     // uniform: the table carries the Doppler sums
-    const double w0 = f.sub_w[0];
+    // (round 11) the usual species of a single-beam sweep: the item phase from the record (gate1_item_single).  Wave-uniform;
+    // a slot the record does not cover keeps classify_item.
+    const bool single = LAST_WAVE && !CPOL_GATE1_LDS && !(sflags & CPOL_G1S_GENERIC);
+    const bool want_rvel = LAST_WAVE ? (sflags & CPOL_G1S_RVEL) != 0 : f.RVEL != nullptr;
+    const bool want_vn = LAST_WAVE ? (sflags & CPOL_G1S_WRITES_VN) != 0 : want_rvel && t.writes_vn;  // uniform: the table carries the Doppler sums
+    const double w0 = LAST_WAVE ? sj.w0 : f.sub_w[0];
 
     // (round 6) k_interp_sweep's word of this tile: bit q clear = no gate of the tile has a positive mass density of slot q, so the slot
     // has no item here (classify_item: valid needs qm > 0).  The wavefront of such a slot -- 60 % of them on the C2 sweep, 2.4 us of
@@ -731,6 +900,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #ifdef CPOL_SUBSUM_TRACE
     unsigned long long g1t[6], g1_valid = 0, g1_hw = 0, g1_pre = 0;
     unsigned long long g1_rule = 0, g1f[5] = {0, 0, 0, 0, 0};      // (round 10: the clock behind the species' rule; the parts of the finish)
+    unsigned long long g1_req = 0;                                 // (round 11: the clock behind the first coefficient request)
     if (LAST_WAVE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         const unsigned long long g1_present = wall_clock64();                          // the presence words have arrived
@@ -752,9 +922,18 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #endif
     if (LAST_WAVE && !here && !(n_here == 0 && j == 0)) return;                        // (the slot is free for the next workgroup's wavefronts)
     const bool inl = in && here;
-    const float e = inl ? a.elev[i] : 0.f;
-    const float T = inl ? a.vals[d.var_t * n + i] : 0.f;
-    const float qm = inl ? a.vals[d.var_q * n + i] : 0.f;                              // (q_source == CPOL_Q_MODEL: no melting species here)
+    // (k_gate1_ray: the three loads behind ONE scalar round, the record's first line: vals + var * n is resolved on the host)
+    float e = 0.f, T = 0.f, qm = 0.f;
+    if (inl) {
+        e = LAST_WAVE ? g1_global(sj_elev, i) : a.elev[i];
+        T = LAST_WAVE ? g1_global(sj_t, i) : a.vals[d.var_t * n + i];
+        qm = LAST_WAVE ? g1_global(sj_q, i) : a.vals[d.var_q * n + i];                            // (q_source == CPOL_Q_MODEL: no melting species here)
+    }
+    if (single) {
+        __builtin_amdgcn_sched_barrier(0);              // (the values are requested; the rest of the record arrives while they travel)
+        gate1_single_operands(sj, sr);
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #ifdef CPOL_SUBSUM_TRACE
     // (-DCPOL_SUBSUM_TRACE build, tools/gate1_trace.py: the phases of every wavefront of k_gate1_ray on the 100-MHz clock)
     g1t[0] = LAST_WAVE ? g1_enter : wall_clock64();
@@ -773,6 +952,19 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     g1t[2] = g1t[3] = g1t[1];
 #endif
     if (!gone) {
+    double2 v[CPOL_N_SZ / 2];
+#pragma unroll
+    for (int c = 0; c < CPOL_N_SZ / 2; ++c) v[c] = make_double2(0.0, 0.0);
+    bool have = false;
+    if (single) {
+#ifdef CPOL_SUBSUM_TRACE
+        g1_rule = g1_req = g1t[1];
+        gate1_item_single(sj, sr, inl, e, T, qm, it, v, wv, have, g1_rule, g1_req);
+        g1t[2] = g1_rule;                              // (the scale and the moments are formed inside the gather here)
+#else
+        gate1_item_single(sj, sr, inl, e, T, qm, it, v, wv, have);
+#endif
+    } else {
 #ifdef CPOL_SUBSUM_TRACE
     g1_rule = g1t[1];
     classify_item(h, t, a, a.vals, n, i, i, inl, qm, 0.0, T, d.var_t, e, it, LAST_WAVE ? &g1_rule : nullptr);
@@ -782,11 +974,8 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #ifdef CPOL_SUBSUM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     g1t[2] = wall_clock64();                           // PSD parameters, table position
+    g1_req = g1t[2];                                   // (the gather starts behind them)
 #endif
-    double2 v[CPOL_N_SZ / 2];
-#pragma unroll
-    for (int c = 0; c < CPOL_N_SZ / 2; ++c) v[c] = make_double2(0.0, 0.0);
-    bool have = false;
 #if CPOL_GATE1_LDS
     {
         // ---- 1-D blocks through LDS (round 6): the 64 gates of a wavefront -- neighbours along one ray, one species -- sit on 4 to 6
@@ -886,6 +1075,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         have = true;
     }
 #endif
+    }   // (!single)
 #ifdef CPOL_SUBSUM_TRACE
     {
         double keep = 0.0;
@@ -895,7 +1085,6 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         g1t[3] = wall_clock64();                       // coefficient gather + Horner chains
     }
 #endif
-    my_lookup = it.lookup ? 1 : 0;
     bool off_table = it.valid && !it.lookup;
     if (RAY) {
         // (items outside the integral table: integrated further down, when the columns of the others have left the registers)
@@ -941,7 +1130,7 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
         }
         off_table = false;                                        // (nothing is deferred)
     }
-    const bool moments = want_rvel && it.valid && f.vsrc[j] == 1;
+    const bool moments = it.valid && (LAST_WAVE ? (sflags & CPOL_G1S_MOMENTS) != 0 : want_rvel && f.vsrc[j] == 1);
     double vj = 0.0, nj = 0.0;
     if (moments) {
         if (want_vn) { vj = wv.x; nj = wv.y; }
@@ -952,15 +1141,16 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
     s_mn[j * 64 + lane] = nj;
     s_flag[j * 64 + lane] = (it.valid ? 1u : 0u) | (off_table ? 2u : 0u) | (moments ? 4u : 0u);
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) my_lookup += __shfl_xor(my_lookup, off);
+    // (a lane holds one item: the count of the wavefront's table items is the ballot's, not six dependent shuffles in front of the ticket)
+    my_lookup = __popcll(__builtin_amdgcn_ballot_w64(it.lookup));
     }   // (!gone)
     bool fast = false;                                // (k_gate1_ray: the gates were finished from the compact record)
     if (LAST_WAVE) {
         // this wavefront's share of the sweep's table-item count, then its ticket: release (its LDS stores are complete),
         // acquire for the wavefront that finds every other ticket taken
         if (lane == 0 && my_lookup) {
-            const unsigned slot = ((blockIdx.x + blockIdx.y * gridDim.x) * 4u + (unsigned)j) & (CPOL_COUNT_SLOTS - 1);
+            // (the grid of tiles is 1-D: blockIdx.y == 0, no awaited load of gridDim in front of the ticket)
+            const unsigned slot = (blockIdx.x * 4u + (unsigned)j) & (CPOL_COUNT_SLOTS - 1);
             atomicAdd(a.n_lookup + 2 + slot, my_lookup);
         }
         // (the tickets count in the low byte; above it bit 8 + q: the wavefront of slot q had no item -- `gone`)
@@ -976,8 +1166,12 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 #ifdef CPOL_SUBSUM_TRACE
         g1t[4] = wall_clock64();                       // terms in LDS, ticket taken
         // (round 10, bits 8-19 of word 6: model values arrived -> the species' rule done, in ticks of 10 ns; the valid lanes keep bits 0-7)
+        // (round 11, bits 20-31: model values arrived -> the first coefficient rows requested, the latest lane's)
+        unsigned req = g1_req > g1t[1] ? (unsigned)min(g1_req - g1t[1], 4095ull) : 0u;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) req = max(req, (unsigned)__shfl_xor((int)req, off));
         g1_valid = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(it.valid)) | ((unsigned long long)j << 32) | g1_pre |
-                   (min(g1_rule - g1t[1], 4095ull) << 8);
+                   (min(g1_rule - g1t[1], 4095ull) << 8) | ((unsigned long long)req << 20);
         g1_hw = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                 (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
         if (old != n_here - 1) {
@@ -1183,14 +1377,14 @@ __device__ __forceinline__ void gate1_species_body(const HydroSet &hs, const Ita
 
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_species(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g)
 {
-    gate1_species_body<false, false>(hs, its, a, f, g, ScanRayArgs{}, Gate1FinishOps{});
+    gate1_species_body<false, false>(hs, its, a, f, g, ScanRayArgs{}, Gate1FinishOps{}, Gate1SpeciesSet{});      // (the record is never read: RAY = false)
 }
 
 // grid = gate1_tiles(n_rays, n_gates).n_blocks, block = 64 * n_hydro, dynamic LDS = n_hydro * (64 * GATE1S_BYTES + GATE1S_BLK_BYTES)
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
-                                                                                  ScanRayArgs r, Gate1FinishOps fo)
+                                                                                  ScanRayArgs r, Gate1FinishOps fo, Gate1SpeciesSet so)
 {
-    gate1_species_body<true, false>(hs, its, a, f, g, r, fo);
+    gate1_species_body<true, false>(hs, its, a, f, g, r, fo, so);
 }
 
 // the same with the ray's scans inside (the ticket: see gate1_species_body); CPOL_GATE1_RAY=3.  grid = (ceil(n_gates / 64), n_rays),
@@ -1199,7 +1393,7 @@ __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_
 __global__ __launch_bounds__(64 * CPOL_MAX_HYDRO) CPOL_GATE1S_ATTR void k_gate1_ray_scan(HydroSet hs, ItabSet its, ClassifyArgs a, FinalArgs f, GateArgs g,
                                                                                        ScanRayArgs r)
 {
-    gate1_species_body<true, true>(hs, its, a, f, g, r, Gate1FinishOps{});
+    gate1_species_body<true, true>(hs, its, a, f, g, r, Gate1FinishOps{}, Gate1SpeciesSet{});                    // (never read: TICKET = true)
 }
 
 // The range scans of a single-beam sweep whose gates k_gate1_ray has finished (no deferred gates: nothing of final_gate):

@@ -10,6 +10,10 @@ formed: `us_rule`, the rest of `us_parameters` is the table position and the fal
 each the latest lane's, counted from the ticket: the species' sums read from LDS, the polarimetric part done and its eight
 stores issued, RVEL's operands arrived (the projection known), arithmetic done (RVEL and mask formed), stores issued; what
 is left of the finish is the wait for the stores.
+Round 11: model values arrived -> the first coefficient rows requested (`us_first_request`, the latest lane's; beside `us_rule`).
+A wavefront whose slot takes the compact species record forms its scale and moments behind that request, inside the gather:
+its `us_parameters` ends with the position on the panel axis.  A build without the point (bits 20-31 of word 6 zero
+everywhere) reports None: there the request follows the parameters, `us_parameters` is its figure.
 ONE isolated c2 sweep on one lane (CPOL_GATE1_RAY=1), and one of three lanes in flight."""
 import contextlib
 import json
@@ -30,6 +34,7 @@ def report(tag, tr):
     t = tr[used].astype(np.int64)
     nv = (tr[used, 6] & np.uint64(0xFF)).astype(np.int64)
     t_rule = ((tr[used, 6] >> np.uint64(8)) & np.uint64(0xFFF)).astype(np.int64)        # values arrived -> the species' rule done
+    t_req = ((tr[used, 6] >> np.uint64(20)) & np.uint64(0xFFF)).astype(np.int64)        # values arrived -> first coefficient rows requested
     sp = ((tr[used, 6] >> np.uint64(32)) & np.uint64(0xFF)).astype(np.int64)
     t_bar = ((tr[used, 6] >> np.uint64(40)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> barrier passed
     t_pre = ((tr[used, 6] >> np.uint64(52)) & np.uint64(0xFFF)).astype(np.int64)      # entry -> presence words known
@@ -51,6 +56,7 @@ def report(tag, tr):
                          'us_life_not_finishing': round(float(us(life[m & ~last]).mean()), 2) if (m & ~last).any() else None,
                          'us_values': round(float(us(ph[m, 0]).mean()), 2), 'us_parameters': round(float(us(ph[m, 1]).mean()), 2),
                          'us_rule': round(float(us(t_rule[m]).mean()), 2),
+                         'us_first_request': round(float(us(t_req[m & (t_req > 0)]).mean()), 2) if (m & (t_req > 0)).any() else None,
                          'us_gather_horner': round(float(us(ph[m, 2]).mean()), 2), 'us_lds_ticket': round(float(us(ph[m, 3]).mean()), 2),
                          'us_life_mean': round(float(us(life[m]).mean()), 2), 'us_life_p95': round(float(np.percentile(us(life[m]), 95)), 2)}
     if last.any():
