@@ -1627,6 +1627,17 @@ class Context(object):
         v = self.debug_read('launch_forms', (len(self.FORM_NAMES),), np.int32)
         return dict(zip(self.FORM_NAMES, (int(x) for x in v)))
 
+    # enum WorkBuf of csrc/cpol_buffers.h, in its order
+    WORK_BUFFERS = ('traj', 'rayc', 'poly', 'timed', 'vals', 'mask', 'elev', 'coords', 'wgate', 'qmelt', 'fwmelt',
+                    'key', 'pos', 'par', 'count', 'totals', 'blkranked', 'rec', 'vmask', 'offset', 'perm', 'res',
+                    'vn', 'icefirst', 'proj', 'colin', 'xscr', 'xgeo', 'beam', 'bsigma', 'bon',
+                    'gscan', 'defer', 'present', 'ticket', 'units', 'szinteg', 'clk')
+
+    def work_buffers(self):
+        """The capacity in bytes of every per-sweep work buffer of this context, 0 where it is absent (a test hook): {name: int}."""
+        v = self.debug_read('work_buffers', (len(self.WORK_BUFFERS),), np.uint64)
+        return dict(zip(self.WORK_BUFFERS, (int(x) for x in v)))
+
     def debug_read(self, name, shape, dtype):
         out = np.empty(shape, dtype=dtype)
         n = self.lib.cpol_debug_read(self.h, name.encode(), _ptr(out), out.nbytes)

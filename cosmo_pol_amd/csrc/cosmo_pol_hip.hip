@@ -27,6 +27,7 @@
 #include "cpol_tile.h"
 #include "cpol_forms.h"
 #include "cpol_place.h"
+#include "cpol_buffers.h"
 #include "cpol_hist.h"
 #include "cpol_comp.h"
 #include "cpol_frac.h"
@@ -53,6 +54,8 @@ static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATE
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
               (int)FORMS_MODE_GAMMA_UNIFORM == (int)PSD_MODE_GAMMA_UNIFORM && (int)FORMS_MODE_ICE == (int)PSD_MODE_ICE &&
               (int)FORMS_MODE_MELTING == (int)PSD_MODE_MELTING, "cpol_forms.h: the build constants of the kernel files");
+static_assert(BUF_GEO_NP == CPOL_GEO_NP && BUF_MAX_PAR == CPOL_MAX_PAR && BUF_COUNT_SLOTS == CPOL_COUNT_SLOTS &&
+              BUF_ICEFIRST_BYTES == sizeof(IceFirst) && BUF_WORKUNIT_BYTES == sizeof(WorkUnit), "cpol_buffers.h: the build constants of the kernel files");
 
 namespace {
 
@@ -276,6 +279,7 @@ struct cpol_ctx {
     bool counters_dirty = false;       // a launch sequence began and did not end in sweep_serial advancing (an error return after
                                        // its first launch): both counter sets are cleared before the next sequence uses one
     int last_par = 0;                  // the set the last sweep used
+    uint64_t graph_captures = 0;       // launch sequences captured into a HIP graph so far (cpol_debug_read "graph_captures": a test hook)
     int last_forms[12] = {0};          // the launch forms of the last sweep (cpol_debug_read "launch_forms"): [0] g1r, [1] k_gate1_ray, [2] single-beam gate kernel,
                                        // [3] k_interp_classify, [4] items off the tables listed directly, [5] k_subbeam_sum, [6] table items evaluated in place,
                                        // [7] coordinate polynomials for the one sub-beam, [8] n_sub, [9] lanes alive, [10] CPOL_SCAN_FORM (1: the range scans by a whole wavefront), [11] HIP graph replayed
@@ -327,6 +331,18 @@ struct cpol_ctx {
 };
 
 namespace {
+
+// the per-sweep work buffers of cpol_buffers.h, in the order of enum WorkBuf: what run_sequence sizes and fills, the graph key
+// mixes, cpol_mem_info counts and cpol_destroy frees
+DevBuf cpol_ctx::*const WORK_BUFS[] = {
+    &cpol_ctx::b_traj, &cpol_ctx::b_rayc, &cpol_ctx::b_poly, &cpol_ctx::b_timed, &cpol_ctx::b_vals, &cpol_ctx::b_mask, &cpol_ctx::b_elev,
+    &cpol_ctx::b_coords, &cpol_ctx::b_wgate, &cpol_ctx::b_qmelt, &cpol_ctx::b_fwmelt,
+    &cpol_ctx::b_key, &cpol_ctx::b_pos, &cpol_ctx::b_par, &cpol_ctx::b_count, &cpol_ctx::b_totals, &cpol_ctx::b_blkranked, &cpol_ctx::b_rec,
+    &cpol_ctx::b_vmask, &cpol_ctx::b_offset, &cpol_ctx::b_perm, &cpol_ctx::b_res,
+    &cpol_ctx::b_vn, &cpol_ctx::b_icefirst, &cpol_ctx::b_proj, &cpol_ctx::b_colin, &cpol_ctx::b_xscr, &cpol_ctx::b_xgeo, &cpol_ctx::b_beam,
+    &cpol_ctx::b_bsigma, &cpol_ctx::b_bon,
+    &cpol_ctx::b_gscan, &cpol_ctx::b_defer, &cpol_ctx::b_present, &cpol_ctx::b_ticket, &cpol_ctx::b_units, &cpol_ctx::b_szinteg, &cpol_ctx::b_clk};
+static_assert(sizeof WORK_BUFS / sizeof WORK_BUFS[0] == WB_N, "cpol_buffers.h: one context member per WorkBuf");
 
 #define HIPCHK(call)                                                                      \
     do {                                                                                  \
@@ -835,17 +851,15 @@ void cpol_destroy(cpol_ctx *ctx)
     free_buf(ctx->d_hdiff);
     if (!ctx->parent) for (auto &b : ctx->members) free_buf(b);      // (the cubes of the ensemble members)
     ctx->members.clear();
-    DevBuf *all[] = {&ctx->d_H, &ctx->d_V, &ctx->b_traj, &ctx->b_wgate, &ctx->b_clk, &ctx->b_rayc,
-                     &ctx->b_beam, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount, &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_hcounts[0], &ctx->b_hcounts[1], &ctx->b_hcounts[2], &ctx->b_hcounts[3], &ctx->b_hcounts[4], &ctx->b_hcounts[5], &ctx->b_hcounts[6], &ctx->b_hcounts[7], &ctx->b_hcounts[8], &ctx->b_hcounts[9], &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane, &ctx->b_cout[0], &ctx->b_cout[1], &ctx->b_cout[2], &ctx->b_cout[3], &ctx->b_cout[4], &ctx->b_cout[5], &ctx->b_cout[6], &ctx->b_cout[7], &ctx->b_cout[8], &ctx->b_cout[9], &ctx->b_fsat, &ctx->b_fobs, &ctx->b_fout[0], &ctx->b_fout[1], &ctx->b_fout[2], &ctx->b_fout[3], &ctx->b_fout[4], &ctx->b_fout[5], &ctx->b_fout[6], &ctx->b_fout[7], &ctx->b_fout[8], &ctx->b_oscr, &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs, &ctx->b_vals, &ctx->b_mask,
-                     &ctx->b_elev, &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key,
-                     &ctx->b_par, &ctx->b_count, &ctx->b_offset, &ctx->b_units,
-                     &ctx->b_totals, &ctx->b_perm, &ctx->b_res, &ctx->b_pos,
-                     &ctx->b_vn, &ctx->b_icefirst, &ctx->b_rvel, &ctx->b_proj, &ctx->b_blkranked, &ctx->b_rec, &ctx->b_vmask, &ctx->b_gscan, &ctx->b_defer,
-                     &ctx->b_szinteg, &ctx->b_sztotal, &ctx->b_model, &ctx->b_ticket, &ctx->b_poly, &ctx->d_geoM, &ctx->b_present, &ctx->b_mask8, &ctx->b_vis,
-                     &ctx->b_colin, &ctx->b_xscr, &ctx->b_xgeo, &ctx->b_bsigma, &ctx->b_bon, &ctx->b_timed};
-    for (DevBuf *b : all) free_buf(*b);
-    for (int k = 9; k < 21; ++k) free_buf(ctx->b_fout[k]);          // (the match, the probabilities, the track)
-    for (int k = CPOL_COMP_FIELDS + 1; k < 5 * CPOL_COMP_FIELDS + 1; ++k) free_buf(ctx->b_cout[k]);     // (column, column_layers, sum, sum_skipped)
+    for (DevBuf cpol_ctx::*m : WORK_BUFS) free_buf(ctx->*m);       // the per-sweep work buffers (cpol_buffers.h)
+    DevBuf *rest[] = {&ctx->d_H, &ctx->d_V, &ctx->d_geoM, &ctx->b_spectrum, &ctx->b_outwin, &ctx->b_superob, &ctx->b_smom, &ctx->b_smcount,
+                      &ctx->b_smvar, &ctx->b_hstate, &ctx->b_hedges, &ctx->b_cstate, &ctx->b_cedges, &ctx->b_crays, &ctx->b_cplane,
+                      &ctx->b_fsat, &ctx->b_fobs, &ctx->b_oscr, &ctx->b_fmaps, &ctx->b_mstate, &ctx->b_msout, &ctx->b_mstash, &ctx->b_mvobs,
+                      &ctx->b_rvel, &ctx->b_sztotal, &ctx->b_model, &ctx->b_mask8, &ctx->b_vis};
+    for (DevBuf *b : rest) free_buf(*b);
+    for (auto &b : ctx->b_hcounts) free_buf(b);
+    for (auto &b : ctx->b_cout) free_buf(b);
+    for (auto &b : ctx->b_fout) free_buf(b);
     free_buf(ctx->b_ctab);
     free_buf(ctx->b_cwtab);
     for (auto &cp : ctx->cplanes) free_buf(cp.buf);
@@ -1039,11 +1053,10 @@ int cpol_mem_info(cpol_ctx *ctx, size_t *free_bytes, size_t *total_bytes, size_t
     // buffers hold already (a scan that fitted as one sequence the first time fits again: a caller that sizes its
     // batches by this figure groups the same scan the same way on every call)
     {
-        const DevBuf *work[] = {&ctx->b_traj, &ctx->b_wgate, &ctx->b_rayc, &ctx->b_beam, &ctx->b_vals, &ctx->b_mask, &ctx->b_elev,
-                                &ctx->b_coords, &ctx->b_qmelt, &ctx->b_fwmelt, &ctx->b_key, &ctx->b_par, &ctx->b_units,
-                                &ctx->b_perm, &ctx->b_res, &ctx->b_pos, &ctx->b_vn, &ctx->b_proj, &ctx->b_rec, &ctx->b_vmask,
-                                &ctx->b_gscan, &ctx->b_defer, &ctx->b_szinteg};
-        for (const DevBuf *b : work) if (b->p) f += b->cap;
+        for (int w = 0; w < WB_N; ++w) {
+            const DevBuf &b = ctx->*WORK_BUFS[w];
+            if (BUF_ROWS[w].held && b.p) f += b.cap;
+        }
         if (f > t) f = t;
     }
     if (free_bytes) *free_bytes = f;
@@ -1052,8 +1065,7 @@ int cpol_mem_info(cpol_ctx *ctx, size_t *free_bytes, size_t *total_bytes, size_t
         // the arenas cpol_run_sweep sizes by n_sbg (vals, masks, elevation, melting scratch, per-item key / pos /
         // par / rec / perm / res / vn, velocity terms, per-gate weights)
         const size_t n_hyd = (size_t)(ctx->hs.n_hydro > 0 ? ctx->hs.n_hydro : 1), n_vars = (size_t)(ctx->model.n_vars > 0 ? ctx->model.n_vars : 9);
-        *per_gate = n_vars * 4 + 1 + 4 + 8 + 16 + 1 + 8 + 8
-                  + n_hyd * (4 + 4 + CPOL_MAX_PAR * 8 + 16 + 4 + CPOL_N_SZ * 8 + 16);
+        *per_gate = buf_per_gate(n_vars, n_hyd);
     }
     return CPOL_OK;
 }
@@ -3584,14 +3596,57 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         memcpy(set->shape, shape, sizeof shape);
     }
     const double t_tables = now_ns();
-    // ---- work buffers ----
-    if (mode == CPOL_GEOM_HOST_PATHS || ctx->keep_debug || f.prep_paths)
-        ENSURE(ctx->b_traj, (size_t)n_rays * n_v * 3 * ng * sizeof(float));
-    if (f.ray_prep) ENSURE(ctx->b_rayc, ((size_t)n_rays * n_h + n_rays) * 2 * sizeof(double));
+    // ---- work buffers: which, and how large, is decided in cpol_buffers.h; every allocation of the sequence happens here, before
+    // anything of the call is queued, like every argument check above (an error return further down would leave the sweep's
+    // counter set half used; see counters_dirty) ----
+    BufIn bi;
+    bi.n_rays = n_rays; bi.n_gates = ng; bi.n_sub = n_sub; bi.n_h = n_h; bi.n_v = n_v; bi.n_vars = n_vars; bi.n_hydro = n_hyd;
+    bi.n_keys = n_keys; bi.n_vbins = n_vb; bi.mode = mode;
+    bi.keep_debug = ctx->keep_debug; bi.ml = ml; bi.doppler = doppler; bi.dop3 = dop3; bi.broaden = broaden; bi.timed = timed;
+    bi.sub_export = sub_out != nullptr;
+    bi.classify_threads = CPOL_CLASSIFY_THREADS; bi.present_words = CPOL_GATE1_PRESENT != 0;
+    bi.f = f;
+    // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
+    const void *col_src[BUF_MAX_COLS] = {};
+    if (cols) {
+        const void *const rest[6] = {cols->mask, cols->elev, ml ? cols->wgate : nullptr, melt_given ? cols->q_melt : nullptr,
+                                     melt_given ? cols->fw_melt : nullptr, melt_given ? cols->has_melting : nullptr};
+        for (int v = 0; v < n_vars; ++v) col_src[v] = cols->vals[v];
+        for (int k = 0; k < 6; ++k) { col_src[n_vars + k] = rest[k]; bi.col_given[k] = rest[k] != nullptr; }
+        bi.columns = true; bi.inputs_on_device = cols->inputs_on_device != 0;
+    }
+    const BufPlan bp = plan_buffers(bi);
+    const long cnt_stride = bp.cnt_stride, unit_cap = bp.unit_cap;
+    const bool was_dirty = ctx->counters_dirty;          // (the previous sequence was cut short: its rays' tickets may be half taken too)
+    // (a buffer the plan gives 0 bytes is not touched; of the buffers a call always needs none can come out at 0: the argument
+    // checks above refuse n_rays, n_gates, n_sub < 1, and n_keys is the sum of n_e * n_t over at least one staged species)
+    bool replaced[WB_N] = {};
+    for (int w = 0; w < WB_N; ++w) {
+        if (!bp.bytes[w]) continue;
+        DevBuf &b = ctx->*WORK_BUFS[w];
+        void *const was = b.p;
+        ENSURE(b, bp.bytes[w]);
+        replaced[w] = b.p != was;
+    }
+    // the fills of a replaced buffer (BufRow::fill), over its whole capacity; the two counter sets together, over what the call
+    // uses, also when the stride changed or the previous call returned an error after its counting kernel was queued
+    // (counters_dirty -- a failed copy or capture: its set holds counts and the serial did not advance, so the set would be used
+    // again as it is; the memsets are queued behind whatever that call left on the stream)
+    const bool clear_counters = replaced[WB_COUNT] || replaced[WB_TOTALS] || ctx->count_stride != cnt_stride || ctx->counters_dirty;
+    for (int w = 0; w < WB_N; ++w) {
+        if (!bp.bytes[w] || BUF_ROWS[w].fill == FILL_NONE) continue;
+        const bool counter = w == WB_COUNT || w == WB_TOTALS;
+        if (!(counter ? clear_counters : replaced[w] || (w == WB_TICKET && was_dirty))) continue;
+        const DevBuf &b = ctx->*WORK_BUFS[w];
+        HIPCHK(hipMemsetAsync(b.p, BUF_ROWS[w].fill == FILL_FF ? 0xFF : 0, counter ? bp.bytes[w] : b.cap, ctx->stream));
+    }
+    if (clear_counters) { ctx->count_stride = cnt_stride; ctx->counters_dirty = false; }
+    const int par = (int)(ctx->sweep_serial & 1);        // (the serial advances once the sequence is queued)
+    int *const cnt_p = (int *)ctx->b_count.p + par * cnt_stride, *const cnt_next = (int *)ctx->b_count.p + (par ^ 1) * cnt_stride;
+    long long *const tot_p = (long long *)ctx->b_totals.p + par * 4, *const tot_next = (long long *)ctx->b_totals.p + (par ^ 1) * 4;
     // arc distance <= slant range; a margin of 1e-3 for the asin of the 4/3-earth formula
     const double geo_poly_scale = 2.0 / ((p->range0 + (double)(ng - 1) * p->range_step) * 1.001);
     if (f.geo_poly || f.poly_single) {
-        if (f.geo_poly) ENSURE(ctx->b_poly, (size_t)n_rays * n_h * 2 * CPOL_GEO_NP * sizeof(double));
         if (!ctx->d_geoM.p) {
             // Chebyshev-node values -> monomial coefficients (as build_itabs' M), extended precision on the host
             constexpr int NP = CPOL_GEO_NP;
@@ -3632,9 +3687,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         // the per-ray brackets: through a slot of the page-locked staging ring (a copy from the caller's pageable arrays would make the
         // call wait for the stream), one host-to-device copy, skipped when the context's device copy already holds these values
         const size_t nb = (size_t)n_rays * sizeof(int32_t), total = 2 * nb;
-        void *const was = ctx->b_timed.p;
-        ENSURE(ctx->b_timed, total);
-        if (ctx->b_timed.p != was) ctx->timed_shadow.clear();
+        if (replaced[WB_TIMED]) ctx->timed_shadow.clear();
         if (ctx->timed_shadow.size() != total || memcmp(ctx->timed_shadow.data(), mem->ray_state, nb) != 0 ||
             memcmp(ctx->timed_shadow.data() + nb, mem->ray_weight, nb) != 0) {
             ctx->timed_shadow.clear();                           // (not valid until the copy is queued)
@@ -3651,114 +3704,18 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             } catch (...) { ctx->timed_shadow.clear(); }
         }
     }
-    ENSURE(ctx->b_vals, (size_t)n_vars * n_sbg * sizeof(float));
-    ENSURE(ctx->b_mask, (size_t)n_sbg);
-    ENSURE(ctx->b_elev, (size_t)n_sbg * sizeof(float));
-    if (ctx->keep_debug) ENSURE(ctx->b_coords, (size_t)n_sbg * 2 * sizeof(float));
-    if (ml) ENSURE(ctx->b_wgate, (size_t)n_sbg * sizeof(double));
-    ENSURE(ctx->b_qmelt, (size_t)2 * n_sbg * sizeof(float));
-    ENSURE(ctx->b_fwmelt, (size_t)2 * n_sbg * sizeof(double));
-    ENSURE(ctx->b_key, (size_t)n_hyd * n_sbg * sizeof(int));
-    ENSURE(ctx->b_pos, (size_t)n_hyd * n_sbg * sizeof(int));
-    ENSURE(ctx->b_par, (size_t)n_hyd * CPOL_MAX_PAR * n_sbg * sizeof(double));
-    // per set: [n_keys] bucket counts, [n_keys + 2]: items ranked, [n_keys + 3 ...): items on integral tables (count_table_items)
-    const long cnt_stride = n_keys + 3 + CPOL_COUNT_SLOTS;
-    const bool was_dirty = ctx->counters_dirty;          // (the previous sequence was cut short: its rays' tickets may be half taken too)
-    {
-        void *const was = ctx->b_count.p, *const was_t = ctx->b_totals.p;
-        ENSURE(ctx->b_count, (size_t)2 * cnt_stride * sizeof(int));
-        ENSURE(ctx->b_totals, 2 * 4 * sizeof(long long));
-        // (counters_dirty: the previous call returned an error after its counting kernel was queued -- an ENSURE that
-        // found no memory, a failed copy or capture: its set holds counts and the serial did not advance, so the set
-        // would be used again as it is; the memsets are queued behind whatever that call left on the stream)
-        if (ctx->b_count.p != was || ctx->b_totals.p != was_t || ctx->count_stride != cnt_stride || ctx->counters_dirty) {
-            HIPCHK(hipMemsetAsync(ctx->b_count.p, 0, (size_t)2 * cnt_stride * sizeof(int), ctx->stream));
-            HIPCHK(hipMemsetAsync(ctx->b_totals.p, 0, 2 * 4 * sizeof(long long), ctx->stream));
-            ctx->count_stride = cnt_stride;
-            ctx->counters_dirty = false;
-        }
-    }
-    const int par = (int)(ctx->sweep_serial & 1);        // (the serial advances once the sequence is queued)
-    int *const cnt_p = (int *)ctx->b_count.p + par * cnt_stride, *const cnt_next = (int *)ctx->b_count.p + (par ^ 1) * cnt_stride;
-    long long *const tot_p = (long long *)ctx->b_totals.p + par * 4, *const tot_next = (long long *)ctx->b_totals.p + (par ^ 1) * 4;
-    ENSURE(ctx->b_blkranked, (size_t)cdiv(n_sbg, CPOL_CLASSIFY_THREADS) * sizeof(int));
-    ENSURE(ctx->b_rec, (size_t)n_hyd * n_sbg * sizeof(double2));
-    ENSURE(ctx->b_vmask, (size_t)n_sbg);
-    ENSURE(ctx->b_offset, (size_t)2 * n_keys * sizeof(int));        // item and unit offsets
-    // (work units: up to 64 / 128 sorted items each; declared here, sized below once the launch mode is known)
-    long unit_cap = (long)n_hyd * n_sbg / 64 + n_keys + 64;
-    ENSURE(ctx->b_perm, (size_t)n_hyd * n_sbg * sizeof(int));
-    ENSURE(ctx->b_res, (size_t)n_hyd * n_sbg * CPOL_N_SZ * sizeof(double));
-    if (doppler) {
-        ENSURE(ctx->b_vn, (size_t)n_hyd * n_sbg * 2 * sizeof(double));
-        ENSURE(ctx->b_icefirst, (size_t)n_rays * n_sub * sizeof(IceFirst));
-        if (f.rvel_terms) ENSURE(ctx->b_proj, (size_t)n_sbg * sizeof(double));
-    }
-    // (every allocation of the sequence happens before its first launch, like every argument check above: an error return
-    // further down would leave the sweep's counter set half used; see counters_dirty)
-    // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
-    const void *col_src[CPOL_MAX_VARS + 6] = {};
-    size_t col_bytes[CPOL_MAX_VARS + 6] = {};
-    int n_col = 0;
-    if (cols) {
-        const size_t gb = (size_t)n_sbg;
-        for (int v = 0; v < n_vars; ++v) { col_src[n_col] = cols->vals[v]; col_bytes[n_col++] = gb * sizeof(float); }
-        const void *const rest[6] = {cols->mask, cols->elev, ml ? cols->wgate : nullptr, melt_given ? cols->q_melt : nullptr,
-                                     melt_given ? cols->fw_melt : nullptr, melt_given ? cols->has_melting : nullptr};
-        const size_t rest_bytes[6] = {gb, gb * sizeof(float), gb * sizeof(double), 2 * gb * sizeof(float), 2 * gb * sizeof(double),
-                                      (size_t)n_rays * n_sub};
-        for (int k = 0; k < 6; ++k) { col_src[n_col] = rest[k]; col_bytes[n_col++] = rest[k] ? rest_bytes[k] : 0; }
-        if (!cols->inputs_on_device) {
-            size_t total = 0;
-            for (int k = 0; k < n_col; ++k) total += (col_bytes[k] + 255) & ~(size_t)255;
-            ENSURE(ctx->b_colin, total);
-        }
-    }
-    // sub-beam export: the long-form gate kernel's own values / mask / elevation (scratch), the geometry of every sub-beam
-    // (lats, lons, dist, heights, elev) and mask_ml
-    const size_t xa8 = ((size_t)n_sbg * sizeof(double) + 255) & ~(size_t)255, xa4 = ((size_t)n_sbg * sizeof(float) + 255) & ~(size_t)255;
-    const size_t xa1 = ((size_t)n_sbg + 255) & ~(size_t)255;
-    if (sub_out) {
-        ENSURE(ctx->b_xscr, (size_t)n_vars * xa4 + xa1 + xa4);
-        ENSURE(ctx->b_xgeo, 2 * xa8 + 3 * xa4 + xa1);
-    }
-    if (dop3) {
-        ENSURE(ctx->b_beam, (size_t)n_sbg * n_vb * sizeof(float));
-        if (broaden) {
-            ENSURE(ctx->b_bsigma, (size_t)n_sbg * sizeof(double));
-            ENSURE(ctx->b_bon, (size_t)n_rays * n_sub * sizeof(int));
-        }
-    }
     // ---- outputs: where the kernels write each array, and how it reaches the caller ----
     const bool dev = p->outputs_on_device == 1;
     const bool async_host = p->outputs_on_device == 2;    // pinned host buffers, no wait
-    if (f.gate1) {
-        ENSURE(ctx->b_gscan, (size_t)3 * n_rg * sizeof(float));
-        ENSURE(ctx->b_defer, (size_t)n_rg);
-    }
-    if (f.gate1_ray && CPOL_GATE1_PRESENT) {
-        // (the presence words: every one "anything may be here" until k_interp_sweep has written it -- a wavefront none of whose gates
-        // exists leaves its word alone)
-        void *const was = ctx->b_present.p;
-        ENSURE(ctx->b_present, (size_t)n_rays * cdiv(ng, 64) * sizeof(unsigned));
-        if (ctx->b_present.p != was) HIPCHK(hipMemsetAsync(ctx->b_present.p, 0xFF, ctx->b_present.cap, ctx->stream));
-    }
-    if (f.gate1_ray && f.g1r == 3) {
-        void *const was = ctx->b_ticket.p;
-        ENSURE(ctx->b_ticket, (size_t)n_rays * sizeof(int));
-        if (ctx->b_ticket.p != was || was_dirty)                 // (the kernel leaves every ticket at 0 behind it)
-            HIPCHK(hipMemsetAsync(ctx->b_ticket.p, 0, ctx->b_ticket.cap, ctx->stream));
-    }
-    if (f.rare_direct) unit_cap = (long)n_hyd * n_sbg;           // (virtual units: no b_units entries are written)
-    else ENSURE(ctx->b_units, (size_t)unit_cap * sizeof(WorkUnit));
-    const bool want_szi = ctx->keep_debug || f.subsum;
-    if (want_szi) ENSURE(ctx->b_szinteg, (size_t)n_rg * n_hyd * CPOL_N_SZ * sizeof(float));
     const bool want_szt = f.want_szt, want_model = fi.want_model;
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
                                  out->DSPECTRUM, out->mask_sum8, out->visibility};
-    for (int k = 0; k < O_N; ++k) { arr[k].user = (uintptr_t)user_out[k]; own[k] = &ctx->b_out[k]; }
+    constexpr int N_OUT = (int)(sizeof ctx->b_out / sizeof ctx->b_out[0]);      // (the arrays behind O_HGT have buffers of their own names, below)
+    static_assert(N_OUT > O_HGT && N_OUT <= O_N, "b_out: a buffer for each of the first fourteen arrays");
+    for (int k = 0; k < O_N; ++k) arr[k].user = (uintptr_t)user_out[k];
+    for (int k = 0; k < N_OUT; ++k) own[k] = &ctx->b_out[k];
     for (int k = 0; k < 14; ++k) {
         arr[k].bytes = (size_t)n_rg * ((k == O_MASK || k == O_LAT || k == O_LON) ? sizeof(double) : sizeof(float));
         arr[k].produced = !(cols && k >= O_LAT && k <= O_HGT);      // (the columns carry no gate coordinates)
@@ -3891,15 +3848,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     ctx->last_poly_fits = (long)geo_rays * n_h;
     if (cols) {
         // ---- 2'. the caller's columns instead of the interpolation ----
-        const void *src[CPOL_MAX_VARS + 6];
-        size_t off = 0;
-        for (int k = 0; k < n_col; ++k) {
+        const void *src[BUF_MAX_COLS];
+        for (int k = 0; k < bp.n_col; ++k) {
             src[k] = col_src[k];
             if (!col_src[k] || cols->inputs_on_device) continue;
-            void *d = (char *)ctx->b_colin.p + off;
-            HIPCHK(hipMemcpyAsync(d, col_src[k], col_bytes[k], hipMemcpyHostToDevice, st));
+            void *d = (char *)ctx->b_colin.p + bp.col_off[k];
+            HIPCHK(hipMemcpyAsync(d, col_src[k], bp.col_bytes[k], hipMemcpyHostToDevice, st));
             src[k] = d;
-            off += (col_bytes[k] + 255) & ~(size_t)255;
         }
         IngestArgs ig{};
         for (int v = 0; v < n_vars; ++v) ig.src_vals[v] = (const float *)src[v];
@@ -3981,19 +3936,19 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         InterpArgs ix = ia;
         char *const xs = (char *)ctx->b_xscr.p, *const xg = (char *)ctx->b_xgeo.p;
         ix.vals = (float *)xs;
-        ix.mask = (signed char *)(xs + (size_t)n_vars * xa4);
-        ix.elev = (float *)(xs + (size_t)n_vars * xa4 + xa1);
+        ix.mask = (signed char *)(xs + bp.xscr_mask);
+        ix.elev = (float *)(xs + bp.xscr_elev);
         ix.zero_buf = nullptr; ix.zero_buf2 = nullptr;
         ix.coords = nullptr; ix.lats = ix.lons = nullptr; ix.dist = ix.heights = nullptr;
         ix.present = nullptr;
         ix.exact_sub = 1;                         // (the long form: float64 latitude / longitude of every sub-beam)
         ExportArgs xa{};
         xa.lats = (double *)xg;
-        xa.lons = (double *)(xg + xa8);
-        xa.dist = (float *)(xg + 2 * xa8);
-        xa.heights = (float *)(xg + 2 * xa8 + xa4);
-        xa.elev = (float *)(xg + 2 * xa8 + 2 * xa4);
-        signed char *const mlmask = (signed char *)(xg + 2 * xa8 + 3 * xa4);
+        xa.lons = (double *)(xg + bp.xgeo_lons);
+        xa.dist = (float *)(xg + bp.xgeo_dist);
+        xa.heights = (float *)(xg + bp.xgeo_heights);
+        xa.elev = (float *)(xg + bp.xgeo_elev);
+        signed char *const mlmask = (signed char *)(xg + bp.xgeo_mlmask);
         hipLaunchKernelGGL(k_interp_export, dim3((unsigned)(n_rays * n_sub), cdiv(ng, 256)), dim3(256), 0, st, ctx->model, ix, xa);
         if (ml) hipLaunchKernelGGL(k_ml_weights, dim3(n_rays * n_sub), dim3(64), 0, st, ml_args());
         if (f.sub_melt)
@@ -4028,7 +3983,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     fa.sub_mask = (const signed char *)ctx->b_mask.p;
     fa.vals = (const float *)ctx->b_vals.p;
     fa.sub_w = (const double *)ctx->v_subw;
-    fa.sz_integ = want_szi ? (float *)ctx->b_szinteg.p : nullptr;
+    fa.sz_integ = bp.bytes[WB_SZINTEG] ? (float *)ctx->b_szinteg.p : nullptr;
     fa.sz_total = want_szt ? (float *)T[O_SZT] : nullptr;
     fa.ZH = (float *)T[O_ZH]; fa.ZV = (float *)T[O_ZV];
     fa.ZDR = (float *)T[O_ZDR]; fa.KDP = (float *)T[O_KDP];
@@ -4262,8 +4217,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         pa.clk = nullptr;
         pa.ice_force_sum = pk.ice_force_sum;
         if (ctx->keep_debug) {
-            ENSURE(ctx->b_clk, 2048 * 4 * sizeof(long long));
-            HIPCHK(hipMemsetAsync(ctx->b_clk.p, 0, 2048 * 4 * sizeof(long long), st));
+            HIPCHK(hipMemsetAsync(ctx->b_clk.p, 0, bp.bytes[WB_CLK], st));
             pa.clk = (long long *)ctx->b_clk.p;
         }
         // (items listed directly: the units are single items outside the tables, a handful per volume -- a small
@@ -4486,14 +4440,13 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         mix(&t->version, sizeof t->version);
         mix(T, O_N * sizeof *T);
         mix(&ctx->stage_serial, sizeof ctx->stage_serial);
-        void *arena[] = {ctx->b_traj.p, ctx->b_vals.p, ctx->b_mask.p, ctx->b_elev.p, ctx->b_qmelt.p,
-                         ctx->b_fwmelt.p, ctx->b_key.p, ctx->b_pos.p, ctx->b_par.p, (void *)cnt_p,
-                         ctx->b_offset.p, ctx->b_units.p, (void *)tot_p, ctx->b_perm.p,
-                         ctx->b_res.p, ctx->b_vn.p, ctx->b_icefirst.p, ctx->b_wgate.p, ctx->b_blkranked.p, ctx->b_rec.p,
-                         ctx->b_vmask.p, ctx->b_rayc.p, ctx->v_traj_in, ctx->v_geo, ctx->v_subh,
-                         ctx->v_subv, ctx->v_subw, ctx->v_sens, ctx->v_site, ctx->v_nyq,
-                         ctx->v_subsmooth, ctx->v_mlfilter, (void *)st, f.poly_single ? set->poly.p : nullptr, f.gate1_ray ? ctx->b_present.p : nullptr};
-        mix(arena, sizeof arena);
+        // (every work buffer the call sized, the per-ray tables, the stream, the table set's polynomials)
+        int keyed[WB_N];
+        const int n_keyed = buf_key_list(bp, keyed);
+        for (int q = 0; q < n_keyed; ++q) mix(&(ctx->*WORK_BUFS[keyed[q]]).p, sizeof(void *));
+        for (void **v : views) mix(v, sizeof *v);
+        void *const more[] = {(void *)st, f.poly_single ? set->poly.p : nullptr};
+        mix(more, sizeof more);
         // (the launch forms chosen above from state outside *p: a graph captured before the lanes were forked must not keep
         // replaying the four-launch sequence once k_gate1_ray is the default, nor the reverse)
         mix(forms, sizeof forms);
@@ -4514,6 +4467,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             (void)hipGraphDestroy(graph);
             if (ie != hipSuccess) { gexec = nullptr; ctx->err = "cpol_run_sweep: hipGraphInstantiate failed"; return CPOL_ERR_HIP; }
             ctx->graph_key[par] = key;
+            ctx->graph_captures += 1;
         }
         HIPCHK(hipGraphLaunch(gexec, st));
         ctx->last_forms[11] = 1;
@@ -5025,6 +4979,19 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
         if (!dst || max_bytes < (int64_t)sizeof ctx->last_forms) return CPOL_ERR_ARG;
         memcpy(dst, ctx->last_forms, sizeof ctx->last_forms);
         return (int64_t)sizeof ctx->last_forms;
+    }
+    if (!strcmp(name, "graph_captures")) {
+        if (!dst || max_bytes < (int64_t)sizeof ctx->graph_captures) return CPOL_ERR_ARG;
+        memcpy(dst, &ctx->graph_captures, sizeof ctx->graph_captures);
+        return (int64_t)sizeof ctx->graph_captures;
+    }
+    if (!strcmp(name, "work_buffers")) {
+        // the capacity of every per-sweep work buffer in the order of enum WorkBuf (cpol_buffers.h), 0: absent; a test hook like "geo_poly"
+        uint64_t cap[WB_N];
+        if (!dst || max_bytes < (int64_t)sizeof cap) return CPOL_ERR_ARG;
+        for (int w = 0; w < WB_N; ++w) { const DevBuf &b = ctx->*WORK_BUFS[w]; cap[w] = b.p ? b.cap : 0; }
+        memcpy(dst, cap, sizeof cap);
+        return (int64_t)sizeof cap;
     }
     if (!strcmp(name, "host_times")) {
         // host time of cpol_run_sweep by section since the last read (see cpol_ctx::host_ns); reading resets
