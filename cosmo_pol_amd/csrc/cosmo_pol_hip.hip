@@ -3907,8 +3907,17 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             form = stencil_pick(ctx, key, n_rg, &sd, &made);
         }
         const dim3 grid((unsigned)(n_rays * n_sub), cdiv(ng, 256));
-        if (form == 2) hipLaunchKernelGGL(k_interp_replay, grid, dim3(256), 0, st, ctx->model, ia, sd);
-        else if (form == 1) {
+        if (form == 2) {
+            // (the replay with the cube's variable count as a constant -- one gather round for the 1-moment cubes, two of eight
+            // variables for the 2-moment ones, each with and without EDR; every other count keeps the run-time loop)
+            switch (CPOL_GATE1_PRESENT ? 0 : ctx->model.n_vars) {
+            case 9: hipLaunchKernelGGL((k_interp_replay_n<9, 9>), grid, dim3(CPOL_REPLAY_THREADS), 0, st, ctx->model, ia, sd); break;
+            case 10: hipLaunchKernelGGL((k_interp_replay_n<10, 10>), grid, dim3(CPOL_REPLAY_THREADS), 0, st, ctx->model, ia, sd); break;
+            case 15: hipLaunchKernelGGL((k_interp_replay_n<15, 8>), grid, dim3(CPOL_REPLAY_THREADS), 0, st, ctx->model, ia, sd); break;
+            case 16: hipLaunchKernelGGL((k_interp_replay_n<16, 8>), grid, dim3(CPOL_REPLAY_THREADS), 0, st, ctx->model, ia, sd); break;
+            default: hipLaunchKernelGGL(k_interp_replay, grid, dim3(256), 0, st, ctx->model, ia, sd);
+            }
+        } else if (form == 1) {
             hipLaunchKernelGGL(k_interp_record, grid, dim3(256), 0, st, ctx->model, ia, sd);
             stencil_recorded(ctx, made);
         } else hipLaunchKernelGGL(k_interp_sweep, grid, dim3(256), 0, st, ctx->model, ia);

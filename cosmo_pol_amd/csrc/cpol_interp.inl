@@ -389,15 +389,16 @@ struct GateGeom {
 };
 
 // the four neighbour columns of grid cell (i0, i1); shared by gate_geometry and the stencil replay (stencil_load), which keeps (i0, i1)
-__device__ __forceinline__ void gate_cells(const ModelDev &m, int i0, int i1, GateGeom &g)
+__device__ __forceinline__ void gate_cells(int ny, int nx, int i0, int i1, GateGeom &g)
 {
-    int i0a = min(max(i0, 0), m.ny - 1), i0b = min(max(i0 + 1, 0), m.ny - 1);
-    int i1a = min(max(i1, 0), m.nx - 1), i1b = min(max(i1 + 1, 0), m.nx - 1);
-    g.cell[0] = (long)i0a * m.nx + i1a;
-    g.cell[1] = (long)i0a * m.nx + i1b;
-    g.cell[2] = (long)i0b * m.nx + i1a;
-    g.cell[3] = (long)i0b * m.nx + i1b;
+    int i0a = min(max(i0, 0), ny - 1), i0b = min(max(i0 + 1, 0), ny - 1);
+    int i1a = min(max(i1, 0), nx - 1), i1b = min(max(i1 + 1, 0), nx - 1);
+    g.cell[0] = (long)i0a * nx + i1a;
+    g.cell[1] = (long)i0a * nx + i1b;
+    g.cell[2] = (long)i0b * nx + i1a;
+    g.cell[3] = (long)i0b * nx + i1b;
 }
+__device__ __forceinline__ void gate_cells(const ModelDev &m, int i0, int i1, GateGeom &g) { gate_cells(m.ny, m.nx, i0, i1, g); }
 
 // the reciprocals of the four column thicknesses (div32_by); shared likewise
 __device__ __forceinline__ void gate_rz(GateGeom &g)
@@ -1238,6 +1239,244 @@ __global__ __launch_bounds__(256) void k_interp_replay(ModelDev m, InterpArgs a,
     long sbg;
     float e;
     interp_gate<false, false, false, false, 2>(m, a, nullptr, sbg, e, nullptr, nullptr, nullptr, &sd);
+}
+
+// ---- the replay with a compile-time variable count (round 12): two awaited memory rounds per gate instead of six ----
+// k_interp_replay above walks interp_gate's path: s, h | status, e | the rest of the record | variables 0-3 | 4-7 | 8, each round
+// awaited in front of the next, the four float64 reciprocals of gate_rz between the record and the first gather, and -- n_vars being
+// a run-time count -- every trip of the variable loop requested only behind the previous trip's stores.  A replayed gate knows all
+// its record addresses at entry and, once the record is there, the addresses of ALL its model values: per column one contiguous run
+// of 2 n_vars floats (V is [ny][nx][nz][n_vars], the bracketing levels c1, c1 + 1 adjacent).  Here
+//   round 1: the ten rows of the record, requested back to back, one wait;
+//   round 2: the runs of all four columns (NB >= NV: 2 NV floats each; otherwise rounds of NB variables, both levels), requested in
+//            front of a scheduling barrier; gate_rz's reciprocals, dx, dy and h - z2[k] are formed while they travel;
+// then the statements of gate_value4 / gate_value per variable, same order, same types (-ffp-contract=off): the parent's bits by
+// construction (tests/test_gpu_interp_replay.py, bit for bit against a sweep that never replays).  Rows of the record that
+// stencil_store never wrote (class != 0) are loaded and dropped: cell / c1 / z are touched under st_class == 0 alone.
+// Single-beam sweeps only (cpol_forms.h: n_sub == 1, no a.traj / a.coords / a.lats / a.lons), so sub = 0 and the launch order is plain.
+// The host picks <NV, NB> from the cube's variable count at the launch (cosmo_pol_hip.hip); counts without an instantiation take
+// k_interp_replay.  Listing, traces and the A/B: profiles/r12_isa_rounds.txt, profiles/r12_variants.txt.
+#define CPOL_REPLAY_THREADS 256      // the workgroup of k_interp_replay_n: a constant of the kernel AND of its launch
+// What a replayed gate reads of the three kernel arguments, in scalar registers from the entry on.  Each field goes through an empty
+// asm statement that "changes" it (as gate1_species_ops does, cpol_gate.inl): left alone the compiler fetches a field in front of its
+// first use, one awaited scalar round per basic block -- five of them between the entry and the gather.  A pointer that went
+// through such a statement is no longer known to point into global memory: the types say so themselves.
+#define CPOL_RP_GLOBAL __attribute__((address_space(1)))
+typedef float rp_f32x4 __attribute__((ext_vector_type(4)));
+typedef float rp_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef float rp_f32x2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef int rp_i32x2 __attribute__((ext_vector_type(2)));
+struct ReplayOps {
+    const signed char CPOL_RP_GLOBAL *status;
+    const float CPOL_RP_GLOBAL *s, *h, *e, *x, *y;
+    const rp_i32x2 CPOL_RP_GLOBAL *cell, *c1;      // (c1: the four shorts as they lie)
+    const rp_f32x4 CPOL_RP_GLOBAL *z1, *z2;
+    const float CPOL_RP_GLOBAL *V;
+    float CPOL_RP_GLOBAL *vals, *elev, *dist, *heights;
+    signed char CPOL_RP_GLOBAL *mask;
+    int CPOL_RP_GLOBAL *zero_buf, *zero_buf2;
+    int nz, ny, nx, n_gates, n_rays, zero_n, zero_n2, central_sub;
+};
+__device__ __forceinline__ ReplayOps replay_ops(const ModelDev &m, const InterpArgs &a, const StencilDev &sd)
+{
+    ReplayOps o;
+    o.status = (const signed char CPOL_RP_GLOBAL *)sd.status;
+    o.s = (const float CPOL_RP_GLOBAL *)sd.s; o.h = (const float CPOL_RP_GLOBAL *)sd.h; o.e = (const float CPOL_RP_GLOBAL *)sd.e;
+    o.x = (const float CPOL_RP_GLOBAL *)sd.x; o.y = (const float CPOL_RP_GLOBAL *)sd.y;
+    o.cell = (const rp_i32x2 CPOL_RP_GLOBAL *)sd.cell; o.c1 = (const rp_i32x2 CPOL_RP_GLOBAL *)sd.c1;
+    o.z1 = (const rp_f32x4 CPOL_RP_GLOBAL *)sd.z1; o.z2 = (const rp_f32x4 CPOL_RP_GLOBAL *)sd.z2;
+    o.V = (const float CPOL_RP_GLOBAL *)m.V;
+    o.vals = (float CPOL_RP_GLOBAL *)a.vals; o.elev = (float CPOL_RP_GLOBAL *)a.elev;
+    o.dist = (float CPOL_RP_GLOBAL *)a.dist; o.heights = (float CPOL_RP_GLOBAL *)a.heights;
+    o.mask = (signed char CPOL_RP_GLOBAL *)a.mask;
+    o.zero_buf = (int CPOL_RP_GLOBAL *)a.zero_buf; o.zero_buf2 = (int CPOL_RP_GLOBAL *)a.zero_buf2;
+    o.nz = m.nz; o.ny = m.ny; o.nx = m.nx; o.n_gates = a.n_gates; o.n_rays = a.n_rays;
+    o.zero_n = a.zero_n; o.zero_n2 = a.zero_n2; o.central_sub = a.central_sub;
+    asm volatile("" : "+s"(o.status), "+s"(o.s), "+s"(o.h), "+s"(o.e), "+s"(o.x), "+s"(o.y), "+s"(o.cell), "+s"(o.c1), "+s"(o.z1), "+s"(o.z2),
+                 "+s"(o.n_gates), "+s"(o.V), "+s"(o.vals), "+s"(o.elev), "+s"(o.dist), "+s"(o.heights), "+s"(o.mask), "+s"(o.zero_buf), "+s"(o.zero_buf2),
+                 "+s"(o.nz), "+s"(o.ny), "+s"(o.nx), "+s"(o.n_rays), "+s"(o.zero_n), "+s"(o.zero_n2), "+s"(o.central_sub));
+    return o;
+}
+
+template <int N>
+__device__ __forceinline__ void replay_run(const float CPOL_RP_GLOBAL *p, float (&r)[N])
+{
+    constexpr int N4 = N / 4 * 4;
+#pragma unroll
+    for (int j = 0; j < N4; j += 4) {
+        const rp_f32x4u t = *(const rp_f32x4u CPOL_RP_GLOBAL *)(p + j);
+        r[j] = t.x; r[j + 1] = t.y; r[j + 2] = t.z; r[j + 3] = t.w;
+    }
+    if constexpr (N - N4 >= 2) {
+        const rp_f32x2u t = *(const rp_f32x2u CPOL_RP_GLOBAL *)(p + N4);
+        r[N4] = t.x; r[N4 + 1] = t.y;
+    }
+    if constexpr ((N - N4) % 2 == 1) r[N - 1] = p[N - 1];
+}
+
+template <int NV, int NB>
+__device__ __forceinline__ void replay_gate(const ModelDev &m, const InterpArgs &a, const StencilDev &sd)
+{
+    const ReplayOps o = replay_ops(m, a, sd);
+    const int gate = blockIdx.y * CPOL_REPLAY_THREADS + threadIdx.x;
+    const int ray = blockIdx.x;
+    constexpr int sub = 0;
+#ifdef CPOL_INTERP_TRACE
+    unsigned long long itr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    itr[0] = wall_clock64();
+#endif
+    const bool in = gate < o.n_gates;
+    const long sbg = (long)ray * o.n_gates + gate;
+    const long n_sbg = (long)o.n_rays * o.n_gates;
+    // ---- round 1: the whole record (a lane without a gate asks for nothing: the rows end at a multiple of 64 gates) ----
+    int st_class = 3;
+    float s32 = 0.0f, h32 = 0.0f, e32 = 0.0f, gx = 0.0f, gy = 0.0f;
+    rp_i32x2 c01 = {0, 0}, c1 = {0, 0};
+    rp_f32x4 z1 = {0.0f, 0.0f, 0.0f, 0.0f}, z2 = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (in) {
+        st_class = o.status[sbg];
+        s32 = o.s[sbg]; h32 = o.h[sbg]; e32 = o.e[sbg];
+        gx = o.x[sbg]; gy = o.y[sbg];
+        c01 = o.cell[sbg];
+        c1 = o.c1[sbg];
+        z1 = o.z1[sbg]; z2 = o.z2[sbg];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // ... and behind the requests the duty every gate kernel has: the NEXT sweep's counters (clear_counters with the launch's 256
+    // threads as a constant: the general form reads blockDim with a vector load of its own and awaits it at entry)
+    if (o.zero_buf) {
+        const long total = (long)gridDim.x * gridDim.y * CPOL_REPLAY_THREADS;
+        const long first = ((long)blockIdx.x * gridDim.y + blockIdx.y) * CPOL_REPLAY_THREADS + threadIdx.x;
+        for (long i = first; i < o.zero_n; i += total) o.zero_buf[i] = 0;
+        if (o.zero_buf2 && first < o.zero_n2) o.zero_buf2[first] = 0;
+    }
+    if (!in) return;
+    const float qnan = __builtin_nanf("");
+    if (!(s32 == s32) || !(h32 == h32)) {               // no gate here: interp_gate's statements
+        o.mask[sbg] = 1;
+        for (int v = 0; v < NV; ++v) o.vals[(long)v * n_sbg + sbg] = qnan;
+        o.elev[sbg] = 0.0f;
+        if (sub == o.central_sub) {
+            if (o.dist) o.dist[sbg] = qnan;
+            if (o.heights) o.heights[sbg] = qnan;
+        }
+        return;
+    }
+    if (st_class == 2) {                                 // outside the domain: a replayed sweep raises it as well
+        atomicOr(a.error_flag, 1);
+        o.mask[sbg] = 2;
+        for (int v = 0; v < NV; ++v) o.vals[(long)v * n_sbg + sbg] = qnan;
+        o.elev[sbg] = e32;
+        if (sub == o.central_sub) {
+            if (o.dist) o.dist[sbg] = qnan;
+            if (o.heights) o.heights[sbg] = qnan;
+        }
+        return;
+    }
+    ITRACE(itr, 1);                                        // the record has arrived
+    int status = st_class;
+    if (status == 0) {
+        GateGeom g;
+        g.x = gx; g.y = gy;
+        gate_cells(o.ny, o.nx, c01.x, c01.y, g);
+        g.c1[0] = (short)(c1.x & 0xffff); g.c1[1] = (short)(c1.x >> 16);          // StencilC1 as it lies (little endian)
+        g.c1[2] = (short)(c1.y & 0xffff); g.c1[3] = (short)(c1.y >> 16);
+        g.z1[0] = z1.x; g.z1[1] = z1.y; g.z1[2] = z1.z; g.z1[3] = z1.w;
+        g.z2[0] = z2.x; g.z2[1] = z2.y; g.z2[2] = z2.z; g.z2[3] = z2.w;
+        const float CPOL_RP_GLOBAL *col[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) col[k] = o.V + (g.cell[k] * o.nz + g.c1[k]) * NV;
+        float dh[4];
+        float v0 = 0.0f;
+#pragma unroll
+        for (int b0 = 0; b0 < NV; b0 += NB) {
+            constexpr int ONE = NB >= NV;                      // the whole run of a column in one request sequence
+            const int nb = NV - b0 < NB ? NV - b0 : NB;        // (a constant of every unrolled trip)
+            float lo[4][ONE ? 2 * NV : NB], hi[4][ONE ? 1 : NB];
+            // ---- round 2: every model value of the trip, requested before anything is awaited ----
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if constexpr (ONE) replay_run(col[k], lo[k]);
+                else if (nb == NB) { replay_run(col[k] + b0, lo[k]); replay_run(col[k] + NV + b0, hi[k]); }
+                else {
+                    constexpr int NT = NV % NB ? NV % NB : NB;
+                    float tl[NT], th[NT];
+                    replay_run(col[k] + b0, tl); replay_run(col[k] + NV + b0, th);
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) { lo[k][j] = tl[j]; hi[k][j] = th[j]; }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (b0 == 0) {                                     // ... and under them what needs the record alone
+                // (an empty statement the heights pass through: the barrier orders instructions, not the values they need, and
+                // without it the first reciprocals were formed in front of the requests)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(g.z1[k]), "+v"(g.z2[k]) :: "memory");
+                g.dx = 1.0f - g.x;
+                g.dy = 1.0f - g.y;
+                gate_rz(g);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dh[k] = h32 - g.z2[k];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                if (j < nb) {
+                    float val[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {                  // gate_value4 / gate_value, interpolation_c.c:151
+                        const float v1 = lo[k][j];
+                        float v2;
+                        if constexpr (ONE) v2 = lo[k][NV + j];
+                        else v2 = hi[k][j];
+#if CPOL_DIV_AS_PRODUCT
+                        val[k] = v2 - div32_by(v2 - v1, g.rz[k]) * dh[k];
+#else
+                        val[k] = v2 - (v2 - v1) / (g.z1[k] - g.z2[k]) * dh[k];
+#endif
+                    }
+                    // interpolation_c.c:162
+                    const float out = g.dx * g.dy * val[0] + g.x * val[2] * g.dy + g.dx * val[1] * g.y + g.x * g.y * val[3];
+                    if (b0 + j == 0) v0 = out;
+                    o.vals[(long)(b0 + j) * n_sbg + sbg] = out;
+                }
+            }
+        }
+        // the mask born from the VALUES of variable 0 (interp_gate)
+        if (v0 == -9999.0f) status = 1;
+        else if (!(v0 == v0)) status = -1;
+    }
+    if (status != 0) {
+        for (int v = 0; v < NV; ++v) o.vals[(long)v * n_sbg + sbg] = qnan;
+    }
+    ITRACE(itr, 5);                                        // the variables gathered and interpolated
+    o.mask[sbg] = (signed char)status;
+    // elevation folded into [0, 90] for the LUT (doppler_scatter.py:173-176, in place)
+    if (e32 > 90.0f) e32 = 180.0f - e32;
+    if (e32 < 0.0f) e32 = -e32;
+    o.elev[sbg] = e32;
+    if (sub == o.central_sub) {
+        if (o.dist) o.dist[sbg] = s32;
+        if (o.heights) o.heights[sbg] = h32;
+    }
+#ifdef CPOL_INTERP_TRACE
+    {
+        ITRACE(itr, 6);                                    // everything stored
+        const unsigned long w = ((unsigned long)blockIdx.y * gridDim.x + blockIdx.x) * (CPOL_REPLAY_THREADS / 64) + threadIdx.x / 64;
+        const unsigned long long n_ok = (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(status == 0));
+        if ((threadIdx.x & 63) == 0 && w < CPOL_SUBSUM_TRACE_N) {
+            for (int q = 0; q < 7; ++q) g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + q] = itr[q];
+            g_subsum_trace[CPOL_SUBSUM_TRACE_W * w + 7] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15ull) << 32 | n_ok << 40;
+        }
+    }
+#endif
+}
+
+template <int NV, int NB>
+__global__ __launch_bounds__(CPOL_REPLAY_THREADS) void k_interp_replay_n(ModelDev m, InterpArgs a, StencilDev sd)
+{
+    replay_gate<NV, NB>(m, a, sd);
 }
 
 // The geometry of every sub-beam gate (cpol_interp_subbeams): the gate kernel in its long form (a.exact_sub), values into a

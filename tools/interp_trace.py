@@ -3,7 +3,8 @@
    make -C cosmo_pol_amd/csrc clean && make -C cosmo_pol_amd/csrc EXTRA=-DCPOL_INTERP_TRACE && python tools/interp_trace.py [--config c2|c4]
 Every wavefront records the 100-MHz clock -- after waiting for everything it has issued -- at: start, trajectory + grid
 coordinates, topography of the four columns, column 0 bisected, neighbour columns bracketed, variables interpolated, all stored.
-c2: ONE isolated sweep (k_interp_sweep, 2 880 wavefronts); c4: one elevation of the 49-sub-beam volume (k_interp_classify; the first
+c2: ONE isolated sweep (2 880 wavefronts; the fourth of a geometry, so with gate stencils the REPLAYED form: phases 2-4 are empty
+there, 'coords' is the record's round and 'variables' the gather rounds), and with --lanes 3 a sweep among three lanes in flight; c4: one elevation of the 49-sub-beam volume (k_interp_classify; the first
 131 072 wavefronts; the time after 'variables' is the classification of the gate's hydrometeors + the stores)."""
 import argparse
 import contextlib
@@ -52,11 +53,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--config', default='c2')
     ap.add_argument('--tag', default='')
+    ap.add_argument('--lanes', type=int, default=1, help='c2: > 1 also reports a sweep among that many lanes in flight')
     args = ap.parse_args()
     wl = args.config
     conf, hyds, cube, luts = bench.make_inputs(wl, False)
     with contextlib.redirect_stdout(sys.stderr):
-        op = RadarOperator(config=conf, luts=luts, output_variables='only_radar', lanes=1)
+        op = RadarOperator(config=conf, luts=luts, output_variables='only_radar', lanes=args.lanes)
         op.load_model_arrays(cube['data'], cube['zlevels'], cube['proj_info'], cube['resolution'])
     az = np.arange(0, 360, 1.0)
     ng = len(op.constants.RANGE_RADAR)
@@ -69,7 +71,21 @@ def main():
             op.simulate_rays(az, np.full(360, el), device_outputs=outs)
         op.wait()
         torch.cuda.synchronize()
-        report('%s %s el %.1f: one isolated sweep' % (args.tag, wl, el), op._ctx.debug_read('subsum_trace', (N, 8), np.uint64))
+        report('%s %s el %.1f: one isolated sweep (form %d)' % (args.tag, wl, el, op.stencil_state()['form']),
+               op._ctx.debug_read('subsum_trace', (N, 8), np.uint64))
+    if wl == 'c2' and args.lanes > 1:
+        # (the trace array is the library's, not the lane's: every slot holds its last writer)
+        [op._lane(i) for i in range(args.lanes)]
+        slabs = [torch.empty((9, 360, ng), dtype=torch.float32, device='cuda') for _ in range(args.lanes)]
+        louts = [{k: s[i].data_ptr() for i, k in enumerate(bench.RADAR_FIELDS)} for s in slabs]
+        els = [np.full(360, e) for e in bench.C2_ELEVATIONS[:8]]
+        for k in range(64):
+            op.simulate_rays(az, els[k % 8], device_outputs=louts[k % args.lanes], lane=k % args.lanes)
+        for i in range(args.lanes):
+            op.wait(i)
+        torch.cuda.synchronize()
+        report('%s %s: a sweep among %d lanes in flight (the last writer of every slot; form %d)'
+               % (args.tag, wl, args.lanes, op.stencil_state()['form']), op._ctx.debug_read('subsum_trace', (N, 8), np.uint64))
     op.close()
 
 
