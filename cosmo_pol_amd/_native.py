@@ -90,7 +90,7 @@ class RayTables(C.Structure):
 
 
 OUTPUT_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'DELTA_HV', 'PHIDP', 'RHOHV', 'ATT_H', 'ATT_V',
-                 'RVEL', 'mask', 'lats', 'lons', 'dist', 'heights', 'visibility', 'model_vars', 'fractions', 'sz_total',
+                 'RVEL', 'mask', 'species', 'lats', 'lons', 'dist', 'heights', 'visibility', 'model_vars', 'fractions', 'sz_total',
                  'composite', 'histogram', 'DSPECTRUM', 'member_verify', 'mask_sum8', 'spectrum_moments']
 
 
@@ -138,6 +138,17 @@ class SpectrumMoments(C.Structure):
     rule).  fields: bit k = row k of `moments` [8][n_rays * n_gates]."""
     _fields_ = [('fields', C.c_uint32), ('min_bins', C.c_int32), ('min_power', C.c_double), ('moments', C.c_void_p),
                 ('count', C.c_void_p)]
+
+
+SPECIES_FIELDS = ['ZH', 'ZV', 'ZDR', 'KDP', 'RHOHV', 'DELTA_HV', 'ATT_H', 'ATT_V']    # the per-species arrays of a cpol_species
+
+
+class Species(C.Structure):
+    """cpol_species: the radar fields per hydrometeor species, the dominant species and its share (cosmo_pol_amd/species.py
+    states the rule).  A NULL array is not written."""
+    _fields_ = ([(n, C.c_void_p) for n in SPECIES_FIELDS]
+                + [('dominant', C.c_void_p), ('present', C.c_void_p), ('share', C.c_void_p), ('sz', C.c_void_p),
+                   ('n_hydro', C.c_int32), ('pad_', C.c_int32)])
 
 
 HISTOGRAM_FIELDS = SUPEROB_FIELDS                   # the fields of a cpol_histogram: the rows of cpol_superob.count
@@ -244,9 +255,9 @@ class _ObjectsNamed(object):
 
 
 class Outputs(C.Structure):
-    # spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8), histogram (directly before DSPECTRUM), composite (directly before histogram) and fractions (directly before sz_total, in front of the members that are pinned where they are): pointers to a struct, not
+    # species (directly behind mask, in front of every member that is pinned where it is), spectrum_moments (the last of OUTPUT_FIELDS), member_verify (directly before mask_sum8), histogram (directly before DSPECTRUM), composite (directly before histogram) and fractions (directly before sz_total, in front of the members that are pinned where they are): pointers to a struct, not
     # arrays; member_stats, superob likewise: NULL = off; superob stays the last member (cpol_outputs)
-    _fields_ = ([(n, {'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify),
+    _fields_ = ([(n, {'species': C.POINTER(Species), 'spectrum_moments': C.POINTER(SpectrumMoments), 'member_verify': C.POINTER(MemberVerify),
                       'histogram': C.POINTER(Histogram), 'composite': C.POINTER(Composite),
                       'fractions': C.POINTER(Fractions)}.get(n, C.c_void_p))
                  for n in OUTPUT_FIELDS]
@@ -1492,6 +1503,52 @@ class Context(object):
         self._check(rc, 'cpol_debug_read(spectrum_moments_rows)')
         res = {k: out[SPECTRUM_MOMENTS_FIELDS.index(k)] for k in spec.fields}
         res['count'] = cnt
+        return res
+
+    @staticmethod
+    def species_struct(n_hydro):
+        """Species for a call with `n_hydro` staged hydrometeor slots; the output pointers are the caller's."""
+        sp = Species()
+        sp.n_hydro = int(n_hydro)
+        return sp
+
+    def species_fields(self, sz, zh_final, c_zh, c_kdp, c_2w, want=None):
+        """Test hook (cpol_debug_read "species_fields"): k_species alone on caller-supplied rows sz [n_rows, n_gates, n_hydro, 12]
+        (float32) and zh_final [n_rows, n_gates] (float32) with the three float32 constants -> what species.fields_of returns
+        for them: the kernel on rows no sweep produces.  `want`: the arrays to ask for, out of SPECIES_FIELDS, 'dominant',
+        'present', 'share' and 'sz' (default: all); the others stay NULL in the struct.  The result holds the requested arrays,
+        each allocated with a sentinel fill so that an array the library must not touch can be told from one it wrote."""
+        class Hook(C.Structure):
+            _fields_ = [('n_rows', C.c_int32), ('n_gates', C.c_int32), ('sz', C.c_void_p), ('zh_final', C.c_void_p),
+                        ('c_zh', C.c_float), ('c_kdp', C.c_float), ('c_2w', C.c_float), ('pad_', C.c_float), ('sp', Species)]
+        S = np.ascontiguousarray(sz, dtype=np.float32)
+        Z = np.ascontiguousarray(zh_final, dtype=np.float32)
+        if S.ndim != 4 or S.shape[3] != 12 or Z.shape != S.shape[:2]:
+            raise ValueError('species_fields: sz is [n_rows, n_gates, n_hydro, 12], zh_final [n_rows, n_gates]')
+        n_rows, n_gates, n_hydro = S.shape[:3]
+        every = SPECIES_FIELDS + ['dominant', 'present', 'share', 'sz']
+        want = every if want is None else list(want)
+        for k in want:
+            if k not in every:
+                raise ValueError('species_fields: no array %r' % (k,))
+        res = {}
+        h = Hook()
+        h.n_rows, h.n_gates = n_rows, n_gates
+        h.sz, h.zh_final = S.ctypes.data, Z.ctypes.data
+        h.c_zh, h.c_kdp, h.c_2w = float(c_zh), float(c_kdp), float(c_2w)
+        h.sp = self.species_struct(n_hydro)
+        for k in want:
+            if k in SPECIES_FIELDS:
+                res[k] = np.full((n_hydro, n_rows, n_gates), 12345.0, dtype=np.float32)
+            elif k == 'share':
+                res[k] = np.full((n_rows, n_gates), 12345.0, dtype=np.float32)
+            elif k == 'sz':
+                res[k] = np.full(S.shape, 12345.0, dtype=np.float32)
+            else:
+                res[k] = np.full((n_rows, n_gates), 0xA5, dtype=np.uint8)
+            setattr(h.sp, k, res[k].ctypes.data)
+        rc = int(self.lib.cpol_debug_read(self.h, b'species_fields', C.byref(h), C.sizeof(h)))
+        self._check(rc, 'cpol_debug_read(species_fields)')
         return res
 
     @staticmethod

@@ -49,6 +49,7 @@
 #include "cpol_frac_prob.inl"
 #include "cpol_obj.inl"
 #include "cpol_shadow.inl"
+#include "cpol_species.inl"
 
 static_assert(FORMS_RAY_PREP_MIN_SUB == CPOL_RAY_PREP_MIN_SUB && FORMS_TILE_GATES_LOG2 == CPOL_TILE_GATES_LOG2 &&
               FORMS_FINAL_THREADS == CPOL_FINAL_THREADS && (int)FORMS_MODE_GAMMA_EXP == (int)PSD_MODE_GAMMA_EXP &&
@@ -188,6 +189,7 @@ struct cpol_ctx {
     DevBuf b_traj, b_wgate, b_clk, b_rayc, b_poly, d_geoM;
     DevBuf b_beam, b_spectrum, b_outwin, b_superob;
     DevBuf b_smom, b_smcount, b_smvar;     // spectrum moments (cpol_spectrum_moments): the two output arrays; the hook's velocity bins
+    DevBuf b_spout[SP_N];                  // hydrometeor contributions (cpol_species): its output arrays outside a window image and the caller's device memory
     // ensemble statistics (cpol_member_stats): the running state of this context's pass, and the block k_member_finish writes
     // when the outputs are host memory outside a window image
     DevBuf b_mstate, b_msout;
@@ -858,6 +860,7 @@ void cpol_destroy(cpol_ctx *ctx)
                       &ctx->b_rvel, &ctx->b_sztotal, &ctx->b_model, &ctx->b_mask8, &ctx->b_vis};
     for (DevBuf *b : rest) free_buf(*b);
     for (auto &b : ctx->b_hcounts) free_buf(b);
+    for (auto &b : ctx->b_spout) free_buf(b);
     for (auto &b : ctx->b_cout) free_buf(b);
     for (auto &b : ctx->b_fout) free_buf(b);
     free_buf(ctx->b_ctab);
@@ -2606,6 +2609,84 @@ static int hist_hook(cpol_ctx *ctx, const HistHook *hk)
     return hook_finish(ctx, arr, own, [&](void *const *T) { return hist_launch(ctx, &hk->h, pl, in, y, y_gates, (long)n, hk->n_gates, T, ctx->stream); });
 }
 
+// ---- hydrometeor contributions (cpol_species, k_species in cpol_species.inl): the checks and the launch, shared by the launch
+// sequence and the test hook ----
+// every refusal of a cpol_species for a call of n_rg gates and n_hyd staged slots; queues nothing.  arr[SP_N]: the caller's arrays
+// for the placement plan (cpol_place.h): arrays of the sweep itself, each with a grow-only buffer of its own, made only when asked for
+static int species_plan(cpol_ctx *ctx, const cpol_species *sp, long n_rg, int n_hyd, PlaceArray *arr)
+{
+    auto bad = [&](const char *why) { ctx->err = std::string("cpol_species: ") + why; return CPOL_ERR_ARG; };
+    void *const f[SP_N] = {sp->ZH, sp->ZV, sp->ZDR, sp->KDP, sp->RHOHV, sp->DELTA_HV, sp->ATT_H, sp->ATT_V, sp->dominant, sp->present,
+                           sp->share, sp->sz};
+    bool any = false;
+    for (int k = 0; k < SP_N; ++k) any = any || f[k] != nullptr;
+    if (!any) return bad("every output pointer is NULL");
+    if (sp->n_hydro != n_hyd) return bad("n_hydro must equal the staged hydrometeor slots");
+    for (int k = 0; k < SP_N; ++k) {
+        arr[k] = PlaceArray{};
+        arr[k].user = (uintptr_t)f[k];
+        arr[k].bytes = k < SP_FIELDS ? (size_t)n_hyd * n_rg * sizeof(float) : k == SP_SHARE ? (size_t)n_rg * sizeof(float)
+                     : k == SP_SZ ? (size_t)n_rg * n_hyd * CPOL_N_SZ * sizeof(float) : (size_t)n_rg;
+        arr[k].produced = f[k] != nullptr;
+        arr[k].product = PLACE_SWEEP;
+    }
+    return CPOL_OK;
+}
+
+// sz_integ [n_rg][n_hyd][12] and zh_final [n_rg]: device arrays; T: where the kernel writes (NULL: not asked for).  ONE kernel;
+// the rows themselves, when asked for, are a device-to-device copy
+static int species_launch(cpol_ctx *ctx, const float *sz_integ, const float *zh_final, void *const T[SP_N], long n_rg, int n_hyd,
+                          float c_zh, float c_kdp, float c_2w, hipStream_t st)
+{
+    SpeciesArgs sa{};
+    sa.sz_integ = sz_integ; sa.zh_final = zh_final;
+    bool any = false;
+    for (int k = 0; k < SP_FIELDS; ++k) { sa.f[k] = (float *)T[k]; any = any || T[k]; }
+    sa.dominant = (unsigned char *)T[SP_DOMINANT]; sa.present = (unsigned char *)T[SP_PRESENT]; sa.share = (float *)T[SP_SHARE];
+    any = any || sa.dominant || sa.present || sa.share;
+    sa.n_rg = n_rg; sa.n_hydro = n_hyd;
+    sa.c_zh = c_zh; sa.c_kdp = c_kdp; sa.c_2w = c_2w;
+    if (any) {
+        hipLaunchKernelGGL(k_species, dim3((unsigned)cdiv(n_rg, (long)CPOL_SPECIES_THREADS)), dim3(CPOL_SPECIES_THREADS), 0, st, sa);
+        HIPCHK(hipGetLastError());
+    }
+    if (T[SP_SZ]) HIPCHK(hipMemcpyAsync(T[SP_SZ], sz_integ, (size_t)n_rg * n_hyd * CPOL_N_SZ * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return CPOL_OK;
+}
+
+// The test hook cpol_debug_read "species_fields": k_species alone on caller-supplied rows (host memory in, host memory out,
+// blocking) -- the kernel on rows no sweep produces (zeros of either sign, infinities, ties, empty and censored gates).
+struct SpeciesHook {
+    int32_t n_rows, n_gates;
+    const float *sz;                        // [n_rows * n_gates][sp.n_hydro][12]
+    const float *zh_final;                  // [n_rows * n_gates]
+    float c_zh, c_kdp, c_2w, pad_;
+    cpol_species sp;                        // host output pointers
+};
+
+static int species_hook(cpol_ctx *ctx, const SpeciesHook *hk)
+{
+    if (hk->n_rows < 1 || hk->n_gates < 1 || (long)hk->n_rows * hk->n_gates >= (1L << 31) || hk->sp.n_hydro < 1 ||
+        hk->sp.n_hydro > CPOL_MAX_HYDRO || !hk->sz || !hk->zh_final) {
+        ctx->err = "species_fields: bad shape (n_rows, n_gates >= 1, n_hydro in 1 ... CPOL_MAX_HYDRO) or a NULL input";
+        return CPOL_ERR_ARG;
+    }
+    const long n = (long)hk->n_rows * hk->n_gates;
+    const int n_hyd = hk->sp.n_hydro;
+    PlaceArray arr[SP_N];
+    int rc = species_plan(ctx, &hk->sp, n, n_hyd, arr);
+    if (rc != CPOL_OK) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, ctx->b_szinteg, hk->sz, (size_t)n * n_hyd * CPOL_N_SZ * sizeof(float))) != CPOL_OK) return rc;
+    if ((rc = upload(ctx, ctx->b_out[0], hk->zh_final, (size_t)n * sizeof(float))) != CPOL_OK) return rc;
+    DevBuf *own[SP_N];
+    for (int k = 0; k < SP_N; ++k) own[k] = &ctx->b_spout[k];
+    return hook_finish(ctx, arr, own, [&](void *const *T) {
+        return species_launch(ctx, (const float *)ctx->b_szinteg.p, (const float *)ctx->b_out[0].p, T, n, n_hyd, hk->c_zh, hk->c_kdp, hk->c_2w,
+                              ctx->stream);
+    });
+}
+
 // ---- gridded composites (cpol_composite, k_comp and k_comp_finish in cpol_comp.inl): the checks (cpol_comp.h), the pass and the
 // launches, shared by the launch sequence and the test hook ----
 #ifndef CPOL_COMP_COMBINE
@@ -3343,7 +3424,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     // (cpol_products.h) in the one slot range behind them, the fractions' behind the composite's
     enum { O_ZH, O_ZV, O_ZDR, O_KDP, O_DHV, O_PHIDP, O_RHOHV, O_ATTH, O_ATTV, O_MASK, O_LAT, O_LON,
            O_DIST, O_HGT, O_RVEL, O_MODEL, O_SZT, O_SPEC, O_MASK8, O_VIS, O_N, A_PR = O_N,
-           PR_MAX = std::max({(int)SO_N, (int)MS_N, (int)SM_N, (int)CPOL_HIST_FIELDS, (int)CP_N + (int)FR_N}), A_N = A_PR + PR_MAX };
+           PR_MAX = std::max({(int)SO_N, (int)MS_N, (int)SM_N, (int)CPOL_HIST_FIELDS, (int)CP_N + (int)FR_N, (int)SP_N}), A_N = A_PR + PR_MAX };
     static_assert(A_N <= PLACE_MAX_ARRAYS, "cpol_place.h: PLACE_MAX_ARRAYS");
     PlaceArray arr[A_N];
     DevBuf *own[A_N] = {};         // outside the window image and the caller's device memory every array of the sweep keeps a grow-only buffer of its own
@@ -3357,6 +3438,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const cpol_histogram *const hg = out->histogram;
     const cpol_composite *const cp = out->composite;
     const cpol_fractions *const fr = out->fractions;                // (the neighbourhood verification of the composite)
+    const cpol_species *const sp = out->species;
     SuperobPlan so_pl{};
     MemberStatsPlan ms_pl{};
     HistPlan hg_pl;
@@ -3395,6 +3477,10 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
         frac_place(fr, fr_pl, ob_pl, arr + A_PR + CP_N);
         break;
     }
+    case PRODUCT_SPECIES:
+        rc = species_plan(ctx, sp, n_rg, n_hyd, arr + A_PR);
+        for (int k = 0; k < SP_N; ++k) own[A_PR + k] = &ctx->b_spout[k];
+        break;
     }
     if (rc != CPOL_OK) return rc;
     if (cq.refuse_after_plan) { ctx->err = cq.refuse_after_plan; return CPOL_ERR_ARG; }
@@ -3458,6 +3544,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     fi.lanes = ctx->parent ? ctx->parent->n_children : ctx->n_children;
     fi.scan_form = CPOL_SCAN_FORM;
     fi.shadow = shadow;
+    fi.want_species = cq.product == PRODUCT_SPECIES;       // (the general launch sequence: it alone forms the per-species rows)
     fi.n_hydro = n_hyd;
     for (int j = 0; j < n_hyd; ++j) {
         const cpol_hydro_desc &d = ctx->hs.h[j].d;
@@ -3604,6 +3691,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     bi.n_keys = n_keys; bi.n_vbins = n_vb; bi.mode = mode;
     bi.keep_debug = ctx->keep_debug; bi.ml = ml; bi.doppler = doppler; bi.dop3 = dop3; bi.broaden = broaden; bi.timed = timed;
     bi.sub_export = sub_out != nullptr;
+    bi.want_species = fi.want_species;
     bi.classify_threads = CPOL_CLASSIFY_THREADS; bi.present_words = CPOL_GATE1_PRESENT != 0;
     bi.f = f;
     // columns: where k_columns_ingest reads each input (host inputs: a device staging area, one copy per array)
@@ -3708,6 +3796,8 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     const bool dev = p->outputs_on_device == 1;
     const bool async_host = p->outputs_on_device == 2;    // pinned host buffers, no wait
     const bool want_szt = f.want_szt, want_model = fi.want_model;
+    // the float32 constants of the final stage, c_zh, c_kdp, c_2w: FinalArgs takes them, and so does k_species behind the sequence
+    const float fa_c[3] = {(float)p->c_zh, (float)(1e-3 * (180.0 / 3.14159265358979323846) * p->wavelength), (float)(2 * p->wavelength)};
     void *const user_out[O_N] = {out->ZH, out->ZV, out->ZDR, out->KDP, out->DELTA_HV, out->PHIDP,
                                  out->RHOHV, out->ATT_H, out->ATT_V, out->mask, out->lats, out->lons,
                                  out->dist, out->heights, out->RVEL, out->model_vars, out->sz_total,
@@ -4002,9 +4092,7 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
     fa.mask8 = (signed char *)T[O_MASK8];
     fa.model_vars = want_model ? (double *)T[O_MODEL] : nullptr;
     fa.n_rays = n_rays; fa.n_gates = ng; fa.n_sub = n_sub; fa.n_hydro = n_hyd; fa.n_vars = n_vars;
-    fa.c_zh = (float)p->c_zh;
-    fa.c_kdp = (float)(1e-3 * (180.0 / 3.14159265358979323846) * p->wavelength);
-    fa.c_2w = (float)(2 * p->wavelength);
+    fa.c_zh = fa_c[0]; fa.c_kdp = fa_c[1]; fa.c_2w = fa_c[2];
     double sum_w = 0;
     for (int s = 0; s < n_sub; ++s) sum_w += t->sub_w[s];
     fa.sum_w = sum_w;
@@ -4517,6 +4605,9 @@ static int run_sequence(cpol_ctx *ctx, const cpol_sweep_params *p, const cpol_ra
             rc = frac_launch(ctx, fr, fr_pl, ob_pl, (const float *)pr_T[fr_pl.field] + fr_pl.plane_first, fr_pl.plane_stride, p->outputs_on_device == 0,
                              pr_T + CP_N, st);
         break;
+    case PRODUCT_SPECIES:          // ONE kernel, on the per-species rows and the delivered ZH: behind the range scans and the cut
+        rc = species_launch(ctx, (const float *)ctx->b_szinteg.p, (const float *)T[O_ZH], pr_T, n_rg, n_hyd, fa_c[0], fa_c[1], fa_c[2], st);
+        break;
     }
     if (rc != CPOL_OK) return rc;
     // ---- outputs that the kernels did not write in place ----
@@ -4925,6 +5016,10 @@ int64_t cpol_debug_read(cpol_ctx *ctx, const char *name, void *dst, int64_t max_
     if (!strcmp(name, "histogram_fields")) {        // a CONTROL name: dst points to a HistHook
         if (!dst || max_bytes < (int64_t)sizeof(HistHook)) { ctx->err = "cpol_debug_read(histogram_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
         return hist_hook(ctx, (const HistHook *)dst);
+    }
+    if (!strcmp(name, "species_fields")) {          // a CONTROL name: dst points to a SpeciesHook
+        if (!dst || max_bytes < (int64_t)sizeof(SpeciesHook)) { ctx->err = "cpol_debug_read(species_fields): dst = the hook's struct"; return CPOL_ERR_ARG; }
+        return species_hook(ctx, (const SpeciesHook *)dst);
     }
     if (!strcmp(name, "histogram_stretch")) {
         if (!dst || max_bytes < (int64_t)sizeof(int32_t)) return CPOL_ERR_ARG;

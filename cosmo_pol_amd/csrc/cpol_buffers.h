@@ -97,7 +97,8 @@ struct BufIn {
     bool columns = false, inputs_on_device = false;
     bool col_given[6] = {false, false, false, false, false, false};    // mask, elev, wgate, q_melt, fw_melt, has_melting as the call reads them
     bool sub_export = false;
-    int classify_threads = 0;                  // CPOL_CLASSIFY_THREADS of the build
+    bool want_species = false;                 // cpol_outputs.species: k_species reads the per-species rows
+    int classify_threads = 0;                 // CPOL_CLASSIFY_THREADS of the build
     bool present_words = false;                // CPOL_GATE1_PRESENT of the build
     Forms f;
 };
@@ -174,7 +175,7 @@ inline BufPlan plan_buffers(const BufIn &in)
     if (f.gate1) { b[WB_GSCAN] = 3 * n_rg * sizeof(float); b[WB_DEFER] = n_rg; }
     if (f.gate1_ray && in.present_words) b[WB_PRESENT] = n_rays * ((ng + 63) / 64) * sizeof(unsigned);
     if (f.gate1_ray && f.g1r == 3) b[WB_TICKET] = n_rays * sizeof(int);
-    if (in.keep_debug || f.subsum) b[WB_SZINTEG] = n_rg * n_hyd * CPOL_N_SZ * sizeof(float);
+    if (in.keep_debug || f.subsum || in.want_species) b[WB_SZINTEG] = n_rg * n_hyd * CPOL_N_SZ * sizeof(float);
     if (in.keep_debug && !in.sub_export) b[WB_CLK] = BUF_CLK_BYTES;      // (the export stops before the PSD stage)
     return pl;
 }

@@ -139,6 +139,7 @@ struct FormIn {
     int timing = 0, lanes = 0, nz = 0;
     int scan_form = 0;                 // CPOL_SCAN_FORM of the build (reported, decides nothing)
     bool shadow = false;               // cpol_sweep_params.terrain_shadow: k_terrain_shadow between the interpolation and the classification
+    bool want_species = false;         // cpol_outputs.species: the per-species rows sz_integ are kept for k_species
     int n_hydro = 0;
     FormSpecies s[CPOL_MAX_HYDRO];
 };
@@ -238,8 +239,12 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
     // launches of the integrating flavours cost more than the two bucket launches they replace (C3 sweep at
     // 3 deg: 203 us this way against 188; the kernel handles them -- CPOL_GATE1=2 forces it, tests do).
     // (columns with given melting fields: k_classify's GIVEN form; the single-beam kernels diagnose melting themselves)
+    // (hydrometeor contributions, FormIn::want_species: the single-beam kernels keep an absent species as 0.f in registers and never
+    // form the NaN-marked rows sz_integ[gate][species][12] that k_species reads; final_gate (k_final) and k_subbeam_sum do.  Such a
+    // call takes the general sequence, exactly what CPOL_GATE1=0 gives: no gate1, and with it no gate1_species, gate1_ray or
+    // fused_gate1, which all hang on it.  Every other rule is untouched.)
     f.gate1 = k.gate1 != 0 && k.subsum != 0 && n_sub == 1 && !dbg && !dop3 && !in.ml && !in.melt_given && !sub_out &&
-              f.all_tab && (k.gate1 == 2 || !f.any_2d);
+              f.all_tab && (k.gate1 == 2 || !f.any_2d) && !in.want_species;
     if (f.gate1) f.final_inplace = true;       // (k_final's recomputed gates take the table items from their records)
     // k_interp_gate1 (CPOL_FUSE_GATE1=1, not the default): the single-beam kernel interpolates its gates too.  Measured: the
     // isolated C2 sweep 95.4 -> 88.6 us (one lane back to back: 70 -> 62 us per sweep), but with three lanes in flight 42.2 ->
@@ -401,7 +406,7 @@ inline Forms choose_forms(const FormIn &in, const Knobs &k, const ProcessKnobs &
     // The launch sequence as a HIP graph (CPOL_USE_GRAPH=1): with device outputs and nothing to upload it is captured and
     // replayed while the arguments stay the same (one graph launch instead of ten kernel launches).
     f.graphable = k.use_graph && in.outputs_on_device == 1 && in.timing == 0 && !dbg && mode != CPOL_GEOM_HOST_PATHS && !cols && !sub_out &&
-                  !mem && !dop3 && in.reuse && !f.want_szt && !in.want_model && !in.shadow;
+                  !mem && !dop3 && in.reuse && !f.want_szt && !in.want_model && !in.shadow && !in.want_species;
     return f;
 }
 

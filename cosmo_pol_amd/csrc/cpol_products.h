@@ -1,6 +1,6 @@
 // cpol_products.h -- which product a call carries behind its launch sequence, or why it is refused: A CALL CARRIES AT MOST ONE of
-// superobservations, ensemble statistics (member_verify rides on them), spectrum moments, sweep histograms and gridded composites
-// (fractions, with its objects, rides on them).  Decided once per call by call_product() from the entry point and the pointers of
+// superobservations, ensemble statistics (member_verify rides on them), spectrum moments, sweep histograms, gridded composites
+// (fractions, with its objects, rides on them) and hydrometeor contributions.  Decided once per call by call_product() from the entry point and the pointers of
 // cpol_outputs.  Plain C++ without HIP types, so that a host test can include it (tests/c_host/products_check.cpp,
 // tests/test_call_product_cpu.py pin every pointer set at every entry point without a GPU).  run_sequence (cosmo_pol_hip.hip)
 // gives the one product the one slot range of the call's array list and runs its *_plan and *_launch alone.
@@ -9,7 +9,7 @@
 #include "../../include/cosmo_pol_amd.h"
 
 enum { CALL_SWEEP = 0, CALL_MEMBERS, CALL_TIMED, CALL_COLUMNS };      // cpol_run_sweep, cpol_run_sweep_members (time_blend 0, 1), cpol_run_columns
-enum { PRODUCT_NONE = 0, PRODUCT_SUPEROB, PRODUCT_MEMBER_STATS, PRODUCT_SPECTRUM_MOMENTS, PRODUCT_HISTOGRAM, PRODUCT_COMPOSITE };
+enum { PRODUCT_NONE = 0, PRODUCT_SUPEROB, PRODUCT_MEMBER_STATS, PRODUCT_SPECTRUM_MOMENTS, PRODUCT_HISTOGRAM, PRODUCT_COMPOSITE, PRODUCT_SPECIES };
 
 struct CallProduct {
     int product = PRODUCT_NONE;
@@ -22,7 +22,7 @@ struct CallProduct {
 inline CallProduct call_product(int entry, const cpol_outputs &o)
 {
     const bool so = o.superob, ms = o.member_stats, mv = o.member_verify, sm = o.spectrum_moments, hg = o.histogram, cp = o.composite,
-               fr = o.fractions;
+               fr = o.fractions, sp = o.species;
     CallProduct r;
     const auto refuse = [&](const char *why) { (r.product == PRODUCT_NONE ? r.refuse : r.refuse_after_plan) = why; return r; };
     if (entry == CALL_COLUMNS) {
@@ -34,6 +34,10 @@ inline CallProduct call_product(int entry, const cpol_outputs &o)
         if (sm) return refuse("cpol_run_columns: spectrum moments (outputs->spectrum_moments) are taken by cpol_run_sweep");
         if (ms) return refuse("cpol_run_columns: ensemble statistics (outputs->member_stats) are taken by cpol_run_sweep and cpol_run_sweep_members");
         if (mv) return refuse("cpol_run_columns: ensemble verification (outputs->member_verify) is taken by cpol_run_sweep and cpol_run_sweep_members");
+        if (sp) {
+            r.at_entry = true;
+            return refuse("cpol_run_columns: hydrometeor contributions (outputs->species) are taken by cpol_run_sweep and a time-blended cpol_run_sweep_members");
+        }
         return r;
     }
     if (sm && entry != CALL_SWEEP) {
@@ -59,5 +63,13 @@ inline CallProduct call_product(int entry, const cpol_outputs &o)
     if (hg) r.product = PRODUCT_HISTOGRAM;          // (alone but for a stray `fractions`: the refusals above)
     if (cp) r.product = PRODUCT_COMPOSITE;
     else if (fr) return refuse("cpol_fractions: needs a composite (outputs->composite) in the same call");
+    // hydrometeor contributions: their refusals stand at the END of the order, so that a call with several faults reports what it
+    // always reported; a pointer set without `species` decides exactly as before
+    if (sp) {
+        if (entry == CALL_MEMBERS)
+            return refuse("cpol_run_sweep_members: hydrometeor contributions (outputs->species) are taken by cpol_run_sweep and by a time-blended call, not by the ensemble form");
+        if (r.product != PRODUCT_NONE) return refuse("cpol_species: not together with another product in one call");
+        r.product = PRODUCT_SPECIES;
+    }
     return r;
 }

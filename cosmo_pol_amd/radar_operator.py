@@ -31,6 +31,7 @@ from . import ensemble_verify as EV
 from . import spectrum_moments as SM
 from . import superob as SO
 from . import histogram as HG
+from . import species as SP
 from . import composite as CP
 from . import neighbourhood as NB
 from . import objects as OB
@@ -1461,10 +1462,12 @@ class RadarOperator(object):
             keep = list(keep) + alive
         if device_outputs is not None:
             for k, ptr in device_outputs.items():
-                if k not in _PRODUCT_OUTPUTS:     # an array of the sweep itself (one look-up, however many products there are)
+                # an array of the sweep itself (one look-up, however many products there are); a dict is some product's entry
+                # (`species` is listed in no table: its key is its product's name)
+                if k not in _PRODUCT_OUTPUTS and not isinstance(ptr, dict):
                     setattr(o, k, ptr)
                 elif product is None or product.name != k:
-                    raise ValueError('device_outputs[%r] without %s' % (k, _PRODUCT_OUTPUTS[k]))
+                    raise ValueError('device_outputs[%r] without %s' % (k, _PRODUCT_OUTPUTS.get(k, 'its product (%s=)' % k)))
                 else:
                     product.bind_device(ptr)
         else:
@@ -2667,6 +2670,53 @@ class RadarOperator(object):
         """The sweeps of get_RHI with spectrum moments: one result per azimuth (see get_PPI_moments)."""
         _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
         return self._moments_sweeps(sweeps, moments, keep_spectrum)
+
+    # ------------------------------------------------------------------ hydrometeor contributions
+    # (replaces in the reference: nothing -- it folds the per-species sums and hands back the totals; its users re-run the sweep
+    # once per species with the others zeroed)
+    def _species_product(self, spec, keep_gates):
+        if not self._check_ready():
+            raise ValueError('no model loaded')
+        return SP.Contributions(spec, self._staged_hydro, keep_gates, self.distributed)
+
+    def simulate_rays_species(self, azimuths, elevations, spec, keep_gates=True, device_outputs=None, lane=0, pinned=False):
+        """simulate_rays handing back HYDROMETEOR CONTRIBUTIONS: `spec` is a species.Species, and the result gains
+        res['species'] = {'names': the species in slot order, one float32 [n_hydro, n_rays, n_gates] array per requested field
+        (what the species alone gives: linear units, NaN where it has no item or the gate is censored; ZDR is the intrinsic
+        ratio, not attenuated), 'dominant' (uint8, the slot with the largest ZH, 255: none), 'present' (uint8, bit j: slot j
+        contributes), 'share' (float32, the dominant species' part of the sum of the species' ZH), and with `raw` 'sz'
+        [n_rays, n_gates, n_hydro, 12]: the per-species sums themselves} -- made on the device behind the sweep's kernels
+        (species.fields_of states the rule, and the arrays are exactly its result on the call's own 'sz' and ZH).  The per-gate
+        arrays of the call have the bits of simulate_rays; the call takes the general launch sequence (a single-beam sweep gives
+        up its fast kernels: they do not form the per-species rows).  Without `keep_gates` no per-gate radar field is produced for
+        the host or copied.  `device_outputs`: its entry 'species' is {array name: device pointer}.  (A method of its own: the
+        keyword list of simulate_rays is pinned.)  ValueError for what the library refuses; NotImplementedError with a process
+        group, for spaceborne geometry and for ensemble calls."""
+        return self._simulate_rays(azimuths, elevations, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                   product=self._species_product(spec, keep_gates))
+
+    def simulate_rays_at_species(self, azimuths, elevations, times, spec, keep_gates=True, device_outputs=None, lane=0, pinned=False):
+        """simulate_rays_at handing back hydrometeor contributions: `spec` and `keep_gates` as for simulate_rays_species
+        (ValueError when the rays fall into several groups of states)."""
+        return self._simulate_rays_at(azimuths, elevations, times, device_outputs=device_outputs, lane=lane, pinned=pinned,
+                                      product=self._species_product(spec, keep_gates))
+
+    def _species_sweeps(self, sweeps, spec, keep_gates):
+        """One pinned call per sweep over the lanes, one wait at the end: every sweep carries the bits of its own
+        simulate_rays_species(..., spec)."""
+        return self._over_lanes(sweeps, lambda az, el, lane: self.simulate_rays_species(az, el, spec, keep_gates=keep_gates,
+                                                                                        pinned=True, lane=lane))
+
+    def get_PPI_species(self, elevations, spec, azimuths=None, az_step=None, az_start=0, az_stop=359, keep_gates=True):
+        """The sweeps of get_PPI with hydrometeor contributions: a list with one simulate_rays_species(..., spec) result per
+        elevation (res['species']), the sweeps spread over the lanes."""
+        _, _, sweeps = self._ppi_sweeps(elevations, azimuths, az_step, az_start, az_stop)
+        return self._species_sweeps(sweeps, spec, keep_gates)
+
+    def get_RHI_species(self, azimuths, spec, elevations=None, elev_step=None, elev_start=0, elev_stop=90, keep_gates=True):
+        """The sweeps of get_RHI with hydrometeor contributions: one result per azimuth (see get_PPI_species)."""
+        _, _, sweeps = self._rhi_sweeps(azimuths, elevations, elev_step, elev_start, elev_stop)
+        return self._species_sweeps(sweeps, spec, keep_gates)
 
     # ------------------------------------------------------------------ ensemble statistics scans
     def _ensemble_stats_sweeps(self, sweeps, stats, members, observations=None):

@@ -1024,13 +1024,55 @@ typedef struct cpol_fractions_ensemble {
  * should believe they were shadowed); visibility with per-gate weights (integration scheme 'ml').
  * cpol_debug_read "terrain_shadow_rows" runs k_terrain_shadow alone on caller arrays (a test hook, see cpol_debug_read). */
 
+/* Hydrometeor contributions: per gate and per hydrometeor slot the radar fields that the species ALONE gives, which species are
+ * present, which one dominates ZH and by what share.  Replaces in the reference: nothing (it folds the per-species sums with
+ * np.nansum(sz_integ, axis=1), doppler_scatter.py:400, and hands back the totals; its users re-run the sweep once per species).
+ * Pointed to by cpol_outputs.species; honoured by cpol_run_sweep and by a time-blended cpol_run_sweep_members.
+ * INPUT per gate: the rows sz_integ[gate][j][0 .. 11] of the call, float32, j = 0 .. n_hydro-1 in slot order -- the sub-beam sums
+ * of species j as k_final / k_subbeam_sum form them, a row of NaNs where the species has no item at the gate -- and ZHf, the
+ * call's own ZH of the gate as delivered, after the range scans and the sensitivity cut.  The constants are the launch
+ * sequence's: c_zh = (float)p->c_zh, c_kdp = (float)(1e-3 * (180 / pi) * p->wavelength), c_2w = (float)(2 * p->wavelength).
+ * RULE per gate and species j, t[c] = the row's column c; every operation ONE float32 operation (no contraction), in this order:
+ *     t[c] == 0.0f (either sign) becomes NaN                                        (quirk Q5, as the totals apply it)
+ *     two_pi = (float)(2 pi); b = t0 - t1 - t2 + t3; cc = t0 + t1 + t2 + t3         (left to right)
+ *     ZH_j = c_zh * (two_pi * b);  ZV_j = c_zh * (two_pi * cc)
+ *     ZDR_j = (two_pi * b) / (two_pi * cc)       the INTRINSIC ratio: the total's ZDR is attenuated, a species' ZDR is not
+ *     KDP_j = c_kdp * (t10 - t8)
+ *     ATT_H_j = 4.343e-3f * (c_2w * t11);  ATT_V_j = 4.343e-3f * (c_2w * t9)
+ *     RHOHV_j = sqrtf(((t4 + t7) * (t4 + t7) + (t6 - t5) * (t6 - t5)) / (b * cc))
+ *     DELTA_HV_j = (float)atan2((double)(t5 - t6), (double)(-t4 - t7))
+ * CENSORING: where ZHf is NaN, ZH_j, ZV_j, ZDR_j, KDP_j and RHOHV_j become NaN for every j; ATT_H_j, ATT_V_j and DELTA_HV_j keep
+ * their values (the set the sensitivity cut touches and leaves in the totals).
+ * present: bit j set iff ZH_j == ZH_j after censoring.  dominant: starts at 255 with no best value; for j ascending, j is taken
+ * when bit j of `present` is set and either nothing has been taken yet or ZH_j > best (strict: a tie keeps the lower slot).
+ * share: S = the float32 sum of the ZH_j with bit j set, j ascending, from +0.0f; share = ZH_dominant / S; NaN where dominant is 255.
+ * The per-species arrays are species-major, [n_hydro][n_rays * n_gates], as model_vars is variable-major.  sz: the rows
+ * themselves.  An array left NULL is not written and costs no store.  The pointers follow p->outputs_on_device like every other
+ * array (mode 2: they count for the one-copy window rule).
+ * CPOL_ERR_ARG, nothing queued, the context usable: every pointer NULL; n_hydro different from the staged slots; any other
+ * product in the same call; cpol_run_columns; cpol_run_sweep_members with time_blend == 0 (the ensemble form).
+ * LAUNCH: a call with the struct takes the general launch sequence, as the debug reads do (the single-beam kernels keep an absent
+ * species as 0.f in registers and never form the NaN-marked rows); every per-gate array has the bits of the plain call.  ONE
+ * kernel (k_species, one lane per gate) runs behind the range scans and the cut and before the output copy.  Without the struct
+ * a call launches what it always launched. */
+typedef struct cpol_species {
+    float   *ZH, *ZV, *ZDR, *KDP, *RHOHV, *DELTA_HV, *ATT_H, *ATT_V;  /* each [n_hydro][n_rays * n_gates], NULL = not wanted */
+    uint8_t *dominant, *present;                                      /* [n_rays * n_gates] */
+    float   *share;                                                   /* [n_rays * n_gates] */
+    float   *sz;                                                      /* [n_rays * n_gates][n_hydro][12]: sz_integ itself */
+    int32_t  n_hydro, pad_;                                           /* must equal the staged slots */
+} cpol_species;
+
 /* cpol_outputs.  A call takes AT MOST ONE product behind its arrays: superob, member_stats (member_verify rides on it),
- * spectrum_moments, histogram or composite (fractions, with its objects, rides on it); any two are refused (CPOL_ERR_ARG). */
+ * spectrum_moments, histogram, composite (fractions, with its objects, rides on it) or species; any two are refused (CPOL_ERR_ARG). */
 typedef struct {
     /* all [n_rays * n_gates]; NULL = not wanted */
     float  *ZH, *ZV, *ZDR, *KDP, *DELTA_HV, *PHIDP, *RHOHV, *ATT_H, *ATT_V;
     double *RVEL;
     double *mask;
+    cpol_species *species;      /* NULL (a zero-initialised struct): off.  The radar fields per hydrometeor species, the dominant
+                                   species and its share, see cpol_species.  (In front of the members that are pinned where
+                                   they are.) */
     double *lats, *lons;        /* central sub-beam                             */
     float  *dist, *heights;
     double *visibility;         /* [n_rays*n_gates] float64, NULL = not wanted: the visible share of the antenna pattern per gate,
@@ -1054,7 +1096,7 @@ typedef struct {
                                    Needs 2 * n_sub <= 127.  When it is asked for and `mask` is not, `mask` is not written. */
     cpol_spectrum_moments *spectrum_moments;    /* NULL (a zero-initialised struct): off.  The moments of every gate's Doppler
                                    spectrum (Doppler scheme 3), see cpol_spectrum_moments */
-    cpol_member_stats *member_stats;   /* NULL (a zero-initialised struct): off.  The call's member(s) folded into the
+    cpol_member_stats *member_stats;  /* NULL (a zero-initialised struct): off.  The call's member(s) folded into the
                                    context's running ensemble statistics, see cpol_member_stats */
     cpol_superob *superob;     /* NULL (a zero-initialised struct): off.  Window averages of the fields above, see cpol_superob.
                                    Stays the LAST member */
@@ -1465,6 +1507,11 @@ CPOL_API int  cpol_enable_timing(cpol_ctx *ctx, int on);
  * host edge and output pointers; blocking; honours h.phase; needs no staged model or tables; cpol_histogram's refusals (Doppler
  * counts as on), and CPOL_ERR_ARG for a bad shape or a missing input.  Returns 0.
  * "histogram_stretch" copies one int32: the gates a workgroup of k_hist owns.
+ * "species_fields" is the same for the hydrometeor contributions: k_species alone on caller-supplied rows.  dst points to
+ * { int32_t n_rows, n_gates; const float *sz; const float *zh_final; float c_zh, c_kdp, c_2w, pad_; cpol_species sp; } -- host
+ * arrays: sz [n_rows * n_gates][sp.n_hydro][12], zh_final [n_rows * n_gates]; `sp` with host output pointers (sp.sz: the rows
+ * back from the device); blocking; needs no staged model or tables (n_hydro is the hook's own, 1 ... CPOL_MAX_HYDRO);
+ * CPOL_ERR_ARG for a bad shape, a NULL input or every output NULL.  Returns 0.
  * "composite_fields" is the same for the gridded composites: the plan, the placement, k_comp, k_comp_finish and the context's
  * running state on caller-supplied rows.  dst points to { int32_t n_rows, n_gates, n_rays, lane_form; const float *in[9];
  * const float *heights, *dist; cpol_composite c; } -- host arrays: `in` in the order of the fields, [n_rows * n_gates] float32,
